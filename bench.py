@@ -13,7 +13,12 @@ window decode + first-layer lookup kernel / conv-tower kernel with head) over on
 cross-position reuse.  N>1: ranks take disjoint site shards (weak scaling) and each step ends with one RCCL
 all_gather of the (batch, 4) fp32 log-probabilities.
 
-Extra objects on the JSON line (N=1, measured after the timed prediction region):
+A plain run sets up, warms up, times the --steps steps and prints the line: headline keys and ``config`` only.
+``--dump-outputs DIR`` writes what the timed path handed back in its last step (the (rows, 4) fp32 log-probabilities; rank 0: the
+gathered rows for N>1) as DIR/log_probs.npy, cut to a fixed seeded sample of its rows above 60 MB.  Inputs are fixed by seeds:
+two builds run with the same arguments can be compared output for output.
+
+Extra objects on the JSON line, only with ``--full`` (N=1, measured after the timed prediction region):
 ``roofline`` (dominant kernel = snv_tower_wave, the wave-private tower kernel: algorithmic FLOP per launch of the layers it evaluates / HIP-event duration of
 that kernel measured live in the timed region, vs the 157.3 TFLOP/s fp32 MFMA peak); ``cpu_baseline`` (oracle = PyTorch-CPU
 restatement of the reference on this box's host cores, os.cpu_count() threads, batch 16 / 256 / 1024, bounded samples);
@@ -22,6 +27,8 @@ restatement of the reference on this box's host cores, os.cpu_count() threads, b
 SURVEY.md section 8f-4 -- reported beside the per-window headline, never in place of it); ``train`` (configs[2]: S-config
 training step at batch 4096, >= 200 steps, un-synchronised and per-step synchronised, with its roofline) and ``indel``
 (configs[3]: UNet_Small with the shipped human insertion weights when the fixture is present, 1e5 positions, with its roofline).
+``--full`` also times the tower kernel per launch inside the timed region and, for N>1, checks the collective afterwards
+(``collective_check``); ``--no-train`` / ``--no-cpu-baseline`` drop legs of a --full run.
 """
 import argparse
 import ctypes as C
@@ -881,6 +888,24 @@ def order_line(line):
     return out
 
 
+DUMP_BYTES = 60_000_000        # the arrays of --dump-outputs together, headers included: under 64 MB however counted
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy (float32 / float64), together at most DUMP_BYTES; an array above its share is
+    cut to a fixed seeded sample of its rows (the same rows in every run of the same arguments), kept in row order."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+        if a.nbytes > share:
+            rows = share // max(a[:1].nbytes, 1)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     try:      # (a side-stream AccumulateGrad warning of the training leg is ~1 KB of stderr per run)
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
@@ -895,8 +920,13 @@ def main():
                     help="weak (default): every rank evaluates --batch sites per step and each step ends with an all_gather; strong: the "
                          "FIXED 10M-position job of the config is split into contiguous blocks (mural_amd.predict.shard_bounds), every "
                          "rank walks its block in --steps slices and ONE all_gather ends the pass (SURVEY.md section 8e)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the short train-steps/s and INDEL measurements (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-launch timing of the tower kernel (roofline), the collective check (N>1), the "
+                         "secondary legs and the CPU baseline (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's log-probabilities as DIR/log_probs.npy (fp32; a fixed sample of rows above 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-train", action="store_true", help="--full without the secondary legs (train, INDEL, variants, reuse, file to file)")
     ap.add_argument("--config5-chr1", action="store_true",
                     help="instead of the bench line: the file-to-file run on one chr1-sized chromosome (one rank, and one rank's share of 8)")
     args = ap.parse_args()
@@ -982,7 +1012,8 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
-        _lib.check(_lib.lib().mural_profile_begin())
+        if args.full:                                # HIP events around every tower-kernel launch: the roofline's kernel time
+            _lib.check(_lib.lib().mural_profile_begin())
         t0 = time.perf_counter()
         for s in range(args.warmup, total_steps):
             out = one_step(s)
@@ -996,21 +1027,25 @@ def main():
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     k_ms, k_n = C.c_double(0.0), C.c_int64(0)
-    _lib.check(_lib.lib().mural_profile_end(C.byref(k_ms), C.byref(k_n)))
+    if args.full:
+        _lib.check(_lib.lib().mural_profile_end(C.byref(k_ms), C.byref(k_n)))
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # The collective, checked: rank 0 recomputes a random sample of the gathered rows -- drawn over every rank's block -- alone
+    if args.dump_outputs and rank == 0:              # what a caller of the timed path received in its last step
+        dump_outputs(args.dump_outputs, {"log_probs": full if strong else (gathered if world > 1 else out)})
+
+    # The collective, checked (--full): rank 0 recomputes a random sample of the gathered rows -- drawn over every rank's block -- alone
     # and compares (per-site results do not depend on batch composition: the expected difference is exactly 0).
     rccl = None
     with torch.no_grad():
-        if strong:
+        if args.full and strong:
             diff, rows, owners = verify_gathered_rows(fwd, all_pos, all_strand, full, sample=8192, seed=rank)
             rccl = {"rccl_ranks": world, "rows_checked": rows, "blocks_touched": owners, "max_abs_diff": diff, "ok": diff == 0.0}
-        elif world > 1:
+        elif args.full and world > 1:
             s_last = total_steps - 1
             firsts = [((s_last * world + r) * B) % GENOME_SITES for r in range(world)]
             idx = torch.cat([(f + torch.arange(B, device=device, dtype=torch.int64)) % GENOME_SITES for f in firsts])
@@ -1029,20 +1064,6 @@ def main():
 
     if rank == 0:
         bases = GENOME_SITES if strong else args.steps * B * world
-        kernel_ms = k_ms.value / max(k_n.value, 1)
-        # the library launches the kernel once per (tower, stage-phase) pair -- the first stages per chunk of <= 131072 sites, the short
-        # stages per four chunks -- each with its own tile size: sites_per_launch is the per-launch SHARE of the sites, so that FLOP_TOWERS x sites_per_launch / avg_launch_ms
-        # = (all tower FLOP of the timed region) / (all tower-kernel time of the timed region)
-        sites_per_launch = ((bhi - blo) if strong else args.steps * B) / max(k_n.value, 1)
-        achieved = FLOP_TOWERS * sites_per_launch / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
-        # HBM bytes per launch: PMC counters need their own profiler passes, so the figure comes from the committed summary of
-        # those passes over this same command (tools/profile_bench.sh -> profiles/hbm_traffic.json), scaled to this run's launches
-        traffic, traffic_source = None, None
-        fact = profile_fact("r06_predict") or profile_fact("r05_predict")
-        if fact and fact.get("tower_hbm_bytes_per_site"):
-            traffic = fact["tower_hbm_bytes_per_site"] * sites_per_launch
-            traffic_source = "profiles/%s.json: %s" % ("r06_predict" if profile_fact("r06_predict") else "r05_predict", fact.get("source", ""))
-        pmc = (fact or {}).get("all_launches", {})
         line = {
             "metric": "predicted bases/s (SNV local=10/distal=1000, 4-class, predict)",
             "value": bases / elapsed, "unit": "bases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1055,52 +1076,68 @@ def main():
                        "collective": ("one all_gather of the (10M, 4) result at the end of the pass" if strong else
                                       ("all_gather per step" if world > 1 else "none"))},
             "collective_check": rccl,
-            "roofline": {"bound": "mfma", "kernel": _lib.lib().mural_snv_kernel_name().decode(),
-                         "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
-                         "flop_per_launch": FLOP_TOWERS * sites_per_launch, "sites_per_launch": sites_per_launch,
-                         "avg_launch_ms": kernel_ms, "launches": int(k_n.value),
-                         # from the committed PMC passes (profiles/r06_predict.json), not measured in this run:
-                         "profiled_mfma_pipe_busy": pmc.get("mfma_pipe_busy"), "profiled_held_clock_ghz": pmc.get("held_clock_ghz"),
-                         "profiled_valu_per_mfma": pmc.get("valu_insts_per_mfma_excl_mfma"),
-                         "note": "four launches per chunk of <= 131072 sites: (large | mid tower) x (first conv stage | the two short "
-                                 "stages + fc + head); sites_per_launch / flop_per_launch / traffic are per-launch averages. "
-                                 "Algorithmic FLOP of the layers this kernel evaluates (6,353,408 per site: every 32->32 "
-                                 "conv + fc of both towers); the 1,691,136 FLOP/site of the two first conv layers are table "
-                                 "lookups in snv_stage1_kernel and the 51,600 FLOP/site local MLP is snv_local_mlp; "
-                                 "end-to-end model FLOP rate = 8,096,144 x value"},
         }
-        def leg(name, fn):
-            # the secondary objects must not cost the headline its line: a failure is reported in place of the object
-            try:
-                if os.environ.get("MURAL_BENCH_EMPTY_CACHE", "1") == "1":      # every leg starts from fresh device allocations
-                    import gc
-                    gc.collect()
-                    torch.cuda.empty_cache()
-                line[name] = fn()
-            except Exception as e:      # noqa: BLE001
-                line[name] = {"error": f"{type(e).__name__}: {e}"[:500]}
-                print(f"bench.py: the '{name}' leg failed: {e!r}", file=sys.stderr, flush=True)
+        if args.full:
+            kernel_ms = k_ms.value / max(k_n.value, 1)
+            # the library launches the kernel once per (tower, stage-phase) pair -- the first stages per chunk of <= 131072 sites, the short
+            # stages per four chunks -- each with its own tile size: sites_per_launch is the per-launch SHARE of the sites, so that FLOP_TOWERS x sites_per_launch / avg_launch_ms
+            # = (all tower FLOP of the timed region) / (all tower-kernel time of the timed region)
+            sites_per_launch = ((bhi - blo) if strong else args.steps * B) / max(k_n.value, 1)
+            achieved = FLOP_TOWERS * sites_per_launch / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
+            # HBM bytes per launch: PMC counters need their own profiler passes, so the figure comes from the committed summary of
+            # those passes over this same command (tools/profile_bench.sh -> profiles/hbm_traffic.json), scaled to this run's launches
+            traffic, traffic_source = None, None
+            fact = profile_fact("r06_predict") or profile_fact("r05_predict")
+            if fact and fact.get("tower_hbm_bytes_per_site"):
+                traffic = fact["tower_hbm_bytes_per_site"] * sites_per_launch
+                traffic_source = "profiles/%s.json: %s" % ("r06_predict" if profile_fact("r06_predict") else "r05_predict", fact.get("source", ""))
+            pmc = (fact or {}).get("all_launches", {})
+            line["roofline"] = {"bound": "mfma", "kernel": _lib.lib().mural_snv_kernel_name().decode(),
+                                "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                                "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
+                                "flop_per_launch": FLOP_TOWERS * sites_per_launch, "sites_per_launch": sites_per_launch,
+                                "avg_launch_ms": kernel_ms, "launches": int(k_n.value),
+                                # from the committed PMC passes (profiles/r06_predict.json), not measured in this run:
+                                "profiled_mfma_pipe_busy": pmc.get("mfma_pipe_busy"), "profiled_held_clock_ghz": pmc.get("held_clock_ghz"),
+                                "profiled_valu_per_mfma": pmc.get("valu_insts_per_mfma_excl_mfma"),
+                                "note": "four launches per chunk of <= 131072 sites: (large | mid tower) x (first conv stage | the two short "
+                                        "stages + fc + head); sites_per_launch / flop_per_launch / traffic are per-launch averages. "
+                                        "Algorithmic FLOP of the layers this kernel evaluates (6,353,408 per site: every 32->32 "
+                                        "conv + fc of both towers); the 1,691,136 FLOP/site of the two first conv layers are table "
+                                        "lookups in snv_stage1_kernel and the 51,600 FLOP/site local MLP is snv_local_mlp; "
+                                        "end-to-end model FLOP rate = 8,096,144 x value"}
+            def leg(name, fn):
+                # the secondary objects must not cost the headline its line: a failure is reported in place of the object
+                try:
+                    if os.environ.get("MURAL_BENCH_EMPTY_CACHE", "1") == "1":      # every leg starts from fresh device allocations
+                        import gc
+                        gc.collect()
+                        torch.cuda.empty_cache()
+                    line[name] = fn()
+                except Exception as e:      # noqa: BLE001
+                    line[name] = {"error": f"{type(e).__name__}: {e}"[:500]}
+                    print(f"bench.py: the '{name}' leg failed: {e!r}", file=sys.stderr, flush=True)
 
-        if world == 1 and not args.no_train:
-            leg("variants", lambda: workload_variants(device, model, genome))
+            if world == 1 and not args.no_train:
+                leg("variants", lambda: workload_variants(device, model, genome))
 
-            def reuse_leg():
-                r = dense_reuse(device, model, genome, sites, max(2, min(args.steps, 10)))
-                r["speedup_vs_per_window"] = r["bases_per_s"] / line["value"]
-                return r
-            # the training leg runs 3 % slower once the file-to-file leg (host threads, 20 GB of cached device blocks, pinned staging) ran
-            # in the same process (603 vs 619 steps/s, same box, same build): the two step-rate legs go first.  MURAL_BENCH_LEG_ORDER
-            # reorders them for A/B runs.
-            order = os.environ.get("MURAL_BENCH_LEG_ORDER", "train,indel,reuse,config5").split(",")
-            legs = {"reuse": lambda: leg("dense_reuse", reuse_leg), "config5": lambda: leg("config5_e2e", lambda: config5_e2e(device)),
-                    "train": lambda: leg("train", lambda: train_steps_per_s(device, genome)),
-                    "indel": lambda: leg("indel", lambda: indel_positions_per_s(device, genome))}
-            for name in order:
-                legs[name]()
-        if world == 1 and not args.no_cpu_baseline:
-            leg("cpu_baseline", lambda: cpu_baseline({k: v.detach().cpu() for k, v in model.state_dict().items()}, codes))
-        print(json.dumps(order_line(line)), flush=True)
+                def reuse_leg():
+                    r = dense_reuse(device, model, genome, sites, max(2, min(args.steps, 10)))
+                    r["speedup_vs_per_window"] = r["bases_per_s"] / line["value"]
+                    return r
+                # the training leg runs 3 % slower once the file-to-file leg (host threads, 20 GB of cached device blocks, pinned staging) ran
+                # in the same process (603 vs 619 steps/s, same box, same build): the two step-rate legs go first.  MURAL_BENCH_LEG_ORDER
+                # reorders them for A/B runs.
+                order = os.environ.get("MURAL_BENCH_LEG_ORDER", "train,indel,reuse,config5").split(",")
+                legs = {"reuse": lambda: leg("dense_reuse", reuse_leg), "config5": lambda: leg("config5_e2e", lambda: config5_e2e(device)),
+                        "train": lambda: leg("train", lambda: train_steps_per_s(device, genome)),
+                        "indel": lambda: leg("indel", lambda: indel_positions_per_s(device, genome))}
+                for name in order:
+                    legs[name]()
+            if world == 1 and not args.no_cpu_baseline:
+                leg("cpu_baseline", lambda: cpu_baseline({k: v.detach().cpu() for k, v in model.state_dict().items()}, codes))
+            line = order_line(line)
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

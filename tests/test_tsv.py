@@ -217,6 +217,7 @@ def test_config1_reference_rows_through_calibrator_and_writer_are_byte_identical
         path = tmp_path / (name + ".tsv")
         assert write_predictions(res, path, **kw) == len(order)
         assert open(path).read() == str(fx[name]), name
-    pkl = "/root/reference/examples/snv/models/checkpoint_6/model.fdiri_cal.pkl"
-    if os.path.exists(pkl):      # (build container only: the shipped calibrator through the jax-free reader)
+    from oracle import ref_import
+    pkl = os.path.join(ref_import.REFERENCE_ROOT, "examples", "snv", "models", "checkpoint_6", "model.fdiri_cal.pkl")
+    if os.path.exists(pkl):      # (only where the reference tree is present: the shipped calibrator through the jax-free reader)
         assert np.array_equal(load_dirichlet_weights(pkl), w)

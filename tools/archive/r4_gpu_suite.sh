@@ -1,11 +1,14 @@
-cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/r4d
-(timeout 2400 python -m pytest tests/ -q -m gpu -x 2>&1 | tail -15) > gpurun_out/r4d/tests.txt
-cat gpurun_out/r4d/tests.txt
-(timeout 1500 python bench.py > gpurun_out/r4d/bench.json 2> gpurun_out/r4d/bench.err); tail -3 gpurun_out/r4d/bench.err
+# GPU tests + the full bench line (bench.py --full) and its main figures; results go to the directory given as $1 (default: a new
+# temporary directory)
+cd "$(dirname "$0")/../.."
+export OUT=${1:-$(mktemp -d)}
+mkdir -p $OUT
+(timeout 2400 python -m pytest tests/ -q -m gpu -x 2>&1 | tail -15) > $OUT/tests.txt
+cat $OUT/tests.txt
+(timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err); tail -3 $OUT/bench.err
 python - <<'PY'
-import json
-l = json.loads(open('gpurun_out/r4d/bench.json').read().strip().splitlines()[-1])
+import json, os
+l = json.loads(open(os.path.join(os.environ['OUT'], 'bench.json')).read().strip().splitlines()[-1])
 print('value', l['value'], 'roofline', l['roofline']['frac'])
 print('train', {k: l['train'].get(k) for k in ('steps_per_s', 'ms_per_step', 'launches_per_step')})
 print('indel', l['indel'].get('positions_per_s'), l['indel'].get('roofline', {}).get('frac'))
