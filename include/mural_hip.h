@@ -496,6 +496,60 @@ int mural_eval_dirichlet_fit_terms(const void* prob, int32_t prob_f64, const int
                                    const double* weights, int32_t need_hessian, double* out, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The prediction table read back (mural_amd/tables.py: evaluate, calc_scaling_factor, scale).  Replaces the per-line parsing
+ * loops of MuRaL/scripts/calc_kmer_corr.py:200-270 and calc_regional_corr.py:168-212 and the whole-table pd.read_csv of
+ * MuRaL/scripts/scaling.py:22, :67.  A reader streams the table (plain or gzip, the header line skipped: the caller validates
+ * it) in chunks cut after a newline (chunk_bytes is the target size; a chunk holds one row at least) and parses each chunk on
+ * the device.  mural_table_next fills *chunk with the device columns of the next chunk (owned by the reader, valid until the
+ * next call; n_rows = 0 at the end) and returns after the parse has completed (the next chunk is read meanwhile).  A malformed
+ * row is MURAL_E_INVALID with its line number.  Chromosome ids are global over the table (order of first appearance),
+ * mural_table_chrom_name names them.  Everything on `stream`.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct MuralTableReader MuralTableReader;
+typedef struct {
+  int64_t n_rows, row0;      /* rows of this chunk; rows of the table before it                                    */
+  int64_t* start;            /* dev [n_rows] */
+  int64_t* end;              /* dev [n_rows] */
+  int32_t* mut_type;         /* dev [n_rows] */
+  float* label;              /* dev [n_rows] mut_type as float (the formatter's label column)                      */
+  uint8_t* strand;           /* dev [n_rows] 0 '+', 1 '-' */
+  double* prob;              /* dev [n_rows][n_class] */
+  int32_t* chrom_id;         /* dev [n_rows] */
+  int32_t n_runs, n_chroms;  /* chromosome runs of this chunk; chromosomes named so far                            */
+  const int64_t* run_row;    /* host [n_runs] first row of each run */
+  const int32_t* run_chrom;  /* host [n_runs] its chromosome id */
+  int64_t text_bytes;        /* bytes of text in the chunk */
+} MuralTableChunk;
+int mural_table_open(const char* path, int32_t n_class, int64_t chunk_bytes, MuralTableReader** reader);
+int mural_table_next(MuralTableReader* reader, MuralTableChunk* chunk, void* stream);
+const char* mural_table_chrom_name(const MuralTableReader* reader, int32_t id);
+/* seconds reading / inflating (worker thread), seconds waiting for it, seconds of the device parse, text bytes so far */
+int mural_table_stats(const MuralTableReader* reader, double* out4);
+void mural_table_close(MuralTableReader* reader);
+/* scaling.py:24-27 on the rows: prob[:, 1:] *= factor; prob[:, 0] = 1 - sum(prob[:, 1:]) (float64, left to right)          */
+int mural_table_scale_rows(double* prob, int64_t n, int32_t n_class, double factor, void* stream);
+/* scaling.py:67-90 (calc_mu_scaling_factor): per-block partials [mural_table_prob_sum_blocks()] of sum_rows w * sum_{c>=1}
+ * prob and of sum_rows w, in an order fixed by n.  w = 1 without regions (reg_off NULL); otherwise the number of regions of
+ * the row's chromosome that overlap [start, end) (pybedtools intersect without -u): reg_b0 / reg_b1 hold each chromosome's
+ * region starts / ends, each sorted, in [reg_off[c], reg_off[c+1])                                                          */
+int32_t mural_table_prob_sum_blocks(void);
+int mural_table_prob_sum(const double* prob, const int32_t* chrom_id, const int64_t* start, const int64_t* end, int64_t n,
+                         int32_t n_class, const int64_t* reg_off, const int64_t* reg_b0, const int64_t* reg_b1,
+                         int32_t n_reg_chrom, double* part_sum, int64_t* part_cnt, void* stream);
+/* calc_kmer_corr.py:246-262 with get_expanded_region (MuRaL/data/preprocessing.py:524-567): key = base-4 k-mer of
+ * chrom[start - k/2 (+1 indel) : end + k/2] (Python slice), reverse-complemented on '-'; -1 if it is not k bases of A/C/G/T.
+ * mode 0: the row's strand, 1 '+', 2 '-', 3 both (key_a forward, key_b reverse complement).  All rows on genome g.          */
+int mural_table_kmer_keys(const MuralGenome* g, const int64_t* start, const int64_t* end, const uint8_t* strand, int64_t n,
+                          int32_t k, int32_t indel, int32_t mode, int32_t* key_a, int32_t* key_b, void* stream);
+/* first[key] = min(first[key], 2 * (row0 + i) + sub) over the rows with a key in [0, n_groups): the dict insertion order of
+ * the reference's per-key tables                                                                                          */
+int mural_table_first_row(const int32_t* keys, int64_t n, int64_t row0, int32_t sub, int32_t n_groups, uint64_t* first,
+                          void* stream);
+/* mn[c] = min(mn[c], start), mx[c] = max(mx[c], start) over the rows of chromosome c (the windows a chunk touches)        */
+int mural_table_start_range(const int32_t* chrom_id, const int64_t* start, int64_t n, int32_t n_chrom, int64_t* mn,
+                            int64_t* mx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

@@ -85,6 +85,13 @@ class MuralSnvParams(C.Structure):
     _fields_ = [("local", MuralLocal), ("mid", MuralTower), ("large", MuralTower)]
 
 
+class MuralTableChunk(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("row0", C.c_int64), ("start", C.c_void_p), ("end", C.c_void_p), ("mut_type", C.c_void_p),
+                ("label", C.c_void_p), ("strand", C.c_void_p), ("prob", C.c_void_p), ("chrom_id", C.c_void_p), ("n_runs", C.c_int32),
+                ("n_chroms", C.c_int32), ("run_row", C.POINTER(C.c_int64)), ("run_chrom", C.POINTER(C.c_int32)),
+                ("text_bytes", C.c_int64)]
+
+
 VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
 
 # every symbol include/mural_hip.h declares: name -> (restype, argtypes)
@@ -199,6 +206,17 @@ PROTOTYPES = {
                                             C.c_float, VP, VP, C.c_size_t, VP]),
     "mural_indel_train_backward": (C.c_int, [C.POINTER(MuralIndelShape), C.POINTER(MuralIndelParams), C.POINTER(MuralIndelParams), VP, VP,
                                              I64, C.c_float, C.c_uint64, VP, VP, C.c_size_t, VP]),
+    "mural_table_open": (C.c_int, [C.c_char_p, I32, I64, C.POINTER(C.c_void_p)]),
+    "mural_table_next": (C.c_int, [VP, C.POINTER(MuralTableChunk), VP]),
+    "mural_table_chrom_name": (C.c_char_p, [VP, I32]),
+    "mural_table_stats": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "mural_table_close": (None, [VP]),
+    "mural_table_scale_rows": (C.c_int, [VP, I64, I32, C.c_double, VP]),
+    "mural_table_prob_sum_blocks": (I32, []),
+    "mural_table_prob_sum": (C.c_int, [VP, VP, VP, VP, I64, I32, VP, VP, VP, I32, VP, VP, VP]),
+    "mural_table_kmer_keys": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, I64, I32, I32, I32, VP, VP, VP]),
+    "mural_table_first_row": (C.c_int, [VP, I64, I64, I32, I32, VP, VP]),
+    "mural_table_start_range": (C.c_int, [VP, VP, I64, I32, VP, VP, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -1,0 +1,538 @@
+"""The prediction table read back on the device: ``evaluate`` (k-mer and regional correlations), ``calc_scaling_factor`` and
+``scale`` on the files ``predict`` writes (columns ``chrom start end strand mut_type prob0 .. prob{n-1}``, plain or gzip).
+
+The entry points carry the names and ``args`` contracts the reference's CLI dispatches to (MuRaL/mural_snv.py:108-124,
+MuRaL/mural_indel.py:109-135): switching the imports there is the whole integration.  The reference parses the
+table row by row in Python (MuRaL/scripts/calc_kmer_corr.py, calc_regional_corr.py) or loads it whole with pandas
+(MuRaL/scripts/scaling.py); here a streaming reader (csrc/tables.hip) parses it chunk by chunk on the device and the per-row work is
+device kernels, the existing '%.4g' row formatter (csrc/tsv.hip) and the group tables of csrc/analytics.hip included.
+
+``chunk_bytes`` (keyword of every function) is the target size of one chunk of text.
+
+Known deviation: pandas re-types a chromosome name that looks like a number when ``scale`` reads the table (``01`` is written back
+as ``1``); here every name is kept verbatim.
+"""
+import concurrent.futures
+import ctypes as C
+import gzip
+import os
+import sys
+import zlib
+
+import numpy as np
+import torch
+
+from . import _lib
+
+DEFAULT_CHUNK_BYTES = 64 << 20
+MAX_KMER = 10
+_NAME_STRIDE = 256
+_GZ_THREADS = 16
+_GZ_BLOCK = 4 << 20
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# header, file names, arguments (host logic)
+# ------------------------------------------------------------------------------------------------------------------
+def _is_gzip(path):
+    with open(path, "rb") as fh:
+        return fh.read(2) == b"\x1f\x8b"
+
+
+def read_header(path):
+    """The first line of a prediction table (plain or gzip), without its line end."""
+    opener = gzip.open if _is_gzip(path) else open
+    with opener(path, "rt") as fh:
+        return fh.readline().rstrip("\r\n")
+
+
+def check_header(header, n_class):
+    """The header check of calc_kmer_corr.py:208-218 / calc_regional_corr.py:178-188: ValueError with the reference's message."""
+    if not header.startswith("chrom"):
+        raise ValueError(f"Invalid file header: {header.strip()}, header should be continue with 'chrom'")
+    fields = header.strip().split("\t")
+    if len(fields) != n_class + 5:
+        raise ValueError(f"Column count mismatch. Expected {n_class + 5} columns, got {len(fields)} in line: {fields}")
+    return fields
+
+
+def kmer_output_names(out_prefix, kmer_length):
+    return f"{out_prefix}.{kmer_length}-mer.mut_rates.tsv", f"{out_prefix}.{kmer_length}-mer.corr.txt"
+
+
+def regional_output_names(out_prefix, window_size):
+    window = f"{int(int(window_size) / 1000)}Kb"
+    return f"{out_prefix}.{window}.mut_rates.tsv", f"{out_prefix}.{window}.corr.txt", window
+
+
+def scaled_output_name(pred_file):
+    return pred_file + ".scaled.tsv.gz"
+
+
+def check_kmer_length(k):
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"--kmer_length must be positive (got {k})")
+    if k > MAX_KMER:
+        raise ValueError(f"--kmer_length {k} is larger than {MAX_KMER}: the k-mer table has 4^k groups")
+    return k
+
+
+_STRAND_MODES = {"+": 1, "pos": 1, "-": 2, "neg": 2, "both": 3}
+
+
+def strand_mode(model_type, strand=None):
+    """0: each row's own strand (SNV); INDEL: --strand as given (pos / neg / both, or the '+' / '-' / 'both' the CLI maps it to)."""
+    if model_type == "snv":
+        return 0
+    if model_type != "indel":
+        raise ValueError(f"model_type {model_type} not supported!")
+    if strand not in _STRAND_MODES:
+        raise ValueError(f"Invalid strand: {strand}")
+    return _STRAND_MODES[strand]
+
+
+def kmer_name(key, k):
+    return "".join("ACGT"[(key >> (2 * (k - 1 - j))) & 3] for j in range(k))
+
+
+def pearson(x, y):
+    """(r, p) of scipy.stats.pearsonr (host work on the small table); p is NaN when SciPy is not installed."""
+    try:
+        from scipy.stats import pearsonr
+    except ImportError:
+        from .evaluation import _pearson
+        return _pearson(x, y), float("nan")
+    res = pearsonr(x, y)
+    return float(res[0]), float(res[1])
+
+
+def _float_text(v):
+    return repr(float(v))
+
+
+def _rates_text(header, rows):
+    return "\t".join(header) + "\n" + "".join("\t".join(r) + "\n" for r in rows)
+
+
+def _corr_text(label, corrs):
+    return "".join(f"{label}\t{c}\t{r:.5f}\t{p:.10e}\n" for c, (r, p) in corrs)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the streaming reader
+# ------------------------------------------------------------------------------------------------------------------
+class TableReader:
+    """Chunks of a prediction table parsed on the current HIP device (``for chunk in reader``: a ``MuralTableChunk`` whose device
+    columns are valid until the next step)."""
+
+    def __init__(self, path, n_class, chunk_bytes=DEFAULT_CHUNK_BYTES):
+        self._h = C.c_void_p()
+        if not torch.cuda.is_available():
+            raise RuntimeError("mural_amd.tables needs a HIP device; there is no CPU path")
+        path = os.fspath(path)
+        self.header = check_header(read_header(path), n_class)
+        self.n_class = int(n_class)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        _lib.check(_lib.lib().mural_table_open(path.encode(), self.n_class, int(chunk_bytes), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _lib.lib().mural_table_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def __iter__(self):
+        lib = _lib.lib()
+        while True:
+            c = _lib.MuralTableChunk()
+            _lib.check(lib.mural_table_next(self._h, C.byref(c), _lib.current_stream_ptr(self.device)))
+            if c.n_rows == 0:
+                return
+            yield c
+
+    def chrom_name(self, cid):
+        return _lib.lib().mural_table_chrom_name(self._h, int(cid)).decode()
+
+    def chrom_names(self, n):
+        return [self.chrom_name(i) for i in range(n)]
+
+    def stats(self):
+        out = (C.c_double * 4)()
+        _lib.check(_lib.lib().mural_table_stats(self._h, out))
+        return dict(read_s=out[0], wait_read_s=out[1], parse_s=out[2], text_bytes=int(out[3]))
+
+
+def _name_table(names):
+    buf = C.create_string_buffer(max(len(names), 1) * _NAME_STRIDE)
+    for i, nm in enumerate(names):
+        raw = nm.encode()
+        if len(raw) >= _NAME_STRIDE:
+            raise ValueError(f"chromosome name longer than {_NAME_STRIDE - 1} bytes: {nm!r}")
+        buf[i * _NAME_STRIDE:i * _NAME_STRIDE + len(raw)] = raw
+    return buf
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# scale
+# ------------------------------------------------------------------------------------------------------------------
+class _Out:
+    """Text sink: a plain file, or gzip written as independent members compressed on up to 16 host threads."""
+
+    def __init__(self, path):
+        self.fh = open(path, "wb")
+        self.gz = str(path).endswith(".gz")
+        self.pool = concurrent.futures.ThreadPoolExecutor(_GZ_THREADS) if self.gz else None
+
+    @staticmethod
+    def _member(data):
+        z = zlib.compressobj(6, zlib.DEFLATED, 31)
+        return z.compress(data) + z.flush()
+
+    def write(self, data):
+        if not self.gz:
+            self.fh.write(data)
+            return
+        mv = memoryview(data)
+        parts = [mv[i:i + _GZ_BLOCK] for i in range(0, len(mv), _GZ_BLOCK)]
+        for blob in self.pool.map(self._member, parts):
+            self.fh.write(blob)
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown()
+        self.fh.close()
+
+
+def _scale_file(pred_file, factor, n_class, out_file, chunk_bytes, timing=None):
+    lib = _lib.lib()
+    with TableReader(pred_file, n_class, chunk_bytes) as rd:
+        out = _Out(out_file)
+        try:
+            out.write(("\t".join(rd.header) + "\n").encode())
+            dev = rd.device
+            text = ws = host = None
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            for c in rd:
+                n = int(c.n_rows)
+                _lib.check(lib.mural_table_scale_rows(c.prob, n, n_class, float(factor), _lib.current_stream_ptr(dev)))
+                names = _name_table(rd.chrom_names(c.n_chroms))
+                t = _lib.MuralTsvRows()
+                t.chrom_names, t.n_chroms, t.name_stride = C.cast(names, C.c_char_p), max(c.n_chroms, 1), _NAME_STRIDE
+                t.chrom_id, t.start, t.end, t.strand, t.label, t.prob = c.chrom_id, c.start, c.end, c.strand, c.label, c.prob
+                t.prob_f64, t.n_class, t.prob_stride, t.perm, t.n, t.layout = 1, n_class, n_class, None, n, 0
+                bound = int(lib.mural_tsv_row_bound(C.byref(t)))
+                if bound < 0:
+                    raise ValueError("prediction table: bad row layout")
+                need = n * bound
+                if text is None or text.numel() < need:
+                    text = torch.empty(need, dtype=torch.uint8, device=dev)
+                    host = torch.empty(need, dtype=torch.uint8).pin_memory()
+                ws_need = int(lib.mural_tsv_format_workspace_bytes(n)) + max(c.n_chroms, 1) * _NAME_STRIDE + 16
+                if ws is None or ws.numel() < ws_need:
+                    ws = torch.empty(ws_need, dtype=torch.uint8, device=dev)
+                _lib.check(lib.mural_tsv_format_device(C.byref(t), text.data_ptr(), text.numel(), count.data_ptr(), ws.data_ptr(),
+                                                      ws.numel(), _lib.current_stream_ptr(dev)))
+                nb = int(count.item())
+                host[:nb].copy_(text[:nb])
+                out.write(host[:nb].numpy().tobytes())
+            if timing is not None:
+                timing.update(rd.stats())
+        finally:
+            out.close()
+
+
+def apply_scaling_file(pred_file, scale_factor, n_class, out_file, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """scaling.py:10-28 (apply_scaling) on a table file: prob1.. *= scale_factor, prob0 = 1 - their sum, rows in file order, floats
+    '%.4g'; an out_file ending in .gz is written as gzip.  (The in-memory rule is ``mural_amd.calibration.apply_scaling``.)"""
+    _scale_file(os.fspath(pred_file), float(scale_factor), int(n_class), os.fspath(out_file), chunk_bytes)
+
+
+def scaling_files(pred_files, scale_factors, n_class, out_files, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """scaling.py:30-40: apply_scaling_file over parallel lists."""
+    if not isinstance(pred_files, list) or not isinstance(scale_factors, list) or not isinstance(out_files, list):
+        print("ERROR: pred_files, scale_factors, and out_files must be lists!", file=sys.stderr)
+        sys.exit()
+    for pred_file, factor, out_file in zip(pred_files, scale_factors, out_files):
+        apply_scaling_file(pred_file, factor, n_class, out_file, chunk_bytes=chunk_bytes)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# calc_scaling_factor
+# ------------------------------------------------------------------------------------------------------------------
+def read_regions(path):
+    """{chrom: (starts, ends)} of a BED file (the first three columns; plain or gzip; track / browser / '#' lines skipped).  The
+    region list is small: host work."""
+    opener = gzip.open if _is_gzip(path) else open
+    out = {}
+    with opener(path, "rt") as fh:
+        for ln, line in enumerate(fh, 1):
+            if not line.strip() or line.startswith(("#", "track", "browser")):
+                continue
+            f = line.rstrip("\r\n").split("\t")
+            if len(f) < 3:
+                raise ValueError(f"{path}:{ln}: a BED row needs chrom, start and end")
+            a, b = out.setdefault(f[0], ([], []))
+            a.append(int(f[1]))
+            b.append(int(f[2]))
+    return out
+
+
+def _regions_on_device(regions, names, dev):
+    """Benchmark regions per table chromosome: (offsets [n+1], each chromosome's sorted starts, its sorted ends) on `dev`."""
+    b0, b1, off = [], [], [0]
+    for nm in names:
+        a, b = regions.get(nm, ([], []))
+        b0.append(np.sort(np.asarray(a, np.int64)))
+        b1.append(np.sort(np.asarray(b, np.int64)))
+        off.append(off[-1] + len(a))
+    cat = lambda xs: torch.from_numpy(np.concatenate(xs + [np.zeros(1, np.int64)])).to(dev)      # noqa: E731
+    return torch.tensor(off, dtype=torch.int64, device=dev), cat(b0), cat(b1)
+
+
+def prob_sum_file(pred_file, n_class, benchmark_regions=None, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(sum over rows of prob1 + .. + prob{n-1}, n_sites) of a table; with benchmark regions each row counts once per overlapping
+    region (bedtools intersect without -u).  float64, fixed reduction order."""
+    lib = _lib.lib()
+    nb = int(lib.mural_table_prob_sum_blocks())
+    total, n_sites = 0.0, 0
+    with TableReader(pred_file, n_class, chunk_bytes) as rd:
+        dev = rd.device
+        part_s = torch.zeros(nb, dtype=torch.float64, device=dev)
+        part_c = torch.zeros(nb, dtype=torch.int64, device=dev)
+        chunks = []
+        bed = read_regions(benchmark_regions) if benchmark_regions else None
+        regions, reg_names = None, 0
+        for c in rd:
+            if bed is not None and (regions is None or reg_names < c.n_chroms):
+                reg_names = c.n_chroms
+                regions = _regions_on_device(bed, rd.chrom_names(reg_names), dev)
+            ro, r0, r1 = (regions[0].data_ptr(), regions[1].data_ptr(), regions[2].data_ptr()) if regions else (None, None, None)
+            _lib.check(lib.mural_table_prob_sum(c.prob, c.chrom_id, c.start, c.end, c.n_rows, n_class, ro, r0, r1, reg_names,
+                                               part_s.data_ptr(), part_c.data_ptr(), _lib.current_stream_ptr(dev)))
+            chunks.append((part_s.cpu().numpy().copy(), part_c.cpu().numpy().copy()))
+        for s, k in chunks:
+            for v in s:
+                total += float(v)
+            n_sites += int(k.sum())
+    return total, n_sites
+
+
+def calc_mu_scaling_factor(args, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """scaling.py:45-107: per prediction file the factor genomewide_mu * n_sites * m_proportion / g_proportion / prob_sum (g = 1
+    for INDEL); prints the reference's lines, writes <pred>.scaled.tsv.gz with --do_scaling, returns the factors."""
+    pred_files = list(args.pred_files)
+    g_props = list(args.g_proportions) if model_type == "snv" else [1] * len(pred_files)
+    m_props = list(args.m_proportions)
+    if len(m_props) != len(pred_files):
+        print("ERROR: length of proportions does not equal to length of pred_files!", file=sys.stderr)
+        sys.exit()
+    factors = []
+    for i, pred_file in enumerate(pred_files):
+        prob_sum, n_sites = prob_sum_file(pred_file, args.n_class, getattr(args, "benchmark_regions", None) or None, chunk_bytes)
+        factor = (args.genomewide_mu * n_sites * m_props[i] / g_props[i]) / prob_sum
+        print("\nType " + str(i + 1) + ":\n" + "pred_file:", pred_file)
+        print("genomewide_mu:", args.genomewide_mu)
+        print("n_sites:", n_sites)
+        print("g_proportion:", g_props[i])
+        print("m_proportion:", m_props[i])
+        print("prob_sum: %.3e" % prob_sum)
+        print("scaling factor: %.3e" % factor)
+        if args.do_scaling:
+            apply_scaling_file(pred_file, factor, args.n_class, scaled_output_name(pred_file), chunk_bytes=chunk_bytes)
+        factors.append(factor)
+    return factors
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# evaluate: k-mer
+# ------------------------------------------------------------------------------------------------------------------
+def _group(keys, c, n_class, n_groups, table, status, dev):
+    _lib.check(_lib.lib().mural_eval_group_obs_pred(keys.data_ptr(), c.mut_type, c.prob, 1, c.n_rows, n_class, n_groups,
+                                                   table.data_ptr(), status.data_ptr(), _lib.current_stream_ptr(dev)))
+
+
+def _check_status(status, what):
+    s = int(status.item())
+    if s & 2:
+        raise ValueError(f"{what}: a mut_type outside 0 .. n_class - 1")
+    if s & 1:
+        raise ValueError(f"{what}: a negative start")
+
+
+def kmer_table(pred_file, ref_genome, kmer_length, n_class, model_type, strand=None, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(k-mer names, table [groups][1 + 2 n_class] of rows / per-class counts / per-class prob sums) in the reference's dict order."""
+    from .data.ingest import read_fasta, scan_fasta
+    k = check_kmer_length(kmer_length)
+    mode = strand_mode(model_type, strand)
+    lib = _lib.lib()
+    n_groups = 4 ** k
+    fasta_names = {r.name for r in scan_fasta(ref_genome)}
+    genomes = {}
+    with TableReader(pred_file, n_class, chunk_bytes) as rd:
+        dev = rd.device
+        stream = lambda: _lib.current_stream_ptr(dev)      # noqa: E731
+        table = torch.zeros((n_groups, 1 + 2 * n_class), dtype=torch.float64, device=dev)
+        first = torch.full((n_groups,), -1, dtype=torch.int64, device=dev)      # (all ones = the largest unsigned value)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        for c in rd:
+            n = int(c.n_rows)
+            key_a = torch.empty(n, dtype=torch.int32, device=dev)
+            key_b = torch.empty(n, dtype=torch.int32, device=dev) if mode == 3 else None
+            rows = list(c.run_row[:c.n_runs]) + [n]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                if name not in genomes:
+                    if name not in fasta_names:
+                        raise ValueError(f"Chromosome {name} not found in {ref_genome} (prediction table line {c.row0 + rows[r] + 2})")
+                    genomes[name] = read_fasta(ref_genome, dev, names={name})[name]
+                g = genomes[name].as_struct()
+                a, b = rows[r], rows[r + 1]
+                _lib.check(lib.mural_table_kmer_keys(C.byref(g), c.start + 8 * a, c.end + 8 * a, c.strand + a, b - a, k,
+                                                    int(model_type == "indel"), mode, key_a[a:].data_ptr(),
+                                                    key_b[a:].data_ptr() if key_b is not None else None, stream()))
+            for sub, keys in enumerate((key_a, key_b)):
+                if keys is None:
+                    continue
+                _group(keys, c, n_class, n_groups, table, status, dev)
+                _lib.check(lib.mural_table_first_row(keys.data_ptr(), n, c.row0, sub, n_groups, first.data_ptr(), stream()))
+        _check_status(status, pred_file)
+        table, first = table.cpu().numpy(), first.cpu().numpy().view(np.uint64)
+    live = np.nonzero(table[:, 0] > 0)[0]
+    order = live[np.argsort(first[live], kind="stable")]
+    return [kmer_name(int(g), k) for g in order], table[order]
+
+
+def _rates(table, n_class):
+    tot = table[:, 1:1 + n_class].sum(axis=1)
+    obs = table[:, 2:1 + n_class] / tot[:, None]
+    pred = table[:, 2 + n_class:] / tot[:, None]
+    return obs, pred, table[:, 2:1 + n_class].astype(np.int64), tot.astype(np.int64)
+
+
+def run_kmer_corr_calc(args, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """calc_kmer_corr.py:195-270: per k-mer observed / predicted rates and their Pearson r per class; writes
+    {out_prefix}.{k}-mer.mut_rates.tsv and .corr.txt."""
+    assert args.ref_genome is not None, "--ref_genome is required for k-mer correlation calculation"
+    n_class = args.n_class
+    names, table = kmer_table(os.fspath(args.pred_file), os.fspath(args.ref_genome), args.kmer_length, n_class, model_type,
+                              getattr(args, "strand", None), chunk_bytes)
+    obs, pred, cnt, tot = _rates(table, n_class)
+    cls = range(1, n_class)
+    header = (["type"] + [f"avg_obs_rate{i}" for i in cls] + [f"avg_pred_rate{i}" for i in cls] + [f"number_of_mut{i}" for i in cls]
+              + ["number_of_all"])
+    rows = [[nm] + [_float_text(v) for v in obs[j]] + [_float_text(v) for v in pred[j]] + [str(int(v)) for v in cnt[j]] + [str(int(tot[j]))]
+            for j, nm in enumerate(names)]
+    rates_path, corr_path = kmer_output_names(args.out_prefix, args.kmer_length)
+    corrs = [(c, pearson(obs[:, c - 1], pred[:, c - 1])) for c in cls]
+    with open(rates_path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    with open(corr_path, "w") as fh:
+        fh.write(_corr_text(f"{args.kmer_length}-mer", corrs))
+    return corrs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# evaluate: regional
+# ------------------------------------------------------------------------------------------------------------------
+_MAX_CHUNK_WINDOWS = 1 << 24
+
+
+def regional_table(pred_file, window_size, n_class, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """([(chrom, window_end)], table [windows][1 + 2 n_class]) in the reference's dict order (first row of each window)."""
+    lib = _lib.lib()
+    W = int(window_size)
+    if W <= 0:
+        raise ValueError(f"--window_size must be positive (got {W})")
+    stride = 1 + 2 * n_class
+    index, first_row, acc = {}, [], []
+    with TableReader(pred_file, n_class, chunk_bytes) as rd:
+        dev = rd.device
+        stream = lambda: _lib.current_stream_ptr(dev)      # noqa: E731
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        keys = None
+        for c in rd:
+            n, nch = int(c.n_rows), int(c.n_chroms)
+            mn = torch.full((nch,), 2 ** 63 - 1, dtype=torch.int64, device=dev)
+            mx = torch.full((nch,), -2 ** 63, dtype=torch.int64, device=dev)
+            _lib.check(lib.mural_table_start_range(c.chrom_id, c.start, n, nch, mn.data_ptr(), mx.data_ptr(), stream()))
+            mn_h, mx_h = mn.cpu().numpy(), mx.cpu().numpy()
+            present = np.nonzero(mx_h >= mn_h)[0]
+            if (mn_h[present] < 0).any():
+                raise ValueError(f"{pred_file}: a negative start near line {c.row0 + 2}")
+            w0 = np.zeros(nch, np.int64)
+            base = np.zeros(nch, np.int64)
+            n_groups = 0
+            for cid in present:
+                w0[cid] = mn_h[cid] // W
+                base[cid] = n_groups - w0[cid]
+                n_groups += int(mx_h[cid] // W - w0[cid] + 1)
+            if n_groups * stride >= 2 ** 31 or n_groups > _MAX_CHUNK_WINDOWS:
+                raise ValueError(f"{pred_file}: the rows of one chunk span {n_groups} windows of {W} bp; use a smaller chunk_bytes")
+            if keys is None or keys.numel() < n:
+                keys = torch.empty(n, dtype=torch.int32, device=dev)
+            table = torch.zeros((n_groups, stride), dtype=torch.float64, device=dev)
+            first = torch.full((n_groups,), -1, dtype=torch.int64, device=dev)
+            base_d = torch.from_numpy(base).to(dev)
+            _lib.check(lib.mural_eval_window_keys(c.chrom_id, c.start, n, W, base_d.data_ptr(), nch, keys.data_ptr(), status.data_ptr(),
+                                                 stream()))
+            _group(keys, c, n_class, n_groups, table, status, dev)
+            _lib.check(lib.mural_table_first_row(keys.data_ptr(), n, c.row0, 0, n_groups, first.data_ptr(), stream()))
+            table, first = table.cpu().numpy(), first.cpu().numpy().view(np.uint64)
+            for cid in present:
+                g0 = int(base[cid] + w0[cid])
+                g1 = int(base[cid] + mx_h[cid] // W) + 1
+                for g in np.nonzero(table[g0:g1, 0] > 0)[0] + g0:
+                    key = (rd.chrom_name(int(cid)), int((g - base[cid]) * W + W))
+                    j = index.get(key)
+                    if j is None:
+                        index[key] = len(acc)
+                        acc.append(table[g].copy())
+                        first_row.append(int(first[g]))
+                    else:
+                        acc[j] += table[g]
+        _check_status(status, pred_file)
+    keys_out = list(index)
+    order = np.argsort(np.asarray(first_row, np.uint64), kind="stable")
+    tab = np.asarray(acc, np.float64).reshape(-1, stride)
+    return [keys_out[j] for j in order], tab[order]
+
+
+def run_regional_corr_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """calc_regional_corr.py:164-212: per window observed / predicted rates (float32), used_or_deprecated by ratio_cutoff *
+    median(number_of_all), Pearson r over the used windows; writes {out_prefix}.{W/1000}Kb.mut_rates.tsv and .corr.txt."""
+    n_class = args.n_class
+    W = int(args.window_size)
+    keys, table = regional_table(os.fspath(args.pred_file), W, n_class, chunk_bytes)
+    obs, pred, cnt, tot = _rates(table, n_class)
+    obs32, pred32 = obs.astype(np.float32), pred.astype(np.float32)
+    cutoff = float(args.ratio_cutoff) * np.median(tot.astype(np.uint64))
+    used = tot >= cutoff
+    cls = range(1, n_class)
+    header = (["chrom", "window_end"] + [f"avg_obs_rate{i}" for i in cls] + [f"avg_pred_rate{i}" for i in cls]
+              + [f"number_of_mut{i}" for i in cls] + ["number_of_all", "used_or_deprecated"])
+    rows = [[ch, str(we)] + [str(v) for v in obs32[j]] + [str(v) for v in pred32[j]] + [str(int(v)) for v in cnt[j]]
+            + [str(int(tot[j])), "used" if used[j] else "deprecated"] for j, (ch, we) in enumerate(keys)]
+    rates_path, corr_path, window = regional_output_names(args.out_prefix, W)
+    corrs = [(c, pearson(obs32[used, c - 1], pred32[used, c - 1])) for c in cls]
+    with open(rates_path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    with open(corr_path, "w") as fh:
+        fh.write(_corr_text(window, corrs))
+    return corrs
+
+
+# the reference's module-level name of the file-to-file scaling (scaling.py:10); mural_amd.calibration.apply_scaling is the
+# in-memory rule and stays as it is
+apply_scaling = apply_scaling_file
+
+__all__ = ["TableReader", "apply_scaling_file", "scaling_files", "calc_mu_scaling_factor", "run_kmer_corr_calc", "run_regional_corr_calc",
+           "prob_sum_file", "read_regions", "kmer_table", "regional_table", "check_header", "read_header", "DEFAULT_CHUNK_BYTES", "MAX_KMER"]
