@@ -561,7 +561,7 @@ int launch_conv1d_direct(const Conv1dArgs& a, hipStream_t stream) {
                            : reinterpret_cast<const void*>(conv1d_direct_kernel<MB_, CP_, U_, false, NB_>);         \
       cap = resident_workgroups(fn, 256);                                                                           \
     }                                                                                                               \
-    if (dev_env("MURAL_DIRECT_GRID_CAP") == nullptr || atoi(dev_env("MURAL_DIRECT_GRID_CAP")) != 0) wgs = std::min(wgs, cap); \
+    wgs = std::min(wgs, cap);                                                                                       \
     if (res) hipLaunchKernelGGL((conv1d_direct_kernel<MB_, CP_, U_, true, NB_>), dim3(wgs), dim3(256), 0, stream, g, a.wt, a.bias);  \
     else hipLaunchKernelGGL((conv1d_direct_kernel<MB_, CP_, U_, false, NB_>), dim3(wgs), dim3(256), 0, stream, g, a.wt, a.bias);     \
   } while (0)

@@ -136,7 +136,7 @@ struct ClFwdArgs {
   int pre_relu, post_relu;
   double* stat_out;       // nullptr: no sums
   int stat_relu;
-  int dbg;                // timing experiments (MURAL_DEBUG_CL): 1 no staging, 2 no MFMA phase, 4 no stream-out, 8 no residual loads
+  int dbg;                // timing experiments (0 in every launch; its switch is retired): 1 no staging, 2 no MFMA phase, 4 no stream-out, 8 no residual loads
 };
 
 __global__ __launch_bounds__(SNV_THREADS, 2) void conv32cl_fwd_kernel(const ClFwdArgs a) {
@@ -241,7 +241,7 @@ struct ClBwdArgs {
   float* part;            // [grid][32*32*3 + 32]
   float* dz;
   double* stat_out;       // sum(dz), sum(dz * xhat)
-  int dbg;                // timing experiments (MURAL_DEBUG_CL): 64 no staging, 128 no weight gradient, 256 no input gradient, 512 no stream-out
+  int dbg;                // timing experiments (0 in every launch; its switch is retired): 64 no staging, 128 no weight gradient, 256 no input gradient, 512 no stream-out
 };
 
 __global__ __launch_bounds__(SNV_THREADS, 2) void conv32cl_bwd_kernel(const ClBwdArgs a) {
@@ -663,12 +663,6 @@ __global__ __launch_bounds__(256) void gmax_relu_bwd_cl_kernel(const GmaxBwdArgs
   }
 }
 
-// phase-ablation switches of the timing tools (tools/time_conv32_cl.py), read once
-int debug_phases() {
-  static const int v = dev_env("MURAL_DEBUG_CL") ? atoi(dev_env("MURAL_DEBUG_CL")) : 0;
-  return v;
-}
-
 int cl_grid(int64_t total, int cap = 8192) {
   const int64_t g = (total + 255) / 256;
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -693,7 +687,6 @@ int cl_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* 
   a.x = x; a.y = y; a.W = W; a.bias = bias; a.res1 = res1; a.res2 = res2; a.pre_relu = pre_relu; a.post_relu = post_relu;
   a.stat_out = acc_out; a.stat_relu = out_relu;
   a.fin = ClFin{acc, (double)B * L, gamma, beta, eps, momentum, running_mean, running_var, state};
-  a.dbg = debug_phases();
   const size_t lds = (size_t)(2 * a.t.nbuf + 3 * CL_C) * 4;
   static DynLdsOnce big_lds;
   if (int rc = big_lds.ensure(&conv32cl_fwd_kernel)) return rc;
@@ -714,7 +707,6 @@ int cl_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, in
   std::memset(&a, 0, sizeof(a));
   MURAL_REQUIRE(cl_tile((int)B, L, &a.t), "conv32_bwd (channel-last): L = %d does not fit the LDS tile", L);
   a.dy = dy; a.x = x; a.W = W; a.state = state; a.pre_relu = pre_relu; a.part = part; a.dz = dz; a.stat_out = stat_out;
-  a.dbg = debug_phases();
   const int64_t ntiles = (B + a.t.R - 1) / a.t.R;
   size_t lds = (size_t)2 * a.t.nbuf * 4;
   const size_t lds_red = (size_t)4 * (CL_C * CL_C * 3 + CL_C) * 4;

@@ -65,12 +65,11 @@ struct CwGeom {
 // prologue (fragments, BatchNorm finalisation) and an epilogue (batch sums / the partial row) for one unit per wave.  Rows short
 // enough to share a unit (P >= 2) ask for ONE slot per CU -- four rows per wave in the short stages, two units per wave in the mid
 // tower's first stage -- and leave the other to the other tower; rows that need a unit each keep both (two units per wave at batch
-// 4096).  Same-box A/B of the whole step, batch 4096: 498 -> 528 steps/s (tools/r6_train_slots.sh; MURAL_CW_FULL_GRID=1 is the old
-// rule).  The choice changes the order of the float sums, not their reproducibility.
+// 4096).  Same-box A/B of the whole step, batch 4096: 498 -> 528 steps/s against two slots for every launch.
+// The choice changes the order of the float sums, not their reproducibility.
 int cw_slots(int L) {
-  static const bool full = dev_env("MURAL_CW_FULL_GRID") && atoi(dev_env("MURAL_CW_FULL_GRID")) != 0;
   const int pmax = (16 * CW_NBMAX - 1) / (L + 1);
-  return (full || pmax < 2) ? 2 * CW_CUS : CW_CUS;
+  return pmax < 2 ? 2 * CW_CUS : CW_CUS;
 }
 
 bool cw_geom(int64_t B, int L, CwGeom* g) {
@@ -816,7 +815,7 @@ __global__ __launch_bounds__(CW_THREADS, 2) void conv32w_bwd_kernel(const CwBwdA
 }
 
 int cw_debug() {
-  static const int v = dev_env("MURAL_DEBUG_CW") ? atoi(dev_env("MURAL_DEBUG_CW")) : 0;
+  static const int v = dev_int("MURAL_DEBUG_CW", 0);
   return v;
 }
 

@@ -21,8 +21,7 @@ constexpr int INDEL_LEVELS = 6;
 // within the 2^31-byte reach of the barrier-free kernels' buffer offsets.  (MURAL_INDEL_CHUNK: A/B switch of the debug flavour, 256 .. 4096)
 constexpr int INDEL_CHUNK_DEFAULT = 4096;
 static int indel_chunk() {
-  const char* e = dev_env("MURAL_INDEL_CHUNK");
-  const int c = e ? atoi(e) : INDEL_CHUNK_DEFAULT;
+  const int c = dev_int("MURAL_INDEL_CHUNK", INDEL_CHUNK_DEFAULT);
   return c >= 256 && c <= 4096 ? c : INDEL_CHUNK_DEFAULT;
 }
 #define INDEL_CHUNK indel_chunk()
@@ -295,11 +294,10 @@ extern "C" void mural_indel_model_destroy(MuralIndelModel* m) {
   delete m;
 }
 
-// chunks in flight: even / odd chunks on two streams; MURAL_INDEL_LANES=3 (experiment): a third one on the second side stream
+// chunks in flight: even / odd chunks on two streams
 static int indel_lanes(int64_t n) {
-  static const int want = dev_env("MURAL_INDEL_LANES") ? atoi(dev_env("MURAL_INDEL_LANES")) : 2;
   const int64_t chunks = (n + INDEL_CHUNK - 1) / INDEL_CHUNK;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(want, 3), chunks));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(2, chunks));
 }
 constexpr size_t INDEL_WS_REGIONS = INDEL_LEVELS + 7;   // S | E[levels] | T1 | T2 | H | SP | M | X
 
@@ -332,8 +330,7 @@ static int run_upconv(const MuralIndelModel* m, int j, const float* in, int B, i
     a.B = B; a.Cin = fp.Cin; a.Lin = Lin; a.Cout = fp.Cout; a.Lout = Lout;
     a.K = fp.K; a.stride = 1; a.pad = m->dn_lp_pad[j]; a.up = 1; a.phases = up;
     a.act = ACT_NONE;
-    static const bool use_direct = !(dev_env("MURAL_CONV1D_DIRECT") && atoi(dev_env("MURAL_CONV1D_DIRECT")) == 0);
-    if (use_direct && (int64_t)B * Lin >= 32768 && conv1d_direct_poly_supported(a)) return launch_conv1d_direct_poly(a, stream);
+    if ((int64_t)B * Lin >= 32768 && conv1d_direct_poly_supported(a)) return launch_conv1d_direct_poly(a, stream);
     if (conv1d_mfma_supported(a)) return launch_conv1d_mfma(a, stream);
   }
   return run_conv(m, m->dn_l[j], in, B, Lin, out, Lout, 1, up, ACT_NONE, nullptr, nullptr, stream);
@@ -430,14 +427,14 @@ static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, c
   SideStreamHold ss;      // holds the device's side streams until this call has joined them again
   if (lanes >= 2) {
     if (int rc = ss.acquire()) return rc;
-    if (int rc = ss->fork(main_stream, lanes == 3)) return rc;
+    if (int rc = ss->fork(main_stream)) return rc;
   }
   int rc_all = MURAL_OK;
   int64_t chunk_no = 0;
   for (int64_t c0 = 0; c0 < n && rc_all == MURAL_OK; c0 += INDEL_CHUNK, ++chunk_no) {
     const int B = (int)std::min<int64_t>(INDEL_CHUNK, n - c0);
     const int lane = (int)(chunk_no % lanes);
-    hipStream_t stream = lane == 0 ? main_stream : lane == 1 ? ss->side : ss->side2;
+    hipStream_t stream = lane == 0 ? main_stream : ss->side;
     const size_t guard_floats = ws_guard_bytes() / 4;
     float* p = static_cast<float*>(workspace) + (size_t)lane * (INDEL_CHUNK * m->per_pos_floats + INDEL_WS_REGIONS * guard_floats);
     if (chunk_no < lanes) {
@@ -476,8 +473,7 @@ static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, c
       // dense one-hot windows (what the reference's loader yields): classified into one symbol byte per column and taken by the same
       // persistent table-driven first level as the packed entry; columns that are no MuRaL symbol are evaluated from their floats there
       // (MURAL_INDEL_DENSE_SYMBOLS=0: the input layer and the first level as launches of their own on the dense tensor)
-      const bool sym_off = (dev_env("MURAL_INDEL_DENSE_SYMBOLS") && atoi(dev_env("MURAL_INDEL_DENSE_SYMBOLS")) == 0) ||
-                           (dev_env("MURAL_INDEL_ENC0") && atoi(dev_env("MURAL_INDEL_ENC0")) == 0) || dev_env("MURAL_DEBUG_CONVBLOCK_VALU") ||
+      const bool sym_off = dev_int("MURAL_INDEL_DENSE_SYMBOLS", 1) == 0 || dev_int("MURAL_INDEL_ENC0", 1) == 0 ||
                            dev_env("MURAL_CONVBLOCK8_VALU");
       if (first_fused && m->e0_t3 && (Lx & 3) == 0 && !sym_off) {
         if ((rc = launch_dense_to_symbols(x, B, Lx, reinterpret_cast<uint8_t*>(X), nullptr, stream, 16))) return rc;
@@ -497,11 +493,9 @@ static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, c
     }
     // the genome-fed first level also emits the second level's strided conv (8 -> 16, k = 7, stride 4) where the shapes are the
     // persistent kernel's (indel_level0.hip); MURAL_INDEL_ENC0_DOWN=0: the conv as a launch of its own
-    const bool down_off = (dev_env("MURAL_INDEL_ENC0_DOWN") && atoi(dev_env("MURAL_INDEL_ENC0_DOWN")) == 0) ||
-                                 (dev_env("MURAL_INDEL_ENC0") && atoi(dev_env("MURAL_INDEL_ENC0")) == 0);
+    const bool down_off = dev_int("MURAL_INDEL_ENC0_DOWN", 1) == 0 || dev_int("MURAL_INDEL_ENC0", 1) == 0;
     const bool emit_down = (gs.g || gs.sym) && m->e0_t3 && !down_off && sh.down[1] == 4 && m->up_l[1].K == 7 && m->up_l[1].Cin == 8 && m->up_l[1].Cout == 16 &&
-                           (m->len[0] & 3) == 0 && m->len[1] == (m->len[0] - 1) / 4 + 1 && !dev_env("MURAL_DEBUG_CONVBLOCK_VALU") &&
-                           !dev_env("MURAL_CONVBLOCK8_VALU");
+                           (m->len[0] & 3) == 0 && m->len[1] == (m->len[0] - 1) / 4 + 1 && !dev_env("MURAL_CONVBLOCK8_VALU");
     for (int i = 0; i < INDEL_LEVELS; ++i) {     // encoder: strided conv+BN, then ConvBlock (x + BN(1x1(SiLU(BN(k5)))))
       const int Li = m->len[i];
       if (sh.down[i] == 1 && block_fusable(m->up5[i], m->up1[i], Li) && front_fusable(m->up_l[i], 1, m->ch[i])) {
@@ -572,7 +566,7 @@ static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, c
     }();
   }
   if (lanes >= 2)
-    if (int rc = ss->join(main_stream, lanes == 3)) return rc;     // also on an error: the side stream must not stay forked
+    if (int rc = ss->join(main_stream)) return rc;     // also on an error: the side stream must not stay forked
   return rc_all;
 }
 

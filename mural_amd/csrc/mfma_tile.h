@@ -9,7 +9,7 @@ namespace mural {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // LDS image [column][32 channels]: the eight 16-byte chunks of a column are XOR-permuted by a per-column key chosen
-// (exhaustive search over 16-entry tables, tools/lds_swizzle_search.py) so that the ds_read_b128 operand reads of all
+// (exhaustive search over 16-entry tables) so that the ds_read_b128 operand reads of all
 // three conv taps are bank-conflict-free for every 16-lane group of the instruction; the key depends on column mod 16,
 // so a wave's blocks, 32 columns apart, keep one base address + immediates.
 __device__ __forceinline__ int lds_key(int pc) {
@@ -27,8 +27,7 @@ __device__ __forceinline__ int xcd_wave_index(int w, int on) {
   return slot * 4 + w;
 }
 inline int xcd_swizzle_enabled() {      // MURAL_XCD_SWIZZLE=0: workgroup b takes slot b (A/B switch)
-  const char* e = dev_env("MURAL_XCD_SWIZZLE");
-  return !(e && atoi(e) == 0);
+  return dev_int("MURAL_XCD_SWIZZLE", 1) != 0;
 }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }

@@ -171,7 +171,6 @@ struct SnvFwdArgs {
   // waves that share a SIMD do not run at the same speed (the older wave slot wins the issue arbitration), so with equal shares
   // the favoured half of the waves is done at 0.72 of the launch and the rest finishes alone; nullptr: fixed stride
   int* unit_counter;
-  int stagger;                    // wave-private launch: late start of every second workgroup of a CU, in units of 8128 cycles
   // Long windows (run-time-geometry first-stage instance, one site per wave): the launch's "rows" are SEGMENTS of the large tower's
   // pooled row read in place from x0 -- row v = segment v % seg_n of site v / seg_n, starting at column seg_col0 + (v % seg_n) *
   // seg_step of that site's x0 row.  seg_n == 0: rows are sites (column offset by tower, as always).
@@ -185,10 +184,7 @@ constexpr int RU_L = 2 * RU_EC;          // data columns per site in the edge ti
 constexpr int RU_SC = RU_L + 1;          // + zero separator
 
 struct EdgeArgs {
-  TowerGeom ge;             // stage 0 = the edge tile: L = 18, Sc = 19
   TowerDev tw;
-  int P;
-  int nbuf;                 // floats per LDS buffer
   int64_t n;                // sites of this launch
   const int64_t* pos;       // genome positions of the sites
   const uint8_t* strand;    // 0 '+', 1 '-' per site: selects the row set

@@ -217,8 +217,7 @@ __global__ __launch_bounds__(256) void hd_bwd2_kernel(const float* __restrict__ 
 }  // namespace headtrain
 
 bool head_train_fused_ok(int nc) {
-  const char* e = dev_env("MURAL_TRAIN_HEAD_OPS");
-  return !(e && atoi(e) != 0) && nc >= 1 && nc <= SNV_MAXCLASS;
+  return dev_int("MURAL_TRAIN_HEAD_OPS", 0) == 0 && nc >= 1 && nc <= SNV_MAXCLASS;
 }
 
 // forward of a tower's head: c3 [B][L][32] (raw conv output) -> feat, arg, fd, logits; acc zeroed by the caller

@@ -292,7 +292,7 @@ struct Workspace { float* local_logits; int64_t* cat; uint8_t* symbols; float* x
 // tail); four chunks' worth are 42.7 / 51.2.  Long windows and models without the split launches keep one chunk.
 constexpr int SNV_SUPER = 4;
 int64_t super_chunk_sites(const MuralSnvModel* m) {
-  const bool off = dev_env("MURAL_SNV_DEFER_SHORT") && atoi(dev_env("MURAL_SNV_DEFER_SHORT")) == 0;
+  const bool off = dev_int("MURAL_SNV_DEFER_SHORT", 1) == 0;
   return (m->split && !m->longwin && !off) ? SNV_SUPER * m->chunk : m->chunk;
 }
 
@@ -430,13 +430,8 @@ extern "C" int mural_snv_model_create(const MuralSnvShape* shape, const MuralSnv
       // form where it applies
       auto plan_part = [&](int q) -> bool {
         const int towers = (q & 1) ? 2 : 1, phase = q < 2 ? 1 : 2;
-        int Pq = 0, Pmax = 32;
-        if (const char* e = dev_env("MURAL_DEBUG_SPLIT_P")) {   // diagnostic: "P0,P1,P2,P3" caps the tile sizes
-          int v[4] = {32, 32, 32, 32};
-          sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]);
-          if (v[q] >= 1) Pmax = v[q];
-        }
-        for (int cand = Pmax; cand >= 1 && !Pq; --cand) {
+        int Pq = 0;
+        for (int cand = 32; cand >= 1 && !Pq; --cand) {
           SnvFwdArgs tmp;
           const size_t need = plan_geometry(tmp, sh.distal_len, cand, sh.n_class, towers, phase);
           if (need && need <= kLdsTwoPerCu) { Pq = cand; m->lds_split[q] = need; }
@@ -451,29 +446,20 @@ extern "C" int mural_snv_model_create(const MuralSnvShape* shape, const MuralSnv
         }
         plan_geometry(m->args_split[q], sh.distal_len, Pq, sh.n_class, towers, phase);
         // Wave-private form of this launch (snv_tower_wave.hip): the most sites per wave that keep a wave within its nine
-        // blocks and two four-wave workgroups on a CU.  MURAL_DEBUG_TOWER_WAVE = bit mask of the launches that may take it
-        // (default: all four); 0 keeps the workgroup-tile kernel everywhere (A/B runs).
-        int wave_mask = 15;
-        if (const char* e = dev_env("MURAL_DEBUG_TOWER_WAVE")) wave_mask = atoi(e);
-        if ((wave_mask >> q) & 1) {
-          for (int cand = 31; cand >= 1; --cand) {
-            SnvFwdArgs tmp;
-            std::memset(&tmp, 0, sizeof(tmp));
-            const size_t need = plan_wave_geometry(tmp, sh.distal_len, cand, sh.n_class, q & 1, phase);
-            if (need && need <= kLdsTwoPerCu) {
-              m->args_split[q] = tmp;
-              m->lds_split[q] = need;
-              break;
-            }
+        // blocks and two four-wave workgroups on a CU.
+        for (int cand = 31; cand >= 1; --cand) {
+          SnvFwdArgs tmp;
+          std::memset(&tmp, 0, sizeof(tmp));
+          const size_t need = plan_wave_geometry(tmp, sh.distal_len, cand, sh.n_class, q & 1, phase);
+          if (need && need <= kLdsTwoPerCu) {
+            m->args_split[q] = tmp;
+            m->lds_split[q] = need;
+            break;
           }
         }
         return true;
       };
       m->chunk = SNV_CHUNK;
-      if (const char* e = dev_env("MURAL_SNV_CHUNK")) {      // experiment: smaller chunks keep x0 in the 256 MB Infinity Cache
-        const long v = atol(e);
-        if (v >= 1024 && v <= SNV_CHUNK) m->chunk = v;
-      }
       m->longwin = false;
       if (!dev_env("MURAL_DEBUG_NO_LONGWIN")) {      // (tried first: a row of 143 .. ~270 columns also fits ONE workgroup tile per CU, slowly)
         // Long window: the large tower's pooled first-stage row (L2 columns) does not fit a wave's image.  Its first conv stage --
@@ -530,7 +516,7 @@ extern "C" int mural_snv_model_create(const MuralSnvShape* shape, const MuralSnv
         // split mode: (tower, phase) pairs in their own launches, each with the largest tile that keeps two workgroups per
         // CU: the mid tower and above all the short stages then run layers that are many blocks wide
         m->split = false;
-        if (lds <= kLdsTwoPerCu && !dev_env("MURAL_DEBUG_NO_TOWER_SPLIT")) {
+        if (lds <= kLdsTwoPerCu) {
           bool ok = true;
           for (int q = 0; q < 4 && ok; ++q) ok = plan_part(q);
           m->split = ok;
@@ -554,8 +540,7 @@ extern "C" int mural_snv_model_create(const MuralSnvShape* shape, const MuralSnv
           m->s1_lds_bytes = (size_t)2 * SNV_LUTBLK * 4 + (size_t)s1.wave_bytes + 64;
         }
         // the large tower's pair table rides along where it fits (15-wide pools: the shipped first max-pool)
-        m->s1_pair = !s1.site_mode && s1.tw[0].pk == 15 && s1.tw[0].ps == 15 && m->s1_lds_bytes + (size_t)SNV_LUT4 * 4 <= kLdsMax &&
-                     !dev_env("MURAL_DEBUG_NO_PAIR_TABLE");
+        m->s1_pair = !s1.site_mode && s1.tw[0].pk == 15 && s1.tw[0].ps == 15 && m->s1_lds_bytes + (size_t)SNV_LUT4 * 4 <= kLdsMax;
         if (m->s1_pair) m->s1_lds_bytes += (size_t)SNV_LUT4 * 4;
         if (m->s1_lds_bytes > kLdsMax || s1.tw[0].pk > 16 || s1.tw[1].pk > 4) {
           set_error("distal_radius %d is too long for the stage-1 kernel's LDS window", (sh.distal_len - 1) / 2);
@@ -615,7 +600,7 @@ extern "C" int mural_snv_model_create(const MuralSnvShape* shape, const MuralSnv
     L.frag = m->blob + loff.frag; L.frag_floats = (int)loff.frag_floats;
     L.cols = sh.local_cols; L.emb_rows = sh.emb_rows; L.in1 = 5 * sh.local_cols; L.h1 = sh.hidden1; L.h2 = sh.hidden2;
     L.n_class = sh.n_class;
-    m->loc_fused = has_towers && local_mfma_plan(L, &m->loc_d, &m->loc_lds) && !dev_env("MURAL_DEBUG_NO_LOCAL_FUSE");
+    m->loc_fused = has_towers && local_mfma_plan(L, &m->loc_d, &m->loc_lds);
   }
   *out = m;
   return MURAL_OK;
@@ -687,7 +672,7 @@ static int run_towers(const MuralSnvModel* m, Stage1Args s1, SnvFwdArgs a, bool 
     if (int rc = launch_snv_stage1(s, packed, s.loc_on ? std::max(m->s1_lds_bytes, m->loc_lds) : m->s1_lds_bytes, stream)) return rc;
     const bool split = m->split && taps == nullptr && !small;   // the debug dump wants both towers in one tile geometry
     // (the unit counters are read only with MURAL_TOWER_DYNAMIC_UNITS=1: the fill is a 4 us launch per chunk otherwise wasted)
-    if (split && dev_env("MURAL_TOWER_DYNAMIC_UNITS") && atoi(dev_env("MURAL_TOWER_DYNAMIC_UNITS")) != 0)
+    if (split && dev_int("MURAL_TOWER_DYNAMIC_UNITS", 0) != 0)
       MURAL_HIP_CHECK(hipMemsetAsync(w.counters, 0, 64, stream));
     bool lw_mid_done = false;      // (long windows: the mid tower's first stage rode in the segments' launch)
     for (int part = 0; part < (split ? (defer ? 2 : 4) : 1); ++part) {
@@ -701,11 +686,10 @@ static int run_towers(const MuralSnvModel* m, Stage1Args s1, SnvFwdArgs a, bool 
         // (round 6: the segments are read in place from x0 -- SnvFwdArgs::seg_n -- instead of being copied out with their halo first:
         // 2 x 70 MB per 512 windows at R = 4000 and two launches less)
         // the two segment launches and the mid tower's first-stage launch are three jobs of one kernel instance: ONE launch (each launch of
-        // its own pays ~14 us of start-up next to 22 us per unit; MURAL_DEBUG_LW_SEPARATE: three launches, same results)
+        // its own pays ~14 us of start-up next to 22 us per unit)
         SnvFwdArgs lw_jobs[3];
         size_t lw_lds[3];
-        const bool lw_merge = m->args_lwA.wave && m->args_lwB.wave && m->args_split[1].wave && !dev_env("MURAL_DEBUG_LW_SEPARATE") &&
-                              (!front_out || m->front_mid);
+        const bool lw_merge = m->args_lwA.wave && m->args_lwB.wave && m->args_split[1].wave && (!front_out || m->front_mid);
         for (int kind = 0; kind < 2; ++kind) {
           SnvFwdArgs t = kind == 0 ? m->args_lwA : m->args_lwB;
           t.n = kind == 0 ? cn * m->lw_nA : cn;
@@ -782,7 +766,7 @@ static int run_towers(const MuralSnvModel* m, Stage1Args s1, SnvFwdArgs a, bool 
       // A workgroup-tile short-stage launch (long windows) packs P sites into a tile so that two workgroups fill a CU -- and then a call of
       // a few hundred windows is a few dozen workgroups on 256 CUs (R = 4000, 512 windows: 171 and 52).  Such a call takes the tile
       // with the fewest sites that still gives every CU two workgroups: same arithmetic per site, a third of the serial work per workgroup.
-      if (split && !t.wave && part >= 2 && t.P > 1 && !dev_env("MURAL_DEBUG_NO_CALL_P")) {
+      if (split && !t.wave && part >= 2 && t.P > 1) {
         const int want = (int)std::max<int64_t>(1, std::min<int64_t>(t.P, (cn + 511) / 512));
         if (want < t.P) {
           SnvFwdArgs t2 = t;

@@ -13,8 +13,8 @@
 //                                 column of a window ending at b) -- all from the same 3-mer tables as snv_stage1_kernel
 //   B  reuse_rows_conv_kernel     the four ResBlock convs as dilated convs over the [base][32] rows (fp32 MFMA), 4 launches/tower
 //   S  reuse_rows_pool_kernel     sliding maxpool2 + BN over the rows: S[b] = pooled column centred on b
-//   E  snv_edge_kernel            per site: the 9 -> 5 pooled columns next to each window edge are recomputed exactly through
-//                                 the four convs (same conv code, same tile layout as the per-window kernel: 18 columns per
+//   E  snv_edge_wave              per site: the 9 -> 5 pooled columns next to each window edge are recomputed exactly through
+//      (snv_tower_wave.hip)       the four convs (same conv code, same tile layout as the per-window kernel: 18 columns per
 //                                 site instead of 134 / 67), the interior of maxpool2 is gathered from S, and the pooled tile
 //                                 s3 goes to the unchanged short-stage launches (snv_towers_fused<2>)
 //
@@ -231,201 +231,6 @@ __global__ __launch_bounds__(256) void reuse_rows_pool_kernel(const float* __res
   }
 }
 
-// --------------------------------------------------------------------------------------------------------------- kernel E
-// stage-2 column of edge-tile column j (0 .. 17): the 9 leftmost, then the 9 rightmost
-__device__ __forceinline__ int edge_q(int j, int L2) { return j < RU_EC ? j : L2 - RU_L + j; }
-
-// row index of a site's first input column | strand << 62, or -1 when the site lies outside the rows
-__device__ __forceinline__ int64_t edge_wstart(const EdgeArgs& args, int64_t row) {
-  if (row >= args.n) return -1;
-  const int64_t gp = args.pos[row];
-  const int neg = args.strand[row] != 0;
-  const int64_t t = neg ? args.glen - 1 - gp : gp;
-  const int64_t w = t + args.woff - args.t0[neg];
-  if (w < 0 || w + args.L1 > args.nb || args.F[neg] == nullptr) return -1;   // the caller's bounds / strand mask were wrong
-  return w | ((int64_t)neg << 62);
-}
-
-// x0 of the lane's edge columns of one tile, raw, in MFMA accumulator layout (requested one tile ahead)
-__device__ __forceinline__ void edge_request_x0(const EdgeArgs& args, const uint32_t (&plan)[SNV_NB2MAX], const int64_t* wst, int nbw,
-                                                int chv, f32x4 (&xres)[SNV_NB2MAX], uint32_t& live) {
-  live = 0;
-#pragma unroll
-  for (int i = 0; i < SNV_NB2MAX; ++i) {
-    xres[i] = splat(0.f);
-    if (i < nbw && plan[i] != ~0u) {
-      const int p = (int)(plan[i] >> 16), q = (int)(plan[i] & 0xFFFFu);
-      const int64_t ws = wst[p];
-      if (ws >= 0) {
-        const int set = (int)(ws >> 62);
-        const int64_t w = ws & ((1ll << 62) - 1);
-        const float* src = args.F[set] + (size_t)(w + (int64_t)args.D * q) * 32;
-        if (q == 0) src = args.El[set] + (size_t)w * 32;
-        else if (q == args.L2 - 1 && args.right_pad) src = args.Er[set] + (size_t)(w + args.L1 - 1) * 32;
-        xres[i] = ld4(src + chv);
-        live |= 1u << i;
-      }
-    }
-  }
-}
-
-constexpr int RU_POOL_SLOTS = 9;      // interior pooled (site, column, channel group) gathers per thread: P * n_int * 8 / 256 <= 9
-
-__global__ __launch_bounds__(SNV_THREADS, 2) void snv_edge_kernel(const EdgeArgs args) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int mb = wave & 1, cgp = wave >> 1;
-  const int n16 = lane & 15, kk = lane >> 4;
-  const int chv = 16 * mb + 4 * kk;
-  const int P = args.P;
-  float* bufA = smem;
-  float* bufB = smem + args.nbuf;
-  int64_t* wbuf = reinterpret_cast<int64_t*>(smem + 2 * args.nbuf);     // [2][P]: this tile's and the next tile's window starts
-  const TowerGeom& g = args.ge;
-  const TowerDev& tw = args.tw;
-  const int64_t n_tiles = (args.n + P - 1) / P;
-  const StageAddr sa = stage_setup(g, 0, P, n16, kk, mb, cgp);
-  const int nb = g.nb[0];
-  const int nbw = nb > cgp ? (nb - cgp + 1) / 2 : 0;
-  // per-lane plan of the entry gather: (site p, stage-2 column q) of the lane's column in each owned block
-  uint32_t plan[SNV_NB2MAX];
-#pragma unroll
-  for (int i = 0; i < SNV_NB2MAX; ++i) {
-    plan[i] = ~0u;
-    const int c = 16 * (cgp + 2 * i) + n16;
-    if (i < nbw && c >= 1) {
-      const uint32_t u = (uint32_t)(c - 1);
-      const uint32_t p = g.dSc[0].div(u);
-      const uint32_t j = u - p * (uint32_t)RU_SC;
-      if (p < (uint32_t)P && j < (uint32_t)RU_L) plan[i] = (p << 16) | (uint32_t)edge_q((int)j, args.L2);
-    }
-  }
-  const f32x4 es = ld4(tw.ex_s + EX_RB1_ENTRY * 32 + chv), et = ld4(tw.ex_t + EX_RB1_ENTRY * 32 + chv);
-  const int cgq = tid & 7;
-  const f32x4 pool_s = ld4(tw.ex_s + EX_BN_MID * 32 + 4 * cgq), pool_t = ld4(tw.ex_t + EX_BN_MID * 32 + 4 * cgq);
-  float a_cur[SNV_KSTEPS];
-  {
-    const float* wf = tw.wfrag + (size_t)mb * SNV_KSTEPS * 64 + lane;
-#pragma unroll
-    for (int s = 0; s < SNV_KSTEPS; ++s) a_cur[s] = wf[s * 64];
-  }
-  f32x4 xres[SNV_NB2MAX];
-  uint32_t live = 0;
-  int cur = 0;
-  if (tid < P) wbuf[tid] = edge_wstart(args, (int64_t)blockIdx.x * P + tid);
-  __syncthreads();
-  edge_request_x0(args, plan, wbuf, nbw, chv, xres, live);
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int64_t row0 = tile * P;
-    const int64_t* wst = wbuf + cur * P;
-    // ---- entry: BN(ReLU(x0)) image of the 18 edge columns into bufA; the raw values stay in the residual registers
-    {
-      char* A = reinterpret_cast<char*>(bufA);
-#pragma unroll
-      for (int i = 0; i < SNV_NB2MAX; ++i)
-        if (i < nbw) lds_st4(A, sa.wr + 4096u * i, ((live >> i) & 1u) ? relu_bn(xres[i], es, et) : splat(0.f));
-    }
-    // window starts of the next tile: the position load hides under the convs
-    if (tid < P) wbuf[(cur ^ 1) * P + tid] = edge_wstart(args, (tile + gridDim.x) * P + tid);
-    __syncthreads();
-    // ---- the four ResBlock convs on the edge tile
-    for (int layer = 0; layer < 4; ++layer) {
-      const LayerK lk = layer_consts(layer_mode(layer));
-      const bool in_is_a = ((0xA5u >> layer) & 1u) != 0;
-      const char* in = reinterpret_cast<const char*>(in_is_a ? bufA : bufB);
-      char* out = reinterpret_cast<char*>(in_is_a ? bufB : bufA);
-      const f32x4 pb = ld4(tw.bias + layer * 32 + chv), ps = ld4(tw.post_s + layer * 32 + chv), pt = ld4(tw.post_t + layer * 32 + chv);
-      __builtin_amdgcn_sched_barrier(0);
-      float a_nxt[SNV_KSTEPS];
-      {
-        const float* wfn = tw.wfrag + (size_t)(layer < 3 ? layer + 1 : 0) * SNV_WFRAG + (size_t)mb * SNV_KSTEPS * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < SNV_KSTEPS; ++s) a_nxt[s] = wfn[s * 64];
-      }
-      conv_layer(in, out, sa, nbw, lk, a_cur, pb, ps, pt, xres);
-      __syncthreads();
-#pragma unroll
-      for (int s = 0; s < SNV_KSTEPS; ++s) a_cur[s] = a_nxt[s];
-    }
-    // the residual registers are dead: the next tile's x0 gathers fly under the pooling
-    if (tile + gridDim.x < n_tiles) edge_request_x0(args, plan, wbuf + (cur ^ 1) * P, nbw, chv, xres, live);
-    // ---- maxpool2 + BN -> s3.  Interior windows (columns u_lo .. u_hi) are gathers from S, all issued before the first store;
-    //      the few windows that touch the edge pyramids read bufA (+ R rows when mixed) and get the BN here.
-    {
-      const int n_int = args.u_hi - args.u_lo + 1;
-      const int total = P * n_int * 8;
-      f32x4 sv[RU_POOL_SLOTS];
-#pragma unroll
-      for (int k = 0; k < RU_POOL_SLOTS; ++k) {
-        const int task = tid + k * SNV_THREADS;
-        sv[k] = splat(__uint_as_float(0x7FC00000u));
-        if (task < total) {
-          const int pj = task >> 3;
-          const int p = pj / n_int, u = args.u_lo + (pj - p * n_int);
-          const int64_t ws = wst[p];
-          if (ws >= 0) {
-            const int set = (int)(ws >> 62);
-            const int64_t w = ws & ((1ll << 62) - 1);
-            sv[k] = ld4(args.S[set] + (size_t)(w + (int64_t)args.D * args.ps2 * u) * 32 + 4 * cgq);
-          }
-        }
-      }
-      // edge / mixed windows while the gathers fly
-      const int n_edge = args.L3 - n_int;
-#pragma unroll 1
-      for (int task = tid; task < P * n_edge * 8; task += SNV_THREADS) {
-        const int pj = task >> 3;
-        const int p = pj / n_edge, e = pj - p * n_edge;
-        const int u = e < args.u_lo ? e : args.u_hi + 1 + (e - args.u_lo);
-        if (row0 + p >= args.n) continue;
-        const int64_t ws = wst[p];
-        f32x4 m = splat(__uint_as_float(0x7FC00000u));
-        if (ws >= 0) {
-          const int set = (int)(ws >> 62);
-          const int64_t w = ws & ((1ll << 62) - 1);
-          const int jlo = u * args.ps2 - args.pp2;
-          const int lo = jlo < 0 ? 0 : jlo;
-          const int hi = (jlo + args.pk2 - 1) < (args.L2 - 1) ? (jlo + args.pk2 - 1) : (args.L2 - 1);
-          f32x4 rv[7];
-#pragma unroll
-          for (int d = 0; d < 7; ++d) {           // the model's second pools are 7 / 3 wide: every row read in flight together
-            rv[d] = splat(-INFINITY);
-            const int q = lo + d;
-            if (q <= hi) {
-              if (q < RU_EV) rv[d] = ld4(bufA + lds_off(1 + p * RU_SC + q + 1, cgq));
-              else if (q > args.L2 - 1 - RU_EV) rv[d] = ld4(bufA + lds_off(1 + p * RU_SC + (q - (args.L2 - RU_L)) + 1, cgq));
-              else rv[d] = ld4(args.R[set] + (size_t)(w + (int64_t)args.D * q) * 32 + 4 * cgq);
-            }
-          }
-          m = max4(max4(max4(rv[0], rv[1]), max4(rv[2], rv[3])), max4(max4(rv[4], rv[5]), rv[6]));
-          for (int q = lo + 7; q <= hi; ++q) {     // wider pools (not in the model): plain loop
-            f32x4 v;
-            if (q < RU_EV) v = ld4(bufA + lds_off(1 + p * RU_SC + q + 1, cgq));
-            else if (q > args.L2 - 1 - RU_EV) v = ld4(bufA + lds_off(1 + p * RU_SC + (q - (args.L2 - RU_L)) + 1, cgq));
-            else v = ld4(args.R[set] + (size_t)(w + (int64_t)args.D * q) * 32 + 4 * cgq);
-            m = max4(m, v);
-          }
-          m = f32x4{fmaf(pool_s.x, m.x, pool_t.x), fmaf(pool_s.y, m.y, pool_t.y), fmaf(pool_s.z, m.z, pool_t.z),
-                    fmaf(pool_s.w, m.w, pool_t.w)};
-        }
-        st4(args.s3 + ((size_t)(row0 + p) * args.L3 + u) * 32 + 4 * cgq, m);
-      }
-#pragma unroll
-      for (int k = 0; k < RU_POOL_SLOTS; ++k) {
-        const int task = tid + k * SNV_THREADS;
-        if (task < total) {
-          const int pj = task >> 3;
-          const int p = pj / n_int, u = args.u_lo + (pj - p * n_int);
-          if (row0 + p < args.n) st4(args.s3 + ((size_t)(row0 + p) * args.L3 + u) * 32 + 4 * cgq, sv[k]);
-        }
-      }
-    }
-    lds_barrier();          // LDS-only hand-off: a full barrier would drain the x0 gathers of the next tile
-    cur ^= 1;
-  }
-}
-
 int pool_len(int L, int k, int s, int p) { return (L + 2 * p - k) / s + 1; }
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -440,7 +245,7 @@ struct ReuseWs {
 
 constexpr int RU_SUPER = 4;
 int64_t reuse_super_sites() {
-  const bool off = dev_env("MURAL_SNV_DEFER_SHORT") && atoi(dev_env("MURAL_SNV_DEFER_SHORT")) == 0;
+  const bool off = dev_int("MURAL_SNV_DEFER_SHORT", 1) == 0;
   return off ? (int64_t)SNV_CHUNK : (int64_t)RU_SUPER * SNV_CHUNK;
 }
 
@@ -480,7 +285,8 @@ size_t carve_reuse(const MuralSnvModel* m, int64_t n, int64_t span, int strands,
   return off;
 }
 
-// edge tile: as many sites as keep <= SNV_NB2MAX blocks per wave (two workgroups per CU fit by far)
+// sites per tile of the interior-gather bound below (RU_POOL_SLOTS): as many as keep <= SNV_NB2MAX blocks per wave
+constexpr int RU_POOL_SLOTS = 9;      // interior pooled (site, column, channel group) gathers per thread: P * n_int * 8 / 256 <= 9
 int reuse_edge_sites() {
   for (int cand = 15; cand >= 1; --cand) {
     const int NC = 1 + cand * RU_SC, nbk = (NC + 15) / 16;
@@ -653,15 +459,6 @@ extern "C" int mural_snv_forward_packed_reuse(const MuralSnvModel* m, const Mura
   // ---- per batch of sites: local branch, edge kernels, short-stage launches
   const int nc = sh.n_class;
   const int P = reuse_edge_sites();
-  TowerGeom ge{};
-  ge.L[0] = RU_L; ge.Sc[0] = RU_SC; ge.NC[0] = 1 + P * RU_SC; ge.nb[0] = (ge.NC[0] + 15) / 16;
-  ge.dL[0] = FastDiv::make(RU_L); ge.dSc[0] = FastDiv::make(RU_SC);
-  const int nbuf = (16 * ge.nb[0] + 2) * SNV_C;
-  const size_t lds_edge = (size_t)2 * nbuf * 4 + (size_t)2 * P * 8 + 64;
-
-  static DynLdsOnce edge_lds;
-  if (int rc = edge_lds.ensure(&snv_edge_kernel)) return rc;
-  const bool edge_wave = !dev_env("MURAL_DEBUG_EDGE_TILE");
   const int64_t super = reuse_super_sites();
   const size_t s3_site[2] = {(size_t)std::max(m->args.geom[0].L[1], 1) * SNV_C, (size_t)std::max(m->args.geom[1].L[1], 1) * SNV_C};
   for (int64_t u0 = 0; u0 < n; u0 += super) {
@@ -678,15 +475,12 @@ extern "C" int mural_snv_forward_packed_reuse(const MuralSnvModel* m, const Mura
       if (int rc = mural_encode_kmer(g, pos + s0, strand + s0, sn, local_radius, local_order, 0, w.cat, stream_)) return rc;
       if (int rc = launch_snv_local(m->local, w.cat, sn, w.local_logits + rel * nc, stream)) return rc;
     }
-    if (dev_env("MURAL_TOWER_DYNAMIC_UNITS") && atoi(dev_env("MURAL_TOWER_DYNAMIC_UNITS")) != 0)
+    if (dev_int("MURAL_TOWER_DYNAMIC_UNITS", 0) != 0)
       MURAL_HIP_CHECK(hipMemsetAsync(w.counters, 0, 64, stream));      // unit counters of this chunk's four wave-private launches (read with that switch only)
     for (int t = 0; t < 2; ++t) {
       const TowerGeom& gg = m->args.geom[t];
       EdgeArgs e{};
-      e.ge = ge;
       e.tw = m->args.tw[t];
-      e.P = P;
-      e.nbuf = nbuf;
       e.n = sn;
       e.pos = pos + s0;
       e.strand = strand + s0;
@@ -713,13 +507,7 @@ extern "C" int mural_snv_forward_packed_reuse(const MuralSnvModel* m, const Mura
         e.S[neg] = Srows[neg][t];
       }
       e.s3 = w.s3[t] + (size_t)rel * s3_site[t];
-      if (edge_wave) {      // wave-private form (snv_tower_wave.hip); MURAL_DEBUG_EDGE_TILE=1 keeps the workgroup-tile kernel (A/B runs)
-        if (int rc = launch_snv_edge_wave(e, w.counters + t, stream)) return rc;
-      } else {
-        const int64_t n_tiles = (sn + P - 1) / P;
-        hipLaunchKernelGGL(snv_edge_kernel, dim3((unsigned)std::min<int64_t>(n_tiles, 2048)), dim3(SNV_THREADS), lds_edge, stream, e);
-        MURAL_HIP_CHECK(hipGetLastError());
-      }
+      if (int rc = launch_snv_edge_wave(e, w.counters + t, stream)) return rc;
     }
   }
     for (int part = 2; part < 4; ++part) {      // the short stages and the head: one launch per tower for the whole super-chunk

@@ -871,7 +871,7 @@ int launch_first_train(FirstTrainArgs a, bool bwd, hipStream_t stream) {
   static DynLdsOnce big_lds[4];                             // once per instantiation and device (never inside a graph capture)
   if (int rc = big_lds[(slot == 4 ? 0 : 2) + (bwd ? 1 : 0)].ensure(fn)) return rc;
   a.stamps = g_first_stamps;
-  static const int dbg = dev_env("MURAL_DEBUG_FIRST") ? atoi(dev_env("MURAL_DEBUG_FIRST")) : 0;
+  static const int dbg = dev_int("MURAL_DEBUG_FIRST", 0);
   a.dbg = dbg;
   hipLaunchKernelGGL(fn, dim3(first_train_grid(a.B)), dim3(S1_THREADS), lds, stream, a);
   MURAL_HIP_CHECK(hipGetLastError());

@@ -366,19 +366,6 @@ __device__ __forceinline__ void wave_zero_gaps(float* img, const TowerGeom& g, i
 //          tower's launch also runs the head.
 // NBA / NBB: 16-column blocks per wave of the launch's main stage / of the last stage (PHASE 2), fixed at compile time for the
 // instances plan_wave_geometry admits (0: the launch phase has no such stage).
-// Arrival counters per CU (never reset: the workgroups resident on a CU at any time hold consecutive counts).  The two
-// workgroups of a CU are symmetric and start together, so left alone their waves run in lockstep: both in their conv layers
-// (sharing the MFMA pipe), then both in their entry / pooling phases (pipe idle).  Every second arrival therefore starts
-// `stagger` x 8 k cycles late; from then on one wave's boundary phases fall under its SIMD partner's MFMAs.
-__device__ int g_cu_arrivals[1024];
-
-__device__ __forceinline__ uint32_t cu_key() {
-  // HW_REG_HW_ID (id 4): cu_id [11:8], sh_id [12], se_id [15:13]; HW_REG_XCC_ID (id 20): xcc_id [3:0]
-  const uint32_t hw = __builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4);      // 8 bits from bit 8
-  const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);    // 4 bits from bit 0
-  return ((xcc & 7u) << 7) | (hw & 127u);
-}
-
 // diagnostic: accumulate one wave's cycles per phase into args.stamps[block][id] (only when stamps != nullptr; tools/phase_stamps.py)
 #define SNVW_STAMP(id)                                                               \
   do {                                                                               \
@@ -427,8 +414,7 @@ __global__ __launch_bounds__(SNV_THREADS, 2) void snv_tower_wave_jobs(const SnvF
 // EW_P = 7 sites x (9 + 9 edge columns + separator) = 134 columns = the nine blocks of a first-stage launch, runs the four
 // ResBlock convs on them with the layer code above (same fragments, k order, epilogue forms -- the per-window kernel's own
 // operation sequence), and pools: interior windows are gathered from the shared rows S, the windows that touch the edge
-// pyramids read the wave's image (+ R rows when mixed).  Replaces the workgroup-tile snv_edge_kernel (two LDS buffers, a
-// workgroup barrier per layer) for the shipped layer shape.
+// pyramids read the wave's image (+ R rows when mixed).
 // ====================================================================================================================
 constexpr int EW_NB = 9;
 constexpr int EW_WST = 32;      // floats per wave behind the image: window starts of this unit and of the next one (2 x 8 int64)
@@ -677,10 +663,7 @@ __global__ __launch_bounds__(SNV_THREADS, 2) void snv_edge_wave(const EdgeArgs a
   }
 }
 
-static bool tower_dynamic_units() {
-  const char* e = dev_env("MURAL_TOWER_DYNAMIC_UNITS");
-  return e && atoi(e) != 0 && !dev_env("MURAL_DEBUG_TOWER_STATIC_UNITS");
-}
+static bool tower_dynamic_units() { return dev_int("MURAL_TOWER_DYNAMIC_UNITS", 0) != 0; }
 
 size_t edge_wave_lds_bytes() {
   return (size_t)(4 * SNV_C + 4 * 3 * SNV_C + SNV_WAVES * ((16 * EW_NB + 2) * SNV_C + EW_WST + TW_DUMP)) * 4;
@@ -725,8 +708,6 @@ size_t plan_wave_geometry(SnvFwdArgs& a, int Lwin, int Pw, int n_class, int towe
   a.tw_last = tower;
   a.phase = phase;
   a.wave = 1;
-  a.stagger = 0;      // measured: no effect (the waves of a CU do not run in lockstep); kept as a diagnostic
-  if (const char* e = dev_env("MURAL_DEBUG_TOWER_STAGGER")) a.stagger = atoi(e);
   a.x0_cols = a.geom[0].L[0] + a.geom[1].L[0];
   a.nbuf = maxcols * SNV_C;
   const size_t par = (size_t)(2 * EX_COUNT * SNV_C + n_class * SNV_C + SNV_MAXCLASS + 4 + 6 * 3 * SNV_C);
@@ -777,8 +758,7 @@ int launch_snv_tower_wave(const SnvFwdArgs& a_in, size_t lds_bytes, hipStream_t 
   if (n_wg == 0) return MURAL_OK;
   // two workgroups per CU are resident: with more work than that every wave walks its units in a grid-stride loop, so the
   // prologue (parameter staging, first fragments, first activations with their full latency) is paid once per wave
-  int resident = 512;
-  if (const char* e = dev_env("MURAL_DEBUG_TOWER_GRID")) resident = std::max(1, atoi(e));
+  const int resident = 512;
   const int grid = (int)(n_wg < resident ? n_wg : resident);
   // Units at a fixed stride (wave w: units w, w + waves, ...).  The ticket counter (MURAL_TOWER_DYNAMIC_UNITS=1: a returning atomic per
   // unit, requested a unit ahead) was the default until the end of round 5 and is 2 - 5 % SLOWER on every batch size measured
@@ -786,10 +766,6 @@ int launch_snv_tower_wave(const SnvFwdArgs& a_in, size_t lds_bytes, hipStream_t 
   // the fixed stride has no tail to repair, and the counter's waves end a unit apart (64 +- 1 units each).  With the counter, units
   // go through it only when every wave has several to take.
   if (n_units < 4 * (int64_t)grid * SNV_WAVES || !tower_dynamic_units()) a.unit_counter = nullptr;
-  if (const char* e = dev_env("MURAL_DEBUG_TOWER_LDS")) {      // diagnostic: inflate the LDS request (one workgroup per CU: occupancy study)
-    const size_t v = (size_t)atol(e);
-    if (v > lds_bytes && v <= 160 * 1024) lds_bytes = v;
-  }
   static DynLdsOnce big_lds;
   if (int rc = big_lds.ensure(&snv_tower_wave<1, 9, 0, 0, 1>, &snv_tower_wave<1, 9, 0, 1, 2>, &snv_tower_wave<2, 8, 4, 0, 6>,
                               &snv_tower_wave<2, 8, 3, 1, 5>, &snv_tower_wave<1, 9, 0>)) return rc;

@@ -59,19 +59,7 @@
     else if (lane < 16) st4(img + lds_off(16 * g.nb[st0] + 1, lane - 8), splat(0.f));
     if (PHASE == 1) wave_zero_gaps(img, g, 0, Pw, lane);      // once: no layer of this launch stores into a gap column
   }
-  if (args.stagger > 0 && tid == 0) {
-    const uint32_t key = cu_key();
-    const int cnt = atomicAdd(&g_cu_arrivals[key], 1);
-    par[lpar0 - 1] = __int_as_float(cnt);
-    if (args.stamps != nullptr && PHASE == 1 && tw_i == 0) {      // diagnostic: which CU, which arrival
-      args.stamps[(size_t)SNVW_BX * 32 + 30] = key;
-      args.stamps[(size_t)SNVW_BX * 32 + 31] = (unsigned long long)cnt;
-      args.stamps[(size_t)SNVW_BX * 32 + 29] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
-    }
-  }
   __syncthreads();      // the only workgroup barrier of the kernel
-  if (args.stagger > 0 && (__float_as_int(par[lpar0 - 1]) & 1))
-    for (int i = 0; i < args.stagger; ++i) __builtin_amdgcn_s_sleep(127);
 
   const int64_t n_units = (args.n + Pw - 1) / Pw;
   // Units come from a counter (args.unit_counter, zero at launch) when there is one: the two waves of a SIMD do not share it evenly

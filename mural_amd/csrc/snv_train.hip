@@ -278,8 +278,7 @@ const float EPS = 1e-5f;
 // which conv kernels the step runs: the wave-private ones (conv32_wave.hip) where they apply, unless MURAL_TRAIN_CONV_CL=1 asks for the
 // workgroup-tile kernels everywhere (A/B runs, parity tests of both)
 bool use_wave_conv(int L, int post_relu, bool stats, int out_relu) {
-  const char* e = dev_env("MURAL_TRAIN_CONV_CL");
-  if (e && atoi(e) != 0) return false;
+  if (dev_int("MURAL_TRAIN_CONV_CL", 0) != 0) return false;
   return cw_conv32_supported(L) && !post_relu && (!stats || out_relu);
 }
 
@@ -477,7 +476,7 @@ int stage_b(Ctx& c, const MuralResBlock* rb, const MuralResBlock* grb, const flo
             float* d_in, float* const* tmp, FirstFold* defer = nullptr) {
   float *dz = tmp[0], *ga = tmp[1], *gb = tmp[2];
   if (defer) defer->dz = nullptr;
-  if (use_wave_conv(L, 0, false, 0) && !dev_env("MURAL_TRAIN_NO_FOLD")) {
+  if (use_wave_conv(L, 0, false, 0)) {
     // Three of the four BatchNorm-backward applies of the stage never run as passes of their own: the conv backward of the layer in
     // front makes its dy from (dz, saved input, sums) of the layer behind while it stages it (conv32_wave.hip, FOLD) -- a read of two
     // tensors instead of one there against a pass of two reads and a write here.  Only d x1, which two consumers need, is also
@@ -697,9 +696,8 @@ extern "C" int mural_snv_train_forward(const MuralSnvShape* shape, const MuralSn
   // histograms, first-layer tables, weight fragments: ~35 us of small launches in a row), so it starts beside them
   SideStreamHold ss;      // holds the device's side streams until this call has joined them again
   if (int rc = ss.acquire()) return rc;
-  static const int order = dev_env("MURAL_TRAIN_ORDER") ? atoi(dev_env("MURAL_TRAIN_ORDER")) : 0;      // experiment: 2 = local branch after the fork of the towers
   int rc_loc = MURAL_OK;
-  if (order != 2 && m == 2) {
+  if (m == 2) {
     if (int rc = ss->fork2((hipStream_t)stream)) return rc;
     c.stream = ss->side2;
     rc_loc = local_f(c, cat_x, dropout_p, seeds, seed_dev);
@@ -737,14 +735,12 @@ extern "C" int mural_snv_train_forward(const MuralSnvShape* shape, const MuralSn
   // kernel back by their enqueue time
   int rc_large = MURAL_OK, rc_mid = MURAL_OK;
   if (!rc_prep && !rc_loc) {
-    if (int rc = ss->fork((hipStream_t)stream, order == 2)) rc_prep = rc;
+    if (int rc = ss->fork((hipStream_t)stream)) rc_prep = rc;
   }
   if (!rc_prep && !rc_loc) {
     rc_large = tower_f(c, 1, params->large, dropout_p[4], seeds[4], seed_dev);
     c.stream = ss->side;
     rc_mid = rc_large ? MURAL_OK : tower_f(c, 0, params->mid, dropout_p[3], seeds[3], seed_dev);
-    c.stream = ss->side2;
-    if (order == 2 && m == 2 && !rc_mid && !rc_large) rc_mid = local_f(c, cat_x, dropout_p, seeds, seed_dev);
     c.stream = stream;
   }
   if (int rc = ss->join((hipStream_t)stream, true)) return rc;     // also on an error: the side streams must not stay forked
@@ -776,19 +772,11 @@ extern "C" int mural_snv_train_backward(const MuralSnvShape* shape, const MuralS
   SideStreamHold ss;      // holds the device's side streams until this call has joined them again
   if (int rc = ss.acquire()) return rc;
   if (int rc = ss->fork((hipStream_t)stream, true)) return rc;
-  static const int order = dev_env("MURAL_TRAIN_ORDER") ? atoi(dev_env("MURAL_TRAIN_ORDER")) : 0;      // experiment: 1 = local branch first
-  int rc_loc = MURAL_OK;
-  if (order == 1 && m == 2) {
-    c.stream = ss->side2;
-    rc_loc = local_b(c, cat_x, P.dlogit[0], dropout_p, seeds, seed_dev);
-    c.stream = stream;
-  }
   int rc_large = tower_b(c, 1, params->large, grads->large, P.dlogit[2], dropout_p[4], seeds[4], seed_dev);   // critical path first
   c.stream = ss->side;
   int rc_mid = rc_large ? MURAL_OK : tower_b(c, 0, params->mid, grads->mid, P.dlogit[1], dropout_p[3], seeds[3], seed_dev);
   c.stream = ss->side2;
-  if (order != 1 && m == 2 && !rc_mid && !rc_large) rc_mid = local_b(c, cat_x, P.dlogit[0], dropout_p, seeds, seed_dev);
-  if (!rc_mid) rc_mid = rc_loc;
+  if (m == 2 && !rc_mid && !rc_large) rc_mid = local_b(c, cat_x, P.dlogit[0], dropout_p, seeds, seed_dev);
   c.stream = stream;
   if (int rc = ss->join((hipStream_t)stream, true)) return rc;
   if (rc_mid) return rc_mid;

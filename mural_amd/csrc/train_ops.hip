@@ -1327,9 +1327,8 @@ extern "C" int mural_op_first_fwd(const uint8_t* sym, int64_t B, int32_t Lwin, i
                                   int32_t ps, int32_t pp, const float* gamma, const float* beta, const float* W,
                                   const float* bias, float eps, float momentum, float* running_mean, float* running_var,
                                   unsigned long long* counts, float* tab, float* y, void* arg, void* stream) {
-  static const int cl = (dev_env("MURAL_DEBUG_FIRST_CL") && C == 32) ? 1 : 0;
   return first_fwd_impl(sym, B, Lwin, col0, L1, C, pk, ps, pp, gamma, beta, W, bias, eps, momentum, running_mean, running_var, counts, tab, y,
-                        arg, cl, nullptr, stream);
+                        arg, 0, nullptr, stream);
 }
 
 static int first_bwd_impl(const float* dy, const void* arg, const uint8_t* sym, int64_t B, int32_t Lwin,
@@ -1380,10 +1379,7 @@ extern "C" int mural_op_first_bwd(const float* dy, const void* arg, const uint8_
                                   int32_t col0, int32_t L1, int32_t C, int32_t pk, int32_t ps, int32_t pp, const float* tab,
                                   const float* W, float* scratch, float* dW, float* dbias, float* dgamma, float* dbeta,
                                   void* stream) {
-  // (MURAL_DEBUG_FIRST_CL=1: tools/phase_stamps_first.py times the channel-last form of the composed step through this entry; the
-  // buffers have the same sizes, only the element order of dy differs)
-  static const int cl = (dev_env("MURAL_DEBUG_FIRST_CL") && C == 32) ? 1 : 0;
-  return first_bwd_impl(dy, arg, sym, B, Lwin, col0, L1, C, pk, ps, pp, tab, W, scratch, dW, dbias, dgamma, dbeta, cl, nullptr, stream);
+  return first_bwd_impl(dy, arg, sym, B, Lwin, col0, L1, C, pk, ps, pp, tab, W, scratch, dW, dbias, dgamma, dbeta, 0, nullptr, stream);
 }
 
 namespace mural {

@@ -222,7 +222,7 @@ def test_fused_and_per_op_routes_agree_on_ragged_shapes(hp, B, monkeypatch):
                         {k: b.detach().clone() for k, b in model.named_buffers() if b.is_floating_point() and b.numel()}))
     (o1, g1, b1), (o2, g2, b2) = results
     # (a batch of two rows: batch-statistics BatchNorm over two samples amplifies float32 round-off -- both routes sit 1.9e-2 from a
-    # float64 evaluation of the same step there, tools/r5_b2check.py)
+    # float64 evaluation of the same step there)
     gtol = 5e-4 if B >= 16 else 2e-2
     assert torch.isfinite(o1).all() and float((o1 - o2).abs().max()) <= (5e-5 if B >= 16 else 1e-3) * (float(o2.abs().max()) + 1.0)
     assert set(g1) == set(g2) and len(g1) >= 6

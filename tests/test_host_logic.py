@@ -42,7 +42,7 @@ def test_abi_library_exports_every_declared_symbol():
 
 
 def test_every_development_switch_is_in_the_one_table():
-    """The product library reads MURAL_HOST_THREADS and TMPDIR; every other environment switch of csrc/ goes through dev_env() and is
+    """The product library reads MURAL_HOST_THREADS and TMPDIR; every other environment switch of csrc/ goes through dev_env() / dev_int() and is
     listed in dev_switch_table (one line of description each), which only the debug flavour honours."""
     import glob
     from mural_amd import _lib
@@ -54,7 +54,7 @@ def test_every_development_switch_is_in_the_one_table():
     used, raw = set(), set()
     for path in glob.glob(os.path.join(ROOT, "mural_amd", "csrc", "*.h*")):
         src = open(path).read()
-        used |= set(re.findall(r'dev_env\("([A-Z_0-9]+)"\)', src))
+        used |= set(re.findall(r'dev_(?:env|int)\("([A-Z_0-9]+)"', src))
         raw |= set(re.findall(r'(?<![a-z_])getenv\("([A-Z_0-9]+)"\)', src))
     assert used == set(table), used ^ set(table)
     assert raw == {"MURAL_HOST_THREADS", "TMPDIR"}, raw

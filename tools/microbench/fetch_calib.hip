@@ -3,7 +3,7 @@
 // known byte count in your own access pattern").  Every kernel below reads a 1 GiB buffer (4 x the Infinity Cache, written by a fill
 // kernel right before) exactly once and is named after its pattern; run as
 //   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d out -- tools/microbench/fetch_calib
-// and divide the buffer size by each kernel's FETCH_SIZE x 1024 (tools/r5_fetch_calib.sh does both).
+// and divide the buffer size by each kernel's FETCH_SIZE x 1024 (the driver script that did both is retired).
 //   wide16     lane l reads the aligned 16-byte piece l of its wave's 1 KB (global_load_dwordx4): the guide's pattern
 //   dword      lane l reads dword l of its wave's 256 bytes (the row loads of convblock_deep.hip, the BatchNorm maps' tails)
 //   bufwide16  wide16 through a raw buffer descriptor (indel_level0.hip's requests)

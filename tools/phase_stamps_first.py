@@ -6,8 +6,6 @@ os.environ.setdefault("MURAL_HIP_FLAVOR", "debug")      # validation hooks / dev
 import sys
 import time
 
-os.environ.setdefault("MURAL_DEBUG_FIRST_CL", "1")      # the channel-last form the composed step runs
-
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -74,11 +74,3 @@ print("distinct CUs:", len(per_cu), "waves per CU:", Counter(len(v) for v in per
 print("waves per (CU, SIMD):", Counter(Counter((c, s_) for c, s_ in zip(cuid.tolist(), ((hw >> 4) & 3).tolist())).values()))
 for c in list(per_cu)[:6]:
     print("  cu %05x:" % c, sorted(per_cu[c]))
-
-raw = stamps.view(2048, 32).cpu()[:512]
-keys, cnts, hw = raw[:, 30].tolist(), raw[:, 31].tolist(), raw[:, 29].tolist()
-print("distinct CU keys:", len(set(keys)), " workgroups per key:", Counter(Counter(keys).values()))
-print("first 12 (block, key, arrival, hw_id):", [(i, hex(keys[i]), cnts[i], hex(hw[i])) for i in range(12)])
-print("blocks 256..262:", [(i, hex(keys[i]), cnts[i], hex(hw[i])) for i in range(256, 262)])
-par = Counter((k, c & 1) for k, c in zip(keys, cnts))
-print("keys with both parities:", sum(1 for k in set(keys) if par[(k, 0)] and par[(k, 1)]))
