@@ -249,33 +249,6 @@ int mural_op_bn_backward(const float* dz, const float* x, int64_t B, int32_t C, 
 int mural_op_conv_wgrad(const float* dy, const float* x, int64_t B, int32_t C, int32_t L, int32_t K,
                         const float* scale, const float* shift, int32_t pre_relu, float* dW, float* db,
                         float* part, size_t part_floats, void* stream);
-/* fp32-MFMA path of the 32->32 k=3 convs on [B][32][L] tensors (L + 2 <= 288): forward / input gradient and weight +
- * bias gradient.  W: PyTorch [32][32][3]; part: mural_op_conv32_wgrad_scratch() floats.  stat_mode 1 / 2: the epilogue
- * also accumulates per-channel sums of the output into the accumulator block stat_out: 1 = sum / sum of
- * squares of act(y) (batch statistics for the next BatchNorm), 2 = sum(y), sum(y * xhat(stat_x)) (BatchNorm backward).  */
-int mural_op_conv32_supported(int32_t L);
-int mural_op_conv32(const float* x, const float* W, const float* bias, float* y, int64_t B, int32_t L, int32_t dgrad,
-                    const float* pre_s, const float* pre_t, int32_t pre_relu, int32_t post_relu, const float* res1,
-                    const float* res2, int32_t stat_mode, int32_t stat_relu, const float* stat_x, const float* stat_mean,
-                    const float* stat_invstd, double* stat_out, void* stream);
-size_t mural_op_conv32_wgrad_scratch(void);
-int mural_op_conv32_wgrad(const float* dy, const float* x, int64_t B, int32_t L, const float* pre_s, const float* pre_t,
-                          int32_t pre_relu, float* dW, float* db, float* part, size_t part_floats, void* stream);
-/* Whole backward of one BN -> conv32 layer in one pass over dy: dW, db, dz = dL/d(conv input) and the BatchNorm-backward
- * sums of dz (accumulator block stat_out, zeroed by the caller; feed it to mural_op_bn_backward with have_sums = 1).      */
-int mural_op_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, int32_t L, const float* pre_s,
-                        const float* pre_t, int32_t pre_relu, const float* mean, const float* invstd, float* dW, float* db,
-                        float* dz, double* stat_out, float* part, size_t part_floats, void* stream);
-/* One call per BN -> conv32 layer and direction (composition of the kernels above).  state: float[4][32] = scale | shift |
- * mean | invstd of this call's batch statistics, written by the forward and read by the backward.                          */
-int mural_op_bnconv32_fwd(const float* x, int64_t B, int32_t L, int32_t pre_relu, double* acc, int32_t have_acc,
-                          const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                          float* running_var, float* state, const float* W, const float* bias, int32_t post_relu,
-                          const float* res1, const float* res2, double* acc_out, int32_t out_relu, float* y, void* stream);
-int mural_op_bnconv32_bwd(const float* dy, const float* x, int64_t B, int32_t L, int32_t pre_relu, const float* state,
-                          const float* gamma, const float* W, double* acc, float* part, size_t part_floats, float* dz,
-                          const float* add1, const float* add2, float* dW, float* db, float* dx, float* dgamma, float* dbeta,
-                          void* stream);
 int mural_op_maxpool_fwd(const float* x, int64_t rows, int32_t L, int32_t k, int32_t s, int32_t p, float* y,
                          int32_t* arg /* argmax positions for the backward; may be NULL (inference) */, void* stream);
 int mural_op_maxpool_bwd_needs_zero(int32_t k, int32_t s);   /* 1: dx must be zeroed by the caller (overlapping windows) */

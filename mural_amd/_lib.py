@@ -103,10 +103,6 @@ PROTOTYPES = {
     "mural_op_bn_apply": (C.c_int, [VP, I64, I32, I32, I32, VP, VP, VP, VP]),
     "mural_op_bn_backward": (C.c_int, [VP, VP, I64, I32, I32, I32, VP, VP, VP, VP, I32, VP, VP, VP, VP, VP, VP]),
     "mural_op_conv_wgrad": (C.c_int, [VP, VP, I64, I32, I32, I32, VP, VP, I32, VP, VP, VP, C.c_size_t, VP]),
-    "mural_op_conv32_supported": (C.c_int, [I32]),
-    "mural_op_conv32": (C.c_int, [VP, VP, VP, VP, I64, I32, I32, VP, VP, I32, I32, VP, VP, I32, I32, VP, VP, VP, VP, VP]),
-    "mural_op_conv32_wgrad_scratch": (C.c_size_t, []),
-    "mural_op_conv32_wgrad": (C.c_int, [VP, VP, I64, I32, VP, VP, I32, VP, VP, VP, C.c_size_t, VP]),
     "mural_op_maxpool_fwd": (C.c_int, [VP, I64, I32, I32, I32, I32, VP, VP, VP]),
     "mural_op_maxpool_bwd_needs_zero": (C.c_int, [I32, I32]),
     "mural_op_maxpool_bwd": (C.c_int, [VP, VP, I64, I32, I32, I32, I32, I32, VP, VP]),
@@ -141,9 +137,6 @@ PROTOTYPES = {
     "mural_op_relayout_multi": (C.c_int, [VP, I32, I64, VP]),
     "mural_op_act_fwd": (C.c_int, [VP, I64, I32, VP, VP]),
     "mural_op_act_bwd": (C.c_int, [VP, VP, I64, I32, VP, VP]),
-    "mural_op_conv32_bwd": (C.c_int, [VP, VP, VP, I64, I32, VP, VP, I32, VP, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
-    "mural_op_bnconv32_fwd": (C.c_int, [VP, I64, I32, I32, VP, I32, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP, I32, VP, VP, VP, I32, VP, VP]),
-    "mural_op_bnconv32_bwd": (C.c_int, [VP, VP, I64, I32, I32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "mural_op_first_plan": (C.c_int, [I32, I32, VP, VP, VP]),
     "mural_op_first_fwd": (C.c_int, [VP, I64, I32, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP, VP, VP]),
     "mural_op_first_bwd": (C.c_int, [VP, VP, VP, I64, I32, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP]),

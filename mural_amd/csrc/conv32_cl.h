@@ -9,7 +9,7 @@ namespace mural {
 
 constexpr int CL_C = 32;
 
-// the same fold of the batch sums into scale / shift / state as conv32_mfma.hip (256 threads, eight loads each)
+// fold of the batch sums into scale / shift / state in a conv kernel's prologue (256 threads, eight loads each)
 struct ClFin {
   const double* acc;
   double n;

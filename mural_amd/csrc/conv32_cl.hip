@@ -2,7 +2,7 @@
 // so a tile of R batch rows is ONE contiguous block of memory whose 16-byte pieces are the 16-byte chunks of the LDS image
 // [column][32 channels] that the prediction kernel uses (mfma_tile.h: XOR-swizzled chunks, ds_read_b128 operands) -- staging,
 // MFMA operand reads and the stream-out move 4 channels per instruction, and per-channel sums ride in registers because a
-// thread always handles the same 4 channels.  (The NCL kernels of conv32_mfma.hip transpose through LDS with 4-byte accesses:
+// thread always handles the same 4 channels.  (The retired first generation worked on [B][32][L] and transposed through LDS with 4-byte accesses:
 // measured there, scatter + stream-out + column sums cost as much as the MFMA phases.)
 //
 //   conv32cl_fwd_kernel : y = conv32(BN(act(x))) [+ bias] [+ res1 + res2] [relu], BatchNorm finalised from the batch sums in the

@@ -54,7 +54,6 @@ const DevSwitch* dev_switch_table() {
     {"MURAL_DEBUG_TOWER_RUNTIME_GEOM", "validation, bit-identical: the first-stage tower instance that reads its geometry from the arguments"},
     {"MURAL_DEBUG_POLY_NARROW", "validation: the polyphase up-conv's dword stores"},
     {"MURAL_DEBUG_FIRST_SCATTER", "validation: the first layer's backward through LDS atomics"},
-    {"MURAL_DEBUG_CONV32_R", "validation: forces the row tile of the tiled conv32 kernels"},
     {"MURAL_DEBUG_S1_ALIAS", "TIMING ONLY, wrong results: every site writes the x0 rows of site (row mod 64)"},
     {"MURAL_DEBUG_FIRST", "TIMING ONLY, wrong results: phases of the training first-layer kernels switched off"},
     {"MURAL_DEBUG_CW", "TIMING ONLY, wrong results: phases of the wave-private conv kernels switched off (bit mask)"},
@@ -256,7 +255,7 @@ int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int3
 using namespace mural;
 
 extern "C" const char* mural_last_error(void) { return mural::last_error_cstr(); }
-extern "C" int mural_abi_version(void) { return 2; }
+extern "C" int mural_abi_version(void) { return 3; }
 
 static int window_geometry(int radius, int indel, int* off, int* width) {
   MURAL_REQUIRE(radius >= 1, "radius must be >= 1, got %d", radius);

@@ -6,7 +6,7 @@
 //                            the caller's workspace.
 // mural_snv_train_backward : gradient of every parameter tensor (written to the caller's buffers, laid out like the parameters)
 //                            from d(loss)/d(output) and that workspace.
-// The host composes the training kernels of train_ops.hip / conv32_mfma.hip / snv_stage1.hip here in C++, so a non-Python host needs
+// The host composes the training kernels of train_ops.hip / conv32_wave.hip / conv32_cl.hip / snv_stage1.hip here in C++, so a non-Python host needs
 // nothing but these two calls, an optimiser and a loss.  Parameters are DEVICE pointers in the reference's state_dict naming
 // (the MuralSnvParams structs of the eval path, here with device addresses).
 #include <algorithm>
@@ -58,7 +58,7 @@ int train_first_fwd_cl_prepared(const uint8_t* sym, int64_t B, int Lwin, int col
 int train_first_bwd_cl(const float* dy, const void* arg, const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp,
                        const float* tab, const float* W, float* scratch, float* dW, float* dbias, float* dgamma, float* dbeta,
                        const FirstFold* fold, hipStream_t stream);
-// conv32_mfma.hip
+// conv32_reduce.hip
 int train_reduce_parts(const float* const* part, const int* nrow, float* const* dW, float* const* db, int njobs, hipStream_t stream);
 // train_ops.hip
 int train_bn2d_apply_dropout(const float* x, int64_t B, int C, int relu, const double* acc, const float* gamma, const float* beta, float eps,

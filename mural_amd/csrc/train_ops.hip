@@ -192,18 +192,6 @@ __global__ __launch_bounds__(256) void bn2d_apply_dropout_kernel(const float* __
   }
 }
 
-// dc3[b][c][l] = (l == arg[b][c] && c3[b][c][l] > 0) ? dfeat[b][c] : 0: backward of the global max over columns and of the ReLU
-// in front of it (model_snv.py:487-489) in one pass
-__global__ void gmax_relu_bwd_kernel(const float* __restrict__ dfeat, const int32_t* __restrict__ arg, const float* __restrict__ c3,
-                                     int64_t rows, int L, float* __restrict__ dx) {
-  const int64_t total = rows * L;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / L;
-    const int l = (int)(i - r * L);
-    dx[i] = (arg[r] == l && c3[i] > 0.f) ? dfeat[r] : 0.f;
-  }
-}
-
 // sums over (B, L) of dz and dz * xhat per channel
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dz, const float* __restrict__ x, int B,
                                                             int C, int L, int relu, const float* __restrict__ mean,
@@ -1220,7 +1208,7 @@ extern "C" int mural_op_bn_apply(const float* x, int64_t B, int32_t C, int32_t L
 }
 
 // BatchNorm (batch statistics) backward.  acc: accumulator block; have_sums == 0: zeroed by the caller and reduced here,
-// != 0: already holds sum(dz) / sum(dz * xhat) (taken by the producer of dz, mural_op_conv32 stat_mode 2).  Writes dx (+ the optional
+// != 0: already holds sum(dz) / sum(dz * xhat) (taken by the kernel that produced dz).  Writes dx (+ the optional
 // add1 / add2 tensors: gradients arriving at x through residual connections), dgamma, dbeta.
 extern "C" int mural_op_bn_backward(const float* dz, const float* x, int64_t B, int32_t C, int32_t L, int32_t relu,
                                     const float* mean, const float* invstd, const float* gamma, double* acc,
@@ -1730,13 +1718,6 @@ int train_bn2d_apply_dropout(const float* x, int64_t B, int C, int relu, const d
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }
-
-int train_gmax_relu_bwd(const float* dfeat, const int32_t* arg, const float* c3, int64_t rows, int L, float* dx, hipStream_t stream) {
-  if (rows * L == 0) return MURAL_OK;
-  hipLaunchKernelGGL(gmax_relu_bwd_kernel, dim3(grid_for(rows * L)), dim3(256), 0, stream, dfeat, arg, c3, rows, L, dx);
-  MURAL_HIP_CHECK(hipGetLastError());
-  return MURAL_OK;
-}
 }  // namespace mural
 
 #include "snv_local_train.h"      // the local branch of the composed training step in three launches per direction
@@ -1746,44 +1727,4 @@ namespace mural { int launch_dense_to_symbols(const float* x, int64_t n, int L, 
 // dense (n,4,L) MuRaL encoding -> 1 symbol per column (status: see mural_snv_forward_dense)
 extern "C" int mural_op_dense_to_symbols(const float* x, int64_t n, int32_t L, uint8_t* sym, int32_t* status, void* stream) {
   return mural::launch_dense_to_symbols(x, n, L, sym, status, STREAM);
-}
-
-// ------------------------------------------------------------------------------------------- composed layer calls
-// One host call per BN -> conv32 layer and direction (the kernels are the ones above / in conv32_mfma.hip; composing them
-// here keeps the Python glue at one ctypes transition per layer, which matters once the step is launch-bound).
-extern "C" int mural_op_conv32(const float* x, const float* W, const float* bias, float* y, int64_t B, int32_t L, int32_t dgrad,
-                               const float* pre_s, const float* pre_t, int32_t pre_relu, int32_t post_relu, const float* res1,
-                               const float* res2, int32_t stat_mode, int32_t stat_relu, const float* stat_x,
-                               const float* stat_mean, const float* stat_invstd, double* stat_out, void* stream);
-extern "C" int mural_op_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, int32_t L, const float* pre_s,
-                                   const float* pre_t, int32_t pre_relu, const float* mean, const float* invstd, float* dW,
-                                   float* db, float* dz, double* stat_out, float* part, size_t part_floats, void* stream);
-
-// forward: batch statistics (taken here unless acc already holds them) -> scale / shift / mean / invstd (state: float[4][32],
-// kept for the backward) + running statistics -> y = conv32(scale * act(x) + shift) [+ bias] [relu] [+ res1 + res2],
-// optionally with the batch sums of act'(y) for the next layer (acc_out)
-extern "C" int mural_op_bnconv32_fwd(const float* x, int64_t B, int32_t L, int32_t pre_relu, double* acc, int32_t have_acc,
-                                     const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                                     float* running_var, float* state, const float* W, const float* bias, int32_t post_relu,
-                                     const float* res1, const float* res2, double* acc_out, int32_t out_relu, float* y,
-                                     void* stream) {
-  if (!have_acc)
-    if (int rc = mural_op_bn_stats(x, B, 32, L, pre_relu, acc, stream)) return rc;
-  if (int rc = mural_op_bn_finalize(acc, (double)B * L, 32, gamma, beta, eps, momentum, running_mean, running_var, state,
-                                    state + 32, state + 64, state + 96, stream))
-    return rc;
-  return mural_op_conv32(x, W, bias, y, B, L, 0, state, state + 32, pre_relu, post_relu, res1, res2, acc_out ? 1 : 0, out_relu,
-                         nullptr, nullptr, nullptr, acc_out, stream);
-}
-
-// backward of the same layer: dW, db, then dx = BatchNorm backward of dz (+ add1 + add2), dgamma, dbeta.  dz: scratch [B][32][L]
-extern "C" int mural_op_bnconv32_bwd(const float* dy, const float* x, int64_t B, int32_t L, int32_t pre_relu, const float* state,
-                                     const float* gamma, const float* W, double* acc, float* part, size_t part_floats, float* dz,
-                                     const float* add1, const float* add2, float* dW, float* db, float* dx, float* dgamma,
-                                     float* dbeta, void* stream) {
-  if (int rc = mural_op_conv32_bwd(dy, x, W, B, L, state, state + 32, pre_relu, state + 64, state + 96, dW, db, dz, acc, part,
-                                   part_floats, stream))
-    return rc;
-  return mural_op_bn_backward(dz, x, B, 32, L, pre_relu, state + 64, state + 96, gamma, acc, 1, add1, add2, dx, dgamma, dbeta,
-                              stream);
 }

@@ -266,11 +266,11 @@ def _unet_forward_train(model, x):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# SNV towers of any width / kernel size (the MFMA training kernels of train_ops.py serve the shipped 32-channel, k=3 shape)
+# SNV towers of any width / kernel size (the shipped 32-channel, k=3 shape trains through the composed C step: train_step.py)
 # ------------------------------------------------------------------------------------------------------------------
 def snv_tower_forward_train(mod, sfx, x, pools, dropout_p):
     """One conv tower of Network1/2 (model_snv.py:473-493 / :496-513) in training mode from the dense (B, 4, L) window, on the
-    general per-layer ops.  Same layer order as ``train_ops.tower_forward``."""
+    general per-layer ops."""
     g = lambda n: getattr(mod, n + sfx)          # noqa: E731
 
     def bnconv(t, seq, pre_relu=False):

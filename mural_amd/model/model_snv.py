@@ -7,8 +7,10 @@ checkpoints load with ``load_state_dict(strict=True)``.
 
 The torch sub-modules here are *parameter containers only*: ``forward`` never runs them.  In eval mode it hands
 the raw parameters to ``libmural_hip.so`` (which folds BN statistics, builds the first-layer 3-mer tables and the
-MFMA weight fragments) and launches the fused kernels on the current HIP stream; in training mode it composes the
-per-op HIP kernels of ``train_ops.py`` under autograd (batch-statistics BatchNorm, dropout, every backward).
+MFMA weight fragments) and launches the fused kernels on the current HIP stream; in training mode the shipped shape
+(32 channels, kernel 3) runs the composed C step (``train_step.py`` over ``csrc/snv_train.hip``: one call per direction),
+every other shape the per-layer HIP ops of ``indel_train.py`` / ``train_ops.py`` under autograd (batch-statistics
+BatchNorm, dropout, every backward).
 There is no CPU path.
 """
 import ctypes as C
@@ -538,14 +540,8 @@ def _shape(model_no, n_class, local_cols=0, emb_rows=0, h1=0, h2=0, channels=32,
 
 
 def _train_towers(mod, distal_x):
-    """(mid, large) tower logits in training mode: the MFMA / table kernels for the shipped 32-channel k=3 shape, the general
-    per-layer ops (indel_train.py) for any other CNN_out_channels / CNN_kernel_size."""
-    from . import train_ops as T
-    if mod.out_channels == 32 and mod.kernel_size == 3:
-        sym = T.dense_to_symbols(distal_x)
-        mid = T.tower_forward(mod, "", sym, mod.seq_len // 2 - 100, 201, POOLS_MID, mod.distal_fc1[1].p)
-        large = T.tower_forward(mod, "_2", sym, 0, mod.seq_len, POOLS_LARGE, mod.distal_fc2[1].p)
-        return mid, large
+    """(mid, large) tower logits in training mode on the general per-layer ops (indel_train.py): the route of every
+    CNN_out_channels / CNN_kernel_size that the composed C step (train_step.supported) does not serve."""
     from .indel_train import snv_tower_forward_train
     x = distal_x.to(torch.float32)
     L = x.shape[2]

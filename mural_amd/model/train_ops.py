@@ -46,10 +46,6 @@ def _bn_acc(Cn, device):
     return _arena.take(BN_SLOTS * 2 * Cn, device).view(BN_SLOTS, 2, Cn)
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 _fn_cache = {}
 _Tensor = torch.Tensor
 
@@ -116,93 +112,6 @@ class _BnState:
         _bn_tick(bn)
 
 
-_part_cache = {}
-
-
-def _wgrad_part(device):
-    """Scratch for the per-workgroup weight-gradient partial rows (written and consumed inside one backward call)."""
-    t = _part_cache.get(device)
-    if t is None:
-        t = _part_cache[device] = torch.empty(int(_lib.lib().mural_op_conv32_wgrad_scratch()), dtype=torch.float32, device=device)
-    return t
-
-
-class BnConv(torch.autograd.Function):
-    """y = Conv1d(BN(act(x))) [+ ReLU] [+ res1 + res2], act = ReLU or identity, 32->32 channels, k=3, pad=1.
-
-    ``stats_in``: batch sums of act(x) taken by the producer of x (skips the statistics pass); ``stats_out`` (None / False /
-    True): also return the batch sums of y (True: of relu(y)) for the BatchNorm that consumes y, taken in the conv epilogue.
-    Returns (y, sums or an empty tensor).  The 32-channel MFMA path is one C call per direction."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, weight, bias, res1, res2, bn, pre_relu, post_relu, stats_in=None, stats_out=None):
-        x = x.contiguous()
-        B, Cn, L = x.shape
-        dev = x.device
-        st = _stream(x)
-        y = torch.empty((B, weight.shape[0], L), dtype=torch.float32, device=dev)
-        mfma = tuple(weight.shape) == (32, 32, 3) and bool(_lib.lib().mural_op_conv32_supported(L))
-        want = stats_out is not None
-        acc_out = _bn_acc(weight.shape[0], dev) if want else torch.empty(0, dtype=torch.float32, device=dev)
-        if mfma:      # fp32 MFMA implicit GEMM (csrc/conv32_mfma.hip)
-            state = torch.empty((4, Cn), dtype=torch.float32, device=dev)
-            acc = stats_in if stats_in is not None else _bn_acc(Cn, dev)
-            _call("mural_op_bnconv32_fwd", x, B, L, int(pre_relu), acc, int(stats_in is not None), _f32(bn.weight), _f32(bn.bias),
-                  EPS, MOMENTUM, bn.running_mean, bn.running_var, state, _f32(weight), _f32(bias), int(post_relu), _p(res1),
-                  _p(res2), acc_out if want else None, int(bool(stats_out)), y, st)
-            _bn_tick(bn)
-        else:         # generic direct conv (csrc/conv1d.hip)
-            bs = _BnState(x, pre_relu, bn, L, stats_in)
-            state = torch.stack([bs.scale, bs.shift, bs.mean, bs.invstd])
-            wt = torch.empty_like(weight)
-            _call("mural_op_relayout", _f32(weight), wt, weight.shape[0], weight.shape[1], weight.shape[2], 0, st)
-            _call("mural_op_conv1d", x, wt, _f32(bias), y, B, Cn, weight.shape[0], L, weight.shape[2], state[0], state[1],
-                  int(pre_relu), int(post_relu), _p(res1), _p(res2), st)
-            if want:
-                _call("mural_op_bn_stats", y, B, weight.shape[0], L, int(bool(stats_out)), acc_out, st)
-        ctx.save_for_backward(x, gamma, weight, y if post_relu else None, state)
-        ctx.flags = (pre_relu, post_relu, res1 is not None, res2 is not None, mfma)
-        ctx.mark_non_differentiable(acc_out)
-        return y, acc_out
-
-    @staticmethod
-    def backward(ctx, dy, _dacc):
-        x, gamma, weight, y, state = ctx.saved_tensors
-        pre_relu, post_relu, has_r1, has_r2, mfma = ctx.flags
-        dy = dy.contiguous()
-        B, Cn, L = x.shape
-        dev = x.device
-        st = _stream(x)
-        dres = dy
-        if post_relu:
-            g = torch.empty_like(dy)
-            _call("mural_op_relu_mask", dy, y, dy.numel(), g, st)
-            dy = g
-        dW = torch.empty_like(weight)
-        small = torch.empty((3, Cn), dtype=torch.float32, device=dev)          # db | dgamma | dbeta
-        db, dgamma, dbeta = small[0], small[1], small[2]
-        dz = torch.empty_like(x)
-        dx = torch.empty_like(x)
-        acc = _bn_acc(Cn, dev)
-        if mfma:      # one pass over dy: weight / bias gradient, input gradient, BatchNorm-backward sums; then the BN backward
-            part = _wgrad_part(dev)
-            _call("mural_op_bnconv32_bwd", dy, x, B, L, int(pre_relu), state, _f32(gamma), _f32(weight), acc, part, part.numel(),
-                  dz, None, None, dW, db, dx, dgamma, dbeta, st)
-        else:
-            scale, shift, mean, invstd = state[0], state[1], state[2], state[3]
-            wt = torch.empty_like(weight)
-            part = torch.empty(1024 * (weight.numel() + weight.shape[0]), dtype=torch.float32, device=dev)
-            _call("mural_op_conv_wgrad", dy, x, B, Cn, L, weight.shape[2], scale, shift, int(pre_relu), dW, db, part,
-                  part.numel(), st)
-            _call("mural_op_relayout", _f32(weight), wt, weight.shape[0], weight.shape[1], weight.shape[2], 1, st)
-            _call("mural_op_conv1d", dy, wt, None, dz, B, weight.shape[0], Cn, L, weight.shape[2], None, None, 0, 0, None, None,
-                  st)
-            _call("mural_op_bn_backward", dz, x, B, Cn, L, int(pre_relu), mean, invstd, _f32(gamma), acc, 0, None, None, dx,
-                  dgamma, dbeta, st)
-        return (dx, dgamma, dbeta, dW, db, (dres if has_r1 else None), (dres if has_r2 else None), None, None, None, None,
-                None)
-
-
 class Bn2d(torch.autograd.Function):
     """y = BN(act(x)) on (B, C) features (batch statistics over B)."""
 
@@ -264,46 +173,6 @@ def _first_plan(Cn, pk):
     t, a, s = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     _lib.check(_lib.lib().mural_op_first_plan(Cn, pk, C.byref(t), C.byref(a), C.byref(s)))
     return t.value, a.value, s.value
-
-
-class FirstLayerPool(torch.autograd.Function):
-    """maxpool1(Conv1d(BN(one-hot))) of one tower from window symbols: 3-mer / per-tap symbol tables rebuilt from the batch
-    statistics of this step, arg-max saved (one byte per pooled output on the table path)."""
-
-    @staticmethod
-    def forward(ctx, sym, gamma, beta, weight, bias, bn, col0, L1, pool):
-        B, Lwin = sym.shape
-        Cn = weight.shape[0]
-        pk, ps, pp = pool
-        L2 = (L1 + 2 * pp - pk) // ps + 1
-        dev = sym.device
-        tab_floats, arg_bytes, _ = _first_plan(Cn, pk)
-        counts = torch.zeros(16, dtype=torch.int64, device=dev)
-        tab = torch.empty(tab_floats, dtype=torch.float32, device=dev)
-        y = torch.empty((B, Cn, L2), dtype=torch.float32, device=dev)
-        arg = torch.empty(B * Cn * L2 * arg_bytes, dtype=torch.uint8, device=dev)
-        _call("mural_op_first_fwd", sym, B, Lwin, col0, L1, Cn, pk, ps, pp, _f32(gamma), _f32(beta), _f32(weight), _f32(bias),
-              EPS, MOMENTUM, bn.running_mean, bn.running_var, counts, tab, y, arg, _stream(sym))
-        _bn_tick(bn)
-        ctx.save_for_backward(sym, arg, tab, weight)
-        ctx.dims = (col0, L1, pool)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        sym, arg, tab, weight = ctx.saved_tensors
-        col0, L1, (pk, ps, pp) = ctx.dims
-        B, Lwin = sym.shape
-        Cn = weight.shape[0]
-        dev = sym.device
-        scratch = torch.empty(_first_plan(Cn, pk)[2], dtype=torch.float32, device=dev)
-        dW = torch.empty_like(weight)
-        db = torch.empty(Cn, dtype=torch.float32, device=dev)
-        dgamma = torch.empty(4, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(4, dtype=torch.float32, device=dev)
-        _call("mural_op_first_bwd", dy.contiguous(), arg, sym, B, Lwin, col0, L1, Cn, pk, ps, pp, tab, _f32(weight), scratch, dW,
-              db, dgamma, dbeta, _stream(sym))
-        return None, dgamma, dbeta, dW, db, None, None, None, None
 
 
 class Linear(torch.autograd.Function):
@@ -456,38 +325,6 @@ def flush_input_checks():
 # ---------------------------------------------------------------------------------------------------------------
 # model composition (training mode)
 # ---------------------------------------------------------------------------------------------------------------
-def tower_forward(mod, sfx, sym, col0, L1, pools, dropout_p, training=True):
-    g = lambda n: getattr(mod, n + sfx)
-    bn_in, conv_in = g("conv1")[0], g("conv1")[1]
-    x0 = FirstLayerPool.apply(sym, bn_in.weight, bn_in.bias, conv_in.weight, conv_in.bias, bn_in, col0, L1, pools[0])
-
-    def bnconv(x, bn, conv, res1=None, res2=None, pre_relu=True, post_relu=False, stats_in=None, stats_out=None):
-        y, acc = BnConv.apply(x, bn.weight, bn.bias, conv.weight, conv.bias, res1, res2, bn, pre_relu, post_relu, stats_in,
-                              stats_out)
-        return y, (acc if stats_out is not None else None)
-
-    def res_blocks(rbs, x_in, st_in):
-        # every conv takes the batch sums of relu(its output) in its epilogue for the BatchNorm of the next layer
-        rb0, rb1 = rbs[0], rbs[1]
-        h, st = bnconv(x_in, rb0.bn1, rb0.conv1, stats_in=st_in, stats_out=True)
-        x1, st = bnconv(h, rb0.bn2, rb0.conv2, res1=x_in, stats_in=st, stats_out=True)
-        h, st = bnconv(x1, rb1.bn1, rb1.conv1, stats_in=st, stats_out=True)
-        # second block's own residual (x1) plus the outer skip (x_in), model_snv.py:477-479
-        return bnconv(h, rb1.bn2, rb1.conv2, res1=x1, res2=x_in, stats_in=st)[0]
-
-    y = res_blocks(g("RBs1"), x0, None)
-    p2 = MaxPool.apply(y, *pools[1])
-    x0b, st = bnconv(p2, g("conv2")[0], g("conv2")[1], pre_relu=False, stats_out=True)
-    y = res_blocks(g("RBs2"), x0b, st)
-    p3 = MaxPool.apply(y, *pools[2])
-    c3 = bnconv(p3, g("conv3")[0], g("conv3")[1], pre_relu=False, post_relu=True)[0]
-    feat = MaxPool.apply(c3, None, None, None)
-    fc = mod.distal_fc1 if sfx == "" else mod.distal_fc2
-    f = Bn2d.apply(feat, fc[0].weight, fc[0].bias, fc[0], False)
-    f = dropout(f, dropout_p, training)
-    return Linear.apply(f, fc[2].weight, fc[2].bias)
-
-
 def local_forward(mod, cat, out_layer, emb_p, lin_ps, training=True):
     h = Embedding.apply(cat, mod.emb_layer.weight)
     h = dropout(h, emb_p, training)

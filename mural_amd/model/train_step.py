@@ -3,7 +3,8 @@
 ``loss.backward()`` of the reference (MuRaL/training.py:424-427) walks ~120 autograd nodes; here the whole model forward is one
 ``torch.autograd.Function`` whose forward and backward are one library call each -- the composition of the ~100 kernels per
 direction lives in C++ (csrc/snv_train.hip), so the host costs two ctypes transitions per step instead of one per layer.
-Serves the shipped shape (32 channels, kernel 3); other shapes train on the per-layer ops of ``train_ops.py`` / ``indel_train.py``.
+Serves Network0 and the shipped tower shape (32 channels, kernel 3); towers of any other shape train on the per-layer ops of
+``indel_train.py`` (``snv_tower_forward_train``) with the local branch and the head from ``train_ops.py``.
 
 Gradients: the C backward writes every parameter gradient into ONE flat buffer.  By default the node then sets ``p.grad`` itself
 -- views of a buffer that lives with the model, created once -- and hands autograd nothing: routing ~150 tensors through the engine

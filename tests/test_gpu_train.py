@@ -539,18 +539,6 @@ def test_eval_after_graph_replays_uses_current_weights():
     assert np.abs(np.exp(outs[0]) - np.exp(outs[1])).max() > 1e-4
 
 
-def test_conv32_kernels_match_torch_fp64():
-    """The MFMA conv kernels behind the training step (forward with pre-op / residuals / fused batch sums, input gradient
-    with BatchNorm-backward sums, weight gradient, fused backward) against torch ops in float64 on the CPU, over full,
-    partial and single-row tiles."""
-    import subprocess
-    import sys
-    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "gpu_debug_conv32.py")
-    out = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "worst" in out.stdout
-
-
 def test_channel_last_conv_kernels_match_torch_fp64():
     """The channel-last [B][L][32] conv kernels the composed step runs on (csrc/conv32_cl.hip): forward with BatchNorm finalisation,
     residuals and fused batch sums; backward with weight / bias gradient, input gradient and BatchNorm-backward sums, with and
