@@ -76,6 +76,27 @@ int mural_encode_onehot(const MuralGenome* g, const int64_t* pos, const uint8_t*
 int mural_encode_symbols(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n, int32_t radius,
                          int32_t indel, uint8_t* out, void* stream);
 
+/* Site enumeration (csrc/sites.hip; no reference counterpart -- its users write one BED row per site with scripts of their own):
+ * the positions of the window [lo, hi) of the record (0-based half-open like a BED row, clamped to the record) that a prediction run
+ * takes as sites, in ascending order, as the (pos, strand) pairs the encoders and the packed forwards take.
+ *   focal A:   base exactly A ('+', strand 0) or exactly T ('-', strand 1);
+ *   focal C:   base exactly C ('+') or exactly G ('-'); context CPG keeps a '+' site whose NEXT base in the record is exactly G and a
+ *              '-' site whose PREVIOUS base is exactly C, NONCPG keeps the others (a neighbour beyond the record's ends, or one that is
+ *              N or an IUPAC code, makes the site non-CpG; a neighbour outside [lo, hi) counts like any other);
+ *   focal ANY: every base that is exactly A, C, G or T, on '+' (INDEL models).
+ * A base whose nmask bit is set (N and every entry of the IUPAC side table) is never a site.  Contexts other than ALL need focal C.
+ * mural_sites_count leaves tile_counts[t] = sites before tile t, tile_counts[tiles] = *total = all sites of the window (dev int64
+ * [mural_sites_tiles(length, lo, hi) + 1] and dev int64 [1]); mural_sites_emit, given the same window and selection and those
+ * offsets, writes the sites number first .. first + n - 1 of the enumeration (the caller keeps first + n <= total) to pos / strand
+ * (dev, n entries each).  Deterministic: no atomics.                                                                              */
+enum { MURAL_FOCAL_A = 0, MURAL_FOCAL_C = 1, MURAL_FOCAL_ANY = 2 };
+enum { MURAL_CONTEXT_ALL = 0, MURAL_CONTEXT_CPG = 1, MURAL_CONTEXT_NONCPG = 2 };
+int64_t mural_sites_tiles(int64_t length, int64_t lo, int64_t hi);
+int mural_sites_count(const MuralGenome* g, int64_t lo, int64_t hi, int32_t focal, int32_t context, int64_t* tile_counts,
+                      int64_t* total, void* stream);
+int mural_sites_emit(const MuralGenome* g, int64_t lo, int64_t hi, int32_t focal, int32_t context, const int64_t* tile_counts,
+                     int64_t first, int64_t n, int64_t* pos, uint8_t* strand, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SNV model family (Network0 / Network1 / Network2, MuRaL/model/model_snv.py:19-525), eval mode.
  * Raw parameters are handed over as HOST pointers in the reference's state_dict naming; the library

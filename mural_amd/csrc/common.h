@@ -168,6 +168,39 @@ struct SideStreamHold {
 };
 
 // ---------------------------------------------------------------------------------------------
+// prefix sums of per-thread counts (tables.hip: rows of a text chunk; sites.hip: sites of a genome tile)
+// ---------------------------------------------------------------------------------------------
+constexpr int SCAN_THREADS = 256;
+
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int u = __shfl_up(v, off, 64);
+    if (lane >= off) v += u;
+  }
+  return v;
+}
+
+// exclusive prefix of `v` over the block (256 threads = 4 waves); *total = the block's sum
+__device__ __forceinline__ int block_excl_scan(int v, int* total) {
+  __shared__ int wave_tot[SCAN_THREADS / 64];
+  const int incl = wave_incl_scan(v);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wave_tot[w] = incl;
+  __syncthreads();
+  int base = 0, sum = 0;
+#pragma unroll
+  for (int k = 0; k < SCAN_THREADS / 64; ++k) {
+    base += k < w ? wave_tot[k] : 0;
+    sum += wave_tot[k];
+  }
+  __syncthreads();
+  *total = sum;
+  return base + incl - v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // packed genome access
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t genome_sym(const uint32_t* __restrict__ packed2,

@@ -49,33 +49,7 @@ struct ChunkMeta {
   unsigned long long n_runs;
 };
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  return v;
-}
-
-// exclusive prefix of `v` over the block (256 threads = 4 waves); *total = the block's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* total) {
-  __shared__ int wave_tot[TB_THREADS / 64];
-  const int incl = wave_incl_scan(v);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 63) wave_tot[w] = incl;
-  __syncthreads();
-  int base = 0, sum = 0;
-#pragma unroll
-  for (int k = 0; k < TB_THREADS / 64; ++k) {
-    base += k < w ? wave_tot[k] : 0;
-    sum += wave_tot[k];
-  }
-  __syncthreads();
-  *total = sum;
-  return base + incl - v;
-}
+static_assert(TB_THREADS == SCAN_THREADS, "block_excl_scan (common.h) is written for 256-thread blocks");
 
 __device__ __forceinline__ int count_newlines(const char* __restrict__ buf, int64_t len, int64_t p0) {
   int c = 0;

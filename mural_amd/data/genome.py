@@ -42,6 +42,40 @@ def pack_sequence(seq):
     return packed, mask, n, (amb, codes[amb].astype(np.uint8))
 
 
+_FOCAL = {"A": 0, "C": 1, "ANY": 2}                    # MURAL_FOCAL_* of include/mural_hip.h
+_CONTEXT = {"all": 0, "cpg": 1, "noncpg": 2}           # MURAL_CONTEXT_*
+
+
+def site_selection(focal, context="all"):
+    """(MURAL_FOCAL_*, MURAL_CONTEXT_*) of a site selection: focal 'A' (A/T sites), 'C' (C/G sites) or 'ANY' (every A/C/G/T position,
+    INDEL models); context 'all', 'CpG' or 'nonCpG' (any case; focal 'C' only).  Raises ValueError."""
+    f, c = _FOCAL.get(str(focal).upper()), _CONTEXT.get(str(context).lower())
+    if f is None:
+        raise ValueError(f"focal must be 'A', 'C' or 'ANY', got {focal!r}")
+    if c is None:
+        raise ValueError(f"context must be 'all', 'CpG' or 'nonCpG', got {context!r}")
+    if c != 0 and f != 1:
+        raise ValueError(f"context {context!r} needs focal 'C' (got focal {focal!r})")
+    return f, c
+
+
+class SiteScan:
+    """The counting pass of a site enumeration (``PackedGenome.scan_sites``): the window, the selection, the per-tile offsets and
+    the total, all on the device; ``total`` reads the count back (one synchronisation, cached)."""
+
+    __slots__ = ("lo", "hi", "focal", "context", "offsets", "total_dev", "_total")
+
+    def __init__(self, lo, hi, focal, context, offsets, total_dev):
+        self.lo, self.hi, self.focal, self.context, self.offsets, self.total_dev = lo, hi, focal, context, offsets, total_dev
+        self._total = None
+
+    @property
+    def total(self):
+        if self._total is None:
+            self._total = int(self.total_dev.item())
+        return self._total
+
+
 class SymbolWindows:
     """Sequence windows as one symbol per column (``PackedGenome.encode_symbols``): ``sym`` is a uint8 (n, W) device tensor of
     MURAL_SYM_* codes (0..14).  Only the encoder makes these -- the kernels index tables with the bytes unchecked."""
@@ -141,3 +175,52 @@ class PackedGenome:
                                                      int(model_type == "indel"), out.data_ptr(),
                                                      _lib.current_stream_ptr(self.device)))
         return out
+
+    # ------------------------------------------------------------------------------------------------
+    # site enumeration (csrc/sites.hip): the sites of a window straight from the resident genome, no BED file
+    def scan_sites(self, lo, hi, focal, context="all"):
+        """Count the sites of the window [lo, hi) (0-based half-open, clamped to the record) on the device: a ``SiteScan`` for
+        ``emit_sites``.  Nothing is read back."""
+        f, c = site_selection(focal, context)
+        lo, hi = int(lo), int(hi)
+        lib = _lib.lib()
+        tiles = int(lib.mural_sites_tiles(self.length, lo, hi))
+        offsets = torch.empty(tiles + 1, dtype=torch.int64, device=self.device)
+        total = torch.empty(1, dtype=torch.int64, device=self.device)
+        g = self.as_struct()
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mural_sites_count(C.byref(g), lo, hi, f, c, offsets.data_ptr(), total.data_ptr(),
+                                             _lib.current_stream_ptr(self.device)))
+        return SiteScan(lo, hi, f, c, offsets, total)
+
+    def emit_sites(self, scan, first, n, pos=None, strand=None):
+        """Sites number first .. first + n - 1 of a scan (the caller keeps first + n <= scan.total) as (pos int64, strand uint8)
+        device tensors -- freshly allocated, or the given n-entry contiguous ones."""
+        first, n = int(first), int(n)
+        if pos is None:
+            pos = torch.empty(n, dtype=torch.int64, device=self.device)
+            strand = torch.empty(n, dtype=torch.uint8, device=self.device)
+        elif (pos.shape != (n,) or strand.shape != (n,) or pos.dtype != torch.int64 or strand.dtype != torch.uint8
+              or not pos.is_contiguous() or not strand.is_contiguous() or pos.device != self.device or strand.device != self.device):
+            raise ValueError("emit_sites: pos / strand must be contiguous int64 / uint8 device tensors of n entries")
+        g = self.as_struct()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mural_sites_emit(C.byref(g), scan.lo, scan.hi, scan.focal, scan.context, scan.offsets.data_ptr(),
+                                                  first, n, pos.data_ptr(), strand.data_ptr(), _lib.current_stream_ptr(self.device)))
+        return pos, strand
+
+    def count_sites(self, lo, hi, focal, context="all"):
+        """Number of sites ``enumerate_sites`` yields for the window."""
+        return self.scan_sites(lo, hi, focal, context).total
+
+    def enumerate_sites(self, lo, hi, focal, context="all", first=0, n=None):
+        """The sites of the window [lo, hi) of the record (0-based half-open like a BED row, clamped to the record) in ascending
+        position order: (pos int64, strand uint8) device tensors in the coordinate the encoders and the packed forwards take for a
+        BED row (p, p + 1).  focal 'A': A ('+', 0) and T ('-', 1); 'C': C ('+') and G ('-'), with context 'CpG' / 'nonCpG' decided by
+        the next ('+') or previous ('-') base of the record; 'ANY': every A/C/G/T position on '+'.  N and IUPAC codes are never sites.
+        `first` / `n`: a contiguous slice of the enumeration (clamped to it; n=None: to its end)."""
+        scan = self.scan_sites(lo, hi, focal, context)
+        first = max(int(first), 0)
+        left = max(scan.total - first, 0)
+        n = left if n is None else min(max(int(n), 0), left)
+        return self.emit_sites(scan, first, n)

@@ -9,6 +9,7 @@ and covered by world_size-2 gloo tests on CPU; the compute function is the HIP m
 import ctypes as C
 import os
 import queue
+import re
 import threading
 import time
 
@@ -924,13 +925,13 @@ class _ShardTail:
         elif int(host[0]) != 0:
             raise ValueError(_FOCAL_MSG)
 
-    def __call__(self, chrom, runs, full, start, end, strand, label, grp, file_rows=None):
+    def __call__(self, chrom, runs, full, start, end, strand, label, grp, file_rows=None, check_focal=True):
         """`full`: (n, k + 1) probabilities + focal base; `grp`: non-decreasing group ids; `runs`: [(lo, hi)] positions of the shard's
         rows in the whole input's bed_reader order; `file_rows`: file row index per row (rank-local ingest) or None."""
         n, k = full.shape[0], full.shape[1] - 1
         dev = self.dev
         if dev is not None:
-            if self.model_type == "snv":
+            if self.model_type == "snv" and check_focal:
                 status = torch.zeros(1, dtype=torch.int32, device=dev)
                 with torch.cuda.device(dev):
                     _lib.check(_lib.lib().mural_focal_group_check(full.data_ptr(), int(full.dtype == torch.float64), full.stride(0), k,
@@ -949,7 +950,7 @@ class _ShardTail:
         else:
             full = full.cpu().numpy() if isinstance(full, torch.Tensor) else np.asarray(full)
             as_np = lambda a: a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)       # noqa: E731
-            if self.model_type == "snv":
+            if self.model_type == "snv" and check_focal:
                 check_focal_groups(full[:, -1].astype(np.int64), as_np(grp))
             shard = {"chrom": chrom, "start": as_np(start), "end": as_np(end), "strand": as_np(strand), "label": as_np(label),
                      "prob": full[:, :-1], "n_class": k, "calibrated": self.calibrated}
@@ -968,15 +969,16 @@ class _ShardTail:
     # check looks across blocks: a (segment, strand) group that straddles a block border must agree on both sides.  Every rank checks its
     # own groups, the ranks exchange 7 numbers -- rows, first / last segment, focal base of the '+' and the '-' group of each (-1: none) --
     # and every rank walks the chain (verdict read one shard late, like the gathered shards').  No all-gather of rows, no sort of n rows.
-    def aligned_part(self, chrom, local, start, end, strand, label, anchor, central_bp):
+    def aligned_part(self, chrom, local, start, end, strand, label, anchor, central_bp, check_focal=True):
         """One PART of this rank's block of an aligned chromosome (the block goes through in parts of <= _ALIGNED_PART_ROWS rows, in file
         order: the table writer works on one part while the next is computed, and host / device memory is bounded by a part).  `local`:
         (m, k + 1) probabilities + focal base, start / strand / end / label: the part's site columns.  Returns the part's border record
-        for ``aligned_close`` (None for models without the focal-base rule)."""
+        for ``aligned_close`` (None for models without the focal-base rule, and with check_focal=False: the region driver's sites
+        are chosen BY their base, see predict_regions_sharded)."""
         m, k = local.shape[0], local.shape[1] - 1
         dev = self.dev
         info = None
-        if self.model_type == "snv":
+        if self.model_type == "snv" and check_focal:
             e0 = (anchor if anchor is not None else 1) + central_bp
             if dev is not None:
                 seg = torch.where(start > e0, (start - e0 + (central_bp - 1)) // central_bp, torch.zeros_like(start))
@@ -1356,3 +1358,171 @@ def _predict_bed_whole(forward, bed_path, segment_center, model_type, group, sin
         tail.abort()
         raise
     return tail.result(n_all, order)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Prediction over genomic regions: the sites are enumerated on the device from the resident genome (csrc/sites.hip,
+# PackedGenome.scan_sites / emit_sites) instead of being read from a BED file with one row per site.  The reference has no
+# counterpart: its users write that BED with scripts of their own.
+# ------------------------------------------------------------------------------------------------------------------
+REGION_END = 1 << 62       # "to the end of the record" (the enumeration clamps every window to the record)
+
+
+def _merge_intervals(intervals):
+    """Sorted disjoint [lo, hi) intervals; overlapping and touching ones merged, empty ones dropped."""
+    out = []
+    for lo, hi in sorted((int(a), int(b)) for a, b in intervals if b > a):
+        if out and lo <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return [(lo, hi) for lo, hi in out]
+
+
+def read_regions_arg(spec):
+    """{chrom: [(lo, hi), ..]} -- sorted, disjoint, 0-based half-open -- of a region argument or a list of them:
+    ``chr`` (the whole record: (0, REGION_END)), ``chr:start-end`` (1-based inclusive, as users write it) or the path of an existing BED-like file of regions (0-based half-open, extra columns ignored, plain or gzip:
+    ``tables.read_regions``).  Overlapping or touching regions are merged, so no site is enumerated twice.  Raises ValueError naming
+    the argument."""
+    specs = [spec] if isinstance(spec, (str, os.PathLike)) else list(spec)
+    found = {}
+    for sp in specs:
+        sp = os.fspath(sp)
+        if os.path.isfile(sp):
+            from .tables import read_regions
+            try:
+                table = read_regions(sp)
+            except ValueError as e:
+                raise ValueError(f"regions {sp!r}: {e}") from None
+            if not table:
+                raise ValueError(f"regions {sp!r}: the file holds no region")
+            for chrom, (starts, ends) in table.items():
+                for lo, hi in zip(starts, ends):
+                    if lo < 0 or hi < lo:
+                        raise ValueError(f"regions {sp!r}: bad interval {chrom} {lo} {hi}")
+                    found.setdefault(chrom, []).append((lo, hi))
+        elif ":" in sp:
+            chrom, _, span = sp.rpartition(":")
+            m = re.fullmatch(r"([0-9]+)-([0-9]+)", span)
+            if not chrom or m is None:
+                raise ValueError(f"regions {sp!r}: expected chr, chr:start-end (1-based, inclusive) or the path of a BED file")
+            a, b = int(m.group(1)), int(m.group(2))
+            if a < 1 or b < a:
+                raise ValueError(f"regions {sp!r}: start must be at least 1 and end at least start")
+            found.setdefault(chrom, []).append((a - 1, b))
+        elif sp.strip():
+            found.setdefault(sp, []).append((0, REGION_END))
+        else:
+            raise ValueError(f"regions {sp!r}: empty argument")
+    return {chrom: _merge_intervals(iv) for chrom, iv in found.items()}
+
+
+def _region_pieces(cum, a, b):
+    """Sites [a, b) of a chromosome's enumeration -- its regions' enumerations one after the other, `cum` their running totals
+    (cum[0] = 0) -- as [(region, first site within the region, sites)] in ascending order, empty pieces left out."""
+    out = []
+    for j in range(max(int(np.searchsorted(cum, a, "right")) - 1, 0), int(np.searchsorted(cum, b, "left"))):
+        s0, s1 = max(a, int(cum[j])), min(b, int(cum[j + 1]))
+        if s1 > s0:
+            out.append((j, s0 - int(cum[j]), s1 - s0))
+    return out
+
+
+def predict_regions_sharded(forward, regions, focal, context="all", model_type="snv", group=None, sink=None, collect=True, timings=None,
+                            emulate=None):
+    """predict_bed_sharded for sites that are not listed in a file but selected by their base: every A/T site (focal 'A'), every C/G
+    site (focal 'C'; context 'all', 'CpG' or 'nonCpG') or, for INDEL models, every A/C/G/T position (focal 'ANY') of `regions` (what
+    read_regions_arg returns, or its argument).  Same forward (HipShardForward: a HIP ``device`` and ``genome(chrom)``), sinks, `timings`,
+    `emulate` and return value as predict_bed_sharded; rows carry end = start + 1 and label 0.  With `collect` the returned rows are in the
+    table's order -- ascending chromosome name, then start: there is no input file whose order could be kept -- and `order` counts them.
+
+    Chromosomes go in ascending name order, the next one is packed while this one is computed.  Per chromosome the regions are counted
+    on the device (one read-back of the totals), rank i of N takes the slice shard_bounds(sites of the chromosome, i, N) of the
+    enumeration and emits it in parts of at most _ALIGNED_PART_ROWS sites.  The enumeration ascends, so with a consumer of aligned
+    blocks (a TsvSink, every rank's with parts=True; collect=False) a rank's rows are its slice of the table: nothing is gathered or
+    sorted.  A caller that wants all rows back, or a sink on rank 0 alone, gets one all_gather per chromosome instead."""
+    from .data.genome import site_selection
+    f_code, _ = site_selection(focal, context)
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
+    if (f_code == 2) != (model_type == "indel"):
+        raise ValueError(f"focal {focal!r} does not go with model_type {model_type!r}: 'ANY' is the INDEL models' selection, "
+                         "'A' / 'C' the SNV models'")
+    if not isinstance(regions, dict):
+        regions = read_regions_arg(regions)
+    dev = _device_of(forward)
+    if dev is None or not hasattr(forward, "genome"):
+        raise ValueError("predict_regions_sharded enumerates the sites on the device: the forward needs a HIP device and genome(chrom)")
+    if emulate is not None:
+        rank, world = int(emulate[0]), int(emulate[1])
+    else:
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    T = {} if timings is None else timings
+    clock = time.perf_counter
+    T["emulation"] = 0.0
+    tail = _ShardTail(forward, model_type, sink, collect, T, dev, rank)
+    T["enumerate"] = 0.0
+    aligned_ok = (not collect and _ALIGNED_BLOCKS and (sink is None or getattr(sink, "takes_aligned_blocks", False))
+                  and (world == 1 or sink is None or getattr(sink, "parts", False)))
+    if emulate is not None and world > 1 and not aligned_ok:
+        raise ValueError("emulate=(rank, world) needs collect=False and a part-file sink: one rank cannot stand in for a gather")
+    names = sorted(regions)
+    rows_all = 0
+    try:
+        for si, chrom in enumerate(names):
+            g = forward.genome(chrom)                      # (KeyError for a chromosome the FASTA lacks, like the BED path)
+            t0 = clock()
+            scans = [g.scan_sites(lo, hi, focal, context) for lo, hi in regions[chrom]]
+            if hasattr(forward, "prefetch") and si + 1 < len(names):
+                forward.prefetch(names[si + 1])
+            # the one read-back per chromosome: the totals size the outputs and the ranks' slices
+            cum = np.r_[0, np.cumsum(torch.cat([sc.total_dev for sc in scans]).tolist() if scans else [])].astype(np.int64)
+            T["enumerate"] += clock() - t0
+            n = int(cum[-1])
+            if n == 0:                                     # (a BED file has no rows for such a chromosome either: it is no shard)
+                continue
+            b0, b1 = shard_bounds(n, rank, world)
+            n_parts = max(1, -(-(-(-n // world)) // _ALIGNED_PART_ROWS)) if aligned_ok else 1
+            for part in range(n_parts):
+                p0, p1 = shard_bounds(b1 - b0, part, n_parts)
+                a, b = b0 + p0, b0 + p1                    # sites [a, b) of the chromosome's enumeration
+                t0 = clock()
+                pos = torch.empty(b - a, dtype=torch.int64, device=dev)
+                strand = torch.empty(b - a, dtype=torch.uint8, device=dev)
+                o = 0
+                for j, first, m in _region_pieces(cum, a, b):
+                    g.emit_sites(scans[j], first, m, pos[o:o + m], strand[o:o + m])
+                    o += m
+                end = pos + 1
+                label = torch.zeros(b - a, dtype=torch.float32, device=dev)
+                T["enumerate"] += clock() - t0
+                t0 = clock()
+                local = forward(chrom, pos, strand)
+                T["compute_enqueue"] += clock() - t0
+                if local.shape[0] != b - a:
+                    raise RuntimeError("forward returned a wrong number of rows")
+                if local.dtype not in (torch.float32, torch.float64):
+                    local = local.to(torch.float32)
+                # The per-(segment, strand) focal-base check of the BED path cannot fail here -- a site is enumerated BECAUSE its base is
+                # the focal one (or, on '-', its complement) -- so it is skipped; the BED drivers keep it unchanged.
+                if aligned_ok:
+                    tail.aligned_part(chrom, local, pos, end, strand, label, None, 0, check_focal=False)
+            if aligned_ok:
+                T["aligned_shards"] = T.get("aligned_shards", 0) + 1
+                rows_all += n
+                continue
+            k = local.shape[1] - 1
+            if world > 1:
+                t0 = clock()
+                full = all_gather_rows(_pack_rows(local, pos, end, strand, label), n, group)
+                T["gather"] += clock() - t0
+                local, pos, end, strand, label = (c.contiguous() for c in _unpack_rows(full, k, local.dtype))
+            file_rows = torch.arange(rows_all, rows_all + n, device=dev) if collect else None
+            tail(chrom, [(rows_all, rows_all + n)], local, pos, end, strand, label, None, file_rows, check_focal=False)
+            rows_all += n
+        tail.close()
+    except BaseException:
+        tail.abort()
+        raise
+    return tail.result(rows_all, None)
