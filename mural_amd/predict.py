@@ -6,6 +6,7 @@ The host logic (block partition, padded all_gather, trimming back to the referen
 and covered by world_size-2 gloo tests on CPU; the compute function is the HIP model's ``forward_packed`` /
 ``forward_packed_reuse``; the prediction table is formatted by ``csrc/tsv.hip`` (device kernel or host threads).
 """
+import contextlib
 import ctypes as C
 import os
 import queue
@@ -878,6 +879,33 @@ def _device_of(forward):
     return None
 
 
+def _rank_world(group, emulate):
+    """(rank, world) of a file-level run: the process group's (0, 1 without one), or the pair `emulate` names."""
+    if emulate is not None:
+        return int(emulate[0]), int(emulate[1])
+    if dist.is_initialized():
+        return dist.get_rank(group), dist.get_world_size(group)
+    return 0, 1
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _forward_rows(forward, chrom, pos, strand, rows, T, normalise=True):
+    """This rank's forward call for `rows` sites of `chrom`: the (rows, n_class + 1) tensor, float32 / float64 with `normalise`."""
+    t0 = time.perf_counter()
+    local = forward(chrom, pos, strand)
+    T["compute_enqueue"] += time.perf_counter() - t0
+    if local.shape[0] != rows:
+        raise RuntimeError("forward returned a wrong number of rows")
+    if not isinstance(local, torch.Tensor):
+        local = torch.from_numpy(np.ascontiguousarray(local))
+    if normalise and local.dtype not in (torch.float32, torch.float64):
+        local = local.to(torch.float32)
+    return local
+
+
 def _aligned_verdict(infos):
     """The focal-base check of an aligned shard from every rank's (rows, first segment, its '+' / '-' focal base, last segment, its
     '+' / '-' focal base, own verdict): a block's own groups were checked by its rank; a (segment, strand) group that runs over a block
@@ -902,8 +930,8 @@ class _ShardTail:
     """What happens to a gathered shard (rows of one chromosome in bed_reader order): the per-(segment, strand) focal-base check --
     its verdict is read one shard late, so no rank waits for work just enqueued --, the sink, the collection for the caller."""
 
-    def __init__(self, forward, model_type, sink, collect, T, dev, rank):
-        self.model_type, self.sink, self.collect, self.T, self.dev = model_type, sink, collect, T, dev
+    def __init__(self, forward, check, sink, collect, T, dev, rank):
+        self.check, self.sink, self.collect, self.T, self.dev = check, sink, collect, T, dev      # check: the focal-base rule applies
         self.feeds_sink = sink is not None and (rank == 0 or getattr(sink, "parts", False))
         self.need_meta = collect or self.feeds_sink
         # HipShardForward with a calibration chain hands over calibrated probabilities: the flag travels with every shard (and the
@@ -920,122 +948,103 @@ class _ShardTail:
         ev, host = pc
         ev.synchronize()
         self.T["focal_wait"] += time.perf_counter() - t
-        if host.dim() == 2:                 # an aligned shard: the ranks' border groups (see aligned())
+        if host.dim() == 2:                 # an aligned shard: the ranks' border groups (see aligned_part)
             _aligned_verdict(host.numpy())
         elif int(host[0]) != 0:
             raise ValueError(_FOCAL_MSG)
 
-    def __call__(self, chrom, runs, full, start, end, strand, label, grp, file_rows=None, check_focal=True):
-        """`full`: (n, k + 1) probabilities + focal base; `grp`: non-decreasing group ids; `runs`: [(lo, hi)] positions of the shard's
-        rows in the whole input's bed_reader order; `file_rows`: file row index per row (rank-local ingest) or None."""
-        n, k = full.shape[0], full.shape[1] - 1
-        dev = self.dev
-        if dev is not None:
-            if self.model_type == "snv" and check_focal:
-                status = torch.zeros(1, dtype=torch.int32, device=dev)
-                with torch.cuda.device(dev):
-                    _lib.check(_lib.lib().mural_focal_group_check(full.data_ptr(), int(full.dtype == torch.float64), full.stride(0), k,
-                                                                 grp.contiguous().data_ptr(), n, status.data_ptr(),
-                                                                 _lib.current_stream_ptr(dev)))
-                    host = torch.zeros(1, dtype=torch.int32).pin_memory()
-                    host.copy_(status, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                self._finish_check()               # the verdict of the PREVIOUS shard
-                self.pending = (ev, host)
-            shard = None
-            if self.need_meta:
-                shard = {"chrom": chrom, "start": start, "end": end, "strand": strand, "label": label, "prob": full, "n_class": k,
-                         "calibrated": self.calibrated}
-        else:
-            full = full.cpu().numpy() if isinstance(full, torch.Tensor) else np.asarray(full)
-            as_np = lambda a: a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)       # noqa: E731
-            if self.model_type == "snv" and check_focal:
-                check_focal_groups(full[:, -1].astype(np.int64), as_np(grp))
-            shard = {"chrom": chrom, "start": as_np(start), "end": as_np(end), "strand": as_np(strand), "label": as_np(label),
-                     "prob": full[:, :-1], "n_class": k, "calibrated": self.calibrated}
+    def _defer(self, verdict):
+        """`verdict` (a device tensor: a status word, or an aligned shard's border records) is read one shard late, the PREVIOUS one now."""
+        with torch.cuda.device(self.dev):
+            host = torch.zeros(verdict.shape, dtype=verdict.dtype).pin_memory()
+            host.copy_(verdict, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._finish_check()
+        self.pending = (ev, host)
+
+    def _hand_over(self, chrom, rows, start, end, strand, label, aligned=False):
+        """The shard dict of `rows` ((n, k + 1): probabilities + focal base) and its site columns -> the sink.  Device tensors stay what
+        they are (`prob` keeps the focal column, `n_class` says where it ends); rows of a host forward become numpy arrays."""
+        if not self.need_meta:
+            return None
+        k = rows.shape[1] - 1
+        if self.dev is None:
+            rows, start, end, strand, label = _np(rows)[:, :k], _np(start), _np(end), _np(strand), _np(label)
+        shard = {"chrom": chrom, "start": start, "end": end, "strand": strand, "label": label, "prob": rows, "n_class": k,
+                 "calibrated": self.calibrated}
+        if aligned:
+            shard["aligned"] = True
         if self.feeds_sink:
             t0 = time.perf_counter()
             self.sink(shard)
             self.T["sink"] += time.perf_counter() - t0
+        return shard
+
+    def __call__(self, chrom, runs, full, start, end, strand, label, grp, file_rows=None):
+        """`full`: (n, k + 1) probabilities + focal base; `grp`: non-decreasing group ids; `runs`: [(lo, hi)] positions of the shard's
+        rows in the whole input's bed_reader order; `file_rows`: file row index per row (rank-local ingest) or None."""
+        n, k = full.shape[0], full.shape[1] - 1
+        if self.check and self.dev is not None:
+            status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            with torch.cuda.device(self.dev):
+                _lib.check(_lib.lib().mural_focal_group_check(full.data_ptr(), int(full.dtype == torch.float64), full.stride(0), k,
+                                                             grp.contiguous().data_ptr(), n, status.data_ptr(),
+                                                             _lib.current_stream_ptr(self.dev)))
+            self._defer(status)
+        elif self.check:
+            check_focal_groups(_np(full)[:, -1].astype(np.int64), _np(grp))
+        shard = self._hand_over(chrom, full, start, end, strand, label)
         if self.collect:
-            cpu = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)     # noqa: E731
-            self.kept.append((runs, {"start": cpu(shard["start"]), "end": cpu(shard["end"]), "strand": cpu(shard["strand"]),
-                                     "label": cpu(shard["label"]), "prob": cpu(shard["prob"])[:, :k], "chrom": chrom,
-                                     "file_rows": None if file_rows is None else cpu(file_rows)}))
+            self.kept.append((runs, {"start": _np(shard["start"]), "end": _np(shard["end"]), "strand": _np(shard["strand"]),
+                                     "label": _np(shard["label"]), "prob": _np(shard["prob"])[:, :k], "chrom": chrom,
+                                     "file_rows": None if file_rows is None else _np(file_rows)}))
 
     # -- a chromosome whose rows already are in the table's order (BedRun.in_order) -------------------------------------------------
     # The file order then IS the output order, this rank's block of the rows IS its slice of the table, and nothing but the focal-base
     # check looks across blocks: a (segment, strand) group that straddles a block border must agree on both sides.  Every rank checks its
     # own groups, the ranks exchange 7 numbers -- rows, first / last segment, focal base of the '+' and the '-' group of each (-1: none) --
     # and every rank walks the chain (verdict read one shard late, like the gathered shards').  No all-gather of rows, no sort of n rows.
-    def aligned_part(self, chrom, local, start, end, strand, label, anchor, central_bp, check_focal=True):
+    def aligned_part(self, chrom, local, start, end, strand, label, anchor, central_bp):
         """One PART of this rank's block of an aligned chromosome (the block goes through in parts of <= _ALIGNED_PART_ROWS rows, in file
         order: the table writer works on one part while the next is computed, and host / device memory is bounded by a part).  `local`:
-        (m, k + 1) probabilities + focal base, start / strand / end / label: the part's site columns.  Returns the part's border record
-        for ``aligned_close`` (None for models without the focal-base rule, and with check_focal=False: the region driver's sites
-        are chosen BY their base, see predict_regions_sharded)."""
+        (m, k + 1) probabilities + focal base, start / strand / end / label: the part's site columns, tensors on one device (CPU tensors
+        with a host forward).  Returns the part's border record for ``aligned_close`` (None without the focal-base check)."""
         m, k = local.shape[0], local.shape[1] - 1
-        dev = self.dev
         info = None
-        if self.model_type == "snv" and check_focal:
+        if self.check:
             e0 = (anchor if anchor is not None else 1) + central_bp
-            if dev is not None:
-                seg = torch.where(start > e0, (start - e0 + (central_bp - 1)) // central_bp, torch.zeros_like(start))
-                key = (seg << 1) | strand.to(torch.int64)
-                key_o, order = torch.sort(key, stable=True)
-                focal_o = local[:, k][order].contiguous()
-                status = torch.zeros(1, dtype=torch.int32, device=dev)
-                info = torch.full((8,), -1, dtype=torch.int64, device=dev)
-                info[0] = m
-                if m:
-                    with torch.cuda.device(dev):
-                        _lib.check(_lib.lib().mural_focal_group_check(focal_o.data_ptr(), int(focal_o.dtype == torch.float64), 1, 0,
-                                                                     key_o.data_ptr(), m, status.data_ptr(), _lib.current_stream_ptr(dev)))
-                    want = torch.stack([key_o[0] & ~1, (key_o[0] & ~1) | 1, key_o[-1] & ~1, (key_o[-1] & ~1) | 1])
-                    at = torch.searchsorted(key_o, want).clamp(max=m - 1)
-                    have = key_o[at] == want
-                    foc = torch.where(have, focal_o[at].to(torch.int64), torch.full_like(at, -1))
-                    info[1], info[4] = key_o[0] >> 1, key_o[-1] >> 1
-                    info[2:4], info[5:7] = foc[0:2], foc[2:4]
-                info[7] = status[0].to(torch.int64)
-            else:
-                start_h, strand_h = np.asarray(start), np.asarray(strand)
-                seg = np.where(start_h > e0, (start_h - e0 + (central_bp - 1)) // central_bp, 0)
-                key = (seg.astype(np.int64) << 1) | strand_h.astype(np.int64)
-                order = np.argsort(key, kind="stable")
-                key_o = key[order]
-                loc_h = local.cpu().numpy() if isinstance(local, torch.Tensor) else np.asarray(local)
-                focal_o = loc_h[:, k][order].astype(np.int64)
-                info = np.full(8, -1, np.int64)
-                info[0], info[7] = m, 0
-                if m:
+            seg = torch.where(start > e0, (start - e0 + (central_bp - 1)) // central_bp, torch.zeros_like(start))
+            key = (seg << 1) | strand.to(torch.int64)
+            key_o, order = torch.sort(key, stable=True)
+            focal_o = local[:, k][order].contiguous()
+            status = torch.zeros(1, dtype=torch.int32, device=local.device)
+            info = torch.full((8,), -1, dtype=torch.int64, device=local.device)
+            info[0] = m
+            if m:
+                if self.dev is not None:
+                    with torch.cuda.device(self.dev):
+                        _lib.check(_lib.lib().mural_focal_group_check(focal_o.data_ptr(), int(focal_o.dtype == torch.float64), 1, 0, key_o.data_ptr(),
+                                                                     m, status.data_ptr(), _lib.current_stream_ptr(self.dev)))
+                else:
                     try:
-                        check_focal_groups(focal_o, key_o)
+                        check_focal_groups(focal_o.numpy().astype(np.int64), key_o.numpy())
                     except ValueError:
-                        info[7] = 1
-                    want = np.array([key_o[0] & ~1, (key_o[0] & ~1) | 1, key_o[-1] & ~1, (key_o[-1] & ~1) | 1])
-                    at = np.minimum(np.searchsorted(key_o, want), m - 1)
-                    foc = np.where(key_o[at] == want, focal_o[at], -1)
-                    info[1], info[4] = key_o[0] >> 1, key_o[-1] >> 1
-                    info[2:4], info[5:7] = foc[0:2], foc[2:4]
-                info = torch.from_numpy(info)
-        shard = None
-        if self.need_meta:
-            as_np = (lambda a: a) if dev is not None else (lambda a: a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a))     # noqa: E731
-            prob = local if dev is not None else (local.cpu().numpy() if isinstance(local, torch.Tensor) else np.asarray(local))[:, :k]
-            shard = {"chrom": chrom, "start": as_np(start), "end": as_np(end), "strand": as_np(strand), "label": as_np(label), "prob": prob,
-                     "n_class": k, "calibrated": self.calibrated, "aligned": True}
-        if self.feeds_sink:
-            t0 = time.perf_counter()
-            self.sink(shard)
-            self.T["sink"] += time.perf_counter() - t0
+                        status[0] = 1
+                want = torch.stack([key_o[0] & ~1, (key_o[0] & ~1) | 1, key_o[-1] & ~1, (key_o[-1] & ~1) | 1])
+                at = torch.searchsorted(key_o, want).clamp(max=m - 1)
+                have = key_o[at] == want
+                foc = torch.where(have, focal_o[at].to(torch.int64), torch.full_like(at, -1))
+                info[1], info[4] = key_o[0] >> 1, key_o[-1] >> 1
+                info[2:4], info[5:7] = foc[0:2], foc[2:4]
+            info[7] = status[0].to(torch.int64)
+        self._hand_over(chrom, local, start, end, strand, label, aligned=True)
         return info
 
     def aligned_close(self, infos, group, world, emulated):
         """The border records of this rank's parts of one aligned chromosome -> ONE small all-gather (parts x 8 numbers per rank) -> the
         chain over (rank, part) in table order; the verdict is read one shard late (no rank waits for work just enqueued)."""
-        if self.model_type != "snv":
+        if not self.check:
             return
         mine = torch.stack(infos)                                    # (parts, 8)
         if world > 1 and not emulated:
@@ -1045,29 +1054,27 @@ class _ShardTail:
         else:
             every = mine
         if self.dev is not None:
-            with torch.cuda.device(self.dev):
-                host = torch.zeros(every.shape, dtype=torch.int64).pin_memory()
-                host.copy_(every, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-            self._finish_check()               # the verdict of the PREVIOUS shard
-            self.pending = (ev, host)
+            self._defer(every)
         else:
             self._finish_check()
             _aligned_verdict(every.numpy())
 
-    def abort(self):
-        # the verdict of a shard's focal-base check is read one shard late, i.e. after that shard's rows went to the sink: a failing
-        # run must not leave a partial table with a valid-looking header behind (the reference exits before writing anything)
-        if self.feeds_sink and hasattr(self.sink, "abort"):
-            self.sink.abort()
-
-    def close(self):
-        self._finish_check()
-        if self.feeds_sink and hasattr(self.sink, "close"):
-            t0 = time.perf_counter()
-            self.sink.close()
-            self.T["sink_close"] = time.perf_counter() - t0
+    @contextlib.contextmanager
+    def frame(self):
+        """Around a driver's shard loop: the last verdict and the sink's close() behind it, the sink's abort() on ANY exception.  The
+        verdict of a shard's focal-base check is read one shard late, i.e. after that shard's rows went to the sink: a failing run must
+        not leave a partial table with a valid-looking header behind (the reference exits before writing anything)."""
+        try:
+            yield
+            self._finish_check()
+            if self.feeds_sink and hasattr(self.sink, "close"):
+                t0 = time.perf_counter()
+                self.sink.close()
+                self.T["sink_close"] = time.perf_counter() - t0
+        except BaseException:
+            if self.feeds_sink and hasattr(self.sink, "abort"):
+                self.sink.abort()
+            raise
 
     def result(self, n_all, order):
         if not self.collect:
@@ -1119,7 +1126,18 @@ def predict_bed_sharded(forward, bed_path, segment_center=300000, model_type="sn
         return _predict_bed_whole(forward, bed_path, segment_center, model_type, group, sink, collect, timings)
     if ingest != "ranked":
         raise ValueError(f"ingest must be 'ranked' or 'whole', got {ingest!r}")
-    return _predict_bed_ranked(forward, bed_path, segment_center, model_type, group, sink, collect, timings, emulate)
+    from .data import ingest as ing
+    rank, world = _rank_world(group, emulate)
+    T = {} if timings is None else timings
+    T["emulation"] = 0.0
+    t0 = time.perf_counter()
+    index = ing.BedIndex.build(bed_path, rank, world, group, emulate=emulate is not None, seconds=T)
+    T["bed_index"] = time.perf_counter() - t0
+    if emulate is not None:
+        T["emulation"] += T["bed_index"] - T["index_scan"]
+    T.update({"bed_parse": 0.0, "pack_rows": 0.0, "reorder": 0.0})
+    return _predict_shards(forward, _BedSites(index), int(segment_center), model_type, group, sink, collect, T, rank, world,
+                           emulate is not None)
 
 
 def _row_layout(k, f64):
@@ -1173,76 +1191,102 @@ _ALIGNED_BLOCKS = True      # (tests switch it off to compare the two routes of 
 _ALIGNED_PART_ROWS = 1 << 22
 
 
-def _predict_bed_ranked(forward, bed_path, segment_center, model_type, group, sink, collect, timings, emulate):
-    from .data import ingest
-    if emulate is not None:
-        rank, world = int(emulate[0]), int(emulate[1])
-    else:
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
-    T = {} if timings is None else timings
+def _takes_aligned_blocks(sink, collect, world):
+    """Aligned blocks need a consumer that takes a rank's own rows as its slice of the table: every rank's part-file sink (or the one
+    rank there is), and nobody who wants all rows back."""
+    return (not collect and _ALIGNED_BLOCKS and (sink is None or getattr(sink, "takes_aligned_blocks", False))
+            and (world == 1 or sink is None or getattr(sink, "parts", False)))
+
+
+def _aligned_parts(n, world):
+    """Parts of <= _ALIGNED_PART_ROWS rows that the longest block of `n` rows over `world` ranks goes through; every rank makes as many."""
+    return max(1, -(-(-(-n // world)) // _ALIGNED_PART_ROWS))
+
+
+def _gather_rows(local, cols, n, group, T, pack_key, stand_in=None):
+    """This rank's (m, k + 1) rows and their site columns (start, end, strand, label) -> the chromosome's `n` rows of every rank, through
+    ONE all_gather of packed rows (or `stand_in(packed)` for it): (rows, start, end, strand, label), views of the gathered buffer."""
+    t0 = time.perf_counter()
+    packed = _pack_rows(local, *cols)
+    T[pack_key] += time.perf_counter() - t0
+    t0 = time.perf_counter()
+    full = all_gather_rows(packed, n, group) if stand_in is None else stand_in(packed)
+    T["gather"] += time.perf_counter() - t0
+    return _unpack_rows(full, local.shape[1] - 1, local.dtype)
+
+
+class _BedSites:
+    """Site source of the ranked BED ingest: a chromosome's rows in FILE order (its runs concatenated), of which a rank parses only the
+    slices it is asked for (data.ingest.BedIndex)."""
+    check_focal = True           # the reference's per-(segment, strand) focal-base check
+    reorder = True               # gathered rows go from file order to bed_reader order
+    read_key = "bed_parse"
+
+    def __init__(self, index):
+        self.index, self.names = index, sorted(index.chroms)
+
+    def open(self, chrom, fetch_next):
+        runs = [self.index.runs[i] for i in self.index.chroms[chrom]]
+        return sum(r.rows for r in runs), len(runs) == 1 and runs[0].in_order
+
+    def columns(self, chrom, lo, hi):
+        start, end, label, strand = self.index.read_block(chrom, lo, hi)
+        return start, end, strand, label
+
+    def layout(self, chrom, row0, n):
+        ids = self.index.chroms[chrom]
+        runs = [(self.index.runs[i].row0, self.index.runs[i].row0 + self.index.runs[i].rows) for i in ids]
+        return runs, self.index.runs[0].first_start if ids[0] == 0 else None      # (the FILE's first run anchors its segment grid)
+
+
+def _predict_shards(forward, src, central_bp, model_type, group, sink, collect, T, rank, world, emulated):
+    """The per-chromosome loop of the file-level drivers, over `src.names` in ascending order: the table's.  Per chromosome `src` answers
+    open(chrom, fetch_next) -> (sites, "they are in the table's order") -- a source that counts on the device calls fetch_next() behind
+    the work it enqueued --, columns(chrom, lo, hi) -> (start, end, strand, label) of sites [lo, hi), host arrays or device tensors,
+    charged to T[src.read_key], and layout(chrom, row0, n) -> ([(lo, hi)] file rows of its runs, the first run's anchor), where `row0`
+    rows precede the chromosome in this loop.  src.check_focal / src.reorder: see _BedSites."""
     clock = time.perf_counter
-    T["emulation"] = 0.0
-    t0 = clock()
-    index = ingest.BedIndex.build(bed_path, rank, world, group, emulate=emulate is not None, seconds=T)
-    T["bed_index"] = clock() - t0
-    if emulate is not None:
-        T["emulation"] += T["bed_index"] - T["index_scan"]
     dev = _device_of(forward)
     tdev = dev if dev is not None else torch.device("cpu")
-    tail = _ShardTail(forward, model_type, sink, collect, T, dev, rank)
-    T.update({"bed_parse": 0.0, "pack_rows": 0.0, "reorder": 0.0})
-    # aligned blocks need a consumer that takes a rank's own rows as its slice of the table: every rank's part-file sink (or the one
-    # rank there is), and nobody who wants all rows back
-    aligned_ok = (not collect and _ALIGNED_BLOCKS and (sink is None or getattr(sink, "takes_aligned_blocks", False))
-                  and (world == 1 or sink is None or getattr(sink, "parts", False)))
-    names = sorted(index.chroms)
-    up = lambda a: torch.from_numpy(a).to(tdev)                                           # noqa: E731
-    try:
-        for si, chrom in enumerate(names):
-            run_ids = index.chroms[chrom]
-            run_rows = [index.runs[i].rows for i in run_ids]
-            n = sum(run_rows)
+    tail = _ShardTail(forward, model_type == "snv" and src.check_focal, sink, collect, T, dev, rank)
+    aligned_ok = _takes_aligned_blocks(sink, collect, world)
+    up = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(tdev)     # noqa: E731
+    rows_all = 0
+    with tail.frame():
+        for si, chrom in enumerate(src.names):
+            todo = [src.names[si + 1]] if hasattr(forward, "prefetch") and si + 1 < len(src.names) else []
+            fetch_next = lambda: todo and forward.prefetch(todo.pop())     # noqa: E731  (the next chromosome's pack is started once)
+            n, in_order = src.open(chrom, fetch_next)
+            if n == 0:                                     # (a BED file has no rows for such a chromosome either: it is no shard)
+                continue
+            runs, anchor = src.layout(chrom, rows_all, n)
+            rows_all += n
             b0, b1 = shard_bounds(n, rank, world)
             # a chromosome whose rows already are in the table's order: this rank's block is its slice of the table (_ShardTail.aligned_part);
             # it goes through in parts (every rank the same number of them: the one collective of the shard carries a record per part)
-            is_aligned = aligned_ok and len(run_ids) == 1 and index.runs[run_ids[0]].in_order
-            n_parts = max(1, -(-(-(-n // world)) // _ALIGNED_PART_ROWS)) if is_aligned else 1
+            is_aligned = aligned_ok and in_order
+            n_parts = _aligned_parts(n, world) if is_aligned else 1
             records = []
             for part in range(n_parts):
                 p0, p1 = shard_bounds(b1 - b0, part, n_parts)
                 t0 = clock()
-                start_h, end_h, label_h, strand_h = index.read_block(chrom, b0 + p0, b0 + p1)
-                T["bed_parse"] += clock() - t0
-                if part == 0 and hasattr(forward, "prefetch") and si + 1 < len(names):
-                    forward.prefetch(names[si + 1])
+                start_h, end_h, strand_h, label_h = src.columns(chrom, b0 + p0, b0 + p1)
+                T[src.read_key] += clock() - t0
+                fetch_next()                               # during the first part: the pack runs beside this chromosome's compute
                 # every site column goes up BEFORE the forward is enqueued: a copy from pageable host memory waits for the stream's earlier
                 # work, and behind the forward it would hold the host for the whole compute instead of letting it parse the next chromosome
                 pos_b, strand_b, end_b, label_b = up(start_h), up(strand_h), up(end_h), up(label_h)
-                t0 = clock()
-                local = forward(chrom, pos_b if dev is not None else start_h, strand_b if dev is not None else strand_h)
-                T["compute_enqueue"] += clock() - t0
-                if local.shape[0] != p1 - p0:
-                    raise RuntimeError("forward returned a wrong number of rows")
-                if not isinstance(local, torch.Tensor):
-                    local = torch.from_numpy(np.ascontiguousarray(local))
-                if local.dtype not in (torch.float32, torch.float64):
-                    local = local.to(torch.float32)
+                local = _forward_rows(forward, chrom, start_h if dev is None else pos_b, strand_h if dev is None else strand_b, p1 - p0, T)
                 if is_aligned:
-                    anchor = index.runs[run_ids[0]].first_start if run_ids[0] == 0 else None
-                    records.append(tail.aligned_part(chrom, local, pos_b, end_b, strand_b, label_b, anchor, int(segment_center)))
+                    records.append(tail.aligned_part(chrom, local, pos_b, end_b, strand_b, label_b, anchor, central_bp))
             if is_aligned:
-                tail.aligned_close(records, group, world, emulate is not None)
+                tail.aligned_close(records, group, world, emulated)
                 T["aligned_shards"] = T.get("aligned_shards", 0) + 1
                 continue
-            k = local.shape[1] - 1
-            t0 = clock()
-            packed = _pack_rows(local, pos_b, end_b, strand_b, label_b)
-            T["pack_rows"] += clock() - t0
-            t0 = clock()
-            if emulate is not None and world > 1:
-                # stand-in for the other ranks' blocks: their site columns (parsed here, outside the share) next to copies of this
-                # rank's probability rows -- the gathered shard has the size, the sort keys and the text width of the real one
+
+            def stand_in(packed):
+                # emulate=(rank, world): the other ranks' blocks are their site columns (parsed here, outside the share) next to copies of
+                # this rank's probability rows -- the gathered shard has the size, the sort keys and the text width of the real one
                 if dev is not None:
                     torch.cuda.synchronize(dev)            # this rank's own work is charged to the share: the stand-in must not hide it
                 te = clock()
@@ -1251,44 +1295,38 @@ def _predict_bed_ranked(forward, bed_path, segment_center, model_type, group, si
                     lo, hi = shard_bounds(n, r, world)
                     if r == rank or hi == lo:
                         continue
-                    s2, e2, l2, d2 = index.read_block(chrom, lo, hi)
-                    src = local[torch.arange(hi - lo, device=tdev) % max(local.shape[0], 1)] if local.shape[0] else \
-                        torch.zeros((hi - lo, k + 1), dtype=local.dtype, device=tdev)
-                    full[lo:hi] = _pack_rows(src, up(s2), up(e2), up(d2), up(l2))
+                    rows = local[torch.arange(hi - lo, device=tdev) % max(local.shape[0], 1)] if local.shape[0] else \
+                        torch.zeros((hi - lo, local.shape[1]), dtype=local.dtype, device=tdev)
+                    full[lo:hi] = _pack_rows(rows, *[up(c) for c in src.columns(chrom, lo, hi)])
                 if dev is not None:
                     torch.cuda.synchronize(dev)            # ... and its device work is excluded with it
                 T["emulation"] += clock() - te
                 full[b0:b1] = packed                       # (the share's own copy: what the collective would deliver)
-            else:
-                full = all_gather_rows(packed, n, group)
-            T["gather"] += clock() - t0
-            t0 = clock()
-            prob, start, end, strand, label = _unpack_rows(full, k, local.dtype)
-            anchor = index.runs[run_ids[0]].first_start if run_ids[0] == 0 else None
-            key = _bed_reader_keys(start, strand, run_rows, anchor, int(segment_center))
-            key_o, order = torch.sort(key, stable=True)
-            full_o = prob[order]                            # (n, k + 1) probabilities + focal base in bed_reader order
-            start_o, strand_o = start[order], strand[order]
-            end_o = label_o = file_rows = None
-            if tail.need_meta:
-                end_o, label_o = end[order], label[order]
-            if collect:
-                file_rows = torch.cat([index.runs[i].row0 + torch.arange(index.runs[i].rows, device=tdev) for i in run_ids])[order]
-            T["reorder"] += clock() - t0
-            runs = [(index.runs[i].row0, index.runs[i].row0 + index.runs[i].rows) for i in run_ids]
-            tail(chrom, runs, full_o, start_o, end_o, strand_o, label_o, key_o, file_rows)
-        tail.close()
-    except BaseException:
-        tail.abort()
-        raise
-    return tail.result(index.rows, None)
+                return full
+
+            cols = (pos_b, end_b, strand_b, label_b)
+            if src.reorder:
+                local, start, end, strand, label = _gather_rows(local, cols, n, group, T, "pack_rows", stand_in if emulated and world > 1 else None)
+                t0 = clock()
+                grp, order = torch.sort(_bed_reader_keys(start, strand, [hi - lo for lo, hi in runs], anchor, central_bp), stable=True)
+                local = local[order]                       # (n, k + 1) probabilities + focal base in bed_reader order
+                start, strand = start[order], strand[order]
+                end, label = (end[order], label[order]) if tail.need_meta else (None, None)
+                file_rows = torch.cat([torch.arange(lo, hi, device=tdev) for lo, hi in runs])[order] if collect else None
+                T["reorder"] += clock() - t0
+                cols = (start, end, strand, label)
+            else:                                          # rows in the table's order: the ranks' blocks one after the other are the shard
+                if world > 1:                              # (the pack has no timing key of its own here: it goes with the gather)
+                    local, *cols = (c.contiguous() for c in _gather_rows(local, cols, n, group, T, "gather"))
+                grp, file_rows = None, torch.arange(*runs[0], device=tdev) if collect else None
+            tail(chrom, runs, local, *cols, grp, file_rows)
+    return tail.result(rows_all, None)
 
 
 def _predict_bed_whole(forward, bed_path, segment_center, model_type, group, sink, collect, timings):
     """Every rank parses the whole BED (see predict_bed_sharded, ingest="whole")."""
     from .data import ingest
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = _rank_world(group, None)
     T = {} if timings is None else timings
     clock = time.perf_counter
     t0 = clock()
@@ -1299,7 +1337,7 @@ def _predict_bed_whole(forward, bed_path, segment_center, model_type, group, sin
     T["bed_order"] = clock() - t0
     n_all = len(order)
     dev = _device_of(forward)
-    tail = _ShardTail(forward, model_type, sink, collect, T, dev, rank)
+    tail = _ShardTail(forward, model_type == "snv", sink, collect, T, dev, rank)
     t0 = clock()
     if dev is not None:
         # every column once to the device in FILE order; the bed_reader order is applied there (gathers at HBM speed)
@@ -1337,26 +1375,19 @@ def _predict_bed_whole(forward, bed_path, segment_center, model_type, group, sin
         parts = [col[lo:hi] for lo, hi in runs]
         return torch.cat(parts) if isinstance(col, torch.Tensor) else np.concatenate(parts)
 
-    try:
+    with tail.frame():
         for si, (chrom, runs) in enumerate(shards):
             n = sum(hi - lo for lo, hi in runs)
             b0, b1 = shard_bounds(n, rank, world)
             pos_s, strand_s = take(start_o, runs), take(strand_o, runs)
             if hasattr(forward, "prefetch") and si + 1 < len(shards):
                 forward.prefetch(shards[si + 1][0])
-            t0 = clock()
-            local = forward(chrom, pos_s[b0:b1], strand_s[b0:b1])
-            T["compute_enqueue"] += clock() - t0
-            if local.shape[0] != b1 - b0:
-                raise RuntimeError("forward returned a wrong number of rows")
+            # (this route has never normalised the forward's dtype: only the probabilities are gathered, and they go out as they came)
+            local = _forward_rows(forward, chrom, pos_s[b0:b1], strand_s[b0:b1], b1 - b0, T, normalise=False)
             t0 = clock()
             full = all_gather_rows(local, n, group)
             T["gather"] += clock() - t0
             tail(chrom, runs, full, pos_s, take(end_o, runs), strand_s, take(label_o, runs), take(grp_o, runs))
-        tail.close()
-    except BaseException:
-        tail.abort()
-        raise
     return tail.result(n_all, order)
 
 
@@ -1428,6 +1459,40 @@ def _region_pieces(cum, a, b):
     return out
 
 
+class _RegionSites:
+    """Site source of predict_regions_sharded: a chromosome's sites are its regions' enumerations one after the other.  The enumeration
+    ascends, so the rows are always in the table's order and a gathered shard needs no reorder; the sites are chosen BY their base, so
+    the per-(segment, strand) focal-base check of the BED path cannot fail and is skipped."""
+    check_focal = reorder = False
+    read_key = "enumerate"
+
+    def __init__(self, forward, regions, focal, context, dev, T):
+        self.forward, self.regions, self.focal, self.context, self.dev, self.T = forward, regions, focal, context, dev, T
+        self.names = sorted(regions)
+
+    def open(self, chrom, fetch_next):
+        self.g = g = self.forward.genome(chrom)            # (KeyError for a chromosome the FASTA lacks, like the BED path)
+        t0 = time.perf_counter()
+        self.scans = [g.scan_sites(lo, hi, self.focal, self.context) for lo, hi in self.regions[chrom]]
+        fetch_next()                                       # right behind the enqueued scans, before the host waits for their totals
+        # the one read-back per chromosome: the totals size the outputs and the ranks' slices
+        self.cum = np.r_[0, np.cumsum(torch.cat([sc.total_dev for sc in self.scans]).tolist() if self.scans else [])].astype(np.int64)
+        self.T["enumerate"] += time.perf_counter() - t0
+        return int(self.cum[-1]), True
+
+    def columns(self, chrom, a, b):
+        pos = torch.empty(b - a, dtype=torch.int64, device=self.dev)
+        strand = torch.empty(b - a, dtype=torch.uint8, device=self.dev)
+        o = 0
+        for j, first, m in _region_pieces(self.cum, a, b):
+            self.g.emit_sites(self.scans[j], first, m, pos[o:o + m], strand[o:o + m])
+            o += m
+        return pos, pos + 1, strand, torch.zeros(b - a, dtype=torch.float32, device=self.dev)
+
+    def layout(self, chrom, row0, n):
+        return [(row0, row0 + n)], None                    # there is no input file: the rows count up in the table's order
+
+
 def predict_regions_sharded(forward, regions, focal, context="all", model_type="snv", group=None, sink=None, collect=True, timings=None,
                             emulate=None):
     """predict_bed_sharded for sites that are not listed in a file but selected by their base: every A/T site (focal 'A'), every C/G
@@ -1453,76 +1518,10 @@ def predict_regions_sharded(forward, regions, focal, context="all", model_type="
     dev = _device_of(forward)
     if dev is None or not hasattr(forward, "genome"):
         raise ValueError("predict_regions_sharded enumerates the sites on the device: the forward needs a HIP device and genome(chrom)")
-    if emulate is not None:
-        rank, world = int(emulate[0]), int(emulate[1])
-    else:
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = _rank_world(group, emulate)
     T = {} if timings is None else timings
-    clock = time.perf_counter
-    T["emulation"] = 0.0
-    tail = _ShardTail(forward, model_type, sink, collect, T, dev, rank)
-    T["enumerate"] = 0.0
-    aligned_ok = (not collect and _ALIGNED_BLOCKS and (sink is None or getattr(sink, "takes_aligned_blocks", False))
-                  and (world == 1 or sink is None or getattr(sink, "parts", False)))
-    if emulate is not None and world > 1 and not aligned_ok:
+    T.update({"emulation": 0.0, "enumerate": 0.0})
+    if emulate is not None and world > 1 and not _takes_aligned_blocks(sink, collect, world):
         raise ValueError("emulate=(rank, world) needs collect=False and a part-file sink: one rank cannot stand in for a gather")
-    names = sorted(regions)
-    rows_all = 0
-    try:
-        for si, chrom in enumerate(names):
-            g = forward.genome(chrom)                      # (KeyError for a chromosome the FASTA lacks, like the BED path)
-            t0 = clock()
-            scans = [g.scan_sites(lo, hi, focal, context) for lo, hi in regions[chrom]]
-            if hasattr(forward, "prefetch") and si + 1 < len(names):
-                forward.prefetch(names[si + 1])
-            # the one read-back per chromosome: the totals size the outputs and the ranks' slices
-            cum = np.r_[0, np.cumsum(torch.cat([sc.total_dev for sc in scans]).tolist() if scans else [])].astype(np.int64)
-            T["enumerate"] += clock() - t0
-            n = int(cum[-1])
-            if n == 0:                                     # (a BED file has no rows for such a chromosome either: it is no shard)
-                continue
-            b0, b1 = shard_bounds(n, rank, world)
-            n_parts = max(1, -(-(-(-n // world)) // _ALIGNED_PART_ROWS)) if aligned_ok else 1
-            for part in range(n_parts):
-                p0, p1 = shard_bounds(b1 - b0, part, n_parts)
-                a, b = b0 + p0, b0 + p1                    # sites [a, b) of the chromosome's enumeration
-                t0 = clock()
-                pos = torch.empty(b - a, dtype=torch.int64, device=dev)
-                strand = torch.empty(b - a, dtype=torch.uint8, device=dev)
-                o = 0
-                for j, first, m in _region_pieces(cum, a, b):
-                    g.emit_sites(scans[j], first, m, pos[o:o + m], strand[o:o + m])
-                    o += m
-                end = pos + 1
-                label = torch.zeros(b - a, dtype=torch.float32, device=dev)
-                T["enumerate"] += clock() - t0
-                t0 = clock()
-                local = forward(chrom, pos, strand)
-                T["compute_enqueue"] += clock() - t0
-                if local.shape[0] != b - a:
-                    raise RuntimeError("forward returned a wrong number of rows")
-                if local.dtype not in (torch.float32, torch.float64):
-                    local = local.to(torch.float32)
-                # The per-(segment, strand) focal-base check of the BED path cannot fail here -- a site is enumerated BECAUSE its base is
-                # the focal one (or, on '-', its complement) -- so it is skipped; the BED drivers keep it unchanged.
-                if aligned_ok:
-                    tail.aligned_part(chrom, local, pos, end, strand, label, None, 0, check_focal=False)
-            if aligned_ok:
-                T["aligned_shards"] = T.get("aligned_shards", 0) + 1
-                rows_all += n
-                continue
-            k = local.shape[1] - 1
-            if world > 1:
-                t0 = clock()
-                full = all_gather_rows(_pack_rows(local, pos, end, strand, label), n, group)
-                T["gather"] += clock() - t0
-                local, pos, end, strand, label = (c.contiguous() for c in _unpack_rows(full, k, local.dtype))
-            file_rows = torch.arange(rows_all, rows_all + n, device=dev) if collect else None
-            tail(chrom, [(rows_all, rows_all + n)], local, pos, end, strand, label, None, file_rows, check_focal=False)
-            rows_all += n
-        tail.close()
-    except BaseException:
-        tail.abort()
-        raise
-    return tail.result(rows_all, None)
+    src = _RegionSites(forward, regions, focal, context, dev, T)
+    return _predict_shards(forward, src, 0, model_type, group, sink, collect, T, rank, world, emulate is not None)

@@ -471,6 +471,94 @@ def test_aligned_verdict_walks_groups_over_block_borders():
     bad((5, 0, 1, 2, 3, 1, 2, 0), (4, 5, 1, 2, 7, 0, 3, 1))                 # a rank's own verdict
 
 
+def border_record_by_loop(start, strand, focal, anchor, central_bp):
+    """The 8 numbers of _ShardTail.aligned_part for rows in the table's order, by bed_reader's own loop (preprocessing.py:63-75): rows,
+    first segment and the focal base of its '+' / '-' group (-1: no such row), the same of the last segment, "a group mixes bases"."""
+    rec = [len(start), -1, -1, -1, -1, -1, -1, 0]
+    end0, seg, segs, base = (anchor if anchor is not None else 1) + central_bp, 0, [], {}
+    for s, st, f in zip(start, strand, focal):
+        while s > end0:
+            end0 += central_bp
+            seg += 1
+        segs.append(seg)
+        if base.setdefault((seg, st), f) != f:
+            rec[7] = 1
+    if segs:
+        rec[1:7] = [segs[0], base.get((segs[0], 0), -1), base.get((segs[0], 1), -1), segs[-1], base.get((segs[-1], 0), -1), base.get((segs[-1], 1), -1)]
+    return rec, segs
+
+
+def border_cases():
+    """[(name, start, strand, focal, anchor, central_bp)]: no row, one row, and 300 rows over six segments of 50 whose first segment has no
+    '-' row and whose last has no '+' row -- on both grids (anchored at 1 and at the first start), clean and with one odd row in a
+    middle group."""
+    rows = sorted([(p, 0) for p in range(8, 228)] + [(p, 1) for p in range(67, 245, 3)] + [(p, 1) for p in range(248, 268)])
+    start, strand = [p for p, _ in rows], [st for _, st in rows]
+    cases = [("empty", [], [], [], None, 50), ("one", [77], [1], [2], None, 50), ("one-anchored", [77], [0], [3], 77, 50)]
+    for anchor in (None, start[0]):
+        segs = border_record_by_loop(start, strand, [0] * len(rows), anchor, 50)[1]
+        assert len(rows) == 300 and segs[-1] == 5 and 1 not in [st for sg, st in zip(segs, strand) if sg == 0] \
+            and 0 not in [st for sg, st in zip(segs, strand) if sg == 5]
+        focal = [(2 * sg + st) % 5 for sg, st in zip(segs, strand)]          # one base per (segment, strand) group ON THIS GRID
+        cases.append(("clean-%s" % anchor, start, strand, focal, anchor, 50))
+        odd = list(focal)
+        at = max(i for i, (sg, st) in enumerate(zip(segs, strand)) if sg == 2 and st == 1) - 3
+        odd[at] = (odd[at] + 1) % 5
+        cases.append(("conflict-%s" % anchor, start, strand, odd, anchor, 50))
+    return cases
+
+
+def aligned_part_record(device, start, strand, focal, anchor, central_bp):
+    """_ShardTail.aligned_part on hand-made columns on `device` (None: a host forward's CPU tensors), no sink, nothing collected."""
+    from mural_amd.predict import _ShardTail
+    dev = torch.device("cpu") if device is None else device
+    m = len(start)
+    local = torch.rand((m, 5), generator=torch.Generator().manual_seed(m))
+    local[:, 4] = torch.tensor(focal, dtype=torch.float32)
+    col = lambda v, dt: torch.tensor(v, dtype=dt).to(dev)          # noqa: E731
+    tail = _ShardTail(None, True, None, False, {}, device, 0)
+    rec = tail.aligned_part("chrA", local.to(dev), col(start, torch.int64), col([s + 1 for s in start], torch.int64), col(strand, torch.uint8),
+                            col([0.0] * m, torch.float32), anchor, central_bp)
+    assert rec.device.type == dev.type and rec.dtype == torch.int64
+    return rec.cpu().tolist()
+
+
+@pytest.mark.parametrize("case", border_cases(), ids=lambda c: c[0])
+def test_aligned_part_border_record_equals_bed_reader_s_loop(case):
+    """One implementation (torch, on the columns' device) of the record that the ranks exchange per part; here on CPU tensors."""
+    _, start, strand, focal, anchor, central_bp = case
+    want = border_record_by_loop(start, strand, focal, anchor, central_bp)[0]
+    assert want[7] == int(case[0].startswith("conflict"))
+    assert aligned_part_record(None, start, strand, focal, anchor, central_bp) == want
+
+
+# The `timings` keys that every route of the file-level driver fills: bench.py and the tools read them.  The sets were recorded by
+# running the commit BEFORE the drivers shared one loop on this very input (_ordered_bed: three chromosomes in order, one not).
+_DRIVER_KEYS = {"emulation", "index_scan", "bed_index", "bed_parse", "pack_rows", "reorder", "compute_enqueue", "gather", "sink", "focal_wait",
+                "sink_close"}
+TIMING_KEYS = {
+    "ranked-aligned": _DRIVER_KEYS | {"aligned_shards"},
+    "ranked-gathered": _DRIVER_KEYS,
+    "whole": {"bed_read", "bed_order", "order_columns", "compute_enqueue", "gather", "sink", "focal_wait", "sink_close"},
+    "ranked-emulated": _DRIVER_KEYS | {"aligned_shards"},
+}
+
+
+def test_every_route_fills_its_timings_keys(tmp_path):
+    from mural_amd.predict import TsvSink, predict_bed_sharded
+    bed = str(tmp_path / "o.bed")
+    _ordered_bed(bed)
+    got = {}
+    for route, kw in (("ranked-aligned", dict(collect=False)), ("ranked-gathered", dict(collect=True)), ("whole", dict(ingest="whole")),
+                      ("ranked-emulated", dict(collect=False, emulate=(1, 3)))):
+        sink = TsvSink(str(tmp_path / (route + ".tsv")), parts=kw.get("emulate", False))
+        got[route] = {}
+        predict_bed_sharded(_ordered_forward(), bed, segment_center=700, sink=sink, timings=got[route], **kw)
+        print(route, sorted(got[route]))
+    assert {r: set(t) for r, t in got.items()} == TIMING_KEYS
+    assert got["ranked-aligned"]["aligned_shards"] == 3 and got["ranked-emulated"]["aligned_shards"] == 3
+
+
 def _overlap_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

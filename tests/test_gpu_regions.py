@@ -224,6 +224,17 @@ def test_region_table_is_the_bed_path_s_table(files, snv_model, focal, context, 
     assert chroms == sorted(chroms) and chroms[0] == b"chr10"      # ascending names, not the FASTA's order
 
 
+def test_aligned_region_route_fills_its_timings_keys(files, snv_model):
+    """The `timings` keys of the aligned route (tools/bench_regions.py reads them), as recorded by running the commit BEFORE the drivers
+    shared one loop on this input."""
+    d, fa = files
+    T = {}
+    n, _, _ = _region_table(snv_model, fa, d / "t.tsv", {"chrA": [(40, 90), (3290, 3410)], "chr10": [(0, 100)]}, "A", timings=T)
+    print(sorted(T))
+    assert n > 0 and set(T) == {"emulation", "enumerate", "compute_enqueue", "gather", "sink", "focal_wait", "aligned_shards", "sink_close"}
+    assert T["aligned_shards"] == 2
+
+
 def test_collected_rows_are_the_table_s_rows(files, snv_model):
     """collect=True (and a sink that gets the gathered shard): the same table, and the rows back in its order."""
     from mural_amd.predict import TsvSink, predict_regions_sharded, write_predictions

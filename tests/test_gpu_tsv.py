@@ -86,6 +86,20 @@ def test_focal_group_check_kernel_matches_host_check():
         check_focal_groups(bad[:, 4].astype(np.int64), group)
 
 
+def _border_cases():
+    from tests.test_dist_gloo import border_cases
+    return border_cases()
+
+
+@pytest.mark.parametrize("case", _border_cases(), ids=lambda c: c[0])
+def test_aligned_part_border_record_on_the_device_equals_bed_reader_s_loop(case):
+    """The twin of tests/test_dist_gloo.py's test: the same torch code on device columns, the per-group verdict from the kernel."""
+    from tests.test_dist_gloo import aligned_part_record, border_record_by_loop
+    _, start, strand, focal, anchor, central_bp = case
+    want = border_record_by_loop(start, strand, focal, anchor, central_bp)[0]
+    assert aligned_part_record(torch.device("cuda", torch.cuda.current_device()), start, strand, focal, anchor, central_bp) == want
+
+
 @pytest.mark.parametrize("calibrated", [False, True])
 def test_tsv_sink_with_device_shards_equals_pandas(tmp_path, calibrated, monkeypatch):
     """Device shards (the gathered (n, k + 1) matrix of the sharded driver) through TsvSink: device sort, device calibration,
