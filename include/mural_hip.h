@@ -270,6 +270,8 @@ int mural_op_bn_backward(const float* dz, const float* x, int64_t B, int32_t C, 
 int mural_op_conv_wgrad(const float* dy, const float* x, int64_t B, int32_t C, int32_t L, int32_t K,
                         const float* scale, const float* shift, int32_t pre_relu, float* dW, float* db,
                         float* part, size_t part_floats, void* stream);
+/* MaxPool1d(k, s, p) in floor mode with -inf padding; arg holds the position of the FIRST maximum of each window, like torch.
+ * A NaN input is skipped, not propagated (torch propagates it): the maximum of the window's other values is returned. */
 int mural_op_maxpool_fwd(const float* x, int64_t rows, int32_t L, int32_t k, int32_t s, int32_t p, float* y,
                          int32_t* arg /* argmax positions for the backward; may be NULL (inference) */, void* stream);
 int mural_op_maxpool_bwd_needs_zero(int32_t k, int32_t s);   /* 1: dx must be zeroed by the caller (overlapping windows) */
@@ -293,6 +295,8 @@ int mural_op_linear_bwd(const float* dy, const float* x, const float* W, int64_t
                         float* dW, float* db, void* stream);
 int mural_op_embedding_fwd(const int64_t* cat, const float* E, int64_t B, int32_t cols, int32_t rows, float* y,
                            void* stream);
+/* dE [rows][5] zeroed by the caller; any table size (a table of up to 150 KB is summed in LDS first, a larger one directly);
+ * indices outside [0, rows) count as row 0 / the last row, as in the forward */
 int mural_op_embedding_bwd(const int64_t* cat, const float* dy, int64_t B, int32_t cols, int32_t rows, float* dE,
                            void* stream);
 int mural_op_dropout(const float* x, int64_t total, float p, uint64_t seed, const uint64_t* seed_dev, float* y,

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   const int c = blockIdx.x;
   double s = 0.0, q = 0.0;
   const int64_t per = (int64_t)B * L;
-  if ((L & 3) == 0 && per * C < (int64_t(1) << 31)) {
+  if ((L & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && per * C < (int64_t(1) << 31)) {
     // four consecutive positions per thread: 16-byte loads and 32-bit index math (a 64-bit division per element made the pass
     // ALU-bound on the long rows of the U-Net's first levels)
     const uint32_t nq = (uint32_t)(per >> 2), qstep = gridDim.y * blockDim.x;
@@ -1041,6 +1041,18 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
     if (se[i] != 0.f) atomicAdd(&dE[i], se[i]);
 }
 
+// tables beyond the LDS budget (local_order >= 7: 4^7 + 1 rows): the same walk with the atomics straight into dE
+__global__ __launch_bounds__(256) void embedding_bwd_direct_kernel(const int64_t* __restrict__ cat, const float* __restrict__ dy,
+                                                                   int64_t B, int cols, int rows, float* __restrict__ dE) {
+  const int64_t total = B * cols * 5;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i % 5);
+    int64_t id = cat[i / 5];
+    id = id < 0 ? 0 : (id >= rows ? rows - 1 : id);
+    atomicAdd(&dE[id * 5 + d], dy[i]);
+  }
+}
+
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -1461,11 +1473,21 @@ extern "C" int mural_op_embedding_fwd(const int64_t* cat, const float* E, int64_
   CHECK_LAUNCH();
 }
 
-// dE [rows][5] zeroed by the caller
+// dE [rows][5] zeroed by the caller.  The table is staged in LDS while it fits the budget of the dense tile (150 KB; above 64 KB the
+// kernel opts in once per device); a larger one (local_order >= 7) receives the atomics directly.
 extern "C" int mural_op_embedding_bwd(const int64_t* cat, const float* dy, int64_t B, int32_t cols, int32_t rows, float* dE,
                                       void* stream) {
   const int64_t total = B * cols * 5;
   if (total == 0) return MURAL_OK;
+  const size_t lds = (size_t)rows * 5 * sizeof(float);
+  if (lds > (size_t)150 * 1024) {
+    hipLaunchKernelGGL(embedding_bwd_direct_kernel, dim3(grid_for(total)), dim3(256), 0, STREAM, cat, dy, B, cols, rows, dE);
+    CHECK_LAUNCH();
+  }
+  if (lds > (size_t)64 * 1024) {
+    static DynLdsOnce big_lds;
+    if (int rc = big_lds.ensure(&embedding_bwd_kernel)) return rc;
+  }
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3(grid_for(total, 256, 256)), dim3(256), (size_t)rows * 5 * 4, STREAM, cat, dy, B,
                      cols, rows, dE);
   CHECK_LAUNCH();

@@ -450,6 +450,44 @@ def test_train_step_with_local_order_6_embedding_table():
             assert np.abs(p.grad.cpu().numpy() - w).max() <= 2e-4 * (np.abs(w).max() + 1e-2), (model_no, k)
 
 
+def test_train_step_with_local_order_7_embedding_table():
+    """At order 7 the embedding has 4 ** 7 + 1 = 16385 rows: its gradient table (328 KB) fits no workgroup's LDS, the local branch
+    takes the per-op launches and mural_op_embedding_bwd adds straight into dE.  Network2 against the oracle's autograd, with the
+    bars of the order-6 step."""
+    hp = np.array([7, 7, 100, 150, 75, 32, 3, 4, 2])
+    model, _ = product_from_hp(hp)
+    orc = U.snv_oracle_from_hp(hp, drops=(0.0, 0.0, 0.0))
+    from oracle import synth
+    sd = synth.synth_state_dict(orc.state_dict(), 707)
+    orc.load_state_dict(sd)
+    model.load_state_dict(sd)
+    assert [v.shape[0] for k, v in model.state_dict().items() if k.endswith("emb_layer.weight")] == [16385]
+    for m in model.modules():
+        if isinstance(m, nn.Dropout):
+            m.p = 0.0
+    model = model.cuda().train()
+    orc.train()
+    rng = np.random.default_rng(7)
+    B = 40
+    codes = rng.integers(0, 4, size=(B, 201)).astype(np.uint8)
+    cat = torch.from_numpy(rng.integers(0, 16385, size=(B, 9)).astype(np.int64))
+    cat[0, :3] = 16384                                 # the padding row
+    y = torch.from_numpy(rng.integers(0, 4, size=B))
+    x = U.onehot(codes)
+    crit = nn.CrossEntropyLoss(reduction="sum")
+    want = crit(orc((torch.zeros(B, 1, dtype=torch.float64), cat), x), y)
+    want.backward()
+    got = crit(model((torch.zeros(B, 1, device="cuda"), cat.cuda()), x.cuda()), y.cuda())
+    got.backward()
+    assert abs(got.item() - want.item()) <= 1e-4 * abs(want.item())
+    ref = dict(orc.named_parameters())
+    for k, p in model.named_parameters():
+        if ".layer." in k or p.numel() == 0:
+            continue
+        w = ref[k].grad.numpy()
+        assert np.abs(p.grad.cpu().numpy() - w).max() <= 2e-4 * (np.abs(w).max() + 1e-2), k
+
+
 def test_graphed_train_step_matches_eager():
     """hipGraph replay of the whole step (mural_amd.train.GraphedTrainStep) == the eager step: same parameters after the
     same batches (dropout off so both paths are deterministic), and a non-encoding input is reported one step late."""
