@@ -548,6 +548,45 @@ int mural_table_start_range(const int32_t* chrom_id, const int64_t* start, int64
                             int64_t* mx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Genome summaries of a shard while it is on the device (mural_amd/predict.py: SummarySink; csrc/summary.hip): what
+ * mural_eval_window_keys + mural_eval_group_obs_pred and mural_table_prob_sum compute from the written table, in one pass
+ * over the rows of ONE chromosome that ascend in start.  No floating-point atomics: the result depends on the input (and the
+ * fixed chunk of mural_summary_chunk_rows() rows per workgroup) alone, bit for bit.  float64 sums, exact counts.
+ *   window tables: table[j] [n_bins[j]][1 + 2 n_class] += { rows, rows with label c, sum of prob[:, c] } of the rows with
+ *     start / window[j] - bin0[j] == bin (the row layout of mural_eval_group_obs_pred); zeroed by the caller before the
+ *     first part of a chromosome;
+ *   totals: total[0] += sum_rows w * sum_{c>=1} prob[c], n_sites[0] += sum_rows w; w = 1 (reg_b0 NULL) or the number of
+ *     regions overlapping [start, end), reg_b0 / reg_b1 [n_reg] the chromosome's region starts / ends, each sorted
+ *     (mural_table_prob_sum's rule);
+ *   status (device int32): bit 0 a negative start, bit 1 a label outside 0 .. n_class - 1 (or no whole number), bit 2 a
+ *     start outside a table's windows or below an earlier row's; such rows are skipped.
+ * Two launches on `stream`, no synchronisation.  n_class <= 8.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MURAL_SUMMARY_MAX_WINDOWS 4
+typedef struct {
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 0 .. n_class-1 are read          */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n] */
+  const int64_t* end;        /* dev [n] (read with regions only) */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_windows;
+  int64_t window[MURAL_SUMMARY_MAX_WINDOWS], bin0[MURAL_SUMMARY_MAX_WINDOWS], n_bins[MURAL_SUMMARY_MAX_WINDOWS];
+  double* table[MURAL_SUMMARY_MAX_WINDOWS];         /* dev */
+  const int64_t* reg_b0;     /* dev [n_reg] or NULL */
+  const int64_t* reg_b1;
+  int64_t n_reg;
+  double* total;             /* dev [1] */
+  int64_t* n_sites;          /* dev [1] */
+  int32_t* status;           /* dev [1] */
+} MuralSummaryRows;
+int32_t mural_summary_chunk_rows(void);
+size_t mural_summary_workspace_bytes(int64_t n, int32_t n_class, int32_t n_windows);
+/* ws: device scratch of mural_summary_workspace_bytes(n, n_class, n_windows) bytes, 8-byte aligned                          */
+int mural_summary_rows(const MuralSummaryRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

@@ -92,6 +92,14 @@ class MuralTableChunk(C.Structure):
                 ("text_bytes", C.c_int64)]
 
 
+class MuralSummaryRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("label_kind", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
+                ("end", C.c_void_p), ("label", C.c_void_p), ("n", C.c_int64), ("n_class", C.c_int32), ("n_windows", C.c_int32),
+                ("window", C.c_int64 * 4), ("bin0", C.c_int64 * 4), ("n_bins", C.c_int64 * 4), ("table", C.c_void_p * 4),
+                ("reg_b0", C.c_void_p), ("reg_b1", C.c_void_p), ("n_reg", C.c_int64), ("total", C.c_void_p), ("n_sites", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
 
 # every symbol include/mural_hip.h declares: name -> (restype, argtypes)
@@ -213,6 +221,9 @@ PROTOTYPES = {
     "mural_table_kmer_keys": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, I64, I32, I32, I32, VP, VP, VP]),
     "mural_table_first_row": (C.c_int, [VP, I64, I64, I32, I32, VP, VP]),
     "mural_table_start_range": (C.c_int, [VP, VP, I64, I32, VP, VP, VP]),
+    "mural_summary_chunk_rows": (I32, []),
+    "mural_summary_workspace_bytes": (C.c_size_t, [I64, I32, I32]),
+    "mural_summary_rows": (C.c_int, [C.POINTER(MuralSummaryRows), VP, C.c_size_t, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

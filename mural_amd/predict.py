@@ -841,6 +841,343 @@ def _refuse_second_calibration(rows, poisson, dirichlet_weights):
                          "dirichlet_weights= here, or build the forward with poisson=False")
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# genome summaries in flight: what calc_scaling_factor and evaluate --window_size read from the written table, reduced from the
+# shards while they are on the device (csrc/summary.hip), so that a summary-only pass needs no table at all
+# ------------------------------------------------------------------------------------------------------------------
+_SUMMARY_STATUS = ((2, "a mut_type outside 0 .. n_class - 1"), (1, "a negative start"),
+                   (4, "rows of a chromosome that do not ascend in start"))
+
+
+def summary_rows_host(prob, start, end, label, n_class, windows, regions=None):
+    """The numpy twin of ``mural_summary_rows`` for the rows of one chromosome (any order): ({W: (bin0, table [bins][1 + 2 n_class])},
+    prob_sum, n_sites, status).  float64, ``np.add.at`` in row order; `regions`: (sorted starts, sorted ends) of the chromosome's
+    benchmark regions or None; status bits as on the device (a negative start 1, a label outside 0 .. n_class - 1 2)."""
+    k = int(n_class)
+    prob = np.asarray(prob)[:, :k].astype(np.float64)
+    start, end, label = np.asarray(start, np.int64), np.asarray(end, np.int64), np.asarray(label)
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= k) | (lab != label)
+    bad_start = start < 0
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0)
+    ok = ~(bad_label | bad_start)
+    prob, start, end, lab = prob[ok], start[ok], end[ok], lab[ok]
+    tables = {}
+    for W in windows:
+        if len(start) == 0:
+            tables[W] = (0, np.zeros((0, 1 + 2 * k)))
+            continue
+        b = start // W
+        bin0 = int(b.min())
+        t = np.zeros((int(b.max()) - bin0 + 1, 1 + 2 * k))
+        np.add.at(t[:, 0], b - bin0, 1.0)
+        np.add.at(t, (b - bin0, 1 + lab), 1.0)
+        for c in range(k):
+            np.add.at(t[:, 1 + k + c], b - bin0, prob[:, c])
+        tables[W] = (bin0, t)
+    if regions is None:
+        w = np.ones(len(start), np.int64)
+    else:
+        w = np.searchsorted(regions[0], end, "left") - np.searchsorted(regions[1], start, "right")
+    total = 0.0
+    for v in (w * prob[:, 1:].sum(axis=1))[w > 0].tolist():
+        total += v
+    return tables, total, int(w[w > 0].sum()), status
+
+
+def _merge_window_table(have, bin0, table):
+    """(bin0, table) of a chromosome's windows so far + one part's: the covering table, the part added behind what was there."""
+    if have is None or have[1].shape[0] == 0:
+        return bin0, table.copy()
+    if table.shape[0] == 0:
+        return have
+    b0, t = have
+    lo, hi = min(b0, bin0), max(b0 + t.shape[0], bin0 + table.shape[0])
+    if lo != b0 or hi != b0 + t.shape[0]:
+        grown = np.zeros((hi - lo, t.shape[1]))
+        grown[b0 - lo:b0 - lo + t.shape[0]] = t
+        b0, t = lo, grown
+    t[bin0 - b0:bin0 - b0 + table.shape[0]] += table
+    return b0, t
+
+
+class SummarySink:
+    """Consumer of shards (the TsvSink protocol) that keeps no row: per window size of `windows` the table ``tables.regional_table``
+    would read back from the written prediction table, and the (prob_sum, n_sites) of ``tables.prob_sum_file`` -- optionally counted per
+    overlapping benchmark region (`benchmark_regions`: a BED path or ``tables.read_regions``' dict) --, reduced from the probabilities
+    the table would hold, before they are rounded to four digits.  Device shards go through csrc/summary.hip (one pass per part, the
+    tables of a part sized from its first and last start and merged on the host in arrival order; nothing waits for work just enqueued:
+    a part is reduced when the next one arrives); host shards through numpy.  Calibration: as TsvSink (`poisson`, `dirichlet_weights`;
+    refused for shards that are calibrated already).  ``parts=True`` under torch.distributed: every rank reduces its rows and close()
+    gathers the ranks' tables -- not rows -- and adds them in rank order.
+
+    close() writes, with an `out_prefix` and on rank 0, ``{out_prefix}.{W/1000}Kb.mut_rates.tsv`` / ``.corr.txt`` per window size
+    (``tables.write_regional_outputs``: the files of ``evaluate --window_size``); ``result()`` and ``scaling_factor()`` are valid after
+    it."""
+
+    takes_aligned_blocks = True
+
+    def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
+                 group=None, parts=False):
+        self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
+        self.windows = tuple(int(w) for w in windows)
+        if any(w <= 0 for w in self.windows) or len(set(self.windows)) != len(self.windows):
+            raise ValueError(f"window sizes must be positive and distinct (got {self.windows})")
+        if isinstance(benchmark_regions, (str, os.PathLike)):
+            from .tables import read_regions
+            benchmark_regions = read_regions(benchmark_regions)
+        self._regions = None if benchmark_regions is None else {
+            c: (np.sort(np.asarray(a, np.int64)), np.sort(np.asarray(b, np.int64))) for c, (a, b) in benchmark_regions.items()}
+        self.ratio_cutoff, self.poisson, self.dirichlet_weights, self.group = ratio_cutoff, poisson, dirichlet_weights, group
+        self.rank = dist.get_rank(group) if (parts and dist.is_initialized()) else 0
+        self.world = dist.get_world_size(group) if (parts and dist.is_initialized()) else 1
+        self.parts = self.world > 1
+        self.rows = 0
+        self._n_class = None
+        self._tables = {}              # chromosome -> {W: (bin0, table)}
+        self._prob_sum, self._n_sites, self._status = 0.0, 0, 0
+        self._pending = None           # a staged device part: reduced when the next one arrives (or at close)
+        self._inflight = []            # [(event, pinned result, chromosome, [(W, bin0, bins)])] of launched parts
+        self._dev_regions = {}
+        self._written = []
+        self._result = None
+
+    # -- one part ---------------------------------------------------------------------------------------------------------
+    def _take(self, name, tables, total, n_sites, status):
+        mine = self._tables.setdefault(name, {})
+        for W, (bin0, t) in tables.items():
+            mine[W] = _merge_window_table(mine.get(W), bin0, t)
+        self._prob_sum += total
+        self._n_sites += n_sites
+        self._status |= status
+
+    def _host_part(self, name, shard, k):
+        prob = TsvSink._host_prob(self, np.asarray(shard["prob"])[:, :k])
+        start = np.asarray(shard["start"])
+        cols = [start, np.asarray(shard["end"]), np.asarray(shard["label"]), prob]
+        if not shard.get("aligned"):
+            perm = np.argsort(start, kind="stable")
+            if self.parts:
+                perm = perm[slice(*shard_bounds(len(perm), self.rank, self.world))]
+            cols = [c[perm] for c in cols]
+        regs = None if self._regions is None else self._regions.get(name, (np.zeros(0, np.int64),) * 2)
+        self._take(name, *summary_rows_host(cols[3], cols[0], cols[1], cols[2], k, self.windows, regs))
+
+    def _stage_device(self, name, shard, k):
+        """Calibrate and order the part on its device, start the read-back of its first and last start."""
+        prob = shard["prob"]
+        dev = prob.device
+        with torch.cuda.device(dev):
+            if self.dirichlet_weights is not None or self.poisson:
+                from .calibration import calibrate_device
+                prob = calibrate_device(prob[:, :k].contiguous() if prob.stride(0) != k else prob, dirichlet_weights=self.dirichlet_weights,
+                                        poisson=self.poisson, input_is_prob=True)
+            if prob.dtype not in (torch.float32, torch.float64):
+                prob = prob.to(torch.float32)
+            if prob.stride(1) != 1:
+                prob = prob.contiguous()
+            to = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, dt).contiguous()   # noqa: E731
+            start, end = to(shard["start"], torch.int64), to(shard["end"], torch.int64)
+            label = shard["label"]
+            label = to(label, label.dtype if isinstance(label, torch.Tensor) and label.dtype in (torch.int32, torch.int64) else torch.float32)
+            if not shard.get("aligned"):
+                perm = torch.sort(start, stable=True).indices
+                if self.parts:
+                    perm = perm[slice(*shard_bounds(perm.shape[0], self.rank, self.world))]
+                prob, start, end, label = prob[perm], start[perm], end[perm], label[perm]
+            if start.shape[0] == 0:
+                return None
+            ends = torch.empty(2, dtype=torch.int64).pin_memory()
+            ends.copy_(torch.stack([start[0], start[-1]]), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        return dict(name=name, prob=prob, start=start, end=end, label=label, k=k, ends=ends, event=ev, dev=dev)
+
+    def _launch_pending(self):
+        """Reduce the staged part: its first and last start (read back by now) size the part's window tables."""
+        p, self._pending = self._pending, None
+        if p is None:
+            return
+        lib = _lib.lib()
+        p["event"].synchronize()
+        self._harvest(done_only=True)                      # (every part launched before is complete by now: same stream)
+        dev, k, n = p["dev"], p["k"], p["start"].shape[0]
+        lo = max(int(p["ends"][0]), 0)
+        hi = max(int(p["ends"][1]), lo)
+        stride = 1 + 2 * k
+        layout, off = [], 3
+        for W in self.windows:
+            bin0, bins = lo // W, hi // W - lo // W + 1
+            if bins * stride >= 2 ** 31:
+                raise ValueError(f"the rows of one part span {bins} windows of {W} bp: too many for one table")
+            layout.append((W, bin0, bins, off))
+            off += bins * stride
+        with torch.cuda.device(dev):
+            out = torch.zeros(off, dtype=torch.float64, device=dev)      # total | n_sites (int64) | status (int32) | the tables
+            regs = None
+            if self._regions is not None:
+                regs = self._dev_regions.get((p["name"], dev))
+                if regs is None:
+                    b0, b1 = self._regions.get(p["name"], (np.zeros(0, np.int64),) * 2)
+                    regs = (torch.from_numpy(np.r_[b0, 0]).to(dev), torch.from_numpy(np.r_[b1, 0]).to(dev), len(b0))
+                    self._dev_regions = {(p["name"], dev): regs}
+            stream = _lib.current_stream_ptr(dev)
+            for g in range(0, max(len(layout), 1), 4):      # MURAL_SUMMARY_MAX_WINDOWS window sizes per call; the totals with the first
+                group = layout[g:g + 4]
+                s = _lib.MuralSummaryRows()
+                s.prob, s.prob_f64, s.prob_stride = p["prob"].data_ptr(), int(p["prob"].dtype == torch.float64), p["prob"].stride(0)
+                s.start, s.end, s.label, s.n, s.n_class = p["start"].data_ptr(), p["end"].data_ptr(), p["label"].data_ptr(), n, k
+                s.label_kind = {torch.float32: 0, torch.int32: 1, torch.int64: 2}[p["label"].dtype]
+                s.n_windows = len(group)
+                for j, (W, bin0, bins, o) in enumerate(group):
+                    s.window[j], s.bin0[j], s.n_bins[j], s.table[j] = W, bin0, bins, out[o:].data_ptr()
+                if regs is not None and g == 0:
+                    s.reg_b0, s.reg_b1, s.n_reg = regs[0].data_ptr(), regs[1].data_ptr(), regs[2]
+                # the totals of a later group of window sizes go to a scratch cell: they are counted once
+                tot = out if g == 0 else torch.zeros(2, dtype=torch.float64, device=dev)
+                s.total, s.n_sites, s.status = tot.data_ptr(), tot[1:].data_ptr(), out[2:].data_ptr()
+                ws = torch.empty(int(lib.mural_summary_workspace_bytes(n, k, len(group))) // 8 + 1, dtype=torch.int64, device=dev)
+                _lib.check(lib.mural_summary_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, stream))
+            host = torch.empty(off, dtype=torch.float64).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._inflight.append((ev, host, p["name"], k, layout))
+
+    def _harvest(self, done_only=False):
+        keep = []
+        for item in self._inflight:
+            ev, host, name, k, layout = item
+            if done_only and (keep or not ev.query()):      # (in arrival order: nothing overtakes an unfinished part)
+                keep.append(item)
+                continue
+            ev.synchronize()
+            a = host.numpy()
+            stride = 1 + 2 * k
+            tables = {W: (bin0, a[o:o + bins * stride].reshape(bins, stride)) for W, bin0, bins, o in layout}
+            self._take(name, tables, float(a[0]), int(a[1:2].view(np.int64)[0]), int(a[2:3].view(np.int32)[0]))
+        self._inflight = keep
+
+    def __call__(self, shard):
+        name = TsvSink._name(shard)
+        n = len(shard["start"])
+        if name is None or n == 0:
+            return
+        _refuse_second_calibration(shard, self.poisson, self.dirichlet_weights)
+        k = int(shard.get("n_class", shard["prob"].shape[1]))
+        if self._n_class not in (None, k):
+            raise ValueError(f"shards of {self._n_class} and of {k} classes in one summary")
+        self._n_class = k
+        self.rows += n
+        if isinstance(shard["prob"], torch.Tensor) and shard["prob"].is_cuda:
+            if k > 8:
+                raise ValueError("SummarySink reduces at most 8 classes on the device")
+            staged = self._stage_device(name, shard, k)      # enqueued behind this part's forward ...
+            self._launch_pending()                           # ... while the part before it, complete by now, is reduced
+            self._pending = staged
+        else:
+            if isinstance(shard["prob"], torch.Tensor):
+                shard = dict(shard, prob=shard["prob"].numpy())
+            self._host_part(name, {key: (_np(v) if isinstance(v, torch.Tensor) else v) for key, v in shard.items()}, k)
+
+    # -- close ------------------------------------------------------------------------------------------------------------
+    def _merged(self, states):
+        """[(tables, prob_sum, n_sites, status, n_class)] of the ranks, added in rank order."""
+        tables, prob_sum, n_sites, status, k = {}, 0.0, 0, 0, None
+        for t, s, c, st, kk in states:
+            for name, per_w in t.items():
+                mine = tables.setdefault(name, {})
+                for W, (bin0, tab) in per_w.items():
+                    mine[W] = _merge_window_table(mine.get(W), bin0, tab)
+            prob_sum, n_sites, status = prob_sum + s, n_sites + c, status | st
+            k = kk if k is None else k
+        return tables, prob_sum, n_sites, status, k
+
+    def close(self):
+        self._launch_pending()
+        self._harvest()
+        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class)
+        if self.world > 1:
+            every = [None] * self.world
+            dist.all_gather_object(every, state, group=self.group)      # the one collective: tables, not rows
+            state = self._merged(every)
+        tables, prob_sum, n_sites, status, k = state
+        for bit, what in _SUMMARY_STATUS:
+            if status & bit:
+                raise ValueError(f"summary: {what}")
+        windows = {}
+        for W in self.windows:
+            keys, rows = [], []
+            for name in sorted(tables):
+                bin0, t = tables[name].get(W, (0, np.zeros((0, 1))))
+                live = np.nonzero(t[:, 0] > 0)[0]
+                keys += [(name, int((bin0 + g) * W + W)) for g in live]
+                rows.append(t[live])
+            windows[W] = (keys, np.concatenate(rows) if rows else np.zeros((0, 1 + 2 * (k or 0))))
+        self._result = {"prob_sum": prob_sum, "n_sites": n_sites, "windows": windows}
+        if self.out_prefix is not None and self.rank == 0 and k is not None:
+            from .tables import regional_output_names, write_regional_outputs
+            for W in self.windows:
+                self._written += list(regional_output_names(self.out_prefix, W)[:2])
+                write_regional_outputs(*windows[W], k, W, self.out_prefix, self.ratio_cutoff)
+
+    def abort(self):
+        """Drop what was reduced and remove any file close() began: the caller's run failed."""
+        self._pending, self._inflight, self._tables, self._result = None, [], {}, None
+        for path in self._written:
+            if os.path.exists(path):
+                os.unlink(path)
+        self._written = []
+
+    def result(self):
+        """{"prob_sum", "n_sites", "windows": {W: ([(chrom, window_end)], table [windows][1 + 2 n_class])}} after close(): the pair of
+        ``tables.prob_sum_file`` and, per window size, of ``tables.regional_table`` (chromosomes by name, windows ascending)."""
+        if self._result is None:
+            raise RuntimeError("SummarySink.result() is valid after close()")
+        return self._result
+
+    def scaling_factor(self, genomewide_mu, m_proportion, g_proportion=1.0):
+        """``tables.calc_mu_scaling_factor``'s factor for the summarised rows, with the lines it prints."""
+        from .tables import mu_scaling_factor, print_scaling_factor
+        res = self.result()
+        factor = mu_scaling_factor(genomewide_mu, res["n_sites"], m_proportion, g_proportion, res["prob_sum"])
+        print_scaling_factor(genomewide_mu, res["n_sites"], g_proportion, m_proportion, res["prob_sum"], factor)
+        return factor
+
+
+class TeeSink:
+    """One shard loop, several consumers: every shard, close() and abort() go to each of `sinks` in turn.  The tee takes aligned blocks,
+    and is a part-file sink, only if all of them do / are; when one of them raises, the others are aborted before the error goes on."""
+
+    def __init__(self, *sinks):
+        if not sinks:
+            raise ValueError("TeeSink needs a sink")
+        self.sinks = sinks
+        self.takes_aligned_blocks = all(getattr(s, "takes_aligned_blocks", False) for s in sinks)
+        self.parts = all(getattr(s, "parts", False) for s in sinks)
+
+    def _each(self, call):
+        for i, s in enumerate(self.sinks):
+            try:
+                call(s)
+            except BaseException:
+                for other in self.sinks[:i] + self.sinks[i + 1:]:
+                    if hasattr(other, "abort"):
+                        other.abort()
+                raise
+
+    def __call__(self, shard):
+        self._each(lambda s: s(shard))
+
+    def close(self):
+        self._each(lambda s: s.close() if hasattr(s, "close") else None)
+
+    def abort(self):
+        for s in self.sinks:
+            if hasattr(s, "abort"):
+                s.abort()
+
+
 def write_predictions(res, path, poisson=False, dirichlet_weights=None):
     """The prediction table of run_predict.py:217-239 from the dict returned by ``predict_bed`` / ``predict_bed_sharded``: optional
     Dirichlet calibration (``calibration.load_dirichlet_weights`` of the model's ``model.fdiri_cal.pkl``), optional Poisson

@@ -338,14 +338,9 @@ def calc_mu_scaling_factor(args, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
     factors = []
     for i, pred_file in enumerate(pred_files):
         prob_sum, n_sites = prob_sum_file(pred_file, args.n_class, getattr(args, "benchmark_regions", None) or None, chunk_bytes)
-        factor = (args.genomewide_mu * n_sites * m_props[i] / g_props[i]) / prob_sum
+        factor = mu_scaling_factor(args.genomewide_mu, n_sites, m_props[i], g_props[i], prob_sum)
         print("\nType " + str(i + 1) + ":\n" + "pred_file:", pred_file)
-        print("genomewide_mu:", args.genomewide_mu)
-        print("n_sites:", n_sites)
-        print("g_proportion:", g_props[i])
-        print("m_proportion:", m_props[i])
-        print("prob_sum: %.3e" % prob_sum)
-        print("scaling factor: %.3e" % factor)
+        print_scaling_factor(args.genomewide_mu, n_sites, g_props[i], m_props[i], prob_sum, factor)
         if args.do_scaling:
             apply_scaling_file(pred_file, factor, args.n_class, scaled_output_name(pred_file), chunk_bytes=chunk_bytes)
         factors.append(factor)
@@ -506,22 +501,21 @@ def regional_table(pred_file, window_size, n_class, chunk_bytes=DEFAULT_CHUNK_BY
     return [keys_out[j] for j in order], tab[order]
 
 
-def run_regional_corr_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
-    """calc_regional_corr.py:164-212: per window observed / predicted rates (float32), used_or_deprecated by ratio_cutoff *
-    median(number_of_all), Pearson r over the used windows; writes {out_prefix}.{W/1000}Kb.mut_rates.tsv and .corr.txt."""
-    n_class = args.n_class
-    W = int(args.window_size)
-    keys, table = regional_table(os.fspath(args.pred_file), W, n_class, chunk_bytes)
+def write_regional_outputs(keys, table, n_class, window_size, out_prefix, ratio_cutoff):
+    """The two files of calc_regional_corr.py:190-212 from a window table (``regional_table``'s pair, or the one a
+    ``predict.SummarySink`` reduced in flight): per window observed / predicted rates (float32), used_or_deprecated by
+    ratio_cutoff * median(number_of_all), Pearson r over the used windows.  Returns [(class, (r, p))]."""
+    W = int(window_size)
     obs, pred, cnt, tot = _rates(table, n_class)
     obs32, pred32 = obs.astype(np.float32), pred.astype(np.float32)
-    cutoff = float(args.ratio_cutoff) * np.median(tot.astype(np.uint64))
+    cutoff = float(ratio_cutoff) * np.median(tot.astype(np.uint64))
     used = tot >= cutoff
     cls = range(1, n_class)
     header = (["chrom", "window_end"] + [f"avg_obs_rate{i}" for i in cls] + [f"avg_pred_rate{i}" for i in cls]
               + [f"number_of_mut{i}" for i in cls] + ["number_of_all", "used_or_deprecated"])
     rows = [[ch, str(we)] + [str(v) for v in obs32[j]] + [str(v) for v in pred32[j]] + [str(int(v)) for v in cnt[j]]
             + [str(int(tot[j])), "used" if used[j] else "deprecated"] for j, (ch, we) in enumerate(keys)]
-    rates_path, corr_path, window = regional_output_names(args.out_prefix, W)
+    rates_path, corr_path, window = regional_output_names(out_prefix, W)
     corrs = [(c, pearson(obs32[used, c - 1], pred32[used, c - 1])) for c in cls]
     with open(rates_path, "w") as fh:
         fh.write(_rates_text(header, rows))
@@ -530,9 +524,32 @@ def run_regional_corr_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
     return corrs
 
 
+def run_regional_corr_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """calc_regional_corr.py:164-212: per window observed / predicted rates (float32), used_or_deprecated by ratio_cutoff *
+    median(number_of_all), Pearson r over the used windows; writes {out_prefix}.{W/1000}Kb.mut_rates.tsv and .corr.txt."""
+    W = int(args.window_size)
+    keys, table = regional_table(os.fspath(args.pred_file), W, args.n_class, chunk_bytes)
+    return write_regional_outputs(keys, table, args.n_class, W, args.out_prefix, args.ratio_cutoff)
+
+
+def mu_scaling_factor(genomewide_mu, n_sites, m_proportion, g_proportion, prob_sum):
+    """scaling.py:92: the factor that makes the mean predicted rate of the table genomewide_mu * m_proportion / g_proportion."""
+    return (genomewide_mu * n_sites * m_proportion / g_proportion) / prob_sum
+
+
+def print_scaling_factor(genomewide_mu, n_sites, g_proportion, m_proportion, prob_sum, factor):
+    """The lines calc_mu_scaling_factor prints below a prediction file's name (scaling.py:94-100)."""
+    print("genomewide_mu:", genomewide_mu)
+    print("n_sites:", n_sites)
+    print("g_proportion:", g_proportion)
+    print("m_proportion:", m_proportion)
+    print("prob_sum: %.3e" % prob_sum)
+    print("scaling factor: %.3e" % factor)
+
+
 # the reference's module-level name of the file-to-file scaling (scaling.py:10); mural_amd.calibration.apply_scaling is the
 # in-memory rule and stays as it is
 apply_scaling = apply_scaling_file
 
-__all__ = ["TableReader", "apply_scaling_file", "scaling_files", "calc_mu_scaling_factor", "run_kmer_corr_calc", "run_regional_corr_calc",
+__all__ = ["TableReader", "apply_scaling_file", "scaling_files", "calc_mu_scaling_factor", "run_kmer_corr_calc", "run_regional_corr_calc", "write_regional_outputs",
            "prob_sum_file", "read_regions", "kmer_table", "regional_table", "check_header", "read_header", "DEFAULT_CHUNK_BYTES", "MAX_KMER"]

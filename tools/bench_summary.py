@@ -1,0 +1,104 @@
+"""Genome summaries in flight against the table route to the same numbers:
+  python tools/bench_summary.py [--bases N] [--repeats K]
+
+One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
+the device (predict_regions_sharded), files in /dev/shm.  Four legs, alternating, --repeats timed runs each after one warm-up run each:
+  a  table     TsvSink alone: the '%.4g' table, nothing else
+  b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
+  c  tee       TeeSink of both
+  d  tools     the route to b's numbers without this sink: leg a's table, then prob_sum_file + regional_table (100 kb, 1 kb) on it
+Prints one JSON line; the summary of leg b must agree with leg d's within the table's four digits."""
+import json
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch  # noqa: E402
+
+from bench import shipped_snv_model  # noqa: E402
+from bench_regions import spread, write_inputs  # noqa: E402
+from mural_amd import tables  # noqa: E402
+from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, predict_regions_sharded  # noqa: E402
+
+WINDOWS = (100_000, 1000)
+LEGS = ("table", "summary", "tee", "tools")
+
+
+def main(argv):
+    bases = int(argv[argv.index("--bases") + 1]) if "--bases" in argv else 50_000_000
+    repeats = int(argv[argv.index("--repeats") + 1]) if "--repeats" in argv else 3
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_summary needs a HIP device")
+    device = torch.device("cuda", 0)
+    model, r, order, _ = shipped_snv_model(device)
+    n_class = model.n_class
+    shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) and shutil.disk_usage("/dev/shm").free > 100 * bases else None
+    with tempfile.TemporaryDirectory(prefix="mural_summary_", dir=shm) as work:
+        fa, _, genome, rows = write_inputs(work, device, bases)
+        del genome
+        torch.cuda.empty_cache()
+        out = os.path.join(work, "table.tsv")
+        kept = {}
+
+        def run(leg):
+            split, extra = {}, {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fwd = HipShardForward(model, fa, r, order, device=device, reuse=True)
+            summary = SummarySink(windows=WINDOWS) if leg in ("summary", "tee") else None
+            sink = {"table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary,
+                    "tee": lambda: TeeSink(TsvSink(out), summary)}[leg]()
+            n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split)
+            torch.cuda.synchronize()
+            extra["predict"] = time.perf_counter() - t0
+            if leg == "tools":
+                t1 = time.perf_counter()
+                total, n_sites = tables.prob_sum_file(out, n_class)
+                extra["prob_sum_file"] = time.perf_counter() - t1
+                wins = {}
+                for W in WINDOWS:
+                    t1 = time.perf_counter()
+                    wins[W] = tables.regional_table(out, W, n_class)
+                    extra["regional_table_%d" % W] = time.perf_counter() - t1
+                kept["tools"] = {"prob_sum": total, "n_sites": n_sites, "windows": wins}
+            dt = time.perf_counter() - t0
+            assert n == rows, (leg, n, rows)
+            if summary is not None:
+                kept[leg] = summary.result()
+            return dt, dict({k: v for k, v in split.items() if isinstance(v, float)}, **extra)
+
+        seconds, splits = {leg: [] for leg in LEGS}, {}
+        for i in range(repeats + 1):
+            for leg in LEGS:
+                dt, split = run(leg)
+                if i:                                      # (round 0 warms kernels, allocator pools and the page cache)
+                    seconds[leg].append(dt)
+                    splits[leg] = split
+        table_bytes = os.path.getsize(out)
+    a, d = kept["summary"], kept["tools"]
+    agree = a["n_sites"] == d["n_sites"] and abs(a["prob_sum"] - d["prob_sum"]) <= 5e-4 * a["prob_sum"] and kept["tee"]["n_sites"] == a["n_sites"]
+    for W in WINDOWS:
+        (ka, ta), (kd, td) = a["windows"][W], d["windows"][W]
+        k = 1 + n_class
+        agree = agree and ka == kd and (ta[:, :k] == td[:, :k]).all() and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
+        agree = agree and bool((kept["tee"]["windows"][W][1] == ta).all())      # bit for bit, with or without the table beside it
+    rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in LEGS}
+    med = {leg: rate[leg]["median"] for leg in LEGS}
+    res = {"workload": "one chromosome of %d bases, focal A, Homo_sapiens/SNV/AT weights, sites enumerated on the device" % bases,
+           "rows": rows, "table_bytes": table_bytes, "windows": list(WINDOWS), "repeats": repeats, "summaries_agree": bool(agree),
+           "rows_per_s": rate, "summary_over_table": med["summary"] / med["table"], "tee_over_table": med["tee"] / med["table"],
+           "tools_over_summary_seconds": statistics.median(seconds["tools"]) / statistics.median(seconds["summary"]),
+           "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}
+    print(json.dumps(res))
+    if not agree:
+        raise SystemExit("the in-flight summary differs from the table tools'")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

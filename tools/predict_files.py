@@ -4,7 +4,15 @@ minus its CLI): python tools/predict_files.py MODEL FASTA BED OUT.tsv [--indel] 
 Without a BED file -- the sites are enumerated from the FASTA on the device (mural_amd.predict.predict_regions_sharded):
   python tools/predict_files.py MODEL FASTA OUT.tsv --regions SPEC [--regions SPEC ..] [--focal A|C] [--context all|CpG|nonCpG]
 SPEC: chr, chr:start-end (1-based, inclusive) or a BED-like file of regions; --focal defaults to A (with --indel every A/C/G/T
-position is a site and --focal / --context do not apply)."""
+position is a site and --focal / --context do not apply).
+
+Genome summaries in flight, in both forms (mural_amd.predict.SummarySink; the numbers `calc_scaling_factor` and `evaluate --window_size`
+read back from the table, taken from the probabilities before they are rounded):
+  --summary PREFIX  --window_size W [--window_size W ..]   PREFIX.{W/1000}Kb.mut_rates.tsv and .corr.txt per window size
+  --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
+  --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
+  --no-table                                                 summaries only: leave OUT.tsv out
+  --scale_factor F                                           write the table scaled by F (the second pass of the two)"""
 import os
 import sys
 
@@ -13,7 +21,9 @@ from mural_amd.calibration import load_dirichlet_weights  # noqa: E402
 from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
-_VALUE_OPTIONS = ("--regions", "--focal", "--context")
+_SUMMARY_OPTIONS = ("--summary", "--window_size", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
+                    "--scale_factor")
+_VALUE_OPTIONS = ("--regions", "--focal", "--context") + _SUMMARY_OPTIONS
 
 
 def _split(argv):
@@ -39,12 +49,22 @@ def main(argv):
     flags, args, values = _split(argv)
     model_type = "indel" if "--indel" in flags else "snv"
     poisson = "--poisson" in flags or model_type == "indel"
-    if "--regions" in values:
-        if len(args) != 3 or len(values.get("--focal", [])) > 1 or len(values.get("--context", [])) > 1:
-            raise SystemExit(__doc__)
-        return _main_regions(args, values, flags, model_type, poisson)
-    if len(args) != 4 or values:
+    opts = _summary_options(flags, values)
+    n_args = (3 if "--regions" in values else 4) - int(opts["no_table"])
+    if opts["no_table"] and len(args) == n_args + 1:
+        raise SystemExit(f"--no-table writes no table: leave {args[-1]} out")
+    if len(args) != n_args:
         raise SystemExit(__doc__)
+    if opts["no_table"]:
+        args = args + [None]
+    if "--regions" in values:
+        if len(values.get("--focal", [])) > 1 or len(values.get("--context", [])) > 1:
+            raise SystemExit(__doc__)
+        return _main_regions(args, values, flags, model_type, poisson, opts)
+    if set(values) - set(_SUMMARY_OPTIONS):
+        raise SystemExit(__doc__)
+    if opts["any"]:
+        return _main_bed_sharded(args, flags, model_type, poisson, opts)
     model_path, fasta, bed, out = args
     model, cfg = load_model(model_path, model_type=model_type)
     res = predict_bed(model, fasta, bed, cfg["local_radius"], cfg.get("local_order", 3), distal_radius=cfg["distal_radius"],
@@ -55,7 +75,66 @@ def main(argv):
     print(f"{len(res['start'])} sites -> {out}")
 
 
-def _main_regions(args, values, flags, model_type, poisson):
+def _summary_options(flags, values):
+    """The summary / scaling options, checked before anything is loaded."""
+    one = lambda name, kind: None if name not in values else kind(values[name][-1])      # noqa: E731
+    opts = {"summary": one("--summary", str), "windows": tuple(int(w) for w in values.get("--window_size", [])),
+            "benchmark_regions": one("--benchmark_regions", str), "genomewide_mu": one("--genomewide_mu", float),
+            "m_proportion": one("--m_proportion", float), "g_proportion": one("--g_proportion", float),
+            "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags}
+    if opts["windows"] and opts["summary"] is None:
+        raise SystemExit("--window_size needs --summary PREFIX: the prefix of the files it writes")
+    if opts["summary"] is not None and not opts["windows"]:
+        raise SystemExit("--summary PREFIX needs a --window_size")
+    if (opts["genomewide_mu"] is None) != (opts["m_proportion"] is None):
+        raise SystemExit("the scaling factor needs --genomewide_mu and --m_proportion")
+    if opts["g_proportion"] is not None and opts["genomewide_mu"] is None:
+        raise SystemExit("--g_proportion goes with --genomewide_mu and --m_proportion")
+    opts["wants_summary"] = opts["summary"] is not None or opts["genomewide_mu"] is not None
+    if opts["benchmark_regions"] is not None and opts["genomewide_mu"] is None:
+        raise SystemExit("--benchmark_regions weighs the scaling totals: it goes with --genomewide_mu and --m_proportion")
+    if opts["no_table"] and not opts["wants_summary"]:
+        raise SystemExit("--no-table leaves nothing to do without --summary or --genomewide_mu")
+    opts["any"] = opts["wants_summary"] or opts["no_table"] or opts["scale_factor"] is not None
+    return opts
+
+
+def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
+    """The forward and the sink(s) of a sharded run.  Without --scale_factor the calibration chain runs in the sinks, as write_predictions
+    applies it in the plain BED form; with it the whole chain, the scaling last, runs behind the head and the sinks take what they get."""
+    from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink
+    model, cfg = load_model(model_path, model_type=model_type)
+    cal = model_path + ".fdiri_cal.pkl"
+    weights = load_dirichlet_weights(cal) if os.path.exists(cal) and "--no-calibration" not in flags else None
+    in_forward = opts["scale_factor"] is not None
+    chain = dict(poisson=poisson, dirichlet_weights=weights)
+    forward = HipShardForward(model, fasta, cfg["local_radius"], cfg.get("local_order", 3), distal_radius=cfg["distal_radius"],
+                              model_type=model_type, scale_factor=opts["scale_factor"], **(chain if in_forward else dict(poisson=False)))
+    sink_chain = {} if in_forward else chain
+    sinks, summary = [], None
+    if out is not None:
+        sinks.append(TsvSink(out, **sink_chain))
+    if opts["wants_summary"]:
+        summary = SummarySink(opts["summary"], opts["windows"], opts["benchmark_regions"], **sink_chain)
+        sinks.append(summary)
+    return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
+
+
+def _report(n, out, summary, opts):
+    print(f"{n} sites -> {out}" if out is not None else f"{n} sites")
+    if summary is not None and opts["genomewide_mu"] is not None:
+        summary.scaling_factor(opts["genomewide_mu"], opts["m_proportion"], 1.0 if opts["g_proportion"] is None else opts["g_proportion"])
+
+
+def _main_bed_sharded(args, flags, model_type, poisson, opts):
+    from mural_amd.predict import predict_bed_sharded
+    model_path, fasta, bed, out = args
+    forward, cfg, sink, summary = _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts)
+    n = predict_bed_sharded(forward, bed, segment_center=cfg.get("segment_center", 300000), model_type=model_type, sink=sink, collect=False)
+    _report(n, out, summary, opts)
+
+
+def _main_regions(args, values, flags, model_type, poisson, opts):
     from mural_amd.predict import HipShardForward, TsvSink, predict_regions_sharded, read_regions_arg
     model_path, fasta, out = args
     if model_type == "indel":
@@ -65,6 +144,10 @@ def _main_regions(args, values, flags, model_type, poisson):
     else:
         focal, context = values.get("--focal", ["A"])[0], values.get("--context", ["all"])[0]
     regions = read_regions_arg(values["--regions"])
+    if opts["any"]:
+        forward, cfg, sink, summary = _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts)
+        n = predict_regions_sharded(forward, regions, focal, context, model_type=model_type, sink=sink, collect=False)
+        return _report(n, out, summary, opts)
     model, cfg = load_model(model_path, model_type=model_type)
     cal = model_path + ".fdiri_cal.pkl"
     weights = load_dirichlet_weights(cal) if os.path.exists(cal) and "--no-calibration" not in flags else None
