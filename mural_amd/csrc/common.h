@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/mural_hip.h"
 
@@ -32,6 +33,11 @@ void set_error(const char* fmt, ...);
 size_t ws_guard_bytes();
 void ws_layout_reset();
 void ws_layout_add(size_t off, size_t bytes);
+extern thread_local std::vector<size_t> g_ws_layout;      // (offset, bytes) pairs, read by mural_debug_last_ws_layout
+
+// dense (n, 4, L) one-hot / IUPAC-fraction windows -> one symbol byte per column (encode.hip).  A column that is no valid encoding
+// becomes N and sets MURAL_E_ENCODING in *status (bad_code < 0), or becomes bad_code without a report
+int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int32_t* status, hipStream_t stream, int bad_code = -1);
 
 #define MURAL_HIP_CHECK(expr)                                                                      \
   do {                                                                                             \

@@ -37,6 +37,7 @@ int launch_conv1d_valu(const Conv1dArgs& a, hipStream_t stream);   // direct for
 // implicit-GEMM version on fp32 MFMA for layers with >= 16 output channels (conv1d_mfma.hip); launch_conv1d routes to it
 bool conv1d_mfma_supported(const Conv1dArgs& a);
 int launch_conv1d_mfma(const Conv1dArgs& a, hipStream_t stream);
+void conv1d_mfma_set_stamps(unsigned long long* p);                // diagnostic (mural_debug_conv1d_set_stamps)
 // stride-1 convs with 3 / 5 / 7 taps, <= 32 channels on long rows, operands straight from global memory (conv1d_direct.hip)
 bool conv1d_direct_supported(const Conv1dArgs& a);
 int launch_conv1d_direct(const Conv1dArgs& a, hipStream_t stream);
@@ -101,6 +102,13 @@ struct ConvBlockArgs {
   const float* tb_b;
   float* tail_max;
 };
+// Tile geometry of the blocks with a front, shared by convblock_kernel (conv1d.hip) and the persistent level-0 kernels
+// (indel_level0.hip): tail_max is sized by convblock_tiles() from one of these and indexed by whichever kernel takes the launch
+constexpr int CB_FRONT_FLOATS = 2048;          // front input tile: Cf x (262 / up + 3) floats
+constexpr int CB_FRONT_OUT = 252;              // output positions per workgroup of the front variant
+constexpr int CB_FRONT_OUT_POLY = 248;         // ... of the split form with the polyphase front on the matrix cores
+extern int g_convblock8_form;                  // validation hook (mural_debug_convblock): 0 vector-ALU form, 1 split form, -1 the environment's choice
+extern unsigned long long* g_cb8_stamps;       // diagnostic (mural_debug_cb8_set_stamps): per-workgroup phase sums of the level-0 blocks, or nullptr
 bool convblock_supported(int C);
 int convblock_tiles(int L, bool front);   // upper bound of the workgroups per row (sizing of tail_max)
 int convblock_tiles_of(const ConvBlockArgs& a);   // workgroups per row of this launch = entries per row of its tail_max

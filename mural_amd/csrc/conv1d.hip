@@ -291,9 +291,9 @@ int launch_conv1d_valu(const Conv1dArgs& a_in, hipStream_t stream) {
 // 1x1 conv contracts them to C outputs, the block input is added back from the tile.  HBM traffic: read x, write out
 // (+ read res2) instead of also writing and re-reading the 2C-channel intermediate.
 int g_convblock8_form = -1;      // validation hook (mural_debug_convblock): 0 vector-ALU form, 1 split form, -1 the environment's choice
-constexpr int CB_FRONT_FLOATS = 2048;          // front input tile: Cf x (262 / up + 3) floats
-constexpr int CB_FRONT_OUT = 252;              // output positions per workgroup of the front variant
-constexpr int CB_FRONT_OUT_POLY = 248;         // ... of the split form with the polyphase front on the matrix cores
+// CB_FRONT_FLOATS (front input tile: Cf x (262 / up + 3) floats), CB_FRONT_OUT (output positions per workgroup of the front variant)
+// and CB_FRONT_OUT_POLY (... of the split form with the polyphase front on the matrix cores) are in conv1d.h: the persistent level-0
+// kernels (indel_level0.hip) tile by the same numbers
 
 // floats of the split form's front-input region (also holds the tail's 32 partial maxima)
 __host__ __device__ inline int convblock_front_floats(int Cf, int f_up, bool front) {
@@ -885,7 +885,7 @@ int convblock_tiles_of(const ConvBlockArgs& a) {
   return (a.L + CB_FRONT_OUT - 1) / CB_FRONT_OUT;
 }
 
-unsigned long long* g_cb8_stamps = nullptr;      // diagnostic (debug flavour: mural_debug_cb8_set_stamps): per-workgroup phase sums of the level-0 blocks      // validation hook (mural_debug_convblock): 0 vector-ALU form, 1 split form, -1 the environment's choice
+unsigned long long* g_cb8_stamps = nullptr;      // diagnostic (debug flavour: mural_debug_cb8_set_stamps): per-workgroup phase sums of the level-0 blocks
 
 template <bool TAIL, bool FRONT>
 static void launch_convblock_t(const ConvBlockArgs& a, hipStream_t stream) {

@@ -3,7 +3,10 @@
 // lockstep: ONE launch per layer index carries up to two jobs (blockIdx.y = job; the large tower first, so that its workgroups are
 // dispatched first and the mid tower's fill the tail) -- half the launches, one launch gap and one tail per layer pair.
 #pragma once
+#include <cstddef>
 #include <cstdint>
+
+#include "common.h"
 
 namespace mural {
 
@@ -92,5 +95,36 @@ struct PoolBwdJob {
 };
 struct GmaxFwdJob { const float* x; int64_t B; int L; int relu; float* feat; int32_t* arg; };
 struct GmaxBwdJob { const float* dfeat; const int32_t* arg; const float* c3; int64_t B; int L; float* dx; };
+
+// ---- host entry points (callers: snv_train.hip, debug_hooks.hip) ---------------------------------------------------------------
+// conv32_cl.hip: workgroup tiles; every activation of a tower is channel-last [B][L][32] inside the step
+int cl_conv32_supported(int L);
+int cl_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* acc, const float* gamma, const float* beta, float eps,
+                  float momentum, float* running_mean, float* running_var, float* state, const float* W, const float* bias, int post_relu,
+                  const float* res1, const float* res2, double* acc_out, int out_relu, float* y, hipStream_t stream);
+size_t cl_conv32_part_floats();
+int cl_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, int L, const float* state, int pre_relu, float* dz,
+                  double* stat_out, float* part, int* nrow, hipStream_t stream);
+int cl_bn_stats(const float* x, int64_t rows, int relu, double* acc, hipStream_t stream);
+int cl_bn_bwd_apply(const float* dz, const float* x, int64_t rows, int relu, const float* state, const float* gamma, const double* acc,
+                    const float* add1, const float* add2, float* dx, float* dgamma, float* dbeta, hipStream_t stream);
+int cl_maxpool_fwd(const float* x, int64_t B, int L, int k, int s, int p, float* y, int32_t* arg, double* acc, hipStream_t stream);
+int cl_maxpool_bwd(const float* dy, const int32_t* arg, int64_t B, int L, int Lout, int k, int s, int p, float* dx, hipStream_t stream);
+int cl_maxpool_bwd_fold(const BnApplyJob& f, const int32_t* arg, int64_t B, int L, int Lout, int k, int s, int p, float* dx, hipStream_t stream);
+int cl_gmax_fwd_jobs(const GmaxFwdJob* jobs, int n, hipStream_t stream);
+int cl_gmax_relu_bwd(const float* dfeat, const int32_t* arg, const float* c3, int64_t B, int L, float* dx, hipStream_t stream);
+// conv32_wave.hip: the same two layers with wave-private units (raw output, batch sums of relu(y))
+int cw_conv32_supported(int L);
+int cw_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* acc, const float* gamma, const float* beta, float eps,
+                  float momentum, float* running_mean, float* running_var, float* state, const float* W, const float* wfrag, const float* bias,
+                  int post_relu, const float* res1, const float* res2, double* acc_out, int out_relu, float* y, hipStream_t stream);
+int cw_conv32_bwd(const float* dy, const float* x, const float* W, const float* wfrag, int64_t B, int L, const float* state, const float* gamma,
+                  int pre_relu, float* dz, double* stat_out, float* part, int* nrow, hipStream_t stream);
+int cw_conv32_bwd_jobs(ConvBwdJob* jobs, int n, hipStream_t stream);
+size_t cw_wfrag_floats();
+int cw_wfrag_build(const float* const* W, int n, float* out, hipStream_t stream);
+extern unsigned long long* g_cw_stamps;      // diagnostic (mural_debug_cw_set_stamps)
+// conv32_reduce.hip: the partial rows of every layer -> dW / db in one launch
+int train_reduce_parts(const float* const* part, const int* nrow, float* const* dW, float* const* db, int njobs, hipStream_t stream);
 
 }  // namespace mural

@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "common.h"
+#include "conv32_jobs.h"
 
 namespace mural {
 

@@ -25,7 +25,7 @@
 // reduced across workgroups by the caller (conv_wgrad_reduce_multi_kernel) -- bitwise reproducible.
 #include <algorithm>
 
-#include "common.h"
+#include "indel_train.h"
 #include "mfma_tile.h"
 
 namespace mural {

@@ -1,7 +1,7 @@
 // Validation hooks and diagnostics (include/mural_hip_debug.h).  This file is linked into libmural_hip_debug.so ONLY: the product
 // library exports no mural_debug_* symbol and reads no development switch.  Every hook is a thin wrapper around an internal entry of
-// the library (declared here or in the internal headers) or a setter of a diagnostic pointer; loading this object also switches the
-// development switches of common.h on (dev_env).
+// the library (declared in the internal header of its subject: conv1d.h, conv32_jobs.h, snv.h, train_ops.h, common.h) or a setter of
+// a diagnostic pointer; loading this object also switches the development switches of common.h on (dev_env).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -10,32 +10,9 @@
 #include "common.h"
 #include "conv1d.h"
 #include "conv32_cl.h"
+#include "conv32_jobs.h"
 #include "snv.h"
-
-namespace mural {
-// conv32_cl.hip / conv32_wave.hip
-int cl_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* acc, const float* gamma, const float* beta, float eps,
-                  float momentum, float* running_mean, float* running_var, float* state, const float* W, const float* bias, int post_relu,
-                  const float* res1, const float* res2, double* acc_out, int out_relu, float* y, hipStream_t stream);
-int cl_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, int L, const float* state, int pre_relu, float* dz,
-                  double* stat_out, float* part, int* nrow, hipStream_t stream);
-int cl_bn_stats(const float* x, int64_t rows, int relu, double* acc, hipStream_t stream);
-int cw_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* acc, const float* gamma, const float* beta, float eps,
-                  float momentum, float* running_mean, float* running_var, float* state, const float* W, const float* wfrag, const float* bias,
-                  int post_relu, const float* res1, const float* res2, double* acc_out, int out_relu, float* y, hipStream_t stream);
-int cw_conv32_bwd(const float* dy, const float* x, const float* W, const float* wfrag, int64_t B, int L, const float* state, const float* gamma,
-                  int pre_relu, float* dz, double* stat_out, float* part, int* nrow, hipStream_t stream);
-int cw_wfrag_build(const float* const* W, int n, float* out, hipStream_t stream);
-extern unsigned long long* g_cw_stamps;
-// encode.hip
-extern thread_local std::vector<size_t> g_ws_layout;
-// snv_model.hip, train_ops.hip (snv_local_train.h), conv1d_mfma.hip, conv1d.hip
-extern unsigned long long* g_tower_stamps;
-namespace ltrain { extern unsigned long long* g_lt_stamps; }
-void conv1d_mfma_set_stamps(unsigned long long* p);
-extern unsigned long long* g_cb8_stamps;
-extern int g_convblock8_form;
-}  // namespace mural
+#include "train_ops.h"
 
 using namespace mural;
 

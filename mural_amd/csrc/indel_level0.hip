@@ -25,10 +25,10 @@
 #include "mfma_tile.h"
 
 namespace mural {
-extern unsigned long long* g_cb8_stamps;      // diagnostic (conv1d.hip): per-workgroup phase sums, or nullptr
 namespace {
 
 constexpr int E0_OUT = 252;         // output positions per tile (= the split form's tile, so tail / tile bookkeeping is shared)
+static_assert(E0_OUT == CB_FRONT_OUT, "the level-0 encoder tile is the split form's (convblock_tiles_of)");
 constexpr int E0_OUT_DOWN = 248;    // ... of the form that also emits the next level's stride-4 conv (62 columns of it per tile)
 constexpr int E0_PITCH = 272;       // = 16 (mod 32) floats
 constexpr int E0_C = 8;
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256, 4) void indel_enc0_kernel(const ConvBlockArgs 
   __shared__ __attribute__((aligned(16))) float biasS[16 + E0_C + 16];       // b5 | b1 | bias of the strided conv (read per tile: fewer registers across the loop)
   __shared__ uint32_t planes[3 * 12];                                        // low bit | high bit | not-ACGT, 320 columns each (+ pad)
   __shared__ uint8_t symb[320];
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n16 = tid & 15, kk = (tid >> 4) & 3;
 
@@ -376,10 +376,10 @@ __global__ __launch_bounds__(256, 4) void indel_enc0_kernel(const ConvBlockArgs 
 // (1x1, BN, ReLU, 1x1, Softplus) and the maximum over positions (model_indel.py:117-134, :136-149, :172-175), persistent like the
 // encoder kernel above: the 16 x 66 source columns of tile t + 1 and the skip values of tile t are requested before tile t's matrix
 // work; every fragment stays in registers (four waves per SIMD: the launch is bound by instruction issue, not latency; LDS only
-// stages them once per workgroup); the maximum over a row's positions
-// is carried in registers from tile to tile and leaves the workgroup once per row segment (the other tiles' slots get 0, the
-// identity of a maximum of Softplus values).  Tile geometry = convblock_kernel<8, true, true, true>'s polyphase form: 248 outputs.
-constexpr int D0_OUT = 248;         // = CB_FRONT_OUT_POLY (conv1d.hip): tail_max has one slot per such tile
+// stages them once per workgroup); the maximum over a row's positions is carried in registers from tile to tile and leaves the workgroup once
+// per row segment (the other tiles' slots get 0, the identity of a maximum of Softplus values).  Tile geometry: the polyphase form's.
+constexpr int D0_OUT = 248;         // tail_max has one slot per such tile
+static_assert(D0_OUT == CB_FRONT_OUT_POLY, "tail_max is sized by convblock_tiles() and indexed per D0_OUT tile");
 constexpr int D0_SPITCH = 68;       // source tile pitch (66 columns used)
 
 template <bool STAMPS>
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(256, 4) void indel_dec0_kernel(const ConvBlockArgs 
     // as scratch reloads behind a full wait -- which is the wait for the next tile's prefetch
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    const int lane = tid & 63, n16 = tid & 15, kk = (tid >> 4) & 3;
+    const int n16 = tid & 15, kk = (tid >> 4) & 3;
     {
       const int ci = tid >> 4, rr0 = tid & 15;
 #pragma unroll

@@ -401,10 +401,6 @@ static int run_block(const MuralIndelModel* m, const FoldedConv& f5, const Folde
   return run_conv(m, f1, H, B, L, out, L, 1, 1, ACT_NONE, x, skip, stream);
 }
 
-extern "C" int mural_encode_onehot(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n, int32_t radius,
-                                   int32_t indel, float* out, void* stream);
-namespace mural { int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int32_t* status, hipStream_t stream, int bad_code = -1); }
-
 // distal_x != nullptr: dense entry; otherwise the windows come from the packed genome (genome, pos, strand; window
 // [pos - radius + 1, pos + radius], preprocessing.py:564-566)
 static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, const MuralGenome* genome, const int64_t* pos,

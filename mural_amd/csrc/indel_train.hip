@@ -8,12 +8,10 @@
 #include <cstring>
 
 #include "conv1d.h"
+#include "indel_train.h"
 #include "mfma_tile.h"
 
 namespace mural {
-// conv_wgrad_mfma.hip: the weight gradient as an implicit GEMM on the matrix cores (nonzero return: shape not covered)
-int launch_conv_wgrad_mfma(const float* dy, const float* x, float* part, int64_t B, int Cin, int Lin, int Cout, int Lout, int K, int stride,
-                           int pad, int up, int max_chunks, int* chunks_out, hipStream_t st);
 namespace {
 
 constexpr int IT_THREADS = 256;
@@ -1021,14 +1019,6 @@ extern "C" int mural_op_convg_bn_fwd(const float* x, const float* W, const float
 
 // backward of the same unit from dz (the gradient of z; the residuals' gradients are dz itself): dgamma, dbeta, then the conv's dx
 // (optional), dW, db (optional).  acc = zeroed accumulator block, dy0 = scratch [B][Cout][Lout], part as for mural_op_convg_bwd.
-namespace mural {
-// mural_op_convg_bn_bwd with dx_add (optional, may alias dx): dx = the conv's input gradient + dx_add -- the composed step
-// (indel_train_step.hip) hands the gradient that reaches x through a residual or skip connection here instead of a separate add pass
-int convg_bn_bwd_add(const float* dz, const float* x, const float* W, const float* y0, const float* state, const float* gamma, int64_t B,
-                     int32_t Cin, int32_t Lin, int32_t Cout, int32_t K, int32_t stride, int32_t pad, int32_t up, int32_t act, double* acc,
-                     float* dy0, float* dx, const float* dx_add, float* dW, float* db, float* dgamma, float* dbeta, float* part,
-                     size_t part_floats, const float* wt_dgrad, void* stream);
-}
 extern "C" int mural_op_convg_bn_bwd(const float* dz, const float* x, const float* W, const float* y0, const float* state,
                                      const float* gamma, int64_t B, int32_t Cin, int32_t Lin, int32_t Cout, int32_t K, int32_t stride,
                                      int32_t pad, int32_t up, int32_t act, double* acc, float* dy0, float* dx, float* dW, float* db,

@@ -11,36 +11,15 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "indel_train.h"
 
 using namespace mural;
-
-namespace mural {
-void wgrad_defer_begin();                 // indel_train.hip: collect the weight-gradient partial rows of the layers that follow ...
-int wgrad_defer_flush(hipStream_t st);    // ... and reduce them all in one launch
-int convg_bn_bwd_add(const float* dz, const float* x, const float* W, const float* y0, const float* state, const float* gamma, int64_t B,
-                     int32_t Cin, int32_t Lin, int32_t Cout, int32_t K, int32_t stride, int32_t pad, int32_t up, int32_t act, double* acc,
-                     float* dy0, float* dx, const float* dx_add, float* dW, float* db, float* dgamma, float* dbeta, float* part,
-                     size_t part_floats, const float* wt_dgrad, void* stream);      // indel_train.hip
-}
 
 namespace {
 
 constexpr int IL = 6;      // U-Net levels
 constexpr float kEps = 1e-5f;
 
-// y = a + b (y may be a or b)
-__global__ void add2_kernel(const float* a, const float* b, float* y, int64_t n4) {
-  using f4 = __attribute__((ext_vector_type(4))) float;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const f4 u = reinterpret_cast<const f4*>(a)[i], v = reinterpret_cast<const f4*>(b)[i];
-    reinterpret_cast<f4*>(y)[i] = u + v;
-  }
-}
-__global__ void add2_tail_kernel(const float* a, const float* b, float* y, int64_t lo, int64_t n) {
-  const int64_t i = lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) y[i] = a[i] + b[i];
-}
 // y[b][c][l] = [add[b][c][l] +] x[b][C-1-c][L-1-l] (flip_c) or x[b][c][L-1-l]
 __global__ void flip_kernel(const float* __restrict__ x, const float* __restrict__ add, float* __restrict__ y, int64_t rows, int C, int L,
                             int flip_c) {
@@ -64,18 +43,6 @@ __global__ void fill_jobs_kernel(const JobPack pack, int n, MuralRelayoutJob* ds
   if ((int)threadIdx.x < n) dst[threadIdx.x] = pack.j[threadIdx.x];
 }
 
-int add2(const float* a, const float* b, float* y, int64_t n, hipStream_t st) {
-  if (n <= 0) return MURAL_OK;
-  const bool al = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
-  const int64_t n4 = al ? n / 4 : 0;
-  if (n4 > 0) {
-    const int64_t g = (n4 + 255) / 256;
-    hipLaunchKernelGGL(add2_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, st, a, b, y, n4);
-  }
-  if (n4 * 4 < n) hipLaunchKernelGGL(add2_tail_kernel, dim3((unsigned)((n - n4 * 4 + 255) / 256)), dim3(256), 0, st, a, b, y, n4 * 4, n);
-  MURAL_HIP_CHECK(hipGetLastError());
-  return MURAL_OK;
-}
 int flip(const float* x, const float* add, float* y, int64_t B, int C, int L, int flip_c, hipStream_t st) {
   const int64_t total = B * C * L;
   if (total == 0) return MURAL_OK;

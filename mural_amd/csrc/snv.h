@@ -131,7 +131,7 @@ struct FirstTrainArgs {
 extern unsigned long long* g_first_stamps;
 int first_train_grid(int64_t B);
 bool first_train_supported(int C, int pk);
-int launch_first_train(FirstTrainArgs a, bool bwd, hipStream_t stream);
+int launch_first_train(FirstTrainArgs a, bool bwd, hipStream_t stream);      // (host entries of the training step around it: train_ops.h)
 
 struct SnvFwdArgs {
   TowerGeom geom[2];              // 0 = large, 1 = mid
@@ -248,3 +248,22 @@ struct MuralSnvModel {
   size_t lds_lwA, lds_lwB;
   int64_t chunk;                  // sites per stage-1 / tower launch sequence (SNV_CHUNK, less for long windows)
 };
+
+namespace mural {
+// ---- forward launchers and planners (callers: snv_model.hip, snv_reuse.hip, snv_tower.hip)
+// snv_stage1.hip
+bool stage1_small_batch(int64_t n);
+int launch_snv_stage1(const Stage1Args& a, bool packed, size_t lds_bytes, hipStream_t stream);
+// snv_local.hip (its plan: snv_local_mfma.h)
+int launch_snv_local(const LocalDev& L, const int64_t* cat, int64_t n, float* out, hipStream_t stream);
+// snv_tower.hip
+int launch_snv_towers(const MuralSnvModel* m, const SnvFwdArgs& a, size_t lds_bytes, hipStream_t stream);
+int profile_begin();      // mural_profile_begin / _end
+int profile_end(double* total_ms, int64_t* launches);
+// snv_tower_wave.hip
+size_t plan_wave_geometry(SnvFwdArgs& a, int Lwin, int Pw, int n_class, int tower, int phase);
+int launch_snv_tower_wave(const SnvFwdArgs& a, size_t lds_bytes, hipStream_t stream);
+int launch_snv_tower_wave_jobs(const SnvFwdArgs* jobs, const size_t* lds_bytes, int n, hipStream_t stream);
+// snv_model.hip
+extern unsigned long long* g_tower_stamps;      // diagnostic (debug flavour: mural_debug_set_stamps)
+}  // namespace mural

@@ -8,16 +8,9 @@
 #include <vector>
 
 #include "snv.h"
+#include "snv_local_mfma.h"
 
 namespace mural {
-int launch_snv_towers(const MuralSnvModel* m, const SnvFwdArgs& a, size_t lds_bytes, hipStream_t stream);
-int launch_snv_tower_wave_jobs(const SnvFwdArgs* jobs, const size_t* lds_bytes, int n, hipStream_t stream);   // snv_tower_wave.hip
-int launch_snv_stage1(const Stage1Args& a, bool packed, size_t lds_bytes, hipStream_t stream);
-size_t plan_wave_geometry(SnvFwdArgs& a, int Lwin, int Pw, int n_class, int tower, int phase);   // snv_tower_wave.hip
-int launch_snv_local(const LocalDev& L, const int64_t* cat, int64_t n, float* out, hipStream_t stream);
-int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int32_t* status, hipStream_t stream, int bad_code = -1);
-bool stage1_small_batch(int64_t n);
-bool local_mfma_plan(const LocalDev& L, LocalMfmaDims* d, size_t* lds_bytes);
 
 namespace {
 
@@ -638,7 +631,6 @@ extern "C" int mural_snv_tap_layout(const MuralSnvModel* m, int32_t* o) {
 
 extern "C" const char* mural_snv_kernel_name(void) { return "snv_tower_wave"; }
 
-namespace mural { int profile_begin(); int profile_end(double*, int64_t*); }
 extern "C" int mural_profile_begin(void) { return mural::profile_begin(); }
 extern "C" int mural_profile_end(double* total_ms, int64_t* launches) { return mural::profile_end(total_ms, launches); }
 

@@ -27,9 +27,6 @@
 #include "snv_tower_conv.h"
 
 namespace mural {
-int launch_snv_towers(const MuralSnvModel* m, const SnvFwdArgs& a, size_t lds_bytes, hipStream_t stream);
-int launch_snv_local(const LocalDev& L, const int64_t* cat, int64_t n, float* out, hipStream_t stream);
-
 namespace {
 
 constexpr int64_t RU_CHUNK_SPAN = 1 << 21;   // bases per row chunk (11 row arrays x 128 B x span = 2.9 GB)
@@ -231,7 +228,6 @@ __global__ __launch_bounds__(256) void reuse_rows_pool_kernel(const float* __res
   }
 }
 
-int pool_len(int L, int k, int s, int p) { return (L + 2 * p - k) / s + 1; }
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct ReuseWs {

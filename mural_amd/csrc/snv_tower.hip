@@ -482,8 +482,6 @@ int profile_end(double* total_ms, int64_t* launches) {
   return MURAL_OK;
 }
 
-int launch_snv_tower_wave(const SnvFwdArgs& a, size_t lds_bytes, hipStream_t stream);   // snv_tower_wave.hip
-
 int launch_snv_towers(const MuralSnvModel* m, const SnvFwdArgs& a, size_t lds_bytes, hipStream_t stream) {
   const int64_t n_tiles = (a.n + a.P - 1) / a.P;
   if (n_tiles == 0) return MURAL_OK;

@@ -6,7 +6,8 @@
 //                            the caller's workspace.
 // mural_snv_train_backward : gradient of every parameter tensor (written to the caller's buffers, laid out like the parameters)
 //                            from d(loss)/d(output) and that workspace.
-// The host composes the training kernels of train_ops.hip / conv32_wave.hip / conv32_cl.hip / snv_stage1.hip here in C++, so a non-Python host needs
+// The host composes the training kernels of train_ops.hip (with snv_head_train.h and snv_local_train.h), conv32_wave.hip, conv32_cl.hip,
+// conv32_reduce.hip and snv_stage1.hip here in C++ (entry points: train_ops.h, conv32_jobs.h, snv.h), so a non-Python host needs
 // nothing but these two calls, an optimiser and a loss.  Parameters are DEVICE pointers in the reference's state_dict naming
 // (the MuralSnvParams structs of the eval path, here with device addresses).
 #include <algorithm>
@@ -14,76 +15,11 @@
 #include <cstring>
 #include <utility>
 
-#include "snv.h"
 #include "conv32_jobs.h"
+#include "snv.h"
+#include "train_ops.h"
 
 using namespace mural;
-
-namespace mural {   // conv32_cl.hip: every activation of a tower is channel-last [B][L][32] inside the step
-int cl_conv32_supported(int L);
-int cl_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* acc, const float* gamma, const float* beta, float eps,
-                  float momentum, float* running_mean, float* running_var, float* state, const float* W, const float* bias, int post_relu,
-                  const float* res1, const float* res2, double* acc_out, int out_relu, float* y, hipStream_t stream);
-size_t cl_conv32_part_floats();
-int cl_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, int L, const float* state, int pre_relu, float* dz,
-                  double* stat_out, float* part, int* nrow, hipStream_t stream);
-// conv32_wave.hip: the same two layers with wave-private units (raw output, batch sums of relu(y))
-int cw_conv32_supported(int L);
-int cw_conv32_fwd(const float* x, int64_t B, int L, int pre_relu, const double* acc, const float* gamma, const float* beta, float eps,
-                  float momentum, float* running_mean, float* running_var, float* state, const float* W, const float* wfrag, const float* bias,
-                  int post_relu, const float* res1, const float* res2, double* acc_out, int out_relu, float* y, hipStream_t stream);
-int cw_conv32_bwd(const float* dy, const float* x, const float* W, const float* wfrag, int64_t B, int L, const float* state, const float* gamma,
-                  int pre_relu, float* dz, double* stat_out, float* part, int* nrow, hipStream_t stream);
-size_t cw_wfrag_floats();
-int cw_wfrag_build(const float* const* W, int n, float* out, hipStream_t stream);
-int cl_bn_stats(const float* x, int64_t rows, int relu, double* acc, hipStream_t stream);
-int cl_bn_bwd_apply(const float* dz, const float* x, int64_t rows, int relu, const float* state, const float* gamma, const double* acc,
-                    const float* add1, const float* add2, float* dx, float* dgamma, float* dbeta, hipStream_t stream);
-int cl_maxpool_fwd(const float* x, int64_t B, int L, int k, int s, int p, float* y, int32_t* arg, double* acc, hipStream_t stream);
-int cl_maxpool_bwd(const float* dy, const int32_t* arg, int64_t B, int L, int Lout, int k, int s, int p, float* dx, hipStream_t stream);
-int cl_maxpool_bwd_fold(const BnApplyJob& f, const int32_t* arg, int64_t B, int L, int Lout, int k, int s, int p, float* dx, hipStream_t stream);
-int cl_gmax_fwd_jobs(const GmaxFwdJob* jobs, int n, hipStream_t stream);
-int cw_conv32_bwd_jobs(ConvBwdJob* jobs, int n, hipStream_t stream);
-int cl_gmax_relu_bwd(const float* dfeat, const int32_t* arg, const float* c3, int64_t B, int L, float* dx, hipStream_t stream);
-// train_ops.hip / snv_stage1.hip: first layer with channel-last output
-int train_first_fwd_cl(const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp, const float* gamma, const float* beta,
-                       const float* W, const float* bias, float eps, float momentum, float* running_mean, float* running_var,
-                       unsigned long long* counts, float* tab, float* y, void* arg, double* stat, hipStream_t stream);
-int train_first_prepare2(const uint8_t* sym, int64_t B, int Lwin, const int* col0, const int* L1, const float* const* gamma,
-                         const float* const* beta, const float* const* W, const float* const* bias, float* const* running_mean,
-                         float* const* running_var, unsigned long long* const* counts, float* const* tab, float eps, float momentum,
-                         hipStream_t stream);
-int train_first_fwd_cl_prepared(const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp, const float* tab, float* y,
-                                void* arg, double* stat, hipStream_t stream);
-int train_first_bwd_cl(const float* dy, const void* arg, const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp,
-                       const float* tab, const float* W, float* scratch, float* dW, float* dbias, float* dgamma, float* dbeta,
-                       const FirstFold* fold, hipStream_t stream);
-// conv32_reduce.hip
-int train_reduce_parts(const float* const* part, const int* nrow, float* const* dW, float* const* db, int njobs, hipStream_t stream);
-// train_ops.hip
-int train_bn2d_apply_dropout(const float* x, int64_t B, int C, int relu, const double* acc, const float* gamma, const float* beta, float eps,
-                             float momentum, float* running_mean, float* running_var, float* state, float p, uint64_t seed,
-                             const uint64_t* seed_dev, float* y_bn, float* y, hipStream_t stream);
-// snv_head_train.h (train_ops.hip): a tower's head in two launches per direction
-bool head_train_fused_ok(int nc);
-int head_train_fwd(const float* c3, int64_t B, int L, float* feat, int32_t* arg, double* acc, const float* gamma, const float* beta, float eps,
-                   float momentum, float* running_mean, float* running_var, float* state, float p, uint64_t seed, const uint64_t* seed_dev,
-                   float* fd, const float* W, const float* bias, int nc, float* logits, hipStream_t stream);
-int head_train_bwd(const float* dlogits, const float* W, int nc, int64_t B, int L, const float* feat, const float* state, const float* gamma,
-                   float p, uint64_t seed, const uint64_t* seed_dev, float* dd, double* acc, const int32_t* arg, const float* c3, float* dx,
-                   float* dgamma, float* dbeta, hipStream_t stream);
-int head_train_wgrad(const float* dlogits, const float* fd, int64_t B, int nc, float* dW, float* db, hipStream_t stream);
-// snv_local_train.h (train_ops.hip): the local branch in three launches per direction
-bool local_train_fused_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B);
-int local_train_fwd(const int64_t* cat, const float* E, int cols, int emb_rows, int64_t B, const int* dims, const float* const* W,
-                    const float* const* bias, const float* const* gamma, const float* const* beta, float* const* running_mean,
-                    float* const* running_var, float* const* state, double* const* acc_f, const float* drop, const uint64_t* seeds,
-                    const uint64_t* seed_dev, float eps, float momentum, float* const* xt, float* const* lin, float* logits, hipStream_t stream);
-int local_train_bwd(const int64_t* cat, int cols, int emb_rows, int64_t B, const int* dims, const float* dlogits, const float* const* W,
-                    const float* const* gamma, const float* const* state, double* const* acc_b, const float* drop, const uint64_t* seeds,
-                    const uint64_t* seed_dev, const float* const* xt, const float* const* lin, float* const* dd, float* const* g,
-                    float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta, float* dE, hipStream_t stream);
-}
 
 namespace {
 

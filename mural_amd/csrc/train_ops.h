@@ -1,0 +1,45 @@
+// Host entry points of train_ops.hip (with snv_head_train.h and snv_local_train.h, whose kernels that file alone instantiates) for
+// the composed SNV training step (snv_train.hip) and the diagnostics (debug_hooks.hip).
+#pragma once
+#include "snv.h"
+
+namespace mural {
+
+// first layer of a tower with channel-last output (kernels: snv_stage1.hip, launch_first_train)
+int train_first_fwd_cl(const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp, const float* gamma, const float* beta,
+                       const float* W, const float* bias, float eps, float momentum, float* running_mean, float* running_var,
+                       unsigned long long* counts, float* tab, float* y, void* arg, double* stat, hipStream_t stream);
+int train_first_prepare2(const uint8_t* sym, int64_t B, int Lwin, const int* col0, const int* L1, const float* const* gamma,
+                         const float* const* beta, const float* const* W, const float* const* bias, float* const* running_mean,
+                         float* const* running_var, unsigned long long* const* counts, float* const* tab, float eps, float momentum,
+                         hipStream_t stream);
+int train_first_fwd_cl_prepared(const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp, const float* tab, float* y,
+                                void* arg, double* stat, hipStream_t stream);
+int train_first_bwd_cl(const float* dy, const void* arg, const uint8_t* sym, int64_t B, int Lwin, int col0, int L1, int pk, int ps, int pp,
+                       const float* tab, const float* W, float* scratch, float* dW, float* dbias, float* dgamma, float* dbeta,
+                       const FirstFold* fold, hipStream_t stream);
+int train_bn2d_apply_dropout(const float* x, int64_t B, int C, int relu, const double* acc, const float* gamma, const float* beta, float eps,
+                             float momentum, float* running_mean, float* running_var, float* state, float p, uint64_t seed,
+                             const uint64_t* seed_dev, float* y_bn, float* y, hipStream_t stream);
+// snv_head_train.h: a tower's head in two launches per direction
+bool head_train_fused_ok(int nc);
+int head_train_fwd(const float* c3, int64_t B, int L, float* feat, int32_t* arg, double* acc, const float* gamma, const float* beta, float eps,
+                   float momentum, float* running_mean, float* running_var, float* state, float p, uint64_t seed, const uint64_t* seed_dev,
+                   float* fd, const float* W, const float* bias, int nc, float* logits, hipStream_t stream);
+int head_train_bwd(const float* dlogits, const float* W, int nc, int64_t B, int L, const float* feat, const float* state, const float* gamma,
+                   float p, uint64_t seed, const uint64_t* seed_dev, float* dd, double* acc, const int32_t* arg, const float* c3, float* dx,
+                   float* dgamma, float* dbeta, hipStream_t stream);
+int head_train_wgrad(const float* dlogits, const float* fd, int64_t B, int nc, float* dW, float* db, hipStream_t stream);
+// snv_local_train.h: the local branch in three launches per direction
+bool local_train_fused_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B);
+int local_train_fwd(const int64_t* cat, const float* E, int cols, int emb_rows, int64_t B, const int* dims, const float* const* W,
+                    const float* const* bias, const float* const* gamma, const float* const* beta, float* const* running_mean,
+                    float* const* running_var, float* const* state, double* const* acc_f, const float* drop, const uint64_t* seeds,
+                    const uint64_t* seed_dev, float eps, float momentum, float* const* xt, float* const* lin, float* logits, hipStream_t stream);
+int local_train_bwd(const int64_t* cat, int cols, int emb_rows, int64_t B, const int* dims, const float* dlogits, const float* const* W,
+                    const float* const* gamma, const float* const* state, double* const* acc_b, const float* drop, const uint64_t* seeds,
+                    const uint64_t* seed_dev, const float* const* xt, const float* const* lin, float* const* dd, float* const* g,
+                    float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta, float* dE, hipStream_t stream);
+namespace ltrain { extern unsigned long long* g_lt_stamps; }      // diagnostic (mural_debug_lt_set_stamps)
+
+}  // namespace mural

@@ -12,6 +12,7 @@
 
 #include "conv1d.h"
 #include "snv.h"
+#include "train_ops.h"
 
 namespace mural {
 namespace {
@@ -21,12 +22,6 @@ using f32x4_t = __attribute__((ext_vector_type(4))) float;
 constexpr int BN_SLOTS = MURAL_BN_SLOTS;
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z);
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------- weight re-layouts
 // W[Cout][Cin][K] -> wt[Cin][K][Cout]  (forward)         or -> wt[Cout][K][Cin] with taps flipped (input gradient)
@@ -1745,7 +1740,6 @@ int train_bn2d_apply_dropout(const float* x, int64_t B, int C, int relu, const d
 #include "snv_local_train.h"      // the local branch of the composed training step in three launches per direction
 #include "snv_head_train.h"       // a tower's head in two launches per direction
 
-namespace mural { int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int32_t* status, hipStream_t stream, int bad_code = -1); }
 // dense (n,4,L) MuRaL encoding -> 1 symbol per column (status: see mural_snv_forward_dense)
 extern "C" int mural_op_dense_to_symbols(const float* x, int64_t n, int32_t L, uint8_t* sym, int32_t* status, void* stream) {
   return mural::launch_dense_to_symbols(x, n, L, sym, status, STREAM);
