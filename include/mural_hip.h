@@ -587,6 +587,47 @@ size_t mural_summary_workspace_bytes(int64_t n, int32_t n_class, int32_t n_windo
 int mural_summary_rows(const MuralSummaryRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * k-mer rate tables of a shard while it is on the device (SummarySink(kmers=...); csrc/summary_kmer.hip): what
+ * mural_table_kmer_keys + mural_eval_group_obs_pred + mural_table_first_row compute from the written table, in one pass
+ * over the rows (any order) of a part of ONE chromosome, for up to MURAL_SUMMARY_MAX_KMERS k-mer lengths at once.  The
+ * key of a row is mural_table_kmer_keys' (csrc/kmer_key.h holds the one decode both use); a row without a key for one k
+ * still counts for the others.  Exact integer sums, integer atomics only: each probability is quantised once to
+ * q = rne(p * 2^71), carried as hi = floor(p * 2^31) and lo = rint((p * 2^31 - hi) * 2^40), so the tables are a function
+ * of the SET of rows alone -- bit-identical across runs and splits into parts.
+ *   table[j] [4^k[j]][3][n_class] of unsigned 64-bit cells += { rows with label c, sum of hi of prob[:, c], sum of lo };
+ *     on return lo < 2^40 (its overflow is carried into hi after at most 2^21 rows); the value of a class's cell is
+ *     (hi * 2^40 + lo) / 2^71; zeroed by the caller before the first part;
+ *   first[j] [4^k[j]] = min(first, order_base + 2 * start + sub), sub = 1 for mode 3's reverse-complement key: the dict
+ *     insertion order of the reference's per-key tables when order_base is the chromosome's ordinal shifted above any
+ *     2 * start + 1; set to all ones by the caller before the first part;
+ *   status (device int32): bit 0 a negative start, bit 1 a label outside 0 .. n_class - 1 (or no whole number), bit 3 a
+ *     probability that is NaN, negative or above 1; such rows are skipped in every table.
+ * indel / mode: as mural_table_kmer_keys (mode 3 adds the row under both keys).  mural_summary_kmer_in_lds: 1 when the
+ * table of (k, n_class) is accumulated in a workgroup's LDS and flushed, 0 when the rows add to global memory.
+ * Launches on `stream`, no synchronisation.  n_class <= 8, 1 <= k <= 15.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MURAL_SUMMARY_MAX_KMERS 4
+typedef struct {
+  const MuralGenome* genome; /* the chromosome of the rows */
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 0 .. n_class-1 are read          */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n] */
+  const int64_t* end;        /* dev [n] */
+  const uint8_t* strand;     /* dev [n], 1 = '-' (read in mode 0 only) */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_k, indel, mode;
+  int32_t k[MURAL_SUMMARY_MAX_KMERS];
+  uint64_t* table[MURAL_SUMMARY_MAX_KMERS];         /* dev */
+  uint64_t* first[MURAL_SUMMARY_MAX_KMERS];         /* dev */
+  int64_t order_base;
+  int32_t* status;           /* dev [1] */
+} MuralSummaryKmerRows;
+int32_t mural_summary_kmer_in_lds(int32_t k, int32_t n_class);
+int mural_summary_kmer_rows(const MuralSummaryKmerRows* s, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

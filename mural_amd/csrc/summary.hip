@@ -13,6 +13,7 @@
 // No floating-point atomics anywhere: the result is a function of the input and of SM_CHUNK alone.  float64 throughout; the row and label
 // counts are carried as integers.
 #include "common.h"
+#include "kmer_key.h"
 
 namespace mural {
 namespace {
@@ -21,7 +22,6 @@ constexpr int SM_CHUNK = 2048;                 // rows of a workgroup's chunk
 constexpr int SM_PASSES = SM_CHUNK / 64;
 constexpr int SM_MAX_CLASS = 8;
 constexpr int SM_CARRY_THREADS = 256;
-enum : int32_t { SM_BAD_START = 1, SM_BAD_LABEL = 2, SM_BAD_ORDER = 4 };
 
 struct SummaryArgs {
   const void* prob;
@@ -41,18 +41,6 @@ struct SummaryArgs {
   int64_t* part_cnt;       // [chunks]
   int32_t* status;
 };
-
-// label of row i as an int, -1 if it is no whole number
-__device__ __forceinline__ int load_label(const void* label, int kind, int64_t i) {
-  if (kind == 0) {
-    const float f = static_cast<const float*>(label)[i];
-    const int v = (f >= -1.0f && f < 1024.0f) ? (int)f : -1;
-    return (float)v == f ? v : -1;
-  }
-  if (kind == 1) return static_cast<const int32_t*>(label)[i];
-  const int64_t v = static_cast<const int64_t*>(label)[i];
-  return (v >= 0 && v < 1024) ? (int)v : -1;
-}
 
 // #(b[0 .. n) < key) or, with `or_equal`, #(b <= key) of an ascending array
 __device__ __forceinline__ int64_t count_below(const int64_t* __restrict__ b, int64_t n, int64_t key, bool or_equal) {

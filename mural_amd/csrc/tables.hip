@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kmer_key.h"
 
 namespace mural {
 namespace {
@@ -360,35 +361,13 @@ __global__ __launch_bounds__(TB_THREADS) void kmer_keys_kernel(MuralGenome g, co
                                                                int32_t* __restrict__ key_a, int32_t* __restrict__ key_b) {
   const int64_t i = (int64_t)blockIdx.x * TB_THREADS + threadIdx.x;
   if (i >= n) return;
-  const int64_t r = k / 2;
-  const int64_t s0 = start[i] - r + (indel ? 1 : 0), s1 = end[i] + r;
-  const int64_t L = g.length;
-  const int64_t lo = s0 < 0 ? max(L + s0, (int64_t)0) : min(s0, L);
-  const int64_t hi = s1 < 0 ? max(L + s1, (int64_t)0) : min(s1, L);
-  int32_t fwd = -1, rev = -1;
-  if (hi - lo == k) {
-    const uint32_t* packed = static_cast<const uint32_t*>(g.packed2);
-    const uint32_t* nmask = static_cast<const uint32_t*>(g.nmask);
-    int32_t f = 0, rv = 0;
-    bool bad = false;
-    for (int j = 0; j < k; ++j) {
-      const int64_t q = lo + j;
-      bad |= ((nmask[q >> 5] >> (q & 31)) & 1u) != 0;
-      const int32_t code = (int32_t)((packed[q >> 4] >> (2 * (q & 15))) & 3u);
-      f = f * 4 + code;
-      rv += (3 - code) << (2 * j);
-    }
-    if (!bad) {
-      fwd = f;
-      rev = rv;
-    }
-  }
+  int32_t fwd, rev;
+  kmer_key_decode(g, start[i], end[i], k, indel, fwd, rev);
   if (mode == 3) {
     key_a[i] = fwd;
     key_b[i] = rev;
   } else {
-    const bool minus = mode == 2 || (mode == 0 && strand[i] != 0);
-    key_a[i] = minus ? rev : fwd;
+    key_a[i] = kmer_key_minus(mode, strand, i) ? rev : fwd;
   }
 }
 

@@ -846,7 +846,7 @@ def _refuse_second_calibration(rows, poisson, dirichlet_weights):
 # shards while they are on the device (csrc/summary.hip), so that a summary-only pass needs no table at all
 # ------------------------------------------------------------------------------------------------------------------
 _SUMMARY_STATUS = ((2, "a mut_type outside 0 .. n_class - 1"), (1, "a negative start"),
-                   (4, "rows of a chromosome that do not ascend in start"))
+                   (4, "rows of a chromosome that do not ascend in start"), (8, "a probability that is NaN, negative or above 1"))
 
 
 def summary_rows_host(prob, start, end, label, n_class, windows, regions=None):
@@ -885,6 +885,164 @@ def summary_rows_host(prob, start, end, label, n_class, windows, regions=None):
     return tables, total, int(w[w > 0].sum()), status
 
 
+# ---- k-mer rate tables (csrc/summary_kmer.hip): exact integer sums of the probabilities quantised to 2^-71 -------------------------------
+_KMER_HI_BITS, _KMER_LO_BITS = 31, 40
+_KMER_LO_MASK = np.uint64((1 << _KMER_LO_BITS) - 1)
+_KMER_ORD_SHIFT = 40               # a chromosome's ordinal sits above any 2 * start + 1 (chromosomes shorter than 2^39 bases)
+_KMER_FOLD_ROWS = 1 << 21          # rows between two folds of the lo limbs (the bound of csrc/summary_kmer.hip)
+_KMER_NEVER = np.uint64(2 ** 64 - 1)
+
+
+def _host_genome(genome):
+    """(packed2 uint32[], nmask uint32[], length) of a sequence (str / bytes), a ``PackedGenome`` or such a triple."""
+    if isinstance(genome, (str, bytes)):
+        from .data.genome import pack_sequence
+        return pack_sequence(genome)[:3]
+    if hasattr(genome, "packed2"):
+        return genome.packed2.cpu().numpy().view(np.uint32), genome.nmask.cpu().numpy().view(np.uint32), int(genome.length)
+    packed, nmask, length = genome[:3]
+    return np.asarray(packed).view(np.uint32), np.asarray(nmask).view(np.uint32), int(length)
+
+
+def kmer_keys_host(genome, start, end, strand, k, indel=False, mode=0):
+    """The numpy twin of ``mural_table_kmer_keys`` (csrc/kmer_key.h): (key_a, key_b) int64, -1 where the Python slice
+    chrom[start - k/2 (+1 indel) : end + k/2] is not k bases of A/C/G/T; key_a follows the strand mode (0 the rows' strand, 1 '+', 2 '-'),
+    in mode 3 key_a is the forward key and key_b its reverse complement (otherwise key_b is all -1)."""
+    packed, nmask, L = _host_genome(genome)
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    s0, s1 = start - k // 2 + (1 if indel else 0), end + k // 2
+    lo = np.where(s0 < 0, np.maximum(L + s0, 0), np.minimum(s0, L))
+    hi = np.where(s1 < 0, np.maximum(L + s1, 0), np.minimum(s1, L))
+    ok = hi - lo == k
+    fwd, rev = np.zeros(len(start), np.int64), np.zeros(len(start), np.int64)
+    base = np.where(ok, lo, 0)
+    for j in range(k):
+        q = np.minimum(base + j, max(L - 1, 0))
+        if L == 0:
+            break
+        ok &= ((nmask[q >> 5] >> (q & 31).astype(np.uint32)) & 1) == 0
+        code = ((packed[q >> 4] >> (2 * (q & 15)).astype(np.uint32)) & 3).astype(np.int64)
+        fwd = fwd * 4 + code
+        rev += (3 - code) << (2 * j)
+    fwd, rev = np.where(ok, fwd, -1), np.where(ok, rev, -1)
+    none = np.full(len(start), -1, np.int64)
+    if mode == 3:
+        return fwd, rev
+    minus = np.ones(len(start), bool) if mode == 2 else (np.asarray(strand) != 0 if mode == 0 else np.zeros(len(start), bool))
+    return np.where(minus, rev, fwd), none
+
+
+def kmer_quantise(prob):
+    """(hi, lo, bad) of float probabilities: q = rne(p * 2^71) as hi = floor(p * 2^31), lo = rint((p * 2^31 - hi) * 2^40) (uint64; every
+    step exact in float64, float32 widened first); bad: NaN, negative or above 1 (hi = lo = 0 there)."""
+    p = np.asarray(prob).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        bad = ~((p >= 0.0) & (p <= 1.0))
+    p = np.where(bad, 0.0, p)
+    s = p * float(1 << _KMER_HI_BITS)
+    h = np.floor(s)
+    return h.astype(np.uint64), np.rint((s - h) * float(1 << _KMER_LO_BITS)).astype(np.uint64), bad
+
+
+def _kmer_fold(table):
+    """Carry the lo limbs' overflow into hi: table [groups][3][n_class] uint64, in place."""
+    carry = table[:, 2] >> np.uint64(_KMER_LO_BITS)
+    table[:, 1] += carry
+    table[:, 2] &= _KMER_LO_MASK
+    return table
+
+
+def summary_kmer_host(genome, prob, start, end, strand, label, n_class, kmers, indel=False, mode=0, order_base=0, into=None):
+    """The numpy twin of ``mural_summary_kmer_rows`` -- and its specification -- for rows (any order) of one chromosome:
+    ({k: (table uint64 [4^k][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^k])}, status).  `genome`: the
+    chromosome as a sequence, a ``PackedGenome`` or (packed2, nmask, length); `into`: tables of earlier parts to add to (in place).  Status
+    bits as on the device (1 a negative start, 2 a label outside 0 .. n_class - 1, 8 a probability that is NaN, negative or above 1);
+    such rows are skipped in every table."""
+    nc = int(n_class)
+    start, end, label = np.asarray(start, np.int64), np.asarray(end, np.int64), np.asarray(label)
+    hi, lo, bad_p = kmer_quantise(np.asarray(prob)[:, :nc])
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= nc) | (lab != label)
+    bad_start, bad_prob = start < 0, bad_p.any(axis=1)
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    ok = ~(bad_label | bad_start | bad_prob)
+    strand = np.zeros(len(start), np.uint8) if strand is None else TsvSink._strand_u8(strand)
+    hi, lo, start, end, lab, strand = hi[ok], lo[ok], start[ok], end[ok], lab[ok], np.asarray(strand)[ok]
+    if len(start) and int(start.max()) >= 1 << (_KMER_ORD_SHIFT - 1):
+        raise ValueError("k-mer summary: a start at or above 2^39")
+    host = _host_genome(genome)
+    out = {} if into is None else into
+    cls = np.arange(nc)
+    for k in kmers:
+        table, first = out.get(k) or (np.zeros((4 ** k, 3, nc), np.uint64), np.full(4 ** k, _KMER_NEVER, np.uint64))
+        for r0 in range(0, len(start), _KMER_FOLD_ROWS):
+            r = slice(r0, r0 + _KMER_FOLD_ROWS)
+            for sub, key in enumerate(kmer_keys_host(host, start[r], end[r], strand[r], k, indel, mode)):
+                live = key >= 0
+                kk = key[live]
+                np.add.at(table[:, 0], (kk, lab[r][live]), np.uint64(1))
+                np.add.at(table[:, 1], (kk[:, None], cls[None, :]), hi[r][live])
+                np.add.at(table[:, 2], (kk[:, None], cls[None, :]), lo[r][live])
+                np.minimum.at(first, kk, (np.uint64(order_base) + (2 * start[r][live] + sub).astype(np.uint64)))
+            _kmer_fold(table)
+        out[k] = (table, first)
+    return out, status
+
+
+def kmer_table_from_sums(table, first, k, n_class):
+    """(k-mer names, table [groups][1 + 2 n_class] of rows / per-class counts / per-class probability sums) -- ``tables.kmer_table``'s
+    pair -- from the integer sums: the keys with a row, by first appearance; a probability sum is (hi * 2^40 + lo) / 2^71, formed from
+    Python integers (true division rounds correctly)."""
+    from .tables import kmer_name
+    nc = int(n_class)
+    live = np.nonzero(table[:, 0].sum(axis=1) > 0)[0]
+    order = live[np.argsort(first[live], kind="stable")]
+    out = np.zeros((len(order), 1 + 2 * nc))
+    out[:, 1:1 + nc] = table[order, 0]
+    out[:, 0] = table[order, 0].sum(axis=1)
+    den = 1 << (_KMER_HI_BITS + _KMER_LO_BITS)
+    hi, lo = table[order, 1].tolist(), table[order, 2].tolist()
+    for j in range(len(order)):
+        out[j, 1 + nc:] = [((h << _KMER_LO_BITS) + l) / den for h, l in zip(hi[j], lo[j])]
+    return [kmer_name(int(g), k) for g in order], out
+
+
+def _kmer_collapse(tables, firsts):
+    """({k: table}, {chromosome: {k: first}}) -> (names ascending, {k: (table, first)}): a k-mer's first appearance over the chromosomes
+    in ascending name order -- the order of the written table -- with the chromosome's ordinal above the word."""
+    names = sorted(firsts)
+    out = {}
+    for k, table in tables.items():
+        first = np.full(table.shape[0], _KMER_NEVER, np.uint64)
+        for ordinal, nm in enumerate(names):
+            f = firsts[nm][k]
+            np.minimum(first, np.where(f != _KMER_NEVER, f | np.uint64(ordinal << _KMER_ORD_SHIFT), _KMER_NEVER), out=first)
+        out[k] = (table, first)
+    return names, out
+
+
+def _kmer_merge(states):
+    """[(chromosome names ascending, {k: (table, first)})] of the ranks (or of a rank's devices and its host rows) -> one such pair:
+    tables added, first-appearance words min-merged after the ordinals are reconciled by name (every list ascends, so renumbering it to
+    the merged list keeps the order it was collapsed under)."""
+    tables = {}
+    names = sorted({nm for their_names, _ in states for nm in their_names})
+    low = np.uint64((1 << _KMER_ORD_SHIFT) - 1)
+    for their_names, their in states:
+        remap = np.array([names.index(nm) for nm in their_names] + [0], np.uint64)
+        for k, (table, first) in their.items():
+            seen = first != _KMER_NEVER
+            moved = first.copy()
+            moved[seen] = (remap[(first[seen] >> np.uint64(_KMER_ORD_SHIFT)).astype(np.int64)] << np.uint64(_KMER_ORD_SHIFT)) | (first[seen] & low)
+            if k not in tables:
+                tables[k] = (table.copy(), moved)
+            else:
+                tables[k][0][...] += table
+                np.minimum(tables[k][1], moved, out=tables[k][1])
+                _kmer_fold(tables[k][0])
+    return names, tables
+
+
 def _merge_window_table(have, bin0, table):
     """(bin0, table) of a chromosome's windows so far + one part's: the covering table, the part added behind what was there."""
     if have is None or have[1].shape[0] == 0:
@@ -913,12 +1071,20 @@ class SummarySink:
 
     close() writes, with an `out_prefix` and on rank 0, ``{out_prefix}.{W/1000}Kb.mut_rates.tsv`` / ``.corr.txt`` per window size
     (``tables.write_regional_outputs``: the files of ``evaluate --window_size``); ``result()`` and ``scaling_factor()`` are valid after
-    it."""
+    it.
+
+    `kmers`: k-mer lengths (1 .. ``tables.MAX_KMER``) whose rate tables -- ``tables.kmer_table``'s, the third thing ``evaluate`` reads
+    from the written table -- are reduced as well (csrc/summary_kmer.hip: exact integer sums of the probabilities quantised to 2^-71,
+    so the tables depend on the set of rows alone, bit for bit, whatever the parts, chunks or ranks).  `genome`: chromosome name ->
+    packed genome (``HipShardForward.genome``; a sequence will do for host shards); `kmer_strand`: None for SNV rows (each row's own
+    strand), 'pos' / 'neg' / 'both' for INDEL rows (``tables.strand_mode``).  A device part is reduced when it arrives, into accumulators
+    that live with the sink and are read back once, at close(); ranks exchange the integer tables in the same collective.  close() then
+    also writes ``{out_prefix}.{k}-mer.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_kmer_outputs``), and result() has "kmers"."""
 
     takes_aligned_blocks = True
 
     def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
-                 group=None, parts=False):
+                 group=None, parts=False, kmers=(), genome=None, kmer_strand=None):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         self.windows = tuple(int(w) for w in windows)
         if any(w <= 0 for w in self.windows) or len(set(self.windows)) != len(self.windows):
@@ -941,6 +1107,19 @@ class SummarySink:
         self._dev_regions = {}
         self._written = []
         self._result = None
+        from .tables import check_kmer_length, strand_mode
+        self.kmers = tuple(check_kmer_length(k) for k in kmers)
+        if len(set(self.kmers)) != len(self.kmers):
+            raise ValueError(f"k-mer lengths must be distinct (got {self.kmers})")
+        if self.kmers and genome is None:
+            raise ValueError("SummarySink(kmers=...) needs genome=: a callable chromosome name -> packed genome")
+        self._genome = genome
+        self._kmer_indel = kmer_strand is not None
+        self._kmer_mode = strand_mode("indel", kmer_strand) if self._kmer_indel else 0
+        # accumulators, read back once at close(): the tables per k, the first-appearance words per chromosome and k (two chromosomes
+        # share k-mers, and the order between chromosomes -- by name, as in the written table -- is only known when all have arrived)
+        self._kmer_host = ({}, {})     # ({k: table}, {chromosome: {k: first}}) of the host shards
+        self._kmer_dev = {}            # device -> ({k: table}, {chromosome: {k: first}}, status)
 
     # -- one part ---------------------------------------------------------------------------------------------------------
     def _take(self, name, tables, total, n_sites, status):
@@ -962,6 +1141,45 @@ class SummarySink:
             cols = [c[perm] for c in cols]
         regs = None if self._regions is None else self._regions.get(name, (np.zeros(0, np.int64),) * 2)
         self._take(name, *summary_rows_host(cols[3], cols[0], cols[1], cols[2], k, self.windows, regs))
+        if self.kmers:
+            strand = TsvSink._strand_u8(shard["strand"])
+            strand = strand if shard.get("aligned") else strand[perm]
+            tabs, firsts = self._kmer_host
+            for kk in self.kmers:
+                tabs.setdefault(kk, np.zeros((4 ** kk, 3, k), np.uint64))
+            mine = firsts.setdefault(name, {kk: np.full(4 ** kk, _KMER_NEVER, np.uint64) for kk in self.kmers})
+            _, status = summary_kmer_host(self._genome(name), cols[3], cols[0], cols[1], strand, cols[2], k, self.kmers, self._kmer_indel,
+                                          self._kmer_mode, into={kk: (tabs[kk], mine[kk]) for kk in self.kmers})
+            self._status |= status
+
+    def _kmer_device(self, name, dev, prob, start, end, strand, label, k):
+        """Enqueue the k-mer reduction of a part behind its forward: the part's chromosome is the resident one now."""
+        lib = _lib.lib()
+        genome = self._genome(name)
+        if genome.length >= 1 << (_KMER_ORD_SHIFT - 1):
+            raise ValueError(f"k-mer summary: chromosome {name} has 2^39 bases or more")
+        acc = self._kmer_dev.get(dev)
+        if acc is None:
+            acc = self._kmer_dev[dev] = ({kk: torch.zeros(4 ** kk * 3 * k, dtype=torch.int64, device=dev) for kk in self.kmers}, {},
+                                         torch.zeros(1, dtype=torch.int32, device=dev))
+        first = acc[1].get(name)
+        if first is None:              # (all ones: the largest unsigned value)
+            first = acc[1][name] = {kk: torch.full((4 ** kk,), -1, dtype=torch.int64, device=dev) for kk in self.kmers}
+        g = genome.as_struct(dev)
+        stream = _lib.current_stream_ptr(dev)
+        for at in range(0, len(self.kmers), 4):          # MURAL_SUMMARY_MAX_KMERS lengths per call
+            group = self.kmers[at:at + 4]
+            s = _lib.MuralSummaryKmerRows()
+            s.genome = C.pointer(g)
+            s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0)
+            s.start, s.end, s.strand, s.label = start.data_ptr(), end.data_ptr(), strand.data_ptr(), label.data_ptr()
+            s.label_kind = {torch.float32: 0, torch.int32: 1, torch.int64: 2}[label.dtype]
+            s.n, s.n_class, s.n_k, s.indel, s.mode = start.shape[0], k, len(group), int(self._kmer_indel), self._kmer_mode
+            for j, kk in enumerate(group):
+                s.k[j], s.table[j], s.first[j] = kk, acc[0][kk].data_ptr(), first[kk].data_ptr()
+            s.order_base, s.status = 0, acc[2].data_ptr()
+            _lib.check(lib.mural_summary_kmer_rows(C.byref(s), stream))
+        return genome
 
     def _stage_device(self, name, shard, k):
         """Calibrate and order the part on its device, start the read-back of its first and last start."""
@@ -980,18 +1198,24 @@ class SummarySink:
             start, end = to(shard["start"], torch.int64), to(shard["end"], torch.int64)
             label = shard["label"]
             label = to(label, label.dtype if isinstance(label, torch.Tensor) and label.dtype in (torch.int32, torch.int64) else torch.float32)
+            strand = to(TsvSink._strand_u8(shard["strand"]), torch.uint8) if self.kmers else None
             if not shard.get("aligned"):
                 perm = torch.sort(start, stable=True).indices
                 if self.parts:
                     perm = perm[slice(*shard_bounds(perm.shape[0], self.rank, self.world))]
                 prob, start, end, label = prob[perm], start[perm], end[perm], label[perm]
+                strand = strand[perm] if self.kmers else None
             if start.shape[0] == 0:
                 return None
+            # the k-mer tables have a fixed size: reduced now, while this part's chromosome is the resident one; the staged part keeps
+            # the packed genome (and the columns) alive all the same -- the window tables are reduced one part late
+            genome = self._kmer_device(name, dev, prob, start, end, strand, label, k) if self.kmers else None
             ends = torch.empty(2, dtype=torch.int64).pin_memory()
             ends.copy_(torch.stack([start[0], start[-1]]), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return dict(name=name, prob=prob, start=start, end=end, label=label, k=k, ends=ends, event=ev, dev=dev)
+        return dict(name=name, prob=prob, start=start, end=end, label=label, k=k, ends=ends, event=ev, dev=dev, strand=strand,
+                    genome=genome)
 
     def _launch_pending(self):
         """Reduce the staged part: its first and last start (read back by now) size the part's window tables."""
@@ -1082,26 +1306,34 @@ class SummarySink:
 
     # -- close ------------------------------------------------------------------------------------------------------------
     def _merged(self, states):
-        """[(tables, prob_sum, n_sites, status, n_class)] of the ranks, added in rank order."""
+        """[(tables, prob_sum, n_sites, status, n_class, k-mer state)] of the ranks, added in rank order."""
         tables, prob_sum, n_sites, status, k = {}, 0.0, 0, 0, None
-        for t, s, c, st, kk in states:
+        for t, s, c, st, kk, _ in states:
             for name, per_w in t.items():
                 mine = tables.setdefault(name, {})
                 for W, (bin0, tab) in per_w.items():
                     mine[W] = _merge_window_table(mine.get(W), bin0, tab)
             prob_sum, n_sites, status = prob_sum + s, n_sites + c, status | st
             k = kk if k is None else k
-        return tables, prob_sum, n_sites, status, k
+        return tables, prob_sum, n_sites, status, k, _kmer_merge([st[5] for st in states]) if self.kmers else None
 
     def close(self):
         self._launch_pending()
         self._harvest()
-        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class)
+        kmer_state = None
+        if self.kmers:                 # the one read-back of the device accumulators
+            mine = [self._kmer_host]
+            for tabs, firsts, dev_status in self._kmer_dev.values():
+                self._status |= int(dev_status.item())
+                mine.append(({kk: t.cpu().numpy().view(np.uint64).reshape(4 ** kk, 3, -1) for kk, t in tabs.items()},
+                             {nm: {kk: f.cpu().numpy().view(np.uint64) for kk, f in per_k.items()} for nm, per_k in firsts.items()}))
+            kmer_state = _kmer_merge([_kmer_collapse(tabs, firsts) for tabs, firsts in mine if tabs])
+        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class, kmer_state)
         if self.world > 1:
             every = [None] * self.world
             dist.all_gather_object(every, state, group=self.group)      # the one collective: tables, not rows
             state = self._merged(every)
-        tables, prob_sum, n_sites, status, k = state
+        tables, prob_sum, n_sites, status, k, kmer_state = state
         for bit, what in _SUMMARY_STATUS:
             if status & bit:
                 raise ValueError(f"summary: {what}")
@@ -1115,15 +1347,25 @@ class SummarySink:
                 rows.append(t[live])
             windows[W] = (keys, np.concatenate(rows) if rows else np.zeros((0, 1 + 2 * (k or 0))))
         self._result = {"prob_sum": prob_sum, "n_sites": n_sites, "windows": windows}
+        if self.kmers:
+            ktables = kmer_state[1]
+            self._kmer_sums = ktables
+            self._result["kmers"] = {kk: (kmer_table_from_sums(*ktables[kk], kk, k) if kk in ktables else ([], np.zeros((0, 1 + 2 * (k or 0)))))
+                                     for kk in self.kmers}
         if self.out_prefix is not None and self.rank == 0 and k is not None:
             from .tables import regional_output_names, write_regional_outputs
             for W in self.windows:
                 self._written += list(regional_output_names(self.out_prefix, W)[:2])
                 write_regional_outputs(*windows[W], k, W, self.out_prefix, self.ratio_cutoff)
+            from .tables import kmer_output_names, write_kmer_outputs
+            for kk in self.kmers:
+                self._written += list(kmer_output_names(self.out_prefix, kk))
+                write_kmer_outputs(*self._result["kmers"][kk], k, kk, self.out_prefix)
 
     def abort(self):
         """Drop what was reduced and remove any file close() began: the caller's run failed."""
         self._pending, self._inflight, self._tables, self._result = None, [], {}, None
+        self._kmer_host, self._kmer_dev = ({}, {}), {}
         for path in self._written:
             if os.path.exists(path):
                 os.unlink(path)
@@ -1131,10 +1373,17 @@ class SummarySink:
 
     def result(self):
         """{"prob_sum", "n_sites", "windows": {W: ([(chrom, window_end)], table [windows][1 + 2 n_class])}} after close(): the pair of
-        ``tables.prob_sum_file`` and, per window size, of ``tables.regional_table`` (chromosomes by name, windows ascending)."""
+        ``tables.prob_sum_file`` and, per window size, of ``tables.regional_table`` (chromosomes by name, windows ascending); with `kmers`
+        also "kmers": {k: (names, table [k-mers][1 + 2 n_class])}, the pair of ``tables.kmer_table``.  ``kmer_sums()`` has the integers."""
         if self._result is None:
             raise RuntimeError("SummarySink.result() is valid after close()")
         return self._result
+
+    def kmer_sums(self):
+        """{k: (table uint64 [4^k][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^k])} after close(): the exact
+        sums behind result()["kmers"] (``summary_kmer_host``'s layout)."""
+        self.result()
+        return self._kmer_sums
 
     def scaling_factor(self, genomewide_mu, m_proportion, g_proportion=1.0):
         """``tables.calc_mu_scaling_factor``'s factor for the summarised rows, with the lines it prints."""

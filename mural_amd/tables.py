@@ -420,18 +420,24 @@ def run_kmer_corr_calc(args, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
     n_class = args.n_class
     names, table = kmer_table(os.fspath(args.pred_file), os.fspath(args.ref_genome), args.kmer_length, n_class, model_type,
                               getattr(args, "strand", None), chunk_bytes)
+    return write_kmer_outputs(names, table, n_class, args.kmer_length, args.out_prefix)
+
+
+def write_kmer_outputs(names, table, n_class, kmer_length, out_prefix):
+    """The two files of calc_kmer_corr.py:252-270 from a k-mer table (``kmer_table``'s pair, or the one a ``predict.SummarySink``
+    reduced in flight): per k-mer observed / predicted rates and counts, Pearson r per class.  Returns [(class, (r, p))]."""
     obs, pred, cnt, tot = _rates(table, n_class)
     cls = range(1, n_class)
     header = (["type"] + [f"avg_obs_rate{i}" for i in cls] + [f"avg_pred_rate{i}" for i in cls] + [f"number_of_mut{i}" for i in cls]
               + ["number_of_all"])
     rows = [[nm] + [_float_text(v) for v in obs[j]] + [_float_text(v) for v in pred[j]] + [str(int(v)) for v in cnt[j]] + [str(int(tot[j]))]
             for j, nm in enumerate(names)]
-    rates_path, corr_path = kmer_output_names(args.out_prefix, args.kmer_length)
+    rates_path, corr_path = kmer_output_names(out_prefix, kmer_length)
     corrs = [(c, pearson(obs[:, c - 1], pred[:, c - 1])) for c in cls]
     with open(rates_path, "w") as fh:
         fh.write(_rates_text(header, rows))
     with open(corr_path, "w") as fh:
-        fh.write(_corr_text(f"{args.kmer_length}-mer", corrs))
+        fh.write(_corr_text(f"{kmer_length}-mer", corrs))
     return corrs
 
 
@@ -551,5 +557,5 @@ def print_scaling_factor(genomewide_mu, n_sites, g_proportion, m_proportion, pro
 # in-memory rule and stays as it is
 apply_scaling = apply_scaling_file
 
-__all__ = ["TableReader", "apply_scaling_file", "scaling_files", "calc_mu_scaling_factor", "run_kmer_corr_calc", "run_regional_corr_calc", "write_regional_outputs",
+__all__ = ["TableReader", "apply_scaling_file", "scaling_files", "calc_mu_scaling_factor", "run_kmer_corr_calc", "run_regional_corr_calc", "write_regional_outputs", "write_kmer_outputs",
            "prob_sum_file", "read_regions", "kmer_table", "regional_table", "check_header", "read_header", "DEFAULT_CHUNK_BYTES", "MAX_KMER"]

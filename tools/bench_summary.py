@@ -1,13 +1,16 @@
 """Genome summaries in flight against the table route to the same numbers:
-  python tools/bench_summary.py [--bases N] [--repeats K]
+  python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Four legs, alternating, --repeats timed runs each after one warm-up run each:
+the device (predict_regions_sharded), files in /dev/shm.  Six legs (--legs picks some by name; the agreement checks need their legs),
+alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
   c  tee       TeeSink of both
   d  tools     the route to b's numbers without this sink: leg a's table, then prob_sum_file + regional_table (100 kb, 1 kb) on it
-Prints one JSON line; the summary of leg b must agree with leg d's within the table's four digits."""
+  e  kmers       leg b with kmers=(3, 5, 7) as well: the k-mer tables reduced from the resident chromosome
+  f  kmer_tools  the route to e's k-mer tables without the sink: leg a's table, then tables.kmer_table x 3 on it (the FASTA packed again)
+Prints one JSON line; the summary of leg b must agree with leg d's, and leg e's k-mer tables with leg f's, within the table's four digits."""
 import json
 import os
 import shutil
@@ -27,12 +30,16 @@ from mural_amd import tables  # noqa: E402
 from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, predict_regions_sharded  # noqa: E402
 
 WINDOWS = (100_000, 1000)
-LEGS = ("table", "summary", "tee", "tools")
+KMERS = (3, 5, 7)
+LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools")
 
 
 def main(argv):
     bases = int(argv[argv.index("--bases") + 1]) if "--bases" in argv else 50_000_000
     repeats = int(argv[argv.index("--repeats") + 1]) if "--repeats" in argv else 3
+    legs = tuple(argv[argv.index("--legs") + 1].split(",")) if "--legs" in argv else LEGS
+    if set(legs) - set(LEGS):
+        raise SystemExit(f"--legs: one of {LEGS}")
     if not torch.cuda.is_available():
         raise SystemExit("bench_summary needs a HIP device")
     device = torch.device("cuda", 0)
@@ -52,8 +59,10 @@ def main(argv):
             t0 = time.perf_counter()
             fwd = HipShardForward(model, fa, r, order, device=device, reuse=True)
             summary = SummarySink(windows=WINDOWS) if leg in ("summary", "tee") else None
-            sink = {"table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary,
-                    "tee": lambda: TeeSink(TsvSink(out), summary)}[leg]()
+            if leg == "kmers":
+                summary = SummarySink(windows=WINDOWS, kmers=KMERS, genome=fwd.genome)
+            sink = {"table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
+                    "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out)}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split)
             torch.cuda.synchronize()
             extra["predict"] = time.perf_counter() - t0
@@ -67,33 +76,47 @@ def main(argv):
                     wins[W] = tables.regional_table(out, W, n_class)
                     extra["regional_table_%d" % W] = time.perf_counter() - t1
                 kept["tools"] = {"prob_sum": total, "n_sites": n_sites, "windows": wins}
+            if leg == "kmer_tools":
+                kept["kmer_tools"] = {}
+                for k in KMERS:
+                    t1 = time.perf_counter()
+                    kept["kmer_tools"][k] = tables.kmer_table(out, fa, k, n_class, "snv")
+                    extra["kmer_table_%d" % k] = time.perf_counter() - t1
             dt = time.perf_counter() - t0
             assert n == rows, (leg, n, rows)
             if summary is not None:
                 kept[leg] = summary.result()
             return dt, dict({k: v for k, v in split.items() if isinstance(v, float)}, **extra)
 
-        seconds, splits = {leg: [] for leg in LEGS}, {}
+        seconds, splits = {leg: [] for leg in legs}, {}
         for i in range(repeats + 1):
-            for leg in LEGS:
+            for leg in legs:
                 dt, split = run(leg)
                 if i:                                      # (round 0 warms kernels, allocator pools and the page cache)
                     seconds[leg].append(dt)
                     splits[leg] = split
-        table_bytes = os.path.getsize(out)
-    a, d = kept["summary"], kept["tools"]
-    agree = a["n_sites"] == d["n_sites"] and abs(a["prob_sum"] - d["prob_sum"]) <= 5e-4 * a["prob_sum"] and kept["tee"]["n_sites"] == a["n_sites"]
-    for W in WINDOWS:
-        (ka, ta), (kd, td) = a["windows"][W], d["windows"][W]
-        k = 1 + n_class
-        agree = agree and ka == kd and (ta[:, :k] == td[:, :k]).all() and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
-        agree = agree and bool((kept["tee"]["windows"][W][1] == ta).all())      # bit for bit, with or without the table beside it
-    rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in LEGS}
-    med = {leg: rate[leg]["median"] for leg in LEGS}
+        table_bytes = os.path.getsize(out) if os.path.exists(out) else 0
+    agree, k = True, 1 + n_class
+    if {"summary", "tools", "tee"} <= set(legs):
+        a, d = kept["summary"], kept["tools"]
+        agree = a["n_sites"] == d["n_sites"] and abs(a["prob_sum"] - d["prob_sum"]) <= 5e-4 * a["prob_sum"] and kept["tee"]["n_sites"] == a["n_sites"]
+        for W in WINDOWS:
+            (ka, ta), (kd, td) = a["windows"][W], d["windows"][W]
+            agree = agree and ka == kd and (ta[:, :k] == td[:, :k]).all() and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
+            agree = agree and bool((kept["tee"]["windows"][W][1] == ta).all())      # bit for bit, with or without the table beside it
+    if {"kmers", "kmer_tools"} <= set(legs):
+        for kk in KMERS:
+            (na, ta), (nd, td) = kept["kmers"]["kmers"][kk], kept["kmer_tools"][kk]
+            agree = agree and na == nd and bool((ta[:, :k] == td[:, :k]).all()) and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
+    rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in legs}
+    med = {leg: rate[leg]["median"] for leg in legs}
+    sec = {leg: statistics.median(seconds[leg]) for leg in legs}
+    ratio = lambda x, y, of: of[x] / of[y] if x in of and y in of else None      # noqa: E731
     res = {"workload": "one chromosome of %d bases, focal A, Homo_sapiens/SNV/AT weights, sites enumerated on the device" % bases,
-           "rows": rows, "table_bytes": table_bytes, "windows": list(WINDOWS), "repeats": repeats, "summaries_agree": bool(agree),
-           "rows_per_s": rate, "summary_over_table": med["summary"] / med["table"], "tee_over_table": med["tee"] / med["table"],
-           "tools_over_summary_seconds": statistics.median(seconds["tools"]) / statistics.median(seconds["summary"]),
+           "rows": rows, "table_bytes": table_bytes, "windows": list(WINDOWS), "kmers": list(KMERS), "repeats": repeats,
+           "summaries_agree": bool(agree), "rows_per_s": rate, "summary_over_table": ratio("summary", "table", med),
+           "tee_over_table": ratio("tee", "table", med), "tools_over_summary_seconds": ratio("tools", "summary", sec),
+           "kmers_over_summary": ratio("kmers", "summary", med), "kmer_tools_over_kmers_seconds": ratio("kmer_tools", "kmers", sec),
            "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}
     print(json.dumps(res))
     if not agree:

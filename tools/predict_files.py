@@ -9,6 +9,10 @@ position is a site and --focal / --context do not apply).
 Genome summaries in flight, in both forms (mural_amd.predict.SummarySink; the numbers `calc_scaling_factor` and `evaluate --window_size`
 read back from the table, taken from the probabilities before they are rounded):
   --summary PREFIX  --window_size W [--window_size W ..]   PREFIX.{W/1000}Kb.mut_rates.tsv and .corr.txt per window size
+  --summary PREFIX  --kmer_length K [--kmer_length K ..]   PREFIX.{K}-mer.mut_rates.tsv and .corr.txt per k-mer length: the files of
+                                                             `evaluate --kmer_only`, the flanks read from the resident chromosome
+                                                             (with either or both of --window_size / --kmer_length)
+  --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
   --no-table                                                 summaries only: leave OUT.tsv out
@@ -21,7 +25,7 @@ from mural_amd.calibration import load_dirichlet_weights  # noqa: E402
 from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
-_SUMMARY_OPTIONS = ("--summary", "--window_size", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
+_SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
                     "--scale_factor")
 _VALUE_OPTIONS = ("--regions", "--focal", "--context") + _SUMMARY_OPTIONS
 
@@ -49,7 +53,7 @@ def main(argv):
     flags, args, values = _split(argv)
     model_type = "indel" if "--indel" in flags else "snv"
     poisson = "--poisson" in flags or model_type == "indel"
-    opts = _summary_options(flags, values)
+    opts = _summary_options(flags, values, model_type)
     n_args = (3 if "--regions" in values else 4) - int(opts["no_table"])
     if opts["no_table"] and len(args) == n_args + 1:
         raise SystemExit(f"--no-table writes no table: leave {args[-1]} out")
@@ -75,17 +79,33 @@ def main(argv):
     print(f"{len(res['start'])} sites -> {out}")
 
 
-def _summary_options(flags, values):
+def _summary_options(flags, values, model_type="snv"):
     """The summary / scaling options, checked before anything is loaded."""
     one = lambda name, kind: None if name not in values else kind(values[name][-1])      # noqa: E731
     opts = {"summary": one("--summary", str), "windows": tuple(int(w) for w in values.get("--window_size", [])),
             "benchmark_regions": one("--benchmark_regions", str), "genomewide_mu": one("--genomewide_mu", float),
             "m_proportion": one("--m_proportion", float), "g_proportion": one("--g_proportion", float),
-            "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags}
+            "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags,
+            "kmers": tuple(int(k) for k in values.get("--kmer_length", [])), "strand": one("--strand", str)}
     if opts["windows"] and opts["summary"] is None:
         raise SystemExit("--window_size needs --summary PREFIX: the prefix of the files it writes")
-    if opts["summary"] is not None and not opts["windows"]:
-        raise SystemExit("--summary PREFIX needs a --window_size")
+    if opts["kmers"] and opts["summary"] is None:
+        raise SystemExit("--kmer_length needs --summary PREFIX: the prefix of the files it writes")
+    if opts["summary"] is not None and not opts["windows"] and not opts["kmers"]:
+        raise SystemExit("--summary PREFIX needs a --window_size or a --kmer_length")
+    if opts["kmers"]:
+        from mural_amd.tables import check_kmer_length, strand_mode
+        try:
+            for k in opts["kmers"]:
+                check_kmer_length(k)
+            if model_type == "indel" or opts["strand"] is not None:
+                if model_type != "indel":
+                    raise ValueError("--strand goes with --indel")
+                strand_mode("indel", opts["strand"])
+        except ValueError as e:
+            raise SystemExit(f"--kmer_length: {e}") from None
+    elif opts["strand"] is not None:
+        raise SystemExit("--strand selects the strand of the k-mer tables: it goes with --indel and --kmer_length")
     if (opts["genomewide_mu"] is None) != (opts["m_proportion"] is None):
         raise SystemExit("the scaling factor needs --genomewide_mu and --m_proportion")
     if opts["g_proportion"] is not None and opts["genomewide_mu"] is None:
@@ -115,7 +135,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
     if out is not None:
         sinks.append(TsvSink(out, **sink_chain))
     if opts["wants_summary"]:
-        summary = SummarySink(opts["summary"], opts["windows"], opts["benchmark_regions"], **sink_chain)
+        summary = SummarySink(opts["summary"], opts["windows"], opts["benchmark_regions"], kmers=opts["kmers"], genome=forward.genome,
+                              kmer_strand=opts["strand"] if model_type == "indel" else None, **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
