@@ -628,6 +628,47 @@ int32_t mural_summary_kmer_in_lds(int32_t k, int32_t n_class);
 int mural_summary_kmer_rows(const MuralSummaryKmerRows* s, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Motif rate tables (`evaluate --motif_only`, MuRaL/scripts/calc_motif_corr.py:191-261; SummarySink(motifs=...) in flight,
+ * tables.motif_table from a written table; csrc/summary_kmer.hip): one pass over the rows (any order) of a part of ONE
+ * chromosome, for up to MURAL_SUMMARY_MAX_KMERS motif lengths m (odd, 3 .. 15) at once.  A row adds to every window of m
+ * bases that contains its site, on the reference strand (no strand is read): window i is the Python slice
+ * chrom[start - i : end + m-1 - i], i = 0 .. m-1, of an SNV row and chrom[start - i + 1 : end + m - i], i = 1 .. m-1, of an
+ * INDEL row (`indel`); a window that is not m bases long after Python's clipping, or holds a base other than A/C/G/T, is
+ * skipped, the row's other windows still count.  A motif and its reverse complement share the cell of
+ * min(key, revcomp(key)), key = the base-4 number of the window (A0 C1 G2 T3, first base most significant): the tables
+ * are indexed by all 4^m keys and the half of them that is the larger of its pair stays zero.  The cells, their
+ * quantisation and the integer atomics are mural_summary_kmer_rows'.
+ *   table[j] [4^m[j]][3][n_class] += per window { 1 for the row's label, hi of prob[:, c], lo of prob[:, c] }; on return
+ *     lo < 2^40 (carried into hi after at most 2^18 rows: a row adds up to m <= 15 times to one cell, so lo stays below
+ *     2^40 + 15 * 2^18 * 2^40 < 2^63; hi is exact for floor((2^32 - 2) / m) rows in one cell); zeroed by the caller;
+ *   first[j] [4^m[j]] = min(first, (order_base + pos) << 5 | i << 1 | o), pos = the row's start, or with order_by_row
+ *     its index in this call; o = 1 where the window's own key is the larger of the pair.  The minimum is the window
+ *     the reference sees first (rows in table order, i ascending), which fixes the dict order of the entries and, by o,
+ *     the orientation an entry is named after; set to all ones by the caller; 0 <= order_base + pos < 2^58;
+ *   status: as mural_summary_kmer_rows; such rows are skipped in every table.
+ * mural_summary_motif_in_lds: mural_summary_kmer_in_lds' rule, 4^m * (3 n_class + 1) * 8 bytes <= 160 KiB (0 for an m
+ * that is refused).  One launch per m.  Launches on `stream`, no synchronisation.  n_class <= 8.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const MuralGenome* genome; /* the chromosome of the rows */
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 0 .. n_class-1 are read          */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n] */
+  const int64_t* end;        /* dev [n] */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_m, indel, order_by_row;
+  int32_t m[MURAL_SUMMARY_MAX_KMERS];
+  uint64_t* table[MURAL_SUMMARY_MAX_KMERS];         /* dev */
+  uint64_t* first[MURAL_SUMMARY_MAX_KMERS];         /* dev */
+  int64_t order_base;
+  int32_t* status;           /* dev [1] */
+} MuralSummaryMotifRows;
+int32_t mural_summary_motif_in_lds(int32_t m, int32_t n_class);
+int mural_summary_motif_rows(const MuralSummaryMotifRows* s, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

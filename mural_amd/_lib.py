@@ -108,6 +108,13 @@ class MuralSummaryKmerRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSummaryMotifRows(C.Structure):
+    _fields_ = [("genome", C.POINTER(MuralGenome)), ("prob", C.c_void_p), ("prob_f64", C.c_int32), ("label_kind", C.c_int32),
+                ("prob_stride", C.c_int64), ("start", C.c_void_p), ("end", C.c_void_p), ("label", C.c_void_p), ("n", C.c_int64),
+                ("n_class", C.c_int32), ("n_m", C.c_int32), ("indel", C.c_int32), ("order_by_row", C.c_int32), ("m", C.c_int32 * 4),
+                ("table", C.c_void_p * 4), ("first", C.c_void_p * 4), ("order_base", C.c_int64), ("status", C.c_void_p)]
+
+
 VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
 
 # every symbol include/mural_hip.h declares: name -> (restype, argtypes)
@@ -234,6 +241,8 @@ PROTOTYPES = {
     "mural_summary_rows": (C.c_int, [C.POINTER(MuralSummaryRows), VP, C.c_size_t, VP]),
     "mural_summary_kmer_in_lds": (I32, [I32, I32]),
     "mural_summary_kmer_rows": (C.c_int, [C.POINTER(MuralSummaryKmerRows), VP]),
+    "mural_summary_motif_in_lds": (I32, [I32, I32]),
+    "mural_summary_motif_rows": (C.c_int, [C.POINTER(MuralSummaryMotifRows), VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

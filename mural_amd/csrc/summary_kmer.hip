@@ -17,6 +17,22 @@
 //     2^40 each, so lo < 2^40 + 2^22 * 2^40 < 2^63 before the next fold.  hi is at most (2^31 + 1) per addition: below 2^64 -- the
 //     cells are read as UNSIGNED 64-bit numbers -- for 2^32 - 2 additions to one cell, more than a genome of 2^32 rows can make in
 //     modes 0 .. 2 (and in mode 3 unless over half of its rows share one palindrome).
+//
+// Motif rate tables (`evaluate --motif_only`, MuRaL/scripts/calc_motif_corr.py:191-261; SummarySink(motifs=...) and tables.motif_table)
+// are the same cells under another key rule: a row adds to EVERY window of m bases (m odd) that contains its site -- m windows of an
+// SNV row (i = 0 .. m-1: chrom[start - i : end + m-1 - i]), m - 1 of an INDEL row (i = 1 .. m-1, the SNV windows 0 .. m-2) --, all on
+// the reference strand, and a motif shares its cell with its reverse complement: the cell is that of min(key, revcomp(key)) in a table
+// indexed by all 4^m keys, of which the half that is the larger of its pair stays zero.
+//   * one read per row: the windows of a row of one base (end = start + 1) away from the chromosome's ends are the m-grams of 2m - 1
+//     consecutive bases; these are decoded once, the forward and the reverse-complement key rolled across them (two shifts and a mask per
+//     base) with a count of the bases since the last non-ACGT one.  Any other row -- within m - 1 bases of an end, or longer than a base,
+//     whose unclipped windows all have the wrong length -- clips every window as a Python slice and decodes the few that are m long
+//     (kmer_key.h: the clipping, the base decode and the window decode are the k-mer key's).
+//   * first[key] = min over the windows of ((order_base + pos) << 5 | i << 1 | o): pos the row's start (or its index in the call,
+//     order_by_row), i the window, o = 1 where the window's own key is the larger of the pair.  The minimum is the first window in the
+//     reference's order (rows ascending, i ascending within a row) AND says under which orientation the reference names the entry.
+//   * fold: a row adds up to m <= 15 times to one cell (a homopolymer run), so the slice between two folds is SM_FOLD_ROWS = 2^18 rows:
+//     lo < 2^40 + 15 * 2^18 * 2^40 < 2^63.  hi grows by at most 2^31 + 1 per addition: exact for floor((2^32 - 2) / m) rows in one cell.
 #include "common.h"
 #include "kmer_key.h"
 
@@ -26,6 +42,7 @@ namespace {
 constexpr int SK_THREADS = 256;
 constexpr int SK_MAX_CLASS = 8;
 constexpr int64_t SK_FOLD_ROWS = 1ll << 21;       // rows between two folds (the bound above)
+constexpr int64_t SM_FOLD_ROWS = 1ll << 18;       // ... of the motif tables: up to 15 additions of a row to one cell
 constexpr int64_t SK_BLOCK_ROWS = 1ll << 14;      // rows of a workgroup: one LDS table is zeroed and flushed per that many rows
 constexpr size_t SK_LDS_BYTES = 160 * 1024;       // LDS of a CU (a single workgroup may take all of it)
 constexpr int SK_LO_BITS = 40;
@@ -40,7 +57,7 @@ struct KmerArgs {
   const uint8_t* strand;
   const void* label;
   int64_t prob_stride, n, order_base;
-  int32_t label_kind, n_class, indel, mode, n_k;
+  int32_t label_kind, n_class, indel, mode, n_k, by_row;      // (k-mer: mode; motif: by_row)
   int32_t k[MURAL_SUMMARY_MAX_KMERS], in_lds[MURAL_SUMMARY_MAX_KMERS];
   u64* table[MURAL_SUMMARY_MAX_KMERS];      // [4^k][3][n_class]: label counts | sums of hi | sums of lo
   u64* first[MURAL_SUMMARY_MAX_KMERS];      // [4^k]
@@ -55,6 +72,78 @@ __device__ __forceinline__ void global_first(u64* __restrict__ first, int64_t ke
   if (first[key] > ord) atomicMin(&first[key], ord);
 }
 
+// The checks of a row (status bits, 0 if it counts) and its probabilities as the two limbs.
+template <typename T>
+__device__ __forceinline__ int32_t quantise_row(const T* __restrict__ prob, int nc, int64_t st, int lab, u64 (&hi)[SK_MAX_CLASS],
+                                                u64 (&lo)[SK_MAX_CLASS]) {
+  int32_t bad_row = 0;
+  if (st < 0) bad_row |= SM_BAD_START;
+  if (lab < 0 || lab >= nc) bad_row |= SM_BAD_LABEL;
+#pragma unroll
+  for (int c = 0; c < SK_MAX_CLASS; ++c) {
+    hi[c] = 0, lo[c] = 0;
+    if (c < nc) {
+      const double p = (double)prob[c];      // (float -> double is exact)
+      // 0 <= p <= 1 on the bit pattern -- non-negative doubles order like their bits --, so that NaN is caught whatever the
+      // compiler assumes about comparisons; -0.0 counts as 0
+      const u64 bits = (u64)__double_as_longlong(p);
+      if (bits > 0x3FF0000000000000ull && bits != 0x8000000000000000ull) {
+        bad_row |= SM_BAD_PROB;
+      } else {
+        const double s = p * 2147483648.0;                       // p * 2^31
+        const double h = floor(s);
+        hi[c] = (u64)(long long)h;
+        lo[c] = (u64)(long long)rint((s - h) * 1099511627776.0);      // * 2^40, half to even
+      }
+    }
+  }
+  return bad_row;
+}
+
+// One row into the cell of `key`: cells = an LDS table's [3 n_class + 1] per key (the last the first-appearance word) when in_lds,
+// the global table's [3 n_class] otherwise, with the word in first[].  (Two instantiations, each called with its own pointer, so that
+// the LDS one keeps LDS atomics.)
+template <bool in_lds>
+__device__ __forceinline__ void add_row(u64* __restrict__ cells, u64* __restrict__ first, int64_t key, int nc, int lab,
+                                        const u64 (&hi)[SK_MAX_CLASS], const u64 (&lo)[SK_MAX_CLASS], u64 ord) {
+  u64* cell = cells + key * (in_lds ? 3 * nc + 1 : 3 * nc);
+  atomicAdd(&cell[lab], 1ull);
+#pragma unroll
+  for (int c = 0; c < SK_MAX_CLASS; ++c) {
+    if (c < nc) {
+      if (hi[c]) atomicAdd(&cell[nc + c], hi[c]);
+      if (lo[c]) atomicAdd(&cell[2 * nc + c], lo[c]);
+    }
+  }
+  if (in_lds)
+    atomicMin(&cell[3 * nc], ord);
+  else
+    global_first(first, key, ord);
+}
+
+// The prologue and the epilogue of a rows kernel whose table lives in LDS: all cells zero and the words at "never"; the non-zero cells
+// added to the global table once.
+__device__ __forceinline__ void lds_table_clear(u64* __restrict__ cells, int64_t groups, int n_cells) {
+  for (int64_t c = threadIdx.x; c < groups * n_cells; c += SK_THREADS) cells[c] = (c % n_cells == n_cells - 1) ? SK_NEVER : 0ull;
+  __syncthreads();
+}
+
+__device__ __forceinline__ void lds_table_flush(const u64* __restrict__ cells, int64_t groups, int nc, u64* __restrict__ table,
+                                                u64* __restrict__ first) {
+  const int n_cells = 3 * nc + 1;
+  __syncthreads();
+  for (int64_t c = threadIdx.x; c < groups * n_cells; c += SK_THREADS) {
+    const u64 v = cells[c];
+    const int64_t key = c / n_cells;
+    const int col = (int)(c % n_cells);
+    if (col == n_cells - 1) {
+      if (v != SK_NEVER) global_first(first, key, v);
+    } else if (v) {
+      atomicAdd(&table[key * (3 * nc) + col], v);
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(SK_THREADS) void summary_kmer_rows_kernel(KmerArgs A, int j, int64_t row0, int64_t row1) {
   extern __shared__ u64 sk_cells[];
@@ -64,38 +153,15 @@ __global__ __launch_bounds__(SK_THREADS) void summary_kmer_rows_kernel(KmerArgs 
   const int64_t groups = (int64_t)1 << (2 * k);
   u64* __restrict__ table = A.table[j];
   u64* __restrict__ first = A.first[j];
-  if (in_lds) {
-    for (int64_t c = threadIdx.x; c < groups * cells; c += SK_THREADS) sk_cells[c] = (c % cells == cells - 1) ? SK_NEVER : 0ull;
-    __syncthreads();
-  }
+  if (in_lds) lds_table_clear(sk_cells, groups, cells);
   const T* __restrict__ prob = static_cast<const T*>(A.prob);
   const int64_t b0 = row0 + (int64_t)blockIdx.x * SK_BLOCK_ROWS, b1 = min(b0 + SK_BLOCK_ROWS, row1);
   int32_t bad = 0;
   for (int64_t i = b0 + threadIdx.x; i < b1; i += SK_THREADS) {
     const int64_t st = A.start[i];
     const int lab = load_label(A.label, A.label_kind, i);
-    int32_t bad_row = 0;
-    if (st < 0) bad_row |= SM_BAD_START;
-    if (lab < 0 || lab >= nc) bad_row |= SM_BAD_LABEL;
     u64 hi[SK_MAX_CLASS], lo[SK_MAX_CLASS];
-#pragma unroll
-    for (int c = 0; c < SK_MAX_CLASS; ++c) {
-      hi[c] = 0, lo[c] = 0;
-      if (c < nc) {
-        const double p = (double)prob[i * A.prob_stride + c];      // (float -> double is exact)
-        // 0 <= p <= 1 on the bit pattern -- non-negative doubles order like their bits --, so that NaN is caught whatever the
-        // compiler assumes about comparisons; -0.0 counts as 0
-        const u64 bits = (u64)__double_as_longlong(p);
-        if (bits > 0x3FF0000000000000ull && bits != 0x8000000000000000ull) {
-          bad_row |= SM_BAD_PROB;
-        } else {
-          const double s = p * 2147483648.0;                       // p * 2^31
-          const double h = floor(s);
-          hi[c] = (u64)(long long)h;
-          lo[c] = (u64)(long long)rint((s - h) * 1099511627776.0);      // * 2^40, half to even
-        }
-      }
-    }
+    const int32_t bad_row = quantise_row(prob + i * A.prob_stride, nc, st, lab, hi, lo);
     if (bad_row) {
       bad |= bad_row;
       continue;
@@ -108,44 +174,70 @@ __global__ __launch_bounds__(SK_THREADS) void summary_kmer_rows_kernel(KmerArgs 
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       if (key[sub] < 0) continue;
-      if (in_lds) {
-        u64* cell = sk_cells + (int64_t)key[sub] * cells;
-        atomicAdd(&cell[lab], 1ull);
-#pragma unroll
-        for (int c = 0; c < SK_MAX_CLASS; ++c) {
-          if (c < nc) {
-            if (hi[c]) atomicAdd(&cell[nc + c], hi[c]);
-            if (lo[c]) atomicAdd(&cell[2 * nc + c], lo[c]);
-          }
-        }
-        atomicMin(&cell[3 * nc], ord + sub);
-      } else {
-        u64* cell = table + (int64_t)key[sub] * (3 * nc);
-        atomicAdd(&cell[lab], 1ull);
-#pragma unroll
-        for (int c = 0; c < SK_MAX_CLASS; ++c) {
-          if (c < nc) {
-            if (hi[c]) atomicAdd(&cell[nc + c], hi[c]);
-            if (lo[c]) atomicAdd(&cell[2 * nc + c], lo[c]);
-          }
-        }
-        global_first(first, key[sub], ord + sub);
+      if (in_lds)
+        add_row<true>(sk_cells, first, key[sub], nc, lab, hi, lo, ord + sub);
+      else
+        add_row<false>(table, first, key[sub], nc, lab, hi, lo, ord + sub);
+    }
+  }
+  if (in_lds) lds_table_flush(sk_cells, groups, nc, table, first);
+  if (bad) atomicOr(A.status, bad);
+}
+
+// The motif windows of a row: see the head of the file.
+template <typename T>
+__global__ __launch_bounds__(SK_THREADS) void summary_motif_rows_kernel(KmerArgs A, int j, int64_t row0, int64_t row1) {
+  extern __shared__ u64 sk_cells[];
+  const int m = A.k[j], nc = A.n_class;
+  const bool in_lds = A.in_lds[j] != 0;
+  const int64_t groups = (int64_t)1 << (2 * m);
+  u64* __restrict__ table = A.table[j];
+  u64* __restrict__ first = A.first[j];
+  if (in_lds) lds_table_clear(sk_cells, groups, 3 * nc + 1);
+  const T* __restrict__ prob = static_cast<const T*>(A.prob);
+  const int64_t b0 = row0 + (int64_t)blockIdx.x * SK_BLOCK_ROWS, b1 = min(b0 + SK_BLOCK_ROWS, row1);
+  const int n_win = m - A.indel;                    // window w = 0 .. n_win - 1 is chrom[start - w : end + m-1 - w], the reference's i = w + indel
+  const uint32_t mask = (uint32_t)(groups - 1);
+  int32_t bad = 0;
+  for (int64_t i = b0 + threadIdx.x; i < b1; i += SK_THREADS) {
+    const int64_t st = A.start[i], en = A.end[i];
+    const int lab = load_label(A.label, A.label_kind, i);
+    u64 hi[SK_MAX_CLASS], lo[SK_MAX_CLASS];
+    const int32_t bad_row = quantise_row(prob + i * A.prob_stride, nc, st, lab, hi, lo);
+    if (bad_row) {
+      bad |= bad_row;
+      continue;
+    }
+    const u64 ord = (u64)(A.order_base + (A.by_row ? i : st)) << 5;
+    auto add = [&](int32_t fwd, int32_t rev, int w) {
+      const u64 word = ord | (u64)((w + A.indel) << 1) | (fwd > rev ? 1u : 0u);
+      if (in_lds)
+        add_row<true>(sk_cells, first, min(fwd, rev), nc, lab, hi, lo, word);
+      else
+        add_row<false>(table, first, min(fwd, rev), nc, lab, hi, lo, word);
+    };
+    if (en - st == 1 && st >= n_win - 1 && en + (m - 1) <= A.g.length) {
+      // no window is clipped: the m-grams of bases start - (n_win-1) .. start + m-1, the one that ends at base q being window
+      // w = start + m-1 - q
+      uint32_t fwd = 0, rev = 0;
+      int run = 0;                                  // bases since the last one that is not A/C/G/T
+      for (int64_t q = st - (n_win - 1); q < st + m; ++q) {
+        bool n_base = false;
+        const uint32_t code = (uint32_t)kmer_base(A.g, q, n_base);
+        fwd = ((fwd << 2) | code) & mask;
+        rev = (rev >> 2) | ((3u - code) << (2 * (m - 1)));
+        run = n_base ? 0 : run + 1;
+        if (run >= m) add((int32_t)fwd, (int32_t)rev, (int)(st + (m - 1) - q));
+      }
+    } else {
+      for (int w = 0; w < n_win; ++w) {
+        int32_t fwd, rev;
+        kmer_window_decode(A.g, st - w, en + (m - 1) - w, m, fwd, rev);
+        if (fwd >= 0) add(fwd, rev, w);
       }
     }
   }
-  if (in_lds) {
-    __syncthreads();
-    for (int64_t c = threadIdx.x; c < groups * cells; c += SK_THREADS) {
-      const u64 v = sk_cells[c];
-      const int64_t key = c / cells;
-      const int col = (int)(c % cells);
-      if (col == cells - 1) {
-        if (v != SK_NEVER) global_first(first, key, v);
-      } else if (v) {
-        atomicAdd(&table[key * (3 * nc) + col], v);
-      }
-    }
-  }
+  if (in_lds) lds_table_flush(sk_cells, groups, nc, table, first);
   if (bad) atomicOr(A.status, bad);
 }
 
@@ -212,6 +304,59 @@ extern "C" int mural_summary_kmer_rows(const MuralSummaryKmerRows* s, void* stre
         hipLaunchKernelGGL(summary_kmer_rows_kernel<double>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, A, j, r0, r1);
       else
         hipLaunchKernelGGL(summary_kmer_rows_kernel<float>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, A, j, r0, r1);
+      MURAL_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(summary_kmer_fold_kernel, fold_grid, dim3(SK_THREADS), 0, (hipStream_t)stream, A);
+    MURAL_HIP_CHECK(hipGetLastError());
+  }
+  return MURAL_OK;
+}
+
+extern "C" int32_t mural_summary_motif_in_lds(int32_t m, int32_t n_class) {
+  if (m < 3 || m > 15 || m % 2 == 0) return 0;
+  return mural_summary_kmer_in_lds(m, n_class);
+}
+
+extern "C" int mural_summary_motif_rows(const MuralSummaryMotifRows* s, void* stream) {
+  MURAL_REQUIRE(s && s->genome, "summary_motif_rows: NULL argument");
+  MURAL_REQUIRE(s->n >= 0 && s->n_class >= 1 && s->n_class <= SK_MAX_CLASS, "summary_motif_rows: n >= 0 and 1 <= n_class <= %d required",
+                SK_MAX_CLASS);
+  MURAL_REQUIRE(s->n_m >= 1 && s->n_m <= MURAL_SUMMARY_MAX_KMERS, "summary_motif_rows: 1 .. %d motif lengths per call",
+                MURAL_SUMMARY_MAX_KMERS);
+  MURAL_REQUIRE(s->label_kind >= 0 && s->label_kind <= 2, "summary_motif_rows: label_kind is 0 (float32), 1 (int32) or 2 (int64)");
+  MURAL_REQUIRE(s->order_base >= 0 && s->order_base < (1ll << 58), "summary_motif_rows: order_base outside 0 .. 2^58 - 1");
+  for (int j = 0; j < s->n_m; ++j)
+    MURAL_REQUIRE(s->m[j] >= 3 && s->m[j] <= 15 && s->m[j] % 2 == 1 && s->table[j] && s->first[j],
+                  "summary_motif_rows: bad motif table %d (m odd, 3 <= m <= 15)", j);
+  if (s->n == 0) return MURAL_OK;
+  MURAL_REQUIRE(s->prob && s->start && s->end && s->label && s->status, "summary_motif_rows: NULL argument");
+  MURAL_REQUIRE(s->genome->packed2 && s->genome->nmask && s->genome->length >= 0, "summary_motif_rows: empty genome");
+  MURAL_REQUIRE(s->prob_stride >= s->n_class, "summary_motif_rows: prob_stride < n_class");
+  KmerArgs A{};
+  A.g = *s->genome;
+  A.prob = s->prob, A.start = s->start, A.end = s->end, A.label = s->label;
+  A.prob_stride = s->prob_stride, A.n = s->n, A.order_base = s->order_base;
+  A.label_kind = s->label_kind, A.n_class = s->n_class, A.indel = s->indel ? 1 : 0, A.n_k = s->n_m, A.by_row = s->order_by_row ? 1 : 0;
+  int64_t fold_threads = 0;
+  for (int j = 0; j < s->n_m; ++j) {
+    A.k[j] = s->m[j];
+    A.in_lds[j] = mural_summary_motif_in_lds(s->m[j], s->n_class);
+    A.table[j] = reinterpret_cast<u64*>(s->table[j]), A.first[j] = reinterpret_cast<u64*>(s->first[j]);
+    fold_threads = std::max(fold_threads, (int64_t)s->n_class << (2 * s->m[j]));
+  }
+  A.status = s->status;
+  static DynLdsOnce once;
+  if (const int rc = once.ensure(summary_motif_rows_kernel<float>, summary_motif_rows_kernel<double>)) return rc;
+  const dim3 fold_grid((unsigned)((fold_threads + SK_THREADS - 1) / SK_THREADS), (unsigned)s->n_m);
+  for (int64_t r0 = 0; r0 < s->n; r0 += SM_FOLD_ROWS) {
+    const int64_t r1 = std::min(r0 + SM_FOLD_ROWS, s->n);
+    const dim3 grid((unsigned)((r1 - r0 + SK_BLOCK_ROWS - 1) / SK_BLOCK_ROWS));
+    for (int j = 0; j < s->n_m; ++j) {
+      const size_t lds = A.in_lds[j] ? lds_bytes_of(A.k[j], A.n_class) : 0;
+      if (s->prob_f64)
+        hipLaunchKernelGGL(summary_motif_rows_kernel<double>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, A, j, r0, r1);
+      else
+        hipLaunchKernelGGL(summary_motif_rows_kernel<float>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, A, j, r0, r1);
       MURAL_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(summary_kmer_fold_kernel, fold_grid, dim3(SK_THREADS), 0, (hipStream_t)stream, A);

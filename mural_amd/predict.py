@@ -904,17 +904,14 @@ def _host_genome(genome):
     return np.asarray(packed).view(np.uint32), np.asarray(nmask).view(np.uint32), int(length)
 
 
-def kmer_keys_host(genome, start, end, strand, k, indel=False, mode=0):
-    """The numpy twin of ``mural_table_kmer_keys`` (csrc/kmer_key.h): (key_a, key_b) int64, -1 where the Python slice
-    chrom[start - k/2 (+1 indel) : end + k/2] is not k bases of A/C/G/T; key_a follows the strand mode (0 the rows' strand, 1 '+', 2 '-'),
-    in mode 3 key_a is the forward key and key_b its reverse complement (otherwise key_b is all -1)."""
-    packed, nmask, L = _host_genome(genome)
-    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
-    s0, s1 = start - k // 2 + (1 if indel else 0), end + k // 2
+def _window_keys_host(host, s0, s1, k):
+    """(fwd, rev) int64 of the Python slices chrom[s0:s1] (csrc/kmer_key.h: kmer_window_decode): -1 where a slice is not k bases of
+    A/C/G/T.  `host`: ``_host_genome``'s triple."""
+    packed, nmask, L = host
     lo = np.where(s0 < 0, np.maximum(L + s0, 0), np.minimum(s0, L))
     hi = np.where(s1 < 0, np.maximum(L + s1, 0), np.minimum(s1, L))
     ok = hi - lo == k
-    fwd, rev = np.zeros(len(start), np.int64), np.zeros(len(start), np.int64)
+    fwd, rev = np.zeros(len(s0), np.int64), np.zeros(len(s0), np.int64)
     base = np.where(ok, lo, 0)
     for j in range(k):
         q = np.minimum(base + j, max(L - 1, 0))
@@ -924,7 +921,15 @@ def kmer_keys_host(genome, start, end, strand, k, indel=False, mode=0):
         code = ((packed[q >> 4] >> (2 * (q & 15)).astype(np.uint32)) & 3).astype(np.int64)
         fwd = fwd * 4 + code
         rev += (3 - code) << (2 * j)
-    fwd, rev = np.where(ok, fwd, -1), np.where(ok, rev, -1)
+    return np.where(ok, fwd, -1), np.where(ok, rev, -1)
+
+
+def kmer_keys_host(genome, start, end, strand, k, indel=False, mode=0):
+    """The numpy twin of ``mural_table_kmer_keys`` (csrc/kmer_key.h): (key_a, key_b) int64, -1 where the Python slice
+    chrom[start - k/2 (+1 indel) : end + k/2] is not k bases of A/C/G/T; key_a follows the strand mode (0 the rows' strand, 1 '+', 2 '-'),
+    in mode 3 key_a is the forward key and key_b its reverse complement (otherwise key_b is all -1)."""
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    fwd, rev = _window_keys_host(_host_genome(genome), start - k // 2 + (1 if indel else 0), end + k // 2, k)
     none = np.full(len(start), -1, np.int64)
     if mode == 3:
         return fwd, rev
@@ -952,6 +957,17 @@ def _kmer_fold(table):
     return table
 
 
+def _kmer_row_checks(prob, start, label, nc):
+    """(hi, lo, integer labels, rows that count, status bits) of the rows of a k-mer or motif summary."""
+    label = np.asarray(label)
+    hi, lo, bad_p = kmer_quantise(np.asarray(prob)[:, :nc])
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= nc) | (lab != label)
+    bad_start, bad_prob = start < 0, bad_p.any(axis=1)
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    return hi, lo, lab, ~(bad_label | bad_start | bad_prob), status
+
+
 def summary_kmer_host(genome, prob, start, end, strand, label, n_class, kmers, indel=False, mode=0, order_base=0, into=None):
     """The numpy twin of ``mural_summary_kmer_rows`` -- and its specification -- for rows (any order) of one chromosome:
     ({k: (table uint64 [4^k][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^k])}, status).  `genome`: the
@@ -959,13 +975,8 @@ def summary_kmer_host(genome, prob, start, end, strand, label, n_class, kmers, i
     bits as on the device (1 a negative start, 2 a label outside 0 .. n_class - 1, 8 a probability that is NaN, negative or above 1);
     such rows are skipped in every table."""
     nc = int(n_class)
-    start, end, label = np.asarray(start, np.int64), np.asarray(end, np.int64), np.asarray(label)
-    hi, lo, bad_p = kmer_quantise(np.asarray(prob)[:, :nc])
-    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
-    bad_label = (lab < 0) | (lab >= nc) | (lab != label)
-    bad_start, bad_prob = start < 0, bad_p.any(axis=1)
-    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
-    ok = ~(bad_label | bad_start | bad_prob)
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    hi, lo, lab, ok, status = _kmer_row_checks(prob, start, label, nc)
     strand = np.zeros(len(start), np.uint8) if strand is None else TsvSink._strand_u8(strand)
     hi, lo, start, end, lab, strand = hi[ok], lo[ok], start[ok], end[ok], lab[ok], np.asarray(strand)[ok]
     if len(start) and int(start.max()) >= 1 << (_KMER_ORD_SHIFT - 1):
@@ -1007,7 +1018,7 @@ def kmer_table_from_sums(table, first, k, n_class):
     return [kmer_name(int(g), k) for g in order], out
 
 
-def _kmer_collapse(tables, firsts):
+def _kmer_collapse(tables, firsts, shift=_KMER_ORD_SHIFT):
     """({k: table}, {chromosome: {k: first}}) -> (names ascending, {k: (table, first)}): a k-mer's first appearance over the chromosomes
     in ascending name order -- the order of the written table -- with the chromosome's ordinal above the word."""
     names = sorted(firsts)
@@ -1016,24 +1027,24 @@ def _kmer_collapse(tables, firsts):
         first = np.full(table.shape[0], _KMER_NEVER, np.uint64)
         for ordinal, nm in enumerate(names):
             f = firsts[nm][k]
-            np.minimum(first, np.where(f != _KMER_NEVER, f | np.uint64(ordinal << _KMER_ORD_SHIFT), _KMER_NEVER), out=first)
+            np.minimum(first, np.where(f != _KMER_NEVER, f | np.uint64(ordinal << shift), _KMER_NEVER), out=first)
         out[k] = (table, first)
     return names, out
 
 
-def _kmer_merge(states):
+def _kmer_merge(states, shift=_KMER_ORD_SHIFT):
     """[(chromosome names ascending, {k: (table, first)})] of the ranks (or of a rank's devices and its host rows) -> one such pair:
     tables added, first-appearance words min-merged after the ordinals are reconciled by name (every list ascends, so renumbering it to
     the merged list keeps the order it was collapsed under)."""
     tables = {}
     names = sorted({nm for their_names, _ in states for nm in their_names})
-    low = np.uint64((1 << _KMER_ORD_SHIFT) - 1)
+    low = np.uint64((1 << shift) - 1)
     for their_names, their in states:
         remap = np.array([names.index(nm) for nm in their_names] + [0], np.uint64)
         for k, (table, first) in their.items():
             seen = first != _KMER_NEVER
             moved = first.copy()
-            moved[seen] = (remap[(first[seen] >> np.uint64(_KMER_ORD_SHIFT)).astype(np.int64)] << np.uint64(_KMER_ORD_SHIFT)) | (first[seen] & low)
+            moved[seen] = (remap[(first[seen] >> np.uint64(shift)).astype(np.int64)] << np.uint64(shift)) | (first[seen] & low)
             if k not in tables:
                 tables[k] = (table.copy(), moved)
             else:
@@ -1041,6 +1052,71 @@ def _kmer_merge(states):
                 np.minimum(tables[k][1], moved, out=tables[k][1])
                 _kmer_fold(tables[k][0])
     return names, tables
+
+
+# ---- motif rate tables (csrc/summary_kmer.hip: mural_summary_motif_rows): the k-mer cells under the key rule of `evaluate --motif_only` ----
+_MOTIF_POS_SHIFT = 5               # first-appearance word: (order_base + pos) << 5 | window i << 1 | orientation
+_MOTIF_ORD_SHIFT = 44              # a chromosome's ordinal sits above any such word of a start below 2^39
+_MOTIF_FOLD_ROWS = 1 << 18         # rows between two folds: a row adds up to m <= 15 times to one cell
+
+
+def summary_motif_host(genome, prob, start, end, label, n_class, motifs, indel=False, order_base=0, into=None, order_by_row=False):
+    """The numpy twin of ``mural_summary_motif_rows`` -- and its specification -- for rows (any order) of one chromosome:
+    ({m: (table uint64 [4^m][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^m])}, status).  A row adds to every
+    window of m bases that holds its site, on the reference strand: the Python slices chrom[start - i : end + m-1 - i], i = 0 .. m-1, of
+    an SNV row, chrom[start - i + 1 : end + m - i], i = 1 .. m-1, of an INDEL row, those that are m bases of A/C/G/T.  A motif and its
+    reverse complement share the cell of the smaller key; first = min of (order_base + pos) << 5 | i << 1 | o over the windows, pos the
+    row's start (its index among the rows given with `order_by_row`), o = 1 where the window's own key is the larger of the two.
+    `genome`, `into` and the status bits as ``summary_kmer_host``."""
+    from .tables import check_motif_length
+    nc = int(n_class)
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    hi, lo, lab, ok, status = _kmer_row_checks(prob, start, label, nc)
+    pos = np.arange(len(start), dtype=np.int64) if order_by_row else start
+    hi, lo, start, end, lab, pos = hi[ok], lo[ok], start[ok], end[ok], lab[ok], pos[ok]
+    if len(start) and int(pos.max()) + int(order_base) >= 1 << 58:
+        raise ValueError("motif summary: a row order at or above 2^58")
+    host = _host_genome(genome)
+    out = {} if into is None else into
+    cls = np.arange(nc)
+    for m in motifs:
+        m = check_motif_length(m, device=True)
+        table, first = out.get(m) or (np.zeros((4 ** m, 3, nc), np.uint64), np.full(4 ** m, _KMER_NEVER, np.uint64))
+        for r0 in range(0, len(start), _MOTIF_FOLD_ROWS):
+            r = slice(r0, r0 + _MOTIF_FOLD_ROWS)
+            word = (np.uint64(order_base) + pos[r].astype(np.uint64)) << np.uint64(_MOTIF_POS_SHIFT)
+            for w in range(m - (1 if indel else 0)):           # the reference's i = w + indel
+                fwd, rev = _window_keys_host(host, start[r] - w, end[r] + (m - 1 - w), m)
+                live = fwd >= 0
+                kk = np.minimum(fwd, rev)[live]
+                np.add.at(table[:, 0], (kk, lab[r][live]), np.uint64(1))
+                np.add.at(table[:, 1], (kk[:, None], cls[None, :]), hi[r][live])
+                np.add.at(table[:, 2], (kk[:, None], cls[None, :]), lo[r][live])
+                np.minimum.at(first, kk, word[live] | np.uint64((w + (1 if indel else 0)) << 1) | (fwd > rev)[live].astype(np.uint64))
+            _kmer_fold(table)
+        out[m] = (table, first)
+    return out, status
+
+
+def motif_table_from_sums(table, first, m, n_class):
+    """(motif names, table [entries][1 + 2 n_class] of windows / per-class counts / per-class probability sums) -- ``tables.motif_table``'s
+    pair -- from the merged integer tables: the keys with a window, by first appearance; an entry is named after the orientation of its
+    first window (the lowest bit of its word: 1 the reverse complement of the smaller key).  Sums as ``kmer_table_from_sums``."""
+    from .tables import kmer_name
+    names, out = kmer_table_from_sums(table, first, m, n_class)
+    live = np.nonzero(table[:, 0].sum(axis=1) > 0)[0]
+    order = live[np.argsort(first[live], kind="stable")]
+    flip = (first[order] & np.uint64(1)).astype(bool)
+    top = 4 ** m - 1
+    return [kmer_name(top - _revdigits(int(g), m) if f else int(g), m) for g, f in zip(order, flip)], out
+
+
+def _revdigits(key, m):
+    """The base-4 digits of a key in reverse order (4^m - 1 - that is the key of the reverse complement)."""
+    out = 0
+    for _ in range(m):
+        out, key = out * 4 + (key & 3), key >> 2
+    return out
 
 
 def _merge_window_table(have, bin0, table):
@@ -1079,12 +1155,18 @@ class SummarySink:
     packed genome (``HipShardForward.genome``; a sequence will do for host shards); `kmer_strand`: None for SNV rows (each row's own
     strand), 'pos' / 'neg' / 'both' for INDEL rows (``tables.strand_mode``).  A device part is reduced when it arrives, into accumulators
     that live with the sink and are read back once, at close(); ranks exchange the integer tables in the same collective.  close() then
-    also writes ``{out_prefix}.{k}-mer.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_kmer_outputs``), and result() has "kmers"."""
+    also writes ``{out_prefix}.{k}-mer.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_kmer_outputs``), and result() has "kmers".
+
+    `motifs`: motif lengths (odd, 3 .. ``tables.MAX_MOTIF``) whose rate tables -- ``tables.motif_table``'s, what ``evaluate --motif_only``
+    reads from the written table -- are reduced the same way (``mural_summary_motif_rows``: every window of m bases that holds a row's
+    site, on the reference strand, a motif and its reverse complement in one entry), alone or beside `kmers` and
+    `windows`; `motif_indel`: the rows are INDEL rows (m - 1 windows each).  They need `genome` as well.  close() writes
+    ``{out_prefix}.{m}-motif.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_motif_outputs``), and result() has "motifs"."""
 
     takes_aligned_blocks = True
 
     def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
-                 group=None, parts=False, kmers=(), genome=None, kmer_strand=None):
+                 group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         self.windows = tuple(int(w) for w in windows)
         if any(w <= 0 for w in self.windows) or len(set(self.windows)) != len(self.windows):
@@ -1120,6 +1202,14 @@ class SummarySink:
         # share k-mers, and the order between chromosomes -- by name, as in the written table -- is only known when all have arrived)
         self._kmer_host = ({}, {})     # ({k: table}, {chromosome: {k: first}}) of the host shards
         self._kmer_dev = {}            # device -> ({k: table}, {chromosome: {k: first}}, status)
+        from .tables import check_motif_length
+        self.motifs = tuple(check_motif_length(m) for m in motifs)
+        if len(set(self.motifs)) != len(self.motifs):
+            raise ValueError(f"motif lengths must be distinct (got {self.motifs})")
+        if self.motifs and genome is None:
+            raise ValueError("SummarySink(motifs=...) needs genome=: a callable chromosome name -> packed genome")
+        self._motif_indel = bool(motif_indel)
+        self._motif_host, self._motif_dev = ({}, {}), {}      # as the k-mer accumulators
 
     # -- one part ---------------------------------------------------------------------------------------------------------
     def _take(self, name, tables, total, n_sites, status):
@@ -1151,6 +1241,14 @@ class SummarySink:
             _, status = summary_kmer_host(self._genome(name), cols[3], cols[0], cols[1], strand, cols[2], k, self.kmers, self._kmer_indel,
                                           self._kmer_mode, into={kk: (tabs[kk], mine[kk]) for kk in self.kmers})
             self._status |= status
+        if self.motifs:
+            tabs, firsts = self._motif_host
+            for m in self.motifs:
+                tabs.setdefault(m, np.zeros((4 ** m, 3, k), np.uint64))
+            mine = firsts.setdefault(name, {m: np.full(4 ** m, _KMER_NEVER, np.uint64) for m in self.motifs})
+            _, status = summary_motif_host(self._genome(name), cols[3], cols[0], cols[1], cols[2], k, self.motifs, self._motif_indel,
+                                           into={m: (tabs[m], mine[m]) for m in self.motifs})
+            self._status |= status
 
     def _kmer_device(self, name, dev, prob, start, end, strand, label, k):
         """Enqueue the k-mer reduction of a part behind its forward: the part's chromosome is the resident one now."""
@@ -1179,6 +1277,35 @@ class SummarySink:
                 s.k[j], s.table[j], s.first[j] = kk, acc[0][kk].data_ptr(), first[kk].data_ptr()
             s.order_base, s.status = 0, acc[2].data_ptr()
             _lib.check(lib.mural_summary_kmer_rows(C.byref(s), stream))
+        return genome
+
+    def _motif_device(self, name, dev, prob, start, end, label, k):
+        """Enqueue the motif reduction of a part behind its forward, as ``_kmer_device``."""
+        lib = _lib.lib()
+        genome = self._genome(name)
+        if genome.length >= 1 << (_KMER_ORD_SHIFT - 1):
+            raise ValueError(f"motif summary: chromosome {name} has 2^39 bases or more")
+        acc = self._motif_dev.get(dev)
+        if acc is None:
+            acc = self._motif_dev[dev] = ({m: torch.zeros(4 ** m * 3 * k, dtype=torch.int64, device=dev) for m in self.motifs}, {},
+                                          torch.zeros(1, dtype=torch.int32, device=dev))
+        first = acc[1].get(name)
+        if first is None:
+            first = acc[1][name] = {m: torch.full((4 ** m,), -1, dtype=torch.int64, device=dev) for m in self.motifs}
+        g = genome.as_struct(dev)
+        stream = _lib.current_stream_ptr(dev)
+        for at in range(0, len(self.motifs), 4):         # MURAL_SUMMARY_MAX_KMERS lengths per call
+            group = self.motifs[at:at + 4]
+            s = _lib.MuralSummaryMotifRows()
+            s.genome = C.pointer(g)
+            s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0)
+            s.start, s.end, s.label = start.data_ptr(), end.data_ptr(), label.data_ptr()
+            s.label_kind = {torch.float32: 0, torch.int32: 1, torch.int64: 2}[label.dtype]
+            s.n, s.n_class, s.n_m, s.indel, s.order_by_row = start.shape[0], k, len(group), int(self._motif_indel), 0
+            for j, m in enumerate(group):
+                s.m[j], s.table[j], s.first[j] = m, acc[0][m].data_ptr(), first[m].data_ptr()
+            s.order_base, s.status = 0, acc[2].data_ptr()
+            _lib.check(lib.mural_summary_motif_rows(C.byref(s), stream))
         return genome
 
     def _stage_device(self, name, shard, k):
@@ -1210,6 +1337,8 @@ class SummarySink:
             # the k-mer tables have a fixed size: reduced now, while this part's chromosome is the resident one; the staged part keeps
             # the packed genome (and the columns) alive all the same -- the window tables are reduced one part late
             genome = self._kmer_device(name, dev, prob, start, end, strand, label, k) if self.kmers else None
+            if self.motifs:
+                genome = self._motif_device(name, dev, prob, start, end, label, k)
             ends = torch.empty(2, dtype=torch.int64).pin_memory()
             ends.copy_(torch.stack([start[0], start[-1]]), non_blocking=True)
             ev = torch.cuda.Event()
@@ -1308,32 +1437,36 @@ class SummarySink:
     def _merged(self, states):
         """[(tables, prob_sum, n_sites, status, n_class, k-mer state)] of the ranks, added in rank order."""
         tables, prob_sum, n_sites, status, k = {}, 0.0, 0, 0, None
-        for t, s, c, st, kk, _ in states:
+        for t, s, c, st, kk, _, _ in states:
             for name, per_w in t.items():
                 mine = tables.setdefault(name, {})
                 for W, (bin0, tab) in per_w.items():
                     mine[W] = _merge_window_table(mine.get(W), bin0, tab)
             prob_sum, n_sites, status = prob_sum + s, n_sites + c, status | st
             k = kk if k is None else k
-        return tables, prob_sum, n_sites, status, k, _kmer_merge([st[5] for st in states]) if self.kmers else None
+        return (tables, prob_sum, n_sites, status, k, _kmer_merge([st[5] for st in states]) if self.kmers else None,
+                _kmer_merge([st[6] for st in states], _MOTIF_ORD_SHIFT) if self.motifs else None)
+
+    def _read_back(self, host, devices, shift):
+        """The one read-back of the device accumulators of the k-mer (or motif) tables, merged with the host rows'."""
+        mine = [host]
+        for tabs, firsts, dev_status in devices.values():
+            self._status |= int(dev_status.item())
+            mine.append(({kk: t.cpu().numpy().view(np.uint64).reshape(4 ** kk, 3, -1) for kk, t in tabs.items()},
+                         {nm: {kk: f.cpu().numpy().view(np.uint64) for kk, f in per_k.items()} for nm, per_k in firsts.items()}))
+        return _kmer_merge([_kmer_collapse(tabs, firsts, shift) for tabs, firsts in mine if tabs], shift)
 
     def close(self):
         self._launch_pending()
         self._harvest()
-        kmer_state = None
-        if self.kmers:                 # the one read-back of the device accumulators
-            mine = [self._kmer_host]
-            for tabs, firsts, dev_status in self._kmer_dev.values():
-                self._status |= int(dev_status.item())
-                mine.append(({kk: t.cpu().numpy().view(np.uint64).reshape(4 ** kk, 3, -1) for kk, t in tabs.items()},
-                             {nm: {kk: f.cpu().numpy().view(np.uint64) for kk, f in per_k.items()} for nm, per_k in firsts.items()}))
-            kmer_state = _kmer_merge([_kmer_collapse(tabs, firsts) for tabs, firsts in mine if tabs])
-        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class, kmer_state)
+        kmer_state = self._read_back(self._kmer_host, self._kmer_dev, _KMER_ORD_SHIFT) if self.kmers else None
+        motif_state = self._read_back(self._motif_host, self._motif_dev, _MOTIF_ORD_SHIFT) if self.motifs else None
+        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class, kmer_state, motif_state)
         if self.world > 1:
             every = [None] * self.world
             dist.all_gather_object(every, state, group=self.group)      # the one collective: tables, not rows
             state = self._merged(every)
-        tables, prob_sum, n_sites, status, k, kmer_state = state
+        tables, prob_sum, n_sites, status, k, kmer_state, motif_state = state
         for bit, what in _SUMMARY_STATUS:
             if status & bit:
                 raise ValueError(f"summary: {what}")
@@ -1352,6 +1485,11 @@ class SummarySink:
             self._kmer_sums = ktables
             self._result["kmers"] = {kk: (kmer_table_from_sums(*ktables[kk], kk, k) if kk in ktables else ([], np.zeros((0, 1 + 2 * (k or 0)))))
                                      for kk in self.kmers}
+        if self.motifs:
+            mtables = motif_state[1]
+            self._motif_sums = mtables
+            self._result["motifs"] = {m: (motif_table_from_sums(*mtables[m], m, k) if m in mtables else ([], np.zeros((0, 1 + 2 * (k or 0)))))
+                                      for m in self.motifs}
         if self.out_prefix is not None and self.rank == 0 and k is not None:
             from .tables import regional_output_names, write_regional_outputs
             for W in self.windows:
@@ -1361,11 +1499,16 @@ class SummarySink:
             for kk in self.kmers:
                 self._written += list(kmer_output_names(self.out_prefix, kk))
                 write_kmer_outputs(*self._result["kmers"][kk], k, kk, self.out_prefix)
+            from .tables import motif_output_names, write_motif_outputs
+            for m in self.motifs:
+                self._written += list(motif_output_names(self.out_prefix, m))
+                write_motif_outputs(*self._result["motifs"][m], k, m, self.out_prefix)
 
     def abort(self):
         """Drop what was reduced and remove any file close() began: the caller's run failed."""
         self._pending, self._inflight, self._tables, self._result = None, [], {}, None
         self._kmer_host, self._kmer_dev = ({}, {}), {}
+        self._motif_host, self._motif_dev = ({}, {}), {}
         for path in self._written:
             if os.path.exists(path):
                 os.unlink(path)
@@ -1374,7 +1517,8 @@ class SummarySink:
     def result(self):
         """{"prob_sum", "n_sites", "windows": {W: ([(chrom, window_end)], table [windows][1 + 2 n_class])}} after close(): the pair of
         ``tables.prob_sum_file`` and, per window size, of ``tables.regional_table`` (chromosomes by name, windows ascending); with `kmers`
-        also "kmers": {k: (names, table [k-mers][1 + 2 n_class])}, the pair of ``tables.kmer_table``.  ``kmer_sums()`` has the integers."""
+        also "kmers": {k: (names, table [k-mers][1 + 2 n_class])}, the pair of ``tables.kmer_table``, and with `motifs` "motifs": {m: the
+        pair of ``tables.motif_table``}.  ``kmer_sums()`` and ``motif_sums()`` have the integers."""
         if self._result is None:
             raise RuntimeError("SummarySink.result() is valid after close()")
         return self._result
@@ -1384,6 +1528,12 @@ class SummarySink:
         sums behind result()["kmers"] (``summary_kmer_host``'s layout)."""
         self.result()
         return self._kmer_sums
+
+    def motif_sums(self):
+        """{m: (table uint64 [4^m][3][n_class], first uint64 [4^m])} after close(): the exact sums behind result()["motifs"]
+        (``summary_motif_host``'s layout, the chromosome's ordinal by name above each first-appearance word)."""
+        self.result()
+        return self._motif_sums
 
     def scaling_factor(self, genomewide_mu, m_proportion, g_proportion=1.0):
         """``tables.calc_mu_scaling_factor``'s factor for the summarised rows, with the lines it prints."""

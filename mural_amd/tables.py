@@ -26,6 +26,9 @@ from . import _lib
 
 DEFAULT_CHUNK_BYTES = 64 << 20
 MAX_KMER = 10
+# the motif tables are indexed by all 4^m keys, 3 n_class cells of 8 bytes each: 50 MB at m = 9 and 805 MB at m = 11 with 8 classes (half
+# of that with 4), once on the device and once on the host when it is read back; m = 13 would take 12.9 GB
+MAX_MOTIF = 11
 _NAME_STRIDE = 256
 _GZ_THREADS = 16
 _GZ_BLOCK = 4 << 20
@@ -76,6 +79,22 @@ def check_kmer_length(k):
     if k > MAX_KMER:
         raise ValueError(f"--kmer_length {k} is larger than {MAX_KMER}: the k-mer table has 4^k groups")
     return k
+
+
+def motif_output_names(out_prefix, motif_length):
+    return f"{out_prefix}.{motif_length}-motif.mut_rates.tsv", f"{out_prefix}.{motif_length}-motif.corr.txt"
+
+
+def check_motif_length(m, device=False):
+    """validate_motif_length of calc_motif_corr.py:83-87 (its message), and the upper bound of the tables here: ``MAX_MOTIF`` (15, the
+    largest key of 32 bits, for a direct call of the device entry with `device`)."""
+    m = int(m)
+    if m <= 1 or m % 2 != 1:
+        raise ValueError("--motif_length must be a positive odd integer >1")
+    top = 15 if device else MAX_MOTIF
+    if m > top:
+        raise ValueError(f"--motif_length {m} is larger than {top}: the motif table has 4^m entries")
+    return m
 
 
 _STRAND_MODES = {"+": 1, "pos": 1, "-": 2, "neg": 2, "both": 3}
@@ -426,19 +445,87 @@ def run_kmer_corr_calc(args, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
 def write_kmer_outputs(names, table, n_class, kmer_length, out_prefix):
     """The two files of calc_kmer_corr.py:252-270 from a k-mer table (``kmer_table``'s pair, or the one a ``predict.SummarySink``
     reduced in flight): per k-mer observed / predicted rates and counts, Pearson r per class.  Returns [(class, (r, p))]."""
+    return _write_type_outputs(names, table, n_class, kmer_output_names(out_prefix, kmer_length), f"{kmer_length}-mer")
+
+
+def _write_type_outputs(names, table, n_class, paths, label):
     obs, pred, cnt, tot = _rates(table, n_class)
     cls = range(1, n_class)
     header = (["type"] + [f"avg_obs_rate{i}" for i in cls] + [f"avg_pred_rate{i}" for i in cls] + [f"number_of_mut{i}" for i in cls]
               + ["number_of_all"])
     rows = [[nm] + [_float_text(v) for v in obs[j]] + [_float_text(v) for v in pred[j]] + [str(int(v)) for v in cnt[j]] + [str(int(tot[j]))]
             for j, nm in enumerate(names)]
-    rates_path, corr_path = kmer_output_names(out_prefix, kmer_length)
+    rates_path, corr_path = paths
     corrs = [(c, pearson(obs[:, c - 1], pred[:, c - 1])) for c in cls]
     with open(rates_path, "w") as fh:
         fh.write(_rates_text(header, rows))
     with open(corr_path, "w") as fh:
-        fh.write(_corr_text(f"{kmer_length}-mer", corrs))
+        fh.write(_corr_text(label, corrs))
     return corrs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# evaluate: motif
+# ------------------------------------------------------------------------------------------------------------------
+def motif_table(pred_file, ref_genome, motif_length, n_class, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(motif names, table [entries][1 + 2 n_class] of windows / per-class counts / per-class prob sums) in the reference's dict order
+    (calc_motif_corr.py:191-254): every window of motif_length bases that holds a row's site, on the reference strand, a motif and its
+    reverse complement in one entry named after the orientation seen first.  The chunks of the table go through the entry point of the
+    in-flight reduction (``mural_summary_motif_rows``; ``predict.SummarySink(motifs=...)``), the rows' order being their line numbers."""
+    from .data.ingest import read_fasta, scan_fasta
+    from .predict import motif_table_from_sums
+    m = check_motif_length(motif_length)
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
+    if not 1 <= int(n_class) <= 8:
+        raise ValueError("the motif tables take 1 .. 8 classes")
+    lib = _lib.lib()
+    fasta_names = {r.name for r in scan_fasta(ref_genome)}
+    genomes = {}
+    with TableReader(pred_file, n_class, chunk_bytes) as rd:
+        dev = rd.device
+        table = torch.zeros(4 ** m * 3 * n_class, dtype=torch.int64, device=dev)
+        first = torch.full((4 ** m,), -1, dtype=torch.int64, device=dev)      # (all ones = the largest unsigned value)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                if name not in genomes:
+                    if name not in fasta_names:
+                        raise ValueError(f"Chromosome {name} not found in {ref_genome} (prediction table line {c.row0 + rows[r] + 2})")
+                    genomes[name] = read_fasta(ref_genome, dev, names={name})[name]
+                g = genomes[name].as_struct()
+                a, b = rows[r], rows[r + 1]
+                s = _lib.MuralSummaryMotifRows()
+                s.genome = C.pointer(g)
+                s.prob, s.prob_f64, s.prob_stride = c.prob + 8 * n_class * a, 1, n_class
+                s.start, s.end, s.label, s.label_kind = c.start + 8 * a, c.end + 8 * a, c.mut_type + 4 * a, 1
+                s.n, s.n_class, s.n_m, s.indel, s.order_by_row = b - a, n_class, 1, int(model_type == "indel"), 1
+                s.m[0], s.table[0], s.first[0] = m, table.data_ptr(), first.data_ptr()
+                s.order_base, s.status = c.row0 + a, status.data_ptr()
+                _lib.check(lib.mural_summary_motif_rows(C.byref(s), _lib.current_stream_ptr(dev)))
+        from .predict import _SUMMARY_STATUS
+        bits = int(status.item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table, first = table.cpu().numpy().view(np.uint64).reshape(4 ** m, 3, n_class), first.cpu().numpy().view(np.uint64)
+    return motif_table_from_sums(table, first, m, n_class)
+
+
+def run_motif_corr_calc(args, model_type, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """calc_motif_corr.py:191-261 (`evaluate --motif_only`): per motif observed / predicted rates and their Pearson r per class; writes
+    {out_prefix}.{m}-motif.mut_rates.tsv and .corr.txt.  As in the reference no strand is read: ``args.strand`` is ignored."""
+    assert args.ref_genome is not None, "--ref_genome is required for motif correlation calculation"
+    names, table = motif_table(os.fspath(args.pred_file), os.fspath(args.ref_genome), args.motif_length, args.n_class, model_type, chunk_bytes)
+    return write_motif_outputs(names, table, args.n_class, args.motif_length, args.out_prefix)
+
+
+def write_motif_outputs(names, table, n_class, motif_length, out_prefix):
+    """The two files of calc_motif_corr.py:256-261 from a motif table (``motif_table``'s pair, or the one a ``predict.SummarySink``
+    reduced in flight); the correlation lines keep the reference's label ``{m}-moitf``.  Returns [(class, (r, p))]."""
+    return _write_type_outputs(names, table, n_class, motif_output_names(out_prefix, motif_length), f"{motif_length}-moitf")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -558,4 +645,4 @@ def print_scaling_factor(genomewide_mu, n_sites, g_proportion, m_proportion, pro
 apply_scaling = apply_scaling_file
 
 __all__ = ["TableReader", "apply_scaling_file", "scaling_files", "calc_mu_scaling_factor", "run_kmer_corr_calc", "run_regional_corr_calc", "write_regional_outputs", "write_kmer_outputs",
-           "prob_sum_file", "read_regions", "kmer_table", "regional_table", "check_header", "read_header", "DEFAULT_CHUNK_BYTES", "MAX_KMER"]
+           "prob_sum_file", "read_regions", "kmer_table", "regional_table", "motif_table", "run_motif_corr_calc", "write_motif_outputs", "MAX_MOTIF", "check_header", "read_header", "DEFAULT_CHUNK_BYTES", "MAX_KMER"]

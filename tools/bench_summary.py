@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Six legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Eight legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -10,7 +10,10 @@ alternating, --repeats timed runs each after one warm-up run each:
   d  tools     the route to b's numbers without this sink: leg a's table, then prob_sum_file + regional_table (100 kb, 1 kb) on it
   e  kmers       leg b with kmers=(3, 5, 7) as well: the k-mer tables reduced from the resident chromosome
   f  kmer_tools  the route to e's k-mer tables without the sink: leg a's table, then tables.kmer_table x 3 on it (the FASTA packed again)
-Prints one JSON line; the summary of leg b must agree with leg d's, and leg e's k-mer tables with leg f's, within the table's four digits."""
+  g  motifs      leg b with motifs=(3, 5, 7) as well: the motif tables reduced from the resident chromosome
+  h  motif_tools the route to g's motif tables without the sink: leg a's table, then tables.motif_table x 3 on it
+Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's and leg g's motif tables with leg
+h's, within the table's four digits (names, order and counts exactly)."""
 import json
 import os
 import shutil
@@ -31,7 +34,8 @@ from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, pr
 
 WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
-LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools")
+MOTIFS = (3, 5, 7)
+LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools")
 
 
 def main(argv):
@@ -61,8 +65,11 @@ def main(argv):
             summary = SummarySink(windows=WINDOWS) if leg in ("summary", "tee") else None
             if leg == "kmers":
                 summary = SummarySink(windows=WINDOWS, kmers=KMERS, genome=fwd.genome)
+            if leg == "motifs":
+                summary = SummarySink(windows=WINDOWS, motifs=MOTIFS, genome=fwd.genome)
             sink = {"table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
-                    "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out)}[leg]()
+                    "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
+                    "motif_tools": lambda: TsvSink(out)}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split)
             torch.cuda.synchronize()
             extra["predict"] = time.perf_counter() - t0
@@ -82,6 +89,12 @@ def main(argv):
                     t1 = time.perf_counter()
                     kept["kmer_tools"][k] = tables.kmer_table(out, fa, k, n_class, "snv")
                     extra["kmer_table_%d" % k] = time.perf_counter() - t1
+            if leg == "motif_tools":
+                kept["motif_tools"] = {}
+                for m in MOTIFS:
+                    t1 = time.perf_counter()
+                    kept["motif_tools"][m] = tables.motif_table(out, fa, m, n_class, "snv")
+                    extra["motif_table_%d" % m] = time.perf_counter() - t1
             dt = time.perf_counter() - t0
             assert n == rows, (leg, n, rows)
             if summary is not None:
@@ -108,6 +121,10 @@ def main(argv):
         for kk in KMERS:
             (na, ta), (nd, td) = kept["kmers"]["kmers"][kk], kept["kmer_tools"][kk]
             agree = agree and na == nd and bool((ta[:, :k] == td[:, :k]).all()) and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
+    if {"motifs", "motif_tools"} <= set(legs):
+        for m in MOTIFS:
+            (na, ta), (nd, td) = kept["motifs"]["motifs"][m], kept["motif_tools"][m]
+            agree = agree and na == nd and bool((ta[:, :k] == td[:, :k]).all()) and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
     rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in legs}
     med = {leg: rate[leg]["median"] for leg in legs}
     sec = {leg: statistics.median(seconds[leg]) for leg in legs}
@@ -117,6 +134,8 @@ def main(argv):
            "summaries_agree": bool(agree), "rows_per_s": rate, "summary_over_table": ratio("summary", "table", med),
            "tee_over_table": ratio("tee", "table", med), "tools_over_summary_seconds": ratio("tools", "summary", sec),
            "kmers_over_summary": ratio("kmers", "summary", med), "kmer_tools_over_kmers_seconds": ratio("kmer_tools", "kmers", sec),
+           "motifs": list(MOTIFS), "motifs_over_summary": ratio("motifs", "summary", med),
+           "motif_tools_over_motifs_seconds": ratio("motif_tools", "motifs", sec),
            "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}
     print(json.dumps(res))
     if not agree:

@@ -12,6 +12,9 @@ read back from the table, taken from the probabilities before they are rounded):
   --summary PREFIX  --kmer_length K [--kmer_length K ..]   PREFIX.{K}-mer.mut_rates.tsv and .corr.txt per k-mer length: the files of
                                                              `evaluate --kmer_only`, the flanks read from the resident chromosome
                                                              (with either or both of --window_size / --kmer_length)
+  --summary PREFIX  --motif_length M [M ..]                PREFIX.{M}-motif.mut_rates.tsv and .corr.txt per motif length (odd, 3 and
+                                                             more): the files of `evaluate --motif_only` -- every window of M bases that
+                                                             holds a site, a motif and its reverse complement in one entry
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -25,7 +28,7 @@ from mural_amd.calibration import load_dirichlet_weights  # noqa: E402
 from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
-_SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
+_SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
                     "--scale_factor")
 _VALUE_OPTIONS = ("--regions", "--focal", "--context") + _SUMMARY_OPTIONS
 
@@ -33,15 +36,21 @@ _VALUE_OPTIONS = ("--regions", "--focal", "--context") + _SUMMARY_OPTIONS
 def _split(argv):
     """(flags, positional arguments, {value option: [values]})"""
     flags, args, values = set(), [], {}
-    it = iter(argv)
-    for a in it:
+    argv = list(argv)
+    it = iter(range(len(argv)))
+    for at in it:
+        a = argv[at]
         name, eq, val = a.partition("=")
         if name in _VALUE_OPTIONS:
             if not eq:
-                val = next(it, None)
-                if val is None:
+                at = next(it, None)
+                if at is None:
                     raise SystemExit(f"{name} needs a value\n\n{__doc__}")
+                val = argv[at]
             values.setdefault(name, []).append(val)
+            while name == "--motif_length" and at + 1 < len(argv) and argv[at + 1].lstrip("-").isdigit():      # M [M ..]
+                at = next(it)
+                values[name].append(argv[at])
         elif a.startswith("--"):
             flags.add(a)
         else:
@@ -86,13 +95,23 @@ def _summary_options(flags, values, model_type="snv"):
             "benchmark_regions": one("--benchmark_regions", str), "genomewide_mu": one("--genomewide_mu", float),
             "m_proportion": one("--m_proportion", float), "g_proportion": one("--g_proportion", float),
             "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags,
-            "kmers": tuple(int(k) for k in values.get("--kmer_length", [])), "strand": one("--strand", str)}
+            "kmers": tuple(int(k) for k in values.get("--kmer_length", [])), "strand": one("--strand", str),
+            "motifs": tuple(int(m) for m in values.get("--motif_length", []))}
     if opts["windows"] and opts["summary"] is None:
         raise SystemExit("--window_size needs --summary PREFIX: the prefix of the files it writes")
     if opts["kmers"] and opts["summary"] is None:
         raise SystemExit("--kmer_length needs --summary PREFIX: the prefix of the files it writes")
-    if opts["summary"] is not None and not opts["windows"] and not opts["kmers"]:
-        raise SystemExit("--summary PREFIX needs a --window_size or a --kmer_length")
+    if opts["motifs"] and opts["summary"] is None:
+        raise SystemExit("--motif_length needs --summary PREFIX: the prefix of the files it writes")
+    if opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"]:
+        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length or a --motif_length")
+    if opts["motifs"]:
+        from mural_amd.tables import check_motif_length
+        try:
+            for m in opts["motifs"]:
+                check_motif_length(m)
+        except ValueError as e:
+            raise SystemExit(f"--motif_length: {e}") from None
     if opts["kmers"]:
         from mural_amd.tables import check_kmer_length, strand_mode
         try:
@@ -136,7 +155,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
         sinks.append(TsvSink(out, **sink_chain))
     if opts["wants_summary"]:
         summary = SummarySink(opts["summary"], opts["windows"], opts["benchmark_regions"], kmers=opts["kmers"], genome=forward.genome,
-                              kmer_strand=opts["strand"] if model_type == "indel" else None, **sink_chain)
+                              kmer_strand=opts["strand"] if model_type == "indel" else None, motifs=opts["motifs"],
+                              motif_indel=model_type == "indel", **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
