@@ -97,6 +97,19 @@ int mural_sites_count(const MuralGenome* g, int64_t lo, int64_t hi, int32_t foca
 int mural_sites_emit(const MuralGenome* g, int64_t lo, int64_t hi, int32_t focal, int32_t context, const int64_t* tile_counts,
                      int64_t first, int64_t n, int64_t* pos, uint8_t* strand, void* stream);
 
+/* Observed mutations joined to enumerated sites (csrc/sites.hip): the label column of a regions run.  pos / strand: what
+ * mural_sites_emit wrote (dev, n entries, pos ascending).  mut_start / mut_strand / mut_label: ONE chromosome's list of observed
+ * mutations (dev, m entries, mut_start STRICTLY ascending; strand 0 '+', 1 '-'; label = the class, mut_type).  One binary search per
+ * site: label[i] = mut_label[j] where mut_start[j] == pos[i], 0 where no entry matches (dev float [n]).
+ *   stats: dev int64 [2], set to {0, INT64_MAX} by the caller before the first call; it accumulates over calls:
+ *     stats[0] += the rows that found an entry (an entry whose label is 0 counts);
+ *     stats[1]  = min(stats[1], j) over matched entries j with mut_strand[j] != strand[i], only when check_strand != 0 (the SNV
+ *                 selections; focal ANY puts every site on '+' and passes 0).
+ *   Integer atomics only: both words depend on the set of rows alone, however they are split into calls, parts or ranks.
+ * n == 0 launches nothing; m == 0 writes zeros and reads no mut_* pointer (they may be NULL).  64-bit indices throughout.          */
+int mural_sites_label(const int64_t* pos, const uint8_t* strand, int64_t n, const int64_t* mut_start, const uint8_t* mut_strand,
+                      const float* mut_label, int64_t m, int32_t check_strand, float* label, int64_t* stats, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SNV model family (Network0 / Network1 / Network2, MuRaL/model/model_snv.py:19-525), eval mode.
  * Raw parameters are handed over as HOST pointers in the reference's state_dict naming; the library

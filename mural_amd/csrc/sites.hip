@@ -12,6 +12,9 @@
 //          [first, first + n) of the enumeration.  Ascending positions, no atomics: the result does not depend on scheduling.
 // A base is a site only when its nmask bit is clear; the packer sets that bit for N and for every IUPAC code of the side table, so
 // the table itself is not consulted.
+//
+// Labels: the regions route has no BED row to take a site's observed mutation from; mural_sites_label joins the enumerated sites to one
+// chromosome's list of observed mutations (start strictly ascending, a few MB: it stays in the caches) with one binary search per site.
 #include "common.h"
 
 namespace mural {
@@ -138,6 +141,41 @@ __global__ __launch_bounds__(ST_THREADS) void sites_emit_kernel(MuralGenome g, i
   }
 }
 
+constexpr int64_t SL_MAX_BLOCKS = 1 << 12;      // 2^20 lanes fill the device twice over; longer calls stride
+
+// label[i] = mut_label[j] where mut_start[j] == pos[i], else 0.  A thread walks sites i, i + grid, ..: neighbouring lanes search for
+// neighbouring positions and take the same path through the list.  stats[0] += matched rows (one integer atomic per block that found
+// any), stats[1] = min(list index of a matched mutation on the other strand): integer atomics only, so both words depend on the set of
+// rows alone.
+__global__ __launch_bounds__(ST_THREADS) void sites_label_kernel(const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
+                                                                 int64_t n, const int64_t* __restrict__ mut_start,
+                                                                 const uint8_t* __restrict__ mut_strand,
+                                                                 const float* __restrict__ mut_label, int64_t m, int check_strand,
+                                                                 float* __restrict__ label, unsigned long long* __restrict__ stats) {
+  int found = 0;
+  const int64_t step = (int64_t)gridDim.x * ST_THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * ST_THREADS + threadIdx.x; i < n; i += step) {
+    const int64_t p = pos[i];
+    int64_t lo = 0, hi = m;                                  // first j with mut_start[j] >= p
+    while (lo < hi) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      if (mut_start[mid] < p) lo = mid + 1;
+      else hi = mid;
+    }
+    float v = 0.0f;
+    if (lo < m && mut_start[lo] == p) {
+      v = mut_label[lo];
+      ++found;
+      // (list indices are >= 0 and the caller starts the word at INT64_MAX: the unsigned minimum is the signed one)
+      if (check_strand && mut_strand[lo] != strand[i]) atomicMin(&stats[1], (unsigned long long)lo);
+    }
+    label[i] = v;
+  }
+  int total = 0;
+  block_excl_scan(found, &total);
+  if (threadIdx.x == 0 && total) atomicAdd(&stats[0], (unsigned long long)total);
+}
+
 struct SiteGrid {
   int64_t lo, hi, word0, tiles;
 };
@@ -193,6 +231,24 @@ extern "C" int mural_sites_emit(const MuralGenome* g, int64_t lo, int64_t hi, in
   MURAL_REQUIRE(tile_counts && pos && strand, "sites_emit: NULL argument");
   hipLaunchKernelGGL(sites_emit_kernel, dim3((unsigned)s.tiles), dim3(ST_THREADS), 0, (hipStream_t)stream, *g, s.lo, s.hi, focal,
                      context, s.word0, tile_counts, first, n, pos, strand);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
+extern "C" int mural_sites_label(const int64_t* pos, const uint8_t* strand, int64_t n, const int64_t* mut_start, const uint8_t* mut_strand,
+                                 const float* mut_label, int64_t m, int32_t check_strand, float* label, int64_t* stats, void* stream) {
+  MURAL_REQUIRE(n >= 0 && m >= 0, "sites_label: bad sizes n %lld, m %lld", (long long)n, (long long)m);
+  if (n == 0) return MURAL_OK;
+  MURAL_REQUIRE(pos && strand && label && stats, "sites_label: NULL argument");
+  if (m == 0) {                                              // no list for this chromosome: zeros, and no mut_* pointer is read
+    MURAL_HIP_CHECK(hipMemsetAsync(label, 0, (size_t)n * sizeof(float), (hipStream_t)stream));
+    return MURAL_OK;
+  }
+  MURAL_REQUIRE(mut_start && mut_strand && mut_label, "sites_label: NULL mutation list");
+  const int64_t blocks = (n + ST_THREADS - 1) / ST_THREADS;
+  hipLaunchKernelGGL(sites_label_kernel, dim3((unsigned)(blocks < SL_MAX_BLOCKS ? blocks : SL_MAX_BLOCKS)), dim3(ST_THREADS), 0,
+                     (hipStream_t)stream, pos, strand, n, mut_start, mut_strand, mut_label, m, (int)check_strand, label,
+                     (unsigned long long*)stats);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }

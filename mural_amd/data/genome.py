@@ -59,6 +59,62 @@ def site_selection(focal, context="all"):
     return f, c
 
 
+STATS_INIT = (0, np.iinfo(np.int64).max)      # the `stats` words of label_sites before the first call
+
+
+def new_label_stats(device=None):
+    """The `stats` pair of ``label_sites`` (a device tensor) / ``label_sites_host`` (device=None: a numpy array) before the first call."""
+    if device is None:
+        return np.array(STATS_INIT, np.int64)
+    return torch.tensor(STATS_INIT, dtype=torch.int64, device=device)
+
+
+def label_sites_host(pos, strand, muts, check_strand, stats):
+    """The specification of ``label_sites`` in numpy: `pos` / `strand` are enumerated sites (pos ascending), `muts` one chromosome's
+    (start int64 strictly ascending, strand uint8, label float32) or None.  Returns float32 labels: the label of the list entry whose
+    start is the site's position, 0 where there is none.  `stats` (int64[2], started at STATS_INIT) accumulates in place: stats[0] += the
+    rows that found an entry, stats[1] = min(stats[1], list index) over matched entries on the other strand than their site -- only
+    with `check_strand`."""
+    pos, strand = np.asarray(pos, np.int64), np.asarray(strand, np.uint8)
+    label = np.zeros(len(pos), np.float32)
+    if muts is None or len(muts[0]) == 0 or len(pos) == 0:
+        return label
+    m_start, m_strand, m_label = muts
+    j = np.minimum(np.searchsorted(m_start, pos, "left"), len(m_start) - 1)
+    hit = m_start[j] == pos
+    label[hit] = np.asarray(m_label, np.float32)[j[hit]]
+    stats[0] += int(hit.sum())
+    if check_strand:
+        wrong = j[hit & (np.asarray(m_strand, np.uint8)[j] != strand)]
+        if len(wrong):
+            stats[1] = min(int(stats[1]), int(wrong.min()))
+    return label
+
+
+def label_sites(pos, strand, muts, check_strand, stats, out=None):
+    """The label column of enumerated sites on the device (``mural_sites_label``: one binary search per site): `pos` int64 / `strand`
+    uint8 contiguous device tensors as ``emit_sites`` wrote them, `muts` one chromosome's (start, strand, label) as contiguous device
+    tensors (int64 strictly ascending, uint8, float32) or None, `stats` an int64[2] device tensor from ``new_label_stats`` that
+    accumulates over calls.  Returns float32 labels (`out` if given).  Same contract as ``label_sites_host``; nothing is read back."""
+    n = pos.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=pos.device)
+    tensors = (pos, strand, out, stats) + (tuple(muts) if muts is not None else ())
+    want = (torch.int64, torch.uint8, torch.float32, torch.int64, torch.int64, torch.uint8, torch.float32)
+    if any(not t.is_cuda or t.device != pos.device or not t.is_contiguous() or t.dtype != dt or t.dim() != 1 for t, dt in zip(tensors, want)):
+        raise ValueError("label_sites: pos / strand / out / stats / the mutation list must be contiguous 1-D int64 / uint8 / float32 / "
+                         "int64 / (int64, uint8, float32) tensors on one HIP device")
+    m = 0 if muts is None else muts[0].shape[0]
+    if strand.shape[0] != n or out.shape[0] != n or stats.shape[0] != 2 or (m and (muts[1].shape[0] != m or muts[2].shape[0] != m)):
+        raise ValueError("label_sites: pos / strand / out must have one length, stats two entries, the list's columns one length")
+    list_ptrs = [t.data_ptr() for t in muts] if m else [None, None, None]
+    with torch.cuda.device(pos.device):
+        _lib.check(_lib.lib().mural_sites_label(pos.data_ptr(), strand.data_ptr(), n, *list_ptrs,
+                                                m, int(bool(check_strand)), out.data_ptr(), stats.data_ptr(),
+                                                _lib.current_stream_ptr(pos.device)))
+    return out
+
+
 class SiteScan:
     """The counting pass of a site enumeration (``PackedGenome.scan_sites``): the window, the selection, the per-tile offsets and
     the total, all on the device; ``total`` reads the count back (one synchronisation, cached)."""

@@ -108,6 +108,32 @@ def read_bed(path):
     return BedSites(cn, cid, start, end, score, strand)
 
 
+def read_mutations(path, n_class=None):
+    """The observed mutations of a regions run (``mural_amd.predict.predict_regions_sharded(mutations=)``): a BED of the mutated sites
+    only -- the rows of the reference's input BED whose score (= mut_type) is not 0; rows with score 0 are allowed --, plain or gzip,
+    in any order.  Returns {chrom: (start int64 strictly ascending, strand uint8 (1 = '-'), label float32)}.  Raises ValueError naming
+    ``chrom:start`` for two rows with the same (chrom, start), a row with end != start + 1, a score that is not an integer >= 0 and,
+    with `n_class`, a score >= n_class."""
+    bed = read_bed(path)
+    out = {}
+    for c, name in enumerate(bed.chrom_names):
+        rows = np.nonzero(bed.chrom_id == c)[0]
+        rows = rows[np.argsort(bed.start[rows], kind="stable")]
+        start, end, score = bed.start[rows], bed.end[rows], bed.score[rows]
+
+        def refuse(bad, what):
+            if bad.any():
+                raise ValueError(f"{os.fspath(path)}: {name}:{int(start[int(np.argmax(bad))])} {what}")
+
+        refuse(end != start + 1, "is not a single site (end must be start + 1)")
+        refuse(~(np.isfinite(score) & (score >= 0) & (score == np.floor(score))), "has a score that is not an integer >= 0 (the score is the mut_type)")
+        if n_class is not None:
+            refuse(score >= n_class, f"has a score outside 0 .. {int(n_class) - 1}, the model's classes")
+        refuse(np.r_[False, start[1:] == start[:-1]], "is listed twice")
+        out[name] = (np.ascontiguousarray(start), np.ascontiguousarray(bed.strand[rows]), np.ascontiguousarray(score, np.float32))
+    return out
+
+
 PIECE_ROWS = 1 << 18      # rows per index piece at most: finding row r of a chromosome costs a newline scan of one piece
 
 

@@ -1969,18 +1969,22 @@ class _BedSites:
         start, end, label, strand = self.index.read_block(chrom, lo, hi)
         return start, end, strand, label
 
+    def done(self, chrom):
+        pass
+
     def layout(self, chrom, row0, n):
         ids = self.index.chroms[chrom]
         runs = [(self.index.runs[i].row0, self.index.runs[i].row0 + self.index.runs[i].rows) for i in ids]
         return runs, self.index.runs[0].first_start if ids[0] == 0 else None      # (the FILE's first run anchors its segment grid)
 
 
-def _predict_shards(forward, src, central_bp, model_type, group, sink, collect, T, rank, world, emulated):
+def _predict_shards(forward, src, central_bp, model_type, group, sink, collect, T, rank, world, emulated, finish=None):
     """The per-chromosome loop of the file-level drivers, over `src.names` in ascending order: the table's.  Per chromosome `src` answers
     open(chrom, fetch_next) -> (sites, "they are in the table's order") -- a source that counts on the device calls fetch_next() behind
     the work it enqueued --, columns(chrom, lo, hi) -> (start, end, strand, label) of sites [lo, hi), host arrays or device tensors,
     charged to T[src.read_key], and layout(chrom, row0, n) -> ([(lo, hi)] file rows of its runs, the first run's anchor), where `row0`
-    rows precede the chromosome in this loop.  src.check_focal / src.reorder: see _BedSites."""
+    rows precede the chromosome in this loop.  src.done(chrom) is called behind the chromosome's last part, `finish()` behind the last
+    chromosome; what they raise aborts the sink.  src.check_focal / src.reorder: see _BedSites."""
     clock = time.perf_counter
     dev = _device_of(forward)
     tdev = dev if dev is not None else torch.device("cpu")
@@ -2015,6 +2019,7 @@ def _predict_shards(forward, src, central_bp, model_type, group, sink, collect, 
                 local = _forward_rows(forward, chrom, start_h if dev is None else pos_b, strand_h if dev is None else strand_b, p1 - p0, T)
                 if is_aligned:
                     records.append(tail.aligned_part(chrom, local, pos_b, end_b, strand_b, label_b, anchor, central_bp))
+            src.done(chrom)
             if is_aligned:
                 tail.aligned_close(records, group, world, emulated)
                 T["aligned_shards"] = T.get("aligned_shards", 0) + 1
@@ -2056,6 +2061,8 @@ def _predict_shards(forward, src, central_bp, model_type, group, sink, collect, 
                     local, *cols = (c.contiguous() for c in _gather_rows(local, cols, n, group, T, "gather"))
                 grp, file_rows = None, torch.arange(*runs[0], device=tdev) if collect else None
             tail(chrom, runs, local, *cols, grp, file_rows)
+        if finish is not None:                             # (inside the frame: what it raises aborts the sink)
+            finish()
     return tail.result(rows_all, None)
 
 
@@ -2195,22 +2202,56 @@ def _region_pieces(cum, a, b):
     return out
 
 
+def mutations_for_regions(mutations, regions):
+    """{chrom of `regions`: (its list (start, strand, label) or None, list rows inside the chromosome's merged regions)}: what a regions
+    run takes from a mutation list ({chrom: (start ascending, strand, label)}, data.ingest.read_mutations).  Chromosomes that only the
+    list names are left out; a chromosome that only the regions name has no list (every label 0)."""
+    out = {}
+    for chrom, intervals in regions.items():
+        listed = mutations.get(chrom)
+        if listed is None or len(listed[0]) == 0:
+            out[chrom] = (None, 0)
+            continue
+        iv = np.asarray(intervals, np.int64).reshape(-1, 2)                        # (merged: sorted and disjoint)
+        start = np.asarray(listed[0], np.int64)
+        at = np.searchsorted(iv[:, 0], start, "right") - 1
+        out[chrom] = (listed, int(((at >= 0) & (start < iv[np.maximum(at, 0), 1])).sum()) if len(iv) else 0)
+    return out
+
+
 class _RegionSites:
     """Site source of predict_regions_sharded: a chromosome's sites are its regions' enumerations one after the other.  The enumeration
     ascends, so the rows are always in the table's order and a gathered shard needs no reorder; the sites are chosen BY their base, so
-    the per-(segment, strand) focal-base check of the BED path cannot fail and is skipped."""
+    the per-(segment, strand) focal-base check of the BED path cannot fail and is skipped.
+
+    `mutations` ({chrom: (start, strand, label)}, data.ingest.read_mutations) gives the rows their labels: a chromosome's list goes to
+    the device once (open), every part's label column is a lookup in it (columns: data.genome.label_sites, this rank's slice only), and
+    the two `stats` words come back once per chromosome behind its last part (done)."""
     check_focal = reorder = False
     read_key = "enumerate"
 
-    def __init__(self, forward, regions, focal, context, dev, T):
+    def __init__(self, forward, regions, focal, context, dev, T, mutations=None, check_strand=False):
         self.forward, self.regions, self.focal, self.context, self.dev, self.T = forward, regions, focal, context, dev, T
         self.names = sorted(regions)
+        self.mutations, self.check_strand = None if mutations is None else mutations_for_regions(mutations, regions), check_strand
+        self.in_regions = self.matched = 0
+        if mutations is not None:
+            T["label"] = 0.0
+            self.in_regions = sum(inside for _, inside in self.mutations.values())
 
     def open(self, chrom, fetch_next):
         self.g = g = self.forward.genome(chrom)            # (KeyError for a chromosome the FASTA lacks, like the BED path)
         t0 = time.perf_counter()
         self.scans = [g.scan_sites(lo, hi, self.focal, self.context) for lo, hi in self.regions[chrom]]
         fetch_next()                                       # right behind the enqueued scans, before the host waits for their totals
+        self.muts = self.stats = None
+        if self.mutations is not None:
+            from .data.genome import new_label_stats
+            self.stats = new_label_stats(self.dev)
+            listed = self.mutations[chrom][0]
+            if listed is not None:
+                self.muts = tuple(torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.dev)
+                                  for a, dt in zip(listed, (np.int64, np.uint8, np.float32)))
         # the one read-back per chromosome: the totals size the outputs and the ranks' slices
         self.cum = np.r_[0, np.cumsum(torch.cat([sc.total_dev for sc in self.scans]).tolist() if self.scans else [])].astype(np.int64)
         self.T["enumerate"] += time.perf_counter() - t0
@@ -2223,25 +2264,73 @@ class _RegionSites:
         for j, first, m in _region_pieces(self.cum, a, b):
             self.g.emit_sites(self.scans[j], first, m, pos[o:o + m], strand[o:o + m])
             o += m
-        return pos, pos + 1, strand, torch.zeros(b - a, dtype=torch.float32, device=self.dev)
+        if self.mutations is None:
+            return pos, pos + 1, strand, torch.zeros(b - a, dtype=torch.float32, device=self.dev)
+        from .data.genome import label_sites
+        t0 = time.perf_counter()
+        label = label_sites(pos, strand, self.muts, self.check_strand, self.stats)
+        self.T["label"] += time.perf_counter() - t0
+        return pos, pos + 1, strand, label
+
+    def done(self, chrom):
+        """Behind the chromosome's last part: its `stats` words, read back once.  A listed mutation on the other strand than the site it
+        lies on raises ValueError (inside the driver's frame: the sink is aborted, no table is left)."""
+        if self.stats is None:
+            return
+        matched, wrong = self.stats.tolist()
+        self.matched += matched
+        if self.muts is not None and wrong < len(self.muts[0]):
+            listed = self.mutations[chrom][0]
+            start, st = int(listed[0][wrong]), int(listed[1][wrong])
+            raise ValueError(f"mutations: {chrom}:{start} is listed on strand '{'+-'[st]}' but the site there is on strand "
+                             f"'{'-+'[st]}' (the strand says which base mutated: A / C sites are '+', T / G sites '-')")
+
+    def finish(self, group, world, emulated, strict):
+        """The counts of the run -> timings['mutations']; `strict`: a listed mutation inside the regions that matched no site raises."""
+        if self.mutations is None:
+            return
+        matched = self.matched
+        if world > 1 and not emulated:
+            total = torch.tensor([matched], dtype=torch.int64, device=self.dev)
+            dist.all_reduce(total, group=group)
+            matched = int(total.item())
+        counts = {"in_regions": self.in_regions, "matched": matched, "unmatched": self.in_regions - matched}
+        self.T["mutations"] = counts
+        if strict and counts["unmatched"]:
+            raise ValueError("mutations: %d of the %d listed mutations inside the regions lie on no enumerated site (%d matched): "
+                             "another focal base or context, an N, or a wrong coordinate" % (counts["unmatched"], self.in_regions, matched))
 
     def layout(self, chrom, row0, n):
         return [(row0, row0 + n)], None                    # there is no input file: the rows count up in the table's order
 
 
 def predict_regions_sharded(forward, regions, focal, context="all", model_type="snv", group=None, sink=None, collect=True, timings=None,
-                            emulate=None):
+                            emulate=None, mutations=None, strict_mutations=False):
     """predict_bed_sharded for sites that are not listed in a file but selected by their base: every A/T site (focal 'A'), every C/G
     site (focal 'C'; context 'all', 'CpG' or 'nonCpG') or, for INDEL models, every A/C/G/T position (focal 'ANY') of `regions` (what
     read_regions_arg returns, or its argument).  Same forward (HipShardForward: a HIP ``device`` and ``genome(chrom)``), sinks, `timings`,
-    `emulate` and return value as predict_bed_sharded; rows carry end = start + 1 and label 0.  With `collect` the returned rows are in the
+    `emulate` and return value as predict_bed_sharded; rows carry end = start + 1 and label 0 (`mutations`: below).  With `collect` the returned rows are in the
     table's order -- ascending chromosome name, then start: there is no input file whose order could be kept -- and `order` counts them.
 
     Chromosomes go in ascending name order, the next one is packed while this one is computed.  Per chromosome the regions are counted
     on the device (one read-back of the totals), rank i of N takes the slice shard_bounds(sites of the chromosome, i, N) of the
     enumeration and emits it in parts of at most _ALIGNED_PART_ROWS sites.  The enumeration ascends, so with a consumer of aligned
     blocks (a TsvSink, every rank's with parts=True; collect=False) a rank's rows are its slice of the table: nothing is gathered or
-    sorted.  A caller that wants all rows back, or a sink on rank 0 alone, gets one all_gather per chromosome instead."""
+    sorted.  A caller that wants all rows back, or a sink on rank 0 alone, gets one all_gather per chromosome instead.
+
+    `mutations`: the observed side -- the path of a BED of the mutated sites (data.ingest.read_mutations: chrom start end name score
+    strand, score = mut_type, checked against the model's n_class) or what read_mutations returns.  A row whose position is a listed
+    start carries that entry's label, every other row 0: the table is the one the BED path writes for a BED with every enumerated site
+    and those scores.  The join is a lookup per site on the device in front of the forward (csrc/sites.hip: mural_sites_label), on every
+    rank for its own slice; nothing is gathered for it.  Chromosomes of the list that the regions lack are ignored.  For the SNV
+    selections a listed mutation on the other strand than the site it lies on raises ValueError (chromosome, start, both strands); like
+    every failure it leaves no table (under a process group the rank whose slice holds the site raises; the others fail with it at
+    their next collective).  Listed mutations inside the regions that lie on NO enumerated site (the other focal base, an N,
+    outside the CpG selection: one list may serve several models) are counted, and raise ValueError only with `strict_mutations`.
+    timings['mutations'] = {in_regions, matched, unmatched = in_regions - matched}: `in_regions` counts the list's rows inside the
+    merged regions on the host, `matched` is summed over the ranks of a process group with one all_reduce at the end of the run; an
+    emulated rank (`emulate=`) reports the matches of ITS slice alone, so `unmatched` means nothing there and `strict_mutations` is
+    refused.  timings['label'] are the host seconds spent enqueueing the lookups (without `mutations` neither key appears)."""
     from .data.genome import site_selection
     f_code, _ = site_selection(focal, context)
     if model_type not in ("snv", "indel"):
@@ -2259,5 +2348,12 @@ def predict_regions_sharded(forward, regions, focal, context="all", model_type="
     T.update({"emulation": 0.0, "enumerate": 0.0})
     if emulate is not None and world > 1 and not _takes_aligned_blocks(sink, collect, world):
         raise ValueError("emulate=(rank, world) needs collect=False and a part-file sink: one rank cannot stand in for a gather")
-    src = _RegionSites(forward, regions, focal, context, dev, T)
-    return _predict_shards(forward, src, 0, model_type, group, sink, collect, T, rank, world, emulate is not None)
+    if strict_mutations and (mutations is None or (emulate is not None and world > 1)):
+        raise ValueError("strict_mutations needs mutations= and every rank's matches: it does not go with emulate=(rank, world)")
+    if mutations is not None and not isinstance(mutations, dict):
+        from .data.ingest import read_mutations
+        mutations = read_mutations(mutations, getattr(getattr(forward, "model", None), "n_class", None))
+    src = _RegionSites(forward, regions, focal, context, dev, T, mutations, check_strand=f_code != 2)
+    emulated = emulate is not None
+    return _predict_shards(forward, src, 0, model_type, group, sink, collect, T, rank, world, emulated,
+                           finish=lambda: src.finish(group, world, emulated, strict_mutations))

@@ -4,7 +4,9 @@
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A (every A a '+'
 site, every T a '-' site).  The BED is written from the device enumeration (one row per site, label 0) and stays in the page cache:
 it is written, and read once by the warm-up run, right before the timed runs.  The two paths alternate, --repeats timed runs each
-after one warm-up run each; the two tables must be byte-identical.  Prints one JSON line."""
+after one warm-up run each; the two tables must be byte-identical.  A third leg in the same rounds is the regions run with observed
+mutations: a synthetic list with every 100th site (1 % of the rows, classes 1 .. 3, a BED in the same directory,
+read by every run), whose table must carry exactly those labels.  Prints one JSON line."""
 import ctypes as C
 import json
 import os
@@ -54,7 +56,12 @@ def write_inputs(work, device, bases, name="chr1", seed=7):
             _lib.check(lib.mural_tsv_format_device(C.byref(t), text.data_ptr(), text.numel(), count.data_ptr(), ws.data_ptr(), ws.numel(),
                                                   _lib.current_stream_ptr(device)))
             b.write(text[:int(count.item())].cpu().numpy().tobytes())
-    return fa, bed, genome, int(pos.shape[0])
+    # the observed side of the labelled leg: every 100th site, its own strand, classes 1 .. 3
+    mut = os.path.join(work, "mutations.bed")
+    m_pos, m_strand = pos[::100].cpu().numpy(), strand[::100].cpu().numpy()
+    with open(mut, "w") as f:
+        f.write("".join(f"{name}\t{p}\t{p + 1}\t.\t{1 + i % 3}\t{'+-'[st]}\n" for i, (p, st) in enumerate(zip(m_pos.tolist(), m_strand.tolist()))))
+    return fa, bed, mut, len(m_pos), genome, int(pos.shape[0])
 
 
 def time_enumeration(genome, repeats):
@@ -88,11 +95,11 @@ def main(argv):
     model, r, order, _ = shipped_snv_model(device)
     shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) and shutil.disk_usage("/dev/shm").free > 100 * bases else None
     with tempfile.TemporaryDirectory(prefix="mural_regions_", dir=shm) as work:
-        fa, bed, genome, rows = write_inputs(work, device, bases)
+        fa, bed, mut, listed, genome, rows = write_inputs(work, device, bases)
         count_ms, both_ms = time_enumeration(genome, max(repeats, 5))
         del genome
         torch.cuda.empty_cache()
-        out = {"regions": os.path.join(work, "regions.tsv"), "bed": os.path.join(work, "bed.tsv")}
+        out = {"regions": os.path.join(work, "regions.tsv"), "bed": os.path.join(work, "bed.tsv"), "labelled": os.path.join(work, "labelled.tsv")}
 
         def run(path):
             split = {}
@@ -101,6 +108,10 @@ def main(argv):
             fwd = HipShardForward(model, fa, r, order, device=device, reuse=True)
             if path == "regions":
                 n = predict_regions_sharded(fwd, "chr1", "A", sink=TsvSink(out[path]), collect=False, timings=split)
+            elif path == "labelled":
+                n = predict_regions_sharded(fwd, "chr1", "A", sink=TsvSink(out[path]), collect=False, timings=split, mutations=mut,
+                                            strict_mutations=True)
+                assert split["mutations"] == {"in_regions": listed, "matched": listed, "unmatched": 0}, split["mutations"]
             else:
                 n = predict_bed_sharded(fwd, bed, sink=TsvSink(out[path]), collect=False, timings=split)
             torch.cuda.synchronize()
@@ -108,9 +119,9 @@ def main(argv):
             assert n == rows, (path, n, rows)
             return dt, {k: v for k, v in split.items() if isinstance(v, float)}
 
-        seconds, splits = {"regions": [], "bed": []}, {}
+        seconds, splits = {"regions": [], "bed": [], "labelled": []}, {}
         for i in range(repeats + 1):
-            for path in ("bed", "regions"):
+            for path in ("bed", "regions", "labelled"):
                 dt, split = run(path)
                 if i:                                      # (round 0 warms kernels, allocator pools and the page cache of the inputs)
                     seconds[path].append(dt)
@@ -118,19 +129,27 @@ def main(argv):
         with open(out["regions"], "rb") as a, open(out["bed"], "rb") as b:
             identical = all(x == y for x, y in zip(iter(lambda: a.read(1 << 24), b""), iter(lambda: b.read(1 << 24), b""))) \
                 and os.path.getsize(out["regions"]) == os.path.getsize(out["bed"])
+        # the labelled table: the same rows, the list's labels per class (the table tools' device parser counts them)
+        from mural_amd.tables import regional_table
+        counts = regional_table(out["labelled"], 100_000, 4)[1][:, :5].sum(axis=0).astype(int).tolist()
+        want = [rows, rows - listed] + [len(range(c, listed, 3)) for c in range(3)]
+        identical = identical and counts == want and os.path.getsize(out["labelled"]) == os.path.getsize(out["regions"])
         sizes = {"fasta_bytes": os.path.getsize(fa), "bed_bytes": os.path.getsize(bed), "table_bytes": os.path.getsize(out["bed"])}
     rate = {p: spread([rows / s for s in seconds[p]]) for p in seconds}
     res = {"workload": "one chromosome of %d bases, focal A, Homo_sapiens/SNV/AT weights, file to file" % bases, "rows": rows, **sizes,
-           "repeats": repeats, "tables_identical": identical,
+           "repeats": repeats, "tables_identical": identical, "labelled_table_counts": counts,
            "enumeration_ms_per_100Mbp": {"count": spread([m * 1e8 / bases for m in count_ms]),
                                          "count_readback_emit": spread([m * 1e8 / bases for m in both_ms])},
            "regions_rows_per_s": rate["regions"], "bed_rows_per_s": rate["bed"],
            "regions_over_bed": rate["regions"]["median"] / rate["bed"]["median"],
-           "regions_seconds": seconds["regions"], "bed_seconds": seconds["bed"], "split_seconds": splits,
+           "labelled_rows_per_s": rate["labelled"], "listed_mutations": listed,
+           "labelled_over_regions": rate["labelled"]["median"] / rate["regions"]["median"],
+           "regions_seconds": seconds["regions"], "bed_seconds": seconds["bed"], "labelled_seconds": seconds["labelled"],
+           "split_seconds": splits,
            "files_in": "/dev/shm" if shm else "the temp directory"}
     print(json.dumps(res))
     if not identical:
-        raise SystemExit("the region table differs from the BED table")
+        raise SystemExit("the region table differs from the BED table, or the labelled table does not carry the list's labels")
 
 
 if __name__ == "__main__":

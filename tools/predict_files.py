@@ -5,6 +5,10 @@ Without a BED file -- the sites are enumerated from the FASTA on the device (mur
   python tools/predict_files.py MODEL FASTA OUT.tsv --regions SPEC [--regions SPEC ..] [--focal A|C] [--context all|CpG|nonCpG]
 SPEC: chr, chr:start-end (1-based, inclusive) or a BED-like file of regions; --focal defaults to A (with --indel every A/C/G/T
 position is a site and --focal / --context do not apply).
+  --mutations FILE      with --regions: the observed mutations, a BED of the mutated sites only (chrom start end name score strand,
+                        score = mut_type, plain or gzip).  A row on a listed position carries that mut_type, every other row 0 -- the
+                        table (and every summary) of a BED with one row per site, without writing that BED
+  --strict_mutations    fail when a listed mutation inside the regions lies on no enumerated site (by default they are only counted)
 
 Genome summaries in flight, in both forms (mural_amd.predict.SummarySink; the numbers `calc_scaling_factor` and `evaluate --window_size`
 read back from the table, taken from the probabilities before they are rounded):
@@ -30,7 +34,7 @@ from mural_amd.model.nn_utils import load_model  # noqa: E402
 
 _SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
                     "--scale_factor")
-_VALUE_OPTIONS = ("--regions", "--focal", "--context") + _SUMMARY_OPTIONS
+_VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _SUMMARY_OPTIONS
 
 
 def _split(argv):
@@ -63,6 +67,9 @@ def main(argv):
     model_type = "indel" if "--indel" in flags else "snv"
     poisson = "--poisson" in flags or model_type == "indel"
     opts = _summary_options(flags, values, model_type)
+    if ("--mutations" in values or "--strict_mutations" in flags) and "--regions" not in values:
+        raise SystemExit("--mutations / --strict_mutations label the sites that --regions enumerates: a BED run takes its labels from "
+                         "the BED's score column")
     n_args = (3 if "--regions" in values else 4) - int(opts["no_table"])
     if opts["no_table"] and len(args) == n_args + 1:
         raise SystemExit(f"--no-table writes no table: leave {args[-1]} out")
@@ -71,7 +78,9 @@ def main(argv):
     if opts["no_table"]:
         args = args + [None]
     if "--regions" in values:
-        if len(values.get("--focal", [])) > 1 or len(values.get("--context", [])) > 1:
+        if "--strict_mutations" in flags and "--mutations" not in values:
+            raise SystemExit("--strict_mutations needs --mutations FILE")
+        if len(values.get("--mutations", [])) > 1 or len(values.get("--focal", [])) > 1 or len(values.get("--context", [])) > 1:
             raise SystemExit(__doc__)
         return _main_regions(args, values, flags, model_type, poisson, opts)
     if set(values) - set(_SUMMARY_OPTIONS):
@@ -167,6 +176,11 @@ def _report(n, out, summary, opts):
         summary.scaling_factor(opts["genomewide_mu"], opts["m_proportion"], 1.0 if opts["g_proportion"] is None else opts["g_proportion"])
 
 
+def _report_mutations(split):
+    if "mutations" in split:
+        print("mutations inside the regions: {in_regions}, on an enumerated site: {matched}, on none: {unmatched}".format(**split["mutations"]))
+
+
 def _main_bed_sharded(args, flags, model_type, poisson, opts):
     from mural_amd.predict import predict_bed_sharded
     model_path, fasta, bed, out = args
@@ -185,9 +199,13 @@ def _main_regions(args, values, flags, model_type, poisson, opts):
     else:
         focal, context = values.get("--focal", ["A"])[0], values.get("--context", ["all"])[0]
     regions = read_regions_arg(values["--regions"])
+    split = {}
+    labels = dict(mutations=values["--mutations"][0], strict_mutations="--strict_mutations" in flags) if "--mutations" in values else {}
     if opts["any"]:
         forward, cfg, sink, summary = _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts)
-        n = predict_regions_sharded(forward, regions, focal, context, model_type=model_type, sink=sink, collect=False)
+        n = predict_regions_sharded(forward, regions, focal, context, model_type=model_type, sink=sink, collect=False, timings=split,
+                                    **labels)
+        _report_mutations(split)
         return _report(n, out, summary, opts)
     model, cfg = load_model(model_path, model_type=model_type)
     cal = model_path + ".fdiri_cal.pkl"
@@ -196,7 +214,8 @@ def _main_regions(args, values, flags, model_type, poisson, opts):
     forward = HipShardForward(model, fasta, cfg["local_radius"], cfg.get("local_order", 3), distal_radius=cfg["distal_radius"],
                               model_type=model_type, poisson=False)
     sink = TsvSink(out, poisson=poisson, dirichlet_weights=weights)
-    n = predict_regions_sharded(forward, regions, focal, context, model_type=model_type, sink=sink, collect=False)
+    n = predict_regions_sharded(forward, regions, focal, context, model_type=model_type, sink=sink, collect=False, timings=split, **labels)
+    _report_mutations(split)
     print(f"{n} sites -> {out}")
 
 
