@@ -28,6 +28,22 @@ int mural_debug_cl_conv32_fwd(const float* x, int64_t B, int32_t L, int32_t pre_
 int mural_debug_cl_conv32_bwd(const float* dy, const float* x, const float* W, int64_t B, int32_t L, const float* state,
                               int32_t pre_relu, float* dz, double* stat_out, float* part, int32_t* nrow, void* stream);
 int mural_debug_cl_bn_stats(const float* x, int64_t rows, int32_t relu, double* acc, void* stream);
+/* Validation hooks of tests/test_gpu_first_layer.py: the channel-last first layer of the composed step on its own (C = 32, pool windows
+ * up to 15; buffers sized by mural_op_first_plan, arguments as mural_op_first_fwd / _bwd).  y / dy are [B][L2][32]; stat: double
+ * [MURAL_BN_SLOTS][2][32] zeroed by the caller, receives the batch sums of relu(y) and relu(y)^2.  Backward: with fold_dz != NULL the
+ * pooled gradient is not read from dy (may be NULL) but made from the BatchNorm-backward apply of the layer behind,
+ * relu'(x) * gamma * invstd * (dz - mean(dz) - xhat * mean(dz * xhat)) + add1 + add2 (add1 / add2 optional): fold_x = that layer's
+ * input, fold_state = scale | beta | mean | invstd [4][32], fold_acc = double [MURAL_BN_SLOTS][2][32] holding sum(dz) | sum(dz * xhat),
+ * fold_n = elements per channel; fold_dgamma / fold_dbeta [32] receive that BatchNorm's parameter gradients. */
+int mural_debug_first_fwd_cl(const uint8_t* sym, int64_t B, int32_t Lwin, int32_t col0, int32_t L1, int32_t pk, int32_t ps, int32_t pp,
+                             const float* gamma, const float* beta, const float* W, const float* bias, float eps, float momentum,
+                             float* running_mean, float* running_var, unsigned long long* counts, float* tab, float* y, void* arg,
+                             double* stat, void* stream);
+int mural_debug_first_bwd_cl(const float* dy, const void* arg, const uint8_t* sym, int64_t B, int32_t Lwin, int32_t col0, int32_t L1,
+                             int32_t pk, int32_t ps, int32_t pp, const float* tab, const float* W, float* scratch, float* dW,
+                             float* dbias, float* dgamma, float* dbeta, const float* fold_dz, const float* fold_x,
+                             const float* fold_add1, const float* fold_add2, const float* fold_state, const float* fold_gamma,
+                             const double* fold_acc, double fold_n, float* fold_dgamma, float* fold_dbeta, void* stream);
 /* the same two layers on the wave-private kernels (csrc/conv32_wave.hip); wfrag_scratch: the 6144 floats mural_debug_cw_wfrag wrote
  * for W (forward | input-gradient filter fragments, the per-step relayout of the composed step) or NULL: the conv gathers its
  * fragments from a copy of W in LDS */

@@ -261,6 +261,10 @@ DEBUG_PROTOTYPES = {
     "mural_debug_cw_conv32_fwd": (C.c_int, [VP, I64, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP, I32, VP, VP, VP]),
     "mural_debug_cw_conv32_bwd": (C.c_int, [VP, VP, VP, I64, I32, VP, VP, I32, VP, VP, VP, VP, VP, VP]),
     "mural_debug_cl_bn_stats": (C.c_int, [VP, I64, I32, VP, VP]),
+    "mural_debug_first_fwd_cl": (C.c_int, [VP, I64, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP, VP,
+                                           VP, VP]),
+    "mural_debug_first_bwd_cl": (C.c_int, [VP, VP, VP, I64, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP,
+                                           VP, C.c_double, VP, VP, VP]),
     "mural_debug_conv1d": (C.c_int, [VP, VP, VP, VP, I64, I32, I32, I32, I32, I32, I32, I32, I32, VP, VP, I32, VP]),
     "mural_debug_conv1d_set_stamps": (C.c_int, [VP]),
     "mural_debug_poison_lds": (C.c_int, [VP]),

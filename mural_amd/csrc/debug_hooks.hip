@@ -163,6 +163,25 @@ extern "C" int mural_debug_cl_bn_stats(const float* x, int64_t rows, int32_t rel
   return mural::cl_bn_stats(x, rows, relu, acc, (hipStream_t)stream);
 }
 
+// ---- validation hooks (tests/test_gpu_first_layer.py): the channel-last first layer of the composed step on its own ------------
+extern "C" int mural_debug_first_fwd_cl(const uint8_t* sym, int64_t B, int32_t Lwin, int32_t col0, int32_t L1, int32_t pk, int32_t ps,
+                                        int32_t pp, const float* gamma, const float* beta, const float* W, const float* bias, float eps,
+                                        float momentum, float* running_mean, float* running_var, unsigned long long* counts, float* tab,
+                                        float* y, void* arg, double* stat, void* stream) {
+  return mural::train_first_fwd_cl(sym, B, Lwin, col0, L1, pk, ps, pp, gamma, beta, W, bias, eps, momentum, running_mean, running_var, counts,
+                                   tab, y, arg, stat, (hipStream_t)stream);
+}
+
+extern "C" int mural_debug_first_bwd_cl(const float* dy, const void* arg, const uint8_t* sym, int64_t B, int32_t Lwin, int32_t col0,
+                                        int32_t L1, int32_t pk, int32_t ps, int32_t pp, const float* tab, const float* W, float* scratch,
+                                        float* dW, float* dbias, float* dgamma, float* dbeta, const float* fold_dz, const float* fold_x,
+                                        const float* fold_add1, const float* fold_add2, const float* fold_state, const float* fold_gamma,
+                                        const double* fold_acc, double fold_n, float* fold_dgamma, float* fold_dbeta, void* stream) {
+  const mural::FirstFold fold{fold_dz, fold_x, fold_add1, fold_add2, fold_state, fold_gamma, fold_acc, fold_n, fold_dgamma, fold_dbeta};
+  return mural::train_first_bwd_cl(dy, arg, sym, B, Lwin, col0, L1, pk, ps, pp, tab, W, scratch, dW, dbias, dgamma, dbeta,
+                                   fold_dz ? &fold : nullptr, (hipStream_t)stream);
+}
+
 // ---- validation hooks (tests/test_gpu_train.py, tools/gpu_debug_conv32_cl.py): the wave-private conv kernels on their own -----
 extern "C" int mural_debug_cw_conv32_fwd(const float* x, int64_t B, int32_t L, int32_t pre_relu, const double* acc, const float* gamma,
                                          const float* beta, float* running_mean, float* running_var, float* state, const float* W,

@@ -55,7 +55,6 @@ const DevSwitch* dev_switch_table() {
     {"MURAL_DEBUG_POLY_NARROW", "validation: the polyphase up-conv's dword stores"},
     {"MURAL_DEBUG_FIRST_SCATTER", "validation: the first layer's backward through LDS atomics"},
     {"MURAL_DEBUG_S1_ALIAS", "TIMING ONLY, wrong results: every site writes the x0 rows of site (row mod 64)"},
-    {"MURAL_DEBUG_FIRST", "TIMING ONLY, wrong results: phases of the training first-layer kernels switched off"},
     {"MURAL_DEBUG_CW", "TIMING ONLY, wrong results: phases of the wave-private conv kernels switched off (bit mask)"},
     {"MURAL_DEBUG_MLP", "TIMING ONLY, wrong results: phases of the local MLP switched off"},
     {"MURAL_DEBUG_CB_STAMP_ONLY", "diagnostic: phase stamps of one workgroup only"},

@@ -125,12 +125,12 @@ struct FirstTrainArgs {
   int cl;                         // 1: y / dy are channel-last [B][L2][32] (the composed training step), 0: [B][32][L2]
   double* stat;                   // forward, cl only: [MURAL_BN_SLOTS][2][32] batch sums of relu(y), relu(y)^2 (nullptr: none)
   FirstFold fold;                 // backward, cl only
-  int dbg;                        // timing experiments (MURAL_DEBUG_FIRST): 1 no LDS atomics, 2 no gradient / arg-max loads, 4 no index reads
   unsigned long long* stamps;     // diagnostic (mural_debug_first_set_stamps): [workgroup][8] wall-clock ticks (100 MHz) of wave 0's phases
 };
 extern unsigned long long* g_first_stamps;
 int first_train_grid(int64_t B);
 bool first_train_supported(int C, int pk);
+bool first_train_fits(int Lwin, int L2, int pk);      // the forward's LDS working set fits (launch_first_train refuses the call otherwise)
 int launch_first_train(FirstTrainArgs a, bool bwd, hipStream_t stream);      // (host entries of the training step around it: train_ops.h)
 
 struct SnvFwdArgs {

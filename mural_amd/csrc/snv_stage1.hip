@@ -530,64 +530,6 @@ __device__ __forceinline__ void pooled_scatter(const Stage1Tower& g, int lane, f
 
 #define FT_STAMP(K) do { if (a.stamps && tid == 0) a.stamps[8 * blockIdx.x + (K)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 
-
-// The same scatter for the channel-last gradient of the composed step, one CHANNEL per lane: lane = (parity of the pooled column,
-// channel).  The 32 lanes of a half-wave add into 32 different LDS banks (table rows are 32 floats), and a wave's gradient load is 256
-// contiguous bytes.  The form above -- lane = (column, four channels) -- puts the eight columns of a wave instruction on the same
-// eight banks: eight serial read-modify-writes per bank, 75 of the launch's 100 us at batch 4096 (tools/phase_stamps_first.py).
-template <int SLOT>
-__device__ __forceinline__ void pooled_scatter_cl(const Stage1Tower& g, int lane, float* acc, const uint8_t* cb0, const uint8_t* kw,
-                                                  const float* __restrict__ dy /* [L2][32] */, const uint8_t* __restrict__ arg /* [L2][32] */,
-                                                  int dbg) {
-  float* tapA = acc + SNV_LUT;
-  float* b0A = tapA + SNV_TAPS;
-  const uint8_t* cb = cb0 + g.col0;
-  const int c = lane & 31, h = lane >> 5;
-  const int npair = (g.L2 + 1) >> 1;
-  float bsum = 0.f;
-  // the row through range-checked descriptors (a column pair behind the row reads as zero), one lane offset, the pair in the immediate
-  const __amdgpu_buffer_rsrc_t gd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy), 0, (dbg & 2) ? 0 : g.L2 * 128, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ad = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(arg), 0, (dbg & 2) ? 0 : g.L2 * 32, 0x00020000);
-  constexpr int NT = 16;                       // column pairs in flight per lane (a row of 134 pooled columns: five round trips)
-  for (int p0 = 0; p0 < npair; p0 += NT) {
-    float gv[NT];
-    uint32_t awv[NT];
-    const uint32_t go = 4u * (uint32_t)lane + 256u * (uint32_t)p0, ao = (uint32_t)lane + 64u * (uint32_t)p0;
-    int hh = h;                                // opaque per batch: the per-pair address pieces (three per pair) are made here, not hoisted
-    asm volatile("" : "+v"(hh));               // out of the batch loop into 48 registers
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      awv[u] = __builtin_amdgcn_raw_buffer_load_b8(ad, ao + 64u * u, 0, 0);
-      gv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(gd, go + 256u * u, 0, 0));
-    }
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      const int j2 = 2 * (p0 + u) + hh;
-      if (j2 < g.L2) {
-        const float gq = gv[u];
-        const int w = (int)(awv[u] & 0xFFu);
-        const uint32_t idx = (dbg & 4) ? (uint32_t)(j2 & 63) : kw[j2 * SLOT + w];
-        bsum += gq;
-        if (dbg & 1) continue;
-        // one add on the common path; a 3-mer with a symbol outside ACGTN (idx 255) goes to the three per-tap tables instead
-        const int j = j2 * g.ps - g.pp + w;
-        const uint32_t sl = (j == 0) ? (uint32_t)SYM_PAD : cb[j];
-        const bool tab = idx != 255u;
-        atomicAdd(tab ? &acc[idx * 32u + c] : &tapA[(0 * N_SYM + sl) * 32 + c], gq);
-        if (!tab) {
-          const uint32_t sc = cb[j + 1];
-          const uint32_t sr = (j == g.L1 - 1) ? (uint32_t)SYM_PAD : cb[j + 2];
-          atomicAdd(&tapA[(1 * N_SYM + sc) * 32 + c], gq);
-          atomicAdd(&tapA[(2 * N_SYM + sr) * 32 + c], gq);
-        }
-      }
-      if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // (left alone the scheduler hoists all sixteen index reads: spills)
-    }
-  }
-  bsum += __shfl_xor(bsum, 32);
-  if (lane < 32) atomicAdd(&b0A[c], bsum);
-}
-
 template <int SLOT, bool BWD>
 __global__ __launch_bounds__(S1_THREADS) void first_train_kernel(const FirstTrainArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s1mem[];
@@ -666,8 +608,8 @@ __global__ __launch_bounds__(S1_THREADS) void first_train_kernel(const FirstTrai
 
 // ---- backward of the channel-last form (the composed training step) ---------------------------------------------------------------
 // The scatter above is bound by the LDS float atomics themselves: a ds_add_f32 wave instruction occupies the LDS pipe for ~128
-// cycles whatever its bank pattern (tools/phase_stamps_first.py with MURAL_DEBUG_FIRST: 100 -> 22 us per batch of 4096 without the
-// adds, the same 100 us with one channel per lane, i.e. conflict-free) -- 4288 adds per row is 75 us of a 100 us launch.  This kernel
+// cycles whatever its bank pattern (tools/phase_stamps_first.py: 100 -> 22 us per batch of 4096 with the adds switched off, the same
+// 100 us with one channel per lane, i.e. conflict-free) -- 4288 adds per row is 75 us of a 100 us launch.  This kernel
 // has none on its common path.  The 3-mer table is a sum of three per-tap symbol tables (lut[l,m,r] = bias + tap0[l] + tap1[m] +
 // tap2[r]; first_param_grad_kernel folds d lut back into d taps anyway), and a tap sees one of FOUR common symbols: a lane owns one
 // channel and keeps d tap[t][A C G T] of it in twelve registers; a pooled gradient goes to the three registers its window position's
@@ -845,13 +787,24 @@ int first_train_grid(int64_t B) {
 
 bool first_train_supported(int C, int pk) { return C == SNV_C && pk >= 1 && pk <= 15; }
 
+// LDS working set of first_train_kernel: the table block + per wave the padded row and its window indices
+static size_t first_train_lds(int Lwin, int L2, int pk, int* cw, int* wave_bytes) {
+  const int slot = pk <= 3 ? 4 : 16;
+  *cw = (Lwin + 2 + 15) & ~15;
+  *wave_bytes = *cw + ((L2 * slot + 15) & ~15);
+  return (size_t)SNV_LUTBLK * 4 + (size_t)S1_WAVES * *wave_bytes;
+}
+
+bool first_train_fits(int Lwin, int L2, int pk) {
+  int cw, wave_bytes;
+  return first_train_lds(Lwin, L2, pk, &cw, &wave_bytes) <= 160 * 1024;
+}
+
 int launch_first_train(FirstTrainArgs a, bool bwd, hipStream_t stream) {
   if (a.B == 0) return MURAL_OK;
   MURAL_REQUIRE(first_train_supported(SNV_C, a.tw.pk), "first layer: pool window %d not supported by the table kernel", a.tw.pk);
   const int slot = a.tw.pk <= 3 ? 4 : 16;
-  a.cw = (a.Lwin + 2 + 15) & ~15;
-  a.wave_bytes = a.cw + ((a.tw.L2 * slot + 15) & ~15);
-  const size_t lds = (size_t)SNV_LUTBLK * 4 + (size_t)S1_WAVES * a.wave_bytes;
+  const size_t lds = first_train_lds(a.Lwin, a.tw.L2, a.tw.pk, &a.cw, &a.wave_bytes);
   MURAL_REQUIRE(lds <= 160 * 1024, "first layer: window of %d columns does not fit the LDS working set", a.Lwin);
   using KernelFn = void (*)(const FirstTrainArgs);
   MURAL_REQUIRE(!a.fold.dz || (bwd && a.cl), "first layer: the folded BatchNorm-backward apply belongs to the channel-last backward");
@@ -871,8 +824,6 @@ int launch_first_train(FirstTrainArgs a, bool bwd, hipStream_t stream) {
   static DynLdsOnce big_lds[4];                             // once per instantiation and device (never inside a graph capture)
   if (int rc = big_lds[(slot == 4 ? 0 : 2) + (bwd ? 1 : 0)].ensure(fn)) return rc;
   a.stamps = g_first_stamps;
-  static const int dbg = dev_int("MURAL_DEBUG_FIRST", 0);
-  a.dbg = dbg;
   hipLaunchKernelGGL(fn, dim3(first_train_grid(a.B)), dim3(S1_THREADS), lds, stream, a);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;

@@ -1298,6 +1298,9 @@ static int first_fwd_impl(const uint8_t* sym, int64_t B, int32_t Lwin, int32_t c
                           unsigned long long* counts, float* tab, float* y, void* arg, int cl, double* stat, void* stream) {
   const int L2 = (L1 + 2 * pp - pk) / ps + 1;
   const bool fast = first_train_supported(C, pk);
+  // refused in front of the first launch: the tables kernel below already updates the running statistics
+  MURAL_REQUIRE(!fast || first_train_fits(Lwin, L2, pk), "first layer: window of %d columns does not fit the LDS working set", Lwin);
+  MURAL_REQUIRE(fast || !cl, "first layer: the channel-last layout is served by the table kernels only");
   hipLaunchKernelGGL(sym_hist_kernel, dim3((unsigned)(B < 1024 ? B : 1024)), dim3(256), 0, STREAM, sym, B, Lwin, col0, L1, counts);
   hipLaunchKernelGGL(first_tables_kernel, dim3(1), dim3(256), 0, STREAM, counts, C, gamma, beta, W, bias, eps, momentum,
                      running_mean, running_var, tab, fast ? 1 : 0);
@@ -1310,7 +1313,6 @@ static int first_fwd_impl(const uint8_t* sym, int64_t B, int32_t Lwin, int32_t c
     a.stat = cl ? stat : nullptr;
     return launch_first_train(a, false, STREAM);
   }
-  MURAL_REQUIRE(!cl, "first layer: the channel-last layout is served by the table kernels only");
   const int64_t total = B * C * L2;
   hipLaunchKernelGGL(first_pool_fwd_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), (size_t)3 * N_SYM * C * 4, STREAM, sym,
                      B, Lwin, col0, L1, C, L2, pk, ps, pp, tab, bias, y, static_cast<int32_t*>(arg));

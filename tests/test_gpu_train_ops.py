@@ -25,57 +25,9 @@ import torch.nn.functional as F
 
 from mural_amd import _lib
 from mural_amd.model import train_ops as T
+from tests._parity import EPS, MOMENTUM, NAN, _Stats, _loose, _sum_check
 
 pytestmark = pytest.mark.gpu
-
-U24 = 2.0 ** -24
-NAN = float("nan")
-EPS, MOMENTUM = 1e-5, 0.1
-
-
-class _Stats:
-    """worst case (kernel error / bound) per checked output, printed at the end of a test"""
-
-    def __init__(self, test):
-        self.test, self.rows = test, {}
-
-    def add(self, what, ref_err, err, bound, case):
-        ratio = err / bound if bound > 0 else (0.0 if err == 0 else math.inf)
-        old = self.rows.get(what)
-        if old is None or ratio >= old[0]:
-            self.rows[what] = (ratio, ref_err, err, bound, case)
-
-    def show(self):
-        for what, (ratio, ref_err, err, bound, case) in self.rows.items():
-            ref = "      n/a" if ref_err is None else f"{ref_err:9.3e}"
-            print(f"[train_ops] {self.test:12s} {what:18s} torch-f32 err {ref}  kernel err {err:9.3e}  bound {bound:9.3e}  at {case}")
-
-
-def _ulp4(want):
-    return 4.0 * float(np.spacing(np.float32(float(want.abs().max()))))
-
-
-def _loose(got, want64, ref32, what, case, stats, other=None):
-    """got within 8 x (torch float32's distance from float64), at least 4 ulp, of float64; or, with ``other``, of that second result"""
-    ref_err = float((ref32.detach().double() - want64).abs().max())
-    err = float((got.detach().double().cpu() - (want64 if other is None else other.detach().double().cpu())).abs().max())
-    bound = max(8.0 * ref_err, _ulp4(want64))
-    stats.add(what, ref_err, err, bound, case)
-    assert err <= bound, f"{what} at {case}: kernel is {err:.3e} from {'float64' if other is None else 'its other result'}, " \
-                         f"allowed {bound:.3e} (torch float32: {ref_err:.3e})"
-
-
-def _sum_check(got, want64, S, n, what, case, stats):
-    """|got - want| <= 2 (n + 2) 2^-24 S element by element; n: number of terms (a number or a tensor shaped like want)"""
-    bound = 2.0 * (torch.as_tensor(n, dtype=torch.float64) + 2.0) * U24 * S
-    err = (got.detach().double().cpu() - want64).abs()
-    bound = bound.expand_as(err)
-    ok = err <= bound                                    # (a NaN is not ok)
-    ratio = torch.where(bound > 0, err / bound, torch.where(err == 0, 0.0, math.inf))      # (reported: the element nearest its bound)
-    worst = int(torch.argmax(torch.nan_to_num(ratio, nan=math.inf).flatten()))
-    e, b = float(err.flatten()[worst]), float(bound.flatten()[worst])
-    stats.add(what, None, e, b, case)
-    assert bool(ok.all()), f"{what} at {case}: {int((~ok).sum())} of {err.numel()} elements beyond the summation bound, worst {e:.3e} > {b:.3e}"
 
 
 def _cuda(t):
