@@ -88,14 +88,39 @@ int mural_encode_symbols(const MuralGenome* g, const int64_t* pos, const uint8_t
  * mural_sites_count leaves tile_counts[t] = sites before tile t, tile_counts[tiles] = *total = all sites of the window (dev int64
  * [mural_sites_tiles(length, lo, hi) + 1] and dev int64 [1]); mural_sites_emit, given the same window and selection and those
  * offsets, writes the sites number first .. first + n - 1 of the enumeration (the caller keeps first + n <= total) to pos / strand
- * (dev, n entries each).  Deterministic: no atomics.                                                                              */
-enum { MURAL_FOCAL_A = 0, MURAL_FOCAL_C = 1, MURAL_FOCAL_ANY = 2 };
+ * (dev, n entries each).  Deterministic: no atomics.
+ *   focal SET: the union of site classes whose MURAL_CLASS_* bits `context` carries (1..7): class A = the sites of focal A, NONCPG /
+ *              CPG = those of focal C with that context.  Strand as above (0 for A / C, 1 for T / G), one ascending enumeration --
+ *              the rows of a run that serves one model per class (mural_sites_classify).  ANY is NOT the union of all three: it puts
+ *              every base on '+'.                                                                                                  */
+enum { MURAL_FOCAL_A = 0, MURAL_FOCAL_C = 1, MURAL_FOCAL_ANY = 2, MURAL_FOCAL_SET = 3 };
+enum { MURAL_CLASS_A = 1, MURAL_CLASS_NONCPG = 2, MURAL_CLASS_CPG = 4 };
 enum { MURAL_CONTEXT_ALL = 0, MURAL_CONTEXT_CPG = 1, MURAL_CONTEXT_NONCPG = 2 };
 int64_t mural_sites_tiles(int64_t length, int64_t lo, int64_t hi);
 int mural_sites_count(const MuralGenome* g, int64_t lo, int64_t hi, int32_t focal, int32_t context, int64_t* tile_counts,
                       int64_t* total, void* stream);
 int mural_sites_emit(const MuralGenome* g, int64_t lo, int64_t hi, int32_t focal, int32_t context, const int64_t* tile_counts,
                      int64_t first, int64_t n, int64_t* pos, uint8_t* strand, void* stream);
+
+/* Rows of several site classes in one call (csrc/sites.hip): which model of a set a row belongs to, the rows of each class, and the
+ * members' outputs back in row order.  Plain loads and stores, no atomics: every result is a function of the inputs alone.
+ *   mural_sites_classify: cls[i] (dev uint8 [n]) = MURAL_ROW_CLASS_A / _NONCPG / _CPG of the site (pos[i], strand[i]) by the rules of
+ *     the enumeration above, MURAL_ROW_CLASS_NONE for a position outside the record, a masked base (N, IUPAC) or a strand that is not
+ *     the base's (0 for A / C, 1 for T / G; any other value included).  n == 0 launches nothing.
+ *   mural_rows_split: the stable partition of the row indices 0 .. n-1 by a class column (dev uint8 [n]).  perm (dev int64 [n]) lists
+ *     every row of class 0 in ascending row order, then class 1, .. class n_classes - 1 (1 <= n_classes <= 8); counts (dev int64
+ *     [n_classes + 1]): counts[c] = rows of class c, counts[n_classes] = rows of a class >= n_classes, which are left out of perm (its
+ *     last counts[n_classes] entries are not written).  workspace: dev, mural_rows_split_workspace_bytes(n, n_classes) bytes (0 for
+ *     bad arguments), MURAL_E_WORKSPACE when smaller.  n == 0 zeroes counts and reads no other pointer.
+ *   mural_rows_scatter: dst[perm[j]][:] = src[j][:] for j < m; rows of `cols` elements of elem_bytes 4 or 8 (float / double), dst of
+ *     dst_rows rows; a perm entry outside [0, dst_rows) is skipped.  perm entries are distinct (a slice of mural_rows_split's).      */
+enum { MURAL_ROW_CLASS_A = 0, MURAL_ROW_CLASS_NONCPG = 1, MURAL_ROW_CLASS_CPG = 2, MURAL_ROW_CLASS_NONE = 255 };
+int mural_sites_classify(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n, uint8_t* cls, void* stream);
+size_t mural_rows_split_workspace_bytes(int64_t n, int32_t n_classes);
+int mural_rows_split(const uint8_t* cls, int64_t n, int32_t n_classes, int64_t* perm, int64_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int mural_rows_scatter(const void* src, const int64_t* perm, int64_t m, int32_t cols, int32_t elem_bytes, void* dst, int64_t dst_rows,
+                       void* stream);
 
 /* Observed mutations joined to enumerated sites (csrc/sites.hip): the label column of a regions run.  pos / strand: what
  * mural_sites_emit wrote (dev, n entries, pos ascending).  mut_start / mut_strand / mut_label: ONE chromosome's list of observed

@@ -194,6 +194,10 @@ PROTOTYPES = {
     "mural_sites_count": (C.c_int, [C.POINTER(MuralGenome), I64, I64, I32, I32, VP, VP, VP]),
     "mural_sites_emit": (C.c_int, [C.POINTER(MuralGenome), I64, I64, I32, I32, VP, I64, I64, VP, VP, VP]),
     "mural_sites_label": (C.c_int, [VP, VP, I64, VP, VP, VP, I64, I32, VP, VP, VP]),
+    "mural_sites_classify": (C.c_int, [C.POINTER(MuralGenome), VP, VP, I64, VP, VP]),
+    "mural_rows_split_workspace_bytes": (C.c_size_t, [I64, I32]),
+    "mural_rows_split": (C.c_int, [VP, I64, I32, VP, VP, VP, C.c_size_t, VP]),
+    "mural_rows_scatter": (C.c_int, [VP, VP, I64, I32, I32, VP, I64, VP]),
     "mural_snv_model_create": (C.c_int, [C.POINTER(MuralSnvShape), C.POINTER(MuralSnvParams), C.POINTER(C.c_void_p)]),
     "mural_snv_model_destroy": (None, [C.c_void_p]),
     "mural_snv_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32]),

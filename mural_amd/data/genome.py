@@ -46,12 +46,44 @@ _FOCAL = {"A": 0, "C": 1, "ANY": 2}                    # MURAL_FOCAL_* of includ
 _CONTEXT = {"all": 0, "cpg": 1, "noncpg": 2}           # MURAL_CONTEXT_*
 
 
-def site_selection(focal, context="all"):
+FOCAL_SET = 3                                          # MURAL_FOCAL_SET: the second selector is a union of MURAL_CLASS_* bits
+SITE_CLASSES = {"A": 1, "nonCpG": 2, "CpG": 4, "C": 6}     # MURAL_CLASS_*; 'C' = nonCpG | CpG
+ROW_CLASSES = ("A", "nonCpG", "CpG")                   # MURAL_ROW_CLASS_*: what classify_sites writes (255: none of them)
+
+
+def class_mask(classes):
+    """The MURAL_CLASS_* mask (1..7) of a union of site classes: names of SITE_CLASSES (one, or an iterable of them) or the mask itself.
+    Raises ValueError for an unknown name and for an empty union."""
+    if isinstance(classes, (int, np.integer)) and not isinstance(classes, bool):
+        mask = int(classes)
+        if not 1 <= mask <= 7:
+            raise ValueError(f"classes: a mask is a non-empty union of A = 1, nonCpG = 2, CpG = 4 (1..7), got {mask}")
+        return mask
+    if classes is None or isinstance(classes, bool) or not (isinstance(classes, str) or hasattr(classes, "__iter__")):
+        raise ValueError(f"focal 'SET' needs classes=: names of 'A', 'C', 'nonCpG', 'CpG' or their mask (1..7), got {classes!r}")
+    mask = 0
+    for name in ([classes] if isinstance(classes, str) else list(classes)):
+        if not isinstance(name, str) or name not in SITE_CLASSES:
+            raise ValueError(f"classes: unknown site class {name!r} (one of 'A', 'C', 'nonCpG', 'CpG')")
+        mask |= SITE_CLASSES[name]
+    if mask == 0:
+        raise ValueError("classes: an empty union selects no site")
+    return mask
+
+
+def site_selection(focal, context="all", classes=None):
     """(MURAL_FOCAL_*, MURAL_CONTEXT_*) of a site selection: focal 'A' (A/T sites), 'C' (C/G sites) or 'ANY' (every A/C/G/T position,
-    INDEL models); context 'all', 'CpG' or 'nonCpG' (any case; focal 'C' only).  Raises ValueError."""
+    INDEL models); context 'all', 'CpG' or 'nonCpG' (any case; focal 'C' only).  focal 'SET': the union of the site classes `classes`
+    names (``class_mask``), as (MURAL_FOCAL_SET, the mask); it takes no context.  Raises ValueError."""
+    if str(focal).upper() == "SET":
+        if str(context).lower() != "all":
+            raise ValueError(f"focal 'SET' takes classes=, not a context (got context {context!r})")
+        return FOCAL_SET, class_mask(classes)
+    if classes is not None:
+        raise ValueError(f"classes= goes with focal 'SET' (got focal {focal!r})")
     f, c = _FOCAL.get(str(focal).upper()), _CONTEXT.get(str(context).lower())
     if f is None:
-        raise ValueError(f"focal must be 'A', 'C' or 'ANY', got {focal!r}")
+        raise ValueError(f"focal must be 'A', 'C', 'ANY' or 'SET', got {focal!r}")
     if c is None:
         raise ValueError(f"context must be 'all', 'CpG' or 'nonCpG', got {context!r}")
     if c != 0 and f != 1:
@@ -234,10 +266,10 @@ class PackedGenome:
 
     # ------------------------------------------------------------------------------------------------
     # site enumeration (csrc/sites.hip): the sites of a window straight from the resident genome, no BED file
-    def scan_sites(self, lo, hi, focal, context="all"):
+    def scan_sites(self, lo, hi, focal, context="all", classes=None):
         """Count the sites of the window [lo, hi) (0-based half-open, clamped to the record) on the device: a ``SiteScan`` for
         ``emit_sites``.  Nothing is read back."""
-        f, c = site_selection(focal, context)
+        f, c = site_selection(focal, context, classes)
         lo, hi = int(lo), int(hi)
         lib = _lib.lib()
         tiles = int(lib.mural_sites_tiles(self.length, lo, hi))
@@ -265,18 +297,65 @@ class PackedGenome:
                                                   first, n, pos.data_ptr(), strand.data_ptr(), _lib.current_stream_ptr(self.device)))
         return pos, strand
 
-    def count_sites(self, lo, hi, focal, context="all"):
+    def count_sites(self, lo, hi, focal, context="all", classes=None):
         """Number of sites ``enumerate_sites`` yields for the window."""
-        return self.scan_sites(lo, hi, focal, context).total
+        return self.scan_sites(lo, hi, focal, context, classes).total
 
-    def enumerate_sites(self, lo, hi, focal, context="all", first=0, n=None):
+    def enumerate_sites(self, lo, hi, focal, context="all", first=0, n=None, classes=None):
         """The sites of the window [lo, hi) of the record (0-based half-open like a BED row, clamped to the record) in ascending
         position order: (pos int64, strand uint8) device tensors in the coordinate the encoders and the packed forwards take for a
         BED row (p, p + 1).  focal 'A': A ('+', 0) and T ('-', 1); 'C': C ('+') and G ('-'), with context 'CpG' / 'nonCpG' decided by
-        the next ('+') or previous ('-') base of the record; 'ANY': every A/C/G/T position on '+'.  N and IUPAC codes are never sites.
-        `first` / `n`: a contiguous slice of the enumeration (clamped to it; n=None: to its end)."""
-        scan = self.scan_sites(lo, hi, focal, context)
+        the next ('+') or previous ('-') base of the record; 'ANY': every A/C/G/T position on '+'; 'SET': the sites of every class that
+        `classes` names ('A', 'C', 'nonCpG', 'CpG', or their mask), each on its own strand, in one ascending enumeration.  N and IUPAC
+        codes are never sites.  `first` / `n`: a contiguous slice of the enumeration (clamped to it; n=None: to its end)."""
+        scan = self.scan_sites(lo, hi, focal, context, classes)
         first = max(int(first), 0)
         left = max(scan.total - first, 0)
         n = left if n is None else min(max(int(n), 0), left)
         return self.emit_sites(scan, first, n)
+
+    def classify_sites(self, pos, strand):
+        """uint8 device tensor, one entry per (pos, strand) row: the index in ROW_CLASSES of the site's class (0 'A', 1 'nonCpG', 2
+        'CpG', by the rules of ``enumerate_sites``), 255 for a position outside the record, an N or IUPAC base, or a strand that is
+        not the base's.  Nothing is read back."""
+        pos, strand = self._prep(pos, strand)
+        cls = torch.empty(pos.shape[0], dtype=torch.uint8, device=self.device)
+        g = self.as_struct()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mural_sites_classify(C.byref(g), pos.data_ptr(), strand.data_ptr(), pos.shape[0], cls.data_ptr(),
+                                                      _lib.current_stream_ptr(self.device)))
+        return cls
+
+
+def split_rows(cls, n_classes):
+    """Stable partition of the rows 0 .. n-1 by a uint8 class column on the device (``mural_rows_split``): (perm int64 [n], counts
+    int64 [n_classes + 1]) device tensors.  perm lists the rows of class 0 in ascending order, then class 1, ..; counts[c] are the
+    class sizes, counts[n_classes] the rows of a class >= n_classes, which perm leaves out (its last counts[n_classes] entries are
+    not written).  No atomics: the same bytes for the same column.  Nothing is read back."""
+    if not cls.is_cuda or cls.dtype != torch.uint8 or cls.dim() != 1 or not cls.is_contiguous():
+        raise ValueError("split_rows: cls must be a contiguous 1-D uint8 tensor on a HIP device")
+    n, k = cls.shape[0], int(n_classes)
+    lib = _lib.lib()
+    perm = torch.empty(n, dtype=torch.int64, device=cls.device)
+    counts = torch.empty(k + 1, dtype=torch.int64, device=cls.device)
+    ws_bytes = int(lib.mural_rows_split_workspace_bytes(n, k))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=cls.device)
+    with torch.cuda.device(cls.device):
+        _lib.check(lib.mural_rows_split(cls.data_ptr(), n, k, perm.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws_bytes,
+                                        _lib.current_stream_ptr(cls.device)))
+    return perm, counts
+
+
+def scatter_rows(src, perm, dst):
+    """dst[perm[j], :] = src[j, :] on the device (``mural_rows_scatter``): `src` (m, cols) and `dst` (rows, cols) contiguous float32 or
+    float64 tensors of one dtype, `perm` m distinct int64 row numbers of dst (a contiguous slice of ``split_rows``' perm).  Returns dst."""
+    if (not src.is_cuda or src.device != dst.device or perm.device != src.device or src.dtype != dst.dtype
+            or src.dtype not in (torch.float32, torch.float64) or perm.dtype != torch.int64 or src.dim() != 2 or dst.dim() != 2
+            or perm.dim() != 1 or src.shape[1] != dst.shape[1] or src.shape[1] < 1 or perm.shape[0] != src.shape[0]
+            or not (src.is_contiguous() and dst.is_contiguous() and perm.is_contiguous())):
+        raise ValueError("scatter_rows: src (m, cols) / dst (rows, cols) must be contiguous float32 or float64 tensors of one dtype on "
+                         "one HIP device, perm m contiguous int64 entries")
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().mural_rows_scatter(src.data_ptr(), perm.data_ptr(), src.shape[0], src.shape[1], src.element_size(),
+                                                dst.data_ptr(), dst.shape[0], _lib.current_stream_ptr(src.device)))
+    return dst

@@ -183,41 +183,34 @@ def check_focal_groups(focal, group):
         raise ValueError(_FOCAL_MSG)
 
 
-class HipShardForward:
-    """Default compute of predict_bed_sharded: packs the shard's chromosome from the FASTA file (C++ packer; the next one on a
-    host thread while this one is computed), keeps exactly one chromosome resident, runs the fused packed-genome forward and
-    returns softmax probabilities with the focal base appended as the last column."""
+class FastaGenomes:
+    """The chromosomes of a FASTA file on a HIP device, one at a time: packed from the file (C++ packer; the next one on a host thread
+    while this one is in use) and uploaded by genome(chrom), which drops the previous one.  A `genome_from` (anything with records /
+    prefetch / genome) takes over all three: this object then neither reads the file nor packs or uploads anything."""
 
-    REUSE_MIN_DENSITY = 0.1        # sites per base of a chunk's span above which the cross-position reuse path pays (DESIGN.md 3c)
-
-    def __init__(self, model, fasta_path, local_radius, local_order=3, distal_radius=None, device="cuda", batch_sites=1 << 20,
-                 model_type="snv", dirichlet_weights=None, poisson=None, scale_factor=None, reuse=True):
-        """`dirichlet_weights` / `poisson` / `scale_factor`: apply the post-head calibration chain of run_predict.py:217-225
-        (and scripts/scaling.py) on the device, fused behind the head (calibration.calibrate_device); the shard then carries
-        float64 calibrated probabilities and the sink must not calibrate again.  `poisson=None` follows the reference's rule
-        (run_predict.py:224: `poisson_calib or model_type == 'indel'`): on for indel models, off for snv.  `reuse`: let dense blocks of sites take the
-        cross-position reuse kernels (same probabilities within rounding, tests/test_gpu_reuse.py)."""
+    def _init_genomes(self, fasta_path, device, genome_from=None):
         from .data import ingest
-        if poisson is None:
-            poisson = model_type == "indel"
-        self.calibration = dict(dirichlet_weights=dirichlet_weights, poisson=poisson, scale_factor=scale_factor)
-        self.calibrated = dirichlet_weights is not None or bool(poisson) or bool(scale_factor)
         self._ingest = ingest
-        self.model = model.to(device).eval()
         self.fasta_path, self.device = fasta_path, torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.local_radius, self.local_order, self.distal_radius = local_radius, local_order, distal_radius
-        self.batch_sites, self.model_type, self.reuse = batch_sites, model_type, bool(reuse) and model_type == "snv"
-        # the FASTA index (record offsets: one pass over the file) is built on a host thread -- the C++ scanner releases the GIL --
-        # so the driver reads the BED beside it; `records` joins
+        self.genome_from = genome_from
         self._records, self._scan_error, self._early = None, None, None
-        self._scan = threading.Thread(target=self._scan_fasta, daemon=True)
-        self._scan.start()
+        self._scan = None
+        if genome_from is None and fasta_path is not None:
+            # the FASTA index (record offsets: one pass over the file) is built on a host thread -- the C++ scanner releases the GIL --
+            # so the driver reads the BED beside it; `records` joins
+            self._scan = threading.Thread(target=self._scan_fasta, daemon=True)
+            self._scan.start()
         self._resident = (None, None)
         self._prefetch = None          # (chrom, thread, result box)
         self.seconds = {"pack_wait": 0.0, "pack": 0.0}
-        self.reuse_sites = 0           # sites that went through the reuse kernels (diagnostics / tests)
+
+    def _source(self):
+        if self.genome_from is None and self._scan is None:
+            raise RuntimeError("this forward was built without a FASTA file (fasta_path=None): it takes its chromosomes from the "
+                               "ModelSetForward it becomes a member of, or from genome_from=")
+        return self.genome_from
 
     def _scan_fasta(self):
         try:
@@ -240,6 +233,8 @@ class HipShardForward:
 
     @property
     def records(self):
+        if self._source() is not None:
+            return self.genome_from.records
         self._scan.join()      # a finished thread joins at once; safe from the packer thread as well
         if self._scan_error is not None:
             raise self._scan_error
@@ -256,6 +251,8 @@ class HipShardForward:
 
     def prefetch(self, chrom):
         """Start packing `chrom` on a host thread (the C++ packer releases the GIL); genome(chrom) picks the result up."""
+        if self._source() is not None:
+            return self.genome_from.prefetch(chrom)
         if chrom is None or chrom not in self.records or self._resident[0] == chrom:
             return
         if self._prefetch is not None and self._prefetch[0] == chrom:
@@ -268,6 +265,8 @@ class HipShardForward:
         self._prefetch = (chrom, th, box)
 
     def genome(self, chrom):
+        if self._source() is not None:
+            return self.genome_from.genome(chrom)
         if self._resident[0] != chrom:
             self._resident = (None, None)              # drop the previous chromosome before the next one is uploaded
             if chrom not in self.records:
@@ -291,6 +290,33 @@ class HipShardForward:
             self._resident = (chrom, PackedGenome(packed, mask, n, self.device, amb))
             self._early = None                         # an unused early pack is dropped with the first resident chromosome
         return self._resident[1]
+
+
+class HipShardForward(FastaGenomes):
+    """Default compute of predict_bed_sharded: packs the shard's chromosome from the FASTA file (C++ packer; the next one on a
+    host thread while this one is computed), keeps exactly one chromosome resident, runs the fused packed-genome forward and
+    returns softmax probabilities with the focal base appended as the last column."""
+
+    REUSE_MIN_DENSITY = 0.1        # sites per base of a chunk's span above which the cross-position reuse path pays (DESIGN.md 3c)
+
+    def __init__(self, model, fasta_path, local_radius, local_order=3, distal_radius=None, device="cuda", batch_sites=1 << 20,
+                 model_type="snv", dirichlet_weights=None, poisson=None, scale_factor=None, reuse=True, genome_from=None):
+        """`dirichlet_weights` / `poisson` / `scale_factor`: apply the post-head calibration chain of run_predict.py:217-225
+        (and scripts/scaling.py) on the device, fused behind the head (calibration.calibrate_device); the shard then carries
+        float64 calibrated probabilities and the sink must not calibrate again.  `poisson=None` follows the reference's rule
+        (run_predict.py:224: `poisson_calib or model_type == 'indel'`): on for indel models, off for snv.  `reuse`: let dense blocks of sites take the
+        cross-position reuse kernels (same probabilities within rounding, tests/test_gpu_reuse.py).  `genome_from`: another forward
+        (or a FastaGenomes) whose resident chromosome this one computes on instead of packing and uploading its own; `fasta_path`
+        may then be None.  With fasta_path=None and no genome_from the forward is a member for a ModelSetForward, which binds it."""
+        if poisson is None:
+            poisson = model_type == "indel"
+        self.calibration = dict(dirichlet_weights=dirichlet_weights, poisson=poisson, scale_factor=scale_factor)
+        self.calibrated = dirichlet_weights is not None or bool(poisson) or bool(scale_factor)
+        self.model = model.to(device).eval()
+        self.local_radius, self.local_order, self.distal_radius = local_radius, local_order, distal_radius
+        self.batch_sites, self.model_type, self.reuse = batch_sites, model_type, bool(reuse) and model_type == "snv"
+        self._init_genomes(fasta_path, device, genome_from)
+        self.reuse_sites = 0           # sites that went through the reuse kernels (diagnostics / tests)
 
     # -- compute ----------------------------------------------------------------------------------------------------------
     def _to_device(self, a, dtype):
@@ -334,6 +360,96 @@ class HipShardForward:
             out[r0:r0 + m, :-1] = calibrate_device(logp, **self.calibration)
         else:
             out[r0:r0 + m, :-1] = torch.softmax(logp, dim=1)
+
+
+class ModelSetForward(FastaGenomes):
+    """One forward for the rows of several site classes, each class served by its own model: the compute of a regions run over a
+    union of classes (predict_regions_sharded, focal "SET").  `members`: {class: HipShardForward} with keys from 'A' (A/T sites),
+    'nonCpG', 'CpG' and 'C' (= nonCpG and CpG through one model; not together with either).  Radii, weights, calibrators,
+    scale_factor and reuse are each member's own; device, model_type 'snv', n_class and "calibrated or not" (the rows' dtype) must
+    agree.
+
+    The set alone packs and uploads a chromosome (FastaGenomes, `fasta_path`: by default the first member's); every member is bound
+    to it and computes on that resident copy -- build the members with fasta_path=None and they never read the file.  A call
+    classifies its rows on the device (PackedGenome.classify_sites), partitions them stably by member (data.genome.split_rows),
+    gives every member its rows in ascending order and scatters the members' outputs into one (rows, n_class + 1) tensor
+    (data.genome.scatter_rows).  The class counts are the one host read-back per call: they size the members' outputs."""
+
+    KEYS = ("A", "C", "nonCpG", "CpG")
+
+    def __init__(self, members, fasta_path=None):
+        from .data.genome import ROW_CLASSES, SITE_CLASSES
+        members = dict(members)
+        unknown = [k for k in members if k not in self.KEYS]
+        if unknown:
+            raise ValueError(f"ModelSetForward: unknown site class {unknown[0]!r} (the keys are 'A', 'C', 'nonCpG', 'CpG')")
+        if not members:
+            raise ValueError("ModelSetForward: no member (at least one of 'A', 'C', 'nonCpG', 'CpG')")
+        if "C" in members and ("CpG" in members or "nonCpG" in members):
+            raise ValueError("ModelSetForward: 'C' serves the CpG and the nonCpG sites: it does not go with a 'CpG' or 'nonCpG' member")
+        self.names = [k for k in self.KEYS if k in members]                    # member order: the order of `perm`'s blocks
+        self.members = [members[k] for k in self.names]
+        for k, m in zip(self.names, self.members):
+            if not isinstance(m, HipShardForward):
+                raise ValueError(f"ModelSetForward: member {k!r} is no HipShardForward")
+        first = self.members[0]
+        for k, m in zip(self.names[1:], self.members[1:]):
+            for what, a, b in (("device", first.device, m.device), ("n_class", first.model.n_class, m.model.n_class),
+                               ("calibrated", first.calibrated, m.calibrated)):
+                if a != b:
+                    raise ValueError(f"ModelSetForward: members {self.names[0]!r} and {k!r} differ in {what}: {a} and {b} "
+                                     + ("(every member calibrated behind its head, or none)" if what == "calibrated" else ""))
+        for k, m in zip(self.names, self.members):
+            if m.model_type != "snv":
+                raise ValueError(f"ModelSetForward: member {k!r} has model_type {m.model_type!r}: the site classes are the SNV models'")
+        if fasta_path is None:
+            fasta_path = next((m.fasta_path for m in self.members if m.fasta_path is not None), None)
+        if fasta_path is None:
+            raise ValueError("ModelSetForward: no FASTA file (fasta_path=, or a member built with one)")
+        self.classes = 0
+        slot = np.full(256, 255, np.uint8)                                     # row class -> member number
+        for j, k in enumerate(self.names):
+            self.classes |= SITE_CLASSES[k]
+            for c, name in enumerate(ROW_CLASSES):
+                if SITE_CLASSES[name] & SITE_CLASSES[k]:
+                    slot[c] = j
+        self.model, self.calibrated, self.model_type = first.model, first.calibrated, "snv"
+        self._init_genomes(fasta_path, first.device)
+        self._slot = torch.from_numpy(slot).to(self.device)
+        for m in self.members:
+            m.genome_from = self
+
+    @property
+    def reuse_sites(self):
+        return sum(m.reuse_sites for m in self.members)
+
+    @torch.no_grad()
+    def __call__(self, chrom, pos, strand):
+        """(rows, n_class + 1) for sites of `chrom`, every row by the member of its class.  A row that belongs to no member (an N, a
+        position outside the record, the wrong strand, a class the set lacks) raises ValueError."""
+        from .data.genome import scatter_rows, split_rows
+        g = self.genome(chrom)
+        pos, strand = g._prep(pos, strand)
+        n, k = pos.shape[0], self.model.n_class
+        out = torch.empty((n, k + 1), dtype=torch.float64 if self.calibrated else torch.float32, device=self.device)
+        if n == 0:
+            return out
+        with torch.cuda.device(self.device):
+            slot = self._slot[g.classify_sites(pos, strand).long()]
+            perm, counts = split_rows(slot, len(self.members))
+            counts = counts.tolist()                                           # the one read-back: the members' outputs must be sized
+            if counts[-1]:
+                i = int(torch.nonzero(slot == 255)[0])
+                raise ValueError(f"ModelSetForward: {chrom}:{int(pos[i])} on strand '{'+-'[int(strand[i]) & 1]}' is a site of no member "
+                                 f"({', '.join(self.names)}): an N or ambiguous base, a position outside the record, the other strand's "
+                                 f"base or a class the set has no model for ({counts[-1]} such rows)")
+            a = 0
+            for m, rows in zip(self.members, counts):
+                if rows:
+                    idx = perm[a:a + rows]
+                    scatter_rows(m(chrom, pos[idx], strand[idx]), idx, out)
+                a += rows
+        return out
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -2230,8 +2346,9 @@ class _RegionSites:
     check_focal = reorder = False
     read_key = "enumerate"
 
-    def __init__(self, forward, regions, focal, context, dev, T, mutations=None, check_strand=False):
+    def __init__(self, forward, regions, focal, context, dev, T, mutations=None, check_strand=False, classes=None):
         self.forward, self.regions, self.focal, self.context, self.dev, self.T = forward, regions, focal, context, dev, T
+        self.classes = classes                             # focal "SET": the union of site classes that is enumerated
         self.names = sorted(regions)
         self.mutations, self.check_strand = None if mutations is None else mutations_for_regions(mutations, regions), check_strand
         self.in_regions = self.matched = 0
@@ -2242,7 +2359,7 @@ class _RegionSites:
     def open(self, chrom, fetch_next):
         self.g = g = self.forward.genome(chrom)            # (KeyError for a chromosome the FASTA lacks, like the BED path)
         t0 = time.perf_counter()
-        self.scans = [g.scan_sites(lo, hi, self.focal, self.context) for lo, hi in self.regions[chrom]]
+        self.scans = [g.scan_sites(lo, hi, self.focal, self.context, self.classes) for lo, hi in self.regions[chrom]]
         fetch_next()                                       # right behind the enqueued scans, before the host waits for their totals
         self.muts = self.stats = None
         if self.mutations is not None:
@@ -2312,6 +2429,10 @@ def predict_regions_sharded(forward, regions, focal, context="all", model_type="
     `emulate` and return value as predict_bed_sharded; rows carry end = start + 1 and label 0 (`mutations`: below).  With `collect` the returned rows are in the
     table's order -- ascending chromosome name, then start: there is no input file whose order could be kept -- and `order` counts them.
 
+    focal 'SET' goes with a ModelSetForward (and only with one): the sites of every class the set has a member for, in one ascending
+    enumeration, every row computed by the model of its class -- one table of the rate at every selected base, its prob columns the
+    substitutions of the row's own base (which strand and genome determine).  One `mutations` list serves all members.
+
     Chromosomes go in ascending name order, the next one is packed while this one is computed.  Per chromosome the regions are counted
     on the device (one read-back of the totals), rank i of N takes the slice shard_bounds(sites of the chromosome, i, N) of the
     enumeration and emits it in parts of at most _ALIGNED_PART_ROWS sites.  The enumeration ascends, so with a consumer of aligned
@@ -2332,7 +2453,15 @@ def predict_regions_sharded(forward, regions, focal, context="all", model_type="
     emulated rank (`emulate=`) reports the matches of ITS slice alone, so `unmatched` means nothing there and `strict_mutations` is
     refused.  timings['label'] are the host seconds spent enqueueing the lookups (without `mutations` neither key appears)."""
     from .data.genome import site_selection
-    f_code, _ = site_selection(focal, context)
+    classes = None
+    if str(focal).upper() == "SET":
+        if not isinstance(forward, ModelSetForward):
+            raise ValueError("focal 'SET' enumerates the site classes of a ModelSetForward: this forward serves one model, name its "
+                             "selection (focal 'A' / 'C' with a context, 'ANY')")
+        classes = forward.classes
+    elif isinstance(forward, ModelSetForward):
+        raise ValueError(f"a ModelSetForward serves the union of its members' site classes: focal 'SET', not {focal!r}")
+    f_code, _ = site_selection(focal, context, classes)
     if model_type not in ("snv", "indel"):
         raise ValueError(f"model_type {model_type} not supported!")
     if (f_code == 2) != (model_type == "indel"):
@@ -2353,7 +2482,7 @@ def predict_regions_sharded(forward, regions, focal, context="all", model_type="
     if mutations is not None and not isinstance(mutations, dict):
         from .data.ingest import read_mutations
         mutations = read_mutations(mutations, getattr(getattr(forward, "model", None), "n_class", None))
-    src = _RegionSites(forward, regions, focal, context, dev, T, mutations, check_strand=f_code != 2)
+    src = _RegionSites(forward, regions, focal, context, dev, T, mutations, check_strand=f_code != 2, classes=classes)
     emulated = emulate is not None
     return _predict_shards(forward, src, 0, model_type, group, sink, collect, T, rank, world, emulated,
                            finish=lambda: src.finish(group, world, emulated, strict_mutations))

@@ -10,6 +10,13 @@ position is a site and --focal / --context do not apply).
                         table (and every summary) of a BED with one row per site, without writing that BED
   --strict_mutations    fail when a listed mutation inside the regions lies on no enumerated site (by default they are only counted)
 
+One table from one model per site class (mural_amd.predict.ModelSetForward) -- no MODEL argument, every row by the model of its own base:
+  python tools/predict_files.py FASTA OUT.tsv --regions SPEC --model_set CLASS=MODEL_PATH [CLASS=MODEL_PATH ..]
+                                [--scale_factors CLASS=F ..] [--mutations FILE] [--no-calibration]
+CLASS: A, nonCpG, CpG, or C (= nonCpG and CpG by one model).  Each model directory brings its own .config.pkl and, if present, its
+.fdiri_cal.pkl; every model is calibrated / scaled behind its own head, so all of them are or none is.  prob1..3 of a row are the
+substitutions of that row's own base (the strand column and the genome say which).  Not with --summary, --focal / --context, --indel.
+
 Genome summaries in flight, in both forms (mural_amd.predict.SummarySink; the numbers `calc_scaling_factor` and `evaluate --window_size`
 read back from the table, taken from the probabilities before they are rounded):
   --summary PREFIX  --window_size W [--window_size W ..]   PREFIX.{W/1000}Kb.mut_rates.tsv and .corr.txt per window size
@@ -34,7 +41,8 @@ from mural_amd.model.nn_utils import load_model  # noqa: E402
 
 _SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
                     "--scale_factor")
-_VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _SUMMARY_OPTIONS
+_PAIR_OPTIONS = ("--model_set", "--scale_factors")      # NAME CLASS=VALUE [CLASS=VALUE ..]
+_VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _PAIR_OPTIONS + _SUMMARY_OPTIONS
 
 
 def _split(argv):
@@ -55,6 +63,9 @@ def _split(argv):
             while name == "--motif_length" and at + 1 < len(argv) and argv[at + 1].lstrip("-").isdigit():      # M [M ..]
                 at = next(it)
                 values[name].append(argv[at])
+            while name in _PAIR_OPTIONS and at + 1 < len(argv) and "=" in argv[at + 1] and not argv[at + 1].startswith("--"):
+                at = next(it)
+                values[name].append(argv[at])
         elif a.startswith("--"):
             flags.add(a)
         else:
@@ -67,6 +78,8 @@ def main(argv):
     model_type = "indel" if "--indel" in flags else "snv"
     poisson = "--poisson" in flags or model_type == "indel"
     opts = _summary_options(flags, values, model_type)
+    if "--model_set" in values or "--scale_factors" in values:
+        return _main_model_set(args, values, flags, model_type, poisson, opts)
     if ("--mutations" in values or "--strict_mutations" in flags) and "--regions" not in values:
         raise SystemExit("--mutations / --strict_mutations label the sites that --regions enumerates: a BED run takes its labels from "
                          "the BED's score column")
@@ -215,6 +228,84 @@ def _main_regions(args, values, flags, model_type, poisson, opts):
                               model_type=model_type, poisson=False)
     sink = TsvSink(out, poisson=poisson, dirichlet_weights=weights)
     n = predict_regions_sharded(forward, regions, focal, context, model_type=model_type, sink=sink, collect=False, timings=split, **labels)
+    _report_mutations(split)
+    print(f"{n} sites -> {out}")
+
+
+_SET_CLASSES = ("A", "C", "nonCpG", "CpG")
+
+
+def _class_pairs(option, items, kind):
+    """{CLASS: kind(VALUE)} of the CLASS=VALUE arguments of `option`."""
+    out = {}
+    for item in items:
+        name, eq, val = item.partition("=")
+        if not eq or not val or name not in _SET_CLASSES:
+            raise SystemExit(f"{option} {item!r}: expected CLASS=VALUE with CLASS one of {', '.join(_SET_CLASSES)}")
+        if name in out:
+            raise SystemExit(f"{option}: class {name} is named twice")
+        try:
+            out[name] = kind(val)
+        except ValueError:
+            raise SystemExit(f"{option} {item!r}: bad value") from None
+    return out
+
+
+def _main_model_set(args, values, flags, model_type, poisson, opts):
+    """--regions with one model per site class: one table, every row by the model of its own base."""
+    if "--model_set" not in values:
+        raise SystemExit("--scale_factors CLASS=F sets the factors of the models that --model_set names")
+    if "--model_path" in flags or len(args) == 3:
+        raise SystemExit("--model_set names the models (CLASS=MODEL_PATH): leave the MODEL argument / --model_path out "
+                         "(FASTA OUT.tsv --regions SPEC --model_set CLASS=MODEL_PATH ..)")
+    if opts["wants_summary"] or opts["no_table"]:
+        raise SystemExit("--model_set does not go with --summary / --genomewide_mu / --no-table: a scaling factor belongs to one model, "
+                         "and per-class summaries are not written; summarise each model's own run")
+    if opts["scale_factor"] is not None:
+        raise SystemExit("--model_set takes a factor per class: --scale_factors CLASS=F ..")
+    if "--regions" not in values:
+        raise SystemExit("--model_set needs --regions: a BED run serves one model (its per-segment focal-base check stands)")
+    if model_type == "indel" or "--focal" in values or "--context" in values:
+        raise SystemExit("--model_set selects the sites by its classes: it takes neither --indel nor --focal / --context")
+    if len(args) != 2:
+        raise SystemExit(__doc__)
+    if "--strict_mutations" in flags and "--mutations" not in values:
+        raise SystemExit("--strict_mutations needs --mutations FILE")
+    if len(values.get("--mutations", [])) > 1:
+        raise SystemExit(__doc__)
+    paths = _class_pairs("--model_set", values["--model_set"], str)
+    factors = _class_pairs("--scale_factors", values.get("--scale_factors", []), float)
+    if "C" in paths and ("CpG" in paths or "nonCpG" in paths):
+        raise SystemExit("--model_set: C serves the CpG and the nonCpG sites: it does not go with a CpG or nonCpG model")
+    for name in factors:
+        if name not in paths:
+            raise SystemExit(f"--scale_factors: class {name} has no model in --model_set")
+    from mural_amd.predict import HipShardForward, ModelSetForward, TsvSink, predict_regions_sharded, read_regions_arg
+    fasta, out = args
+    regions = read_regions_arg(values["--regions"])
+    chains = {}
+    for name, path in paths.items():
+        cal = path + ".fdiri_cal.pkl"
+        weights = load_dirichlet_weights(cal) if os.path.exists(cal) and "--no-calibration" not in flags else None
+        chains[name] = dict(dirichlet_weights=weights, poisson=poisson, scale_factor=factors.get(name))
+    # every member runs its own chain behind its head (the sink could apply one calibrator only), so all of them have one or none has
+    has = {name: c["dirichlet_weights"] is not None or bool(c["poisson"]) or bool(c["scale_factor"]) for name, c in chains.items()}
+    if len(set(has.values())) > 1:
+        raise SystemExit("--model_set: %s would be calibrated or scaled and %s would not, but one table has one number format: give every "
+                         "model a calibrator or a --scale_factors entry, or pass --no-calibration"
+                         % (", ".join(k for k in has if has[k]), ", ".join(k for k in has if not has[k])))
+    members = {}
+    for name, path in paths.items():
+        model, cfg = load_model(path, model_type="snv")
+        members[name] = HipShardForward(model, None, cfg["local_radius"], cfg.get("local_order", 3), distal_radius=cfg["distal_radius"],
+                                        model_type="snv", **chains[name])
+    try:
+        forward = ModelSetForward(members, fasta_path=fasta)
+    except ValueError as e:
+        raise SystemExit(f"--model_set: {e}") from None
+    split = {}
+    labels = dict(mutations=values["--mutations"][0], strict_mutations="--strict_mutations" in flags) if "--mutations" in values else {}
+    n = predict_regions_sharded(forward, regions, "SET", sink=TsvSink(out), collect=False, timings=split, **labels)
     _report_mutations(split)
     print(f"{n} sites -> {out}")
 
