@@ -707,6 +707,43 @@ int32_t mural_summary_motif_in_lds(int32_t m, int32_t n_class);
 int mural_summary_motif_rows(const MuralSummaryMotifRows* s, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Loss and calibration metrics of a shard while it is on the device (SummarySink(calibration=True);
+ * csrc/summary_calib.hip): the sums behind NLL / ECE / classwise ECE / Brier as calibrate_prob reports them
+ * (MuRaL/evaluation/evaluation.py:207-295, 339-358), in one pass over the rows (any order) of a part.  Per row, in the
+ * probabilities' own precision: q = softmax(log(prob)), confidence = max q (the first maximum is the prediction), Brier
+ * term = sum_c ([c == label] - q_c)^2, NLL term = -log q_label, bins (lower, upper] on bounds [n_bins + 1] (the float32
+ * linspace(0, 1, n_bins + 1) of the reference).  Integer cells and integer atomics only: the table is a function of the SET
+ * of valid rows, bit for bit.
+ *   table [mural_summary_calib_cells(n_class, n_bins)] of unsigned 64-bit cells, H = 6 + n_class, zeroed by the caller
+ *     before the first part:
+ *       [0] rows  [1] inf_rows  [2 + c] rows with label c  [2 + nc], [3 + nc] NLL hi, lo  [4 + nc], [5 + nc] Brier hi, lo
+ *       [H + 4 (g n_bins + b) + 0 .. 3] rows, score hi, score lo, hits of bin b of group g: g = 0 the top-label bins
+ *       (score = the confidence, hit = the prediction is the label), g = 1 + c class c (score = q_c, hit = label is c);
+ *     a sum's term v is quantised once to rne(v * 2^(S + 46)): hi = floor(v * 2^S), lo = rint((v * 2^S - hi) * 2^46), value
+ *     of a pair (hi * 2^46 + lo) / 2^(S + 46); S = 16 for scores and Brier terms, 13 for NLL terms (a row's error is at
+ *     most 2^-60); on return lo < 2^46; 2^40 rows do not overflow a cell;
+ *   a valid row with q_label == 0 (an infinite NLL term) counts in inf_rows and everywhere but the NLL sum;
+ *   status (device int32): bit 1 a label outside 0 .. n_class - 1 (or no whole number), bit 3 a probability that is NaN,
+ *     negative or above 1 (or a row with no positive probability); such rows are skipped everywhere.
+ * mural_summary_calib_cells: 6 + n_class + 4 n_bins (n_class + 1), or 0 where that is more than the 4096 cells a
+ * workgroup holds (or a size is out of range): mural_summary_calib_rows refuses such a table with MURAL_E_INVALID.
+ * Two launches on `stream` per 2^28 rows, no synchronisation.  n_class <= 16.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 0 .. n_class-1 are read          */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_bins;
+  const float* bounds;       /* dev [n_bins + 1], ascending */
+  uint64_t* table;           /* dev */
+  int32_t* status;           /* dev [1] */
+} MuralSummaryCalibRows;
+int64_t mural_summary_calib_cells(int32_t n_class, int32_t n_bins);
+int mural_summary_calib_rows(const MuralSummaryCalibRows* s, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

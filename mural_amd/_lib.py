@@ -115,6 +115,12 @@ class MuralSummaryMotifRows(C.Structure):
                 ("table", C.c_void_p * 4), ("first", C.c_void_p * 4), ("order_base", C.c_int64), ("status", C.c_void_p)]
 
 
+class MuralSummaryCalibRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("label_kind", C.c_int32), ("prob_stride", C.c_int64), ("label", C.c_void_p),
+                ("n", C.c_int64), ("n_class", C.c_int32), ("n_bins", C.c_int32), ("bounds", C.c_void_p), ("table", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
 
 # every symbol include/mural_hip.h declares: name -> (restype, argtypes)
@@ -248,6 +254,8 @@ PROTOTYPES = {
     "mural_summary_kmer_rows": (C.c_int, [C.POINTER(MuralSummaryKmerRows), VP]),
     "mural_summary_motif_in_lds": (I32, [I32, I32]),
     "mural_summary_motif_rows": (C.c_int, [C.POINTER(MuralSummaryMotifRows), VP]),
+    "mural_summary_calib_cells": (I64, [I32, I32]),
+    "mural_summary_calib_rows": (C.c_int, [C.POINTER(MuralSummaryCalibRows), VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

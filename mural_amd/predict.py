@@ -957,6 +957,16 @@ def _refuse_second_calibration(rows, poisson, dirichlet_weights):
                          "dirichlet_weights= here, or build the forward with poisson=False")
 
 
+def _refuse_fit_on_calibrated(calibrated):
+    """``SummarySink(fit_calibrator=...)`` fits the raw softmax (MuRaL/training.py:478): refused where the sink or the forward
+    calibrates."""
+    if calibrated:
+        raise ValueError("these probabilities are calibrated already (HipShardForward applied its dirichlet_weights / poisson / "
+                         "scale_factor chain on the device, or the sink was given poisson= / dirichlet_weights=; poisson defaults to on "
+                         "for model_type='indel'): fit_calibrator= fits a calibrator on the raw softmax: drop poisson= / "
+                         "dirichlet_weights= / scale_factor=, or build the forward with poisson=False")
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # genome summaries in flight: what calc_scaling_factor and evaluate --window_size read from the written table, reduced from the
 # shards while they are on the device (csrc/summary.hip), so that a summary-only pass needs no table at all
@@ -1235,6 +1245,167 @@ def _revdigits(key, m):
     return out
 
 
+# ---- loss and calibration metrics (csrc/summary_calib.hip: mural_summary_calib_rows): integer sums behind NLL / ECE / CwECE / Brier ----
+# Scaling of the two-limb sums: a term v >= 0 is quantised once to rne(v * 2^(S + 46)), hi = floor(v * 2^S), lo = rint((v * 2^S - hi) *
+# 2^46), every step exact in float64; S = 16 for the scores (in [0, 1]) and the Brier terms (in [0, 2]) -- a row's error at most 2^-63
+# --, S = 13 for the NLL terms (below 2^10: -log of the smallest positive double is 744.5) -- at most 2^-60.  A folded pair has
+# lo < 2^46; hi grows by at most 2^23 a row plus the carries, so 2^40 rows stay below 2^64.
+_CALIB_LO_BITS, _CALIB_SCORE_BITS, _CALIB_NLL_BITS = 46, 16, 13
+_CALIB_LO_MASK = np.uint64((1 << _CALIB_LO_BITS) - 1)
+_CALIB_FOLD_ROWS = 1 << 17         # rows between two folds here: lo < 2^46 + 2^17 * 2^46 < 2^64
+_CALIB_MAX_CELLS = 4096            # the table a workgroup of csrc/summary_calib.hip holds
+
+
+def calib_cells(n_class, n_bins):
+    """Cells of the table of ``mural_summary_calib_rows``: 6 + n_class header cells and 4 per bin of the n_class + 1 groups."""
+    return 6 + int(n_class) + 4 * int(n_bins) * (int(n_class) + 1)
+
+
+def calib_bounds(n_bins):
+    """The reference's bin bounds: float32 ``torch.linspace(0, 1, n_bins + 1)`` (evaluation.py:218)."""
+    return torch.linspace(0, 1, int(n_bins) + 1).numpy()
+
+
+def _calib_lo_cells(n_class, n_bins):
+    h = 6 + n_class
+    return np.r_[3 + n_class, 5 + n_class, h + 2 + 4 * np.arange(n_bins * (n_class + 1))].astype(np.int64)
+
+
+def _calib_fold(table, n_class, n_bins):
+    """Carry the lo limbs' overflow into the hi limbs in front of them: table uint64 [cells], in place."""
+    lo = _calib_lo_cells(n_class, n_bins)
+    table[lo - 1] += table[lo] >> np.uint64(_CALIB_LO_BITS)
+    table[lo] &= _CALIB_LO_MASK
+    return table
+
+
+def _calib_quantise(v, bits):
+    """(hi, lo) uint64 of float64 terms v >= 0 (the rule above)."""
+    v = np.where(v > 0.0, v, 0.0)
+    s = v * float(1 << bits)
+    h = np.floor(s)
+    return h.astype(np.uint64), np.rint((s - h) * float(1 << _CALIB_LO_BITS)).astype(np.uint64)
+
+
+def summary_calib_host(prob, label, n_class, n_bins=50, bounds=None, into=None):
+    """The numpy twin of ``mural_summary_calib_rows`` -- and its specification -- for rows in any order: (table uint64 [6 + n_class +
+    4 n_bins (n_class + 1)], status).  Per row, in the probabilities' own precision (float32 or float64; anything else is taken as
+    float32): q = softmax(log(prob)), summed over the classes in ascending order; confidence = max q, the prediction its first maximum;
+    Brier term = sum_c ([c == label] - q_c)^2, the squares widened to float64 and added in class order; NLL term = -log q_label; bins
+    (lower, upper] on `bounds` (default ``calib_bounds(n_bins)``), compared in float64.  Cells, H = 6 + n_class:
+      [0] rows  [1] inf_rows  [2 + c] rows with label c  [2 + nc], [3 + nc] NLL hi, lo  [4 + nc], [5 + nc] Brier hi, lo
+      [H + 4 (g n_bins + b) + 0 .. 3] rows, score hi, score lo, hits of bin b of group g: g = 0 the top-label bins (score = confidence,
+      hit = the prediction is the label), g = 1 + c class c (score = q_c, hit = the label is c); a score in no bin (0) adds nowhere.
+    The real-valued sums are the two-limb integers described above this function, so the table depends on the SET of valid rows alone,
+    bit for bit.  `into`: the table of earlier parts to add to (in place).  Status bits as on the device: 2 a label outside
+    0 .. n_class - 1 (or no whole number), 8 a probability that is NaN, negative or above 1 -- or a row without a positive probability,
+    whose softmax is undefined; such rows are skipped everywhere.  A valid row with q_label == 0 counts in inf_rows and everywhere but
+    the NLL sum.
+
+    Device and twin agree EXACTLY in what no transcendental's last bit decides: rows, label counts, status, inf_rows for exact zeros.
+    The score sums and the bin a score falls in go through ``log`` and ``exp`` of two math libraries: they are compared through the
+    derived metrics (``calib_metrics_from_sums``), not bit for bit."""
+    nc, nb = int(n_class), int(n_bins)
+    prob = np.asarray(prob)[:, :nc]
+    if prob.dtype not in (np.float32, np.float64):
+        prob = prob.astype(np.float32)
+    P = prob.dtype.type
+    bounds = (calib_bounds(nb) if bounds is None else np.asarray(bounds, np.float32)).astype(np.float64)
+    if len(bounds) != nb + 1:
+        raise ValueError(f"{nb} bins need {nb + 1} bounds")
+    table = np.zeros(calib_cells(nc, nb), np.uint64) if into is None else into
+    label = np.asarray(label)
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= nc) | (lab != label)
+    with np.errstate(invalid="ignore"):
+        bad_prob = ~((prob >= 0) & (prob <= 1)).all(axis=1) | ~(prob > 0).any(axis=1)
+    status = (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    ok = ~(bad_label | bad_prob)
+    prob, lab = prob[ok], lab[ok]
+    H = 6 + nc
+    for r0 in range(0, len(lab), _CALIB_FOLD_ROWS):
+        p, y = prob[r0:r0 + _CALIB_FOLD_ROWS], lab[r0:r0 + _CALIB_FOLD_ROWS]
+        rows = np.arange(len(y))
+        with np.errstate(divide="ignore"):
+            lg = np.log(p)
+        e = np.exp(lg - lg.max(axis=1, keepdims=True))
+        s = np.zeros(len(y), P)
+        for c in range(nc):
+            s = s + e[:, c]
+        q = e / s[:, None]
+        conf, arg = q.max(axis=1), q.argmax(axis=1)
+        brier = np.zeros(len(y))
+        for c in range(nc):
+            d = (y == c).astype(P) - q[:, c]
+            brier = brier + (d * d).astype(np.float64)
+        q_lab = q[rows, y]
+        inf = ~(q_lab > 0)
+        table[0] += np.uint64(len(y))
+        table[1] += np.uint64(int(inf.sum()))
+        table[2:2 + nc] += np.bincount(y, minlength=nc).astype(np.uint64)
+        hi, lo = _calib_quantise(-np.log(q_lab[~inf]).astype(np.float64), _CALIB_NLL_BITS)
+        table[2 + nc] += hi.sum(dtype=np.uint64)
+        table[3 + nc] += lo.sum(dtype=np.uint64)
+        hi, lo = _calib_quantise(brier, _CALIB_SCORE_BITS)
+        table[4 + nc] += hi.sum(dtype=np.uint64)
+        table[5 + nc] += lo.sum(dtype=np.uint64)
+        for g in range(nc + 1):
+            v = (conf if g == 0 else q[:, g - 1]).astype(np.float64)
+            hit = (arg == y) if g == 0 else (y == g - 1)
+            b = np.searchsorted(bounds, v, side="left") - 1      # bounds[b] < v <= bounds[b + 1]
+            live = (b >= 0) & (b < nb)
+            cell = H + 4 * (g * nb + b[live])
+            hi, lo = _calib_quantise(v[live], _CALIB_SCORE_BITS)
+            np.add.at(table, cell, np.uint64(1))
+            np.add.at(table, cell + 1, hi)
+            np.add.at(table, cell + 2, lo)
+            np.add.at(table, cell + 3, hit[live].astype(np.uint64))
+        _calib_fold(table, nc, nb)
+    return table, status
+
+
+def calib_rows_device(prob, label, n_class, n_bins, bounds, table, status):
+    """One call of ``mural_summary_calib_rows`` on the current stream of `prob`'s device: prob (n, >= n_class) float32 / float64 with unit
+    column stride, label (n,) float32 / int32 / int64, bounds float32 [n_bins + 1], table int64 [calib_cells] and status int32 [1] -- all
+    device tensors; table and status are added to."""
+    s = _lib.MuralSummaryCalibRows()
+    s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0) if prob.shape[0] > 1 else prob.shape[1]
+    s.label, s.label_kind = label.data_ptr(), {torch.float32: 0, torch.int32: 1, torch.int64: 2}[label.dtype]
+    s.n, s.n_class, s.n_bins = prob.shape[0], int(n_class), int(n_bins)
+    s.bounds, s.table, s.status = bounds.data_ptr(), table.data_ptr(), status.data_ptr()
+    with torch.cuda.device(prob.device):
+        _lib.check(_lib.lib().mural_summary_calib_rows(C.byref(s), _lib.current_stream_ptr(prob.device)))
+
+
+def calib_metrics_from_sums(tables, n_bins, n_class):
+    """{"rows", "nll", "ece", "c_ece", "brier", "label_counts"} from the integer table of ``summary_calib_host`` /
+    ``mural_summary_calib_rows``, formed from Python integers (true division rounds correctly): nll = NLL sum / rows (inf where a row
+    had q_label == 0, as the reference's mean would be), brier = Brier sum / rows, ece = sum over the top-label bins of
+    |score sum / rows_b - hits_b / rows_b| * rows_b / rows -- which is |score sum - hits_b| / rows, summed exactly --, c_ece the mean of
+    the same over the bins of class c for c < (the highest label seen) + 1: the reference's ClasswiseECELoss sizes itself by
+    max(labels) + 1.  NaN where there is no row."""
+    nc, nb = int(n_class), int(n_bins)
+    t = np.asarray(tables).astype(np.uint64).tolist()
+    rows, inf_rows, counts = t[0], t[1], t[2:2 + nc]
+    out = {"rows": rows, "label_counts": counts}
+    if rows == 0:
+        return dict(out, nll=float("nan"), ece=float("nan"), c_ece=float("nan"), brier=float("nan"))
+    pair = lambda at: (t[at] << _CALIB_LO_BITS) + t[at + 1]      # noqa: E731
+    one = 1 << (_CALIB_SCORE_BITS + _CALIB_LO_BITS)
+    H = 6 + nc
+
+    def gap(g):
+        """sum over the bins of group g of |score sum - hits|, in units of 2^-62"""
+        return sum(abs(pair(at + 1) - t[at + 3] * one) for at in range(H + 4 * g * nb, H + 4 * (g + 1) * nb, 4) if t[at])
+
+    n_seen = max(c for c in range(nc) if counts[c]) + 1
+    out["nll"] = float("inf") if inf_rows else pair(2 + nc) / (rows << (_CALIB_NLL_BITS + _CALIB_LO_BITS))
+    out["brier"] = pair(4 + nc) / (rows * one)
+    out["ece"] = gap(0) / (rows * one)
+    out["c_ece"] = sum(gap(1 + c) for c in range(n_seen)) / (n_seen * rows * one)
+    return out
+
+
 def _merge_window_table(have, bin0, table):
     """(bin0, table) of a chromosome's windows so far + one part's: the covering table, the part added behind what was there."""
     if have is None or have[1].shape[0] == 0:
@@ -1277,12 +1448,32 @@ class SummarySink:
     reads from the written table -- are reduced the same way (``mural_summary_motif_rows``: every window of m bases that holds a row's
     site, on the reference strand, a motif and its reverse complement in one entry), alone or beside `kmers` and
     `windows`; `motif_indel`: the rows are INDEL rows (m - 1 windows each).  They need `genome` as well.  close() writes
-    ``{out_prefix}.{m}-motif.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_motif_outputs``), and result() has "motifs"."""
+    ``{out_prefix}.{m}-motif.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_motif_outputs``), and result() has "motifs".
+
+    `calibration`: the NLL / ECE / classwise ECE / Brier block of the reference's validation report (``calibrate_prob``,
+    evaluation.py:297-365) from the rows' own labels, on `calibration_bins` bins, alone or beside the other summaries; it needs no
+    `genome`.  Device parts go through ``mural_summary_calib_rows`` (csrc/summary_calib.hip), host shards through
+    ``summary_calib_host``: integer tables per chromosome, read back once at close(), exchanged between ranks in the same collective and
+    added -- the metrics depend on the set of rows alone, bit for bit.  result()["calibration"] = ``calib_metrics_from_sums`` of all rows
+    + "per_chromosome": {name: the same}; close() writes ``{out_prefix}.calibration.txt`` (a header, an `all` line, a line per
+    chromosome by name: rows nll ece c_ece brier, '%.8f'); ``calibration_sums()`` has the integers.
+
+    `fit_calibrator`: a key of ``evaluation.CALIBRATORS`` ('FullDiri', ...) to fit on the same rows (training.py:478 fits the raw
+    softmax, so the option is refused where the sink or the forward calibrates); it turns `calibration` on.  The sink retains (float32
+    prob[n_class], uint8 label) of every row -- device parts in device blocks, host shards on the host until close() uploads them -- and
+    raises ValueError at the shard that takes a rank beyond `fit_rows_max` retained rows; nothing is subsampled.  close() runs
+    ``evaluation.newton_calibrator`` on the sums ``mural_eval_dirichlet_fit_terms`` makes of each block (all_reduced over the ranks, one
+    small collective per evaluation), saves ``{out_prefix}.fdiri_cal.pkl`` on rank 0, calibrates the blocks and reduces their metrics
+    through the same entry: result()["calibration"] gains "after", "weights" and "fit_loss", the text file an `all (after NAME)` line.
+    The fit's sums are float64 atomics: the weights are reproducible to rounding, not bit for bit; only the metrics are bit-exact.
+    `fit_row_terms`: (prob, label, weights, need_hessian) -> (loss, gradient, Hessian) SUMS over the given rows, a stand-in for the
+    device kernel that keeps host shards on the host (tests without a device)."""
 
     takes_aligned_blocks = True
 
     def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
-                 group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False):
+                 group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
+                 calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         self.windows = tuple(int(w) for w in windows)
         if any(w <= 0 for w in self.windows) or len(set(self.windows)) != len(self.windows):
@@ -1326,6 +1517,20 @@ class SummarySink:
             raise ValueError("SummarySink(motifs=...) needs genome=: a callable chromosome name -> packed genome")
         self._motif_indel = bool(motif_indel)
         self._motif_host, self._motif_dev = ({}, {}), {}      # as the k-mer accumulators
+        self.fit_calibrator, self.fit_rows_max, self._fit_row_terms = fit_calibrator, int(fit_rows_max), fit_row_terms
+        if fit_calibrator is not None:
+            from .evaluation import CALIBRATORS
+            if fit_calibrator not in CALIBRATORS:
+                raise ValueError(f"unknown calibrator {fit_calibrator!r} (one of {sorted(CALIBRATORS)})")
+            _refuse_fit_on_calibrated(poisson or dirichlet_weights is not None)
+        self.calibration = bool(calibration) or fit_calibrator is not None
+        self.calibration_bins = int(calibration_bins)
+        if self.calibration and self.calibration_bins < 1:
+            raise ValueError(f"calibration_bins must be positive (got {calibration_bins})")
+        self._calib_bounds = calib_bounds(self.calibration_bins) if self.calibration else None
+        self._calib_host = {}          # chromosome -> table uint64 [cells] of the host shards
+        self._calib_dev = {}           # device -> ({chromosome: table}, status, bounds): read back once, at close()
+        self._fit_blocks, self._fit_rows = [], 0      # [(prob float32 [n][n_class], label uint8 [n])], on a device or on the host
 
     # -- one part ---------------------------------------------------------------------------------------------------------
     def _take(self, name, tables, total, n_sites, status):
@@ -1365,6 +1570,45 @@ class SummarySink:
             _, status = summary_motif_host(self._genome(name), cols[3], cols[0], cols[1], cols[2], k, self.motifs, self._motif_indel,
                                            into={m: (tabs[m], mine[m]) for m in self.motifs})
             self._status |= status
+        if self.calibration:
+            _, status = summary_calib_host(cols[3], cols[2], k, self.calibration_bins, self._calib_bounds,
+                                           into=self._calib_table(self._calib_host, name, k))
+            self._status |= status
+        if self.fit_calibrator is not None:
+            lab = np.asarray(cols[2])
+            good = np.isfinite(lab.astype(np.float64)) & (lab >= 0) & (lab < k) & (lab == np.floor(lab.astype(np.float64)))
+            self._retain(np.ascontiguousarray(cols[3], np.float32), np.where(good, lab, 255).astype(np.uint8))
+
+    def _calib_table(self, tables, name, k):
+        cells = calib_cells(k, self.calibration_bins)
+        if cells > _CALIB_MAX_CELLS:
+            raise ValueError(f"calibration_bins * (n_class + 1) = {self.calibration_bins * (k + 1)} is too large: the table of {cells} "
+                             f"cells does not fit the {_CALIB_MAX_CELLS} a workgroup holds")
+        if name not in tables:
+            tables[name] = np.zeros(cells, np.uint64)
+        return tables[name]
+
+    def _retain(self, prob, label):
+        """Keep a part's (float32 probabilities, uint8 labels -- 255 where the label is none) for the fit at close().  Every row of the
+        part counts against `fit_rows_max`: an invalid row makes close() raise before anything is fitted."""
+        if self._fit_rows + len(label) > self.fit_rows_max:
+            raise ValueError(f"fit_calibrator={self.fit_calibrator!r}: this shard takes the rows retained on this rank from {self._fit_rows} to "
+                             f"{self._fit_rows + len(label)}, beyond fit_rows_max={self.fit_rows_max}; raise the budget or fit on fewer rows "
+                             "(nothing is subsampled silently)")
+        self._fit_rows += len(label)
+        self._fit_blocks.append((prob, label))
+
+    def _calib_device(self, name, dev, prob, label, k):
+        """Enqueue the metrics reduction of a part behind its forward: one launch (and the fold of the carries) into the chromosome's
+        accumulator on that device."""
+        acc = self._calib_dev.get(dev)
+        if acc is None:
+            acc = self._calib_dev[dev] = ({}, torch.zeros(1, dtype=torch.int32, device=dev), torch.from_numpy(self._calib_bounds).to(dev))
+        table = acc[0].get(name)
+        if table is None:
+            cells = len(self._calib_table({}, name, k))
+            table = acc[0][name] = torch.zeros(cells, dtype=torch.int64, device=dev)
+        calib_rows_device(prob, label, k, self.calibration_bins, acc[2], table, acc[1])
 
     def _kmer_device(self, name, dev, prob, start, end, strand, label, k):
         """Enqueue the k-mer reduction of a part behind its forward: the part's chromosome is the resident one now."""
@@ -1455,6 +1699,11 @@ class SummarySink:
             genome = self._kmer_device(name, dev, prob, start, end, strand, label, k) if self.kmers else None
             if self.motifs:
                 genome = self._motif_device(name, dev, prob, start, end, label, k)
+            if self.calibration:
+                self._calib_device(name, dev, prob, label, k)
+            if self.fit_calibrator is not None:
+                good = (label >= 0) & (label < k) & (label == label.to(torch.int64))
+                self._retain(prob[:, :k].to(torch.float32, copy=True).contiguous(), torch.where(good, label, 255).to(torch.uint8))
             ends = torch.empty(2, dtype=torch.int64).pin_memory()
             ends.copy_(torch.stack([start[0], start[-1]]), non_blocking=True)
             ev = torch.cuda.Event()
@@ -1533,6 +1782,8 @@ class SummarySink:
         if name is None or n == 0:
             return
         _refuse_second_calibration(shard, self.poisson, self.dirichlet_weights)
+        if self.fit_calibrator is not None:
+            _refuse_fit_on_calibrated(shard.get("calibrated"))
         k = int(shard.get("n_class", shard["prob"].shape[1]))
         if self._n_class not in (None, k):
             raise ValueError(f"shards of {self._n_class} and of {k} classes in one summary")
@@ -1553,7 +1804,7 @@ class SummarySink:
     def _merged(self, states):
         """[(tables, prob_sum, n_sites, status, n_class, k-mer state)] of the ranks, added in rank order."""
         tables, prob_sum, n_sites, status, k = {}, 0.0, 0, 0, None
-        for t, s, c, st, kk, _, _ in states:
+        for t, s, c, st, kk, *_ in states:
             for name, per_w in t.items():
                 mine = tables.setdefault(name, {})
                 for W, (bin0, tab) in per_w.items():
@@ -1561,7 +1812,27 @@ class SummarySink:
             prob_sum, n_sites, status = prob_sum + s, n_sites + c, status | st
             k = kk if k is None else k
         return (tables, prob_sum, n_sites, status, k, _kmer_merge([st[5] for st in states]) if self.kmers else None,
-                _kmer_merge([st[6] for st in states], _MOTIF_ORD_SHIFT) if self.motifs else None)
+                _kmer_merge([st[6] for st in states], _MOTIF_ORD_SHIFT) if self.motifs else None,
+                self._calib_merged([st[7] for st in states if st[7]], k) if self.calibration else None)
+
+    def _calib_merged(self, per_rank, k):
+        """[{chromosome: table}] of the ranks (or of a rank's devices and its host rows) -> one such dict: integer tables added, carries
+        folded."""
+        out = {}
+        for tables in per_rank:
+            for name, t in tables.items():
+                if name in out:
+                    _calib_fold(np.add(out[name], t, out=out[name]), k, self.calibration_bins)
+                else:
+                    out[name] = t.copy()
+        return out
+
+    def _calib_read_back(self):
+        mine = [self._calib_host]
+        for tables, dev_status, _ in self._calib_dev.values():
+            self._status |= int(dev_status.item())
+            mine.append({name: t.cpu().numpy().view(np.uint64) for name, t in tables.items()})
+        return self._calib_merged([m for m in mine if m], self._n_class)
 
     def _read_back(self, host, devices, shift):
         """The one read-back of the device accumulators of the k-mer (or motif) tables, merged with the host rows'."""
@@ -1577,12 +1848,13 @@ class SummarySink:
         self._harvest()
         kmer_state = self._read_back(self._kmer_host, self._kmer_dev, _KMER_ORD_SHIFT) if self.kmers else None
         motif_state = self._read_back(self._motif_host, self._motif_dev, _MOTIF_ORD_SHIFT) if self.motifs else None
-        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class, kmer_state, motif_state)
+        calib_state = self._calib_read_back() if self.calibration else None
+        state = (self._tables, self._prob_sum, self._n_sites, self._status, self._n_class, kmer_state, motif_state, calib_state)
         if self.world > 1:
             every = [None] * self.world
             dist.all_gather_object(every, state, group=self.group)      # the one collective: tables, not rows
             state = self._merged(every)
-        tables, prob_sum, n_sites, status, k, kmer_state, motif_state = state
+        tables, prob_sum, n_sites, status, k, kmer_state, motif_state, calib_state = state
         for bit, what in _SUMMARY_STATUS:
             if status & bit:
                 raise ValueError(f"summary: {what}")
@@ -1606,6 +1878,8 @@ class SummarySink:
             self._motif_sums = mtables
             self._result["motifs"] = {m: (motif_table_from_sums(*mtables[m], m, k) if m in mtables else ([], np.zeros((0, 1 + 2 * (k or 0)))))
                                       for m in self.motifs}
+        if self.calibration:
+            self._close_calibration(calib_state or {}, k)
         if self.out_prefix is not None and self.rank == 0 and k is not None:
             from .tables import regional_output_names, write_regional_outputs
             for W in self.windows:
@@ -1619,12 +1893,134 @@ class SummarySink:
             for m in self.motifs:
                 self._written += list(motif_output_names(self.out_prefix, m))
                 write_motif_outputs(*self._result["motifs"][m], k, m, self.out_prefix)
+            if self.calibration:
+                self._write_calibration()
+
+    # -- calibration metrics and the calibrator fit ---------------------------------------------------------------------------
+    def _calib_total(self, per_chrom, k):
+        total = np.zeros(calib_cells(k or 1, self.calibration_bins), np.uint64)
+        for t in per_chrom.values():
+            _calib_fold(np.add(total, t, out=total), k or 1, self.calibration_bins)
+        return total
+
+    def _close_calibration(self, per_chrom, k):
+        nb = self.calibration_bins
+        total = self._calib_total(per_chrom, k)
+        self._calib_sums = {"all": total, "per_chromosome": per_chrom}
+        res = calib_metrics_from_sums(total, nb, k or 1)
+        res["per_chromosome"] = {name: calib_metrics_from_sums(per_chrom[name], nb, k) for name in sorted(per_chrom)}
+        self._result["calibration"] = res
+        if self.fit_calibrator is not None:
+            self._fit(res, k)
+
+    def _block_terms(self, prob, label, w, need_hessian):
+        """(loss sum, gradient sum, Hessian sum) of one retained block: the device kernel, or the stand-in given as `fit_row_terms`."""
+        k = prob.shape[1]
+        km = k * (k + 1)
+        if self._fit_row_terms is not None:
+            loss, g, h = self._fit_row_terms(_np(prob), _np(label), w, need_hessian)
+            return np.r_[loss, np.ravel(g), np.ravel(h)]
+        out = torch.zeros(1 + km + km * km, dtype=torch.float64, device=prob.device)
+        status = torch.zeros(1, dtype=torch.int32, device=prob.device)
+        wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(prob.device)
+        with torch.cuda.device(prob.device):
+            _lib.check(_lib.lib().mural_eval_dirichlet_fit_terms(prob.data_ptr(), 0, label.to(torch.int32).data_ptr(), prob.shape[0], k,
+                                                                wd.data_ptr(), int(need_hessian), out.data_ptr(), status.data_ptr(),
+                                                                _lib.current_stream_ptr(prob.device)))
+        return out.cpu().numpy()
+
+    def _fit(self, res, k):
+        """Fit the named calibrator on the retained raw-softmax rows (training.py:478), save it, and reduce the metrics of the calibrated
+        rows through the same entry.  The data terms are the float64 atomic sums of ``mural_eval_dirichlet_fit_terms`` per block, added
+        over blocks and -- one small all_reduce per evaluation -- over ranks: the weights are reproducible to rounding, not bit for bit.
+        Only the metrics carry the bit-exact promise."""
+        from .calibration import calibrate_device, dirichlet_calibrate, save_dirichlet_calibrator
+        from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
+        name = self.fit_calibrator
+        method, ref_row, reg_lambda, reg_mu, reg_norm = CALIBRATORS[name]
+        if k is None or k < 2 or k > _FIT_MAX_CLASSES:
+            raise ValueError(f"fit_calibrator supports 2..{_FIT_MAX_CLASSES} classes, got {k}")
+        if any(c == 0 for c in res["label_counts"]):
+            raise ValueError("every class 0..n_class-1 must occur in the labels (the reference sizes the map by unique(y))")
+        if reg_norm:                                              # multinomial.py:81-86
+            if reg_mu is None:
+                reg_lambda = reg_lambda / (k * (k + 1))
+            else:
+                reg_lambda, reg_mu = reg_lambda / (k * (k - 1)), reg_mu / k
+        if self._fit_row_terms is None:                           # host shards are uploaded now, beside the device blocks
+            dev = next((p.device for p, _ in self._fit_blocks if isinstance(p, torch.Tensor)), None)
+            dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+            self._fit_blocks = [(p, y) if isinstance(p, torch.Tensor) else (torch.from_numpy(p).to(dev), torch.from_numpy(y).to(dev))
+                                for p, y in self._fit_blocks]
+        km = k * (k + 1)
+        n = res["rows"]
+
+        def row_terms(w, need_hessian):
+            sums = np.zeros(1 + km + km * km)
+            for p, y in self._fit_blocks:
+                sums += self._block_terms(p, y, w, need_hessian)
+            if self.world > 1:
+                t = torch.from_numpy(sums)                        # (shares its memory)
+                if dist.get_backend(self.group) == "nccl":
+                    t = t.cuda()
+                dist.all_reduce(t, group=self.group)
+                sums = t.cpu().numpy()
+            return sums[0] / n, sums[1:1 + km] / n, sums[1 + km:].reshape(km, km) / n
+
+        weights, loss = newton_calibrator(row_terms, k, method, ref_row, reg_lambda, reg_mu)
+        after = {}
+        bounds = {}
+        for p, y in self._fit_blocks:
+            if isinstance(p, torch.Tensor):
+                dev = p.device
+                if dev not in after:
+                    after[dev] = (torch.zeros(calib_cells(k, self.calibration_bins), dtype=torch.int64, device=dev),
+                                  torch.zeros(1, dtype=torch.int32, device=dev))
+                    bounds[dev] = torch.from_numpy(self._calib_bounds).to(dev)
+                with torch.cuda.device(dev):
+                    cal = calibrate_device(p, dirichlet_weights=weights, input_is_prob=True)
+                    calib_rows_device(cal, y.to(torch.int32), k, self.calibration_bins, bounds[dev], *after[dev])
+            else:
+                summary_calib_host(dirichlet_calibrate(p, weights), y, k, self.calibration_bins, self._calib_bounds,
+                                   into=self._calib_table(after, "host", k))
+        tables = {key: (v if isinstance(v, np.ndarray) else v[0].cpu().numpy().view(np.uint64)) for key, v in after.items()}
+        if self.world > 1:
+            every = [None] * self.world
+            dist.all_gather_object(every, tables, group=self.group)
+            tables = {(r, key): t for r, ts in enumerate(every) for key, t in ts.items()}
+        total = self._calib_total(tables, k)
+        self._calib_sums["after"] = total
+        res["after"] = calib_metrics_from_sums(total, self.calibration_bins, k)
+        res["weights"], res["fit_loss"] = weights, float(loss)
+        if self.out_prefix is not None and self.rank == 0:
+            path = self.out_prefix + ".fdiri_cal.pkl"
+            self._written.append(path)
+            save_dirichlet_calibrator(weights, path)
+
+    def _write_calibration(self):
+        res = self._result["calibration"]
+        path = self.out_prefix + ".calibration.txt"
+        self._written.append(path)
+        line = lambda tag, m: "%s\t%d\t%.8f\t%.8f\t%.8f\t%.8f\n" % (tag, m["rows"], m["nll"], m["ece"], m["c_ece"], m["brier"])      # noqa: E731
+        with open(path, "w") as fh:
+            fh.write("chrom\trows\tnll\tece\tc_ece\tbrier\n" + line("all", res))
+            if "after" in res:
+                fh.write(line(f"all (after {self.fit_calibrator})", res["after"]))
+            for name, m in res["per_chromosome"].items():
+                fh.write(line(name, m))
+
+    def calibration_sums(self):
+        """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind
+        result()["calibration"] (``summary_calib_host``'s layout)."""
+        self.result()
+        return self._calib_sums
 
     def abort(self):
         """Drop what was reduced and remove any file close() began: the caller's run failed."""
         self._pending, self._inflight, self._tables, self._result = None, [], {}, None
         self._kmer_host, self._kmer_dev = ({}, {}), {}
         self._motif_host, self._motif_dev = ({}, {}), {}
+        self._calib_host, self._calib_dev, self._fit_blocks, self._fit_rows = {}, {}, [], 0
         for path in self._written:
             if os.path.exists(path):
                 os.unlink(path)
@@ -1634,7 +2030,9 @@ class SummarySink:
         """{"prob_sum", "n_sites", "windows": {W: ([(chrom, window_end)], table [windows][1 + 2 n_class])}} after close(): the pair of
         ``tables.prob_sum_file`` and, per window size, of ``tables.regional_table`` (chromosomes by name, windows ascending); with `kmers`
         also "kmers": {k: (names, table [k-mers][1 + 2 n_class])}, the pair of ``tables.kmer_table``, and with `motifs` "motifs": {m: the
-        pair of ``tables.motif_table``}.  ``kmer_sums()`` and ``motif_sums()`` have the integers."""
+        pair of ``tables.motif_table``}, with `calibration` "calibration": ``calib_metrics_from_sums``' dict of all rows + "per_chromosome"
+        (and "after", "weights", "fit_loss" with `fit_calibrator`).  ``kmer_sums()``, ``motif_sums()`` and ``calibration_sums()`` have the
+        integers."""
         if self._result is None:
             raise RuntimeError("SummarySink.result() is valid after close()")
         return self._result

@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Eight legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Ten legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -12,6 +12,11 @@ alternating, --repeats timed runs each after one warm-up run each:
   f  kmer_tools  the route to e's k-mer tables without the sink: leg a's table, then tables.kmer_table x 3 on it (the FASTA packed again)
   g  motifs      leg b with motifs=(3, 5, 7) as well: the motif tables reduced from the resident chromosome
   h  motif_tools the route to g's motif tables without the sink: leg a's table, then tables.motif_table x 3 on it
+  i  calib       leg b with calibration=True as well: loss and calibration metrics reduced in flight; the
+                 comparison is leg b, the same run without it
+  j  calib_fit   leg b with fit_calibrator="FullDiri" and a synthetic mutation list (every 100th site, classes 1 .. 3 in turn) so that
+                 every class occurs: the rows retained on the device, the fit and the metrics after it at close(); reports close()
+                 seconds, the retained bytes and the leg's peak device memory
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's and leg g's motif tables with leg
 h's, within the table's four digits (names, order and counts exactly)."""
 import json
@@ -35,7 +40,7 @@ from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, pr
 WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
-LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools")
+LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit")
 
 
 def main(argv):
@@ -51,7 +56,7 @@ def main(argv):
     n_class = model.n_class
     shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) and shutil.disk_usage("/dev/shm").free > 100 * bases else None
     with tempfile.TemporaryDirectory(prefix="mural_summary_", dir=shm) as work:
-        fa, _, genome, rows = write_inputs(work, device, bases)
+        fa, _, mutations, _, genome, rows = write_inputs(work, device, bases)      # (its mutation list: every 100th site, classes 1 .. 3)
         del genome
         torch.cuda.empty_cache()
         out = os.path.join(work, "table.tsv")
@@ -67,12 +72,30 @@ def main(argv):
                 summary = SummarySink(windows=WINDOWS, kmers=KMERS, genome=fwd.genome)
             if leg == "motifs":
                 summary = SummarySink(windows=WINDOWS, motifs=MOTIFS, genome=fwd.genome)
-            sink = {"table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
+            if leg == "calib":
+                summary = SummarySink(windows=WINDOWS, calibration=True)
+            if leg == "calib_fit":
+                torch.cuda.reset_peak_memory_stats(device)
+                summary = SummarySink(windows=WINDOWS, fit_calibrator="FullDiri")
+                close = summary.close
+
+                def timed_close():
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    extra["retained_bytes"] = float(sum(p.numel() * p.element_size() + y.numel() for p, y in summary._fit_blocks))
+                    close()
+                    torch.cuda.synchronize()
+                    extra["close"] = time.perf_counter() - t1
+                summary.close = timed_close
+            sink = {"calib": lambda: summary, "calib_fit": lambda: summary, "table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
                     "motif_tools": lambda: TsvSink(out)}[leg]()
-            n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split)
+            n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
+                                        **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
             extra["predict"] = time.perf_counter() - t0
+            if leg == "calib_fit":
+                extra["peak_device_bytes"] = float(torch.cuda.max_memory_allocated(device))
             if leg == "tools":
                 t1 = time.perf_counter()
                 total, n_sites = tables.prob_sum_file(out, n_class)
@@ -136,6 +159,9 @@ def main(argv):
            "kmers_over_summary": ratio("kmers", "summary", med), "kmer_tools_over_kmers_seconds": ratio("kmer_tools", "kmers", sec),
            "motifs": list(MOTIFS), "motifs_over_summary": ratio("motifs", "summary", med),
            "motif_tools_over_motifs_seconds": ratio("motif_tools", "motifs", sec),
+           "calib_over_summary": ratio("calib", "summary", med), "calib_fit_over_summary": ratio("calib_fit", "summary", med),
+           "calibration": {leg: {key: val for key, val in kept[leg]["calibration"].items() if key not in ("per_chromosome", "weights")}
+                           for leg in ("calib", "calib_fit") if leg in kept},
            "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}
     print(json.dumps(res))
     if not agree:

@@ -26,6 +26,15 @@ read back from the table, taken from the probabilities before they are rounded):
   --summary PREFIX  --motif_length M [M ..]                PREFIX.{M}-motif.mut_rates.tsv and .corr.txt per motif length (odd, 3 and
                                                              more): the files of `evaluate --motif_only` -- every window of M bases that
                                                              holds a site, a motif and its reverse complement in one entry
+  --summary PREFIX  --calibration_metrics [--n_bins N]     PREFIX.calibration.txt: rows, NLL, ECE, classwise ECE and Brier score of all
+                                                             rows and per chromosome, from the rows' labels (a BED's score column, or
+                                                             --regions with --mutations FILE; refused for --regions alone, where every
+                                                             label is 0); N bins, 50 by default; alone or with the options above
+  --fit_calibrator NAME                                      with --calibration_metrics: fit that calibrator (FullDiri, FullDiriODIR,
+                                                             FullDiri1, FullDiri2, VectS, TempS) on the raw softmax of the same run,
+                                                             write PREFIX.fdiri_cal.pkl and the metrics after it; the run itself is not
+                                                             calibrated (not with --scale_factor, --poisson / --indel's Poisson step;
+                                                             a MODEL.fdiri_cal.pkl next to the model needs --no-calibration)
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -40,7 +49,7 @@ from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
 _SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
-                    "--scale_factor")
+                    "--scale_factor", "--n_bins", "--fit_calibrator")
 _PAIR_OPTIONS = ("--model_set", "--scale_factors")      # NAME CLASS=VALUE [CLASS=VALUE ..]
 _VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _PAIR_OPTIONS + _SUMMARY_OPTIONS
 
@@ -78,6 +87,11 @@ def main(argv):
     model_type = "indel" if "--indel" in flags else "snv"
     poisson = "--poisson" in flags or model_type == "indel"
     opts = _summary_options(flags, values, model_type)
+    if opts["calibration"] and "--regions" in values and "--mutations" not in values:
+        raise SystemExit("--calibration_metrics needs labels: --regions alone gives every row the label 0; add --mutations FILE")
+    if opts["fit_calibrator"] is not None and poisson:
+        raise SystemExit("--fit_calibrator fits the raw softmax: it does not go with the Poisson calibration (--poisson; on by default "
+                         "with --indel)")
     if "--model_set" in values or "--scale_factors" in values:
         return _main_model_set(args, values, flags, model_type, poisson, opts)
     if ("--mutations" in values or "--strict_mutations" in flags) and "--regions" not in values:
@@ -118,15 +132,29 @@ def _summary_options(flags, values, model_type="snv"):
             "m_proportion": one("--m_proportion", float), "g_proportion": one("--g_proportion", float),
             "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags,
             "kmers": tuple(int(k) for k in values.get("--kmer_length", [])), "strand": one("--strand", str),
-            "motifs": tuple(int(m) for m in values.get("--motif_length", []))}
+            "motifs": tuple(int(m) for m in values.get("--motif_length", [])), "calibration": "--calibration_metrics" in flags,
+            "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str)}
+    if opts["calibration"] and opts["summary"] is None:
+        raise SystemExit("--calibration_metrics needs --summary PREFIX: the prefix of the file it writes")
+    if (opts["n_bins"] is not None or opts["fit_calibrator"] is not None) and not opts["calibration"]:
+        raise SystemExit("--n_bins / --fit_calibrator go with --calibration_metrics")
+    if opts["n_bins"] is not None and opts["n_bins"] < 1:
+        raise SystemExit("--n_bins must be positive")
+    if opts["fit_calibrator"] is not None:
+        from mural_amd.evaluation import CALIBRATORS
+        if opts["fit_calibrator"] not in CALIBRATORS:
+            raise SystemExit(f"--fit_calibrator {opts['fit_calibrator']}: one of {', '.join(sorted(CALIBRATORS))}")
+        if opts["scale_factor"] is not None:
+            raise SystemExit("--fit_calibrator fits the raw softmax (the reference fits its calibrator before any scaling): it does not go "
+                             "with --scale_factor")
     if opts["windows"] and opts["summary"] is None:
         raise SystemExit("--window_size needs --summary PREFIX: the prefix of the files it writes")
     if opts["kmers"] and opts["summary"] is None:
         raise SystemExit("--kmer_length needs --summary PREFIX: the prefix of the files it writes")
     if opts["motifs"] and opts["summary"] is None:
         raise SystemExit("--motif_length needs --summary PREFIX: the prefix of the files it writes")
-    if opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"]:
-        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length or a --motif_length")
+    if opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"] and not opts["calibration"]:
+        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length or --calibration_metrics")
     if opts["motifs"]:
         from mural_amd.tables import check_motif_length
         try:
@@ -167,6 +195,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
     model, cfg = load_model(model_path, model_type=model_type)
     cal = model_path + ".fdiri_cal.pkl"
     weights = load_dirichlet_weights(cal) if os.path.exists(cal) and "--no-calibration" not in flags else None
+    if opts["fit_calibrator"] is not None and weights is not None:
+        raise SystemExit(f"--fit_calibrator fits the raw softmax, but {cal} would calibrate this run: pass --no-calibration")
     in_forward = opts["scale_factor"] is not None
     chain = dict(poisson=poisson, dirichlet_weights=weights)
     forward = HipShardForward(model, fasta, cfg["local_radius"], cfg.get("local_order", 3), distal_radius=cfg["distal_radius"],
@@ -178,13 +208,20 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
     if opts["wants_summary"]:
         summary = SummarySink(opts["summary"], opts["windows"], opts["benchmark_regions"], kmers=opts["kmers"], genome=forward.genome,
                               kmer_strand=opts["strand"] if model_type == "indel" else None, motifs=opts["motifs"],
-                              motif_indel=model_type == "indel", **sink_chain)
+                              motif_indel=model_type == "indel", calibration=opts["calibration"],
+                              calibration_bins=50 if opts["n_bins"] is None else opts["n_bins"], fit_calibrator=opts["fit_calibrator"],
+                              **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
 
 def _report(n, out, summary, opts):
     print(f"{n} sites -> {out}" if out is not None else f"{n} sites")
+    if summary is not None and opts["calibration"]:
+        res = summary.result()["calibration"]
+        for tag, m in (("", res),) + (((" (after %s)" % opts["fit_calibrator"], res["after"]),) if "after" in res else ()):
+            print("calibration%s - rows: %d, NLL: %.8f, ECE: %.8f, CwECE: %.8f, Brier: %.8f" % (tag, m["rows"], m["nll"], m["ece"], m["c_ece"],
+                                                                                              m["brier"]))
     if summary is not None and opts["genomewide_mu"] is not None:
         summary.scaling_factor(opts["genomewide_mu"], opts["m_proportion"], 1.0 if opts["g_proportion"] is None else opts["g_proportion"])
 
