@@ -339,7 +339,7 @@ def poisson_calibrate(prob):
 
 
 def write_predictions(res, path, poisson=False, dirichlet_weights=None):
-    """The prediction table of run_predict.py:217-239 (see ``mural_amd.predict.write_predictions``, which formats it with the C++ row
+    """The prediction table of run_predict.py:217-239 (see ``mural_amd.sinks.write_predictions``, which formats it with the C++ row
     formatter of csrc/tsv.hip, byte-identical to the reference's pandas writer)."""
-    from ..predict import write_predictions as impl
+    from ..sinks import write_predictions as impl
     return impl(res, path, poisson, dirichlet_weights)

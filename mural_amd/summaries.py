@@ -1,0 +1,1187 @@
+"""Genome summaries reduced in flight from the shards of a file-level prediction: the numpy "host twins" that specify the device
+reductions (csrc/summary.hip, csrc/summary_kmer.hip, csrc/summary_calib.hip) and ``SummarySink``, the shard consumer that runs one
+reducer per summary kind -- window tables and totals, k-mer tables, motif tables, calibration metrics with the calibrator fit."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import _lib
+from .calibration import calibrate_device, dirichlet_calibrate, save_dirichlet_calibrator
+from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
+from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds, shard_name, strand_u8
+from .tables import (check_kmer_length, check_motif_length, kmer_name, kmer_output_names, motif_output_names, mu_scaling_factor,
+                     print_scaling_factor, read_regions, regional_output_names, strand_mode, write_kmer_outputs, write_motif_outputs,
+                     write_regional_outputs)
+
+
+def _refuse_fit_on_calibrated(calibrated):
+    """``SummarySink(fit_calibrator=...)`` fits the raw softmax (MuRaL/training.py:478): refused where the sink or the forward
+    calibrates."""
+    if calibrated:
+        raise ValueError("these probabilities are calibrated already (HipShardForward applied its dirichlet_weights / poisson / "
+                         "scale_factor chain on the device, or the sink was given poisson= / dirichlet_weights=; poisson defaults to on "
+                         "for model_type='indel'): fit_calibrator= fits a calibrator on the raw softmax: drop poisson= / "
+                         "dirichlet_weights= / scale_factor=, or build the forward with poisson=False")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# genome summaries in flight: what calc_scaling_factor and evaluate --window_size read from the written table, reduced from the
+# shards while they are on the device (csrc/summary.hip), so that a summary-only pass needs no table at all
+# ------------------------------------------------------------------------------------------------------------------
+_SUMMARY_STATUS = ((2, "a mut_type outside 0 .. n_class - 1"), (1, "a negative start"),
+                   (4, "rows of a chromosome that do not ascend in start"), (8, "a probability that is NaN, negative or above 1"))
+_LABEL_KIND = {torch.float32: 0, torch.int32: 1, torch.int64: 2}      # `label_kind` of the device entry points, by the label column's dtype
+
+
+def summary_rows_host(prob, start, end, label, n_class, windows, regions=None):
+    """The numpy twin of ``mural_summary_rows`` for the rows of one chromosome (any order): ({W: (bin0, table [bins][1 + 2 n_class])},
+    prob_sum, n_sites, status).  float64, ``np.add.at`` in row order; `regions`: (sorted starts, sorted ends) of the chromosome's
+    benchmark regions or None; status bits as on the device (a negative start 1, a label outside 0 .. n_class - 1 2)."""
+    k = int(n_class)
+    prob = np.asarray(prob)[:, :k].astype(np.float64)
+    start, end, label = np.asarray(start, np.int64), np.asarray(end, np.int64), np.asarray(label)
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= k) | (lab != label)
+    bad_start = start < 0
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0)
+    ok = ~(bad_label | bad_start)
+    prob, start, end, lab = prob[ok], start[ok], end[ok], lab[ok]
+    tables = {}
+    for W in windows:
+        if len(start) == 0:
+            tables[W] = (0, np.zeros((0, 1 + 2 * k)))
+            continue
+        b = start // W
+        bin0 = int(b.min())
+        t = np.zeros((int(b.max()) - bin0 + 1, 1 + 2 * k))
+        np.add.at(t[:, 0], b - bin0, 1.0)
+        np.add.at(t, (b - bin0, 1 + lab), 1.0)
+        for c in range(k):
+            np.add.at(t[:, 1 + k + c], b - bin0, prob[:, c])
+        tables[W] = (bin0, t)
+    if regions is None:
+        w = np.ones(len(start), np.int64)
+    else:
+        w = np.searchsorted(regions[0], end, "left") - np.searchsorted(regions[1], start, "right")
+    total = 0.0
+    for v in (w * prob[:, 1:].sum(axis=1))[w > 0].tolist():
+        total += v
+    return tables, total, int(w[w > 0].sum()), status
+
+
+# ---- k-mer rate tables (csrc/summary_kmer.hip): exact integer sums of the probabilities quantised to 2^-71 -------------------------------
+_KMER_HI_BITS, _KMER_LO_BITS = 31, 40
+_KMER_LO_MASK = np.uint64((1 << _KMER_LO_BITS) - 1)
+_KMER_ORD_SHIFT = 40               # a chromosome's ordinal sits above any 2 * start + 1 (chromosomes shorter than 2^39 bases)
+_KMER_FOLD_ROWS = 1 << 21          # rows between two folds of the lo limbs (the bound of csrc/summary_kmer.hip)
+_KMER_NEVER = np.uint64(2 ** 64 - 1)
+
+
+def _host_genome(genome):
+    """(packed2 uint32[], nmask uint32[], length) of a sequence (str / bytes), a ``PackedGenome`` or such a triple."""
+    if isinstance(genome, (str, bytes)):
+        from .data.genome import pack_sequence
+        return pack_sequence(genome)[:3]
+    if hasattr(genome, "packed2"):
+        return genome.packed2.cpu().numpy().view(np.uint32), genome.nmask.cpu().numpy().view(np.uint32), int(genome.length)
+    packed, nmask, length = genome[:3]
+    return np.asarray(packed).view(np.uint32), np.asarray(nmask).view(np.uint32), int(length)
+
+
+def _window_keys_host(host, s0, s1, k):
+    """(fwd, rev) int64 of the Python slices chrom[s0:s1] (csrc/kmer_key.h: kmer_window_decode): -1 where a slice is not k bases of
+    A/C/G/T.  `host`: ``_host_genome``'s triple."""
+    packed, nmask, L = host
+    lo = np.where(s0 < 0, np.maximum(L + s0, 0), np.minimum(s0, L))
+    hi = np.where(s1 < 0, np.maximum(L + s1, 0), np.minimum(s1, L))
+    ok = hi - lo == k
+    fwd, rev = np.zeros(len(s0), np.int64), np.zeros(len(s0), np.int64)
+    base = np.where(ok, lo, 0)
+    for j in range(k):
+        q = np.minimum(base + j, max(L - 1, 0))
+        if L == 0:
+            break
+        ok &= ((nmask[q >> 5] >> (q & 31).astype(np.uint32)) & 1) == 0
+        code = ((packed[q >> 4] >> (2 * (q & 15)).astype(np.uint32)) & 3).astype(np.int64)
+        fwd = fwd * 4 + code
+        rev += (3 - code) << (2 * j)
+    return np.where(ok, fwd, -1), np.where(ok, rev, -1)
+
+
+def kmer_keys_host(genome, start, end, strand, k, indel=False, mode=0):
+    """The numpy twin of ``mural_table_kmer_keys`` (csrc/kmer_key.h): (key_a, key_b) int64, -1 where the Python slice
+    chrom[start - k/2 (+1 indel) : end + k/2] is not k bases of A/C/G/T; key_a follows the strand mode (0 the rows' strand, 1 '+', 2 '-'),
+    in mode 3 key_a is the forward key and key_b its reverse complement (otherwise key_b is all -1)."""
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    fwd, rev = _window_keys_host(_host_genome(genome), start - k // 2 + (1 if indel else 0), end + k // 2, k)
+    none = np.full(len(start), -1, np.int64)
+    if mode == 3:
+        return fwd, rev
+    minus = np.ones(len(start), bool) if mode == 2 else (np.asarray(strand) != 0 if mode == 0 else np.zeros(len(start), bool))
+    return np.where(minus, rev, fwd), none
+
+
+def kmer_quantise(prob):
+    """(hi, lo, bad) of float probabilities: q = rne(p * 2^71) as hi = floor(p * 2^31), lo = rint((p * 2^31 - hi) * 2^40) (uint64; every
+    step exact in float64, float32 widened first); bad: NaN, negative or above 1 (hi = lo = 0 there)."""
+    p = np.asarray(prob).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        bad = ~((p >= 0.0) & (p <= 1.0))
+    p = np.where(bad, 0.0, p)
+    s = p * float(1 << _KMER_HI_BITS)
+    h = np.floor(s)
+    return h.astype(np.uint64), np.rint((s - h) * float(1 << _KMER_LO_BITS)).astype(np.uint64), bad
+
+
+def _kmer_fold(table):
+    """Carry the lo limbs' overflow into hi: table [groups][3][n_class] uint64, in place."""
+    carry = table[:, 2] >> np.uint64(_KMER_LO_BITS)
+    table[:, 1] += carry
+    table[:, 2] &= _KMER_LO_MASK
+    return table
+
+
+def _kmer_row_checks(prob, start, label, nc):
+    """(hi, lo, integer labels, rows that count, status bits) of the rows of a k-mer or motif summary."""
+    label = np.asarray(label)
+    hi, lo, bad_p = kmer_quantise(np.asarray(prob)[:, :nc])
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= nc) | (lab != label)
+    bad_start, bad_prob = start < 0, bad_p.any(axis=1)
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    return hi, lo, lab, ~(bad_label | bad_start | bad_prob), status
+
+
+def summary_kmer_host(genome, prob, start, end, strand, label, n_class, kmers, indel=False, mode=0, order_base=0, into=None):
+    """The numpy twin of ``mural_summary_kmer_rows`` -- and its specification -- for rows (any order) of one chromosome:
+    ({k: (table uint64 [4^k][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^k])}, status).  `genome`: the
+    chromosome as a sequence, a ``PackedGenome`` or (packed2, nmask, length); `into`: tables of earlier parts to add to (in place).  Status
+    bits as on the device (1 a negative start, 2 a label outside 0 .. n_class - 1, 8 a probability that is NaN, negative or above 1);
+    such rows are skipped in every table."""
+    nc = int(n_class)
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    hi, lo, lab, ok, status = _kmer_row_checks(prob, start, label, nc)
+    strand = np.zeros(len(start), np.uint8) if strand is None else strand_u8(strand)
+    hi, lo, start, end, lab, strand = hi[ok], lo[ok], start[ok], end[ok], lab[ok], np.asarray(strand)[ok]
+    if len(start) and int(start.max()) >= 1 << (_KMER_ORD_SHIFT - 1):
+        raise ValueError("k-mer summary: a start at or above 2^39")
+    host = _host_genome(genome)
+    out = {} if into is None else into
+    cls = np.arange(nc)
+    for k in kmers:
+        table, first = out.get(k) or (np.zeros((4 ** k, 3, nc), np.uint64), np.full(4 ** k, _KMER_NEVER, np.uint64))
+        for r0 in range(0, len(start), _KMER_FOLD_ROWS):
+            r = slice(r0, r0 + _KMER_FOLD_ROWS)
+            for sub, key in enumerate(kmer_keys_host(host, start[r], end[r], strand[r], k, indel, mode)):
+                live = key >= 0
+                kk = key[live]
+                np.add.at(table[:, 0], (kk, lab[r][live]), np.uint64(1))
+                np.add.at(table[:, 1], (kk[:, None], cls[None, :]), hi[r][live])
+                np.add.at(table[:, 2], (kk[:, None], cls[None, :]), lo[r][live])
+                np.minimum.at(first, kk, (np.uint64(order_base) + (2 * start[r][live] + sub).astype(np.uint64)))
+            _kmer_fold(table)
+        out[k] = (table, first)
+    return out, status
+
+
+def kmer_table_from_sums(table, first, k, n_class):
+    """(k-mer names, table [groups][1 + 2 n_class] of rows / per-class counts / per-class probability sums) -- ``tables.kmer_table``'s
+    pair -- from the integer sums: the keys with a row, by first appearance; a probability sum is (hi * 2^40 + lo) / 2^71, formed from
+    Python integers (true division rounds correctly)."""
+    nc = int(n_class)
+    live = np.nonzero(table[:, 0].sum(axis=1) > 0)[0]
+    order = live[np.argsort(first[live], kind="stable")]
+    out = np.zeros((len(order), 1 + 2 * nc))
+    out[:, 1:1 + nc] = table[order, 0]
+    out[:, 0] = table[order, 0].sum(axis=1)
+    den = 1 << (_KMER_HI_BITS + _KMER_LO_BITS)
+    hi, lo = table[order, 1].tolist(), table[order, 2].tolist()
+    for j in range(len(order)):
+        out[j, 1 + nc:] = [((h << _KMER_LO_BITS) + l) / den for h, l in zip(hi[j], lo[j])]
+    return [kmer_name(int(g), k) for g in order], out
+
+
+def _kmer_collapse(tables, firsts, shift=_KMER_ORD_SHIFT):
+    """({k: table}, {chromosome: {k: first}}) -> (names ascending, {k: (table, first)}): a k-mer's first appearance over the chromosomes
+    in ascending name order -- the order of the written table -- with the chromosome's ordinal above the word."""
+    names = sorted(firsts)
+    out = {}
+    for k, table in tables.items():
+        first = np.full(table.shape[0], _KMER_NEVER, np.uint64)
+        for ordinal, nm in enumerate(names):
+            f = firsts[nm][k]
+            np.minimum(first, np.where(f != _KMER_NEVER, f | np.uint64(ordinal << shift), _KMER_NEVER), out=first)
+        out[k] = (table, first)
+    return names, out
+
+
+def _kmer_merge(states, shift=_KMER_ORD_SHIFT):
+    """[(chromosome names ascending, {k: (table, first)})] of the ranks (or of a rank's devices and its host rows) -> one such pair:
+    tables added, first-appearance words min-merged after the ordinals are reconciled by name (every list ascends, so renumbering it to
+    the merged list keeps the order it was collapsed under)."""
+    tables = {}
+    names = sorted({nm for their_names, _ in states for nm in their_names})
+    low = np.uint64((1 << shift) - 1)
+    for their_names, their in states:
+        remap = np.array([names.index(nm) for nm in their_names] + [0], np.uint64)
+        for k, (table, first) in their.items():
+            seen = first != _KMER_NEVER
+            moved = first.copy()
+            moved[seen] = (remap[(first[seen] >> np.uint64(shift)).astype(np.int64)] << np.uint64(shift)) | (first[seen] & low)
+            if k not in tables:
+                tables[k] = (table.copy(), moved)
+            else:
+                tables[k][0][...] += table
+                np.minimum(tables[k][1], moved, out=tables[k][1])
+                _kmer_fold(tables[k][0])
+    return names, tables
+
+
+# ---- motif rate tables (csrc/summary_kmer.hip: mural_summary_motif_rows): the k-mer cells under the key rule of `evaluate --motif_only` ----
+_MOTIF_POS_SHIFT = 5               # first-appearance word: (order_base + pos) << 5 | window i << 1 | orientation
+_MOTIF_ORD_SHIFT = 44              # a chromosome's ordinal sits above any such word of a start below 2^39
+_MOTIF_FOLD_ROWS = 1 << 18         # rows between two folds: a row adds up to m <= 15 times to one cell
+
+
+def summary_motif_host(genome, prob, start, end, label, n_class, motifs, indel=False, order_base=0, into=None, order_by_row=False):
+    """The numpy twin of ``mural_summary_motif_rows`` -- and its specification -- for rows (any order) of one chromosome:
+    ({m: (table uint64 [4^m][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^m])}, status).  A row adds to every
+    window of m bases that holds its site, on the reference strand: the Python slices chrom[start - i : end + m-1 - i], i = 0 .. m-1, of
+    an SNV row, chrom[start - i + 1 : end + m - i], i = 1 .. m-1, of an INDEL row, those that are m bases of A/C/G/T.  A motif and its
+    reverse complement share the cell of the smaller key; first = min of (order_base + pos) << 5 | i << 1 | o over the windows, pos the
+    row's start (its index among the rows given with `order_by_row`), o = 1 where the window's own key is the larger of the two.
+    `genome`, `into` and the status bits as ``summary_kmer_host``."""
+    nc = int(n_class)
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    hi, lo, lab, ok, status = _kmer_row_checks(prob, start, label, nc)
+    pos = np.arange(len(start), dtype=np.int64) if order_by_row else start
+    hi, lo, start, end, lab, pos = hi[ok], lo[ok], start[ok], end[ok], lab[ok], pos[ok]
+    if len(start) and int(pos.max()) + int(order_base) >= 1 << 58:
+        raise ValueError("motif summary: a row order at or above 2^58")
+    host = _host_genome(genome)
+    out = {} if into is None else into
+    cls = np.arange(nc)
+    for m in motifs:
+        m = check_motif_length(m, device=True)
+        table, first = out.get(m) or (np.zeros((4 ** m, 3, nc), np.uint64), np.full(4 ** m, _KMER_NEVER, np.uint64))
+        for r0 in range(0, len(start), _MOTIF_FOLD_ROWS):
+            r = slice(r0, r0 + _MOTIF_FOLD_ROWS)
+            word = (np.uint64(order_base) + pos[r].astype(np.uint64)) << np.uint64(_MOTIF_POS_SHIFT)
+            for w in range(m - (1 if indel else 0)):           # the reference's i = w + indel
+                fwd, rev = _window_keys_host(host, start[r] - w, end[r] + (m - 1 - w), m)
+                live = fwd >= 0
+                kk = np.minimum(fwd, rev)[live]
+                np.add.at(table[:, 0], (kk, lab[r][live]), np.uint64(1))
+                np.add.at(table[:, 1], (kk[:, None], cls[None, :]), hi[r][live])
+                np.add.at(table[:, 2], (kk[:, None], cls[None, :]), lo[r][live])
+                np.minimum.at(first, kk, word[live] | np.uint64((w + (1 if indel else 0)) << 1) | (fwd > rev)[live].astype(np.uint64))
+            _kmer_fold(table)
+        out[m] = (table, first)
+    return out, status
+
+
+def motif_table_from_sums(table, first, m, n_class):
+    """(motif names, table [entries][1 + 2 n_class] of windows / per-class counts / per-class probability sums) -- ``tables.motif_table``'s
+    pair -- from the merged integer tables: the keys with a window, by first appearance; an entry is named after the orientation of its
+    first window (the lowest bit of its word: 1 the reverse complement of the smaller key).  Sums as ``kmer_table_from_sums``."""
+    names, out = kmer_table_from_sums(table, first, m, n_class)
+    live = np.nonzero(table[:, 0].sum(axis=1) > 0)[0]
+    order = live[np.argsort(first[live], kind="stable")]
+    flip = (first[order] & np.uint64(1)).astype(bool)
+    top = 4 ** m - 1
+    return [kmer_name(top - _revdigits(int(g), m) if f else int(g), m) for g, f in zip(order, flip)], out
+
+
+def _revdigits(key, m):
+    """The base-4 digits of a key in reverse order (4^m - 1 - that is the key of the reverse complement)."""
+    out = 0
+    for _ in range(m):
+        out, key = out * 4 + (key & 3), key >> 2
+    return out
+
+
+# ---- loss and calibration metrics (csrc/summary_calib.hip: mural_summary_calib_rows): integer sums behind NLL / ECE / CwECE / Brier ----
+# Scaling of the two-limb sums: a term v >= 0 is quantised once to rne(v * 2^(S + 46)), hi = floor(v * 2^S), lo = rint((v * 2^S - hi) *
+# 2^46), every step exact in float64; S = 16 for the scores (in [0, 1]) and the Brier terms (in [0, 2]) -- a row's error at most 2^-63
+# --, S = 13 for the NLL terms (below 2^10: -log of the smallest positive double is 744.5) -- at most 2^-60.  A folded pair has
+# lo < 2^46; hi grows by at most 2^23 a row plus the carries, so 2^40 rows stay below 2^64.
+_CALIB_LO_BITS, _CALIB_SCORE_BITS, _CALIB_NLL_BITS = 46, 16, 13
+_CALIB_LO_MASK = np.uint64((1 << _CALIB_LO_BITS) - 1)
+_CALIB_FOLD_ROWS = 1 << 17         # rows between two folds here: lo < 2^46 + 2^17 * 2^46 < 2^64
+_CALIB_MAX_CELLS = 4096            # the table a workgroup of csrc/summary_calib.hip holds
+
+
+def calib_cells(n_class, n_bins):
+    """Cells of the table of ``mural_summary_calib_rows``: 6 + n_class header cells and 4 per bin of the n_class + 1 groups."""
+    return 6 + int(n_class) + 4 * int(n_bins) * (int(n_class) + 1)
+
+
+def calib_bounds(n_bins):
+    """The reference's bin bounds: float32 ``torch.linspace(0, 1, n_bins + 1)`` (evaluation.py:218)."""
+    return torch.linspace(0, 1, int(n_bins) + 1).numpy()
+
+
+def _calib_lo_cells(n_class, n_bins):
+    h = 6 + n_class
+    return np.r_[3 + n_class, 5 + n_class, h + 2 + 4 * np.arange(n_bins * (n_class + 1))].astype(np.int64)
+
+
+def _calib_fold(table, n_class, n_bins):
+    """Carry the lo limbs' overflow into the hi limbs in front of them: table uint64 [cells], in place."""
+    lo = _calib_lo_cells(n_class, n_bins)
+    table[lo - 1] += table[lo] >> np.uint64(_CALIB_LO_BITS)
+    table[lo] &= _CALIB_LO_MASK
+    return table
+
+
+def _calib_quantise(v, bits):
+    """(hi, lo) uint64 of float64 terms v >= 0 (the rule above)."""
+    v = np.where(v > 0.0, v, 0.0)
+    s = v * float(1 << bits)
+    h = np.floor(s)
+    return h.astype(np.uint64), np.rint((s - h) * float(1 << _CALIB_LO_BITS)).astype(np.uint64)
+
+
+def summary_calib_host(prob, label, n_class, n_bins=50, bounds=None, into=None):
+    """The numpy twin of ``mural_summary_calib_rows`` -- and its specification -- for rows in any order: (table uint64 [6 + n_class +
+    4 n_bins (n_class + 1)], status).  Per row, in the probabilities' own precision (float32 or float64; anything else is taken as
+    float32): q = softmax(log(prob)), summed over the classes in ascending order; confidence = max q, the prediction its first maximum;
+    Brier term = sum_c ([c == label] - q_c)^2, the squares widened to float64 and added in class order; NLL term = -log q_label; bins
+    (lower, upper] on `bounds` (default ``calib_bounds(n_bins)``), compared in float64.  Cells, H = 6 + n_class:
+      [0] rows  [1] inf_rows  [2 + c] rows with label c  [2 + nc], [3 + nc] NLL hi, lo  [4 + nc], [5 + nc] Brier hi, lo
+      [H + 4 (g n_bins + b) + 0 .. 3] rows, score hi, score lo, hits of bin b of group g: g = 0 the top-label bins (score = confidence,
+      hit = the prediction is the label), g = 1 + c class c (score = q_c, hit = the label is c); a score in no bin (0) adds nowhere.
+    The real-valued sums are the two-limb integers described above this function, so the table depends on the SET of valid rows alone,
+    bit for bit.  `into`: the table of earlier parts to add to (in place).  Status bits as on the device: 2 a label outside
+    0 .. n_class - 1 (or no whole number), 8 a probability that is NaN, negative or above 1 -- or a row without a positive probability,
+    whose softmax is undefined; such rows are skipped everywhere.  A valid row with q_label == 0 counts in inf_rows and everywhere but
+    the NLL sum.
+
+    Device and twin agree EXACTLY in what no transcendental's last bit decides: rows, label counts, status, inf_rows for exact zeros.
+    The score sums and the bin a score falls in go through ``log`` and ``exp`` of two math libraries: they are compared through the
+    derived metrics (``calib_metrics_from_sums``), not bit for bit."""
+    nc, nb = int(n_class), int(n_bins)
+    prob = np.asarray(prob)[:, :nc]
+    if prob.dtype not in (np.float32, np.float64):
+        prob = prob.astype(np.float32)
+    P = prob.dtype.type
+    bounds = (calib_bounds(nb) if bounds is None else np.asarray(bounds, np.float32)).astype(np.float64)
+    if len(bounds) != nb + 1:
+        raise ValueError(f"{nb} bins need {nb + 1} bounds")
+    table = np.zeros(calib_cells(nc, nb), np.uint64) if into is None else into
+    label = np.asarray(label)
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= nc) | (lab != label)
+    with np.errstate(invalid="ignore"):
+        bad_prob = ~((prob >= 0) & (prob <= 1)).all(axis=1) | ~(prob > 0).any(axis=1)
+    status = (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    ok = ~(bad_label | bad_prob)
+    prob, lab = prob[ok], lab[ok]
+    H = 6 + nc
+    for r0 in range(0, len(lab), _CALIB_FOLD_ROWS):
+        p, y = prob[r0:r0 + _CALIB_FOLD_ROWS], lab[r0:r0 + _CALIB_FOLD_ROWS]
+        rows = np.arange(len(y))
+        with np.errstate(divide="ignore"):
+            lg = np.log(p)
+        e = np.exp(lg - lg.max(axis=1, keepdims=True))
+        s = np.zeros(len(y), P)
+        for c in range(nc):
+            s = s + e[:, c]
+        q = e / s[:, None]
+        conf, arg = q.max(axis=1), q.argmax(axis=1)
+        brier = np.zeros(len(y))
+        for c in range(nc):
+            d = (y == c).astype(P) - q[:, c]
+            brier = brier + (d * d).astype(np.float64)
+        q_lab = q[rows, y]
+        inf = ~(q_lab > 0)
+        table[0] += np.uint64(len(y))
+        table[1] += np.uint64(int(inf.sum()))
+        table[2:2 + nc] += np.bincount(y, minlength=nc).astype(np.uint64)
+        hi, lo = _calib_quantise(-np.log(q_lab[~inf]).astype(np.float64), _CALIB_NLL_BITS)
+        table[2 + nc] += hi.sum(dtype=np.uint64)
+        table[3 + nc] += lo.sum(dtype=np.uint64)
+        hi, lo = _calib_quantise(brier, _CALIB_SCORE_BITS)
+        table[4 + nc] += hi.sum(dtype=np.uint64)
+        table[5 + nc] += lo.sum(dtype=np.uint64)
+        for g in range(nc + 1):
+            v = (conf if g == 0 else q[:, g - 1]).astype(np.float64)
+            hit = (arg == y) if g == 0 else (y == g - 1)
+            b = np.searchsorted(bounds, v, side="left") - 1      # bounds[b] < v <= bounds[b + 1]
+            live = (b >= 0) & (b < nb)
+            cell = H + 4 * (g * nb + b[live])
+            hi, lo = _calib_quantise(v[live], _CALIB_SCORE_BITS)
+            np.add.at(table, cell, np.uint64(1))
+            np.add.at(table, cell + 1, hi)
+            np.add.at(table, cell + 2, lo)
+            np.add.at(table, cell + 3, hit[live].astype(np.uint64))
+        _calib_fold(table, nc, nb)
+    return table, status
+
+
+def calib_rows_device(prob, label, n_class, n_bins, bounds, table, status):
+    """One call of ``mural_summary_calib_rows`` on the current stream of `prob`'s device: prob (n, >= n_class) float32 / float64 with unit
+    column stride, label (n,) float32 / int32 / int64, bounds float32 [n_bins + 1], table int64 [calib_cells] and status int32 [1] -- all
+    device tensors; table and status are added to."""
+    s = _lib.MuralSummaryCalibRows()
+    s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0) if prob.shape[0] > 1 else prob.shape[1]
+    s.label, s.label_kind = label.data_ptr(), _LABEL_KIND[label.dtype]
+    s.n, s.n_class, s.n_bins = prob.shape[0], int(n_class), int(n_bins)
+    s.bounds, s.table, s.status = bounds.data_ptr(), table.data_ptr(), status.data_ptr()
+    with torch.cuda.device(prob.device):
+        _lib.check(_lib.lib().mural_summary_calib_rows(C.byref(s), _lib.current_stream_ptr(prob.device)))
+
+
+def calib_metrics_from_sums(tables, n_bins, n_class):
+    """{"rows", "nll", "ece", "c_ece", "brier", "label_counts"} from the integer table of ``summary_calib_host`` /
+    ``mural_summary_calib_rows``, formed from Python integers (true division rounds correctly): nll = NLL sum / rows (inf where a row
+    had q_label == 0, as the reference's mean would be), brier = Brier sum / rows, ece = sum over the top-label bins of
+    |score sum / rows_b - hits_b / rows_b| * rows_b / rows -- which is |score sum - hits_b| / rows, summed exactly --, c_ece the mean of
+    the same over the bins of class c for c < (the highest label seen) + 1: the reference's ClasswiseECELoss sizes itself by
+    max(labels) + 1.  NaN where there is no row."""
+    nc, nb = int(n_class), int(n_bins)
+    t = np.asarray(tables).astype(np.uint64).tolist()
+    rows, inf_rows, counts = t[0], t[1], t[2:2 + nc]
+    out = {"rows": rows, "label_counts": counts}
+    if rows == 0:
+        return dict(out, nll=float("nan"), ece=float("nan"), c_ece=float("nan"), brier=float("nan"))
+    pair = lambda at: (t[at] << _CALIB_LO_BITS) + t[at + 1]      # noqa: E731
+    one = 1 << (_CALIB_SCORE_BITS + _CALIB_LO_BITS)
+    H = 6 + nc
+
+    def gap(g):
+        """sum over the bins of group g of |score sum - hits|, in units of 2^-62"""
+        return sum(abs(pair(at + 1) - t[at + 3] * one) for at in range(H + 4 * g * nb, H + 4 * (g + 1) * nb, 4) if t[at])
+
+    n_seen = max(c for c in range(nc) if counts[c]) + 1
+    out["nll"] = float("inf") if inf_rows else pair(2 + nc) / (rows << (_CALIB_NLL_BITS + _CALIB_LO_BITS))
+    out["brier"] = pair(4 + nc) / (rows * one)
+    out["ece"] = gap(0) / (rows * one)
+    out["c_ece"] = sum(gap(1 + c) for c in range(n_seen)) / (n_seen * rows * one)
+    return out
+
+
+def _merge_window_table(have, bin0, table):
+    """(bin0, table) of a chromosome's windows so far + one part's: the covering table, the part added behind what was there."""
+    if have is None or have[1].shape[0] == 0:
+        return bin0, table.copy()
+    if table.shape[0] == 0:
+        return have
+    b0, t = have
+    lo, hi = min(b0, bin0), max(b0 + t.shape[0], bin0 + table.shape[0])
+    if lo != b0 or hi != b0 + t.shape[0]:
+        grown = np.zeros((hi - lo, t.shape[1]))
+        grown[b0 - lo:b0 - lo + t.shape[0]] = t
+        b0, t = lo, grown
+    t[bin0 - b0:bin0 - b0 + table.shape[0]] += table
+    return b0, t
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# One reducer per summary kind, and SummarySink over them.  A reducer is a plain class with a `name` (its key in a rank's state) and
+#   host_part / device_part(name, prob, start, end, strand, label, k)   reduce a part of host rows -> status bits / enqueue the same for
+#                                                   device columns -> what must outlive the part.  The columns are calibrated and ascend in
+#                                                   start; `strand` is None unless k-mers are reduced
+#   read_back(k) -> (state, status bits)            once, at close(): the picklable state of this rank
+#   merge(states, k) -> state                       the ranks' states, in rank order
+#   finish(state, k, result)                        the entries of result() (and the reducer's own sums)
+#   write(out_prefix, result, k, written)           the files; a path goes to `written` before it is created
+#   reset()                                         drop everything (abort())
+# ------------------------------------------------------------------------------------------------------------------
+def _calls_of(items):
+    """`items` in the groups of 4 (MURAL_SUMMARY_MAX_WINDOWS, MURAL_SUMMARY_MAX_KMERS) that one call of an entry point takes; one call
+    even for none (the totals of the window reduction)."""
+    return [items[at:at + 4] for at in range(0, max(len(items), 1), 4)]
+
+
+def _row_fields(s, prob, start, end, label):
+    """The fields every ``MuralSummary*Rows`` struct has for the rows of a part (device tensors)."""
+    s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0)
+    s.start, s.end, s.label, s.label_kind = start.data_ptr(), end.data_ptr(), label.data_ptr(), _LABEL_KIND[label.dtype]
+    s.n = start.shape[0]
+
+
+class _WindowReducer:
+    """The window tables per chromosome and window size, prob_sum and n_sites (counted per overlapping benchmark region where there are
+    regions).  A device part is reduced one part late: its first and last start size its tables, and they are read back while the next
+    part is computed.  The tables are float64 sums: parts are added in arrival order, ranks in rank order."""
+    name = "windows"
+
+    def __init__(self, sizes, benchmark_regions, ratio_cutoff):
+        self.sizes = tuple(int(w) for w in sizes)
+        if any(w <= 0 for w in self.sizes) or len(set(self.sizes)) != len(self.sizes):
+            raise ValueError(f"window sizes must be positive and distinct (got {self.sizes})")
+        if isinstance(benchmark_regions, (str, os.PathLike)):
+            benchmark_regions = read_regions(benchmark_regions)
+        self.regions = None if benchmark_regions is None else {
+            c: (np.sort(np.asarray(a, np.int64)), np.sort(np.asarray(b, np.int64))) for c, (a, b) in benchmark_regions.items()}
+        self.ratio_cutoff = ratio_cutoff
+        self.reset()
+
+    def reset(self):
+        self.tables = {}               # chromosome -> {W: (bin0, table)}
+        self.prob_sum, self.n_sites, self.status = 0.0, 0, 0
+        self.pending = None            # a staged device part: reduced when the next one arrives (or at close)
+        self.inflight = []             # [(event, pinned result, chromosome, n_class, [(W, bin0, bins, offset)])] of launched parts
+        self.dev_regions = {}
+
+    def _take(self, name, tables, total, n_sites):
+        mine = self.tables.setdefault(name, {})
+        for W, (bin0, t) in tables.items():
+            mine[W] = _merge_window_table(mine.get(W), bin0, t)
+        self.prob_sum += total
+        self.n_sites += n_sites
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        regs = None if self.regions is None else self.regions.get(name, (np.zeros(0, np.int64),) * 2)
+        *sums, status = summary_rows_host(prob, start, end, label, k, self.sizes, regs)
+        self._take(name, *sums)
+        return status
+
+    def device_part(self, name, prob, start, end, strand, label, k, held=None):
+        """Stage the part -- the read-back of its first and last start goes behind what the other reducers enqueued for it -- and launch
+        the part staged before it, complete by now.  The staged part keeps its columns and `held` (the packed genome of the keyed
+        reductions) alive until its own reduction has run."""
+        staged = None
+        if start.shape[0]:
+            dev = prob.device
+            with torch.cuda.device(dev):
+                ends = torch.empty(2, dtype=torch.int64).pin_memory()
+                ends.copy_(torch.stack([start[0], start[-1]]), non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+            staged = dict(name=name, prob=prob, start=start, end=end, label=label, k=k, ends=ends, event=ev, dev=dev, strand=strand,
+                          genome=held)
+        self._launch_pending()
+        self.pending = staged
+
+    def _launch_pending(self):
+        """Reduce the staged part: its first and last start (read back by now) size the part's window tables."""
+        p, self.pending = self.pending, None
+        if p is None:
+            return
+        lib = _lib.lib()
+        p["event"].synchronize()
+        self._harvest(done_only=True)                      # (every part launched before is complete by now: same stream)
+        dev, k, n = p["dev"], p["k"], p["start"].shape[0]
+        lo = max(int(p["ends"][0]), 0)
+        hi = max(int(p["ends"][1]), lo)
+        stride = 1 + 2 * k
+        layout, off = [], 3
+        for W in self.sizes:
+            bin0, bins = lo // W, hi // W - lo // W + 1
+            if bins * stride >= 2 ** 31:
+                raise ValueError(f"the rows of one part span {bins} windows of {W} bp: too many for one table")
+            layout.append((W, bin0, bins, off))
+            off += bins * stride
+        with torch.cuda.device(dev):
+            out = torch.zeros(off, dtype=torch.float64, device=dev)      # total | n_sites (int64) | status (int32) | the tables
+            regs = None
+            if self.regions is not None:
+                regs = self.dev_regions.get((p["name"], dev))
+                if regs is None:
+                    b0, b1 = self.regions.get(p["name"], (np.zeros(0, np.int64),) * 2)
+                    regs = (torch.from_numpy(np.r_[b0, 0]).to(dev), torch.from_numpy(np.r_[b1, 0]).to(dev), len(b0))
+                    self.dev_regions = {(p["name"], dev): regs}
+            stream = _lib.current_stream_ptr(dev)
+            for g, group in enumerate(_calls_of(layout)):      # the totals (and the benchmark regions) go with the first call
+                s = _lib.MuralSummaryRows()
+                _row_fields(s, p["prob"], p["start"], p["end"], p["label"])
+                s.n_class, s.n_windows = k, len(group)
+                for j, (W, bin0, bins, o) in enumerate(group):
+                    s.window[j], s.bin0[j], s.n_bins[j], s.table[j] = W, bin0, bins, out[o:].data_ptr()
+                if regs is not None and g == 0:
+                    s.reg_b0, s.reg_b1, s.n_reg = regs[0].data_ptr(), regs[1].data_ptr(), regs[2]
+                # the totals of a later group of window sizes go to a scratch cell: they are counted once
+                tot = out if g == 0 else torch.zeros(2, dtype=torch.float64, device=dev)
+                s.total, s.n_sites, s.status = tot.data_ptr(), tot[1:].data_ptr(), out[2:].data_ptr()
+                ws = torch.empty(int(lib.mural_summary_workspace_bytes(n, k, len(group))) // 8 + 1, dtype=torch.int64, device=dev)
+                _lib.check(lib.mural_summary_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, stream))
+            host = torch.empty(off, dtype=torch.float64).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.inflight.append((ev, host, p["name"], k, layout))
+
+    def _harvest(self, done_only=False):
+        keep = []
+        for item in self.inflight:
+            ev, host, name, k, layout = item
+            if done_only and (keep or not ev.query()):      # (in arrival order: nothing overtakes an unfinished part)
+                keep.append(item)
+                continue
+            ev.synchronize()
+            a = host.numpy()
+            stride = 1 + 2 * k
+            tables = {W: (bin0, a[o:o + bins * stride].reshape(bins, stride)) for W, bin0, bins, o in layout}
+            self._take(name, tables, float(a[0]), int(a[1:2].view(np.int64)[0]))
+            self.status |= int(a[2:3].view(np.int32)[0])
+        self.inflight = keep
+
+    def read_back(self, k):
+        self._launch_pending()
+        self._harvest()
+        return (self.tables, self.prob_sum, self.n_sites), self.status
+
+    def merge(self, states, k):
+        tables, prob_sum, n_sites = {}, 0.0, 0
+        for t, s, c in states:
+            for name, per_w in t.items():
+                mine = tables.setdefault(name, {})
+                for W, (bin0, tab) in per_w.items():
+                    mine[W] = _merge_window_table(mine.get(W), bin0, tab)
+            prob_sum, n_sites = prob_sum + s, n_sites + c
+        return tables, prob_sum, n_sites
+
+    def finish(self, state, k, result):
+        tables, prob_sum, n_sites = state
+        windows = {}
+        for W in self.sizes:
+            keys, rows = [], []
+            for name in sorted(tables):
+                bin0, t = tables[name].get(W, (0, np.zeros((0, 1))))
+                live = np.nonzero(t[:, 0] > 0)[0]
+                keys += [(name, int((bin0 + g) * W + W)) for g in live]
+                rows.append(t[live])
+            windows[W] = (keys, np.concatenate(rows) if rows else np.zeros((0, 1 + 2 * (k or 0))))
+        result.update(prob_sum=prob_sum, n_sites=n_sites, windows=windows)
+
+    def write(self, out_prefix, result, k, written):
+        for W in self.sizes:
+            written += list(regional_output_names(out_prefix, W)[:2])
+            write_regional_outputs(*result["windows"][W], k, W, out_prefix, self.ratio_cutoff)
+
+
+def _kmer_part_host(genome, prob, start, end, strand, label, k, lengths, fields, into):
+    return summary_kmer_host(genome, prob, start, end, strand, label, k, lengths, bool(fields["indel"]), fields["mode"], into=into)
+
+
+def _motif_part_host(genome, prob, start, end, strand, label, k, lengths, fields, into):
+    return summary_motif_host(genome, prob, start, end, label, k, lengths, bool(fields["indel"]), into=into)
+
+
+# what tells the k-mer reduction from the motif reduction (`fields`, the struct's own settings, come from the sink)
+_KMERS = dict(name="kmers", what="k-mer", check=check_kmer_length, struct=_lib.MuralSummaryKmerRows, entry="mural_summary_kmer_rows",
+              count="n_k", length="k", strand=True, host=_kmer_part_host, shift=_KMER_ORD_SHIFT, from_sums=kmer_table_from_sums,
+              output_names=kmer_output_names, write=write_kmer_outputs)
+_MOTIFS = dict(name="motifs", what="motif", check=check_motif_length, struct=_lib.MuralSummaryMotifRows, entry="mural_summary_motif_rows",
+               count="n_m", length="m", strand=False, host=_motif_part_host, shift=_MOTIF_ORD_SHIFT, from_sums=motif_table_from_sums,
+               output_names=motif_output_names, write=write_motif_outputs)
+
+
+class _KeyedReducer:
+    """The rate tables keyed by a sequence word around the site, for each of `lengths`: the k-mer tables (`kind` = _KMERS) or the motif
+    tables (_MOTIFS).  Exact integer sums in accumulators of a fixed size -- the tables per length, the first-appearance words per
+    chromosome and length (two chromosomes share words, and their order, by name as in the written table, is known only when all have
+    arrived) --, on the host and per device, read back once."""
+
+    def __init__(self, kind, lengths, genome):
+        self.kind, self.name = kind, kind["name"]
+        self.lengths = tuple(kind["check"](n) for n in lengths)
+        if len(set(self.lengths)) != len(self.lengths):
+            raise ValueError(f"{kind['what']} lengths must be distinct (got {self.lengths})")
+        if self.lengths and genome is None:
+            raise ValueError(f"SummarySink({self.name}=...) needs genome=: a callable chromosome name -> packed genome")
+        self.genome = genome
+        self.fields = {}               # the struct's settings beside rows and tables (indel, mode / order_by_row): the sink's to set
+        self.reset()
+
+    def reset(self):
+        self.host = ({}, {})           # ({length: table}, {chromosome: {length: first}}) of the host shards
+        self.dev = {}                  # device -> ({length: table}, {chromosome: {length: first}}, status)
+        self.sums = None
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        tabs, firsts = self.host
+        for n in self.lengths:
+            tabs.setdefault(n, np.zeros((4 ** n, 3, k), np.uint64))
+        mine = firsts.setdefault(name, {n: np.full(4 ** n, _KMER_NEVER, np.uint64) for n in self.lengths})
+        _, status = self.kind["host"](self.genome(name), prob, start, end, strand, label, k, self.lengths, self.fields,
+                                      {n: (tabs[n], mine[n]) for n in self.lengths})
+        return status
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the reduction of a part behind its forward: the part's chromosome is the resident one now."""
+        kind, dev = self.kind, prob.device
+        genome = self.genome(name)
+        if genome.length >= 1 << (_KMER_ORD_SHIFT - 1):
+            raise ValueError(f"{kind['what']} summary: chromosome {name} has 2^39 bases or more")
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = ({n: torch.zeros(4 ** n * 3 * k, dtype=torch.int64, device=dev) for n in self.lengths}, {},
+                                   torch.zeros(1, dtype=torch.int32, device=dev))
+        first = acc[1].get(name)
+        if first is None:              # (all ones: the largest unsigned value)
+            first = acc[1][name] = {n: torch.full((4 ** n,), -1, dtype=torch.int64, device=dev) for n in self.lengths}
+        g = genome.as_struct(dev)
+        entry, stream = getattr(_lib.lib(), kind["entry"]), _lib.current_stream_ptr(dev)
+        for group in _calls_of(self.lengths):
+            s = kind["struct"]()
+            s.genome = C.pointer(g)
+            _row_fields(s, prob, start, end, label)
+            if kind["strand"]:
+                s.strand = strand.data_ptr()
+            s.n_class = k
+            setattr(s, kind["count"], len(group))
+            for key, value in self.fields.items():
+                setattr(s, key, value)
+            lengths = getattr(s, kind["length"])
+            for j, n in enumerate(group):
+                lengths[j], s.table[j], s.first[j] = n, acc[0][n].data_ptr(), first[n].data_ptr()
+            s.order_base, s.status = 0, acc[2].data_ptr()
+            _lib.check(entry(C.byref(s), stream))
+        return genome
+
+    def read_back(self, k):
+        """The one read-back of the device accumulators, merged with the host rows'."""
+        status, mine = 0, [self.host]
+        for tabs, firsts, dev_status in self.dev.values():
+            status |= int(dev_status.item())
+            mine.append(({n: t.cpu().numpy().view(np.uint64).reshape(4 ** n, 3, -1) for n, t in tabs.items()},
+                         {nm: {n: f.cpu().numpy().view(np.uint64) for n, f in per_n.items()} for nm, per_n in firsts.items()}))
+        shift = self.kind["shift"]
+        return _kmer_merge([_kmer_collapse(tabs, firsts, shift) for tabs, firsts in mine if tabs], shift), status
+
+    def merge(self, states, k):
+        return _kmer_merge(states, self.kind["shift"])
+
+    def finish(self, state, k, result):
+        self.sums = state[1]
+        none = ([], np.zeros((0, 1 + 2 * (k or 0))))
+        result[self.name] = {n: (self.kind["from_sums"](*self.sums[n], n, k) if n in self.sums else none) for n in self.lengths}
+
+    def write(self, out_prefix, result, k, written):
+        for n in self.lengths:
+            written += list(self.kind["output_names"](out_prefix, n))
+            self.kind["write"](*result[self.name][n], k, n, out_prefix)
+
+
+class _CalibrationReducer:
+    """The integer tables behind NLL / ECE / classwise ECE / Brier per chromosome and, with `fit_calibrator`, the retained rows and the
+    calibrator fit on them at close()."""
+    name = "calibration"
+
+    def __init__(self, calibration, n_bins, fit_calibrator, fit_rows_max, fit_row_terms, calibrated, group, world):
+        self.fit_calibrator, self.fit_rows_max, self.fit_row_terms = fit_calibrator, int(fit_rows_max), fit_row_terms
+        if fit_calibrator is not None:
+            if fit_calibrator not in CALIBRATORS:
+                raise ValueError(f"unknown calibrator {fit_calibrator!r} (one of {sorted(CALIBRATORS)})")
+            _refuse_fit_on_calibrated(calibrated)
+        self.active = bool(calibration) or fit_calibrator is not None
+        self.n_bins = int(n_bins)
+        if self.active and self.n_bins < 1:
+            raise ValueError(f"calibration_bins must be positive (got {n_bins})")
+        self.bounds = calib_bounds(self.n_bins) if self.active else None
+        self.group, self.world = group, world
+        self.reset()
+
+    def reset(self):
+        self.host = {}                 # chromosome -> table uint64 [cells] of the host shards
+        self.dev = {}                  # device -> ({chromosome: table}, status, bounds): read back once, at close()
+        self.fit_blocks, self.fit_rows = [], 0      # [(prob float32 [n][n_class], label uint8 [n])], on a device or on the host
+        self.sums = None
+
+    def _table(self, tables, name, k):
+        cells = calib_cells(k, self.n_bins)
+        if cells > _CALIB_MAX_CELLS:
+            raise ValueError(f"calibration_bins * (n_class + 1) = {self.n_bins * (k + 1)} is too large: the table of {cells} "
+                             f"cells does not fit the {_CALIB_MAX_CELLS} a workgroup holds")
+        if name not in tables:
+            tables[name] = np.zeros(cells, np.uint64)
+        return tables[name]
+
+    def _retain(self, prob, label):
+        """Keep a part's (float32 probabilities, uint8 labels -- 255 where the label is none) for the fit at close().  Every row of the
+        part counts against `fit_rows_max`: an invalid row makes close() raise before anything is fitted."""
+        if self.fit_rows + len(label) > self.fit_rows_max:
+            raise ValueError(f"fit_calibrator={self.fit_calibrator!r}: this shard takes the rows retained on this rank from {self.fit_rows} to "
+                             f"{self.fit_rows + len(label)}, beyond fit_rows_max={self.fit_rows_max}; raise the budget or fit on fewer rows "
+                             "(nothing is subsampled silently)")
+        self.fit_rows += len(label)
+        self.fit_blocks.append((prob, label))
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        _, status = summary_calib_host(prob, label, k, self.n_bins, self.bounds, into=self._table(self.host, name, k))
+        if self.fit_calibrator is not None:
+            lab = np.asarray(label)
+            good = np.isfinite(lab.astype(np.float64)) & (lab >= 0) & (lab < k) & (lab == np.floor(lab.astype(np.float64)))
+            self._retain(np.ascontiguousarray(prob, np.float32), np.where(good, lab, 255).astype(np.uint8))
+        return status
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the metrics reduction of a part behind its forward -- one launch (and the fold of the carries) into the chromosome's
+        accumulator on that device --, then the fit's copy of the part."""
+        dev = prob.device
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = ({}, torch.zeros(1, dtype=torch.int32, device=dev), torch.from_numpy(self.bounds).to(dev))
+        table = acc[0].get(name)
+        if table is None:
+            cells = len(self._table({}, name, k))
+            table = acc[0][name] = torch.zeros(cells, dtype=torch.int64, device=dev)
+        calib_rows_device(prob, label, k, self.n_bins, acc[2], table, acc[1])
+        if self.fit_calibrator is not None:
+            good = (label >= 0) & (label < k) & (label == label.to(torch.int64))
+            self._retain(prob[:, :k].to(torch.float32, copy=True).contiguous(), torch.where(good, label, 255).to(torch.uint8))
+
+    def read_back(self, k):
+        status, mine = 0, [self.host]
+        for tables, dev_status, _ in self.dev.values():
+            status |= int(dev_status.item())
+            mine.append({name: t.cpu().numpy().view(np.uint64) for name, t in tables.items()})
+        return self._added([m for m in mine if m], k), status
+
+    def _added(self, per_rank, k):
+        """[{chromosome: table}] of the ranks (or of a rank's devices and its host rows) -> one such dict: integer tables added, carries
+        folded."""
+        out = {}
+        for tables in per_rank:
+            for name, t in tables.items():
+                if name in out:
+                    _calib_fold(np.add(out[name], t, out=out[name]), k, self.n_bins)
+                else:
+                    out[name] = t.copy()
+        return out
+
+    def merge(self, states, k):
+        return self._added([s for s in states if s], k)
+
+    def _total(self, per_chrom, k):
+        total = np.zeros(calib_cells(k or 1, self.n_bins), np.uint64)
+        for t in per_chrom.values():
+            _calib_fold(np.add(total, t, out=total), k or 1, self.n_bins)
+        return total
+
+    def finish(self, state, k, result):
+        per_chrom = state or {}
+        total = self._total(per_chrom, k)
+        self.sums = {"all": total, "per_chromosome": per_chrom}
+        res = calib_metrics_from_sums(total, self.n_bins, k or 1)
+        res["per_chromosome"] = {name: calib_metrics_from_sums(per_chrom[name], self.n_bins, k) for name in sorted(per_chrom)}
+        result["calibration"] = res
+        if self.fit_calibrator is not None:
+            self._fit(res, k)
+
+    def _block_terms(self, prob, label, w, need_hessian):
+        """(loss sum, gradient sum, Hessian sum) of one retained block: the device kernel, or the stand-in given as `fit_row_terms`."""
+        k = prob.shape[1]
+        km = k * (k + 1)
+        if self.fit_row_terms is not None:
+            loss, g, h = self.fit_row_terms(_np(prob), _np(label), w, need_hessian)
+            return np.r_[loss, np.ravel(g), np.ravel(h)]
+        out = torch.zeros(1 + km + km * km, dtype=torch.float64, device=prob.device)
+        status = torch.zeros(1, dtype=torch.int32, device=prob.device)
+        wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(prob.device)
+        with torch.cuda.device(prob.device):
+            _lib.check(_lib.lib().mural_eval_dirichlet_fit_terms(prob.data_ptr(), 0, label.to(torch.int32).data_ptr(), prob.shape[0], k,
+                                                                wd.data_ptr(), int(need_hessian), out.data_ptr(), status.data_ptr(),
+                                                                _lib.current_stream_ptr(prob.device)))
+        return out.cpu().numpy()
+
+    def _fit(self, res, k):
+        """Fit the named calibrator on the retained raw-softmax rows (training.py:478) and reduce the metrics of the calibrated rows
+        through the same entry.  The data terms are the float64 atomic sums of ``mural_eval_dirichlet_fit_terms`` per block, added
+        over blocks and -- one small all_reduce per evaluation -- over ranks: the weights are reproducible to rounding, not bit for bit.
+        Only the metrics carry the bit-exact promise."""
+        method, ref_row, reg_lambda, reg_mu, reg_norm = CALIBRATORS[self.fit_calibrator]
+        if k is None or k < 2 or k > _FIT_MAX_CLASSES:
+            raise ValueError(f"fit_calibrator supports 2..{_FIT_MAX_CLASSES} classes, got {k}")
+        if any(c == 0 for c in res["label_counts"]):
+            raise ValueError("every class 0..n_class-1 must occur in the labels (the reference sizes the map by unique(y))")
+        if reg_norm:                                              # multinomial.py:81-86
+            if reg_mu is None:
+                reg_lambda = reg_lambda / (k * (k + 1))
+            else:
+                reg_lambda, reg_mu = reg_lambda / (k * (k - 1)), reg_mu / k
+        if self.fit_row_terms is None:                            # host shards are uploaded now, beside the device blocks
+            dev = next((p.device for p, _ in self.fit_blocks if isinstance(p, torch.Tensor)), None)
+            dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+            self.fit_blocks = [(p, y) if isinstance(p, torch.Tensor) else (torch.from_numpy(p).to(dev), torch.from_numpy(y).to(dev))
+                               for p, y in self.fit_blocks]
+        km = k * (k + 1)
+        n = res["rows"]
+
+        def row_terms(w, need_hessian):
+            sums = np.zeros(1 + km + km * km)
+            for p, y in self.fit_blocks:
+                sums += self._block_terms(p, y, w, need_hessian)
+            if self.world > 1:
+                t = torch.from_numpy(sums)                        # (shares its memory)
+                if dist.get_backend(self.group) == "nccl":
+                    t = t.cuda()
+                dist.all_reduce(t, group=self.group)
+                sums = t.cpu().numpy()
+            return sums[0] / n, sums[1:1 + km] / n, sums[1 + km:].reshape(km, km) / n
+
+        weights, loss = newton_calibrator(row_terms, k, method, ref_row, reg_lambda, reg_mu)
+        after = {}
+        bounds = {}
+        for p, y in self.fit_blocks:
+            if isinstance(p, torch.Tensor):
+                dev = p.device
+                if dev not in after:
+                    after[dev] = (torch.zeros(calib_cells(k, self.n_bins), dtype=torch.int64, device=dev),
+                                  torch.zeros(1, dtype=torch.int32, device=dev))
+                    bounds[dev] = torch.from_numpy(self.bounds).to(dev)
+                with torch.cuda.device(dev):
+                    cal = calibrate_device(p, dirichlet_weights=weights, input_is_prob=True)
+                    calib_rows_device(cal, y.to(torch.int32), k, self.n_bins, bounds[dev], *after[dev])
+            else:
+                summary_calib_host(dirichlet_calibrate(p, weights), y, k, self.n_bins, self.bounds, into=self._table(after, "host", k))
+        tables = {key: (v if isinstance(v, np.ndarray) else v[0].cpu().numpy().view(np.uint64)) for key, v in after.items()}
+        if self.world > 1:
+            every = [None] * self.world
+            dist.all_gather_object(every, tables, group=self.group)
+            tables = {(r, key): t for r, ts in enumerate(every) for key, t in ts.items()}
+        total = self._total(tables, k)
+        self.sums["after"] = total
+        res["after"] = calib_metrics_from_sums(total, self.n_bins, k)
+        res["weights"], res["fit_loss"] = weights, float(loss)
+
+    def write(self, out_prefix, result, k, written):
+        res = result["calibration"]
+        path = out_prefix + ".calibration.txt"
+        written.append(path)
+        line = lambda tag, m: "%s\t%d\t%.8f\t%.8f\t%.8f\t%.8f\n" % (tag, m["rows"], m["nll"], m["ece"], m["c_ece"], m["brier"])      # noqa: E731
+        with open(path, "w") as fh:
+            fh.write("chrom\trows\tnll\tece\tc_ece\tbrier\n" + line("all", res))
+            if "after" in res:
+                fh.write(line(f"all (after {self.fit_calibrator})", res["after"]))
+            for name, m in res["per_chromosome"].items():
+                fh.write(line(name, m))
+        if "weights" in res:
+            written.append(out_prefix + ".fdiri_cal.pkl")
+            save_dirichlet_calibrator(res["weights"], written[-1])
+
+
+class SummarySink:
+    """Consumer of shards (the TsvSink protocol) that keeps no row: per window size of `windows` the table ``tables.regional_table``
+    would read back from the written prediction table, and the (prob_sum, n_sites) of ``tables.prob_sum_file`` -- optionally counted per
+    overlapping benchmark region (`benchmark_regions`: a BED path or ``tables.read_regions``' dict) --, reduced from the probabilities
+    the table would hold, before they are rounded to four digits.  Device shards go through csrc/summary.hip (one pass per part, the
+    tables of a part sized from its first and last start and merged on the host in arrival order; nothing waits for work just enqueued:
+    a part is reduced when the next one arrives); host shards through numpy.  Calibration: as TsvSink (`poisson`, `dirichlet_weights`;
+    refused for shards that are calibrated already).  ``parts=True`` under torch.distributed: every rank reduces its rows and close()
+    gathers the ranks' tables -- not rows -- and adds them in rank order.
+
+    close() writes, with an `out_prefix` and on rank 0, ``{out_prefix}.{W/1000}Kb.mut_rates.tsv`` / ``.corr.txt`` per window size
+    (``tables.write_regional_outputs``: the files of ``evaluate --window_size``); ``result()`` and ``scaling_factor()`` are valid after
+    it.
+
+    `kmers`: k-mer lengths (1 .. ``tables.MAX_KMER``) whose rate tables -- ``tables.kmer_table``'s, the third thing ``evaluate`` reads
+    from the written table -- are reduced as well (csrc/summary_kmer.hip: exact integer sums of the probabilities quantised to 2^-71,
+    so the tables depend on the set of rows alone, bit for bit, whatever the parts, chunks or ranks).  `genome`: chromosome name ->
+    packed genome (``HipShardForward.genome``; a sequence will do for host shards); `kmer_strand`: None for SNV rows (each row's own
+    strand), 'pos' / 'neg' / 'both' for INDEL rows (``tables.strand_mode``).  A device part is reduced when it arrives, into accumulators
+    that live with the sink and are read back once, at close(); ranks exchange the integer tables in the same collective.  close() then
+    also writes ``{out_prefix}.{k}-mer.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_kmer_outputs``), and result() has "kmers".
+
+    `motifs`: motif lengths (odd, 3 .. ``tables.MAX_MOTIF``) whose rate tables -- ``tables.motif_table``'s, what ``evaluate --motif_only``
+    reads from the written table -- are reduced the same way (``mural_summary_motif_rows``: every window of m bases that holds a row's
+    site, on the reference strand, a motif and its reverse complement in one entry), alone or beside `kmers` and
+    `windows`; `motif_indel`: the rows are INDEL rows (m - 1 windows each).  They need `genome` as well.  close() writes
+    ``{out_prefix}.{m}-motif.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_motif_outputs``), and result() has "motifs".
+
+    `calibration`: the NLL / ECE / classwise ECE / Brier block of the reference's validation report (``calibrate_prob``,
+    evaluation.py:297-365) from the rows' own labels, on `calibration_bins` bins, alone or beside the other summaries; it needs no
+    `genome`.  Device parts go through ``mural_summary_calib_rows`` (csrc/summary_calib.hip), host shards through
+    ``summary_calib_host``: integer tables per chromosome, read back once at close(), exchanged between ranks in the same collective and
+    added -- the metrics depend on the set of rows alone, bit for bit.  result()["calibration"] = ``calib_metrics_from_sums`` of all rows
+    + "per_chromosome": {name: the same}; close() writes ``{out_prefix}.calibration.txt`` (a header, an `all` line, a line per
+    chromosome by name: rows nll ece c_ece brier, '%.8f'); ``calibration_sums()`` has the integers.
+
+    `fit_calibrator`: a key of ``evaluation.CALIBRATORS`` ('FullDiri', ...) to fit on the same rows (training.py:478 fits the raw
+    softmax, so the option is refused where the sink or the forward calibrates); it turns `calibration` on.  The sink retains (float32
+    prob[n_class], uint8 label) of every row -- device parts in device blocks, host shards on the host until close() uploads them -- and
+    raises ValueError at the shard that takes a rank beyond `fit_rows_max` retained rows; nothing is subsampled.  close() runs
+    ``evaluation.newton_calibrator`` on the sums ``mural_eval_dirichlet_fit_terms`` makes of each block (all_reduced over the ranks, one
+    small collective per evaluation), saves ``{out_prefix}.fdiri_cal.pkl`` on rank 0, calibrates the blocks and reduces their metrics
+    through the same entry: result()["calibration"] gains "after", "weights" and "fit_loss", the text file an `all (after NAME)` line.
+    The fit's sums are float64 atomics: the weights are reproducible to rounding, not bit for bit; only the metrics are bit-exact.
+    `fit_row_terms`: (prob, label, weights, need_hessian) -> (loss, gradient, Hessian) SUMS over the given rows, a stand-in for the
+    device kernel that keeps host shards on the host (tests without a device).
+
+    The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
+    reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
+
+    takes_aligned_blocks = True
+
+    def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
+                 group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
+                 calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None):
+        self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
+        by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
+        self.windows = by_window.sizes
+        self.ratio_cutoff, self.poisson, self.dirichlet_weights, self.group = ratio_cutoff, poisson, dirichlet_weights, group
+        self.rank = dist.get_rank(group) if (parts and dist.is_initialized()) else 0
+        self.world = dist.get_world_size(group) if (parts and dist.is_initialized()) else 1
+        self.parts = self.world > 1
+        by_kmer = _KeyedReducer(_KMERS, kmers, genome)
+        by_kmer.fields = dict(indel=int(kmer_strand is not None), mode=strand_mode("indel", kmer_strand) if kmer_strand is not None else 0)
+        by_motif = _KeyedReducer(_MOTIFS, motifs, genome)
+        by_motif.fields = dict(indel=int(bool(motif_indel)), order_by_row=0)
+        self.kmers, self.motifs = by_kmer.lengths, by_motif.lengths
+        metrics = _CalibrationReducer(calibration, calibration_bins, fit_calibrator, fit_rows_max, fit_row_terms,
+                                      poisson or dirichlet_weights is not None, group, self.world)
+        self.fit_calibrator, self.fit_rows_max = fit_calibrator, metrics.fit_rows_max
+        self.calibration, self.calibration_bins = metrics.active, metrics.n_bins
+        # the reducers of the summaries asked for, in the order of their files; the totals go with the windows, so those always run
+        active = [by_window] + [r for r, on in ((by_kmer, self.kmers), (by_motif, self.motifs), (metrics, self.calibration)) if on]
+        self._reducers = {r.name: r for r in active}
+        self.rows = 0
+        self._n_class = None
+        self._status = 0
+        self._written = []
+        self._result = None
+
+    @property
+    def _pending(self):
+        """The staged device part of the window reduction (None between parts on the host)."""
+        return self._reducers["windows"].pending
+
+    # -- one part ---------------------------------------------------------------------------------------------------------
+    def _host_part(self, name, shard, k):
+        """Calibrate and order the part, reduce it in every reducer."""
+        prob = host_calibrate(np.asarray(shard["prob"])[:, :k], self.poisson, self.dirichlet_weights)
+        start = np.asarray(shard["start"])
+        cols = [prob, start, np.asarray(shard["end"]), strand_u8(shard["strand"]) if self.kmers else None, np.asarray(shard["label"])]
+        if not shard.get("aligned"):
+            perm = np.argsort(start, kind="stable")
+            if self.parts:
+                perm = perm[slice(*shard_bounds(len(perm), self.rank, self.world))]
+            cols = [c if c is None else c[perm] for c in cols]
+        for r in self._reducers.values():
+            self._status |= r.host_part(name, *cols, k)
+
+    def _device_part(self, name, shard, k):
+        """Calibrate and order the part on its device, enqueue every reducer's work behind this part's forward: the fixed-size tables
+        (k-mers, motifs, calibration) now, while this part's chromosome is the resident one; the windows last -- they stage this part and
+        reduce the one before it."""
+        prob = shard["prob"]
+        dev = prob.device
+        with torch.cuda.device(dev):
+            if self.dirichlet_weights is not None or self.poisson:
+                prob = calibrate_device(prob[:, :k].contiguous() if prob.stride(0) != k else prob, dirichlet_weights=self.dirichlet_weights,
+                                        poisson=self.poisson, input_is_prob=True)
+            if prob.dtype not in (torch.float32, torch.float64):
+                prob = prob.to(torch.float32)
+            if prob.stride(1) != 1:
+                prob = prob.contiguous()
+            to = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, dt).contiguous()   # noqa: E731
+            start, end = to(shard["start"], torch.int64), to(shard["end"], torch.int64)
+            label = shard["label"]
+            label = to(label, label.dtype if isinstance(label, torch.Tensor) and label.dtype in (torch.int32, torch.int64) else torch.float32)
+            strand = to(strand_u8(shard["strand"]), torch.uint8) if self.kmers else None
+            if not shard.get("aligned"):
+                perm = torch.sort(start, stable=True).indices
+                if self.parts:
+                    perm = perm[slice(*shard_bounds(perm.shape[0], self.rank, self.world))]
+                prob, start, end, label = prob[perm], start[perm], end[perm], label[perm]
+                strand = strand[perm] if self.kmers else None
+            cols = (name, prob, start, end, strand, label, k)
+            held = None
+            by_window, *others = self._reducers.values()
+            if start.shape[0]:
+                for r in others:
+                    keep = r.device_part(*cols)
+                    held = held if keep is None else keep
+        by_window.device_part(*cols, held=held)
+
+    def __call__(self, shard):
+        name = shard_name(shard)
+        n = len(shard["start"])
+        if name is None or n == 0:
+            return
+        _refuse_second_calibration(shard, self.poisson, self.dirichlet_weights)
+        if self.fit_calibrator is not None:
+            _refuse_fit_on_calibrated(shard.get("calibrated"))
+        k = int(shard.get("n_class", shard["prob"].shape[1]))
+        if self._n_class not in (None, k):
+            raise ValueError(f"shards of {self._n_class} and of {k} classes in one summary")
+        self._n_class = k
+        self.rows += n
+        if isinstance(shard["prob"], torch.Tensor) and shard["prob"].is_cuda:
+            if k > 8:
+                raise ValueError("SummarySink reduces at most 8 classes on the device")
+            self._device_part(name, shard, k)
+        else:
+            if isinstance(shard["prob"], torch.Tensor):
+                shard = dict(shard, prob=shard["prob"].numpy())
+            self._host_part(name, {key: (_np(v) if isinstance(v, torch.Tensor) else v) for key, v in shard.items()}, k)
+
+    # -- close ------------------------------------------------------------------------------------------------------------
+    def close(self):
+        state = {"n_class": self._n_class}
+        for r in self._reducers.values():
+            state[r.name], status = r.read_back(self._n_class)
+            self._status |= status
+        state["status"] = self._status
+        k = self._n_class
+        if self.world > 1:
+            every = [None] * self.world
+            dist.all_gather_object(every, state, group=self.group)      # the one collective: tables, not rows
+            k = next((st["n_class"] for st in every if st["n_class"] is not None), None)
+            state = {r.name: r.merge([st[r.name] for st in every], k) for r in self._reducers.values()}
+            state["status"] = 0
+            for st in every:
+                state["status"] |= st["status"]
+        for bit, what in _SUMMARY_STATUS:
+            if state["status"] & bit:
+                raise ValueError(f"summary: {what}")
+        self._result = {}
+        for r in self._reducers.values():
+            r.finish(state[r.name], k, self._result)
+        if self.out_prefix is not None and self.rank == 0 and k is not None:
+            for r in self._reducers.values():
+                r.write(self.out_prefix, self._result, k, self._written)
+
+    def abort(self):
+        """Drop what was reduced and remove any file close() began: the caller's run failed."""
+        for r in self._reducers.values():
+            r.reset()
+        self._result = None
+        for path in self._written:
+            if os.path.exists(path):
+                os.unlink(path)
+        self._written = []
+
+    def result(self):
+        """{"prob_sum", "n_sites", "windows": {W: ([(chrom, window_end)], table [windows][1 + 2 n_class])}} after close(): the pair of
+        ``tables.prob_sum_file`` and, per window size, of ``tables.regional_table`` (chromosomes by name, windows ascending); with `kmers`
+        also "kmers": {k: (names, table [k-mers][1 + 2 n_class])}, the pair of ``tables.kmer_table``, and with `motifs` "motifs": {m: the
+        pair of ``tables.motif_table``}, with `calibration` "calibration": ``calib_metrics_from_sums``' dict of all rows + "per_chromosome"
+        (and "after", "weights", "fit_loss" with `fit_calibrator`).  ``kmer_sums()``, ``motif_sums()`` and ``calibration_sums()`` have the
+        integers."""
+        if self._result is None:
+            raise RuntimeError("SummarySink.result() is valid after close()")
+        return self._result
+
+    def kmer_sums(self):
+        """{k: (table uint64 [4^k][3][n_class] of label counts | sums of hi | sums of lo, first uint64 [4^k])} after close(): the exact
+        sums behind result()["kmers"] (``summary_kmer_host``'s layout)."""
+        self.result()
+        return self._reducers["kmers"].sums
+
+    def motif_sums(self):
+        """{m: (table uint64 [4^m][3][n_class], first uint64 [4^m])} after close(): the exact sums behind result()["motifs"]
+        (``summary_motif_host``'s layout, the chromosome's ordinal by name above each first-appearance word)."""
+        self.result()
+        return self._reducers["motifs"].sums
+
+    def calibration_sums(self):
+        """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind
+        result()["calibration"] (``summary_calib_host``'s layout)."""
+        self.result()
+        return self._reducers["calibration"].sums
+
+    def scaling_factor(self, genomewide_mu, m_proportion, g_proportion=1.0):
+        """``tables.calc_mu_scaling_factor``'s factor for the summarised rows, with the lines it prints."""
+        res = self.result()
+        factor = mu_scaling_factor(genomewide_mu, res["n_sites"], m_proportion, g_proportion, res["prob_sum"])
+        print_scaling_factor(genomewide_mu, res["n_sites"], g_proportion, m_proportion, res["prob_sum"], factor)
+        return factor
+
+

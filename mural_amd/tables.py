@@ -473,7 +473,7 @@ def motif_table(pred_file, ref_genome, motif_length, n_class, model_type, chunk_
     reverse complement in one entry named after the orientation seen first.  The chunks of the table go through the entry point of the
     in-flight reduction (``mural_summary_motif_rows``; ``predict.SummarySink(motifs=...)``), the rows' order being their line numbers."""
     from .data.ingest import read_fasta, scan_fasta
-    from .predict import motif_table_from_sums
+    from .summaries import _SUMMARY_STATUS, motif_table_from_sums      # (summaries imports this module: not at the top)
     m = check_motif_length(motif_length)
     if model_type not in ("snv", "indel"):
         raise ValueError(f"model_type {model_type} not supported!")
@@ -505,7 +505,6 @@ def motif_table(pred_file, ref_genome, motif_length, n_class, model_type, chunk_
                 s.m[0], s.table[0], s.first[0] = m, table.data_ptr(), first.data_ptr()
                 s.order_base, s.status = c.row0 + a, status.data_ptr()
                 _lib.check(lib.mural_summary_motif_rows(C.byref(s), _lib.current_stream_ptr(dev)))
-        from .predict import _SUMMARY_STATUS
         bits = int(status.item())
         for bit, what in _SUMMARY_STATUS:
             if bits & bit:

@@ -82,7 +82,7 @@ def main(argv):
                 def timed_close():
                     torch.cuda.synchronize()
                     t1 = time.perf_counter()
-                    extra["retained_bytes"] = float(sum(p.numel() * p.element_size() + y.numel() for p, y in summary._fit_blocks))
+                    extra["retained_bytes"] = float(sum(p.numel() * p.element_size() + y.numel() for p, y in summary._reducers["calibration"].fit_blocks))
                     close()
                     torch.cuda.synchronize()
                     extra["close"] = time.perf_counter() - t1
