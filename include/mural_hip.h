@@ -76,6 +76,25 @@ int mural_encode_onehot(const MuralGenome* g, const int64_t* pos, const uint8_t*
 int mural_encode_symbols(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n, int32_t radius,
                          int32_t indel, uint8_t* out, void* stream);
 
+/* One training batch gathered and encoded from ROW INDICES in one launch (csrc/train_batch.hip): the rows of a batch may lie on several
+ * chromosomes, which the three encoders above cannot take in one call.
+ *   genomes    : dev MuralGenome[n_genomes] (the structs themselves live on the device)
+ *   row_chrom / row_pos / row_strand / row_label : dev int32 / int64 / uint8 / uint8 [n_rows], the sites of an epoch (row_chrom
+ *                indexes genomes; row_strand 1 = '-'; row_label the class label)
+ *   order      : dev int64 [n_order], row numbers in the order the epoch visits them; the batch is order[first .. first + B - 1]
+ * For batch row b, r = order[first + b]:
+ *   cat_out[b]    (dev int64 [B][cols], cols as mural_encode_kmer's)      = mural_encode_kmer of (row_pos[r], row_strand[r]) on genome row_chrom[r]
+ *   sym_out[b]    (dev uint8 [B][W], W as mural_encode_symbols', 4-byte aligned; NULL: not written)   = mural_encode_symbols of the same site
+ *   onehot_out[b] (dev float [B][4][W]; NULL: not written)                = mural_encode_onehot of the same site
+ *   y_out[b]      (dev float [B])                                         = row_label[r]
+ * bit for bit.  At least one of sym_out / onehot_out is given.  An order entry outside [0, n_rows) or a row_chrom outside [0, n_genomes)
+ * is never dereferenced: that batch row is encoded as a window of N (k-mer id 4^local_order) with label 0, and MURAL_E_INVALID is OR-ed
+ * into *status (dev int32[1], never NULL; nothing is read back).  first / B outside the order fail on the host (MURAL_E_INVALID).    */
+int mural_train_batch_encode(const MuralGenome* genomes, int32_t n_genomes, const int32_t* row_chrom, const int64_t* row_pos,
+                             const uint8_t* row_strand, const uint8_t* row_label, int64_t n_rows, const int64_t* order, int64_t n_order,
+                             int64_t first, int32_t B, int32_t local_radius, int32_t local_order, int32_t distal_radius, int32_t indel,
+                             int64_t* cat_out, uint8_t* sym_out, float* onehot_out, float* y_out, int32_t* status, void* stream);
+
 /* Site enumeration (csrc/sites.hip; no reference counterpart -- its users write one BED row per site with scripts of their own):
  * the positions of the window [lo, hi) of the record (0-based half-open like a BED row, clamped to the record) that a prediction run
  * takes as sites, in ascending order, as the (pos, strand) pairs the encoders and the packed forwards take.

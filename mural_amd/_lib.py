@@ -196,6 +196,7 @@ PROTOTYPES = {
                                       C.c_void_p, C.c_void_p]),
     "mural_encode_symbols": (C.c_int, [C.POINTER(MuralGenome), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p]),
+    "mural_train_batch_encode": (C.c_int, [VP, I32, VP, VP, VP, VP, I64, VP, I64, I64, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP]),
     "mural_sites_tiles": (I64, [I64, I64, I64]),
     "mural_sites_count": (C.c_int, [C.POINTER(MuralGenome), I64, I64, I32, I32, VP, VP, VP]),
     "mural_sites_emit": (C.c_int, [C.POINTER(MuralGenome), I64, I64, I32, I32, VP, I64, I64, VP, VP, VP]),

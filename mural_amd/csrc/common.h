@@ -56,6 +56,15 @@ int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int3
     }                                       \
   } while (0)
 
+// the window of a site at `pos` (reference: MuRaL/data/preprocessing.py:559-567): genome positions pos + off .. pos + off + width - 1; the
+// indel window is the even one (:564-566)
+inline int window_geometry(int radius, int indel, int* off, int* width) {
+  MURAL_REQUIRE(radius >= 1, "radius must be >= 1, got %d", radius);
+  *off = indel ? -radius + 1 : -radius;
+  *width = indel ? 2 * radius : 2 * radius + 1;
+  return MURAL_OK;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to (kernel, device): a launch site raises it once per device ordinal
 // (never inside a stream capture after the first call on that device).  Thread-safe; setting it twice is harmless.
 struct DynLdsOnce {
@@ -247,17 +256,21 @@ __device__ __forceinline__ int64_t amb_lower_bound_wave(const int64_t* __restric
   return lo;
 }
 
-// symbol of genome position g with IUPAC codes resolved through the side table (strand-agnostic, forward symbol)
-__device__ __forceinline__ uint32_t genome_sym_iupac(const MuralGenome& gn, int64_t g) {
-  if (g < 0 || g >= gn.length) return SYM_N;
-  const uint32_t w = gn.packed2[g >> 4];
-  const uint32_t m = gn.nmask[g >> 5];
+// symbol of position g inside the record, given its packed2 word `w` and nmask word `m` (from memory or from a staged copy): the IUPAC
+// codes are resolved through the side table (strand-agnostic, forward symbol)
+__device__ __forceinline__ uint32_t sym_from_words(const MuralGenome& gn, int64_t g, uint32_t w, uint32_t m) {
   if (((m >> (uint32_t)(g & 31)) & 1u) == 0u) return (w >> (2u * (uint32_t)(g & 15))) & 3u;
   if (gn.n_amb > 0) {
     const int64_t i = amb_lower_bound(gn.amb_pos, gn.n_amb, g);
     if (i < gn.n_amb && gn.amb_pos[i] == g) return gn.amb_sym[i];
   }
   return SYM_N;
+}
+
+// symbol of genome position g with IUPAC codes resolved through the side table (strand-agnostic, forward symbol)
+__device__ __forceinline__ uint32_t genome_sym_iupac(const MuralGenome& gn, int64_t g) {
+  if (g < 0 || g >= gn.length) return SYM_N;
+  return sym_from_words(gn, g, gn.packed2[g >> 4], gn.nmask[g >> 5]);
 }
 
 // complement within the 16-symbol alphabet (A<->T, C<->G, N, R<->Y, M<->K, S, W, B<->V, D<->H, PAD)

@@ -15,6 +15,16 @@ __device__ __forceinline__ int frac_digit(float v) {
   return -1;
 }
 
+// symbol -> its dense column: o[ch * stride] for the 4 channels.  Channel set of the symbol (bit ch = base ch is possible): one-hot,
+// pairs 0.5, triples 1/3, N 0.25 (preprocessing.py:758-772)
+__device__ __forceinline__ void symbol_to_dense(uint32_t s, float* __restrict__ o, int64_t stride) {
+  const uint32_t set = (0xF7BDEC963A5F8421ull >> (4u * s)) & 0xFu;
+  const int members = __popc(set);
+  const float v = members == 1 ? 1.0f : members == 2 ? 0.5f : members == 3 ? (float)(1.0 / 3.0) : 0.25f;
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) o[(int64_t)ch * stride] = ((set >> ch) & 1u) ? v : 0.0f;
+}
+
 // dense (n,4,L) one-hot / IUPAC-fraction tensor -> 1 symbol per column (what the fused kernel consumes)
 __device__ __forceinline__ int dense_symbol(float v0, float v1, float v2, float v3) {
   const int d0 = frac_digit(v0), d1 = frac_digit(v1), d2 = frac_digit(v2), d3 = frac_digit(v3);

@@ -130,13 +130,7 @@ __global__ void encode_onehot_kernel(MuralGenome g, const int64_t* __restrict__ 
     const bool neg = strand[row] != 0;
     uint32_t s = genome_sym_iupac(g, neg ? ws + (width - 1 - j) : ws + j);
     if (neg) s = sym_complement(s);
-    float* o = out + row * 4 * (int64_t)width + j;
-    // channel set of the symbol (bit ch = base ch is possible): one-hot, pairs 0.5, triples 1/3, N 0.25 (preprocessing.py:758-772)
-    const uint32_t set = (0xF7BDEC963A5F8421ull >> (4u * s)) & 0xFu;
-    const int members = __popc(set);
-    const float v = members == 1 ? 1.0f : members == 2 ? 0.5f : members == 3 ? (float)(1.0 / 3.0) : 0.25f;
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) o[(int64_t)ch * width] = ((set >> ch) & 1u) ? v : 0.0f;
+    symbol_to_dense(s, out + row * 4 * (int64_t)width + j, width);
   }
 }
 
@@ -255,13 +249,6 @@ using namespace mural;
 
 extern "C" const char* mural_last_error(void) { return mural::last_error_cstr(); }
 extern "C" int mural_abi_version(void) { return 3; }
-
-static int window_geometry(int radius, int indel, int* off, int* width) {
-  MURAL_REQUIRE(radius >= 1, "radius must be >= 1, got %d", radius);
-  *off = indel ? -radius + 1 : -radius;
-  *width = indel ? 2 * radius : 2 * radius + 1;
-  return MURAL_OK;
-}
 
 extern "C" int mural_encode_kmer(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n,
                                  int32_t radius, int32_t order, int32_t indel, int64_t* out, void* stream) {

@@ -8,6 +8,8 @@
                                   are concatenated, cut into `batch_size` batches, a short tail batch is PREPENDED to the
                                   next group, and the final short batch is emitted.  Works on any sequence of 4-tuples
                                   of tensors shaped like the reference's DataLoader output (leading dim 1).
+  * ``epoch_order``            -- the rows ``generate_data_batches`` yields, as row numbers: the order of a whole epoch and its
+                                  batch boundaries from the group sizes alone (what a device-side loader gathers by).
 """
 import numpy as np
 import torch
@@ -89,3 +91,36 @@ def generate_data_batches(segment_loader, batch_segment, batch_size, shuffle=Tru
                 y, cat, dist = torch.cat([carry[0], y]), torch.cat([carry[1], cat]), torch.cat([carry[2], dist])
                 carry = None
             yield from batches_of(y, cat, dist, last=pending is None)
+
+
+def epoch_order(group_sizes, batch_segment, batch_size, shuffle=True, generator=None):
+    """(order, batch_bounds) of one epoch of ``generate_data_batches`` over segments of `group_sizes` rows each (the (segment, strand)
+    groups of ``bed_order``, in order), with row i = the i-th row in bed_reader order: `order` (int64, a permutation of 0..n-1) lists
+    the rows as the batches yield them, batch k is ``order[batch_bounds[k]:batch_bounds[k + 1]]`` (int64, len = batches + 1).  Same
+    draws from `generator` as ``generate_data_batches``: one ``torch.randperm`` over the rows of each group of `batch_segment` segments,
+    a carried tail included, in group order."""
+    sizes = [int(v) for v in group_sizes]
+    if any(v < 0 for v in sizes) or int(batch_segment) < 1 or int(batch_size) < 1:
+        raise ValueError("epoch_order: group sizes must be >= 0, batch_segment and batch_size >= 1")
+    starts = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+    order, bounds, emitted = [], [0], 0
+    carry = None
+    for g0 in range(0, len(sizes), batch_segment):
+        g1 = min(g0 + batch_segment, len(sizes))
+        rows = torch.arange(int(starts[g0]), int(starts[g1]), dtype=torch.int64)
+        if carry is not None:                           # the short tail of the previous group goes FIRST
+            rows = torch.cat([carry, rows])
+            carry = None
+        n = rows.shape[0]
+        idx = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
+        rows = rows[idx]
+        last = g1 == len(sizes)
+        full = n if last else n - n % batch_size
+        if full < n:
+            carry = rows[full:]
+        for o in range(0, full, batch_size):
+            emitted += min(batch_size, full - o)
+            bounds.append(emitted)
+        order.append(rows[:full])
+    order = torch.cat(order) if order else torch.zeros(0, dtype=torch.int64)
+    return order, torch.tensor(bounds, dtype=torch.int64)

@@ -177,6 +177,13 @@ class SymbolWindows:
     def shape(self):
         return self.sym.shape
 
+    def to(self, *args, **kwargs):
+        """The windows on another device (``train_epoch`` moves every member of a batch with ``.to(device)``); self where nothing moves."""
+        sym = self.sym.to(*args, **kwargs)
+        if sym.dtype != torch.uint8:
+            raise TypeError("SymbolWindows hold uint8 symbols: .to() moves them, it does not convert them")
+        return self if sym is self.sym else SymbolWindows(sym)
+
 
 class PackedGenome:
     """One chromosome resident on a HIP device."""

@@ -1,0 +1,109 @@
+"""Training batches gathered and encoded on the device, one launch per batch (``mural_train_batch_encode``, csrc/train_batch.hip).
+
+``train_batches_from_files`` encodes every bed_reader segment as a dense one-hot tensor, concatenates `sampled_segments` of them and
+shuffles the group with an index-select over those dense rows.  ``EpochLoader`` keeps the row table (chromosome, start, strand, label)
+and the packed chromosomes on the device, takes an epoch's order as pure index logic (``batching.epoch_order``: the same rows, the same
+draws from the generator) and encodes each batch from its row numbers: k-mer ids, one symbol byte per window column, labels.  The files
+are read once for any number of epochs.
+"""
+import numpy as np
+import torch
+
+from .. import _lib
+from .batching import epoch_order
+from .genome import SymbolWindows
+from .ingest import bed_order, read_bed, read_fasta
+
+
+class EpochLoader:
+    """Batches ``(y (B, 1) float32, cont_x (B, 1) float64 zeros, cat_x (B, cols) int64, distal_x)`` of a FASTA + BED pair in the order
+    and with the values of ``train_batches_from_files``, for ``train_epoch``.
+
+    ``distal_x`` is ``SymbolWindows`` over the uint8 (B, W) symbol tensor for SNV models -- the form their training forward takes in
+    place of the dense tensor, bit-identical to converting it.  With ``dense=True``, and always for ``model_type="indel"`` (the INDEL
+    training path, model/indel_train.py, takes the dense tensor only), it is the float32 (B, 4, W) one-hot tensor of the batch's rows,
+    written by the same launch.  Every batch owns freshly allocated tensors: a caller may keep any number of them."""
+
+    def __init__(self, fasta_path, bed_path, batch_size, local_radius, local_order=3, distal_radius=None, segment_center=300000,
+                 sampled_segments=10, model_type="snv", device="cuda", dense=False):
+        if model_type not in ("snv", "indel"):
+            raise ValueError(f"model_type {model_type} not supported!")
+        if distal_radius is None:
+            raise ValueError("EpochLoader: distal_radius is required")
+        if int(batch_size) < 1 or int(sampled_segments) < 1:
+            raise ValueError("batch_size and sampled_segments must be >= 1")
+        self.batch_size, self.sampled_segments = int(batch_size), int(sampled_segments)
+        self.local_radius, self.local_order, self.distal_radius = int(local_radius), int(local_order), int(distal_radius)
+        self.indel = model_type == "indel"
+        self.dense = bool(dense) or self.indel
+        self.device = torch.device(device)
+        odd = 0 if self.indel else 1
+        self.cols, self.width = 2 * self.local_radius + odd - (self.local_order - 1), 2 * self.distal_radius + odd
+        sites = read_bed(bed_path)
+        order, group = bed_order(sites, segment_center)
+        used_ids = np.unique(sites.chrom_id)
+        used = {sites.chrom_names[c] for c in used_ids}
+        self.genomes = read_fasta(fasta_path, self.device, names=used)
+        missing = used - set(self.genomes)
+        if missing:
+            raise KeyError(sorted(missing)[0])
+        label = sites.score[order]
+        if len(label) and not (np.isfinite(label).all() and (label >= 0).all() and (label <= 255).all() and (label == np.floor(label)).all()):
+            raise ValueError("EpochLoader: the BED scores (class labels) must be integers in 0 .. 255")
+        # rows in bed_reader order; the chromosomes in use numbered 0 .. in the order of the BED's name table
+        slot = np.full(max(len(sites.chrom_names), 1), -1, np.int32)
+        slot[used_ids] = np.arange(len(used_ids), dtype=np.int32)
+        self.n_rows = len(order)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.device)      # noqa: E731
+        self.row_chrom, self.row_pos = up(slot[sites.chrom_id[order]], np.int32), up(sites.start[order], np.int64)
+        self.row_strand, self.row_label = up(sites.strand[order], np.uint8), up(label, np.uint8)
+        structs = (_lib.MuralGenome * max(len(used_ids), 1))()
+        for i, c in enumerate(used_ids):
+            structs[i] = self.genomes[sites.chrom_names[c]].as_struct()
+        self.n_genomes = len(used_ids)
+        self.chrom_names = [sites.chrom_names[c] for c in used_ids]      # row_chrom indexes this list
+        self._genome_structs = torch.frombuffer(bytearray(bytes(structs)), dtype=torch.uint8).to(self.device)
+        edges = np.r_[0, np.nonzero(group[1:] != group[:-1])[0] + 1, len(group)] if len(group) else np.zeros(1, np.int64)
+        self.group_sizes = np.diff(edges).astype(np.int64)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return self.n_rows
+
+    @property
+    def n_batches(self):
+        """Batches per epoch (the same for every shuffle: the carry rule depends on the group sizes alone)."""
+        return int(epoch_order(self.group_sizes, self.sampled_segments, self.batch_size, shuffle=False)[1].shape[0]) - 1
+
+    def encode(self, order, first, n):
+        """(y, cat_x, distal tensor) of the rows ``order[first : first + n]`` (`order`: int64 device tensor of row numbers): one launch."""
+        dev = self.device
+        y = torch.empty((n, 1), dtype=torch.float32, device=dev)
+        cat = torch.empty((n, self.cols), dtype=torch.int64, device=dev)
+        if self.dense:
+            distal = torch.empty((n, 4, self.width), dtype=torch.float32, device=dev)
+            sym_ptr, dense_ptr = None, distal.data_ptr()
+        else:
+            distal = torch.empty((n, self.width), dtype=torch.uint8, device=dev)
+            sym_ptr, dense_ptr = distal.data_ptr(), None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mural_train_batch_encode(
+                self._genome_structs.data_ptr(), self.n_genomes, self.row_chrom.data_ptr(), self.row_pos.data_ptr(),
+                self.row_strand.data_ptr(), self.row_label.data_ptr(), self.n_rows, order.data_ptr(), order.shape[0], int(first), int(n),
+                self.local_radius, self.local_order, self.distal_radius, int(self.indel), cat.data_ptr(), sym_ptr, dense_ptr,
+                y.data_ptr(), self._status.data_ptr(), _lib.current_stream_ptr(dev)))
+        return y, cat, distal
+
+    def epoch(self, shuffle=True, generator=None):
+        """The batches of one epoch (a generator): the rows and the generator draws of ``train_batches_from_files`` with the same
+        `shuffle` / `generator`.  The order is uploaded once; nothing is read back until the epoch's last batch has been yielded."""
+        order, bounds = epoch_order(self.group_sizes, self.sampled_segments, self.batch_size, shuffle=shuffle, generator=generator)
+        order_dev = order.to(self.device)
+        bounds = bounds.tolist()
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            y, cat, distal = self.encode(order_dev, lo, hi - lo)
+            cont = torch.zeros((hi - lo, 1), dtype=torch.float64, device=self.device)
+            yield y, cont, cat, (distal if self.dense else SymbolWindows(distal))
+        if bounds[-1] and int(self._status.item()) != 0:      # (cannot happen with an order of epoch_order: a corrupted row table)
+            self._status.zero_()
+            raise RuntimeError("EpochLoader: a batch named a row or a chromosome outside the tables")
