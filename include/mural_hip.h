@@ -815,6 +815,31 @@ int mural_indel_train_forward(const MuralIndelShape* shape, const MuralIndelPara
 int mural_indel_train_backward(const MuralIndelShape* shape, const MuralIndelParams* params, const MuralIndelParams* grads,
                                const float* x, const float* dout, int64_t B, float dropout_p, uint64_t seed,
                                const uint64_t* seed_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* The same step from SYMBOL WINDOWS: symbols = dev uint8 [B][length], one MURAL_SYM_* code per window column (what
+ * mural_train_batch_encode / mural_encode_symbols / mural_op_dense_to_symbols write; a byte above 14 counts as N, the bytes are not
+ * checked otherwise).  Same semantics as the dense pair -- running statistics (the strand-symmetrising BatchNorm's twice), every
+ * gradient fully written -- but the unit that consumes the window (the strand-symmetrising conv with use_reverse, up_l[0] otherwise)
+ * is evaluated per symbol (mural_op_indel_first_fwd / _bwd): neither the dense window nor its flipped copy exists, and the workspace is
+ * smaller by at least that copy (B * 4 * length floats) with use_reverse.  The backward takes the forward's symbols and workspace. */
+size_t mural_indel_train_symbols_workspace_bytes(const MuralIndelShape* shape, int64_t B);
+int mural_indel_train_forward_symbols(const MuralIndelShape* shape, const MuralIndelParams* params, const uint8_t* symbols, int64_t B,
+                                      float dropout_p, uint64_t seed, const uint64_t* seed_dev, float momentum, float* out,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int mural_indel_train_backward_symbols(const MuralIndelShape* shape, const MuralIndelParams* params, const MuralIndelParams* grads,
+                                       const uint8_t* symbols, const float* dout, int64_t B, float dropout_p, uint64_t seed,
+                                       const uint64_t* seed_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* The conv of that unit alone, Conv1d(4 -> Cout, K, stride, pad) over the one-hot / IUPAC-fraction columns of the symbols (sym: dev uint8
+ * [B][L]; Cout a multiple of 4, K <= 63; W [Cout][4][K], bias [Cout] or NULL).  y [B][Cout][Lout], Lout = (L + 2 pad - K) / stride + 1.
+ * y_rev (optional; needs stride 1, pad (K - 1) / 2): the same conv of the channel- and length-flipped window, from the same bytes.
+ * Backward: dW [Cout][4][K] and db [Cout] (optional) = the weight gradient of dz, plus that of dz_rev (optional) through the flipped
+ * window; fully written, summed in a fixed order.  part: scratch of mural_op_indel_first_scratch floats (rev: dz_rev will be given). */
+size_t mural_op_indel_first_scratch(int64_t B, int32_t L, int32_t Cout, int32_t K, int32_t stride, int32_t pad, int32_t rev);
+int mural_op_indel_first_fwd(const uint8_t* sym, const float* W, const float* bias, int64_t B, int32_t L, int32_t Cout, int32_t K,
+                             int32_t stride, int32_t pad, float* y, float* y_rev, void* stream);
+int mural_op_indel_first_bwd(const uint8_t* sym, const float* dz, const float* dz_rev, int64_t B, int32_t L, int32_t Cout, int32_t K,
+                             int32_t stride, int32_t pad, float* dW, float* db, float* part, size_t part_floats, void* stream);
+/* symbols -> the dense columns they stand for: x [n][4][L] float (the inverse of mural_op_dense_to_symbols; a byte above 14 gives N) */
+int mural_op_symbols_to_dense(const uint8_t* sym, int64_t n, int32_t L, float* x, void* stream);
 /* kind: 1 ReLU, 2 SiLU, 3 Softplus (beta 1, threshold 20); backward takes the forward INPUT x */
 int mural_op_act_fwd(const float* x, int64_t n, int32_t kind, float* y, void* stream);
 int mural_op_act_bwd(const float* dy, const float* x, int64_t n, int32_t kind, float* dx, void* stream);

@@ -237,6 +237,15 @@ PROTOTYPES = {
                                             C.c_float, VP, VP, C.c_size_t, VP]),
     "mural_indel_train_backward": (C.c_int, [C.POINTER(MuralIndelShape), C.POINTER(MuralIndelParams), C.POINTER(MuralIndelParams), VP, VP,
                                              I64, C.c_float, C.c_uint64, VP, VP, C.c_size_t, VP]),
+    "mural_indel_train_symbols_workspace_bytes": (C.c_size_t, [C.POINTER(MuralIndelShape), I64]),
+    "mural_indel_train_forward_symbols": (C.c_int, [C.POINTER(MuralIndelShape), C.POINTER(MuralIndelParams), VP, I64, C.c_float, C.c_uint64,
+                                                    VP, C.c_float, VP, VP, C.c_size_t, VP]),
+    "mural_indel_train_backward_symbols": (C.c_int, [C.POINTER(MuralIndelShape), C.POINTER(MuralIndelParams), C.POINTER(MuralIndelParams),
+                                                     VP, VP, I64, C.c_float, C.c_uint64, VP, VP, C.c_size_t, VP]),
+    "mural_op_indel_first_scratch": (C.c_size_t, [I64, I32, I32, I32, I32, I32, I32]),
+    "mural_op_indel_first_fwd": (C.c_int, [VP, VP, VP, I64, I32, I32, I32, I32, I32, VP, VP, VP]),
+    "mural_op_indel_first_bwd": (C.c_int, [VP, VP, VP, I64, I32, I32, I32, I32, I32, VP, VP, VP, C.c_size_t, VP]),
+    "mural_op_symbols_to_dense": (C.c_int, [VP, I64, I32, VP, VP]),
     "mural_table_open": (C.c_int, [C.c_char_p, I32, I64, C.POINTER(C.c_void_p)]),
     "mural_table_next": (C.c_int, [VP, C.POINTER(MuralTableChunk), VP]),
     "mural_table_chrom_name": (C.c_char_p, [VP, I32]),

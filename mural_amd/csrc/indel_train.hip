@@ -987,7 +987,14 @@ extern "C" int mural_op_convg_bn_fwd(const float* x, const float* W, const float
   MURAL_REQUIRE(Cout <= CB_MAXC, "convg_bn_fwd: at most %d output channels (got %d)", CB_MAXC, Cout);
   if (int rc = mural_op_convg_fwd(x, W, bias, wt, y0, B, Cin, Lin, Cout, K, stride, pad, up, stream)) return rc;
   if (B == 0) return MURAL_OK;
-  const int Lout = out_length(Lin, K, stride, pad, up);
+  return bn_post_fwd(y0, B, Cout, out_length(Lin, K, stride, pad, up), gamma, beta, eps, momentum, running_mean, running_var, acc, state, act,
+                     res1, res2, z, stream);
+}
+// the unit behind its conv: batch statistics of y0 [B][Cout][Lout], running statistics, BatchNorm, activation, residuals -> z
+int mural::bn_post_fwd(const float* y0, int64_t B, int32_t Cout, int32_t Lout, const float* gamma, const float* beta, float eps, float momentum,
+                       float* running_mean, float* running_var, double* acc, float* state, int32_t act, const float* res1, const float* res2,
+                       float* z, void* stream) {
+  MURAL_REQUIRE(act >= 0 && act <= 3 && B >= 1 && Lout >= 1 && y0 && gamma && beta && acc && state && z && Cout <= CB_MAXC, "bn_post_fwd: bad argument");
   if (B * Lout <= CB_ONEPASS2 && B * Cout * Lout < (int64_t(1) << 31)) {       // short tensor: sums and map in one launch, one workgroup per channel
     if (B * Lout <= CB_ONEPASS)
       hipLaunchKernelGGL((bn_post_onepass_fwd_kernel<IT_THREADS, CB_OP_PER>), dim3(Cout), dim3(IT_THREADS), 0, (hipStream_t)stream, y0, (int)B,
@@ -1030,10 +1037,18 @@ int mural::convg_bn_bwd_add(const float* dz, const float* x, const float* W, con
                             int32_t Cin, int32_t Lin, int32_t Cout, int32_t K, int32_t stride, int32_t pad, int32_t up, int32_t act,
                             double* acc, float* dy0, float* dx, const float* dx_add, float* dW, float* db, float* dgamma, float* dbeta,
                             float* part, size_t part_floats, const float* wt_dgrad, void* stream) {
+  const int Lout = mural_op_convg_out_length(Lin, K, stride, pad, up);
+  MURAL_REQUIRE(Lout >= 1, "convg_bn_bwd: bad geometry");
+  if (int rc = bn_post_bwd(dz, y0, state, gamma, B, Cout, Lout, act, acc, dy0, dgamma, dbeta, stream)) return rc;
+  MURAL_REQUIRE(dx || !dx_add, "convg_bn_bwd: dx_add without dx");
+  return convg_bwd_impl(dy0, x, W, wt_dgrad, B, Cin, Lin, Cout, K, stride, pad, up, dx, dx_add, dW, db, part, part_floats, stream);
+}
+// the unit's BatchNorm + activation backward alone: dy0 = gradient of the conv output y0, dgamma, dbeta
+int mural::bn_post_bwd(const float* dz, const float* y0, const float* state, const float* gamma, int64_t B, int32_t Cout, int32_t Lout,
+                       int32_t act, double* acc, float* dy0, float* dgamma, float* dbeta, void* stream) {
   MURAL_REQUIRE(act >= 0 && act <= 3, "convg_bn_bwd: act must be 0 (none), 1 (ReLU), 2 (SiLU) or 3 (Softplus)");
   MURAL_REQUIRE(B >= 1 && dz && y0 && state && gamma && acc && dy0 && dgamma && dbeta, "convg_bn_bwd: null pointer / empty batch");
   MURAL_REQUIRE(Cout <= CB_MAXC, "convg_bn_bwd: at most %d output channels (got %d)", CB_MAXC, Cout);
-  const int Lout = mural_op_convg_out_length(Lin, K, stride, pad, up);
   MURAL_REQUIRE(Lout >= 1, "convg_bn_bwd: bad geometry");
   hipStream_t st = (hipStream_t)stream;
   const int64_t per = B * Lout, total = per * Cout;
@@ -1053,8 +1068,7 @@ int mural::convg_bn_bwd_add(const float* dz, const float* x, const float* W, con
                        dbeta);
   }
   MURAL_HIP_CHECK(hipGetLastError());
-  MURAL_REQUIRE(dx || !dx_add, "convg_bn_bwd: dx_add without dx");
-  return convg_bwd_impl(dy0, x, W, wt_dgrad, B, Cin, Lin, Cout, K, stride, pad, up, dx, dx_add, dW, db, part, part_floats, stream);
+  return MURAL_OK;
 }
 
 // every conv weight of a model into its forward (and, where wt_dgrad is set, input-gradient) layout in one launch; jobs: device

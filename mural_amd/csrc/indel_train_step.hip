@@ -72,6 +72,7 @@ struct Unit {
 struct Plan {
   int B, C[IL], L[IL], Lx, n_class;
   bool rev;
+  bool symbols;                         // the window arrives as one symbol byte per column: the input unit's conv is indel_first.hip's
   std::vector<Unit> u;                  // forward order
   // workspace regions
   MuralRelayoutJob* jobs_dev = nullptr;
@@ -107,9 +108,12 @@ struct Arena {
 
 int conv_out(int Lin, int K, int stride, int pad, int up) { return mural_op_convg_out_length(Lin, K, stride, pad, up); }
 
-// lays out the units and the workspace; base == nullptr: sizes only.  params / grads may be NULL for a sizing call.
-int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralIndelParams* gr, const float* x, int64_t B64, void* base, Plan* out) {
+// lays out the units and the workspace; base == nullptr: sizes only.  params / grads may be NULL for a sizing call.  symbols: the
+// input form (the dense float window, or one symbol byte per column) -- the units are the same, the input unit's scratch differs and
+// the flipped copy of the window has no region
+int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralIndelParams* gr, bool symbols, int64_t B64, void* base, Plan* out) {
   Plan& P = *out;
+  P.symbols = symbols;
   MURAL_REQUIRE(B64 >= 1 && B64 <= (1 << 20), "batch out of range");
   MURAL_REQUIRE(sh.channels >= 4 && sh.channels % 4 == 0 && sh.ksize >= 1 && (sh.ksize & 1) && sh.length >= 1 && sh.n_class >= 1,
                 "bad INDEL shape");
@@ -219,7 +223,7 @@ int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralI
   // ---- the rest of the forward state
   const size_t in_floats = Bz * 4 * P.Lx, l0 = Bz * P.C[0] * P.L[0];
   if (P.rev) {
-    P.xf = A.f(in_floats);
+    if (!P.symbols) P.xf = A.f(in_floats);
     P.s2f = A.f(in_floats);
   }
   P.o2 = A.f(l0);
@@ -238,8 +242,11 @@ int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralI
     P.gh[i] = A.f(2 * n);
     dy0max = std::max(dy0max, 2 * n);
   }
-  for (Unit& u : P.u) {
+  for (size_t i = 0; i < P.u.size(); ++i) {
+    Unit& u = P.u[i];
     u.part_floats = mural_op_convg_bwd_scratch(u.Cin, u.Cout, u.K);
+    // the input unit from symbols: per-(tap, symbol) partial tables; both strand-symmetry applications share unit 0's
+    if (P.symbols && i < (P.rev ? 2u : 1u)) u.part_floats = i == 0 ? indel_first_scratch_floats(P.B, u.Lout, u.Cout, u.K, P.rev) : 0;
     u.part = A.f(u.part_floats);
   }
   partmax = mural_op_convg_bwd_scratch(P.C[0], P.C[0], 1);
@@ -248,7 +255,6 @@ int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralI
   P.part_floats = partmax;
   P.tmpW = A.f((size_t)4 * 4 * K + 4 + 4 + 4 + 64);
   P.bytes = A.off;
-  (void)x;
   return MURAL_OK;
 }
 
@@ -256,6 +262,12 @@ int unit_fwd(const Plan& P, Unit& u, const float* x, const float* res1, const fl
   u.x = x; u.res1 = res1; u.res2 = res2;
   return mural_op_convg_bn_fwd(x, nullptr, u.bias, u.wt_fwd, u.y0, P.B, u.Cin, u.Lin, u.Cout, u.K, u.stride, u.pad, u.up, u.gamma, u.beta, kEps,
                                momentum, u.rmean, u.rvar, u.acc_f, u.state, u.act, res1, res2, u.z, st);
+}
+
+// the unit behind a conv output that indel_first_fwd has written to u.y0
+int unit_bn_fwd(const Plan& P, Unit& u, float momentum, hipStream_t st) {
+  return bn_post_fwd(u.y0, P.B, u.Cout, u.Lout, u.gamma, u.beta, kEps, momentum, u.rmean, u.rvar, u.acc_f, u.state, u.act, nullptr, nullptr, u.z,
+                     st);
 }
 
 // dW / db / dgamma / dbeta of the unit go to its gradient slots (or to alternative destinations), dx optional; dx_add (optional, may be
@@ -309,22 +321,25 @@ int check_params(const MuralIndelShape& sh, const MuralIndelParams& p, bool grad
 
 }  // namespace
 
-extern "C" size_t mural_indel_train_workspace_bytes(const MuralIndelShape* shape, int64_t B) {
+static size_t workspace_bytes_of(const MuralIndelShape* shape, int64_t B, bool symbols) {
   if (!shape || B < 1) return 0;
   Plan P;
-  if (make_plan(*shape, nullptr, nullptr, nullptr, B, nullptr, &P)) return 0;
+  if (make_plan(*shape, nullptr, nullptr, symbols, B, nullptr, &P)) return 0;
   return P.bytes;
 }
+extern "C" size_t mural_indel_train_workspace_bytes(const MuralIndelShape* shape, int64_t B) { return workspace_bytes_of(shape, B, false); }
+extern "C" size_t mural_indel_train_symbols_workspace_bytes(const MuralIndelShape* shape, int64_t B) { return workspace_bytes_of(shape, B, true); }
 
 // out [B][n_class] = UNet_Small.forward(x) in training mode (positive Softplus scores); everything the backward needs stays in the
-// workspace.  x: dev float [B][4][length].  dropout_p / seed / seed_dev: out_fc's Dropout (counter-based generator, mural_op_dropout).
-extern "C" int mural_indel_train_forward(const MuralIndelShape* shape, const MuralIndelParams* params, const float* x, int64_t B,
-                                         float dropout_p, uint64_t seed, const uint64_t* seed_dev, float momentum, float* out, void* workspace,
-                                         size_t workspace_bytes, void* stream_) {
-  MURAL_REQUIRE(shape && params && x && out && workspace, "NULL argument");
+// workspace.  The window is x: dev float [B][4][length], or sym: dev uint8 [B][length] (exactly one of them).  dropout_p / seed /
+// seed_dev: out_fc's Dropout (counter-based generator, mural_op_dropout).
+static int train_forward(const MuralIndelShape* shape, const MuralIndelParams* params, const float* x, const uint8_t* sym, int64_t B,
+                         float dropout_p, uint64_t seed, const uint64_t* seed_dev, float momentum, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(shape && params && (x || sym) && out && workspace, "NULL argument");
   if (int rc = check_params(*shape, *params, false)) return rc;
   Plan P;
-  if (int rc = make_plan(*shape, params, nullptr, x, B, workspace, &P)) return rc;
+  if (int rc = make_plan(*shape, params, nullptr, sym != nullptr, B, workspace, &P)) return rc;
   if (workspace_bytes < P.bytes) {
     set_error("workspace too small: need %zu bytes, got %zu", P.bytes, workspace_bytes);
     return MURAL_E_WORKSPACE;
@@ -338,9 +353,16 @@ extern "C" int mural_indel_train_forward(const MuralIndelShape* shape, const Mur
   if (P.rev) {
     // conv(x) + flip_L(conv(flip_CL(x))) (model_indel.py:154-155): the same Conv1d + BatchNorm module applied twice -- first to x,
     // then to the flipped x -- so its batch statistics are taken and its running statistics updated twice, in that order
-    if (int rc = unit_fwd(P, P.u[0], x, nullptr, nullptr, momentum, st)) return rc;
-    if (int rc = flip(x, nullptr, P.xf, P.B, 4, P.Lx, 1, st)) return rc;
-    if (int rc = unit_fwd(P, P.u[1], P.xf, nullptr, nullptr, momentum, st)) return rc;
+    if (sym) {      // both convs from the symbol bytes in one launch: neither x nor its flipped copy exists
+      Unit &a = P.u[0], &b = P.u[1];
+      if (int rc = indel_first_fwd(sym, a.W, a.bias, P.B, P.Lx, a.Cout, a.K, a.stride, a.pad, a.y0, b.y0, st)) return rc;
+      if (int rc = unit_bn_fwd(P, a, momentum, st)) return rc;
+      if (int rc = unit_bn_fwd(P, b, momentum, st)) return rc;
+    } else {
+      if (int rc = unit_fwd(P, P.u[0], x, nullptr, nullptr, momentum, st)) return rc;
+      if (int rc = flip(x, nullptr, P.xf, P.B, 4, P.Lx, 1, st)) return rc;
+      if (int rc = unit_fwd(P, P.u[1], P.xf, nullptr, nullptr, momentum, st)) return rc;
+    }
     if (int rc = flip(P.u[1].z, P.u[0].z, P.s2f, P.B, 4, P.Lx, 0, st)) return rc;
     h = P.s2f;
     ui = 2;
@@ -348,7 +370,12 @@ extern "C" int mural_indel_train_forward(const MuralIndelShape* shape, const Mur
   const float* enc[IL];
   for (int i = 0; i < IL; ++i) {
     Unit &a = P.u[ui], &b5 = P.u[ui + 1], &b1 = P.u[ui + 2];
-    if (int rc = unit_fwd(P, a, h, nullptr, nullptr, momentum, st)) return rc;
+    if (i == 0 && sym && !P.rev) {      // the first strided conv is the unit that consumes the window
+      if (int rc = indel_first_fwd(sym, a.W, a.bias, P.B, P.Lx, a.Cout, a.K, a.stride, a.pad, a.y0, nullptr, st)) return rc;
+      if (int rc = unit_bn_fwd(P, a, momentum, st)) return rc;
+    } else {
+      if (int rc = unit_fwd(P, a, h, nullptr, nullptr, momentum, st)) return rc;
+    }
     if (int rc = unit_fwd(P, b5, a.z, nullptr, nullptr, momentum, st)) return rc;
     if (int rc = unit_fwd(P, b1, b5.z, a.z, nullptr, momentum, st)) return rc;      // x + BN(1x1(SiLU(BN(k5(x)))))
     h = enc[i] = b1.z;
@@ -383,17 +410,29 @@ extern "C" int mural_indel_train_forward(const MuralIndelShape* shape, const Mur
   if (int rc = mural_op_linear_fwd(fin, p.fc.weight, p.fc.bias, P.B, C0, P.n_class, P.lin, st)) return rc;
   return mural_op_act_fwd(P.lin, (int64_t)P.B * P.n_class, 3, out, st);
 }
+extern "C" int mural_indel_train_forward(const MuralIndelShape* shape, const MuralIndelParams* params, const float* x, int64_t B,
+                                         float dropout_p, uint64_t seed, const uint64_t* seed_dev, float momentum, float* out, void* workspace,
+                                         size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(x, "NULL argument");
+  return train_forward(shape, params, x, nullptr, B, dropout_p, seed, seed_dev, momentum, out, workspace, workspace_bytes, stream_);
+}
+extern "C" int mural_indel_train_forward_symbols(const MuralIndelShape* shape, const MuralIndelParams* params, const uint8_t* symbols, int64_t B,
+                                                 float dropout_p, uint64_t seed, const uint64_t* seed_dev, float momentum, float* out,
+                                                 void* workspace, size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(symbols, "NULL argument");
+  return train_forward(shape, params, nullptr, symbols, B, dropout_p, seed, seed_dev, momentum, out, workspace, workspace_bytes, stream_);
+}
 
 // gradients of every parameter from dout = dL/d(out); `grads` mirrors `params` (running statistics unused).  Must follow the
-// forward of the same batch on the same workspace; x is the forward's input.
-extern "C" int mural_indel_train_backward(const MuralIndelShape* shape, const MuralIndelParams* params, const MuralIndelParams* grads,
-                                          const float* x, const float* dout, int64_t B, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
-                                          void* workspace, size_t workspace_bytes, void* stream_) {
-  MURAL_REQUIRE(shape && params && grads && x && dout && workspace, "NULL argument");
+// forward of the same batch on the same workspace; x / sym is the forward's input, in the forward's form.
+static int train_backward(const MuralIndelShape* shape, const MuralIndelParams* params, const MuralIndelParams* grads, const float* x,
+                          const uint8_t* sym, const float* dout, int64_t B, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
+                          void* workspace, size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(shape && params && grads && (x || sym) && dout && workspace, "NULL argument");
   if (int rc = check_params(*shape, *params, false)) return rc;
   if (int rc = check_params(*shape, *grads, true)) return rc;
   Plan P;
-  if (int rc = make_plan(*shape, params, grads, x, B, workspace, &P)) return rc;
+  if (int rc = make_plan(*shape, params, grads, sym != nullptr, B, workspace, &P)) return rc;
   MURAL_REQUIRE(workspace_bytes >= P.bytes, "workspace too small");
   hipStream_t st = (hipStream_t)stream_;
   const MuralIndelParams &p = *params, &g = *grads;
@@ -489,16 +528,29 @@ extern "C" int mural_indel_train_backward(const MuralIndelShape* shape, const Mu
       // Both are the same module: the second call's parameter gradients go to a scratch and are added to the first's.
       const Unit &s_a = P.u[0], &s_b = P.u[1];
       const int nW = 4 * 4 * s_a.K;
-      if (int rc = unit_bwd(P, s_a, x, dh0, nullptr, nullptr, s_a.gW, s_a.gbias, s_a.ggamma, s_a.gbeta, st)) return rc;
       float* dflip = P.g[0][0];
-      if (int rc = flip(dh0, nullptr, dflip, P.B, 4, P.Lx, 0, st)) return rc;
       float *tW = P.tmpW, *tb = P.tmpW + ((nW + 3) & ~3), *tg = tb + 4, *tbe = tg + 4;
-      if (int rc = unit_bwd(P, s_b, P.xf, dflip, nullptr, nullptr, tW, tb, tg, tbe, st)) return rc;
+      if (sym) {
+        // the two BatchNorm backwards leave the conv outputs' gradients in the units' z regions (the forward's z is spent once h0 is
+        // formed); ONE histogram pass over the symbol bytes then sums both applications' weight gradients into the module's slots
+        if (int rc = bn_post_bwd(dh0, s_a.y0, s_a.state, s_a.gamma, P.B, 4, P.Lx, 0, s_a.acc_b, s_a.z, s_a.ggamma, s_a.gbeta, st)) return rc;
+        if (int rc = flip(dh0, nullptr, dflip, P.B, 4, P.Lx, 0, st)) return rc;
+        if (int rc = bn_post_bwd(dflip, s_b.y0, s_b.state, s_b.gamma, P.B, 4, P.Lx, 0, s_b.acc_b, s_b.z, tg, tbe, st)) return rc;
+        if (int rc = indel_first_bwd(sym, s_a.z, s_b.z, P.B, P.Lx, 4, s_a.K, 1, s_a.pad, s_a.gW, s_a.gbias, s_a.part, s_a.part_floats, st)) return rc;
+      } else {
+        if (int rc = unit_bwd(P, s_a, x, dh0, nullptr, nullptr, s_a.gW, s_a.gbias, s_a.ggamma, s_a.gbeta, st)) return rc;
+        if (int rc = flip(dh0, nullptr, dflip, P.B, 4, P.Lx, 0, st)) return rc;
+        if (int rc = unit_bwd(P, s_b, P.xf, dflip, nullptr, nullptr, tW, tb, tg, tbe, st)) return rc;
+      }
       defer.flushed = true;
       if (int rc = wgrad_defer_flush(st)) return rc;
-      const Add4 j4{{s_a.gW, s_a.gbias, s_a.ggamma, s_a.gbeta}, {tW, tb, tg, tbe}, {nW, 4, 4, 4}};
+      const Add4 j4{{s_a.gW, s_a.gbias, s_a.ggamma, s_a.gbeta}, {tW, tb, tg, tbe}, {sym ? 0 : nW, sym ? 0 : 4, 4, 4}};
       hipLaunchKernelGGL(add4_kernel, dim3(4), dim3(128), 0, st, j4);
       MURAL_HIP_CHECK(hipGetLastError());
+    } else if (sym) {
+      if (int rc = bn_post_bwd(s1, ua.y0, ua.state, ua.gamma, P.B, ua.Cout, ua.Lout, ua.act, ua.acc_b, P.dy0, ua.ggamma, ua.gbeta, st)) return rc;
+      if (int rc = indel_first_bwd(sym, P.dy0, nullptr, P.B, P.Lx, ua.Cout, ua.K, ua.stride, ua.pad, ua.gW, ua.gbias, ua.part, ua.part_floats, st))
+        return rc;
     } else {
       if (int rc = unit_bwd(P, ua, unit_in[a], s1, nullptr, nullptr, ua.gW, ua.gbias, ua.ggamma, ua.gbeta, st)) return rc;
     }
@@ -508,4 +560,16 @@ extern "C" int mural_indel_train_backward(const MuralIndelShape* shape, const Mu
     return wgrad_defer_flush(st);
   }
   return MURAL_OK;
+}
+extern "C" int mural_indel_train_backward(const MuralIndelShape* shape, const MuralIndelParams* params, const MuralIndelParams* grads,
+                                          const float* x, const float* dout, int64_t B, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
+                                          void* workspace, size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(x, "NULL argument");
+  return train_backward(shape, params, grads, x, nullptr, dout, B, dropout_p, seed, seed_dev, workspace, workspace_bytes, stream_);
+}
+extern "C" int mural_indel_train_backward_symbols(const MuralIndelShape* shape, const MuralIndelParams* params, const MuralIndelParams* grads,
+                                                  const uint8_t* symbols, const float* dout, int64_t B, float dropout_p, uint64_t seed,
+                                                  const uint64_t* seed_dev, void* workspace, size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(symbols, "NULL argument");
+  return train_backward(shape, params, grads, nullptr, symbols, dout, B, dropout_p, seed, seed_dev, workspace, workspace_bytes, stream_);
 }

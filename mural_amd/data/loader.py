@@ -20,12 +20,13 @@ class EpochLoader:
     and with the values of ``train_batches_from_files``, for ``train_epoch``.
 
     ``distal_x`` is ``SymbolWindows`` over the uint8 (B, W) symbol tensor for SNV models -- the form their training forward takes in
-    place of the dense tensor, bit-identical to converting it.  With ``dense=True``, and always for ``model_type="indel"`` (the INDEL
-    training path, model/indel_train.py, takes the dense tensor only), it is the float32 (B, 4, W) one-hot tensor of the batch's rows,
-    written by the same launch.  Every batch owns freshly allocated tensors: a caller may keep any number of them."""
+    place of the dense tensor, bit-identical to converting it.  With ``dense=True``, and by default for ``model_type="indel"``, it is
+    the float32 (B, 4, W) one-hot tensor of the batch's rows, written by the same launch.  ``symbols=True`` asks for ``SymbolWindows``
+    from an INDEL loader too (``UNet_Small`` trains from them through model/indel_train_step.py: 1 byte per column instead of 16).
+    Every batch owns freshly allocated tensors: a caller may keep any number of them."""
 
     def __init__(self, fasta_path, bed_path, batch_size, local_radius, local_order=3, distal_radius=None, segment_center=300000,
-                 sampled_segments=10, model_type="snv", device="cuda", dense=False):
+                 sampled_segments=10, model_type="snv", device="cuda", dense=False, symbols=False):
         if model_type not in ("snv", "indel"):
             raise ValueError(f"model_type {model_type} not supported!")
         if distal_radius is None:
@@ -35,7 +36,9 @@ class EpochLoader:
         self.batch_size, self.sampled_segments = int(batch_size), int(sampled_segments)
         self.local_radius, self.local_order, self.distal_radius = int(local_radius), int(local_order), int(distal_radius)
         self.indel = model_type == "indel"
-        self.dense = bool(dense) or self.indel
+        if dense and symbols:
+            raise ValueError("EpochLoader: dense=True and symbols=True exclude each other")
+        self.dense = bool(dense) or (self.indel and not symbols)
         self.device = torch.device(device)
         odd = 0 if self.indel else 1
         self.cols, self.width = 2 * self.local_radius + odd - (self.local_order - 1), 2 * self.distal_radius + odd

@@ -1,4 +1,5 @@
-"""The INDEL training step as ONE autograd node over two C calls (include/mural_hip.h: mural_indel_train_forward / _backward).
+"""The INDEL training step as ONE autograd node over two C calls (include/mural_hip.h: mural_indel_train_forward / _backward, or
+their ``_symbols`` twins when the window comes as one symbol byte per column).
 
 ``UNet_Small.forward`` under ``model.train()`` (MuRaL/model/model_indel.py:151-176) inside the step of MuRaL/training.py:424-436: the
 per-unit composition of ``indel_train.py`` walks ~40 autograd nodes and issues ~340 launches from Python; here the composition lives
@@ -104,23 +105,25 @@ class ModelStep(torch.autograd.Function):
     def forward(ctx, model, x, drop_p, seed, seed_dev, *params):
         lay = _layout(model)
         dev = x.device
-        B, length = x.shape[0], x.shape[2]
+        symbols = x.dtype is torch.uint8          # (B, L) symbol bytes: the input form decides the entry, nothing else differs
+        B, length = x.shape[0], x.shape[-1]
         shape = _shape(model, length)
         lib = _lib.lib()
-        need = int(lib.mural_indel_train_workspace_bytes(C.byref(shape), B))
+        need = int((lib.mural_indel_train_symbols_workspace_bytes if symbols else lib.mural_indel_train_workspace_bytes)(C.byref(shape), B))
         if need == 0:
             raise ValueError(f"input length {length} is not compatible with down_list {list(model.downsize)}")
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         out = torch.empty((B, model.n_class), dtype=torch.float32, device=dev)
         ps = lay.params_struct()
-        _lib.check(lib.mural_indel_train_forward(C.byref(shape), C.byref(ps), x.data_ptr(), B, float(drop_p), int(seed),
-                                                 None if seed_dev is None else seed_dev.data_ptr(), MOMENTUM, out.data_ptr(), ws.data_ptr(),
-                                                 need, _lib.current_stream_ptr(dev)))
+        fwd = lib.mural_indel_train_forward_symbols if symbols else lib.mural_indel_train_forward
+        _lib.check(fwd(C.byref(shape), C.byref(ps), x.data_ptr(), B, float(drop_p), int(seed),
+                       None if seed_dev is None else seed_dev.data_ptr(), MOMENTUM, out.data_ptr(), ws.data_ptr(), need,
+                       _lib.current_stream_ptr(dev)))
         if lay.counters:
             torch._foreach_add_(lay.counters, 1)
         if lay.twice is not None:
             lay.twice.add_(1)
-        ctx.model, ctx.shape, ctx.ws, ctx.args, ctx.params = model, shape, ws, (x, drop_p, seed, seed_dev, B), params
+        ctx.model, ctx.shape, ctx.ws, ctx.args, ctx.params = model, shape, ws, (x, drop_p, seed, seed_dev, B, symbols), params
         return out
 
     @staticmethod
@@ -130,23 +133,30 @@ class ModelStep(torch.autograd.Function):
         if ws is None:
             raise RuntimeError("the INDEL training step keeps its saved activations for ONE backward (retain_graph=True is not supported: "
                                "run the forward again)")
-        x, drop_p, seed, seed_dev, B = ctx.args
+        x, drop_p, seed, seed_dev, B, symbols = ctx.args
         lay = _layout(model)
         dev = ws.device
         flat = torch.zeros(lay.total, dtype=torch.float32, device=dev)     # zero padding between the slots
         lay.last_flat = flat
         ps, gs = lay.params_struct(), lay.grads_struct(flat.data_ptr())
         dout = dout.contiguous()
-        _lib.check(_lib.lib().mural_indel_train_backward(C.byref(shape), C.byref(ps), C.byref(gs), x.data_ptr(), dout.data_ptr(), B,
-                                                         float(drop_p), int(seed), None if seed_dev is None else seed_dev.data_ptr(),
-                                                         ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(dev)))
+        bwd = _lib.lib().mural_indel_train_backward_symbols if symbols else _lib.lib().mural_indel_train_backward
+        _lib.check(bwd(C.byref(shape), C.byref(ps), C.byref(gs), x.data_ptr(), dout.data_ptr(), B, float(drop_p), int(seed),
+                       None if seed_dev is None else seed_dev.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(dev)))
         ctx.ws = None
         grads = {id(p): flat[o:o + p.numel()].view(p.shape) for p, o in zip(lay.plist, lay.poffs)}
         return (None,) * 5 + tuple(grads[id(p)] if p.numel() else torch.zeros_like(p) for p in ctx.params)
 
 
 def run(model, x):
-    """Training-mode forward of `model` (UNet_Small) on x float32 (B, 4, L)."""
+    """Training-mode forward of `model` (UNet_Small) on x float32 (B, 4, L), or on x uint8 (B, L): one MURAL_SYM_* symbol per window
+    column (``SymbolWindows.sym``), which takes the symbol entries -- the dense window is never built."""
+    if x.dtype is torch.uint8:
+        if x.dim() != 2:
+            raise ValueError(f"symbol windows must be uint8 (B, L), got {tuple(x.shape)}")
+    elif x.dtype is not torch.float32 or x.dim() != 3 or x.shape[1] != 4:
+        raise ValueError(f"the INDEL training step takes float32 (B, 4, L) or uint8 (B, L) symbols, got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
     from . import train_ops as T
     p = float(model.out_fc[1].p)
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0     # torch's CPU generator: torch.manual_seed applies

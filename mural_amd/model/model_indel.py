@@ -136,10 +136,25 @@ class UNet_Small(nn.Module):
             pass
 
     def forward(self, distal_input):
-        """Forward propagation of a batch: (B, 4, 2*distal_radius) fp32 one-hot -> (B, n_class) Softplus scores."""
+        """Forward propagation of a batch: (B, 4, 2*distal_radius) fp32 one-hot -> (B, n_class) Softplus scores.  ``SymbolWindows``
+        (uint8 (B, 2*distal_radius), one symbol per column) are taken in place of the dense tensor: the training step reads the bytes
+        themselves (model/indel_train_step.py), eval mode expands them to the dense window they stand for first."""
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("mural_amd models run on a HIP device only: call model.to('cuda') first")
+        from ..data.genome import SymbolWindows
+        if isinstance(distal_input, SymbolWindows):
+            sym = distal_input.sym
+            if sym.dim() != 2 or sym.dtype != torch.uint8:
+                raise TypeError("SymbolWindows.sym must be a uint8 (B, L) tensor")
+            sym = _lib.require_cuda(sym, "distal_input").contiguous()
+            with torch.cuda.device(dev):
+                if self.training and not __import__("os").environ.get("MURAL_INDEL_TRAIN_PER_UNIT"):
+                    from . import indel_train_step
+                    return indel_train_step.run(self, sym)
+                distal_input = torch.empty((sym.shape[0], 4, sym.shape[1]), dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib().mural_op_symbols_to_dense(sym.data_ptr(), sym.shape[0], sym.shape[1], distal_input.data_ptr(),
+                                                               _lib.current_stream_ptr(dev)))
         x = _lib.require_cuda(distal_input, "distal_input").to(torch.float32).contiguous()
         if x.dim() != 3 or x.shape[1] != 4:
             raise ValueError(f"distal_input must be (B, 4, L), got {tuple(x.shape)}")

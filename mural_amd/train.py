@@ -107,13 +107,21 @@ class GraphedIndelTrainStep(GraphedTrainStep):
     """The same for ``UNet_Small`` (one input tensor): ``step = GraphedIndelTrainStep(model, opt, crit, x, y); loss = step(x, y)``."""
 
     def __init__(self, model, optimizer, criterion, x, y, max_norm=10.0, warmup=3):
-        self._capture(model, optimizer, criterion, x, y, max_norm, warmup)
+        self._capture(model, optimizer, criterion, self._tensor(x), y, max_norm, warmup)
+
+    @staticmethod
+    def _tensor(x):
+        """The static input is a tensor: float32 (B, 4, L), or the uint8 (B, L) symbols (given as such or as ``SymbolWindows``)."""
+        return getattr(x, "sym", x)
 
     def _forward(self):
+        if self.x.dtype is torch.uint8:
+            from .data.genome import SymbolWindows
+            return self.model(SymbolWindows(self.x))
         return self.model(self.x)
 
     def __call__(self, x, y):
-        return self._replay(x, y)
+        return self._replay(self._tensor(x), y)
 
 
 class _CESum(torch.autograd.Function):
