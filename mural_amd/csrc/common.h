@@ -35,6 +35,27 @@ void ws_layout_reset();
 void ws_layout_add(size_t off, size_t bytes);
 extern thread_local std::vector<size_t> g_ws_layout;      // (offset, bytes) pairs, read by mural_debug_last_ws_layout
 
+// THE workspace carver: a bump pointer over the caller's workspace, regions at 256-byte offsets.  base == nullptr: a sizing run
+// (every region comes back nullptr, `off` ends at the bytes needed).  An empty region takes no space, no guard and no layout entry.
+struct WsArena {
+  char* base;
+  size_t off = 0;
+  size_t guard;           // validation only (MURAL_DEBUG_WS_GUARD above): unused bytes behind every region
+  explicit WsArena(void* b) : base(static_cast<char*>(b)), guard(ws_guard_bytes()) { ws_layout_reset(); }
+  void* take(size_t bytes) {
+    const size_t o = off;
+    if (bytes) ws_layout_add(o, bytes);
+    off = (off + bytes + (bytes ? guard : 0) + 255) & ~size_t(255);
+    return base ? base + o : nullptr;
+  }
+  template <typename T>
+  T* as(size_t n) { return static_cast<T*>(take(n * sizeof(T))); }
+  float* f(size_t n) { return as<float>(n); }
+  double* d(size_t n) { return as<double>(n); }
+  int32_t* i(size_t n) { return as<int32_t>(n); }
+  uint8_t* b(size_t n) { return as<uint8_t>(n); }
+};
+
 // dense (n, 4, L) one-hot / IUPAC-fraction windows -> one symbol byte per column (encode.hip).  A column that is no valid encoding
 // becomes N and sets MURAL_E_ENCODING in *status (bad_code < 0), or becomes bad_code without a report
 int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int32_t* status, hipStream_t stream, int bad_code = -1);

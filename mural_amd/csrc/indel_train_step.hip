@@ -92,20 +92,6 @@ struct Plan {
   size_t bytes = 0;
 };
 
-struct Arena {
-  char* base;
-  size_t off = 0, guard;
-  explicit Arena(void* b) : base(static_cast<char*>(b)), guard(ws_guard_bytes()) { ws_layout_reset(); }
-  void* take(size_t bytes) {
-    const size_t o = off;
-    if (bytes) ws_layout_add(o, bytes);
-    off = (off + bytes + (bytes ? guard : 0) + 255) & ~size_t(255);
-    return base ? base + o : nullptr;
-  }
-  float* f(size_t n) { return static_cast<float*>(take(n * 4)); }
-  double* d(size_t n) { return static_cast<double*>(take(n * 8)); }
-};
-
 int conv_out(int Lin, int K, int stride, int pad, int up) { return mural_op_convg_out_length(Lin, K, stride, pad, up); }
 
 // lays out the units and the workspace; base == nullptr: sizes only.  params / grads may be NULL for a sizing call.  symbols: the
@@ -132,7 +118,7 @@ int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralI
   }
   for (int i = IL - 1; i >= 1; --i)
     MURAL_REQUIRE(P.L[i] * sh.down[i] == P.L[i - 1], "input length %d is not compatible with down_list (level %d)", sh.length, i);
-  Arena A(base);
+  WsArena A(base);
   const size_t Bz = (size_t)P.B;
   auto mk = [&](const MuralAffine* cv, const float* w_only, const MuralBN* bn, const MuralAffine* gcv, const float* gw_only, const MuralBN* gbn,
                 int Cin, int Lin, int Cout, int k, int stride, int up, int act) {
@@ -188,7 +174,7 @@ int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralI
   }
   const int64_t n_out2 = (int64_t)P.C[0] * P.C[0];
   P.wt_total = total;
-  P.jobs_dev = static_cast<MuralRelayoutJob*>(A.take((size_t)kMaxJobs * sizeof(MuralRelayoutJob)));
+  P.jobs_dev = A.as<MuralRelayoutJob>(kMaxJobs);
   P.wt = A.f((size_t)2 * total);
   P.wt_out2 = A.f((size_t)n_out2);
   {
@@ -228,7 +214,7 @@ int make_plan(const MuralIndelShape& sh, const MuralIndelParams* p, const MuralI
   }
   P.o2 = A.f(l0);
   P.sp = A.f(l0);
-  P.arg = static_cast<int32_t*>(A.take(Bz * P.C[0] * 4));
+  P.arg = A.i(Bz * P.C[0]);
   P.feat = A.f(Bz * P.C[0]);
   P.fc_state = A.f((size_t)4 * P.C[0]);
   P.fbn = A.f(Bz * P.C[0]);

@@ -275,10 +275,8 @@ size_t plan_geometry(SnvFwdArgs& a, int Lwin, int P, int n_class, int towers = 3
 constexpr size_t kLdsTwoPerCu = 80 * 1024;
 constexpr size_t kLdsMax = 160 * 1024;
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct Workspace { float* local_logits; int64_t* cat; uint8_t* symbols; float* x0; float* xlogit; float* s3[2]; int* counters;
-                   float *vx0A, *vx0B, *vs3A, *vs3B; };      // long windows: the segments' inputs and pooled outputs
+                   float *vs3A, *vs3B; };      // long windows: the segments' pooled outputs (the segments are read in place from x0)
 
 // Sites whose short-stage launches are deferred into ONE launch per tower (run_towers): with the units at a fixed stride a launch takes
 // ceil(units / 2048 waves) unit-times, and a 131 072-site chunk gives the short stages 10.67 / 12.8 units per wave (3 % / 1.5 % of
@@ -289,51 +287,26 @@ int64_t super_chunk_sites(const MuralSnvModel* m) {
   return (m->split && !m->longwin && !off) ? SNV_SUPER * m->chunk : m->chunk;
 }
 
-// one_chunk: the layout whose short stages run per chunk (s3 / xlogit of one chunk: the smallest workspace a call accepts)
+// base == nullptr (and w == nullptr): sizes only.  one_chunk: the layout whose short stages run per chunk (s3 / xlogit of one chunk:
+// the smallest workspace a call accepts).  Network0 has no towers (chunk == 0): its x0 / xlogit / s3 regions are empty.
 size_t carve(const MuralSnvModel* m, int64_t n, bool dense, void* base, Workspace* w, bool one_chunk = false) {
-  size_t off = 0;
-  const size_t guard = ws_guard_bytes();      // 0 outside the validation tests (common.h)
-  ws_layout_reset();
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    ws_layout_add(o, bytes);
-    off = align_up(off + bytes + guard, 256);
-    return o;
-  };
-  const size_t o_ll = take((size_t)n * m->shape.n_class * 4);
-  const size_t o_cat = take((size_t)n * std::max(m->shape.local_cols, 1) * 8);
-  const size_t o_sym = take(dense ? (size_t)n * m->shape.distal_len : 16);
-  const size_t o_x0 = take((size_t)std::min<int64_t>(n, m->chunk) * std::max(m->args.x0_cols, 1) * SNV_C * 4);
+  Workspace sizing;
+  if (!w) w = &sizing;
+  WsArena A(base);
+  w->local_logits = A.f((size_t)n * m->shape.n_class);
+  w->cat = A.as<int64_t>((size_t)n * std::max(m->shape.local_cols, 1));
+  w->symbols = A.b(dense ? (size_t)n * m->shape.distal_len : 16);
+  w->x0 = A.f((size_t)std::min<int64_t>(n, m->chunk) * std::max(m->args.x0_cols, 1) * SNV_C);
   // (the short-stage launches run once per SUPER-chunk of up to SNV_SUPER chunks: their inputs and the mid logits are kept that long)
-  const int64_t s3_sites = std::min<int64_t>(n, one_chunk ? m->chunk : super_chunk_sites(m));
-  const size_t o_xl = take((size_t)s3_sites * SNV_MAXCLASS * 4);
-  const size_t o_s3l = take((size_t)s3_sites * std::max(m->args.geom[0].L[1], 1) * SNV_C * 4);
-  const size_t o_s3m = take((size_t)s3_sites * std::max(m->args.geom[1].L[1], 1) * SNV_C * 4);
-  const size_t o_cnt = take(64);      // unit counters of the wave-private launches of a chunk (SnvFwdArgs::unit_counter)
-  size_t o_vxa = 0, o_vxb = 0, o_vsa = 0, o_vsb = 0;
-  if (m->longwin) {
-    const size_t cn = (size_t)std::min<int64_t>(n, m->chunk);
-    (void)o_vxa;      // (until round 6 the segments were copied out of x0 with their halo: 0.6 GB per chunk of 8192 sites at R = 4000)
-    (void)o_vxb;
-    o_vsa = take(cn * m->lw_nA * m->args_lwA.geom[0].L[1] * SNV_C * 4);
-    o_vsb = take(cn * m->args_lwB.geom[0].L[1] * SNV_C * 4);
-  }
-  if (w) {
-    char* b = static_cast<char*>(base);
-    w->local_logits = reinterpret_cast<float*>(b + o_ll);
-    w->cat = reinterpret_cast<int64_t*>(b + o_cat);
-    w->symbols = reinterpret_cast<uint8_t*>(b + o_sym);
-    w->x0 = reinterpret_cast<float*>(b + o_x0);
-    w->xlogit = reinterpret_cast<float*>(b + o_xl);
-    w->s3[0] = reinterpret_cast<float*>(b + o_s3l);
-    w->s3[1] = reinterpret_cast<float*>(b + o_s3m);
-    w->counters = reinterpret_cast<int*>(b + o_cnt);
-    w->vx0A = reinterpret_cast<float*>(b + o_vxa);
-    w->vx0B = reinterpret_cast<float*>(b + o_vxb);
-    w->vs3A = reinterpret_cast<float*>(b + o_vsa);
-    w->vs3B = reinterpret_cast<float*>(b + o_vsb);
-  }
-  return off;
+  const size_t s3_sites = (size_t)std::min<int64_t>(n, one_chunk ? m->chunk : super_chunk_sites(m));
+  w->xlogit = A.f(s3_sites * SNV_MAXCLASS);
+  w->s3[0] = A.f(s3_sites * std::max(m->args.geom[0].L[1], 1) * SNV_C);
+  w->s3[1] = A.f(s3_sites * std::max(m->args.geom[1].L[1], 1) * SNV_C);
+  w->counters = A.as<int>(16);      // unit counters of the wave-private launches of a chunk (SnvFwdArgs::unit_counter)
+  const size_t cn = m->longwin ? (size_t)std::min<int64_t>(n, m->chunk) : 0;
+  w->vs3A = A.f(cn * m->lw_nA * m->args_lwA.geom[0].L[1] * SNV_C);
+  w->vs3B = A.f(cn * m->args_lwB.geom[0].L[1] * SNV_C);
+  return A.off;
 }
 
 // ---- long windows: segments of the large tower's pooled first-stage row (MuralSnvModel::longwin) -------------------------------

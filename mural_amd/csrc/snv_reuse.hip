@@ -228,8 +228,6 @@ __global__ __launch_bounds__(256) void reuse_rows_pool_kernel(const float* __res
   }
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct ReuseWs {
   float* rows[2][11];       // per strand: FL FM ELl ELr EMl | T1 T2 T3 large | T1 T2 T3 mid
   int64_t* cat;
@@ -245,40 +243,23 @@ int64_t reuse_super_sites() {
   return off ? (int64_t)SNV_CHUNK : (int64_t)RU_SUPER * SNV_CHUNK;
 }
 
+// base == nullptr (and w == nullptr): sizes only
 size_t carve_reuse(const MuralSnvModel* m, int64_t n, int64_t span, int strands, void* base, ReuseWs* w) {
-  const int64_t nb = std::min<int64_t>(span, RU_CHUNK_SPAN) + m->shape.distal_len;
-  size_t off = 0;
-  const size_t guard = ws_guard_bytes();      // 0 outside the validation tests (common.h)
-  ws_layout_reset();
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    ws_layout_add(o, bytes);
-    off = align_up(off + bytes + guard, 256);
-    return o;
-  };
-  size_t o_rows[2][11];
+  ReuseWs sizing;
+  if (!w) w = &sizing;
+  const size_t nb = (size_t)(std::min<int64_t>(span, RU_CHUNK_SPAN) + m->shape.distal_len);
+  WsArena A(base);
   for (int st = 0; st < 2; ++st)
-    for (int i = 0; i < 11; ++i) o_rows[st][i] = ((strands >> st) & 1) ? take((size_t)nb * 32 * 4) : 0;
+    for (int i = 0; i < 11; ++i) w->rows[st][i] = ((strands >> st) & 1) ? A.f(nb * 32) : nullptr;
   // (the short-stage launches run once per RU_SUPER chunks, as in the per-window path: snv_model.hip, super_chunk_sites)
-  const int64_t ns = std::min<int64_t>(std::max<int64_t>(n, 1), reuse_super_sites());
-  const size_t o_cat = take((size_t)ns * std::max(m->shape.local_cols, 1) * 8);
-  const size_t o_ll = take((size_t)ns * m->shape.n_class * 4);
-  const size_t o_xl = take((size_t)ns * SNV_MAXCLASS * 4);
-  const size_t o_s3l = take((size_t)ns * std::max(m->args.geom[0].L[1], 1) * SNV_C * 4);
-  const size_t o_s3m = take((size_t)ns * std::max(m->args.geom[1].L[1], 1) * SNV_C * 4);
-  const size_t o_cnt = take(64);      // unit counters of the wave-private launches (SnvFwdArgs::unit_counter)
-  if (w) {
-    char* b = static_cast<char*>(base);
-    for (int st = 0; st < 2; ++st)
-      for (int i = 0; i < 11; ++i) w->rows[st][i] = ((strands >> st) & 1) ? reinterpret_cast<float*>(b + o_rows[st][i]) : nullptr;
-    w->cat = reinterpret_cast<int64_t*>(b + o_cat);
-    w->local_logits = reinterpret_cast<float*>(b + o_ll);
-    w->xlogit = reinterpret_cast<float*>(b + o_xl);
-    w->s3[0] = reinterpret_cast<float*>(b + o_s3l);
-    w->s3[1] = reinterpret_cast<float*>(b + o_s3m);
-    w->counters = reinterpret_cast<int*>(b + o_cnt);
-  }
-  return off;
+  const size_t ns = (size_t)std::min<int64_t>(std::max<int64_t>(n, 1), reuse_super_sites());
+  w->cat = A.as<int64_t>(ns * std::max(m->shape.local_cols, 1));
+  w->local_logits = A.f(ns * m->shape.n_class);
+  w->xlogit = A.f(ns * SNV_MAXCLASS);
+  w->s3[0] = A.f(ns * std::max(m->args.geom[0].L[1], 1) * SNV_C);
+  w->s3[1] = A.f(ns * std::max(m->args.geom[1].L[1], 1) * SNV_C);
+  w->counters = A.as<int>(16);      // unit counters of the wave-private launches (SnvFwdArgs::unit_counter)
+  return A.off;
 }
 
 // sites per tile of the interior-gather bound below (RU_POOL_SLOTS): as many as keep <= SNV_NB2MAX blocks per wave

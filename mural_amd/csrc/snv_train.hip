@@ -26,23 +26,6 @@ namespace {
 constexpr int TR_C = 32;
 constexpr size_t ACC_DOUBLES_32 = (size_t)MURAL_BN_SLOTS * 2 * TR_C;
 
-struct Arena {            // bump allocator over the caller's workspace; base == nullptr: dry run that only measures
-  char* base;
-  size_t off = 0;
-  size_t guard;           // validation only (MURAL_DEBUG_WS_GUARD, common.h): unused bytes behind every region
-  explicit Arena(void* b) : base(static_cast<char*>(b)), guard(ws_guard_bytes()) { ws_layout_reset(); }
-  void* take(size_t bytes) {
-    const size_t o = off;
-    if (bytes) ws_layout_add(o, bytes);
-    off = (off + bytes + (bytes ? guard : 0) + 255) & ~size_t(255);
-    return base ? base + o : nullptr;
-  }
-  float* f(size_t n) { return static_cast<float*>(take(n * 4)); }
-  double* d(size_t n) { return static_cast<double*>(take(n * 8)); }
-  int32_t* i(size_t n) { return static_cast<int32_t*>(take(n * 4)); }
-  uint8_t* b(size_t n) { return static_cast<uint8_t*>(take(n)); }
-};
-
 struct TowerGeo { int L1, col0, L[3], pk[3], ps[3], pp[3]; };
 
 struct StageBufs {        // a run of two ResBlocks on [B][32][L]
@@ -96,7 +79,7 @@ struct Plan {
 
 int pool_len(int L, int k, int s, int p) { return (L + 2 * p - k) / s + 1; }
 
-void stage_bufs(Arena& A, StageBufs& s, size_t n) {
+void stage_bufs(WsArena& A, StageBufs& s, size_t n) {
   for (int i = 0; i < 4; ++i) {
     s.t[i] = A.f(n);
     s.state[i] = A.f(4 * TR_C);
@@ -110,7 +93,7 @@ int make_plan(const MuralSnvShape& sh, int64_t B, void* ws, Plan* P) {
   P->B = (int)B;
   P->nc = sh.n_class;
   P->Lwin = sh.distal_len;
-  Arena A(ws);
+  WsArena A(ws);
   const bool towers = sh.model_no != 0, local = sh.model_no != 1;
   size_t max_act = 0;
   if (towers) {
@@ -173,7 +156,7 @@ int make_plan(const MuralSnvShape& sh, int64_t B, void* ws, Plan* P) {
       b.acc_c2_f = A.d(ACC_DOUBLES_32); b.acc_c2_b = A.d(ACC_DOUBLES_32);
       b.acc_c3_f = A.d(ACC_DOUBLES_32); b.acc_c3_b = A.d(ACC_DOUBLES_32);
       b.acc_fc_f = A.d(ACC_DOUBLES_32); b.acc_fc_b = A.d(ACC_DOUBLES_32);
-      b.counts = static_cast<unsigned long long*>(A.take(16 * 8));     // symbol histogram of the first layer (forward only)
+      b.counts = A.as<unsigned long long>(16);     // symbol histogram of the first layer (forward only)
     }
   }
   if (local) {

@@ -8,7 +8,6 @@ differentiable per-layer HIP ops of ``indel_train.py`` in training mode.  No CPU
 """
 import ctypes as C
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -89,27 +88,8 @@ class UNet_Small(nn.Module):
         return tuple([(t.data_ptr(), t._version) for t in self._plist])
 
     def _params(self, keep):
-        def ptr(t):
-            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            keep.append(a)
-            return a.ctypes.data_as(C.c_void_p)
-
-        bn = lambda m: _lib.MuralBN(ptr(m.weight), ptr(m.bias), ptr(m.running_mean), ptr(m.running_var))
-        aff = lambda m: _lib.MuralAffine(ptr(m.weight), ptr(m.bias))
-        convbn = lambda conv, b: _lib.MuralConvBN(aff(conv), bn(b))
-        block = lambda cb: _lib.MuralConvBlock(ptr(cb.conv[0].weight), bn(cb.conv[1]), ptr(cb.conv[3].weight), bn(cb.conv[4]))
-        p = _lib.MuralIndelParams()
-        if self.use_reverse:
-            p.sym = convbn(self.conv[0], self.conv[1])
-        for i in range(self.N_LEVELS):
-            p.up_l[i] = convbn(self.uplblocks[i][0], self.uplblocks[i][1])
-            p.up_b[i] = block(self.upblocks[i][0])
-        for j in range(self.N_LEVELS - 1):
-            p.down_l[j] = convbn(self.downlblocks[j][1], self.downlblocks[j][2])
-            p.down_b[j] = block(self.downblocks[j][0])
-        p.out1, p.out_bn, p.out2 = aff(self.out_conv[0]), bn(self.out_conv[1]), aff(self.out_conv[3])
-        p.fc_bn, p.fc = bn(self.out_fc[0]), aff(self.out_fc[2])
-        return p
+        from .step_layout import fill_indel, host_copy_ptr
+        return fill_indel(self, host_copy_ptr(keep))
 
     def _get_handle(self, length):
         key = (length, self._state_key())

@@ -15,11 +15,11 @@ There is no CPU path.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _lib
+from .step_layout import _HostParams      # parameter hand-over to the C ABI
 
 POOLS_MID = ((3, 3, 1), (3, 3, 1), (3, 3, 1))          # model_snv.py:356,361,371
 POOLS_LARGE = ((15, 15, 7), (7, 7, 3), (3, 3, 1))      # model_snv.py:399,404,414
@@ -71,50 +71,6 @@ def _add_tower(mod, sfx, in_channels, out_channels, kernel_size, pools, dropout,
     setattr(mod, "conv3" + sfx, bn_conv(out_channels, relu=True))
     setattr(mod, "distal_fc1" if sfx == "" else "distal_fc2",
             nn.Sequential(nn.BatchNorm1d(out_channels), nn.Dropout(dropout), nn.Linear(out_channels, n_class)))
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# parameter hand-over to the C ABI
-# ---------------------------------------------------------------------------------------------------------------
-class _HostParams:
-    """Keeps contiguous fp32 host copies alive while the C side reads them."""
-
-    def __init__(self):
-        self.keep = []
-
-    def ptr(self, t):
-        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-        self.keep.append(a)
-        return a.ctypes.data_as(C.c_void_p)
-
-    def bn(self, m):
-        return _lib.MuralBN(self.ptr(m.weight), self.ptr(m.bias), self.ptr(m.running_mean), self.ptr(m.running_var))
-
-    def affine(self, m):
-        return _lib.MuralAffine(self.ptr(m.weight), self.ptr(m.bias))
-
-    def resblock(self, rb):
-        return _lib.MuralResBlock(self.bn(rb.bn1), self.affine(rb.conv1), self.bn(rb.bn2), self.affine(rb.conv2))
-
-    def tower(self, mod, sfx):
-        g = lambda n: getattr(mod, n + sfx)
-        fc = mod.distal_fc1 if sfx == "" else mod.distal_fc2
-        t = _lib.MuralTower()
-        t.bn_in, t.conv_in = self.bn(g("conv1")[0]), self.affine(g("conv1")[1])
-        t.rbs1[0], t.rbs1[1] = self.resblock(g("RBs1")[0]), self.resblock(g("RBs1")[1])
-        t.bn_mid, t.conv_mid = self.bn(g("conv2")[0]), self.affine(g("conv2")[1])
-        t.rbs2[0], t.rbs2[1] = self.resblock(g("RBs2")[0]), self.resblock(g("RBs2")[1])
-        t.bn_out, t.conv_out = self.bn(g("conv3")[0]), self.affine(g("conv3")[1])
-        t.fc_bn, t.fc = self.bn(fc[0]), self.affine(fc[2])
-        return t
-
-    def local(self, mod, out_layer):
-        l = _lib.MuralLocal()
-        l.emb = self.ptr(mod.emb_layer.weight)
-        l.lin[0], l.lin[1] = self.affine(mod.lin_layers[0]), self.affine(mod.lin_layers[1])
-        l.bn[0], l.bn[1] = self.bn(mod.bn_layers[0]), self.bn(mod.bn_layers[1])
-        l.out = self.affine(out_layer)
-        return l
 
 
 class _on_device:
@@ -563,8 +519,7 @@ class FeedForwardNN(_HipSnvBase):
 
     def _shape_and_params(self):
         hp = _HostParams()
-        params = _lib.MuralSnvParams()
-        params.local = hp.local(self, self.output_layer)
+        params = hp.fill(self)
         shape = _shape(0, self.n_class, self.no_of_cat, self.emb_layer.num_embeddings, self.lin_layers[0].out_features,
                        self.lin_layers[1].out_features)
         return shape, params, hp
@@ -638,8 +593,7 @@ class Network1(_HipSnvBase):
 
     def _shape_and_params(self):
         hp = _HostParams()
-        params = _lib.MuralSnvParams()
-        params.mid, params.large = hp.tower(self, ""), hp.tower(self, "_2")
+        params = hp.fill(self)
         shape = _shape(1, self.n_class, channels=self.out_channels, ksize=self.kernel_size, distal_len=self.seq_len)
         return shape, params, hp
 
@@ -683,9 +637,7 @@ class Network2(_HipSnvBase):
 
     def _shape_and_params(self):
         hp = _HostParams()
-        params = _lib.MuralSnvParams()
-        params.local = hp.local(self, self.local_fc[0])
-        params.mid, params.large = hp.tower(self, ""), hp.tower(self, "_2")
+        params = hp.fill(self)
         shape = _shape(2, self.n_class, self.no_of_cat, self.emb_layer.num_embeddings, self.lin_layers[0].out_features,
                        self.lin_layers[1].out_features, self.out_channels, self.kernel_size, self.seq_len)
         return shape, params, hp

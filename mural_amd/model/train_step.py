@@ -22,7 +22,6 @@ last step's gradients for accumulation or logging gets a fresh buffer instead of
 """
 import os
 import sys
-import weakref
 
 import ctypes as C
 
@@ -30,102 +29,17 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import step_layout
+from .step_layout import layout_of_params      # noqa: F401  (mural_amd.train imports it from here)
 
 MOMENTUM = 0.1
-_SLOTS = C.sizeof(_lib.MuralSnvParams) // 8          # the parameter struct is a flat run of pointers
-
-
-_LAYOUT_OF = {}      # id(first parameter) -> (weak reference to that parameter, weak reference to the layout): mural_amd.train.Adam finds it
-
-
-def layout_of_params(params):
-    """The layout whose parameter list is exactly `params` (any order), or None."""
-    if not params or not _LAYOUT_OF:
-        return None
-    for p in params:
-        hit = _LAYOUT_OF.get(id(p))
-        if hit is not None and hit[0]() is p:
-            lay = hit[1]()
-            if lay is not None and len(lay.plist) == len(params) and {id(q) for q in lay.plist} == {id(q) for q in params}:
-                return lay
-    return None
-
-
-class _Layout:
-    """Which tensor sits in which pointer slot of MuralSnvParams, found by building the struct once with slot tokens."""
-
-    def __init__(self, model):
-        from .model_snv import _HostParams
-        tensors = []
-
-        class Tok(_HostParams):
-            def ptr(self, t):
-                tensors.append(t)
-                return C.c_void_p(len(tensors))            # token = 1-based index into `tensors`
-
-        tok = Tok()
-        params = _lib.MuralSnvParams()
-        if model.model_no != 1:
-            params.local = tok.local(model, model.output_layer if model.model_no == 0 else model.local_fc[0])
-        if model.model_no != 0:
-            params.mid, params.large = tok.tower(model, ""), tok.tower(model, "_2")
-        raw = np.frombuffer(bytes(params), dtype=np.int64)
-        assert raw.shape[0] == _SLOTS
-        self.slot_tensor = [tensors[v - 1] if v else None for v in raw.tolist()]
-        self.params_all = list(model.parameters())     # cached: walking the module tree costs ~0.2 ms per step
-        self.plist = [p for p in self.params_all if p.numel()]
-        self.model_ref = weakref.ref(model)
-        if self.plist:
-            for k in [k for k, (r, _) in _LAYOUT_OF.items() if r() is None]:      # (entries of models that are gone)
-                del _LAYOUT_OF[k]
-            _LAYOUT_OF[id(self.plist[0])] = (weakref.ref(self.plist[0]), weakref.ref(self))
-        self.last_flat = None                          # the flat buffer behind the .grad views of the latest backward (clip_grad_norm_)
-        self.own_flat = None                           # direct-gradient mode: the buffer and the views into it, created once
-        self.own_views = None
-        self.own_base = None                           # holder counts of own_flat / own_views when they were made (_holder_counts)
-        index = {id(p): i for i, p in enumerate(self.plist)}
-        # gradient slots: offset of each parameter in one flat float32 buffer (running statistics have none)
-        offs, o = [], 0
-        for p in self.plist:
-            offs.append(o)
-            o += (p.numel() + 63) // 64 * 64
-        self.total = o
-        self.poffs = offs
-        self.grad_off = np.full(_SLOTS, -1, np.int64)
-        for s, t in enumerate(self.slot_tensor):
-            if t is not None and id(t) in index:
-                self.grad_off[s] = offs[index[id(t)]] * 4
-        self.has_grad = self.grad_off >= 0
-        self.counters = [m.num_batches_tracked for m in model.modules()
-                         if isinstance(m, torch.nn.BatchNorm1d) and m.num_batches_tracked is not None and m.weight.numel()]
-        seen, uniq = set(), []
-        for t in self.counters:                       # ResBlock registers its BatchNorms twice
-            if id(t) not in seen:
-                seen.add(id(t))
-                uniq.append(t)
-        self.counters = uniq
-
-    def params_struct(self):
-        for t in self.slot_tensor:
-            if t is not None and (t.dtype is not torch.float32 or not t.is_contiguous()):
-                raise RuntimeError("the HIP training step needs contiguous float32 parameters and buffers")
-        raw = np.array([0 if t is None else t.data_ptr() for t in self.slot_tensor], dtype=np.int64)
-        s = _lib.MuralSnvParams()
-        C.memmove(C.byref(s), raw.ctypes.data, _SLOTS * 8)
-        return s
-
-    def grads_struct(self, base):
-        raw = np.where(self.has_grad, self.grad_off + base, 0)
-        s = _lib.MuralSnvParams()
-        C.memmove(C.byref(s), raw.ctypes.data, _SLOTS * 8)
-        return s
 
 
 def _layout(model):
-    lay = getattr(model, "_train_layout", None)
-    if lay is None:
-        lay = model._train_layout = _Layout(model)
-    return lay
+    # no identity check of the cached layout: walking the module tree costs ~0.2 ms of a 1.6 ms step.  _apply / load_state_dict of the
+    # model clear _train_layout (model_snv._HipSnvBase)
+    return step_layout.FlatGradLayout.cached(
+        model, lambda m: step_layout.FlatGradLayout(m, _lib.MuralSnvParams, step_layout.fill_snv, register=True))
 
 
 def supported(model):
@@ -155,28 +69,21 @@ class ModelStep(torch.autograd.Function):
         B = (cat_x if cat_x is not None else symbols).shape[0]
         lib = _lib.lib()
         need = int(lib.mural_snv_train_workspace_bytes(C.byref(shape), B))
-        if need == 0:
-            _lib.check(_lib.MURAL_E_INVALID)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        out = torch.empty((B, model.n_class), dtype=torch.float32, device=dev)
+        ws, out = step_layout.step_buffers(torch, need, B, model.n_class, dev)
         ps = lay.params_struct()
         stream = _lib.current_stream_ptr(dev)
         _lib.check(lib.mural_snv_train_forward(C.byref(shape), C.byref(ps), None if cat_x is None else cat_x.data_ptr(), None,
                                                None if symbols is None else symbols.data_ptr(), B, drops.ctypes.data, seeds.ctypes.data,
                                                None if seed_dev is None else seed_dev.data_ptr(), MOMENTUM, out.data_ptr(), ws.data_ptr(),
                                                need, None, stream))
-        if lay.counters:
-            torch._foreach_add_(lay.counters, 1)
+        lay.bump_counters()
         ctx.model, ctx.shape, ctx.ws, ctx.args, ctx.params = model, shape, ws, (cat_x, drops, seeds, seed_dev, B), params
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
-        model, shape, ws = ctx.model, ctx.shape, ctx.ws
-        if ws is None:
-            raise RuntimeError("the SNV training step keeps its saved activations for ONE backward (retain_graph=True is not supported: "
-                               "run the forward again)")
+        model, shape, ws = ctx.model, ctx.shape, step_layout.saved_workspace(ctx, "SNV")
         cat_x, drops, seeds, seed_dev, B = ctx.args
         lay = _layout(model)
         dev = ws.device
@@ -189,13 +96,13 @@ class ModelStep(torch.autograd.Function):
             if lay.own_views is not None and not _views_are_ours(lay):
                 lay.own_flat = lay.own_views = None
             if lay.own_flat is None or lay.own_flat.device != dev:
-                lay.own_flat = torch.zeros(lay.total, dtype=torch.float32, device=dev)
-                lay.own_views = [lay.own_flat[o:o + p.numel()].view(p.shape) for p, o in zip(lay.plist, lay.poffs)]
+                lay.own_flat = lay.zero_flat(dev)
+                lay.own_views = lay.grad_views(lay.own_flat)
                 lay.own_base = _holder_counts(lay)
             flat = lay.own_flat      # every slot is rewritten by the call below; the padding between the slots stays zero
         else:
-            flat = torch.zeros(lay.total, dtype=torch.float32, device=dev)    # zero padding between the slots: the norm of the buffer
-        lay.last_flat = flat                                                   # is the norm of the gradients
+            flat = lay.zero_flat(dev)
+        lay.last_flat = flat
         ps, gs = lay.params_struct(), lay.grads_struct(flat.data_ptr())
         dout = dout.contiguous()
         _lib.check(_lib.lib().mural_snv_train_backward(C.byref(shape), C.byref(ps), C.byref(gs), None if cat_x is None else cat_x.data_ptr(),
@@ -208,15 +115,13 @@ class ModelStep(torch.autograd.Function):
                 for p, v in zip(lay.plist, lay.own_views):
                     p.grad = v
             else:
-                for p, o in zip(lay.plist, lay.poffs):
-                    g = flat[o:o + p.numel()].view(p.shape)
+                for p, g in zip(lay.plist, lay.grad_views(flat)):
                     if p.grad is None:
                         p.grad = g
                     else:
                         p.grad.add_(g)
-            return (None,) * (8 + len(ctx.params))
-        grads = {id(p): flat[o:o + p.numel()].view(p.shape) for p, o in zip(lay.plist, lay.poffs)}
-        return (None,) * 8 + tuple(grads[id(p)] if p.numel() else torch.zeros_like(p) for p in ctx.params)
+            return step_layout.node_grads(8, (None,) * len(ctx.params))
+        return step_layout.node_grads(8, lay.grads_for(ctx.params, flat))
 
 
 def _holder_counts(lay):

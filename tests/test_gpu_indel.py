@@ -681,6 +681,15 @@ def test_one_call_train_step_equals_per_unit_composition_and_keeps_to_its_worksp
     for (k, b), c in zip(model.named_buffers(), ref.buffers()):
         assert float((b.double() - c.double()).abs().max()) <= 1e-6 * max(1.0, float(c.double().abs().max())), k
     grads = {k: p.grad.clone() for k, p in model.named_parameters()}
+    # mural_amd.train.Adam on a UNet_Small (batch 4): its layout is not in the registry of the one-launch step, the update is torch's
+    from mural_amd.train import Adam
+    stepped = fresh()
+    optimizer = Adam(stepped.parameters(), lr=1e-3)
+    _train_step(stepped, x[:4], y[:4])
+    before = [p.detach().clone() for p in stepped.parameters()]
+    optimizer.step()
+    assert stepped._train_layout.last_flat is not None and optimizer._flat is None
+    assert any(not torch.equal(p, q) for p, q in zip(stepped.parameters(), before))
     # poisoned allocations
     monkeypatch.setattr(ITS, "torch", _PoisonedTorch())
     model2 = fresh()
