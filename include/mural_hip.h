@@ -421,6 +421,34 @@ int mural_op_clip_grad_norm(float* flat, int64_t n, float max_norm, double* scra
 int mural_op_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                        double beta2, double eps, double weight_decay, int64_t step, void* stream);
 
+/* The state of a training loop that the HOST keeps in the reference (Adam's step count and bias corrections, the scheduled learning rate,
+ * the epoch's loss sum: MuRaL/training.py:432-450) as one 128-byte block in DEVICE memory (8-byte aligned, zeroed by the caller, lr set),
+ * so that a step captured into a HIP graph reads this step's values at every replay.  Only the tick kernel writes it; the caller writes
+ * fields between steps with ordinary stream-ordered copies and reads the block back when it wants the figures.                         */
+typedef struct MuralTrainState {
+  double lr;            /*   0: the learning rate of the NEXT update                                                    */
+  int64_t step;         /*   8: Adam updates done (the `step` of torch's optimizer state)                                */
+  int64_t ticks;        /*  16: scheduler ticks done (`last_epoch` of torch's StepLR)                                    */
+  double loss_sum;      /*  24: sum of the losses handed to the ticks, in double, in tick order                          */
+  int64_t rows;         /*  32: sum of the ticks' `rows`                                                                 */
+  int64_t steps_done;   /*  40: ticks since the caller last zeroed loss_sum / rows / steps_done                          */
+  float step_size;      /*  48: (float)(lr / (1 - beta1^step))   } what the latest tick left for                         */
+  float bc2_sqrt;       /*  52: (float)sqrt(1 - beta2^step)      } mural_op_adam_flat_state                              */
+  int64_t reserved[9];  /*  56: zero                                                                                     */
+} MuralTrainState;
+
+/* One step of that state, one single-workgroup launch, in this order: step += 1; step_size / bc2_sqrt from the current lr (the host
+ * expressions of mural_op_adam_flat, in double, rounded once); if loss (device float*, may be NULL): loss_sum += *loss, rows += rows;
+ * steps_done += 1; then the scheduler tick -- torch's chainable StepLR plus the reference's restart rule (training.py:444-450), IEEE double
+ * operations in the host's order: ticks += 1; if sched_step_size > 0 and ticks % sched_step_size == 0: lr *= gamma; if lr < min_lr: lr =
+ * restart_lr.  sched_step_size == 0: no per-step scheduler (min_lr = 0 then switches the restart rule off as well).                    */
+int mural_op_train_state_tick(MuralTrainState* state, const float* loss, int64_t rows, double beta1, double beta2,
+                              int64_t sched_step_size, double gamma, double min_lr, double restart_lr, void* stream);
+/* mural_op_adam_flat with step_size / bc2_sqrt read from *state (left there by the tick enqueued before it): same update, vector width,
+ * grid and argument checks.  Reads the block, never writes it.                                                                        */
+int mural_op_adam_flat_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const MuralTrainState* state,
+                             double beta1, double beta2, double eps, double weight_decay, void* stream);
+
 /* Long windows (distal_radius from ~15000 up to the first-stage kernel's LDS limit) whose second conv stage fits no fused kernel: the
  * handle is FRONT-ONLY (mural_snv_tap_layout()[10] == 1; the forward entries above refuse it) and this entry runs what still is fused --
  * window decode + first layer + pool (model_snv.py:473-476 of the large tower) and its first ResBlock stage on halo'd segments of the

@@ -42,4 +42,34 @@ int local_train_bwd(const int64_t* cat, int cols, int emb_rows, int64_t B, const
                     float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta, float* dE, hipStream_t stream);
 namespace ltrain { extern unsigned long long* g_lt_stamps; }      // diagnostic (mural_debug_lt_set_stamps)
 
+// The flat Adam step behind its two entries: mural_op_adam_flat (train_ops.hip: step_size / bc2_sqrt formed on the host) and
+// mural_op_adam_flat_state (train_state.hip: read from a MuralTrainState block).  One argument check, one grid, one element loop.
+int adam_flat_check(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq, int64_t n, double beta1,
+                    double beta2, double eps, double weight_decay);
+int adam_flat_grid(int64_t n4);
+//   g' = g + weight_decay p;  m = m + (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g';
+//   p = p - step_size m / (sqrt(v) / bc2_sqrt + eps)          with step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)
+// (torch's fused kernel's update, in float) over n4 float4 groups, grid-strided.
+__device__ __forceinline__ void adam_flat_elements(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n4, float w1, float beta2, float w2, float step_size,
+                                                   float bc2_sqrt, float eps, float wd) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float* pp = &pv.x; float* mp = &mv.x; float* vp = &vv.x;
+    const float* gp = &gv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gk = gp[k] + wd * pp[k];
+      mp[k] = mp[k] + (gk - mp[k]) * w1;
+      vp[k] = beta2 * vp[k] + w2 * gk * gk;
+      const float denom = sqrtf(vp[k]) / bc2_sqrt + eps;
+      pp[k] = pp[k] - step_size * mp[k] / denom;
+    }
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+}
+
 }  // namespace mural

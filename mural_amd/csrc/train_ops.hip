@@ -1628,38 +1628,30 @@ extern "C" int mural_op_ce_sum_bwd(const float* prob, const int64_t* y, const fl
 // at the end of every step with nothing beside them).  The update is torch's fused kernel's, in float:
 //   g' = g + weight_decay p;  m = m + (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g';
 //   p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
-// (the bias corrections come from the host in double, rounded once).
+// (the bias corrections come from the host in double, rounded once; the element loop is train_ops.h's, shared with the entry that
+// reads them from a device block: train_state.hip).
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, int64_t n4, float w1, float beta2, float w2, float step_size,
                                                         float bc2_sqrt, float eps, float wd) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float* pp = &pv.x; float* mp = &mv.x; float* vp = &vv.x;
-    const float* gp = &gv.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gk = gp[k] + wd * pp[k];
-      mp[k] = mp[k] + (gk - mp[k]) * w1;
-      vp[k] = beta2 * vp[k] + w2 * gk * gk;
-      const float denom = sqrtf(vp[k]) / bc2_sqrt + eps;
-      pp[k] = pp[k] - step_size * mp[k] / denom;
-    }
-    reinterpret_cast<float4*>(p)[i] = pv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
+  adam_flat_elements(p, g, m, v, n4, w1, beta2, w2, step_size, bc2_sqrt, eps, wd);
 }
-extern "C" int mural_op_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
-                                  double beta2, double eps, double weight_decay, int64_t step, void* stream) {
+int mural::adam_flat_check(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq, int64_t n, double beta1,
+                           double beta2, double eps, double weight_decay) {
   MURAL_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 0 && (n & 3) == 0, "adam_flat: NULL buffer or a length that is no multiple of 4");
-  MURAL_REQUIRE(step >= 1 && lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0,
+  MURAL_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0,
                 "adam_flat: step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0, weight_decay >= 0");
   MURAL_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
                   reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0, "adam_flat: buffers must be 16-byte aligned");
+  return MURAL_OK;
+}
+int mural::adam_flat_grid(int64_t n4) { return grid_for(n4); }
+extern "C" int mural_op_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
+                                  double beta2, double eps, double weight_decay, int64_t step, void* stream) {
+  if (const int rc = adam_flat_check(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, weight_decay)) return rc;
+  MURAL_REQUIRE(step >= 1 && lr >= 0, "adam_flat: step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0, weight_decay >= 0");
   if (n == 0) return MURAL_OK;
   const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
-  hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n / 4)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq, n / 4, (float)(1.0 - beta1),
+  hipLaunchKernelGGL(adam_flat_kernel, dim3(adam_flat_grid(n / 4)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq, n / 4, (float)(1.0 - beta1),
                      (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps, (float)weight_decay);
   CHECK_LAUNCH();
 }

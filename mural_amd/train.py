@@ -6,7 +6,9 @@ captures one step into a HIP graph (``torch.cuda.CUDAGraph``) and replays it: th
 
 Differences from a plain loop, all of them the usual graph-capture contract:
   * batch shapes are fixed at capture; inputs are copied into static tensors before every replay;
-  * the optimizer must be capturable (``torch.optim.Adam(..., capturable=True)``) and is stepped inside the graph;
+  * the optimizer must be capturable and is stepped inside the graph: ``torch.optim.Adam(..., capturable=True)`` (torch's multi-tensor
+    sequence), or ``mural_amd.train.Adam(..., device_state=DeviceStepState(...))`` -- the one-launch step with its step count, bias
+    corrections and scheduled learning rate in a device block that a tick kernel advances inside the graph (csrc/train_state.hip);
   * dropout masks: the host-drawn seeds are baked into the graph, a device-resident counter advanced inside the graph is
     added to them, so every replay draws new masks (``train_ops.set_device_seed``);
   * the encoding check of ``distal_x`` (ValueError on a non-MuRaL column) is read back after the replay, one step late.
@@ -24,7 +26,13 @@ from ._host import freeze_host_heap  # noqa: E402,F401  (re-exported: train_epoc
 class GraphedTrainStep:
     def __init__(self, model, optimizer, criterion, cont_x, cat_x, distal_x, y, max_norm=10.0, warmup=3):
         self.cont, self.cat = (None if t is None else t.clone() for t in (cont_x, cat_x))
-        self._capture(model, optimizer, criterion, distal_x, y, max_norm, warmup)
+        self._capture(model, optimizer, criterion, self._tensor(distal_x), y, max_norm, warmup)
+
+    @staticmethod
+    def _tensor(x):
+        """The static input is a tensor: the dense float (B, 4, L) windows, or the uint8 (B, L) symbols (given as such or as
+        ``SymbolWindows``, the form ``EpochLoader`` yields)."""
+        return getattr(x, "sym", x)
 
     def _capture(self, model, optimizer, criterion, distal_x, y, max_norm, warmup):
         dev = distal_x.device
@@ -63,16 +71,22 @@ class GraphedTrainStep:
         self.opt.zero_grad(set_to_none=True)
         self.loss.backward()
         clip_grad_norm_(self.model, self.max_norm)
+        state = getattr(self.opt, "device_state", None)
+        if state is not None:                  # the step's tick adds this loss to the block's sum (no launch of its own)
+            state.observe(self.loss, self.y.shape[0])
         self.opt.step()
 
     def _forward(self):
+        if self.x.dtype is torch.uint8:
+            from .data.genome import SymbolWindows
+            return self.model((self.cont, self.cat), SymbolWindows(self.x))
         return self.model((self.cont, self.cat), self.x)
 
     def __call__(self, cont_x, cat_x, distal_x, y):
         """Run one training step on this batch; returns the (device) loss tensor of the step."""
         self.cont.copy_(cont_x, non_blocking=True)
         self.cat.copy_(cat_x, non_blocking=True)
-        return self._replay(distal_x, y)
+        return self._replay(self._tensor(distal_x), y)
 
     def _replay(self, distal_x, y):
         self._check()
@@ -108,11 +122,6 @@ class GraphedIndelTrainStep(GraphedTrainStep):
 
     def __init__(self, model, optimizer, criterion, x, y, max_norm=10.0, warmup=3):
         self._capture(model, optimizer, criterion, self._tensor(x), y, max_norm, warmup)
-
-    @staticmethod
-    def _tensor(x):
-        """The static input is a tensor: float32 (B, 4, L), or the uint8 (B, L) symbols (given as such or as ``SymbolWindows``)."""
-        return getattr(x, "sym", x)
 
     def _forward(self):
         if self.x.dtype is torch.uint8:
@@ -205,6 +214,102 @@ def clip_grad_norm_(model, max_norm):
     return total
 
 
+def _schedule(config, train_size=None):
+    kind = config["lr_scheduler"]
+    if kind == "StepLR":
+        return (5000 * 128) // config["batch_size"], float(config["LR_gamma"]), float(config["min_lr"]), float(config["restart_lr"])
+    if kind == "StepLR2":
+        gamma = (config["min_lr"] / config["restart_lr"]) ** (1 / (train_size // config["batch_size"]))
+        return 1, float(gamma), float(config["min_lr"]), float(config["restart_lr"])
+    if kind == "ROP":           # ReduceLROnPlateau: the host writes the rate between epochs (set_lr); train_epoch applies no restart rule
+        return 0, 1.0, 0.0, 0.0
+    raise ValueError(f"unknown lr_scheduler {kind}")
+
+
+class DeviceStepState:
+    """What the reference's loop keeps on the host between steps (training.py:432-450), as one ``MuralTrainState`` block in device memory
+    (include/mural_hip.h): the learning rate, Adam's step count and the two bias-correction factors of the coming update, the per-batch
+    scheduler's tick count, the epoch's loss sum / rows / steps.  ``mural_op_train_state_tick`` advances it once per step -- inside a
+    captured graph too, which is what lets ``GraphedTrainStep`` replay ``Adam(..., device_state=...)`` with a moving step count and a
+    scheduled rate -- and nothing is read back until somebody asks (``read``: one synchronising copy).
+
+    The BLOCK holds the learning rate of an optimiser built on it, not ``param_groups`` (they are brought up to date whenever a step
+    goes through torch, and by ``train_epoch_device`` at the end of an epoch); ``set_lr`` writes it."""
+
+    NO_SCHEDULE = (0, 1.0, 0.0, 0.0)
+
+    def __init__(self, device, lr, betas=(0.9, 0.999)):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"the step state lives on a HIP device (got {self.device}); mural_amd has no CPU path")
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.sched = self.NO_SCHEDULE          # (sched_step_size, gamma, min_lr, restart_lr) of the ticks to come
+        self.buf = torch.zeros(16, dtype=torch.int64, device=self.device)      # the 128 bytes; fields by word: mural_hip.h
+        self._f64 = self.buf.view(torch.float64)
+        self._loss, self._rows = None, 0
+        self.set_lr(lr)
+
+    # -- host writes (stream-ordered little fills; never inside a captured region) and the one read --------------------------------
+    def set_lr(self, lr):
+        self._f64[0:1].fill_(float(lr))
+
+    def set_step(self, step):
+        self.buf[1:2].fill_(int(step))
+
+    def reset_epoch(self):
+        """Zero loss_sum, rows and steps_done; step, ticks and lr stay."""
+        self.buf[3:6].zero_()
+
+    def read(self):
+        """The fields as a dict (ONE synchronising copy of the block)."""
+        w = self.buf.cpu().numpy()
+        d, f = w.view("float64"), w.view("float32")
+        return dict(lr=float(d[0]), step=int(w[1]), ticks=int(w[2]), loss_sum=float(d[3]), rows=int(w[4]), steps_done=int(w[5]),
+                    step_size=float(f[12]), bc2_sqrt=float(f[13]))
+
+    # -- the schedule ----------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def schedule(config, train_size=None):
+        """The reference's ``config`` -> (sched_step_size, gamma, min_lr, restart_lr) of the tick: what ``make_scheduler`` builds and
+        ``train_epoch`` applies per batch.  'ROP' has no per-batch part: (0, 1.0) and no restart rule."""
+        return _schedule(config, train_size)
+
+    def set_schedule(self, config, train_size=None):
+        self.sched = self.schedule(config, train_size)
+        return self.sched
+
+    @staticmethod
+    def lr_sequence(config, lr0, n, train_size=None, ticks0=0):
+        """Host mirror of the tick's scheduler: the learning rates of `n` consecutive updates that start at rate `lr0` with `ticks0`
+        ticks done -- the same double operations in the same order, hence the same bits as the device's and as the host loop's."""
+        k, gamma, min_lr, restart_lr = _schedule(config, train_size)
+        out, lr, ticks = [], float(lr0), int(ticks0)
+        for _ in range(n):
+            out.append(lr)
+            ticks += 1
+            if k > 0 and ticks % k == 0:
+                lr = lr * gamma
+            if lr < min_lr:
+                lr = restart_lr
+        return out
+
+    # -- the step --------------------------------------------------------------------------------------------------------------------
+    def observe(self, loss, rows):
+        """Remember the step's loss (a float32 device scalar) for the NEXT tick, which adds it to loss_sum and `rows` to rows."""
+        if not (torch.is_tensor(loss) and loss.is_cuda and loss.dtype is torch.float32 and loss.numel() == 1 and loss.device == self.buf.device):
+            raise ValueError("DeviceStepState.observe takes the loss as a float32 scalar on the state's device")
+        self._loss, self._rows = loss, int(rows)
+
+    def tick(self):
+        from . import _lib
+        loss, rows, self._loss, self._rows = self._loss, self._rows, None, 0
+        k, gamma, min_lr, restart_lr = self.sched
+        with torch.cuda.device(self.buf.device):
+            _lib.check(_lib.lib().mural_op_train_state_tick(self.buf.data_ptr(), None if loss is None else loss.data_ptr(), rows, self.betas[0],
+                                                            self.betas[1], int(k), float(gamma), float(min_lr), float(restart_lr),
+                                                            _lib.current_stream_ptr(self.buf.device)))
+
+
 class Adam(torch.optim.Adam):
     """``torch.optim.Adam`` (the reference's default optimiser, training.py:346-350, stepped at :432) with a ONE-launch step for a model
     whose training step runs in the library (model/train_step.py): there every gradient is a view of one flat buffer, so the
@@ -216,9 +321,15 @@ class Adam(torch.optim.Adam):
     Same constructor as ``torch.optim.Adam``.  Everything the one launch does not cover goes through ``torch.optim.Adam.step`` itself,
     on the same state tensors: more than one parameter group, amsgrad / maximize / capturable / differentiable, a tensor learning rate,
     a closure, parameters that are not exactly one HIP model's (or a model without the flat gradient buffer: UNet_Small, CPU), a gradient
-    that is not the latest backward's view.  ``state_dict`` / ``load_state_dict`` are torch's (step counters are materialised first)."""
+    that is not the latest backward's view.  ``state_dict`` / ``load_state_dict`` are torch's (step counters are materialised first).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
+    ``device_state=DeviceStepState(...)``: the step count, the bias corrections and the learning rate live in that device block, and
+    the step is two launches -- ``mural_op_train_state_tick`` (step += 1, the two factors from the block's rate, the observed loss added,
+    the per-batch scheduler) + ``mural_op_adam_flat_state`` -- that read nothing from the host, so ``GraphedTrainStep`` can capture them.
+    A step the flat kernel does not cover still goes through torch: the block's step and rate are read back first (into the step
+    counters and ``param_groups``) and the block is ticked all the same, so the two routes stay one sequence."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, device_state=None, **kw):
         params = list(params)
         if "fused" not in kw and "foreach" not in kw:      # torch's fused implementation for the steps that fall through, where it applies
             flat = [q for p in params for q in (p["params"] if isinstance(p, dict) else [p])]
@@ -226,11 +337,26 @@ class Adam(torch.optim.Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._flat = None          # (layout, params, param buffer, exp_avg buffer, exp_avg_sq buffer) while the one-launch step applies
         self._flat_t = 0           # updates done (the step counters of torch's state, materialised on demand)
+        if device_state is not None and tuple(float(b) for b in betas) != device_state.betas:
+            raise ValueError(f"betas {tuple(betas)} differ from the device state's {device_state.betas}")
+        self.device_state = device_state      # with one, the BLOCK counts the updates (_flat_t: its value at the last read-back)
 
     # -- torch's state <-> the flat buffers -----------------------------------------------------------------------------------
+    def _state_to_host(self):
+        """The block's step count and learning rate -> _flat_t and param_groups (one synchronising read)."""
+        r = self.device_state.read()
+        self._flat_t = r["step"]
+        for g in self.param_groups:
+            g["lr"] = r["lr"]
+
     def _materialise_steps(self):
         if self._flat is None:
             return
+        if self.device_state is not None:
+            self._state_to_host()
+        self._write_steps()
+
+    def _write_steps(self):
         g = self.param_groups[0]
         on_dev = bool(g.get("fused")) or bool(g.get("capturable"))
         for p in self._flat[1]:
@@ -266,7 +392,9 @@ class Adam(torch.optim.Adam):
             p.data = slot(pf)
             st["exp_avg"], st["exp_avg_sq"] = slot(mf), slot(vf)
         self._flat, self._flat_t = (lay, list(lay.plist), pf, mf, vf), int(t)
-        self._materialise_steps()
+        if self.device_state is not None:
+            self.device_state.set_step(int(t))      # torch's counters are the record while the flat layout is not entered
+        self._write_steps()
         return True
 
     def _flat_step(self):
@@ -293,11 +421,21 @@ class Adam(torch.optim.Adam):
                 return False
         from . import _lib
         b1, b2 = g["betas"]
-        self._flat_t += 1
-        with torch.cuda.device(pf.device):
-            _lib.check(_lib.lib().mural_op_adam_flat(pf.data_ptr(), gbase, mf.data_ptr(), vf.data_ptr(), pf.numel(), float(g["lr"]), float(b1),
-                                                     float(b2), float(g["eps"]), float(g["weight_decay"]), self._flat_t,
-                                                     _lib.current_stream_ptr(pf.device)))
+        st = self.device_state
+        if st is not None:
+            if st.buf.device != pf.device or (float(b1), float(b2)) != st.betas:
+                return False
+            st.tick()
+            with torch.cuda.device(pf.device):
+                _lib.check(_lib.lib().mural_op_adam_flat_state(pf.data_ptr(), gbase, mf.data_ptr(), vf.data_ptr(), pf.numel(), st.buf.data_ptr(),
+                                                               float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]),
+                                                               _lib.current_stream_ptr(pf.device)))
+        else:
+            self._flat_t += 1
+            with torch.cuda.device(pf.device):
+                _lib.check(_lib.lib().mural_op_adam_flat(pf.data_ptr(), gbase, mf.data_ptr(), vf.data_ptr(), pf.numel(), float(g["lr"]),
+                                                         float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), self._flat_t,
+                                                         _lib.current_stream_ptr(pf.device)))
         model = lay.model_ref()
         if model is not None and not model.training:      # (a step in eval mode: the kernel bumps no tensor version the folded copy watches)
             model.invalidate_folded()
@@ -309,7 +447,14 @@ class Adam(torch.optim.Adam):
         # parent's step is called without ITS wrapper so that they do not fire twice)
         if closure is None and self._flat_step():
             return None
-        self._leave_flat()
+        if self.device_state is not None:      # torch's step on the block's count and rate; the block takes the step all the same
+            self._state_to_host()
+            if self._flat is not None:
+                self._write_steps()
+                self._flat = None
+            self.device_state.tick()
+        else:
+            self._leave_flat()
         parent = torch.optim.Adam.step
         if getattr(parent, "hooked", False):
             parent = getattr(parent, "__wrapped__", parent)
@@ -329,13 +474,16 @@ class Adam(torch.optim.Adam):
 # per-batch policy (skip batches of one row, clip at 10, step the scheduler every batch, restart a learning rate that decayed
 # below min_lr).  Host logic only; the model does the device work.
 # ------------------------------------------------------------------------------------------------------------------
-def make_optimizer(config, params):
+def make_optimizer(config, params, device_state=None):
     """training.py:346-360: Adam / AdamW / AdamW2 (both amsgrad) / SGD (momentum 0.98, nesterov) by ``config['optim']``."""
     params = [p for p in params if p.requires_grad]
     lr, wd = config["learning_rate"], config["weight_decay"]
     name = config["optim"]
     if name == "Adam":
-        return Adam(params, lr=lr, weight_decay=wd)      # torch.optim.Adam; one launch per step behind the library's training step
+        # torch.optim.Adam; one launch per step behind the library's training step (device_state: tick + one launch, capturable)
+        return Adam(params, lr=lr, weight_decay=wd, device_state=device_state)
+    if device_state is not None:
+        raise ValueError(f"the device step state serves optim 'Adam' only, not {name}")
     if name in ("AdamW", "AdamW2"):
         return torch.optim.AdamW(params, lr=lr, weight_decay=wd, amsgrad=True)
     if name == "SGD":
@@ -383,3 +531,90 @@ def train_epoch(model, batches, criterion, optimizer, scheduler, config, device,
                 for g in optimizer.param_groups:
                     g["lr"] = config["restart_lr"]
     return total_loss
+
+
+def _device_epoch_refusal(model, criterion, optimizer):
+    from .model import train_step
+    from .model.model_snv import Network0, _HipSnvBase
+    core = model.model if isinstance(model, Network0) else model
+    if not isinstance(core, _HipSnvBase) or not train_step.supported(core):
+        return "the model does not train on the one-call step (an SNV model with 32 conv channels of kernel 3, or the local-only one)"
+    if not isinstance(optimizer, Adam) or optimizer.device_state is None:
+        return "the optimizer is not mural_amd.train.Adam(..., device_state=DeviceStepState(...))"
+    if not isinstance(criterion, (CrossEntropySum, torch.nn.CrossEntropyLoss)):
+        return "the criterion is not a cross-entropy loss giving one float32 device scalar"
+    return None
+
+
+def _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y):
+    loss = criterion(model((cont_x, cat_x), distal_x), y)
+    optimizer.zero_grad()
+    loss.backward()
+    clip_grad_norm_(model, 10)
+    optimizer.device_state.observe(loss, y.shape[0])
+    optimizer.step()
+
+
+def _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, distal_x, y):
+    """(the model's captured step for batches of y's rows, whether it was captured just now -- its one warm-up step then WAS the step
+    on this batch).  Captured again when what the graph baked in is gone: another optimiser / criterion / schedule, parameters that
+    left the optimiser's flat buffer, another input form."""
+    steps = model.__dict__.setdefault("_device_epoch_steps", {})
+    x = GraphedTrainStep._tensor(distal_x)
+    hit = steps.get(y.shape[0])
+    if hit is not None:
+        step, key, pbase = hit
+        flat = optimizer._flat
+        if (key == (id(optimizer), id(criterion), sched) and step.opt is optimizer and step.crit is criterion and flat is not None
+                and flat[2].data_ptr() == pbase and step.x.shape == x.shape and step.x.dtype == x.dtype):
+            return step, False
+    step = GraphedTrainStep(model, optimizer, criterion, cont_x, cat_x, distal_x, y, max_norm=10, warmup=1)
+    if optimizer._flat is None:
+        raise RuntimeError("train_epoch_device: the optimiser did not take its one-launch step on this model")
+    steps[y.shape[0]] = (step, (id(optimizer), id(criterion), sched), optimizer._flat[2].data_ptr())
+    return step, True
+
+
+def train_epoch_device(model, batches, criterion, optimizer, config, device, epoch=0, train_size=None):
+    """``train_epoch`` with the loop's state on the device (``optimizer = Adam(..., device_state=DeviceStepState(...))``): the same
+    policy -- batches of one row skipped, clipping at 10, the scheduler of ``config`` ticked every batch unless 'ROP', the restart of a
+    rate below min_lr, the rate reset to restart_lr for 'StepLR2' when epoch > 0 -- with the scheduler inside the tick kernel instead
+    of a host ``scheduler`` object, and NOTHING read back before the epoch's end:
+
+      * batches of ``config['batch_size']`` rows replay a ``GraphedTrainStep`` captured once per (model, rows) and kept on the model;
+      * batches of any other size (the carry batches of ``epoch_order``) run the same kernels eagerly, so the block sees one sequence;
+      * at the end ONE ``state.read()``: ``param_groups[..]['lr']`` is set from it (a host ``ReduceLROnPlateau`` can act between epochs),
+        the deferred input check of the last replay is raised, the block's loss sum is returned.
+
+    SNV models on the one-call training step with this module's ``Adam`` and a cross-entropy criterion; anything else raises ValueError
+    (``train_epoch`` is the loop for it)."""
+    why = _device_epoch_refusal(model, criterion, optimizer)
+    if why is not None:
+        raise ValueError(f"train_epoch_device: {why}; use train_epoch")
+    state = optimizer.device_state
+    model.train()
+    freeze_host_heap()
+    if epoch > 0 and config["lr_scheduler"] == "StepLR2":
+        for g in optimizer.param_groups:
+            g["lr"] = config["restart_lr"]
+    sched = state.set_schedule(config, train_size)
+    state.set_lr(optimizer.param_groups[0]["lr"])
+    state.reset_epoch()
+    common, graphed = int(config["batch_size"]), None
+    for y, cont_x, cat_x, distal_x in batches:
+        if y.shape[0] == 1:                       # a single row cannot feed a batch-statistics BatchNorm (training.py:415)
+            continue
+        cat_x, cont_x, distal_x, y = cat_x.to(device), cont_x.to(device), distal_x.to(device), y.to(device).long().squeeze()
+        if y.shape[0] == common:
+            graphed, fresh = _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, distal_x, y)
+            if not fresh:
+                graphed(cont_x, cat_x, distal_x, y)
+        else:
+            _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y)
+    r = state.read()
+    optimizer._flat_t = r["step"]
+    for g in optimizer.param_groups:
+        g["lr"] = r["lr"]
+    if graphed is not None:
+        graphed.finish()
+    return r["loss_sum"]
