@@ -1524,7 +1524,9 @@ extern "C" int mural_op_head_bwd(const float* loc, const float* mid, const float
 // The criterion of the training loops (training.py: nn.CrossEntropyLoss(reduction='sum') on the model output) in two launches instead of
 // torch's four-to-six: loss = -sum_i (x[i][y_i] - logsumexp(x[i])), prob = softmax(x) kept for the backward, dx = g (prob - onehot(y)).
 // ONE workgroup: the sum is taken in a fixed order (double accumulators), the loss is reproducible.  A label outside [0, nc) makes the
-// loss NaN (torch raises a device assert there).
+// loss NaN (torch raises a device assert there).  A row's term is (m - x_t) + log(sum exp(x - m)) with the difference taken in double (exact):
+// formed as (m + log(sum)) - x_t in float it carried a rounding of the size of m, which a row whose label is at or next to the maximum
+// does not have in torch (log_softmax subtracts the maximum first) -- 6e-5 on a term of 1.39 for logits near 1500.
 // NC > 0: the class count at compile time -- a thread's rows (B / 1024 of them, four at a time) are requested before the first one is
 // used, a row's logits stay in registers and its probabilities are stored once (the run-time form reads a logit three times and makes
 // one dependent round trip to memory per row: 17 us for 4096 x 4 logits against 6).  Same operations in the same order per row and
@@ -1560,7 +1562,7 @@ __global__ __launch_bounds__(1024) void ce_sum_fwd_kernel(const float* __restric
           e[k] = expf(r[u][k] - m);
           s += e[k];
         }
-        const float lse = m + logf(s);
+        const float ls = logf(s);
         const float inv = 1.f / s;
         float rt = 0.f;
 #pragma unroll
@@ -1568,7 +1570,7 @@ __global__ __launch_bounds__(1024) void ce_sum_fwd_kernel(const float* __restric
           prob[i * NC + k] = e[k] * inv;
           rt = t[u] == k ? r[u][k] : rt;
         }
-        acc += (t[u] >= 0 && t[u] < NC) ? (double)(lse - rt) : __longlong_as_double(0x7ff8000000000000LL);      // (NaN by its bits: this file is built with -fno-honor-nans)
+        acc += (t[u] >= 0 && t[u] < NC) ? ((double)m - (double)rt) + (double)ls : __longlong_as_double(0x7ff8000000000000LL);      // (NaN by its bits: this file is built with -fno-honor-nans)
       }
     }
   } else {
@@ -1583,11 +1585,11 @@ __global__ __launch_bounds__(1024) void ce_sum_fwd_kernel(const float* __restric
         prob[i * nc + k] = e;
         s += e;
       }
-      const float lse = m + logf(s);
+      const float ls = logf(s);
       const float inv = 1.f / s;
       for (int k = 0; k < nc; ++k) prob[i * nc + k] *= inv;
       const int64_t t = y[i];
-      acc += (t >= 0 && t < nc) ? (double)(lse - r[t]) : __longlong_as_double(0x7ff8000000000000LL);
+      acc += (t >= 0 && t < nc) ? ((double)m - (double)r[t]) + (double)ls : __longlong_as_double(0x7ff8000000000000LL);
     }
   }
 #pragma unroll

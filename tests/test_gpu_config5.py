@@ -148,6 +148,67 @@ def test_device_poisson_and_scaling_match_reference_tables(tmp_path):
     assert calibrate_device(torch.zeros(0, 4).cuda(), poisson=True).shape == (0, 4)
 
 
+def test_device_calibration_beyond_one_round_of_its_grid():
+    """4096 x 256 + 1 rows: every thread of the capped grid (csrc/calibrate.hip: 4096 workgroups of 256 rows) takes a second row or
+    not.  The whole chain and Poisson + scaling alone against the host functions in float64, with the bars of the tests above."""
+    from mural_amd.calibration import apply_scaling, calibrate_device, dirichlet_calibrate
+    from mural_amd.data.ingest import poisson_calibrate
+    n, k, factor = 4096 * 256 + 1, 4, 0.0123
+    p = torch.softmax(torch.randn(n, k, generator=torch.Generator().manual_seed(41)), dim=1)
+    w = np.hstack([np.eye(k), np.zeros((k, 1))]) + 0.3 * np.random.default_rng(41).normal(size=(k, k + 1))      # a fitted map is near the identity
+    pd = p.cuda()
+    want = apply_scaling(poisson_calibrate(dirichlet_calibrate(p.numpy(), w)), factor)
+    got = calibrate_device(pd, dirichlet_weights=w, poisson=True, scale_factor=factor, input_is_prob=True).cpu().numpy()
+    assert got.shape == (n, k) and np.abs(got - want).max() <= 1e-6 * max(1.0, np.abs(want).max())
+    want = apply_scaling(poisson_calibrate(p.numpy().astype(np.float64)), factor)
+    got = calibrate_device(pd, poisson=True, scale_factor=factor, input_is_prob=True).cpu().numpy()
+    np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-15)
+
+
+@pytest.mark.parametrize("k", [5, 16])
+def test_device_calibration_run_time_class_loop_float32_output_and_wide_logits(k):
+    """1000 rows of 5 and of 16 classes (the run-time class loop: above the 8 the templates reach): the chain from probabilities with
+    the bar of the tests above; dtype=float32 is the float64 result rounded once; then from model output whose logits span +-80 (the
+    softmax inside the kernel: whole rows underflow to one class), where the measure is torch's float32 softmax on the CPU followed by
+    the host chain in float64, the target the same chain from the float64 softmax, and the bar ``_loose``'s (tests/_parity.py).  The
+    clip in front of the logarithm is float32's in both (the input's dtype: calibration.dirichlet_calibrate)."""
+    from mural_amd.calibration import apply_scaling, calibrate_device, dirichlet_calibrate
+    from mural_amd.data.ingest import poisson_calibrate
+    from tests._parity import _Stats, _loose
+    tg = torch.Generator().manual_seed(50 + k)
+    rng = np.random.default_rng(50 + k)
+    n, factor = 1000, 0.0123
+    p = torch.softmax(torch.randn(n, k, generator=tg), dim=1)
+    w = rng.normal(size=(k, k + 1))
+    want = poisson_calibrate(dirichlet_calibrate(p.numpy(), w))
+    got = calibrate_device(p.cuda(), dirichlet_weights=w, poisson=True, input_is_prob=True)
+    assert np.abs(got.cpu().numpy() - want).max() <= 1e-6 * max(1.0, np.abs(want).max())
+    got32 = calibrate_device(p.cuda(), dirichlet_weights=w, poisson=True, input_is_prob=True, dtype=torch.float32)
+    assert got32.dtype == torch.float32 and torch.equal(got32, got.float())
+
+    stats = _Stats(f"calib k{k}", tag="calibrate")
+    x = 160.0 * torch.rand(n, k, generator=tg) - 80.0
+    x[0], x[1] = 80.0, -80.0
+    x[2, 0], x[2, 1:] = 80.0, -80.0
+    x[3, 0], x[3, 1:] = -80.0, 80.0
+    x[4:300] *= 0.05                                   # rows where several classes keep a share
+    tiny = float(np.finfo(np.float32).tiny)
+    p64 = torch.softmax(x.double(), 1).clamp(tiny, 1.0).numpy()      # (float64 input to the host chain, float32's clip)
+    p32 = torch.softmax(x, 1).numpy()
+    mild = np.hstack([np.eye(k), np.zeros((k, 1))]) + 0.02 * w       # keeps class 0 away from 1: Poisson's 0 / 0 is not under test here
+    chains = [("softmax", lambda q: np.asarray(q, np.float64), dict()),
+              ("dirichlet", lambda q: dirichlet_calibrate(q, w), dict(dirichlet_weights=w)),
+              ("chain", lambda q: apply_scaling(poisson_calibrate(dirichlet_calibrate(q, 0.05 * mild)), factor),
+               dict(dirichlet_weights=0.05 * mild, poisson=True, scale_factor=factor))]
+    for name, host, kw in chains:
+        want64, ref32 = torch.from_numpy(host(p64)), torch.from_numpy(host(p32))
+        assert bool(torch.isfinite(want64).all()) and bool(torch.isfinite(ref32).all()), name
+        got = calibrate_device(x.cuda(), **kw)
+        _loose(got, want64, ref32, name, f"k{k} n{n} logits +-80", stats)
+        _loose(calibrate_device(x.cuda(), dtype=torch.float32, **kw), want64, ref32, name + " (float32)", f"k{k} n{n} logits +-80", stats)
+    stats.show()
+
+
 def test_sharded_driver_with_device_calibration_writes_the_same_table(tmp_path):
     """HipShardForward with the calibration fused behind the head + a plain sink == host-side calibration in the sink."""
     from mural_amd.predict import HipShardForward, TsvSink, predict_bed_sharded

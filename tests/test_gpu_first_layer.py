@@ -47,6 +47,8 @@ _G = {
     "batch4097": [(4097, 31, 0, 31, 32, 3, 3, 1)],
     "generic": [(37, 200, 0, 200, 32, 16, 16, 8), (37, 200, 0, 200, 32, 20, 20, 10)] +
                [(37, 97, 0, 97, Cn, k, k, k // 2) for Cn in (16, 24, 64) for k in (15, 3)],
+    # 125 x 64 x 33 = 264 000 pooled outputs: beyond one round of the generic backward's scatter launch (1024 workgroups of 256)
+    "generic_batch125": [(125, 97, 0, 97, 64, 3, 3, 1)],
 }
 GEOMS = [g for grp in _G.values() for g in grp]
 KINDS = ("acgt", "iupac", "ties")

@@ -188,7 +188,7 @@ def test_embedding_forward_and_backward_against_torch_float64(rows):
     E = torch.randn((rows, 5), generator=rng)
     Ed = E.cuda()
     for cols in (1, 9, 19):
-        for B in (1, 40, 300):
+        for B in (1, 40, 300, 700):          # 700 x 19 x 5 = 66 500 gradients: beyond one round of the staged kernel's 256 workgroups of 256
             for dist in ("uniform", "equal", "last row"):
                 case = dict(rows=rows, cols=cols, B=B, indices=dist)
                 cat = torch.randint(0, rows, (B, cols), generator=rng)
@@ -225,7 +225,9 @@ BN_CASES = [(2, 1, 1, 0, "plain", 0), (2, 75, 1, 1, "plain", 0), (2, 5, 1, 0, "o
             (37, 5, 4, 0, "offset", 1), (2, 150, 4, 1, "plain", 0), (2, 150, 4, 1, "plain", 1), (3, 32, 8, 1, "plain", 0),
             (3, 32, 8, 1, "plain", 1), (2, 75, 8, 0, "offset", 0), (2, 75, 8, 0, "offset", 1), (37, 1, 8, 0, "plain", 0),
             (37, 32, 250, 0, "offset", 0), (3, 150, 250, 1, "plain", 0), (2, 32, 251, 1, "offset", 0), (37, 5, 251, 0, "plain", 0),
-            (37, 5, 251, 0, "plain", 1), (3, 75, 251, 1, "plain", 0)]
+            (37, 5, 251, 0, "plain", 1), (3, 75, 251, 1, "plain", 0),
+            # 527 250 elements: beyond one round of bn_backward's apply launch (capped at 2048 workgroups of 256 elements)
+            (37, 57, 250, 1, "plain", 0)]
 
 
 def _bn_reference(x, gamma, beta, rm, rv, g, relu, dtype):
