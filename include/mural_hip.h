@@ -449,6 +449,25 @@ int mural_op_train_state_tick(MuralTrainState* state, const float* loss, int64_t
 int mural_op_adam_flat_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const MuralTrainState* state,
                              double beta1, double beta2, double eps, double weight_decay, void* stream);
 
+/* torch.optim.AdamW(amsgrad=True).step() (the reference's 'AdamW' / 'AdamW2', training.py:351-356; maximize off) over flat float32 buffers
+ * of ONE slot layout -- parameters, gradients, exp_avg, exp_avg_sq, max_exp_avg_sq; zero padding stays zero -- as one elementwise launch:
+ * p *= 1 - lr weight_decay (formed in double, rounded once); m += (1 - beta1)(g - m); v = beta2 v + (1 - beta2) g^2; vmax = max(vmax, v);
+ * p -= step_size m / (sqrt(vmax) / bc2_sqrt + eps), step_size and bc2_sqrt as in mural_op_adam_flat.  n, alignment, step: as there.   */
+int mural_op_adamw_amsgrad_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                                double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream);
+/* ... with lr, step_size and bc2_sqrt read from *state as a tick left them (lr: the rate the tick's scheduler left for the next update).
+ * Same update, vector width, grid and argument checks.  Reads the block, never writes it.                                              */
+int mural_op_adamw_amsgrad_flat_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                                      const MuralTrainState* state, double beta1, double beta2, double eps, double weight_decay,
+                                      void* stream);
+/* torch.optim.SGD(momentum, nesterov=True, dampening=0).step() with L2 weight decay (the reference's 'SGD', training.py:357-360) over flat
+ * float32 buffers of ONE slot layout (parameters, gradients, momentum buffer), one elementwise launch: g' = g + weight_decay p;
+ * buf = momentum buf + g'; p -= lr (g' + momentum buf).  A zero buf reproduces torch's first step (buf = g').                         */
+int mural_op_sgd_flat(float* param, const float* grad, float* buf, int64_t n, double lr, double momentum, double weight_decay, void* stream);
+/* ... with lr read from *state.  Reads the block, never writes it.                                                                    */
+int mural_op_sgd_flat_state(float* param, const float* grad, float* buf, int64_t n, const MuralTrainState* state, double momentum,
+                            double weight_decay, void* stream);
+
 /* Long windows (distal_radius from ~15000 up to the first-stage kernel's LDS limit) whose second conv stage fits no fused kernel: the
  * handle is FRONT-ONLY (mural_snv_tap_layout()[10] == 1; the forward entries above refuse it) and this entry runs what still is fused --
  * window decode + first layer + pool (model_snv.py:473-476 of the large tower) and its first ResBlock stage on halo'd segments of the

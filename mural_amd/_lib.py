@@ -190,6 +190,10 @@ PROTOTYPES = {
     "mural_op_adam_flat": (C.c_int, [VP, VP, VP, VP, I64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I64, VP]),
     "mural_op_train_state_tick": (C.c_int, [VP, VP, I64, C.c_double, C.c_double, I64, C.c_double, C.c_double, C.c_double, VP]),
     "mural_op_adam_flat_state": (C.c_int, [VP, VP, VP, VP, I64, VP, C.c_double, C.c_double, C.c_double, C.c_double, VP]),
+    "mural_op_adamw_amsgrad_flat": (C.c_int, [VP, VP, VP, VP, VP, I64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I64, VP]),
+    "mural_op_adamw_amsgrad_flat_state": (C.c_int, [VP, VP, VP, VP, VP, I64, VP, C.c_double, C.c_double, C.c_double, C.c_double, VP]),
+    "mural_op_sgd_flat": (C.c_int, [VP, VP, VP, I64, C.c_double, C.c_double, C.c_double, VP]),
+    "mural_op_sgd_flat_state": (C.c_int, [VP, VP, VP, I64, VP, C.c_double, C.c_double, VP]),
     "mural_last_error": (C.c_char_p, []),
     "mural_abi_version": (C.c_int, []),
     "mural_encode_kmer": (C.c_int, [C.POINTER(MuralGenome), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,

@@ -72,4 +72,57 @@ __device__ __forceinline__ void adam_flat_elements(float* __restrict__ p, const 
   }
 }
 
+// The flat AdamW (amsgrad) and SGD (momentum, nesterov) steps, built like the Adam step above: one argument check and one element loop each
+// behind two entries -- mural_op_adamw_amsgrad_flat / mural_op_sgd_flat (train_ops.hip: lr and step from the host) and their _state twins
+// (train_state.hip: read from a MuralTrainState block) -- on adam_flat_grid.
+int adamw_amsgrad_flat_check(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq, const float* max_exp_avg_sq,
+                             int64_t n, double beta1, double beta2, double eps, double weight_decay);
+int sgd_flat_check(const float* param, const float* grad, const float* buf, int64_t n, double momentum, double weight_decay);
+// torch.optim.AdamW(amsgrad=True)'s single-tensor update, in float; decay = (float)(1 - lr weight_decay), formed in double:
+//   p = p decay;  m = m + (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g;  vmax = max(vmax, v);
+//   p = p - step_size m / (sqrt(vmax) / bc2_sqrt + eps)       with step_size, bc2_sqrt as in adam_flat_elements
+__device__ __forceinline__ void adamw_amsgrad_flat_elements(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, float* __restrict__ vmax, int64_t n4, float decay, float w1,
+                                                            float beta2, float w2, float step_size, float bc2_sqrt, float eps) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    float4 xv = reinterpret_cast<float4*>(vmax)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float* pp = &pv.x; float* mp = &mv.x; float* vp = &vv.x; float* xp = &xv.x;
+    const float* gp = &gv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gk = gp[k];
+      mp[k] = mp[k] + (gk - mp[k]) * w1;
+      vp[k] = beta2 * vp[k] + w2 * gk * gk;
+      xp[k] = fmaxf(xp[k], vp[k]);
+      const float denom = sqrtf(xp[k]) / bc2_sqrt + eps;
+      pp[k] = pp[k] * decay - step_size * mp[k] / denom;
+    }
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(vmax)[i] = xv;
+  }
+}
+// torch.optim.SGD(momentum, nesterov=True, dampening=0)'s update with L2 weight decay, in float (a zero buf gives torch's first step):
+//   g' = g + weight_decay p;  buf = momentum buf + g';  p = p - lr (g' + momentum buf)
+__device__ __forceinline__ void sgd_flat_elements(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n4,
+                                                  float lr, float momentum, float wd) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], bv = reinterpret_cast<float4*>(buf)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float* pp = &pv.x; float* bp = &bv.x;
+    const float* gp = &gv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gk = gp[k] + wd * pp[k];
+      bp[k] = momentum * bp[k] + gk;
+      pp[k] = pp[k] - lr * (gk + momentum * bp[k]);
+    }
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(buf)[i] = bv;
+  }
+}
+
 }  // namespace mural

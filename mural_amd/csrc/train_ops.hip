@@ -1658,6 +1658,59 @@ extern "C" int mural_op_adam_flat(float* param, const float* grad, float* exp_av
   CHECK_LAUNCH();
 }
 
+// torch.optim.AdamW(amsgrad=True).step() and torch.optim.SGD(momentum, nesterov=True).step() (training.py:351-360; maximize off) over flat
+// buffers of the same slot layout, one elementwise launch each on the Adam step's grid (element loops: train_ops.h; the entries that read
+// lr and the bias corrections from a device block: train_state.hip).  Zero padding stays zero in every buffer: 0 * decay - s * 0 / eps' = 0.
+__global__ __launch_bounds__(256) void adamw_amsgrad_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                 float* __restrict__ v, float* __restrict__ vmax, int64_t n4, float decay,
+                                                                 float w1, float beta2, float w2, float step_size, float bc2_sqrt, float eps) {
+  adamw_amsgrad_flat_elements(p, g, m, v, vmax, n4, decay, w1, beta2, w2, step_size, bc2_sqrt, eps);
+}
+int mural::adamw_amsgrad_flat_check(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                                    const float* max_exp_avg_sq, int64_t n, double beta1, double beta2, double eps, double weight_decay) {
+  MURAL_REQUIRE(param && grad && exp_avg && exp_avg_sq && max_exp_avg_sq && n >= 0 && (n & 3) == 0,
+                "adamw_amsgrad_flat: NULL buffer or a length that is no multiple of 4");
+  MURAL_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0,
+                "adamw_amsgrad_flat: step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0, weight_decay >= 0");
+  MURAL_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+                  reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(max_exp_avg_sq)) & 15) == 0,
+                "adamw_amsgrad_flat: buffers must be 16-byte aligned");
+  return MURAL_OK;
+}
+extern "C" int mural_op_adamw_amsgrad_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                                           double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream) {
+  if (const int rc = adamw_amsgrad_flat_check(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, beta1, beta2, eps, weight_decay)) return rc;
+  MURAL_REQUIRE(step >= 1 && lr >= 0, "adamw_amsgrad_flat: step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0, weight_decay >= 0");
+  if (n == 0) return MURAL_OK;
+  const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+  // (fma: one rounding in double, the same on the host and in the kernel that forms the factor from the block's rate)
+  hipLaunchKernelGGL(adamw_amsgrad_flat_kernel, dim3(adam_flat_grid(n / 4)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq,
+                     n / 4, (float)std::fma(-lr, weight_decay, 1.0), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1),
+                     (float)std::sqrt(bc2), (float)eps);
+  CHECK_LAUNCH();
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n4,
+                                                       float lr, float momentum, float wd) {
+  sgd_flat_elements(p, g, buf, n4, lr, momentum, wd);
+}
+int mural::sgd_flat_check(const float* param, const float* grad, const float* buf, int64_t n, double momentum, double weight_decay) {
+  MURAL_REQUIRE(param && grad && buf && n >= 0 && (n & 3) == 0, "sgd_flat: NULL buffer or a length that is no multiple of 4");
+  MURAL_REQUIRE(momentum >= 0 && weight_decay >= 0, "sgd_flat: lr >= 0, momentum >= 0, weight_decay >= 0");
+  MURAL_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(buf)) & 15) == 0,
+                "sgd_flat: buffers must be 16-byte aligned");
+  return MURAL_OK;
+}
+extern "C" int mural_op_sgd_flat(float* param, const float* grad, float* buf, int64_t n, double lr, double momentum, double weight_decay,
+                                 void* stream) {
+  if (const int rc = sgd_flat_check(param, grad, buf, n, momentum, weight_decay)) return rc;
+  MURAL_REQUIRE(lr >= 0, "sgd_flat: lr >= 0, momentum >= 0, weight_decay >= 0");
+  if (n == 0) return MURAL_OK;
+  hipLaunchKernelGGL(sgd_flat_kernel, dim3(adam_flat_grid(n / 4)), dim3(256), 0, STREAM, param, grad, buf, n / 4, (float)lr, (float)momentum,
+                     (float)weight_decay);
+  CHECK_LAUNCH();
+}
+
 // torch.nn.utils.clip_grad_norm_(params, max_norm) (training.py:430) over ONE flat gradient buffer (zero between the parameters' slots) in
 // two launches: sums of squares per workgroup (fixed order inside a workgroup and over the workgroups: reproducible), then every workgroup
 // adds the CLIP_WGS partial sums in the same order, forms coef = min(max_norm / (norm + 1e-6), 1) -- torch's rule -- and scales its share;

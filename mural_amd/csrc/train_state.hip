@@ -47,6 +47,20 @@ __global__ __launch_bounds__(256) void adam_flat_state_kernel(float* __restrict_
   adam_flat_elements(p, g, m, v, n4, w1, beta2, w2, st->step_size, st->bc2_sqrt, eps, wd);
 }
 
+// (the block's lr AFTER a tick is the rate the tick's scheduler left for the next update: the rate of this update wherever the scheduler
+// did not move it at this tick.  mural_amd/train.py orders its launches accordingly.)
+__global__ __launch_bounds__(256) void adamw_amsgrad_flat_state_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                       float* __restrict__ v, float* __restrict__ vmax, int64_t n4,
+                                                                       const MuralTrainState* __restrict__ st, double wd, float w1, float beta2,
+                                                                       float w2, float eps) {
+  adamw_amsgrad_flat_elements(p, g, m, v, vmax, n4, (float)fma(-st->lr, wd, 1.0), w1, beta2, w2, st->step_size, st->bc2_sqrt, eps);
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_state_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                             int64_t n4, const MuralTrainState* __restrict__ st, float momentum, float wd) {
+  sgd_flat_elements(p, g, buf, n4, (float)st->lr, momentum, wd);
+}
+
 }  // namespace
 }  // namespace mural
 
@@ -74,5 +88,27 @@ extern "C" int mural_op_adam_flat_state(float* param, const float* grad, float* 
   if (n == 0) return MURAL_OK;
   hipLaunchKernelGGL(adam_flat_state_kernel, dim3(adam_flat_grid(n / 4)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq, n / 4, state,
                      (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay);
+  CHECK_LAUNCH();
+}
+
+extern "C" int mural_op_adamw_amsgrad_flat_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                                                 int64_t n, const MuralTrainState* state, double beta1, double beta2, double eps,
+                                                 double weight_decay, void* stream) {
+  if (const int rc = adamw_amsgrad_flat_check(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, beta1, beta2, eps, weight_decay)) return rc;
+  MURAL_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 7) == 0,
+                "adamw_amsgrad_flat_state: the state block must be an 8-byte aligned device pointer");
+  if (n == 0) return MURAL_OK;
+  hipLaunchKernelGGL(adamw_amsgrad_flat_state_kernel, dim3(adam_flat_grid(n / 4)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq,
+                     max_exp_avg_sq, n / 4, state, weight_decay, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
+  CHECK_LAUNCH();
+}
+
+extern "C" int mural_op_sgd_flat_state(float* param, const float* grad, float* buf, int64_t n, const MuralTrainState* state, double momentum,
+                                       double weight_decay, void* stream) {
+  if (const int rc = sgd_flat_check(param, grad, buf, n, momentum, weight_decay)) return rc;
+  MURAL_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 7) == 0, "sgd_flat_state: the state block must be an 8-byte aligned device pointer");
+  if (n == 0) return MURAL_OK;
+  hipLaunchKernelGGL(sgd_flat_state_kernel, dim3(adam_flat_grid(n / 4)), dim3(256), 0, STREAM, param, grad, buf, n / 4, state, (float)momentum,
+                     (float)weight_decay);
   CHECK_LAUNCH();
 }

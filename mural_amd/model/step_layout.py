@@ -6,9 +6,12 @@
 * ``FlatGradLayout``: which tensor sits in which pointer slot, and where each parameter's gradient lives in ONE flat float32 buffer.
   ``mural_amd.train.clip_grad_norm_`` and ``mural_amd.train.Adam`` read its attributes.
 * The lines the two ``ModelStep`` autograd nodes have in common (workspace and output allocation, BatchNorm counters, the
-  one-backward rule).
+  one-backward rule) and their direct-gradient mode (train_step.py's docstring): when it is safe (``want_direct``), which buffer a
+  backward writes (``backward_flat``) and how its slots become ``p.grad`` (``hand_out``).
 """
 import ctypes as C
+import os
+import sys
 import weakref
 
 import numpy as np
@@ -104,9 +107,10 @@ def fill_indel(model, ptr):
 _LAYOUT_OF = {}      # id(first parameter) -> (weak reference to that parameter, weak reference to the layout): mural_amd.train.Adam finds it
 
 
-def layout_of_params(params):
+def layout_of_params(params, device_state=False):
     """The REGISTERED layout whose parameter list is exactly `params` (any order; empty parameters have no slot and do not count),
-    or None."""
+    or None.  A layout registered for the device loop only (``register="device_state"``: UNet_Small) is returned to an optimiser that
+    carries a device step state and to nobody else: an optimiser built without one keeps torch's own step on such a model."""
     if not params or not _LAYOUT_OF:
         return None
     params = [p for p in params if p.numel()]
@@ -114,7 +118,8 @@ def layout_of_params(params):
         hit = _LAYOUT_OF.get(id(p))
         if hit is not None and hit[0]() is p:
             lay = hit[1]()
-            if lay is not None and len(lay.plist) == len(params) and {id(q) for q in lay.plist} == {id(q) for q in params}:
+            if (lay is not None and (lay.register is True or device_state) and len(lay.plist) == len(params)
+                    and {id(q) for q in lay.plist} == {id(q) for q in params}):
                 return lay
     return None
 
@@ -127,7 +132,8 @@ class FlatGradLayout:
     """Which tensor sits in which pointer slot of `struct_type` (a flat run of pointers), found by running `fill(model, ptr)` once
     with slot tokens, and the offset of each parameter's gradient in one flat float32 buffer.
 
-    register: mural_amd.train.Adam finds the layout (layout_of_params) and takes its one-launch step.
+    register: True -- mural_amd.train's optimisers find the layout (layout_of_params) and take their one-launch step;
+    "device_state" -- only those built with a device step state do (the device loop), the others keep torch's step.
     check_identity: `cached` rebuilds the layout when a parameter / buffer object of the model was replaced.
     twice: a BatchNorm counter that one forward bumps a second time."""
 
@@ -147,6 +153,7 @@ class FlatGradLayout:
         self.plist = [p for p in self.params_all if p.numel()]
         self.model_ref = weakref.ref(model)
         self.identity = _tensors_of(model) if check_identity else None
+        self.register = register
         if register and self.plist:
             for k in [k for k, (r, _) in _LAYOUT_OF.items() if r() is None]:      # (entries of models that are gone)
                 del _LAYOUT_OF[k]
@@ -245,3 +252,73 @@ def saved_workspace(ctx, name):
 def node_grads(n_inputs, grads):
     """The return tuple of a ModelStep backward: nothing for the `n_inputs` non-parameter inputs, then the parameters' gradients."""
     return (None,) * n_inputs + tuple(grads)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# direct-gradient mode of the two ModelStep nodes (model/train_step.py: module docstring)
+# ---------------------------------------------------------------------------------------------------------------
+def _holder_counts(lay):
+    """(references to the storage of the gradient buffer, Python + C++ references of every view into it)."""
+    storage = torch._C._storage_Use_Count(lay.own_flat.untyped_storage()._cdata)
+    return storage, [(sys.getrefcount(v), v._use_count()) for v in lay.own_views]
+
+
+def _views_are_ours(lay):
+    """Nobody but the layout holds last step's gradient views or anything derived from them (counts as at their creation)."""
+    return _holder_counts(lay) == lay.own_base
+
+
+def _direct_is_safe(params):
+    """Direct-gradient mode only where nothing but ``p.grad`` observes the gradients, and every parameter takes one."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        return False
+    for p in params:
+        if not p.requires_grad or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
+            return False
+    return True
+
+
+def want_direct(model, params):
+    """The node sets every ``.grad`` itself (one parameter anchors it in the autograd graph) unless the caller asked for the autograd
+    route (``model._autograd_params`` / MURAL_TRAIN_AUTOGRAD_PARAMS) or a direct gradient could go unseen."""
+    return (not getattr(model, "_autograd_params", False) and not os.environ.get("MURAL_TRAIN_AUTOGRAD_PARAMS")
+            and _direct_is_safe(params))
+
+
+def backward_flat(lay, dev, ctx_direct):
+    """(the flat buffer this backward writes, whether its slots ARE the gradients): in direct mode with no ``.grad`` present, the
+    buffer that lives with the layout -- same addresses every step -- else a fresh one (an existing ``.grad`` is accumulated into)."""
+    direct = ctx_direct and all(p.grad is None for p in lay.plist)
+    if direct:
+        # Last step's gradients that somebody still holds (kept across zero_grad(set_to_none=True)) are not rewritten in place.
+        # Three holders are looked for, each against the count recorded when the views were made: Python references to a view
+        # object, C++ references to its TensorImpl, and -- what a derived tensor (`g.view(-1)`, `g[0]`, `g.detach()`) or any
+        # other holder of the memory adds -- references to the buffer's storage.
+        if lay.own_views is not None and not _views_are_ours(lay):
+            lay.own_flat = lay.own_views = None
+        if lay.own_flat is None or lay.own_flat.device != dev:
+            lay.own_flat = lay.zero_flat(dev)
+            lay.own_views = lay.grad_views(lay.own_flat)
+            lay.own_base = _holder_counts(lay)
+        flat = lay.own_flat      # every slot is rewritten by the backward call; the padding between the slots stays zero
+    else:
+        flat = lay.zero_flat(dev)
+    lay.last_flat = flat
+    return flat, direct
+
+
+def hand_out(lay, flat, ctx_direct, direct, n_inputs, params):
+    """The return tuple of a ModelStep backward that wrote `flat`: in direct mode the node sets / accumulates ``p.grad`` itself and
+    hands autograd nothing; else the gradients of `params` as views of `flat`."""
+    if ctx_direct:
+        if direct:
+            for p, v in zip(lay.plist, lay.own_views):
+                p.grad = v
+        else:
+            for p, g in zip(lay.plist, lay.grad_views(flat)):
+                if p.grad is None:
+                    p.grad = g
+                else:
+                    p.grad.add_(g)
+        return node_grads(n_inputs, (None,) * len(params))
+    return node_grads(n_inputs, lay.grads_for(params, flat))

@@ -20,9 +20,6 @@ on parameters other than the anchor fails with autograd's own "not used in the g
 are handed out again by the next one only while nobody else still holds them (reference count of the views): a caller who keeps
 last step's gradients for accumulation or logging gets a fresh buffer instead of having them rewritten in place.
 """
-import os
-import sys
-
 import ctypes as C
 
 import numpy as np
@@ -87,22 +84,7 @@ class ModelStep(torch.autograd.Function):
         cat_x, drops, seeds, seed_dev, B = ctx.args
         lay = _layout(model)
         dev = ws.device
-        direct = ctx.direct and all(p.grad is None for p in lay.plist)     # (an existing .grad is accumulated into: a fresh buffer then)
-        if direct:
-            # Last step's gradients that somebody still holds (kept across zero_grad(set_to_none=True)) are not rewritten in place.
-            # Three holders are looked for, each against the count recorded when the views were made: Python references to a view
-            # object, C++ references to its TensorImpl, and -- what a derived tensor (`g.view(-1)`, `g[0]`, `g.detach()`) or any
-            # other holder of the memory adds -- references to the buffer's storage.
-            if lay.own_views is not None and not _views_are_ours(lay):
-                lay.own_flat = lay.own_views = None
-            if lay.own_flat is None or lay.own_flat.device != dev:
-                lay.own_flat = lay.zero_flat(dev)
-                lay.own_views = lay.grad_views(lay.own_flat)
-                lay.own_base = _holder_counts(lay)
-            flat = lay.own_flat      # every slot is rewritten by the call below; the padding between the slots stays zero
-        else:
-            flat = lay.zero_flat(dev)
-        lay.last_flat = flat
+        flat, direct = step_layout.backward_flat(lay, dev, ctx.direct)
         ps, gs = lay.params_struct(), lay.grads_struct(flat.data_ptr())
         dout = dout.contiguous()
         _lib.check(_lib.lib().mural_snv_train_backward(C.byref(shape), C.byref(ps), C.byref(gs), None if cat_x is None else cat_x.data_ptr(),
@@ -110,39 +92,7 @@ class ModelStep(torch.autograd.Function):
                                                        None if seed_dev is None else seed_dev.data_ptr(), ws.data_ptr(), ws.numel(),
                                                        _lib.current_stream_ptr(dev)))
         ctx.ws = None
-        if ctx.direct:
-            if direct:
-                for p, v in zip(lay.plist, lay.own_views):
-                    p.grad = v
-            else:
-                for p, g in zip(lay.plist, lay.grad_views(flat)):
-                    if p.grad is None:
-                        p.grad = g
-                    else:
-                        p.grad.add_(g)
-            return step_layout.node_grads(8, (None,) * len(ctx.params))
-        return step_layout.node_grads(8, lay.grads_for(ctx.params, flat))
-
-
-def _holder_counts(lay):
-    """(references to the storage of the gradient buffer, Python + C++ references of every view into it)."""
-    storage = torch._C._storage_Use_Count(lay.own_flat.untyped_storage()._cdata)
-    return storage, [(sys.getrefcount(v), v._use_count()) for v in lay.own_views]
-
-
-def _views_are_ours(lay):
-    """Nobody but the layout holds last step's gradient views or anything derived from them (counts as at their creation)."""
-    return _holder_counts(lay) == lay.own_base
-
-
-def _direct_is_safe(params):
-    """Direct-gradient mode only where nothing but ``p.grad`` observes the gradients (module docstring)."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        return False
-    for p in params:
-        if not p.requires_grad or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
-            return False
-    return True
+        return step_layout.hand_out(lay, flat, ctx.direct, direct, 8, ctx.params)
 
 
 def run(model, cat_x, distal_x):
@@ -163,8 +113,7 @@ def run(model, cat_x, distal_x):
             seeds[i] = int(torch.randint(0, 2 ** 62, (1,)).item())
     params = _layout(model).params_all
     # direct-gradient mode (module docstring): one parameter anchors the node in the autograd graph, the node sets every .grad itself
-    direct = (not getattr(model, "_autograd_params", False) and not os.environ.get("MURAL_TRAIN_AUTOGRAD_PARAMS")
-              and _direct_is_safe(params))
+    direct = step_layout.want_direct(model, params)
     try:
         if direct:
             anchor = next(p for p in params if p.numel())

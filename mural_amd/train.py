@@ -7,7 +7,7 @@ captures one step into a HIP graph (``torch.cuda.CUDAGraph``) and replays it: th
 Differences from a plain loop, all of them the usual graph-capture contract:
   * batch shapes are fixed at capture; inputs are copied into static tensors before every replay;
   * the optimizer must be capturable and is stepped inside the graph: ``torch.optim.Adam(..., capturable=True)`` (torch's multi-tensor
-    sequence), or ``mural_amd.train.Adam(..., device_state=DeviceStepState(...))`` -- the one-launch step with its step count, bias
+    sequence), or ``mural_amd.train.Adam`` / ``AdamW`` / ``SGD(..., device_state=DeviceStepState(...))`` -- the one-launch step with its step count, bias
     corrections and scheduled learning rate in a device block that a tick kernel advances inside the graph (csrc/train_state.hip);
   * dropout masks: the host-drawn seeds are baked into the graph, a device-resident counter advanced inside the graph is
     added to them, so every replay draws new masks (``train_ops.set_device_seed``);
@@ -310,35 +310,27 @@ class DeviceStepState:
                                                             _lib.current_stream_ptr(self.buf.device)))
 
 
-class Adam(torch.optim.Adam):
-    """``torch.optim.Adam`` (the reference's default optimiser, training.py:346-350, stepped at :432) with a ONE-launch step for a model
-    whose training step runs in the library (model/train_step.py): there every gradient is a view of one flat buffer, so the
-    parameters and the two moment buffers are laid out the same way -- ``p.data`` becomes a view of one flat buffer at the first step,
-    ``state[p]['exp_avg']`` / ``['exp_avg_sq']`` are views as well -- and the update is one elementwise kernel
-    (``mural_op_adam_flat``: torch's fused update rule, bias corrections from the host) instead of torch's multi-tensor sequence (a
-    step-counter foreach + three launches over ~150 tensor quadruples, 40 us at the end of every step with nothing beside them).
+class _FlatStep:
+    """What ``Adam``, ``AdamW`` and ``SGD`` below share: the flat layout of the parameters and of the optimiser's state tensors, the
+    checks that decide whether the one launch covers a step, and the fall-through to the torch class's own step on the same state.
 
-    Same constructor as ``torch.optim.Adam``.  Everything the one launch does not cover goes through ``torch.optim.Adam.step`` itself,
-    on the same state tensors: more than one parameter group, amsgrad / maximize / capturable / differentiable, a tensor learning rate,
-    a closure, parameters that are not exactly one HIP model's (or a model without the flat gradient buffer: UNet_Small, CPU), a gradient
-    that is not the latest backward's view.  ``state_dict`` / ``load_state_dict`` are torch's (step counters are materialised first).
+    A subclass names its torch class (``_TORCH``), the state tensors that become views of flat buffers (``_BUFFERS``), whether torch keeps
+    a step counter per parameter (``_COUNTS``), which settings of a parameter group the launch covers (``_covers``) and the launch
+    itself (``_launch``).
 
-    ``device_state=DeviceStepState(...)``: the step count, the bias corrections and the learning rate live in that device block, and
-    the step is two launches -- ``mural_op_train_state_tick`` (step += 1, the two factors from the block's rate, the observed loss added,
-    the per-batch scheduler) + ``mural_op_adam_flat_state`` -- that read nothing from the host, so ``GraphedTrainStep`` can capture them.
-    A step the flat kernel does not cover still goes through torch: the block's step and rate are read back first (into the step
-    counters and ``param_groups``) and the block is ticked all the same, so the two routes stay one sequence."""
+    ``p.data`` becomes a view of one flat buffer at the first covered step (``_enter_flat``; only when every parameter has state or none
+    has) and the state tensors are views of buffers with the same slot layout (zero padding that stays zero).  ``_flat`` is (layout,
+    parameters, parameter buffer, state buffers...) while the launch applies, None otherwise; leaving the layout keeps the views -- torch
+    steps on them -- and materialises the step counters.  With a ``device_state`` the block counts the updates and holds the rate; a step
+    that goes through torch reads both back first and ticks the block all the same, so the two routes stay one sequence."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, device_state=None, **kw):
-        params = list(params)
-        if "fused" not in kw and "foreach" not in kw:      # torch's fused implementation for the steps that fall through, where it applies
-            flat = [q for p in params for q in (p["params"] if isinstance(p, dict) else [p])]
-            kw["fused"] = bool(flat) and all(torch.is_tensor(q) and q.is_cuda and q.is_floating_point() for q in flat)
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
-        self._flat = None          # (layout, params, param buffer, exp_avg buffer, exp_avg_sq buffer) while the one-launch step applies
+    _TORCH = None
+    _BUFFERS = ()
+    _COUNTS = True
+
+    def _init_flat(self, device_state):
+        self._flat = None          # (layout, params, param buffer, state buffers...) while the one-launch step applies
         self._flat_t = 0           # updates done (the step counters of torch's state, materialised on demand)
-        if device_state is not None and tuple(float(b) for b in betas) != device_state.betas:
-            raise ValueError(f"betas {tuple(betas)} differ from the device state's {device_state.betas}")
         self.device_state = device_state      # with one, the BLOCK counts the updates (_flat_t: its value at the last read-back)
 
     # -- torch's state <-> the flat buffers -----------------------------------------------------------------------------------
@@ -357,6 +349,8 @@ class Adam(torch.optim.Adam):
         self._write_steps()
 
     def _write_steps(self):
+        if not self._COUNTS:
+            return
         g = self.param_groups[0]
         on_dev = bool(g.get("fused")) or bool(g.get("capturable"))
         for p in self._flat[1]:
@@ -374,24 +368,26 @@ class Adam(torch.optim.Adam):
         have = [p for p in params if len(self.state.get(p, {}))]
         t = 0
         if have:
-            if len(have) != len(params):
+            if len(have) != len(params) or any(not torch.is_tensor(self.state[p].get(k)) for p in params for k in self._BUFFERS):
                 return False
-            steps = torch.stack([self.state[p]["step"].detach().to(device=dev, dtype=torch.float32).reshape(()) for p in params])
-            t = float(steps[0].item())
-            if t != int(t) or not bool((steps == t).all().item()):
-                return False
-        pf, mf, vf = (torch.zeros(lay.total, dtype=torch.float32, device=dev) for _ in range(3))
+            if self._COUNTS:
+                steps = torch.stack([self.state[p]["step"].detach().to(device=dev, dtype=torch.float32).reshape(()) for p in params])
+                t = float(steps[0].item())
+                if t != int(t) or not bool((steps == t).all().item()):
+                    return False
+        pf, *bufs = (torch.zeros(lay.total, dtype=torch.float32, device=dev) for _ in range(1 + len(self._BUFFERS)))
         for p, o in zip(lay.plist, lay.poffs):
             n = p.numel()
             slot = lambda f: f[o:o + n].view(p.shape)      # noqa: E731
             slot(pf).copy_(p.data)
             st = self.state[p]
             if have:
-                slot(mf).copy_(st["exp_avg"])
-                slot(vf).copy_(st["exp_avg_sq"])
+                for k, f in zip(self._BUFFERS, bufs):
+                    slot(f).copy_(st[k])
             p.data = slot(pf)
-            st["exp_avg"], st["exp_avg_sq"] = slot(mf), slot(vf)
-        self._flat, self._flat_t = (lay, list(lay.plist), pf, mf, vf), int(t)
+            for k, f in zip(self._BUFFERS, bufs):
+                st[k] = slot(f)
+        self._flat, self._flat_t = (lay, list(lay.plist), pf, *bufs), int(t)
         if self.device_state is not None:
             self.device_state.set_step(int(t))      # torch's counters are the record while the flat layout is not entered
         self._write_steps()
@@ -401,16 +397,15 @@ class Adam(torch.optim.Adam):
         if len(self.param_groups) != 1:
             return False
         g = self.param_groups[0]
-        if (g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or torch.is_tensor(g["lr"])
-                or g.get("decoupled_weight_decay")):
+        if g.get("maximize") or g.get("capturable") or g.get("differentiable") or torch.is_tensor(g["lr"]) or not self._covers(g):
             return False
         if self._flat is None:
             params = [p for p in g["params"] if p.numel()]
-            from .model.train_step import layout_of_params
-            lay = layout_of_params(params)
+            from .model.step_layout import layout_of_params
+            lay = layout_of_params(params, device_state=self.device_state is not None)
             if lay is None or lay.last_flat is None or not self._enter_flat(lay, params):
                 return False
-        lay, params, pf, mf, vf = self._flat
+        lay, params, pf = self._flat[:3]
         flat = lay.last_flat
         if flat is None or flat.device != pf.device or flat.numel() != pf.numel():
             return False
@@ -419,26 +414,20 @@ class Adam(torch.optim.Adam):
             gr = p.grad
             if gr is None or gr.data_ptr() != gbase + 4 * off or p.data_ptr() != pbase + 4 * off:
                 return False
-        from . import _lib
-        b1, b2 = g["betas"]
         st = self.device_state
-        if st is not None:
-            if st.buf.device != pf.device or (float(b1), float(b2)) != st.betas:
-                return False
-            st.tick()
-            with torch.cuda.device(pf.device):
-                _lib.check(_lib.lib().mural_op_adam_flat_state(pf.data_ptr(), gbase, mf.data_ptr(), vf.data_ptr(), pf.numel(), st.buf.data_ptr(),
-                                                               float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]),
-                                                               _lib.current_stream_ptr(pf.device)))
-        else:
+        if st is not None and (st.buf.device != pf.device or not self._state_fits(g, st)):
+            return False
+        if st is None:
             self._flat_t += 1
-            with torch.cuda.device(pf.device):
-                _lib.check(_lib.lib().mural_op_adam_flat(pf.data_ptr(), gbase, mf.data_ptr(), vf.data_ptr(), pf.numel(), float(g["lr"]),
-                                                         float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), self._flat_t,
-                                                         _lib.current_stream_ptr(pf.device)))
+        from . import _lib
+        with torch.cuda.device(pf.device):
+            self._launch(_lib, g, [f.data_ptr() for f in self._flat[2:]], gbase, pf.numel(), st, _lib.current_stream_ptr(pf.device))
         model = lay.model_ref()
         if model is not None and not model.training:      # (a step in eval mode: the kernel bumps no tensor version the folded copy watches)
             model.invalidate_folded()
+        return True
+
+    def _state_fits(self, g, st):
         return True
 
     @torch.no_grad()
@@ -455,7 +444,7 @@ class Adam(torch.optim.Adam):
             self.device_state.tick()
         else:
             self._leave_flat()
-        parent = torch.optim.Adam.step
+        parent = self._TORCH.step
         if getattr(parent, "hooked", False):
             parent = getattr(parent, "__wrapped__", parent)
         return parent(self, closure)
@@ -469,6 +458,126 @@ class Adam(torch.optim.Adam):
         return super().load_state_dict(state_dict)
 
 
+class Adam(_FlatStep, torch.optim.Adam):
+    """``torch.optim.Adam`` (the reference's default optimiser, training.py:346-350, stepped at :432) with a ONE-launch step for a model
+    whose training step runs in the library (model/train_step.py, model/indel_train_step.py): there every gradient is a view of one flat
+    buffer, so the parameters and the two moment buffers are laid out the same way -- ``p.data`` becomes a view of one flat buffer at the
+    first step, ``state[p]['exp_avg']`` / ``['exp_avg_sq']`` are views as well -- and the update is one elementwise kernel
+    (``mural_op_adam_flat``: torch's fused update rule, bias corrections from the host) instead of torch's multi-tensor sequence (a
+    step-counter foreach + three launches over ~150 tensor quadruples, 40 us at the end of every step with nothing beside them).
+
+    Same constructor as ``torch.optim.Adam``.  Everything the one launch does not cover goes through ``torch.optim.Adam.step`` itself,
+    on the same state tensors: more than one parameter group, amsgrad / maximize / capturable / differentiable, a tensor learning rate,
+    a closure, parameters that are not exactly one HIP model's (or a model without the flat gradient buffer: the per-layer paths, CPU; a
+    UNet_Small unless the optimiser carries a ``device_state``), a
+    gradient that is not the latest backward's view.  ``state_dict`` / ``load_state_dict`` are torch's (step counters are materialised
+    first).
+
+    ``device_state=DeviceStepState(...)``: the step count, the bias corrections and the learning rate live in that device block, and
+    the step is two launches -- ``mural_op_train_state_tick`` (step += 1, the two factors from the block's rate, the observed loss added,
+    the per-batch scheduler) + ``mural_op_adam_flat_state`` -- that read nothing from the host, so ``GraphedTrainStep`` can capture them.
+    A step the flat kernel does not cover still goes through torch: the block's step and rate are read back first (into the step
+    counters and ``param_groups``) and the block is ticked all the same, so the two routes stay one sequence."""
+
+    _TORCH = torch.optim.Adam
+    _BUFFERS = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, device_state=None, **kw):
+        params = list(params)
+        if "fused" not in kw and "foreach" not in kw:      # torch's fused implementation for the steps that fall through, where it applies
+            flat = [q for p in params for q in (p["params"] if isinstance(p, dict) else [p])]
+            kw["fused"] = bool(flat) and all(torch.is_tensor(q) and q.is_cuda and q.is_floating_point() for q in flat)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+        if device_state is not None and tuple(float(b) for b in betas) != device_state.betas:
+            raise ValueError(f"betas {tuple(betas)} differ from the device state's {device_state.betas}")
+        self._init_flat(device_state)
+
+    def _covers(self, g):
+        return not (g.get("amsgrad") or g.get("decoupled_weight_decay"))
+
+    def _state_fits(self, g, st):
+        return (float(g["betas"][0]), float(g["betas"][1])) == st.betas
+
+    def _launch(self, _lib, g, ptrs, gbase, n, st, stream):
+        pf, mf, vf = ptrs
+        b1, b2 = g["betas"]
+        if st is not None:
+            st.tick()
+            _lib.check(_lib.lib().mural_op_adam_flat_state(pf, gbase, mf, vf, n, st.buf.data_ptr(), float(b1), float(b2), float(g["eps"]),
+                                                           float(g["weight_decay"]), stream))
+        else:
+            _lib.check(_lib.lib().mural_op_adam_flat(pf, gbase, mf, vf, n, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                                                     float(g["weight_decay"]), self._flat_t, stream))
+
+
+class AdamW(_FlatStep, torch.optim.AdamW):
+    """``torch.optim.AdamW`` (the reference's 'AdamW' / 'AdamW2', training.py:351-356: ``amsgrad=True``) with the one-launch step of ``Adam``
+    above: parameters, ``exp_avg``, ``exp_avg_sq`` and ``max_exp_avg_sq`` in flat buffers of one slot layout, stepped by
+    ``mural_op_adamw_amsgrad_flat`` (decoupled decay, then the amsgrad update).  Same constructor as ``torch.optim.AdamW``; what the launch
+    does not cover -- ``amsgrad=False`` and every case listed for ``Adam`` -- is ``torch.optim.AdamW.step`` on the same state tensors.
+
+    ``device_state``: tick + ``mural_op_adamw_amsgrad_flat_state``, which reads the two bias-correction floats and the rate from the block.
+    The rate it finds there is the one the tick's scheduler left for the NEXT update: at a tick where the scheduler moves the rate, the
+    decoupled decay ``1 - lr weight_decay`` of this update is formed from the new rate, one update earlier than on the host loop (the
+    Adam part of the update uses the tick's ``step_size``, formed from this update's rate)."""
+
+    _TORCH = torch.optim.AdamW
+    _BUFFERS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, device_state=None, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+        if device_state is not None and tuple(float(b) for b in betas) != device_state.betas:
+            raise ValueError(f"betas {tuple(betas)} differ from the device state's {device_state.betas}")
+        self._init_flat(device_state)
+
+    def _covers(self, g):
+        return bool(g.get("amsgrad"))
+
+    _state_fits = Adam._state_fits
+
+    def _launch(self, _lib, g, ptrs, gbase, n, st, stream):
+        pf, mf, vf, xf = ptrs
+        b1, b2 = g["betas"]
+        if st is not None:
+            st.tick()
+            _lib.check(_lib.lib().mural_op_adamw_amsgrad_flat_state(pf, gbase, mf, vf, xf, n, st.buf.data_ptr(), float(b1), float(b2),
+                                                                    float(g["eps"]), float(g["weight_decay"]), stream))
+        else:
+            _lib.check(_lib.lib().mural_op_adamw_amsgrad_flat(pf, gbase, mf, vf, xf, n, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                                                              float(g["weight_decay"]), self._flat_t, stream))
+
+
+class SGD(_FlatStep, torch.optim.SGD):
+    """``torch.optim.SGD`` (the reference's 'SGD', training.py:357-360: momentum 0.98, nesterov) with the one-launch step of ``Adam`` above:
+    parameters and ``momentum_buffer`` in flat buffers of one slot layout, stepped by ``mural_op_sgd_flat`` (a zero buffer gives torch's
+    first step, so entering the layout before any state exists needs no flag).  Same constructor as ``torch.optim.SGD``; what the launch
+    does not cover -- no nesterov momentum, dampening, and every case listed for ``Adam`` -- is ``torch.optim.SGD.step`` on the same state.
+
+    ``device_state``: ``mural_op_sgd_flat_state`` reads the rate from the block, then the tick advances the block (count, loss sum,
+    scheduler) -- in this order, so the update runs at the rate the previous tick left for it, as on the host loop.  The tick's betas are
+    the state's; its two bias-correction floats go unused."""
+
+    _TORCH = torch.optim.SGD
+    _BUFFERS = ("momentum_buffer",)
+    _COUNTS = False
+
+    def __init__(self, params, *args, device_state=None, **kw):
+        super().__init__(params, *args, **kw)
+        self._init_flat(device_state)
+
+    def _covers(self, g):
+        return bool(g.get("nesterov")) and g.get("momentum", 0) > 0 and not g.get("dampening")
+
+    def _launch(self, _lib, g, ptrs, gbase, n, st, stream):
+        pf, bf = ptrs
+        if st is not None:
+            _lib.check(_lib.lib().mural_op_sgd_flat_state(pf, gbase, bf, n, st.buf.data_ptr(), float(g["momentum"]),
+                                                          float(g["weight_decay"]), stream))
+            st.tick()
+        else:
+            _lib.check(_lib.lib().mural_op_sgd_flat(pf, gbase, bf, n, float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), stream))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # the reference's epoch loop (MuRaL/training.py:346-450) around the HIP models: optimiser / scheduler choice and the
 # per-batch policy (skip batches of one row, clip at 10, step the scheduler every batch, restart a learning rate that decayed
@@ -479,15 +588,13 @@ def make_optimizer(config, params, device_state=None):
     params = [p for p in params if p.requires_grad]
     lr, wd = config["learning_rate"], config["weight_decay"]
     name = config["optim"]
+    # the torch classes with one launch per step behind the library's training step (device_state: tick + one launch, capturable)
     if name == "Adam":
-        # torch.optim.Adam; one launch per step behind the library's training step (device_state: tick + one launch, capturable)
         return Adam(params, lr=lr, weight_decay=wd, device_state=device_state)
-    if device_state is not None:
-        raise ValueError(f"the device step state serves optim 'Adam' only, not {name}")
     if name in ("AdamW", "AdamW2"):
-        return torch.optim.AdamW(params, lr=lr, weight_decay=wd, amsgrad=True)
+        return AdamW(params, lr=lr, weight_decay=wd, amsgrad=True, device_state=device_state)
     if name == "SGD":
-        return torch.optim.SGD(params, lr=lr, weight_decay=wd, momentum=0.98, nesterov=True)
+        return SGD(params, lr=lr, weight_decay=wd, momentum=0.98, nesterov=True, device_state=device_state)
     raise ValueError(f"Error: unsupported optimization method {name}")
 
 
@@ -533,21 +640,27 @@ def train_epoch(model, batches, criterion, optimizer, scheduler, config, device,
     return total_loss
 
 
-def _device_epoch_refusal(model, criterion, optimizer):
-    from .model import train_step
-    from .model.model_snv import Network0, _HipSnvBase
-    core = model.model if isinstance(model, Network0) else model
-    if not isinstance(core, _HipSnvBase) or not train_step.supported(core):
-        return "the model does not train on the one-call step (an SNV model with 32 conv channels of kernel 3, or the local-only one)"
-    if not isinstance(optimizer, Adam) or optimizer.device_state is None:
-        return "the optimizer is not mural_amd.train.Adam(..., device_state=DeviceStepState(...))"
+def _device_epoch_refusal(model, criterion, optimizer, model_type="snv"):
+    if model_type == "snv":
+        from .model import train_step
+        from .model.model_snv import Network0, _HipSnvBase
+        core = model.model if isinstance(model, Network0) else model
+        if not isinstance(core, _HipSnvBase) or not train_step.supported(core):
+            return "the model does not train on the one-call step (an SNV model with 32 conv channels of kernel 3, or the local-only one)"
+    else:
+        import os
+        from .model.model_indel import UNet_Small
+        if not isinstance(model, UNet_Small) or os.environ.get("MURAL_INDEL_TRAIN_PER_UNIT"):
+            return "the model does not train on the one-call step (a UNet_Small, without MURAL_INDEL_TRAIN_PER_UNIT)"
+    if not isinstance(optimizer, _FlatStep) or optimizer.device_state is None:
+        return "the optimizer is not mural_amd.train.Adam / AdamW / SGD(..., device_state=DeviceStepState(...))"
     if not isinstance(criterion, (CrossEntropySum, torch.nn.CrossEntropyLoss)):
         return "the criterion is not a cross-entropy loss giving one float32 device scalar"
     return None
 
 
-def _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y):
-    loss = criterion(model((cont_x, cat_x), distal_x), y)
+def _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y, model_type="snv"):
+    loss = criterion(model((cont_x, cat_x), distal_x) if model_type == "snv" else model(distal_x), y)
     optimizer.zero_grad()
     loss.backward()
     clip_grad_norm_(model, 10)
@@ -555,7 +668,7 @@ def _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y):
     optimizer.step()
 
 
-def _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, distal_x, y):
+def _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, distal_x, y, model_type="snv"):
     """(the model's captured step for batches of y's rows, whether it was captured just now -- its one warm-up step then WAS the step
     on this batch).  Captured again when what the graph baked in is gone: another optimiser / criterion / schedule, parameters that
     left the optimiser's flat buffer, another input form."""
@@ -568,27 +681,31 @@ def _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, dista
         if (key == (id(optimizer), id(criterion), sched) and step.opt is optimizer and step.crit is criterion and flat is not None
                 and flat[2].data_ptr() == pbase and step.x.shape == x.shape and step.x.dtype == x.dtype):
             return step, False
-    step = GraphedTrainStep(model, optimizer, criterion, cont_x, cat_x, distal_x, y, max_norm=10, warmup=1)
+    if model_type == "snv":
+        step = GraphedTrainStep(model, optimizer, criterion, cont_x, cat_x, distal_x, y, max_norm=10, warmup=1)
+    else:
+        step = GraphedIndelTrainStep(model, optimizer, criterion, distal_x, y, max_norm=10, warmup=1)
     if optimizer._flat is None:
         raise RuntimeError("train_epoch_device: the optimiser did not take its one-launch step on this model")
     steps[y.shape[0]] = (step, (id(optimizer), id(criterion), sched), optimizer._flat[2].data_ptr())
     return step, True
 
 
-def train_epoch_device(model, batches, criterion, optimizer, config, device, epoch=0, train_size=None):
-    """``train_epoch`` with the loop's state on the device (``optimizer = Adam(..., device_state=DeviceStepState(...))``): the same
-    policy -- batches of one row skipped, clipping at 10, the scheduler of ``config`` ticked every batch unless 'ROP', the restart of a
-    rate below min_lr, the rate reset to restart_lr for 'StepLR2' when epoch > 0 -- with the scheduler inside the tick kernel instead
-    of a host ``scheduler`` object, and NOTHING read back before the epoch's end:
+def train_epoch_device(model, batches, criterion, optimizer, config, device, epoch=0, train_size=None, model_type="snv"):
+    """``train_epoch`` with the loop's state on the device (``optimizer = make_optimizer(config, params, device_state=DeviceStepState(...))``:
+    this module's ``Adam``, ``AdamW`` or ``SGD``): the same policy -- batches of one row skipped, clipping at 10, the scheduler of ``config``
+    ticked every batch unless 'ROP', the restart of a rate below min_lr, the rate reset to restart_lr for 'StepLR2' when epoch > 0 -- with
+    the scheduler inside the tick kernel instead of a host ``scheduler`` object, and NOTHING read back before the epoch's end:
 
-      * batches of ``config['batch_size']`` rows replay a ``GraphedTrainStep`` captured once per (model, rows) and kept on the model;
+      * batches of ``config['batch_size']`` rows replay a ``GraphedTrainStep`` (``model_type="indel"``: a ``GraphedIndelTrainStep``, on dense
+        windows or ``SymbolWindows``) captured once per (model, rows) and kept on the model;
       * batches of any other size (the carry batches of ``epoch_order``) run the same kernels eagerly, so the block sees one sequence;
       * at the end ONE ``state.read()``: ``param_groups[..]['lr']`` is set from it (a host ``ReduceLROnPlateau`` can act between epochs),
         the deferred input check of the last replay is raised, the block's loss sum is returned.
 
-    SNV models on the one-call training step with this module's ``Adam`` and a cross-entropy criterion; anything else raises ValueError
-    (``train_epoch`` is the loop for it)."""
-    why = _device_epoch_refusal(model, criterion, optimizer)
+    Models on a one-call training step (the SNV models ``train_step.supported`` names, ``UNet_Small``) with one of this module's optimisers
+    on a device state and a cross-entropy criterion; anything else raises ValueError (``train_epoch`` is the loop for it)."""
+    why = _device_epoch_refusal(model, criterion, optimizer, model_type)
     if why is not None:
         raise ValueError(f"train_epoch_device: {why}; use train_epoch")
     state = optimizer.device_state
@@ -606,11 +723,11 @@ def train_epoch_device(model, batches, criterion, optimizer, config, device, epo
             continue
         cat_x, cont_x, distal_x, y = cat_x.to(device), cont_x.to(device), distal_x.to(device), y.to(device).long().squeeze()
         if y.shape[0] == common:
-            graphed, fresh = _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, distal_x, y)
+            graphed, fresh = _graphed_epoch_step(model, criterion, optimizer, sched, cont_x, cat_x, distal_x, y, model_type)
             if not fresh:
-                graphed(cont_x, cat_x, distal_x, y)
+                graphed(cont_x, cat_x, distal_x, y) if model_type == "snv" else graphed(distal_x, y)
         else:
-            _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y)
+            _device_eager_step(model, criterion, optimizer, cont_x, cat_x, distal_x, y, model_type)
     r = state.read()
     optimizer._flat_t = r["step"]
     for g in optimizer.param_groups:
