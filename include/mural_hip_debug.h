@@ -55,6 +55,42 @@ int mural_debug_cw_set_stamps(void* dev_ptr);
 int mural_debug_first_set_stamps(void* dev_ptr);
 /* the same for the three backward launches of the fused local branch (csrc/snv_local_train.h), uint64 [3][256][8]; NULL: off */
 int mural_debug_lt_set_stamps(void* dev_ptr);
+/* Validation hooks of tests/test_gpu_snv_train_fused.py: the fused local branch of the composed SNV training step on its own
+ * (csrc/snv_local_train.h: gather -> Dropout -> [Linear -> ReLU -> BatchNorm1d -> Dropout] x 2 -> Linear in three launches per direction
+ * and one for the three weight gradients).  Always the fused launches: no development switch is read.  MURAL_E_INVALID for the shapes
+ * the composed step keeps on its per-op route (a Linear dimension outside 1 .. 256, 8 h1 + 5 emb_rows floats beyond 64 KB, B > 2^20)
+ * and for dims[0] != 5 * cols; B == 0 returns MURAL_OK and touches nothing.
+ * HOST arrays: dims[4] = in1, h1, h2, nc; drop[3], seeds[3] (dropout in front of Linear l; the draw of mural_op_dropout over that
+ * Linear's [B][K] input, seed_dev as there); W, bias, xt [3] and gamma, beta, running_mean, running_var, state, acc_f, acc_b, lin, dd, g,
+ * dgamma, dbeta [2], dW, db [3] hold DEVICE pointers.  Device tensors: cat [B][cols] int64 (clamped into the table), E [emb_rows][5],
+ * W[l] [N_l][K_l], xt[l] [B][K_l] (the Linear's input as used), lin[l] [B][N_l] (its raw output), logits [B][nc], state[l] [4][N_l] =
+ * scale | shift | mean | invstd, dd[l] [B][N_l] (the masked gradient of BatchNorm l's output), g[l] [B][N_l] (the gradient of lin[l]),
+ * dE [emb_rows][5].
+ * The caller zeroes acc_f[l] (forward) and acc_b[l] (backward), double [MURAL_BN_SLOTS][2][N_l] each; the backward zeroes dE itself.
+ * The backward reads what the forward saved (xt, lin, state) with the same drop / seeds / seed_dev. */
+int mural_debug_local_train_fwd(const int64_t* cat, const float* E, int32_t cols, int32_t emb_rows, int64_t B, const int32_t* dims,
+                                const float* const* W, const float* const* bias, const float* const* gamma, const float* const* beta,
+                                float* const* running_mean, float* const* running_var, float* const* state, double* const* acc_f,
+                                const float* drop, const uint64_t* seeds, const uint64_t* seed_dev, float eps, float momentum,
+                                float* const* xt, float* const* lin, float* logits, void* stream);
+int mural_debug_local_train_bwd(const int64_t* cat, int32_t cols, int32_t emb_rows, int64_t B, const int32_t* dims, const float* dlogits,
+                                const float* const* W, const float* const* gamma, const float* const* state, double* const* acc_b,
+                                const float* drop, const uint64_t* seeds, const uint64_t* seed_dev, const float* const* xt,
+                                const float* const* lin, float* const* dd, float* const* g, float* const* dW, float* const* db,
+                                float* const* dgamma, float* const* dbeta, float* dE, void* stream);
+/* The same for a tower's head (csrc/snv_head_train.h): c3 [B][L][32] (raw conv output) -> feat = relu(max over L) [B][32], arg [B][32]
+ * (the first maximum), BatchNorm1d(32) -> Dropout (the draw of mural_op_dropout over [B][32]) = fd -> Linear(32, nc) = logits, and back:
+ * dd [B][32] (the masked gradient of the BatchNorm output), dx [B][L][32], dgamma, dbeta [32]; the backward hook also runs the Linear's
+ * weight gradient (dW [nc][32], db [nc] from dlogits and fd).  MURAL_E_INVALID unless 1 <= nc <= 16; B == 0 returns MURAL_OK and
+ * touches nothing.  The caller zeroes `acc` in front of each hook (double [MURAL_BN_SLOTS][2][32], one block per direction). */
+int mural_debug_head_train_fwd(const float* c3, int64_t B, int32_t L, float* feat, int32_t* arg, double* acc, const float* gamma,
+                               const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* state,
+                               float p, uint64_t seed, const uint64_t* seed_dev, float* fd, const float* W, const float* bias, int32_t nc,
+                               float* logits, void* stream);
+int mural_debug_head_train_bwd(const float* dlogits, const float* W, int32_t nc, int64_t B, int32_t L, const float* feat,
+                               const float* state, const float* gamma, float p, uint64_t seed, const uint64_t* seed_dev, float* dd,
+                               double* acc, const int32_t* arg, const float* c3, float* dx, float* dgamma, float* dbeta, const float* fd,
+                               float* dW, float* db, void* stream);
 int mural_debug_cw_conv32_fwd(const float* x, int64_t B, int32_t L, int32_t pre_relu, const double* acc, const float* gamma,
                               const float* beta, float* running_mean, float* running_var, float* state, const float* W,
                               const float* bias, int32_t post_relu, const float* res1, const float* res2, double* acc_out,

@@ -289,6 +289,13 @@ DEBUG_PROTOTYPES = {
     "mural_debug_cw_conv32_fwd": (C.c_int, [VP, I64, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP, I32, VP, VP, VP]),
     "mural_debug_cw_conv32_bwd": (C.c_int, [VP, VP, VP, I64, I32, VP, VP, I32, VP, VP, VP, VP, VP, VP]),
     "mural_debug_cl_bn_stats": (C.c_int, [VP, I64, I32, VP, VP]),
+    "mural_debug_local_train_fwd": (C.c_int, [VP, VP, I32, I32, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_float, C.c_float, VP,
+                                              VP, VP, VP]),
+    "mural_debug_local_train_bwd": (C.c_int, [VP, I32, I32, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "mural_debug_head_train_fwd": (C.c_int, [VP, I64, I32, VP, VP, VP, VP, VP, C.c_float, C.c_float, VP, VP, VP, C.c_float, C.c_uint64, VP, VP,
+                                             VP, VP, I32, VP, VP]),
+    "mural_debug_head_train_bwd": (C.c_int, [VP, VP, I32, I64, I32, VP, VP, VP, C.c_float, C.c_uint64, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP,
+                                             VP, VP]),
     "mural_debug_first_fwd_cl": (C.c_int, [VP, I64, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP, VP,
                                            VP, VP]),
     "mural_debug_first_bwd_cl": (C.c_int, [VP, VP, VP, I64, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP,

@@ -233,6 +233,64 @@ extern "C" int mural_debug_first_set_stamps(void* dev_ptr) {
   return MURAL_OK;
 }
 
+// ---- validation hooks (tests/test_gpu_snv_train_fused.py): the fused local branch and tower head of the composed SNV step on their own.
+// Always the fused launches (no development switch is consulted); the shapes the composed step sends down the per-op route are refused.
+static int local_train_hook_shape(int32_t cols, int32_t emb_rows, int64_t B, const int32_t* dims) {
+  MURAL_REQUIRE(dims && cols >= 1 && emb_rows >= 1 && B >= 0, "local branch (fused): cols, emb_rows >= 1, B >= 0 and dims[4] are needed");
+  MURAL_REQUIRE(dims[0] == 5 * cols, "local branch (fused): dims[0] must be 5 * cols");
+  MURAL_REQUIRE(mural::local_train_shape_ok(dims[0], dims[1], dims[2], dims[3], emb_rows, B),
+                "local branch (fused): 1 .. 256 features per Linear, 8 h1 + 5 emb_rows floats within 64 KB and B <= 2^20 "
+                "(got in1 %d, h1 %d, h2 %d, nc %d, emb_rows %d, B %lld)", dims[0], dims[1], dims[2], dims[3], emb_rows, (long long)B);
+  return MURAL_OK;
+}
+
+extern "C" int mural_debug_local_train_fwd(const int64_t* cat, const float* E, int32_t cols, int32_t emb_rows, int64_t B, const int32_t* dims,
+                                           const float* const* W, const float* const* bias, const float* const* gamma,
+                                           const float* const* beta, float* const* running_mean, float* const* running_var,
+                                           float* const* state, double* const* acc_f, const float* drop, const uint64_t* seeds,
+                                           const uint64_t* seed_dev, float eps, float momentum, float* const* xt, float* const* lin,
+                                           float* logits, void* stream) {
+  if (int rc = local_train_hook_shape(cols, emb_rows, B, dims)) return rc;
+  return mural::local_train_fwd(cat, E, cols, emb_rows, B, dims, W, bias, gamma, beta, running_mean, running_var, state, acc_f, drop, seeds,
+                                seed_dev, eps, momentum, xt, lin, logits, STREAM);
+}
+
+extern "C" int mural_debug_local_train_bwd(const int64_t* cat, int32_t cols, int32_t emb_rows, int64_t B, const int32_t* dims,
+                                           const float* dlogits, const float* const* W, const float* const* gamma,
+                                           const float* const* state, double* const* acc_b, const float* drop, const uint64_t* seeds,
+                                           const uint64_t* seed_dev, const float* const* xt, const float* const* lin, float* const* dd,
+                                           float* const* g, float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta,
+                                           float* dE, void* stream) {
+  if (int rc = local_train_hook_shape(cols, emb_rows, B, dims)) return rc;
+  return mural::local_train_bwd(cat, cols, emb_rows, B, dims, dlogits, W, gamma, state, acc_b, drop, seeds, seed_dev, xt, lin, dd, g, dW, db,
+                                dgamma, dbeta, dE, STREAM);
+}
+
+static int head_train_hook_shape(int64_t B, int32_t L, int32_t nc) {
+  MURAL_REQUIRE(B >= 0 && L >= 1, "tower head (fused): B >= 0 and L >= 1 are needed");
+  MURAL_REQUIRE(mural::head_train_shape_ok(nc), "tower head (fused): 1 .. %d classes (got %d)", SNV_MAXCLASS, nc);
+  return MURAL_OK;
+}
+
+extern "C" int mural_debug_head_train_fwd(const float* c3, int64_t B, int32_t L, float* feat, int32_t* arg, double* acc, const float* gamma,
+                                          const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                          float* state, float p, uint64_t seed, const uint64_t* seed_dev, float* fd, const float* W,
+                                          const float* bias, int32_t nc, float* logits, void* stream) {
+  if (int rc = head_train_hook_shape(B, L, nc)) return rc;
+  return mural::head_train_fwd(c3, B, L, feat, arg, acc, gamma, beta, eps, momentum, running_mean, running_var, state, p, seed, seed_dev, fd, W,
+                               bias, nc, logits, STREAM);
+}
+
+extern "C" int mural_debug_head_train_bwd(const float* dlogits, const float* W, int32_t nc, int64_t B, int32_t L, const float* feat,
+                                          const float* state, const float* gamma, float p, uint64_t seed, const uint64_t* seed_dev,
+                                          float* dd, double* acc, const int32_t* arg, const float* c3, float* dx, float* dgamma,
+                                          float* dbeta, const float* fd, float* dW, float* db, void* stream) {
+  if (int rc = head_train_hook_shape(B, L, nc)) return rc;
+  if (int rc = mural::head_train_bwd(dlogits, W, nc, B, L, feat, state, gamma, p, seed, seed_dev, dd, acc, arg, c3, dx, dgamma, dbeta, STREAM))
+    return rc;
+  return mural::head_train_wgrad(dlogits, fd, B, nc, dW, db, STREAM);
+}
+
 // diagnostic: wall-clock stamps of the fused local branch's three backward launches (uint64 [3][256][8]); NULL: off
 extern "C" int mural_debug_lt_set_stamps(void* dev_ptr) {
   mural::ltrain::g_lt_stamps = static_cast<unsigned long long*>(dev_ptr);

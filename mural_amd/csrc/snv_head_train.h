@@ -21,9 +21,11 @@ constexpr int HC = 32;      // channels of a tower
 // ---- forward 1: feat[b][c] = relu?(max_l x[b][l][c]), arg; batch sums of feat, feat^2
 __global__ __launch_bounds__(256) void hd_gmax_stats_kernel(const float* __restrict__ x, int64_t B, int L, int relu, float* __restrict__ feat,
                                                             int32_t* __restrict__ arg, double* __restrict__ acc) {
-  __shared__ float red[2][32][HC + 1];
+  // (the sums in double like bn_stats_kernel's: the variance is E[f^2] - mean^2, and with squares and partial sums rounded to float
+  // a channel whose spread is small against its mean kept few digits of it, or none)
+  __shared__ double red[2][32][HC + 1];
   const int tid = threadIdx.x, chunk = tid & 7, rsub = tid >> 3;
-  f32x4 s1 = splat(0.f), s2 = splat(0.f);
+  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t b = (int64_t)blockIdx.x * 32 + rsub; b < B; b += (int64_t)gridDim.x * 32) {
     f32x4 m = splat(-INFINITY);
     int am[4] = {0, 0, 0, 0};
@@ -40,8 +42,12 @@ __global__ __launch_bounds__(256) void hd_gmax_stats_kernel(const float* __restr
     st4(feat + (size_t)b * HC + 4 * chunk, m);
     int32_t* ap = arg + (size_t)b * HC + 4 * chunk;
     ap[0] = am[0]; ap[1] = am[1]; ap[2] = am[2]; ap[3] = am[3];
-    s1 += m;
-    s2 += m * m;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double w = (double)m[q];
+      s1[q] += w;
+      s2[q] += w * w;
+    }
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -51,10 +57,10 @@ __global__ __launch_bounds__(256) void hd_gmax_stats_kernel(const float* __restr
   __syncthreads();
   if (tid < 2 * HC) {
     const int which = tid >> 5, c = tid & 31;
-    float t = 0.f;
+    double t = 0.0;
 #pragma unroll
     for (int r = 0; r < 32; ++r) t += red[which][r][c];
-    atomicAdd(&acc[((size_t)(blockIdx.x % MURAL_BN_SLOTS) * 2 + which) * HC + c], (double)t);
+    atomicAdd(&acc[((size_t)(blockIdx.x % MURAL_BN_SLOTS) * 2 + which) * HC + c], t);
   }
 }
 
@@ -216,8 +222,9 @@ __global__ __launch_bounds__(256) void hd_bwd2_kernel(const float* __restrict__ 
 
 }  // namespace headtrain
 
+bool head_train_shape_ok(int nc) { return nc >= 1 && nc <= SNV_MAXCLASS; }
 bool head_train_fused_ok(int nc) {
-  return dev_int("MURAL_TRAIN_HEAD_OPS", 0) == 0 && nc >= 1 && nc <= SNV_MAXCLASS;
+  return dev_int("MURAL_TRAIN_HEAD_OPS", 0) == 0 && head_train_shape_ok(nc);
 }
 
 // forward of a tower's head: c3 [B][L][32] (raw conv output) -> feat, arg, fd, logits; acc zeroed by the caller

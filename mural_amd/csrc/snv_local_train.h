@@ -187,13 +187,15 @@ __global__ __launch_bounds__(256) void lt_fwd_kernel(const LtFwd a) {
 #pragma unroll
     for (int s = 0; s < KQ; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bf[s], acc, 0, 0, 0);
     // D[row 4 q + r][column m]
-    float s1 = 0.f, s2 = 0.f;
+    // (the sums in double like bn_stats_kernel's: the variance is E[w^2] - mean^2, and with squares and partial sums rounded to float
+    // a channel whose spread is small against its mean -- two close rows at B = 2 -- kept few digits of it, or none)
+    double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t row = row0 + 4 * q + r;
       if (row < a.B && nv) {
         a.y[row * N + n] = acc[r];
-        const float w = fmaxf(acc[r], 0.f);
+        const double w = (double)fmaxf(acc[r], 0.f);
         s1 += w;
         s2 += w * w;
       }
@@ -203,8 +205,8 @@ __global__ __launch_bounds__(256) void lt_fwd_kernel(const LtFwd a) {
       s2 += __shfl_xor(s2, 16); s2 += __shfl_xor(s2, 32);
       if (q == 0 && nv) {
         double* slot = a.acc_out + (size_t)(blockIdx.x % MURAL_BN_SLOTS) * 2 * N;
-        atomicAdd(&slot[n], (double)s1);
-        atomicAdd(&slot[N + n], (double)s2);
+        atomicAdd(&slot[n], s1);
+        atomicAdd(&slot[N + n], s2);
       }
     }
   }
@@ -499,11 +501,13 @@ int lt_launch_bwd(LtBwd a, hipStream_t stream) {
 // The bottom backward launch keeps the embedding-gradient table (emb_rows x 5 floats) and eight rows of the Linear's output in LDS:
 // tables beyond the 64 KB a launch gets without opting in (local_order >= 6: 4097 rows = 82 KB) and batches beyond the launchers'
 // 32-bit offsets take the per-op route, which has neither limit.
-bool local_train_fused_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B) {
-  if (dev_int("MURAL_TRAIN_LOCAL_OPS", 0) != 0) return false;
+bool local_train_shape_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B) {
   const size_t bottom_lds = ((size_t)8 * (size_t)h1 + (size_t)emb_rows * 5) * 4;
   if (bottom_lds > (size_t)64 * 1024 || B > (1 << 20)) return false;
   return in1 <= 256 && h1 <= 256 && h2 <= 256 && nc <= 256 && in1 >= 1 && h1 >= 1 && h2 >= 1 && nc >= 1;
+}
+bool local_train_fused_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B) {
+  return dev_int("MURAL_TRAIN_LOCAL_OPS", 0) == 0 && local_train_shape_ok(in1, h1, h2, nc, emb_rows, B);
 }
 
 int local_train_fwd(const int64_t* cat, const float* E, int cols, int emb_rows, int64_t B, const int* dims /* in1, h1, h2, nc */,

@@ -22,7 +22,8 @@ int train_bn2d_apply_dropout(const float* x, int64_t B, int C, int relu, const d
                              float momentum, float* running_mean, float* running_var, float* state, float p, uint64_t seed,
                              const uint64_t* seed_dev, float* y_bn, float* y, hipStream_t stream);
 // snv_head_train.h: a tower's head in two launches per direction
-bool head_train_fused_ok(int nc);
+bool head_train_shape_ok(int nc);      // the shapes the fused form serves
+bool head_train_fused_ok(int nc);      // ... and MURAL_TRAIN_HEAD_OPS does not ask for the per-op launches
 int head_train_fwd(const float* c3, int64_t B, int L, float* feat, int32_t* arg, double* acc, const float* gamma, const float* beta, float eps,
                    float momentum, float* running_mean, float* running_var, float* state, float p, uint64_t seed, const uint64_t* seed_dev,
                    float* fd, const float* W, const float* bias, int nc, float* logits, hipStream_t stream);
@@ -31,7 +32,8 @@ int head_train_bwd(const float* dlogits, const float* W, int nc, int64_t B, int 
                    float* dgamma, float* dbeta, hipStream_t stream);
 int head_train_wgrad(const float* dlogits, const float* fd, int64_t B, int nc, float* dW, float* db, hipStream_t stream);
 // snv_local_train.h: the local branch in three launches per direction
-bool local_train_fused_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B);
+bool local_train_shape_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B);      // the shapes the fused form serves
+bool local_train_fused_ok(int in1, int h1, int h2, int nc, int emb_rows, int64_t B);      // ... unless MURAL_TRAIN_LOCAL_OPS is set
 int local_train_fwd(const int64_t* cat, const float* E, int cols, int emb_rows, int64_t B, const int* dims, const float* const* W,
                     const float* const* bias, const float* const* gamma, const float* const* beta, float* const* running_mean,
                     float* const* running_var, float* const* state, double* const* acc_f, const float* drop, const uint64_t* seeds,
