@@ -10,6 +10,8 @@
                                   of tensors shaped like the reference's DataLoader output (leading dim 1).
   * ``epoch_order``            -- the rows ``generate_data_batches`` yields, as row numbers: the order of a whole epoch and its
                                   batch boundaries from the group sizes alone (what a device-side loader gathers by).
+  * ``split_segments``         -- the training / validation split by segment of MuRaL/training.py:220-227; ``segment_rows`` lists
+                                  the rows of a set of segments.  ``epoch_order(groups=)`` runs an epoch over such a set.
 """
 import numpy as np
 import torch
@@ -93,28 +95,62 @@ def generate_data_batches(segment_loader, batch_segment, batch_size, shuffle=Tru
             yield from batches_of(y, cat, dist, last=pending is None)
 
 
-def epoch_order(group_sizes, batch_segment, batch_size, shuffle=True, generator=None):
+def split_segments(n_segments, valid_ratio, split_seed):
+    """(training segments, validation segments) of a run without a validation file (MuRaL/training.py:220-227):
+    ``n_valid = int(n_segments * valid_ratio)`` segments go to validation, assigned by ``torch.utils.data.random_split`` over the segment
+    numbers with ``torch.Generator().manual_seed(split_seed)``; the validation segments are sorted ascending, the training segments stay in
+    the order the split gave them.  A ratio that leaves either side empty raises ValueError."""
+    n_segments = int(n_segments)
+    n_valid = int(n_segments * valid_ratio)
+    if n_valid < 1 or n_valid >= n_segments:
+        raise ValueError(f"valid_ratio {valid_ratio} of {n_segments} segments leaves {n_valid} for validation and {n_segments - n_valid} "
+                         "for training: both sides need at least one segment")
+    train, valid = torch.utils.data.random_split(range(n_segments), [n_segments - n_valid, n_valid],
+                                                 torch.Generator().manual_seed(int(split_seed)))
+    return [int(i) for i in train.indices], sorted(int(i) for i in valid.indices)
+
+
+def segment_rows(group_sizes, groups):
+    """Row numbers (int64 numpy, rows of the whole table) of the segments `groups`, segment after segment in the order given."""
+    starts = np.concatenate([[0], np.cumsum([int(v) for v in group_sizes], dtype=np.int64)]).astype(np.int64)
+    parts = [np.arange(starts[g], starts[g + 1], dtype=np.int64) for g in groups]
+    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
+
+
+def epoch_order(group_sizes, batch_segment, batch_size, shuffle=True, generator=None, groups=None):
     """(order, batch_bounds) of one epoch of ``generate_data_batches`` over segments of `group_sizes` rows each (the (segment, strand)
     groups of ``bed_order``, in order), with row i = the i-th row in bed_reader order: `order` (int64, a permutation of 0..n-1) lists
     the rows as the batches yield them, batch k is ``order[batch_bounds[k]:batch_bounds[k + 1]]`` (int64, len = batches + 1).  Same
     draws from `generator` as ``generate_data_batches``: one ``torch.randperm`` over the rows of each group of `batch_segment` segments,
-    a carried tail included, in group order."""
+    a carried tail included, in group order.
+
+    `groups` (a sequence of indices into `group_sizes`, each at most once) runs the epoch over those segments alone, in the order given --
+    what ``EpochLoader.split`` hands its two views: `order` then lists the rows of those segments, still numbered as rows of the WHOLE
+    table, and the groups of `batch_segment` are taken along `groups`.  None is every segment in table order."""
     sizes = [int(v) for v in group_sizes]
     if any(v < 0 for v in sizes) or int(batch_segment) < 1 or int(batch_size) < 1:
         raise ValueError("epoch_order: group sizes must be >= 0, batch_segment and batch_size >= 1")
     starts = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+    if groups is not None:
+        groups = [int(g) for g in groups]
+        if any(g < 0 or g >= len(sizes) for g in groups) or len(set(groups)) != len(groups):
+            raise ValueError("epoch_order: groups must be distinct indices into group_sizes")
+    n_groups = len(sizes) if groups is None else len(groups)
     order, bounds, emitted = [], [0], 0
     carry = None
-    for g0 in range(0, len(sizes), batch_segment):
-        g1 = min(g0 + batch_segment, len(sizes))
-        rows = torch.arange(int(starts[g0]), int(starts[g1]), dtype=torch.int64)
+    for g0 in range(0, n_groups, batch_segment):
+        g1 = min(g0 + batch_segment, n_groups)
+        if groups is None:
+            rows = torch.arange(int(starts[g0]), int(starts[g1]), dtype=torch.int64)
+        else:
+            rows = torch.cat([torch.arange(int(starts[g]), int(starts[g + 1]), dtype=torch.int64) for g in groups[g0:g1]])
         if carry is not None:                           # the short tail of the previous group goes FIRST
             rows = torch.cat([carry, rows])
             carry = None
         n = rows.shape[0]
         idx = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
         rows = rows[idx]
-        last = g1 == len(sizes)
+        last = g1 == n_groups
         full = n if last else n - n % batch_size
         if full < n:
             carry = rows[full:]
