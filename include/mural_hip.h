@@ -810,6 +810,52 @@ int64_t mural_summary_calib_cells(int32_t n_class, int32_t n_bins);
 int mural_summary_calib_rows(const MuralSummaryCalibRows* s, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Expected and observed mutations per annotated interval set of a shard while it is on the device
+ * (SummarySink(annotations=...) in flight, tables.annotation_table from a written table; csrc/summary_annot.hip): per
+ * group -- a name of the annotation file, e.g. the exons of a gene -- the label counts and probability sums of the rows
+ * whose start lies in one of the group's pieces.  One call takes the rows of a part of ONE chromosome, ascending in start
+ * (equal starts are legal), and that chromosome's pieces: piece p is [piece_b0[p], piece_b1[p]) of group piece_group[p];
+ * row i belongs to it when piece_b0[p] <= start[i] < piece_b1[p] (`end` is not read).  The pieces of one group are
+ * disjoint (tables.read_annotations merges them), those of different groups overlap freely, in any order.  Both ends of a
+ * piece are lower bounds in start (the first row with start >= b), so a piece's rows are one range and its sums the
+ * difference of two row prefix sums: tile sums of mural_summary_annot_tile_rows() rows, their exclusive scan, one lookup
+ * per piece -- no per-row search of the pieces.  The cells, their quantisation (q = rne(p * 2^71) as two limbs) and the
+ * integer atomics are mural_summary_kmer_rows': the table is a function of the SET of rows alone, bit for bit.
+ *   table [n_groups][3][n_class] of unsigned 64-bit cells += per row of a piece { 1 for the row's label, hi of prob[:, c],
+ *     lo of prob[:, c] }; on return lo < 2^40; the value of a class's cell is (hi * 2^40 + lo) / 2^71; zeroed by the
+ *     caller once -- the groups are global, one table serves every chromosome and part;
+ *   status (device int32): bit 0 a negative start, bit 1 a label outside 0 .. n_class - 1 (or no whole number), bit 3 a
+ *     probability that is NaN, negative or above 1 -- such rows are skipped; bit 2 a start below the row before it inside
+ *     the call: the table's content is then unspecified (nothing is read or written out of bounds).  A piece whose group
+ *     is outside 0 .. n_groups - 1 is skipped.
+ * The call works through slices of mural_summary_annot_slice_rows() = 2^23 rows (the unfolded lo prefixes stay below
+ * 2^63) and mural_summary_annot_fold_pieces() = 2^20 pieces between two folds of the table; both are additive and invisible
+ * to the caller.  ws: device scratch of mural_summary_annot_workspace_bytes(n, n_class) bytes -- (tiles of a slice + 1) *
+ * 3 n_class * 8: 7.5 MB for a part of 5 M rows of 4 classes --, 8-byte aligned.  n == 0 or n_pieces == 0 launches nothing.
+ * Launches on `stream`, no synchronisation, no read-back, no floating-point atomics.  n_class <= 8.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 0 .. n_class-1 are read          */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_groups;
+  const int64_t* piece_b0;   /* dev [n_pieces] */
+  const int64_t* piece_b1;   /* dev [n_pieces] */
+  const int32_t* piece_group; /* dev [n_pieces] */
+  int64_t n_pieces;
+  uint64_t* table;           /* dev [n_groups][3][n_class] */
+  int32_t* status;           /* dev [1] */
+} MuralSummaryAnnotRows;
+int32_t mural_summary_annot_tile_rows(void);
+int64_t mural_summary_annot_slice_rows(void);
+int64_t mural_summary_annot_fold_pieces(void);
+size_t mural_summary_annot_workspace_bytes(int64_t n, int32_t n_class);
+int mural_summary_annot_rows(const MuralSummaryAnnotRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

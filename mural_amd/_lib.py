@@ -121,6 +121,13 @@ class MuralSummaryCalibRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSummaryAnnotRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("label_kind", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
+                ("label", C.c_void_p), ("n", C.c_int64), ("n_class", C.c_int32), ("n_groups", C.c_int32), ("piece_b0", C.c_void_p),
+                ("piece_b1", C.c_void_p), ("piece_group", C.c_void_p), ("n_pieces", C.c_int64), ("table", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
 
 # every symbol include/mural_hip.h declares: name -> (restype, argtypes)
@@ -272,6 +279,11 @@ PROTOTYPES = {
     "mural_summary_motif_rows": (C.c_int, [C.POINTER(MuralSummaryMotifRows), VP]),
     "mural_summary_calib_cells": (I64, [I32, I32]),
     "mural_summary_calib_rows": (C.c_int, [C.POINTER(MuralSummaryCalibRows), VP]),
+    "mural_summary_annot_tile_rows": (I32, []),
+    "mural_summary_annot_slice_rows": (I64, []),
+    "mural_summary_annot_fold_pieces": (I64, []),
+    "mural_summary_annot_workspace_bytes": (C.c_size_t, [I64, I32]),
+    "mural_summary_annot_rows": (C.c_int, [C.POINTER(MuralSummaryAnnotRows), VP, C.c_size_t, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -35,19 +35,17 @@
 //     lo < 2^40 + 15 * 2^18 * 2^40 < 2^63.  hi grows by at most 2^31 + 1 per addition: exact for floor((2^32 - 2) / m) rows in one cell.
 #include "common.h"
 #include "kmer_key.h"
+#include "summary_quant.h"      // quantise_row, SK_MAX_CLASS, SK_LO_BITS: the cells' limbs, shared with csrc/summary_annot.hip
 
 namespace mural {
 namespace {
 
 constexpr int SK_THREADS = 256;
-constexpr int SK_MAX_CLASS = 8;
 constexpr int64_t SK_FOLD_ROWS = 1ll << 21;       // rows between two folds (the bound above)
 constexpr int64_t SM_FOLD_ROWS = 1ll << 18;       // ... of the motif tables: up to 15 additions of a row to one cell
 constexpr int64_t SK_BLOCK_ROWS = 1ll << 14;      // rows of a workgroup: one LDS table is zeroed and flushed per that many rows
 constexpr size_t SK_LDS_BYTES = 160 * 1024;       // LDS of a CU (a single workgroup may take all of it)
-constexpr int SK_LO_BITS = 40;
 constexpr unsigned long long SK_NEVER = ~0ull;
-typedef unsigned long long u64;
 
 struct KmerArgs {
   MuralGenome g;
@@ -70,34 +68,6 @@ size_t lds_bytes_of(int k, int n_class) { return ((size_t)1 << (2 * k)) * (size_
 // atomic that was not needed, never one that was.
 __device__ __forceinline__ void global_first(u64* __restrict__ first, int64_t key, u64 ord) {
   if (first[key] > ord) atomicMin(&first[key], ord);
-}
-
-// The checks of a row (status bits, 0 if it counts) and its probabilities as the two limbs.
-template <typename T>
-__device__ __forceinline__ int32_t quantise_row(const T* __restrict__ prob, int nc, int64_t st, int lab, u64 (&hi)[SK_MAX_CLASS],
-                                                u64 (&lo)[SK_MAX_CLASS]) {
-  int32_t bad_row = 0;
-  if (st < 0) bad_row |= SM_BAD_START;
-  if (lab < 0 || lab >= nc) bad_row |= SM_BAD_LABEL;
-#pragma unroll
-  for (int c = 0; c < SK_MAX_CLASS; ++c) {
-    hi[c] = 0, lo[c] = 0;
-    if (c < nc) {
-      const double p = (double)prob[c];      // (float -> double is exact)
-      // 0 <= p <= 1 on the bit pattern -- non-negative doubles order like their bits --, so that NaN is caught whatever the
-      // compiler assumes about comparisons; -0.0 counts as 0
-      const u64 bits = (u64)__double_as_longlong(p);
-      if (bits > 0x3FF0000000000000ull && bits != 0x8000000000000000ull) {
-        bad_row |= SM_BAD_PROB;
-      } else {
-        const double s = p * 2147483648.0;                       // p * 2^31
-        const double h = floor(s);
-        hi[c] = (u64)(long long)h;
-        lo[c] = (u64)(long long)rint((s - h) * 1099511627776.0);      // * 2^40, half to even
-      }
-    }
-  }
-  return bad_row;
 }
 
 // One row into the cell of `key`: cells = an LDS table's [3 n_class + 1] per key (the last the first-appearance word) when in_lds,

@@ -1,6 +1,7 @@
 """Genome summaries reduced in flight from the shards of a file-level prediction: the numpy "host twins" that specify the device
-reductions (csrc/summary.hip, csrc/summary_kmer.hip, csrc/summary_calib.hip) and ``SummarySink``, the shard consumer that runs one
-reducer per summary kind -- window tables and totals, k-mer tables, motif tables, calibration metrics with the calibrator fit."""
+reductions (csrc/summary.hip, csrc/summary_kmer.hip, csrc/summary_calib.hip, csrc/summary_annot.hip) and ``SummarySink``, the shard
+consumer that runs one reducer per summary kind -- window tables and totals, k-mer tables, motif tables, calibration metrics with the
+calibrator fit, annotation tables."""
 import ctypes as C
 import os
 
@@ -12,9 +13,9 @@ from . import _lib
 from .calibration import calibrate_device, dirichlet_calibrate, save_dirichlet_calibrator
 from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
 from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds, shard_name, strand_u8
-from .tables import (check_kmer_length, check_motif_length, kmer_name, kmer_output_names, motif_output_names, mu_scaling_factor,
-                     print_scaling_factor, read_regions, regional_output_names, strand_mode, write_kmer_outputs, write_motif_outputs,
-                     write_regional_outputs)
+from .tables import (annotation_meta, annotation_output_names, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
+                     motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
+                     strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs)
 
 
 def _refuse_fit_on_calibrated(calibrated):
@@ -300,6 +301,58 @@ def _revdigits(key, m):
     out = 0
     for _ in range(m):
         out, key = out * 4 + (key & 3), key >> 2
+    return out
+
+
+# ---- annotation tables (csrc/summary_annot.hip: mural_summary_annot_rows): the k-mer cells per named interval set ----------------------
+_ANNOT_SLICE_ROWS = 1 << 20        # rows of one prefix-sum slice here (any size below 2^23 keeps the unfolded lo prefixes below 2^63)
+_ANNOT_FOLD_PIECES = 1 << 20       # pieces between two folds of the table: lo < 2^40 + 2^20 * 2^40
+
+
+def summary_annot_host(prob, start, label, n_class, pieces, n_groups, into=None):
+    """The numpy twin of ``mural_summary_annot_rows`` -- and its specification -- for rows (any order) of one chromosome:
+    (table uint64 [n_groups][3][n_class] of label counts | sums of hi | sums of lo, status).  `pieces`: the chromosome's (b0, b1, group)
+    of ``tables.read_annotations`` (or None); a row adds to the cells of piece p's group when b0[p] <= start < b1[p] -- the pieces of one
+    group are disjoint, so once per group that covers it.  The rows are sorted by start, a piece's rows are the range between the lower
+    bounds of its two ends, its sums the difference of two prefix sums: integer sums of the limbs of ``kmer_quantise``, so the table is a
+    function of the SET of rows alone, bit for bit; on return lo < 2^40.  `into`: the table of earlier parts (and chromosomes) to add
+    to, in place.  Status bits as ``summary_kmer_host`` (1, 2, 8); such rows are skipped."""
+    nc, ng = int(n_class), int(n_groups)
+    start = np.asarray(start, np.int64)
+    hi, lo, lab, ok, status = _kmer_row_checks(prob, start, label, nc)
+    table = np.zeros((ng, 3, nc), np.uint64) if into is None else into
+    if pieces is None or len(pieces[0]) == 0:
+        return table, status
+    b0, b1, grp = (np.asarray(x) for x in pieces)
+    order = np.argsort(start[ok], kind="stable")
+    hi, lo, start, lab = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order]
+    for r0 in range(0, len(start), _ANNOT_SLICE_ROWS):
+        r = slice(r0, r0 + _ANNOT_SLICE_ROWS)
+        st = start[r]
+        prefix = np.zeros((len(st) + 1, 3, nc), np.uint64)
+        np.cumsum(lab[r][:, None] == np.arange(nc)[None, :], axis=0, dtype=np.uint64, out=prefix[1:, 0])
+        np.cumsum(hi[r], axis=0, dtype=np.uint64, out=prefix[1:, 1])
+        np.cumsum(lo[r], axis=0, dtype=np.uint64, out=prefix[1:, 2])
+        i0 = np.searchsorted(st, b0, "left")
+        i1 = np.maximum(np.searchsorted(st, b1, "left"), i0)
+        live = np.nonzero(i1 > i0)[0]
+        for q0 in range(0, len(live), _ANNOT_FOLD_PIECES):
+            q = live[q0:q0 + _ANNOT_FOLD_PIECES]
+            np.add.at(table, grp[q], _kmer_fold(prefix[i1[q]] - prefix[i0[q]]))
+            _kmer_fold(table)
+    return table, status
+
+
+def annot_table_from_sums(table, n_class):
+    """table float64 [n_groups][1 + 2 n_class] of rows / per-class counts / per-class probability sums from the integer sums of
+    ``summary_annot_host`` / ``mural_summary_annot_rows``: a probability sum is (hi * 2^40 + lo) / 2^71, formed from Python integers."""
+    nc = int(n_class)
+    out = np.zeros((table.shape[0], 1 + 2 * nc))
+    out[:, 1:1 + nc] = table[:, 0]
+    out[:, 0] = table[:, 0].sum(axis=1)
+    den = 1 << (_KMER_HI_BITS + _KMER_LO_BITS)
+    hi, lo = table[:, 1].ravel().tolist(), table[:, 2].ravel().tolist()      # (one flat pass: there may be 10^5 names)
+    out[:, 1 + nc:] = np.array([((h << _KMER_LO_BITS) + l) / den for h, l in zip(hi, lo)], np.float64).reshape(table.shape[0], nc)
     return out
 
 
@@ -759,6 +812,86 @@ class _KeyedReducer:
             self.kind["write"](*result[self.name][n], k, n, out_prefix)
 
 
+class _AnnotationReducer:
+    """Expected and observed mutations per name of an annotation BED (``tables.read_annotations``): ONE integer table [names][3][n_class]
+    for the whole run on the host and one per device -- the group ids are global --, a chromosome's pieces uploaded the first time the
+    chromosome arrives on a device, read back once.  A chromosome without pieces reduces nothing."""
+    name = "annotations"
+
+    def __init__(self, annotations):
+        self.names, self.meta, self.pieces = read_annotations(annotations)
+        if len(self.names) >= 2 ** 31:
+            raise ValueError("annotations: 2^31 names or more")
+        self.reset()
+
+    def reset(self):
+        self.host = None               # table uint64 [names][3][n_class] of the host shards
+        self.dev = {}                  # device -> dict(table, status, pieces {chromosome: (b0, b1, group)}, ws)
+        self.sums = None
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        pieces = self.pieces.get(name)
+        if pieces is None:
+            return 0
+        if self.host is None:
+            self.host = np.zeros((len(self.names), 3, k), np.uint64)
+        return summary_annot_host(prob, start, label, k, pieces, len(self.names), into=self.host)[1]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the reduction of a part behind its forward, into the device's one table."""
+        pieces = self.pieces.get(name)
+        if pieces is None or start.shape[0] == 0:
+            return None
+        dev, lib = prob.device, _lib.lib()
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(len(self.names) * 3 * k, dtype=torch.int64, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev), pieces={}, ws=None)
+        on_dev = acc["pieces"].get(name)
+        if on_dev is None:             # from pinned memory, behind the work already enqueued: a pageable copy would wait for the forward
+            pinned = tuple(torch.from_numpy(np.ascontiguousarray(x)).pin_memory() for x in pieces)
+            on_dev = acc["pieces"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+        need = int(lib.mural_summary_annot_workspace_bytes(start.shape[0], k))
+        if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+            acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+        s = _lib.MuralSummaryAnnotRows()
+        s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0)
+        s.start, s.label, s.label_kind = start.data_ptr(), label.data_ptr(), _LABEL_KIND[label.dtype]
+        s.n, s.n_class, s.n_groups = start.shape[0], k, len(self.names)
+        s.piece_b0, s.piece_b1, s.piece_group, s.n_pieces = (on_dev[0].data_ptr(), on_dev[1].data_ptr(), on_dev[2].data_ptr(),
+                                                             on_dev[0].shape[0])
+        s.table, s.status = acc["table"].data_ptr(), acc["status"].data_ptr()
+        _lib.check(lib.mural_summary_annot_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+        return None
+
+    def _added(self, tables):
+        """Integer tables added, carries folded; None where there is none."""
+        out = None
+        for t in tables:
+            if t is not None:
+                out = t.copy() if out is None else _kmer_fold(np.add(out, t, out=out))
+        return out
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, mine = 0, [self.host]
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine.append(acc["table"].cpu().numpy().view(np.uint64).reshape(len(self.names), 3, k))
+        return self._added(mine), status
+
+    def merge(self, states, k):
+        return self._added(states)
+
+    def finish(self, state, k, result):
+        self.sums = np.zeros((len(self.names), 3, k or 0), np.uint64) if state is None else state
+        result[self.name] = (list(self.names), annotation_meta(self.names, self.meta), annot_table_from_sums(self.sums, k or 0))
+
+    def write(self, out_prefix, result, k, written):
+        written += list(annotation_output_names(out_prefix))
+        write_annotation_outputs(*result[self.name], k, out_prefix)
+
+
 class _CalibrationReducer:
     """The integer tables behind NLL / ECE / classwise ECE / Brier per chromosome and, with `fit_calibrator`, the retained rows and the
     calibrator fit on them at close()."""
@@ -1004,6 +1137,17 @@ class SummarySink:
     `fit_row_terms`: (prob, label, weights, need_hessian) -> (loss, gradient, Hessian) SUMS over the given rows, a stand-in for the
     device kernel that keeps host shards on the host (tests without a device).
 
+    `annotations`: a BED path or ``tables.read_annotations``' result: per NAME of the file (column 4; the exons of a gene share one) the
+    observed mutations and the expected ones -- the label counts and the probability sums of the rows whose start lies in one of the
+    name's intervals, which may be unsorted, overlap and nest --, alone or beside the other summaries; no `genome` is needed.  Device
+    parts go through ``mural_summary_annot_rows`` (csrc/summary_annot.hip; DESIGN.md section 3.19: row prefix sums and one lookup per
+    merged piece), host shards through ``summary_annot_host``: one integer table for the run, read back once at close(), exchanged
+    between ranks in the same collective and added -- a function of the set of rows alone, bit for bit.  result()["annotations"] =
+    (names, meta int64 [n][2] of n_intervals / length, table float64 [n][1 + 2 n_class] of rows / per-class counts / per-class
+    probability sums); a name whose chromosomes never arrive stays, with zeros.  close() writes
+    ``{out_prefix}.annotation.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_annotation_outputs``); ``annotation_sums()`` has the
+    integers.
+
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
 
@@ -1011,7 +1155,7 @@ class SummarySink:
 
     def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
                  group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
-                 calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None):
+                 calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -1030,6 +1174,9 @@ class SummarySink:
         self.calibration, self.calibration_bins = metrics.active, metrics.n_bins
         # the reducers of the summaries asked for, in the order of their files; the totals go with the windows, so those always run
         active = [by_window] + [r for r, on in ((by_kmer, self.kmers), (by_motif, self.motifs), (metrics, self.calibration)) if on]
+        self.annotations = annotations is not None
+        if self.annotations:
+            active.append(_AnnotationReducer(annotations))
         self._reducers = {r.name: r for r in active}
         self.rows = 0
         self._n_class = None
@@ -1170,6 +1317,12 @@ class SummarySink:
         (``summary_motif_host``'s layout, the chromosome's ordinal by name above each first-appearance word)."""
         self.result()
         return self._reducers["motifs"].sums
+
+    def annotation_sums(self):
+        """table uint64 [names][3][n_class] of label counts | sums of hi | sums of lo after close(): the exact sums behind
+        result()["annotations"] (``summary_annot_host``'s layout, the names in ``read_annotations``' order)."""
+        self.result()
+        return self._reducers["annotations"].sums
 
     def calibration_sums(self):
         """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind

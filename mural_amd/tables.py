@@ -528,6 +528,161 @@ def write_motif_outputs(names, table, n_class, motif_length, out_prefix):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# annotations: expected and observed mutations per named interval set (the exons of a gene, an enhancer set)
+# ------------------------------------------------------------------------------------------------------------------
+def annotation_output_names(out_prefix):
+    return f"{out_prefix}.annotation.mut_rates.tsv", f"{out_prefix}.annotation.corr.txt"
+
+
+def _annotation_rows(source):
+    """(chrom, start, end, name or None, where) of a BED file (plain or gzip; the lines ``read_regions`` skips are skipped) or of a dict
+    {chrom: [(start, end[, name])]}."""
+    if isinstance(source, dict):
+        for chrom, items in source.items():
+            for j, item in enumerate(items):
+                yield str(chrom), int(item[0]), int(item[1]), (str(item[2]) if len(item) > 2 else None), f"annotations[{chrom!r}][{j}]"
+        return
+    path = os.fspath(source)
+    opener = gzip.open if _is_gzip(path) else open
+    with opener(path, "rt") as fh:
+        for ln, line in enumerate(fh, 1):
+            if not line.strip() or line.startswith(("#", "track", "browser")):
+                continue
+            f = line.rstrip("\r\n").split("\t")
+            if len(f) < 3:
+                raise ValueError(f"{path}:{ln}: a BED row needs chrom, start and end")
+            yield f[0], int(f[1]), int(f[2]), (f[3] if len(f) > 3 and f[3] else None), f"{path}:{ln}"
+
+
+def read_annotations(source):
+    """(names, meta, pieces) of an annotation BED (a path, plain or gzip; a dict {chrom: [(start, end[, name])]}; or this function's own
+    result, returned as it is).  Columns 1-3 are required, column 4 is the NAME of the row's interval set (``chrom:start-end`` where
+    there is none); rows may be unsorted, overlap and nest, many rows may share a name (the exons of a gene), and a name may occur on
+    several chromosomes.  ``start < 0`` or ``end <= start`` raises ValueError with file and line.
+      names: in order of first appearance;
+      meta[name] = (n_intervals, length): the input rows of the name, and the bases of the union of its intervals summed over chromosomes;
+      pieces[chrom] = (b0 int64, b1 int64, group int32), sorted by (b0, b1, group): each name's intervals on that chromosome merged into
+        disjoint pieces that do not touch, `group` the name's index in `names`; pieces of different names overlap freely.
+    A prediction row belongs to a piece when b0 <= row.start < b1 (BED half-open on the row's own position): at most once per name, and
+    once for every name that covers it.  The list is small: host work."""
+    if isinstance(source, tuple) and len(source) == 3 and isinstance(source[2], dict):
+        return source
+    index, counts, per_chrom = {}, [], {}
+    for chrom, a, b, name, where in _annotation_rows(source):
+        if a < 0:
+            raise ValueError(f"{where}: a negative start ({a})")
+        if b <= a:
+            raise ValueError(f"{where}: end {b} is not above start {a}")
+        name = f"{chrom}:{a}-{b}" if name is None else name
+        g = index.setdefault(name, len(index))
+        if g == len(counts):
+            counts.append(0)
+        counts[g] += 1
+        per_chrom.setdefault(chrom, []).append((g, a, b))
+    names = list(index)
+    length = [0] * len(names)
+    pieces = {}
+    for chrom, rows in per_chrom.items():
+        rows.sort()
+        merged = []
+        for g, a, b in rows:
+            if merged and merged[-1][2] == g and a <= merged[-1][1]:      # overlaps or touches the name's piece before it
+                merged[-1][1] = max(merged[-1][1], b)
+            else:
+                merged.append([a, b, g])
+        merged.sort()
+        arr = np.asarray(merged, np.int64).reshape(-1, 3)
+        for a, b, g in merged:
+            length[g] += b - a
+        pieces[chrom] = (arr[:, 0].copy(), arr[:, 1].copy(), arr[:, 2].astype(np.int32))
+    return names, {nm: (counts[g], length[g]) for g, nm in enumerate(names)}, pieces
+
+
+def annotation_meta(names, meta):
+    """int64 [n][2] of (n_intervals, length) in `names` order."""
+    return np.asarray([meta[nm] for nm in names], np.int64).reshape(-1, 2)
+
+
+def annotation_table(pred_file, annotations, n_class, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, meta int64 [n][2], table float64 [n][1 + 2 n_class] of rows / per-class counts / per-class probability sums) per name of
+    `annotations` (a BED path or ``read_annotations``' result) from a written prediction table: what ``SummarySink(annotations=...)``
+    reduces in flight, through the same entry point (``mural_summary_annot_rows``), chromosome run by chromosome run of each chunk.
+    The rows of a chromosome must ascend in start, as ``predict`` writes them; no genome is read."""
+    from .summaries import _SUMMARY_STATUS, annot_table_from_sums      # (summaries imports this module: not at the top)
+    names, meta, pieces = read_annotations(annotations)
+    if not 1 <= int(n_class) <= 8:
+        raise ValueError("the annotation tables take 1 .. 8 classes")
+    lib = _lib.lib()
+    n_groups = len(names)
+    with TableReader(pred_file, n_class, chunk_bytes) as rd:
+        dev = rd.device
+        table = torch.zeros(max(n_groups, 1) * 3 * n_class, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        on_dev, ws = {}, None
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in pieces or b == a:
+                    continue
+                if name not in on_dev:
+                    on_dev[name] = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in pieces[name])
+                b0, b1, grp = on_dev[name]
+                need = int(lib.mural_summary_annot_workspace_bytes(b - a, n_class))
+                if ws is None or ws.numel() * 8 < need:
+                    ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+                s = _lib.MuralSummaryAnnotRows()
+                s.prob, s.prob_f64, s.prob_stride = c.prob + 8 * n_class * a, 1, n_class
+                s.start, s.label, s.label_kind = c.start + 8 * a, c.mut_type + 4 * a, 1
+                s.n, s.n_class, s.n_groups = b - a, n_class, n_groups
+                s.piece_b0, s.piece_b1, s.piece_group, s.n_pieces = b0.data_ptr(), b1.data_ptr(), grp.data_ptr(), b0.shape[0]
+                s.table, s.status = table.data_ptr(), status.data_ptr()
+                _lib.check(lib.mural_summary_annot_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, _lib.current_stream_ptr(dev)))
+        bits = int(status.item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        sums = table.cpu().numpy().view(np.uint64)[:n_groups * 3 * n_class].reshape(n_groups, 3, n_class)
+    return names, annotation_meta(names, meta), annot_table_from_sums(sums, n_class)
+
+
+def write_annotation_outputs(names, meta, table, n_class, out_prefix):
+    """The two files of an annotation summary (``annotation_table``'s triple, or the one a ``SummarySink`` reduced in flight):
+    ``{out_prefix}.annotation.mut_rates.tsv`` -- name, n_intervals, length, number_of_all, the observed number_of_mut{c} and the
+    expected_mut{c} (the probability sums) per class c >= 1, a row per name in `names` order -- and ``.annotation.corr.txt``, the Pearson
+    r of observed against expected over the names with a row.  Returns [(class, (r, p))]."""
+    cls = range(1, n_class)
+    table = np.asarray(table, np.float64).reshape(len(names), 1 + 2 * n_class)
+    header = (["name", "n_intervals", "length", "number_of_all"] + [f"number_of_mut{c}" for c in cls] + [f"expected_mut{c}" for c in cls])
+    rows = [[nm, str(int(meta[j][0])), str(int(meta[j][1])), str(int(table[j, 0]))] + [str(int(table[j, 1 + c])) for c in cls]
+            + [_float_text(table[j, 1 + n_class + c]) for c in cls] for j, nm in enumerate(names)]
+    used = table[:, 0] > 0
+    corrs = []
+    for c in cls:
+        obs, exp = table[used, 1 + c], table[used, 1 + n_class + c]
+        if len(obs) < 2 or np.ptp(obs) == 0 or np.ptp(exp) == 0:      # (no labels: every observed column is zero)
+            corrs.append((c, (float("nan"), float("nan"))))
+        else:
+            corrs.append((c, pearson(obs, exp)))
+    rates_path, corr_path = annotation_output_names(out_prefix)
+    with open(rates_path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    with open(corr_path, "w") as fh:
+        fh.write(_corr_text("annotation", corrs))
+    return corrs
+
+
+def run_annotation_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.annotations, args.n_class, args.out_prefix): per name of the annotation BED
+    the observed and expected mutations of the table's rows inside its intervals; writes {out_prefix}.annotation.mut_rates.tsv and
+    .corr.txt."""
+    assert getattr(args, "annotations", None) is not None, "--annotations is required for the annotation table"
+    names, meta, table = annotation_table(os.fspath(args.pred_file), args.annotations, args.n_class, chunk_bytes)
+    return write_annotation_outputs(names, meta, table, args.n_class, args.out_prefix)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # evaluate: regional
 # ------------------------------------------------------------------------------------------------------------------
 _MAX_CHUNK_WINDOWS = 1 << 24

@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Ten legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Twelve legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -17,8 +17,12 @@ alternating, --repeats timed runs each after one warm-up run each:
   j  calib_fit   leg b with fit_calibrator="FullDiri" and a synthetic mutation list (every 100th site, classes 1 .. 3 in turn) so that
                  every class occurs: the rows retained on the device, the fit and the metrics after it at close(); reports close()
                  seconds, the retained bytes and the leg's peak device memory
-Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's and leg g's motif tables with leg
-h's, within the table's four digits (names, order and counts exactly)."""
+  k  annot       leg b with annotations= as well: expected and observed mutations per name of a synthetic
+                 annotation file -- 20 000 names x 10 intervals of 150 bp spread over the chromosome, 5 % of the names overlapping a
+                 neighbour --; the comparison is leg b, the same run without it
+  l  annot_tools the route to k's table without the sink: leg a's table, then tables.annotation_table on it
+Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
+h's and leg k's annotation table with leg l's, within the table's four digits (names, order and counts exactly)."""
 import json
 import os
 import shutil
@@ -40,7 +44,21 @@ from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, pr
 WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
-LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit")
+LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools")
+ANNOT_NAMES, ANNOT_INTERVALS, ANNOT_BP, ANNOT_OVERLAP = 20_000, 10, 150, 0.05
+
+
+def synthetic_annotations(bases, chrom="chr1"):
+    """``tables.read_annotations``' result for ANNOT_NAMES names of ANNOT_INTERVALS intervals of ANNOT_BP bases each, a name per equal
+    span of the chromosome; every 20th name is moved half a span up, into its neighbour's intervals."""
+    span = bases // ANNOT_NAMES
+    step = max(span // ANNOT_INTERVALS, 1)
+    every = int(round(1 / ANNOT_OVERLAP))
+    rows = []
+    for g in range(ANNOT_NAMES):
+        at = g * span + (span // 2 if g % every == every - 1 else 0)
+        rows += [(at + j * step, at + j * step + ANNOT_BP, "set%05d" % g) for j in range(ANNOT_INTERVALS)]
+    return tables.read_annotations({chrom: rows})
 
 
 def main(argv):
@@ -60,7 +78,8 @@ def main(argv):
         del genome
         torch.cuda.empty_cache()
         out = os.path.join(work, "table.tsv")
-        kept = {}
+        kept, closes = {}, {}
+        annot = synthetic_annotations(bases) if {"annot", "annot_tools"} & set(legs) else None
 
         def run(leg):
             split, extra = {}, {}
@@ -74,6 +93,18 @@ def main(argv):
                 summary = SummarySink(windows=WINDOWS, motifs=MOTIFS, genome=fwd.genome)
             if leg == "calib":
                 summary = SummarySink(windows=WINDOWS, calibration=True)
+            if leg == "annot":
+                summary = SummarySink(windows=WINDOWS, annotations=annot)
+            if leg in ("summary", "annot") and "annot" in legs:      # close() alone, of every run: where leg k's host work would be
+                plain_close = summary.close
+
+                def close_timed():
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    plain_close()
+                    torch.cuda.synchronize()
+                    closes.setdefault(leg, []).append(time.perf_counter() - t1)
+                summary.close = close_timed
             if leg == "calib_fit":
                 torch.cuda.reset_peak_memory_stats(device)
                 summary = SummarySink(windows=WINDOWS, fit_calibrator="FullDiri")
@@ -89,7 +120,7 @@ def main(argv):
                 summary.close = timed_close
             sink = {"calib": lambda: summary, "calib_fit": lambda: summary, "table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
-                    "motif_tools": lambda: TsvSink(out)}[leg]()
+                    "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out)}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
                                         **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
@@ -118,6 +149,10 @@ def main(argv):
                     t1 = time.perf_counter()
                     kept["motif_tools"][m] = tables.motif_table(out, fa, m, n_class, "snv")
                     extra["motif_table_%d" % m] = time.perf_counter() - t1
+            if leg == "annot_tools":
+                t1 = time.perf_counter()
+                kept["annot_tools"] = tables.annotation_table(out, annot, n_class)
+                extra["annotation_table"] = time.perf_counter() - t1
             dt = time.perf_counter() - t0
             assert n == rows, (leg, n, rows)
             if summary is not None:
@@ -148,6 +183,10 @@ def main(argv):
         for m in MOTIFS:
             (na, ta), (nd, td) = kept["motifs"]["motifs"][m], kept["motif_tools"][m]
             agree = agree and na == nd and bool((ta[:, :k] == td[:, :k]).all()) and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all())
+    if {"annot", "annot_tools"} <= set(legs):
+        (na, ma, ta), (nd, md, td) = kept["annot"]["annotations"], kept["annot_tools"]
+        agree = agree and na == nd and bool((ma == md).all()) and bool((ta[:, :k] == td[:, :k]).all())
+        agree = agree and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all()) and bool(ta[:, 0].sum() > 0)
     rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in legs}
     med = {leg: rate[leg]["median"] for leg in legs}
     sec = {leg: statistics.median(seconds[leg]) for leg in legs}
@@ -160,6 +199,10 @@ def main(argv):
            "motifs": list(MOTIFS), "motifs_over_summary": ratio("motifs", "summary", med),
            "motif_tools_over_motifs_seconds": ratio("motif_tools", "motifs", sec),
            "calib_over_summary": ratio("calib", "summary", med), "calib_fit_over_summary": ratio("calib_fit", "summary", med),
+           "annot_over_summary": ratio("annot", "summary", med), "annot_tools_over_annot_seconds": ratio("annot_tools", "annot", sec),
+           "annotations": {"names": ANNOT_NAMES, "intervals": ANNOT_INTERVALS, "bp": ANNOT_BP,
+                           "close_seconds": {leg: v[1:] for leg, v in closes.items()},      # (without the warm-up round's)
+                           "rows_in_a_piece": float(kept["annot"]["annotations"][2][:, 0].sum()) if "annot" in kept else None},
            "calibration": {leg: {key: val for key, val in kept[leg]["calibration"].items() if key not in ("per_chromosome", "weights")}
                            for leg in ("calib", "calib_fit") if leg in kept},
            "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}

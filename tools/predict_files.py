@@ -35,6 +35,10 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              write PREFIX.fdiri_cal.pkl and the metrics after it; the run itself is not
                                                              calibrated (not with --scale_factor, --poisson / --indel's Poisson step;
                                                              a MODEL.fdiri_cal.pkl next to the model needs --no-calibration)
+  --summary PREFIX  --annotations BED                      PREFIX.annotation.mut_rates.tsv and .corr.txt: per name (column 4 of the
+                                                             BED; the exons of a gene share one) the observed mutations and the
+                                                             expected ones, the sums of the probabilities over the rows inside the
+                                                             name's intervals; alone or with the options above
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -48,7 +52,7 @@ from mural_amd.calibration import load_dirichlet_weights  # noqa: E402
 from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
-_SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
+_SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--annotations", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
                     "--scale_factor", "--n_bins", "--fit_calibrator")
 _PAIR_OPTIONS = ("--model_set", "--scale_factors")      # NAME CLASS=VALUE [CLASS=VALUE ..]
 _VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _PAIR_OPTIONS + _SUMMARY_OPTIONS
@@ -133,7 +137,7 @@ def _summary_options(flags, values, model_type="snv"):
             "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags,
             "kmers": tuple(int(k) for k in values.get("--kmer_length", [])), "strand": one("--strand", str),
             "motifs": tuple(int(m) for m in values.get("--motif_length", [])), "calibration": "--calibration_metrics" in flags,
-            "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str)}
+            "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str), "annotations": one("--annotations", str)}
     if opts["calibration"] and opts["summary"] is None:
         raise SystemExit("--calibration_metrics needs --summary PREFIX: the prefix of the file it writes")
     if (opts["n_bins"] is not None or opts["fit_calibrator"] is not None) and not opts["calibration"]:
@@ -153,8 +157,17 @@ def _summary_options(flags, values, model_type="snv"):
         raise SystemExit("--kmer_length needs --summary PREFIX: the prefix of the files it writes")
     if opts["motifs"] and opts["summary"] is None:
         raise SystemExit("--motif_length needs --summary PREFIX: the prefix of the files it writes")
-    if opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"] and not opts["calibration"]:
-        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length or --calibration_metrics")
+    if opts["annotations"] is not None and opts["summary"] is None:
+        raise SystemExit("--annotations needs --summary PREFIX: the prefix of the files it writes")
+    if (opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"] and not opts["calibration"]
+            and opts["annotations"] is None):
+        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics or --annotations")
+    if opts["annotations"] is not None:
+        from mural_amd.tables import read_annotations
+        try:
+            opts["annotations"] = read_annotations(opts["annotations"])
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--annotations: {e}") from None
     if opts["motifs"]:
         from mural_amd.tables import check_motif_length
         try:
@@ -210,7 +223,7 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               kmer_strand=opts["strand"] if model_type == "indel" else None, motifs=opts["motifs"],
                               motif_indel=model_type == "indel", calibration=opts["calibration"],
                               calibration_bins=50 if opts["n_bins"] is None else opts["n_bins"], fit_calibrator=opts["fit_calibrator"],
-                              **sink_chain)
+                              annotations=opts["annotations"], **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
