@@ -856,6 +856,81 @@ size_t mural_summary_annot_workspace_bytes(int64_t n, int32_t n_class);
 int mural_summary_annot_rows(const MuralSummaryAnnotRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Mutation sets drawn from the rates of a shard while it is on the device (SummarySink(simulate=R, ...) in flight,
+ * tables.simulate_table from a written table; csrc/simulate.hip).  The draw is stateless and integer
+ * (mural_amd.summaries.simulate_rows_host is its specification): Philox4x32-10 with key (seed lo, seed hi) and counter
+ * (start lo, start hi, chrom_key, (replicate >> 2) | (strand << 31)), replicate r reading output word r & 3 as u;
+ * q_c = floor(double(p_c) * 2^32) (2^32 from p_c = 1 on) for c = 1 .. n_class - 1, cum_c = min(q_1 + .. + q_c, 2^32); the
+ * class of the row is the smallest c >= 1 with u < cum_c, 0 where there is none (class 0's probability is never read).
+ * A draw depends on (seed, chrom_key, start, strand, replicate) alone -- not on the row's index --, so every output is a
+ * function of the SET of rows, bit for bit, for any split into calls; two rows with equal chrom_key, start and strand
+ * draw the same value.  chrom_key: crc32 of the chromosome's name (the caller forms it).  strand: dev uint8 [n], non-zero
+ * for '-', or NULL for all '+'.  status (device int32, bits as mural_summary_kmer_rows): bit 3 a probability of a class
+ * >= 1 that is NaN, negative or infinite, bit 0 a negative start -- such rows draw class 0 in every replicate --, bit 2
+ * (mural_simulate_annot_rows only) a start below the row before it inside the call.  2 <= n_class <= 8.
+ *
+ * mural_simulate_annot_rows: rows and pieces as mural_summary_annot_rows (one chromosome, start ascending; no label).
+ *   table [n_groups][n_class - 1][n_rep] of unsigned 32-bit cells: cell [g][c - 1][r] += the rows inside the pieces of
+ *   group g whose replicate-r draw is class c (a row counts once per group that covers it); zeroed by the caller once,
+ *   it accumulates over calls, parts and chromosomes.  1 <= n_rep <= mural_simulate_max_replicates() = 2^20.
+ *   A piece's rows are one range of start (two lower bounds); the ranges are cut into chunks of at most
+ *   mural_simulate_chunk_rows() rows, listed by an exclusive scan of the chunk counts (one workgroup of
+ *   mural_simulate_scan_threads() threads, a run of pieces each), and a grid of at most mural_simulate_grid_waves() waves
+ *   strides over the (chunk, block of 64 replicates) units: a row per lane, four replicates per Philox call, hits counted
+ *   by ballot and popcount, one 32-bit INTEGER atomic wave-instruction of 64 contiguous replicates per class and chunk.
+ *   ws: mural_simulate_annot_workspace_bytes(n_pieces) bytes (24 per piece), 8-byte aligned; MURAL_E_WORKSPACE when
+ *   smaller.  n == 0 launches nothing; n_pieces == 0 only checks the rows.
+ * mural_simulate_rows: replicate `replicate` of the rows as a mutation list -- the rows whose draw is not 0, compacted
+ *   in row order (stable): out_start / out_strand / out_label [n] hold *count entries (count: dev int64, SET, not added
+ *   to).  ws: mural_simulate_rows_workspace_bytes(n) bytes (8 per 64 rows); MURAL_E_WORKSPACE when smaller.  n == 0
+ *   launches nothing and leaves *count as it is.
+ * Both launch on `stream`: no synchronisation, no read-back, no floating-point atomics; draws are recomputed, never
+ * stored.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. n_class-1 are read          */
+  int32_t prob_f64, n_class;
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const uint8_t* strand;     /* dev [n] or NULL */
+  int64_t n;
+  uint32_t chrom_key;
+  int32_t n_rep;
+  uint64_t seed;
+  const int64_t* piece_b0;   /* dev [n_pieces] */
+  const int64_t* piece_b1;   /* dev [n_pieces] */
+  const int32_t* piece_group; /* dev [n_pieces] */
+  int64_t n_pieces;
+  int32_t n_groups, reserved;
+  uint32_t* table;           /* dev [n_groups][n_class - 1][n_rep] */
+  int32_t* status;           /* dev [1] */
+} MuralSimulateAnnotRows;
+typedef struct {
+  const void* prob;
+  int32_t prob_f64, n_class;
+  int64_t prob_stride;
+  const int64_t* start;      /* dev [n] */
+  const uint8_t* strand;     /* dev [n] or NULL */
+  int64_t n;
+  uint32_t chrom_key;
+  int32_t replicate;
+  uint64_t seed;
+  int64_t* out_start;        /* dev [n] */
+  uint8_t* out_strand;       /* dev [n] */
+  uint8_t* out_label;        /* dev [n] */
+  int64_t* count;            /* dev [1] */
+  int32_t* status;           /* dev [1] */
+} MuralSimulateRows;
+int64_t mural_simulate_chunk_rows(void);
+int64_t mural_simulate_grid_waves(void);
+int32_t mural_simulate_scan_threads(void);
+int32_t mural_simulate_max_replicates(void);
+size_t mural_simulate_annot_workspace_bytes(int64_t n_pieces);
+int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* ws, size_t ws_bytes, void* stream);
+size_t mural_simulate_rows_workspace_bytes(int64_t n);
+int mural_simulate_rows(const MuralSimulateRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

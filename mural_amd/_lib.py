@@ -128,6 +128,20 @@ class MuralSummaryAnnotRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSimulateAnnotRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
+                ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("n_rep", C.c_int32), ("seed", C.c_uint64),
+                ("piece_b0", C.c_void_p), ("piece_b1", C.c_void_p), ("piece_group", C.c_void_p), ("n_pieces", C.c_int64),
+                ("n_groups", C.c_int32), ("reserved", C.c_int32), ("table", C.c_void_p), ("status", C.c_void_p)]
+
+
+class MuralSimulateRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
+                ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("replicate", C.c_int32), ("seed", C.c_uint64),
+                ("out_start", C.c_void_p), ("out_strand", C.c_void_p), ("out_label", C.c_void_p), ("count", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
 
 # every symbol include/mural_hip.h declares: name -> (restype, argtypes)
@@ -284,6 +298,14 @@ PROTOTYPES = {
     "mural_summary_annot_fold_pieces": (I64, []),
     "mural_summary_annot_workspace_bytes": (C.c_size_t, [I64, I32]),
     "mural_summary_annot_rows": (C.c_int, [C.POINTER(MuralSummaryAnnotRows), VP, C.c_size_t, VP]),
+    "mural_simulate_chunk_rows": (I64, []),
+    "mural_simulate_grid_waves": (I64, []),
+    "mural_simulate_scan_threads": (I32, []),
+    "mural_simulate_max_replicates": (I32, []),
+    "mural_simulate_annot_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_simulate_annot_rows": (C.c_int, [C.POINTER(MuralSimulateAnnotRows), VP, C.c_size_t, VP]),
+    "mural_simulate_rows_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_simulate_rows": (C.c_int, [C.POINTER(MuralSimulateRows), VP, C.c_size_t, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

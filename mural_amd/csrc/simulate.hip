@@ -1,0 +1,426 @@
+// Mutation sets drawn from the predicted rates while a prediction shard is on the device (mural_amd/summaries.py:
+// SummarySink(simulate=R, ...); tables.simulate_table from a written table): every row's class is drawn from its probabilities in each of
+// R replicates, and either counted per named interval set (mural_simulate_annot_rows: the null distribution of §3.19's observed counts)
+// or written out for one replicate as a compacted mutation list (mural_simulate_rows).
+//
+// The draw is stateless (simulate_rows_host in summaries.py is the specification): Philox4x32-10 with key (seed lo, seed hi) and counter
+// (start lo, start hi, chrom_key, (replicate >> 2) | (strand << 31)); replicate r reads output word r & 3 as u.  With
+// q_c = floor(double(p_c) * 2^32) (exact; taken as 2^32 from p_c = 1 on) and cum_c = min(q_1 + .. + q_c, 2^32), the class is the smallest
+// c >= 1 with u < cum_c and 0 where there is none.  A draw depends on (seed, chromosome, start, strand, replicate) alone, so every table
+// is a function of the SET of rows, bit for bit, whatever the parts, chunks or ranks.  All state is integer; draws are recomputed where
+// they are needed and never stored.
+//
+// mural_simulate_annot_rows, per call:
+//   * check kernel, a thread per row: the status bits (a bad probability, a negative start, a start below the row before it);
+//   * range kernel, a wave per piece: its rows [i0, i1) by two 64-ary searches in start, and its number of CHUNKS of at most
+//     SIM_CHUNK_ROWS rows -- a long piece becomes many units of work, so it cannot serialise the launch;
+//   * scan kernel, one workgroup: the exclusive prefix of the chunk counts (chunk t belongs to the piece p with pre[p] <= t < pre[p + 1]);
+//   * draw kernel, a fixed grid of SIM_GRID_WAVES waves striding over the units (chunk, block of 64 replicates): the wave finds the
+//     chunk's piece by a 64-ary search in the prefix, walks the chunk 64 rows at a time (a row per lane, four replicates per Philox
+//     call), counts the hits of a (class, replicate) over the 64 rows by ballot + popcount and keeps the count of replicate r0 + l in
+//     lane l; after the chunk ONE wave-instruction per class adds the 64 counts -- 256 contiguous bytes -- with 32-bit INTEGER atomics.
+// mural_simulate_rows: tile counts of the non-zero labels of one replicate (a wave per 64 rows), their exclusive scan, and a second pass
+// that recomputes the labels and writes each hit at prefix + its rank among the tile's hits: stable in row order.
+// No floating-point atomics, no synchronisation, no read-back.
+#include "common.h"
+#include "kmer_key.h"
+
+namespace mural {
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int SIM_MAX_CLASS = 8;
+constexpr int SIM_THREADS = 256;
+constexpr int SIM_WAVES = SIM_THREADS / 64;
+constexpr int SIM_SCAN_THREADS = 1024;
+constexpr int64_t SIM_CHUNK_ROWS = 1024;          // rows of one unit of the draw kernel: 16 tiles of 64
+constexpr int64_t SIM_GRID_WAVES = 8192;          // waves of the draw kernel's grid; they stride over the units
+constexpr int32_t SIM_MAX_REP = 1 << 20;
+constexpr u64 SIM_ONE = 1ull << 32;
+
+struct SimRows {
+  const void* prob;
+  const int64_t* start;
+  const uint8_t* strand;      // or nullptr: all '+'
+  int64_t prob_stride;
+  int32_t n_class;
+  uint32_t chrom_key, seed_lo, seed_hi;
+  int32_t* status;
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&out)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+// cum[c - 1] of row i for c = 1 .. n_class - 1 (0 beyond, and 0 everywhere for a bad row); returns the row's status bits
+template <typename T>
+__device__ __forceinline__ int32_t row_cum(const SimRows& A, int64_t i, u64 (&cum)[SIM_MAX_CLASS - 1]) {
+  const T* __restrict__ p_row = static_cast<const T*>(A.prob) + i * A.prob_stride;
+  int32_t bad = A.start[i] < 0 ? (int32_t)SM_BAD_START : 0;
+  u64 run = 0;
+#pragma unroll
+  for (int c = 1; c < SIM_MAX_CLASS; ++c) {
+    cum[c - 1] = 0;
+    if (c < A.n_class) {
+      const double p = (double)p_row[c];      // (float -> double is exact)
+      // finite and not negative, on the bit pattern -- non-negative doubles order like their bits --, so that NaN is caught whatever
+      // the compiler assumes about comparisons; -0.0 counts as 0
+      const u64 bits = (u64)__double_as_longlong(p);
+      if (bits >= 0x7FF0000000000000ull && bits != 0x8000000000000000ull) {
+        bad |= SM_BAD_PROB;
+      } else {
+        double s = p * 4294967296.0;          // exact: a power of two
+        if (s > 4294967296.0) s = 4294967296.0;
+        run += (u64)(long long)floor(s);
+        cum[c - 1] = run < SIM_ONE ? run : SIM_ONE;
+      }
+    }
+  }
+  if (bad) {
+#pragma unroll
+    for (int c = 0; c < SIM_MAX_CLASS - 1; ++c) cum[c] = 0;
+  }
+  return bad;
+}
+
+__device__ __forceinline__ uint32_t last_counter_word(const SimRows& A, int64_t i, uint32_t block) {
+  return block | ((A.strand != nullptr && A.strand[i] != 0) ? 0x80000000u : 0u);
+}
+
+template <typename T>
+__global__ __launch_bounds__(SIM_THREADS) void simulate_check_kernel(SimRows A, int64_t n, int check_order) {
+  const int64_t i = (int64_t)blockIdx.x * SIM_THREADS + threadIdx.x;
+  int32_t bad = 0;
+  if (i < n) {
+    u64 cum[SIM_MAX_CLASS - 1];
+    bad = row_cum<T>(A, i, cum);
+    if (check_order && i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
+  }
+  if (bad) atomicOr(A.status, bad);
+}
+
+// first index of [lo, hi) where pred fails, the whole wave searching; pred holds on a prefix of the range.  A probe per lane splits the
+// range 64 ways a round; the range shrinks every round whatever the data hold, and no probe leaves it.
+template <typename Pred>
+__device__ __forceinline__ int64_t wave_partition_point(int64_t lo, int64_t hi, Pred pred) {
+  const int lane = threadIdx.x & 63;
+  while (lo < hi) {
+    const int64_t step = (hi - lo + 63) / 64;
+    const int64_t p = lo + lane * step;
+    const int holds = __popcll(__ballot(p < hi && pred(p)));
+    if (holds == 0) {
+      hi = lo;
+    } else {
+      hi = min(hi, lo + holds * step);
+      lo = lo + (holds - 1) * step + 1;
+    }
+  }
+  return lo;
+}
+
+// a wave per piece: its rows [i0, i1) and its chunk count
+__global__ __launch_bounds__(SIM_THREADS) void simulate_range_kernel(const int64_t* __restrict__ start, int64_t n,
+                                                                     const int64_t* __restrict__ b0, const int64_t* __restrict__ b1,
+                                                                     const int32_t* __restrict__ group, int32_t n_groups, int64_t n_pieces,
+                                                                     int64_t* __restrict__ row0, int64_t* __restrict__ row1,
+                                                                     int64_t* __restrict__ pre) {
+  const int64_t p = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
+  if (p >= n_pieces) return;
+  const int32_t g = group[p];
+  int64_t i0 = 0, i1 = 0;
+  if (g >= 0 && g < n_groups) {
+    const int64_t lo = b0[p], hi = b1[p];
+    i0 = wave_partition_point(0, n, [&](int64_t i) { return start[i] < lo; });
+    i1 = wave_partition_point(i0, n, [&](int64_t i) { return start[i] < hi; });
+  }
+  if ((threadIdx.x & 63) == 0) {
+    row0[p] = i0, row1[p] = i1;
+    pre[p] = (i1 - i0 + SIM_CHUNK_ROWS - 1) / SIM_CHUNK_ROWS;
+  }
+}
+
+// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total (also to *total_out where given): one workgroup, a thread owns a run
+__global__ __launch_bounds__(SIM_SCAN_THREADS) void simulate_scan_kernel(int64_t* __restrict__ v, int64_t m, int64_t* __restrict__ total_out) {
+  __shared__ int64_t wave_tot[SIM_SCAN_THREADS / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t run = (m + SIM_SCAN_THREADS - 1) / SIM_SCAN_THREADS;
+  const int64_t t0 = min((int64_t)threadIdx.x * run, m), t1 = min(t0 + run, m);
+  int64_t mine = 0;
+  for (int64_t t = t0; t < t1; ++t) mine += v[t];
+  int64_t incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int64_t up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  if (lane == 63) wave_tot[w] = incl;
+  __syncthreads();
+  int64_t base = 0, total = 0;
+#pragma unroll
+  for (int k = 0; k < SIM_SCAN_THREADS / 64; ++k) {
+    base += k < w ? wave_tot[k] : 0;
+    total += wave_tot[k];
+  }
+  int64_t running = base + incl - mine;
+  for (int64_t t = t0; t < t1; ++t) {
+    const int64_t x = v[t];
+    v[t] = running;
+    running += x;
+  }
+  if (threadIdx.x == 0) {
+    v[m] = total;
+    if (total_out) *total_out = total;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SIM_THREADS) void simulate_draw_kernel(SimRows A, const int32_t* __restrict__ group, int64_t n_pieces,
+                                                                    const int64_t* __restrict__ row0, const int64_t* __restrict__ row1,
+                                                                    const int64_t* __restrict__ pre, int32_t n_rep, int64_t n_waves,
+                                                                    uint32_t* __restrict__ table) {
+  const int lane = threadIdx.x & 63, nc = A.n_class;
+  const int64_t wave = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
+  const int64_t n_rb = (n_rep + 63) / 64;
+  const int64_t units = pre[n_pieces] * n_rb;
+  for (int64_t unit = wave; unit < units; unit += n_waves) {
+    const int64_t t = unit / n_rb;
+    const int rb = (int)(unit % n_rb);
+    // the piece of chunk t: the last p with pre[p] <= t (pre[n_pieces] = the total > t, so the point lies in 1 .. n_pieces)
+    const int64_t p = wave_partition_point(0, n_pieces + 1, [&](int64_t q) { return pre[q] <= t; }) - 1;
+    const int64_t r0 = row0[p] + (t - pre[p]) * SIM_CHUNK_ROWS;
+    const int64_t r1 = min(r0 + SIM_CHUNK_ROWS, row1[p]);
+    const int reps_here = min(64, n_rep - rb * 64);
+    const int n_blocks = (reps_here + 3) / 4;
+    uint32_t acc[SIM_MAX_CLASS - 1];
+#pragma unroll
+    for (int c = 0; c < SIM_MAX_CLASS - 1; ++c) acc[c] = 0;
+    for (int64_t row = r0; row < r1; row += 64) {
+      const int64_t i = row + lane;
+      u64 cum[SIM_MAX_CLASS - 1];
+#pragma unroll
+      for (int c = 0; c < SIM_MAX_CLASS - 1; ++c) cum[c] = 0;
+      uint32_t s_lo = 0, s_hi = 0, last = 0;
+      if (i < r1) {
+        row_cum<T>(A, i, cum);      // (the status is the check kernel's)
+        const u64 s = (u64)A.start[i];
+        s_lo = (uint32_t)s, s_hi = (uint32_t)(s >> 32);
+        last = last_counter_word(A, i, 0);
+      }
+      for (int j = 0; j < n_blocks; ++j) {
+        uint32_t u[4];
+        philox4x32_10(s_lo, s_hi, A.chrom_key, last | (uint32_t)(rb * 16 + j), A.seed_lo, A.seed_hi, u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          uint32_t below = 0;      // rows of the tile whose label is in 1 .. c - 1
+#pragma unroll
+          for (int c = 1; c < SIM_MAX_CLASS; ++c) {
+            if (c < nc) {      // (wave-uniform)
+              const uint32_t upto = (uint32_t)__popcll(__ballot((u64)u[k] < cum[c - 1]));      // cum ascends: labels 1 .. c
+              if (lane == j * 4 + k) acc[c - 1] += upto - below;
+              below = upto;
+            }
+          }
+        }
+      }
+    }
+    const int32_t g = group[p];
+    if (lane < reps_here) {
+#pragma unroll
+      for (int c = 1; c < SIM_MAX_CLASS; ++c)
+        if (c < nc && acc[c - 1]) atomicAdd(&table[((int64_t)g * (nc - 1) + (c - 1)) * n_rep + rb * 64 + lane], acc[c - 1]);
+    }
+  }
+}
+
+// the label of row i in replicate `rep`
+template <typename T>
+__device__ __forceinline__ int row_label(const SimRows& A, int64_t i, int32_t rep) {
+  u64 cum[SIM_MAX_CLASS - 1];
+  row_cum<T>(A, i, cum);
+  const u64 s = (u64)A.start[i];
+  uint32_t u[4];
+  philox4x32_10((uint32_t)s, (uint32_t)(s >> 32), A.chrom_key, last_counter_word(A, i, (uint32_t)(rep >> 2)), A.seed_lo, A.seed_hi, u);
+  const u64 mine = u[rep & 3];
+  int lab = 0;
+#pragma unroll
+  for (int c = SIM_MAX_CLASS - 1; c >= 1; --c)
+    if (c < A.n_class && mine < cum[c - 1]) lab = c;
+  return lab;
+}
+
+// a wave per tile of 64 rows: the number of non-zero labels
+template <typename T>
+__global__ __launch_bounds__(SIM_THREADS) void simulate_count_kernel(SimRows A, int64_t n, int32_t rep, int64_t n_tiles,
+                                                                     int64_t* __restrict__ pre) {
+  const int64_t t = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
+  if (t >= n_tiles) return;
+  const int64_t i = t * 64 + (threadIdx.x & 63);
+  const int lab = i < n ? row_label<T>(A, i, rep) : 0;
+  const int hits = __popcll(__ballot(lab != 0));
+  if ((threadIdx.x & 63) == 0) pre[t] = hits;
+}
+
+template <typename T>
+__global__ __launch_bounds__(SIM_THREADS) void simulate_write_kernel(SimRows A, int64_t n, int32_t rep, int64_t n_tiles,
+                                                                     const int64_t* __restrict__ pre, int64_t* __restrict__ out_start,
+                                                                     uint8_t* __restrict__ out_strand, uint8_t* __restrict__ out_label) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
+  if (t >= n_tiles) return;
+  const int64_t i = t * 64 + lane;
+  const int lab = i < n ? row_label<T>(A, i, rep) : 0;
+  const u64 hits = __ballot(lab != 0);
+  if (lab != 0) {
+    const int64_t at = pre[t] + __popcll(hits & ((1ull << lane) - 1));      // below n: the hits before this one are rows before i
+    out_start[at] = A.start[i];
+    out_strand[at] = (A.strand != nullptr && A.strand[i] != 0) ? 1 : 0;
+    out_label[at] = (uint8_t)lab;
+  }
+}
+
+int fill_rows(SimRows& A, const void* prob, int64_t prob_stride, const int64_t* start, const uint8_t* strand, int32_t n_class,
+              uint32_t chrom_key, uint64_t seed, int32_t* status) {
+  A.prob = prob, A.start = start, A.strand = strand, A.prob_stride = prob_stride, A.n_class = n_class;
+  A.chrom_key = chrom_key, A.seed_lo = (uint32_t)seed, A.seed_hi = (uint32_t)(seed >> 32), A.status = status;
+  return MURAL_OK;
+}
+
+struct AnnotWs { int64_t *row0, *row1, *pre; };
+AnnotWs carve_annot(WsArena& ws, int64_t n_pieces) {
+  AnnotWs w;
+  w.row0 = ws.as<int64_t>((size_t)n_pieces);
+  w.row1 = ws.as<int64_t>((size_t)n_pieces);
+  w.pre = ws.as<int64_t>((size_t)n_pieces + 1);
+  return w;
+}
+
+int64_t tiles_of(int64_t n) { return (n + 63) / 64; }
+
+}  // namespace
+}  // namespace mural
+
+using namespace mural;
+
+extern "C" int64_t mural_simulate_chunk_rows(void) { return SIM_CHUNK_ROWS; }
+extern "C" int64_t mural_simulate_grid_waves(void) { return SIM_GRID_WAVES; }
+extern "C" int32_t mural_simulate_scan_threads(void) { return SIM_SCAN_THREADS; }
+extern "C" int32_t mural_simulate_max_replicates(void) { return SIM_MAX_REP; }
+
+extern "C" size_t mural_simulate_annot_workspace_bytes(int64_t n_pieces) {
+  if (n_pieces <= 0) return 0;
+  WsArena ws(nullptr);
+  carve_annot(ws, n_pieces);
+  return ws.off;
+}
+
+extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* ws_ptr, size_t ws_bytes, void* stream) {
+  MURAL_REQUIRE(s, "simulate_annot_rows: NULL argument");
+  MURAL_REQUIRE(s->n >= 0 && s->n_class >= 2 && s->n_class <= SIM_MAX_CLASS, "simulate_annot_rows: n >= 0 and 2 <= n_class <= %d required",
+                SIM_MAX_CLASS);
+  MURAL_REQUIRE(s->n_pieces >= 0 && s->n_groups >= 0, "simulate_annot_rows: n_pieces < 0 or n_groups < 0");
+  MURAL_REQUIRE(s->n_rep >= 1 && s->n_rep <= SIM_MAX_REP, "simulate_annot_rows: 1 <= n_rep <= 2^20 required");
+  if (s->n == 0) return MURAL_OK;
+  MURAL_REQUIRE(s->prob && s->start && s->status, "simulate_annot_rows: NULL argument");
+  MURAL_REQUIRE(s->prob_stride >= s->n_class, "simulate_annot_rows: prob_stride < n_class");
+  SimRows A{};
+  fill_rows(A, s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 block(SIM_THREADS);
+  const dim3 row_grid((unsigned)((s->n + SIM_THREADS - 1) / SIM_THREADS));
+  if (s->n_pieces > 0) {      // (everything is checked before the first launch)
+    MURAL_REQUIRE(s->piece_b0 && s->piece_b1 && s->piece_group && s->n_groups >= 1 && s->table,
+                  "simulate_annot_rows: pieces without groups or table");
+    const size_t need = mural_simulate_annot_workspace_bytes(s->n_pieces);
+    if (!ws_ptr || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws_ptr) & 7) != 0) {
+      set_error("simulate_annot_rows: the workspace is NULL, misaligned or smaller than mural_simulate_annot_workspace_bytes (%zu)", need);
+      return MURAL_E_WORKSPACE;
+    }
+  }
+  if (s->prob_f64)
+    hipLaunchKernelGGL(simulate_check_kernel<double>, row_grid, block, 0, st, A, s->n, 1);
+  else
+    hipLaunchKernelGGL(simulate_check_kernel<float>, row_grid, block, 0, st, A, s->n, 1);
+  MURAL_HIP_CHECK(hipGetLastError());
+  if (s->n_pieces == 0) return MURAL_OK;
+  WsArena ws(ws_ptr);
+  const AnnotWs w = carve_annot(ws, s->n_pieces);
+  const dim3 piece_grid((unsigned)((s->n_pieces + SIM_WAVES - 1) / SIM_WAVES));
+  hipLaunchKernelGGL(simulate_range_kernel, piece_grid, block, 0, st, s->start, s->n, s->piece_b0, s->piece_b1, s->piece_group, s->n_groups,
+                     s->n_pieces, w.row0, w.row1, w.pre);
+  MURAL_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(simulate_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, w.pre, s->n_pieces, (int64_t*)nullptr);
+  MURAL_HIP_CHECK(hipGetLastError());
+  // the units are known on the device only; the host knows a bound: every piece has at most ceil(n / chunk) chunks
+  const int64_t n_rb = (s->n_rep + 63) / 64;
+  const int64_t per_piece = (s->n + SIM_CHUNK_ROWS - 1) / SIM_CHUNK_ROWS;
+  int64_t n_waves = SIM_GRID_WAVES;
+  if (per_piece * n_rb < SIM_GRID_WAVES && s->n_pieces < SIM_GRID_WAVES / (per_piece * n_rb)) n_waves = s->n_pieces * per_piece * n_rb;
+  n_waves = (n_waves + SIM_WAVES - 1) / SIM_WAVES * SIM_WAVES;
+  const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES));
+  if (s->prob_f64)
+    hipLaunchKernelGGL(simulate_draw_kernel<double>, draw_grid, block, 0, st, A, s->piece_group, s->n_pieces, w.row0, w.row1, w.pre, s->n_rep,
+                       n_waves, s->table);
+  else
+    hipLaunchKernelGGL(simulate_draw_kernel<float>, draw_grid, block, 0, st, A, s->piece_group, s->n_pieces, w.row0, w.row1, w.pre, s->n_rep,
+                       n_waves, s->table);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
+extern "C" size_t mural_simulate_rows_workspace_bytes(int64_t n) {
+  if (n <= 0) return 0;
+  WsArena ws(nullptr);
+  ws.as<int64_t>((size_t)tiles_of(n) + 1);
+  return ws.off;
+}
+
+extern "C" int mural_simulate_rows(const MuralSimulateRows* s, void* ws_ptr, size_t ws_bytes, void* stream) {
+  MURAL_REQUIRE(s, "simulate_rows: NULL argument");
+  MURAL_REQUIRE(s->n >= 0 && s->n_class >= 2 && s->n_class <= SIM_MAX_CLASS, "simulate_rows: n >= 0 and 2 <= n_class <= %d required",
+                SIM_MAX_CLASS);
+  MURAL_REQUIRE(s->replicate >= 0 && s->replicate < SIM_MAX_REP, "simulate_rows: 0 <= replicate < 2^20 required");
+  if (s->n == 0) return MURAL_OK;
+  MURAL_REQUIRE(s->prob && s->start && s->status && s->out_start && s->out_strand && s->out_label && s->count, "simulate_rows: NULL argument");
+  MURAL_REQUIRE(s->prob_stride >= s->n_class, "simulate_rows: prob_stride < n_class");
+  const size_t need = mural_simulate_rows_workspace_bytes(s->n);
+  if (!ws_ptr || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws_ptr) & 7) != 0) {
+    set_error("simulate_rows: the workspace is NULL, misaligned or smaller than mural_simulate_rows_workspace_bytes (%zu)", need);
+    return MURAL_E_WORKSPACE;
+  }
+  SimRows A{};
+  fill_rows(A, s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
+  const int64_t n_tiles = tiles_of(s->n);
+  WsArena ws(ws_ptr);
+  int64_t* pre = ws.as<int64_t>((size_t)n_tiles + 1);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 block(SIM_THREADS);
+  const dim3 row_grid((unsigned)((s->n + SIM_THREADS - 1) / SIM_THREADS));
+  const dim3 tile_grid((unsigned)((n_tiles + SIM_WAVES - 1) / SIM_WAVES));
+  if (s->prob_f64) {
+    hipLaunchKernelGGL(simulate_check_kernel<double>, row_grid, block, 0, st, A, s->n, 0);
+    hipLaunchKernelGGL(simulate_count_kernel<double>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre);
+  } else {
+    hipLaunchKernelGGL(simulate_check_kernel<float>, row_grid, block, 0, st, A, s->n, 0);
+    hipLaunchKernelGGL(simulate_count_kernel<float>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre);
+  }
+  MURAL_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(simulate_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, pre, n_tiles, s->count);
+  MURAL_HIP_CHECK(hipGetLastError());
+  if (s->prob_f64)
+    hipLaunchKernelGGL(simulate_write_kernel<double>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre, s->out_start, s->out_strand,
+                       s->out_label);
+  else
+    hipLaunchKernelGGL(simulate_write_kernel<float>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre, s->out_start, s->out_strand,
+                       s->out_label);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}

@@ -4,6 +4,7 @@ consumer that runs one reducer per summary kind -- window tables and totals, k-m
 calibrator fit, annotation tables."""
 import ctypes as C
 import os
+import zlib
 
 import numpy as np
 import torch
@@ -13,7 +14,8 @@ from . import _lib
 from .calibration import calibrate_device, dirichlet_calibrate, save_dirichlet_calibrator
 from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
 from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds, shard_name, strand_u8
-from .tables import (annotation_meta, annotation_output_names, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
+from .tables import (annotation_meta, annotation_output_names, simulation_bed_name, simulation_bed_text, simulation_output_name,
+                     write_simulation_outputs, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
                      strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs)
 
@@ -353,6 +355,121 @@ def annot_table_from_sums(table, n_class):
     den = 1 << (_KMER_HI_BITS + _KMER_LO_BITS)
     hi, lo = table[:, 1].ravel().tolist(), table[:, 2].ravel().tolist()      # (one flat pass: there may be 10^5 names)
     out[:, 1 + nc:] = np.array([((h << _KMER_LO_BITS) + l) / den for h, l in zip(hi, lo)], np.float64).reshape(table.shape[0], nc)
+    return out
+
+
+# ---- mutation sets drawn from the rates (csrc/simulate.hip: mural_simulate_annot_rows, mural_simulate_rows) -----------------------------
+SIMULATE_MAX_REPLICATES = 1 << 20
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def simulate_chrom_key(name):
+    """The third counter word of a chromosome's draws: crc32 of its name as UTF-8, formed on the host so that every rank has the same."""
+    return zlib.crc32(str(name).encode("utf-8")) & 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on arrays: counter uint [..., 4], key uint [..., 2] (broadcast against each other) -> uint32 [..., 4]."""
+    c = [np.asarray(counter, np.uint64)[..., j] & _U32 for j in range(4)]
+    k = [np.asarray(key, np.uint64)[..., j] & _U32 for j in range(2)]
+    for rnd in range(10):
+        if rnd:
+            k = [(k[0] + np.uint64(_PHILOX_W0)) & _U32, (k[1] + np.uint64(_PHILOX_W1)) & _U32]
+        p0, p1 = c[0] * np.uint64(_PHILOX_M0), c[2] * np.uint64(_PHILOX_M1)
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & _U32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & _U32]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def simulate_cum_host(prob, start, n_class):
+    """(cum uint64 [n][n_class - 1], bad rows, status) of the class rule: q_c = floor(double(p_c) * 2^32) for c >= 1 (the product is
+    exact; a p_c of 1 or more gives 2^32 or more and is taken as 2^32, which the clamp below would make of it anyway),
+    cum_c = min(q_1 + .. + q_c, 2^32).  Bad rows -- a NaN, negative or infinite p_c (status 8), a negative start (status 1) -- have
+    cum = 0: they draw class 0 in every replicate."""
+    nc = int(n_class)
+    p = np.asarray(prob)[:, 1:nc].astype(np.float64)
+    start = np.asarray(start, np.int64)
+    bad_p = ~(np.isfinite(p) & ~np.signbit(np.where(p == 0, 0.0, p))).all(axis=1)
+    bad_s = start < 0
+    one = float(1 << 32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.floor(np.minimum(np.where(bad_p[:, None], 0.0, p) * one, one)).astype(np.uint64)
+    cum = np.minimum(np.cumsum(q, axis=1, dtype=np.uint64), np.uint64(1 << 32))
+    cum[bad_p | bad_s] = 0
+    return cum, bad_p | bad_s, (8 if bad_p.any() else 0) | (1 if bad_s.any() else 0)
+
+
+def simulate_rows_host(prob, start, strand, n_class, chrom_key, seed, reps, with_status=False):
+    """The numpy twin of the draw of csrc/simulate.hip -- and its specification: labels uint8 [n][len(reps)], the class of every row in
+    every replicate of `reps`.  Generator: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (start & 0xffffffff,
+    start >> 32, chrom_key, (replicate >> 2) | (strand << 31)), `strand` 1 for '-' (None: all '+'); replicate r reads output word r & 3
+    as u.  The label is the smallest c >= 1 with u < cum_c (``simulate_cum_host``), 0 where there is none; class 0's probability is
+    never read.  A draw depends on (seed, chromosome, start, strand, replicate) alone -- never on the row's index in a call, so any
+    split of the rows into parts draws the same --, and two rows with the same chromosome, start and strand draw the same value."""
+    reps = np.asarray(reps, np.int64).reshape(-1)
+    if len(reps) and (reps.min() < 0 or reps.max() >= SIMULATE_MAX_REPLICATES):
+        raise ValueError(f"replicates are 0 .. {SIMULATE_MAX_REPLICATES - 1}")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("the seed is an unsigned 64-bit integer")
+    start = np.asarray(start, np.int64)
+    n = len(start)
+    cum, _, status = simulate_cum_host(prob, start, n_class)
+    minus = np.zeros(n, np.uint64) if strand is None else (np.asarray(strand) != 0).astype(np.uint64)
+    s = start.view(np.uint64)
+    labels = np.zeros((n, len(reps)), np.uint8)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64)
+    for block in np.unique(reps >> 2):
+        ctr = np.stack([s & _U32, s >> np.uint64(32), np.full(n, int(chrom_key) & 0xFFFFFFFF, np.uint64),
+                        np.uint64(block) | (minus << np.uint64(31))], axis=-1)
+        words = philox4x32_10(ctr, key).astype(np.uint64)
+        for j in np.nonzero((reps >> 2) == block)[0]:
+            u = words[:, reps[j] & 3]
+            hit = u[:, None] < cum
+            labels[:, j] = np.where(hit.any(axis=1), hit.argmax(axis=1) + 1, 0)
+    return (labels, status) if with_status else labels
+
+
+def simulate_annot_host(prob, start, strand, n_class, chrom_key, seed, pieces, n_groups, n_rep, into=None):
+    """The numpy twin of ``mural_simulate_annot_rows``: (table uint32 [n_groups][n_class - 1][n_rep], status).  Cell [g][c - 1][r]: the
+    rows inside the pieces of group g (b0 <= start < b1; once per name that covers the row, as ``summary_annot_host``) whose
+    replicate-r draw of ``simulate_rows_host`` is class c.  `into`: the table of earlier parts and chromosomes, added to in place."""
+    nc, ng, R = int(n_class), int(n_groups), int(n_rep)
+    start = np.asarray(start, np.int64)
+    labels, status = simulate_rows_host(prob, start, strand, nc, chrom_key, seed, np.arange(R), with_status=True)
+    if len(start) > 1 and (start[1:] < start[:-1]).any():
+        status |= 4
+    table = np.zeros((ng, max(nc - 1, 0), R), np.uint32) if into is None else into
+    if pieces is None or len(pieces[0]) == 0 or nc < 2 or R == 0:
+        return table, status
+    b0, b1, grp = (np.asarray(x) for x in pieces)
+    order = np.argsort(start, kind="stable")
+    st = start[order]
+    prefix = np.zeros((len(st) + 1, nc - 1, R), np.uint32)
+    np.cumsum(labels[order][:, None, :] == np.arange(1, nc, dtype=np.uint8)[None, :, None], axis=0, dtype=np.uint32, out=prefix[1:])
+    i0 = np.searchsorted(st, b0, "left")
+    i1 = np.maximum(np.searchsorted(st, b1, "left"), i0)
+    live = np.nonzero((i1 > i0) & (grp >= 0) & (grp < ng))[0]
+    np.add.at(table, grp[live], prefix[i1[live]] - prefix[i0[live]])
+    return table, status
+
+
+def simulate_pvalues(counts, observed=None):
+    """Per row of `counts` int [m][R] (the simulated counts of a name and class): (sim_mean, sim_min, sim_max, n_ge, n_le, p_upper,
+    p_lower), the last four None without `observed` [m]: n_ge / n_le the replicates with a count at least / at most the observed one,
+    p_upper = (n_ge + 1) / (R + 1), p_lower = (n_le + 1) / (R + 1)."""
+    counts = np.asarray(counts, np.int64)
+    R = counts.shape[1]
+    out = []
+    for j, row in enumerate(counts):
+        total = int(row.sum())
+        head = (total / R, int(row.min()), int(row.max()))
+        if observed is None:
+            out.append(head + (None,) * 4)
+        else:
+            n_ge, n_le = int((row >= int(observed[j])).sum()), int((row <= int(observed[j])).sum())
+            out.append(head + (n_ge, n_le, (n_ge + 1) / (R + 1), (n_le + 1) / (R + 1)))
     return out
 
 
@@ -892,6 +1009,218 @@ class _AnnotationReducer:
         write_annotation_outputs(*result[self.name], k, out_prefix)
 
 
+class _SimulationReducer:
+    """Mutation sets drawn from the rates (``simulate_rows_host`` is the rule): per name of the annotation reducer beside it the counts
+    of every class in each of `n_rep` replicates -- ONE uint32 table [names][n_class - 1][n_rep] on the host and one per device, the
+    pieces the annotation reducer uploaded, read back once --, and the replicates of `write` as mutation lists, a file per replicate
+    written part by part (a rank's parts into its own part file; rank 0 strings them together in (shard, rank) order at close)."""
+    name = "simulation"
+
+    def __init__(self, n_rep, seed, write, annot, table_bytes_max, out_prefix, labels, rank, world):
+        self.n_rep, self.seed, self.write_reps = int(n_rep), int(seed), tuple(int(r) for r in write)
+        if not 1 <= self.n_rep <= SIMULATE_MAX_REPLICATES:
+            raise ValueError("simulate: 1 .. 2^20 replicates")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError("simulate_seed is an unsigned 64-bit integer")
+        if any(not 0 <= r < self.n_rep for r in self.write_reps) or len(set(self.write_reps)) != len(self.write_reps):
+            raise ValueError(f"simulate_write: distinct replicates in 0 .. {self.n_rep - 1}")
+        if self.write_reps and out_prefix is None:
+            raise ValueError("simulate_write needs an out_prefix")
+        self.annot, self.table_bytes_max, self.out_prefix, self.labels = annot, int(table_bytes_max), out_prefix, bool(labels)
+        self.rank, self.world = rank, world
+        self.reset()
+
+    def reset(self):
+        self.host = None               # table uint32 [names][n_class - 1][n_rep] of the host shards
+        self.dev = {}                  # device -> dict(table, status, ws, out)
+        self.counts = None
+        self.pending = []              # device mutation lists not yet on the host: (event, chrom, shard number, {replicate: buffers})
+        self.shard, self.last = -1, None
+        self.index = {r: [] for r in self.write_reps}      # replicate -> [chromosome, bytes] per run of parts of one chromosome, in file order
+        for fh in getattr(self, "files", {}).values():
+            fh.close()
+        self.files = {}
+
+    def _groups(self):
+        return 0 if self.annot is None else len(self.annot.names)
+
+    def _check_table(self, k):
+        need = self._groups() * (k - 1) * self.n_rep * 4
+        if need > self.table_bytes_max:
+            raise ValueError(f"simulate: the table of {self._groups()} names x {k - 1} classes x {self.n_rep} replicates takes {need} "
+                             f"bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        if k < 2:
+            raise ValueError("simulate needs at least 2 classes")
+
+    def _next_shard(self, name):
+        """Parts of one chromosome continue its shard (the sink takes the chromosomes one after the other)."""
+        if name != self.last:
+            self.shard, self.last = self.shard + 1, name
+            for r in self.write_reps:
+                self.index[r].append([name, 0])
+
+    def _path(self, r):
+        path = simulation_bed_name(self.out_prefix, r)
+        return path + (".part%04d" % self.rank if self.world > 1 else "")
+
+    def _emit(self, chrom, r, start, strand, label):
+        if r not in self.files:
+            self.files[r] = open(self._path(r), "w")
+        text = simulation_bed_text(chrom, start, strand, label)
+        self.files[r].write(text)
+        self.index[r][-1][1] += len(text)
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        self._check_table(k)
+        self._next_shard(name)
+        key = simulate_chrom_key(name)
+        status = 0
+        pieces = None if self.annot is None else self.annot.pieces.get(name)
+        if pieces is not None:
+            if self.host is None:
+                self.host = np.zeros((self._groups(), k - 1, self.n_rep), np.uint32)
+            status |= simulate_annot_host(prob, start, strand, k, key, self.seed, pieces, self._groups(), self.n_rep, into=self.host)[1]
+        if self.write_reps:
+            self._drain()
+            labels, st = simulate_rows_host(prob, start, strand, k, key, self.seed, self.write_reps, with_status=True)
+            status |= st
+            for j, r in enumerate(self.write_reps):
+                hit = labels[:, j] > 0
+                self._emit(name, r, np.asarray(start)[hit], np.asarray(strand)[hit], labels[hit, j])
+        return status
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        self._check_table(k)
+        self._next_shard(name)
+        n = start.shape[0]
+        if n == 0:
+            return None
+        dev, lib = prob.device, _lib.lib()
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(max(self._groups() * (k - 1) * self.n_rep, 1), dtype=torch.int32, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev), ws=None, copy=torch.cuda.Stream(dev))
+        key = simulate_chrom_key(name)
+        stream = _lib.current_stream_ptr(dev)
+
+        def workspace(need):
+            if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+                acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+            return acc["ws"]
+
+        on_dev = None if self.annot is None else self.annot.dev.get(dev, {}).get("pieces", {}).get(name)      # uploaded just before
+        if on_dev is not None:
+            s = _lib.MuralSimulateAnnotRows()
+            s.prob, s.prob_f64, s.prob_stride, s.n_class = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0), k
+            s.start, s.strand, s.n = start.data_ptr(), strand.data_ptr(), n
+            s.chrom_key, s.n_rep, s.seed = key, self.n_rep, self.seed
+            s.piece_b0, s.piece_b1, s.piece_group, s.n_pieces = (on_dev[0].data_ptr(), on_dev[1].data_ptr(), on_dev[2].data_ptr(),
+                                                                 on_dev[0].shape[0])
+            s.n_groups, s.table, s.status = self._groups(), acc["table"].data_ptr(), acc["status"].data_ptr()
+            ws = workspace(int(lib.mural_simulate_annot_workspace_bytes(on_dev[0].shape[0])))
+            _lib.check(lib.mural_simulate_annot_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, stream))
+        if self.write_reps:
+            self._drain()
+            lists = {}
+            for r in self.write_reps:
+                out = dict(start=torch.empty(n, dtype=torch.int64, device=dev), strand=torch.empty(n, dtype=torch.uint8, device=dev),
+                           label=torch.empty(n, dtype=torch.uint8, device=dev), count=torch.zeros(1, dtype=torch.int64, device=dev))
+                s = _lib.MuralSimulateRows()
+                s.prob, s.prob_f64, s.prob_stride, s.n_class = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0), k
+                s.start, s.strand, s.n = start.data_ptr(), strand.data_ptr(), n
+                s.chrom_key, s.replicate, s.seed = key, r, self.seed
+                s.out_start, s.out_strand, s.out_label = out["start"].data_ptr(), out["strand"].data_ptr(), out["label"].data_ptr()
+                s.count, s.status = out["count"].data_ptr(), acc["status"].data_ptr()
+                ws = workspace(int(lib.mural_simulate_rows_workspace_bytes(n)))      # (the launches of one stream run in order)
+                _lib.check(lib.mural_simulate_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, stream))
+                lists[r] = out
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(dev))
+            self.pending.append((event, name, len(self.index[self.write_reps[0]]) - 1, lists, acc["copy"]))
+        return None
+
+    def _drain(self, wait=False):
+        """Bring the finished device lists to the host, in order, and write them.  The copies run on a stream of their own, so that
+        they do not wait for the forward that is already enqueued; without `wait` the lists still in flight stay (they keep their
+        place: nothing later is written before them)."""
+        while self.pending:
+            event, name, shard, lists, copy = self.pending[0]
+            if not wait and not event.query():
+                return
+            event.synchronize()
+            with torch.cuda.stream(copy):
+                for r, out in lists.items():
+                    m = int(out["count"].cpu().item())
+                    cols = [out[key][:m].cpu().numpy() for key in ("start", "strand", "label")]
+                    if r not in self.files:
+                        self.files[r] = open(self._path(r), "w")
+                    text = simulation_bed_text(name, *cols)
+                    self.files[r].write(text)
+                    self.index[r][shard][1] += len(text)
+            self.pending.pop(0)
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'; the mutation lists are flushed."""
+        status, table = 0, self.host
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            if self._groups() and k is not None:
+                mine = acc["table"].cpu().numpy().view(np.uint32)[:self._groups() * (k - 1) * self.n_rep]
+                mine = mine.reshape(self._groups(), k - 1, self.n_rep)
+                table = mine.copy() if table is None else table + mine
+        self._drain(wait=True)
+        for r in self.write_reps:      # a rank without rows still has its (empty) file
+            if r not in self.files:
+                self.files[r] = open(self._path(r), "w")
+        for fh in self.files.values():
+            fh.close()
+        return dict(table=table, index={r: [tuple(v) for v in segs] for r, segs in self.index.items()}), status
+
+    def merge(self, states, k):
+        table = None
+        for st in states:
+            if st["table"] is not None:
+                table = st["table"].copy() if table is None else table + st["table"]
+        return dict(table=table, index=[st["index"] for st in states])
+
+    def finish(self, state, k, result):
+        table = state["table"]
+        self.counts = np.zeros((self._groups(), max((k or 1) - 1, 0), self.n_rep), np.uint32) if table is None else table
+        self._index = state["index"]
+        if self.annot is not None:
+            names, _, annot = result["annotations"]
+            observed = annot[:, 2:1 + k] if (k and self.labels) else None
+            expected = annot[:, 2 + k:1 + 2 * k] if k else None
+            result[self.name] = (names, self.counts, observed, expected)
+
+    def write(self, out_prefix, result, k, written):
+        if self.annot is not None:
+            written.append(simulation_output_name(out_prefix))
+            write_simulation_outputs(*result[self.name], k, out_prefix)
+        for r in self.write_reps:
+            path = simulation_bed_name(out_prefix, r)
+            written.append(path)
+            if self.world > 1:             # every rank closed its part before the sink's collective returned
+                index = [st[r] for st in self._index]
+                order = list(dict.fromkeys(name for segs in index for name, _ in segs))      # rank 0's shard order, then the others'
+                srcs = [open(path + ".part%04d" % rank, "r") for rank in range(self.world)]
+                try:
+                    with open(path, "w") as dst:
+                        for name in order:
+                            for rank, src in enumerate(srcs):
+                                at = 0
+                                for seg_name, size in index[rank]:
+                                    if seg_name == name and size:
+                                        src.seek(at)
+                                        dst.write(src.read(size))
+                                    at += size
+                finally:
+                    for src in srcs:
+                        src.close()
+                for rank in range(self.world):
+                    os.unlink(path + ".part%04d" % rank)
+
+
 class _CalibrationReducer:
     """The integer tables behind NLL / ECE / classwise ECE / Brier per chromosome and, with `fit_calibrator`, the retained rows and the
     calibrator fit on them at close()."""
@@ -1148,6 +1477,24 @@ class SummarySink:
     ``{out_prefix}.annotation.mut_rates.tsv`` / ``.corr.txt`` (``tables.write_annotation_outputs``); ``annotation_sums()`` has the
     integers.
 
+    `simulate`: R replicates (1 .. 2^20) of the run's mutations drawn from its probabilities with `simulate_seed` (required: an unsigned
+    64-bit integer; there is no default randomness).  The rule is ``simulate_rows_host``: stateless Philox
+    draws keyed by (seed, chromosome, start, strand, replicate), so the results depend on the set of rows and the seed alone, bit for
+    bit, for any parts, shards or ranks; two rows with the same chromosome, start and strand draw the same value.  With `annotations`
+    the counts of every name, class and replicate are reduced beside the annotation table (``mural_simulate_annot_rows``,
+    csrc/simulate.hip, on the pieces the annotation reducer uploaded; host shards through ``simulate_annot_host``) into one uint32 table
+    [names][n_class - 1][R], refused with ValueError above `simulate_table_bytes_max` bytes (1 GiB: a stated cap, not a tuned value),
+    read back once and added across ranks in the same collective.  close() writes ``{out_prefix}.annotation.sim.tsv``
+    (``tables.write_simulation_outputs``: name, class, observed, expected, sim_mean, sim_min, sim_max, n_ge, n_le, p_upper = (n_ge + 1)
+    / (R + 1), p_lower); `simulate_labels=False` says that the rows carry no labels: the observed column and the four after sim_max are
+    NA.  result()["simulation"] = (names, counts, observed or None, expected); ``simulation_counts()`` has the table.
+    `simulate_write`: replicates whose mutation lists -- the rows whose draw is not 0, in run order -- are written to
+    ``{out_prefix}.sim{r}.mutations.bed`` (chrom start end name score strand, score = class: what ``data.read_mutations`` reads), device
+    parts through ``mural_simulate_rows`` (compacted on the device; the lists of a part come to the host when the next part arrives).
+    With ranks every rank writes ``....bed.part<rank>`` and rank 0 strings the parts together chromosome by chromosome in its own
+    shard order, the ranks' parts of a chromosome in rank order.  The sink takes
+    the chromosomes one after the other.
+
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
 
@@ -1155,7 +1502,8 @@ class SummarySink:
 
     def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
                  group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
-                 calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None):
+                 calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
+                 simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -1177,6 +1525,16 @@ class SummarySink:
         self.annotations = annotations is not None
         if self.annotations:
             active.append(_AnnotationReducer(annotations))
+        self.simulate = simulate is not None
+        if self.simulate:
+            if simulate_seed is None:
+                raise ValueError("simulate needs simulate_seed: there is no default randomness")
+            if annotations is None and not tuple(simulate_write):
+                raise ValueError("simulate needs annotations= (the counts per name) or a replicate in simulate_write")
+            active.append(_SimulationReducer(simulate, simulate_seed, simulate_write, active[-1] if self.annotations else None,
+                                             simulate_table_bytes_max, self.out_prefix, simulate_labels, self.rank, self.world))
+        elif simulate_seed is not None or tuple(simulate_write):
+            raise ValueError("simulate_seed and simulate_write go with simulate=R")
         self._reducers = {r.name: r for r in active}
         self.rows = 0
         self._n_class = None
@@ -1194,7 +1552,8 @@ class SummarySink:
         """Calibrate and order the part, reduce it in every reducer."""
         prob = host_calibrate(np.asarray(shard["prob"])[:, :k], self.poisson, self.dirichlet_weights)
         start = np.asarray(shard["start"])
-        cols = [prob, start, np.asarray(shard["end"]), strand_u8(shard["strand"]) if self.kmers else None, np.asarray(shard["label"])]
+        cols = [prob, start, np.asarray(shard["end"]), strand_u8(shard["strand"]) if (self.kmers or self.simulate) else None,
+                np.asarray(shard["label"])]
         if not shard.get("aligned"):
             perm = np.argsort(start, kind="stable")
             if self.parts:
@@ -1221,13 +1580,13 @@ class SummarySink:
             start, end = to(shard["start"], torch.int64), to(shard["end"], torch.int64)
             label = shard["label"]
             label = to(label, label.dtype if isinstance(label, torch.Tensor) and label.dtype in (torch.int32, torch.int64) else torch.float32)
-            strand = to(strand_u8(shard["strand"]), torch.uint8) if self.kmers else None
+            strand = to(strand_u8(shard["strand"]), torch.uint8) if (self.kmers or self.simulate) else None
             if not shard.get("aligned"):
                 perm = torch.sort(start, stable=True).indices
                 if self.parts:
                     perm = perm[slice(*shard_bounds(perm.shape[0], self.rank, self.world))]
                 prob, start, end, label = prob[perm], start[perm], end[perm], label[perm]
-                strand = strand[perm] if self.kmers else None
+                strand = strand[perm] if strand is not None else None
             cols = (name, prob, start, end, strand, label, k)
             held = None
             by_window, *others = self._reducers.values()
@@ -1323,6 +1682,12 @@ class SummarySink:
         result()["annotations"] (``summary_annot_host``'s layout, the names in ``read_annotations``' order)."""
         self.result()
         return self._reducers["annotations"].sums
+
+    def simulation_counts(self):
+        """table uint32 [names][n_class - 1][simulate] after close(): the simulated count of every name, class >= 1 and replicate
+        (``simulate_annot_host``'s layout, the names in ``read_annotations``' order)."""
+        self.result()
+        return self._reducers["simulation"].counts
 
     def calibration_sums(self):
         """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind

@@ -683,6 +683,146 @@ def run_annotation_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# simulation: mutation sets drawn from the rates, per-name empirical p-values
+# ------------------------------------------------------------------------------------------------------------------
+def simulation_output_name(out_prefix):
+    return f"{out_prefix}.annotation.sim.tsv"
+
+
+def simulation_bed_name(out_prefix, replicate):
+    return f"{out_prefix}.sim{int(replicate)}.mutations.bed"
+
+
+def simulation_bed_text(chrom, start, strand, label):
+    """The rows of a simulated mutation list as BED text: chrom start end name score strand, score = class (``data.read_mutations``)."""
+    return "".join(f"{chrom}\t{s}\t{s + 1}\t.\t{c}\t{'-' if m else '+'}\n"
+                   for s, m, c in zip(np.asarray(start).tolist(), np.asarray(strand).tolist(), np.asarray(label).tolist()))
+
+
+def write_simulation_outputs(names, counts, observed, expected, n_class, out_prefix):
+    """``{out_prefix}.annotation.sim.tsv``: one line per name and class c >= 1 -- name, class, observed, expected, sim_mean, sim_min,
+    sim_max, n_ge, n_le, p_upper, p_lower (``summaries.simulate_pvalues``) -- from counts [names][n_class - 1][R], observed
+    [names][n_class - 1] (None: no labels, 'NA' in the observed column and the last four) and expected [names][n_class - 1]."""
+    from .summaries import simulate_pvalues      # (summaries imports this module: not at the top)
+    header = ["name", "class", "observed", "expected", "sim_mean", "sim_min", "sim_max", "n_ge", "n_le", "p_upper", "p_lower"]
+    counts = np.asarray(counts)
+    rows = []
+    stats = {c: simulate_pvalues(counts[:, c - 1], None if observed is None else np.asarray(observed)[:, c - 1]) for c in range(1, n_class)}
+    for j, nm in enumerate(names):
+        for c in range(1, n_class):
+            mean, lo, hi, n_ge, n_le, p_up, p_lo = stats[c][j]
+            obs = "NA" if observed is None else str(int(observed[j][c - 1]))
+            tail = ["NA"] * 4 if observed is None else [str(n_ge), str(n_le), _float_text(p_up), _float_text(p_lo)]
+            rows.append([nm, str(c), obs, _float_text(expected[j][c - 1]), _float_text(mean), str(lo), str(hi)] + tail)
+    path = simulation_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    return path
+
+
+def simulate_table(pred_file, annotations, n_rep, seed, n_class, write=(), out_prefix=None, labels=True, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, counts uint32 [names][n_class - 1][n_rep], observed or None, expected) from a written prediction table: what
+    ``SummarySink(simulate=n_rep, simulate_seed=seed, annotations=...)`` reduces in flight, through the same entries
+    (``mural_simulate_annot_rows`` beside ``mural_summary_annot_rows``), chromosome run by chromosome run of each chunk; the draws are
+    made from the table's four-digit probabilities.  `write`: replicates whose mutation lists go to
+    ``{out_prefix}.sim{r}.mutations.bed`` (``mural_simulate_rows``).  `annotations` may be None when only lists are asked for."""
+    from .summaries import _SUMMARY_STATUS, SIMULATE_MAX_REPLICATES, annot_table_from_sums, simulate_chrom_key
+    n_class, n_rep, seed, write = int(n_class), int(n_rep), int(seed), tuple(int(r) for r in write)
+    if not 2 <= n_class <= 8:
+        raise ValueError("the simulation takes 2 .. 8 classes")
+    if not 1 <= n_rep <= SIMULATE_MAX_REPLICATES or not 0 <= seed < 1 << 64:
+        raise ValueError("simulate_table: 1 .. 2^20 replicates and an unsigned 64-bit seed")
+    if any(not 0 <= r < n_rep for r in write) or (write and out_prefix is None):
+        raise ValueError("simulate_table: `write` holds replicates below n_rep and needs an out_prefix")
+    if annotations is None and not write:
+        raise ValueError("simulate_table needs annotations or a replicate to write")
+    names, meta, pieces = read_annotations(annotations) if annotations is not None else ([], {}, {})
+    lib = _lib.lib()
+    n_groups = len(names)
+    files = {r: open(simulation_bed_name(out_prefix, r), "w") for r in write}
+    try:
+        with TableReader(pred_file, n_class, chunk_bytes) as rd:
+            dev = rd.device
+            sums = torch.zeros(max(n_groups, 1) * 3 * n_class, dtype=torch.int64, device=dev)
+            table = torch.zeros(max(n_groups * (n_class - 1) * n_rep, 1), dtype=torch.int32, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            on_dev, ws = {}, None
+            stream = _lib.current_stream_ptr(dev)
+
+            def workspace(need):
+                nonlocal ws
+                if ws is None or ws.numel() * 8 < need:
+                    ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+                return ws
+
+            for c in rd:
+                rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+                for r in range(c.n_runs):
+                    name = rd.chrom_name(c.run_chrom[r])
+                    a, b = rows[r], rows[r + 1]
+                    if b == a:
+                        continue
+                    key = simulate_chrom_key(name)
+                    if name in pieces:
+                        if name not in on_dev:
+                            on_dev[name] = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in pieces[name])
+                        b0, b1, grp = on_dev[name]
+                        s = _lib.MuralSummaryAnnotRows()
+                        s.prob, s.prob_f64, s.prob_stride = c.prob + 8 * n_class * a, 1, n_class
+                        s.start, s.label, s.label_kind = c.start + 8 * a, c.mut_type + 4 * a, 1
+                        s.n, s.n_class, s.n_groups = b - a, n_class, n_groups
+                        s.piece_b0, s.piece_b1, s.piece_group, s.n_pieces = b0.data_ptr(), b1.data_ptr(), grp.data_ptr(), b0.shape[0]
+                        s.table, s.status = sums.data_ptr(), status.data_ptr()
+                        w = workspace(int(lib.mural_summary_annot_workspace_bytes(b - a, n_class)))
+                        _lib.check(lib.mural_summary_annot_rows(C.byref(s), w.data_ptr(), w.numel() * 8, stream))
+                        m = _lib.MuralSimulateAnnotRows()
+                        m.prob, m.prob_f64, m.prob_stride, m.n_class = c.prob + 8 * n_class * a, 1, n_class, n_class
+                        m.start, m.strand, m.n = c.start + 8 * a, c.strand + a, b - a
+                        m.chrom_key, m.n_rep, m.seed = key, n_rep, seed
+                        m.piece_b0, m.piece_b1, m.piece_group, m.n_pieces = b0.data_ptr(), b1.data_ptr(), grp.data_ptr(), b0.shape[0]
+                        m.n_groups, m.table, m.status = n_groups, table.data_ptr(), status.data_ptr()
+                        w = workspace(int(lib.mural_simulate_annot_workspace_bytes(b0.shape[0])))
+                        _lib.check(lib.mural_simulate_annot_rows(C.byref(m), w.data_ptr(), w.numel() * 8, stream))
+                    for rep in write:      # (a table is read at the host's pace: the list is read back part by part)
+                        out = (torch.empty(b - a, dtype=torch.int64, device=dev), torch.empty(b - a, dtype=torch.uint8, device=dev),
+                               torch.empty(b - a, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+                        m = _lib.MuralSimulateRows()
+                        m.prob, m.prob_f64, m.prob_stride, m.n_class = c.prob + 8 * n_class * a, 1, n_class, n_class
+                        m.start, m.strand, m.n = c.start + 8 * a, c.strand + a, b - a
+                        m.chrom_key, m.replicate, m.seed = key, rep, seed
+                        m.out_start, m.out_strand, m.out_label, m.count = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                                           out[3].data_ptr())
+                        m.status = status.data_ptr()
+                        w = workspace(int(lib.mural_simulate_rows_workspace_bytes(b - a)))
+                        _lib.check(lib.mural_simulate_rows(C.byref(m), w.data_ptr(), w.numel() * 8, stream))
+                        hits = int(out[3].item())
+                        files[rep].write(simulation_bed_text(name, *(x[:hits].cpu().numpy() for x in out[:3])))
+            bits = int(status.item())
+            for bit, what in _SUMMARY_STATUS:
+                if bits & bit:
+                    raise ValueError(f"{pred_file}: {what}")
+            annot = annot_table_from_sums(sums.cpu().numpy().view(np.uint64)[:n_groups * 3 * n_class].reshape(n_groups, 3, n_class), n_class)
+            counts = table.cpu().numpy().view(np.uint32)[:n_groups * (n_class - 1) * n_rep].reshape(n_groups, n_class - 1, n_rep)
+    finally:
+        for fh in files.values():
+            fh.close()
+    return names, counts, (annot[:, 2:1 + n_class] if labels else None), annot[:, 2 + n_class:1 + 2 * n_class]
+
+
+def run_simulate_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.annotations, args.simulate, args.seed, args.n_class, args.out_prefix,
+    optionally args.write_simulated): the simulated counts per name of the annotation BED from the table's rows; writes
+    {out_prefix}.annotation.sim.tsv and the mutation lists asked for."""
+    assert getattr(args, "seed", None) is not None, "--seed is required with --simulate: there is no default randomness"
+    write = tuple(getattr(args, "write_simulated", None) or ())
+    names, counts, observed, expected = simulate_table(os.fspath(args.pred_file), getattr(args, "annotations", None), args.simulate, args.seed,
+                                                       args.n_class, write, args.out_prefix, True, chunk_bytes)
+    if getattr(args, "annotations", None) is None:
+        return None
+    return write_simulation_outputs(names, counts, observed, expected, args.n_class, args.out_prefix)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # evaluate: regional
 # ------------------------------------------------------------------------------------------------------------------
 _MAX_CHUNK_WINDOWS = 1 << 24

@@ -1,0 +1,30 @@
+"""The simulation's entry points in the PRODUCT library (the suite itself runs on the debug flavour, tests/conftest.py)."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("mural_simulate_annot_rows", "mural_simulate_annot_workspace_bytes", "mural_simulate_rows", "mural_simulate_rows_workspace_bytes",
+           "mural_simulate_chunk_rows", "mural_simulate_grid_waves", "mural_simulate_scan_threads", "mural_simulate_max_replicates")
+
+
+def test_both_flavours_export_the_simulation_entries_and_the_source_is_linked():
+    from mural_amd import _lib
+    for path in (_lib.LIB_PATH, _lib.DEBUG_LIB_PATH):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        defined = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+        assert set(ENTRIES) <= defined, (path, set(ENTRIES) - defined)
+    assert set(ENTRIES) <= set(_lib.PROTOTYPES)
+    make = open(os.path.join(ROOT, "mural_amd", "csrc", "Makefile")).read()
+    srcs = next(ln for ln in make.splitlines() if ln.startswith("SRCS"))
+    assert "simulate.hip" in srcs.split()
+
+
+@pytest.mark.gpu
+def test_product_library_draws_the_table_and_the_list():
+    env = {k: v for k, v in os.environ.items() if k != "MURAL_HIP_FLAVOR"}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_product_simulate_checks.py")], capture_output=True, text=True,
+                         timeout=600, env=env, cwd=ROOT)
+    assert out.returncode == 0 and "PRODUCT_SIMULATE_OK" in out.stdout, (out.stdout[-2000:], out.stderr[-4000:])

@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Twelve legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Fourteen legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -21,6 +21,9 @@ alternating, --repeats timed runs each after one warm-up run each:
                  annotation file -- 20 000 names x 10 intervals of 150 bp spread over the chromosome, 5 % of the names overlapping a
                  neighbour --; the comparison is leg b, the same run without it
   l  annot_tools the route to k's table without the sink: leg a's table, then tables.annotation_table on it
+  m  sim100      leg k with simulate=100, simulate_seed=1 as well: the counts of 100 mutation sets drawn from the
+                 rates per name; the comparison is leg k, the same run without it
+  n  sim1000     leg k with simulate=1000 (a table of 240 MB, below the sink's cap)
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
 h's and leg k's annotation table with leg l's, within the table's four digits (names, order and counts exactly)."""
 import json
@@ -44,7 +47,8 @@ from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, pr
 WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
-LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools")
+LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000")
+SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
 ANNOT_NAMES, ANNOT_INTERVALS, ANNOT_BP, ANNOT_OVERLAP = 20_000, 10, 150, 0.05
 
 
@@ -79,7 +83,7 @@ def main(argv):
         torch.cuda.empty_cache()
         out = os.path.join(work, "table.tsv")
         kept, closes = {}, {}
-        annot = synthetic_annotations(bases) if {"annot", "annot_tools"} & set(legs) else None
+        annot = synthetic_annotations(bases) if {"annot", "annot_tools", "sim100", "sim1000"} & set(legs) else None
 
         def run(leg):
             split, extra = {}, {}
@@ -95,7 +99,9 @@ def main(argv):
                 summary = SummarySink(windows=WINDOWS, calibration=True)
             if leg == "annot":
                 summary = SummarySink(windows=WINDOWS, annotations=annot)
-            if leg in ("summary", "annot") and "annot" in legs:      # close() alone, of every run: where leg k's host work would be
+            if leg in SIM_REPLICATES:
+                summary = SummarySink(windows=WINDOWS, annotations=annot, simulate=SIM_REPLICATES[leg], simulate_seed=1, simulate_labels=False)
+            if leg in ("summary", "annot", "sim100", "sim1000") and "annot" in legs:      # close() alone, of every run: where leg k's host work would be
                 plain_close = summary.close
 
                 def close_timed():
@@ -120,7 +126,8 @@ def main(argv):
                 summary.close = timed_close
             sink = {"calib": lambda: summary, "calib_fit": lambda: summary, "table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
-                    "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out)}[leg]()
+                    "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out), "sim100": lambda: summary,
+                    "sim1000": lambda: summary}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
                                         **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
@@ -200,6 +207,8 @@ def main(argv):
            "motif_tools_over_motifs_seconds": ratio("motif_tools", "motifs", sec),
            "calib_over_summary": ratio("calib", "summary", med), "calib_fit_over_summary": ratio("calib_fit", "summary", med),
            "annot_over_summary": ratio("annot", "summary", med), "annot_tools_over_annot_seconds": ratio("annot_tools", "annot", sec),
+           "sim100_over_annot": ratio("sim100", "annot", med), "sim1000_over_annot": ratio("sim1000", "annot", med),
+           "simulated_draws": {leg: float(kept[leg]["simulation"][1].sum()) for leg in SIM_REPLICATES if leg in kept},
            "annotations": {"names": ANNOT_NAMES, "intervals": ANNOT_INTERVALS, "bp": ANNOT_BP,
                            "close_seconds": {leg: v[1:] for leg, v in closes.items()},      # (without the warm-up round's)
                            "rows_in_a_piece": float(kept["annot"]["annotations"][2][:, 0].sum()) if "annot" in kept else None},

@@ -39,6 +39,15 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              BED; the exons of a gene share one) the observed mutations and the
                                                              expected ones, the sums of the probabilities over the rows inside the
                                                              name's intervals; alone or with the options above
+  --summary PREFIX  --simulate R --seed S [--write_simulated r ..]
+                                                             R mutation sets drawn from the run's probabilities (stateless Philox draws
+                                                             keyed by the 64-bit seed S, chromosome, start, strand and replicate; there
+                                                             is no default seed).  With --annotations: PREFIX.annotation.sim.tsv, per
+                                                             name and class the observed and expected counts, the mean, minimum and
+                                                             maximum of the R simulated counts, n_ge / n_le and the empirical p-values
+                                                             (n + 1) / (R + 1); observed and the p-values are NA where the rows carry no
+                                                             labels (--regions without --mutations).  --write_simulated r ..: replicate
+                                                             r as PREFIX.sim{r}.mutations.bed, a list that --mutations reads
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -53,7 +62,7 @@ from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
 _SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--annotations", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
-                    "--scale_factor", "--n_bins", "--fit_calibrator")
+                    "--scale_factor", "--n_bins", "--fit_calibrator", "--simulate", "--seed", "--write_simulated")
 _PAIR_OPTIONS = ("--model_set", "--scale_factors")      # NAME CLASS=VALUE [CLASS=VALUE ..]
 _VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _PAIR_OPTIONS + _SUMMARY_OPTIONS
 
@@ -73,7 +82,7 @@ def _split(argv):
                     raise SystemExit(f"{name} needs a value\n\n{__doc__}")
                 val = argv[at]
             values.setdefault(name, []).append(val)
-            while name == "--motif_length" and at + 1 < len(argv) and argv[at + 1].lstrip("-").isdigit():      # M [M ..]
+            while name in ("--motif_length", "--write_simulated") and at + 1 < len(argv) and argv[at + 1].lstrip("-").isdigit():      # M [M ..]
                 at = next(it)
                 values[name].append(argv[at])
             while name in _PAIR_OPTIONS and at + 1 < len(argv) and "=" in argv[at + 1] and not argv[at + 1].startswith("--"):
@@ -93,6 +102,9 @@ def main(argv):
     opts = _summary_options(flags, values, model_type)
     if opts["calibration"] and "--regions" in values and "--mutations" not in values:
         raise SystemExit("--calibration_metrics needs labels: --regions alone gives every row the label 0; add --mutations FILE")
+    opts["labelled"] = "--regions" not in values or "--mutations" in values      # --regions alone gives every row the label 0
+    if opts["simulate"] is not None and ("--model_set" in values or "--scale_factors" in values):
+        raise SystemExit("--simulate does not go with --model_set")
     if opts["fit_calibrator"] is not None and poisson:
         raise SystemExit("--fit_calibrator fits the raw softmax: it does not go with the Poisson calibration (--poisson; on by default "
                          "with --indel)")
@@ -137,7 +149,22 @@ def _summary_options(flags, values, model_type="snv"):
             "scale_factor": one("--scale_factor", float), "no_table": "--no-table" in flags,
             "kmers": tuple(int(k) for k in values.get("--kmer_length", [])), "strand": one("--strand", str),
             "motifs": tuple(int(m) for m in values.get("--motif_length", [])), "calibration": "--calibration_metrics" in flags,
-            "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str), "annotations": one("--annotations", str)}
+            "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str), "annotations": one("--annotations", str),
+            "simulate": one("--simulate", int), "seed": one("--seed", lambda v: int(v, 0)),
+            "write_simulated": tuple(int(r) for r in values.get("--write_simulated", []))}
+    if opts["simulate"] is not None and opts["seed"] is None:
+        raise SystemExit("--simulate needs --seed S: there is no default randomness")
+    if opts["simulate"] is None and (opts["seed"] is not None or opts["write_simulated"]):
+        raise SystemExit("--seed / --write_simulated go with --simulate R")
+    if opts["simulate"] is not None:
+        if opts["summary"] is None:
+            raise SystemExit("--simulate needs --summary PREFIX: the prefix of the files it writes")
+        if opts["annotations"] is None and not opts["write_simulated"]:
+            raise SystemExit("--simulate needs --annotations BED (the counts per name) or --write_simulated r")
+        if not 1 <= opts["simulate"] <= 1 << 20 or not 0 <= opts["seed"] < 1 << 64:
+            raise SystemExit("--simulate takes 1 .. 2^20 replicates and an unsigned 64-bit --seed")
+        if any(not 0 <= r < opts["simulate"] for r in opts["write_simulated"]) or len(set(opts["write_simulated"])) != len(opts["write_simulated"]):
+            raise SystemExit("--write_simulated takes distinct replicates below --simulate R")
     if opts["calibration"] and opts["summary"] is None:
         raise SystemExit("--calibration_metrics needs --summary PREFIX: the prefix of the file it writes")
     if (opts["n_bins"] is not None or opts["fit_calibrator"] is not None) and not opts["calibration"]:
@@ -160,8 +187,9 @@ def _summary_options(flags, values, model_type="snv"):
     if opts["annotations"] is not None and opts["summary"] is None:
         raise SystemExit("--annotations needs --summary PREFIX: the prefix of the files it writes")
     if (opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"] and not opts["calibration"]
-            and opts["annotations"] is None):
-        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics or --annotations")
+            and opts["annotations"] is None and opts["simulate"] is None):
+        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics, --annotations "
+                         "or --simulate")
     if opts["annotations"] is not None:
         from mural_amd.tables import read_annotations
         try:
@@ -223,7 +251,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               kmer_strand=opts["strand"] if model_type == "indel" else None, motifs=opts["motifs"],
                               motif_indel=model_type == "indel", calibration=opts["calibration"],
                               calibration_bins=50 if opts["n_bins"] is None else opts["n_bins"], fit_calibrator=opts["fit_calibrator"],
-                              annotations=opts["annotations"], **sink_chain)
+                              annotations=opts["annotations"], simulate=opts["simulate"], simulate_seed=opts["seed"],
+                              simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
