@@ -856,6 +856,72 @@ size_t mural_summary_annot_workspace_bytes(int64_t n, int32_t n_class);
 int mural_summary_annot_rows(const MuralSummaryAnnotRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Expected and observed mutations per transcript by consequence of a shard while it is on the device
+ * (SummarySink(transcripts=...) in flight, tables.consequence_table from a written table; csrc/summary_conseq.hip;
+ * mural_amd.summaries.summary_conseq_host is the specification).  One call takes the SNV rows (n_class == 4) of a part of ONE
+ * chromosome, ascending in start (equal starts are legal), and that chromosome's CDS segments as tables.read_transcripts
+ * lists them: segment s is [seg_b0[s], seg_b1[s]) of transcript seg_tx[s], seg_cds0[s] the CDS offset of its first base in
+ * transcript orientation (its last genomic base on a '-' transcript), seg_prev / seg_next the indices of the transcript's
+ * neighbouring segments in that orientation (-1 at the ends); tx_strand [n_transcripts] (non-zero: '-') and tx_cds_len
+ * [n_transcripts] are global.  For row i at q = start[i] and every segment with seg_b0 <= q < seg_b1:
+ *   g = the reference base at q, r = the row's own base (complemented where strand[i] != 0); class c = 1 .. 3 is the
+ *   substitution r > alt_order[r][c - 1] on the row's strand; x = the CDS offset of q; the codon is offsets 3 floor(x / 3) ..
+ *   + 2, mapped to genomic positions over seg_prev / seg_next (at most two hops each) and read 5' -> 3' on the
+ *   transcript's strand; aa [64] is indexed by 16 b0 + 4 b1 + b2 (A0 C1 G2 T3), '*' a stop.  All three classes go to bin 4
+ *   (unresolved) where 3 floor(x / 3) + 2 >= tx_cds_len, a codon base is masked or lies outside the record, or a position is
+ *   not found; otherwise class c goes to bin 0 (aa_ref == aa_alt), 2 (aa_alt == '*'), 3 (aa_ref == '*') or 1.
+ *   table [n_transcripts][5][3] of unsigned 64-bit cells: cell [t][b] += { 1 where label[i] == c, hi of prob[i][c], lo of
+ *     prob[i][c] } per (row, c) routed to bin b, the limbs of mural_summary_kmer_rows (q = rne(p * 2^71)); on return
+ *     lo < 2^40; zeroed by the caller once -- the transcript ids are global, one table serves every chromosome and part;
+ *   rows [n_transcripts][2] += { rows inside the CDS, rows of label 0 among them };
+ *   class 0's probability is never read; a row counts once per transcript that covers it; both tables are a function of
+ *   the SET of rows alone, bit for bit;
+ *   status (device int32): bit 0 a negative start, bit 1 a label outside 0 .. 3 (or no whole number), bit 3 a probability
+ *     of a class >= 1 that is NaN, negative or above 1 -- such rows are skipped; bit 2 a start below the row before it
+ *     inside the call: the tables' content is then unspecified (nothing is read or written out of bounds).  A segment
+ *     whose transcript is outside 0 .. n_transcripts - 1 is skipped.
+ * strand: dev uint8 [n] or NULL for all '+'.  alt_order: each row names the three other bases once (MURAL_E_INVALID
+ * otherwise).  The segments' row ranges are cut into chunks of at most mural_summary_conseq_chunk_rows() rows, listed by an
+ * exclusive scan of the chunk counts (one workgroup of mural_summary_conseq_scan_threads() threads, a run of segments
+ * each), and a grid of at most mural_summary_conseq_grid_waves() waves strides over the chunks.  n <= 2^31 and n_segments <=
+ * 2^22 per call (MURAL_E_INVALID above: the bound that keeps a cell's lo limb below 2^63 until the fold that ends the call).
+ * ws: mural_summary_conseq_workspace_bytes(n_segments) bytes (24 per segment), 8-byte aligned; MURAL_E_WORKSPACE when
+ * smaller.  n == 0 or n_segments == 0 launches nothing.  Launches on `stream`, no synchronisation, no read-back, no
+ * floating-point atomics.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const MuralGenome* genome; /* the chromosome of the rows */
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. 3 are read                  */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const uint8_t* strand;     /* dev [n], 1 = '-', or NULL */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_transcripts;                   /* n_class == 4 */
+  const int64_t* seg_b0;     /* dev [n_segments] */
+  const int64_t* seg_b1;     /* dev [n_segments] */
+  const int64_t* seg_cds0;   /* dev [n_segments] */
+  const int32_t* seg_tx;     /* dev [n_segments] */
+  const int32_t* seg_prev;   /* dev [n_segments] */
+  const int32_t* seg_next;   /* dev [n_segments] */
+  int64_t n_segments;
+  const uint8_t* tx_strand;  /* dev [n_transcripts] */
+  const int64_t* tx_cds_len; /* dev [n_transcripts] */
+  uint8_t aa[64];
+  uint8_t alt_order[4][3];
+  uint8_t reserved[4];
+  uint64_t* table;           /* dev [n_transcripts][5][3] */
+  uint64_t* rows;            /* dev [n_transcripts][2] */
+  int32_t* status;           /* dev [1] */
+} MuralSummaryConseqRows;
+int64_t mural_summary_conseq_chunk_rows(void);
+int64_t mural_summary_conseq_grid_waves(void);
+int32_t mural_summary_conseq_scan_threads(void);
+size_t mural_summary_conseq_workspace_bytes(int64_t n_segments);
+int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Mutation sets drawn from the rates of a shard while it is on the device (SummarySink(simulate=R, ...) in flight,
  * tables.simulate_table from a written table; csrc/simulate.hip).  The draw is stateless and integer
  * (mural_amd.summaries.simulate_rows_host is its specification): Philox4x32-10 with key (seed lo, seed hi) and counter

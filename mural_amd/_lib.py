@@ -128,6 +128,16 @@ class MuralSummaryAnnotRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSummaryConseqRows(C.Structure):
+    _fields_ = [("genome", C.POINTER(MuralGenome)), ("prob", C.c_void_p), ("prob_f64", C.c_int32), ("label_kind", C.c_int32),
+                ("prob_stride", C.c_int64), ("start", C.c_void_p), ("strand", C.c_void_p), ("label", C.c_void_p), ("n", C.c_int64),
+                ("n_class", C.c_int32), ("n_transcripts", C.c_int32), ("seg_b0", C.c_void_p), ("seg_b1", C.c_void_p),
+                ("seg_cds0", C.c_void_p), ("seg_tx", C.c_void_p), ("seg_prev", C.c_void_p), ("seg_next", C.c_void_p),
+                ("n_segments", C.c_int64), ("tx_strand", C.c_void_p), ("tx_cds_len", C.c_void_p), ("aa", C.c_uint8 * 64),
+                ("alt_order", (C.c_uint8 * 3) * 4), ("reserved", C.c_uint8 * 4), ("table", C.c_void_p), ("rows", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 class MuralSimulateAnnotRows(C.Structure):
     _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
                 ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("n_rep", C.c_int32), ("seed", C.c_uint64),
@@ -298,6 +308,11 @@ PROTOTYPES = {
     "mural_summary_annot_fold_pieces": (I64, []),
     "mural_summary_annot_workspace_bytes": (C.c_size_t, [I64, I32]),
     "mural_summary_annot_rows": (C.c_int, [C.POINTER(MuralSummaryAnnotRows), VP, C.c_size_t, VP]),
+    "mural_summary_conseq_chunk_rows": (I64, []),
+    "mural_summary_conseq_grid_waves": (I64, []),
+    "mural_summary_conseq_scan_threads": (I32, []),
+    "mural_summary_conseq_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_summary_conseq_rows": (C.c_int, [C.POINTER(MuralSummaryConseqRows), VP, C.c_size_t, VP]),
     "mural_simulate_chunk_rows": (I64, []),
     "mural_simulate_grid_waves": (I64, []),
     "mural_simulate_scan_threads": (I32, []),

@@ -1,7 +1,7 @@
 """Genome summaries reduced in flight from the shards of a file-level prediction: the numpy "host twins" that specify the device
-reductions (csrc/summary.hip, csrc/summary_kmer.hip, csrc/summary_calib.hip, csrc/summary_annot.hip) and ``SummarySink``, the shard
+reductions (csrc/summary.hip, csrc/summary_kmer.hip, csrc/summary_calib.hip, csrc/summary_annot.hip, csrc/summary_conseq.hip) and ``SummarySink``, the shard
 consumer that runs one reducer per summary kind -- window tables and totals, k-mer tables, motif tables, calibration metrics with the
-calibrator fit, annotation tables."""
+calibrator fit, annotation tables, consequence tables."""
 import ctypes as C
 import os
 import zlib
@@ -14,7 +14,8 @@ from . import _lib
 from .calibration import calibrate_device, dirichlet_calibrate, save_dirichlet_calibrator
 from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
 from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds, shard_name, strand_u8
-from .tables import (annotation_meta, annotation_output_names, simulation_bed_name, simulation_bed_text, simulation_output_name,
+from .tables import (annotation_meta, annotation_output_names, check_alt_order, consequence_output_name, consequence_table_from_sums,
+                     read_transcripts, write_consequence_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
                      write_simulation_outputs, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
                      strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs)
@@ -356,6 +357,151 @@ def annot_table_from_sums(table, n_class):
     hi, lo = table[:, 1].ravel().tolist(), table[:, 2].ravel().tolist()      # (one flat pass: there may be 10^5 names)
     out[:, 1 + nc:] = np.array([((h << _KMER_LO_BITS) + l) / den for h, l in zip(hi, lo)], np.float64).reshape(table.shape[0], nc)
     return out
+
+
+# ---- consequence tables (csrc/summary_conseq.hip: mural_summary_conseq_rows): the k-mer cells per transcript and consequence ---------------
+_CONSEQ_PAIRS = 1 << 20            # (row, segment) pairs of one vectorised pass here
+_CONSEQ_STOP = ord("*")
+
+
+def _conseq_row_checks(prob, start, label):
+    """(hi, lo [n][3] of classes 1 .. 3, integer labels, rows that count, status bits): class 0's probability is not read."""
+    label = np.asarray(label)
+    hi, lo, bad_p = kmer_quantise(np.asarray(prob)[:, 1:4])
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= 4) | (lab != label)
+    bad_start, bad_prob = start < 0, bad_p.any(axis=1)
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    return hi, lo, lab, ~(bad_label | bad_start | bad_prob), status
+
+
+def summary_conseq_host(genome, prob, start, strand, label, segments, n_transcripts, aa=None, alt_order=None, into=None, n_class=4):
+    """The numpy twin of ``mural_summary_conseq_rows`` -- and its specification -- for SNV rows (any order) of one chromosome:
+    (table uint64 [n_transcripts][5][3], rows uint64 [n_transcripts][2], status).  `segments`: the chromosome's dict of
+    ``tables.read_transcripts`` (or None); `aa`: uint8 [64] (``tables.check_codon_table``; None: the standard code); `alt_order`:
+    ``tables.check_alt_order``'s argument; `strand`: 1 / '-' where the row is on the reverse strand, None for all '+'.
+
+    For row i at q = start[i] and every segment with seg_b0 <= q < seg_b1: g = the reference base at q, r = the row's own base
+    (comp(g) where strand[i]); class c = 1 .. 3 is the substitution r > alt_order[r][c - 1] on the row's strand, complemented onto the
+    reference strand where strand[i]; x = seg_cds0 + (q - seg_b0) on a '+' transcript, seg_cds0 + (seg_b1 - 1 - q) on a '-' one; the
+    codon is offsets 3 floor(x / 3) .. + 2, mapped to genomic positions over seg_prev / seg_next (at most two hops each), complemented
+    for a '-' transcript and read 5' -> 3'.  All three classes go to bin 4 (unresolved) when 3 floor(x / 3) + 2 >= tx_cds_len, a codon
+    base is masked (N or IUPAC) or a codon position falls outside the record; otherwise class c goes to bin 0 (synonymous: aa_ref ==
+    aa_alt, stop -> stop included), 2 (stop gained: aa_alt == '*'), 3 (stop lost: aa_ref == '*') or 1 (missense).  Cell [t][b] += {label
+    == c, hi(p_c), lo(p_c)} (the limbs of ``kmer_quantise``) per (row, c) routed to bin b of transcript t; rows[t] += {1, label == 0}
+    per row inside t's CDS.  A row counts once per transcript that covers it; integer sums, so both tables are a function of the SET of
+    rows, bit for bit; on return lo < 2^40.  `into`: (table, rows) of earlier parts and chromosomes to add to, in place.  Status bits: 1
+    a negative start, 2 a label outside 0 .. 3, 8 a probability of a class >= 1 that is NaN, negative or above 1; such rows are
+    skipped."""
+    from .tables import check_alt_order, check_codon_table
+    if int(n_class) != 4:
+        raise ValueError("the consequence table takes SNV rows of 4 classes (INDEL tables are out of scope)")
+    n_tx = int(n_transcripts)
+    aa = check_codon_table(aa).astype(np.int64)
+    alt_of = check_alt_order(alt_order).astype(np.int64)
+    start = np.asarray(start, np.int64)
+    hi, lo, lab, ok, status = _conseq_row_checks(prob, start, label)
+    table, rows = (np.zeros((n_tx, 5, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if into is None else into
+    if segments is None or len(segments["seg_b0"]) == 0 or not ok.any():
+        return table, rows, status
+    rs = np.zeros(len(start), np.int64) if strand is None else strand_u8(strand).astype(np.int64)
+    order = np.argsort(start[ok], kind="stable")
+    hi, lo, start, lab, rs = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order], rs[ok][order]
+    b0, b1, cds0 = (np.asarray(segments[key], np.int64) for key in ("seg_b0", "seg_b1", "seg_cds0"))
+    seg_tx, prev, nxt = (np.asarray(segments[key], np.int64) for key in ("seg_tx", "seg_prev", "seg_next"))
+    tx_minus, tx_len = np.asarray(segments["tx_strand"]) != 0, np.asarray(segments["tx_cds_len"], np.int64)
+    packed, nmask, L = _host_genome(genome)
+    i0 = np.searchsorted(start, b0, "left")
+    i1 = np.maximum(np.searchsorted(start, b1, "left"), i0)
+    n_in = i1 - i0
+    ends = np.cumsum(n_in)
+    flat_table, flat_rows = table.reshape(-1), rows.reshape(-1)
+    for p0 in range(0, int(ends[-1]), _CONSEQ_PAIRS):
+        pair = np.arange(p0, min(p0 + _CONSEQ_PAIRS, int(ends[-1])), dtype=np.int64)
+        s = np.searchsorted(ends, pair, "right")                       # the pair's segment
+        i = i0[s] + (pair - (ends[s] - n_in[s]))                       # and its row
+        q, tx = start[i], seg_tx[s]
+        minus = tx_minus[tx]
+        x = cds0[s] + np.where(minus, b1[s] - 1 - q, q - b0[s])
+        cs = x - x % 3
+        found = cs + 2 < tx_len[tx]
+        codon = np.zeros(len(pair), np.int64)
+        for j in range(3):
+            o, cur = cs + j, s.copy()
+            for _ in range(2):
+                c0, ln = cds0[cur], b1[cur] - b0[cur]
+                hop = np.where(o < c0, prev[cur], np.where(o >= c0 + ln, nxt[cur], cur))
+                found &= hop >= 0
+                cur = np.where(hop >= 0, hop, cur)
+            c0 = cds0[cur]
+            found &= (o >= c0) & (o < c0 + b1[cur] - b0[cur]) & (seg_tx[cur] == tx)
+            pos = np.where(minus, b1[cur] - 1 - (o - c0), b0[cur] + (o - c0))
+            found &= (pos >= 0) & (pos < L)
+            at = np.where(found, pos, 0)
+            if L:
+                found &= ((nmask[at >> 5] >> (at & 31).astype(np.uint32)) & 1) == 0
+                code = ((packed[at >> 4] >> (2 * (at & 15)).astype(np.uint32)) & 3).astype(np.int64)
+            else:
+                code = np.zeros(len(pair), np.int64)
+            codon = codon * 4 + np.where(minus, 3 - code, code)
+        codon = np.where(found, codon, 0)
+        sh = 2 * (2 - (x - cs))
+        own_tx = (codon >> sh) & 3
+        flip = minus != (rs[i] != 0)
+        r = np.where(flip, 3 - own_tx, own_tx)
+        cell = tx * 15
+        for c in range(3):
+            alt = alt_of[r, c]
+            alt_tx = np.where(flip, 3 - alt, alt)
+            a_ref, a_alt = aa[codon], aa[(codon & ~(3 << sh)) | (alt_tx << sh)]
+            b = np.where(a_ref == a_alt, 0, np.where(a_alt == _CONSEQ_STOP, 2, np.where(a_ref == _CONSEQ_STOP, 3, 1)))
+            b = np.where(found, b, 4)
+            np.add.at(flat_table, cell + 3 * b, (lab[i] == c + 1).astype(np.uint64))
+            np.add.at(flat_table, cell + 3 * b + 1, hi[i, c])
+            np.add.at(flat_table, cell + 3 * b + 2, lo[i, c])
+        np.add.at(flat_rows, 2 * tx, np.uint64(1))
+        np.add.at(flat_rows, 2 * tx + 1, (lab[i] == 0).astype(np.uint64))
+        _conseq_fold(table)
+    return table, rows, status
+
+
+def _conseq_fold(table):
+    """Carry the lo limbs' overflow into hi: table [transcripts][5][3] uint64, in place."""
+    table[:, :, 1] += table[:, :, 2] >> np.uint64(_KMER_LO_BITS)
+    table[:, :, 2] &= _KMER_LO_MASK
+    return table
+
+
+def conseq_rows_device(acc, name, segments, n_transcripts, aa, alt_order, genome_struct, dev, *, prob, prob_f64, prob_stride, start,
+                       strand, label, label_kind, n):
+    """One ``mural_summary_conseq_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 15],
+    rows int64 [n_transcripts * 2], status int32 [1], segments {chromosome: device arrays}, ws): the chromosome's segment arrays are
+    uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --, the workspace grows as needed."""
+    lib = _lib.lib()
+    on_dev = acc["segments"].get(name)
+    if on_dev is None:
+        keys = ("seg_b0", "seg_b1", "seg_cds0", "seg_tx", "seg_prev", "seg_next")
+        if "tx" not in acc:
+            pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in ("tx_strand", "tx_cds_len"))
+            acc["tx"] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+        pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in keys)
+        on_dev = acc["segments"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    n_seg = int(on_dev[0].shape[0])
+    need = int(lib.mural_summary_conseq_workspace_bytes(n_seg))
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _lib.MuralSummaryConseqRows()
+    s.genome = C.pointer(genome_struct)
+    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
+    s.start, s.strand, s.label, s.label_kind = start, strand, label, int(label_kind)
+    s.n, s.n_class, s.n_transcripts = int(n), 4, int(n_transcripts)
+    s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in on_dev[:6])
+    s.n_segments = n_seg
+    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
+    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
+    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+    s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
+    _lib.check(lib.mural_summary_conseq_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
 
 
 # ---- mutation sets drawn from the rates (csrc/simulate.hip: mural_simulate_annot_rows, mural_simulate_rows) -----------------------------
@@ -1009,6 +1155,88 @@ class _AnnotationReducer:
         write_annotation_outputs(*result[self.name], k, out_prefix)
 
 
+class _ConsequenceReducer:
+    """Expected and observed mutations per transcript of a BED12 file by consequence (``summary_conseq_host`` is the rule): ONE integer
+    table [transcripts][5][3] + row counters [transcripts][2] for the whole run on the host and one pair per device -- the transcript
+    ids are global --, a chromosome's segment arrays uploaded the first time the chromosome arrives on a device, read back once.  A
+    chromosome without CDS segments reduces nothing."""
+    name = "consequences"
+
+    def __init__(self, transcripts, genome, codon_table, alt_order, labels=True):
+        self.names, self.meta, self.segments = read_transcripts(transcripts, codon_table)
+        self.alt_order, self.labels = check_alt_order(alt_order), bool(labels)
+        if genome is None:
+            raise ValueError("SummarySink(transcripts=...) needs genome=: a callable chromosome name -> packed genome")
+        self.genome = genome
+        self.reset()
+
+    def reset(self):
+        self.host = None               # (table, rows) of the host shards
+        self.dev = {}                  # device -> dict(table, rows, status, segments {chromosome: device arrays}, tx, ws)
+        self.sums = None
+
+    def _check(self, k):
+        if k != 4:
+            raise ValueError(f"SummarySink(transcripts=...) takes SNV rows of 4 classes (got {k}; INDEL tables are out of scope)")
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        self._check(k)
+        segments = self.segments.get(name)
+        if segments is None:
+            return 0
+        if self.host is None:
+            self.host = (np.zeros((len(self.names), 5, 3), np.uint64), np.zeros((len(self.names), 2), np.uint64))
+        return summary_conseq_host(self.genome(name), prob, start, strand, label, segments, len(self.names), self.meta["aa"],
+                                   self.alt_order, into=self.host)[2]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the reduction of a part behind its forward, into the device's one pair of tables."""
+        self._check(k)
+        segments = self.segments.get(name)
+        if segments is None or start.shape[0] == 0:
+            return None
+        dev, n_tx = prob.device, len(self.names)
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(n_tx * 15, dtype=torch.int64, device=dev),
+                                       rows=torch.zeros(n_tx * 2, dtype=torch.int64, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev), segments={}, ws=None)
+        genome = self.genome(name)
+        conseq_rows_device(acc, name, segments, n_tx, self.meta["aa"], self.alt_order, genome.as_struct(dev), dev, prob=prob.data_ptr(),
+                           prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
+                           strand=strand.data_ptr(), label=label.data_ptr(), label_kind=_LABEL_KIND[label.dtype], n=start.shape[0])
+        return genome
+
+    def _added(self, states):
+        out = None
+        for st in states:
+            if st is not None:
+                out = (st[0].copy(), st[1].copy()) if out is None else (_conseq_fold(np.add(out[0], st[0], out=out[0])),
+                                                                        np.add(out[1], st[1], out=out[1]))
+        return out
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, mine, n_tx = 0, [self.host], len(self.names)
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine.append((acc["table"].cpu().numpy().view(np.uint64).reshape(n_tx, 5, 3),
+                         acc["rows"].cpu().numpy().view(np.uint64).reshape(n_tx, 2)))
+        return self._added(mine), status
+
+    def merge(self, states, k):
+        return self._added(states)
+
+    def finish(self, state, k, result):
+        n_tx = len(self.names)
+        self.sums = (np.zeros((n_tx, 5, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if state is None else state
+        result[self.name] = (list(self.names), self.meta, consequence_table_from_sums(*self.sums))
+
+    def write(self, out_prefix, result, k, written):
+        written.append(consequence_output_name(out_prefix))
+        write_consequence_outputs(*result[self.name], out_prefix, labels=self.labels)
+
+
 class _SimulationReducer:
     """Mutation sets drawn from the rates (``simulate_rows_host`` is the rule): per name of the annotation reducer beside it the counts
     of every class in each of `n_rep` replicates -- ONE uint32 table [names][n_class - 1][n_rep] on the host and one per device, the
@@ -1495,6 +1723,18 @@ class SummarySink:
     shard order, the ranks' parts of a chromosome in rank order.  The sink takes
     the chromosomes one after the other.
 
+    `transcripts`: a BED12 path or ``tables.read_transcripts``' result: per transcript the expected and observed mutations of the SNV
+    rows (4 classes) inside its CDS, split by what each of a row's three substitutions does to its codon -- synonymous, missense, stop
+    gained, stop lost, or unresolved (an incomplete or masked codon) --, alone or beside the other summaries; it needs `genome`.
+    `codon_table`: 64 characters indexed by 16 b0 + 4 b1 + b2 (A0 C1 G2 T3, '*' a stop; default the standard code); `alt_order`: the
+    alternative base of class 1 .. 3 per own base (``tables.check_alt_order``; default the other bases in A < C < G < T order).  Device
+    parts go through ``mural_summary_conseq_rows`` (csrc/summary_conseq.hip), host shards through
+    ``summary_conseq_host``: one integer table for the run, read back once at close(), exchanged between ranks in the same collective and
+    added -- a function of the set of rows alone, bit for bit.  result()["consequences"] = (names, meta, table float64 [n][12] of
+    ``tables.consequence_table_from_sums``); close() writes ``{out_prefix}.consequence.mut_rates.tsv``
+    (``tables.write_consequence_outputs``; `transcript_labels=False` says that the rows carry no labels: the observed columns are NA);
+    ``consequence_sums()`` has the integers.
+
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
 
@@ -1503,7 +1743,8 @@ class SummarySink:
     def __init__(self, out_prefix=None, windows=(), benchmark_regions=None, ratio_cutoff=0.2, poisson=False, dirichlet_weights=None,
                  group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
                  calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
-                 simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True):
+                 simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True, transcripts=None,
+                 codon_table=None, alt_order=None, transcript_labels=True):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -1535,6 +1776,11 @@ class SummarySink:
                                              simulate_table_bytes_max, self.out_prefix, simulate_labels, self.rank, self.world))
         elif simulate_seed is not None or tuple(simulate_write):
             raise ValueError("simulate_seed and simulate_write go with simulate=R")
+        self.transcripts = transcripts is not None
+        if self.transcripts:
+            active.append(_ConsequenceReducer(transcripts, genome, codon_table, alt_order, transcript_labels))
+        elif codon_table is not None or alt_order is not None:
+            raise ValueError("codon_table and alt_order go with transcripts=")
         self._reducers = {r.name: r for r in active}
         self.rows = 0
         self._n_class = None
@@ -1552,7 +1798,7 @@ class SummarySink:
         """Calibrate and order the part, reduce it in every reducer."""
         prob = host_calibrate(np.asarray(shard["prob"])[:, :k], self.poisson, self.dirichlet_weights)
         start = np.asarray(shard["start"])
-        cols = [prob, start, np.asarray(shard["end"]), strand_u8(shard["strand"]) if (self.kmers or self.simulate) else None,
+        cols = [prob, start, np.asarray(shard["end"]), strand_u8(shard["strand"]) if (self.kmers or self.simulate or self.transcripts) else None,
                 np.asarray(shard["label"])]
         if not shard.get("aligned"):
             perm = np.argsort(start, kind="stable")
@@ -1580,7 +1826,7 @@ class SummarySink:
             start, end = to(shard["start"], torch.int64), to(shard["end"], torch.int64)
             label = shard["label"]
             label = to(label, label.dtype if isinstance(label, torch.Tensor) and label.dtype in (torch.int32, torch.int64) else torch.float32)
-            strand = to(strand_u8(shard["strand"]), torch.uint8) if (self.kmers or self.simulate) else None
+            strand = to(strand_u8(shard["strand"]), torch.uint8) if (self.kmers or self.simulate or self.transcripts) else None
             if not shard.get("aligned"):
                 perm = torch.sort(start, stable=True).indices
                 if self.parts:
@@ -1682,6 +1928,12 @@ class SummarySink:
         result()["annotations"] (``summary_annot_host``'s layout, the names in ``read_annotations``' order)."""
         self.result()
         return self._reducers["annotations"].sums
+
+    def consequence_sums(self):
+        """(table uint64 [transcripts][5][3] of label counts | sums of hi | sums of lo per bin, rows uint64 [transcripts][2]) after close():
+        the exact sums behind result()["consequences"] (``summary_conseq_host``'s layout, the transcripts in file order)."""
+        self.result()
+        return self._reducers["consequences"].sums
 
     def simulation_counts(self):
         """table uint32 [names][n_class - 1][simulate] after close(): the simulated count of every name, class >= 1 and replicate

@@ -683,6 +683,239 @@ def run_annotation_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# consequences: expected and observed mutations per transcript, split by what a substitution does to its codon
+# ------------------------------------------------------------------------------------------------------------------
+STANDARD_CODON_TABLE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"      # index 16 b0 + 4 b1 + b2, A0 C1 G2 T3
+CONSEQUENCES = ("syn", "mis", "stop_gained", "stop_lost")      # bins 0 .. 3 of the consequence table; bin 4 is `unresolved`
+_SEG_FIELDS = ("seg_b0", "seg_b1", "seg_cds0", "seg_tx", "seg_prev", "seg_next")
+
+
+def consequence_output_name(out_prefix):
+    return f"{out_prefix}.consequence.mut_rates.tsv"
+
+
+def check_codon_table(codon_table=None):
+    """uint8 [64] of a codon table: 64 characters indexed by 16 b0 + 4 b1 + b2 (A0 C1 G2 T3), '*' a stop; None: the standard code."""
+    if codon_table is None:
+        codon_table = STANDARD_CODON_TABLE
+    if isinstance(codon_table, np.ndarray):
+        codon_table = bytes(np.asarray(codon_table, np.uint8)).decode("latin-1")
+    text = codon_table.decode("ascii") if isinstance(codon_table, bytes) else str(codon_table)
+    if len(text) != 64 or not text.isascii() or any(ch.isspace() for ch in text):
+        raise ValueError("codon_table: 64 ASCII characters are required, indexed by 16 b0 + 4 b1 + b2 with A0 C1 G2 T3 ('*' marks a stop)")
+    return np.frombuffer(text.encode("ascii"), np.uint8).copy()
+
+
+def check_alt_order(alt_order=None):
+    """uint8 [4][3]: the alternative base of class c = 1 .. 3 of a row whose own base is r (A0 C1 G2 T3), on the row's strand.  None:
+    the three other bases in A < C < G < T order (A>C, A>G, A>T; ...).  A text spec names the 12 alternatives row by row
+    ("CGT,AGT,ACT,ACG" is the default; commas and blanks are optional).  A row that names r itself or repeats a base is refused."""
+    if alt_order is None:
+        out = np.array([[b for b in range(4) if b != r] for r in range(4)], np.uint8)
+    elif isinstance(alt_order, str):
+        text = "".join(ch for ch in alt_order.upper() if ch not in ", ;/")
+        if len(text) != 12 or set(text) - set("ACGT"):
+            raise ValueError(f"alt_order: 12 letters of ACGT are required, three per own base A, C, G, T (got {alt_order!r})")
+        out = np.array(["ACGT".index(ch) for ch in text], np.uint8).reshape(4, 3)
+    else:
+        out = np.asarray(alt_order)
+        if out.shape != (4, 3) or not np.issubdtype(out.dtype, np.integer) or (out < 0).any() or (out > 3).any():
+            raise ValueError("alt_order: an integer array [4][3] of base codes 0 .. 3 is required")
+        out = out.astype(np.uint8)
+    for r in range(4):
+        if sorted(out[r].tolist() + [r]) != [0, 1, 2, 3]:
+            raise ValueError(f"alt_order: the row of own base {'ACGT'[r]} must name the three other bases once each")
+    return out
+
+
+def _bed12_lines(source):
+    """(text line, where) of a BED12 source: a path (plain or gzip) or an open handle (text or bytes)."""
+    if hasattr(source, "read"):
+        name = getattr(source, "name", "<transcripts>")
+        for ln, line in enumerate(source, 1):
+            yield (line.decode() if isinstance(line, bytes) else line), f"{name}:{ln}"
+        return
+    path = os.fspath(source)
+    opener = gzip.open if _is_gzip(path) else open
+    with opener(path, "rt") as fh:
+        for ln, line in enumerate(fh, 1):
+            yield line, f"{path}:{ln}"
+
+
+def read_transcripts(source, codon_table=None):
+    """(names, meta, segments) of a BED12 transcript file (a path, plain or gzip; an open handle; or this function's own result, returned
+    as it is): chrom start end name score strand thickStart thickEnd rgb blockCount blockSizes blockStarts, trailing commas tolerated; the
+    lines ``read_regions`` skips are skipped.  A transcript's CDS segments are its blocks clipped to [thickStart, thickEnd), empty ones
+    dropped; a transcript without CDS (thickStart == thickEnd) stays, with zeros.  BED12 carries no frame: CDS offset 0 is the 5'-most
+    CDS base in transcript orientation (for strand '-' the last base of the last segment), and the trailing cds_length % 3 bases at the
+    3' end belong to no complete codon.  ValueError with file and line: a duplicate name, a strand other than + / -, blocks that overlap
+    or do not ascend, blocks that leave [start, end).
+      names: in file order;
+      meta: dict(chrom [n] list, strand uint8 [n] (1: '-'), cds_length int64 [n], n_segments int32 [n], aa uint8 [64] -- `codon_table`,
+        ``check_codon_table``);
+      segments[chrom]: dict of flat arrays sorted by (seg_b0, seg_b1, seg_tx): seg_b0, seg_b1 int64 (genomic, half-open), seg_cds0 int64
+        (the CDS offset of the segment's first base in transcript orientation), seg_tx int32 (the transcript's index in `names`),
+        seg_prev / seg_next int32 (the indices, in the same arrays, of the same transcript's neighbouring segments in transcript
+        orientation, -1 at the ends), and tx_strand uint8 / tx_cds_len int64 (meta's arrays: indexed by the global transcript id).
+    Transcripts overlap and nest freely, across strands too.  GTF / GFF input and explicit frames are out of scope."""
+    if isinstance(source, tuple) and len(source) == 3 and isinstance(source[1], dict) and "aa" in source[1]:
+        if codon_table is not None:
+            source = (source[0], dict(source[1], aa=check_codon_table(codon_table)), source[2])
+        return source
+    aa = check_codon_table(codon_table)
+    names, index, chroms, strands, cds_len, n_segs, per_chrom = [], set(), [], [], [], [], {}
+    for line, where in _bed12_lines(source):
+        if not line.strip() or line.startswith(("#", "track", "browser")):
+            continue
+        f = line.rstrip("\r\n").split("\t")
+        if len(f) < 12:
+            raise ValueError(f"{where}: a BED12 row needs 12 columns (got {len(f)})")
+        try:
+            start, end, thick0, thick1, n_blocks = int(f[1]), int(f[2]), int(f[6]), int(f[7]), int(f[9])
+            sizes = [int(v) for v in f[10].rstrip(",").split(",")] if f[10].strip(",") else []
+            offs = [int(v) for v in f[11].rstrip(",").split(",")] if f[11].strip(",") else []
+        except ValueError:
+            raise ValueError(f"{where}: a BED12 column that should be a number is not") from None
+        name = f[3]
+        if name in index:
+            raise ValueError(f"{where}: duplicate transcript name {name!r}")
+        if f[5] not in ("+", "-"):
+            raise ValueError(f"{where}: strand {f[5]!r} is neither + nor -")
+        if start < 0 or end < start:
+            raise ValueError(f"{where}: start {start} / end {end} out of order")
+        if len(sizes) != n_blocks or len(offs) != n_blocks:
+            raise ValueError(f"{where}: blockCount {n_blocks} against {len(sizes)} blockSizes and {len(offs)} blockStarts")
+        if not (thick0 == thick1 or (start <= thick0 < thick1 <= end)):
+            raise ValueError(f"{where}: thickStart {thick0} / thickEnd {thick1} outside [{start}, {end})")
+        at, segs = start, []
+        for size, off in zip(sizes, offs):
+            a, b = start + off, start + off + size
+            if size <= 0 or a < start or b > end:
+                raise ValueError(f"{where}: block [{a}, {b}) leaves [{start}, {end})")
+            if a < at:
+                raise ValueError(f"{where}: blocks overlap or do not ascend at [{a}, {b})")
+            at = b
+            a, b = max(a, thick0), min(b, thick1)
+            if a < b:
+                segs.append((a, b))
+        t = len(names)
+        index.add(name)
+        names.append(name)
+        minus = f[5] == "-"
+        total = sum(b - a for a, b in segs)
+        chroms.append(f[0])
+        strands.append(int(minus))
+        cds_len.append(total)
+        n_segs.append(len(segs))
+        done = 0                          # CDS bases 5' of the segment, in transcript orientation
+        for j, (a, b) in (reversed(list(enumerate(segs))) if minus else enumerate(segs)):
+            per_chrom.setdefault(f[0], []).append((a, b, t, done, j))
+            done += b - a
+    if len(names) >= 2 ** 31:
+        raise ValueError("transcripts: 2^31 names or more")
+    meta = dict(chrom=chroms, strand=np.asarray(strands, np.uint8), cds_length=np.asarray(cds_len, np.int64),
+                n_segments=np.asarray(n_segs, np.int32), aa=aa)
+    segments = {}
+    for chrom, rows in per_chrom.items():
+        rows.sort()
+        arr = np.asarray(rows, np.int64).reshape(-1, 5)
+        tx, rank = arr[:, 2], arr[:, 4]
+        where = {(int(t), int(j)): i for i, (t, j) in enumerate(zip(tx, rank))}
+        lower = np.array([where.get((int(t), int(j) - 1), -1) for t, j in zip(tx, rank)], np.int32)      # the neighbour at lower coordinates
+        upper = np.array([where.get((int(t), int(j) + 1), -1) for t, j in zip(tx, rank)], np.int32)
+        minus = meta["strand"][tx] != 0
+        segments[chrom] = dict(seg_b0=arr[:, 0].copy(), seg_b1=arr[:, 1].copy(), seg_cds0=arr[:, 3].copy(), seg_tx=tx.astype(np.int32),
+                               seg_prev=np.where(minus, upper, lower).astype(np.int32), seg_next=np.where(minus, lower, upper).astype(np.int32),
+                               tx_strand=meta["strand"], tx_cds_len=meta["cds_length"])
+    return names, meta, segments
+
+
+def consequence_table_from_sums(table, rows):
+    """float64 [n][3 + 2 * 4 + 1] per transcript from the integer sums of ``summary_conseq_host`` / ``mural_summary_conseq_rows``: n_rows,
+    n_nonmut, n_unresolved (the mutated rows of bin 4), then expected, observed per consequence of ``CONSEQUENCES`` and the expected
+    value of bin 4.  A probability sum is (hi * 2^40 + lo) / 2^71, formed from Python integers (true division rounds correctly)."""
+    table, rows = np.asarray(table, np.uint64).reshape(-1, 5, 3), np.asarray(rows, np.uint64).reshape(-1, 2)
+    out = np.zeros((table.shape[0], 12))
+    out[:, 0], out[:, 1], out[:, 2] = rows[:, 0], rows[:, 1], table[:, 4, 0]
+    den = 1 << 71
+    hi, lo = table[:, :, 1].ravel().tolist(), table[:, :, 2].ravel().tolist()
+    exp = np.array([((h << 40) + l) / den for h, l in zip(hi, lo)], np.float64).reshape(-1, 5)
+    out[:, 3:11:2], out[:, 4:11:2], out[:, 11] = exp[:, :4], table[:, :4, 0], exp[:, 4]
+    return out
+
+
+def write_consequence_outputs(names, meta, table, out_prefix, labels=True):
+    """``{out_prefix}.consequence.mut_rates.tsv`` from a consequence table (``consequence_table``'s triple, or the one a ``SummarySink``
+    reduced in flight): a line per transcript in file order -- name, chrom, strand, cds_length, n_rows (the rows inside the CDS), n_nonmut
+    (those of label 0), n_unresolved (the mutated rows in incomplete or masked codons), then expected_* and observed_* for syn, mis,
+    stop_gained and stop_lost.  `labels=False`: the rows carried no labels, the observed_* columns are NA.  Returns the path."""
+    table = np.asarray(table, np.float64).reshape(len(names), 12)
+    header = ["name", "chrom", "strand", "cds_length", "n_rows", "n_nonmut", "n_unresolved"]
+    for what in CONSEQUENCES:
+        header += [f"expected_{what}", f"observed_{what}"]
+    rows = []
+    for j, nm in enumerate(names):
+        row = [nm, meta["chrom"][j], "-" if meta["strand"][j] else "+", str(int(meta["cds_length"][j]))] + [str(int(v)) for v in table[j, :3]]
+        for b in range(4):
+            row += [_float_text(table[j, 3 + 2 * b]), str(int(table[j, 4 + 2 * b])) if labels else "NA"]
+        rows.append(row)
+    path = consequence_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    return path
+
+
+def consequence_table(pred_file, transcripts, ref_genome, codon_table=None, alt_order=None, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, meta, table float64 [n][12] -- ``consequence_table_from_sums``) per transcript of `transcripts` (a BED12 path or
+    ``read_transcripts``' result) from a written SNV prediction table (4 classes): what ``SummarySink(transcripts=...)`` reduces in
+    flight, through the same entry point (``mural_summary_conseq_rows``), chromosome run by chromosome run of each chunk.  The rows of a
+    chromosome must ascend in start, as ``predict`` writes them; the codons are read from `ref_genome` (a FASTA path)."""
+    from .data.ingest import read_fasta, scan_fasta
+    from .summaries import _SUMMARY_STATUS, conseq_rows_device      # (summaries imports this module: not at the top)
+    names, meta, segments = read_transcripts(transcripts, codon_table)
+    alt = check_alt_order(alt_order)
+    n_tx = len(names)
+    fasta_names = {r.name for r in scan_fasta(ref_genome)}
+    with TableReader(pred_file, 4, chunk_bytes) as rd:
+        dev = rd.device
+        acc = dict(table=torch.zeros(max(n_tx, 1) * 15, dtype=torch.int64, device=dev), rows=torch.zeros(max(n_tx, 1) * 2, dtype=torch.int64, device=dev),
+                   status=torch.zeros(1, dtype=torch.int32, device=dev), segments={}, ws=None)
+        genomes = {}
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in segments or b == a:
+                    continue
+                if name not in genomes:
+                    if name not in fasta_names:
+                        raise ValueError(f"Chromosome {name} not found in {ref_genome} (prediction table line {c.row0 + a + 2})")
+                    genomes[name] = read_fasta(ref_genome, dev, names={name})[name]
+                conseq_rows_device(acc, name, segments[name], n_tx, meta["aa"], alt, genomes[name].as_struct(), dev,
+                                   prob=c.prob + 8 * 4 * a, prob_f64=1, prob_stride=4, start=c.start + 8 * a, strand=c.strand + a,
+                                   label=c.mut_type + 4 * a, label_kind=1, n=b - a)
+        bits = int(acc["status"].item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table = acc["table"].cpu().numpy().view(np.uint64)[:n_tx * 15].reshape(n_tx, 5, 3)
+        counts = acc["rows"].cpu().numpy().view(np.uint64)[:n_tx * 2].reshape(n_tx, 2)
+    return names, meta, consequence_table_from_sums(table, counts)
+
+
+def run_consequence_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.transcripts, args.ref_genome, args.out_prefix; optional args.codon_table,
+    args.alt_order): per transcript of the BED12 file the expected and observed mutations of the table's rows inside its CDS by
+    consequence; writes {out_prefix}.consequence.mut_rates.tsv."""
+    assert getattr(args, "transcripts", None) is not None, "--transcripts is required for the consequence table"
+    assert getattr(args, "ref_genome", None) is not None, "--ref_genome is required for the consequence table"
+    names, meta, table = consequence_table(os.fspath(args.pred_file), args.transcripts, os.fspath(args.ref_genome),
+                                           getattr(args, "codon_table", None), getattr(args, "alt_order", None), chunk_bytes)
+    return write_consequence_outputs(names, meta, table, args.out_prefix)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # simulation: mutation sets drawn from the rates, per-name empirical p-values
 # ------------------------------------------------------------------------------------------------------------------
 def simulation_output_name(out_prefix):

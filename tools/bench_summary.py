@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Fourteen legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Sixteen legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -24,8 +24,13 @@ alternating, --repeats timed runs each after one warm-up run each:
   m  sim100      leg k with simulate=100, simulate_seed=1 as well: the counts of 100 mutation sets drawn from the
                  rates per name; the comparison is leg k, the same run without it
   n  sim1000     leg k with simulate=1000 (a table of 240 MB, below the sink's cap)
+  o  conseq       leg b with transcripts= as well: expected and observed mutations per transcript by consequence,
+                  leg k's 200 000 pieces regrouped into 20 000 ten-exon transcripts on alternating strands; the comparisons are leg b, the
+                  same run without it, and leg k
+  p  conseq_tools the route to o's table without the sink: leg a's table, then tables.consequence_table on it (the FASTA packed again)
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
-h's and leg k's annotation table with leg l's, within the table's four digits (names, order and counts exactly)."""
+h's, leg k's annotation table with leg l's and leg o's consequence table with leg p's, within the table's four digits (names, order and
+counts exactly)."""
 import json
 import os
 import shutil
@@ -47,7 +52,8 @@ from mural_amd.predict import HipShardForward, SummarySink, TeeSink, TsvSink, pr
 WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
-LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000")
+LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000",
+        "conseq", "conseq_tools")
 SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
 ANNOT_NAMES, ANNOT_INTERVALS, ANNOT_BP, ANNOT_OVERLAP = 20_000, 10, 150, 0.05
 
@@ -63,6 +69,22 @@ def synthetic_annotations(bases, chrom="chr1"):
         at = g * span + (span // 2 if g % every == every - 1 else 0)
         rows += [(at + j * step, at + j * step + ANNOT_BP, "set%05d" % g) for j in range(ANNOT_INTERVALS)]
     return tables.read_annotations({chrom: rows})
+
+
+def synthetic_transcripts(bases, chrom="chr1"):
+    """``tables.read_transcripts``' result for the intervals of ``synthetic_annotations`` as ANNOT_NAMES transcripts of ANNOT_INTERVALS
+    exons each, all of it CDS, on alternating strands."""
+    import io
+    span = bases // ANNOT_NAMES
+    step = max(span // ANNOT_INTERVALS, 1)
+    every = int(round(1 / ANNOT_OVERLAP))
+    lines = []
+    for g in range(ANNOT_NAMES):
+        at = g * span + (span // 2 if g % every == every - 1 else 0)
+        end = at + (ANNOT_INTERVALS - 1) * step + ANNOT_BP
+        lines.append("\t".join([chrom, str(at), str(end), "tx%05d" % g, "0", "+-"[g & 1], str(at), str(end), "0", str(ANNOT_INTERVALS),
+                                ",".join([str(ANNOT_BP)] * ANNOT_INTERVALS), ",".join(str(j * step) for j in range(ANNOT_INTERVALS))]))
+    return tables.read_transcripts(io.StringIO("\n".join(lines) + "\n"))
 
 
 def main(argv):
@@ -85,6 +107,8 @@ def main(argv):
         kept, closes = {}, {}
         annot = synthetic_annotations(bases) if {"annot", "annot_tools", "sim100", "sim1000"} & set(legs) else None
 
+        transcripts = synthetic_transcripts(bases) if {"conseq", "conseq_tools"} & set(legs) else None
+
         def run(leg):
             split, extra = {}, {}
             torch.cuda.synchronize()
@@ -101,7 +125,9 @@ def main(argv):
                 summary = SummarySink(windows=WINDOWS, annotations=annot)
             if leg in SIM_REPLICATES:
                 summary = SummarySink(windows=WINDOWS, annotations=annot, simulate=SIM_REPLICATES[leg], simulate_seed=1, simulate_labels=False)
-            if leg in ("summary", "annot", "sim100", "sim1000") and "annot" in legs:      # close() alone, of every run: where leg k's host work would be
+            if leg == "conseq":
+                summary = SummarySink(windows=WINDOWS, transcripts=transcripts, genome=fwd.genome, transcript_labels=False)
+            if leg in ("summary", "annot", "sim100", "sim1000", "conseq") and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
                 plain_close = summary.close
 
                 def close_timed():
@@ -127,7 +153,7 @@ def main(argv):
             sink = {"calib": lambda: summary, "calib_fit": lambda: summary, "table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
                     "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out), "sim100": lambda: summary,
-                    "sim1000": lambda: summary}[leg]()
+                    "sim1000": lambda: summary, "conseq": lambda: summary, "conseq_tools": lambda: TsvSink(out)}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
                                         **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
@@ -160,6 +186,10 @@ def main(argv):
                 t1 = time.perf_counter()
                 kept["annot_tools"] = tables.annotation_table(out, annot, n_class)
                 extra["annotation_table"] = time.perf_counter() - t1
+            if leg == "conseq_tools":
+                t1 = time.perf_counter()
+                kept["conseq_tools"] = tables.consequence_table(out, transcripts, fa)
+                extra["consequence_table"] = time.perf_counter() - t1
             dt = time.perf_counter() - t0
             assert n == rows, (leg, n, rows)
             if summary is not None:
@@ -194,6 +224,11 @@ def main(argv):
         (na, ma, ta), (nd, md, td) = kept["annot"]["annotations"], kept["annot_tools"]
         agree = agree and na == nd and bool((ma == md).all()) and bool((ta[:, :k] == td[:, :k]).all())
         agree = agree and bool((abs(ta[:, k:] - td[:, k:]) <= 5e-4 * ta[:, k:]).all()) and bool(ta[:, 0].sum() > 0)
+    if {"conseq", "conseq_tools"} <= set(legs):
+        (na, _, ta), (nd, _, td) = kept["conseq"]["consequences"], kept["conseq_tools"]
+        counts, sums = [0, 1, 2, 4, 6, 8, 10], [3, 5, 7, 9, 11]
+        agree = agree and na == nd and bool((ta[:, counts] == td[:, counts]).all()) and bool(ta[:, 0].sum() > 0)
+        agree = agree and bool((abs(ta[:, sums] - td[:, sums]) <= 5e-4 * ta[:, sums]).all())
     rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in legs}
     med = {leg: rate[leg]["median"] for leg in legs}
     sec = {leg: statistics.median(seconds[leg]) for leg in legs}
@@ -208,6 +243,11 @@ def main(argv):
            "calib_over_summary": ratio("calib", "summary", med), "calib_fit_over_summary": ratio("calib_fit", "summary", med),
            "annot_over_summary": ratio("annot", "summary", med), "annot_tools_over_annot_seconds": ratio("annot_tools", "annot", sec),
            "sim100_over_annot": ratio("sim100", "annot", med), "sim1000_over_annot": ratio("sim1000", "annot", med),
+           "conseq_over_summary": ratio("conseq", "summary", med), "conseq_over_annot": ratio("conseq", "annot", med),
+           "conseq_tools_over_conseq_seconds": ratio("conseq_tools", "conseq", sec),
+           "consequences": {"transcripts": ANNOT_NAMES, "exons": ANNOT_INTERVALS, "bp": ANNOT_BP,
+                            "rows_in_a_cds": float(kept["conseq"]["consequences"][2][:, 0].sum()) if "conseq" in kept else None,
+                            "expected": kept["conseq"]["consequences"][2][:, 3:11:2].sum(axis=0).tolist() if "conseq" in kept else None},
            "simulated_draws": {leg: float(kept[leg]["simulation"][1].sum()) for leg in SIM_REPLICATES if leg in kept},
            "annotations": {"names": ANNOT_NAMES, "intervals": ANNOT_INTERVALS, "bp": ANNOT_BP,
                            "close_seconds": {leg: v[1:] for leg, v in closes.items()},      # (without the warm-up round's)

@@ -48,6 +48,15 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              (n + 1) / (R + 1); observed and the p-values are NA where the rows carry no
                                                              labels (--regions without --mutations).  --write_simulated r ..: replicate
                                                              r as PREFIX.sim{r}.mutations.bed, a list that --mutations reads
+  --summary PREFIX  --transcripts BED12 [--codon_table STR] [--alt_order SPEC]
+                                                             PREFIX.consequence.mut_rates.tsv: per transcript of the BED12 file the
+                                                             expected and observed mutations of the SNV rows inside its CDS, split into
+                                                             synonymous, missense, stop gained and stop lost (blocks clipped to
+                                                             thickStart .. thickEnd; offset 0 is the 5'-most CDS base).  STR: 64 amino
+                                                             acids indexed by 16 b0 + 4 b1 + b2 with A0 C1 G2 T3, * a stop (default the
+                                                             standard code); SPEC: the alternative base of mut_type 1, 2, 3 per own base
+                                                             A, C, G, T (default CGT,AGT,ACT,ACG); observed is NA where the rows carry
+                                                             no labels; not with --indel; alone or with the options above
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -62,7 +71,8 @@ from mural_amd.data import predict_bed, write_predictions  # noqa: E402
 from mural_amd.model.nn_utils import load_model  # noqa: E402
 
 _SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--annotations", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
-                    "--scale_factor", "--n_bins", "--fit_calibrator", "--simulate", "--seed", "--write_simulated")
+                    "--scale_factor", "--n_bins", "--fit_calibrator", "--simulate", "--seed", "--write_simulated", "--transcripts", "--codon_table",
+                    "--alt_order")
 _PAIR_OPTIONS = ("--model_set", "--scale_factors")      # NAME CLASS=VALUE [CLASS=VALUE ..]
 _VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _PAIR_OPTIONS + _SUMMARY_OPTIONS
 
@@ -151,7 +161,8 @@ def _summary_options(flags, values, model_type="snv"):
             "motifs": tuple(int(m) for m in values.get("--motif_length", [])), "calibration": "--calibration_metrics" in flags,
             "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str), "annotations": one("--annotations", str),
             "simulate": one("--simulate", int), "seed": one("--seed", lambda v: int(v, 0)),
-            "write_simulated": tuple(int(r) for r in values.get("--write_simulated", []))}
+            "write_simulated": tuple(int(r) for r in values.get("--write_simulated", [])), "transcripts": one("--transcripts", str),
+            "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str)}
     if opts["simulate"] is not None and opts["seed"] is None:
         raise SystemExit("--simulate needs --seed S: there is no default randomness")
     if opts["simulate"] is None and (opts["seed"] is not None or opts["write_simulated"]):
@@ -186,10 +197,23 @@ def _summary_options(flags, values, model_type="snv"):
         raise SystemExit("--motif_length needs --summary PREFIX: the prefix of the files it writes")
     if opts["annotations"] is not None and opts["summary"] is None:
         raise SystemExit("--annotations needs --summary PREFIX: the prefix of the files it writes")
+    if opts["transcripts"] is not None and opts["summary"] is None:
+        raise SystemExit("--transcripts needs --summary PREFIX: the prefix of the file it writes")
+    if opts["transcripts"] is None and (opts["codon_table"] is not None or opts["alt_order"] is not None):
+        raise SystemExit("--codon_table / --alt_order go with --transcripts BED12")
+    if opts["transcripts"] is not None and model_type == "indel":
+        raise SystemExit("--transcripts takes SNV rows: it does not go with --indel")
     if (opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"] and not opts["calibration"]
-            and opts["annotations"] is None and opts["simulate"] is None):
-        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics, --annotations "
-                         "or --simulate")
+            and opts["annotations"] is None and opts["simulate"] is None and opts["transcripts"] is None):
+        raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics, --annotations, "
+                         "--simulate or --transcripts")
+    if opts["transcripts"] is not None:
+        from mural_amd.tables import check_alt_order, read_transcripts
+        try:
+            opts["transcripts"] = read_transcripts(opts["transcripts"], opts["codon_table"])
+            opts["alt_order"] = check_alt_order(opts["alt_order"])
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--transcripts: {e}") from None
     if opts["annotations"] is not None:
         from mural_amd.tables import read_annotations
         try:
@@ -252,7 +276,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               motif_indel=model_type == "indel", calibration=opts["calibration"],
                               calibration_bins=50 if opts["n_bins"] is None else opts["n_bins"], fit_calibrator=opts["fit_calibrator"],
                               annotations=opts["annotations"], simulate=opts["simulate"], simulate_seed=opts["seed"],
-                              simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), **sink_chain)
+                              simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), transcripts=opts["transcripts"], alt_order=opts["alt_order"],
+                              transcript_labels=opts.get("labelled", True), **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
