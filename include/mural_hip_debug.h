@@ -18,6 +18,11 @@ extern "C" {
  * workspace, run a call and check that nothing was written outside the regions. */
 int mural_debug_last_ws_layout(size_t* out_pairs, int32_t max_pairs);
 
+/* Validation hook: the one-workgroup run scan that the table kernels share (csrc/common.h: run_excl_scan) on its own.  The words
+ * v[0], v[stride], .. v[(m - 1) stride] (device) become their exclusive prefix in place, *total (device) their sum; the words between
+ * them are not touched.  threads: 256 or 1024, the workgroup sizes the library's scan kernels use. */
+int mural_debug_run_scan(int64_t* v, int64_t m, int64_t stride, int32_t threads, int64_t* total, void* stream);
+
 /* Validation hooks of the parity tests: the channel-last conv kernels of the composed training step on their own.  Tensors are
  * [B][L][32]; acc blocks are double[MURAL_BN_SLOTS][2][32] (the forward reads the batch sums of act(x) from `acc` and finalises the
  * BatchNorm itself; acc_out / stat_out zeroed by the caller); part: 1024 * (32*32*3 + 32) floats of partial rows, *nrow of them written. */

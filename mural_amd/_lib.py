@@ -329,6 +329,7 @@ PROTOTYPES = {
 # the validation hooks / diagnostics of include/mural_hip_debug.h: exported by the debug flavour only (libmural_hip_debug.so)
 DEBUG_PROTOTYPES = {
     "mural_debug_last_ws_layout": (C.c_int, [VP, I32]),
+    "mural_debug_run_scan": (C.c_int, [VP, I64, I64, I32, VP, VP]),
     "mural_debug_cl_conv32_fwd": (C.c_int, [VP, I64, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, VP, I32, VP, VP]),
     "mural_debug_cl_conv32_bwd": (C.c_int, [VP, VP, VP, I64, I32, VP, I32, VP, VP, VP, VP, VP]),
     "mural_debug_cw_wfrag": (C.c_int, [VP, VP, VP]),

@@ -77,6 +77,13 @@ int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int3
     }                                       \
   } while (0)
 
+// MURAL_OK, or the refusal of a workspace that is NULL, not 8-byte aligned or smaller than the `need` bytes that `bytes_fn` names
+inline int check_workspace(const char* entry, const char* bytes_fn, const void* ws, size_t ws_bytes, size_t need) {
+  if (ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 7) == 0) return MURAL_OK;
+  set_error("%s: the workspace is NULL, misaligned or smaller than %s (%zu)", entry, bytes_fn, need);
+  return MURAL_E_WORKSPACE;
+}
+
 // the window of a site at `pos` (reference: MuRaL/data/preprocessing.py:559-567): genome positions pos + off .. pos + off + width - 1; the
 // indel window is the even one (:564-566)
 inline int window_geometry(int radius, int indel, int* off, int* width) {
@@ -234,6 +241,69 @@ __device__ __forceinline__ int block_excl_scan(int v, int* total) {
   __syncthreads();
   *total = sum;
   return base + incl - v;
+}
+
+typedef unsigned long long u64;      // the integer cells of the table reductions (summary_*.hip, simulate.hip)
+
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// first index of [lo, hi) where pred fails, the whole wave searching; pred holds on a prefix of the range.  A probe per lane splits the
+// range 64 ways a round; the range shrinks every round whatever the data hold, and no probe leaves it.  (amb_lower_bound_wave below is
+// the same search with its predicate written in: it is inlined into the encode and stage-1 kernels, whose code is left as it is.)
+template <typename Pred>
+__device__ __forceinline__ int64_t wave_partition_point(int64_t lo, int64_t hi, Pred pred) {
+  const int lane = threadIdx.x & 63;
+  while (lo < hi) {
+    const int64_t step = (hi - lo + 63) / 64;
+    const int64_t p = lo + lane * step;
+    const int holds = __popcll(__ballot(p < hi && pred(p)));
+    if (holds == 0) {
+      hi = lo;
+    } else {
+      hi = min(hi, lo + holds * step);
+      lo = lo + (holds - 1) * step + 1;
+    }
+  }
+  return lo;
+}
+
+// The exclusive prefix of m elements by ONE workgroup of THREADS threads, every thread of which calls: store(t, load(0) + .. +
+// load(t - 1)) for t = 0 .. m - 1, the total comes back in every thread.  A thread owns a run of ceil(m / THREADS) consecutive elements
+// (the last runs may be short or empty): it sums its run, the run sums are scanned by shuffles and the wave totals through LDS, and it
+// walks its run again.  load(t) is called before store(t) and by the same thread, so the prefix may replace the elements in place.
+template <int THREADS, typename T, typename Load, typename Store>
+__device__ __forceinline__ T run_excl_scan(int64_t m, Load load, Store store) {
+  __shared__ T wave_tot[THREADS / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t run = (m + THREADS - 1) / THREADS;
+  const int64_t t0 = min((int64_t)threadIdx.x * run, m), t1 = min(t0 + run, m);
+  T mine = 0;
+  for (int64_t t = t0; t < t1; ++t) mine += load(t);
+  T incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  if (lane == 63) wave_tot[w] = incl;
+  __syncthreads();
+  T base = 0, total = 0;
+#pragma unroll
+  for (int k = 0; k < THREADS / 64; ++k) {
+    base += k < w ? wave_tot[k] : 0;
+    total += wave_tot[k];
+  }
+  T running = base + incl - mine;
+  for (int64_t t = t0; t < t1; ++t) {
+    const T x = load(t);
+    store(t, running);
+    running += x;
+  }
+  return total;
 }
 
 // ---------------------------------------------------------------------------------------------

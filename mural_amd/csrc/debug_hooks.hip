@@ -222,6 +222,26 @@ extern "C" int mural_debug_last_ws_layout(size_t* out, int32_t max_pairs) {
   return m;
 }
 
+// ---- validation hook (tests/test_gpu_run_scan.py): the one-workgroup run scan of common.h on its own, every `stride`-th word of v
+namespace {
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void run_scan_kernel(int64_t* __restrict__ v, int64_t m, int64_t stride, int64_t* __restrict__ total) {
+  const int64_t all = run_excl_scan<THREADS, int64_t>(m, [&](int64_t t) { return v[t * stride]; }, [&](int64_t t, int64_t x) { v[t * stride] = x; });
+  if (threadIdx.x == 0) *total = all;
+}
+}  // namespace
+
+extern "C" int mural_debug_run_scan(int64_t* v, int64_t m, int64_t stride, int32_t threads, int64_t* total, void* stream) {
+  MURAL_REQUIRE(m >= 0 && stride >= 1 && (v || m == 0) && total, "run_scan: m >= 0, stride >= 1, v and total are needed");
+  MURAL_REQUIRE(threads == 256 || threads == 1024, "run_scan: 256 or 1024 threads (got %d)", threads);
+  if (threads == 256)
+    hipLaunchKernelGGL(run_scan_kernel<256>, dim3(1), dim3(256), 0, STREAM, v, m, stride, total);
+  else
+    hipLaunchKernelGGL(run_scan_kernel<1024>, dim3(1), dim3(1024), 0, STREAM, v, m, stride, total);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
 extern "C" int mural_debug_set_stamps(void* dev_ptr) {
   mural::g_tower_stamps = static_cast<unsigned long long*>(dev_ptr);
   return MURAL_OK;

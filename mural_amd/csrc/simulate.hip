@@ -12,23 +12,20 @@
 //
 // mural_simulate_annot_rows, per call:
 //   * check kernel, a thread per row: the status bits (a bad probability, a negative start, a start below the row before it);
-//   * range kernel, a wave per piece: its rows [i0, i1) by two 64-ary searches in start, and its number of CHUNKS of at most
-//     SIM_CHUNK_ROWS rows -- a long piece becomes many units of work, so it cannot serialise the launch;
-//   * scan kernel, one workgroup: the exclusive prefix of the chunk counts (chunk t belongs to the piece p with pre[p] <= t < pre[p + 1]);
+//   * range and scan kernels: the pieces' rows cut into chunks of at most SIM_CHUNK_ROWS rows (row_chunks.h);
 //   * draw kernel, a fixed grid of SIM_GRID_WAVES waves striding over the units (chunk, block of 64 replicates): the wave finds the
-//     chunk's piece by a 64-ary search in the prefix, walks the chunk 64 rows at a time (a row per lane, four replicates per Philox
-//     call), counts the hits of a (class, replicate) over the 64 rows by ballot + popcount and keeps the count of replicate r0 + l in
-//     lane l; after the chunk ONE wave-instruction per class adds the 64 counts -- 256 contiguous bytes -- with 32-bit INTEGER atomics.
+//     chunk's piece, walks the chunk 64 rows at a time (a row per lane, four replicates per Philox call), counts the hits of a (class,
+//     replicate) over the 64 rows by ballot + popcount and keeps the count of replicate r0 + l in lane l; after the chunk ONE
+//     wave-instruction per class adds the 64 counts -- 256 contiguous bytes -- with 32-bit INTEGER atomics.
 // mural_simulate_rows: tile counts of the non-zero labels of one replicate (a wave per 64 rows), their exclusive scan, and a second pass
 // that recomputes the labels and writes each hit at prefix + its rank among the tile's hits: stable in row order.
 // No floating-point atomics, no synchronisation, no read-back.
 #include "common.h"
 #include "kmer_key.h"
+#include "row_chunks.h"
 
 namespace mural {
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int SIM_MAX_CLASS = 8;
 constexpr int SIM_THREADS = 256;
@@ -108,74 +105,9 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_check_kernel(SimRows A, 
   if (bad) atomicOr(A.status, bad);
 }
 
-// first index of [lo, hi) where pred fails, the whole wave searching; pred holds on a prefix of the range.  A probe per lane splits the
-// range 64 ways a round; the range shrinks every round whatever the data hold, and no probe leaves it.
-template <typename Pred>
-__device__ __forceinline__ int64_t wave_partition_point(int64_t lo, int64_t hi, Pred pred) {
-  const int lane = threadIdx.x & 63;
-  while (lo < hi) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t p = lo + lane * step;
-    const int holds = __popcll(__ballot(p < hi && pred(p)));
-    if (holds == 0) {
-      hi = lo;
-    } else {
-      hi = min(hi, lo + holds * step);
-      lo = lo + (holds - 1) * step + 1;
-    }
-  }
-  return lo;
-}
-
-// a wave per piece: its rows [i0, i1) and its chunk count
-__global__ __launch_bounds__(SIM_THREADS) void simulate_range_kernel(const int64_t* __restrict__ start, int64_t n,
-                                                                     const int64_t* __restrict__ b0, const int64_t* __restrict__ b1,
-                                                                     const int32_t* __restrict__ group, int32_t n_groups, int64_t n_pieces,
-                                                                     int64_t* __restrict__ row0, int64_t* __restrict__ row1,
-                                                                     int64_t* __restrict__ pre) {
-  const int64_t p = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
-  if (p >= n_pieces) return;
-  const int32_t g = group[p];
-  int64_t i0 = 0, i1 = 0;
-  if (g >= 0 && g < n_groups) {
-    const int64_t lo = b0[p], hi = b1[p];
-    i0 = wave_partition_point(0, n, [&](int64_t i) { return start[i] < lo; });
-    i1 = wave_partition_point(i0, n, [&](int64_t i) { return start[i] < hi; });
-  }
-  if ((threadIdx.x & 63) == 0) {
-    row0[p] = i0, row1[p] = i1;
-    pre[p] = (i1 - i0 + SIM_CHUNK_ROWS - 1) / SIM_CHUNK_ROWS;
-  }
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total (also to *total_out where given): one workgroup, a thread owns a run
+// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total (also to *total_out where given): one workgroup
 __global__ __launch_bounds__(SIM_SCAN_THREADS) void simulate_scan_kernel(int64_t* __restrict__ v, int64_t m, int64_t* __restrict__ total_out) {
-  __shared__ int64_t wave_tot[SIM_SCAN_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t run = (m + SIM_SCAN_THREADS - 1) / SIM_SCAN_THREADS;
-  const int64_t t0 = min((int64_t)threadIdx.x * run, m), t1 = min(t0 + run, m);
-  int64_t mine = 0;
-  for (int64_t t = t0; t < t1; ++t) mine += v[t];
-  int64_t incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int64_t up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wave_tot[w] = incl;
-  __syncthreads();
-  int64_t base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < SIM_SCAN_THREADS / 64; ++k) {
-    base += k < w ? wave_tot[k] : 0;
-    total += wave_tot[k];
-  }
-  int64_t running = base + incl - mine;
-  for (int64_t t = t0; t < t1; ++t) {
-    const int64_t x = v[t];
-    v[t] = running;
-    running += x;
-  }
+  const int64_t total = run_excl_scan<SIM_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
   if (threadIdx.x == 0) {
     v[m] = total;
     if (total_out) *total_out = total;
@@ -194,8 +126,7 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_draw_kernel(SimRows A, c
   for (int64_t unit = wave; unit < units; unit += n_waves) {
     const int64_t t = unit / n_rb;
     const int rb = (int)(unit % n_rb);
-    // the piece of chunk t: the last p with pre[p] <= t (pre[n_pieces] = the total > t, so the point lies in 1 .. n_pieces)
-    const int64_t p = wave_partition_point(0, n_pieces + 1, [&](int64_t q) { return pre[q] <= t; }) - 1;
+    const int64_t p = row_chunk_item(pre, n_pieces, t);
     const int64_t r0 = row0[p] + (t - pre[p]) * SIM_CHUNK_ROWS;
     const int64_t r1 = min(r0 + SIM_CHUNK_ROWS, row1[p]);
     const int reps_here = min(64, n_rep - rb * 64);
@@ -294,15 +225,6 @@ int fill_rows(SimRows& A, const void* prob, int64_t prob_stride, const int64_t* 
   return MURAL_OK;
 }
 
-struct AnnotWs { int64_t *row0, *row1, *pre; };
-AnnotWs carve_annot(WsArena& ws, int64_t n_pieces) {
-  AnnotWs w;
-  w.row0 = ws.as<int64_t>((size_t)n_pieces);
-  w.row1 = ws.as<int64_t>((size_t)n_pieces);
-  w.pre = ws.as<int64_t>((size_t)n_pieces + 1);
-  return w;
-}
-
 int64_t tiles_of(int64_t n) { return (n + 63) / 64; }
 
 }  // namespace
@@ -316,10 +238,7 @@ extern "C" int32_t mural_simulate_scan_threads(void) { return SIM_SCAN_THREADS; 
 extern "C" int32_t mural_simulate_max_replicates(void) { return SIM_MAX_REP; }
 
 extern "C" size_t mural_simulate_annot_workspace_bytes(int64_t n_pieces) {
-  if (n_pieces <= 0) return 0;
-  WsArena ws(nullptr);
-  carve_annot(ws, n_pieces);
-  return ws.off;
+  return row_chunks_bytes(n_pieces);
 }
 
 extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* ws_ptr, size_t ws_bytes, void* stream) {
@@ -339,11 +258,9 @@ extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* 
   if (s->n_pieces > 0) {      // (everything is checked before the first launch)
     MURAL_REQUIRE(s->piece_b0 && s->piece_b1 && s->piece_group && s->n_groups >= 1 && s->table,
                   "simulate_annot_rows: pieces without groups or table");
-    const size_t need = mural_simulate_annot_workspace_bytes(s->n_pieces);
-    if (!ws_ptr || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws_ptr) & 7) != 0) {
-      set_error("simulate_annot_rows: the workspace is NULL, misaligned or smaller than mural_simulate_annot_workspace_bytes (%zu)", need);
-      return MURAL_E_WORKSPACE;
-    }
+    if (const int rc = check_workspace("simulate_annot_rows", "mural_simulate_annot_workspace_bytes", ws_ptr, ws_bytes,
+                                       mural_simulate_annot_workspace_bytes(s->n_pieces)))
+      return rc;
   }
   if (s->prob_f64)
     hipLaunchKernelGGL(simulate_check_kernel<double>, row_grid, block, 0, st, A, s->n, 1);
@@ -352,19 +269,14 @@ extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* 
   MURAL_HIP_CHECK(hipGetLastError());
   if (s->n_pieces == 0) return MURAL_OK;
   WsArena ws(ws_ptr);
-  const AnnotWs w = carve_annot(ws, s->n_pieces);
+  const RowChunks w = carve_row_chunks(ws, s->n_pieces);
   const dim3 piece_grid((unsigned)((s->n_pieces + SIM_WAVES - 1) / SIM_WAVES));
-  hipLaunchKernelGGL(simulate_range_kernel, piece_grid, block, 0, st, s->start, s->n, s->piece_b0, s->piece_b1, s->piece_group, s->n_groups,
-                     s->n_pieces, w.row0, w.row1, w.pre);
+  hipLaunchKernelGGL(row_chunk_range_kernel<SIM_THREADS>, piece_grid, block, 0, st, s->start, s->n, s->piece_b0, s->piece_b1, s->piece_group,
+                     s->n_groups, s->n_pieces, SIM_CHUNK_ROWS, w);
   MURAL_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(simulate_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, w.pre, s->n_pieces, (int64_t*)nullptr);
   MURAL_HIP_CHECK(hipGetLastError());
-  // the units are known on the device only; the host knows a bound: every piece has at most ceil(n / chunk) chunks
-  const int64_t n_rb = (s->n_rep + 63) / 64;
-  const int64_t per_piece = (s->n + SIM_CHUNK_ROWS - 1) / SIM_CHUNK_ROWS;
-  int64_t n_waves = SIM_GRID_WAVES;
-  if (per_piece * n_rb < SIM_GRID_WAVES && s->n_pieces < SIM_GRID_WAVES / (per_piece * n_rb)) n_waves = s->n_pieces * per_piece * n_rb;
-  n_waves = (n_waves + SIM_WAVES - 1) / SIM_WAVES * SIM_WAVES;
+  const int64_t n_waves = row_chunk_grid_waves(s->n, SIM_CHUNK_ROWS, (s->n_rep + 63) / 64, s->n_pieces, SIM_GRID_WAVES, SIM_WAVES);
   const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES));
   if (s->prob_f64)
     hipLaunchKernelGGL(simulate_draw_kernel<double>, draw_grid, block, 0, st, A, s->piece_group, s->n_pieces, w.row0, w.row1, w.pre, s->n_rep,
@@ -391,11 +303,9 @@ extern "C" int mural_simulate_rows(const MuralSimulateRows* s, void* ws_ptr, siz
   if (s->n == 0) return MURAL_OK;
   MURAL_REQUIRE(s->prob && s->start && s->status && s->out_start && s->out_strand && s->out_label && s->count, "simulate_rows: NULL argument");
   MURAL_REQUIRE(s->prob_stride >= s->n_class, "simulate_rows: prob_stride < n_class");
-  const size_t need = mural_simulate_rows_workspace_bytes(s->n);
-  if (!ws_ptr || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws_ptr) & 7) != 0) {
-    set_error("simulate_rows: the workspace is NULL, misaligned or smaller than mural_simulate_rows_workspace_bytes (%zu)", need);
-    return MURAL_E_WORKSPACE;
-  }
+  if (const int rc = check_workspace("simulate_rows", "mural_simulate_rows_workspace_bytes", ws_ptr, ws_bytes,
+                                     mural_simulate_rows_workspace_bytes(s->n)))
+    return rc;
   SimRows A{};
   fill_rows(A, s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
   const int64_t n_tiles = tiles_of(s->n);

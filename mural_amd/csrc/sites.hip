@@ -124,29 +124,10 @@ __global__ __launch_bounds__(ST_THREADS) void sites_count_kernel(MuralGenome g, 
 
 // one block, in place: counts[t] -> sites before tile t; counts[nt] = *total = all sites
 __global__ __launch_bounds__(ST_THREADS) void sites_scan_kernel(int64_t* __restrict__ counts, int64_t nt, int64_t* __restrict__ total) {
-  const int64_t per = (nt + ST_THREADS - 1) / ST_THREADS;
-  const int64_t b0 = (int64_t)threadIdx.x * per;
-  int64_t s = 0;
-  for (int64_t b = b0; b < b0 + per && b < nt; ++b) s += counts[b];
-  __shared__ int64_t part[ST_THREADS];
-  part[threadIdx.x] = s;
-  __syncthreads();
+  const int64_t all = run_excl_scan<ST_THREADS, int64_t>(nt, [&](int64_t b) { return counts[b]; }, [&](int64_t b, int64_t x) { counts[b] = x; });
   if (threadIdx.x == 0) {
-    int64_t acc = 0;
-    for (int t = 0; t < ST_THREADS; ++t) {
-      const int64_t v = part[t];
-      part[t] = acc;
-      acc += v;
-    }
-    counts[nt] = acc;
-    *total = acc;
-  }
-  __syncthreads();
-  int64_t acc = part[threadIdx.x];
-  for (int64_t b = b0; b < b0 + per && b < nt; ++b) {      // (every thread reads and writes its own tiles only)
-    const int64_t v = counts[b];
-    counts[b] = acc;
-    acc += v;
+    counts[nt] = all;
+    *total = all;
   }
 }
 

@@ -12,14 +12,14 @@
 //   * tile kernel, a wave per tile of SA_TILE = 64 consecutive rows (a row per lane): quantise, reduce the 3 n_class words -- label
 //     counts by ballot, the limbs by a wave butterfly -- and store them with plain vector stores; rows that fail a check quantise to
 //     nothing and set status; start[i] < start[i - 1] sets bit 2.
-//   * scan kernel, a workgroup per word: the exclusive prefix over the tiles in place, per limb and WITHOUT folding: a slice adds at
-//     most 2^23 terms of at most 2^40 to a lo word, so the prefixes stay below 2^63 and their differences are exact.
-//   * piece kernel, a wave per piece: two 64-ary searches in start (4 rounds of one probe per lane for 2^23 rows), prefix(i) = the tile
-//     prefix + a masked reduce over the at most 63 rows of the partial tile, re-read and re-quantised (mostly L2 hits: at most
-//     2 * n_pieces * 64 rows); the difference is folded (hi += lo >> 40, lo &= 2^40 - 1) and its non-zero words are added to the group's
-//     cells with 64-bit INTEGER atomics, one wave-instruction of 3 n_class contiguous words.  Empty pieces add nothing.
-//   * fold kernel, a thread per (group, class), no atomics, after every SA_FOLD_PIECES pieces: a piece adds lo < 2^40 to a cell, so
-//     lo < 2^40 + 2^20 * 2^40 < 2^61 before the next fold, and lo < 2^40 on return.
+//   * scan kernel, a workgroup per word (common.h: run_excl_scan): the exclusive prefix over the tiles in place, per limb and WITHOUT
+//     folding: a slice adds at most 2^23 terms of at most 2^40 to a lo word, so the prefixes do not wrap and their differences are exact.
+//   * piece kernel, a wave per piece: two 64-ary searches in start (common.h: wave_partition_point; 4 rounds of one probe per lane for
+//     2^23 rows), prefix(i) = the tile prefix + a masked reduce over the at most 63 rows of the partial tile, re-read and re-quantised
+//     (mostly L2 hits: at most 2 * n_pieces * 64 rows); the difference is folded and its non-zero words are added to the group's cells
+//     with 64-bit INTEGER atomics, one wave-instruction of 3 n_class contiguous words.  Empty pieces add nothing.
+//   * fold kernel (summary_quant.h, with the limb bound), after every SA_FOLD_PIECES pieces: a piece adds one folded term to a cell,
+//     X = SA_FOLD_PIECES = 2^20 terms between two folds.
 // No floating-point atomics, no synchronisation, no read-back.
 #include "common.h"
 #include "kmer_key.h"
@@ -34,7 +34,6 @@ constexpr int SA_WAVES = SA_THREADS / 64;
 constexpr int SA_SCAN_THREADS = 1024;
 constexpr int64_t SA_SLICE_ROWS = 1ll << 23;      // rows whose unfolded lo prefixes stay below 2^63
 constexpr int64_t SA_FOLD_PIECES = 1ll << 20;     // pieces between two folds of the table
-constexpr u64 SA_LO_MASK = (1ull << SK_LO_BITS) - 1;
 
 struct AnnotArgs {
   const void* prob;
@@ -49,12 +48,6 @@ struct AnnotArgs {
   u64* table;
   int32_t* status;
 };
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // The 3 n_class words of rows row .. row + cnt - 1 (0 <= cnt <= 64, a row per lane): word j -- label counts | sums of hi | sums of
 // lo -- comes back in lane j, 0 in the lanes from 3 n_class on.  `bad`: the status bits of the rows.
@@ -107,52 +100,11 @@ __global__ __launch_bounds__(SA_THREADS) void summary_annot_tile_kernel(AnnotArg
 
 // exclusive prefix over the tiles of word blockIdx.x, in place; entry n_tiles gets the total.  A thread owns a run of consecutive tiles.
 __global__ __launch_bounds__(SA_SCAN_THREADS) void summary_annot_scan_kernel(AnnotArgs A, int64_t n_tiles) {
-  __shared__ u64 wave_tot[SA_SCAN_THREADS / 64];
-  const int words = 3 * A.n_class, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int words = 3 * A.n_class;
   u64* __restrict__ col = A.tiles + blockIdx.x;
-  const int64_t run = (n_tiles + SA_SCAN_THREADS - 1) / SA_SCAN_THREADS;
-  const int64_t t0 = min((int64_t)threadIdx.x * run, n_tiles), t1 = min(t0 + run, n_tiles);
-  u64 mine = 0;
-  for (int64_t t = t0; t < t1; ++t) mine += col[t * words];
-  u64 incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const u64 up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wave_tot[w] = incl;
-  __syncthreads();
-  u64 base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < SA_SCAN_THREADS / 64; ++k) {
-    base += k < w ? wave_tot[k] : 0;
-    total += wave_tot[k];
-  }
-  u64 running = base + incl - mine;
-  for (int64_t t = t0; t < t1; ++t) {
-    const u64 v = col[t * words];
-    col[t * words] = running;
-    running += v;
-  }
+  const u64 total = run_excl_scan<SA_SCAN_THREADS, u64>(n_tiles, [&](int64_t t) { return col[t * words]; },
+                                                        [&](int64_t t, u64 x) { col[t * words] = x; });
   if (threadIdx.x == 0) col[n_tiles * words] = total;
-}
-
-// the first row of [lo, hi) with start >= b (hi if none), the whole wave searching: a probe per lane splits the range 64 ways a round.
-// The range shrinks every round whatever the rows hold, and no probe leaves it.
-__device__ __forceinline__ int64_t wave_lower_bound(const int64_t* __restrict__ start, int64_t lo, int64_t hi, int64_t b) {
-  const int lane = threadIdx.x & 63;
-  while (lo < hi) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t p = lo + lane * step;
-    const int below = __popcll(__ballot(p < hi && start[p] < b));      // (the rows ascend: the lanes below the bound come first)
-    if (below == 0) {
-      hi = lo;
-    } else {
-      hi = min(hi, lo + below * step);
-      lo = lo + (below - 1) * step + 1;
-    }
-  }
-  return lo;
 }
 
 // lane j: word j of the sums over rows s0 .. i - 1 of the slice
@@ -174,28 +126,18 @@ __global__ __launch_bounds__(SA_THREADS) void summary_annot_piece_kernel(AnnotAr
   if (p >= p1) return;
   const int32_t g = A.group[p];
   if (g < 0 || g >= A.n_groups) return;
-  const int64_t i0 = wave_lower_bound(A.start, s0, s1, A.b0[p]);
-  const int64_t i1 = wave_lower_bound(A.start, i0, s1, A.b1[p]);
+  // both ends are lower bounds: the first row with start >= b (the rows ascend: the rows below the bound come first)
+  const int64_t* __restrict__ start = A.start;
+  const int64_t b0 = A.b0[p], b1 = A.b1[p];
+  const int64_t i0 = wave_partition_point(s0, s1, [&](int64_t i) { return start[i] < b0; });
+  const int64_t i1 = wave_partition_point(i0, s1, [&](int64_t i) { return start[i] < b1; });
   if (i1 <= i0) return;
   const u64 sum = prefix_words<T>(A, s0, i1) - prefix_words<T>(A, s0, i0);
   const u64 above = __shfl(sum, (lane + nc) & 63, 64);      // a hi lane reads its lo lane
   u64 word = sum;
-  if (lane >= nc && lane < 2 * nc) word += above >> SK_LO_BITS;
-  if (lane >= 2 * nc) word &= SA_LO_MASK;
+  if (lane >= nc && lane < 2 * nc) word += above >> SK_LO_BITS;      // (fold_limbs, the two limbs in two lanes)
+  if (lane >= 2 * nc) word &= SK_LO_MASK;
   if (lane < 3 * nc && word) atomicAdd(&A.table[(int64_t)g * (3 * nc) + lane], word);
-}
-
-// carry the overflow of the table's lo limbs into its hi limbs: a thread per (group, class), plain loads and stores
-__global__ __launch_bounds__(SA_THREADS) void summary_annot_fold_kernel(AnnotArgs A) {
-  const int nc = A.n_class;
-  const int64_t t = (int64_t)blockIdx.x * SA_THREADS + threadIdx.x;
-  if (t >= (int64_t)A.n_groups * nc) return;
-  u64* __restrict__ cell = A.table + (t / nc) * (3 * nc) + t % nc;
-  const u64 lo = cell[2 * nc];
-  if (lo >> SK_LO_BITS) {
-    cell[nc] += lo >> SK_LO_BITS;
-    cell[2 * nc] = lo & SA_LO_MASK;
-  }
 }
 
 int64_t tiles_of(int64_t rows) { return (rows + SA_TILE - 1) / SA_TILE; }
@@ -234,6 +176,8 @@ extern "C" int mural_summary_annot_rows(const MuralSummaryAnnotRows* s, void* ws
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(SA_THREADS);
   const dim3 fold_grid((unsigned)(((int64_t)s->n_groups * s->n_class + SA_THREADS - 1) / SA_THREADS));
+  FoldTables F{};
+  F.table[0] = A.table, F.n_groups[0] = s->n_groups, F.nc = s->n_class;
   for (int64_t s0 = 0; s0 < s->n; s0 += SA_SLICE_ROWS) {
     const int64_t s1 = std::min(s0 + SA_SLICE_ROWS, s->n);
     const int64_t n_tiles = tiles_of(s1 - s0);
@@ -253,7 +197,7 @@ extern "C" int mural_summary_annot_rows(const MuralSummaryAnnotRows* s, void* ws
       else
         hipLaunchKernelGGL(summary_annot_piece_kernel<float>, piece_grid, block, 0, st, A, s0, s1, p0, p1);
       MURAL_HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(summary_annot_fold_kernel, fold_grid, block, 0, st, A);
+      hipLaunchKernelGGL(summary_fold_kernel<SA_THREADS>, fold_grid, block, 0, st, F);
       MURAL_HIP_CHECK(hipGetLastError());
     }
   }

@@ -31,11 +31,11 @@
 // negative or above 1 -- or a row without one positive probability, whose softmax is undefined -- (bit 3).  A valid row with
 // q_label == 0 has an infinite NLL term: it is counted in inf_rows, left out of the NLL sum and counted everywhere else.
 #include "common.h"
+#include "kmer_key.h"      // load_label, the status bits
 
 namespace mural {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int CB_THREADS = 256;
 constexpr int CB_MAX_CLASS = 16;
 constexpr int CB_LDS_CELLS = 4096;                 // the workgroup's image of the table: 32 KB
@@ -45,7 +45,6 @@ constexpr int64_t CB_SLICE_ROWS = 1ll << 28;       // rows of a launch (the boun
 constexpr int CB_LO_BITS = 46;
 constexpr u64 CB_LO_MASK = (1ull << CB_LO_BITS) - 1;
 constexpr int CB_SCORE_BITS = 16, CB_NLL_BITS = 13;
-constexpr int32_t CB_BAD_LABEL = 2, CB_BAD_PROB = 8;
 
 struct CalibArgs {
   const void* prob;
@@ -62,18 +61,6 @@ __host__ __device__ __forceinline__ int header_cells(int nc) { return 6 + nc; }
 __device__ __forceinline__ bool is_lo_cell(int idx, int nc) {
   const int h = header_cells(nc);
   return idx < h ? (idx == 3 + nc || idx == 5 + nc) : ((idx - h) & 3) == 2;
-}
-
-// label of row i as an int, -1 if it is no whole number (kind: 0 float32, 1 int32, 2 int64)
-__device__ __forceinline__ int label_of(const void* label, int kind, int64_t i) {
-  if (kind == 0) {
-    const float f = static_cast<const float*>(label)[i];
-    const int v = (f >= -1.0f && f < 1024.0f) ? (int)f : -1;
-    return (float)v == f ? v : -1;
-  }
-  if (kind == 1) return static_cast<const int32_t*>(label)[i];
-  const int64_t v = static_cast<const int64_t*>(label)[i];
-  return (v >= 0 && v < 1024) ? (int)v : -1;
 }
 
 __device__ __forceinline__ void quantise(double v, int bits, u64& hi, u64& lo) {
@@ -94,12 +81,6 @@ __device__ __forceinline__ int bin_of(double v, const float* __restrict__ bounds
   return -1;
 }
 
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __device__ __forceinline__ void add_cells(u64* __restrict__ cell, u64 rows, u64 hi, u64 lo, u64 hits) {
   atomicAdd(&cell[0], rows);
   if (hi) atomicAdd(&cell[1], hi);
@@ -117,7 +98,7 @@ __device__ __forceinline__ void add_binned(u64* __restrict__ group, int bin, u64
     const bool mine = bin == b0;
     const u64 mask = __ballot(mine);
     const u64 hits = (u64)__popcll(__ballot(mine && hit));
-    const u64 h = wave_sum_u64(mine ? hi : 0ull), l = wave_sum_u64(mine ? lo : 0ull);
+    const u64 h = wave_sum(mine ? hi : 0ull), l = wave_sum(mine ? lo : 0ull);
     if (lane == leader) add_cells(group + 4 * b0, (u64)__popcll(mask), h, l, hits);
     if (mine) bin = -1;
     todo &= ~mask;
@@ -148,8 +129,8 @@ __global__ __launch_bounds__(CB_THREADS) void summary_calib_rows_kernel(CalibArg
     P m = (P)-INFINITY;
     bool inf_row = false;
     if (valid) {
-      lab = label_of(A.label, A.label_kind, i);
-      int32_t bad_row = (lab < 0 || lab >= nc) ? CB_BAD_LABEL : 0;
+      lab = load_label(A.label, A.label_kind, i);
+      int32_t bad_row = (lab < 0 || lab >= nc) ? SM_BAD_LABEL : 0;
       // the reference's pseudo-logits are log(prob) and its scores softmax(log(prob)), evaluated in prob's own precision
       bool positive = false;
 #pragma unroll
@@ -159,13 +140,13 @@ __global__ __launch_bounds__(CB_THREADS) void summary_calib_rows_kernel(CalibArg
           // 0 <= p <= 1 on the bit pattern -- non-negative doubles order like their bits --, so that NaN is caught whatever the
           // compiler assumes about comparisons; -0.0 counts as 0
           const u64 bits = (u64)__double_as_longlong((double)p);
-          if (bits > 0x3FF0000000000000ull && bits != 0x8000000000000000ull) bad_row |= CB_BAD_PROB;
+          if (bits > 0x3FF0000000000000ull && bits != 0x8000000000000000ull) bad_row |= SM_BAD_PROB;
           positive |= bits != 0ull && bits != 0x8000000000000000ull;
           q[c] = (P)log(p);
           m = q[c] > m ? q[c] : m;
         }
       }
-      if (!positive) bad_row |= CB_BAD_PROB;
+      if (!positive) bad_row |= SM_BAD_PROB;
       if (bad_row) {
         bad |= bad_row;
         valid = false;
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(CB_THREADS) void summary_calib_rows_kernel(CalibArg
       }
     }
   }
-  nll_hi = wave_sum_u64(nll_hi), nll_lo = wave_sum_u64(nll_lo), br_hi = wave_sum_u64(br_hi), br_lo = wave_sum_u64(br_lo);
+  nll_hi = wave_sum(nll_hi), nll_lo = wave_sum(nll_lo), br_hi = wave_sum(br_hi), br_lo = wave_sum(br_lo);
   if (lane == 0) {
     if (nll_hi) atomicAdd(&cells[2 + nc], nll_hi);
     if (nll_lo) atomicAdd(&cells[3 + nc], nll_lo);

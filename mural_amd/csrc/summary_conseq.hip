@@ -9,23 +9,22 @@
 // per-row stabbing query is unbounded, and a row's bin depends on the transcript, so row prefix sums do not apply.  The rows of a part
 // ascend in start, so the rows of a segment are ONE range [i0, i1); the work is cut per segment, as csrc/simulate.hip cuts it per piece:
 //   * check kernel, a thread per row: the status bits;
-//   * range kernel, a wave per segment: [i0, i1) by two 64-ary searches in start, and the number of CHUNKS of at most SC_CHUNK_ROWS rows;
-//   * scan kernel, one workgroup: the exclusive prefix of the chunk counts;
-//   * reduce kernel, a grid of at most SC_GRID_WAVES waves striding over the chunks: the wave finds the chunk's segment by a 64-ary
-//     search in the prefix and walks the chunk 64 rows at a time, a row per lane: the row's CDS offset, its codon's three genomic
-//     positions (at most two hops over seg_prev / seg_next each: exons may be 1 bp long), the two amino acids from a 64-byte table in
-//     LDS, a bin per class.  The limbs (summary_quant.h: q = rne(p * 2^71) as hi, lo) add up per lane and bin over the chunk, the label
-//     counts per bin by ballot + popcount; after the chunk 10 wave butterflies, the fold of lo into hi, and ONE wave-instruction of
-//     64-bit INTEGER atomics over the transcript's 15 contiguous cells + its two row counters, zero words skipped;
-//   * fold kernel, a thread per (transcript, bin), no atomics: the overflow of the table's lo limbs into hi.
-// Bounds.  A lane adds at most 3 limbs below 2^40 per row and SC_CHUNK_ROWS / 64 = 16 rows per chunk: below 2^46 per lane, below 2^52
-// per wave before the fold.  A chunk adds lo < 2^40 to a cell; the segments of one transcript are disjoint, so one call adds at most
-// n / SC_CHUNK_ROWS + n_segments chunks to a cell; the entry refuses n > 2^31 or n_segments > 2^22, so lo < 2^40 (1 + 2^21 + 2^22) < 2^63
-// before the fold that ends every call, and lo < 2^40 on return.
+//   * range and scan kernels: the segments' rows cut into chunks of at most SC_CHUNK_ROWS rows (row_chunks.h);
+//   * reduce kernel, a grid of at most SC_GRID_WAVES waves striding over the chunks: the wave finds the chunk's segment and walks the
+//     chunk 64 rows at a time, a row per lane: the row's CDS offset, its codon's three genomic positions (at most two hops over
+//     seg_prev / seg_next each: exons may be 1 bp long), the two amino acids from a 64-byte table in LDS, a bin per class.  The limbs
+//     (summary_quant.h: q = rne(p * 2^71) as hi, lo) add up per lane and bin over the chunk, the label counts per bin by ballot +
+//     popcount; after the chunk 10 wave butterflies, the fold of lo into hi, and ONE wave-instruction of 64-bit INTEGER atomics over
+//     the transcript's 15 contiguous cells + its two row counters, zero words skipped;
+//   * fold kernel (summary_quant.h, with the limb bound): the table as [transcript * bin][3][1], at the end of every call.
+// Terms.  A lane adds at most 3 limbs per row and SC_CHUNK_ROWS / 64 = 16 rows per chunk: X = 3 * 16 * 64 < 2^12 terms in a wave's sum
+// before its fold.  A chunk then adds one folded term to a cell; the segments of one transcript are disjoint, so one call adds at most
+// n / SC_CHUNK_ROWS + n_segments chunks to a cell; the entry refuses n > 2^31 or n_segments > 2^22: X <= 2^21 + 2^22 terms per call.
 // No per-row bin is stored (the check and the reduce kernel both recompute a row); no floating-point atomics, no synchronisation, no
 // read-back.
 #include "common.h"
 #include "kmer_key.h"
+#include "row_chunks.h"
 #include "summary_quant.h"
 
 namespace mural {
@@ -41,7 +40,6 @@ constexpr int64_t SC_MAX_SEGMENTS = 1ll << 22;    // per call
 constexpr int SC_BINS = 5;                        // synonymous, missense, stop gained, stop lost, unresolved
 constexpr int SC_CELL_WORDS = 3 * SC_BINS;        // per transcript: [bin][label count | sum of hi | sum of lo]
 constexpr int SC_NOWHERE = SC_BINS;               // the bin of a class that is not counted
-constexpr u64 SC_LO_MASK = (1ull << SK_LO_BITS) - 1;
 
 struct ConseqArgs {
   MuralGenome g;
@@ -66,31 +64,6 @@ struct ConseqArgs {
   u64* rows;
   int32_t* status;
 };
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// first index of [lo, hi) where pred fails, the whole wave searching; pred holds on a prefix of the range.  A probe per lane splits the
-// range 64 ways a round; the range shrinks every round whatever the data hold, and no probe leaves it.
-template <typename Pred>
-__device__ __forceinline__ int64_t wave_partition_point(int64_t lo, int64_t hi, Pred pred) {
-  const int lane = threadIdx.x & 63;
-  while (lo < hi) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t p = lo + lane * step;
-    const int holds = __popcll(__ballot(p < hi && pred(p)));
-    if (holds == 0) {
-      hi = lo;
-    } else {
-      hi = min(hi, lo + holds * step);
-      lo = lo + (holds - 1) * step + 1;
-    }
-  }
-  return lo;
-}
 
 // The checks of row i (status bits, 0 if it counts) and the limbs of its classes 1 .. 3; class 0's probability is not read.
 template <typename T>
@@ -119,53 +92,9 @@ __global__ __launch_bounds__(SC_THREADS) void summary_conseq_check_kernel(Conseq
   if (bad) atomicOr(A.status, bad);
 }
 
-// a wave per segment: its rows [i0, i1) and its chunk count; a segment that is empty or names no transcript has none
-__global__ __launch_bounds__(SC_THREADS) void summary_conseq_range_kernel(ConseqArgs A, int64_t* __restrict__ row0, int64_t* __restrict__ row1,
-                                                                          int64_t* __restrict__ pre) {
-  const int64_t s = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);
-  if (s >= A.n_seg) return;
-  const int32_t tx = A.seg_tx[s];
-  const int64_t b0 = A.seg_b0[s], b1 = A.seg_b1[s];
-  int64_t i0 = 0, i1 = 0;
-  if (tx >= 0 && tx < A.n_tx && b0 < b1) {
-    const int64_t* __restrict__ start = A.start;
-    i0 = wave_partition_point(0, A.n, [&](int64_t i) { return start[i] < b0; });
-    i1 = wave_partition_point(i0, A.n, [&](int64_t i) { return start[i] < b1; });
-  }
-  if ((threadIdx.x & 63) == 0) {
-    row0[s] = i0, row1[s] = i1;
-    pre[s] = (i1 - i0 + SC_CHUNK_ROWS - 1) / SC_CHUNK_ROWS;
-  }
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup, a thread owns a run
+// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup
 __global__ __launch_bounds__(SC_SCAN_THREADS) void summary_conseq_scan_kernel(int64_t* __restrict__ v, int64_t m) {
-  __shared__ int64_t wave_tot[SC_SCAN_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t run = (m + SC_SCAN_THREADS - 1) / SC_SCAN_THREADS;
-  const int64_t t0 = min((int64_t)threadIdx.x * run, m), t1 = min(t0 + run, m);
-  int64_t mine = 0;
-  for (int64_t t = t0; t < t1; ++t) mine += v[t];
-  int64_t incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int64_t up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wave_tot[w] = incl;
-  __syncthreads();
-  int64_t base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < SC_SCAN_THREADS / 64; ++k) {
-    base += k < w ? wave_tot[k] : 0;
-    total += wave_tot[k];
-  }
-  int64_t running = base + incl - mine;
-  for (int64_t t = t0; t < t1; ++t) {
-    const int64_t x = v[t];
-    v[t] = running;
-    running += x;
-  }
+  const int64_t total = run_excl_scan<SC_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
   if (threadIdx.x == 0) v[m] = total;
 }
 
@@ -221,8 +150,7 @@ __global__ __launch_bounds__(SC_THREADS) void summary_conseq_reduce_kernel(Conse
   const int64_t wave = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);
   const int64_t units = pre[A.n_seg];
   for (int64_t unit = wave; unit < units; unit += n_waves) {
-    // the segment of chunk `unit`: the last s with pre[s] <= unit (pre[n_seg] = the total > unit, so the point lies in 1 .. n_seg)
-    const int64_t s = wave_partition_point(0, A.n_seg + 1, [&](int64_t q) { return pre[q] <= unit; }) - 1;
+    const int64_t s = row_chunk_item(pre, A.n_seg, unit);
     const int64_t r0 = row0[s] + (unit - pre[s]) * SC_CHUNK_ROWS;
     const int64_t r1 = min(r0 + SC_CHUNK_ROWS, row1[s]);
     const int64_t b0 = A.seg_b0[s], b1 = A.seg_b1[s], cds0 = A.seg_cds0[s];
@@ -285,11 +213,11 @@ __global__ __launch_bounds__(SC_THREADS) void summary_conseq_reduce_kernel(Conse
     u64 word = 0;      // lane 3 b + w: word w of bin b; lanes 15, 16: the row counters
 #pragma unroll
     for (int b = 0; b < SC_BINS; ++b) {
-      const u64 l = wave_sum(acc_lo[b]);
-      const u64 h = wave_sum(acc_hi[b]) + (l >> SK_LO_BITS);
+      u64 l = wave_sum(acc_lo[b]), h = wave_sum(acc_hi[b]);
+      fold_limbs(h, l);
       if (lane == 3 * b) word = cnt[b];
       if (lane == 3 * b + 1) word = h;
-      if (lane == 3 * b + 2) word = l & SC_LO_MASK;
+      if (lane == 3 * b + 2) word = l;
     }
     if (lane == SC_CELL_WORDS) word = n_rows;
     if (lane == SC_CELL_WORDS + 1) word = n_lab0;
@@ -298,27 +226,6 @@ __global__ __launch_bounds__(SC_THREADS) void summary_conseq_reduce_kernel(Conse
       else atomicAdd(&A.rows[(int64_t)tx * 2 + (lane - SC_CELL_WORDS)], word);
     }
   }
-}
-
-// carry the overflow of the table's lo limbs into its hi limbs: a thread per (transcript, bin), plain loads and stores
-__global__ __launch_bounds__(SC_THREADS) void summary_conseq_fold_kernel(u64* __restrict__ table, int64_t n_cells) {
-  const int64_t t = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
-  if (t >= n_cells) return;
-  u64* __restrict__ cell = table + t * 3;
-  const u64 lo = cell[2];
-  if (lo >> SK_LO_BITS) {
-    cell[1] += lo >> SK_LO_BITS;
-    cell[2] = lo & SC_LO_MASK;
-  }
-}
-
-struct ConseqWs { int64_t *row0, *row1, *pre; };
-ConseqWs carve(WsArena& ws, int64_t n_seg) {
-  ConseqWs w;
-  w.row0 = ws.as<int64_t>((size_t)n_seg);
-  w.row1 = ws.as<int64_t>((size_t)n_seg);
-  w.pre = ws.as<int64_t>((size_t)n_seg + 1);
-  return w;
 }
 
 }  // namespace
@@ -331,10 +238,7 @@ extern "C" int64_t mural_summary_conseq_grid_waves(void) { return SC_GRID_WAVES;
 extern "C" int32_t mural_summary_conseq_scan_threads(void) { return SC_SCAN_THREADS; }
 
 extern "C" size_t mural_summary_conseq_workspace_bytes(int64_t n_segments) {
-  if (n_segments <= 0) return 0;
-  WsArena ws(nullptr);
-  carve(ws, n_segments);
-  return ws.off;
+  return row_chunks_bytes(n_segments);
 }
 
 extern "C" int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* ws_ptr, size_t ws_bytes, void* stream) {
@@ -361,11 +265,9 @@ extern "C" int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* 
                     s->n_transcripts >= 1,
                 "summary_conseq_rows: segments without transcripts");
   MURAL_REQUIRE(s->prob_stride >= 4, "summary_conseq_rows: prob_stride < n_class");
-  const size_t need = mural_summary_conseq_workspace_bytes(s->n_segments);
-  if (!ws_ptr || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws_ptr) & 7) != 0) {
-    set_error("summary_conseq_rows: the workspace is NULL, misaligned or smaller than mural_summary_conseq_workspace_bytes (%zu)", need);
-    return MURAL_E_WORKSPACE;
-  }
+  if (const int rc = check_workspace("summary_conseq_rows", "mural_summary_conseq_workspace_bytes", ws_ptr, ws_bytes,
+                                     mural_summary_conseq_workspace_bytes(s->n_segments)))
+    return rc;
   ConseqArgs A{};
   A.g = *s->genome;
   A.prob = s->prob, A.start = s->start, A.strand = s->strand, A.label = s->label, A.prob_stride = s->prob_stride, A.n = s->n;
@@ -376,7 +278,7 @@ extern "C" int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* 
   A.alt_packed = alt_packed;
   A.table = reinterpret_cast<u64*>(s->table), A.rows = reinterpret_cast<u64*>(s->rows), A.status = s->status;
   WsArena ws(ws_ptr);
-  const ConseqWs w = carve(ws, s->n_segments);
+  const RowChunks w = carve_row_chunks(ws, s->n_segments);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(SC_THREADS);
   const dim3 row_grid((unsigned)((s->n + SC_THREADS - 1) / SC_THREADS));
@@ -386,15 +288,12 @@ extern "C" int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* 
     hipLaunchKernelGGL(summary_conseq_check_kernel<float>, row_grid, block, 0, st, A);
   MURAL_HIP_CHECK(hipGetLastError());
   const dim3 seg_grid((unsigned)((s->n_segments + SC_WAVES - 1) / SC_WAVES));
-  hipLaunchKernelGGL(summary_conseq_range_kernel, seg_grid, block, 0, st, A, w.row0, w.row1, w.pre);
+  hipLaunchKernelGGL(row_chunk_range_kernel<SC_THREADS>, seg_grid, block, 0, st, A.start, A.n, A.seg_b0, A.seg_b1, A.seg_tx, A.n_tx, A.n_seg,
+                     SC_CHUNK_ROWS, w);
   MURAL_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(summary_conseq_scan_kernel, dim3(1), dim3(SC_SCAN_THREADS), 0, st, w.pre, s->n_segments);
   MURAL_HIP_CHECK(hipGetLastError());
-  // the chunks are known on the device only; the host knows a bound: every segment has at most ceil(n / chunk) of them
-  const int64_t per_seg = (s->n + SC_CHUNK_ROWS - 1) / SC_CHUNK_ROWS;
-  int64_t n_waves = SC_GRID_WAVES;
-  if (per_seg < SC_GRID_WAVES && s->n_segments < SC_GRID_WAVES / per_seg) n_waves = s->n_segments * per_seg;
-  n_waves = (n_waves + SC_WAVES - 1) / SC_WAVES * SC_WAVES;
+  const int64_t n_waves = row_chunk_grid_waves(s->n, SC_CHUNK_ROWS, 1, s->n_segments, SC_GRID_WAVES, SC_WAVES);
   const dim3 reduce_grid((unsigned)(n_waves / SC_WAVES));
   if (s->prob_f64)
     hipLaunchKernelGGL(summary_conseq_reduce_kernel<double>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
@@ -402,7 +301,9 @@ extern "C" int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* 
     hipLaunchKernelGGL(summary_conseq_reduce_kernel<float>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
   MURAL_HIP_CHECK(hipGetLastError());
   const int64_t n_cells = (int64_t)s->n_transcripts * SC_BINS;
-  hipLaunchKernelGGL(summary_conseq_fold_kernel, dim3((unsigned)((n_cells + SC_THREADS - 1) / SC_THREADS)), block, 0, st, A.table, n_cells);
+  FoldTables F{};
+  F.table[0] = A.table, F.n_groups[0] = n_cells, F.nc = 1;      // [transcript][bin][3] = [cell][3][1]
+  hipLaunchKernelGGL(summary_fold_kernel<SC_THREADS>, dim3((unsigned)((n_cells + SC_THREADS - 1) / SC_THREADS)), block, 0, st, F);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }

@@ -12,11 +12,9 @@
 //   * rows kernel, one launch per k-mer length (each with the LDS its table needs): a workgroup takes a fixed range of rows.  Where the k's table
 //     (4^k keys x (3 n_class + 1) cells of 8 bytes, the last the first-appearance word) fits the workgroup's LDS it is accumulated there
 //     with LDS atomics and flushed once -- the non-zero cells only -- with global atomics; otherwise every row adds to the global table.
-//   * fold kernel, a thread per (key, class), no atomics: hi += lo >> 40, lo &= 2^40 - 1, after every slice of at most SK_FOLD_ROWS
-//     rows.  Bound: lo < 2^40 after a fold; a slice adds at most 2 * SK_FOLD_ROWS terms (mode 3 counts a palindrome twice) of at most
-//     2^40 each, so lo < 2^40 + 2^22 * 2^40 < 2^63 before the next fold.  hi is at most (2^31 + 1) per addition: below 2^64 -- the
-//     cells are read as UNSIGNED 64-bit numbers -- for 2^32 - 2 additions to one cell, more than a genome of 2^32 rows can make in
-//     modes 0 .. 2 (and in mode 3 unless over half of its rows share one palindrome).
+//   * fold kernel (summary_quant.h, with the limb bound), after every slice of at most SK_FOLD_ROWS rows: a slice adds at most
+//     X = 2 * SK_FOLD_ROWS = 2^22 terms to a cell (mode 3 counts a palindrome twice).  hi stays exact for 2^32 - 2 additions to one
+//     cell, more than a genome of 2^32 rows can make in modes 0 .. 2 (and in mode 3 unless over half of its rows share one palindrome).
 //
 // Motif rate tables (`evaluate --motif_only`, MuRaL/scripts/calc_motif_corr.py:191-261; SummarySink(motifs=...) and tables.motif_table)
 // are the same cells under another key rule: a row adds to EVERY window of m bases (m odd) that contains its site -- m windows of an
@@ -32,10 +30,10 @@
 //     order_by_row), i the window, o = 1 where the window's own key is the larger of the pair.  The minimum is the first window in the
 //     reference's order (rows ascending, i ascending within a row) AND says under which orientation the reference names the entry.
 //   * fold: a row adds up to m <= 15 times to one cell (a homopolymer run), so the slice between two folds is SM_FOLD_ROWS = 2^18 rows:
-//     lo < 2^40 + 15 * 2^18 * 2^40 < 2^63.  hi grows by at most 2^31 + 1 per addition: exact for floor((2^32 - 2) / m) rows in one cell.
+//     X = 15 * 2^18 < 2^22 terms.  hi is exact for floor((2^32 - 2) / m) rows in one cell.
 #include "common.h"
 #include "kmer_key.h"
-#include "summary_quant.h"      // quantise_row, SK_MAX_CLASS, SK_LO_BITS: the cells' limbs, shared with csrc/summary_annot.hip
+#include "summary_quant.h"      // quantise_row, SK_MAX_CLASS, the fold: the cells' limbs, shared with the other integer-sum tables
 
 namespace mural {
 namespace {
@@ -211,17 +209,19 @@ __global__ __launch_bounds__(SK_THREADS) void summary_motif_rows_kernel(KmerArgs
   if (bad) atomicOr(A.status, bad);
 }
 
-// carry the overflow of the lo limbs into the hi limbs: a thread per (key, class), plain loads and stores
-__global__ __launch_bounds__(SK_THREADS) void summary_kmer_fold_kernel(KmerArgs A) {
-  const int j = blockIdx.y, nc = A.n_class;
-  const int64_t t = (int64_t)blockIdx.x * SK_THREADS + threadIdx.x;
-  if (t >= ((int64_t)nc << (2 * A.k[j]))) return;
-  u64* __restrict__ cell = A.table[j] + (t / nc) * (3 * nc) + t % nc;
-  const u64 lo = cell[2 * nc];
-  if (lo >> SK_LO_BITS) {
-    cell[nc] += lo >> SK_LO_BITS;
-    cell[2 * nc] = lo & ((1ull << SK_LO_BITS) - 1);
+// the k-mer (or motif) tables of a call as the fold kernel takes them, and its grid
+int launch_fold(const KmerArgs& A, hipStream_t stream) {
+  FoldTables F{};
+  int64_t fold_threads = 0;
+  for (int j = 0; j < A.n_k; ++j) {
+    F.table[j] = A.table[j], F.n_groups[j] = (int64_t)1 << (2 * A.k[j]);
+    fold_threads = std::max(fold_threads, F.n_groups[j] * A.n_class);
   }
+  F.nc = A.n_class;
+  const dim3 fold_grid((unsigned)((fold_threads + SK_THREADS - 1) / SK_THREADS), (unsigned)A.n_k);
+  hipLaunchKernelGGL(summary_fold_kernel<SK_THREADS>, fold_grid, dim3(SK_THREADS), 0, stream, F);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
 }
 
 }  // namespace
@@ -254,17 +254,14 @@ extern "C" int mural_summary_kmer_rows(const MuralSummaryKmerRows* s, void* stre
   A.prob = s->prob, A.start = s->start, A.end = s->end, A.strand = s->strand, A.label = s->label;
   A.prob_stride = s->prob_stride, A.n = s->n, A.order_base = s->order_base;
   A.label_kind = s->label_kind, A.n_class = s->n_class, A.indel = s->indel ? 1 : 0, A.mode = s->mode, A.n_k = s->n_k;
-  int64_t fold_threads = 0;
   for (int j = 0; j < s->n_k; ++j) {
     A.k[j] = s->k[j];
     A.in_lds[j] = mural_summary_kmer_in_lds(s->k[j], s->n_class);
     A.table[j] = reinterpret_cast<u64*>(s->table[j]), A.first[j] = reinterpret_cast<u64*>(s->first[j]);
-    fold_threads = std::max(fold_threads, (int64_t)s->n_class << (2 * s->k[j]));
   }
   A.status = s->status;
   static DynLdsOnce once;
   if (const int rc = once.ensure(summary_kmer_rows_kernel<float>, summary_kmer_rows_kernel<double>)) return rc;
-  const dim3 fold_grid((unsigned)((fold_threads + SK_THREADS - 1) / SK_THREADS), (unsigned)s->n_k);
   for (int64_t r0 = 0; r0 < s->n; r0 += SK_FOLD_ROWS) {
     const int64_t r1 = std::min(r0 + SK_FOLD_ROWS, s->n);
     const dim3 grid((unsigned)((r1 - r0 + SK_BLOCK_ROWS - 1) / SK_BLOCK_ROWS));
@@ -276,8 +273,7 @@ extern "C" int mural_summary_kmer_rows(const MuralSummaryKmerRows* s, void* stre
         hipLaunchKernelGGL(summary_kmer_rows_kernel<float>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, A, j, r0, r1);
       MURAL_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(summary_kmer_fold_kernel, fold_grid, dim3(SK_THREADS), 0, (hipStream_t)stream, A);
-    MURAL_HIP_CHECK(hipGetLastError());
+    if (const int rc = launch_fold(A, (hipStream_t)stream)) return rc;
   }
   return MURAL_OK;
 }
@@ -307,17 +303,14 @@ extern "C" int mural_summary_motif_rows(const MuralSummaryMotifRows* s, void* st
   A.prob = s->prob, A.start = s->start, A.end = s->end, A.label = s->label;
   A.prob_stride = s->prob_stride, A.n = s->n, A.order_base = s->order_base;
   A.label_kind = s->label_kind, A.n_class = s->n_class, A.indel = s->indel ? 1 : 0, A.n_k = s->n_m, A.by_row = s->order_by_row ? 1 : 0;
-  int64_t fold_threads = 0;
   for (int j = 0; j < s->n_m; ++j) {
     A.k[j] = s->m[j];
     A.in_lds[j] = mural_summary_motif_in_lds(s->m[j], s->n_class);
     A.table[j] = reinterpret_cast<u64*>(s->table[j]), A.first[j] = reinterpret_cast<u64*>(s->first[j]);
-    fold_threads = std::max(fold_threads, (int64_t)s->n_class << (2 * s->m[j]));
   }
   A.status = s->status;
   static DynLdsOnce once;
   if (const int rc = once.ensure(summary_motif_rows_kernel<float>, summary_motif_rows_kernel<double>)) return rc;
-  const dim3 fold_grid((unsigned)((fold_threads + SK_THREADS - 1) / SK_THREADS), (unsigned)s->n_m);
   for (int64_t r0 = 0; r0 < s->n; r0 += SM_FOLD_ROWS) {
     const int64_t r1 = std::min(r0 + SM_FOLD_ROWS, s->n);
     const dim3 grid((unsigned)((r1 - r0 + SK_BLOCK_ROWS - 1) / SK_BLOCK_ROWS));
@@ -329,8 +322,7 @@ extern "C" int mural_summary_motif_rows(const MuralSummaryMotifRows* s, void* st
         hipLaunchKernelGGL(summary_motif_rows_kernel<float>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, A, j, r0, r1);
       MURAL_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(summary_kmer_fold_kernel, fold_grid, dim3(SK_THREADS), 0, (hipStream_t)stream, A);
-    MURAL_HIP_CHECK(hipGetLastError());
+    if (const int rc = launch_fold(A, (hipStream_t)stream)) return rc;
   }
   return MURAL_OK;
 }

@@ -1,7 +1,7 @@
-// The row checks and the two-limb quantisation of the integer-sum summaries, shared by csrc/summary_kmer.hip (k-mer and motif tables)
-// csrc/summary_annot.hip (annotation tables) and csrc/summary_conseq.hip (consequence tables) so that their cells cannot drift:
-// q = rne(p * 2^71) carried as
-// hi = floor(p * 2^31) and lo = rint((p * 2^31 - hi) * 2^40), each step exact in float64.
+// The row checks, the two-limb quantisation and the limb fold of the integer-sum summaries, shared by csrc/summary_kmer.hip (k-mer and
+// motif tables), csrc/summary_annot.hip (annotation tables) and csrc/summary_conseq.hip (consequence tables) so that their cells cannot
+// drift: q = rne(p * 2^71) carried as hi = floor(p * 2^31) and lo = rint((p * 2^31 - hi) * 2^40), each step exact in float64.
+// (csrc/summary_calib.hip carries 46-bit limbs at irregular cell positions: it has a quantisation, a fold and bounds of its own.)
 #pragma once
 #include "common.h"
 #include "kmer_key.h"
@@ -10,7 +10,7 @@ namespace mural {
 
 constexpr int SK_MAX_CLASS = 8;
 constexpr int SK_LO_BITS = 40;
-typedef unsigned long long u64;
+constexpr u64 SK_LO_MASK = (1ull << SK_LO_BITS) - 1;
 
 // One probability as the two limbs; false (and hi = lo = 0) where it is NaN, negative or above 1.
 __device__ __forceinline__ bool quantise_prob(double p, u64& hi, u64& lo) {
@@ -39,6 +39,39 @@ __device__ __forceinline__ int32_t quantise_row(const T* __restrict__ prob, int 
     if (c < nc && !quantise_prob((double)prob[c], hi[c], lo[c])) bad_row |= SM_BAD_PROB;      // (float -> double is exact)
   }
   return bad_row;
+}
+
+// The fold: the overflow of a sum of lo limbs goes into the sum of hi limbs; the pair's value hi * 2^40 + lo does not change.
+// THE LIMB BOUND.  A lo limb is at most 2^40 (2^40 itself where the fraction rounds up: the pair's value stays right), and a folded
+// lo is below 2^40.  A TERM is a lo limb or a folded sum of lo limbs; unfolded sums count as the terms they hold.  A cell that takes at
+// most X terms between two folds holds lo <= 2^40 (1 + X) before the next fold: below 2^63 while X <= 2^23 - 2, and below 2^40 on
+// return from an entry that folds last.  Each file that adds to such cells gives its X in its head comment; with this rule that is
+// all a reader needs.  A hi limb is at most 2^31 and a row's carry at most 1: a cell's hi is exact for 2^32 - 2 additions.
+__device__ __forceinline__ void fold_limbs(u64& hi, u64& lo) {
+  hi += lo >> SK_LO_BITS;
+  lo &= SK_LO_MASK;
+}
+
+// The tables whose lo limbs one launch folds: table blockIdx.y is [n_groups][3][nc] -- label counts | sums of hi | sums of lo.
+struct FoldTables {
+  u64* table[MURAL_SUMMARY_MAX_KMERS];
+  int64_t n_groups[MURAL_SUMMARY_MAX_KMERS];
+  int32_t nc;
+};
+
+// carry the overflow of the tables' lo limbs into their hi limbs: a thread per (group, class), plain loads and stores
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void summary_fold_kernel(FoldTables F) {
+  const int j = blockIdx.y, nc = F.nc;
+  const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (t >= F.n_groups[j] * nc) return;
+  u64* __restrict__ cell = F.table[j] + (t / nc) * (3 * nc) + t % nc;
+  u64 lo = cell[2 * nc];
+  if (lo >> SK_LO_BITS) {
+    u64 hi = cell[nc];
+    fold_limbs(hi, lo);
+    cell[nc] = hi, cell[2 * nc] = lo;
+  }
 }
 
 }  // namespace mural

@@ -69,28 +69,9 @@ __global__ __launch_bounds__(TB_THREADS) void nl_count_kernel(const char* __rest
 // one block: block_off[b] = rows before tile b, meta->n_rows = all rows
 __global__ __launch_bounds__(TB_THREADS) void nl_scan_kernel(const int32_t* __restrict__ block_cnt, int64_t nb,
                                                              int64_t* __restrict__ block_off, ChunkMeta* __restrict__ meta) {
-  const int64_t per = (nb + TB_THREADS - 1) / TB_THREADS;
-  const int64_t b0 = (int64_t)threadIdx.x * per;
-  int64_t s = 0;
-  for (int64_t b = b0; b < b0 + per && b < nb; ++b) s += block_cnt[b];
-  __shared__ int64_t part[TB_THREADS];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t acc = 0;
-    for (int t = 0; t < TB_THREADS; ++t) {
-      const int64_t v = part[t];
-      part[t] = acc;
-      acc += v;
-    }
-    meta->n_rows = acc;
-  }
-  __syncthreads();
-  int64_t acc = part[threadIdx.x];
-  for (int64_t b = b0; b < b0 + per && b < nb; ++b) {
-    block_off[b] = acc;
-    acc += block_cnt[b];
-  }
+  const int64_t rows = run_excl_scan<TB_THREADS, int64_t>(nb, [&](int64_t b) { return (int64_t)block_cnt[b]; },
+                                                          [&](int64_t b, int64_t x) { block_off[b] = x; });
+  if (threadIdx.x == 0) meta->n_rows = rows;
 }
 
 __global__ __launch_bounds__(TB_THREADS) void nl_emit_kernel(const char* __restrict__ buf, int64_t len,

@@ -346,30 +346,9 @@ __global__ void __launch_bounds__(256) tsv_format_kernel(MuralTsvRows t, const c
 
 // exclusive scan of the per-workgroup byte counts (in place) by ONE workgroup; total -> *n_bytes
 __global__ void __launch_bounds__(1024) tsv_scan_kernel(int64_t* __restrict__ block_bytes, int64_t nb, int64_t* __restrict__ n_bytes) {
-  __shared__ int64_t part[1024];
-  const int tid = threadIdx.x;
-  const int64_t per = (nb + 1023) / 1024;
-  const int64_t lo = tid * per < nb ? tid * per : nb, hi = lo + per < nb ? lo + per : nb;
-  int64_t sum = 0;
-  for (int64_t k = lo; k < hi; ++k) sum += block_bytes[k];
-  part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    int64_t run = 0;
-    for (int k = 0; k < 1024; ++k) {
-      const int64_t v = part[k];
-      part[k] = run;
-      run += v;
-    }
-    *n_bytes = run;
-  }
-  __syncthreads();
-  int64_t run = part[tid];
-  for (int64_t k = lo; k < hi; ++k) {
-    const int64_t v = block_bytes[k];
-    block_bytes[k] = run;
-    run += v;
-  }
+  const int64_t total = mural::run_excl_scan<1024, int64_t>(nb, [&](int64_t k) { return block_bytes[k]; },
+                                                            [&](int64_t k, int64_t x) { block_bytes[k] = x; });
+  if (threadIdx.x == 0) *n_bytes = total;
 }
 
 // rows i-1 and i of the same (segment, strand) group must carry the same strand-complemented focal base

@@ -158,6 +158,31 @@ def test_chunk_boundaries(files, golden, tmp_path, chunk_bytes):
     _cmp_rates(open(tables.regional_output_names(prefix, 1000)[0]).read(), str(golden[f"{name}/win1000/rates"]), f32=True)
 
 
+def test_one_chunk_of_more_tiles_than_scan_threads(tmp_path):
+    """A chunk's newline counts per tile of 4096 bytes are scanned by ONE workgroup of 256 threads (nl_scan_kernel): a table of a
+    little over 1 MiB read as one chunk has more tiles than that, so a thread owns a run of two tiles and the last threads none.
+    Row for row -- every column goes through the scaled table's text -- it equals the same file read in chunks of 4096 bytes (one
+    tile each), the route that test_chunk_boundaries ties to the reference."""
+    from mural_amd import tables
+    rng = np.random.default_rng(11)
+    n = 26_000
+    start = np.cumsum(rng.integers(1, 2000, size=n))
+    prob = rng.dirichlet([40, 1, 1, 1], size=n)
+    lines = [_HEAD]
+    for i in range(n):
+        lines.append("chr%d\t%d\t%d\t%s\t%d\t%s" % (1 + i * 3 // n, start[i], start[i] + 1, "+-"[i % 7 == 0], i % 4,
+                                                   "\t".join("%.4g" % p for p in prob[i])))
+    table = _bad_table(tmp_path, lines)
+    size = len(open(table, "rb").read())
+    assert 257 * 4096 < size < (1 << 21)
+    texts = []
+    for chunk_bytes in (1 << 21, 4096):
+        out = str(tmp_path / f"scaled{chunk_bytes}.tsv")
+        tables.apply_scaling_file(table, 0.5, 4, out, chunk_bytes=chunk_bytes)
+        texts.append(_text(out).splitlines())
+    assert len(texts[0]) == n + 1 and texts[0] == texts[1]
+
+
 def _bad_table(tmp_path, lines, gz=False):
     text = "".join(ln + "\n" for ln in lines)
     p = tmp_path / ("bad.tsv" + (".gz" if gz else ""))

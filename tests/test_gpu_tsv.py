@@ -50,6 +50,29 @@ def test_device_formatter_equals_host_formatter_and_pandas(dtype, k, n):
         assert table.split(b"\n", 1)[1] == got
 
 
+def test_more_format_blocks_than_scan_threads_equals_two_smaller_calls():
+    """The byte counts of the format workgroups are scanned by ONE workgroup of 1024 threads (tsv_scan_kernel): with 40 classes a row
+    may take 513 bytes, a workgroup then formats 32 rows, and 32 * 1024 + 5 rows are 1025 workgroups -- a thread of the scan owns two
+    of them and half of the threads none.  The text equals that of the same rows formatted in two calls of 513 workgroups each."""
+    k, n = 40, 32 * 1024 + 5
+    r = _random_rows(np.random.default_rng(7), n, k, np.float32)
+    st = (r["strand"] == "-").astype(np.uint8)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    cols = [dev(r["start"]), dev(r["end"]), dev(st), dev(r["label"]), dev(r["prob"])]
+    # the entry's rule for the rows of a workgroup (mural_tsv_format_device)
+    names = _name_table(["chr12"])
+    t = _tsv_struct(names, 1, None, *[c.data_ptr() for c in cols], False, k, k, None, n)
+    bound, rows = int(_lib.lib().mural_tsv_row_bound(C.byref(t))), 256
+    while rows > 32 and 2 * rows * bound > 64 * 1024:
+        rows //= 2
+    half = (n // 2 + rows - 1) // rows * rows
+    assert -(-n // rows) > 1024 and -(-half // rows) <= 1024 and -(-(n - half) // rows) <= 1024
+    whole = _format_device("chr12", *cols, k)
+    parts = [_format_device("chr12", *[c[a:b] for c in cols], k) for a, b in ((0, half), (half, n))]
+    assert whole == parts[0] + parts[1]
+    assert whole.count(b"\n") == n
+
+
 def test_device_formatter_empty_and_long_names():
     z = lambda dt: torch.zeros(0, dtype=dt, device="cuda")      # noqa: E731
     assert _format_device("c", z(torch.int64), z(torch.int64), z(torch.uint8), z(torch.float32), torch.zeros((0, 5), device="cuda"), 4) == b""
