@@ -997,6 +997,58 @@ size_t mural_simulate_rows_workspace_bytes(int64_t n);
 int mural_simulate_rows(const MuralSimulateRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The simulated null of the consequence table of a shard while it is on the device (SummarySink(simulate=R,
+ * transcripts=..., simulate_transcripts=True) in flight, tables.simulate_consequence_table from a written table;
+ * csrc/simulate_conseq.hip; mural_amd.summaries.simulate_conseq_host is the specification).  Rows as
+ * mural_simulate_annot_rows (SNV rows, n_class == 4, of a part of ONE chromosome, ascending in start; no label is read),
+ * genome, segments, transcripts, aa and alt_order as mural_summary_conseq_rows.
+ *   table [n_transcripts][5][n_rep] of unsigned 32-bit cells: cell [t][b][r] += the rows inside the CDS of transcript t
+ *   whose replicate-r draw (the draw of mural_simulate_annot_rows, unchanged) is a class c >= 1 whose substitution falls in
+ *   bin b of t (the bin of mural_summary_conseq_rows: 0 syn, 1 mis, 2 stop gained, 3 stop lost, 4 unresolved).  A row
+ *   counts once per transcript that covers it; class 0 counts nowhere.  Zeroed by the caller once, it accumulates over
+ *   calls, parts and chromosomes, and is a function of the SET of rows and the seed alone, bit for bit.
+ *   status: the simulation's bits -- bit 3 a probability of a class >= 1 that is NaN, negative or infinite, bit 0 a
+ *   negative start (such rows draw class 0 in every replicate), bit 2 a start below the row before it inside the call;
+ *   a probability of 1 or more is taken as 1.  A segment whose transcript is outside 0 .. n_transcripts - 1 is skipped.
+ * MURAL_E_INVALID, before the first launch: n_class != 4, n_rep outside 1 .. 2^20, n > 2^31, n_segments > 2^22, an
+ * alt_order row that does not name the three other bases once each.  The loop bounds are mural_simulate_chunk_rows(),
+ * mural_simulate_grid_waves() and mural_simulate_scan_threads(): the grid strides over units of (chunk of a segment,
+ * group of up to 16 blocks of 64 replicates); a row's bins are formed once per unit.
+ * ws: mural_simulate_conseq_workspace_bytes(n_segments) bytes (24 per segment), 8-byte aligned; MURAL_E_WORKSPACE when
+ * smaller.  n == 0 launches nothing; n_segments == 0 only checks the rows.  Launches on `stream`: no synchronisation, no
+ * read-back, no floating-point atomics; draws and bins are recomputed, never stored.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const MuralGenome* genome; /* the chromosome of the rows */
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. 3 are read                  */
+  int32_t prob_f64, n_class; /* n_class == 4 */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const uint8_t* strand;     /* dev [n], 1 = '-', or NULL */
+  int64_t n;
+  uint32_t chrom_key;
+  int32_t n_rep;
+  uint64_t seed;
+  const int64_t* seg_b0;     /* dev [n_segments] */
+  const int64_t* seg_b1;     /* dev [n_segments] */
+  const int64_t* seg_cds0;   /* dev [n_segments] */
+  const int32_t* seg_tx;     /* dev [n_segments] */
+  const int32_t* seg_prev;   /* dev [n_segments] */
+  const int32_t* seg_next;   /* dev [n_segments] */
+  int64_t n_segments;
+  const uint8_t* tx_strand;  /* dev [n_transcripts] */
+  const int64_t* tx_cds_len; /* dev [n_transcripts] */
+  int32_t n_transcripts, reserved;
+  uint8_t aa[64];
+  uint8_t alt_order[4][3];
+  uint8_t reserved2[4];
+  uint32_t* table;           /* dev [n_transcripts][5][n_rep] */
+  int32_t* status;           /* dev [1] */
+} MuralSimulateConseqRows;
+size_t mural_simulate_conseq_workspace_bytes(int64_t n_segments);
+int mural_simulate_conseq_rows(const MuralSimulateConseqRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

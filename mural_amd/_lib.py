@@ -145,6 +145,16 @@ class MuralSimulateAnnotRows(C.Structure):
                 ("n_groups", C.c_int32), ("reserved", C.c_int32), ("table", C.c_void_p), ("status", C.c_void_p)]
 
 
+class MuralSimulateConseqRows(C.Structure):
+    _fields_ = [("genome", C.POINTER(MuralGenome)), ("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32),
+                ("prob_stride", C.c_int64), ("start", C.c_void_p), ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32),
+                ("n_rep", C.c_int32), ("seed", C.c_uint64), ("seg_b0", C.c_void_p), ("seg_b1", C.c_void_p), ("seg_cds0", C.c_void_p),
+                ("seg_tx", C.c_void_p), ("seg_prev", C.c_void_p), ("seg_next", C.c_void_p), ("n_segments", C.c_int64),
+                ("tx_strand", C.c_void_p), ("tx_cds_len", C.c_void_p), ("n_transcripts", C.c_int32), ("reserved", C.c_int32),
+                ("aa", C.c_uint8 * 64), ("alt_order", (C.c_uint8 * 3) * 4), ("reserved2", C.c_uint8 * 4), ("table", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 class MuralSimulateRows(C.Structure):
     _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
                 ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("replicate", C.c_int32), ("seed", C.c_uint64),
@@ -321,6 +331,8 @@ PROTOTYPES = {
     "mural_simulate_annot_rows": (C.c_int, [C.POINTER(MuralSimulateAnnotRows), VP, C.c_size_t, VP]),
     "mural_simulate_rows_workspace_bytes": (C.c_size_t, [I64]),
     "mural_simulate_rows": (C.c_int, [C.POINTER(MuralSimulateRows), VP, C.c_size_t, VP]),
+    "mural_simulate_conseq_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_simulate_conseq_rows": (C.c_int, [C.POINTER(MuralSimulateConseqRows), VP, C.c_size_t, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

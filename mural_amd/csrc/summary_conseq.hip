@@ -2,7 +2,8 @@
 // SummarySink(transcripts=...); tables.consequence_table from a written table): per transcript of a BED12 file the label counts and the
 // sums of the probabilities of the SNV rows inside its CDS, split by what each of a row's three substitutions does to the codon it falls
 // in -- synonymous, missense, stop gained, stop lost, or unresolved (an incomplete or masked codon).  summaries.summary_conseq_host is
-// the specification; DESIGN.md section 3.21.
+// the specification; DESIGN.md section 3.21.  The codon and the class-to-bin rule live in conseq_bins.h, which csrc/simulate_conseq.hip
+// includes as well.
 //
 // The host (tables.read_transcripts) turns every transcript into its CDS SEGMENTS [b0, b1) with the CDS offset of the segment's first
 // base in transcript orientation and the indices of the transcript's neighbouring segments; transcripts overlap and nest freely, so a
@@ -23,6 +24,7 @@
 // No per-row bin is stored (the check and the reduce kernel both recompute a row); no floating-point atomics, no synchronisation, no
 // read-back.
 #include "common.h"
+#include "conseq_bins.h"
 #include "kmer_key.h"
 #include "row_chunks.h"
 #include "summary_quant.h"
@@ -37,9 +39,7 @@ constexpr int64_t SC_CHUNK_ROWS = 1024;           // rows of one unit of the red
 constexpr int64_t SC_GRID_WAVES = 8192;           // waves of the reduce kernel's grid; they stride over the chunks
 constexpr int64_t SC_MAX_ROWS = 1ll << 31;        // per call (the fold bound above)
 constexpr int64_t SC_MAX_SEGMENTS = 1ll << 22;    // per call
-constexpr int SC_BINS = 5;                        // synonymous, missense, stop gained, stop lost, unresolved
 constexpr int SC_CELL_WORDS = 3 * SC_BINS;        // per transcript: [bin][label count | sum of hi | sum of lo]
-constexpr int SC_NOWHERE = SC_BINS;               // the bin of a class that is not counted
 
 struct ConseqArgs {
   MuralGenome g;
@@ -98,44 +98,6 @@ __global__ __launch_bounds__(SC_SCAN_THREADS) void summary_conseq_scan_kernel(in
   if (threadIdx.x == 0) v[m] = total;
 }
 
-// The codon (16 b0 + 4 b1 + b2, read 5' -> 3' on the transcript's strand) that holds CDS offsets cs .. cs + 2 of the transcript of
-// segment s, or -1 where a position is not found within two hops, lies outside the record or is masked.  Every index is checked
-// before it is used.
-__device__ __forceinline__ int conseq_codon(const ConseqArgs& A, int64_t s, int32_t tx, bool minus, int64_t cs) {
-  int codon = 0;
-  bool found = true;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int64_t o = cs + j;
-    int64_t cur = s;
-#pragma unroll
-    for (int hop = 0; hop < 2; ++hop) {
-      const int64_t c0 = A.seg_cds0[cur], len = A.seg_b1[cur] - A.seg_b0[cur];
-      int64_t nx = cur;
-      if (o < c0) nx = A.seg_prev[cur];
-      else if (o >= c0 + len) nx = A.seg_next[cur];
-      if (nx < 0 || nx >= A.n_seg) {
-        found = false;
-        nx = cur;
-      }
-      cur = nx;
-    }
-    const int64_t c0 = A.seg_cds0[cur], sb0 = A.seg_b0[cur], sb1 = A.seg_b1[cur];
-    found = found && o >= c0 && o < c0 + (sb1 - sb0) && A.seg_tx[cur] == tx;
-    const int64_t pos = minus ? sb1 - 1 - (o - c0) : sb0 + (o - c0);
-    int32_t code = 0;
-    if (found && pos >= 0 && pos < A.g.length) {
-      bool masked = false;
-      code = kmer_base(A.g, pos, masked);
-      found = !masked;
-    } else {
-      found = false;
-    }
-    codon = codon * 4 + (minus ? 3 - code : code);
-  }
-  return found ? codon : -1;
-}
-
 template <typename T>
 __global__ __launch_bounds__(SC_THREADS) void summary_conseq_reduce_kernel(ConseqArgs A, const int64_t* __restrict__ row0,
                                                                            const int64_t* __restrict__ row1, const int64_t* __restrict__ pre,
@@ -173,25 +135,7 @@ __global__ __launch_bounds__(SC_THREADS) void summary_conseq_reduce_kernel(Conse
         // (the status is the check kernel's; q lies in [b0, b1) unless the rows do not ascend: then the row is skipped here)
         live = conseq_row<T>(A, i, lab, hi, lo) == 0 && q >= b0 && q < b1;
         if (live) {
-          const int64_t x = cds0 + (minus ? b1 - 1 - q : q - b0);
-          const int64_t cs = x - x % 3;
-          const int codon = (x >= 0 && cs + 2 < cds_len) ? conseq_codon(A, s, tx, minus, cs) : -1;
-          if (codon < 0) {
-            bins[0] = bins[1] = bins[2] = SC_BINS - 1;
-          } else {
-            const int sh = 2 * (2 - (int)(x - cs));
-            const int own_tx = (codon >> sh) & 3;                       // the base at q, on the transcript's strand
-            const bool row_minus = A.strand != nullptr && A.strand[i] != 0;
-            const int r = (minus != row_minus) ? 3 - own_tx : own_tx;   // the row's own base
-            const uint8_t aa_ref = aa[codon];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-              const int alt = (int)(A.alt_packed >> (2 * (3 * r + c))) & 3;      // on the row's strand
-              const int alt_tx = (minus != row_minus) ? 3 - alt : alt;
-              const uint8_t aa_alt = aa[(codon & ~(3 << sh)) | (alt_tx << sh)];
-              bins[c] = aa_ref == aa_alt ? 0 : aa_alt == '*' ? 2 : aa_ref == '*' ? 3 : 1;
-            }
-          }
+          conseq_row_bins(A, aa, s, tx, minus, cds_len, b0, b1, cds0, i, q, bins);
         } else {
 #pragma unroll
           for (int c = 0; c < 3; ++c) hi[c] = 0, lo[c] = 0;
@@ -249,15 +193,9 @@ extern "C" int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* 
   MURAL_REQUIRE(s->n_transcripts >= 0, "summary_conseq_rows: n_transcripts < 0");
   MURAL_REQUIRE(s->label_kind >= 0 && s->label_kind <= 2, "summary_conseq_rows: label_kind is 0 (float32), 1 (int32) or 2 (int64)");
   uint32_t alt_packed = 0;
-  for (int r = 0; r < 4; ++r) {
-    unsigned seen = 1u << r;
-    for (int j = 0; j < 3; ++j) {
-      const unsigned a = s->alt_order[r][j];
-      MURAL_REQUIRE(a < 4 && !(seen & (1u << a)), "summary_conseq_rows: alt_order[%d] must name the three other bases once each", r);
-      seen |= 1u << a;
-      alt_packed |= a << (2 * (3 * r + j));
-    }
-  }
+  int bad_alt = 0;
+  MURAL_REQUIRE(conseq_pack_alt_order(s->alt_order, alt_packed, bad_alt),
+                "summary_conseq_rows: alt_order[%d] must name the three other bases once each", bad_alt);
   if (s->n == 0 || s->n_segments == 0) return MURAL_OK;
   MURAL_REQUIRE(s->genome && s->genome->packed2 && s->genome->nmask && s->genome->length >= 0, "summary_conseq_rows: empty genome");
   MURAL_REQUIRE(s->prob && s->start && s->label && s->status && s->table && s->rows, "summary_conseq_rows: NULL argument");

@@ -14,7 +14,8 @@ from . import _lib
 from .calibration import calibrate_device, dirichlet_calibrate, save_dirichlet_calibrator
 from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
 from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds, shard_name, strand_u8
-from .tables import (annotation_meta, annotation_output_names, check_alt_order, consequence_output_name, consequence_table_from_sums,
+from .tables import (annotation_meta, annotation_output_names, check_alt_order, consequence_output_name,
+                     consequence_simulation_output_name, consequence_table_from_sums, write_consequence_simulation_outputs,
                      read_transcripts, write_consequence_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
                      write_simulation_outputs, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
@@ -375,38 +376,11 @@ def _conseq_row_checks(prob, start, label):
     return hi, lo, lab, ~(bad_label | bad_start | bad_prob), status
 
 
-def summary_conseq_host(genome, prob, start, strand, label, segments, n_transcripts, aa=None, alt_order=None, into=None, n_class=4):
-    """The numpy twin of ``mural_summary_conseq_rows`` -- and its specification -- for SNV rows (any order) of one chromosome:
-    (table uint64 [n_transcripts][5][3], rows uint64 [n_transcripts][2], status).  `segments`: the chromosome's dict of
-    ``tables.read_transcripts`` (or None); `aa`: uint8 [64] (``tables.check_codon_table``; None: the standard code); `alt_order`:
-    ``tables.check_alt_order``'s argument; `strand`: 1 / '-' where the row is on the reverse strand, None for all '+'.
-
-    For row i at q = start[i] and every segment with seg_b0 <= q < seg_b1: g = the reference base at q, r = the row's own base
-    (comp(g) where strand[i]); class c = 1 .. 3 is the substitution r > alt_order[r][c - 1] on the row's strand, complemented onto the
-    reference strand where strand[i]; x = seg_cds0 + (q - seg_b0) on a '+' transcript, seg_cds0 + (seg_b1 - 1 - q) on a '-' one; the
-    codon is offsets 3 floor(x / 3) .. + 2, mapped to genomic positions over seg_prev / seg_next (at most two hops each), complemented
-    for a '-' transcript and read 5' -> 3'.  All three classes go to bin 4 (unresolved) when 3 floor(x / 3) + 2 >= tx_cds_len, a codon
-    base is masked (N or IUPAC) or a codon position falls outside the record; otherwise class c goes to bin 0 (synonymous: aa_ref ==
-    aa_alt, stop -> stop included), 2 (stop gained: aa_alt == '*'), 3 (stop lost: aa_ref == '*') or 1 (missense).  Cell [t][b] += {label
-    == c, hi(p_c), lo(p_c)} (the limbs of ``kmer_quantise``) per (row, c) routed to bin b of transcript t; rows[t] += {1, label == 0}
-    per row inside t's CDS.  A row counts once per transcript that covers it; integer sums, so both tables are a function of the SET of
-    rows, bit for bit; on return lo < 2^40.  `into`: (table, rows) of earlier parts and chromosomes to add to, in place.  Status bits: 1
-    a negative start, 2 a label outside 0 .. 3, 8 a probability of a class >= 1 that is NaN, negative or above 1; such rows are
-    skipped."""
-    from .tables import check_alt_order, check_codon_table
-    if int(n_class) != 4:
-        raise ValueError("the consequence table takes SNV rows of 4 classes (INDEL tables are out of scope)")
-    n_tx = int(n_transcripts)
-    aa = check_codon_table(aa).astype(np.int64)
-    alt_of = check_alt_order(alt_order).astype(np.int64)
-    start = np.asarray(start, np.int64)
-    hi, lo, lab, ok, status = _conseq_row_checks(prob, start, label)
-    table, rows = (np.zeros((n_tx, 5, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if into is None else into
-    if segments is None or len(segments["seg_b0"]) == 0 or not ok.any():
-        return table, rows, status
-    rs = np.zeros(len(start), np.int64) if strand is None else strand_u8(strand).astype(np.int64)
-    order = np.argsort(start[ok], kind="stable")
-    hi, lo, start, lab, rs = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order], rs[ok][order]
+def _conseq_pairs(genome, start, rs, segments, aa, alt_of):
+    """The one bin rule of the consequence tables on the host, shared by ``summary_conseq_host`` and ``simulate_conseq_host``: for rows
+    sorted by start (`rs`: their strands as int64 0 / 1) and a chromosome's `segments`, yields (i, tx, bins) per pass of at most
+    ``_CONSEQ_PAIRS`` (segment, row) pairs with seg_b0 <= start[i] < seg_b1 -- the row index, the segment's transcript and bins int64
+    [pairs][3], the bin 0 .. 4 of classes 1 .. 3 by the rule ``summary_conseq_host`` states."""
     b0, b1, cds0 = (np.asarray(segments[key], np.int64) for key in ("seg_b0", "seg_b1", "seg_cds0"))
     seg_tx, prev, nxt = (np.asarray(segments[key], np.int64) for key in ("seg_tx", "seg_prev", "seg_next"))
     tx_minus, tx_len = np.asarray(segments["tx_strand"]) != 0, np.asarray(segments["tx_cds_len"], np.int64)
@@ -415,7 +389,6 @@ def summary_conseq_host(genome, prob, start, strand, label, segments, n_transcri
     i1 = np.maximum(np.searchsorted(start, b1, "left"), i0)
     n_in = i1 - i0
     ends = np.cumsum(n_in)
-    flat_table, flat_rows = table.reshape(-1), rows.reshape(-1)
     for p0 in range(0, int(ends[-1]), _CONSEQ_PAIRS):
         pair = np.arange(p0, min(p0 + _CONSEQ_PAIRS, int(ends[-1])), dtype=np.int64)
         s = np.searchsorted(ends, pair, "right")                       # the pair's segment
@@ -449,13 +422,53 @@ def summary_conseq_host(genome, prob, start, strand, label, segments, n_transcri
         own_tx = (codon >> sh) & 3
         flip = minus != (rs[i] != 0)
         r = np.where(flip, 3 - own_tx, own_tx)
-        cell = tx * 15
+        bins = np.empty((len(pair), 3), np.int64)
         for c in range(3):
             alt = alt_of[r, c]
             alt_tx = np.where(flip, 3 - alt, alt)
             a_ref, a_alt = aa[codon], aa[(codon & ~(3 << sh)) | (alt_tx << sh)]
             b = np.where(a_ref == a_alt, 0, np.where(a_alt == _CONSEQ_STOP, 2, np.where(a_ref == _CONSEQ_STOP, 3, 1)))
-            b = np.where(found, b, 4)
+            bins[:, c] = np.where(found, b, 4)
+        yield i, tx, bins
+
+
+def summary_conseq_host(genome, prob, start, strand, label, segments, n_transcripts, aa=None, alt_order=None, into=None, n_class=4):
+    """The numpy twin of ``mural_summary_conseq_rows`` -- and its specification -- for SNV rows (any order) of one chromosome:
+    (table uint64 [n_transcripts][5][3], rows uint64 [n_transcripts][2], status).  `segments`: the chromosome's dict of
+    ``tables.read_transcripts`` (or None); `aa`: uint8 [64] (``tables.check_codon_table``; None: the standard code); `alt_order`:
+    ``tables.check_alt_order``'s argument; `strand`: 1 / '-' where the row is on the reverse strand, None for all '+'.
+
+    For row i at q = start[i] and every segment with seg_b0 <= q < seg_b1: g = the reference base at q, r = the row's own base
+    (comp(g) where strand[i]); class c = 1 .. 3 is the substitution r > alt_order[r][c - 1] on the row's strand, complemented onto the
+    reference strand where strand[i]; x = seg_cds0 + (q - seg_b0) on a '+' transcript, seg_cds0 + (seg_b1 - 1 - q) on a '-' one; the
+    codon is offsets 3 floor(x / 3) .. + 2, mapped to genomic positions over seg_prev / seg_next (at most two hops each), complemented
+    for a '-' transcript and read 5' -> 3'.  All three classes go to bin 4 (unresolved) when 3 floor(x / 3) + 2 >= tx_cds_len, a codon
+    base is masked (N or IUPAC) or a codon position falls outside the record; otherwise class c goes to bin 0 (synonymous: aa_ref ==
+    aa_alt, stop -> stop included), 2 (stop gained: aa_alt == '*'), 3 (stop lost: aa_ref == '*') or 1 (missense).  Cell [t][b] += {label
+    == c, hi(p_c), lo(p_c)} (the limbs of ``kmer_quantise``) per (row, c) routed to bin b of transcript t; rows[t] += {1, label == 0}
+    per row inside t's CDS.  A row counts once per transcript that covers it; integer sums, so both tables are a function of the SET of
+    rows, bit for bit; on return lo < 2^40.  `into`: (table, rows) of earlier parts and chromosomes to add to, in place.  Status bits: 1
+    a negative start, 2 a label outside 0 .. 3, 8 a probability of a class >= 1 that is NaN, negative or above 1; such rows are
+    skipped."""
+    from .tables import check_alt_order, check_codon_table
+    if int(n_class) != 4:
+        raise ValueError("the consequence table takes SNV rows of 4 classes (INDEL tables are out of scope)")
+    n_tx = int(n_transcripts)
+    aa = check_codon_table(aa).astype(np.int64)
+    alt_of = check_alt_order(alt_order).astype(np.int64)
+    start = np.asarray(start, np.int64)
+    hi, lo, lab, ok, status = _conseq_row_checks(prob, start, label)
+    table, rows = (np.zeros((n_tx, 5, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if into is None else into
+    if segments is None or len(segments["seg_b0"]) == 0 or not ok.any():
+        return table, rows, status
+    rs = np.zeros(len(start), np.int64) if strand is None else strand_u8(strand).astype(np.int64)
+    order = np.argsort(start[ok], kind="stable")
+    hi, lo, start, lab, rs = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order], rs[ok][order]
+    flat_table, flat_rows = table.reshape(-1), rows.reshape(-1)
+    for i, tx, bins in _conseq_pairs(genome, start, rs, segments, aa, alt_of):
+        cell = tx * 15
+        for c in range(3):
+            b = bins[:, c]
             np.add.at(flat_table, cell + 3 * b, (lab[i] == c + 1).astype(np.uint64))
             np.add.at(flat_table, cell + 3 * b + 1, hi[i, c])
             np.add.at(flat_table, cell + 3 * b + 2, lo[i, c])
@@ -599,6 +612,71 @@ def simulate_annot_host(prob, start, strand, n_class, chrom_key, seed, pieces, n
     live = np.nonzero((i1 > i0) & (grp >= 0) & (grp < ng))[0]
     np.add.at(table, grp[live], prefix[i1[live]] - prefix[i0[live]])
     return table, status
+
+
+def simulate_conseq_host(genome, prob, start, strand, segments, n_transcripts, chrom_key, seed, n_rep, aa=None, alt_order=None, into=None):
+    """The numpy twin of ``mural_simulate_conseq_rows`` -- and its specification -- for SNV rows (4 classes; no label is read) of one
+    chromosome: (table uint32 [n_transcripts][5][n_rep], status).  Cell [t][b][r]: the rows inside the CDS of transcript t whose
+    replicate-r draw is a class c >= 1 whose substitution c falls in bin b of t.  The draw is ``simulate_rows_host``'s, unchanged
+    (Philox key and counter, cum, ties); the bin is ``summary_conseq_host``'s rule (0 syn, 1 mis, 2 stop gained, 3 stop lost, 4
+    unresolved; `segments`, `aa`, `alt_order` and `strand` as there).  A row counts once per transcript that covers it; class 0 counts
+    nowhere.  The row checks are the simulation's: a NaN, negative or infinite p_c of a class c >= 1 sets status 8, a negative start
+    status 1 -- such rows draw class 0 in every replicate --, a start below the row before it status 4; p_c >= 1 is taken as 1 and is
+    no error here.  The table is a function of the SET of rows and the seed alone, bit for bit, for any parts, shards or ranks.
+    `into`: the table of earlier parts and chromosomes, added to in place.
+
+    THE DEFINING IDENTITY.  For rows that both rules accept (finite p in [0, 1], start >= 0), cell [t][b][r] equals cell [t][b][0] --
+    the observed count -- of ``summary_conseq_host`` run with label = ``simulate_rows_host(..)[:, r]``: two specifications with
+    independent oracles, composed, are the oracle of this one."""
+    from .tables import check_alt_order, check_codon_table
+    n_tx, R = int(n_transcripts), int(n_rep)
+    if not 1 <= R <= SIMULATE_MAX_REPLICATES:
+        raise ValueError("simulate: 1 .. 2^20 replicates")
+    aa = check_codon_table(aa).astype(np.int64)
+    alt_of = check_alt_order(alt_order).astype(np.int64)
+    start = np.asarray(start, np.int64)
+    labels, status = simulate_rows_host(prob, start, strand, 4, chrom_key, seed, np.arange(R), with_status=True)
+    if len(start) > 1 and (start[1:] < start[:-1]).any():
+        status |= 4
+    table = np.zeros((n_tx, 5, R), np.uint32) if into is None else into
+    if segments is None or len(segments["seg_b0"]) == 0 or len(start) == 0:
+        return table, status
+    rs = np.zeros(len(start), np.int64) if strand is None else strand_u8(strand).astype(np.int64)
+    order = np.argsort(start, kind="stable")
+    start, labels, rs = start[order], labels[order], rs[order]
+    flat = table.reshape(-1, R)
+    for i, tx, bins in _conseq_pairs(genome, start, rs, segments, aa, alt_of):
+        lab = labels[i].astype(np.int64)                                                 # [pairs][R]
+        lb = np.take_along_axis(bins, np.maximum(lab - 1, 0), axis=1)                    # the bin of the drawn class
+        for b in range(5):
+            hit = ((lab > 0) & (lb == b)).astype(np.uint32)
+            np.add.at(flat, tx * 5 + b, hit)
+    return table, status
+
+
+def simulate_conseq_rows_device(table, status, acc, name, n_transcripts, aa, alt_order, genome_struct, dev, n_rep, seed, *, prob, prob_f64,
+                                prob_stride, start, strand, n):
+    """One ``mural_simulate_conseq_rows`` call on device pointers into `table` (int32 [n_transcripts * 5 * n_rep]) and `status`, on the
+    segment arrays ``conseq_rows_device`` uploaded into `acc` for chromosome `name` just before; the workspace is `acc`'s (24 bytes a
+    segment in both entries, and the launches of one stream run in order)."""
+    lib = _lib.lib()
+    on_dev = acc["segments"][name]
+    n_seg = int(on_dev[0].shape[0])
+    need = int(lib.mural_simulate_conseq_workspace_bytes(n_seg))
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _lib.MuralSimulateConseqRows()
+    s.genome = C.pointer(genome_struct)
+    s.prob, s.prob_f64, s.prob_stride, s.n_class = prob, int(prob_f64), int(prob_stride), 4
+    s.start, s.strand, s.n = start, strand, int(n)
+    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
+    s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in on_dev[:6])
+    s.n_segments, s.n_transcripts = n_seg, int(n_transcripts)
+    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
+    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
+    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+    s.table, s.status = table.data_ptr(), status.data_ptr()
+    _lib.check(lib.mural_simulate_conseq_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
 
 
 def simulate_pvalues(counts, observed=None):
@@ -1449,6 +1527,83 @@ class _SimulationReducer:
                     os.unlink(path + ".part%04d" % rank)
 
 
+class _ConsequenceSimulationReducer:
+    """The simulated null of the consequence table (``simulate_conseq_host`` is the rule): per transcript of the consequence reducer
+    before it, consequence bin and replicate the simulated count -- ONE uint32 table [transcripts][5][n_rep] on the host and one per
+    device, on the segment arrays the consequence reducer uploaded just before, read back once."""
+    name = "consequence_simulation"
+
+    def __init__(self, n_rep, seed, conseq, table_bytes_max):
+        self.n_rep, self.seed, self.conseq, self.table_bytes_max = int(n_rep), int(seed), conseq, int(table_bytes_max)
+        if not 1 <= self.n_rep <= SIMULATE_MAX_REPLICATES:
+            raise ValueError("simulate: 1 .. 2^20 replicates")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError("simulate_seed is an unsigned 64-bit integer")
+        need = len(conseq.names) * 5 * self.n_rep * 4
+        if need > self.table_bytes_max:
+            raise ValueError(f"simulate: the table of {len(conseq.names)} transcripts x 5 consequences x {self.n_rep} replicates takes "
+                             f"{need} bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        self.reset()
+
+    def reset(self):
+        self.host = None               # table uint32 [transcripts][5][n_rep] of the host shards
+        self.dev = {}                  # device -> dict(table, status)
+        self.counts = None
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        self.conseq._check(k)
+        segments = self.conseq.segments.get(name)
+        if segments is None:
+            return 0
+        if self.host is None:
+            self.host = np.zeros((len(self.conseq.names), 5, self.n_rep), np.uint32)
+        return simulate_conseq_host(self.conseq.genome(name), prob, start, strand, segments, len(self.conseq.names), simulate_chrom_key(name),
+                                    self.seed, self.n_rep, self.conseq.meta["aa"], self.conseq.alt_order, into=self.host)[1]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the draws of a part behind its consequence reduction, into the device's one table."""
+        self.conseq._check(k)
+        if self.conseq.segments.get(name) is None or start.shape[0] == 0:
+            return None
+        dev, n_tx = prob.device, len(self.conseq.names)
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(max(n_tx * 5 * self.n_rep, 1), dtype=torch.int32, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev))
+        genome = self.conseq.genome(name)
+        simulate_conseq_rows_device(acc["table"], acc["status"], self.conseq.dev[dev], name, n_tx, self.conseq.meta["aa"],
+                                    self.conseq.alt_order, genome.as_struct(dev), dev, self.n_rep, self.seed, prob=prob.data_ptr(),
+                                    prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
+                                    strand=strand.data_ptr(), n=start.shape[0])
+        return genome
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, table, n_tx = 0, self.host, len(self.conseq.names)
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine = acc["table"].cpu().numpy().view(np.uint32)[:n_tx * 5 * self.n_rep].reshape(n_tx, 5, self.n_rep)
+            table = mine.copy() if table is None else table + mine
+        return table, status
+
+    def merge(self, states, k):
+        table = None
+        for st in states:
+            if st is not None:
+                table = st.copy() if table is None else table + st
+        return table
+
+    def finish(self, state, k, result):
+        self.counts = np.zeros((len(self.conseq.names), 5, self.n_rep), np.uint32) if state is None else state
+        names, _, table = result["consequences"]
+        observed = table[:, 4:11:2] if self.conseq.labels else None
+        result[self.name] = (names, self.counts, observed, table[:, 3:11:2])
+
+    def write(self, out_prefix, result, k, written):
+        written.append(consequence_simulation_output_name(out_prefix))
+        write_consequence_simulation_outputs(*result[self.name], out_prefix)
+
+
 class _CalibrationReducer:
     """The integer tables behind NLL / ECE / classwise ECE / Brier per chromosome and, with `fit_calibrator`, the retained rows and the
     calibrator fit on them at close()."""
@@ -1734,6 +1889,15 @@ class SummarySink:
     ``tables.consequence_table_from_sums``); close() writes ``{out_prefix}.consequence.mut_rates.tsv``
     (``tables.write_consequence_outputs``; `transcript_labels=False` says that the rows carry no labels: the observed columns are NA);
     ``consequence_sums()`` has the integers.
+    `simulate_transcripts=True` (with `simulate`, `simulate_seed` and `transcripts`; opt-in: `simulate` beside `transcripts` alone
+    draws nothing per transcript): the null distribution of the observed_* columns -- per transcript, consequence and replicate the
+    rows inside the CDS whose draw is a class whose substitution has that consequence (``simulate_conseq_host`` is the rule; DESIGN.md
+    section 3.22), device parts through ``mural_simulate_conseq_rows`` (csrc/simulate_conseq.hip) on the segment arrays the consequence
+    reduction uploaded, one uint32 table [transcripts][5][R] (checked against `simulate_table_bytes_max` on its own) read back once and
+    added across ranks in the same collective.  `simulate` then needs neither `annotations` nor `simulate_write`.
+    result()["consequence_simulation"] = (names, counts, observed or None, expected), the last two [transcripts][4] from the
+    consequence table; close() writes ``{out_prefix}.consequence.sim.tsv`` (``tables.write_consequence_simulation_outputs``);
+    ``consequence_simulation_counts()`` has the table.
 
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
@@ -1744,7 +1908,7 @@ class SummarySink:
                  group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
                  calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
                  simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True, transcripts=None,
-                 codon_table=None, alt_order=None, transcript_labels=True):
+                 codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -1770,17 +1934,24 @@ class SummarySink:
         if self.simulate:
             if simulate_seed is None:
                 raise ValueError("simulate needs simulate_seed: there is no default randomness")
-            if annotations is None and not tuple(simulate_write):
+            if annotations is None and not tuple(simulate_write) and not simulate_transcripts:
                 raise ValueError("simulate needs annotations= (the counts per name) or a replicate in simulate_write")
-            active.append(_SimulationReducer(simulate, simulate_seed, simulate_write, active[-1] if self.annotations else None,
-                                             simulate_table_bytes_max, self.out_prefix, simulate_labels, self.rank, self.world))
+            if self.annotations or tuple(simulate_write):      # (otherwise the draws are the consequence simulation's alone)
+                active.append(_SimulationReducer(simulate, simulate_seed, simulate_write, active[-1] if self.annotations else None,
+                                                 simulate_table_bytes_max, self.out_prefix, simulate_labels, self.rank, self.world))
         elif simulate_seed is not None or tuple(simulate_write):
             raise ValueError("simulate_seed and simulate_write go with simulate=R")
         self.transcripts = transcripts is not None
         if self.transcripts:
             active.append(_ConsequenceReducer(transcripts, genome, codon_table, alt_order, transcript_labels))
+            if simulate_transcripts and self.simulate:      # behind the consequence reducer: it uploads the segment arrays
+                active.append(_ConsequenceSimulationReducer(simulate, simulate_seed, active[-1], simulate_table_bytes_max))
         elif codon_table is not None or alt_order is not None:
             raise ValueError("codon_table and alt_order go with transcripts=")
+        if simulate_transcripts and not self.transcripts:
+            raise ValueError("simulate_transcripts goes with transcripts= (and simulate=R)")
+        if simulate_transcripts and not self.simulate:
+            raise ValueError("simulate_transcripts goes with simulate=R and simulate_seed")
         self._reducers = {r.name: r for r in active}
         self.rows = 0
         self._n_class = None
@@ -1940,6 +2111,12 @@ class SummarySink:
         (``simulate_annot_host``'s layout, the names in ``read_annotations``' order)."""
         self.result()
         return self._reducers["simulation"].counts
+
+    def consequence_simulation_counts(self):
+        """table uint32 [transcripts][5][simulate] after close(): the simulated count of every transcript, consequence bin (0 syn, 1
+        mis, 2 stop gained, 3 stop lost, 4 unresolved) and replicate (``simulate_conseq_host``'s layout, the transcripts in file order)."""
+        self.result()
+        return self._reducers["consequence_simulation"].counts
 
     def calibration_sums(self):
         """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind

@@ -1055,6 +1055,95 @@ def run_simulate_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
     return write_simulation_outputs(names, counts, observed, expected, args.n_class, args.out_prefix)
 
 
+def consequence_simulation_output_name(out_prefix):
+    return f"{out_prefix}.consequence.sim.tsv"
+
+
+def write_consequence_simulation_outputs(names, counts, observed, expected, out_prefix):
+    """``{out_prefix}.consequence.sim.tsv``: one line per transcript and consequence of ``CONSEQUENCES`` -- name, consequence, observed,
+    expected, sim_mean, sim_min, sim_max, n_ge, n_le, p_upper, p_lower (``summaries.simulate_pvalues``) -- from counts
+    [transcripts][5][R] (bin 4, unresolved, stays in the counts and gets no line), observed [transcripts][4] (None: no labels, 'NA' in
+    the observed column and the last four) and expected [transcripts][4]: the consequence table's own columns.  Returns the path."""
+    from .summaries import simulate_pvalues      # (summaries imports this module: not at the top)
+    header = ["name", "consequence", "observed", "expected", "sim_mean", "sim_min", "sim_max", "n_ge", "n_le", "p_upper", "p_lower"]
+    counts = np.asarray(counts).reshape(len(names), 5, -1)
+    stats = [simulate_pvalues(counts[:, b], None if observed is None else np.asarray(observed)[:, b]) for b in range(len(CONSEQUENCES))]
+    rows = []
+    for j, nm in enumerate(names):
+        for b, what in enumerate(CONSEQUENCES):
+            mean, lo, hi, n_ge, n_le, p_up, p_lo = stats[b][j]
+            obs = "NA" if observed is None else str(int(observed[j][b]))
+            tail = ["NA"] * 4 if observed is None else [str(n_ge), str(n_le), _float_text(p_up), _float_text(p_lo)]
+            rows.append([nm, what, obs, _float_text(expected[j][b]), _float_text(mean), str(lo), str(hi)] + tail)
+    path = consequence_simulation_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    return path
+
+
+def simulate_consequence_table(pred_file, transcripts, ref_genome, n_rep, seed, codon_table=None, alt_order=None, labels=True,
+                               chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, counts uint32 [transcripts][5][n_rep], observed or None, expected) from a written SNV prediction table (4 classes): what
+    ``SummarySink(simulate=n_rep, simulate_seed=seed, transcripts=..., simulate_transcripts=True)`` reduces in flight, through the same
+    entries (``mural_simulate_conseq_rows`` beside ``mural_summary_conseq_rows``), chromosome run by chromosome run of each chunk; the
+    draws are made from the table's four-digit probabilities.  observed and expected [transcripts][4] are the consequence table's
+    columns (``consequence_table``); `labels=False`: observed is None."""
+    from .data.ingest import read_fasta, scan_fasta
+    from .summaries import (_SUMMARY_STATUS, SIMULATE_MAX_REPLICATES, conseq_rows_device,      # (summaries imports this module)
+                            simulate_conseq_rows_device)
+    n_rep, seed = int(n_rep), int(seed)
+    if not 1 <= n_rep <= SIMULATE_MAX_REPLICATES or not 0 <= seed < 1 << 64:
+        raise ValueError("simulate_consequence_table: 1 .. 2^20 replicates and an unsigned 64-bit seed")
+    names, meta, segments = read_transcripts(transcripts, codon_table)
+    alt = check_alt_order(alt_order)
+    n_tx = len(names)
+    fasta_names = {r.name for r in scan_fasta(ref_genome)}
+    with TableReader(pred_file, 4, chunk_bytes) as rd:
+        dev = rd.device
+        acc = dict(table=torch.zeros(max(n_tx, 1) * 15, dtype=torch.int64, device=dev), rows=torch.zeros(max(n_tx, 1) * 2, dtype=torch.int64, device=dev),
+                   status=torch.zeros(1, dtype=torch.int32, device=dev), segments={}, ws=None)
+        sim = torch.zeros(max(n_tx * 5 * n_rep, 1), dtype=torch.int32, device=dev)
+        genomes = {}
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in segments or b == a:
+                    continue
+                if name not in genomes:
+                    if name not in fasta_names:
+                        raise ValueError(f"Chromosome {name} not found in {ref_genome} (prediction table line {c.row0 + a + 2})")
+                    genomes[name] = read_fasta(ref_genome, dev, names={name})[name]
+                part = dict(prob=c.prob + 8 * 4 * a, prob_f64=1, prob_stride=4, start=c.start + 8 * a, strand=c.strand + a, n=b - a)
+                conseq_rows_device(acc, name, segments[name], n_tx, meta["aa"], alt, genomes[name].as_struct(), dev,
+                                   label=c.mut_type + 4 * a, label_kind=1, **part)
+                simulate_conseq_rows_device(sim, acc["status"], acc, name, n_tx, meta["aa"], alt, genomes[name].as_struct(), dev, n_rep, seed,
+                                            **part)
+        bits = int(acc["status"].item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table = acc["table"].cpu().numpy().view(np.uint64)[:n_tx * 15].reshape(n_tx, 5, 3)
+        counts = acc["rows"].cpu().numpy().view(np.uint64)[:n_tx * 2].reshape(n_tx, 2)
+        sim = sim.cpu().numpy().view(np.uint32)[:n_tx * 5 * n_rep].reshape(n_tx, 5, n_rep)
+    conseq = consequence_table_from_sums(table, counts)
+    return names, sim, (conseq[:, 4:11:2] if labels else None), conseq[:, 3:11:2]
+
+
+def run_simulate_consequence_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.transcripts, args.ref_genome, args.simulate, args.seed, args.out_prefix;
+    optional args.codon_table, args.alt_order): the simulated counts per transcript and consequence from the table's rows; writes
+    {out_prefix}.consequence.sim.tsv."""
+    assert getattr(args, "transcripts", None) is not None, "--transcripts is required for the consequence simulation"
+    assert getattr(args, "ref_genome", None) is not None, "--ref_genome is required for the consequence simulation"
+    assert getattr(args, "seed", None) is not None, "--seed is required with --simulate: there is no default randomness"
+    names, counts, observed, expected = simulate_consequence_table(os.fspath(args.pred_file), args.transcripts, os.fspath(args.ref_genome),
+                                                                   args.simulate, args.seed, getattr(args, "codon_table", None),
+                                                                   getattr(args, "alt_order", None), True, chunk_bytes)
+    return write_consequence_simulation_outputs(names, counts, observed, expected, args.out_prefix)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # evaluate: regional
 # ------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Sixteen legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Eighteen legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -28,6 +28,9 @@ alternating, --repeats timed runs each after one warm-up run each:
                   leg k's 200 000 pieces regrouped into 20 000 ten-exon transcripts on alternating strands; the comparisons are leg b, the
                   same run without it, and leg k
   p  conseq_tools the route to o's table without the sink: leg a's table, then tables.consequence_table on it (the FASTA packed again)
+  q  conseq_sim100  leg o with simulate=100, simulate_seed=1, simulate_transcripts=True as well: the counts of 100
+                  mutation sets per transcript and consequence; the comparison is leg o, the same run without it
+  r  conseq_sim1000 leg o with simulate=1000 (a table of 400 MB, below the sink's cap)
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
 h's, leg k's annotation table with leg l's and leg o's consequence table with leg p's, within the table's four digits (names, order and
 counts exactly)."""
@@ -53,8 +56,9 @@ WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
 LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000",
-        "conseq", "conseq_tools")
+        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000")
 SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
+CONSEQ_SIM_REPLICATES = {"conseq_sim100": 100, "conseq_sim1000": 1000}
 ANNOT_NAMES, ANNOT_INTERVALS, ANNOT_BP, ANNOT_OVERLAP = 20_000, 10, 150, 0.05
 
 
@@ -107,7 +111,7 @@ def main(argv):
         kept, closes = {}, {}
         annot = synthetic_annotations(bases) if {"annot", "annot_tools", "sim100", "sim1000"} & set(legs) else None
 
-        transcripts = synthetic_transcripts(bases) if {"conseq", "conseq_tools"} & set(legs) else None
+        transcripts = synthetic_transcripts(bases) if {"conseq", "conseq_tools", *CONSEQ_SIM_REPLICATES} & set(legs) else None
 
         def run(leg):
             split, extra = {}, {}
@@ -127,7 +131,10 @@ def main(argv):
                 summary = SummarySink(windows=WINDOWS, annotations=annot, simulate=SIM_REPLICATES[leg], simulate_seed=1, simulate_labels=False)
             if leg == "conseq":
                 summary = SummarySink(windows=WINDOWS, transcripts=transcripts, genome=fwd.genome, transcript_labels=False)
-            if leg in ("summary", "annot", "sim100", "sim1000", "conseq") and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
+            if leg in CONSEQ_SIM_REPLICATES:
+                summary = SummarySink(windows=WINDOWS, transcripts=transcripts, genome=fwd.genome, transcript_labels=False,
+                                      simulate=CONSEQ_SIM_REPLICATES[leg], simulate_seed=1, simulate_transcripts=True)
+            if leg in ("summary", "annot", "sim100", "sim1000", "conseq", *CONSEQ_SIM_REPLICATES) and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
                 plain_close = summary.close
 
                 def close_timed():
@@ -153,7 +160,8 @@ def main(argv):
             sink = {"calib": lambda: summary, "calib_fit": lambda: summary, "table": lambda: TsvSink(out), "tools": lambda: TsvSink(out), "summary": lambda: summary, "kmers": lambda: summary,
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
                     "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out), "sim100": lambda: summary,
-                    "sim1000": lambda: summary, "conseq": lambda: summary, "conseq_tools": lambda: TsvSink(out)}[leg]()
+                    "sim1000": lambda: summary, "conseq": lambda: summary, "conseq_tools": lambda: TsvSink(out),
+                    "conseq_sim100": lambda: summary, "conseq_sim1000": lambda: summary}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
                                         **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
@@ -248,6 +256,8 @@ def main(argv):
            "consequences": {"transcripts": ANNOT_NAMES, "exons": ANNOT_INTERVALS, "bp": ANNOT_BP,
                             "rows_in_a_cds": float(kept["conseq"]["consequences"][2][:, 0].sum()) if "conseq" in kept else None,
                             "expected": kept["conseq"]["consequences"][2][:, 3:11:2].sum(axis=0).tolist() if "conseq" in kept else None},
+           "conseq_sim100_over_conseq": ratio("conseq_sim100", "conseq", med), "conseq_sim1000_over_conseq": ratio("conseq_sim1000", "conseq", med),
+           "simulated_consequence_draws": {leg: float(kept[leg]["consequence_simulation"][1].sum()) for leg in CONSEQ_SIM_REPLICATES if leg in kept},
            "simulated_draws": {leg: float(kept[leg]["simulation"][1].sum()) for leg in SIM_REPLICATES if leg in kept},
            "annotations": {"names": ANNOT_NAMES, "intervals": ANNOT_INTERVALS, "bp": ANNOT_BP,
                            "close_seconds": {leg: v[1:] for leg, v in closes.items()},      # (without the warm-up round's)

@@ -57,6 +57,13 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              standard code); SPEC: the alternative base of mut_type 1, 2, 3 per own base
                                                              A, C, G, T (default CGT,AGT,ACT,ACG); observed is NA where the rows carry
                                                              no labels; not with --indel; alone or with the options above
+  --summary PREFIX  --transcripts BED12 --simulate R --seed S --simulate_consequences
+                                                             PREFIX.consequence.sim.tsv: per transcript and consequence the observed and
+                                                             expected counts of the consequence table beside the mean, minimum and
+                                                             maximum of the R simulated counts -- the rows inside the CDS whose draw is a
+                                                             class whose substitution has that consequence --, n_ge / n_le and the
+                                                             empirical p-values (n + 1) / (R + 1); --simulate then needs neither
+                                                             --annotations nor --write_simulated
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -162,7 +169,12 @@ def _summary_options(flags, values, model_type="snv"):
             "n_bins": one("--n_bins", int), "fit_calibrator": one("--fit_calibrator", str), "annotations": one("--annotations", str),
             "simulate": one("--simulate", int), "seed": one("--seed", lambda v: int(v, 0)),
             "write_simulated": tuple(int(r) for r in values.get("--write_simulated", [])), "transcripts": one("--transcripts", str),
-            "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str)}
+            "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str),
+            "simulate_consequences": "--simulate_consequences" in flags}
+    if opts["simulate_consequences"] and opts["transcripts"] is None:
+        raise SystemExit("--simulate_consequences needs --transcripts BED12: the transcripts whose consequence counts it simulates")
+    if opts["simulate_consequences"] and opts["simulate"] is None:
+        raise SystemExit("--simulate_consequences needs --simulate R --seed S: the replicates it counts")
     if opts["simulate"] is not None and opts["seed"] is None:
         raise SystemExit("--simulate needs --seed S: there is no default randomness")
     if opts["simulate"] is None and (opts["seed"] is not None or opts["write_simulated"]):
@@ -170,7 +182,7 @@ def _summary_options(flags, values, model_type="snv"):
     if opts["simulate"] is not None:
         if opts["summary"] is None:
             raise SystemExit("--simulate needs --summary PREFIX: the prefix of the files it writes")
-        if opts["annotations"] is None and not opts["write_simulated"]:
+        if opts["annotations"] is None and not opts["write_simulated"] and not opts["simulate_consequences"]:
             raise SystemExit("--simulate needs --annotations BED (the counts per name) or --write_simulated r")
         if not 1 <= opts["simulate"] <= 1 << 20 or not 0 <= opts["seed"] < 1 << 64:
             raise SystemExit("--simulate takes 1 .. 2^20 replicates and an unsigned 64-bit --seed")
@@ -277,7 +289,7 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               calibration_bins=50 if opts["n_bins"] is None else opts["n_bins"], fit_calibrator=opts["fit_calibrator"],
                               annotations=opts["annotations"], simulate=opts["simulate"], simulate_seed=opts["seed"],
                               simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), transcripts=opts["transcripts"], alt_order=opts["alt_order"],
-                              transcript_labels=opts.get("labelled", True), **sink_chain)
+                              transcript_labels=opts.get("labelled", True), simulate_transcripts=opts["simulate_consequences"], **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
