@@ -922,6 +922,73 @@ size_t mural_summary_conseq_workspace_bytes(int64_t n_segments);
 int mural_summary_conseq_rows(const MuralSummaryConseqRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Expected and observed mutations per transcript by where a row lies in the transcript's structure
+ * (SummarySink(transcripts=..., transcript_structure=True) in flight, tables.structure_table from a written table;
+ * csrc/summary_txstruct.hip; mural_amd.summaries.summary_txstruct_host is the specification).  The rows, the genome, the
+ * segments, the transcripts, aa, alt_order, the status bits and the limbs are those of mural_summary_conseq_rows.  The
+ * chromosome's ITEMS are those of tables.read_transcript_structure: item f is [feat_b0[f], feat_b1[f]) of transcript
+ * feat_tx[f]; a transcript's items tile its span without overlap.  feat_kind[f] is 0 a 5'UTR exon part, 1 a 3'UTR exon part, 2
+ * an exon of a transcript without CDS, 3 a coding intron (a CDS base on both sides), 4 any other gap, 5 a CDS part, which is
+ * CDS segment feat_seg[f] (-1 for the other kinds).  For row i at q = start[i] and every item with feat_b0 <= q < feat_b1, its
+ * classes c = 1 .. 3 go to one of 9 bins:
+ *   kinds 0, 1, 2: bin 0 (utr5), 1 (utr3), 2 (noncoding_exon);
+ *   kinds 3, 4: an item shorter than 4 bases has no splice sites (bin 6, intron); otherwise its 5' two bases in transcript
+ *     orientation are the donor, the other end's two the acceptor: bin 3 (splice_donor) / 4 (splice_acceptor) in a coding
+ *     intron, bin 5 (splice_utr) in any other, and bin 6 for the bases between;
+ *   kind 5: x = the CDS offset of q, the codon and the amino acids as mural_summary_conseq_rows; class c goes to bin 7
+ *     (start_lost) where x < 3, the codon resolves and aa_alt != aa_ref, to bin 8 (cds) otherwise.  BED12 carries no
+ *     frame and ATG is not demanded: start lost is "changes the amino acid of CDS codon 0".
+ *   table [n_transcripts][9][3] += { 1 where label[i] == c, hi of prob[i][c], lo of prob[i][c] }; on return lo < 2^40;
+ *   rows [n_transcripts][2] += { rows inside the span, rows of label 0 among them }; a row counts once per transcript whose
+ *   span covers it.  Bins 7 + 8 of a transcript add up to the five bins of mural_summary_conseq_rows.
+ * A CDS item whose feat_seg is outside 0 .. n_segments - 1 or names another segment, an item of an unknown kind and an item
+ * whose transcript is outside 0 .. n_transcripts - 1 are skipped.  Chunks of at most mural_summary_txstruct_chunk_rows()
+ * rows, a scan workgroup of mural_summary_txstruct_scan_threads() threads, a grid of at most
+ * mural_summary_txstruct_grid_waves() waves.  n <= 2^31 and n_features <= 2^22 per call (MURAL_E_INVALID above: a
+ * transcript's items are disjoint, so a cell takes at most n / chunk_rows + n_features folded terms in a call, which keeps its
+ * lo limb below 2^63 until the fold that ends the call).  ws: mural_summary_txstruct_workspace_bytes(n_features) bytes (24
+ * per item), 8-byte aligned; MURAL_E_WORKSPACE when smaller.  n == 0 or n_features == 0 launches nothing; n_segments == 0
+ * is legal (no CDS on the chromosome).  Launches on `stream`, no synchronisation, no read-back, no floating-point atomics.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const MuralGenome* genome; /* the chromosome of the rows */
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. 3 are read                  */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const uint8_t* strand;     /* dev [n], 1 = '-', or NULL */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_transcripts;                   /* n_class == 4 */
+  const int64_t* seg_b0;     /* dev [n_segments] */
+  const int64_t* seg_b1;     /* dev [n_segments] */
+  const int64_t* seg_cds0;   /* dev [n_segments] */
+  const int32_t* seg_tx;     /* dev [n_segments] */
+  const int32_t* seg_prev;   /* dev [n_segments] */
+  const int32_t* seg_next;   /* dev [n_segments] */
+  int64_t n_segments;
+  const uint8_t* tx_strand;  /* dev [n_transcripts] */
+  const int64_t* tx_cds_len; /* dev [n_transcripts] */
+  uint8_t aa[64];
+  uint8_t alt_order[4][3];
+  uint8_t reserved[4];
+  uint64_t* table;           /* dev [n_transcripts][9][3] */
+  uint64_t* rows;            /* dev [n_transcripts][2] */
+  int32_t* status;           /* dev [1] */
+  const int64_t* feat_b0;    /* dev [n_features] */
+  const int64_t* feat_b1;    /* dev [n_features] */
+  const int32_t* feat_tx;    /* dev [n_features] */
+  const uint8_t* feat_kind;  /* dev [n_features] */
+  const int32_t* feat_seg;   /* dev [n_features] */
+  int64_t n_features;
+} MuralSummaryTxstructRows;
+int64_t mural_summary_txstruct_chunk_rows(void);
+int64_t mural_summary_txstruct_grid_waves(void);
+int32_t mural_summary_txstruct_scan_threads(void);
+size_t mural_summary_txstruct_workspace_bytes(int64_t n_features);
+int mural_summary_txstruct_rows(const MuralSummaryTxstructRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Mutation sets drawn from the rates of a shard while it is on the device (SummarySink(simulate=R, ...) in flight,
  * tables.simulate_table from a written table; csrc/simulate.hip).  The draw is stateless and integer
  * (mural_amd.summaries.simulate_rows_host is its specification): Philox4x32-10 with key (seed lo, seed hi) and counter

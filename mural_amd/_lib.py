@@ -138,6 +138,11 @@ class MuralSummaryConseqRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSummaryTxstructRows(C.Structure):
+    _fields_ = MuralSummaryConseqRows._fields_ + [("feat_b0", C.c_void_p), ("feat_b1", C.c_void_p), ("feat_tx", C.c_void_p),
+                                                  ("feat_kind", C.c_void_p), ("feat_seg", C.c_void_p), ("n_features", C.c_int64)]
+
+
 class MuralSimulateAnnotRows(C.Structure):
     _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
                 ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("n_rep", C.c_int32), ("seed", C.c_uint64),
@@ -323,6 +328,11 @@ PROTOTYPES = {
     "mural_summary_conseq_scan_threads": (I32, []),
     "mural_summary_conseq_workspace_bytes": (C.c_size_t, [I64]),
     "mural_summary_conseq_rows": (C.c_int, [C.POINTER(MuralSummaryConseqRows), VP, C.c_size_t, VP]),
+    "mural_summary_txstruct_chunk_rows": (I64, []),
+    "mural_summary_txstruct_grid_waves": (I64, []),
+    "mural_summary_txstruct_scan_threads": (I32, []),
+    "mural_summary_txstruct_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_summary_txstruct_rows": (C.c_int, [C.POINTER(MuralSummaryTxstructRows), VP, C.c_size_t, VP]),
     "mural_simulate_chunk_rows": (I64, []),
     "mural_simulate_grid_waves": (I64, []),
     "mural_simulate_scan_threads": (I32, []),

@@ -16,7 +16,8 @@ from .evaluation import _FIT_MAX_CLASSES, CALIBRATORS, newton_calibrator
 from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds, shard_name, strand_u8
 from .tables import (annotation_meta, annotation_output_names, check_alt_order, consequence_output_name,
                      consequence_simulation_output_name, consequence_table_from_sums, write_consequence_simulation_outputs,
-                     read_transcripts, write_consequence_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
+                     read_transcripts, read_transcript_structure, structure_output_name, write_consequence_outputs,
+                     write_structure_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
                      write_simulation_outputs, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
                      strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs)
@@ -376,29 +377,37 @@ def _conseq_row_checks(prob, start, label):
     return hi, lo, lab, ~(bad_label | bad_start | bad_prob), status
 
 
-def _conseq_pairs(genome, start, rs, segments, aa, alt_of):
-    """The one bin rule of the consequence tables on the host, shared by ``summary_conseq_host`` and ``simulate_conseq_host``: for rows
-    sorted by start (`rs`: their strands as int64 0 / 1) and a chromosome's `segments`, yields (i, tx, bins) per pass of at most
-    ``_CONSEQ_PAIRS`` (segment, row) pairs with seg_b0 <= start[i] < seg_b1 -- the row index, the segment's transcript and bins int64
-    [pairs][3], the bin 0 .. 4 of classes 1 .. 3 by the rule ``summary_conseq_host`` states."""
-    b0, b1, cds0 = (np.asarray(segments[key], np.int64) for key in ("seg_b0", "seg_b1", "seg_cds0"))
-    seg_tx, prev, nxt = (np.asarray(segments[key], np.int64) for key in ("seg_tx", "seg_prev", "seg_next"))
-    tx_minus, tx_len = np.asarray(segments["tx_strand"]) != 0, np.asarray(segments["tx_cds_len"], np.int64)
-    packed, nmask, L = _host_genome(genome)
+def _item_row_pairs(start, b0, b1):
+    """(item, row) index arrays of every pair with b0[item] <= start[row] < b1[item], `start` ascending: passes of at most
+    ``_CONSEQ_PAIRS`` pairs, item by item."""
     i0 = np.searchsorted(start, b0, "left")
     i1 = np.maximum(np.searchsorted(start, b1, "left"), i0)
     n_in = i1 - i0
     ends = np.cumsum(n_in)
-    for p0 in range(0, int(ends[-1]), _CONSEQ_PAIRS):
-        pair = np.arange(p0, min(p0 + _CONSEQ_PAIRS, int(ends[-1])), dtype=np.int64)
-        s = np.searchsorted(ends, pair, "right")                       # the pair's segment
-        i = i0[s] + (pair - (ends[s] - n_in[s]))                       # and its row
+    total = int(ends[-1]) if len(ends) else 0
+    for p0 in range(0, total, _CONSEQ_PAIRS):
+        pair = np.arange(p0, min(p0 + _CONSEQ_PAIRS, total), dtype=np.int64)
+        s = np.searchsorted(ends, pair, "right")                       # the pair's item
+        yield s, i0[s] + (pair - (ends[s] - n_in[s]))                  # and its row
+
+
+def _conseq_pairs(genome, start, rs, segments, aa, alt_of, with_offset=False):
+    """The one bin rule of the consequence tables on the host, shared by ``summary_conseq_host`` and ``simulate_conseq_host``: for rows
+    sorted by start (`rs`: their strands as int64 0 / 1) and a chromosome's `segments`, yields (i, tx, bins) per pass of at most
+    ``_CONSEQ_PAIRS`` (segment, row) pairs with seg_b0 <= start[i] < seg_b1 -- the row index, the segment's transcript and bins int64
+    [pairs][3], the bin 0 .. 4 of classes 1 .. 3 by the rule ``summary_conseq_host`` states.  `with_offset`: (i, tx, bins, x), x the CDS
+    offset of each pair's row (``summary_txstruct_host`` asks whether it lies in codon 0)."""
+    b0, b1, cds0 = (np.asarray(segments[key], np.int64) for key in ("seg_b0", "seg_b1", "seg_cds0"))
+    seg_tx, prev, nxt = (np.asarray(segments[key], np.int64) for key in ("seg_tx", "seg_prev", "seg_next"))
+    tx_minus, tx_len = np.asarray(segments["tx_strand"]) != 0, np.asarray(segments["tx_cds_len"], np.int64)
+    packed, nmask, L = _host_genome(genome)
+    for s, i in _item_row_pairs(start, b0, b1):
         q, tx = start[i], seg_tx[s]
         minus = tx_minus[tx]
         x = cds0[s] + np.where(minus, b1[s] - 1 - q, q - b0[s])
         cs = x - x % 3
         found = cs + 2 < tx_len[tx]
-        codon = np.zeros(len(pair), np.int64)
+        codon = np.zeros(len(s), np.int64)
         for j in range(3):
             o, cur = cs + j, s.copy()
             for _ in range(2):
@@ -415,21 +424,21 @@ def _conseq_pairs(genome, start, rs, segments, aa, alt_of):
                 found &= ((nmask[at >> 5] >> (at & 31).astype(np.uint32)) & 1) == 0
                 code = ((packed[at >> 4] >> (2 * (at & 15)).astype(np.uint32)) & 3).astype(np.int64)
             else:
-                code = np.zeros(len(pair), np.int64)
+                code = np.zeros(len(s), np.int64)
             codon = codon * 4 + np.where(minus, 3 - code, code)
         codon = np.where(found, codon, 0)
         sh = 2 * (2 - (x - cs))
         own_tx = (codon >> sh) & 3
         flip = minus != (rs[i] != 0)
         r = np.where(flip, 3 - own_tx, own_tx)
-        bins = np.empty((len(pair), 3), np.int64)
+        bins = np.empty((len(s), 3), np.int64)
         for c in range(3):
             alt = alt_of[r, c]
             alt_tx = np.where(flip, 3 - alt, alt)
             a_ref, a_alt = aa[codon], aa[(codon & ~(3 << sh)) | (alt_tx << sh)]
             b = np.where(a_ref == a_alt, 0, np.where(a_alt == _CONSEQ_STOP, 2, np.where(a_ref == _CONSEQ_STOP, 3, 1)))
             bins[:, c] = np.where(found, b, 4)
-        yield i, tx, bins
+        yield (i, tx, bins, x) if with_offset else (i, tx, bins)
 
 
 def summary_conseq_host(genome, prob, start, strand, label, segments, n_transcripts, aa=None, alt_order=None, into=None, n_class=4):
@@ -485,20 +494,29 @@ def _conseq_fold(table):
     return table
 
 
+def _conseq_segments_device(acc, name, segments, dev):
+    """The device arrays of chromosome `name`'s segments in acc["segments"], and the transcripts' strands and CDS lengths in acc["tx"]
+    (`segments` may be a chromosome's dict of features: it has the same two): uploaded the first time, from pinned memory."""
+    if "tx" not in acc:
+        pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in ("tx_strand", "tx_cds_len"))
+        acc["tx"] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    if "seg_b0" not in segments:
+        return None
+    on_dev = acc["segments"].get(name)
+    if on_dev is None:
+        keys = ("seg_b0", "seg_b1", "seg_cds0", "seg_tx", "seg_prev", "seg_next")
+        pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in keys)
+        on_dev = acc["segments"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    return on_dev
+
+
 def conseq_rows_device(acc, name, segments, n_transcripts, aa, alt_order, genome_struct, dev, *, prob, prob_f64, prob_stride, start,
                        strand, label, label_kind, n):
     """One ``mural_summary_conseq_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 15],
     rows int64 [n_transcripts * 2], status int32 [1], segments {chromosome: device arrays}, ws): the chromosome's segment arrays are
     uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --, the workspace grows as needed."""
     lib = _lib.lib()
-    on_dev = acc["segments"].get(name)
-    if on_dev is None:
-        keys = ("seg_b0", "seg_b1", "seg_cds0", "seg_tx", "seg_prev", "seg_next")
-        if "tx" not in acc:
-            pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in ("tx_strand", "tx_cds_len"))
-            acc["tx"] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
-        pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in keys)
-        on_dev = acc["segments"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    on_dev = _conseq_segments_device(acc, name, segments, dev)
     n_seg = int(on_dev[0].shape[0])
     need = int(lib.mural_summary_conseq_workspace_bytes(n_seg))
     if acc["ws"] is None or acc["ws"].numel() * 8 < need:
@@ -515,6 +533,112 @@ def conseq_rows_device(acc, name, segments, n_transcripts, aa, alt_order, genome
     C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
     s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
     _lib.check(lib.mural_summary_conseq_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+
+
+# ---- structure tables (csrc/summary_txstruct.hip: mural_summary_txstruct_rows): the same cells per transcript and place in its structure ---
+TX_BINS = 9
+
+
+def summary_txstruct_host(genome, prob, start, strand, label, segments, features, n_transcripts, aa=None, alt_order=None, into=None,
+                          n_class=4):
+    """The numpy twin of ``mural_summary_txstruct_rows`` -- and its specification -- for SNV rows (any order) of one chromosome: (table
+    uint64 [n_transcripts][9][3], rows uint64 [n_transcripts][2], status).  `segments`, `features`: the chromosome's dicts of
+    ``tables.read_transcript_structure`` (or None); the other arguments, the row checks and the status bits are
+    ``summary_conseq_host``'s.  The bins (``tables.STRUCTURE_BINS``): 0 utr5, 1 utr3, 2 noncoding_exon, 3 splice_donor, 4
+    splice_acceptor, 5 splice_utr, 6 intron, 7 start_lost, 8 cds.
+
+    For row i at q = start[i] and every item [a, b) = [feat_b0, feat_b1) with a <= q < b, by the item's kind:
+      0, 1, 2 (5'UTR part, 3'UTR part, exon of a transcript without CDS): all three classes go to bin 0, 1 or 2;
+      3, 4 (coding intron, other gap): with b - a < 4 there are no splice sites and all classes go to bin 6; otherwise the 5' two bases
+        in transcript orientation are the donor ([a, a + 2) on '+', [b - 2, b) on '-') and the other end's two the acceptor: a donor or
+        acceptor row goes to bin 3 or 4 in a coding intron and to bin 5 in any other gap, every other row to bin 6;
+      5 (CDS part): x and the codon are ``summary_conseq_host``'s (``_conseq_pairs``); class c goes to bin 7 iff x < 3, the codon
+        resolves and aa_alt != aa_ref, and to bin 8 otherwise -- an unresolved first codon and cds_length < 3 included.  BED12 carries no
+        frame and the rule does not demand ATG: `start lost` is "changes the amino acid of CDS codon 0".
+    Cell [t][b] += {label == c, hi(p_c), lo(p_c)} per class c that lands in bin b of transcript t; rows[t] += {1, label == 0} per row
+    inside t's span -- a transcript's items tile its span, so a row counts once per transcript that covers it.  Integer sums: both
+    tables are a function of the SET of rows, bit for bit; on return lo < 2^40; class 0's probability is never read.  For every t the
+    cells [t][7] + [t][8] add up to the five cells of ``summary_conseq_host``'s table[t], the observed word by word and the
+    probability as the integer hi 2^40 + lo.  `into`: (table, rows) of earlier parts and chromosomes to add to, in place."""
+    from .tables import check_alt_order, check_codon_table
+    if int(n_class) != 4:
+        raise ValueError("the structure table takes SNV rows of 4 classes (INDEL tables are out of scope)")
+    n_tx = int(n_transcripts)
+    aa = check_codon_table(aa).astype(np.int64)
+    alt_of = check_alt_order(alt_order).astype(np.int64)
+    start = np.asarray(start, np.int64)
+    hi, lo, lab, ok, status = _conseq_row_checks(prob, start, label)
+    table, rows = (np.zeros((n_tx, TX_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if into is None else into
+    if features is None or len(features["feat_b0"]) == 0 or not ok.any():
+        return table, rows, status
+    rs = np.zeros(len(start), np.int64) if strand is None else strand_u8(strand).astype(np.int64)
+    order = np.argsort(start[ok], kind="stable")
+    hi, lo, start, lab, rs = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order], rs[ok][order]
+    flat_table, flat_rows = table.reshape(-1), rows.reshape(-1)
+
+    def add(i, tx, bins):      # bins int64 [pairs][3]
+        cell = tx * (3 * TX_BINS)
+        for c in range(3):
+            b = bins[:, c]
+            np.add.at(flat_table, cell + 3 * b, (lab[i] == c + 1).astype(np.uint64))
+            np.add.at(flat_table, cell + 3 * b + 1, hi[i, c])
+            np.add.at(flat_table, cell + 3 * b + 2, lo[i, c])
+        np.add.at(flat_rows, 2 * tx, np.uint64(1))
+        np.add.at(flat_rows, 2 * tx + 1, (lab[i] == 0).astype(np.uint64))
+        _conseq_fold(table)
+
+    kind = np.asarray(features["feat_kind"], np.int64)
+    other = np.nonzero(kind != 5)[0]                       # the CDS parts are the segments: they go through _conseq_pairs below
+    a, b = np.asarray(features["feat_b0"], np.int64)[other], np.asarray(features["feat_b1"], np.int64)[other]
+    f_tx, kind = np.asarray(features["feat_tx"], np.int64)[other], kind[other]
+    tx_minus = np.asarray(features["tx_strand"]) != 0
+    for f, i in _item_row_pairs(start, a, b):
+        q, tx = start[i], f_tx[f]
+        sites = (kind[f] >= 3) & (b[f] - a[f] >= 4)
+        low, high = sites & (q < a[f] + 2), sites & (q >= b[f] - 2)
+        donor = np.where(tx_minus[tx], high, low)
+        site_bin = np.where(kind[f] == 3, np.where(donor, 3, 4), 5)
+        bins = np.where(kind[f] < 3, kind[f], np.where(low | high, site_bin, 6))
+        add(i, tx, np.repeat(bins[:, None], 3, axis=1))
+    if segments is not None and len(segments["seg_b0"]):
+        for i, tx, bins, x in _conseq_pairs(genome, start, rs, segments, aa, alt_of, with_offset=True):
+            add(i, tx, np.where((x < 3)[:, None] & (bins >= 1) & (bins <= 3), 7, 8))
+    return table, rows, status
+
+
+def txstruct_rows_device(acc, conseq_acc, name, segments, features, n_transcripts, aa, alt_order, genome_struct, dev, *, prob, prob_f64,
+                         prob_stride, start, strand, label, label_kind, n):
+    """One ``mural_summary_txstruct_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts *
+    27], rows int64 [n_transcripts * 2], status int32 [1], features {chromosome: device arrays}, ws): the chromosome's item arrays are
+    uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --, the workspace grows as needed.  The
+    segment arrays are those of `conseq_acc` (dict with "segments": {}), ``conseq_rows_device``'s accumulators, which uploaded them for
+    chromosome `name` just before -- or they are uploaded into it now; `segments` None: the chromosome has no CDS."""
+    lib = _lib.lib()
+    on_dev = acc["features"].get(name)
+    if on_dev is None:
+        keys = ("feat_b0", "feat_b1", "feat_tx", "feat_kind", "feat_seg")
+        pinned = tuple(torch.from_numpy(np.ascontiguousarray(features[key])).pin_memory() for key in keys)
+        on_dev = acc["features"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    seg_dev = _conseq_segments_device(conseq_acc, name, features if segments is None else segments, dev)
+    n_feat = int(on_dev[0].shape[0])
+    need = int(lib.mural_summary_txstruct_workspace_bytes(n_feat))
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _lib.MuralSummaryTxstructRows()
+    s.genome = C.pointer(genome_struct)
+    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
+    s.start, s.strand, s.label, s.label_kind = start, strand, label, int(label_kind)
+    s.n, s.n_class, s.n_transcripts = int(n), 4, int(n_transcripts)
+    if seg_dev is not None and seg_dev[0].shape[0]:
+        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in seg_dev[:6])
+        s.n_segments = int(seg_dev[0].shape[0])
+    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg = (x.data_ptr() for x in on_dev[:5])
+    s.n_features = n_feat
+    s.tx_strand, s.tx_cds_len = conseq_acc["tx"][0].data_ptr(), conseq_acc["tx"][1].data_ptr()
+    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
+    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+    s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
+    _lib.check(lib.mural_summary_txstruct_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
 
 
 # ---- mutation sets drawn from the rates (csrc/simulate.hip: mural_simulate_annot_rows, mural_simulate_rows) -----------------------------
@@ -1315,6 +1439,76 @@ class _ConsequenceReducer:
         write_consequence_outputs(*result[self.name], out_prefix, labels=self.labels)
 
 
+class _StructureReducer:
+    """Expected and observed mutations per transcript by where a row lies in the transcript's structure (``summary_txstruct_host`` is
+    the rule), behind the consequence reducer `conseq`, whose names, genome, codon table and device segment arrays it uses: ONE integer
+    table [transcripts][9][3] + row counters [transcripts][2] for the whole run on the host and one pair per device, a chromosome's item
+    arrays uploaded the first time the chromosome arrives on a device, read back once.  A chromosome without items reduces nothing."""
+    name = "transcript_structure"
+
+    def __init__(self, features, conseq):
+        self.features, self.conseq = features, conseq
+        self.reset()
+
+    def reset(self):
+        self.host = None               # (table, rows) of the host shards
+        self.dev = {}                  # device -> dict(table, rows, status, features {chromosome: device arrays}, ws)
+        self.sums = None
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        self.conseq._check(k)
+        features = self.features.get(name)
+        if features is None:
+            return 0
+        n_tx = len(self.conseq.names)
+        if self.host is None:
+            self.host = (np.zeros((n_tx, TX_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64))
+        return summary_txstruct_host(self.conseq.genome(name), prob, start, strand, label, self.conseq.segments.get(name), features, n_tx,
+                                     self.conseq.meta["aa"], self.conseq.alt_order, into=self.host)[2]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the reduction of a part behind its consequence reduction, into the device's one pair of tables."""
+        self.conseq._check(k)
+        features = self.features.get(name)
+        if features is None or start.shape[0] == 0:
+            return None
+        dev, n_tx = prob.device, len(self.conseq.names)
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(n_tx * 3 * TX_BINS, dtype=torch.int64, device=dev),
+                                       rows=torch.zeros(n_tx * 2, dtype=torch.int64, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev), features={}, ws=None, no_cds=dict(segments={}))
+        genome = self.conseq.genome(name)
+        # (the consequence reducer has no accumulators on a device that saw only chromosomes without CDS: the strands go to `no_cds`)
+        txstruct_rows_device(acc, self.conseq.dev.get(dev, acc["no_cds"]), name, self.conseq.segments.get(name), features, n_tx,
+                             self.conseq.meta["aa"], self.conseq.alt_order, genome.as_struct(dev), dev, prob=prob.data_ptr(),
+                             prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
+                             strand=strand.data_ptr(), label=label.data_ptr(), label_kind=_LABEL_KIND[label.dtype], n=start.shape[0])
+        return genome
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, mine, n_tx = 0, [self.host], len(self.conseq.names)
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine.append((acc["table"].cpu().numpy().view(np.uint64).reshape(n_tx, TX_BINS, 3),
+                         acc["rows"].cpu().numpy().view(np.uint64).reshape(n_tx, 2)))
+        return self.conseq._added(mine), status
+
+    def merge(self, states, k):
+        return self.conseq._added(states)
+
+    def finish(self, state, k, result):
+        n_tx = len(self.conseq.names)
+        self.sums = (np.zeros((n_tx, TX_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if state is None else state
+        result[self.name] = (list(self.conseq.names), *self.sums)
+
+    def write(self, out_prefix, result, k, written):
+        written.append(structure_output_name(out_prefix))
+        names, table, rows = result[self.name]
+        write_structure_outputs(names, self.conseq.meta, table, rows, self.conseq.sums[0][:, 2], out_prefix, labels=self.conseq.labels)
+
+
 class _SimulationReducer:
     """Mutation sets drawn from the rates (``simulate_rows_host`` is the rule): per name of the annotation reducer beside it the counts
     of every class in each of `n_rep` replicates -- ONE uint32 table [names][n_class - 1][n_rep] on the host and one per device, the
@@ -1898,6 +2092,15 @@ class SummarySink:
     result()["consequence_simulation"] = (names, counts, observed or None, expected), the last two [transcripts][4] from the
     consequence table; close() writes ``{out_prefix}.consequence.sim.tsv`` (``tables.write_consequence_simulation_outputs``);
     ``consequence_simulation_counts()`` has the table.
+    `transcript_structure=True` (with `transcripts`: a BED12 path or ``tables.read_transcript_structure``'s result -- a
+    ``read_transcripts`` triple holds no blocks any more; opt-in: without it nothing more is computed or written): a second table per
+    transcript over every SNV row inside [chromStart, chromEnd), split into 5'UTR, 3'UTR, non-coding exon, splice donor, splice
+    acceptor, splice site of a non-coding intron, intron, start lost and (other) CDS (``summary_txstruct_host`` is the rule; DESIGN.md
+    section 3.23).  Device parts go through ``mural_summary_txstruct_rows`` (csrc/summary_txstruct.hip) on the segment arrays the
+    consequence reduction uploaded and a chromosome's item arrays, uploaded once; one integer table pair per device, read back once
+    and added across ranks in the same collective.  result()["transcript_structure"] = (names, table uint64 [n][9][3], rows uint64
+    [n][2]); close() writes ``{out_prefix}.consequence.structure.tsv`` (``tables.write_structure_outputs``: the nine bins and
+    expected_lof / observed_lof = stop gained + splice donor + splice acceptor + start lost); ``structure_sums()`` has the integers.
 
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
@@ -1908,7 +2111,7 @@ class SummarySink:
                  group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
                  calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
                  simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True, transcripts=None,
-                 codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False):
+                 codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False, transcript_structure=False):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -1942,10 +2145,21 @@ class SummarySink:
         elif simulate_seed is not None or tuple(simulate_write):
             raise ValueError("simulate_seed and simulate_write go with simulate=R")
         self.transcripts = transcripts is not None
+        if transcript_structure and not self.transcripts:
+            raise ValueError("transcript_structure goes with transcripts= (a BED12 path or tables.read_transcript_structure's result)")
         if self.transcripts:
-            active.append(_ConsequenceReducer(transcripts, genome, codon_table, alt_order, transcript_labels))
+            features = None
+            if transcript_structure:
+                *transcripts, features = read_transcript_structure(transcripts, codon_table)
+                transcripts = tuple(transcripts)
+            elif isinstance(transcripts, tuple) and len(transcripts) == 4:
+                transcripts = transcripts[:3]
+            by_tx = _ConsequenceReducer(transcripts, genome, codon_table, alt_order, transcript_labels)
+            active.append(by_tx)
             if simulate_transcripts and self.simulate:      # behind the consequence reducer: it uploads the segment arrays
-                active.append(_ConsequenceSimulationReducer(simulate, simulate_seed, active[-1], simulate_table_bytes_max))
+                active.append(_ConsequenceSimulationReducer(simulate, simulate_seed, by_tx, simulate_table_bytes_max))
+            if features is not None:                        # behind it as well
+                active.append(_StructureReducer(features, by_tx))
         elif codon_table is not None or alt_order is not None:
             raise ValueError("codon_table and alt_order go with transcripts=")
         if simulate_transcripts and not self.transcripts:
@@ -2105,6 +2319,12 @@ class SummarySink:
         the exact sums behind result()["consequences"] (``summary_conseq_host``'s layout, the transcripts in file order)."""
         self.result()
         return self._reducers["consequences"].sums
+
+    def structure_sums(self):
+        """(table uint64 [transcripts][9][3] of label counts | sums of hi | sums of lo per bin of ``tables.STRUCTURE_BINS``, rows uint64
+        [transcripts][2]) after close(): ``summary_txstruct_host``'s layout, the transcripts in file order."""
+        self.result()
+        return self._reducers["transcript_structure"].sums
 
     def simulation_counts(self):
         """table uint32 [names][n_class - 1][simulate] after close(): the simulated count of every name, class >= 1 and replicate

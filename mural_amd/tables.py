@@ -762,8 +762,14 @@ def read_transcripts(source, codon_table=None):
         if codon_table is not None:
             source = (source[0], dict(source[1], aa=check_codon_table(codon_table)), source[2])
         return source
+    return _parse_transcripts(source, codon_table)[:3]
+
+
+def _parse_transcripts(source, codon_table=None):
+    """``read_transcripts``' result from a path or a handle, and a fourth item for ``read_transcript_structure``: per transcript
+    (chromStart, chromEnd, thickStart, thickEnd, [(block start, block end)])."""
     aa = check_codon_table(codon_table)
-    names, index, chroms, strands, cds_len, n_segs, per_chrom = [], set(), [], [], [], [], {}
+    names, index, chroms, strands, cds_len, n_segs, per_chrom, spans = [], set(), [], [], [], [], {}, []
     for line, where in _bed12_lines(source):
         if not line.strip() or line.startswith(("#", "track", "browser")):
             continue
@@ -787,7 +793,7 @@ def read_transcripts(source, codon_table=None):
             raise ValueError(f"{where}: blockCount {n_blocks} against {len(sizes)} blockSizes and {len(offs)} blockStarts")
         if not (thick0 == thick1 or (start <= thick0 < thick1 <= end)):
             raise ValueError(f"{where}: thickStart {thick0} / thickEnd {thick1} outside [{start}, {end})")
-        at, segs = start, []
+        at, segs, blocks = start, [], []
         for size, off in zip(sizes, offs):
             a, b = start + off, start + off + size
             if size <= 0 or a < start or b > end:
@@ -795,6 +801,7 @@ def read_transcripts(source, codon_table=None):
             if a < at:
                 raise ValueError(f"{where}: blocks overlap or do not ascend at [{a}, {b})")
             at = b
+            blocks.append((a, b))
             a, b = max(a, thick0), min(b, thick1)
             if a < b:
                 segs.append((a, b))
@@ -807,6 +814,7 @@ def read_transcripts(source, codon_table=None):
         strands.append(int(minus))
         cds_len.append(total)
         n_segs.append(len(segs))
+        spans.append((start, end, thick0, thick1, blocks))
         done = 0                          # CDS bases 5' of the segment, in transcript orientation
         for j, (a, b) in (reversed(list(enumerate(segs))) if minus else enumerate(segs)):
             per_chrom.setdefault(f[0], []).append((a, b, t, done, j))
@@ -827,7 +835,50 @@ def read_transcripts(source, codon_table=None):
         segments[chrom] = dict(seg_b0=arr[:, 0].copy(), seg_b1=arr[:, 1].copy(), seg_cds0=arr[:, 3].copy(), seg_tx=tx.astype(np.int32),
                                seg_prev=np.where(minus, upper, lower).astype(np.int32), seg_next=np.where(minus, lower, upper).astype(np.int32),
                                tx_strand=meta["strand"], tx_cds_len=meta["cds_length"])
-    return names, meta, segments
+    return names, meta, segments, spans
+
+
+def read_transcript_structure(source, codon_table=None):
+    """(names, meta, segments, features) of a BED12 transcript file: ``read_transcripts``' three (the same line parser and refusals) and
+    the transcripts' STRUCTURE for ``summary_txstruct_host`` / ``mural_summary_txstruct_rows``.  `source`: a path (plain or gzip), an
+    open handle, or this function's own result, returned as it is; a ``read_transcripts`` triple holds no blocks any more and is refused.
+      features[chrom]: dict of flat arrays sorted by (feat_b0, feat_b1, feat_tx): feat_b0, feat_b1 int64 (genomic, half-open), feat_tx
+        int32, feat_kind uint8, feat_seg int32 (kind 5: the index in segments[chrom] of the CDS segment that equals the item; else -1),
+        and tx_strand / tx_cds_len as `segments` has them.
+    A transcript's items TILE [chromStart, chromEnd) without overlap: its blocks, cut at thickStart / thickEnd, and the gaps between
+    them (an empty gap between abutting blocks is dropped; where the blocks do not reach an end of the span, the rest is a gap too).
+    Kinds: 0 a 5'UTR exon part, 1 a 3'UTR exon part -- in transcript orientation: on '-' the part at or above thickEnd is the 5'UTR --, 2
+    an exon of a transcript without CDS (thickStart == thickEnd), 3 a coding intron -- a gap [a, b) with thickStart < a and b <
+    thickEnd: a CDS base on both sides --, 4 any other gap, 5 a CDS part."""
+    if isinstance(source, tuple) and len(source) == 4 and isinstance(source[1], dict) and "aa" in source[1]:
+        return source
+    if isinstance(source, tuple):
+        raise ValueError("read_transcript_structure: a read_transcripts result holds no UTR exons and introns; pass the BED12 path")
+    names, meta, segments, spans = _parse_transcripts(source, codon_table)
+    per_chrom = {}
+    for t, (start, end, thick0, thick1, blocks) in enumerate(spans):
+        items, minus, at = per_chrom.setdefault(meta["chrom"][t], []), bool(meta["strand"][t]), start
+        for a, b in blocks + [(end, end)]:
+            if at < a:
+                items.append((at, a, t, 3 if thick0 < at and a < thick1 else 4))
+            at = b
+            if thick0 == thick1:
+                cuts = [(a, b, 2)]
+            else:
+                cuts = [(a, min(b, thick0), 1 if minus else 0), (max(a, thick0), min(b, thick1), 5), (max(a, thick1), b, 0 if minus else 1)]
+            items += [(lo, hi, t, kind) for lo, hi, kind in cuts if lo < hi]
+    features = {}
+    for chrom, items in per_chrom.items():
+        if not items:
+            continue
+        items.sort()
+        arr = np.asarray(items, np.int64).reshape(-1, 4)
+        seg = segments.get(chrom)
+        where = {} if seg is None else {key: j for j, key in enumerate(zip(seg["seg_b0"].tolist(), seg["seg_b1"].tolist(), seg["seg_tx"].tolist()))}
+        feat_seg = np.array([where[(a, b, t)] if kind == 5 else -1 for a, b, t, kind in arr.tolist()], np.int32)
+        features[chrom] = dict(feat_b0=arr[:, 0].copy(), feat_b1=arr[:, 1].copy(), feat_tx=arr[:, 2].astype(np.int32),
+                               feat_kind=arr[:, 3].astype(np.uint8), feat_seg=feat_seg, tx_strand=meta["strand"], tx_cds_len=meta["cds_length"])
+    return names, meta, segments, features
 
 
 def consequence_table_from_sums(table, rows):
@@ -913,6 +964,101 @@ def run_consequence_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
     names, meta, table = consequence_table(os.fspath(args.pred_file), args.transcripts, os.fspath(args.ref_genome),
                                            getattr(args, "codon_table", None), getattr(args, "alt_order", None), chunk_bytes)
     return write_consequence_outputs(names, meta, table, args.out_prefix)
+
+
+# the structure table: where a row lies in the transcript, beside the consequence table (``summaries.summary_txstruct_host`` is the rule)
+STRUCTURE_BINS = ("utr5", "utr3", "noncoding_exon", "splice_donor", "splice_acceptor", "splice_utr", "intron", "start_lost", "cds")
+
+
+def structure_output_name(out_prefix):
+    return f"{out_prefix}.consequence.structure.tsv"
+
+
+def _structure_acc(n_tx, dev):
+    """The device accumulators of ``summaries.txstruct_rows_device`` and, in `conseq`, of ``summaries.conseq_rows_device``."""
+    zeros = lambda n, dt=torch.int64: torch.zeros(n, dtype=dt, device=dev)      # noqa: E731
+    return dict(table=zeros(max(n_tx, 1) * 27), rows=zeros(max(n_tx, 1) * 2), status=zeros(1, torch.int32), features={}, ws=None,
+                conseq=dict(table=zeros(max(n_tx, 1) * 15), rows=zeros(max(n_tx, 1) * 2), status=zeros(1, torch.int32), segments={}, ws=None))
+
+
+def write_structure_outputs(names, meta, table, rows, stop_gained, out_prefix, labels=True):
+    """``{out_prefix}.consequence.structure.tsv`` from the integer sums of ``summary_txstruct_host`` / ``mural_summary_txstruct_rows``
+    (table uint64 [n][9][3], rows uint64 [n][2]) and `stop_gained` uint64 [n][3], bin 2 of the consequence table's own integers: a line
+    per transcript in file order -- name, chrom, strand, n_rows (the rows inside the span), n_nonmut (those of label 0), expected_* and
+    observed_* for the nine bins of ``STRUCTURE_BINS``, and expected_lof / observed_lof = stop gained + splice donor + splice acceptor +
+    start lost.  An expected value is (hi * 2^40 + lo) / 2^71, formed from Python integers by true division (the LoF sum is added as
+    integers first).  `labels=False`: the rows carried no labels, the observed_* columns are NA.  Returns the path."""
+    table = np.asarray(table, np.uint64).reshape(len(names), 9, 3).tolist()
+    rows = np.asarray(rows, np.uint64).reshape(len(names), 2).tolist()
+    stop_gained = np.asarray(stop_gained, np.uint64).reshape(len(names), 3).tolist()
+    header = ["name", "chrom", "strand", "n_rows", "n_nonmut"]
+    for what in STRUCTURE_BINS + ("lof",):
+        header += [f"expected_{what}", f"observed_{what}"]
+    den, lines = 1 << 71, []
+    for j, nm in enumerate(names):
+        cells = table[j] + [[sum(c[w] for c in (stop_gained[j], table[j][3], table[j][4], table[j][7])) for w in range(3)]]
+        line = [nm, meta["chrom"][j], "-" if meta["strand"][j] else "+", str(rows[j][0]), str(rows[j][1])]
+        for count, hi, lo in cells:
+            line += [_float_text(((hi << 40) + lo) / den), str(count) if labels else "NA"]
+        lines.append(line)
+    path = structure_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, lines))
+    return path
+
+
+def structure_table(pred_file, transcripts, ref_genome, codon_table=None, alt_order=None, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, meta, table uint64 [n][9][3], rows uint64 [n][2], stop_gained uint64 [n][3]) per transcript of `transcripts` (a BED12
+    path or ``read_transcript_structure``'s result) from a written SNV prediction table (4 classes): what ``SummarySink(transcripts=...,
+    transcript_structure=True)`` reduces in flight, through the same entry points (``mural_summary_txstruct_rows``, and
+    ``mural_summary_conseq_rows`` for the stop-gained integers of the LoF column), chromosome run by chromosome run of each chunk.  The
+    rows of a chromosome must ascend in start, as ``predict`` writes them; the codons are read from `ref_genome` (a FASTA path)."""
+    from .data.ingest import read_fasta, scan_fasta
+    from .summaries import _SUMMARY_STATUS, conseq_rows_device, txstruct_rows_device      # (summaries imports this module: not at the top)
+    names, meta, segments, features = read_transcript_structure(transcripts, codon_table)
+    alt = check_alt_order(alt_order)
+    n_tx = len(names)
+    fasta_names = {r.name for r in scan_fasta(ref_genome)}
+    with TableReader(pred_file, 4, chunk_bytes) as rd:
+        dev = rd.device
+        acc = _structure_acc(n_tx, dev)
+        genomes = {}
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in features or b == a:
+                    continue
+                if name not in genomes:
+                    if name not in fasta_names:
+                        raise ValueError(f"Chromosome {name} not found in {ref_genome} (prediction table line {c.row0 + a + 2})")
+                    genomes[name] = read_fasta(ref_genome, dev, names={name})[name]
+                cols = dict(prob=c.prob + 8 * 4 * a, prob_f64=1, prob_stride=4, start=c.start + 8 * a, strand=c.strand + a,
+                            label=c.mut_type + 4 * a, label_kind=1, n=b - a)
+                if name in segments:
+                    conseq_rows_device(acc["conseq"], name, segments[name], n_tx, meta["aa"], alt, genomes[name].as_struct(), dev, **cols)
+                txstruct_rows_device(acc, acc["conseq"], name, segments.get(name), features[name], n_tx, meta["aa"], alt,
+                                     genomes[name].as_struct(), dev, **cols)
+        bits = int(acc["status"].item()) | int(acc["conseq"]["status"].item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table = acc["table"].cpu().numpy().view(np.uint64)[:n_tx * 27].reshape(n_tx, 9, 3)
+        counts = acc["rows"].cpu().numpy().view(np.uint64)[:n_tx * 2].reshape(n_tx, 2)
+        stop_gained = acc["conseq"]["table"].cpu().numpy().view(np.uint64)[:n_tx * 15].reshape(n_tx, 5, 3)[:, 2].copy()
+    return names, meta, table, counts, stop_gained
+
+
+def run_structure_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.transcripts, args.ref_genome, args.out_prefix; optional args.codon_table,
+    args.alt_order): per transcript of the BED12 file the expected and observed mutations of the table's rows inside its span by where
+    they lie in its structure; writes {out_prefix}.consequence.structure.tsv."""
+    assert getattr(args, "transcripts", None) is not None, "--transcripts is required for the structure table"
+    assert getattr(args, "ref_genome", None) is not None, "--ref_genome is required for the structure table"
+    result = structure_table(os.fspath(args.pred_file), args.transcripts, os.fspath(args.ref_genome), getattr(args, "codon_table", None),
+                             getattr(args, "alt_order", None), chunk_bytes)
+    return write_structure_outputs(*result, args.out_prefix)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -31,6 +31,8 @@ alternating, --repeats timed runs each after one warm-up run each:
   q  conseq_sim100  leg o with simulate=100, simulate_seed=1, simulate_transcripts=True as well: the counts of 100
                   mutation sets per transcript and consequence; the comparison is leg o, the same run without it
   r  conseq_sim1000 leg o with simulate=1000 (a table of 400 MB, below the sink's cap)
+  s  conseq_struct  leg o with transcript_structure=True as well: the structure table of the same transcripts --
+                  their exons and the coding introns between them --; the comparison is leg o, the same run without it
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
 h's, leg k's annotation table with leg l's and leg o's consequence table with leg p's, within the table's four digits (names, order and
 counts exactly)."""
@@ -56,7 +58,7 @@ WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
 LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000",
-        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000")
+        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct")
 SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
 CONSEQ_SIM_REPLICATES = {"conseq_sim100": 100, "conseq_sim1000": 1000}
 ANNOT_NAMES, ANNOT_INTERVALS, ANNOT_BP, ANNOT_OVERLAP = 20_000, 10, 150, 0.05
@@ -75,8 +77,8 @@ def synthetic_annotations(bases, chrom="chr1"):
     return tables.read_annotations({chrom: rows})
 
 
-def synthetic_transcripts(bases, chrom="chr1"):
-    """``tables.read_transcripts``' result for the intervals of ``synthetic_annotations`` as ANNOT_NAMES transcripts of ANNOT_INTERVALS
+def synthetic_transcripts(bases, chrom="chr1", structure=False):
+    """``tables.read_transcripts``' result (`structure`: ``tables.read_transcript_structure``'s) for the intervals of ``synthetic_annotations`` as ANNOT_NAMES transcripts of ANNOT_INTERVALS
     exons each, all of it CDS, on alternating strands."""
     import io
     span = bases // ANNOT_NAMES
@@ -88,7 +90,7 @@ def synthetic_transcripts(bases, chrom="chr1"):
         end = at + (ANNOT_INTERVALS - 1) * step + ANNOT_BP
         lines.append("\t".join([chrom, str(at), str(end), "tx%05d" % g, "0", "+-"[g & 1], str(at), str(end), "0", str(ANNOT_INTERVALS),
                                 ",".join([str(ANNOT_BP)] * ANNOT_INTERVALS), ",".join(str(j * step) for j in range(ANNOT_INTERVALS))]))
-    return tables.read_transcripts(io.StringIO("\n".join(lines) + "\n"))
+    return (tables.read_transcript_structure if structure else tables.read_transcripts)(io.StringIO("\n".join(lines) + "\n"))
 
 
 def main(argv):
@@ -113,6 +115,8 @@ def main(argv):
 
         transcripts = synthetic_transcripts(bases) if {"conseq", "conseq_tools", *CONSEQ_SIM_REPLICATES} & set(legs) else None
 
+        structure = synthetic_transcripts(bases, structure=True) if "conseq_struct" in legs else None
+
         def run(leg):
             split, extra = {}, {}
             torch.cuda.synchronize()
@@ -131,10 +135,13 @@ def main(argv):
                 summary = SummarySink(windows=WINDOWS, annotations=annot, simulate=SIM_REPLICATES[leg], simulate_seed=1, simulate_labels=False)
             if leg == "conseq":
                 summary = SummarySink(windows=WINDOWS, transcripts=transcripts, genome=fwd.genome, transcript_labels=False)
+            if leg == "conseq_struct":
+                summary = SummarySink(windows=WINDOWS, transcripts=structure, genome=fwd.genome, transcript_labels=False,
+                                      transcript_structure=True)
             if leg in CONSEQ_SIM_REPLICATES:
                 summary = SummarySink(windows=WINDOWS, transcripts=transcripts, genome=fwd.genome, transcript_labels=False,
                                       simulate=CONSEQ_SIM_REPLICATES[leg], simulate_seed=1, simulate_transcripts=True)
-            if leg in ("summary", "annot", "sim100", "sim1000", "conseq", *CONSEQ_SIM_REPLICATES) and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
+            if leg in ("summary", "annot", "sim100", "sim1000", "conseq", "conseq_struct", *CONSEQ_SIM_REPLICATES) and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
                 plain_close = summary.close
 
                 def close_timed():
@@ -161,7 +168,7 @@ def main(argv):
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
                     "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out), "sim100": lambda: summary,
                     "sim1000": lambda: summary, "conseq": lambda: summary, "conseq_tools": lambda: TsvSink(out),
-                    "conseq_sim100": lambda: summary, "conseq_sim1000": lambda: summary}[leg]()
+                    "conseq_sim100": lambda: summary, "conseq_sim1000": lambda: summary, "conseq_struct": lambda: summary}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
                                         **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
@@ -237,6 +244,10 @@ def main(argv):
         counts, sums = [0, 1, 2, 4, 6, 8, 10], [3, 5, 7, 9, 11]
         agree = agree and na == nd and bool((ta[:, counts] == td[:, counts]).all()) and bool(ta[:, 0].sum() > 0)
         agree = agree and bool((abs(ta[:, sums] - td[:, sums]) <= 5e-4 * ta[:, sums]).all())
+    if {"conseq", "conseq_struct"} <= set(legs):      # the consequence table beside the structure table is leg o's, and bins 7 + 8 are its rows
+        (na, _, ta), (ns, _, ts) = kept["conseq"]["consequences"], kept["conseq_struct"]["consequences"]
+        struct = kept["conseq_struct"]["transcript_structure"][1]
+        agree = agree and na == ns and bool((ta == ts).all()) and bool((struct[:, 7:9, 0].sum(axis=1) == ta[:, [2, 4, 6, 8, 10]].sum(axis=1)).all())
     rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in legs}
     med = {leg: rate[leg]["median"] for leg in legs}
     sec = {leg: statistics.median(seconds[leg]) for leg in legs}
@@ -257,6 +268,8 @@ def main(argv):
                             "rows_in_a_cds": float(kept["conseq"]["consequences"][2][:, 0].sum()) if "conseq" in kept else None,
                             "expected": kept["conseq"]["consequences"][2][:, 3:11:2].sum(axis=0).tolist() if "conseq" in kept else None},
            "conseq_sim100_over_conseq": ratio("conseq_sim100", "conseq", med), "conseq_sim1000_over_conseq": ratio("conseq_sim1000", "conseq", med),
+           "conseq_struct_over_conseq": ratio("conseq_struct", "conseq", med),
+           "structure_rows": kept["conseq_struct"]["transcript_structure"][2][:, 0].sum().item() if "conseq_struct" in kept else None,
            "simulated_consequence_draws": {leg: float(kept[leg]["consequence_simulation"][1].sum()) for leg in CONSEQ_SIM_REPLICATES if leg in kept},
            "simulated_draws": {leg: float(kept[leg]["simulation"][1].sum()) for leg in SIM_REPLICATES if leg in kept},
            "annotations": {"names": ANNOT_NAMES, "intervals": ANNOT_INTERVALS, "bp": ANNOT_BP,

@@ -64,6 +64,15 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              class whose substitution has that consequence --, n_ge / n_le and the
                                                              empirical p-values (n + 1) / (R + 1); --simulate then needs neither
                                                              --annotations nor --write_simulated
+  --summary PREFIX  --transcripts BED12 --transcript_structure
+                                                             PREFIX.consequence.structure.tsv as well: per transcript the expected and
+                                                             observed mutations of the SNV rows inside chromStart .. chromEnd, split
+                                                             into utr5, utr3, noncoding_exon, splice_donor, splice_acceptor (the two
+                                                             essential bases at the ends of an intron between CDS bases), splice_utr
+                                                             (those of any other intron), intron, start_lost (a change of the amino acid
+                                                             of CDS codon 0: BED12 carries no frame, ATG is not demanded) and cds, and
+                                                             expected_lof / observed_lof = stop gained + splice donor + splice acceptor
+                                                             + start lost
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -170,7 +179,11 @@ def _summary_options(flags, values, model_type="snv"):
             "simulate": one("--simulate", int), "seed": one("--seed", lambda v: int(v, 0)),
             "write_simulated": tuple(int(r) for r in values.get("--write_simulated", [])), "transcripts": one("--transcripts", str),
             "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str),
-            "simulate_consequences": "--simulate_consequences" in flags}
+            "simulate_consequences": "--simulate_consequences" in flags, "transcript_structure": "--transcript_structure" in flags}
+    if opts["transcript_structure"] and opts["transcripts"] is None:
+        raise SystemExit("--transcript_structure needs --transcripts BED12: the transcripts whose UTRs, introns and splice sites it bins")
+    if opts["transcript_structure"] and model_type == "indel":
+        raise SystemExit("--transcript_structure takes SNV rows: it does not go with --indel")
     if opts["simulate_consequences"] and opts["transcripts"] is None:
         raise SystemExit("--simulate_consequences needs --transcripts BED12: the transcripts whose consequence counts it simulates")
     if opts["simulate_consequences"] and opts["simulate"] is None:
@@ -220,9 +233,10 @@ def _summary_options(flags, values, model_type="snv"):
         raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics, --annotations, "
                          "--simulate or --transcripts")
     if opts["transcripts"] is not None:
-        from mural_amd.tables import check_alt_order, read_transcripts
+        from mural_amd.tables import check_alt_order, read_transcript_structure, read_transcripts
         try:
-            opts["transcripts"] = read_transcripts(opts["transcripts"], opts["codon_table"])
+            opts["transcripts"] = (read_transcript_structure if opts["transcript_structure"] else read_transcripts)(opts["transcripts"],
+                                                                                                                   opts["codon_table"])
             opts["alt_order"] = check_alt_order(opts["alt_order"])
         except (OSError, ValueError) as e:
             raise SystemExit(f"--transcripts: {e}") from None
@@ -289,7 +303,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               calibration_bins=50 if opts["n_bins"] is None else opts["n_bins"], fit_calibrator=opts["fit_calibrator"],
                               annotations=opts["annotations"], simulate=opts["simulate"], simulate_seed=opts["seed"],
                               simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), transcripts=opts["transcripts"], alt_order=opts["alt_order"],
-                              transcript_labels=opts.get("labelled", True), simulate_transcripts=opts["simulate_consequences"], **sink_chain)
+                              transcript_labels=opts.get("labelled", True), simulate_transcripts=opts["simulate_consequences"],
+                              transcript_structure=opts["transcript_structure"], **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
