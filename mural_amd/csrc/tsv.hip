@@ -153,7 +153,8 @@ HD double scale10(double a, int p) {
   return a / pow10_tab(-p);
 }
 
-// '%.4g' % v, NaN -> nothing (pandas' na_rep='').  Returns the number of characters written (at most 10).
+// '%.4g' % v, NaN -> nothing (pandas' na_rep='').  Returns the number of characters written (at most 11:
+// '-1.234e-308').
 HD int fmt_g4(double v, char* o) {
   const uint64_t bits = f64_bits(v);
   const uint64_t ab = bits & 0x7fffffffffffffffull;
@@ -302,7 +303,7 @@ int row_bound(const MuralTsvRows& t, const char* names_host) {
   int longest = 0;
   for (int c = 0; c < t.n_chroms; ++c)
     longest = std::max(longest, (int)strnlen(names_host + (int64_t)c * t.name_stride, (size_t)t.name_stride));
-  return longest + 1 + 20 + 1 + 20 + 1 + 1 + 1 + 20 + t.n_class * 11 + 1 + 2;
+  return longest + 1 + 20 + 1 + 20 + 1 + 1 + 1 + 20 + t.n_class * 12 + 1 + 2;      // a class: tab + fmt_g4's 11
 }
 
 // ---- device side --------------------------------------------------------------------------------------------------------------

@@ -9,18 +9,20 @@ import torch
 
 from mural_amd import _lib
 from mural_amd.predict import TsvSink, _name_table, _tsv_struct, check_focal_groups, format_rows_host
-from tests.test_tsv import _pandas_table, _random_rows
+from tests import _g4_data as G
+from tests.test_tsv import _longest_rows, _pandas_table, _random_rows
 
 pytestmark = pytest.mark.gpu
 
 
-def _format_device(name, start, end, strand, label, prob, k, perm=None):
+def _format_device(name, start, end, strand, label, prob, k, perm=None, layout=0):
     lib = _lib.lib()
     dev = prob.device
     n = start.shape[0]
     names = _name_table([name])
     t = _tsv_struct(names, 1, None, start.data_ptr(), end.data_ptr(), strand.data_ptr(), label.data_ptr(), prob.data_ptr(),
                     prob.dtype == torch.float64, k, prob.stride(0), None if perm is None else perm.data_ptr(), n)
+    t.layout = layout
     bound = int(lib.mural_tsv_row_bound(C.byref(t)))
     text = torch.empty(max(n * bound, 1), dtype=torch.uint8, device=dev)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -81,6 +83,95 @@ def test_device_formatter_empty_and_long_names():
     got = _format_device(name, one(2 ** 62, torch.int64), one(2 ** 62 + 1, torch.int64), one(1, torch.uint8), one(3, torch.float32),
                          torch.tensor([[0.25, 1e-7]], device="cuda"), 2)
     assert got == f"{name}\t{2 ** 62}\t{2 ** 62 + 1}\t-\t3\t0.25\t1e-07\n".encode()
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def test_rows_of_eleven_character_values_fit_the_row_bound_on_the_device():
+    """tests/test_tsv.py's longest rows (64 classes of '-1.234e-308' / '-1.234e+308') through the kernel: its LDS slots and the text
+    buffer are sized by mural_tsv_row_bound, which has to budget tab + 11 per class."""
+    cols, want = _longest_rows()
+    got = _format_device("c", _dev(cols["start"]), _dev(cols["end"]), _dev(cols["strand"]), _dev(cols["label"]), _dev(cols["prob"]), 64)
+    assert got == want
+
+
+def test_tie_values_hold_every_exact_tie_and_reach_the_big_integer_comparison():
+    """What keeps test_device_formatter_equals_python_at_every_tie from thinning out unseen: the generator finds every exactly
+    representable tie (the counts are those of every N = 1000 .. 9999 over every decade of the double range), and at least 100,000 of
+    its float64 values have |p| > 22 and scale to within 1e-6 of N + 0.5, the condition under which fmt_g4 calls exact_cmp_half."""
+    for dtype, count in G.EXACT_TIES.items():
+        ties = G.exact_ties(dtype)
+        assert len(ties) == count
+        assert np.isin(ties, G.values(dtype, "ties")).all()
+    assert G.far_and_near_half(np.concatenate([G.values("float64", g) for g in G.GROUPS])) >= 100_000
+
+
+@pytest.mark.parametrize("group", G.GROUPS)
+@pytest.mark.parametrize("dtype", list(G.DTYPES))
+def test_device_formatter_equals_python_at_every_tie(dtype, group):
+    """The device compile of fmt_g4 where '%.4g' is decided: (N + 0.5) x 10^(e10 - 3) rounded to the table's type with its +-1 and +-2
+    ulp neighbours -- all N = 1000 .. 9999 in the probability decades, either side of every change of rounding route, in the lowest
+    and the highest decades, every 37th N elsewhere -- and every exactly representable tie (tests/_g4_data.py).  One value per row,
+    k = 1, in an (n, 2) matrix so that the row stride counts.  CPython's '%.4g' is the oracle; the host compile has to agree too."""
+    vals = G.values(dtype, group)
+    n = len(vals)
+    wide = np.stack([vals, np.full(n, 7, vals.dtype)], axis=1)
+    start, end, strand, label = np.zeros(n, np.int64), np.ones(n, np.int64), np.zeros(n, np.uint8), np.zeros(n, np.float32)
+    got = _format_device("c", _dev(start), _dev(end), _dev(strand), _dev(label), _dev(wide), 1)
+    G.assert_same_rows(got, G.g4_rows(vals), vals, "device formatter against '%.4g'")
+    host = format_rows_host(["c"], None, start, end, strand, label, vals.reshape(n, 1))
+    G.assert_same_rows(got, host, vals, "device formatter against the host formatter")
+
+
+_I64 = [0, -1] + [v for k in range(1, 19) for v in (10 ** k - 1, 10 ** k)] + [2 ** 63 - 1, -2 ** 63]
+# label_to_i64: truncation towards zero; NaN, the infinities and |v| >= 2^63 give INT64_MIN
+_LABELS = np.array([0, 3.9, -0.5, -3.9, 2.0 ** 62, 2.0 ** 63, -2.0 ** 63, np.inf, -np.inf, np.nan, 1e-45], np.float32)
+
+
+def _format_host(name, start, end, strand, label, prob, k, layout):
+    lib = _lib.lib()
+    n = len(start)
+    t = _tsv_struct(_name_table([name]), 1, None, start.ctypes.data, end.ctypes.data, strand.ctypes.data, label.ctypes.data,
+                    prob.ctypes.data, prob.dtype == np.float64, k, prob.shape[1], None, n)
+    t.layout = layout
+    out = np.empty(n * int(lib.mural_tsv_row_bound(C.byref(t))), np.uint8)
+    count = C.c_int64(0)
+    _lib.check(lib.mural_tsv_format_host(C.byref(t), out.ctypes.data, out.size, C.byref(count), 1))
+    return out[:count.value].tobytes()
+
+
+@pytest.mark.parametrize("layout", [0, 1], ids=["table", "bed6"])
+def test_integer_fields_on_the_device_equal_python_and_the_host_formatter(layout):
+    """start / end at every power of ten and one below it, 0, -1 and both ends of int64; the label column (a float32 cast the way
+    numpy casts to int64) at fractions either side of zero, 2^62, +-2^63, +-inf, NaN and a subnormal.  str(int) is the oracle for
+    start, end and the finite labels below 2^63 in size (-2^63 included); every row equals the host formatter's, in both layouts."""
+    assert _LABELS[-1] > 0 and _LABELS[-1] < np.finfo(np.float32).tiny
+    n = len(_I64) * len(_LABELS)
+    start = np.repeat(np.array(_I64, np.int64), len(_LABELS))
+    end = start[::-1].copy()
+    label = np.tile(_LABELS, len(_I64))
+    strand = (np.arange(n) % 3 == 0).astype(np.uint8)
+    prob = np.full((n, 2), 0.25, np.float32)
+    got = _format_device("c", _dev(start), _dev(end), _dev(strand), _dev(label), _dev(prob), 1, layout=layout)
+    assert got == _format_host("c", start, end, strand, label, prob, 1, layout)
+    rows = got.decode().split("\n")
+    assert len(rows) == n + 1 and rows[-1] == ""
+    for i, row in enumerate(rows[:-1]):
+        f = row.split("\t")
+        if layout == 0:
+            assert len(f) == 6 and f[5] == "0.25", row
+            sign, text = f[3], f[4]
+        else:
+            assert len(f) == 6 and f[3] == ".", row
+            sign, text = f[5], f[4]
+        assert (f[0], f[1], f[2], sign) == ("c", str(int(start[i])), str(int(end[i])), "-" if strand[i] else "+"), row
+        v = label[i]
+        if np.isfinite(v) and -2.0 ** 63 <= v < 2.0 ** 63:
+            assert text == str(int(np.trunc(v))), row
+        else:
+            assert text == str(-2 ** 63), row
 
 
 def test_focal_group_check_kernel_matches_host_check():

@@ -9,8 +9,9 @@ import pandas as pd
 import pytest
 
 from mural_amd import _lib
-from mural_amd.predict import TsvSink, format_rows_host, write_predictions
+from mural_amd.predict import TsvSink, _name_table, _tsv_struct, format_rows_host, write_predictions
 
+from . import _g4_data as G
 from . import _util as U
 
 
@@ -58,6 +59,46 @@ def test_g4_matches_python_on_random_bit_patterns_and_near_ties():
             if _g4(v) != "%.4g" % v:
                 bad.append(v)
     assert not bad, bad[:5]
+
+
+@pytest.mark.parametrize("group", G.GROUPS)
+@pytest.mark.parametrize("dtype", list(G.DTYPES))
+def test_host_formatter_equals_python_at_every_tie(dtype, group):
+    """The host compile over the values of tests/_g4_data.py (every N of the decades that matter, every exactly representable tie,
+    +-1 / +-2 ulp neighbours), through the row formatter; tests/test_gpu_tsv.py runs the same values through the device compile."""
+    vals = G.values(dtype, group)
+    n = len(vals)
+    got = format_rows_host(["c"], None, np.zeros(n, np.int64), np.ones(n, np.int64), np.zeros(n, np.uint8), np.zeros(n, np.float32),
+                           vals.reshape(n, 1))
+    G.assert_same_rows(got, G.g4_rows(vals), vals, "host formatter against '%.4g'")
+
+
+def _longest_rows(k=64):
+    """Two float64 rows of `k` classes (the most mural_tsv_row_bound's validation accepts) whose every value takes the 11 characters
+    '%.4g' can reach -- a sign, four digits, a three-digit exponent -- behind one-digit start, end and label and a one-character name."""
+    prob = np.repeat(np.array([[-1.234e-308], [-1.234e+308]]), k, axis=1)
+    cols = dict(start=np.array([1, 2], np.int64), end=np.array([2, 3], np.int64), strand=np.array([0, 1], np.uint8),
+                label=np.array([3, 0], np.float32), prob=prob)
+    want = "".join("c\t%d\t%d\t%s\t%d\t%s\n" % (cols["start"][i], cols["end"][i], "+-"[cols["strand"][i]], cols["label"][i],
+                                               "\t".join("%.4g" % v for v in prob[i])) for i in range(2)).encode()
+    return cols, want
+
+
+def _row_bound(name, k, f64=True):
+    t = _tsv_struct(_name_table([name]), 1, None, None, None, None, None, None, f64, k, k, None, 0)
+    return int(_lib.lib().mural_tsv_row_bound(C.byref(t)))
+
+
+def test_row_bound_covers_rows_of_eleven_character_values():
+    """'-1.234e-308' is 11 characters: with 64 of them a row is longer than a bound of tab + 10 per class, and the bound sizes the host
+    formatter's buffer, the kernel's LDS slots and the caller's text buffer."""
+    cols, want = _longest_rows()
+    assert all(len("%.4g" % v) == 11 for v in cols["prob"].ravel())
+    assert _row_bound("c", 65) == -1        # 64 classes is the cap
+    got = format_rows_host(["c"], None, cols["start"], cols["end"], cols["strand"], cols["label"], cols["prob"])
+    assert got == want
+    bound = _row_bound("c", 64)
+    assert max(len(ln) + 1 for ln in got.split(b"\n")[:-1]) <= bound
 
 
 def _pandas_table(chrom, start, end, strand, label, prob):
