@@ -1116,6 +1116,68 @@ size_t mural_simulate_conseq_workspace_bytes(int64_t n_segments);
 int mural_simulate_conseq_rows(const MuralSimulateConseqRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The simulated null of the structure table of a shard while it is on the device (SummarySink(simulate=R,
+ * transcripts=..., transcript_structure=True, simulate_transcripts=True, simulate_structure=True) in flight,
+ * tables.simulate_structure_table from a written table; csrc/simulate_txstruct.hip;
+ * mural_amd.summaries.simulate_txstruct_host is the specification).  Rows, chrom_key, n_rep, seed, genome, segments,
+ * transcripts, aa and alt_order as mural_simulate_conseq_rows; the chromosome's items (feat_*) as
+ * mural_summary_txstruct_rows.
+ *   table [n_transcripts][9][n_rep] of unsigned 32-bit cells: cell [t][b][r] += the rows inside [chromStart, chromEnd) of
+ *   transcript t whose replicate-r draw (the draw of mural_simulate_annot_rows, unchanged) is a class c >= 1 that falls in
+ *   bin b of t (the bin of mural_summary_txstruct_rows: 0 utr5 .. 8 cds).  A row counts once per transcript whose span
+ *   covers it; class 0 counts nowhere; no label is read.  Zeroed by the caller once, it accumulates over calls, parts and
+ *   chromosomes, and is a function of the SET of rows and the seed alone, bit for bit.  Bins 7 + 8 of a transcript and
+ *   replicate add up to the five bins of mural_simulate_conseq_rows at the same chrom_key and seed.
+ *   status: the simulation's bits -- bit 3 a probability of a class >= 1 that is NaN, negative or infinite, bit 0 a
+ *   negative start (such rows draw class 0 in every replicate), bit 2 a start below the row before it inside the call;
+ *   a probability of 1 or more is taken as 1.  A CDS item whose feat_seg is outside 0 .. n_segments - 1 or names another
+ *   segment, an item of an unknown kind and an item whose transcript is outside 0 .. n_transcripts - 1 are skipped.
+ * MURAL_E_INVALID, before the first launch: n_class != 4, n_rep outside 1 .. 2^20, n > 2^31, n_features > 2^22,
+ * n_segments > 2^22, an alt_order row that does not name the three other bases once each.  The loop bounds are
+ * mural_simulate_chunk_rows(), mural_simulate_grid_waves() and mural_simulate_scan_threads(): the grid strides over units
+ * of (chunk of an item, group of up to 16 blocks of 64 replicates); a row's three slots are formed once per unit.
+ * ws: mural_simulate_txstruct_workspace_bytes(n_features) bytes (24 per item), 8-byte aligned; MURAL_E_WORKSPACE when
+ * smaller.  n == 0 launches nothing; n_features == 0 only checks the rows; n_segments == 0 is legal (no CDS on the
+ * chromosome).  Launches on `stream`: no synchronisation, no read-back, no floating-point atomics; draws and bins are
+ * recomputed, never stored.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const MuralGenome* genome; /* the chromosome of the rows */
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. 3 are read                  */
+  int32_t prob_f64, n_class; /* n_class == 4 */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const uint8_t* strand;     /* dev [n], 1 = '-', or NULL */
+  int64_t n;
+  uint32_t chrom_key;
+  int32_t n_rep;
+  uint64_t seed;
+  const int64_t* seg_b0;     /* dev [n_segments] */
+  const int64_t* seg_b1;     /* dev [n_segments] */
+  const int64_t* seg_cds0;   /* dev [n_segments] */
+  const int32_t* seg_tx;     /* dev [n_segments] */
+  const int32_t* seg_prev;   /* dev [n_segments] */
+  const int32_t* seg_next;   /* dev [n_segments] */
+  int64_t n_segments;
+  const uint8_t* tx_strand;  /* dev [n_transcripts] */
+  const int64_t* tx_cds_len; /* dev [n_transcripts] */
+  int32_t n_transcripts, reserved;
+  uint8_t aa[64];
+  uint8_t alt_order[4][3];
+  uint8_t reserved2[4];
+  uint32_t* table;           /* dev [n_transcripts][9][n_rep] */
+  int32_t* status;           /* dev [1] */
+  const int64_t* feat_b0;    /* dev [n_features] */
+  const int64_t* feat_b1;    /* dev [n_features] */
+  const int32_t* feat_tx;    /* dev [n_features] */
+  const uint8_t* feat_kind;  /* dev [n_features] */
+  const int32_t* feat_seg;   /* dev [n_features] */
+  int64_t n_features;
+} MuralSimulateTxstructRows;
+size_t mural_simulate_txstruct_workspace_bytes(int64_t n_features);
+int mural_simulate_txstruct_rows(const MuralSimulateTxstructRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

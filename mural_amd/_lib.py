@@ -160,6 +160,11 @@ class MuralSimulateConseqRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSimulateTxstructRows(C.Structure):
+    _fields_ = MuralSimulateConseqRows._fields_ + [("feat_b0", C.c_void_p), ("feat_b1", C.c_void_p), ("feat_tx", C.c_void_p),
+                                                   ("feat_kind", C.c_void_p), ("feat_seg", C.c_void_p), ("n_features", C.c_int64)]
+
+
 class MuralSimulateRows(C.Structure):
     _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
                 ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("replicate", C.c_int32), ("seed", C.c_uint64),
@@ -343,6 +348,8 @@ PROTOTYPES = {
     "mural_simulate_rows": (C.c_int, [C.POINTER(MuralSimulateRows), VP, C.c_size_t, VP]),
     "mural_simulate_conseq_workspace_bytes": (C.c_size_t, [I64]),
     "mural_simulate_conseq_rows": (C.c_int, [C.POINTER(MuralSimulateConseqRows), VP, C.c_size_t, VP]),
+    "mural_simulate_txstruct_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_simulate_txstruct_rows": (C.c_int, [C.POINTER(MuralSimulateTxstructRows), VP, C.c_size_t, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -17,7 +17,8 @@ from .sinks import _np, _refuse_second_calibration, host_calibrate, shard_bounds
 from .tables import (annotation_meta, annotation_output_names, check_alt_order, consequence_output_name,
                      consequence_simulation_output_name, consequence_table_from_sums, write_consequence_simulation_outputs,
                      read_transcripts, read_transcript_structure, structure_output_name, write_consequence_outputs,
-                     write_structure_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
+                     write_structure_outputs, structure_cells_from_sums, structure_simulation_output_name,
+                     write_structure_simulation_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
                      write_simulation_outputs, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
                      strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs)
@@ -539,6 +540,30 @@ def conseq_rows_device(acc, name, segments, n_transcripts, aa, alt_order, genome
 TX_BINS = 9
 
 
+def _txstruct_pairs(genome, start, rs, segments, features, aa, alt_of):
+    """The one item walk and bin rule of the structure tables on the host, shared by ``summary_txstruct_host`` and
+    ``simulate_txstruct_host``: for rows sorted by start (`rs`: their strands as int64 0 / 1), a chromosome's `features` and its
+    `segments` (or None), yields (i, tx, bins) per pass of at most ``_CONSEQ_PAIRS`` (item, row) pairs with feat_b0 <= start[i] <
+    feat_b1 -- the row index, the item's transcript and bins int64 [pairs][3], the bin 0 .. 8 of classes 1 .. 3 by the rule
+    ``summary_txstruct_host`` states.  The CDS parts are the segments: they go through ``_conseq_pairs``."""
+    kind = np.asarray(features["feat_kind"], np.int64)
+    other = np.nonzero(kind != 5)[0]
+    a, b = np.asarray(features["feat_b0"], np.int64)[other], np.asarray(features["feat_b1"], np.int64)[other]
+    f_tx, kind = np.asarray(features["feat_tx"], np.int64)[other], kind[other]
+    tx_minus = np.asarray(features["tx_strand"]) != 0
+    for f, i in _item_row_pairs(start, a, b):
+        q, tx = start[i], f_tx[f]
+        sites = (kind[f] >= 3) & (b[f] - a[f] >= 4)
+        low, high = sites & (q < a[f] + 2), sites & (q >= b[f] - 2)
+        donor = np.where(tx_minus[tx], high, low)
+        site_bin = np.where(kind[f] == 3, np.where(donor, 3, 4), 5)
+        bins = np.where(kind[f] < 3, kind[f], np.where(low | high, site_bin, 6))
+        yield i, tx, np.repeat(bins[:, None], 3, axis=1)
+    if segments is not None and len(segments["seg_b0"]):
+        for i, tx, bins, x in _conseq_pairs(genome, start, rs, segments, aa, alt_of, with_offset=True):
+            yield i, tx, np.where((x < 3)[:, None] & (bins >= 1) & (bins <= 3), 7, 8)
+
+
 def summary_txstruct_host(genome, prob, start, strand, label, segments, features, n_transcripts, aa=None, alt_order=None, into=None,
                           n_class=4):
     """The numpy twin of ``mural_summary_txstruct_rows`` -- and its specification -- for SNV rows (any order) of one chromosome: (table
@@ -587,22 +612,8 @@ def summary_txstruct_host(genome, prob, start, strand, label, segments, features
         np.add.at(flat_rows, 2 * tx + 1, (lab[i] == 0).astype(np.uint64))
         _conseq_fold(table)
 
-    kind = np.asarray(features["feat_kind"], np.int64)
-    other = np.nonzero(kind != 5)[0]                       # the CDS parts are the segments: they go through _conseq_pairs below
-    a, b = np.asarray(features["feat_b0"], np.int64)[other], np.asarray(features["feat_b1"], np.int64)[other]
-    f_tx, kind = np.asarray(features["feat_tx"], np.int64)[other], kind[other]
-    tx_minus = np.asarray(features["tx_strand"]) != 0
-    for f, i in _item_row_pairs(start, a, b):
-        q, tx = start[i], f_tx[f]
-        sites = (kind[f] >= 3) & (b[f] - a[f] >= 4)
-        low, high = sites & (q < a[f] + 2), sites & (q >= b[f] - 2)
-        donor = np.where(tx_minus[tx], high, low)
-        site_bin = np.where(kind[f] == 3, np.where(donor, 3, 4), 5)
-        bins = np.where(kind[f] < 3, kind[f], np.where(low | high, site_bin, 6))
-        add(i, tx, np.repeat(bins[:, None], 3, axis=1))
-    if segments is not None and len(segments["seg_b0"]):
-        for i, tx, bins, x in _conseq_pairs(genome, start, rs, segments, aa, alt_of, with_offset=True):
-            add(i, tx, np.where((x < 3)[:, None] & (bins >= 1) & (bins <= 3), 7, 8))
+    for i, tx, bins in _txstruct_pairs(genome, start, rs, segments, features, aa, alt_of):
+        add(i, tx, bins)
     return table, rows, status
 
 
@@ -801,6 +812,91 @@ def simulate_conseq_rows_device(table, status, acc, name, n_transcripts, aa, alt
     C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
     s.table, s.status = table.data_ptr(), status.data_ptr()
     _lib.check(lib.mural_simulate_conseq_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+
+
+def simulate_txstruct_host(genome, prob, start, strand, segments, features, n_transcripts, chrom_key, seed, n_rep, aa=None, alt_order=None,
+                           into=None):
+    """The numpy twin of ``mural_simulate_txstruct_rows`` -- and its specification -- for SNV rows (4 classes; no label is read) of one
+    chromosome: (table uint32 [n_transcripts][9][n_rep], status).  Cell [t][b][r]: the rows inside [chromStart, chromEnd) of transcript
+    t whose replicate-r draw is a class c >= 1 that falls in structure bin b of t.  The draw is ``simulate_rows_host``'s, unchanged
+    (Philox key and counter, cum, ties, p_c >= 1 taken as 1); the bin is ``summary_txstruct_host``'s rule through the same item walk
+    (``_txstruct_pairs``; `segments`, `features`, `aa`, `alt_order` and `strand` as there).  A row counts once per transcript whose
+    span covers it; class 0 counts nowhere.  The row checks are the simulation's, as ``simulate_conseq_host``: status 8 a NaN, negative
+    or infinite p_c, status 1 a negative start -- such rows draw class 0 in every replicate --, status 4 a start below the row before
+    it.  The table is a function of the SET of rows and the seed alone, bit for bit, for any parts, shards or ranks.  `into`: the table
+    of earlier parts and chromosomes, added to in place.
+
+    THE DEFINING IDENTITIES.  (a) For rows that both rules accept, cell [t][b][r] equals the observed word [t][b][0] of
+    ``summary_txstruct_host`` run with label = ``simulate_rows_host(..)[:, r]``.  (b) For every t and r, bins 7 + 8 add up to the five
+    bins of ``simulate_conseq_host``'s table at the same key, seed and replicate.  (c) ``simulate_lof_counts`` of that table and this
+    one is the observed_lof of ``tables.write_structure_outputs`` for a run labelled with replicate r."""
+    from .tables import check_alt_order, check_codon_table
+    n_tx, R = int(n_transcripts), int(n_rep)
+    if not 1 <= R <= SIMULATE_MAX_REPLICATES:
+        raise ValueError("simulate: 1 .. 2^20 replicates")
+    aa = check_codon_table(aa).astype(np.int64)
+    alt_of = check_alt_order(alt_order).astype(np.int64)
+    start = np.asarray(start, np.int64)
+    labels, status = simulate_rows_host(prob, start, strand, 4, chrom_key, seed, np.arange(R), with_status=True)
+    if len(start) > 1 and (start[1:] < start[:-1]).any():
+        status |= 4
+    table = np.zeros((n_tx, TX_BINS, R), np.uint32) if into is None else into
+    if features is None or len(features["feat_b0"]) == 0 or len(start) == 0:
+        return table, status
+    rs = np.zeros(len(start), np.int64) if strand is None else strand_u8(strand).astype(np.int64)
+    order = np.argsort(start, kind="stable")
+    start, labels, rs = start[order], labels[order], rs[order]
+    flat = table.reshape(-1, R)
+    for i, tx, bins in _txstruct_pairs(genome, start, rs, segments, features, aa, alt_of):
+        lab = labels[i].astype(np.int64)                                                 # [pairs][R]
+        lb = np.take_along_axis(bins, np.maximum(lab - 1, 0), axis=1)                    # the bin of the drawn class
+        for b in np.unique(bins):
+            hit = ((lab > 0) & (lb == b)).astype(np.uint32)
+            np.add.at(flat, tx * TX_BINS + b, hit)
+    return table, status
+
+
+def simulate_lof_counts(conseq_counts, struct_counts):
+    """lof int64 [transcripts][R] of the simulated loss-of-function count: stop gained (bin 2 of ``simulate_conseq_host``'s table
+    [transcripts][5][R]) + splice donor + splice acceptor + start lost (bins 3, 4, 7 of ``simulate_txstruct_host``'s table
+    [transcripts][9][R]) of the SAME draws -- the four terms by which ``tables.write_structure_outputs`` forms observed_lof."""
+    conseq_counts, struct_counts = np.asarray(conseq_counts), np.asarray(struct_counts)
+    if conseq_counts.ndim != 3 or struct_counts.ndim != 3 or conseq_counts.shape[1] != 5 or struct_counts.shape[1] != TX_BINS or \
+            conseq_counts.shape[::2] != struct_counts.shape[::2]:
+        raise ValueError("simulate_lof_counts: counts [transcripts][5][R] and [transcripts][9][R] of the same transcripts and replicates")
+    lof = conseq_counts[:, 2].astype(np.int64)
+    for term in (struct_counts[:, 3], struct_counts[:, 4], struct_counts[:, 7]):
+        lof += term
+    return lof
+
+
+def simulate_txstruct_rows_device(table, status, acc, conseq_acc, name, n_transcripts, aa, alt_order, genome_struct, dev, n_rep, seed, *,
+                                  prob, prob_f64, prob_stride, start, strand, n):
+    """One ``mural_simulate_txstruct_rows`` call on device pointers into `table` (int32 [n_transcripts * 9 * n_rep]) and `status`, on
+    the item arrays ``txstruct_rows_device`` uploaded into `acc` for chromosome `name` just before and the segment arrays of
+    `conseq_acc`; the workspace is `acc`'s (24 bytes an item in both entries, and the launches of one stream run in order)."""
+    lib = _lib.lib()
+    on_dev = acc["features"][name]
+    seg_dev = conseq_acc["segments"].get(name)
+    n_feat = int(on_dev[0].shape[0])
+    need = int(lib.mural_simulate_txstruct_workspace_bytes(n_feat))
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _lib.MuralSimulateTxstructRows()
+    s.genome = C.pointer(genome_struct)
+    s.prob, s.prob_f64, s.prob_stride, s.n_class = prob, int(prob_f64), int(prob_stride), 4
+    s.start, s.strand, s.n = start, strand, int(n)
+    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
+    if seg_dev is not None and seg_dev[0].shape[0]:
+        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in seg_dev[:6])
+        s.n_segments = int(seg_dev[0].shape[0])
+    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg = (x.data_ptr() for x in on_dev[:5])
+    s.n_features, s.n_transcripts = n_feat, int(n_transcripts)
+    s.tx_strand, s.tx_cds_len = conseq_acc["tx"][0].data_ptr(), conseq_acc["tx"][1].data_ptr()
+    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
+    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+    s.table, s.status = table.data_ptr(), status.data_ptr()
+    _lib.check(lib.mural_simulate_txstruct_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
 
 
 def simulate_pvalues(counts, observed=None):
@@ -1798,6 +1894,82 @@ class _ConsequenceSimulationReducer:
         write_consequence_simulation_outputs(*result[self.name], out_prefix)
 
 
+class _StructureSimulationReducer:
+    """The simulated null of the structure table and of the loss-of-function count (``simulate_txstruct_host`` is the rule): per
+    transcript, structure bin and replicate the simulated count -- ONE uint32 table [transcripts][9][n_rep] on the host and one per
+    device, behind the structure reducer `struct` (whose item arrays and workspace it uses) and the consequence simulation `conseq_sim`
+    (whose stop-gained counts of the same draws complete the LoF count), read back once."""
+    name = "structure_simulation"
+
+    def __init__(self, n_rep, seed, struct, conseq_sim, table_bytes_max):
+        self.n_rep, self.seed, self.struct, self.conseq_sim = int(n_rep), int(seed), struct, conseq_sim
+        self.conseq, self.table_bytes_max = struct.conseq, int(table_bytes_max)
+        need = len(self.conseq.names) * TX_BINS * self.n_rep * 4
+        if need > self.table_bytes_max:
+            raise ValueError(f"simulate: the table of {len(self.conseq.names)} transcripts x {TX_BINS} structure bins x {self.n_rep} "
+                             f"replicates takes {need} bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        self.reset()
+
+    def reset(self):
+        self.host = None               # table uint32 [transcripts][9][n_rep] of the host shards
+        self.dev = {}                  # device -> dict(table, status)
+        self.counts = self.lof = None
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        self.conseq._check(k)
+        features = self.struct.features.get(name)
+        if features is None:
+            return 0
+        n_tx = len(self.conseq.names)
+        if self.host is None:
+            self.host = np.zeros((n_tx, TX_BINS, self.n_rep), np.uint32)
+        return simulate_txstruct_host(self.conseq.genome(name), prob, start, strand, self.conseq.segments.get(name), features, n_tx,
+                                      simulate_chrom_key(name), self.seed, self.n_rep, self.conseq.meta["aa"], self.conseq.alt_order,
+                                      into=self.host)[1]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the draws of a part behind its structure reduction, into the device's one table."""
+        self.conseq._check(k)
+        if self.struct.features.get(name) is None or start.shape[0] == 0:
+            return None
+        dev, n_tx = prob.device, len(self.conseq.names)
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(max(n_tx * TX_BINS * self.n_rep, 1), dtype=torch.int32, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev))
+        genome = self.conseq.genome(name)
+        items = self.struct.dev[dev]
+        simulate_txstruct_rows_device(acc["table"], acc["status"], items, self.conseq.dev.get(dev, items["no_cds"]), name, n_tx,
+                                      self.conseq.meta["aa"], self.conseq.alt_order, genome.as_struct(dev), dev, self.n_rep, self.seed,
+                                      prob=prob.data_ptr(), prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0),
+                                      start=start.data_ptr(), strand=strand.data_ptr(), n=start.shape[0])
+        return genome
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, table, n_tx = 0, self.host, len(self.conseq.names)
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine = acc["table"].cpu().numpy().view(np.uint32)[:n_tx * TX_BINS * self.n_rep].reshape(n_tx, TX_BINS, self.n_rep)
+            table = mine if table is None else table + mine      # (the copy the device gave is this call's own)
+        return table, status
+
+    def merge(self, states, k):
+        return self.conseq_sim.merge(states, k)
+
+    def finish(self, state, k, result):
+        n_tx = len(self.conseq.names)
+        self.counts = np.zeros((n_tx, TX_BINS, self.n_rep), np.uint32) if state is None else state
+        self.lof = simulate_lof_counts(self.conseq_sim.counts, self.counts)
+        names, table, _ = result["transcript_structure"]
+        expected, observed = structure_cells_from_sums(table, self.conseq.sums[0][:, 2])
+        result[self.name] = (names, self.counts, self.lof, observed if self.conseq.labels else None, expected)
+
+    def write(self, out_prefix, result, k, written):
+        written.append(structure_simulation_output_name(out_prefix))
+        write_structure_simulation_outputs(*result[self.name], out_prefix)
+
+
 class _CalibrationReducer:
     """The integer tables behind NLL / ECE / classwise ECE / Brier per chromosome and, with `fit_calibrator`, the retained rows and the
     calibrator fit on them at close()."""
@@ -2101,6 +2273,18 @@ class SummarySink:
     and added across ranks in the same collective.  result()["transcript_structure"] = (names, table uint64 [n][9][3], rows uint64
     [n][2]); close() writes ``{out_prefix}.consequence.structure.tsv`` (``tables.write_structure_outputs``: the nine bins and
     expected_lof / observed_lof = stop gained + splice donor + splice acceptor + start lost); ``structure_sums()`` has the integers.
+    `simulate_structure=True` (opt-in; with `simulate` and `simulate_seed`, `transcript_structure=True` and
+    `simulate_transcripts=True`, ValueError naming what is missing otherwise): the null distribution of the structure table's
+    observed_* columns and of observed_lof -- per transcript, structure bin and replicate the rows inside the span whose draw is a
+    class that falls in that bin (``simulate_txstruct_host`` is the rule), device parts through
+    ``mural_simulate_txstruct_rows`` (csrc/simulate_txstruct.hip) on the item and segment arrays the two reductions before it
+    uploaded, one uint32 table [transcripts][9][R] (checked against `simulate_table_bytes_max` on its own) read back once and added
+    across ranks in the same collective.  The LoF count of replicate r adds the stop-gained count of the consequence simulation and
+    the donor, acceptor and start-lost counts of this table, all of the same draw (``simulate_lof_counts``).
+    result()["structure_simulation"] = (names, counts [transcripts][9][R], lof [transcripts][R], observed [transcripts][10] or None,
+    expected [transcripts][10]), the last two the structure file's own numbers, LoF last; close() writes
+    ``{out_prefix}.consequence.structure.sim.tsv`` (``tables.write_structure_simulation_outputs``);
+    ``structure_simulation_counts()`` has the table.
 
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
@@ -2111,7 +2295,8 @@ class SummarySink:
                  group=None, parts=False, kmers=(), genome=None, kmer_strand=None, motifs=(), motif_indel=False, calibration=False,
                  calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
                  simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True, transcripts=None,
-                 codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False, transcript_structure=False):
+                 codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False, transcript_structure=False,
+                 simulate_structure=False):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -2134,6 +2319,13 @@ class SummarySink:
         if self.annotations:
             active.append(_AnnotationReducer(annotations))
         self.simulate = simulate is not None
+        if simulate_structure:      # opt-in, and only on top of the three it builds on
+            missing = [what for what, on in (("simulate=R with simulate_seed", simulate is not None and simulate_seed is not None),
+                                             ("transcript_structure=True (the item arrays)", transcript_structure and transcripts is not None),
+                                             ("simulate_transcripts=True (the stop-gained counts of the same draws)",
+                                              simulate_transcripts and transcripts is not None)) if not on]
+            if missing:
+                raise ValueError("simulate_structure needs " + ", ".join(missing))
         if self.simulate:
             if simulate_seed is None:
                 raise ValueError("simulate needs simulate_seed: there is no default randomness")
@@ -2160,6 +2352,8 @@ class SummarySink:
                 active.append(_ConsequenceSimulationReducer(simulate, simulate_seed, by_tx, simulate_table_bytes_max))
             if features is not None:                        # behind it as well
                 active.append(_StructureReducer(features, by_tx))
+            if simulate_structure:                          # behind both: the item arrays, and the stop-gained counts of the same draws
+                active.append(_StructureSimulationReducer(simulate, simulate_seed, active[-1], active[-2], simulate_table_bytes_max))
         elif codon_table is not None or alt_order is not None:
             raise ValueError("codon_table and alt_order go with transcripts=")
         if simulate_transcripts and not self.transcripts:
@@ -2337,6 +2531,12 @@ class SummarySink:
         mis, 2 stop gained, 3 stop lost, 4 unresolved) and replicate (``simulate_conseq_host``'s layout, the transcripts in file order)."""
         self.result()
         return self._reducers["consequence_simulation"].counts
+
+    def structure_simulation_counts(self):
+        """table uint32 [transcripts][9][simulate] after close(): the simulated count of every transcript, structure bin of
+        ``tables.STRUCTURE_BINS`` and replicate (``simulate_txstruct_host``'s layout, the transcripts in file order)."""
+        self.result()
+        return self._reducers["structure_simulation"].counts
 
     def calibration_sums(self):
         """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind

@@ -981,6 +981,32 @@ def _structure_acc(n_tx, dev):
                 conseq=dict(table=zeros(max(n_tx, 1) * 15), rows=zeros(max(n_tx, 1) * 2), status=zeros(1, torch.int32), segments={}, ws=None))
 
 
+def _structure_cells(cells, stop_gained):
+    """The ten [count, hi, lo] cells of a transcript as Python integers: its nine bins and LoF = stop gained + splice donor + splice
+    acceptor + start lost, added word by word."""
+    return cells + [[sum(c[w] for c in (stop_gained, cells[3], cells[4], cells[7])) for w in range(3)]]
+
+
+def structure_cells_from_sums(table, stop_gained):
+    """(expected float64 [n][10], observed int64 [n][10]) of the nine bins of ``STRUCTURE_BINS`` and LoF from the integer sums
+    ``write_structure_outputs`` takes: the numbers of its expected_* and observed_* columns.  Where every limb is below 2^51 -- any
+    real run -- the LoF words are added as uint64 without overflow, hi and lo are exact in float64 and hi * 2^40 + lo is ONE float64
+    addition of two exact terms: rounded correctly, as the writer's true division of Python integers is, and the scaling by 2^-71 is
+    exact; the same numbers without a walk over the cells.  Otherwise the writer's own arithmetic, cell by cell."""
+    table = np.asarray(table, np.uint64).reshape(-1, 9, 3)
+    stop_gained = np.asarray(stop_gained, np.uint64).reshape(len(table), 3)
+    limit = np.uint64(1 << 51)
+    if (table < limit).all() and (stop_gained < limit).all():
+        full = np.concatenate([table, (stop_gained + table[:, 3] + table[:, 4] + table[:, 7])[:, None, :]], axis=1)
+        expected = (full[:, :, 1].astype(np.float64) * 2.0 ** 40 + full[:, :, 2].astype(np.float64)) * 2.0 ** -71
+        return expected, full[:, :, 0].astype(np.int64)
+    den = 1 << 71
+    cells = [_structure_cells(c, s) for c, s in zip(table.tolist(), stop_gained.tolist())]
+    expected = np.array([[((hi << 40) + lo) / den for _, hi, lo in c] for c in cells], np.float64).reshape(len(table), 10)
+    observed = np.array([[count for count, _, _ in c] for c in cells], np.int64).reshape(len(table), 10)
+    return expected, observed
+
+
 def write_structure_outputs(names, meta, table, rows, stop_gained, out_prefix, labels=True):
     """``{out_prefix}.consequence.structure.tsv`` from the integer sums of ``summary_txstruct_host`` / ``mural_summary_txstruct_rows``
     (table uint64 [n][9][3], rows uint64 [n][2]) and `stop_gained` uint64 [n][3], bin 2 of the consequence table's own integers: a line
@@ -996,8 +1022,8 @@ def write_structure_outputs(names, meta, table, rows, stop_gained, out_prefix, l
         header += [f"expected_{what}", f"observed_{what}"]
     den, lines = 1 << 71, []
     for j, nm in enumerate(names):
-        cells = table[j] + [[sum(c[w] for c in (stop_gained[j], table[j][3], table[j][4], table[j][7])) for w in range(3)]]
-        line = [nm, meta["chrom"][j], "-" if meta["strand"][j] else "+", str(rows[j][0]), str(rows[j][1])]
+        cells = _structure_cells(table[j], stop_gained[j])
+        line =[nm, meta["chrom"][j], "-" if meta["strand"][j] else "+", str(rows[j][0]), str(rows[j][1])]
         for count, hi, lo in cells:
             line += [_float_text(((hi << 40) + lo) / den), str(count) if labels else "NA"]
         lines.append(line)
@@ -1288,6 +1314,106 @@ def run_simulate_consequence_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
                                                                    args.simulate, args.seed, getattr(args, "codon_table", None),
                                                                    getattr(args, "alt_order", None), True, chunk_bytes)
     return write_consequence_simulation_outputs(names, counts, observed, expected, args.out_prefix)
+
+
+def structure_simulation_output_name(out_prefix):
+    return f"{out_prefix}.consequence.structure.sim.tsv"
+
+
+def write_structure_simulation_outputs(names, counts, lof, observed, expected, out_prefix):
+    """``{out_prefix}.consequence.structure.sim.tsv``: one line per transcript and row of ``STRUCTURE_BINS`` + ("lof",) -- name, bin,
+    observed, expected, sim_mean, sim_min, sim_max, n_ge, n_le, p_upper, p_lower (``summaries.simulate_pvalues``) -- from counts
+    [transcripts][9][R], lof [transcripts][R] (``summaries.simulate_lof_counts``), observed [transcripts][10] (None: no labels, 'NA' in
+    the observed column and the last four) and expected [transcripts][10]: the structure file's own numbers
+    (``structure_cells_from_sums``), LoF last.  Returns the path."""
+    from .summaries import simulate_pvalues      # (summaries imports this module: not at the top)
+    header = ["name", "bin", "observed", "expected", "sim_mean", "sim_min", "sim_max", "n_ge", "n_le", "p_upper", "p_lower"]
+    counts = np.asarray(counts).reshape(len(names), 9, -1)
+    lof = np.asarray(lof).reshape(len(names), -1)
+    what_all = STRUCTURE_BINS + ("lof",)
+    stats = [simulate_pvalues(counts[:, b] if b < 9 else lof, None if observed is None else np.asarray(observed)[:, b])
+             for b in range(len(what_all))]
+    rows = []
+    for j, nm in enumerate(names):
+        for b, what in enumerate(what_all):
+            mean, lo, hi, n_ge, n_le, p_up, p_lo = stats[b][j]
+            obs = "NA" if observed is None else str(int(observed[j][b]))
+            tail = ["NA"] * 4 if observed is None else [str(n_ge), str(n_le), _float_text(p_up), _float_text(p_lo)]
+            rows.append([nm, what, obs, _float_text(expected[j][b]), _float_text(mean), str(lo), str(hi)] + tail)
+    path = structure_simulation_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    return path
+
+
+def simulate_structure_table(pred_file, transcripts, ref_genome, n_rep, seed, codon_table=None, alt_order=None, labels=True,
+                             chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, counts uint32 [transcripts][9][n_rep], lof int64 [transcripts][n_rep], observed [transcripts][10] or None, expected
+    [transcripts][10]) from a written SNV prediction table (4 classes): what ``SummarySink(simulate=n_rep, simulate_seed=seed,
+    transcripts=..., transcript_structure=True, simulate_transcripts=True, simulate_structure=True)`` reduces in flight, through the
+    same entries (``mural_simulate_txstruct_rows`` beside ``mural_summary_conseq_rows``, ``mural_simulate_conseq_rows`` and
+    ``mural_summary_txstruct_rows``), chromosome run by chromosome run of each chunk; the draws are made from the table's four-digit
+    probabilities.  observed and expected are the structure table's numbers, LoF last; `labels=False`: observed is None."""
+    from .data.ingest import read_fasta, scan_fasta
+    from .summaries import (_SUMMARY_STATUS, SIMULATE_MAX_REPLICATES, conseq_rows_device,      # (summaries imports this module)
+                            simulate_conseq_rows_device, simulate_lof_counts, simulate_txstruct_rows_device, txstruct_rows_device)
+    n_rep, seed = int(n_rep), int(seed)
+    if not 1 <= n_rep <= SIMULATE_MAX_REPLICATES or not 0 <= seed < 1 << 64:
+        raise ValueError("simulate_structure_table: 1 .. 2^20 replicates and an unsigned 64-bit seed")
+    names, meta, segments, features = read_transcript_structure(transcripts, codon_table)
+    alt = check_alt_order(alt_order)
+    n_tx = len(names)
+    fasta_names = {r.name for r in scan_fasta(ref_genome)}
+    with TableReader(pred_file, 4, chunk_bytes) as rd:
+        dev = rd.device
+        acc = _structure_acc(n_tx, dev)
+        sim_conseq = torch.zeros(max(n_tx * 5 * n_rep, 1), dtype=torch.int32, device=dev)
+        sim = torch.zeros(max(n_tx * 9 * n_rep, 1), dtype=torch.int32, device=dev)
+        genomes = {}
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in features or b == a:
+                    continue
+                if name not in genomes:
+                    if name not in fasta_names:
+                        raise ValueError(f"Chromosome {name} not found in {ref_genome} (prediction table line {c.row0 + a + 2})")
+                    genomes[name] = read_fasta(ref_genome, dev, names={name})[name]
+                genome = genomes[name].as_struct()
+                part = dict(prob=c.prob + 8 * 4 * a, prob_f64=1, prob_stride=4, start=c.start + 8 * a, strand=c.strand + a, n=b - a)
+                labelled = dict(label=c.mut_type + 4 * a, label_kind=1, **part)
+                if name in segments:
+                    conseq_rows_device(acc["conseq"], name, segments[name], n_tx, meta["aa"], alt, genome, dev, **labelled)
+                    simulate_conseq_rows_device(sim_conseq, acc["status"], acc["conseq"], name, n_tx, meta["aa"], alt, genome, dev, n_rep,
+                                                seed, **part)
+                txstruct_rows_device(acc, acc["conseq"], name, segments.get(name), features[name], n_tx, meta["aa"], alt, genome, dev,
+                                     **labelled)
+                simulate_txstruct_rows_device(sim, acc["status"], acc, acc["conseq"], name, n_tx, meta["aa"], alt, genome, dev, n_rep, seed,
+                                              **part)
+        bits = int(acc["status"].item()) | int(acc["conseq"]["status"].item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table = acc["table"].cpu().numpy().view(np.uint64)[:n_tx * 27].reshape(n_tx, 9, 3)
+        stop_gained = acc["conseq"]["table"].cpu().numpy().view(np.uint64)[:n_tx * 15].reshape(n_tx, 5, 3)[:, 2].copy()
+        sim_conseq = sim_conseq.cpu().numpy().view(np.uint32)[:n_tx * 5 * n_rep].reshape(n_tx, 5, n_rep)
+        sim = sim.cpu().numpy().view(np.uint32)[:n_tx * 9 * n_rep].reshape(n_tx, 9, n_rep)
+    expected, observed = structure_cells_from_sums(table, stop_gained)
+    return names, sim, simulate_lof_counts(sim_conseq, sim), (observed if labels else None), expected
+
+
+def run_simulate_structure_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.transcripts, args.ref_genome, args.simulate, args.seed, args.out_prefix;
+    optional args.codon_table, args.alt_order): the simulated counts per transcript, structure bin and LoF from the table's rows;
+    writes {out_prefix}.consequence.structure.sim.tsv."""
+    assert getattr(args, "transcripts", None) is not None, "--transcripts is required for the structure simulation"
+    assert getattr(args, "ref_genome", None) is not None, "--ref_genome is required for the structure simulation"
+    assert getattr(args, "seed", None) is not None, "--seed is required with --simulate: there is no default randomness"
+    result = simulate_structure_table(os.fspath(args.pred_file), args.transcripts, os.fspath(args.ref_genome), args.simulate, args.seed,
+                                      getattr(args, "codon_table", None), getattr(args, "alt_order", None), True, chunk_bytes)
+    return write_structure_simulation_outputs(*result, args.out_prefix)
 
 
 # ------------------------------------------------------------------------------------------------------------------

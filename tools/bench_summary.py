@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Eighteen legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Twenty-one legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -33,6 +33,9 @@ alternating, --repeats timed runs each after one warm-up run each:
   r  conseq_sim1000 leg o with simulate=1000 (a table of 400 MB, below the sink's cap)
   s  conseq_struct  leg o with transcript_structure=True as well: the structure table of the same transcripts --
                   their exons and the coding introns between them --; the comparison is leg o, the same run without it
+  t  struct_sim100  leg s with simulate=100, simulate_seed=1, simulate_transcripts=True, simulate_structure=True as well (DESIGN.md section
+                  3.24): the counts of 100 mutation sets per transcript, structure bin and LoF; the comparisons are leg s and leg q
+  u  struct_sim1000 leg s with simulate=1000 (tables of 720 MB and 400 MB, each below the sink's cap)
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
 h's, leg k's annotation table with leg l's and leg o's consequence table with leg p's, within the table's four digits (names, order and
 counts exactly)."""
@@ -58,9 +61,10 @@ WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
 LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000",
-        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct")
+        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct", "struct_sim100", "struct_sim1000")
 SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
 CONSEQ_SIM_REPLICATES = {"conseq_sim100": 100, "conseq_sim1000": 1000}
+STRUCT_SIM_REPLICATES = {"struct_sim100": 100, "struct_sim1000": 1000}
 ANNOT_NAMES, ANNOT_INTERVALS, ANNOT_BP, ANNOT_OVERLAP = 20_000, 10, 150, 0.05
 
 
@@ -115,7 +119,7 @@ def main(argv):
 
         transcripts = synthetic_transcripts(bases) if {"conseq", "conseq_tools", *CONSEQ_SIM_REPLICATES} & set(legs) else None
 
-        structure = synthetic_transcripts(bases, structure=True) if "conseq_struct" in legs else None
+        structure = synthetic_transcripts(bases, structure=True) if {"conseq_struct", *STRUCT_SIM_REPLICATES} & set(legs) else None
 
         def run(leg):
             split, extra = {}, {}
@@ -138,10 +142,14 @@ def main(argv):
             if leg == "conseq_struct":
                 summary = SummarySink(windows=WINDOWS, transcripts=structure, genome=fwd.genome, transcript_labels=False,
                                       transcript_structure=True)
+            if leg in STRUCT_SIM_REPLICATES:
+                summary = SummarySink(windows=WINDOWS, transcripts=structure, genome=fwd.genome, transcript_labels=False,
+                                      transcript_structure=True, simulate=STRUCT_SIM_REPLICATES[leg], simulate_seed=1,
+                                      simulate_transcripts=True, simulate_structure=True)
             if leg in CONSEQ_SIM_REPLICATES:
                 summary = SummarySink(windows=WINDOWS, transcripts=transcripts, genome=fwd.genome, transcript_labels=False,
                                       simulate=CONSEQ_SIM_REPLICATES[leg], simulate_seed=1, simulate_transcripts=True)
-            if leg in ("summary", "annot", "sim100", "sim1000", "conseq", "conseq_struct", *CONSEQ_SIM_REPLICATES) and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
+            if leg in ("summary", "annot", "sim100", "sim1000", "conseq", "conseq_struct", *CONSEQ_SIM_REPLICATES, *STRUCT_SIM_REPLICATES) and {"annot", "conseq"} & set(legs):      # close() alone, of every run: where leg k's host work would be
                 plain_close = summary.close
 
                 def close_timed():
@@ -168,7 +176,8 @@ def main(argv):
                     "tee": lambda: TeeSink(TsvSink(out), summary), "kmer_tools": lambda: TsvSink(out), "motifs": lambda: summary,
                     "motif_tools": lambda: TsvSink(out), "annot": lambda: summary, "annot_tools": lambda: TsvSink(out), "sim100": lambda: summary,
                     "sim1000": lambda: summary, "conseq": lambda: summary, "conseq_tools": lambda: TsvSink(out),
-                    "conseq_sim100": lambda: summary, "conseq_sim1000": lambda: summary, "conseq_struct": lambda: summary}[leg]()
+                    "conseq_sim100": lambda: summary, "conseq_sim1000": lambda: summary, "conseq_struct": lambda: summary,
+                    "struct_sim100": lambda: summary, "struct_sim1000": lambda: summary}[leg]()
             n = predict_regions_sharded(fwd, "chr1", "A", sink=sink, collect=False, timings=split,
                                         **(dict(mutations=mutations) if leg == "calib_fit" else {}))
             torch.cuda.synchronize()
@@ -248,6 +257,10 @@ def main(argv):
         (na, _, ta), (ns, _, ts) = kept["conseq"]["consequences"], kept["conseq_struct"]["consequences"]
         struct = kept["conseq_struct"]["transcript_structure"][1]
         agree = agree and na == ns and bool((ta == ts).all()) and bool((struct[:, 7:9, 0].sum(axis=1) == ta[:, [2, 4, 6, 8, 10]].sum(axis=1)).all())
+    for leg in STRUCT_SIM_REPLICATES:      # bins 7 + 8 of the structure draws are the five bins of the consequence draws, replicate by replicate
+        if leg in kept:
+            sim, conseq_sim = kept[leg]["structure_simulation"][1], kept[leg]["consequence_simulation"][1]
+            agree = agree and bool((sim[:, 7].astype("int64") + sim[:, 8] == conseq_sim.astype("int64").sum(axis=1)).all()) and bool(sim.any())
     rate = {leg: spread([rows / s for s in seconds[leg]]) for leg in legs}
     med = {leg: rate[leg]["median"] for leg in legs}
     sec = {leg: statistics.median(seconds[leg]) for leg in legs}
@@ -269,6 +282,12 @@ def main(argv):
                             "expected": kept["conseq"]["consequences"][2][:, 3:11:2].sum(axis=0).tolist() if "conseq" in kept else None},
            "conseq_sim100_over_conseq": ratio("conseq_sim100", "conseq", med), "conseq_sim1000_over_conseq": ratio("conseq_sim1000", "conseq", med),
            "conseq_struct_over_conseq": ratio("conseq_struct", "conseq", med),
+           "struct_sim100_over_conseq_struct": ratio("struct_sim100", "conseq_struct", med),
+           "struct_sim1000_over_conseq_struct": ratio("struct_sim1000", "conseq_struct", med),
+           "struct_sim100_over_conseq_sim100": ratio("struct_sim100", "conseq_sim100", med),
+           "struct_sim1000_over_conseq_sim1000": ratio("struct_sim1000", "conseq_sim1000", med),
+           "simulated_structure_draws": {leg: float(kept[leg]["structure_simulation"][1].sum()) for leg in STRUCT_SIM_REPLICATES if leg in kept},
+           "simulated_lof": {leg: float(kept[leg]["structure_simulation"][2].sum()) for leg in STRUCT_SIM_REPLICATES if leg in kept},
            "structure_rows": kept["conseq_struct"]["transcript_structure"][2][:, 0].sum().item() if "conseq_struct" in kept else None,
            "simulated_consequence_draws": {leg: float(kept[leg]["consequence_simulation"][1].sum()) for leg in CONSEQ_SIM_REPLICATES if leg in kept},
            "simulated_draws": {leg: float(kept[leg]["simulation"][1].sum()) for leg in SIM_REPLICATES if leg in kept},

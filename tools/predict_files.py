@@ -73,6 +73,13 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              of CDS codon 0: BED12 carries no frame, ATG is not demanded) and cds, and
                                                              expected_lof / observed_lof = stop gained + splice donor + splice acceptor
                                                              + start lost
+  --summary PREFIX  --transcripts BED12 --transcript_structure --simulate R --seed S --simulate_consequences --simulate_structure
+                                                             PREFIX.consequence.structure.sim.tsv as well: per transcript, structure bin
+                                                             and lof the observed and expected counts of the structure file beside the
+                                                             mean, minimum and maximum of the R simulated counts, n_ge / n_le and the
+                                                             empirical p-values (n + 1) / (R + 1); the lof count of a replicate adds the
+                                                             stop-gained, splice and start-lost events of the same draw; it needs every
+                                                             flag named here; not with --indel
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -179,7 +186,18 @@ def _summary_options(flags, values, model_type="snv"):
             "simulate": one("--simulate", int), "seed": one("--seed", lambda v: int(v, 0)),
             "write_simulated": tuple(int(r) for r in values.get("--write_simulated", [])), "transcripts": one("--transcripts", str),
             "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str),
-            "simulate_consequences": "--simulate_consequences" in flags, "transcript_structure": "--transcript_structure" in flags}
+            "simulate_consequences": "--simulate_consequences" in flags, "transcript_structure": "--transcript_structure" in flags,
+            "simulate_structure": "--simulate_structure" in flags}
+    if opts["simulate_structure"] and model_type == "indel":
+        raise SystemExit("--simulate_structure takes SNV rows: it does not go with --indel")
+    if opts["simulate_structure"] and opts["transcripts"] is None:
+        raise SystemExit("--simulate_structure needs --transcripts BED12: the transcripts whose structure counts it simulates")
+    if opts["simulate_structure"] and not opts["transcript_structure"]:
+        raise SystemExit("--simulate_structure needs --transcript_structure: the structure table whose counts it simulates")
+    if opts["simulate_structure"] and opts["simulate"] is None:
+        raise SystemExit("--simulate_structure needs --simulate R --seed S: the replicates it counts")
+    if opts["simulate_structure"] and not opts["simulate_consequences"]:
+        raise SystemExit("--simulate_structure needs --simulate_consequences: the stop-gained counts of the same draws complete the lof count")
     if opts["transcript_structure"] and opts["transcripts"] is None:
         raise SystemExit("--transcript_structure needs --transcripts BED12: the transcripts whose UTRs, introns and splice sites it bins")
     if opts["transcript_structure"] and model_type == "indel":
@@ -304,7 +322,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               annotations=opts["annotations"], simulate=opts["simulate"], simulate_seed=opts["seed"],
                               simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), transcripts=opts["transcripts"], alt_order=opts["alt_order"],
                               transcript_labels=opts.get("labelled", True), simulate_transcripts=opts["simulate_consequences"],
-                              transcript_structure=opts["transcript_structure"], **sink_chain)
+                              transcript_structure=opts["transcript_structure"], simulate_structure=opts["simulate_structure"],
+                              **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
