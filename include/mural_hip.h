@@ -989,6 +989,89 @@ size_t mural_summary_txstruct_workspace_bytes(int64_t n_features);
 int mural_summary_txstruct_rows(const MuralSummaryTxstructRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Expected and observed INDEL events per transcript by what they do to the transcript's structure
+ * (SummarySink(indel_transcripts=...) in flight, tables.indel_structure_table from a written table;
+ * csrc/summary_txindel.hip; mural_amd.summaries.summary_txindel_host is the specification).  One call takes the INDEL rows
+ * (2 <= n_class <= 16) of a part of ONE chromosome, ascending in start (equal starts are legal); the limbs, the tables'
+ * layout and the status bits are those of mural_summary_conseq_rows, bit 1 a label outside 0 .. n_class - 1.  Class 0's
+ * probability, the rows' strand and the genome are never read: an INDEL event is a reference-strand fact.  The items, the
+ * segments and the transcripts are those of mural_summary_txstruct_rows (seg_prev / seg_next are not needed); feat_prev /
+ * feat_next [n_features] are the same transcript's neighbouring items in genomic order, -1 at the span's ends
+ * (tables.structure_links).
+ *   kind: 0 insertion, 1 deletion start, 2 deletion end -- of the whole call, as there is one model per kind.
+ *   breakpoint_offset: 0 or 1; the event's boundary is j = start + breakpoint_offset, between 0-based bases j - 1 and j.
+ *   class_len[c] = { lo, hi } for c >= 1, 1 <= lo <= hi <= 64 (MURAL_E_INVALID otherwise): the lengths class c stands for.
+ *     A class is FRAMED when lo == hi, MIXED when its range holds a multiple of 3 and another length; any other range
+ *     (1-2, 4-5) shifts the frame whatever its length.  A deletion of class c is located by its L = lo bases.
+ *   The home base h is j - 1 for an insertion and a deletion end, j for a deletion start.  A row counts for every
+ *   transcript whose span holds h (an insertion: and j), once, through the item that holds h.  The 10 bins: 0 utr5, 1 utr3,
+ *   2 noncoding_exon, 3 splice, 4 splice_utr, 5 intron, 6 start_lost, 7 frameshift, 8 inframe, 9 cds_mixed.
+ *   x(j) is the number of CDS bases 5' of boundary j in transcript orientation: seg_cds0 + (j - seg_b0) on '+', seg_cds0 +
+ *   (seg_b1 - j) on '-'.  The FRAME BIN of class c with n CDS bases affected: 9 for a mixed class, 7 for a range that always
+ *   shifts, and for a framed class 7 where n % 3 != 0, else 8.  The CDS RULE at boundary j: x == 0 gives bin 0, x ==
+ *   tx_cds_len bin 1, x <= 2 bin 6 for every class, otherwise the frame bin with n = lo.
+ *   Insertion, A the item of base j - 1 and B that of base j.  A == B: kinds 0, 1, 2 give bins 0, 1, 2; in a gap of 4 or more
+ *   bases j == a + 1 or j == b - 1 splits a splice dinucleotide -- bin 3 in a coding intron (kind 3), bin 4 in any other gap
+ *   (kind 4) --, every other gap position is bin 5; a CDS part follows the CDS rule.  A != B: a gap yields to an exon part
+ *   (the inserted bases extend the exon); where one of the two is a CDS part it decides by the CDS rule (A first); two other
+ *   exon parts have one kind.
+ *   Deletion: the deleted bases are D = [j, j + L) (deletion start) or [j - L, j) (deletion end), clipped to the
+ *   transcript's span and, where chrom_length >= 0, to [0, chrom_length) (the home base stays).  Over the items that meet D,
+ *   reached from the home item over feat_next / feat_prev: n_cds = the CDS bases in D; touch_start = a CDS base of offset < 3
+ *   is in D; touch_splice = one of the first two or last two bases of a coding intron of 4 or more bases is in D;
+ *   touch_splice_utr = the same for a kind-4 gap.  The first that holds decides: touch_start bin 6; touch_splice bin 3; n_cds
+ *   > 0 the frame bin with n = n_cds; touch_splice_utr bin 4; a kind-2 base bin 2; a kind-0 base bin 0; a kind-1 base bin 1;
+ *   otherwise bin 5.  A link that is out of range, names another transcript, an item that is empty, of an unknown kind, a
+ *   CDS part without its segment or that does not abut the item before it ends the walk (a home item of that sort is
+ *   skipped, and so is an insertion whose B is one): nothing is read out of bounds and a walk has at most 64 steps.
+ *   table [n_transcripts][10][3] += { 1 where label[i] == c, hi of prob[i][c], lo of prob[i][c] } per (row, c >= 1) routed to
+ *     bin b; on return lo < 2^40;  rows [n_transcripts][2] += { rows counted, rows of label 0 among them }.  Both are a
+ *     function of the SET of rows alone, bit for bit.
+ * Chunks of at most mural_summary_txindel_chunk_rows() rows of one home item, a scan workgroup of
+ * mural_summary_txindel_scan_threads() threads, a grid of at most mural_summary_txindel_grid_waves() waves.  n <= 2^31 and
+ * n_features <= 2^22 per call (MURAL_E_INVALID above: a row adds at most n_class - 1 <= 15 limbs to a cell, a wave folds
+ * its chunk's sum before it adds, and a cell takes at most n / chunk_rows + n_features folded terms in a call, which keeps
+ * its lo limb below 2^63 until the fold that ends the call).  ws: mural_summary_txindel_workspace_bytes(n_features) bytes (24
+ * per item), 8-byte aligned; MURAL_E_WORKSPACE when smaller.  n == 0 or n_features == 0 launches nothing.  Launches on
+ * `stream`, no synchronisation, no read-back, no floating-point atomics.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. n_class - 1 are read        */
+  int32_t prob_f64, label_kind;                     /* label: 0 float32, 1 int32, 2 int64                                       */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const void* label;         /* dev [n] */
+  int64_t n;
+  int32_t n_class, n_transcripts;
+  int32_t kind, breakpoint_offset;
+  int64_t chrom_length;      /* or -1: not known */
+  int32_t class_len[16][2];  /* [c] = { lo, hi }, c >= 1 */
+  const int64_t* seg_b0;     /* dev [n_segments] */
+  const int64_t* seg_b1;     /* dev [n_segments] */
+  const int64_t* seg_cds0;   /* dev [n_segments] */
+  const int32_t* seg_tx;     /* dev [n_segments] */
+  int64_t n_segments;
+  const uint8_t* tx_strand;  /* dev [n_transcripts] */
+  const int64_t* tx_cds_len; /* dev [n_transcripts] */
+  uint64_t* table;           /* dev [n_transcripts][10][3] */
+  uint64_t* rows;            /* dev [n_transcripts][2] */
+  int32_t* status;           /* dev [1] */
+  const int64_t* feat_b0;    /* dev [n_features] */
+  const int64_t* feat_b1;    /* dev [n_features] */
+  const int32_t* feat_tx;    /* dev [n_features] */
+  const uint8_t* feat_kind;  /* dev [n_features] */
+  const int32_t* feat_seg;   /* dev [n_features] */
+  const int32_t* feat_prev;  /* dev [n_features] */
+  const int32_t* feat_next;  /* dev [n_features] */
+  int64_t n_features;
+} MuralSummaryTxindelRows;
+int64_t mural_summary_txindel_chunk_rows(void);
+int64_t mural_summary_txindel_grid_waves(void);
+int32_t mural_summary_txindel_scan_threads(void);
+size_t mural_summary_txindel_workspace_bytes(int64_t n_features);
+int mural_summary_txindel_rows(const MuralSummaryTxindelRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Mutation sets drawn from the rates of a shard while it is on the device (SummarySink(simulate=R, ...) in flight,
  * tables.simulate_table from a written table; csrc/simulate.hip).  The draw is stateless and integer
  * (mural_amd.summaries.simulate_rows_host is its specification): Philox4x32-10 with key (seed lo, seed hi) and counter

@@ -160,6 +160,16 @@ class MuralSimulateConseqRows(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class MuralSummaryTxindelRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("label_kind", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
+                ("label", C.c_void_p), ("n", C.c_int64), ("n_class", C.c_int32), ("n_transcripts", C.c_int32), ("kind", C.c_int32),
+                ("breakpoint_offset", C.c_int32), ("chrom_length", C.c_int64), ("class_len", (C.c_int32 * 2) * 16),
+                ("seg_b0", C.c_void_p), ("seg_b1", C.c_void_p), ("seg_cds0", C.c_void_p), ("seg_tx", C.c_void_p), ("n_segments", C.c_int64),
+                ("tx_strand", C.c_void_p), ("tx_cds_len", C.c_void_p), ("table", C.c_void_p), ("rows", C.c_void_p), ("status", C.c_void_p),
+                ("feat_b0", C.c_void_p), ("feat_b1", C.c_void_p), ("feat_tx", C.c_void_p), ("feat_kind", C.c_void_p), ("feat_seg", C.c_void_p),
+                ("feat_prev", C.c_void_p), ("feat_next", C.c_void_p), ("n_features", C.c_int64)]
+
+
 class MuralSimulateTxstructRows(C.Structure):
     _fields_ = MuralSimulateConseqRows._fields_ + [("feat_b0", C.c_void_p), ("feat_b1", C.c_void_p), ("feat_tx", C.c_void_p),
                                                    ("feat_kind", C.c_void_p), ("feat_seg", C.c_void_p), ("n_features", C.c_int64)]
@@ -338,6 +348,11 @@ PROTOTYPES = {
     "mural_summary_txstruct_scan_threads": (I32, []),
     "mural_summary_txstruct_workspace_bytes": (C.c_size_t, [I64]),
     "mural_summary_txstruct_rows": (C.c_int, [C.POINTER(MuralSummaryTxstructRows), VP, C.c_size_t, VP]),
+    "mural_summary_txindel_chunk_rows": (I64, []),
+    "mural_summary_txindel_grid_waves": (I64, []),
+    "mural_summary_txindel_scan_threads": (I32, []),
+    "mural_summary_txindel_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_summary_txindel_rows": (C.c_int, [C.POINTER(MuralSummaryTxindelRows), VP, C.c_size_t, VP]),
     "mural_simulate_chunk_rows": (I64, []),
     "mural_simulate_grid_waves": (I64, []),
     "mural_simulate_scan_threads": (I32, []),

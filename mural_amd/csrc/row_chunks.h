@@ -50,6 +50,27 @@ __global__ __launch_bounds__(THREADS) void row_chunk_range_kernel(const int64_t*
   }
 }
 
+// The same for csrc/summary_txindel.hip, whose rows belong to an item by start + shift (a row's home base is not its start).
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void row_chunk_range_shift_kernel(const int64_t* __restrict__ start, int64_t n,
+                                                                        const int64_t* __restrict__ b0, const int64_t* __restrict__ b1,
+                                                                        const int32_t* __restrict__ owner, int32_t n_owners, int64_t n_items,
+                                                                        int64_t shift, int64_t chunk_rows, RowChunks w) {
+  const int64_t p = (int64_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+  if (p >= n_items) return;
+  const int32_t g = owner[p];
+  const int64_t lo = b0[p], hi = b1[p];
+  int64_t i0 = 0, i1 = 0;
+  if (g >= 0 && g < n_owners && lo < hi) {
+    i0 = wave_partition_point(0, n, [&](int64_t i) { return start[i] + shift < lo; });
+    i1 = wave_partition_point(i0, n, [&](int64_t i) { return start[i] + shift < hi; });
+  }
+  if ((threadIdx.x & 63) == 0) {
+    w.row0[p] = i0, w.row1[p] = i1;
+    w.pre[p] = (i1 - i0 + chunk_rows - 1) / chunk_rows;
+  }
+}
+
 // the item of chunk t: the last p with pre[p] <= t (pre[n_items] = the total > t, so the point lies in 1 .. n_items); the whole wave
 __device__ __forceinline__ int64_t row_chunk_item(const int64_t* __restrict__ pre, int64_t n_items, int64_t t) {
   return wave_partition_point(0, n_items + 1, [&](int64_t q) { return pre[q] <= t; }) - 1;

@@ -1,0 +1,366 @@
+// Expected and observed INDEL events per transcript by what they do to the transcript's STRUCTURE while a prediction shard is on the
+// device (mural_amd/summaries.py: SummarySink(indel_transcripts=...); tables.indel_structure_table from a written table): per transcript
+// of a BED12 file the label counts and the sums of the probabilities of the INDEL rows whose home base lies inside [chromStart,
+// chromEnd), split into utr5, utr3, noncoding_exon, splice, splice_utr, intron, start_lost, frameshift, inframe and cds_mixed.
+// summaries.summary_txindel_host is the specification; DESIGN.md section 3.25.  No genome is read: nothing here depends on sequence.
+//
+// The items are those of csrc/summary_txstruct.hip (tables.read_transcript_structure) with two link arrays, feat_prev / feat_next, the
+// same transcript's neighbouring items in genomic order (tables.structure_links).  The stages are those of csrc/summary_txstruct.hip:
+//   * check kernel, a thread per row: the status bits;
+//   * range and scan kernels (row_chunks.h): an item's rows are those whose HOME BASE -- start + breakpoint_offset - 1 for an insertion
+//     and a deletion end, start + breakpoint_offset for a deletion start -- lies in it, cut into chunks of at most TI_CHUNK_ROWS rows;
+//   * reduce kernel, a grid of at most TI_GRID_WAVES waves striding over the chunks, a row per lane.  An insertion looks at the home
+//     item and, on its last boundary, at the item behind it (wave-uniform: loaded once per chunk).  A deletion of class c removes L =
+//     lo(c) <= 64 bases: the lane walks from the home item over feat_next (deletion start) or feat_prev (deletion end) while the items
+//     meet the deleted bases, one O(1) overlap per item; a link that is out of range, names another transcript or does not abut ends
+//     the walk, so every step moves on by at least one base and a walk has at most 64 steps.  A lane carries 10 bins x (hi | count <<
+//     48, lo); after the chunk 20 wave butterflies, the fold of lo into hi, and ONE wave-instruction of 64-bit INTEGER atomics over the
+//     transcript's 30 contiguous cells + its two row counters, zero words skipped;
+//   * fold kernel (summary_quant.h, with the limb bound): the table as [transcript * bin][3][1], at the end of every call.
+// Terms.  A lane adds at most n_class - 1 <= 15 limbs per row and TI_CHUNK_ROWS / 64 = 16 rows per chunk: 240 terms per lane (lo < 2^48,
+// hi < 2^39, count < 2^8 above bit 48) and 64 * 240 < 2^14 terms in a wave's sum before its fold (lo < 2^54, hi < 2^45, count < 2^14).
+// A chunk then adds one folded term to a cell; the items of one transcript are disjoint and a row has one home item per transcript,
+// so one call adds at most n / TI_CHUNK_ROWS + n_features chunks to a cell; the entry refuses n > 2^31 or n_features > 2^22: X <= 2^21
+// + 2^22 terms per call.  No per-row bin is stored; no floating-point atomics, no synchronisation, no read-back.
+#include "common.h"
+#include "kmer_key.h"
+#include "row_chunks.h"
+#include "summary_quant.h"
+
+namespace mural {
+namespace {
+
+constexpr int TI_THREADS = 256;
+constexpr int TI_WAVES = TI_THREADS / 64;
+constexpr int TI_SCAN_THREADS = 1024;
+constexpr int64_t TI_CHUNK_ROWS = 1024;           // rows of one unit of the reduce kernel: 16 tiles of 64
+constexpr int64_t TI_GRID_WAVES = 8192;           // waves of the reduce kernel's grid; they stride over the chunks
+constexpr int64_t TI_MAX_ROWS = 1ll << 31;        // per call (the fold bound above)
+constexpr int64_t TI_MAX_FEATURES = 1ll << 22;    // per call
+constexpr int TI_MAX_CLASS = 16;
+constexpr int TI_MAX_LEN = 64;
+constexpr int TI_BINS = 10;      // utr5, utr3, noncoding_exon, splice, splice_utr, intron, start_lost, frameshift, inframe, cds_mixed
+constexpr int TI_CELL_WORDS = 3 * TI_BINS;        // per transcript: [bin][label count | sum of hi | sum of lo]
+constexpr int TI_COUNT_SHIFT = 48;                // a lane's label count rides above its sum of hi limbs
+constexpr int TI_KIND_CODING_INTRON = 3, TI_KIND_INTRON = 4, TI_KIND_CDS = 5;
+constexpr int TI_INSERTION = 0, TI_DELETION_START = 1;      // (2: deletion end)
+constexpr int TI_FRAMED = 0, TI_MIXED = 1;                  // (2: a range without a multiple of 3 -- frameshift)
+constexpr int TI_FRAME = -1;                                // an insertion whose bin is its class's frame bin
+enum : uint32_t { TI_T_START = 1, TI_T_SPLICE = 2, TI_T_SPLICE_UTR = 4, TI_T_NONCODING = 8, TI_T_UTR5 = 16, TI_T_UTR3 = 32 };
+
+struct TxindelArgs {
+  const void* prob;
+  const int64_t* start;
+  const void* label;
+  int64_t prob_stride, n, chrom_len;      // chrom_len < 0: not known, a deletion is clipped to the span alone
+  int32_t label_kind, n_tx, n_class, kind, off;
+  const int64_t* seg_b0;
+  const int64_t* seg_b1;
+  const int64_t* seg_cds0;
+  const int32_t* seg_tx;
+  int64_t n_seg;
+  const int64_t* feat_b0;
+  const int64_t* feat_b1;
+  const int32_t* feat_tx;
+  const uint8_t* feat_kind;
+  const int32_t* feat_seg;
+  const int32_t* feat_prev;
+  const int32_t* feat_next;
+  int64_t n_feat;
+  const uint8_t* tx_strand;
+  const int64_t* tx_cds_len;
+  uint32_t cls[TI_MAX_CLASS];      // class c: lo | frame mode << 8
+  u64* table;
+  u64* rows;
+  int32_t* status;
+};
+
+// 0 <= p <= 1, summary_quant.h's test (quantise_prob returns it): on the bit pattern, so that NaN is caught whatever the compiler assumes
+__device__ __forceinline__ bool txindel_prob_ok(double p) {
+  const u64 bits = (u64)__double_as_longlong(p);
+  return !(bits > 0x3FF0000000000000ull && bits != 0x8000000000000000ull);
+}
+
+// The checks of row i (status bits, 0 if it counts); class 0's probability is not read.  Nothing is quantised here: the reduce kernel
+// quantises a class once, where it adds it.
+template <typename T>
+__device__ __forceinline__ int32_t txindel_row(const TxindelArgs& A, int64_t i, int& lab) {
+  const T* __restrict__ p_row = static_cast<const T*>(A.prob) + i * A.prob_stride;
+  lab = load_label(A.label, A.label_kind, i);
+  int32_t bad = 0;
+  if (A.start[i] < 0) bad |= SM_BAD_START;
+  if (lab < 0 || lab >= A.n_class) bad |= SM_BAD_LABEL;
+  for (int c = 1; c < A.n_class; ++c)
+    if (!txindel_prob_ok((double)p_row[c])) bad |= SM_BAD_PROB;      // (float -> double is exact)
+  return bad;
+}
+
+template <typename T>
+__global__ __launch_bounds__(TI_THREADS) void summary_txindel_check_kernel(TxindelArgs A) {
+  const int64_t i = (int64_t)blockIdx.x * TI_THREADS + threadIdx.x;
+  int32_t bad = 0;
+  if (i < A.n) {
+    int lab;
+    bad = txindel_row<T>(A, i, lab);
+    if (i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
+  }
+  if (bad) atomicOr(A.status, bad);
+}
+
+// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup
+__global__ __launch_bounds__(TI_SCAN_THREADS) void summary_txindel_scan_kernel(int64_t* __restrict__ v, int64_t m) {
+  const int64_t total = run_excl_scan<TI_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
+  if (threadIdx.x == 0) v[m] = total;
+}
+
+struct TiItem {
+  int64_t b0, b1, cds0;
+  int kind;
+  bool ok;
+};
+
+// Item f as transcript tx sees it; !ok: f is out of range, names another transcript, is empty, has an unknown kind or is a CDS part
+// without its segment.  Nothing is read before its index is checked.
+__device__ __forceinline__ TiItem txindel_item(const TxindelArgs& A, int64_t f, int32_t tx) {
+  TiItem it{0, 0, 0, 0, false};
+  if (f < 0 || f >= A.n_feat) return it;
+  if (A.feat_tx[f] != tx) return it;
+  it.b0 = A.feat_b0[f], it.b1 = A.feat_b1[f], it.kind = A.feat_kind[f];
+  if (it.b1 <= it.b0 || it.kind > TI_KIND_CDS) return it;
+  if (it.kind == TI_KIND_CDS) {
+    const int64_t seg = A.feat_seg[f];
+    if (seg < 0 || seg >= A.n_seg) return it;
+    if (A.seg_b0[seg] != it.b0 || A.seg_b1[seg] != it.b1 || A.seg_tx[seg] != tx) return it;
+    it.cds0 = A.seg_cds0[seg];
+  }
+  it.ok = true;
+  return it;
+}
+
+// the frame bin of a class of frame mode `mode`, n CDS bases affected
+__device__ __forceinline__ int txindel_frame_bin(int mode, int64_t n) {
+  return mode == TI_MIXED ? 9 : (mode != TI_FRAMED || n % 3 != 0) ? 7 : 8;
+}
+
+// the CDS rule at a boundary with x CDS bases 5' of it
+__device__ __forceinline__ int txindel_cds_rule(int64_t x, int64_t cds_len) {
+  return x == 0 ? 0 : x == cds_len ? 1 : x <= 2 ? 6 : TI_FRAME;
+}
+
+// what the deleted bases [d0, d1) meet in item `it`: the CDS bases, and the touch flags
+__device__ __forceinline__ void txindel_meet(const TiItem& it, bool minus, int64_t d0, int64_t d1, int64_t& n_cds, uint32_t& touch) {
+  const int64_t u = max(it.b0, d0), v = min(it.b1, d1);
+  if (u >= v) return;
+  if (it.kind == TI_KIND_CDS) {
+    n_cds += v - u;
+    if (it.cds0 < 3) {      // the item holds CDS offsets cds0 .. 2: its 5'-most 3 - cds0 bases
+      const bool hit = minus ? v > max(it.b0, it.b1 - (3 - it.cds0)) : u < min(it.b1, it.b0 + (3 - it.cds0));
+      if (hit) touch |= TI_T_START;
+    }
+  } else if (it.kind >= TI_KIND_CODING_INTRON) {
+    if (it.b1 - it.b0 >= 4 && (u < it.b0 + 2 || v > it.b1 - 2)) touch |= it.kind == TI_KIND_CODING_INTRON ? TI_T_SPLICE : TI_T_SPLICE_UTR;
+  } else {
+    touch |= it.kind == 2 ? TI_T_NONCODING : it.kind == 0 ? TI_T_UTR5 : TI_T_UTR3;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(TI_THREADS) void summary_txindel_reduce_kernel(TxindelArgs A, const int64_t* __restrict__ row0,
+                                                                            const int64_t* __restrict__ row1,
+                                                                            const int64_t* __restrict__ pre, int64_t n_waves) {
+  __shared__ uint32_t cls_words[TI_MAX_CLASS];
+#pragma unroll
+  for (int j = 0; j < TI_MAX_CLASS; ++j)      // (constant indices: the words stay scalar arguments)
+    if (threadIdx.x == j) cls_words[j] = A.cls[j];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * TI_WAVES + (threadIdx.x >> 6);
+  const int64_t units = pre[A.n_feat];
+  const int64_t home_shift = A.off - (A.kind == TI_DELETION_START ? 0 : 1);
+  for (int64_t unit = wave; unit < units; unit += n_waves) {
+    const int64_t f = row_chunk_item(pre, A.n_feat, unit);
+    const int64_t r0 = row0[f] + (unit - pre[f]) * TI_CHUNK_ROWS;
+    const int64_t r1 = min(r0 + TI_CHUNK_ROWS, row1[f]);
+    const int32_t tx = A.feat_tx[f];      // (0 <= tx < n_tx: the range kernel gave other items no chunk)
+    const TiItem home = txindel_item(A, f, tx);
+    if (!home.ok) continue;      // (an item of an unknown kind or a CDS part without its segment: skipped)
+    const bool minus = A.tx_strand[tx] != 0;
+    const int64_t cds_len = A.tx_cds_len[tx];
+    TiItem behind{0, 0, 0, 0, false};      // an insertion on the home item's last boundary: the item of base j
+    if (A.kind == TI_INSERTION) {
+      behind = txindel_item(A, A.feat_next[f], tx);
+      behind.ok = behind.ok && behind.b0 == home.b1;
+    }
+    u64 acc_hi[TI_BINS], acc_lo[TI_BINS];
+#pragma unroll
+    for (int b = 0; b < TI_BINS; ++b) acc_hi[b] = 0, acc_lo[b] = 0;
+    uint32_t n_rows = 0, n_lab0 = 0;
+    for (int64_t row = r0; row < r1; row += 64) {
+      const int64_t i = row + lane;
+      int lab = -1;
+      bool live = false;
+      int64_t j = 0;
+      if (i < r1) {
+        j = A.start[i] + A.off;
+        const int64_t h = A.start[i] + home_shift;
+        // (the status is the check kernel's; h lies in the item unless the rows do not ascend: then the row is skipped here)
+        live = txindel_row<T>(A, i, lab) == 0 && h >= home.b0 && h < home.b1;
+      }
+      int site = 5;      // an insertion's bin, or TI_FRAME
+      if (A.kind == TI_INSERTION) {
+        const bool gap_a = home.kind == TI_KIND_CODING_INTRON || home.kind == TI_KIND_INTRON;
+        if (j < home.b1) {      // bases j - 1 and j in one item
+          if (home.kind < TI_KIND_CODING_INTRON) site = home.kind;
+          else if (gap_a) site = (home.b1 - home.b0 >= 4 && (j == home.b0 + 1 || j == home.b1 - 1)) ? (home.kind == TI_KIND_CODING_INTRON ? 3 : 4) : 5;
+          else site = txindel_cds_rule(home.cds0 + (minus ? home.b1 - j : j - home.b0), cds_len);
+        } else {                // on the boundary of two items: base j must lie in the span as well
+          live = live && behind.ok;
+          const bool gap_b = behind.kind == TI_KIND_CODING_INTRON || behind.kind == TI_KIND_INTRON;
+          if (home.kind == TI_KIND_CDS) site = txindel_cds_rule(home.cds0 + (minus ? 0 : home.b1 - home.b0), cds_len);
+          else if (behind.kind == TI_KIND_CDS) site = txindel_cds_rule(behind.cds0 + (minus ? behind.b1 - behind.b0 : 0), cds_len);
+          else if (gap_a && gap_b) site = 5;
+          else site = gap_a ? behind.kind : home.kind;      // a gap yields to an exon part
+        }
+      }
+      const T* __restrict__ p_row = static_cast<const T*>(A.prob) + i * A.prob_stride;      // (read in live lanes only)
+      for (int c = 1; c < A.n_class; ++c) {
+        const uint32_t w = cls_words[c];
+        const int64_t len = w & 0xFF;
+        const int mode = (int)(w >> 8);
+        u64 hi = 0, lo = 0;
+        int bin = TI_BINS;      // not counted
+        if (live) {
+          quantise_prob((double)p_row[c], hi, lo);
+          if (A.kind == TI_INSERTION) {
+            bin = site == TI_FRAME ? txindel_frame_bin(mode, len) : site;
+          } else {
+            const bool fwd = A.kind == TI_DELETION_START;
+            int64_t d0 = fwd ? j : max(j - len, (int64_t)0), d1 = fwd ? j + len : j;
+            if (fwd && A.chrom_len >= 0) d1 = max(min(d1, A.chrom_len), j + 1);      // (the home base stays)
+            int64_t n_cds = 0;
+            uint32_t touch = 0;
+            txindel_meet(home, minus, d0, d1, n_cds, touch);
+            TiItem cur = home;
+            int64_t at = f;
+            while (fwd ? cur.b1 < d1 : cur.b0 > d0) {      // at most 64 steps: every step moves on by a base or more
+              at = fwd ? A.feat_next[at] : A.feat_prev[at];
+              const TiItem it = txindel_item(A, at, tx);
+              if (!it.ok || (fwd ? it.b0 != cur.b1 : it.b1 != cur.b0)) break;
+              txindel_meet(it, minus, d0, d1, n_cds, touch);
+              cur = it;
+            }
+            bin = (touch & TI_T_START) ? 6 : (touch & TI_T_SPLICE) ? 3 : n_cds > 0 ? txindel_frame_bin(mode, n_cds) : (touch & TI_T_SPLICE_UTR) ? 4
+                : (touch & TI_T_NONCODING) ? 2 : (touch & TI_T_UTR5) ? 0 : (touch & TI_T_UTR3) ? 1 : 5;
+          }
+          hi |= (u64)(lab == c) << TI_COUNT_SHIFT;
+        }
+#pragma unroll
+        for (int b = 0; b < TI_BINS; ++b) {
+          acc_hi[b] += bin == b ? hi : 0;
+          acc_lo[b] += bin == b ? lo : 0;
+        }
+      }
+      n_rows += (uint32_t)__popcll(__ballot(live));
+      n_lab0 += (uint32_t)__popcll(__ballot(live && lab == 0));
+    }
+    u64 word = 0;      // lane 3 b + w: word w of bin b; lanes 30, 31: the row counters
+    const int my_bin = lane / 3, my_word = lane - 3 * my_bin;
+#pragma unroll
+    for (int b = 0; b < TI_BINS; ++b) {
+      u64 l = wave_sum(acc_lo[b]), h = wave_sum(acc_hi[b]);
+      const u64 cnt = h >> TI_COUNT_SHIFT;
+      h &= (1ull << TI_COUNT_SHIFT) - 1;
+      fold_limbs(h, l);
+      if (my_bin == b) word = my_word == 0 ? cnt : my_word == 1 ? h : l;
+    }
+    if (lane == TI_CELL_WORDS) word = n_rows;
+    if (lane == TI_CELL_WORDS + 1) word = n_lab0;
+    if (word) {      // (0 in the lanes from 32 on)
+      if (lane < TI_CELL_WORDS) atomicAdd(&A.table[(int64_t)tx * TI_CELL_WORDS + lane], word);
+      else atomicAdd(&A.rows[(int64_t)tx * 2 + (lane - TI_CELL_WORDS)], word);
+    }
+  }
+}
+
+}  // namespace
+}  // namespace mural
+
+using namespace mural;
+
+extern "C" int64_t mural_summary_txindel_chunk_rows(void) { return TI_CHUNK_ROWS; }
+extern "C" int64_t mural_summary_txindel_grid_waves(void) { return TI_GRID_WAVES; }
+extern "C" int32_t mural_summary_txindel_scan_threads(void) { return TI_SCAN_THREADS; }
+
+extern "C" size_t mural_summary_txindel_workspace_bytes(int64_t n_features) {
+  return row_chunks_bytes(n_features);
+}
+
+extern "C" int mural_summary_txindel_rows(const MuralSummaryTxindelRows* s, void* ws_ptr, size_t ws_bytes, void* stream) {
+  MURAL_REQUIRE(s, "summary_txindel_rows: NULL argument");
+  MURAL_REQUIRE(s->n_class >= 2 && s->n_class <= TI_MAX_CLASS, "summary_txindel_rows: 2 <= n_class <= 16 required (n_class = %d)", s->n_class);
+  MURAL_REQUIRE(s->kind >= 0 && s->kind <= 2, "summary_txindel_rows: kind is 0 (insertion), 1 (deletion start) or 2 (deletion end)");
+  MURAL_REQUIRE(s->breakpoint_offset == 0 || s->breakpoint_offset == 1, "summary_txindel_rows: breakpoint_offset is 0 or 1");
+  MURAL_REQUIRE(s->n >= 0 && s->n <= TI_MAX_ROWS, "summary_txindel_rows: 0 <= n <= 2^31 required");
+  MURAL_REQUIRE(s->n_features >= 0 && s->n_features <= TI_MAX_FEATURES, "summary_txindel_rows: 0 <= n_features <= 2^22 required");
+  MURAL_REQUIRE(s->n_segments >= 0, "summary_txindel_rows: n_segments < 0");
+  MURAL_REQUIRE(s->n_transcripts >= 0, "summary_txindel_rows: n_transcripts < 0");
+  MURAL_REQUIRE(s->label_kind >= 0 && s->label_kind <= 2, "summary_txindel_rows: label_kind is 0 (float32), 1 (int32) or 2 (int64)");
+  for (int c = 1; c < s->n_class; ++c)
+    MURAL_REQUIRE(1 <= s->class_len[c][0] && s->class_len[c][0] <= s->class_len[c][1] && s->class_len[c][1] <= TI_MAX_LEN,
+                  "summary_txindel_rows: class_len[%d] must be 1 <= lo <= hi <= 64", c);
+  if (s->n == 0 || s->n_features == 0) return MURAL_OK;
+  MURAL_REQUIRE(s->prob && s->start && s->label && s->status && s->table && s->rows, "summary_txindel_rows: NULL argument");
+  MURAL_REQUIRE(s->feat_b0 && s->feat_b1 && s->feat_tx && s->feat_kind && s->feat_seg && s->feat_prev && s->feat_next && s->tx_strand &&
+                    s->tx_cds_len && s->n_transcripts >= 1,
+                "summary_txindel_rows: items without links or transcripts");
+  MURAL_REQUIRE(s->n_segments == 0 || (s->seg_b0 && s->seg_b1 && s->seg_cds0 && s->seg_tx),
+                "summary_txindel_rows: n_segments without the segment arrays");
+  MURAL_REQUIRE(s->prob_stride >= s->n_class, "summary_txindel_rows: prob_stride < n_class");
+  if (const int rc = check_workspace("summary_txindel_rows", "mural_summary_txindel_workspace_bytes", ws_ptr, ws_bytes,
+                                     mural_summary_txindel_workspace_bytes(s->n_features)))
+    return rc;
+  TxindelArgs A{};
+  A.prob = s->prob, A.start = s->start, A.label = s->label, A.prob_stride = s->prob_stride, A.n = s->n, A.chrom_len = s->chrom_length;
+  A.label_kind = s->label_kind, A.n_tx = s->n_transcripts, A.n_class = s->n_class, A.kind = s->kind, A.off = s->breakpoint_offset;
+  A.seg_b0 = s->seg_b0, A.seg_b1 = s->seg_b1, A.seg_cds0 = s->seg_cds0, A.seg_tx = s->seg_tx, A.n_seg = s->n_segments;
+  A.feat_b0 = s->feat_b0, A.feat_b1 = s->feat_b1, A.feat_tx = s->feat_tx, A.feat_kind = s->feat_kind, A.feat_seg = s->feat_seg;
+  A.feat_prev = s->feat_prev, A.feat_next = s->feat_next, A.n_feat = s->n_features;
+  A.tx_strand = s->tx_strand, A.tx_cds_len = s->tx_cds_len;
+  for (int c = 1; c < s->n_class; ++c) {
+    const int lo = s->class_len[c][0], hi = s->class_len[c][1];
+    // framed: one length; mixed: the range holds a multiple of 3 and another length; otherwise every length shifts the frame
+    const int mode = lo == hi ? TI_FRAMED : (hi / 3 > (lo - 1) / 3) ? TI_MIXED : 2;
+    A.cls[c] = (uint32_t)lo | (uint32_t)mode << 8;
+  }
+  A.table = reinterpret_cast<u64*>(s->table), A.rows = reinterpret_cast<u64*>(s->rows), A.status = s->status;
+  WsArena ws(ws_ptr);
+  const RowChunks w = carve_row_chunks(ws, s->n_features);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 block(TI_THREADS);
+  const dim3 row_grid((unsigned)((s->n + TI_THREADS - 1) / TI_THREADS));
+  if (s->prob_f64)
+    hipLaunchKernelGGL(summary_txindel_check_kernel<double>, row_grid, block, 0, st, A);
+  else
+    hipLaunchKernelGGL(summary_txindel_check_kernel<float>, row_grid, block, 0, st, A);
+  MURAL_HIP_CHECK(hipGetLastError());
+  const dim3 feat_grid((unsigned)((s->n_features + TI_WAVES - 1) / TI_WAVES));
+  const int64_t home_shift = A.off - (A.kind == TI_DELETION_START ? 0 : 1);
+  hipLaunchKernelGGL(row_chunk_range_shift_kernel<TI_THREADS>, feat_grid, block, 0, st, A.start, A.n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx,
+                     A.n_feat, home_shift, TI_CHUNK_ROWS, w);
+  MURAL_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(summary_txindel_scan_kernel, dim3(1), dim3(TI_SCAN_THREADS), 0, st, w.pre, s->n_features);
+  MURAL_HIP_CHECK(hipGetLastError());
+  const int64_t n_waves = row_chunk_grid_waves(s->n, TI_CHUNK_ROWS, 1, s->n_features, TI_GRID_WAVES, TI_WAVES);
+  const dim3 reduce_grid((unsigned)(n_waves / TI_WAVES));
+  if (s->prob_f64)
+    hipLaunchKernelGGL(summary_txindel_reduce_kernel<double>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
+  else
+    hipLaunchKernelGGL(summary_txindel_reduce_kernel<float>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
+  MURAL_HIP_CHECK(hipGetLastError());
+  const int64_t n_cells = (int64_t)s->n_transcripts * TI_BINS;
+  FoldTables F{};
+  F.table[0] = A.table, F.n_groups[0] = n_cells, F.nc = 1;      // [transcript][bin][3] = [cell][3][1]
+  hipLaunchKernelGGL(summary_fold_kernel<TI_THREADS>, dim3((unsigned)((n_cells + TI_THREADS - 1) / TI_THREADS)), block, 0, st, F);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}

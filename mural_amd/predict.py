@@ -25,7 +25,7 @@ from .summaries import (_MOTIF_ORD_SHIFT, _MOTIF_POS_SHIFT, SummarySink, _calib_
                         _kmer_fold, _kmer_merge, annot_table_from_sums, calib_bounds, calib_cells, calib_metrics_from_sums,
                         calib_rows_device, kmer_keys_host, kmer_table_from_sums, motif_table_from_sums, summary_annot_host,
                         summary_calib_host, summary_conseq_host, summary_kmer_host, summary_motif_host, summary_rows_host,
-                        summary_txstruct_host)
+                        summary_txindel_host, summary_txstruct_host)
 
 
 def all_gather_rows(local, n_total, group=None):

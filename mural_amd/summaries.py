@@ -21,7 +21,9 @@ from .tables import (annotation_meta, annotation_output_names, check_alt_order, 
                      write_structure_simulation_outputs, simulation_bed_name, simulation_bed_text, simulation_output_name,
                      write_simulation_outputs, check_kmer_length, check_motif_length, kmer_name, kmer_output_names,
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
-                     strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs)
+                     strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs,
+                     check_breakpoint_offset, check_indel_kind, check_indel_lengths, indel_structure_output_name, structure_links,
+                     write_indel_structure_outputs)
 
 
 def _refuse_fit_on_calibrated(calibrated):
@@ -650,6 +652,190 @@ def txstruct_rows_device(acc, conseq_acc, name, segments, features, n_transcript
     C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
     s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
     _lib.check(lib.mural_summary_txstruct_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+
+
+# ---- INDEL structure tables (csrc/summary_txindel.hip: mural_summary_txindel_rows): what an INDEL event does to the transcript -----------
+TXINDEL_BINS = 10
+_TXINDEL_MAX_WALK = 64             # the longest deletion: a walk moves on by a base or more every step
+
+
+def _txindel_frame_bin(lo, hi, n):
+    """The frame bin of a class of lengths lo .. hi with `n` CDS bases affected (an array): 9 for a mixed class, 7 for a range without a
+    multiple of 3, and for a framed class 7 where n % 3 != 0, else 8."""
+    if lo == hi:
+        return np.where(n % 3 != 0, 7, 8)
+    return np.full(np.shape(n), 9 if hi // 3 > (lo - 1) // 3 else 7, np.int64)
+
+
+def summary_txindel_host(prob, start, label, n_class, segments, features, n_transcripts, kind, breakpoint_offset=1, class_len=None,
+                         chrom_length=None, links=None, into=None):
+    """The numpy twin of ``mural_summary_txindel_rows`` -- and its specification -- for INDEL rows (any order) of one chromosome: (table
+    uint64 [n_transcripts][10][3], rows uint64 [n_transcripts][2], status).  `segments`, `features`: the chromosome's dicts of
+    ``tables.read_transcript_structure`` (or None); `links`: ``tables.structure_links(features)`` (None: built here); `kind`: 0 / 1 / 2 or
+    'insertion' / 'deletion_start' / 'deletion_end', of all rows; `class_len`: ``tables.check_indel_lengths``' argument, the inclusive
+    lengths lo .. hi of every class c >= 1; `chrom_length`: the chromosome's, or None.  2 <= n_class <= 16.  Class 0's probability, the
+    rows' strand and the genome are never read.  The bins (``tables.INDEL_STRUCTURE_BINS``): 0 utr5, 1 utr3, 2 noncoding_exon, 3 splice,
+    4 splice_utr, 5 intron, 6 start_lost, 7 frameshift, 8 inframe, 9 cds_mixed.
+
+    The event's boundary is j = start + breakpoint_offset, between bases j - 1 and j; its home base h is j - 1 for an insertion and a
+    deletion end, j for a deletion start.  A row counts for every transcript whose span holds h (an insertion: and j), once, through the
+    item [a, b) that holds h.  x(j) is the number of CDS bases 5' of boundary j in transcript orientation.  The FRAME BIN of class c
+    with n CDS bases affected: 9 where the range lo .. hi holds a multiple of 3 and another length (mixed), 7 for any other range of two
+    lengths, and for lo == hi (framed) 7 where n % 3 != 0, else 8.  The CDS RULE at boundary j: x == 0 bin 0, x == cds_length bin 1, x <=
+    2 bin 6 for every class, otherwise the frame bin with n = lo.
+      Insertion, A the item of base j - 1, B that of base j.  A == B: kinds 0, 1, 2 give bins 0, 1, 2; in a gap of 4 bases or more, j ==
+        a + 1 or j == b - 1 splits a splice dinucleotide: bin 3 for kind 3, bin 4 for kind 4; any other gap position is bin 5; a CDS part
+        follows the CDS rule.  A != B: a gap yields to an exon part; a CDS part decides by the CDS rule (A first); two other exon parts
+        have one kind.
+      Deletion: D = [j, j + L) (deletion start) or [j - L, j) (deletion end), L = lo, clipped to the span and to [0, chrom_length) (the
+        home base stays).  Over the items that meet D, reached from the home item over the links: n_cds = the CDS bases in D, touch_start
+        = a CDS base of offset < 3 is in D, touch_splice = one of the first two or last two bases of a kind-3 gap of 4 bases or more is in
+        D, touch_splice_utr = the same for kind 4.  The first that holds: touch_start bin 6, touch_splice bin 3, n_cds > 0 the frame bin
+        with n = n_cds, touch_splice_utr bin 4, a kind-2 base bin 2, a kind-0 base bin 0, a kind-1 base bin 1, otherwise bin 5.
+    A link that is out of range or names another transcript, and an item that is empty, of an unknown kind, a CDS part without its
+    segment or that does not abut the item before it, end the walk; such a home item is skipped, and so is an insertion whose B is one.
+    Cell [t][b] += {label == c, hi(p_c), lo(p_c)} per (row, c >= 1) routed to bin b of transcript t; rows[t] += {1, label == 0} per row
+    counted.  Integer sums: both tables are a function of the SET of rows, bit for bit; on return lo < 2^40.  `into`: (table, rows) of
+    earlier parts and chromosomes to add to, in place.  Status bits: 1 a negative start, 2 a label outside 0 .. n_class - 1, 8 a
+    probability of a class >= 1 that is NaN, negative or above 1; such rows are skipped."""
+    k = int(n_class)
+    if not 2 <= k <= 16:
+        raise ValueError(f"the INDEL structure table takes rows of 2 .. 16 classes (got {k})")
+    kind, off, cl = check_indel_kind(kind), check_breakpoint_offset(breakpoint_offset), check_indel_lengths(class_len, k)
+    n_tx = int(n_transcripts)
+    start, label = np.asarray(start, np.int64), np.asarray(label)
+    hi, lo, bad_p = kmer_quantise(np.asarray(prob)[:, 1:k])
+    lab = np.where(np.isfinite(label.astype(np.float64)), label, -1).astype(np.int64)
+    bad_label = (lab < 0) | (lab >= k) | (lab != label)
+    bad_start, bad_prob = start < 0, bad_p.any(axis=1)
+    status = (1 if bad_start.any() else 0) | (2 if bad_label.any() else 0) | (8 if bad_prob.any() else 0)
+    ok = ~(bad_label | bad_start | bad_prob)
+    table, rows = (np.zeros((n_tx, TXINDEL_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if into is None else into
+    if features is None or len(features["feat_b0"]) == 0 or not ok.any():
+        return table, rows, status
+    order = np.argsort(start[ok], kind="stable")
+    hi, lo, start, lab = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order]
+    b0, b1 = np.asarray(features["feat_b0"], np.int64), np.asarray(features["feat_b1"], np.int64)
+    f_tx, f_kind, f_seg = (np.asarray(features[key], np.int64) for key in ("feat_tx", "feat_kind", "feat_seg"))
+    prev, nxt = (np.asarray(x, np.int64) for x in (structure_links(features) if links is None else links))
+    tx_minus, tx_len = np.asarray(features["tx_strand"]) != 0, np.asarray(features["tx_cds_len"], np.int64)
+    n_feat = len(b0)
+    # the items a walk may stand on, and the CDS offset of a CDS part's first base in transcript orientation
+    item_ok = (b1 > b0) & (f_kind <= 5) & (f_tx >= 0) & (f_tx < n_tx)
+    cds0, is_cds = np.zeros(n_feat, np.int64), f_kind == 5
+    if is_cds.any():
+        n_seg = 0 if segments is None else len(segments["seg_b0"])
+        good = is_cds & (f_seg >= 0) & (f_seg < n_seg)
+        if n_seg:
+            s = np.where(good, f_seg, 0)
+            good &= ((np.asarray(segments["seg_b0"], np.int64)[s] == b0) & (np.asarray(segments["seg_b1"], np.int64)[s] == b1)
+                     & (np.asarray(segments["seg_tx"], np.int64)[s] == f_tx))
+            cds0 = np.where(good, np.asarray(segments["seg_cds0"], np.int64)[s], 0)
+        item_ok &= ~is_cds | good
+    home = np.nonzero(item_ok)[0]
+    shift = off - (0 if kind == 1 else 1)
+    flat_table, flat_rows = table.reshape(-1), rows.reshape(-1)
+
+    def neighbour(cur, tx, step):
+        """(index, usable) of the item behind `cur` (step: the link array) for transcript tx."""
+        at = step[cur]
+        inside = (at >= 0) & (at < n_feat)
+        at = np.where(inside, at, 0)
+        return at, inside & item_ok[at] & (f_tx[at] == tx)
+
+    def cds_rule(x, cds_len):
+        return np.where(x == 0, 0, np.where(x == cds_len, 1, np.where(x <= 2, 6, -1)))
+
+    for s, i in _item_row_pairs(start + shift, b0[home], b1[home]):
+        f = home[s]
+        j, tx, a, b, kd = start[i] + off, f_tx[f], b0[f], b1[f], f_kind[f]
+        minus, cds_len = tx_minus[tx], tx_len[tx]
+        if kind == 0:
+            at, usable = neighbour(f, tx, nxt)
+            usable &= b0[at] == b
+            same, kb = j < b, f_kind[at]
+            gap_a, gap_b = (kd == 3) | (kd == 4), (kb == 3) | (kb == 4)
+            split = (b - a >= 4) & ((j == a + 1) | (j == b - 1))
+            site_same = np.where(kd < 3, kd, np.where(gap_a, np.where(split, np.where(kd == 3, 3, 4), 5),
+                                                      cds_rule(cds0[f] + np.where(minus, b - j, j - a), cds_len)))
+            site_diff = np.where(kd == 5, cds_rule(cds0[f] + np.where(minus, 0, b - a), cds_len),
+                                 np.where(kb == 5, cds_rule(cds0[at] + np.where(minus, b1[at] - b0[at], 0), cds_len),
+                                          np.where(gap_a & gap_b, 5, np.where(gap_a, kb, kd))))
+            site, counted = np.where(same, site_same, site_diff), same | usable
+        else:
+            counted = np.ones(len(i), bool)
+        for c in range(1, k):
+            c_lo, c_hi = int(cl[c, 0]), int(cl[c, 1])
+            if kind == 0:
+                bins = np.where(site < 0, _txindel_frame_bin(c_lo, c_hi, np.full(len(i), c_lo, np.int64)), site)
+            else:
+                fwd = kind == 1
+                d0, d1 = (j, j + c_lo) if fwd else (np.maximum(j - c_lo, 0), j)
+                if fwd and chrom_length is not None and int(chrom_length) >= 0:
+                    d1 = np.maximum(np.minimum(d1, int(chrom_length)), j + 1)
+                n_cds, touch = np.zeros(len(i), np.int64), np.zeros(len(i), np.int64)
+                cur, on = f.copy(), np.ones(len(i), bool)
+                for _ in range(_TXINDEL_MAX_WALK + 1):
+                    u, v = np.maximum(b0[cur], d0), np.minimum(b1[cur], d1)
+                    meets, ck, c0 = on & (u < v), f_kind[cur], cds0[cur]
+                    n_cds += np.where(meets & (ck == 5), v - u, 0)
+                    first = np.where(minus, v > np.maximum(b0[cur], b1[cur] - (3 - c0)), u < np.minimum(b1[cur], b0[cur] + (3 - c0)))
+                    sites = (b1[cur] - b0[cur] >= 4) & ((u < b0[cur] + 2) | (v > b1[cur] - 2))
+                    for bit, where in ((1, (ck == 5) & (c0 < 3) & first), (2, (ck == 3) & sites), (4, (ck == 4) & sites), (8, ck == 2),
+                                       (16, ck == 0), (32, ck == 1)):
+                        touch |= np.where(meets & where, bit, 0)
+                    on &= (b1[cur] < d1) if fwd else (b0[cur] > d0)
+                    if not on.any():
+                        break
+                    at, usable = neighbour(cur, tx, nxt if fwd else prev)
+                    on &= usable & ((b0[at] == b1[cur]) if fwd else (b1[at] == b0[cur]))
+                    cur = np.where(on, at, cur)
+                bins = np.where(touch & 1, 6, np.where(touch & 2, 3, np.where(n_cds > 0, _txindel_frame_bin(c_lo, c_hi, n_cds),
+                                np.where(touch & 4, 4, np.where(touch & 8, 2, np.where(touch & 16, 0, np.where(touch & 32, 1, 5)))))))
+            ic, cell = i[counted], (tx * (3 * TXINDEL_BINS) + 3 * bins)[counted]
+            np.add.at(flat_table, cell, (lab[ic] == c).astype(np.uint64))
+            np.add.at(flat_table, cell + 1, hi[ic, c - 1])
+            np.add.at(flat_table, cell + 2, lo[ic, c - 1])
+            # (per class: a pass holds up to 2^20 pairs, and 15 classes of them unfolded would bring a cell's lo limb to 2^64)
+            _conseq_fold(table)
+        np.add.at(flat_rows, 2 * tx[counted], np.uint64(1))
+        np.add.at(flat_rows, 2 * tx[counted] + 1, (lab[i[counted]] == 0).astype(np.uint64))
+    return table, rows, status
+
+
+def txindel_rows_device(acc, name, segments, features, links, n_transcripts, kind, breakpoint_offset, class_len, chrom_length, dev, *,
+                        prob, prob_f64, prob_stride, start, label, label_kind, n, n_class):
+    """One ``mural_summary_txindel_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 30],
+    rows int64 [n_transcripts * 2], status int32 [1], features {chromosome: device arrays}, segments {the same}, ws): the chromosome's
+    item, link and segment arrays are uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --,
+    the workspace grows as needed.  `segments` None: the chromosome has no CDS.  `class_len`: int32 [n_class][2]
+    (``tables.check_indel_lengths``); `chrom_length` None: not known."""
+    lib = _lib.lib()
+    on_dev = acc["features"].get(name)
+    if on_dev is None:
+        arrays = [features[key] for key in ("feat_b0", "feat_b1", "feat_tx", "feat_kind", "feat_seg")] + [np.asarray(x, np.int32) for x in links]
+        pinned = tuple(torch.from_numpy(np.ascontiguousarray(x)).pin_memory() for x in arrays)
+        on_dev = acc["features"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    seg_dev = _conseq_segments_device(acc, name, features if segments is None else segments, dev)
+    n_feat = int(on_dev[0].shape[0])
+    need = int(lib.mural_summary_txindel_workspace_bytes(n_feat))
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _lib.MuralSummaryTxindelRows()
+    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
+    s.start, s.label, s.label_kind = start, label, int(label_kind)
+    s.n, s.n_class, s.n_transcripts = int(n), int(n_class), int(n_transcripts)
+    s.kind, s.breakpoint_offset, s.chrom_length = int(kind), int(breakpoint_offset), -1 if chrom_length is None else int(chrom_length)
+    for c, (lo, hi) in enumerate(np.asarray(class_len).tolist()[:16]):
+        s.class_len[c][0], s.class_len[c][1] = lo, hi
+    if seg_dev is not None and seg_dev[0].shape[0]:
+        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx = (x.data_ptr() for x in seg_dev[:4])
+        s.n_segments = int(seg_dev[0].shape[0])
+    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg, s.feat_prev, s.feat_next = (x.data_ptr() for x in on_dev[:7])
+    s.n_features = n_feat
+    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
+    s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
+    _lib.check(lib.mural_summary_txindel_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
 
 
 # ---- mutation sets drawn from the rates (csrc/simulate.hip: mural_simulate_annot_rows, mural_simulate_rows) -----------------------------
@@ -1605,6 +1791,103 @@ class _StructureReducer:
         write_structure_outputs(names, self.conseq.meta, table, rows, self.conseq.sums[0][:, 2], out_prefix, labels=self.conseq.labels)
 
 
+class _IndelStructureReducer:
+    """Expected and observed INDEL events per transcript of a BED12 file by what they do to the transcript's structure
+    (``summary_txindel_host`` is the rule): ONE integer table [transcripts][10][3] + row counters [transcripts][2] for the whole run on
+    the host and one pair per device -- the transcript ids are global --, a chromosome's item, link and segment arrays uploaded the
+    first time the chromosome arrives on a device, read back once.  A chromosome without items reduces nothing.  `genome` (optional)
+    gives the chromosomes' lengths; no base is read."""
+    name = "indel_structure"
+
+    def __init__(self, transcripts, kind, lengths, breakpoint_offset, genome=None, labels=True):
+        self.names, self.meta, self.segments, self.features = read_transcript_structure(transcripts)
+        if kind is None:
+            raise ValueError("SummarySink(indel_transcripts=...) needs indel_kind=: 'insertion', 'deletion_start' or 'deletion_end'")
+        self.kind, self.offset = check_indel_kind(kind), check_breakpoint_offset(breakpoint_offset)
+        self.lengths = lengths if lengths is None else check_indel_lengths(lengths)      # (the count is checked when the classes are known)
+        self.genome, self.labels = genome, bool(labels)
+        self.links, self.class_len = {}, None
+        self.reset()
+
+    def reset(self):
+        self.host = None               # (table, rows) of the host shards
+        self.dev = {}                  # device -> dict(table, rows, status, features, segments {chromosome: device arrays}, tx, ws)
+        self.sums = None
+
+    def _part(self, name, k):
+        """(features, links, chromosome length or None) of chromosome `name`, None where it has no items; the classes' lengths checked."""
+        if not 2 <= k <= 16:
+            raise ValueError(f"SummarySink(indel_transcripts=...) takes INDEL rows of 2 .. 16 classes (got {k})")
+        if self.class_len is None or len(self.class_len) != k:
+            self.class_len = check_indel_lengths(self.lengths, k)
+        features = self.features.get(name)
+        if features is None:
+            return None
+        if name not in self.links:
+            self.links[name] = structure_links(features)
+        length = None
+        if self.genome is not None:
+            genome = self.genome(name)
+            length = int(genome.length) if hasattr(genome, "length") else len(genome)
+        return features, self.links[name], length
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        part = self._part(name, k)
+        if part is None:
+            return 0
+        n_tx = len(self.names)
+        if self.host is None:
+            self.host = (np.zeros((n_tx, TXINDEL_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64))
+        return summary_txindel_host(prob, start, label, k, self.segments.get(name), part[0], n_tx, self.kind, self.offset, self.class_len,
+                                    part[2], links=part[1], into=self.host)[2]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the reduction of a part behind its forward, into the device's one pair of tables."""
+        part = self._part(name, k)
+        if part is None or start.shape[0] == 0:
+            return None
+        dev, n_tx = prob.device, len(self.names)
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(n_tx * 3 * TXINDEL_BINS, dtype=torch.int64, device=dev),
+                                       rows=torch.zeros(n_tx * 2, dtype=torch.int64, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev), features={}, segments={}, ws=None)
+        txindel_rows_device(acc, name, self.segments.get(name), part[0], part[1], n_tx, self.kind, self.offset, self.class_len, part[2], dev,
+                            prob=prob.data_ptr(), prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
+                            label=label.data_ptr(), label_kind=_LABEL_KIND[label.dtype], n=start.shape[0], n_class=k)
+        return None
+
+    def _added(self, states):
+        out = None
+        for st in states:
+            if st is not None:
+                out = (st[0].copy(), st[1].copy()) if out is None else (_conseq_fold(np.add(out[0], st[0], out=out[0])),
+                                                                        np.add(out[1], st[1], out=out[1]))
+        return out
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, mine, n_tx = 0, [self.host], len(self.names)
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine.append((acc["table"].cpu().numpy().view(np.uint64).reshape(n_tx, TXINDEL_BINS, 3),
+                         acc["rows"].cpu().numpy().view(np.uint64).reshape(n_tx, 2)))
+        return self._added(mine), status
+
+    def merge(self, states, k):
+        return self._added(states)
+
+    def finish(self, state, k, result):
+        n_tx = len(self.names)
+        self.sums = (np.zeros((n_tx, TXINDEL_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if state is None else state
+        result[self.name] = (list(self.names), *self.sums)
+
+    def write(self, out_prefix, result, k, written):
+        written.append(indel_structure_output_name(out_prefix))
+        names, table, rows = result[self.name]
+        write_indel_structure_outputs(names, self.meta, table, rows, self.kind, out_prefix, labels=self.labels)
+
+
 class _SimulationReducer:
     """Mutation sets drawn from the rates (``simulate_rows_host`` is the rule): per name of the annotation reducer beside it the counts
     of every class in each of `n_rep` replicates -- ONE uint32 table [names][n_class - 1][n_rep] on the host and one per device, the
@@ -2286,6 +2569,21 @@ class SummarySink:
     ``{out_prefix}.consequence.structure.sim.tsv`` (``tables.write_structure_simulation_outputs``);
     ``structure_simulation_counts()`` has the table.
 
+    `indel_transcripts`: a BED12 path or ``tables.read_transcript_structure``'s result, for INDEL rows (2 .. 16 classes; 8 on the
+    device, as every summary here): per transcript the expected and observed INDEL events by what they do to the transcript -- utr5,
+    utr3, noncoding_exon, splice, splice_utr, intron, start_lost, frameshift, inframe and cds_mixed (``summary_txindel_host`` is the
+    rule) --, alone or beside the other summaries.  `indel_kind` (required): 'insertion', 'deletion_start' or
+    'deletion_end', of the whole run -- there is one model per kind; `indel_lengths`: the lengths each class >= 1 stands for
+    (``tables.check_indel_lengths``; default "1,2,3,4,5,6,7-20" for 8 classes, any other class count needs it); `breakpoint_offset`: 0
+    or 1 (default), the event's boundary is start + breakpoint_offset.  No base is read; with `genome` a deletion is clipped to the
+    chromosome's length as well.  Device parts go through ``mural_summary_txindel_rows`` (csrc/summary_txindel.hip) on a chromosome's
+    item, link and segment arrays, uploaded once; one integer table pair per device, read back once and added across ranks in the
+    same collective -- a function of the set of rows alone, bit for bit.  result()["indel_structure"] = (names, table uint64 [n][10][3],
+    rows uint64 [n][2]); close() writes ``{out_prefix}.indel_structure.tsv`` (``tables.write_indel_structure_outputs``: the ten bins,
+    expected_lof / observed_lof = splice + start lost + frameshift and the _upper pair = that + cds_mixed; `transcript_labels=False`:
+    the observed columns are NA); ``indel_structure_sums()`` has the integers.  `transcripts=` keeps refusing rows of other than 4
+    classes.
+
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
 
@@ -2296,7 +2594,7 @@ class SummarySink:
                  calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
                  simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True, transcripts=None,
                  codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False, transcript_structure=False,
-                 simulate_structure=False):
+                 simulate_structure=False, indel_transcripts=None, indel_kind=None, indel_lengths=None, breakpoint_offset=1):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -2360,6 +2658,10 @@ class SummarySink:
             raise ValueError("simulate_transcripts goes with transcripts= (and simulate=R)")
         if simulate_transcripts and not self.simulate:
             raise ValueError("simulate_transcripts goes with simulate=R and simulate_seed")
+        if indel_transcripts is not None:
+            active.append(_IndelStructureReducer(indel_transcripts, indel_kind, indel_lengths, breakpoint_offset, genome, transcript_labels))
+        elif indel_kind is not None or indel_lengths is not None or breakpoint_offset != 1:
+            raise ValueError("indel_kind, indel_lengths and breakpoint_offset go with indel_transcripts=")
         self._reducers = {r.name: r for r in active}
         self.rows = 0
         self._n_class = None
@@ -2519,6 +2821,12 @@ class SummarySink:
         [transcripts][2]) after close(): ``summary_txstruct_host``'s layout, the transcripts in file order."""
         self.result()
         return self._reducers["transcript_structure"].sums
+
+    def indel_structure_sums(self):
+        """(table uint64 [transcripts][10][3] of label counts | sums of hi | sums of lo per bin of ``tables.INDEL_STRUCTURE_BINS``, rows
+        uint64 [transcripts][2]) after close(): ``summary_txindel_host``'s layout, the transcripts in file order."""
+        self.result()
+        return self._reducers["indel_structure"].sums
 
     def simulation_counts(self):
         """table uint32 [names][n_class - 1][simulate] after close(): the simulated count of every name, class >= 1 and replicate

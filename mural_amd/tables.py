@@ -1087,6 +1087,186 @@ def run_structure_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
     return write_structure_outputs(*result, args.out_prefix)
 
 
+# the INDEL structure table: what an INDEL event does to the transcript (``summaries.summary_txindel_host`` is the rule)
+INDEL_STRUCTURE_BINS = ("utr5", "utr3", "noncoding_exon", "splice", "splice_utr", "intron", "start_lost", "frameshift", "inframe", "cds_mixed")
+INDEL_KINDS = ("insertion", "deletion_start", "deletion_end")      # the models the reference ships: `kind` 0, 1, 2
+INDEL_DEFAULT_LENGTHS = "1,2,3,4,5,6,7-20"                          # the reference's labelling of its 8 classes
+INDEL_MAX_LENGTH = 64
+
+
+def indel_structure_output_name(out_prefix):
+    return f"{out_prefix}.indel_structure.tsv"
+
+
+def check_indel_kind(kind):
+    """0, 1 or 2 from a kind's number or its name in ``INDEL_KINDS``; ValueError otherwise."""
+    if isinstance(kind, str) and kind in INDEL_KINDS:
+        return INDEL_KINDS.index(kind)
+    if isinstance(kind, (int, np.integer)) and not isinstance(kind, bool) and 0 <= int(kind) <= 2:
+        return int(kind)
+    raise ValueError(f"indel_kind: one of {', '.join(INDEL_KINDS)} (or 0, 1, 2) is required, got {kind!r}")
+
+
+def check_breakpoint_offset(offset):
+    if isinstance(offset, (int, np.integer)) and not isinstance(offset, bool) and int(offset) in (0, 1):
+        return int(offset)
+    raise ValueError(f"breakpoint_offset: 0 or 1 is required, got {offset!r}")
+
+
+def check_indel_lengths(lengths=None, n_class=None):
+    """int32 [n_class][2]: the inclusive (lo, hi) of the lengths that class c >= 1 stands for, row 0 zeros.  `lengths`: a text spec, one
+    entry per class >= 1 ("1,2,3,4-6": a number or lo-hi), a sequence or array of numbers or (lo, hi) pairs, this function's own result
+    (an array whose row 0 is (0, 0): no class has lo = 0), or None -- ``INDEL_DEFAULT_LENGTHS``, which serves 8 classes only.  1 <= lo <= hi <= 64, and with `n_class` one entry per class
+    >= 1; ValueError otherwise."""
+    if lengths is None:
+        if n_class is not None and int(n_class) != 8:
+            raise ValueError(f"indel_lengths: the default {INDEL_DEFAULT_LENGTHS} serves 8 classes; {n_class} classes need their own")
+        lengths = INDEL_DEFAULT_LENGTHS
+    if isinstance(lengths, np.ndarray) and lengths.ndim == 2 and lengths.shape[1] == 2 and len(lengths) and not lengths[0].any():
+        pairs = [tuple(int(v) for v in row) for row in lengths[1:].tolist()]      # this function's own result: row 0 is (0, 0), no class's
+    elif isinstance(lengths, str):
+        pairs = []
+        for item in lengths.replace(" ", "").strip(",").split(","):
+            lo, dash, hi = item.partition("-")
+            if not lo.isdigit() or (dash and not hi.isdigit()):
+                raise ValueError(f"indel_lengths: {item!r} is neither a length nor lo-hi (got {lengths!r})")
+            pairs.append((int(lo), int(hi) if dash else int(lo)))
+    else:
+        try:
+            pairs = [(int(v), int(v)) if np.ndim(v) == 0 else (int(v[0]), int(v[1])) for v in lengths]
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("indel_lengths: a text spec or a sequence of lengths / (lo, hi) pairs is required") from None
+    if not 1 <= len(pairs) <= 15:
+        raise ValueError(f"indel_lengths: 1 .. 15 classes above class 0 (got {len(pairs)})")
+    if n_class is not None and len(pairs) != int(n_class) - 1:
+        raise ValueError(f"indel_lengths: {len(pairs)} entries for {int(n_class) - 1} classes above class 0")
+    for c, (lo, hi) in enumerate(pairs, 1):
+        if not 1 <= lo <= hi <= INDEL_MAX_LENGTH:
+            raise ValueError(f"indel_lengths: class {c} needs 1 <= lo <= hi <= {INDEL_MAX_LENGTH} (got {lo}-{hi})")
+    return np.asarray([(0, 0)] + pairs, np.int32)
+
+
+def structure_links(features):
+    """(feat_prev, feat_next) int32 of a chromosome's dict of ``read_transcript_structure``'s features: per item the index, in the same
+    arrays, of the same transcript's neighbouring item at lower / higher coordinates (genomic order), -1 at the ends of the span.  A
+    transcript's items tile its span, so the neighbour at higher coordinates starts where the item ends."""
+    tx, b0 = np.asarray(features["feat_tx"], np.int64), np.asarray(features["feat_b0"], np.int64)
+    order = np.lexsort((b0, tx))      # by transcript, then by position
+    prev, nxt = np.full(len(tx), -1, np.int32), np.full(len(tx), -1, np.int32)
+    if len(order) > 1:
+        same = tx[order[1:]] == tx[order[:-1]]
+        prev[order[1:][same]] = order[:-1][same]
+        nxt[order[:-1][same]] = order[1:][same]
+    return prev, nxt
+
+
+def _indel_lof_cells(cells):
+    """The twelve [count, hi, lo] cells of a transcript as Python integers: its ten bins, LoF = splice + start lost + frameshift and the
+    upper LoF = that + cds_mixed, added word by word."""
+    lof = [cells[3][w] + cells[6][w] + cells[7][w] for w in range(3)]
+    return cells + [lof, [lof[w] + cells[9][w] for w in range(3)]]
+
+
+def write_indel_structure_outputs(names, meta, table, rows, kind, out_prefix, labels=True):
+    """``{out_prefix}.indel_structure.tsv`` from the integer sums of ``summary_txindel_host`` / ``mural_summary_txindel_rows`` (table
+    uint64 [n][10][3], rows uint64 [n][2]) of a run of `kind` (``check_indel_kind``): a line per transcript in file order -- name, chrom,
+    strand, kind, n_rows (the rows counted), n_nonmut (those of label 0), expected_* and observed_* for the ten bins of
+    ``INDEL_STRUCTURE_BINS``, expected_lof / observed_lof = splice + start lost + frameshift and expected_lof_upper / observed_lof_upper =
+    that + cds_mixed.  The integers are added as integers; an expected value is (hi * 2^40 + lo) / 2^71, formed from Python integers by
+    true division.  `labels=False`: the rows carried no labels, the observed_* columns are NA.  Returns the path."""
+    kind = INDEL_KINDS[check_indel_kind(kind)]
+    table = np.asarray(table, np.uint64).reshape(len(names), 10, 3).tolist()
+    rows = np.asarray(rows, np.uint64).reshape(len(names), 2).tolist()
+    header = ["name", "chrom", "strand", "kind", "n_rows", "n_nonmut"]
+    for what in INDEL_STRUCTURE_BINS + ("lof", "lof_upper"):
+        header += [f"expected_{what}", f"observed_{what}"]
+    den, lines = 1 << 71, []
+    for j, nm in enumerate(names):
+        line = [nm, meta["chrom"][j], "-" if meta["strand"][j] else "+", kind, str(rows[j][0]), str(rows[j][1])]
+        for count, hi, lo in _indel_lof_cells(table[j]):
+            line += [_float_text(((hi << 40) + lo) / den), str(count) if labels else "NA"]
+        lines.append(line)
+    path = indel_structure_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, lines))
+    return path
+
+
+def _indel_structure_acc(n_tx, dev):
+    """The device accumulators of ``summaries.txindel_rows_device``."""
+    zeros = lambda n, dt=torch.int64: torch.zeros(n, dtype=dt, device=dev)      # noqa: E731
+    return dict(table=zeros(max(n_tx, 1) * 30), rows=zeros(max(n_tx, 1) * 2), status=zeros(1, torch.int32), features={}, segments={}, ws=None)
+
+
+def indel_structure_table(pred_file, transcripts, n_class, kind, lengths=None, breakpoint_offset=1, chrom_lengths=None,
+                          chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, meta, table uint64 [n][10][3], rows uint64 [n][2]) per transcript of `transcripts` (a BED12 path or
+    ``read_transcript_structure``'s result) from a written INDEL prediction table of `n_class` classes: what
+    ``SummarySink(indel_transcripts=...)`` reduces in flight, through the same entry point (``mural_summary_txindel_rows``), chromosome
+    run by chromosome run of each chunk.  `kind`, `lengths`, `breakpoint_offset`: ``summary_txindel_host``'s; `chrom_lengths`: {name:
+    length} or None -- a deletion is then clipped to the transcript's span alone.  The rows of a chromosome must ascend in start, as
+    ``predict`` writes them; no genome is read."""
+    from .summaries import _SUMMARY_STATUS, txindel_rows_device      # (summaries imports this module: not at the top)
+    names, meta, segments, features = read_transcript_structure(transcripts)
+    k, kind, off = int(n_class), check_indel_kind(kind), check_breakpoint_offset(breakpoint_offset)
+    class_len = check_indel_lengths(lengths, k)
+    n_tx = len(names)
+    links = {}
+    with TableReader(pred_file, k, chunk_bytes) as rd:
+        dev = rd.device
+        acc = _indel_structure_acc(n_tx, dev)
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in features or b == a:
+                    continue
+                if name not in links:
+                    links[name] = structure_links(features[name])
+                txindel_rows_device(acc, name, segments.get(name), features[name], links[name], n_tx, kind, off, class_len,
+                                    None if chrom_lengths is None else chrom_lengths.get(name), dev, prob=c.prob + 8 * k * a, prob_f64=1,
+                                    prob_stride=k, start=c.start + 8 * a, label=c.mut_type + 4 * a, label_kind=1, n=b - a, n_class=k)
+        bits = int(acc["status"].item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table = acc["table"].cpu().numpy().view(np.uint64)[:n_tx * 30].reshape(n_tx, 10, 3)
+        counts = acc["rows"].cpu().numpy().view(np.uint64)[:n_tx * 2].reshape(n_tx, 2)
+    return names, meta, table, counts
+
+
+def read_chrom_lengths(source):
+    """{name: length} from a dict (returned as it is), or from a FASTA index (.fai) or any tab-separated file of name and length."""
+    if isinstance(source, dict):
+        return source
+    out = {}
+    with open(os.fspath(source)) as fh:
+        for ln, line in enumerate(fh, 1):
+            f = line.rstrip("\r\n").split("\t")
+            if not line.strip() or line.startswith("#"):
+                continue
+            if len(f) < 2 or not f[1].isdigit():
+                raise ValueError(f"{source}:{ln}: a chromosome name and its length are required")
+            out[f[0]] = int(f[1])
+    return out
+
+
+def run_indel_structure_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.indel_transcripts, args.n_class, args.indel_kind, args.out_prefix; optional
+    args.indel_lengths, args.breakpoint_offset, args.chrom_lengths): per transcript of the BED12 file the expected and observed INDEL
+    events of the table's rows by what they do to its structure; writes {out_prefix}.indel_structure.tsv.  args.chrom_lengths: {name:
+    length}, or a FASTA index (.fai) -- ``read_chrom_lengths``.  ``SummarySink(indel_transcripts=, genome=)`` clips a deletion to the
+    chromosome; this route gives the same table for a transcript that runs past the chromosome's end only with the lengths."""
+    assert getattr(args, "indel_transcripts", None) is not None, "--indel_transcripts is required for the INDEL structure table"
+    assert getattr(args, "indel_kind", None) is not None, "--indel_kind is required for the INDEL structure table"
+    lengths = getattr(args, "chrom_lengths", None)
+    names, meta, table, rows = indel_structure_table(os.fspath(args.pred_file), args.indel_transcripts, args.n_class, args.indel_kind,
+                                                     getattr(args, "indel_lengths", None), getattr(args, "breakpoint_offset", 1),
+                                                     None if lengths is None else read_chrom_lengths(lengths), chunk_bytes)
+    return write_indel_structure_outputs(names, meta, table, rows, args.indel_kind, args.out_prefix)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # simulation: mutation sets drawn from the rates, per-name empirical p-values
 # ------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 """Genome summaries in flight against the table route to the same numbers:
-  python tools/bench_summary.py [--bases N] [--repeats K] [--legs a,b,..]
+  python tools/bench_summary.py [--bases N] [--indel_bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Twenty-one legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Twenty-three legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -36,6 +36,14 @@ alternating, --repeats timed runs each after one warm-up run each:
   t  struct_sim100  leg s with simulate=100, simulate_seed=1, simulate_transcripts=True, simulate_structure=True as well (DESIGN.md section
                   3.24): the counts of 100 mutation sets per transcript, structure bin and LoF; the comparisons are leg s and leg q
   u  struct_sim1000 leg s with simulate=1000 (tables of 720 MB and 400 MB, each below the sink's cap)
+  v  indel         an INDEL-row run: a second synthetic chromosome of --indel_bases bases (5 Mbp by default),
+                  the shipped Homo_sapiens/INDEL/deletion_start weights (tests/golden), every A/C/G/T position a row of 8 classes,
+                  SummarySink with the 100 kb + 1 kb windows alone
+  w  indel_struct  leg v with indel_transcripts= as well: ten-exon transcripts of 2 500 bases each on alternating strands (exons of 150
+                  bases, introns of 100), indel_kind="deletion_start"; the comparison is leg v, the same run without it: the difference
+                  of the medians beside leg v's own repeat spread.  With leg w the entry alone, mural_summary_txindel_rows over the
+                  whole chromosome's rows in one call, is timed under HIP events for each of the three kinds (the rows' probabilities
+                  uniform random: the entry's work does not depend on them)
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
 h's, leg k's annotation table with leg l's and leg o's consequence table with leg p's, within the table's four digits (names, order and
 counts exactly)."""
@@ -61,7 +69,9 @@ WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
 LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000",
-        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct", "struct_sim100", "struct_sim1000")
+        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct", "struct_sim100", "struct_sim1000", "indel", "indel_struct")
+INDEL_LEGS = ("indel", "indel_struct")
+INDEL_TX_SPAN = 2500
 SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
 CONSEQ_SIM_REPLICATES = {"conseq_sim100": 100, "conseq_sim1000": 1000}
 STRUCT_SIM_REPLICATES = {"struct_sim100": 100, "struct_sim1000": 1000}
@@ -81,15 +91,15 @@ def synthetic_annotations(bases, chrom="chr1"):
     return tables.read_annotations({chrom: rows})
 
 
-def synthetic_transcripts(bases, chrom="chr1", structure=False):
+def synthetic_transcripts(bases, chrom="chr1", structure=False, names=ANNOT_NAMES):
     """``tables.read_transcripts``' result (`structure`: ``tables.read_transcript_structure``'s) for the intervals of ``synthetic_annotations`` as ANNOT_NAMES transcripts of ANNOT_INTERVALS
     exons each, all of it CDS, on alternating strands."""
     import io
-    span = bases // ANNOT_NAMES
+    span = bases // names
     step = max(span // ANNOT_INTERVALS, 1)
     every = int(round(1 / ANNOT_OVERLAP))
     lines = []
-    for g in range(ANNOT_NAMES):
+    for g in range(names):
         at = g * span + (span // 2 if g % every == every - 1 else 0)
         end = at + (ANNOT_INTERVALS - 1) * step + ANNOT_BP
         lines.append("\t".join([chrom, str(at), str(end), "tx%05d" % g, "0", "+-"[g & 1], str(at), str(end), "0", str(ANNOT_INTERVALS),
@@ -97,7 +107,82 @@ def synthetic_transcripts(bases, chrom="chr1", structure=False):
     return (tables.read_transcript_structure if structure else tables.read_transcripts)(io.StringIO("\n".join(lines) + "\n"))
 
 
+def shipped_indel_model(device, name="indel_pretrained_human_deletion_start.npz"):
+    """UNet_Small with the shipped Homo_sapiens/INDEL/deletion_start weights (they travel inside the parity fixture tests/golden/<name>);
+    (model, distal_radius, n_class)."""
+    from mural_amd.model import model_choice
+    from tests import _util as U
+    fx = U.load(name)
+    R, C, k, n_class, rev = [int(v) for v in fx["hp"]]
+    model = model_choice(0, dict(CNN_out_channels=C, CNN_kernel_size=k, down_list=[int(d) for d in fx["down"]], use_reverse=bool(rev)),
+                         dict(n_class=n_class), "indel")
+    model.load_state_dict(U.indel_state_for(fx, U.indel_oracle_from_hp(fx["hp"], fx["down"])), strict=True)
+    return model.to(device).eval(), R, n_class
+
+
+def indel_legs(legs, device, bases, repeats, shm):
+    """Legs v and w, alternating, and the entry alone under HIP events: the "indel_structure" block of the result."""
+    import numpy as np
+    from mural_amd.summaries import txindel_rows_device
+    model, R, n_class = shipped_indel_model(device)
+    with tempfile.TemporaryDirectory(prefix="mural_summary_indel_", dir=shm) as work:
+        fa = write_inputs(work, device, bases)[0]
+        torch.cuda.empty_cache()
+        tx = synthetic_transcripts(bases, structure=True, names=max(bases // INDEL_TX_SPAN, 1))
+        seconds, kept, rows = {leg: [] for leg in legs}, {}, None
+
+        def run(leg):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fwd = HipShardForward(model, fa, 5, 3, distal_radius=R, model_type="indel", device=device, poisson=False)
+            extra = dict(indel_transcripts=tx, indel_kind="deletion_start", genome=fwd.genome, transcript_labels=False) if leg == "indel_struct" else {}
+            summary = SummarySink(windows=WINDOWS, **extra)
+            n = predict_regions_sharded(fwd, "chr1", "ANY", model_type="indel", sink=summary, collect=False)
+            torch.cuda.synchronize()
+            kept[leg] = summary.result()
+            return time.perf_counter() - t0, n
+
+        for i in range(repeats + 1):
+            for leg in legs:
+                dt, rows = run(leg)
+                if i:
+                    seconds[leg].append(dt)
+    out = {"bases": bases, "rows": rows, "classes": n_class, "transcripts": len(tx[0]), "repeats": repeats, "seconds": seconds,
+           "rows_per_s": {leg: spread([rows / v for v in seconds[leg]]) for leg in legs}}
+    if set(INDEL_LEGS) <= set(legs):
+        plain, with_it = seconds["indel"], seconds["indel_struct"]
+        out["indel_struct_minus_indel_seconds"] = statistics.median(with_it) - statistics.median(plain)
+        out["indel_repeat_spread_seconds"] = max(plain) - min(plain)
+        out["indel_struct_over_indel"] = statistics.median(plain) / statistics.median(with_it)
+    if "indel_struct" in legs:
+        table, counters = kept["indel_struct"]["indel_structure"][1:]
+        out["rows_counted"], out["expected_by_bin"] = int(counters[:, 0].sum()), (table[:, :, 1].sum(axis=0) / float(1 << 31)).tolist()
+        # the entry alone: every position of the chromosome a row, one call, HIP events around it
+        k, n_tx, features, segments = n_class, len(tx[0]), tx[3]["chr1"], tx[2]["chr1"]
+        links, class_len = tables.structure_links(features), tables.check_indel_lengths(None, k)
+        gen = torch.Generator(device=device).manual_seed(3)
+        prob = torch.rand((bases, k), device=device, generator=gen) / k
+        start, label = torch.arange(bases, dtype=torch.int64, device=device), torch.zeros(bases, dtype=torch.int32, device=device)
+        out["entry_ms"] = {}
+        for kind, what in enumerate(tables.INDEL_KINDS):
+            acc, ms = tables._indel_structure_acc(n_tx, device), []
+            for i in range(repeats + 1):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                txindel_rows_device(acc, "chr1", segments, features, links, n_tx, kind, 1, class_len, bases, device, prob=prob.data_ptr(),
+                                    prob_f64=0, prob_stride=k, start=start.data_ptr(), label=label.data_ptr(), label_kind=1, n=bases, n_class=k)
+                b.record()
+                b.synchronize()
+                if i:
+                    ms.append(a.elapsed_time(b))
+            assert int(acc["status"].item()) == 0
+            out["entry_ms"][what] = spread(ms)
+        out["entry_rows"] = bases
+    return out
+
+
 def main(argv):
+    indel_bases = int(argv[argv.index("--indel_bases") + 1]) if "--indel_bases" in argv else 5_000_000
     bases = int(argv[argv.index("--bases") + 1]) if "--bases" in argv else 50_000_000
     repeats = int(argv[argv.index("--repeats") + 1]) if "--repeats" in argv else 3
     legs = tuple(argv[argv.index("--legs") + 1].split(",")) if "--legs" in argv else LEGS
@@ -106,6 +191,13 @@ def main(argv):
     if not torch.cuda.is_available():
         raise SystemExit("bench_summary needs a HIP device")
     device = torch.device("cuda", 0)
+    indel = [leg for leg in legs if leg in INDEL_LEGS]
+    legs = tuple(leg for leg in legs if leg not in INDEL_LEGS)
+    shm_ok = os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK)
+    indel_result = indel_legs(indel, device, indel_bases, repeats, "/dev/shm" if shm_ok else None) if indel else None
+    if not legs:
+        print(json.dumps({"indel_structure": indel_result}))
+        return
     model, r, order, _ = shipped_snv_model(device)
     n_class = model.n_class
     shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) and shutil.disk_usage("/dev/shm").free > 100 * bases else None
@@ -296,7 +388,7 @@ def main(argv):
                            "rows_in_a_piece": float(kept["annot"]["annotations"][2][:, 0].sum()) if "annot" in kept else None},
            "calibration": {leg: {key: val for key, val in kept[leg]["calibration"].items() if key not in ("per_chromosome", "weights")}
                            for leg in ("calib", "calib_fit") if leg in kept},
-           "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}
+           "indel_structure": indel_result, "seconds": seconds, "split_seconds": splits, "files_in": "/dev/shm" if shm else "the temp directory"}
     print(json.dumps(res))
     if not agree:
         raise SystemExit("the in-flight summary differs from the table tools'")

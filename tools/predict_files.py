@@ -80,6 +80,17 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              empirical p-values (n + 1) / (R + 1); the lof count of a replicate adds the
                                                              stop-gained, splice and start-lost events of the same draw; it needs every
                                                              flag named here; not with --indel
+  --indel --summary PREFIX  --indel_transcripts BED12 --indel_kind insertion|deletion_start|deletion_end [--indel_lengths SPEC]
+                                  [--breakpoint_offset 0|1]  PREFIX.indel_structure.tsv: per transcript the expected and observed INDEL
+                                                             events of the model's kind by what they do to the transcript -- utr5,
+                                                             utr3, noncoding_exon, splice (a splice dinucleotide of an intron between
+                                                             CDS bases split or deleted), splice_utr (of any other intron), intron,
+                                                             start_lost (CDS offsets 0 .. 2), frameshift, inframe and cds_mixed (a
+                                                             class whose lengths hold both) --, expected_lof / observed_lof = splice +
+                                                             start_lost + frameshift and the _upper pair = that + cds_mixed.  SPEC: the
+                                                             lengths of mut_type 1, 2, .. (default 1,2,3,4,5,6,7-20 for 8 classes); the
+                                                             event's boundary is start + offset (default 1); alone or with the
+                                                             options above
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -95,7 +106,7 @@ from mural_amd.model.nn_utils import load_model  # noqa: E402
 
 _SUMMARY_OPTIONS = ("--summary", "--window_size", "--kmer_length", "--motif_length", "--annotations", "--strand", "--benchmark_regions", "--genomewide_mu", "--m_proportion", "--g_proportion",
                     "--scale_factor", "--n_bins", "--fit_calibrator", "--simulate", "--seed", "--write_simulated", "--transcripts", "--codon_table",
-                    "--alt_order")
+                    "--alt_order", "--indel_transcripts", "--indel_kind", "--indel_lengths", "--breakpoint_offset")
 _PAIR_OPTIONS = ("--model_set", "--scale_factors")      # NAME CLASS=VALUE [CLASS=VALUE ..]
 _VALUE_OPTIONS = ("--regions", "--focal", "--context", "--mutations") + _PAIR_OPTIONS + _SUMMARY_OPTIONS
 
@@ -187,7 +198,18 @@ def _summary_options(flags, values, model_type="snv"):
             "write_simulated": tuple(int(r) for r in values.get("--write_simulated", [])), "transcripts": one("--transcripts", str),
             "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str),
             "simulate_consequences": "--simulate_consequences" in flags, "transcript_structure": "--transcript_structure" in flags,
-            "simulate_structure": "--simulate_structure" in flags}
+            "simulate_structure": "--simulate_structure" in flags, "indel_transcripts": one("--indel_transcripts", str),
+            "indel_kind": one("--indel_kind", str), "indel_lengths": one("--indel_lengths", str),
+            "breakpoint_offset": one("--breakpoint_offset", str)}
+    if opts["indel_transcripts"] is not None and model_type != "indel":
+        raise SystemExit("--indel_transcripts takes INDEL rows: it goes with --indel")
+    if opts["indel_transcripts"] is not None and opts["indel_kind"] is None:
+        raise SystemExit("--indel_transcripts needs --indel_kind insertion|deletion_start|deletion_end: the events the model predicts")
+    if opts["indel_transcripts"] is None and (opts["indel_kind"] is not None or opts["indel_lengths"] is not None
+                                              or opts["breakpoint_offset"] is not None):
+        raise SystemExit("--indel_kind / --indel_lengths / --breakpoint_offset go with --indel_transcripts BED12")
+    if opts["indel_transcripts"] is not None and opts["summary"] is None:
+        raise SystemExit("--indel_transcripts needs --summary PREFIX: the prefix of the file it writes")
     if opts["simulate_structure"] and model_type == "indel":
         raise SystemExit("--simulate_structure takes SNV rows: it does not go with --indel")
     if opts["simulate_structure"] and opts["transcripts"] is None:
@@ -247,7 +269,8 @@ def _summary_options(flags, values, model_type="snv"):
     if opts["transcripts"] is not None and model_type == "indel":
         raise SystemExit("--transcripts takes SNV rows: it does not go with --indel")
     if (opts["summary"] is not None and not opts["windows"] and not opts["kmers"] and not opts["motifs"] and not opts["calibration"]
-            and opts["annotations"] is None and opts["simulate"] is None and opts["transcripts"] is None):
+            and opts["annotations"] is None and opts["simulate"] is None and opts["transcripts"] is None
+            and opts["indel_transcripts"] is None):
         raise SystemExit("--summary PREFIX needs a --window_size, a --kmer_length, a --motif_length, --calibration_metrics, --annotations, "
                          "--simulate or --transcripts")
     if opts["transcripts"] is not None:
@@ -258,6 +281,17 @@ def _summary_options(flags, values, model_type="snv"):
             opts["alt_order"] = check_alt_order(opts["alt_order"])
         except (OSError, ValueError) as e:
             raise SystemExit(f"--transcripts: {e}") from None
+    if opts["indel_transcripts"] is not None:
+        from mural_amd.tables import check_breakpoint_offset, check_indel_kind, check_indel_lengths, read_transcript_structure
+        try:
+            opts["indel_kind"] = check_indel_kind(opts["indel_kind"])
+            if opts["indel_lengths"] is not None:
+                opts["indel_lengths"] = check_indel_lengths(opts["indel_lengths"])
+            offset = opts["breakpoint_offset"]
+            opts["breakpoint_offset"] = 1 if offset is None else check_breakpoint_offset(int(offset) if offset.isdigit() else offset)
+            opts["indel_transcripts"] = read_transcript_structure(opts["indel_transcripts"])
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--indel_transcripts: {e}") from None
     if opts["annotations"] is not None:
         from mural_amd.tables import read_annotations
         try:
@@ -323,7 +357,9 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               simulate_write=opts["write_simulated"], simulate_labels=opts.get("labelled", True), transcripts=opts["transcripts"], alt_order=opts["alt_order"],
                               transcript_labels=opts.get("labelled", True), simulate_transcripts=opts["simulate_consequences"],
                               transcript_structure=opts["transcript_structure"], simulate_structure=opts["simulate_structure"],
-                              **sink_chain)
+                              **(dict(indel_transcripts=opts["indel_transcripts"], indel_kind=opts["indel_kind"],
+                                      indel_lengths=opts["indel_lengths"], breakpoint_offset=opts["breakpoint_offset"])
+                                 if opts["indel_transcripts"] is not None else {}), **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
 
