@@ -1261,6 +1261,73 @@ size_t mural_simulate_txstruct_workspace_bytes(int64_t n_features);
 int mural_simulate_txstruct_rows(const MuralSimulateTxstructRows* s, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The simulated null of the INDEL structure table of a shard while it is on the device (SummarySink(simulate=R,
+ * indel_transcripts=..., indel_kind=..., simulate_indel_structure=True) in flight,
+ * tables.simulate_indel_structure_table from a written table; csrc/simulate_txindel.hip;
+ * mural_amd.summaries.simulate_txindel_host is the specification).  Rows, strand, chrom_key, n_rep and seed as
+ * mural_simulate_annot_rows, 2 <= n_class <= 8 (the bound of the simulation's draw); kind, breakpoint_offset,
+ * chrom_length, class_len, the items with their links, the segments and the transcripts as mural_summary_txindel_rows.
+ *   DRAW.  That of mural_simulate_annot_rows, unchanged: Philox4x32-10 with key (seed lo, seed hi) and counter (start lo,
+ *   start hi, chrom_key, (replicate >> 2) | strand << 31), replicate r reading word r & 3 as u; q_c = floor(p_c 2^32) with
+ *   p_c >= 1 taken as 1, cum_c = min(q_1 + .. + q_c, 2^32); the class is the smallest c >= 1 with u < cum_c, 0 where there is
+ *   none.  A row with a NaN, negative or infinite p_c (status bit 3) or a negative start (bit 0) draws class 0 in every
+ *   replicate; a start below the row before it inside the call sets bit 2.  Two rows of equal chromosome, start and strand
+ *   draw the same value.
+ *   BIN.  That of mural_summary_txindel_rows, unchanged (txindel_bins.h): the home base h = start + breakpoint_offset - 1
+ *   for an insertion and a deletion end, start + breakpoint_offset for a deletion start; a row counts for every transcript
+ *   whose span holds h (an insertion: and base j = start + breakpoint_offset), once, through the item that holds h; the bin
+ *   of class c is the insertion's site or frame bin, or what the L = lo(c) deleted bases meet on the walk over feat_next /
+ *   feat_prev, clipped to the span and to chrom_length.  Broken links end a walk; a home item that is empty, of an unknown
+ *   kind or a CDS part without its segment is skipped, and so is an insertion whose second item is one.
+ *   table [n_transcripts][10][n_rep] of unsigned 32-bit cells: cell [t][b][r] += the rows that transcript t counts whose
+ *   replicate-r draw is a class c >= 1 with bin(row, t, c) == b.  Class 0 counts nowhere; no label is read.  Zeroed by the
+ *   caller once, it accumulates over calls, parts and chromosomes, and is a function of the SET of rows and the seed alone,
+ *   bit for bit.  A cell takes at most one count per row per call: with n <= 2^31 it cannot wrap in a call; across calls
+ *   the caller keeps the rows a transcript counts below 2^32.
+ * MURAL_E_INVALID, before the first launch: n_class outside 2 .. 8, n_rep outside 1 .. 2^20, n > 2^31, n_features > 2^22,
+ * n_segments > 2^22, kind outside 0 .. 2, breakpoint_offset outside 0 .. 1, a class_len pair outside 1 <= lo <= hi <= 64.
+ * The loop bounds are mural_simulate_chunk_rows(), mural_simulate_grid_waves() and mural_simulate_scan_threads(): the grid
+ * strides over units of (chunk of a home item, group of up to 16 blocks of 64 replicates); a row's bins are formed once per
+ * unit.  ws: mural_simulate_txindel_workspace_bytes(n_features) bytes (24 per item), 8-byte aligned; MURAL_E_WORKSPACE when
+ * smaller.  n == 0 launches nothing; n_features == 0 only checks the rows; n_segments == 0 is legal.  Launches on `stream`:
+ * no synchronisation, no read-back, no floating-point atomics; draws and bins are recomputed, never stored.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* prob;          /* dev [n][prob_stride], float (prob_f64 = 0) or double; columns 1 .. n_class - 1 are read        */
+  int32_t prob_f64, n_class; /* 2 <= n_class <= 8 */
+  int64_t prob_stride;       /* elements */
+  const int64_t* start;      /* dev [n], ascending */
+  const uint8_t* strand;     /* dev [n], 1 = '-', or NULL */
+  int64_t n;
+  uint32_t chrom_key;
+  int32_t n_rep;
+  uint64_t seed;
+  int32_t kind, breakpoint_offset;
+  int64_t chrom_length;      /* or -1: not known */
+  int32_t class_len[16][2];  /* [c] = { lo, hi }, c >= 1 */
+  const int64_t* seg_b0;     /* dev [n_segments] */
+  const int64_t* seg_b1;     /* dev [n_segments] */
+  const int64_t* seg_cds0;   /* dev [n_segments] */
+  const int32_t* seg_tx;     /* dev [n_segments] */
+  int64_t n_segments;
+  const uint8_t* tx_strand;  /* dev [n_transcripts] */
+  const int64_t* tx_cds_len; /* dev [n_transcripts] */
+  int32_t n_transcripts, reserved;
+  uint32_t* table;           /* dev [n_transcripts][10][n_rep] */
+  int32_t* status;           /* dev [1] */
+  const int64_t* feat_b0;    /* dev [n_features] */
+  const int64_t* feat_b1;    /* dev [n_features] */
+  const int32_t* feat_tx;    /* dev [n_features] */
+  const uint8_t* feat_kind;  /* dev [n_features] */
+  const int32_t* feat_seg;   /* dev [n_features] */
+  const int32_t* feat_prev;  /* dev [n_features] */
+  const int32_t* feat_next;  /* dev [n_features] */
+  int64_t n_features;
+} MuralSimulateTxindelRows;
+size_t mural_simulate_txindel_workspace_bytes(int64_t n_features);
+int mural_simulate_txindel_rows(const MuralSimulateTxindelRows* s, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Training-mode ops of the INDEL U-Net (MuRaL/model/model_indel.py:6-19, :151-176 under model.train()): a general
  * Conv1d (stride, zero padding, input upsampled by `up` = nn.Upsample(scale_factor) in front of the conv) with its
  * backward, and the element-wise activations.  x [B][Cin][Lin], W [Cout][Cin][K] (torch layout), y [B][Cout][Lout].

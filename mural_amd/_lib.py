@@ -175,6 +175,17 @@ class MuralSimulateTxstructRows(C.Structure):
                                                    ("feat_kind", C.c_void_p), ("feat_seg", C.c_void_p), ("n_features", C.c_int64)]
 
 
+class MuralSimulateTxindelRows(C.Structure):
+    _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
+                ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("n_rep", C.c_int32), ("seed", C.c_uint64),
+                ("kind", C.c_int32), ("breakpoint_offset", C.c_int32), ("chrom_length", C.c_int64), ("class_len", (C.c_int32 * 2) * 16),
+                ("seg_b0", C.c_void_p), ("seg_b1", C.c_void_p), ("seg_cds0", C.c_void_p), ("seg_tx", C.c_void_p), ("n_segments", C.c_int64),
+                ("tx_strand", C.c_void_p), ("tx_cds_len", C.c_void_p), ("n_transcripts", C.c_int32), ("reserved", C.c_int32),
+                ("table", C.c_void_p), ("status", C.c_void_p), ("feat_b0", C.c_void_p), ("feat_b1", C.c_void_p), ("feat_tx", C.c_void_p),
+                ("feat_kind", C.c_void_p), ("feat_seg", C.c_void_p), ("feat_prev", C.c_void_p), ("feat_next", C.c_void_p),
+                ("n_features", C.c_int64)]
+
+
 class MuralSimulateRows(C.Structure):
     _fields_ = [("prob", C.c_void_p), ("prob_f64", C.c_int32), ("n_class", C.c_int32), ("prob_stride", C.c_int64), ("start", C.c_void_p),
                 ("strand", C.c_void_p), ("n", C.c_int64), ("chrom_key", C.c_uint32), ("replicate", C.c_int32), ("seed", C.c_uint64),
@@ -365,6 +376,8 @@ PROTOTYPES = {
     "mural_simulate_conseq_rows": (C.c_int, [C.POINTER(MuralSimulateConseqRows), VP, C.c_size_t, VP]),
     "mural_simulate_txstruct_workspace_bytes": (C.c_size_t, [I64]),
     "mural_simulate_txstruct_rows": (C.c_int, [C.POINTER(MuralSimulateTxstructRows), VP, C.c_size_t, VP]),
+    "mural_simulate_txindel_workspace_bytes": (C.c_size_t, [I64]),
+    "mural_simulate_txindel_rows": (C.c_int, [C.POINTER(MuralSimulateTxindelRows), VP, C.c_size_t, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

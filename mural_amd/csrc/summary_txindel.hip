@@ -3,6 +3,8 @@
 // of a BED12 file the label counts and the sums of the probabilities of the INDEL rows whose home base lies inside [chromStart,
 // chromEnd), split into utr5, utr3, noncoding_exon, splice, splice_utr, intron, start_lost, frameshift, inframe and cds_mixed.
 // summaries.summary_txindel_host is the specification; DESIGN.md section 3.25.  No genome is read: nothing here depends on sequence.
+// The bin rule itself -- an item as a transcript sees it, an insertion's site, the bin of a class with the deletion's walk -- lives in
+// txindel_bins.h, which csrc/simulate_txindel.hip shares.
 //
 // The items are those of csrc/summary_txstruct.hip (tables.read_transcript_structure) with two link arrays, feat_prev / feat_next, the
 // same transcript's neighbouring items in genomic order (tables.structure_links).  The stages are those of csrc/summary_txstruct.hip:
@@ -26,6 +28,7 @@
 #include "kmer_key.h"
 #include "row_chunks.h"
 #include "summary_quant.h"
+#include "txindel_bins.h"
 
 namespace mural {
 namespace {
@@ -38,15 +41,8 @@ constexpr int64_t TI_GRID_WAVES = 8192;           // waves of the reduce kernel'
 constexpr int64_t TI_MAX_ROWS = 1ll << 31;        // per call (the fold bound above)
 constexpr int64_t TI_MAX_FEATURES = 1ll << 22;    // per call
 constexpr int TI_MAX_CLASS = 16;
-constexpr int TI_MAX_LEN = 64;
-constexpr int TI_BINS = 10;      // utr5, utr3, noncoding_exon, splice, splice_utr, intron, start_lost, frameshift, inframe, cds_mixed
 constexpr int TI_CELL_WORDS = 3 * TI_BINS;        // per transcript: [bin][label count | sum of hi | sum of lo]
 constexpr int TI_COUNT_SHIFT = 48;                // a lane's label count rides above its sum of hi limbs
-constexpr int TI_KIND_CODING_INTRON = 3, TI_KIND_INTRON = 4, TI_KIND_CDS = 5;
-constexpr int TI_INSERTION = 0, TI_DELETION_START = 1;      // (2: deletion end)
-constexpr int TI_FRAMED = 0, TI_MIXED = 1;                  // (2: a range without a multiple of 3 -- frameshift)
-constexpr int TI_FRAME = -1;                                // an insertion whose bin is its class's frame bin
-enum : uint32_t { TI_T_START = 1, TI_T_SPLICE = 2, TI_T_SPLICE_UTR = 4, TI_T_NONCODING = 8, TI_T_UTR5 = 16, TI_T_UTR3 = 32 };
 
 struct TxindelArgs {
   const void* prob;
@@ -113,57 +109,6 @@ __global__ __launch_bounds__(TI_SCAN_THREADS) void summary_txindel_scan_kernel(i
   if (threadIdx.x == 0) v[m] = total;
 }
 
-struct TiItem {
-  int64_t b0, b1, cds0;
-  int kind;
-  bool ok;
-};
-
-// Item f as transcript tx sees it; !ok: f is out of range, names another transcript, is empty, has an unknown kind or is a CDS part
-// without its segment.  Nothing is read before its index is checked.
-__device__ __forceinline__ TiItem txindel_item(const TxindelArgs& A, int64_t f, int32_t tx) {
-  TiItem it{0, 0, 0, 0, false};
-  if (f < 0 || f >= A.n_feat) return it;
-  if (A.feat_tx[f] != tx) return it;
-  it.b0 = A.feat_b0[f], it.b1 = A.feat_b1[f], it.kind = A.feat_kind[f];
-  if (it.b1 <= it.b0 || it.kind > TI_KIND_CDS) return it;
-  if (it.kind == TI_KIND_CDS) {
-    const int64_t seg = A.feat_seg[f];
-    if (seg < 0 || seg >= A.n_seg) return it;
-    if (A.seg_b0[seg] != it.b0 || A.seg_b1[seg] != it.b1 || A.seg_tx[seg] != tx) return it;
-    it.cds0 = A.seg_cds0[seg];
-  }
-  it.ok = true;
-  return it;
-}
-
-// the frame bin of a class of frame mode `mode`, n CDS bases affected
-__device__ __forceinline__ int txindel_frame_bin(int mode, int64_t n) {
-  return mode == TI_MIXED ? 9 : (mode != TI_FRAMED || n % 3 != 0) ? 7 : 8;
-}
-
-// the CDS rule at a boundary with x CDS bases 5' of it
-__device__ __forceinline__ int txindel_cds_rule(int64_t x, int64_t cds_len) {
-  return x == 0 ? 0 : x == cds_len ? 1 : x <= 2 ? 6 : TI_FRAME;
-}
-
-// what the deleted bases [d0, d1) meet in item `it`: the CDS bases, and the touch flags
-__device__ __forceinline__ void txindel_meet(const TiItem& it, bool minus, int64_t d0, int64_t d1, int64_t& n_cds, uint32_t& touch) {
-  const int64_t u = max(it.b0, d0), v = min(it.b1, d1);
-  if (u >= v) return;
-  if (it.kind == TI_KIND_CDS) {
-    n_cds += v - u;
-    if (it.cds0 < 3) {      // the item holds CDS offsets cds0 .. 2: its 5'-most 3 - cds0 bases
-      const bool hit = minus ? v > max(it.b0, it.b1 - (3 - it.cds0)) : u < min(it.b1, it.b0 + (3 - it.cds0));
-      if (hit) touch |= TI_T_START;
-    }
-  } else if (it.kind >= TI_KIND_CODING_INTRON) {
-    if (it.b1 - it.b0 >= 4 && (u < it.b0 + 2 || v > it.b1 - 2)) touch |= it.kind == TI_KIND_CODING_INTRON ? TI_T_SPLICE : TI_T_SPLICE_UTR;
-  } else {
-    touch |= it.kind == 2 ? TI_T_NONCODING : it.kind == 0 ? TI_T_UTR5 : TI_T_UTR3;
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(TI_THREADS) void summary_txindel_reduce_kernel(TxindelArgs A, const int64_t* __restrict__ row0,
                                                                             const int64_t* __restrict__ row1,
@@ -207,51 +152,15 @@ __global__ __launch_bounds__(TI_THREADS) void summary_txindel_reduce_kernel(Txin
         live = txindel_row<T>(A, i, lab) == 0 && h >= home.b0 && h < home.b1;
       }
       int site = 5;      // an insertion's bin, or TI_FRAME
-      if (A.kind == TI_INSERTION) {
-        const bool gap_a = home.kind == TI_KIND_CODING_INTRON || home.kind == TI_KIND_INTRON;
-        if (j < home.b1) {      // bases j - 1 and j in one item
-          if (home.kind < TI_KIND_CODING_INTRON) site = home.kind;
-          else if (gap_a) site = (home.b1 - home.b0 >= 4 && (j == home.b0 + 1 || j == home.b1 - 1)) ? (home.kind == TI_KIND_CODING_INTRON ? 3 : 4) : 5;
-          else site = txindel_cds_rule(home.cds0 + (minus ? home.b1 - j : j - home.b0), cds_len);
-        } else {                // on the boundary of two items: base j must lie in the span as well
-          live = live && behind.ok;
-          const bool gap_b = behind.kind == TI_KIND_CODING_INTRON || behind.kind == TI_KIND_INTRON;
-          if (home.kind == TI_KIND_CDS) site = txindel_cds_rule(home.cds0 + (minus ? 0 : home.b1 - home.b0), cds_len);
-          else if (behind.kind == TI_KIND_CDS) site = txindel_cds_rule(behind.cds0 + (minus ? behind.b1 - behind.b0 : 0), cds_len);
-          else if (gap_a && gap_b) site = 5;
-          else site = gap_a ? behind.kind : home.kind;      // a gap yields to an exon part
-        }
-      }
+      if (A.kind == TI_INSERTION) site = txindel_insertion_site(home, behind, minus, cds_len, j, live);
       const T* __restrict__ p_row = static_cast<const T*>(A.prob) + i * A.prob_stride;      // (read in live lanes only)
       for (int c = 1; c < A.n_class; ++c) {
         const uint32_t w = cls_words[c];
-        const int64_t len = w & 0xFF;
-        const int mode = (int)(w >> 8);
         u64 hi = 0, lo = 0;
         int bin = TI_BINS;      // not counted
         if (live) {
           quantise_prob((double)p_row[c], hi, lo);
-          if (A.kind == TI_INSERTION) {
-            bin = site == TI_FRAME ? txindel_frame_bin(mode, len) : site;
-          } else {
-            const bool fwd = A.kind == TI_DELETION_START;
-            int64_t d0 = fwd ? j : max(j - len, (int64_t)0), d1 = fwd ? j + len : j;
-            if (fwd && A.chrom_len >= 0) d1 = max(min(d1, A.chrom_len), j + 1);      // (the home base stays)
-            int64_t n_cds = 0;
-            uint32_t touch = 0;
-            txindel_meet(home, minus, d0, d1, n_cds, touch);
-            TiItem cur = home;
-            int64_t at = f;
-            while (fwd ? cur.b1 < d1 : cur.b0 > d0) {      // at most 64 steps: every step moves on by a base or more
-              at = fwd ? A.feat_next[at] : A.feat_prev[at];
-              const TiItem it = txindel_item(A, at, tx);
-              if (!it.ok || (fwd ? it.b0 != cur.b1 : it.b1 != cur.b0)) break;
-              txindel_meet(it, minus, d0, d1, n_cds, touch);
-              cur = it;
-            }
-            bin = (touch & TI_T_START) ? 6 : (touch & TI_T_SPLICE) ? 3 : n_cds > 0 ? txindel_frame_bin(mode, n_cds) : (touch & TI_T_SPLICE_UTR) ? 4
-                : (touch & TI_T_NONCODING) ? 2 : (touch & TI_T_UTR5) ? 0 : (touch & TI_T_UTR3) ? 1 : 5;
-          }
+          bin = txindel_class_bin(A, f, tx, home, minus, site, j, w);
           hi |= (u64)(lab == c) << TI_COUNT_SHIFT;
         }
 #pragma unroll
@@ -327,10 +236,7 @@ extern "C" int mural_summary_txindel_rows(const MuralSummaryTxindelRows* s, void
   A.feat_prev = s->feat_prev, A.feat_next = s->feat_next, A.n_feat = s->n_features;
   A.tx_strand = s->tx_strand, A.tx_cds_len = s->tx_cds_len;
   for (int c = 1; c < s->n_class; ++c) {
-    const int lo = s->class_len[c][0], hi = s->class_len[c][1];
-    // framed: one length; mixed: the range holds a multiple of 3 and another length; otherwise every length shifts the frame
-    const int mode = lo == hi ? TI_FRAMED : (hi / 3 > (lo - 1) / 3) ? TI_MIXED : 2;
-    A.cls[c] = (uint32_t)lo | (uint32_t)mode << 8;
+    A.cls[c] = txindel_class_word(s->class_len[c][0], s->class_len[c][1]);
   }
   A.table = reinterpret_cast<u64*>(s->table), A.rows = reinterpret_cast<u64*>(s->rows), A.status = s->status;
   WsArena ws(ws_ptr);

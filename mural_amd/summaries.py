@@ -23,7 +23,8 @@ from .tables import (annotation_meta, annotation_output_names, check_alt_order, 
                      motif_output_names, mu_scaling_factor, print_scaling_factor, read_annotations, read_regions, regional_output_names,
                      strand_mode, write_annotation_outputs, write_kmer_outputs, write_motif_outputs, write_regional_outputs,
                      check_breakpoint_offset, check_indel_kind, check_indel_lengths, indel_structure_output_name, structure_links,
-                     write_indel_structure_outputs)
+                     write_indel_structure_outputs, indel_structure_cells_from_sums, indel_structure_simulation_output_name,
+                     write_indel_structure_simulation_outputs)
 
 
 def _refuse_fit_on_calibrated(calibrated):
@@ -667,6 +668,95 @@ def _txindel_frame_bin(lo, hi, n):
     return np.full(np.shape(n), 9 if hi // 3 > (lo - 1) // 3 else 7, np.int64)
 
 
+def _txindel_pairs(start, segments, features, links, n_tx, kind, off, cl, chrom_length):
+    """The one item walk and bin rule of the INDEL structure tables on the host, shared by ``summary_txindel_host`` and
+    ``simulate_txindel_host``: for rows sorted by start, a chromosome's `features`, its `segments` (or None) and `links` (None: built
+    here), the checked `kind` 0 / 1 / 2, breakpoint offset `off` and class lengths `cl` int [n_class][2], yields (i, tx, counted, bins)
+    per pass of at most ``_CONSEQ_PAIRS`` (home item, row) pairs -- the row indices, the home item's transcript, whether the transcript
+    counts the row (an insertion on the span's last boundary does not) and bins int64 [pairs][n_class - 1], the bin 0 .. 9 of classes
+    1 .. n_class - 1 by the rule ``summary_txindel_host`` states.  Home items that a walk may not stand on are skipped."""
+    k = len(cl)
+    b0, b1 = np.asarray(features["feat_b0"], np.int64), np.asarray(features["feat_b1"], np.int64)
+    f_tx, f_kind, f_seg = (np.asarray(features[key], np.int64) for key in ("feat_tx", "feat_kind", "feat_seg"))
+    prev, nxt = (np.asarray(x, np.int64) for x in (structure_links(features) if links is None else links))
+    tx_minus, tx_len = np.asarray(features["tx_strand"]) != 0, np.asarray(features["tx_cds_len"], np.int64)
+    n_feat = len(b0)
+    # the items a walk may stand on, and the CDS offset of a CDS part's first base in transcript orientation
+    item_ok = (b1 > b0) & (f_kind <= 5) & (f_tx >= 0) & (f_tx < n_tx)
+    cds0, is_cds = np.zeros(n_feat, np.int64), f_kind == 5
+    if is_cds.any():
+        n_seg = 0 if segments is None else len(segments["seg_b0"])
+        good = is_cds & (f_seg >= 0) & (f_seg < n_seg)
+        if n_seg:
+            s = np.where(good, f_seg, 0)
+            good &= ((np.asarray(segments["seg_b0"], np.int64)[s] == b0) & (np.asarray(segments["seg_b1"], np.int64)[s] == b1)
+                     & (np.asarray(segments["seg_tx"], np.int64)[s] == f_tx))
+            cds0 = np.where(good, np.asarray(segments["seg_cds0"], np.int64)[s], 0)
+        item_ok &= ~is_cds | good
+    home = np.nonzero(item_ok)[0]
+    shift = off - (0 if kind == 1 else 1)
+
+    def neighbour(cur, tx, step):
+        """(index, usable) of the item behind `cur` (step: the link array) for transcript tx."""
+        at = step[cur]
+        inside = (at >= 0) & (at < n_feat)
+        at = np.where(inside, at, 0)
+        return at, inside & item_ok[at] & (f_tx[at] == tx)
+
+    def cds_rule(x, cds_len):
+        return np.where(x == 0, 0, np.where(x == cds_len, 1, np.where(x <= 2, 6, -1)))
+
+    for s, i in _item_row_pairs(start + shift, b0[home], b1[home]):
+        f = home[s]
+        j, tx, a, b, kd = start[i] + off, f_tx[f], b0[f], b1[f], f_kind[f]
+        minus, cds_len = tx_minus[tx], tx_len[tx]
+        if kind == 0:
+            at, usable = neighbour(f, tx, nxt)
+            usable &= b0[at] == b
+            same, kb = j < b, f_kind[at]
+            gap_a, gap_b = (kd == 3) | (kd == 4), (kb == 3) | (kb == 4)
+            split = (b - a >= 4) & ((j == a + 1) | (j == b - 1))
+            site_same = np.where(kd < 3, kd, np.where(gap_a, np.where(split, np.where(kd == 3, 3, 4), 5),
+                                                      cds_rule(cds0[f] + np.where(minus, b - j, j - a), cds_len)))
+            site_diff = np.where(kd == 5, cds_rule(cds0[f] + np.where(minus, 0, b - a), cds_len),
+                                 np.where(kb == 5, cds_rule(cds0[at] + np.where(minus, b1[at] - b0[at], 0), cds_len),
+                                          np.where(gap_a & gap_b, 5, np.where(gap_a, kb, kd))))
+            site, counted = np.where(same, site_same, site_diff), same | usable
+        else:
+            counted = np.ones(len(i), bool)
+        bins_all = np.empty((len(i), k - 1), np.int64)
+        for c in range(1, k):
+            c_lo, c_hi = int(cl[c, 0]), int(cl[c, 1])
+            if kind == 0:
+                bins = np.where(site < 0, _txindel_frame_bin(c_lo, c_hi, np.full(len(i), c_lo, np.int64)), site)
+            else:
+                fwd = kind == 1
+                d0, d1 = (j, j + c_lo) if fwd else (np.maximum(j - c_lo, 0), j)
+                if fwd and chrom_length is not None and int(chrom_length) >= 0:
+                    d1 = np.maximum(np.minimum(d1, int(chrom_length)), j + 1)
+                n_cds, touch = np.zeros(len(i), np.int64), np.zeros(len(i), np.int64)
+                cur, on = f.copy(), np.ones(len(i), bool)
+                for _ in range(_TXINDEL_MAX_WALK + 1):
+                    u, v = np.maximum(b0[cur], d0), np.minimum(b1[cur], d1)
+                    meets, ck, c0 = on & (u < v), f_kind[cur], cds0[cur]
+                    n_cds += np.where(meets & (ck == 5), v - u, 0)
+                    first = np.where(minus, v > np.maximum(b0[cur], b1[cur] - (3 - c0)), u < np.minimum(b1[cur], b0[cur] + (3 - c0)))
+                    sites = (b1[cur] - b0[cur] >= 4) & ((u < b0[cur] + 2) | (v > b1[cur] - 2))
+                    for bit, where in ((1, (ck == 5) & (c0 < 3) & first), (2, (ck == 3) & sites), (4, (ck == 4) & sites), (8, ck == 2),
+                                       (16, ck == 0), (32, ck == 1)):
+                        touch |= np.where(meets & where, bit, 0)
+                    on &= (b1[cur] < d1) if fwd else (b0[cur] > d0)
+                    if not on.any():
+                        break
+                    at, usable = neighbour(cur, tx, nxt if fwd else prev)
+                    on &= usable & ((b0[at] == b1[cur]) if fwd else (b1[at] == b0[cur]))
+                    cur = np.where(on, at, cur)
+                bins = np.where(touch & 1, 6, np.where(touch & 2, 3, np.where(n_cds > 0, _txindel_frame_bin(c_lo, c_hi, n_cds),
+                                np.where(touch & 4, 4, np.where(touch & 8, 2, np.where(touch & 16, 0, np.where(touch & 32, 1, 5)))))))
+            bins_all[:, c - 1] = bins
+        yield i, tx, counted, bins_all
+
+
 def summary_txindel_host(prob, start, label, n_class, segments, features, n_transcripts, kind, breakpoint_offset=1, class_len=None,
                          chrom_length=None, links=None, into=None):
     """The numpy twin of ``mural_summary_txindel_rows`` -- and its specification -- for INDEL rows (any order) of one chromosome: (table
@@ -715,91 +805,18 @@ def summary_txindel_host(prob, start, label, n_class, segments, features, n_tran
         return table, rows, status
     order = np.argsort(start[ok], kind="stable")
     hi, lo, start, lab = hi[ok][order], lo[ok][order], start[ok][order], lab[ok][order]
-    b0, b1 = np.asarray(features["feat_b0"], np.int64), np.asarray(features["feat_b1"], np.int64)
-    f_tx, f_kind, f_seg = (np.asarray(features[key], np.int64) for key in ("feat_tx", "feat_kind", "feat_seg"))
-    prev, nxt = (np.asarray(x, np.int64) for x in (structure_links(features) if links is None else links))
-    tx_minus, tx_len = np.asarray(features["tx_strand"]) != 0, np.asarray(features["tx_cds_len"], np.int64)
-    n_feat = len(b0)
-    # the items a walk may stand on, and the CDS offset of a CDS part's first base in transcript orientation
-    item_ok = (b1 > b0) & (f_kind <= 5) & (f_tx >= 0) & (f_tx < n_tx)
-    cds0, is_cds = np.zeros(n_feat, np.int64), f_kind == 5
-    if is_cds.any():
-        n_seg = 0 if segments is None else len(segments["seg_b0"])
-        good = is_cds & (f_seg >= 0) & (f_seg < n_seg)
-        if n_seg:
-            s = np.where(good, f_seg, 0)
-            good &= ((np.asarray(segments["seg_b0"], np.int64)[s] == b0) & (np.asarray(segments["seg_b1"], np.int64)[s] == b1)
-                     & (np.asarray(segments["seg_tx"], np.int64)[s] == f_tx))
-            cds0 = np.where(good, np.asarray(segments["seg_cds0"], np.int64)[s], 0)
-        item_ok &= ~is_cds | good
-    home = np.nonzero(item_ok)[0]
-    shift = off - (0 if kind == 1 else 1)
     flat_table, flat_rows = table.reshape(-1), rows.reshape(-1)
-
-    def neighbour(cur, tx, step):
-        """(index, usable) of the item behind `cur` (step: the link array) for transcript tx."""
-        at = step[cur]
-        inside = (at >= 0) & (at < n_feat)
-        at = np.where(inside, at, 0)
-        return at, inside & item_ok[at] & (f_tx[at] == tx)
-
-    def cds_rule(x, cds_len):
-        return np.where(x == 0, 0, np.where(x == cds_len, 1, np.where(x <= 2, 6, -1)))
-
-    for s, i in _item_row_pairs(start + shift, b0[home], b1[home]):
-        f = home[s]
-        j, tx, a, b, kd = start[i] + off, f_tx[f], b0[f], b1[f], f_kind[f]
-        minus, cds_len = tx_minus[tx], tx_len[tx]
-        if kind == 0:
-            at, usable = neighbour(f, tx, nxt)
-            usable &= b0[at] == b
-            same, kb = j < b, f_kind[at]
-            gap_a, gap_b = (kd == 3) | (kd == 4), (kb == 3) | (kb == 4)
-            split = (b - a >= 4) & ((j == a + 1) | (j == b - 1))
-            site_same = np.where(kd < 3, kd, np.where(gap_a, np.where(split, np.where(kd == 3, 3, 4), 5),
-                                                      cds_rule(cds0[f] + np.where(minus, b - j, j - a), cds_len)))
-            site_diff = np.where(kd == 5, cds_rule(cds0[f] + np.where(minus, 0, b - a), cds_len),
-                                 np.where(kb == 5, cds_rule(cds0[at] + np.where(minus, b1[at] - b0[at], 0), cds_len),
-                                          np.where(gap_a & gap_b, 5, np.where(gap_a, kb, kd))))
-            site, counted = np.where(same, site_same, site_diff), same | usable
-        else:
-            counted = np.ones(len(i), bool)
+    for i, tx, counted, bins in _txindel_pairs(start, segments, features, links, n_tx, kind, off, cl, chrom_length):
+        ic = i[counted]
         for c in range(1, k):
-            c_lo, c_hi = int(cl[c, 0]), int(cl[c, 1])
-            if kind == 0:
-                bins = np.where(site < 0, _txindel_frame_bin(c_lo, c_hi, np.full(len(i), c_lo, np.int64)), site)
-            else:
-                fwd = kind == 1
-                d0, d1 = (j, j + c_lo) if fwd else (np.maximum(j - c_lo, 0), j)
-                if fwd and chrom_length is not None and int(chrom_length) >= 0:
-                    d1 = np.maximum(np.minimum(d1, int(chrom_length)), j + 1)
-                n_cds, touch = np.zeros(len(i), np.int64), np.zeros(len(i), np.int64)
-                cur, on = f.copy(), np.ones(len(i), bool)
-                for _ in range(_TXINDEL_MAX_WALK + 1):
-                    u, v = np.maximum(b0[cur], d0), np.minimum(b1[cur], d1)
-                    meets, ck, c0 = on & (u < v), f_kind[cur], cds0[cur]
-                    n_cds += np.where(meets & (ck == 5), v - u, 0)
-                    first = np.where(minus, v > np.maximum(b0[cur], b1[cur] - (3 - c0)), u < np.minimum(b1[cur], b0[cur] + (3 - c0)))
-                    sites = (b1[cur] - b0[cur] >= 4) & ((u < b0[cur] + 2) | (v > b1[cur] - 2))
-                    for bit, where in ((1, (ck == 5) & (c0 < 3) & first), (2, (ck == 3) & sites), (4, (ck == 4) & sites), (8, ck == 2),
-                                       (16, ck == 0), (32, ck == 1)):
-                        touch |= np.where(meets & where, bit, 0)
-                    on &= (b1[cur] < d1) if fwd else (b0[cur] > d0)
-                    if not on.any():
-                        break
-                    at, usable = neighbour(cur, tx, nxt if fwd else prev)
-                    on &= usable & ((b0[at] == b1[cur]) if fwd else (b1[at] == b0[cur]))
-                    cur = np.where(on, at, cur)
-                bins = np.where(touch & 1, 6, np.where(touch & 2, 3, np.where(n_cds > 0, _txindel_frame_bin(c_lo, c_hi, n_cds),
-                                np.where(touch & 4, 4, np.where(touch & 8, 2, np.where(touch & 16, 0, np.where(touch & 32, 1, 5)))))))
-            ic, cell = i[counted], (tx * (3 * TXINDEL_BINS) + 3 * bins)[counted]
+            cell = (tx * (3 * TXINDEL_BINS) + 3 * bins[:, c - 1])[counted]
             np.add.at(flat_table, cell, (lab[ic] == c).astype(np.uint64))
             np.add.at(flat_table, cell + 1, hi[ic, c - 1])
             np.add.at(flat_table, cell + 2, lo[ic, c - 1])
             # (per class: a pass holds up to 2^20 pairs, and 15 classes of them unfolded would bring a cell's lo limb to 2^64)
             _conseq_fold(table)
         np.add.at(flat_rows, 2 * tx[counted], np.uint64(1))
-        np.add.at(flat_rows, 2 * tx[counted] + 1, (lab[i[counted]] == 0).astype(np.uint64))
+        np.add.at(flat_rows, 2 * tx[counted] + 1, (lab[ic] == 0).astype(np.uint64))
     return table, rows, status
 
 
@@ -1083,6 +1100,98 @@ def simulate_txstruct_rows_device(table, status, acc, conseq_acc, name, n_transc
     C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
     s.table, s.status = table.data_ptr(), status.data_ptr()
     _lib.check(lib.mural_simulate_txstruct_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+
+
+def simulate_txindel_host(prob, start, strand, n_class, segments, features, n_transcripts, kind, chrom_key, seed, n_rep,
+                          breakpoint_offset=1, class_len=None, chrom_length=None, links=None, into=None):
+    """The numpy twin of ``mural_simulate_txindel_rows`` -- and its specification -- for INDEL rows (any order; no label is read) of one
+    chromosome: (counts uint32 [n_transcripts][10][n_rep], status).  Cell [t][b][r]: the rows that transcript t counts whose
+    replicate-r draw is a class c >= 1 with bin(row, t, c) == b; class 0 counts nowhere.  2 <= n_class <= 8, the bound of the
+    simulation's draw (``SIM_MAX_CLASS`` of csrc/simulate_draw.h).
+
+    DRAW.  ``simulate_rows_host``'s, unchanged: the Philox key (seed) and counter (start, chrom_key, replicate >> 2, the strand bit),
+    cum, ties, p_c >= 1 taken as 1.  A row with a NaN, negative or infinite p_c (status 8) or a negative start (status 1) draws class 0
+    in every replicate; a start below the row before it sets status 4.  A draw depends on (seed, chromosome, start, strand, replicate)
+    alone, so two rows with equal chromosome, start and strand -- two events recorded at one position -- draw the SAME value, as
+    DESIGN.md section 3.20 documents for every simulation here: their counts move together, they are not independent.
+    BIN.  ``summary_txindel_host``'s, unchanged, through the same item walk (``_txindel_pairs``): the home base by `kind` and
+    `breakpoint_offset`, the insertion on one item or on the boundary of two, the deletion's walk located by L = lo(c), the clipping
+    by `chrom_length`, what ends a walk, skipped home items; `segments`, `features`, `links`, `class_len` as there.  "Counted" is that
+    rule's as well: once per transcript whose span holds the home base (an insertion: and base j).
+    The table is a function of the SET of rows and the seed alone, bit for bit, for any parts, shards or ranks.  `into`: the table of
+    earlier parts and chromosomes, added to in place.
+
+    THE DEFINING IDENTITIES.  (a) For rows that both rules accept (finite p in [0, 1], start >= 0), cell [t][b][r] equals the observed
+    word [t][b][0] of ``summary_txindel_host`` run with label = ``simulate_rows_host(..)[:, r]``.  (b) ``simulate_indel_lof_counts`` of
+    this table gives, per replicate r, the observed_lof / observed_lof_upper of ``tables.write_indel_structure_outputs`` for a run
+    labelled with replicate r.  (c) Any split of the rows into parts, any permutation of rows with equal starts and any number of
+    ranks give the same bytes."""
+    k = int(n_class)
+    if not 2 <= k <= 8:
+        raise ValueError(f"simulate: the INDEL structure simulation takes rows of 2 .. 8 classes, the bound of the draw (SIM_MAX_CLASS = 8; "
+                         f"got {k})")
+    n_tx, R = int(n_transcripts), int(n_rep)
+    if not 1 <= R <= SIMULATE_MAX_REPLICATES:
+        raise ValueError("simulate: 1 .. 2^20 replicates")
+    kind, off, cl = check_indel_kind(kind), check_breakpoint_offset(breakpoint_offset), check_indel_lengths(class_len, k)
+    start = np.asarray(start, np.int64)
+    labels, status = simulate_rows_host(prob, start, strand, k, chrom_key, seed, np.arange(R), with_status=True)
+    if len(start) > 1 and (start[1:] < start[:-1]).any():
+        status |= 4
+    table = np.zeros((n_tx, TXINDEL_BINS, R), np.uint32) if into is None else into
+    if features is None or len(features["feat_b0"]) == 0 or len(start) == 0:
+        return table, status
+    order = np.argsort(start, kind="stable")
+    start, labels = start[order], labels[order]
+    flat = table.reshape(-1, R)
+    for i, tx, counted, bins in _txindel_pairs(start, segments, features, links, n_tx, kind, off, cl, chrom_length):
+        i, tx, bins = i[counted], tx[counted], bins[counted]
+        lab = labels[i].astype(np.int64)                                                 # [pairs][R]
+        lb = np.take_along_axis(bins, np.maximum(lab - 1, 0), axis=1)                    # the bin of the drawn class
+        for b in np.unique(bins):
+            hit = ((lab > 0) & (lb == b)).astype(np.uint32)
+            np.add.at(flat, tx * TXINDEL_BINS + b, hit)
+    return table, status
+
+
+def simulate_indel_lof_counts(counts):
+    """(lof, lof_upper) int64 [transcripts][R] of the simulated INDEL loss-of-function count from ``simulate_txindel_host``'s table
+    [transcripts][10][R]: lof = splice + start_lost + frameshift (bins 3 + 6 + 7) of the SAME draws, lof_upper = lof + cds_mixed (bin
+    9) -- the terms by which ``tables._indel_lof_cells`` forms observed_lof / observed_lof_upper."""
+    counts = np.asarray(counts)
+    if counts.ndim != 3 or counts.shape[1] != TXINDEL_BINS:
+        raise ValueError("simulate_indel_lof_counts: counts [transcripts][10][R]")
+    lof = counts[:, 3].astype(np.int64) + counts[:, 6] + counts[:, 7]
+    return lof, lof + counts[:, 9]
+
+
+def simulate_txindel_rows_device(table, status, acc, name, n_transcripts, kind, breakpoint_offset, class_len, chrom_length, dev, n_rep,
+                                 seed, *, prob, prob_f64, prob_stride, start, strand, n, n_class):
+    """One ``mural_simulate_txindel_rows`` call on device pointers into `table` (int32 [n_transcripts * 10 * n_rep]) and `status`, on
+    the item, link and segment arrays ``txindel_rows_device`` uploaded into `acc` for chromosome `name` just before; the workspace is
+    `acc`'s (24 bytes an item in both entries, and the launches of one stream run in order)."""
+    lib = _lib.lib()
+    on_dev = acc["features"][name]
+    seg_dev = acc["segments"].get(name)
+    n_feat = int(on_dev[0].shape[0])
+    need = int(lib.mural_simulate_txindel_workspace_bytes(n_feat))
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _lib.MuralSimulateTxindelRows()
+    s.prob, s.prob_f64, s.prob_stride, s.n_class = prob, int(prob_f64), int(prob_stride), int(n_class)
+    s.start, s.strand, s.n = start, strand, int(n)
+    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
+    s.kind, s.breakpoint_offset, s.chrom_length = int(kind), int(breakpoint_offset), -1 if chrom_length is None else int(chrom_length)
+    for c, (lo, hi) in enumerate(np.asarray(class_len).tolist()[:16]):
+        s.class_len[c][0], s.class_len[c][1] = lo, hi
+    if seg_dev is not None and seg_dev[0].shape[0]:
+        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx = (x.data_ptr() for x in seg_dev[:4])
+        s.n_segments = int(seg_dev[0].shape[0])
+    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg, s.feat_prev, s.feat_next = (x.data_ptr() for x in on_dev[:7])
+    s.n_features, s.n_transcripts = n_feat, int(n_transcripts)
+    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
+    s.table, s.status = table.data_ptr(), status.data_ptr()
+    _lib.check(lib.mural_simulate_txindel_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
 
 
 def simulate_pvalues(counts, observed=None):
@@ -2253,6 +2362,92 @@ class _StructureSimulationReducer:
         write_structure_simulation_outputs(*result[self.name], out_prefix)
 
 
+class _IndelStructureSimulationReducer:
+    """The simulated null of the INDEL structure table and of its loss-of-function counts (``simulate_txindel_host`` is the rule): per
+    transcript, INDEL structure bin and replicate the simulated count -- ONE uint32 table [transcripts][10][n_rep] on the host and one
+    per device, behind the INDEL structure reducer `struct`, whose item, link and segment arrays and workspace it uses, read back once.
+    A cell takes one count per row that its transcript counts: the run keeps those below 2^32, as the structure simulation does."""
+    name = "indel_structure_simulation"
+
+    def __init__(self, n_rep, seed, struct, table_bytes_max):
+        self.n_rep, self.seed, self.struct, self.table_bytes_max = int(n_rep), int(seed), struct, int(table_bytes_max)
+        if not 1 <= self.n_rep <= SIMULATE_MAX_REPLICATES:
+            raise ValueError("simulate: 1 .. 2^20 replicates")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError("simulate: the seed is an unsigned 64-bit integer")
+        need = len(struct.names) * TXINDEL_BINS * self.n_rep * 4
+        if need > self.table_bytes_max:
+            raise ValueError(f"simulate: the table of {len(struct.names)} transcripts x {TXINDEL_BINS} INDEL structure bins x {self.n_rep} "
+                             f"replicates takes {need} bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        self.reset()
+
+    def reset(self):
+        self.host = None               # table uint32 [transcripts][10][n_rep] of the host shards
+        self.dev = {}                  # device -> dict(table, status)
+        self.counts = self.lof = self.lof_upper = None
+
+    def _part(self, name, k):
+        if not 2 <= k <= 8:
+            raise ValueError(f"SummarySink(simulate_indel_structure=True) takes INDEL rows of 2 .. 8 classes, the bound of the "
+                             f"simulation's draw (got {k})")
+        return self.struct._part(name, k)
+
+    def host_part(self, name, prob, start, end, strand, label, k):
+        part = self._part(name, k)
+        if part is None:
+            return 0
+        n_tx = len(self.struct.names)
+        if self.host is None:
+            self.host = np.zeros((n_tx, TXINDEL_BINS, self.n_rep), np.uint32)
+        return simulate_txindel_host(prob, start, strand, k, self.struct.segments.get(name), part[0], n_tx, self.struct.kind,
+                                     simulate_chrom_key(name), self.seed, self.n_rep, self.struct.offset, self.struct.class_len, part[2],
+                                     links=part[1], into=self.host)[1]
+
+    def device_part(self, name, prob, start, end, strand, label, k):
+        """Enqueue the draws of a part behind its INDEL structure reduction, into the device's one table."""
+        part = self._part(name, k)
+        if part is None or start.shape[0] == 0:
+            return None
+        dev, n_tx = prob.device, len(self.struct.names)
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = dict(table=torch.zeros(max(n_tx * TXINDEL_BINS * self.n_rep, 1), dtype=torch.int32, device=dev),
+                                       status=torch.zeros(1, dtype=torch.int32, device=dev))
+        simulate_txindel_rows_device(acc["table"], acc["status"], self.struct.dev[dev], name, n_tx, self.struct.kind, self.struct.offset,
+                                     self.struct.class_len, part[2], dev, self.n_rep, self.seed, prob=prob.data_ptr(),
+                                     prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
+                                     strand=None if strand is None else strand.data_ptr(), n=start.shape[0], n_class=k)
+        return None
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, table, n_tx = 0, self.host, len(self.struct.names)
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine = acc["table"].cpu().numpy().view(np.uint32)[:n_tx * TXINDEL_BINS * self.n_rep].reshape(n_tx, TXINDEL_BINS, self.n_rep)
+            table = mine if table is None else table + mine      # (the copy the device gave is this call's own)
+        return table, status
+
+    def merge(self, states, k):
+        table = None
+        for st in states:
+            if st is not None:
+                table = st.copy() if table is None else table + st
+        return table
+
+    def finish(self, state, k, result):
+        n_tx = len(self.struct.names)
+        self.counts = np.zeros((n_tx, TXINDEL_BINS, self.n_rep), np.uint32) if state is None else state
+        self.lof, self.lof_upper = simulate_indel_lof_counts(self.counts)
+        names, table, _ = result["indel_structure"]
+        expected, observed = indel_structure_cells_from_sums(table)
+        result[self.name] = (names, self.counts, self.lof, self.lof_upper, observed if self.struct.labels else None, expected)
+
+    def write(self, out_prefix, result, k, written):
+        written.append(indel_structure_simulation_output_name(out_prefix))
+        write_indel_structure_simulation_outputs(*result[self.name], out_prefix)
+
+
 class _CalibrationReducer:
     """The integer tables behind NLL / ECE / classwise ECE / Brier per chromosome and, with `fit_calibrator`, the retained rows and the
     calibrator fit on them at close()."""
@@ -2583,6 +2778,18 @@ class SummarySink:
     expected_lof / observed_lof = splice + start lost + frameshift and the _upper pair = that + cds_mixed; `transcript_labels=False`:
     the observed columns are NA); ``indel_structure_sums()`` has the integers.  `transcripts=` keeps refusing rows of other than 4
     classes.
+    `simulate_indel_structure=True` (opt-in; with `simulate` and `simulate_seed`, `indel_transcripts` and `indel_kind`, ValueError
+    naming what is missing otherwise; `simulate` then needs neither `annotations` nor `simulate_write`): the null distribution of the
+    INDEL structure table's observed_* columns and of observed_lof / observed_lof_upper -- per transcript, bin and replicate the rows
+    the transcript counts whose draw is a class that falls in that bin (``simulate_txindel_host`` is the rule; DESIGN.md section
+    3.26; 2 .. 8 classes), device parts through ``mural_simulate_txindel_rows`` (csrc/simulate_txindel.hip) on the item, link and
+    segment arrays the reduction before it uploaded, one uint32 table [transcripts][10][R] (checked against
+    `simulate_table_bytes_max` on its own, when the sink is built) read back once and added across ranks in the same collective.
+    The LoF counts of replicate r add the splice, start-lost and frameshift counts (and cds_mixed for the upper one) of the same
+    draw (``simulate_indel_lof_counts``).  result()["indel_structure_simulation"] = (names, counts [transcripts][10][R], lof
+    [transcripts][R], lof_upper [transcripts][R], observed [transcripts][12] or None, expected [transcripts][12]), the last two the
+    INDEL structure file's own numbers, lof and lof_upper last; close() writes ``{out_prefix}.indel_structure.sim.tsv``
+    (``tables.write_indel_structure_simulation_outputs``); ``indel_structure_simulation_counts()`` has the table.
 
     The sink checks the shard, calibrates and orders the part and hands its columns to the reducer of every summary asked for; close()
     reads the reducers back, exchanges the ranks' states in ONE collective and lets each reducer merge, finish and write its own."""
@@ -2594,7 +2801,8 @@ class SummarySink:
                  calibration_bins=50, fit_calibrator=None, fit_rows_max=1 << 27, fit_row_terms=None, annotations=None, simulate=None,
                  simulate_seed=None, simulate_write=(), simulate_table_bytes_max=1 << 30, simulate_labels=True, transcripts=None,
                  codon_table=None, alt_order=None, transcript_labels=True, simulate_transcripts=False, transcript_structure=False,
-                 simulate_structure=False, indel_transcripts=None, indel_kind=None, indel_lengths=None, breakpoint_offset=1):
+                 simulate_structure=False, indel_transcripts=None, indel_kind=None, indel_lengths=None, breakpoint_offset=1,
+                 simulate_indel_structure=False):
         self.out_prefix = None if out_prefix is None else os.fspath(out_prefix)
         by_window = _WindowReducer(windows, benchmark_regions, ratio_cutoff)
         self.windows = by_window.sizes
@@ -2624,10 +2832,16 @@ class SummarySink:
                                               simulate_transcripts and transcripts is not None)) if not on]
             if missing:
                 raise ValueError("simulate_structure needs " + ", ".join(missing))
+        if simulate_indel_structure:      # opt-in as well, behind the INDEL structure reducer
+            missing = [what for what, on in (("simulate=R with simulate_seed", simulate is not None and simulate_seed is not None),
+                                             ("indel_transcripts= with indel_kind= (the item arrays and the bin rule)",
+                                              indel_transcripts is not None and indel_kind is not None)) if not on]
+            if missing:
+                raise ValueError("simulate_indel_structure needs " + ", ".join(missing))
         if self.simulate:
             if simulate_seed is None:
                 raise ValueError("simulate needs simulate_seed: there is no default randomness")
-            if annotations is None and not tuple(simulate_write) and not simulate_transcripts:
+            if annotations is None and not tuple(simulate_write) and not simulate_transcripts and not simulate_indel_structure:
                 raise ValueError("simulate needs annotations= (the counts per name) or a replicate in simulate_write")
             if self.annotations or tuple(simulate_write):      # (otherwise the draws are the consequence simulation's alone)
                 active.append(_SimulationReducer(simulate, simulate_seed, simulate_write, active[-1] if self.annotations else None,
@@ -2660,6 +2874,8 @@ class SummarySink:
             raise ValueError("simulate_transcripts goes with simulate=R and simulate_seed")
         if indel_transcripts is not None:
             active.append(_IndelStructureReducer(indel_transcripts, indel_kind, indel_lengths, breakpoint_offset, genome, transcript_labels))
+            if simulate_indel_structure:      # behind it: its item, link and segment arrays and its workspace
+                active.append(_IndelStructureSimulationReducer(simulate, simulate_seed, active[-1], simulate_table_bytes_max))
         elif indel_kind is not None or indel_lengths is not None or breakpoint_offset != 1:
             raise ValueError("indel_kind, indel_lengths and breakpoint_offset go with indel_transcripts=")
         self._reducers = {r.name: r for r in active}
@@ -2845,6 +3061,12 @@ class SummarySink:
         ``tables.STRUCTURE_BINS`` and replicate (``simulate_txstruct_host``'s layout, the transcripts in file order)."""
         self.result()
         return self._reducers["structure_simulation"].counts
+
+    def indel_structure_simulation_counts(self):
+        """table uint32 [transcripts][10][simulate] after close(): the simulated count of every transcript, bin of
+        ``tables.INDEL_STRUCTURE_BINS`` and replicate (``simulate_txindel_host``'s layout, the transcripts in file order)."""
+        self.result()
+        return self._reducers["indel_structure_simulation"].counts
 
     def calibration_sums(self):
         """{"all": table, "per_chromosome": {name: table}[, "after": table]} after close(): the integer tables behind

@@ -1167,6 +1167,21 @@ def _indel_lof_cells(cells):
     return cells + [lof, [lof[w] + cells[9][w] for w in range(3)]]
 
 
+def indel_structure_cells_from_sums(table):
+    """(expected, observed) of the INDEL structure file from the integer sums [n][10][3] (an array or nested lists): per transcript
+    twelve Python floats and twelve Python integers -- the ten bins of ``INDEL_STRUCTURE_BINS``, then lof and lof_upper
+    (``_indel_lof_cells``).  The integers are added as integers; an expected value is (hi * 2^40 + lo) / 2^71, formed from Python
+    integers by true division.  The one place where ``write_indel_structure_outputs`` and
+    ``write_indel_structure_simulation_outputs`` take their numbers from."""
+    table = table.tolist() if isinstance(table, np.ndarray) else table
+    den, expected, observed = 1 << 71, [], []
+    for cells in table:
+        cells = _indel_lof_cells([[int(w) for w in cell] for cell in cells])
+        expected.append([((hi << 40) + lo) / den for _, hi, lo in cells])
+        observed.append([count for count, _, _ in cells])
+    return expected, observed
+
+
 def write_indel_structure_outputs(names, meta, table, rows, kind, out_prefix, labels=True):
     """``{out_prefix}.indel_structure.tsv`` from the integer sums of ``summary_txindel_host`` / ``mural_summary_txindel_rows`` (table
     uint64 [n][10][3], rows uint64 [n][2]) of a run of `kind` (``check_indel_kind``): a line per transcript in file order -- name, chrom,
@@ -1180,11 +1195,12 @@ def write_indel_structure_outputs(names, meta, table, rows, kind, out_prefix, la
     header = ["name", "chrom", "strand", "kind", "n_rows", "n_nonmut"]
     for what in INDEL_STRUCTURE_BINS + ("lof", "lof_upper"):
         header += [f"expected_{what}", f"observed_{what}"]
-    den, lines = 1 << 71, []
+    expected, observed = indel_structure_cells_from_sums(table)
+    lines = []
     for j, nm in enumerate(names):
         line = [nm, meta["chrom"][j], "-" if meta["strand"][j] else "+", kind, str(rows[j][0]), str(rows[j][1])]
-        for count, hi, lo in _indel_lof_cells(table[j]):
-            line += [_float_text(((hi << 40) + lo) / den), str(count) if labels else "NA"]
+        for value, count in zip(expected[j], observed[j]):
+            line += [_float_text(value), str(count) if labels else "NA"]
         lines.append(line)
     path = indel_structure_output_name(out_prefix)
     with open(path, "w") as fh:
@@ -1594,6 +1610,102 @@ def run_simulate_structure_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
     result = simulate_structure_table(os.fspath(args.pred_file), args.transcripts, os.fspath(args.ref_genome), args.simulate, args.seed,
                                       getattr(args, "codon_table", None), getattr(args, "alt_order", None), True, chunk_bytes)
     return write_structure_simulation_outputs(*result, args.out_prefix)
+
+
+def indel_structure_simulation_output_name(out_prefix):
+    return f"{out_prefix}.indel_structure.sim.tsv"
+
+
+def write_indel_structure_simulation_outputs(names, counts, lof, lof_upper, observed, expected, out_prefix):
+    """``{out_prefix}.indel_structure.sim.tsv``: one line per transcript and row of ``INDEL_STRUCTURE_BINS`` + ("lof", "lof_upper") --
+    name, bin, observed, expected, sim_mean, sim_min, sim_max, n_ge, n_le, p_upper, p_lower (``summaries.simulate_pvalues``) -- from
+    counts [transcripts][10][R], lof and lof_upper [transcripts][R] (``summaries.simulate_indel_lof_counts``), observed
+    [transcripts][12] (None: no labels, 'NA' in the observed column and the last four) and expected [transcripts][12]: the numbers
+    ``write_indel_structure_outputs`` writes (``indel_structure_cells_from_sums``), lof and lof_upper last.  Returns the path."""
+    from .summaries import simulate_pvalues      # (summaries imports this module: not at the top)
+    header = ["name", "bin", "observed", "expected", "sim_mean", "sim_min", "sim_max", "n_ge", "n_le", "p_upper", "p_lower"]
+    counts = np.asarray(counts).reshape(len(names), 10, -1)
+    extra = (np.asarray(lof).reshape(len(names), -1), np.asarray(lof_upper).reshape(len(names), -1))
+    what_all = INDEL_STRUCTURE_BINS + ("lof", "lof_upper")
+    stats = [simulate_pvalues(counts[:, b] if b < 10 else extra[b - 10], None if observed is None else [row[b] for row in observed])
+             for b in range(len(what_all))]
+    rows = []
+    for j, nm in enumerate(names):
+        for b, what in enumerate(what_all):
+            mean, lo, hi, n_ge, n_le, p_up, p_lo = stats[b][j]
+            obs = "NA" if observed is None else str(int(observed[j][b]))
+            tail = ["NA"] * 4 if observed is None else [str(n_ge), str(n_le), _float_text(p_up), _float_text(p_lo)]
+            rows.append([nm, what, obs, _float_text(expected[j][b]), _float_text(mean), str(lo), str(hi)] + tail)
+    path = indel_structure_simulation_output_name(out_prefix)
+    with open(path, "w") as fh:
+        fh.write(_rates_text(header, rows))
+    return path
+
+
+def simulate_indel_structure_table(pred_file, transcripts, n_class, kind, n_rep, seed, lengths=None, breakpoint_offset=1,
+                                   chrom_lengths=None, labels=True, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """(names, counts uint32 [transcripts][10][n_rep], lof int64 [transcripts][n_rep], lof_upper the same, observed [transcripts][12]
+    or None, expected [transcripts][12]) from a written INDEL prediction table of `n_class` classes (2 .. 8): what
+    ``SummarySink(simulate=n_rep, simulate_seed=seed, indel_transcripts=..., indel_kind=kind, simulate_indel_structure=True)`` reduces
+    in flight, through the same entries (``mural_simulate_txindel_rows`` beside ``mural_summary_txindel_rows``), chromosome run by
+    chromosome run of each chunk.  The draws are made from the table's four-digit probabilities, not from the model's: as DESIGN.md
+    section 3.20 says of every table route, the counts differ from the in-flight ones of the same seed wherever the rounding moves a
+    class bound across a draw.  observed and expected are the INDEL structure file's numbers, lof and lof_upper last;
+    `labels=False`: observed is None.  `kind`, `lengths`, `breakpoint_offset`, `chrom_lengths`: ``indel_structure_table``'s."""
+    from .summaries import (_SUMMARY_STATUS, SIMULATE_MAX_REPLICATES, simulate_indel_lof_counts,      # (summaries imports this module)
+                            simulate_txindel_rows_device, txindel_rows_device)
+    n_rep, seed, k = int(n_rep), int(seed), int(n_class)
+    if not 1 <= n_rep <= SIMULATE_MAX_REPLICATES or not 0 <= seed < 1 << 64:
+        raise ValueError("simulate_indel_structure_table: 1 .. 2^20 replicates and an unsigned 64-bit seed")
+    if not 2 <= k <= 8:
+        raise ValueError(f"simulate_indel_structure_table: 2 .. 8 classes, the bound of the simulation's draw (got {k})")
+    names, meta, segments, features = read_transcript_structure(transcripts)
+    kind, off = check_indel_kind(kind), check_breakpoint_offset(breakpoint_offset)
+    class_len = check_indel_lengths(lengths, k)
+    n_tx = len(names)
+    links = {}
+    with TableReader(pred_file, k, chunk_bytes) as rd:
+        dev = rd.device
+        acc = _indel_structure_acc(n_tx, dev)
+        sim = torch.zeros(max(n_tx * 10 * n_rep, 1), dtype=torch.int32, device=dev)
+        for c in rd:
+            rows = list(c.run_row[:c.n_runs]) + [int(c.n_rows)]
+            for r in range(c.n_runs):
+                name = rd.chrom_name(c.run_chrom[r])
+                a, b = rows[r], rows[r + 1]
+                if name not in features or b == a:
+                    continue
+                if name not in links:
+                    links[name] = structure_links(features[name])
+                length = None if chrom_lengths is None else chrom_lengths.get(name)
+                part = dict(prob=c.prob + 8 * k * a, prob_f64=1, prob_stride=k, start=c.start + 8 * a, n=b - a, n_class=k)
+                txindel_rows_device(acc, name, segments.get(name), features[name], links[name], n_tx, kind, off, class_len, length, dev,
+                                    label=c.mut_type + 4 * a, label_kind=1, **part)
+                simulate_txindel_rows_device(sim, acc["status"], acc, name, n_tx, kind, off, class_len, length, dev, n_rep, seed,
+                                             strand=c.strand + a, **part)
+        bits = int(acc["status"].item())
+        for bit, what in _SUMMARY_STATUS:
+            if bits & bit:
+                raise ValueError(f"{pred_file}: {what}")
+        table = acc["table"].cpu().numpy().view(np.uint64)[:n_tx * 30].reshape(n_tx, 10, 3)
+        sim = sim.cpu().numpy().view(np.uint32)[:n_tx * 10 * n_rep].reshape(n_tx, 10, n_rep)
+    expected, observed = indel_structure_cells_from_sums(table)
+    lof, lof_upper = simulate_indel_lof_counts(sim)
+    return names, sim, lof, lof_upper, (observed if labels else None), expected
+
+
+def run_simulate_indel_structure_calc(args, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """For an `evaluate`-style caller (args.pred_file, args.indel_transcripts, args.n_class, args.indel_kind, args.simulate, args.seed,
+    args.out_prefix; optional args.indel_lengths, args.breakpoint_offset, args.chrom_lengths): the simulated counts per transcript,
+    INDEL structure bin, lof and lof_upper from the table's rows; writes {out_prefix}.indel_structure.sim.tsv."""
+    assert getattr(args, "indel_transcripts", None) is not None, "--indel_transcripts is required for the INDEL structure simulation"
+    assert getattr(args, "indel_kind", None) is not None, "--indel_kind is required for the INDEL structure simulation"
+    assert getattr(args, "seed", None) is not None, "--seed is required with --simulate: there is no default randomness"
+    lengths = getattr(args, "chrom_lengths", None)
+    result = simulate_indel_structure_table(os.fspath(args.pred_file), args.indel_transcripts, args.n_class, args.indel_kind, args.simulate,
+                                            args.seed, getattr(args, "indel_lengths", None), getattr(args, "breakpoint_offset", 1),
+                                            None if lengths is None else read_chrom_lengths(lengths), True, chunk_bytes)
+    return write_indel_structure_simulation_outputs(*result, args.out_prefix)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
   python tools/bench_summary.py [--bases N] [--indel_bases N] [--repeats K] [--legs a,b,..]
 
 One synthetic chromosome (i.i.d. uniform ACGT, 50 Mbp by default), the shipped Homo_sapiens/SNV/AT weights, focal A, sites enumerated on
-the device (predict_regions_sharded), files in /dev/shm.  Twenty-three legs (--legs picks some by name; the agreement checks need their legs),
+the device (predict_regions_sharded), files in /dev/shm.  Twenty-five legs (--legs picks some by name; the agreement checks need their legs),
 alternating, --repeats timed runs each after one warm-up run each:
   a  table     TsvSink alone: the '%.4g' table, nothing else
   b  summary   SummarySink alone, 100 kb + 1 kb windows and the scaling totals: no text
@@ -44,6 +44,9 @@ alternating, --repeats timed runs each after one warm-up run each:
                   of the medians beside leg v's own repeat spread.  With leg w the entry alone, mural_summary_txindel_rows over the
                   whole chromosome's rows in one call, is timed under HIP events for each of the three kinds (the rows' probabilities
                   uniform random: the entry's work does not depend on them)
+  x  indel_struct_sim100   leg w with simulate=100, simulate_seed=, simulate_indel_structure=True
+  y  indel_struct_sim1000  the same at 1000 replicates; with leg w, mural_simulate_txindel_rows alone on leg w's part under HIP events,
+                  each of the three kinds at 100 and 1000 replicates; close() alone is timed in every INDEL leg
 Prints one JSON line; the summary of leg b must agree with leg d's, leg e's k-mer tables with leg f's, leg g's motif tables with leg
 h's, leg k's annotation table with leg l's and leg o's consequence table with leg p's, within the table's four digits (names, order and
 counts exactly)."""
@@ -69,8 +72,10 @@ WINDOWS = (100_000, 1000)
 KMERS = (3, 5, 7)
 MOTIFS = (3, 5, 7)
 LEGS = ("table", "summary", "tee", "tools", "kmers", "kmer_tools", "motifs", "motif_tools", "calib", "calib_fit", "annot", "annot_tools", "sim100", "sim1000",
-        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct", "struct_sim100", "struct_sim1000", "indel", "indel_struct")
-INDEL_LEGS = ("indel", "indel_struct")
+        "conseq", "conseq_tools", "conseq_sim100", "conseq_sim1000", "conseq_struct", "struct_sim100", "struct_sim1000", "indel", "indel_struct",
+        "indel_struct_sim100", "indel_struct_sim1000")
+INDEL_LEGS = ("indel", "indel_struct", "indel_struct_sim100", "indel_struct_sim1000")
+INDEL_SIM_REPLICATES = {"indel_struct_sim100": 100, "indel_struct_sim1000": 1000}      # leg w's run with simulate_indel_structure=True
 INDEL_TX_SPAN = 2500
 SIM_REPLICATES = {"sim100": 100, "sim1000": 1000}
 CONSEQ_SIM_REPLICATES = {"conseq_sim100": 100, "conseq_sim1000": 1000}
@@ -123,20 +128,31 @@ def shipped_indel_model(device, name="indel_pretrained_human_deletion_start.npz"
 def indel_legs(legs, device, bases, repeats, shm):
     """Legs v and w, alternating, and the entry alone under HIP events: the "indel_structure" block of the result."""
     import numpy as np
-    from mural_amd.summaries import txindel_rows_device
+    from mural_amd.summaries import simulate_txindel_rows_device, txindel_rows_device
     model, R, n_class = shipped_indel_model(device)
     with tempfile.TemporaryDirectory(prefix="mural_summary_indel_", dir=shm) as work:
         fa = write_inputs(work, device, bases)[0]
         torch.cuda.empty_cache()
         tx = synthetic_transcripts(bases, structure=True, names=max(bases // INDEL_TX_SPAN, 1))
-        seconds, kept, rows = {leg: [] for leg in legs}, {}, None
+        seconds, kept, rows, close_seconds = {leg: [] for leg in legs}, {}, None, {}
 
         def run(leg):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fwd = HipShardForward(model, fa, 5, 3, distal_radius=R, model_type="indel", device=device, poisson=False)
-            extra = dict(indel_transcripts=tx, indel_kind="deletion_start", genome=fwd.genome, transcript_labels=False) if leg == "indel_struct" else {}
+            extra = dict(indel_transcripts=tx, indel_kind="deletion_start", genome=fwd.genome, transcript_labels=False) if leg != "indel" else {}
+            if leg in INDEL_SIM_REPLICATES:
+                extra.update(simulate=INDEL_SIM_REPLICATES[leg], simulate_seed=7, simulate_indel_structure=True)
             summary = SummarySink(windows=WINDOWS, **extra)
+            plain_close = summary.close
+
+            def close_timed():      # close() alone, of every run: the read-back and the host's share
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                plain_close()
+                torch.cuda.synchronize()
+                close_seconds.setdefault(leg, []).append(time.perf_counter() - t1)
+            summary.close = close_timed
             n = predict_regions_sharded(fwd, "chr1", "ANY", model_type="indel", sink=summary, collect=False)
             torch.cuda.synchronize()
             kept[leg] = summary.result()
@@ -148,8 +164,9 @@ def indel_legs(legs, device, bases, repeats, shm):
                 if i:
                     seconds[leg].append(dt)
     out = {"bases": bases, "rows": rows, "classes": n_class, "transcripts": len(tx[0]), "repeats": repeats, "seconds": seconds,
-           "rows_per_s": {leg: spread([rows / v for v in seconds[leg]]) for leg in legs}}
-    if set(INDEL_LEGS) <= set(legs):
+           "rows_per_s": {leg: spread([rows / v for v in seconds[leg]]) for leg in legs},
+           "close_seconds": {leg: spread(v[1:]) for leg, v in close_seconds.items() if len(v) > 1}}
+    if {"indel", "indel_struct"} <= set(legs):
         plain, with_it = seconds["indel"], seconds["indel_struct"]
         out["indel_struct_minus_indel_seconds"] = statistics.median(with_it) - statistics.median(plain)
         out["indel_repeat_spread_seconds"] = max(plain) - min(plain)
@@ -178,6 +195,24 @@ def indel_legs(legs, device, bases, repeats, shm):
             assert int(acc["status"].item()) == 0
             out["entry_ms"][what] = spread(ms)
         out["entry_rows"] = bases
+        # the simulation's entry alone on the same part, each kind at 100 and 1000 replicates
+        out["simulate_entry_ms"] = {}
+        strand, status = torch.zeros(bases, dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+        for n_rep in sorted(set(INDEL_SIM_REPLICATES.values())):
+            sim = torch.zeros(n_tx * 10 * n_rep, dtype=torch.int32, device=device)
+            for kind, what in enumerate(tables.INDEL_KINDS):
+                ms = []
+                for i in range(repeats + 1):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    simulate_txindel_rows_device(sim, status, acc, "chr1", n_tx, kind, 1, class_len, bases, device, n_rep, 7, prob=prob.data_ptr(),
+                                                 prob_f64=0, prob_stride=k, start=start.data_ptr(), strand=strand.data_ptr(), n=bases, n_class=k)
+                    b.record()
+                    b.synchronize()
+                    if i:
+                        ms.append(a.elapsed_time(b))
+                out["simulate_entry_ms"][f"{what}_R{n_rep}"] = spread(ms)
+        assert int(status.item()) == 0
     return out
 
 

@@ -91,6 +91,14 @@ read back from the table, taken from the probabilities before they are rounded):
                                                              lengths of mut_type 1, 2, .. (default 1,2,3,4,5,6,7-20 for 8 classes); the
                                                              event's boundary is start + offset (default 1); alone or with the
                                                              options above
+  --indel --summary PREFIX  --indel_transcripts BED12 --indel_kind K --simulate R --seed S --simulate_indel_structure
+                                                             PREFIX.indel_structure.sim.tsv as well: per transcript, INDEL structure
+                                                             bin, lof and lof_upper the observed and expected counts of the INDEL
+                                                             structure file beside the mean, minimum and maximum of the R simulated
+                                                             counts, n_ge / n_le and the empirical p-values (n + 1) / (R + 1); the lof
+                                                             counts of a replicate add the splice, start-lost and frameshift events (and
+                                                             cds_mixed for lof_upper) of the same draw; --simulate then needs neither
+                                                             --annotations nor --write_simulated; 2 .. 8 classes
   --strand pos|neg|both                                      with --indel and --kmer_length: the strand(s) the k-mers are counted on
   --benchmark_regions BED                                    count a site once per overlapping region in the scaling totals
   --genomewide_mu X --m_proportion M [--g_proportion G]     print the scaling factor
@@ -198,7 +206,8 @@ def _summary_options(flags, values, model_type="snv"):
             "write_simulated": tuple(int(r) for r in values.get("--write_simulated", [])), "transcripts": one("--transcripts", str),
             "codon_table": one("--codon_table", str), "alt_order": one("--alt_order", str),
             "simulate_consequences": "--simulate_consequences" in flags, "transcript_structure": "--transcript_structure" in flags,
-            "simulate_structure": "--simulate_structure" in flags, "indel_transcripts": one("--indel_transcripts", str),
+            "simulate_structure": "--simulate_structure" in flags, "simulate_indel_structure": "--simulate_indel_structure" in flags,
+            "indel_transcripts": one("--indel_transcripts", str),
             "indel_kind": one("--indel_kind", str), "indel_lengths": one("--indel_lengths", str),
             "breakpoint_offset": one("--breakpoint_offset", str)}
     if opts["indel_transcripts"] is not None and model_type != "indel":
@@ -210,6 +219,12 @@ def _summary_options(flags, values, model_type="snv"):
         raise SystemExit("--indel_kind / --indel_lengths / --breakpoint_offset go with --indel_transcripts BED12")
     if opts["indel_transcripts"] is not None and opts["summary"] is None:
         raise SystemExit("--indel_transcripts needs --summary PREFIX: the prefix of the file it writes")
+    if opts["simulate_indel_structure"] and model_type != "indel":
+        raise SystemExit("--simulate_indel_structure takes INDEL rows: it goes with --indel")
+    if opts["simulate_indel_structure"] and opts["indel_transcripts"] is None:
+        raise SystemExit("--simulate_indel_structure needs --indel_transcripts BED12 --indel_kind K: the transcripts whose INDEL structure counts it simulates")
+    if opts["simulate_indel_structure"] and (opts["simulate"] is None or opts["seed"] is None):
+        raise SystemExit("--simulate_indel_structure needs --simulate R --seed S: the replicates it counts")
     if opts["simulate_structure"] and model_type == "indel":
         raise SystemExit("--simulate_structure takes SNV rows: it does not go with --indel")
     if opts["simulate_structure"] and opts["transcripts"] is None:
@@ -235,7 +250,7 @@ def _summary_options(flags, values, model_type="snv"):
     if opts["simulate"] is not None:
         if opts["summary"] is None:
             raise SystemExit("--simulate needs --summary PREFIX: the prefix of the files it writes")
-        if opts["annotations"] is None and not opts["write_simulated"] and not opts["simulate_consequences"]:
+        if opts["annotations"] is None and not opts["write_simulated"] and not opts["simulate_consequences"] and not opts["simulate_indel_structure"]:
             raise SystemExit("--simulate needs --annotations BED (the counts per name) or --write_simulated r")
         if not 1 <= opts["simulate"] <= 1 << 20 or not 0 <= opts["seed"] < 1 << 64:
             raise SystemExit("--simulate takes 1 .. 2^20 replicates and an unsigned 64-bit --seed")
@@ -358,7 +373,8 @@ def _forward_and_sink(model_path, fasta, out, flags, model_type, poisson, opts):
                               transcript_labels=opts.get("labelled", True), simulate_transcripts=opts["simulate_consequences"],
                               transcript_structure=opts["transcript_structure"], simulate_structure=opts["simulate_structure"],
                               **(dict(indel_transcripts=opts["indel_transcripts"], indel_kind=opts["indel_kind"],
-                                      indel_lengths=opts["indel_lengths"], breakpoint_offset=opts["breakpoint_offset"])
+                                      indel_lengths=opts["indel_lengths"], breakpoint_offset=opts["breakpoint_offset"],
+                                      simulate_indel_structure=opts["simulate_indel_structure"])
                                  if opts["indel_transcripts"] is not None else {}), **sink_chain)
         sinks.append(summary)
     return forward, cfg, sinks[0] if len(sinks) == 1 else TeeSink(*sinks), summary
