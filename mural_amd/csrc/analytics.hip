@@ -143,32 +143,33 @@ __global__ __launch_bounds__(AN_THREADS) void calib_metrics_kernel(const P* __re
       atomicOr(status, 2);
       continue;
     }
-    // the reference's pseudo-logits are log(prob) and its scores softmax(log(prob)), evaluated in prob's own precision
-    P q[16];
-    P m = (P)-INFINITY;
+    // the reference's pseudo-logits are log(prob) and its scores softmax(log(prob)): evaluated in double and rounded once to prob's own
+    // precision (the precision the scores are binned in); float logs would carry up to |log p| ulp into every score of the row
+    double q[16];
+    double m = -INFINITY;
     for (int c = 0; c < nc; ++c) {
-      q[c] = (P)log((P)prob[i * nc + c]);
+      q[c] = log((double)prob[i * nc + c]);
       m = q[c] > m ? q[c] : m;
     }
-    P s = (P)0;
+    double s = 0.0;
     for (int c = 0; c < nc; ++c) {
-      q[c] = (P)exp(q[c] - m);
+      q[c] = exp(q[c] - m);
       s += q[c];
     }
     P conf = (P)-1;
     int arg = 0;
     for (int c = 0; c < nc; ++c) {
       q[c] = q[c] / s;
-      if (q[c] > conf) {
-        conf = q[c];
+      if ((P)q[c] > conf) {
+        conf = (P)q[c];
         arg = c;
       }
-      const P dlt = (c == lab ? (P)1 : (P)0) - q[c];
-      brier += (double)(dlt * dlt);
+      const double dlt = (c == lab ? 1.0 : 0.0) - q[c];
+      brier += dlt * dlt;
     }
-    nll -= (double)log(q[lab]);
+    nll -= log(q[lab]);
     for (int c = -1; c < nc; ++c) {
-      const P v = c < 0 ? conf : q[c];
+      const P v = c < 0 ? conf : (P)q[c];
       int b = -1;
       for (int t = 0; t < nb; ++t)
         if ((double)v > (double)bounds[t] && (double)v <= (double)bounds[t + 1]) b = t;
@@ -202,6 +203,7 @@ __global__ __launch_bounds__(AN_THREADS) void dirichlet_fit_kernel(const P* __re
   __shared__ double sx[FIT_ROWS][FIT_MAX_M];
   __shared__ double ss[FIT_ROWS][FIT_MAX_K];      // softmax outputs; zeroed for rows without a gradient
   __shared__ double sr[FIT_ROWS][FIT_MAX_K];      // s - onehot(y)
+  __shared__ double so[FIT_ROWS][FIT_MAX_K];      // 1 - s_j as the sum of the other classes: no cancellation where s_j rounds to 1
   __shared__ double sloss[AN_THREADS / 64];
   const int m = k + 1, km = k * m;
   for (int t = threadIdx.x; t < km; t += AN_THREADS) sW[t] = W[t];
@@ -255,13 +257,18 @@ __global__ __launch_bounds__(AN_THREADS) void dirichlet_fit_kernel(const P* __re
         lacc -= log(clipped ? (sy < eps ? eps : 1.0 - eps) : sy);
         // d(-log s_y)/dz_j = s_j - [j == y];  d2/dz_j dz_j' = s_j [j == j'] - s_j s_j'   (both vanish where the clip is active)
         for (int j = 0; j < k; ++j) {
+          double others = 0.0;
+          for (int j2 = 0; j2 < k; ++j2)
+            if (j2 != j) others += z[j2];
           const double s = clipped ? 0.0 : z[j] / tot;
+          const double om = clipped ? 0.0 : others / tot;
           ss[r][j] = s;
-          sr[r][j] = clipped ? 0.0 : s - (j == lab ? 1.0 : 0.0);
+          so[r][j] = om;
+          sr[r][j] = j == lab ? -om : s;
         }
       } else {
         for (int c = 0; c < m; ++c) sx[r][c] = 0.0;
-        for (int j = 0; j < k; ++j) ss[r][j] = sr[r][j] = 0.0;
+        for (int j = 0; j < k; ++j) ss[r][j] = sr[r][j] = so[r][j] = 0.0;
       }
     }
     __syncthreads();
@@ -280,7 +287,7 @@ __global__ __launch_bounds__(AN_THREADS) void dirichlet_fit_kernel(const P* __re
         double a = 0.0;
         for (int r = 0; r < FIT_ROWS; ++r) {
           const double sj = ss[r][j];
-          a += (j == j2 ? sj : 0.0) * sx[r][c] * sx[r][c2] - sj * ss[r][j2] * sx[r][c] * sx[r][c2];
+          a += (j == j2 ? sj * so[r][j] : -sj * ss[r][j2]) * sx[r][c] * sx[r][c2];
         }
         acc[e] += a;
       }

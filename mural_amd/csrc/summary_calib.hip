@@ -2,7 +2,8 @@
 // the sums behind the NLL / ECE / classwise ECE / Brier block of the reference's validation report (MuRaL/evaluation/evaluation.py:
 // 207-295, 339-358), reduced in one pass over the rows of a part from the probabilities and the labels the table would hold.
 //
-// The per-row arithmetic is that of calib_metrics_kernel (analytics.hip), in the probabilities' own precision P: q = softmax(log(prob)),
+// The per-row definitions are those of calib_metrics_kernel (analytics.hip); this kernel evaluates them in the probabilities' own
+// precision P, that one in float64 whatever P is (it rounds each score once to P before binning): q = softmax(log(prob)),
 // confidence = max q (the first maximum is the prediction), Brier term = sum_c ([c == label] - q_c)^2, NLL term = -log q_label, bins
 // (lower, upper] on the caller's float32 bounds.  What differs is how the rows are ADDED: every cell is an unsigned 64-bit integer and
 // every addition an integer one, so the table is a function of the SET of valid rows, bit for bit, whatever the parts, the launch
