@@ -76,6 +76,49 @@ int mural_encode_onehot(const MuralGenome* g, const int64_t* pos, const uint8_t*
 int mural_encode_symbols(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n, int32_t radius,
                          int32_t indel, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * In-silico saturation mutagenesis around the SNV forward (csrc/mutagenesis.hip).  The reference has no such
+ * tool; the windows are its encoders' (seq_digit_encoder, MuRaL/data/preprocessing.py:636-723; seq_ohe_encoder, :756-816) on a
+ * genome with ONE base replaced, and the forward in between is mural_snv_forward_symbols.
+ *
+ * mural_encode_subst_windows: one row per (site, substitution), SNV windows (indel = 0).
+ *   pos / strand         : dev int64 / uint8 [n], the row's site (strand 1 = '-')
+ *   sub_pos / sub_base   : dev int64 / uint8 [n], a '+'-strand genomic position and a '+'-strand base 0..3 (A C G T); a sub_base above 3
+ *                          (255 by convention) means "no substitution"
+ *   symbols              : dev uint8 [n][2*radius+1], 4-byte aligned, or NULL
+ *   cat_x                : dev int64 [n][2*local_radius+1-(local_order-1)], or NULL
+ * Row i is, bit for bit, mural_encode_symbols(.., radius, indel=0) / mural_encode_kmer(.., local_radius, local_order, indel=0) of
+ * (pos[i], strand[i]) on a genome that is g with the base at sub_pos[i] replaced by sub_base[i]: an N or IUPAC position becomes a plain
+ * base (nmask and the amb_pos side table are overridden for that row only).  A sub_pos outside [0, g->length), one outside the row's
+ * windows, or "no substitution" gives the unchanged encodings.  The genome buffers are only read.  One launch; n == 0 launches nothing.
+ *
+ * mural_mutagenesis_rows: the enumerator.  With W = 2*radius+1, variant id v = (site*W + j)*3 + a for site < n_sites, window column j
+ * (strand-oriented, as the symbols are) and a in {0,1,2}; the call writes ids [first, first+count) to index v - first of
+ *   row_pos / row_strand : dev int64 / uint8 [count], the site's pos / strand
+ *   sub_pos              : dev int64 [count], the genomic position of column j: pos + (j - radius) on '+', pos - (j - radius) on '-'
+ *   sub_base             : dev uint8 [count]: in WINDOW orientation the alternative is the a-th of {A,C,G,T} without the column's
+ *                          reference symbol, ascending; sub_base is that alternative on the '+' strand (complemented for '-' rows).  A
+ *                          column whose reference symbol is not A/C/G/T (N, IUPAC, outside the record) has none: its ids get 255.
+ *
+ * mural_mutagenesis_reduce: ids [first, first+count) scattered into the map.
+ *   ref_logp             : dev float [n_sites][n_class], the forward of the unchanged windows
+ *   var_logp             : dev float [count][n_class], the forward of the ids' rows
+ *   ref_symbols          : dev uint8 [n_sites][W], mural_encode_symbols of the sites
+ *   delta                : dev float [n_sites][W][4][n_class], indexed by the alternative base in window orientation:
+ *                          var_logp - ref_logp (one float32 subtraction); +0.0 at the reference base; NaN (0x7fc00000) in all four
+ *                          entries of a column whose reference symbol is not A/C/G/T
+ *   logp_map             : the same shape or NULL: var_logp itself, ref_logp at the reference base, NaN where delta is
+ * Every element has one writer among the ids of a run and nothing is accumulated: the maps do not depend on how the ids are chunked.
+ * ---------------------------------------------------------------------------------------------- */
+int mural_encode_subst_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                               const uint8_t* sub_base, int64_t n, int32_t radius, int32_t local_radius, int32_t local_order,
+                               uint8_t* symbols, int64_t* cat_x, void* stream);
+int mural_mutagenesis_rows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n_sites, int32_t radius,
+                           int64_t first, int64_t count, int64_t* row_pos, uint8_t* row_strand, int64_t* sub_pos, uint8_t* sub_base,
+                           void* stream);
+int mural_mutagenesis_reduce(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites, int32_t radius,
+                             int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map, void* stream);
+
 /* One training batch gathered and encoded from ROW INDICES in one launch (csrc/train_batch.hip): the rows of a batch may lie on several
  * chromosomes, which the three encoders above cannot take in one call.
  *   genomes    : dev MuralGenome[n_genomes] (the structs themselves live on the device)

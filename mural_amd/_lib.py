@@ -378,6 +378,9 @@ PROTOTYPES = {
     "mural_simulate_txstruct_rows": (C.c_int, [C.POINTER(MuralSimulateTxstructRows), VP, C.c_size_t, VP]),
     "mural_simulate_txindel_workspace_bytes": (C.c_size_t, [I64]),
     "mural_simulate_txindel_rows": (C.c_int, [C.POINTER(MuralSimulateTxindelRows), VP, C.c_size_t, VP]),
+    "mural_encode_subst_windows": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, VP, I64, I32, I32, I32, VP, VP, VP]),
+    "mural_mutagenesis_rows": (C.c_int, [C.POINTER(MuralGenome), VP, VP, I64, I32, I64, I64, VP, VP, VP, VP, VP]),
+    "mural_mutagenesis_reduce": (C.c_int, [VP, VP, VP, I64, I32, I32, I64, I64, VP, VP, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

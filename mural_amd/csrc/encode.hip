@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "dense_symbol.h"
+#include "encode_window.h"
 
 namespace mural {
 
@@ -103,19 +104,7 @@ __global__ void encode_kmer_kernel(MuralGenome g, const int64_t* __restrict__ po
     const int col = (int)(i - row * ncol);
     const int64_t ws = pos[row] + off;
     const bool neg = strand[row] != 0;
-    int64_t val = 0;
-    bool bad = false;
-    for (int d = 0; d < order; ++d) {
-      const int j = col + d;  // index in the strand-oriented window
-      uint32_t s = neg ? genome_sym(g.packed2, g.nmask, g.length, ws + (width - 1 - j))
-                       : genome_sym(g.packed2, g.nmask, g.length, ws + j);
-      if (s > 3u) bad = true;
-      if (neg) s = 3u - (s & 3u);
-      val = val * 4 + (int64_t)(s & 3u);
-    }
-    int64_t sentinel = 1;
-    for (int d = 0; d < order; ++d) sentinel *= 4;
-    out[i] = bad ? sentinel : val;
+    out[i] = window_kmer_id(g, ws, width, neg, col, order, NoSubst{});
   }
 }
 
@@ -128,8 +117,7 @@ __global__ void encode_onehot_kernel(MuralGenome g, const int64_t* __restrict__ 
     const int j = (int)(i - row * width);
     const int64_t ws = pos[row] + off;
     const bool neg = strand[row] != 0;
-    uint32_t s = genome_sym_iupac(g, neg ? ws + (width - 1 - j) : ws + j);
-    if (neg) s = sym_complement(s);
+    const uint32_t s = window_symbol(g, ws, width, neg, j, NoSubst{});
     symbol_to_dense(s, out + row * 4 * (int64_t)width + j, width);
   }
 }
@@ -152,9 +140,7 @@ __global__ __launch_bounds__(256) void encode_symbols_kernel(MuralGenome g, cons
       uint32_t packed = 0;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        uint32_t s = genome_sym_iupac(g, neg ? ws + (width - 1 - (j + e)) : ws + (j + e));
-        if (neg) s = sym_complement(s);
-        packed |= s << (8 * e);
+        packed |= window_symbol(g, ws, width, neg, j + e, NoSubst{}) << (8 * e);
       }
       *reinterpret_cast<uint32_t*>(out + i0) = packed;
     } else {
@@ -164,9 +150,7 @@ __global__ __launch_bounds__(256) void encode_symbols_kernel(MuralGenome g, cons
         const int jj = (int)(i - r * width);
         const int64_t ws = pos[r] + off;
         const bool neg = strand[r] != 0;
-        uint32_t s = genome_sym_iupac(g, neg ? ws + (width - 1 - jj) : ws + jj);
-        if (neg) s = sym_complement(s);
-        out[i] = (uint8_t)s;
+        out[i] = (uint8_t)window_symbol(g, ws, width, neg, jj, NoSubst{});
       }
     }
   }

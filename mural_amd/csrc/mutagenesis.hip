@@ -1,0 +1,191 @@
+// In-silico saturation mutagenesis around the SNV forward: the window "as if one base were different" (one row per (site, substitution)),
+// the enumerator of a window's 3 * W substitutions, and the scatter of the re-predicted log-probabilities into the map.
+// Window, strand and k-mer-id rules are encode.hip's, through the same column helpers (encode_window.h; reference:
+// MuRaL/data/preprocessing.py:636-723, 756-816).  The forward in between is mural_snv_forward_symbols, untouched.
+#include "common.h"
+#include "encode_window.h"
+
+namespace mural {
+
+// the row's substitution as the column helpers read it: none for sub_base > 3 (255 = "no substitution") or a position outside the record
+__device__ __forceinline__ OneSubst row_subst(const MuralGenome& g, const int64_t* __restrict__ sub_pos, const uint8_t* __restrict__ sub_base,
+                                              int64_t row) {
+  const int64_t p = sub_pos[row];
+  const uint32_t b = sub_base[row];
+  return OneSubst{p, b & 3u, b < 4u && p >= 0 && p < g.length};
+}
+
+// One launch for both outputs.  Units [0, sym_groups): 4 consecutive bytes of the flattened (row, column) index of `symbols` (one aligned
+// 4-byte store where the group lies in one row, as encode_symbols_kernel does); units [sym_groups, sym_groups + n * ncol): one k-mer id.
+__global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
+                                                            const int64_t* __restrict__ sub_pos, const uint8_t* __restrict__ sub_base, int64_t n,
+                                                            int W, int radius, int lwidth, int lradius, int order, int ncol,
+                                                            int64_t sym_groups, uint8_t* __restrict__ symbols, int64_t* __restrict__ cat_x) {
+  const int64_t total_sym = symbols ? n * W : 0;
+  const int64_t units = sym_groups + (cat_x ? n * ncol : 0);
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    if (u < sym_groups) {
+      const int64_t i0 = u << 2;
+      const int64_t row = i0 / W;
+      const int j = (int)(i0 - row * W);
+      if (j + 3 < W) {
+        const int64_t ws = pos[row] - radius;
+        const bool neg = strand[row] != 0;
+        const OneSubst sub = row_subst(g, sub_pos, sub_base, row);
+        uint32_t packed = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) packed |= window_symbol(g, ws, W, neg, j + e, sub) << (8 * e);
+        *reinterpret_cast<uint32_t*>(symbols + i0) = packed;
+      } else {
+        for (int e = 0; e < 4 && i0 + e < total_sym; ++e) {
+          const int64_t i = i0 + e;
+          const int64_t r = i / W;
+          const int jj = (int)(i - r * W);
+          symbols[i] = (uint8_t)window_symbol(g, pos[r] - radius, W, strand[r] != 0, jj, row_subst(g, sub_pos, sub_base, r));
+        }
+      }
+    } else {
+      const int64_t i = u - sym_groups;
+      const int64_t row = i / ncol;
+      const int col = (int)(i - row * ncol);
+      cat_x[i] = window_kmer_id(g, pos[row] - lradius, lwidth, strand[row] != 0, col, order, row_subst(g, sub_pos, sub_base, row));
+    }
+  }
+}
+
+// variant id v = (site * W + j) * 3 + a  ->  the row (site's pos / strand) and its '+'-strand substitution
+__global__ __launch_bounds__(256) void mutagenesis_rows_kernel(MuralGenome g, const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
+                                                               int W, int radius, int64_t first, int64_t count, int64_t* __restrict__ row_pos,
+                                                               uint8_t* __restrict__ row_strand, int64_t* __restrict__ sub_pos,
+                                                               uint8_t* __restrict__ sub_base) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t v = first + k;
+    const int64_t cell = v / 3;                  // site * W + j
+    const uint32_t a = (uint32_t)(v - cell * 3);
+    const int64_t site = cell / W;
+    const int j = (int)(cell - site * W);
+    const int64_t p = pos[site];
+    const bool neg = strand[site] != 0;
+    const uint32_t ref = window_symbol(g, p - radius, W, neg, j, NoSubst{});      // window orientation
+    uint32_t b = 255u;
+    if (ref < 4u) {
+      const uint32_t alt = a + (a >= ref ? 1u : 0u);                               // a-th of {A, C, G, T} \ {ref}, ascending
+      b = neg ? 3u - alt : alt;                                                    // back on the '+' strand
+    }
+    row_pos[k] = p;
+    row_strand[k] = neg ? 1 : 0;
+    sub_pos[k] = window_genome_pos(p - radius, W, neg, j);
+    sub_base[k] = (uint8_t)b;
+  }
+}
+
+// Every element of the maps has ONE writer among the ids of a run, whatever the chunking: in an A/C/G/T column id a writes its
+// alternative's entry and id a = 0 the reference base's as well; in any other column id a writes entry a and id a = 2 entry 3 too.
+// The maps are written as bit patterns: the library is built with -fno-honor-nans, a NaN must not pass through float code.
+__global__ __launch_bounds__(256) void mutagenesis_reduce_kernel(const float* __restrict__ ref_logp, const float* __restrict__ var_logp,
+                                                                 const uint8_t* __restrict__ ref_sym, int W, int C, int64_t first, int64_t count,
+                                                                 uint32_t* __restrict__ delta, uint32_t* __restrict__ logp_map) {
+  constexpr uint32_t NAN_BITS = 0x7fc00000u;
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t v = first + k;
+    const int64_t cell = v / 3;
+    const uint32_t a = (uint32_t)(v - cell * 3);
+    const int64_t site = cell / W;
+    const uint32_t ref = ref_sym[cell];
+    const float* __restrict__ rl = ref_logp + site * C;
+    const float* __restrict__ vl = var_logp + k * C;
+    const int64_t base = cell * 4 * C;
+    if (ref < 4u) {
+      const uint32_t alt = a + (a >= ref ? 1u : 0u);
+      for (int c = 0; c < C; ++c) {
+        const float x = vl[c];
+        delta[base + alt * C + c] = __float_as_uint(x - rl[c]);
+        if (logp_map) logp_map[base + alt * C + c] = __float_as_uint(x);
+      }
+      if (a == 0u) {
+        for (int c = 0; c < C; ++c) {
+          delta[base + ref * C + c] = 0u;                                          // +0.0
+          if (logp_map) logp_map[base + ref * C + c] = __float_as_uint(rl[c]);
+        }
+      }
+    } else {
+      for (uint32_t b = a; b < (a == 2u ? 4u : a + 1u); ++b) {
+        for (int c = 0; c < C; ++c) {
+          delta[base + b * C + c] = NAN_BITS;
+          if (logp_map) logp_map[base + b * C + c] = NAN_BITS;
+        }
+      }
+    }
+  }
+}
+
+static int grid_for(int64_t units, int block, int cap) {
+  const int64_t blocks = (units + block - 1) / block;
+  return (int)(blocks < cap ? blocks : cap);
+}
+
+}  // namespace mural
+
+using namespace mural;
+
+extern "C" int mural_encode_subst_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                                          const uint8_t* sub_base, int64_t n, int32_t radius, int32_t local_radius, int32_t local_order,
+                                          uint8_t* symbols, int64_t* cat_x, void* stream) {
+  MURAL_REQUIRE(g && g->packed2 && g->nmask, "genome pointers must not be NULL");
+  MURAL_REQUIRE(g->n_amb == 0 || (g->amb_pos && g->amb_sym), "genome: n_amb > 0 needs amb_pos and amb_sym");
+  MURAL_REQUIRE(n >= 0, "encode_subst_windows: n must be >= 0");
+  int off = 0, W = 0, loff = 0, lwidth = 0, ncol = 0;
+  if (symbols) {
+    if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
+    MURAL_REQUIRE((reinterpret_cast<uintptr_t>(symbols) & 3u) == 0, "encode_subst_windows: symbols must be 4-byte aligned");
+  }
+  if (cat_x) {
+    MURAL_REQUIRE(local_order >= 1 && local_order <= 12, "local_order must be in [1,12], got %d", local_order);
+    if (int rc = window_geometry(local_radius, 0, &loff, &lwidth)) return rc;
+    ncol = lwidth - (local_order - 1);
+    MURAL_REQUIRE(ncol >= 1, "window too short for order %d", local_order);
+  }
+  if (n == 0 || (!symbols && !cat_x)) return MURAL_OK;
+  MURAL_REQUIRE(pos && strand && sub_pos && sub_base, "pos/strand/sub_pos/sub_base must not be NULL");
+  const int64_t sym_groups = symbols ? (n * W + 3) / 4 : 0;
+  const int64_t units = sym_groups + (cat_x ? n * ncol : 0);
+  hipLaunchKernelGGL(subst_windows_kernel, dim3(grid_for(units, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, sub_pos,
+                     sub_base, n, W, (int)radius, lwidth, (int)local_radius, (int)local_order, ncol, sym_groups, symbols, cat_x);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
+extern "C" int mural_mutagenesis_rows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n_sites, int32_t radius,
+                                      int64_t first, int64_t count, int64_t* row_pos, uint8_t* row_strand, int64_t* sub_pos,
+                                      uint8_t* sub_base, void* stream) {
+  MURAL_REQUIRE(g && g->packed2 && g->nmask, "genome pointers must not be NULL");
+  MURAL_REQUIRE(g->n_amb == 0 || (g->amb_pos && g->amb_sym), "genome: n_amb > 0 needs amb_pos and amb_sym");
+  int off, W;
+  if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
+  MURAL_REQUIRE(n_sites >= 0 && n_sites <= INT64_MAX / (3 * (int64_t)W), "mutagenesis_rows: n_sites out of range");
+  MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_sites * W * 3 - count,
+                "mutagenesis_rows: ids [first, first + count) must lie in [0, n_sites * W * 3)");
+  if (count == 0) return MURAL_OK;
+  MURAL_REQUIRE(pos && strand && row_pos && row_strand && sub_pos && sub_base, "mutagenesis_rows: pointers must not be NULL");
+  hipLaunchKernelGGL(mutagenesis_rows_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, W,
+                     (int)radius, first, count, row_pos, row_strand, sub_pos, sub_base);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
+extern "C" int mural_mutagenesis_reduce(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites,
+                                        int32_t radius, int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map,
+                                        void* stream) {
+  int off, W;
+  if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
+  MURAL_REQUIRE(n_class >= 1, "mutagenesis_reduce: n_class must be >= 1, got %d", n_class);
+  MURAL_REQUIRE(n_sites >= 0 && n_sites <= INT64_MAX / (4 * (int64_t)W * n_class), "mutagenesis_reduce: n_sites out of range");
+  MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_sites * W * 3 - count,
+                "mutagenesis_reduce: ids [first, first + count) must lie in [0, n_sites * W * 3)");
+  if (count == 0) return MURAL_OK;
+  MURAL_REQUIRE(ref_logp && var_logp && ref_symbols && delta, "mutagenesis_reduce: pointers must not be NULL");
+  hipLaunchKernelGGL(mutagenesis_reduce_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, ref_logp, var_logp,
+                     ref_symbols, W, (int)n_class, first, count, reinterpret_cast<uint32_t*>(delta), reinterpret_cast<uint32_t*>(logp_map));
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}

@@ -1,0 +1,351 @@
+"""In-silico saturation mutagenesis and variant footprints on top of the SNV forward (csrc/mutagenesis.hip).
+
+``saturation_mutagenesis`` answers "which bases of the +-distal_radius window make this site's rate what it is": every column of the
+window is replaced by each of its three alternatives, the window re-predicted, and the change in log-probability reported as a map
+``delta[site, column, alternative base, class]``.  ``variant_footprint`` is the transposed question: what one variant does to the rate of
+every site around it.  Both encode "the window as if one base were different" on the device (``mural_encode_subst_windows``) and run the
+existing ``forward_symbols``; nothing patches a FASTA and no dense one-hot tensor is assembled.
+
+The numpy twins (``encode_subst_windows_host``, ``mutagenesis_rows_host``, ``mutagenesis_reduce_host``) are the specification the CPU
+tests pin against brute force (patch the sequence string, encode with the oracle).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .data.genome import _CODE, PackedGenome, SymbolWindows  # noqa: F401
+
+NO_SUBST = 255                      # sub_base of "no substitution"
+_COMPLEMENT = np.array([3, 2, 1, 0, 4, 6, 5, 10, 8, 9, 7, 14, 13, 12, 11, 15], np.uint8)      # csrc/common.h: sym_complement
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# host twins
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _codes(genome):
+    """uint8 MURAL_SYM_* codes of a sequence (str / bytes) or of such a code array."""
+    if isinstance(genome, (str, bytes)):
+        raw = np.frombuffer(genome.encode("ascii") if isinstance(genome, str) else bytes(genome), np.uint8)
+        codes = _CODE[raw]
+        if (codes == 255).any():
+            raise KeyError(chr(int(raw[int(np.argmax(codes == 255))])))
+        return codes
+    return np.asarray(genome, np.uint8)
+
+
+def _window_symbols_host(codes, pos, strand, radius, sub_pos=None, sub_base=None):
+    """(n, 2 * radius + 1) strand-oriented symbols of the sites' windows ('-': reversed and complemented; outside the record: N), with
+    the base at sub_pos replaced by sub_base where the row has a substitution."""
+    pos, neg = np.asarray(pos, np.int64), np.asarray(strand) != 0
+    W, L = 2 * radius + 1, len(codes)
+    off = np.arange(W, dtype=np.int64) - radius
+    gp = pos[:, None] + np.where(neg[:, None], -off[None, :], off[None, :])            # genome position of column j
+    inside = (gp >= 0) & (gp < L)
+    sym = np.full(gp.shape, 4, np.uint8)
+    sym[inside] = codes[gp[inside]]
+    if sub_pos is not None:
+        sp, sb = np.asarray(sub_pos, np.int64), np.asarray(sub_base, np.uint8)
+        live = (sb < 4) & (sp >= 0) & (sp < L)
+        hit = live[:, None] & (gp == sp[:, None])
+        sym = np.where(hit, sb[:, None], sym)
+    return np.where(neg[:, None], _COMPLEMENT[sym], sym).astype(np.uint8), gp
+
+
+def encode_subst_windows_host(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order):
+    """The numpy twin of ``mural_encode_subst_windows``: (symbols uint8 (n, 2 * radius + 1), cat_x int64 (n, 2 * local_radius + 1 -
+    (local_order - 1))) of the rows' windows on the genome with the base at sub_pos replaced by sub_base ('+'-strand base 0..3; above 3:
+    no substitution; a position outside the record or the window changes nothing)."""
+    codes = _codes(genome)
+    symbols, _ = _window_symbols_host(codes, pos, strand, radius, sub_pos, sub_base)
+    local, _ = _window_symbols_host(codes, pos, strand, local_radius, sub_pos, sub_base)
+    ncol = 2 * local_radius + 1 - (local_order - 1)
+    digit = local.astype(np.int64)
+    val = np.zeros((len(digit), ncol), np.int64)
+    bad = np.zeros((len(digit), ncol), bool)
+    for d in range(local_order):
+        col = digit[:, d:d + ncol]
+        bad |= col > 3                                   # N and the IUPAC codes alike (preprocessing.py:655-666)
+        val = val * 4 + np.where(col > 3, 0, col)
+    return symbols, np.where(bad, 4 ** local_order, val)
+
+
+def mutagenesis_ids_host(first, count, radius):
+    """(site, column, a) of the variant ids [first, first + count): v = (site * W + column) * 3 + a."""
+    v = first + np.arange(count, dtype=np.int64)
+    cell, a = v // 3, v % 3
+    W = 2 * radius + 1
+    return cell // W, cell % W, a
+
+
+def mutagenesis_rows_host(genome, pos, strand, radius, first, count):
+    """The numpy twin of ``mural_mutagenesis_rows``: (row_pos int64, row_strand uint8, sub_pos int64, sub_base uint8) of the ids
+    [first, first + count).  In window orientation the alternative is the a-th of {A, C, G, T} without the column's reference symbol,
+    ascending; sub_base is that alternative on the '+' strand; a column that is not A/C/G/T gives 255."""
+    codes = _codes(genome)
+    pos, strand = np.asarray(pos, np.int64), (np.asarray(strand) != 0).astype(np.uint8)
+    W = 2 * radius + 1
+    if first < 0 or count < 0 or first + count > len(pos) * W * 3:
+        raise ValueError("mutagenesis_rows: ids [first, first + count) must lie in [0, n_sites * W * 3)")
+    site, j, a = mutagenesis_ids_host(first, count, radius)
+    sym, gp = _window_symbols_host(codes, pos, strand, radius)
+    ref = sym[site, j].astype(np.int64)
+    alt = a + (a >= ref)
+    neg = strand[site] != 0
+    sub_base = np.where(ref < 4, np.where(neg, 3 - alt, alt), NO_SUBST).astype(np.uint8)
+    return pos[site], strand[site], gp[site, j], sub_base
+
+
+def mutagenesis_reduce_host(ref_logp, var_logp, ref_symbols, first, delta, logp_map=None):
+    """The numpy twin of ``mural_mutagenesis_reduce``: scatters var_logp (count, n_class) of the ids [first, first + count) into `delta`
+    (n_sites, W, 4, n_class) float32 in place (and var_logp itself into `logp_map`).  Id a of an A/C/G/T column writes its alternative's
+    entry, id a = 0 the reference base's (+0.0; ref_logp in the second map) too; in any other column id a writes NaN to entry a, id a = 2
+    to entry 3 as well."""
+    ref_logp, var_logp = np.asarray(ref_logp, np.float32), np.asarray(var_logp, np.float32)
+    ref_symbols = np.asarray(ref_symbols, np.uint8)
+    n, W = ref_symbols.shape
+    site, j, a = mutagenesis_ids_host(first, len(var_logp), (W - 1) // 2)
+    ref = ref_symbols[site, j].astype(np.int64)
+    plain = ref < 4
+    alt = a + (a >= ref)
+    nan = np.float32(np.nan)
+    s, c, b = site[plain], j[plain], alt[plain]
+    delta[s, c, b] = var_logp[plain] - ref_logp[s]
+    if logp_map is not None:
+        logp_map[s, c, b] = var_logp[plain]
+    z = plain & (a == 0)
+    delta[site[z], j[z], ref[z]] = np.float32(0.0)
+    if logp_map is not None:
+        logp_map[site[z], j[z], ref[z]] = ref_logp[site[z]]
+    for maps in (delta, logp_map):
+        if maps is None:
+            continue
+        maps[site[~plain], j[~plain], a[~plain]] = nan
+        last = ~plain & (a == 2)
+        maps[site[last], j[last], 3] = nan
+    return delta
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# device entry points
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _encode_subst_into(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order, symbols, cat_x):
+    g = genome.as_struct()
+    with torch.cuda.device(genome.device):
+        _lib.check(_lib.lib().mural_encode_subst_windows(
+            C.byref(g), pos.data_ptr(), strand.data_ptr(), sub_pos.data_ptr(), sub_base.data_ptr(), pos.shape[0], int(radius),
+            int(local_radius), int(local_order), None if symbols is None else symbols.data_ptr(),
+            None if cat_x is None else cat_x.data_ptr(), _lib.current_stream_ptr(genome.device)))
+
+
+def encode_subst_windows(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order):
+    """``PackedGenome.encode_subst_windows``: (symbols uint8 (n, 2 * radius + 1), cat_x int64 (n, 2 * local_radius + 1 - (local_order - 1)))
+    of one row per (site, substitution), bit for bit ``encode_symbols`` / ``encode_kmer`` on the genome with that base replaced.  `sub_pos`
+    is a '+'-strand position, `sub_base` a '+'-strand base 0..3 or 255 for none."""
+    pos, strand = genome._prep(pos, strand)
+    sub_pos = torch.as_tensor(sub_pos, dtype=torch.int64, device=genome.device).contiguous()
+    sub_base = torch.as_tensor(sub_base, dtype=torch.uint8, device=genome.device).contiguous()
+    if sub_pos.shape != pos.shape or sub_base.shape != pos.shape:
+        raise ValueError("sub_pos and sub_base must be 1-D and as long as pos")
+    n = pos.shape[0]
+    symbols = torch.empty((n, 2 * radius + 1), dtype=torch.uint8, device=genome.device)
+    cat_x = torch.empty((n, 2 * local_radius + 1 - (local_order - 1)), dtype=torch.int64, device=genome.device)
+    _encode_subst_into(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order, symbols, cat_x)
+    return symbols, cat_x
+
+
+def mutagenesis_rows(genome, pos, strand, radius, first, count):
+    """``mural_mutagenesis_rows`` on the device: (row_pos, row_strand, sub_pos, sub_base) of the variant ids [first, first + count)."""
+    pos, strand = genome._prep(pos, strand)
+    dev = genome.device
+    out = (torch.empty(count, dtype=torch.int64, device=dev), torch.empty(count, dtype=torch.uint8, device=dev),
+           torch.empty(count, dtype=torch.int64, device=dev), torch.empty(count, dtype=torch.uint8, device=dev))
+    g = genome.as_struct()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mural_mutagenesis_rows(C.byref(g), pos.data_ptr(), strand.data_ptr(), pos.shape[0], int(radius), int(first),
+                                                    int(count), *[t.data_ptr() for t in out], _lib.current_stream_ptr(dev)))
+    return out
+
+
+def mutagenesis_reduce(ref_logp, var_logp, ref_symbols, first, delta, logp_map=None):
+    """``mural_mutagenesis_reduce`` on the device: var_logp (count, n_class) of the ids [first, first + count) into `delta` (n_sites, W, 4,
+    n_class) in place (and into `logp_map`).  Contiguous float32 / uint8 device tensors."""
+    n, W = ref_symbols.shape
+    n_class = ref_logp.shape[1]
+    tensors = [(ref_logp, torch.float32, (n, n_class)), (var_logp, torch.float32, (var_logp.shape[0], n_class)),
+               (ref_symbols, torch.uint8, (n, W)), (delta, torch.float32, (n, W, 4, n_class))]
+    if logp_map is not None:
+        tensors.append((logp_map, torch.float32, (n, W, 4, n_class)))
+    for t, dt, shape in tensors:
+        _lib.require_cuda(t, "mutagenesis_reduce input")
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"mutagenesis_reduce: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    if W % 2 != 1:
+        raise ValueError("mutagenesis_reduce: ref_symbols must be (n_sites, 2 * radius + 1)")
+    dev = delta.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mural_mutagenesis_reduce(ref_logp.data_ptr(), var_logp.data_ptr(), ref_symbols.data_ptr(), n, (W - 1) // 2,
+                                                      n_class, int(first), var_logp.shape[0], delta.data_ptr(),
+                                                      None if logp_map is None else logp_map.data_ptr(), _lib.current_stream_ptr(dev)))
+    return delta
+
+
+def _require_model(model, local_radius, local_order):
+    """(distal radius, local radius) of a model the symbols entry serves; RuntimeError that names the reason otherwise."""
+    model_no = getattr(model, "model_no", -1)
+    if model_no == 0:
+        raise RuntimeError("mutagenesis needs a model with a distal window: Network0 has none (it reads the local k-mers only)")
+    if model_no not in (1, 2):
+        raise RuntimeError(f"mutagenesis serves the SNV models Network1 / Network2, not {type(model).__name__}")
+    if model.training:
+        raise RuntimeError("internal: the fused inference kernels serve eval mode only")
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError("mural_amd models run on a HIP device only: call model.to('cuda') first")
+    if not model.symbols_entry_ok():
+        if model._front_ok():
+            raise RuntimeError("mutagenesis runs through forward_symbols, which this model does not have: its window is so long that only "
+                               "the front of the large tower is fused (front-only long windows)")
+        raise RuntimeError("mutagenesis runs through forward_symbols, which this model does not have: its shape evaluates through the "
+                           "per-layer path (CNN_out_channels != 32, CNN_kernel_size != 3 or a window too long for LDS)")
+    if local_radius is None:
+        local_radius = (getattr(model, "no_of_cat", 1) + local_order - 2) // 2
+    return (model.seq_len - 1) // 2, int(local_radius)
+
+
+def _sites(genome, model, pos, strand):
+    pos = _lib.require_cuda(torch.as_tensor(pos), "pos").to(torch.int64).contiguous()
+    strand = _lib.require_cuda(torch.as_tensor(strand), "strand").to(torch.uint8).contiguous()
+    if pos.dim() != 1 or pos.shape != strand.shape:
+        raise ValueError("pos and strand must be 1-D and of equal length")
+    dev = next(model.parameters()).device
+    if genome.packed2.device != dev or pos.device != dev or strand.device != dev:
+        raise RuntimeError(f"genome ({genome.packed2.device}), sites ({pos.device}) and model ({dev}) must live on one HIP device")
+    return pos, strand
+
+
+class MutagenesisMap:
+    """The result of ``saturation_mutagenesis``.  Device tensors: ``delta`` float32 (n, W, 4, n_class), indexed [site, window column,
+    alternative base in window orientation, class] -- +0.0 at the reference base, NaN in all four entries of a column whose reference
+    symbol is not A/C/G/T; ``ref_logp`` (n, n_class); ``ref_symbols`` uint8 (n, W), strand-oriented MURAL_SYM_* codes; ``var_logp`` (the
+    variants' log-probabilities in the layout of ``delta``, ref_logp at the reference base) when asked for, else None."""
+
+    __slots__ = ("delta", "ref_logp", "ref_symbols", "var_logp", "pos", "strand", "radius")
+
+    def __init__(self, delta, ref_logp, ref_symbols, var_logp, pos, strand, radius):
+        self.delta, self.ref_logp, self.ref_symbols, self.var_logp = delta, ref_logp, ref_symbols, var_logp
+        self.pos, self.strand, self.radius = pos, strand, radius
+
+    def genomic_positions(self):
+        """int64 (n, W): the '+'-strand position of every window column (pos + (j - R) on '+', pos - (j - R) on '-'; may lie outside
+        the record, where the column is N)."""
+        off = torch.arange(-self.radius, self.radius + 1, dtype=torch.int64, device=self.pos.device)
+        sign = 1 - 2 * self.strand.to(torch.int64)
+        return self.pos[:, None] + sign[:, None] * off[None, :]
+
+    def importance(self):
+        """float32 (n, W): the largest |delta| over alternatives and classes; NaN where the column has no substitutions."""
+        mag = self.delta.abs().flatten(2)
+        nan = torch.isnan(mag)
+        best = torch.where(nan, torch.full_like(mag, -1.0), mag).amax(dim=2)
+        return torch.where(nan.all(dim=2), torch.full_like(best, float("nan")), best)
+
+
+def saturation_mutagenesis(model, genome, pos, strand, local_radius=None, local_order=3, chunk_windows=1 << 17, return_logp=False,
+                           timings=None):
+    """The saturation-mutagenesis map of the sites `pos` / `strand` (device int64 / uint8, 1 = '-') of a ``PackedGenome``: a
+    ``MutagenesisMap``.  Every chunk of `chunk_windows` variant ids runs enumerate -> encode -> ``forward_symbols`` -> reduce; the row
+    buffers are allocated once.  The map is bit-identical for every `chunk_windows`.  Serves Network1 / Network2 in eval mode whose
+    ``symbols_entry_ok()``; anything else raises RuntimeError with the reason.  `timings`: an optional dict that receives the device
+    time of the chunks' three phases from HIP events (``rows_encode_ms``, ``forward_ms``, ``reduce_ms``; it synchronises at the end)."""
+    R, r = _require_model(model, local_radius, local_order)
+    pos, strand = _sites(genome, model, pos, strand)
+    if chunk_windows < 1:
+        raise ValueError("chunk_windows must be >= 1")
+    dev, n, W, n_class = pos.device, pos.shape[0], 2 * R + 1, model.n_class
+    with_cat = model.model_no == 2
+    with torch.no_grad(), torch.cuda.device(dev):
+        ref_symbols = genome.encode_symbols(pos, strand, R).sym
+        ref_cat = genome.encode_kmer(pos, strand, r, local_order) if with_cat else None
+        ref_logp = model.forward_symbols(ref_cat, ref_symbols) if n else torch.empty((0, n_class), dtype=torch.float32, device=dev)
+        # every element is written by the reduce (one writer each): no fill
+        delta = torch.empty((n, W, 4, n_class), dtype=torch.float32, device=dev)
+        logp_map = torch.empty_like(delta) if return_logp else None
+        total = n * W * 3
+        cap = min(int(chunk_windows), max(total, 1))
+        row_pos = torch.empty(cap, dtype=torch.int64, device=dev)
+        row_strand = torch.empty(cap, dtype=torch.uint8, device=dev)
+        sub_pos = torch.empty(cap, dtype=torch.int64, device=dev)
+        sub_base = torch.empty(cap, dtype=torch.uint8, device=dev)
+        symbols = torch.empty((cap, W), dtype=torch.uint8, device=dev)
+        cat_x = torch.empty((cap, 2 * r + 1 - (local_order - 1)), dtype=torch.int64, device=dev) if with_cat else None
+        lib, g, stream = _lib.lib(), genome.as_struct(dev), _lib.current_stream_ptr(dev)
+        marks = []
+
+        def mark():
+            if timings is not None:
+                marks.append(torch.cuda.Event(enable_timing=True))
+                marks[-1].record()
+
+        for first in range(0, total, cap):
+            m = min(cap, total - first)
+            mark()
+            _lib.check(lib.mural_mutagenesis_rows(C.byref(g), pos.data_ptr(), strand.data_ptr(), n, R, first, m, row_pos.data_ptr(),
+                                                  row_strand.data_ptr(), sub_pos.data_ptr(), sub_base.data_ptr(), stream))
+            _lib.check(lib.mural_encode_subst_windows(C.byref(g), row_pos.data_ptr(), row_strand.data_ptr(), sub_pos.data_ptr(),
+                                                      sub_base.data_ptr(), m, R, r, int(local_order), symbols.data_ptr(),
+                                                      cat_x.data_ptr() if with_cat else None, stream))
+            mark()
+            var = model.forward_symbols(cat_x[:m] if with_cat else None, symbols[:m])
+            mark()
+            _lib.check(lib.mural_mutagenesis_reduce(ref_logp.data_ptr(), var.data_ptr(), ref_symbols.data_ptr(), n, R, n_class, first, m,
+                                                    delta.data_ptr(), logp_map.data_ptr() if return_logp else None, stream))
+            mark()
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            for k, name in enumerate(("rows_encode_ms", "forward_ms", "reduce_ms")):
+                timings[name] = timings.get(name, 0.0) + sum(marks[c + k].elapsed_time(marks[c + k + 1]) for c in range(0, len(marks), 4))
+    return MutagenesisMap(delta, ref_logp, ref_symbols, logp_map, pos, strand, R)
+
+
+def variant_footprint(model, genome, var_pos, var_base, strand, local_radius=None, local_order=3, chunk_windows=1 << 17):
+    """What each variant does to the sites around it: for variant i (`var_pos` '+'-strand position, `var_base` '+'-strand base 0..3) the
+    change in log-probability of every neighbouring site var_pos + d, d in [-R, R], read on `strand` (uint8 per variant, 1 = '-'), as
+    ``(delta float32 (m, W, n_class), focal uint8 (m, W))``: entry [i, d + R].  d = 0 and neighbours outside the chromosome are NaN.
+    `focal` is each neighbour's reference focal symbol on `strand` (MURAL_SYM_*; N outside the chromosome), for masking to the model's
+    site class.  Rows go through the same encoder and ``forward_symbols`` as ``saturation_mutagenesis``: entry (i, d) equals, bit for
+    bit, that map's entry of site var_pos + d at the column and alternative that name the same genomic substitution."""
+    R, r = _require_model(model, local_radius, local_order)
+    var_pos, strand = _sites(genome, model, var_pos, strand)
+    var_base = _lib.require_cuda(torch.as_tensor(var_base), "var_base").to(torch.uint8).contiguous()
+    if var_base.shape != var_pos.shape:
+        raise ValueError("var_base must be as long as var_pos")
+    if chunk_windows < 1:
+        raise ValueError("chunk_windows must be >= 1")
+    dev, m, W, n_class = var_pos.device, var_pos.shape[0], 2 * R + 1, model.n_class
+    with_cat = model.model_no == 2
+    with torch.no_grad(), torch.cuda.device(dev):
+        d = torch.arange(-R, R + 1, dtype=torch.int64, device=dev)
+        row_pos = (var_pos[:, None] + d[None, :]).reshape(-1).contiguous()
+        row_strand = strand[:, None].expand(m, W).reshape(-1).contiguous()
+        sub_pos = var_pos[:, None].expand(m, W).reshape(-1).contiguous()
+        sub_base = var_base[:, None].expand(m, W).reshape(-1).contiguous()
+        none = torch.full_like(sub_base, NO_SUBST)
+        total = m * W
+        cap = min(int(chunk_windows), max(total, 1))
+        symbols = torch.empty((cap, W), dtype=torch.uint8, device=dev)
+        cat_x = torch.empty((cap, 2 * r + 1 - (local_order - 1)), dtype=torch.int64, device=dev) if with_cat else None
+        delta = torch.empty((total, n_class), dtype=torch.float32, device=dev)
+        focal = torch.empty(total, dtype=torch.uint8, device=dev)
+        for c0 in range(0, total, cap):
+            k = min(cap, total - c0)
+            rows = slice(c0, c0 + k)
+            logp = []
+            for base in (sub_base, none):
+                _encode_subst_into(genome, row_pos[rows], row_strand[rows], sub_pos[rows], base[rows], R, r, local_order, symbols, cat_x)
+                logp.append(model.forward_symbols(cat_x[:k] if with_cat else None, symbols[:k]))
+            delta[rows] = logp[0] - logp[1]
+            focal[rows] = symbols[:k, R]                      # (the unchanged windows were encoded last)
+        dead = (row_pos < 0) | (row_pos >= genome.length) | (row_pos == sub_pos)
+        delta = torch.where(dead[:, None], torch.full_like(delta, float("nan")), delta)
+    return delta.reshape(m, W, n_class), focal.reshape(m, W)

@@ -19,6 +19,8 @@ import torch.distributed as dist
 
 from . import _lib
 # the names that moved to sinks.py and summaries.py, re-exported: bench.py, the tools and the tests import them from here
+from .mutagenesis import (MutagenesisMap, encode_subst_windows_host, mutagenesis_reduce_host, mutagenesis_rows_host,  # noqa: F401
+                          saturation_mutagenesis, variant_footprint)
 from .sinks import (TeeSink, TsvSink, _name_table, _np, _tsv_struct, format_rows_host, shard_bounds,  # noqa: F401
                     write_predictions)
 from .summaries import (_MOTIF_ORD_SHIFT, _MOTIF_POS_SHIFT, SummarySink, _calib_fold, _calib_lo_cells, _kmer_collapse,  # noqa: F401
