@@ -118,6 +118,24 @@ int mural_mutagenesis_rows(const MuralGenome* g, const int64_t* pos, const uint8
                            void* stream);
 int mural_mutagenesis_reduce(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites, int32_t radius,
                              int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map, void* stream);
+/* The same three for either window (the three above are these with indel = 0; same kernels, same bits):
+ *   indel = 0: [pos - R, pos + R], W = 2*radius + 1;   indel = 1: [pos - R + 1, pos + R], W = 2*radius (the INDEL model's window).
+ * mural_encode_subst_symbols: row i is, bit for bit, mural_encode_symbols(.., radius, indel) on the genome with the base at sub_pos[i]
+ *   replaced; symbols dev uint8 [n][W], 4-byte aligned.
+ * mural_mutagenesis_rows_window: ids v = (site*W + j)*3 + a with that W; sub_pos is the genomic position of column j of that window
+ *   (indel = 1: pos - R + 1 + j on '+', pos + R - j on '-').
+ * mural_mutagenesis_reduce_window: takes W itself (any W >= 1; ref_symbols [n_sites][W], maps [n_sites][W][4][n_class]).
+ * mural_scores_log_softmax: out[i][c] = s[c] - (max_c s + log sum_c exp(s[c] - max_c s)), float32, one thread per row, classes in
+ *   ascending order: a row's bits do not depend on n or on the other rows.  Turns the INDEL forward's Softplus scores into the
+ *   log-probabilities of softmax(scores) (what predict writes).  scores / out: dev float [n][n_class], two buffers. */
+int mural_encode_subst_symbols(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                               const uint8_t* sub_base, int64_t n, int32_t radius, int32_t indel, uint8_t* symbols, void* stream);
+int mural_mutagenesis_rows_window(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n_sites, int32_t radius,
+                                  int32_t indel, int64_t first, int64_t count, int64_t* row_pos, uint8_t* row_strand, int64_t* sub_pos,
+                                  uint8_t* sub_base, void* stream);
+int mural_mutagenesis_reduce_window(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites, int32_t W,
+                                    int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map, void* stream);
+int mural_scores_log_softmax(const float* scores, int64_t n, int32_t n_class, float* out, void* stream);
 
 /* One training batch gathered and encoded from ROW INDICES in one launch (csrc/train_batch.hip): the rows of a batch may lie on several
  * chromosomes, which the three encoders above cannot take in one call.
@@ -344,6 +362,15 @@ int mural_indel_forward_dense(const MuralIndelModel* m, const float* distal_x, i
  * exists in HBM.  pos: dev int64 [n], strand: dev uint8 [n] (1 = '-'); the model's length must be 2 * R.                    */
 int mural_indel_forward_packed(const MuralIndelModel* m, const MuralGenome* genome, const int64_t* pos, const uint8_t* strand,
                                int64_t n, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same from one symbol byte per window column: symbols dev uint8 [n][length], MURAL_SYM_* codes 0..14 (what mural_encode_symbols /
+ * mural_encode_subst_symbols write).  The scores equal, bit for bit, mural_indel_forward_dense on the one-hot windows the bytes stand
+ * for (and so mural_indel_forward_packed when the bytes are mural_encode_symbols(.., indel = 1) of the sites).  Where the first level is
+ * the fused kernel (down_list[0] == 1, 8 channels, k = 7, length a multiple of 4) the bytes are its input as they are: no dense window
+ * exists in HBM and nothing is classified back; any other geometry expands each chunk into the workspace first.  A byte above 14 is
+ * outside the contract: it reads as N in both geometries and never causes an access outside the caller's buffers.
+ * mural_indel_workspace_bytes(m, n) suffices; n == 0 launches nothing.                                                         */
+int mural_indel_forward_symbols(const MuralIndelModel* m, const uint8_t* symbols, int64_t n, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training-mode building blocks (MuRaL/training.py:404-450 over model_snv.py:439-525): forward with

@@ -310,6 +310,7 @@ PROTOTYPES = {
                                             C.c_void_p]),
     "mural_indel_forward_packed": (C.c_int, [C.c_void_p, C.POINTER(MuralGenome), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mural_indel_forward_symbols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mural_indel_train_workspace_bytes": (C.c_size_t, [C.POINTER(MuralIndelShape), I64]),
     "mural_indel_train_forward": (C.c_int, [C.POINTER(MuralIndelShape), C.POINTER(MuralIndelParams), VP, I64, C.c_float, C.c_uint64, VP,
                                             C.c_float, VP, VP, C.c_size_t, VP]),
@@ -381,6 +382,10 @@ PROTOTYPES = {
     "mural_encode_subst_windows": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, VP, I64, I32, I32, I32, VP, VP, VP]),
     "mural_mutagenesis_rows": (C.c_int, [C.POINTER(MuralGenome), VP, VP, I64, I32, I64, I64, VP, VP, VP, VP, VP]),
     "mural_mutagenesis_reduce": (C.c_int, [VP, VP, VP, I64, I32, I32, I64, I64, VP, VP, VP]),
+    "mural_encode_subst_symbols": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, VP, I64, I32, I32, VP, VP]),
+    "mural_mutagenesis_rows_window": (C.c_int, [C.POINTER(MuralGenome), VP, VP, I64, I32, I32, I64, I64, VP, VP, VP, VP, VP]),
+    "mural_mutagenesis_reduce_window": (C.c_int, [VP, VP, VP, I64, I32, I32, I64, I64, VP, VP, VP]),
+    "mural_scores_log_softmax": (C.c_int, [VP, I64, I32, VP, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),
     "mural_profile_begin": (C.c_int, []),
     "mural_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -82,7 +82,8 @@ struct ConvBlockArgs {
   const float* sym_bias;
   int sym_taps;
   // optional, instead of the genome (persistent first-level kernel only): one symbol byte per column, [B][Lf] (0 .. 14 the MuRaL symbols,
-  // 16: no symbol -- the column's floats are read from f_in [B][4][Lf], which must then be set)
+  // 16: no symbol -- the column's floats are read from f_in [B][4][Lf], which must then be set; with f_in == nullptr the bytes are the
+  // caller's, symbols entry: a byte above 14 reads as N and nothing else is read)
   const uint8_t* sym_in;
   // optional (genome source): the per-symbol layer and the k=7 front composed into ONE conv of 6 + sym_taps taps, summed per group of
   // three taps over A C G T (indel_enc0_compose, indel_level0.hip): the persistent first-level kernel takes the launch then
@@ -123,6 +124,7 @@ void indel_enc0_compose(const float* fw, const float* fb, const float* symtab, c
                         std::vector<float>* t1, std::vector<float>* bias);
 bool indel_enc0_supported(const ConvBlockArgs& a);
 int launch_indel_enc0(const ConvBlockArgs& a, hipStream_t stream);
+int launch_indel_enc0_symbols(const ConvBlockArgs& a, int tiles_per_row, long long total, hipStream_t stream);      // indel_level0_symbols.hip
 // the last decoder level (polyphase front from 16 channels, + skip, with or without the out_conv tail), persistent as well
 bool indel_dec0_supported(const ConvBlockArgs& a);
 int launch_indel_dec0(const ConvBlockArgs& a, hipStream_t stream);

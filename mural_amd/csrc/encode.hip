@@ -232,7 +232,7 @@ int launch_dense_to_symbols(const float* x, int64_t n, int L, uint8_t* sym, int3
 using namespace mural;
 
 extern "C" const char* mural_last_error(void) { return mural::last_error_cstr(); }
-extern "C" int mural_abi_version(void) { return 3; }
+extern "C" int mural_abi_version(void) { return 4; }
 
 extern "C" int mural_encode_kmer(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n,
                                  int32_t radius, int32_t order, int32_t indel, int64_t* out, void* stream) {

@@ -355,7 +355,8 @@ struct GenomeSrc {      // packed-genome source of the first level's front input
   const int64_t* pos = nullptr;
   const uint8_t* strand = nullptr;
   int off = 0;
-  const uint8_t* sym = nullptr;      // or: one symbol byte per column of the dense windows (ConvBlockArgs::sym_in; the front input is the dense tensor)
+  const uint8_t* sym = nullptr;      // or: one symbol byte per column (ConvBlockArgs::sym_in; the front input is the dense tensor they were
+                                     // classified from, or nullptr where the bytes are the caller's: symbols entry)
 };
 
 static int run_block(const MuralIndelModel* m, const FoldedConv& f5, const FoldedConv& f1, const float* x, int B, int L,
@@ -401,14 +402,21 @@ static int run_block(const MuralIndelModel* m, const FoldedConv& f5, const Folde
   return run_conv(m, f1, H, B, L, out, L, 1, 1, ACT_NONE, x, skip, stream);
 }
 
-// distal_x != nullptr: dense entry; otherwise the windows come from the packed genome (genome, pos, strand; window
-// [pos - radius + 1, pos + radius], preprocessing.py:564-566)
+// the switches of the byte route into the first level, shared by the dense and the symbols entry so that the two stay bit-equal under
+// each (MURAL_INDEL_DENSE_SYMBOLS=0: the input layer and the first level as launches of their own on the dense tensor)
+static bool sym_route_off() {
+  return dev_int("MURAL_INDEL_DENSE_SYMBOLS", 1) == 0 || dev_int("MURAL_INDEL_ENC0", 1) == 0 || dev_env("MURAL_CONVBLOCK8_VALU");
+}
+
+// distal_x != nullptr: dense entry; symbols != nullptr: one MURAL_SYM_* byte per column, [n][length]; otherwise the windows come from
+// the packed genome (genome, pos, strand; window [pos - radius + 1, pos + radius], preprocessing.py:564-566)
 static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, const MuralGenome* genome, const int64_t* pos,
-                              const uint8_t* strand, int64_t n, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
+                              const uint8_t* strand, int64_t n, float* out, void* workspace, size_t workspace_bytes, void* stream_,
+                              const uint8_t* symbols = nullptr) {
   MURAL_REQUIRE(m, "model handle is NULL");
   MURAL_REQUIRE(n >= 0, "negative batch");
   if (n == 0) return MURAL_OK;
-  MURAL_REQUIRE((distal_x || (genome && pos && strand)) && out, "input/out is NULL");
+  MURAL_REQUIRE((distal_x || symbols || (genome && pos && strand)) && out, "input/out is NULL");
   if (!workspace || workspace_bytes < mural_indel_workspace_bytes(m, n)) {
     set_error("workspace too small: need %zu bytes, got %zu", mural_indel_workspace_bytes(m, n), workspace_bytes);
     return MURAL_E_WORKSPACE;
@@ -464,14 +472,22 @@ static int indel_forward_impl(const MuralIndelModel* m, const float* distal_x, c
     GenomeSrc gs;
     const bool first_fused = sh.down[0] == 1 && block_fusable(m->up5[0], m->up1[0], m->len[0]) && front_fusable(m->up_l[0], 1, m->ch[0]);
     const float* x = nullptr;
-    if (distal_x) {
+    if (symbols) {
+      // symbols entry: where the dense entry would classify its windows into bytes, the caller's bytes ARE that buffer (the first
+      // level reads a byte above 14 as N and never looks for a dense window behind it); any other geometry expands the chunk into
+      // X and goes on as the dense entry does
+      const uint8_t* sy = symbols + (size_t)c0 * Lx;
+      if (first_fused && m->e0_t3 && (Lx & 3) == 0 && !sym_route_off()) {
+        gs.sym = sy;
+      } else {
+        if ((rc = mural_op_symbols_to_dense(sy, B, Lx, X, stream))) return rc;
+        x = X;
+      }
+    } else if (distal_x) {
       x = distal_x + (size_t)c0 * 4 * Lx;
       // dense one-hot windows (what the reference's loader yields): classified into one symbol byte per column and taken by the same
       // persistent table-driven first level as the packed entry; columns that are no MuRaL symbol are evaluated from their floats there
-      // (MURAL_INDEL_DENSE_SYMBOLS=0: the input layer and the first level as launches of their own on the dense tensor)
-      const bool sym_off = dev_int("MURAL_INDEL_DENSE_SYMBOLS", 1) == 0 || dev_int("MURAL_INDEL_ENC0", 1) == 0 ||
-                           dev_env("MURAL_CONVBLOCK8_VALU");
-      if (first_fused && m->e0_t3 && (Lx & 3) == 0 && !sym_off) {
+      if (first_fused && m->e0_t3 && (Lx & 3) == 0 && !sym_route_off()) {
         if ((rc = launch_dense_to_symbols(x, B, Lx, reinterpret_cast<uint8_t*>(X), nullptr, stream, 16))) return rc;
         gs.sym = reinterpret_cast<const uint8_t*>(X);
       }
@@ -586,4 +602,14 @@ extern "C" int mural_indel_forward_packed(const MuralIndelModel* m, const MuralG
   MURAL_REQUIRE((m->shape.length & 1) == 0, "the indel window is 2 * distal_radius wide: model length %d is odd", m->shape.length);
   MURAL_REQUIRE(n <= 0 || (pos && strand), "pos/strand is NULL");
   return indel_forward_impl(m, nullptr, genome, pos, strand, n, out, workspace, workspace_bytes, stream_);
+}
+
+// The same from one MURAL_SYM_* byte per window column (symbols dev [n][length]; what mural_encode_symbols / mural_encode_subst_symbols
+// write).  With the geometry of the fused first level the bytes are that kernel's input as they are: no dense window exists in HBM and
+// nothing is classified back.  Any other geometry expands each chunk into the workspace and goes on as the dense entry.  Either way the
+// scores are those of mural_indel_forward_dense on the one-hot windows the bytes stand for, bit for bit.  A byte above 14 reads as N.
+extern "C" int mural_indel_forward_symbols(const MuralIndelModel* m, const uint8_t* symbols, int64_t n, float* out, void* workspace,
+                                           size_t workspace_bytes, void* stream_) {
+  MURAL_REQUIRE(n <= 0 || symbols, "symbols is NULL");
+  return indel_forward_impl(m, nullptr, nullptr, nullptr, nullptr, n, out, workspace, workspace_bytes, stream_, symbols);
 }

@@ -1,7 +1,9 @@
-// In-silico saturation mutagenesis around the SNV forward: the window "as if one base were different" (one row per (site, substitution)),
+// In-silico saturation mutagenesis around the SNV and INDEL forwards: the window "as if one base were different" (one row per (site, substitution)),
 // the enumerator of a window's 3 * W substitutions, and the scatter of the re-predicted log-probabilities into the map.
 // Window, strand and k-mer-id rules are encode.hip's, through the same column helpers (encode_window.h; reference:
-// MuRaL/data/preprocessing.py:636-723, 756-816).  The forward in between is mural_snv_forward_symbols, untouched.
+// MuRaL/data/preprocessing.py:636-723, 756-816; windows :559-567: SNV [pos - R, pos + R], INDEL [pos - R + 1, pos + R]).  The forward in
+// between is mural_snv_forward_symbols or mural_indel_forward_symbols; for the latter mural_scores_log_softmax turns its Softplus
+// scores into the log-probabilities the map is made of.
 #include "common.h"
 #include "encode_window.h"
 
@@ -19,7 +21,7 @@ __device__ __forceinline__ OneSubst row_subst(const MuralGenome& g, const int64_
 // 4-byte store where the group lies in one row, as encode_symbols_kernel does); units [sym_groups, sym_groups + n * ncol): one k-mer id.
 __global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
                                                             const int64_t* __restrict__ sub_pos, const uint8_t* __restrict__ sub_base, int64_t n,
-                                                            int W, int radius, int lwidth, int lradius, int order, int ncol,
+                                                            int W, int off, int lwidth, int lradius, int order, int ncol,
                                                             int64_t sym_groups, uint8_t* __restrict__ symbols, int64_t* __restrict__ cat_x) {
   const int64_t total_sym = symbols ? n * W : 0;
   const int64_t units = sym_groups + (cat_x ? n * ncol : 0);
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const
       const int64_t row = i0 / W;
       const int j = (int)(i0 - row * W);
       if (j + 3 < W) {
-        const int64_t ws = pos[row] - radius;
+        const int64_t ws = pos[row] + off;
         const bool neg = strand[row] != 0;
         const OneSubst sub = row_subst(g, sub_pos, sub_base, row);
         uint32_t packed = 0;
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const
           const int64_t i = i0 + e;
           const int64_t r = i / W;
           const int jj = (int)(i - r * W);
-          symbols[i] = (uint8_t)window_symbol(g, pos[r] - radius, W, strand[r] != 0, jj, row_subst(g, sub_pos, sub_base, r));
+          symbols[i] = (uint8_t)window_symbol(g, pos[r] + off, W, strand[r] != 0, jj, row_subst(g, sub_pos, sub_base, r));
         }
       }
     } else {
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const
 
 // variant id v = (site * W + j) * 3 + a  ->  the row (site's pos / strand) and its '+'-strand substitution
 __global__ __launch_bounds__(256) void mutagenesis_rows_kernel(MuralGenome g, const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
-                                                               int W, int radius, int64_t first, int64_t count, int64_t* __restrict__ row_pos,
+                                                               int W, int off, int64_t first, int64_t count, int64_t* __restrict__ row_pos,
                                                                uint8_t* __restrict__ row_strand, int64_t* __restrict__ sub_pos,
                                                                uint8_t* __restrict__ sub_base) {
   for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) {
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void mutagenesis_rows_kernel(MuralGenome g, co
     const int j = (int)(cell - site * W);
     const int64_t p = pos[site];
     const bool neg = strand[site] != 0;
-    const uint32_t ref = window_symbol(g, p - radius, W, neg, j, NoSubst{});      // window orientation
+    const uint32_t ref = window_symbol(g, p + off, W, neg, j, NoSubst{});      // window orientation
     uint32_t b = 255u;
     if (ref < 4u) {
       const uint32_t alt = a + (a >= ref ? 1u : 0u);                               // a-th of {A, C, G, T} \ {ref}, ascending
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void mutagenesis_rows_kernel(MuralGenome g, co
     }
     row_pos[k] = p;
     row_strand[k] = neg ? 1 : 0;
-    sub_pos[k] = window_genome_pos(p - radius, W, neg, j);
+    sub_pos[k] = window_genome_pos(p + off, W, neg, j);
     sub_base[k] = (uint8_t)b;
   }
 }
@@ -119,6 +121,20 @@ __global__ __launch_bounds__(256) void mutagenesis_reduce_kernel(const float* __
   }
 }
 
+// out[i][c] = s[c] - (max + log sum exp(s - max)): one thread per row, classes in ascending order, so a row's bits depend on nothing
+// but the row
+__global__ __launch_bounds__(256) void scores_log_softmax_kernel(const float* __restrict__ scores, int64_t n, int C, float* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float* __restrict__ s = scores + i * C;
+    float mx = s[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, s[c]);
+    float sum = 0.f;
+    for (int c = 0; c < C; ++c) sum += expf(s[c] - mx);
+    const float lse = mx + logf(sum);
+    for (int c = 0; c < C; ++c) out[i * C + c] = s[c] - lse;
+  }
+}
+
 static int grid_for(int64_t units, int block, int cap) {
   const int64_t blocks = (units + block - 1) / block;
   return (int)(blocks < cap ? blocks : cap);
@@ -128,16 +144,22 @@ static int grid_for(int64_t units, int block, int cap) {
 
 using namespace mural;
 
-extern "C" int mural_encode_subst_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
-                                          const uint8_t* sub_base, int64_t n, int32_t radius, int32_t local_radius, int32_t local_order,
-                                          uint8_t* symbols, int64_t* cat_x, void* stream) {
+static int require_genome(const MuralGenome* g) {
   MURAL_REQUIRE(g && g->packed2 && g->nmask, "genome pointers must not be NULL");
   MURAL_REQUIRE(g->n_amb == 0 || (g->amb_pos && g->amb_sym), "genome: n_amb > 0 needs amb_pos and amb_sym");
-  MURAL_REQUIRE(n >= 0, "encode_subst_windows: n must be >= 0");
+  return MURAL_OK;
+}
+
+// symbols (window of `radius` / `indel`) and / or cat_x (the SNV local window) of the rows
+static int encode_subst(const char* who, const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                        const uint8_t* sub_base, int64_t n, int32_t radius, int32_t indel, int32_t local_radius, int32_t local_order,
+                        uint8_t* symbols, int64_t* cat_x, void* stream) {
+  if (int rc = require_genome(g)) return rc;
+  MURAL_REQUIRE(n >= 0, "%s: n must be >= 0", who);
   int off = 0, W = 0, loff = 0, lwidth = 0, ncol = 0;
   if (symbols) {
-    if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
-    MURAL_REQUIRE((reinterpret_cast<uintptr_t>(symbols) & 3u) == 0, "encode_subst_windows: symbols must be 4-byte aligned");
+    if (int rc = window_geometry(radius, indel, &off, &W)) return rc;
+    MURAL_REQUIRE((reinterpret_cast<uintptr_t>(symbols) & 3u) == 0, "%s: symbols must be 4-byte aligned", who);
   }
   if (cat_x) {
     MURAL_REQUIRE(local_order >= 1 && local_order <= 12, "local_order must be in [1,12], got %d", local_order);
@@ -147,10 +169,40 @@ extern "C" int mural_encode_subst_windows(const MuralGenome* g, const int64_t* p
   }
   if (n == 0 || (!symbols && !cat_x)) return MURAL_OK;
   MURAL_REQUIRE(pos && strand && sub_pos && sub_base, "pos/strand/sub_pos/sub_base must not be NULL");
+  MURAL_REQUIRE(n <= INT64_MAX / 4 / (W > ncol ? W : ncol), "%s: n out of range", who);
   const int64_t sym_groups = symbols ? (n * W + 3) / 4 : 0;
   const int64_t units = sym_groups + (cat_x ? n * ncol : 0);
   hipLaunchKernelGGL(subst_windows_kernel, dim3(grid_for(units, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, sub_pos,
-                     sub_base, n, W, (int)radius, lwidth, (int)local_radius, (int)local_order, ncol, sym_groups, symbols, cat_x);
+                     sub_base, n, W, off, lwidth, (int)local_radius, (int)local_order, ncol, sym_groups, symbols, cat_x);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
+extern "C" int mural_encode_subst_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                                          const uint8_t* sub_base, int64_t n, int32_t radius, int32_t local_radius, int32_t local_order,
+                                          uint8_t* symbols, int64_t* cat_x, void* stream) {
+  return encode_subst("encode_subst_windows", g, pos, strand, sub_pos, sub_base, n, radius, 0, local_radius, local_order, symbols, cat_x, stream);
+}
+
+extern "C" int mural_encode_subst_symbols(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                                          const uint8_t* sub_base, int64_t n, int32_t radius, int32_t indel, uint8_t* symbols, void* stream) {
+  MURAL_REQUIRE(n <= 0 || symbols, "encode_subst_symbols: symbols must not be NULL");
+  return encode_subst("encode_subst_symbols", g, pos, strand, sub_pos, sub_base, n, radius, indel, 0, 0, symbols, nullptr, stream);
+}
+
+extern "C" int mural_mutagenesis_rows_window(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n_sites, int32_t radius,
+                                             int32_t indel, int64_t first, int64_t count, int64_t* row_pos, uint8_t* row_strand,
+                                             int64_t* sub_pos, uint8_t* sub_base, void* stream) {
+  if (int rc = require_genome(g)) return rc;
+  int off, W;
+  if (int rc = window_geometry(radius, indel, &off, &W)) return rc;
+  MURAL_REQUIRE(n_sites >= 0 && n_sites <= INT64_MAX / (3 * (int64_t)W), "mutagenesis_rows: n_sites out of range");
+  MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_sites * W * 3 - count,
+                "mutagenesis_rows: ids [first, first + count) must lie in [0, n_sites * W * 3)");
+  if (count == 0) return MURAL_OK;
+  MURAL_REQUIRE(pos && strand && row_pos && row_strand && sub_pos && sub_base, "mutagenesis_rows: pointers must not be NULL");
+  hipLaunchKernelGGL(mutagenesis_rows_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, W,
+                     off, first, count, row_pos, row_strand, sub_pos, sub_base);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }
@@ -158,17 +210,21 @@ extern "C" int mural_encode_subst_windows(const MuralGenome* g, const int64_t* p
 extern "C" int mural_mutagenesis_rows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, int64_t n_sites, int32_t radius,
                                       int64_t first, int64_t count, int64_t* row_pos, uint8_t* row_strand, int64_t* sub_pos,
                                       uint8_t* sub_base, void* stream) {
-  MURAL_REQUIRE(g && g->packed2 && g->nmask, "genome pointers must not be NULL");
-  MURAL_REQUIRE(g->n_amb == 0 || (g->amb_pos && g->amb_sym), "genome: n_amb > 0 needs amb_pos and amb_sym");
-  int off, W;
-  if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
-  MURAL_REQUIRE(n_sites >= 0 && n_sites <= INT64_MAX / (3 * (int64_t)W), "mutagenesis_rows: n_sites out of range");
+  return mural_mutagenesis_rows_window(g, pos, strand, n_sites, radius, 0, first, count, row_pos, row_strand, sub_pos, sub_base, stream);
+}
+
+extern "C" int mural_mutagenesis_reduce_window(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites,
+                                               int32_t W, int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map,
+                                               void* stream) {
+  MURAL_REQUIRE(W >= 1, "mutagenesis_reduce: W must be >= 1, got %d", W);
+  MURAL_REQUIRE(n_class >= 1, "mutagenesis_reduce: n_class must be >= 1, got %d", n_class);
+  MURAL_REQUIRE(n_sites >= 0 && n_sites <= INT64_MAX / (4 * (int64_t)W * n_class), "mutagenesis_reduce: n_sites out of range");
   MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_sites * W * 3 - count,
-                "mutagenesis_rows: ids [first, first + count) must lie in [0, n_sites * W * 3)");
+                "mutagenesis_reduce: ids [first, first + count) must lie in [0, n_sites * W * 3)");
   if (count == 0) return MURAL_OK;
-  MURAL_REQUIRE(pos && strand && row_pos && row_strand && sub_pos && sub_base, "mutagenesis_rows: pointers must not be NULL");
-  hipLaunchKernelGGL(mutagenesis_rows_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, W,
-                     (int)radius, first, count, row_pos, row_strand, sub_pos, sub_base);
+  MURAL_REQUIRE(ref_logp && var_logp && ref_symbols && delta, "mutagenesis_reduce: pointers must not be NULL");
+  hipLaunchKernelGGL(mutagenesis_reduce_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, ref_logp, var_logp,
+                     ref_symbols, (int)W, (int)n_class, first, count, reinterpret_cast<uint32_t*>(delta), reinterpret_cast<uint32_t*>(logp_map));
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }
@@ -178,14 +234,14 @@ extern "C" int mural_mutagenesis_reduce(const float* ref_logp, const float* var_
                                         void* stream) {
   int off, W;
   if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
-  MURAL_REQUIRE(n_class >= 1, "mutagenesis_reduce: n_class must be >= 1, got %d", n_class);
-  MURAL_REQUIRE(n_sites >= 0 && n_sites <= INT64_MAX / (4 * (int64_t)W * n_class), "mutagenesis_reduce: n_sites out of range");
-  MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_sites * W * 3 - count,
-                "mutagenesis_reduce: ids [first, first + count) must lie in [0, n_sites * W * 3)");
-  if (count == 0) return MURAL_OK;
-  MURAL_REQUIRE(ref_logp && var_logp && ref_symbols && delta, "mutagenesis_reduce: pointers must not be NULL");
-  hipLaunchKernelGGL(mutagenesis_reduce_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, ref_logp, var_logp,
-                     ref_symbols, W, (int)n_class, first, count, reinterpret_cast<uint32_t*>(delta), reinterpret_cast<uint32_t*>(logp_map));
+  return mural_mutagenesis_reduce_window(ref_logp, var_logp, ref_symbols, n_sites, W, n_class, first, count, delta, logp_map, stream);
+}
+
+extern "C" int mural_scores_log_softmax(const float* scores, int64_t n, int32_t n_class, float* out, void* stream) {
+  MURAL_REQUIRE(n >= 0 && n_class >= 1 && n <= INT64_MAX / n_class / 4, "scores_log_softmax: bad sizes (n %lld, n_class %d)", (long long)n, n_class);
+  if (n == 0) return MURAL_OK;
+  MURAL_REQUIRE(scores && out, "scores_log_softmax: pointers must not be NULL");
+  hipLaunchKernelGGL(scores_log_softmax_kernel, dim3(grid_for(n, 256, 16384)), dim3(256), 0, (hipStream_t)stream, scores, n, (int)n_class, out);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }

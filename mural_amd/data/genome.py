@@ -256,12 +256,14 @@ class PackedGenome:
                                                       _lib.current_stream_ptr(self.device)))
         return SymbolWindows(out)
 
-    def encode_subst_windows(self, pos, strand, sub_pos, sub_base, radius, local_radius, local_order):
+    def encode_subst_windows(self, pos, strand, sub_pos, sub_base, radius, local_radius=None, local_order=None, model_type="snv"):
         """One row per (site, substitution): ``(symbols uint8 (n, 2 * radius + 1), cat_x int64 (n, 2 * local_radius + 1 - (local_order - 1)))``,
         bit for bit ``encode_symbols`` / ``encode_kmer`` of (pos, strand) on this genome with the base at the '+'-strand position `sub_pos`
-        replaced by the '+'-strand base `sub_base` (0..3; 255: none).  The genome itself is only read (``mural_amd.mutagenesis``)."""
+        replaced by the '+'-strand base `sub_base` (0..3; 255: none).  ``model_type="indel"``: ``(symbols uint8 (n, 2 * radius), None)`` of
+        the INDEL window, the local arguments are not read.  The genome itself is only read (``mural_amd.mutagenesis``)."""
         from ..mutagenesis import encode_subst_windows
-        return encode_subst_windows(self, pos, strand, sub_pos, sub_base, int(radius), int(local_radius), int(local_order))
+        return encode_subst_windows(self, pos, strand, sub_pos, sub_base, int(radius), None if local_radius is None else int(local_radius),
+                                    None if local_order is None else int(local_order), model_type)
 
     def encode_onehot(self, pos, strand, radius, model_type="snv"):
         """float32 (n, 4, W) one-hot windows (N -> 0.25 each, other IUPAC codes -> their fractional columns), exact w.r.t.

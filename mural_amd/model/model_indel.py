@@ -182,5 +182,30 @@ class UNet_Small(nn.Module):
                                                             self._ws.data_ptr(), self._ws.numel(), _lib.current_stream_ptr(dev)))
         return out
 
+    def forward_symbols(self, symbols):
+        """Scores of windows given as one symbol byte per column: a uint8 (n, L) device tensor of MURAL_SYM_* codes or ``SymbolWindows``
+        (what ``PackedGenome.encode_symbols(.., "indel")`` / ``encode_subst_windows(.., model_type="indel")`` return).  Eval mode only:
+        ONE library call (``mural_indel_forward_symbols``) -- with the fused first level the bytes are that kernel's input, no dense
+        window is assembled.  Bit-equal to ``forward`` on the one-hot windows the bytes stand for; a byte above 14 reads as N."""
+        if self.training:
+            raise RuntimeError("internal: the fused inference kernels serve eval mode only")
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("mural_amd models run on a HIP device only: call model.to('cuda') first")
+        sym = getattr(symbols, "sym", symbols)
+        if not isinstance(sym, torch.Tensor) or sym.dim() != 2 or sym.dtype != torch.uint8:
+            raise TypeError("symbols must be a uint8 (n, L) tensor or SymbolWindows")
+        sym = _lib.require_cuda(sym, "symbols").contiguous()
+        n, length = sym.shape
+        with torch.cuda.device(dev):
+            handle = self._get_handle(length)
+            out = torch.empty((n, self.n_class), dtype=torch.float32, device=dev)
+            need = int(_lib.lib().mural_indel_workspace_bytes(handle, max(n, 1)))
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib().mural_indel_forward_symbols(handle, sym.data_ptr(), n, out.data_ptr(), self._ws.data_ptr(),
+                                                             self._ws.numel(), _lib.current_stream_ptr(dev)))
+        return out
+
     def reverse_input(self, distal_input):
         return distal_input.flip([1, 2])

@@ -1,13 +1,17 @@
-"""In-silico saturation mutagenesis and variant footprints on top of the SNV forward (csrc/mutagenesis.hip).
+"""In-silico saturation mutagenesis and variant footprints on top of the SNV and INDEL forwards (csrc/mutagenesis.hip; DESIGN.md
+sections 3.27 and 3.28).
 
 ``saturation_mutagenesis`` answers "which bases of the +-distal_radius window make this site's rate what it is": every column of the
 window is replaced by each of its three alternatives, the window re-predicted, and the change in log-probability reported as a map
 ``delta[site, column, alternative base, class]``.  ``variant_footprint`` is the transposed question: what one variant does to the rate of
 every site around it.  Both encode "the window as if one base were different" on the device (``mural_encode_subst_windows``) and run the
-existing ``forward_symbols``; nothing patches a FASTA and no dense one-hot tensor is assembled.
+models' ``forward_symbols``; nothing patches a FASTA and no dense one-hot tensor is assembled.  For the INDEL model (``UNet_Small``)
+the window is [pos - R + 1, pos + R] (W = 2 R) and the log-probabilities are the log-softmax of the forward's Softplus scores
+(``mural_scores_log_softmax``), which is what predict writes.
 
 The numpy twins (``encode_subst_windows_host``, ``mutagenesis_rows_host``, ``mutagenesis_reduce_host``) are the specification the CPU
-tests pin against brute force (patch the sequence string, encode with the oracle).
+tests pin against brute force (patch the sequence string, encode with the oracle); ``log_softmax_host`` is the float64 twin of the
+log-softmax.
 """
 import ctypes as C
 
@@ -35,13 +39,20 @@ def _codes(genome):
     return np.asarray(genome, np.uint8)
 
 
-def _window_symbols_host(codes, pos, strand, radius, sub_pos=None, sub_base=None):
-    """(n, 2 * radius + 1) strand-oriented symbols of the sites' windows ('-': reversed and complemented; outside the record: N), with
-    the base at sub_pos replaced by sub_base where the row has a substitution."""
+def _window(radius, model_type="snv"):
+    """(offset of the window's first base from the site, W): csrc/common.h window_geometry"""
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
+    return (-radius, 2 * radius + 1) if model_type == "snv" else (-radius + 1, 2 * radius)
+
+
+def _window_symbols_host(codes, pos, strand, radius, sub_pos=None, sub_base=None, model_type="snv"):
+    """(n, W) strand-oriented symbols of the sites' windows ('-': reversed and complemented; outside the record: N), with the base at
+    sub_pos replaced by sub_base where the row has a substitution."""
     pos, neg = np.asarray(pos, np.int64), np.asarray(strand) != 0
-    W, L = 2 * radius + 1, len(codes)
-    off = np.arange(W, dtype=np.int64) - radius
-    gp = pos[:, None] + np.where(neg[:, None], -off[None, :], off[None, :])            # genome position of column j
+    (off0, W), L = _window(radius, model_type), len(codes)
+    j = np.arange(W, dtype=np.int64)
+    gp = pos[:, None] + off0 + np.where(neg[:, None], W - 1 - j[None, :], j[None, :])  # genome position of column j
     inside = (gp >= 0) & (gp < L)
     sym = np.full(gp.shape, 4, np.uint8)
     sym[inside] = codes[gp[inside]]
@@ -53,12 +64,15 @@ def _window_symbols_host(codes, pos, strand, radius, sub_pos=None, sub_base=None
     return np.where(neg[:, None], _COMPLEMENT[sym], sym).astype(np.uint8), gp
 
 
-def encode_subst_windows_host(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order):
+def encode_subst_windows_host(genome, pos, strand, sub_pos, sub_base, radius, local_radius=None, local_order=None, model_type="snv"):
     """The numpy twin of ``mural_encode_subst_windows``: (symbols uint8 (n, 2 * radius + 1), cat_x int64 (n, 2 * local_radius + 1 -
     (local_order - 1))) of the rows' windows on the genome with the base at sub_pos replaced by sub_base ('+'-strand base 0..3; above 3:
-    no substitution; a position outside the record or the window changes nothing)."""
+    no substitution; a position outside the record or the window changes nothing).  ``model_type="indel"``: the twin of
+    ``mural_encode_subst_symbols(.., indel = 1)``, (symbols uint8 (n, 2 * radius), None)."""
     codes = _codes(genome)
-    symbols, _ = _window_symbols_host(codes, pos, strand, radius, sub_pos, sub_base)
+    symbols, _ = _window_symbols_host(codes, pos, strand, radius, sub_pos, sub_base, model_type)
+    if model_type == "indel":
+        return symbols, None
     local, _ = _window_symbols_host(codes, pos, strand, local_radius, sub_pos, sub_base)
     ncol = 2 * local_radius + 1 - (local_order - 1)
     digit = local.astype(np.int64)
@@ -71,25 +85,28 @@ def encode_subst_windows_host(genome, pos, strand, sub_pos, sub_base, radius, lo
     return symbols, np.where(bad, 4 ** local_order, val)
 
 
-def mutagenesis_ids_host(first, count, radius):
-    """(site, column, a) of the variant ids [first, first + count): v = (site * W + column) * 3 + a."""
+def _ids(first, count, W):
     v = first + np.arange(count, dtype=np.int64)
     cell, a = v // 3, v % 3
-    W = 2 * radius + 1
     return cell // W, cell % W, a
 
 
-def mutagenesis_rows_host(genome, pos, strand, radius, first, count):
-    """The numpy twin of ``mural_mutagenesis_rows``: (row_pos int64, row_strand uint8, sub_pos int64, sub_base uint8) of the ids
-    [first, first + count).  In window orientation the alternative is the a-th of {A, C, G, T} without the column's reference symbol,
-    ascending; sub_base is that alternative on the '+' strand; a column that is not A/C/G/T gives 255."""
+def mutagenesis_ids_host(first, count, radius, model_type="snv"):
+    """(site, column, a) of the variant ids [first, first + count): v = (site * W + column) * 3 + a."""
+    return _ids(first, count, _window(radius, model_type)[1])
+
+
+def mutagenesis_rows_host(genome, pos, strand, radius, first, count, model_type="snv"):
+    """The numpy twin of ``mural_mutagenesis_rows`` (``.._window``): (row_pos int64, row_strand uint8, sub_pos int64, sub_base uint8) of
+    the ids [first, first + count).  In window orientation the alternative is the a-th of {A, C, G, T} without the column's reference
+    symbol, ascending; sub_base is that alternative on the '+' strand; a column that is not A/C/G/T gives 255."""
     codes = _codes(genome)
     pos, strand = np.asarray(pos, np.int64), (np.asarray(strand) != 0).astype(np.uint8)
-    W = 2 * radius + 1
+    W = _window(radius, model_type)[1]
     if first < 0 or count < 0 or first + count > len(pos) * W * 3:
         raise ValueError("mutagenesis_rows: ids [first, first + count) must lie in [0, n_sites * W * 3)")
-    site, j, a = mutagenesis_ids_host(first, count, radius)
-    sym, gp = _window_symbols_host(codes, pos, strand, radius)
+    site, j, a = _ids(first, count, W)
+    sym, gp = _window_symbols_host(codes, pos, strand, radius, model_type=model_type)
     ref = sym[site, j].astype(np.int64)
     alt = a + (a >= ref)
     neg = strand[site] != 0
@@ -98,14 +115,14 @@ def mutagenesis_rows_host(genome, pos, strand, radius, first, count):
 
 
 def mutagenesis_reduce_host(ref_logp, var_logp, ref_symbols, first, delta, logp_map=None):
-    """The numpy twin of ``mural_mutagenesis_reduce``: scatters var_logp (count, n_class) of the ids [first, first + count) into `delta`
+    """The numpy twin of ``mural_mutagenesis_reduce`` (``.._window``: any W >= 1): scatters var_logp (count, n_class) of the ids [first, first + count) into `delta`
     (n_sites, W, 4, n_class) float32 in place (and var_logp itself into `logp_map`).  Id a of an A/C/G/T column writes its alternative's
     entry, id a = 0 the reference base's (+0.0; ref_logp in the second map) too; in any other column id a writes NaN to entry a, id a = 2
     to entry 3 as well."""
     ref_logp, var_logp = np.asarray(ref_logp, np.float32), np.asarray(var_logp, np.float32)
     ref_symbols = np.asarray(ref_symbols, np.uint8)
     n, W = ref_symbols.shape
-    site, j, a = mutagenesis_ids_host(first, len(var_logp), (W - 1) // 2)
+    site, j, a = _ids(first, len(var_logp), W)
     ref = ref_symbols[site, j].astype(np.int64)
     plain = ref < 4
     alt = a + (a >= ref)
@@ -127,6 +144,13 @@ def mutagenesis_reduce_host(ref_logp, var_logp, ref_symbols, first, delta, logp_
     return delta
 
 
+def log_softmax_host(scores):
+    """The float64 twin of ``mural_scores_log_softmax``: s - (max + log sum exp(s - max)) per row."""
+    s = np.asarray(scores, np.float64)
+    mx = s.max(axis=1, keepdims=True)
+    return s - (mx + np.log(np.exp(s - mx).sum(axis=1, keepdims=True)))
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # device entry points
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -139,38 +163,64 @@ def _encode_subst_into(genome, pos, strand, sub_pos, sub_base, radius, local_rad
             None if cat_x is None else cat_x.data_ptr(), _lib.current_stream_ptr(genome.device)))
 
 
-def encode_subst_windows(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order):
+def _encode_subst_symbols_into(genome, pos, strand, sub_pos, sub_base, radius, indel, symbols):
+    g = genome.as_struct()
+    with torch.cuda.device(genome.device):
+        _lib.check(_lib.lib().mural_encode_subst_symbols(
+            C.byref(g), pos.data_ptr(), strand.data_ptr(), sub_pos.data_ptr(), sub_base.data_ptr(), pos.shape[0], int(radius), int(indel),
+            symbols.data_ptr(), _lib.current_stream_ptr(genome.device)))
+
+
+def encode_subst_windows(genome, pos, strand, sub_pos, sub_base, radius, local_radius=None, local_order=None, model_type="snv"):
     """``PackedGenome.encode_subst_windows``: (symbols uint8 (n, 2 * radius + 1), cat_x int64 (n, 2 * local_radius + 1 - (local_order - 1)))
     of one row per (site, substitution), bit for bit ``encode_symbols`` / ``encode_kmer`` on the genome with that base replaced.  `sub_pos`
-    is a '+'-strand position, `sub_base` a '+'-strand base 0..3 or 255 for none."""
+    is a '+'-strand position, `sub_base` a '+'-strand base 0..3 or 255 for none.  ``model_type="indel"``: (symbols uint8 (n, 2 * radius),
+    None) of the INDEL window; the local arguments are not read."""
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
     pos, strand = genome._prep(pos, strand)
     sub_pos = torch.as_tensor(sub_pos, dtype=torch.int64, device=genome.device).contiguous()
     sub_base = torch.as_tensor(sub_base, dtype=torch.uint8, device=genome.device).contiguous()
     if sub_pos.shape != pos.shape or sub_base.shape != pos.shape:
         raise ValueError("sub_pos and sub_base must be 1-D and as long as pos")
     n = pos.shape[0]
+    if model_type == "indel":
+        symbols = torch.empty((n, 2 * radius), dtype=torch.uint8, device=genome.device)
+        _encode_subst_symbols_into(genome, pos, strand, sub_pos, sub_base, radius, 1, symbols)
+        return symbols, None
+    if local_radius is None or local_order is None:
+        raise ValueError("encode_subst_windows: the SNV windows need local_radius and local_order")
     symbols = torch.empty((n, 2 * radius + 1), dtype=torch.uint8, device=genome.device)
     cat_x = torch.empty((n, 2 * local_radius + 1 - (local_order - 1)), dtype=torch.int64, device=genome.device)
     _encode_subst_into(genome, pos, strand, sub_pos, sub_base, radius, local_radius, local_order, symbols, cat_x)
     return symbols, cat_x
 
 
-def mutagenesis_rows(genome, pos, strand, radius, first, count):
-    """``mural_mutagenesis_rows`` on the device: (row_pos, row_strand, sub_pos, sub_base) of the variant ids [first, first + count)."""
+def mutagenesis_rows(genome, pos, strand, radius, first, count, model_type="snv"):
+    """``mural_mutagenesis_rows`` (``.._window`` for ``model_type="indel"``) on the device: (row_pos, row_strand, sub_pos, sub_base) of the
+    variant ids [first, first + count)."""
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
     pos, strand = genome._prep(pos, strand)
     dev = genome.device
     out = (torch.empty(count, dtype=torch.int64, device=dev), torch.empty(count, dtype=torch.uint8, device=dev),
            torch.empty(count, dtype=torch.int64, device=dev), torch.empty(count, dtype=torch.uint8, device=dev))
     g = genome.as_struct()
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mural_mutagenesis_rows(C.byref(g), pos.data_ptr(), strand.data_ptr(), pos.shape[0], int(radius), int(first),
-                                                    int(count), *[t.data_ptr() for t in out], _lib.current_stream_ptr(dev)))
+        if model_type == "indel":
+            _lib.check(_lib.lib().mural_mutagenesis_rows_window(C.byref(g), pos.data_ptr(), strand.data_ptr(), pos.shape[0], int(radius), 1,
+                                                               int(first), int(count), *[t.data_ptr() for t in out],
+                                                               _lib.current_stream_ptr(dev)))
+        else:
+            _lib.check(_lib.lib().mural_mutagenesis_rows(C.byref(g), pos.data_ptr(), strand.data_ptr(), pos.shape[0], int(radius), int(first),
+                                                        int(count), *[t.data_ptr() for t in out], _lib.current_stream_ptr(dev)))
     return out
 
 
 def mutagenesis_reduce(ref_logp, var_logp, ref_symbols, first, delta, logp_map=None):
     """``mural_mutagenesis_reduce`` on the device: var_logp (count, n_class) of the ids [first, first + count) into `delta` (n_sites, W, 4,
-    n_class) in place (and into `logp_map`).  Contiguous float32 / uint8 device tensors."""
+    n_class) in place (and into `logp_map`).  Contiguous float32 / uint8 device tensors.  An odd W is the SNV entry (W = 2 * radius + 1),
+    an even one ``mural_mutagenesis_reduce_window``: the same kernel."""
     n, W = ref_symbols.shape
     n_class = ref_logp.shape[1]
     tensors = [(ref_logp, torch.float32, (n, n_class)), (var_logp, torch.float32, (var_logp.shape[0], n_class)),
@@ -181,14 +231,51 @@ def mutagenesis_reduce(ref_logp, var_logp, ref_symbols, first, delta, logp_map=N
         _lib.require_cuda(t, "mutagenesis_reduce input")
         if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"mutagenesis_reduce: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
-    if W % 2 != 1:
-        raise ValueError("mutagenesis_reduce: ref_symbols must be (n_sites, 2 * radius + 1)")
+    if W < 1:
+        raise ValueError("mutagenesis_reduce: ref_symbols must be (n_sites, W) with W >= 1")
     dev = delta.device
     with torch.cuda.device(dev):
+        if W % 2 == 0:
+            _lib.check(_lib.lib().mural_mutagenesis_reduce_window(ref_logp.data_ptr(), var_logp.data_ptr(), ref_symbols.data_ptr(), n, W, n_class,
+                                                                 int(first), var_logp.shape[0], delta.data_ptr(),
+                                                                 None if logp_map is None else logp_map.data_ptr(),
+                                                                 _lib.current_stream_ptr(dev)))
+            return delta
         _lib.check(_lib.lib().mural_mutagenesis_reduce(ref_logp.data_ptr(), var_logp.data_ptr(), ref_symbols.data_ptr(), n, (W - 1) // 2,
                                                       n_class, int(first), var_logp.shape[0], delta.data_ptr(),
                                                       None if logp_map is None else logp_map.data_ptr(), _lib.current_stream_ptr(dev)))
     return delta
+
+
+def scores_log_softmax(scores):
+    """``mural_scores_log_softmax`` on the device: float32 (n, n_class) scores -> the log-probabilities of softmax(scores), a new tensor.
+    One thread per row: a row's bits do not depend on the rows it shares the call with."""
+    _lib.require_cuda(scores, "scores")
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[1] < 1 or not scores.is_contiguous():
+        raise ValueError(f"scores_log_softmax: expected a contiguous float32 (n, n_class) tensor, got {scores.dtype} {tuple(scores.shape)}")
+    out = torch.empty_like(scores)
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.lib().mural_scores_log_softmax(scores.data_ptr(), scores.shape[0], scores.shape[1], out.data_ptr(),
+                                                      _lib.current_stream_ptr(scores.device)))
+    return out
+
+
+def _is_indel(model):
+    from .model.model_indel import UNet_Small
+    return isinstance(model, UNet_Small)
+
+
+def _require_indel(model, radius):
+    """distal radius of a UNet_Small the symbols entry serves; RuntimeError that names the reason otherwise."""
+    if model.training:
+        raise RuntimeError("internal: the fused inference kernels serve eval mode only")
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError("mural_amd models run on a HIP device only: call model.to('cuda') first")
+    if radius is None:
+        radius = getattr(model, "distal_radius", None)
+    if radius is None or int(radius) < 1:
+        raise ValueError("mutagenesis of the INDEL model needs distal_radius >= 1 (UNet_Small does not carry its window length)")
+    return int(radius)
 
 
 def _require_model(model, local_radius, local_order):
@@ -230,18 +317,19 @@ class MutagenesisMap:
     symbol is not A/C/G/T; ``ref_logp`` (n, n_class); ``ref_symbols`` uint8 (n, W), strand-oriented MURAL_SYM_* codes; ``var_logp`` (the
     variants' log-probabilities in the layout of ``delta``, ref_logp at the reference base) when asked for, else None."""
 
-    __slots__ = ("delta", "ref_logp", "ref_symbols", "var_logp", "pos", "strand", "radius")
+    __slots__ = ("delta", "ref_logp", "ref_symbols", "var_logp", "pos", "strand", "radius", "model_type")
 
-    def __init__(self, delta, ref_logp, ref_symbols, var_logp, pos, strand, radius):
+    def __init__(self, delta, ref_logp, ref_symbols, var_logp, pos, strand, radius, model_type="snv"):
         self.delta, self.ref_logp, self.ref_symbols, self.var_logp = delta, ref_logp, ref_symbols, var_logp
-        self.pos, self.strand, self.radius = pos, strand, radius
+        self.pos, self.strand, self.radius, self.model_type = pos, strand, radius, model_type
 
     def genomic_positions(self):
-        """int64 (n, W): the '+'-strand position of every window column (pos + (j - R) on '+', pos - (j - R) on '-'; may lie outside
-        the record, where the column is N)."""
-        off = torch.arange(-self.radius, self.radius + 1, dtype=torch.int64, device=self.pos.device)
-        sign = 1 - 2 * self.strand.to(torch.int64)
-        return self.pos[:, None] + sign[:, None] * off[None, :]
+        """int64 (n, W): the '+'-strand position of every window column (SNV: pos + (j - R) on '+', pos - (j - R) on '-'; INDEL, W = 2 R:
+        pos - R + 1 + j on '+', pos + R - j on '-'; may lie outside the record, where the column is N)."""
+        off0, W = _window(self.radius, self.model_type)
+        j = torch.arange(W, dtype=torch.int64, device=self.pos.device)
+        neg = self.strand.to(torch.bool)
+        return self.pos[:, None] + off0 + torch.where(neg[:, None], W - 1 - j[None, :], j[None, :])
 
     def importance(self):
         """float32 (n, W): the largest |delta| over alternatives and classes; NaN where the column has no substitutions."""
@@ -252,22 +340,36 @@ class MutagenesisMap:
 
 
 def saturation_mutagenesis(model, genome, pos, strand, local_radius=None, local_order=3, chunk_windows=1 << 17, return_logp=False,
-                           timings=None):
+                           timings=None, distal_radius=None):
     """The saturation-mutagenesis map of the sites `pos` / `strand` (device int64 / uint8, 1 = '-') of a ``PackedGenome``: a
     ``MutagenesisMap``.  Every chunk of `chunk_windows` variant ids runs enumerate -> encode -> ``forward_symbols`` -> reduce; the row
     buffers are allocated once.  The map is bit-identical for every `chunk_windows`.  Serves Network1 / Network2 in eval mode whose
     ``symbols_entry_ok()``; anything else raises RuntimeError with the reason.  `timings`: an optional dict that receives the device
-    time of the chunks' three phases from HIP events (``rows_encode_ms``, ``forward_ms``, ``reduce_ms``; it synchronises at the end)."""
-    R, r = _require_model(model, local_radius, local_order)
+    time of the chunks' three phases from HIP events (``rows_encode_ms``, ``forward_ms``, ``reduce_ms``; it synchronises at the end).
+
+    A ``UNet_Small`` in eval mode gives the map of the INDEL window: `distal_radius` R is required (or ``model.distal_radius``), W = 2 R,
+    `local_radius` / `local_order` are ignored, and the log-probabilities are the log-softmax of ``forward_symbols``' scores (counted in
+    ``forward_ms``).  The INDEL forward picks kernels by the size of a call, so its map is reproducible for one `chunk_windows` and
+    agrees across values of it within the forward's own accuracy, not bit for bit."""
+    indel = _is_indel(model)
+    if indel:
+        R, r = _require_indel(model, distal_radius), 0
+    else:
+        R, r = _require_model(model, local_radius, local_order)
     pos, strand = _sites(genome, model, pos, strand)
     if chunk_windows < 1:
         raise ValueError("chunk_windows must be >= 1")
-    dev, n, W, n_class = pos.device, pos.shape[0], 2 * R + 1, model.n_class
-    with_cat = model.model_no == 2
+    model_type = "indel" if indel else "snv"
+    dev, n, W, n_class = pos.device, pos.shape[0], _window(R, model_type)[1], model.n_class
+    with_cat = not indel and model.model_no == 2
+
+    def forward(cat, sym):
+        return scores_log_softmax(model.forward_symbols(sym)) if indel else model.forward_symbols(cat, sym)
+
     with torch.no_grad(), torch.cuda.device(dev):
-        ref_symbols = genome.encode_symbols(pos, strand, R).sym
+        ref_symbols = genome.encode_symbols(pos, strand, R, model_type).sym
         ref_cat = genome.encode_kmer(pos, strand, r, local_order) if with_cat else None
-        ref_logp = model.forward_symbols(ref_cat, ref_symbols) if n else torch.empty((0, n_class), dtype=torch.float32, device=dev)
+        ref_logp = forward(ref_cat, ref_symbols) if n else torch.empty((0, n_class), dtype=torch.float32, device=dev)
         # every element is written by the reduce (one writer each): no fill
         delta = torch.empty((n, W, 4, n_class), dtype=torch.float32, device=dev)
         logp_map = torch.empty_like(delta) if return_logp else None
@@ -290,42 +392,64 @@ def saturation_mutagenesis(model, genome, pos, strand, local_radius=None, local_
         for first in range(0, total, cap):
             m = min(cap, total - first)
             mark()
-            _lib.check(lib.mural_mutagenesis_rows(C.byref(g), pos.data_ptr(), strand.data_ptr(), n, R, first, m, row_pos.data_ptr(),
-                                                  row_strand.data_ptr(), sub_pos.data_ptr(), sub_base.data_ptr(), stream))
-            _lib.check(lib.mural_encode_subst_windows(C.byref(g), row_pos.data_ptr(), row_strand.data_ptr(), sub_pos.data_ptr(),
-                                                      sub_base.data_ptr(), m, R, r, int(local_order), symbols.data_ptr(),
-                                                      cat_x.data_ptr() if with_cat else None, stream))
+            _lib.check(lib.mural_mutagenesis_rows_window(C.byref(g), pos.data_ptr(), strand.data_ptr(), n, R, int(indel), first, m,
+                                                         row_pos.data_ptr(), row_strand.data_ptr(), sub_pos.data_ptr(), sub_base.data_ptr(),
+                                                         stream))
+            if indel:
+                _lib.check(lib.mural_encode_subst_symbols(C.byref(g), row_pos.data_ptr(), row_strand.data_ptr(), sub_pos.data_ptr(),
+                                                          sub_base.data_ptr(), m, R, 1, symbols.data_ptr(), stream))
+            else:
+                _lib.check(lib.mural_encode_subst_windows(C.byref(g), row_pos.data_ptr(), row_strand.data_ptr(), sub_pos.data_ptr(),
+                                                          sub_base.data_ptr(), m, R, r, int(local_order), symbols.data_ptr(),
+                                                          cat_x.data_ptr() if with_cat else None, stream))
             mark()
-            var = model.forward_symbols(cat_x[:m] if with_cat else None, symbols[:m])
+            var = forward(cat_x[:m] if with_cat else None, symbols[:m])
             mark()
-            _lib.check(lib.mural_mutagenesis_reduce(ref_logp.data_ptr(), var.data_ptr(), ref_symbols.data_ptr(), n, R, n_class, first, m,
-                                                    delta.data_ptr(), logp_map.data_ptr() if return_logp else None, stream))
+            _lib.check(lib.mural_mutagenesis_reduce_window(ref_logp.data_ptr(), var.data_ptr(), ref_symbols.data_ptr(), n, W, n_class, first,
+                                                           m, delta.data_ptr(), logp_map.data_ptr() if return_logp else None, stream))
             mark()
         if timings is not None:
             torch.cuda.synchronize(dev)
             for k, name in enumerate(("rows_encode_ms", "forward_ms", "reduce_ms")):
                 timings[name] = timings.get(name, 0.0) + sum(marks[c + k].elapsed_time(marks[c + k + 1]) for c in range(0, len(marks), 4))
-    return MutagenesisMap(delta, ref_logp, ref_symbols, logp_map, pos, strand, R)
+    return MutagenesisMap(delta, ref_logp, ref_symbols, logp_map, pos, strand, R, model_type)
 
 
-def variant_footprint(model, genome, var_pos, var_base, strand, local_radius=None, local_order=3, chunk_windows=1 << 17):
+def footprint_offsets(radius, model_type="snv", device=None):
+    """int64 offsets d of ``variant_footprint``'s second axis: [-R, R] for the SNV models, [-R, R - 1] for the INDEL model."""
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
+    return torch.arange(-radius, radius + (1 if model_type == "snv" else 0), dtype=torch.int64, device=device)
+
+
+def variant_footprint(model, genome, var_pos, var_base, strand, local_radius=None, local_order=3, chunk_windows=1 << 17,
+                      distal_radius=None):
     """What each variant does to the sites around it: for variant i (`var_pos` '+'-strand position, `var_base` '+'-strand base 0..3) the
     change in log-probability of every neighbouring site var_pos + d, d in [-R, R], read on `strand` (uint8 per variant, 1 = '-'), as
     ``(delta float32 (m, W, n_class), focal uint8 (m, W))``: entry [i, d + R].  d = 0 and neighbours outside the chromosome are NaN.
     `focal` is each neighbour's reference focal symbol on `strand` (MURAL_SYM_*; N outside the chromosome), for masking to the model's
     site class.  Rows go through the same encoder and ``forward_symbols`` as ``saturation_mutagenesis``: entry (i, d) equals, bit for
-    bit, that map's entry of site var_pos + d at the column and alternative that name the same genomic substitution."""
-    R, r = _require_model(model, local_radius, local_order)
+    bit, that map's entry of site var_pos + d at the column and alternative that name the same genomic substitution.
+
+    A ``UNet_Small`` (`distal_radius` as in ``saturation_mutagenesis``): the neighbours are the sites whose INDEL window holds the variant,
+    d in [-R, R - 1], entry [i, d + R] of ``(delta (m, 2 R, n_class), focal (m, 2 R))``.  d = 0 is a live entry (a substitution at the
+    focal base does not remove an INDEL site); only neighbours outside the chromosome are NaN.  Entries equal the map's where both ran
+    calls of the same size, and agree within the forward's accuracy otherwise.  ``footprint_offsets`` gives d."""
+    indel = _is_indel(model)
+    if indel:
+        R, r = _require_indel(model, distal_radius), 0
+    else:
+        R, r = _require_model(model, local_radius, local_order)
     var_pos, strand = _sites(genome, model, var_pos, strand)
     var_base = _lib.require_cuda(torch.as_tensor(var_base), "var_base").to(torch.uint8).contiguous()
     if var_base.shape != var_pos.shape:
         raise ValueError("var_base must be as long as var_pos")
     if chunk_windows < 1:
         raise ValueError("chunk_windows must be >= 1")
-    dev, m, W, n_class = var_pos.device, var_pos.shape[0], 2 * R + 1, model.n_class
-    with_cat = model.model_no == 2
+    dev, m, W, n_class = var_pos.device, var_pos.shape[0], 2 * R if indel else 2 * R + 1, model.n_class
+    with_cat = not indel and model.model_no == 2
     with torch.no_grad(), torch.cuda.device(dev):
-        d = torch.arange(-R, R + 1, dtype=torch.int64, device=dev)
+        d = footprint_offsets(R, "indel" if indel else "snv", dev)
         row_pos = (var_pos[:, None] + d[None, :]).reshape(-1).contiguous()
         row_strand = strand[:, None].expand(m, W).reshape(-1).contiguous()
         sub_pos = var_pos[:, None].expand(m, W).reshape(-1).contiguous()
@@ -342,10 +466,20 @@ def variant_footprint(model, genome, var_pos, var_base, strand, local_radius=Non
             rows = slice(c0, c0 + k)
             logp = []
             for base in (sub_base, none):
-                _encode_subst_into(genome, row_pos[rows], row_strand[rows], sub_pos[rows], base[rows], R, r, local_order, symbols, cat_x)
-                logp.append(model.forward_symbols(cat_x[:k] if with_cat else None, symbols[:k]))
+                if indel:
+                    _encode_subst_symbols_into(genome, row_pos[rows], row_strand[rows], sub_pos[rows], base[rows], R, 1, symbols)
+                    logp.append(scores_log_softmax(model.forward_symbols(symbols[:k])))
+                else:
+                    _encode_subst_into(genome, row_pos[rows], row_strand[rows], sub_pos[rows], base[rows], R, r, local_order, symbols, cat_x)
+                    logp.append(model.forward_symbols(cat_x[:k] if with_cat else None, symbols[:k]))
             delta[rows] = logp[0] - logp[1]
-            focal[rows] = symbols[:k, R]                      # (the unchanged windows were encoded last)
-        dead = (row_pos < 0) | (row_pos >= genome.length) | (row_pos == sub_pos)
+            # (the unchanged windows were encoded last; the INDEL window holds the site in column R - 1 on '+', R on '-')
+            if indel:
+                focal[rows] = symbols[:k].gather(1, (R - 1 + row_strand[rows].to(torch.int64))[:, None])[:, 0]
+            else:
+                focal[rows] = symbols[:k, R]
+        dead = (row_pos < 0) | (row_pos >= genome.length)
+        if not indel:
+            dead |= row_pos == sub_pos
         delta = torch.where(dead[:, None], torch.full_like(delta, float("nan")), delta)
     return delta.reshape(m, W, n_class), focal.reshape(m, W)

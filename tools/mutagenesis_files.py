@@ -1,7 +1,7 @@
-"""Saturation-mutagenesis table of BED sites (mural_amd.mutagenesis.saturation_mutagenesis):
+"""Saturation-mutagenesis table of BED sites (mural_amd.mutagenesis.saturation_mutagenesis; DESIGN.md sections 3.27, 3.28):
 
   python tools/mutagenesis_files.py --ref_genome FASTA --sites BED --model_path MODEL [--model_config_path CONFIG] --out PREFIX
-                                    [--top K] [--batch_sites N]
+                                    [--model_type snv|indel] [--top K] [--batch_sites N]
 
 Writes PREFIX.mutagenesis.tsv, one row per (site, window column, alternative base):
   chrom  site_start  strand  offset  genomic_pos  ref  alt  delta_logp1 .. delta_logp{n_class}
@@ -9,7 +9,9 @@ offset is the column's distance from the site in window orientation (negative = 
 0-based '+'-strand position of that column, ref / alt the base there and its replacement ON THE GENOMIC '+' STRAND, delta_logp the change
 of the model's log-probabilities (%.4g).  Columns that are not A/C/G/T in the genome (N, IUPAC codes, beyond the chromosome ends) have no
 rows.  --top K keeps, per site, the K columns of largest importance (max |delta| over alternatives and classes).  --model_path /
---model_config_path / --ref_genome are the reference's flag names (MuRaL/commands/predict.py); the config defaults to MODEL.config.pkl."""
+--model_config_path / --ref_genome are the reference's flag names (MuRaL/commands/predict.py); the config defaults to MODEL.config.pkl.
+--model_type indel: a UNet_Small checkpoint; the window is [site - R + 1, site + R] (R = the config's distal_radius), so on '+' the
+offsets run from -(R - 1) to R and on '-' from -R to R - 1; the same table otherwise."""
 import argparse
 import os
 import sys
@@ -38,6 +40,7 @@ def write_rows(fh, chrom, res, top=None):
     rows = 0
     for s in range(len(pos)):
         neg = bool(strand[s])
+        site_col = R if res.model_type == "snv" or neg else R - 1      # the window column that holds the site itself
         cols = np.nonzero(sym[s] < 4)[0]
         if top is not None:
             keep = cols[np.argsort(-imp[s, cols], kind="stable")[:top]]
@@ -50,7 +53,7 @@ def write_rows(fh, chrom, res, top=None):
                     continue
                 alt = "ACGT"[3 - b if neg else b]
                 vals = "\t".join("%.4g" % v for v in delta[s, j, b])
-                fh.write(f"{chrom}\t{pos[s]}\t{'-' if neg else '+'}\t{j - R}\t{gpos[s, j]}\t{ref}\t{alt}\t{vals}\n")
+                fh.write(f"{chrom}\t{pos[s]}\t{'-' if neg else '+'}\t{j - site_col}\t{gpos[s, j]}\t{ref}\t{alt}\t{vals}\n")
                 rows += 1
     return rows
 
@@ -62,12 +65,13 @@ def main(argv=None):
     ap.add_argument("--model_path", required=True)
     ap.add_argument("--model_config_path", default=None)
     ap.add_argument("--out", required=True, help="prefix of PREFIX.mutagenesis.tsv")
+    ap.add_argument("--model_type", default="snv", choices=["snv", "indel"])
     ap.add_argument("--top", type=int, default=None)
     ap.add_argument("--batch_sites", type=int, default=64, help="sites per map held on the device")
     args = ap.parse_args(argv)
     if args.top is not None and args.top < 1:
         raise SystemExit("--top must be positive")
-    model, cfg = load_model(args.model_path, args.model_config_path, model_type="snv")
+    model, cfg = load_model(args.model_path, args.model_config_path, model_type=args.model_type)
     bed = read_bed(args.sites)
     out, rows = output_name(args.out), 0
     with open(out, "w") as fh:
@@ -82,7 +86,10 @@ def main(argv=None):
                 part = sel[b0:b0 + args.batch_sites]
                 pos = torch.from_numpy(bed.start[part]).cuda()
                 strand = torch.from_numpy(bed.strand[part]).cuda()
-                res = saturation_mutagenesis(model, genome, pos, strand, cfg["local_radius"], cfg.get("local_order", 3))
+                if args.model_type == "indel":
+                    res = saturation_mutagenesis(model, genome, pos, strand, distal_radius=cfg["distal_radius"])
+                else:
+                    res = saturation_mutagenesis(model, genome, pos, strand, cfg["local_radius"], cfg.get("local_order", 3))
                 rows += write_rows(fh, chrom, res, args.top)
     print(f"{len(bed.start)} sites, {rows} rows -> {out}")
 
