@@ -136,6 +136,38 @@ int mural_mutagenesis_rows_window(const MuralGenome* g, const int64_t* pos, cons
 int mural_mutagenesis_reduce_window(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites, int32_t W,
                                     int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map, void* stream);
 int mural_scores_log_softmax(const float* scores, int64_t n, int32_t n_class, float* out, void* stream);
+/* Alleles that change the sequence's length.  Allele v of the table replaces the '+'-strand bases
+ * [a_pos[v], a_pos[v] + a_ref_len[v]) by a_alt_len[v] plain bases: base i (0..3 = A C G T) in bits 2i, 2i+1 of a_alt[v].  ref_len = 0 is
+ * an insertion before a_pos (a_pos = g->length appends), alt_len = 0 a deletion.  An allele is LIVE iff 0 <= a_pos, 0 <= a_ref_len,
+ * a_pos + a_ref_len <= g->length and 0 <= a_alt_len <= 32; any other reads the genome as it is.  Position q of the alternate haplotype
+ * (length g->length + alt_len - ref_len) is genome[q] for q < p, alt[q - p] for p <= q < p + alt_len, genome[q - (alt_len - ref_len)]
+ * after that and N outside it.  The inserted bases are plain bases (nmask and the amb_pos side table are not consulted for them); every
+ * other column keeps the N / IUPAC rules of the plain encoders.
+ *
+ * mural_encode_allele_windows: one row per (site, allele).
+ *   pos / strand         : dev int64 / uint8 [n], the row's site IN ALTERNATE-HAPLOTYPE COORDINATES (strand 1 = '-')
+ *   allele               : dev int64 [n], an index into the table; -1 or any value outside [0, n_alleles): no allele
+ *   a_pos, a_ref_len, a_alt_len : dev int64 [n_alleles];   a_alt : dev uint64 [n_alleles]
+ *   symbols              : dev uint8 [n][W] of window_geometry(radius, indel), 4-byte aligned, or NULL
+ *   cat_x                : dev int64 [n][2*local_radius+1-(local_order-1)] (the SNV local window), or NULL
+ * Row i is, bit for bit, mural_encode_symbols(.., radius, indel) / mural_encode_kmer(.., local_radius, local_order, indel=0) of (pos[i],
+ * strand[i]) on the alternate haplotype.  The kernel of mural_encode_subst_windows with another base reader: one launch, n == 0 launches
+ * nothing, the genome buffers are only read.
+ *
+ * mural_allele_rows: the sites an allele can reach, i.e. all sites outside the replaced span whose window can differ between the two
+ * haplotypes.  With (off0, W) the window of (radius, indel), allele v has W - 1 slots; slot c stands for e = c - (off0 + W - 1) (indel =
+ * 0: e in [-R, R - 1]; indel = 1: [-R, R - 2]).  e < 0: ref_pos = alt_pos = p + e;  e >= 0: ref_pos = p + ref_len + e, alt_pos = ref_pos +
+ * alt_len - ref_len.  Row id = v*(W - 1) + c; the call writes ids [first, first+count) to index id - first of
+ *   ref_pos / alt_pos    : dev int64 [count], the site on the genome / on the alternate haplotype (either may lie outside its record)
+ *   row_strand           : dev uint8 [count], strand[v] (strand: dev uint8 [n_alleles], one per allele)
+ *   row_allele           : dev int64 [count], v, or -1 for an allele that is not live (whose rows are those of ref_len = alt_len = 0) */
+int mural_encode_allele_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* allele, int64_t n,
+                                const int64_t* a_pos, const int64_t* a_ref_len, const int64_t* a_alt_len, const uint64_t* a_alt,
+                                int64_t n_alleles, int32_t radius, int32_t indel, int32_t local_radius, int32_t local_order,
+                                uint8_t* symbols, int64_t* cat_x, void* stream);
+int mural_allele_rows(const MuralGenome* g, const int64_t* a_pos, const int64_t* a_ref_len, const int64_t* a_alt_len, int64_t n_alleles,
+                      const uint8_t* strand, int32_t radius, int32_t indel, int64_t first, int64_t count, int64_t* ref_pos,
+                      int64_t* alt_pos, uint8_t* row_strand, int64_t* row_allele, void* stream);
 
 /* One training batch gathered and encoded from ROW INDICES in one launch (csrc/train_batch.hip): the rows of a batch may lie on several
  * chromosomes, which the three encoders above cannot take in one call.

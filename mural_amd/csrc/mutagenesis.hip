@@ -1,5 +1,6 @@
 // In-silico saturation mutagenesis around the SNV and INDEL forwards: the window "as if one base were different" (one row per (site, substitution)),
-// the enumerator of a window's 3 * W substitutions, and the scatter of the re-predicted log-probabilities into the map.
+// the enumerator of a window's 3 * W substitutions, and the scatter of the re-predicted log-probabilities into the map; and the window on
+// the alternate haplotype of an insertion, deletion or multi-base allele with the enumerator of the sites it reaches (section 3.29).
 // Window, strand and k-mer-id rules are encode.hip's, through the same column helpers (encode_window.h; reference:
 // MuRaL/data/preprocessing.py:636-723, 756-816; windows :559-567: SNV [pos - R, pos + R], INDEL [pos - R + 1, pos + R]).  The forward in
 // between is mural_snv_forward_symbols or mural_indel_forward_symbols; for the latter mural_scores_log_softmax turns its Softplus
@@ -9,20 +10,49 @@
 
 namespace mural {
 
-// the row's substitution as the column helpers read it: none for sub_base > 3 (255 = "no substitution") or a position outside the record
-__device__ __forceinline__ OneSubst row_subst(const MuralGenome& g, const int64_t* __restrict__ sub_pos, const uint8_t* __restrict__ sub_base,
-                                              int64_t row) {
-  const int64_t p = sub_pos[row];
-  const uint32_t b = sub_base[row];
-  return OneSubst{p, b & 3u, b < 4u && p >= 0 && p < g.length};
+// The rows' base readers.  A row source is a small struct of table pointers whose operator() builds row i's reader; the window kernel
+// below is written once over it.
+
+// one substitution per row: none for sub_base > 3 (255 = "no substitution") or a position outside the record
+struct SubstRows {
+  const int64_t* __restrict__ sub_pos;
+  const uint8_t* __restrict__ sub_base;
+  __device__ __forceinline__ OneSubst operator()(const MuralGenome& g, int64_t row) const {
+    const int64_t p = sub_pos[row];
+    const uint32_t b = sub_base[row];
+    return OneSubst{p, b & 3u, b < 4u && p >= 0 && p < g.length};
+  }
+};
+
+// live: 0 <= p, 0 <= d, p + d <= length, 0 <= k <= 32 (written so that nothing overflows)
+__device__ __forceinline__ bool allele_live(int64_t length, int64_t p, int64_t d, int64_t k) {
+  return p >= 0 && p <= length && d >= 0 && d <= length - p && k >= 0 && k <= 32;
 }
+
+// one index into the allele table per row: -1 or any index outside [0, n_alleles), or an allele that is not live, reads the genome as it is
+struct AlleleRows {
+  const int64_t* __restrict__ allele;
+  const int64_t* __restrict__ a_pos;
+  const int64_t* __restrict__ a_ref_len;
+  const int64_t* __restrict__ a_alt_len;
+  const uint64_t* __restrict__ a_alt;
+  int64_t n_alleles;
+  __device__ __forceinline__ AlleleEdit operator()(const MuralGenome& g, int64_t row) const {
+    const int64_t v = allele[row];
+    if (v < 0 || v >= n_alleles) return AlleleEdit{0, 0, 0, 0ull, false};
+    const int64_t p = a_pos[v], d = a_ref_len[v], k = a_alt_len[v];
+    if (!allele_live(g.length, p, d, k)) return AlleleEdit{0, 0, 0, 0ull, false};
+    return AlleleEdit{p, k, k - d, a_alt[v], true};
+  }
+};
 
 // One launch for both outputs.  Units [0, sym_groups): 4 consecutive bytes of the flattened (row, column) index of `symbols` (one aligned
 // 4-byte store where the group lies in one row, as encode_symbols_kernel does); units [sym_groups, sym_groups + n * ncol): one k-mer id.
-__global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
-                                                            const int64_t* __restrict__ sub_pos, const uint8_t* __restrict__ sub_base, int64_t n,
-                                                            int W, int off, int lwidth, int lradius, int order, int ncol,
-                                                            int64_t sym_groups, uint8_t* __restrict__ symbols, int64_t* __restrict__ cat_x) {
+// pos[] is in the coordinates of the rows' readers: the genome's for SubstRows, the alternate haplotype's for AlleleRows.
+template <class Rows>
+__global__ __launch_bounds__(256) void reader_windows_kernel(MuralGenome g, const int64_t* __restrict__ pos, const uint8_t* __restrict__ strand,
+                                                             Rows rows, int64_t n, int W, int off, int lwidth, int lradius, int order, int ncol,
+                                                             int64_t sym_groups, uint8_t* __restrict__ symbols, int64_t* __restrict__ cat_x) {
   const int64_t total_sym = symbols ? n * W : 0;
   const int64_t units = sym_groups + (cat_x ? n * ncol : 0);
   for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
@@ -33,7 +63,7 @@ __global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const
       if (j + 3 < W) {
         const int64_t ws = pos[row] + off;
         const bool neg = strand[row] != 0;
-        const OneSubst sub = row_subst(g, sub_pos, sub_base, row);
+        const auto sub = rows(g, row);
         uint32_t packed = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) packed |= window_symbol(g, ws, W, neg, j + e, sub) << (8 * e);
@@ -43,15 +73,40 @@ __global__ __launch_bounds__(256) void subst_windows_kernel(MuralGenome g, const
           const int64_t i = i0 + e;
           const int64_t r = i / W;
           const int jj = (int)(i - r * W);
-          symbols[i] = (uint8_t)window_symbol(g, pos[r] + off, W, strand[r] != 0, jj, row_subst(g, sub_pos, sub_base, r));
+          symbols[i] = (uint8_t)window_symbol(g, pos[r] + off, W, strand[r] != 0, jj, rows(g, r));
         }
       }
     } else {
       const int64_t i = u - sym_groups;
       const int64_t row = i / ncol;
       const int col = (int)(i - row * ncol);
-      cat_x[i] = window_kmer_id(g, pos[row] - lradius, lwidth, strand[row] != 0, col, order, row_subst(g, sub_pos, sub_base, row));
+      cat_x[i] = window_kmer_id(g, pos[row] - lradius, lwidth, strand[row] != 0, col, order, rows(g, row));
     }
+  }
+}
+
+// The sites an allele can reach.  Row id = v * (W - 1) + c: slot c of allele v is the site at e = c - (off + W - 1) (SNV: e in [-R, R - 1];
+// INDEL: [-R, R - 2]); e < 0 lies left of the allele (ref_pos = alt_pos = p + e), e >= 0 right of the replaced span (ref_pos = p + d + e,
+// alt_pos = ref_pos + k - d).  An allele that is not live enumerates as d = k = 0 around its p, with row_allele = -1.  (Sums of table
+// values wrap instead of overflowing: such rows are dead anyway.)
+__global__ __launch_bounds__(256) void allele_rows_kernel(int64_t length, const int64_t* __restrict__ a_pos, const int64_t* __restrict__ a_ref_len,
+                                                          const int64_t* __restrict__ a_alt_len, const uint8_t* __restrict__ strand, int slots,
+                                                          int e0, int64_t first, int64_t count, int64_t* __restrict__ ref_pos,
+                                                          int64_t* __restrict__ alt_pos, uint8_t* __restrict__ row_strand,
+                                                          int64_t* __restrict__ row_allele) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t id = first + i;
+    const int64_t v = id / slots;
+    const int64_t e = (int64_t)(id - v * slots) - e0;
+    const int64_t p = a_pos[v];
+    int64_t d = a_ref_len[v], k = a_alt_len[v];
+    const bool live = allele_live(length, p, d, k);
+    if (!live) d = k = 0;
+    const uint64_t rp = (uint64_t)p + (uint64_t)e + (e < 0 ? 0ull : (uint64_t)d);
+    ref_pos[i] = (int64_t)rp;
+    alt_pos[i] = (int64_t)(e < 0 ? rp : rp + (uint64_t)(k - d));
+    row_strand[i] = strand[v] != 0 ? 1 : 0;
+    row_allele[i] = live ? v : -1;
   }
 }
 
@@ -150,10 +205,11 @@ static int require_genome(const MuralGenome* g) {
   return MURAL_OK;
 }
 
-// symbols (window of `radius` / `indel`) and / or cat_x (the SNV local window) of the rows
-static int encode_subst(const char* who, const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
-                        const uint8_t* sub_base, int64_t n, int32_t radius, int32_t indel, int32_t local_radius, int32_t local_order,
-                        uint8_t* symbols, int64_t* cat_x, void* stream) {
+// symbols (window of `radius` / `indel`) and / or cat_x (the SNV local window) of the rows, read through the rows' readers
+template <class Rows>
+static int encode_rows(const char* who, const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const Rows& rows, bool rows_ok,
+                       int64_t n, int32_t radius, int32_t indel, int32_t local_radius, int32_t local_order, uint8_t* symbols, int64_t* cat_x,
+                       void* stream) {
   if (int rc = require_genome(g)) return rc;
   MURAL_REQUIRE(n >= 0, "%s: n must be >= 0", who);
   int off = 0, W = 0, loff = 0, lwidth = 0, ncol = 0;
@@ -168,14 +224,21 @@ static int encode_subst(const char* who, const MuralGenome* g, const int64_t* po
     MURAL_REQUIRE(ncol >= 1, "window too short for order %d", local_order);
   }
   if (n == 0 || (!symbols && !cat_x)) return MURAL_OK;
-  MURAL_REQUIRE(pos && strand && sub_pos && sub_base, "pos/strand/sub_pos/sub_base must not be NULL");
+  MURAL_REQUIRE(pos && strand && rows_ok, "%s: the row arrays must not be NULL", who);
   MURAL_REQUIRE(n <= INT64_MAX / 4 / (W > ncol ? W : ncol), "%s: n out of range", who);
   const int64_t sym_groups = symbols ? (n * W + 3) / 4 : 0;
   const int64_t units = sym_groups + (cat_x ? n * ncol : 0);
-  hipLaunchKernelGGL(subst_windows_kernel, dim3(grid_for(units, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, sub_pos,
-                     sub_base, n, W, off, lwidth, (int)local_radius, (int)local_order, ncol, sym_groups, symbols, cat_x);
+  hipLaunchKernelGGL(reader_windows_kernel<Rows>, dim3(grid_for(units, 256, 16384)), dim3(256), 0, (hipStream_t)stream, *g, pos, strand, rows,
+                     n, W, off, lwidth, (int)local_radius, (int)local_order, ncol, sym_groups, symbols, cat_x);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
+}
+
+static int encode_subst(const char* who, const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
+                        const uint8_t* sub_base, int64_t n, int32_t radius, int32_t indel, int32_t local_radius, int32_t local_order,
+                        uint8_t* symbols, int64_t* cat_x, void* stream) {
+  return encode_rows(who, g, pos, strand, SubstRows{sub_pos, sub_base}, sub_pos && sub_base, n, radius, indel, local_radius, local_order,
+                     symbols, cat_x, stream);
 }
 
 extern "C" int mural_encode_subst_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* sub_pos,
@@ -242,6 +305,35 @@ extern "C" int mural_scores_log_softmax(const float* scores, int64_t n, int32_t 
   if (n == 0) return MURAL_OK;
   MURAL_REQUIRE(scores && out, "scores_log_softmax: pointers must not be NULL");
   hipLaunchKernelGGL(scores_log_softmax_kernel, dim3(grid_for(n, 256, 16384)), dim3(256), 0, (hipStream_t)stream, scores, n, (int)n_class, out);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
+extern "C" int mural_encode_allele_windows(const MuralGenome* g, const int64_t* pos, const uint8_t* strand, const int64_t* allele, int64_t n,
+                                           const int64_t* a_pos, const int64_t* a_ref_len, const int64_t* a_alt_len, const uint64_t* a_alt,
+                                           int64_t n_alleles, int32_t radius, int32_t indel, int32_t local_radius, int32_t local_order,
+                                           uint8_t* symbols, int64_t* cat_x, void* stream) {
+  MURAL_REQUIRE(n_alleles >= 0, "encode_allele_windows: n_alleles must be >= 0");
+  const bool tables = n_alleles == 0 || (a_pos && a_ref_len && a_alt_len && a_alt);
+  return encode_rows("encode_allele_windows", g, pos, strand, AlleleRows{allele, a_pos, a_ref_len, a_alt_len, a_alt, n_alleles},
+                     allele && tables, n, radius, indel, local_radius, local_order, symbols, cat_x, stream);
+}
+
+extern "C" int mural_allele_rows(const MuralGenome* g, const int64_t* a_pos, const int64_t* a_ref_len, const int64_t* a_alt_len,
+                                 int64_t n_alleles, const uint8_t* strand, int32_t radius, int32_t indel, int64_t first, int64_t count,
+                                 int64_t* ref_pos, int64_t* alt_pos, uint8_t* row_strand, int64_t* row_allele, void* stream) {
+  if (int rc = require_genome(g)) return rc;
+  int off, W;
+  if (int rc = window_geometry(radius, indel, &off, &W)) return rc;
+  const int slots = W - 1;
+  MURAL_REQUIRE(n_alleles >= 0 && n_alleles <= INT64_MAX / slots, "allele_rows: n_alleles out of range");
+  MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_alleles * slots - count,
+                "allele_rows: ids [first, first + count) must lie in [0, n_alleles * (W - 1))");
+  if (count == 0) return MURAL_OK;
+  MURAL_REQUIRE(a_pos && a_ref_len && a_alt_len && strand && ref_pos && alt_pos && row_strand && row_allele,
+                "allele_rows: pointers must not be NULL");
+  hipLaunchKernelGGL(allele_rows_kernel, dim3(grid_for(count, 256, 16384)), dim3(256), 0, (hipStream_t)stream, g->length, a_pos, a_ref_len,
+                     a_alt_len, strand, slots, off + W - 1, first, count, ref_pos, alt_pos, row_strand, row_allele);
   MURAL_HIP_CHECK(hipGetLastError());
   return MURAL_OK;
 }

@@ -265,6 +265,15 @@ class PackedGenome:
         return encode_subst_windows(self, pos, strand, sub_pos, sub_base, int(radius), None if local_radius is None else int(local_radius),
                                     None if local_order is None else int(local_order), model_type)
 
+    def encode_allele_windows(self, pos, strand, allele, alleles, radius, local_radius=None, local_order=None, model_type="snv"):
+        """One row per (site, allele): ``(symbols, cat_x)`` shaped as ``encode_subst_windows`` gives them, bit for bit ``encode_symbols`` /
+        ``encode_kmer`` of (pos, strand) on the alternate haplotype of allele ``allele[i]`` of the ``mural_amd.mutagenesis.Alleles`` table
+        (an insertion, deletion or multi-base replacement; -1: none).  `pos` is in the coordinates of THAT haplotype.  The genome itself is
+        only read."""
+        from ..mutagenesis import encode_allele_windows
+        return encode_allele_windows(self, pos, strand, allele, alleles, int(radius), None if local_radius is None else int(local_radius),
+                                     None if local_order is None else int(local_order), model_type)
+
     def encode_onehot(self, pos, strand, radius, model_type="snv"):
         """float32 (n, 4, W) one-hot windows (N -> 0.25 each, other IUPAC codes -> their fractional columns), exact w.r.t.
         seq_ohe_encoder."""

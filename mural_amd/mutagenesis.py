@@ -1,5 +1,5 @@
 """In-silico saturation mutagenesis and variant footprints on top of the SNV and INDEL forwards (csrc/mutagenesis.hip; DESIGN.md
-sections 3.27 and 3.28).
+sections 3.27, 3.28 and 3.29).
 
 ``saturation_mutagenesis`` answers "which bases of the +-distal_radius window make this site's rate what it is": every column of the
 window is replaced by each of its three alternatives, the window re-predicted, and the change in log-probability reported as a map
@@ -12,6 +12,11 @@ the window is [pos - R + 1, pos + R] (W = 2 R) and the log-probabilities are the
 The numpy twins (``encode_subst_windows_host``, ``mutagenesis_rows_host``, ``mutagenesis_reduce_host``) are the specification the CPU
 tests pin against brute force (patch the sequence string, encode with the oracle); ``log_softmax_host`` is the float64 twin of the
 log-softmax.
+
+``allele_footprint`` is the footprint of an allele that may change the sequence's length -- an insertion, a deletion, a multi-base
+replacement (``Alleles``) -- on the sites it can reach; its windows come from ``mural_encode_allele_windows``, which reads the
+alternate haplotype in its own coordinates.  Twins: ``encode_allele_windows_host``, ``allele_rows_host``; ``alternate_sequence`` is the
+string patch they are pinned against.
 """
 import ctypes as C
 
@@ -483,3 +488,317 @@ def variant_footprint(model, genome, var_pos, var_base, strand, local_radius=Non
             dead |= row_pos == sub_pos
         delta = torch.where(dead[:, None], torch.full_like(delta, float("nan")), delta)
     return delta.reshape(m, W, n_class), focal.reshape(m, W)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# alleles that change the sequence's length: insertions, deletions, multi-base replacements
+# ----------------------------------------------------------------------------------------------------------------------------------
+MAX_ALT = 32                        # bases of an alternate allele: 2 bits each in one uint64
+
+
+def _pack_alt(alt):
+    """The alternate bases as one integer (base i in bits 2i, 2i+1); ValueError for more than 32 bases or anything but A/C/G/T."""
+    if len(alt) > MAX_ALT:
+        raise ValueError(f"alternate allele of {len(alt)} bases: at most {MAX_ALT} are held")
+    word = 0
+    for i, ch in enumerate(alt):
+        b = "ACGT".find(ch.upper())
+        if b < 0 or len(ch) != 1:
+            raise ValueError(f"alternate allele {alt!r}: only A/C/G/T can be inserted")
+        word |= b << (2 * i)
+    return word
+
+
+def _live(length, p, d, k):
+    return (p >= 0) & (d >= 0) & (p + d <= length) & (k >= 0) & (k <= MAX_ALT)
+
+
+def alternate_sequence(seq, p, d, alt):
+    """The string patch: `seq` with [p, p + d) replaced by `alt`; `seq` itself where the allele is not live."""
+    if not bool(_live(len(seq), p, d, len(alt))):
+        return seq
+    return seq[:p] + alt + seq[p + d:]
+
+
+class Alleles:
+    """A table of alleles on the device: allele v replaces the '+'-strand reference bases [pos[v], pos[v] + ref_len[v]) by alt_len[v] plain
+    bases, base i (0..3 = A, C, G, T) in bits 2i, 2i+1 of alt[v].  Four int64 tensors of one length (``alt`` holds the uint64 bit
+    pattern).  ref_len = 0 inserts before pos (pos = chromosome length appends), alt_len = 0 deletes.  An allele is live iff 0 <= pos,
+    0 <= ref_len, pos + ref_len <= length and 0 <= alt_len <= 32; the encoder reads the genome as it is for any other."""
+
+    __slots__ = ("pos", "ref_len", "alt_len", "alt")
+
+    def __init__(self, pos, ref_len, alt_len, alt):
+        self.pos, self.ref_len, self.alt_len, self.alt = (t.to(torch.int64).contiguous() for t in (pos, ref_len, alt_len, alt))
+        if self.pos.dim() != 1 or any(t.shape != self.pos.shape or t.device != self.pos.device for t in (self.ref_len, self.alt_len, self.alt)):
+            raise ValueError("Alleles: four 1-D tensors of one length on one device")
+
+    def __len__(self):
+        return self.pos.shape[0]
+
+    @property
+    def device(self):
+        return self.pos.device
+
+    @classmethod
+    def from_host(cls, pos, ref_len, alt_strings, device="cuda"):
+        """From 0-based positions, reference lengths and alternate strings ("" deletes).  ValueError for an alternate longer than 32, one
+        that holds anything but A/C/G/T, or a negative reference length."""
+        pos, ref_len = np.asarray(pos, np.int64).reshape(-1), np.asarray(ref_len, np.int64).reshape(-1)
+        if len(pos) != len(ref_len) or len(pos) != len(alt_strings):
+            raise ValueError("Alleles.from_host: pos, ref_len and alt_strings must be equally long")
+        if (ref_len < 0).any():
+            raise ValueError("Alleles.from_host: a reference length is negative")
+        words = np.array([_pack_alt(a) for a in alt_strings], np.uint64).reshape(-1)
+        alt_len = np.array([len(a) for a in alt_strings], np.int64).reshape(-1)
+        return cls(*(torch.from_numpy(a).to(device) for a in (pos, ref_len, alt_len, words.view(np.int64))))
+
+    @staticmethod
+    def from_vcf_fields(pos1, ref, alt):
+        """0-based (p, d, alt) of a VCF record's 1-based POS, REF and one ALT: the shared prefix (the anchor base of an insertion or
+        deletion) and then the shared suffix are trimmed.  Identical REF and ALT give the identity (d = 0, alt "")."""
+        ref, alt = ref.upper(), alt.upper()
+        lead = 0
+        while lead < len(ref) and lead < len(alt) and ref[lead] == alt[lead]:
+            lead += 1
+        ref, alt = ref[lead:], alt[lead:]
+        tail = 0
+        while tail < len(ref) and tail < len(alt) and ref[-1 - tail] == alt[-1 - tail]:
+            tail += 1
+        return int(pos1) - 1 + lead, len(ref) - tail, alt[:len(alt) - tail]
+
+    def host(self):
+        """(pos, ref_len, alt_len int64; alt uint64) as numpy arrays."""
+        p, d, k, a = (t.cpu().numpy() for t in (self.pos, self.ref_len, self.alt_len, self.alt))
+        return p, d, k, a.view(np.uint64)
+
+
+def _alleles_host(alleles):
+    if isinstance(alleles, Alleles):
+        return alleles.host()
+    p, d, k, a = alleles
+    a = np.asarray(a)
+    return (np.asarray(p, np.int64), np.asarray(d, np.int64), np.asarray(k, np.int64),
+            a.view(np.uint64) if a.dtype == np.int64 else a.astype(np.uint64))
+
+
+def _allele_symbols_host(codes, pos, neg, off0, W, live, p, k, shift, alt):
+    """(n, W) strand-oriented symbols of the windows at `pos` on the rows' alternate haplotypes (per-row live / p / k / shift / alt)"""
+    L = len(codes)
+    j = np.arange(W, dtype=np.int64)
+    q = pos[:, None] + off0 + np.where(neg[:, None], W - 1 - j[None, :], j[None, :])     # position on the alternate haplotype
+    p, k, shift, live = p[:, None], k[:, None], shift[:, None], live[:, None]
+    hit = live & (q >= p) & (q < p + k)
+    ref = np.where(live & (q >= p + k), q - shift, q)
+    inside = (ref >= 0) & (ref < L)
+    sym = np.full(q.shape, 4, np.uint8)
+    sym[inside] = codes[ref[inside]]
+    idx = np.where(hit, q - p, 0).astype(np.uint64)
+    own = ((alt[:, None] >> (np.uint64(2) * idx)) & np.uint64(3)).astype(np.uint8)
+    sym = np.where(hit, own, sym)
+    return np.where(neg[:, None], _COMPLEMENT[sym], sym).astype(np.uint8)
+
+
+def encode_allele_windows_host(genome, pos, strand, allele, alleles, radius, local_radius=None, local_order=None, model_type="snv"):
+    """The numpy twin of ``mural_encode_allele_windows``: (symbols uint8 (n, W), cat_x int64 or None) of the windows at `pos` (alternate-
+    haplotype coordinates) / `strand`, row i on the haplotype of allele ``allele[i]`` of `alleles` (an ``Alleles`` or a (pos, ref_len,
+    alt_len, alt) tuple of arrays); -1, an index outside the table or an allele that is not live: the genome as it is."""
+    codes = _codes(genome)
+    pos, neg = np.asarray(pos, np.int64), np.asarray(strand) != 0
+    a_pos, a_d, a_k, a_alt = _alleles_host(alleles)
+    v = np.asarray(allele, np.int64)
+    named = (v >= 0) & (v < len(a_pos))
+    vi = np.where(named, v, 0)
+    if len(a_pos):
+        p, d, k, alt = a_pos[vi], a_d[vi], a_k[vi], a_alt[vi]
+    else:
+        p = d = k = np.zeros(len(v), np.int64)
+        alt = np.zeros(len(v), np.uint64)
+    live = named & _live(len(codes), p, d, k)
+    p, k, shift = np.where(live, p, 0), np.where(live, k, 0), np.where(live, k - d, 0)
+    off0, W = _window(radius, model_type)
+    symbols = _allele_symbols_host(codes, pos, neg, off0, W, live, p, k, shift, alt)
+    if model_type == "indel":
+        return symbols, None
+    loff, lW = _window(local_radius)
+    digit = _allele_symbols_host(codes, pos, neg, loff, lW, live, p, k, shift, alt).astype(np.int64)
+    ncol = lW - (local_order - 1)
+    val = np.zeros((len(digit), ncol), np.int64)
+    bad = np.zeros((len(digit), ncol), bool)
+    for t in range(local_order):
+        col = digit[:, t:t + ncol]
+        bad |= col > 3
+        val = val * 4 + np.where(col > 3, 0, col)
+    return symbols, np.where(bad, 4 ** local_order, val)
+
+
+def allele_footprint_offsets(radius, model_type="snv", device=None):
+    """int64 offsets e of ``allele_footprint``'s second axis: [-R, R - 1] for the SNV models, [-R, R - 2] for the INDEL model.  e < 0 is
+    the site p + e left of the allele, e >= 0 the site p + ref_len + e right of the replaced span."""
+    off0, W = _window(radius, model_type)
+    return torch.arange(W - 1, dtype=torch.int64, device=device) - (off0 + W - 1)
+
+
+def allele_rows_host(length, alleles, strand, radius, first, count, model_type="snv"):
+    """The numpy twin of ``mural_allele_rows``: (ref_pos int64, alt_pos int64, row_strand uint8, row_allele int64) of the row ids [first,
+    first + count), id = v * (W - 1) + c.  `length` is the chromosome's."""
+    a_pos, a_d, a_k, _ = _alleles_host(alleles)
+    strand = (np.asarray(strand) != 0).astype(np.uint8)
+    off0, W = _window(radius, model_type)
+    slots = W - 1
+    if first < 0 or count < 0 or first + count > len(a_pos) * slots:
+        raise ValueError("allele_rows: ids [first, first + count) must lie in [0, n_alleles * (W - 1))")
+    ids = first + np.arange(count, dtype=np.int64)
+    v = ids // slots
+    e = ids % slots - (off0 + W - 1)
+    p = a_pos[v]
+    live = _live(length, p, a_d[v], a_k[v])
+    d, k = np.where(live, a_d[v], 0), np.where(live, a_k[v], 0)
+    ref_pos = p + e + np.where(e < 0, 0, d)
+    alt_pos = np.where(e < 0, ref_pos, ref_pos + k - d)
+    return ref_pos, alt_pos, strand[v], np.where(live, v, -1)
+
+
+def _encode_allele_into(genome, pos, strand, allele, alleles, radius, indel, local_radius, local_order, symbols, cat_x):
+    g = genome.as_struct()
+    with torch.cuda.device(genome.device):
+        _lib.check(_lib.lib().mural_encode_allele_windows(
+            C.byref(g), pos.data_ptr(), strand.data_ptr(), allele.data_ptr(), pos.shape[0], alleles.pos.data_ptr(),
+            alleles.ref_len.data_ptr(), alleles.alt_len.data_ptr(), alleles.alt.data_ptr(), len(alleles), int(radius), int(indel),
+            int(local_radius), int(local_order), None if symbols is None else symbols.data_ptr(),
+            None if cat_x is None else cat_x.data_ptr(), _lib.current_stream_ptr(genome.device)))
+
+
+def _require_alleles(alleles, device):
+    if not isinstance(alleles, Alleles):
+        raise TypeError("alleles must be a mural_amd.mutagenesis.Alleles")
+    _lib.require_cuda(alleles.pos, "alleles")
+    if alleles.device != torch.device(device):
+        raise RuntimeError(f"alleles ({alleles.device}) and genome ({device}) must live on one HIP device")
+
+
+def encode_allele_windows(genome, pos, strand, allele, alleles, radius, local_radius=None, local_order=None, model_type="snv"):
+    """``PackedGenome.encode_allele_windows``: see there."""
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
+    _require_alleles(alleles, genome.packed2.device)
+    pos, strand = genome._prep(pos, strand)
+    allele = torch.as_tensor(allele, dtype=torch.int64, device=genome.device).contiguous()
+    if allele.shape != pos.shape:
+        raise ValueError("allele must be 1-D and as long as pos")
+    n = pos.shape[0]
+    if model_type == "indel":
+        symbols = torch.empty((n, 2 * radius), dtype=torch.uint8, device=genome.device)
+        _encode_allele_into(genome, pos, strand, allele, alleles, radius, 1, 0, 0, symbols, None)
+        return symbols, None
+    if local_radius is None or local_order is None:
+        raise ValueError("encode_allele_windows: the SNV windows need local_radius and local_order")
+    symbols = torch.empty((n, 2 * radius + 1), dtype=torch.uint8, device=genome.device)
+    cat_x = torch.empty((n, 2 * local_radius + 1 - (local_order - 1)), dtype=torch.int64, device=genome.device)
+    _encode_allele_into(genome, pos, strand, allele, alleles, radius, 0, local_radius, local_order, symbols, cat_x)
+    return symbols, cat_x
+
+
+def _allele_rows_into(genome, alleles, strand, radius, indel, first, count, out):
+    g = genome.as_struct()
+    with torch.cuda.device(genome.device):
+        _lib.check(_lib.lib().mural_allele_rows(C.byref(g), alleles.pos.data_ptr(), alleles.ref_len.data_ptr(), alleles.alt_len.data_ptr(),
+                                               len(alleles), strand.data_ptr(), int(radius), int(indel), int(first), int(count),
+                                               *[t.data_ptr() for t in out], _lib.current_stream_ptr(genome.device)))
+
+
+def allele_rows(genome, alleles, strand, radius, first, count, model_type="snv"):
+    """``mural_allele_rows`` on the device: (ref_pos, alt_pos, row_strand, row_allele) of the row ids [first, first + count); `strand` is
+    one byte per allele.  ValueError for ids outside [0, n_alleles * (W - 1))."""
+    if model_type not in ("snv", "indel"):
+        raise ValueError(f"model_type {model_type} not supported!")
+    _require_alleles(alleles, genome.packed2.device)
+    dev = genome.device
+    strand = torch.as_tensor(strand, dtype=torch.uint8, device=dev).contiguous()
+    if strand.shape != alleles.pos.shape:
+        raise ValueError("strand must hold one byte per allele")
+    count = max(int(count), -1)
+    out = (torch.empty(max(count, 0), dtype=torch.int64, device=dev), torch.empty(max(count, 0), dtype=torch.int64, device=dev),
+           torch.empty(max(count, 0), dtype=torch.uint8, device=dev), torch.empty(max(count, 0), dtype=torch.int64, device=dev))
+    _allele_rows_into(genome, alleles, strand, radius, model_type == "indel", first, count, out)
+    return out
+
+
+def allele_footprint(model, genome, alleles, strand, local_radius=None, local_order=3, chunk_windows=1 << 17, distal_radius=None, timings=None):
+    """What each allele of an ``Alleles`` table (insertions, deletions, multi-base replacements) does to the sites it can reach, read on
+    `strand` (uint8 per allele, 1 = '-'): ``(delta float32 (m, W - 1, n_class), focal uint8 (m, W - 1))``, second axis
+    ``allele_footprint_offsets`` (e < 0: the site pos + e; e >= 0: the site pos + ref_len + e, which sits at + alt_len - ref_len on the
+    alternate haplotype).  These are exactly the sites outside the replaced span whose window can differ between the two haplotypes.
+    Every chunk of `chunk_windows` rows runs enumerate (``mural_allele_rows``) -> encode on the alternate haplotype -> encode on the
+    reference -> two ``forward_symbols`` (and ``scores_log_softmax`` for a ``UNet_Small``) -> one float32 subtraction.  NaN where the
+    site lies outside the chromosome and in every row of an allele that is not live; `focal` is the site's reference focal symbol on
+    `strand` (N outside the chromosome).
+
+    Sites inside the replaced span and on inserted bases have no counterpart on the other haplotype and are not part of the footprint;
+    for what a one-base substitution does to the rate of its own site, ``saturation_mutagenesis`` / ``variant_footprint`` remain the
+    tools.  Models and errors as ``variant_footprint``.  `timings`: as in ``saturation_mutagenesis`` (``rows_encode_ms``,
+    ``forward_ms``)."""
+    indel = _is_indel(model)
+    if indel:
+        R, r = _require_indel(model, distal_radius), 0
+    else:
+        R, r = _require_model(model, local_radius, local_order)
+    if not isinstance(alleles, Alleles):
+        raise TypeError("alleles must be a mural_amd.mutagenesis.Alleles")
+    a_pos, strand = _sites(genome, model, alleles.pos, strand)
+    if chunk_windows < 1:
+        raise ValueError("chunk_windows must be >= 1")
+    model_type = "indel" if indel else "snv"
+    dev, m, slots, n_class = a_pos.device, len(alleles), _window(R, model_type)[1] - 1, model.n_class
+    W = slots + 1
+    with_cat = not indel and model.model_no == 2
+    with torch.no_grad(), torch.cuda.device(dev):
+        total = m * slots
+        cap = min(int(chunk_windows), max(total, 1))
+        rows = (torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev),
+                torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(cap, dtype=torch.int64, device=dev))
+        ref_pos, alt_pos, row_strand, row_allele = rows
+        none = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        symbols = torch.empty((cap, W), dtype=torch.uint8, device=dev)
+        cat_x = torch.empty((cap, 2 * r + 1 - (local_order - 1)), dtype=torch.int64, device=dev) if with_cat else None
+        delta = torch.empty((total, n_class), dtype=torch.float32, device=dev)
+        focal = torch.empty(total, dtype=torch.uint8, device=dev)
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        marks = []
+
+        def mark():
+            if timings is not None:
+                marks.append(torch.cuda.Event(enable_timing=True))
+                marks[-1].record()
+
+        def forward(k):
+            if indel:
+                return scores_log_softmax(model.forward_symbols(symbols[:k]))
+            return model.forward_symbols(cat_x[:k] if with_cat else None, symbols[:k])
+
+        for c0 in range(0, total, cap):
+            k = min(cap, total - c0)
+            mark()
+            _allele_rows_into(genome, alleles, strand, R, indel, c0, k, rows)
+            _encode_allele_into(genome, alt_pos[:k], row_strand[:k], row_allele[:k], alleles, R, indel, r, local_order, symbols, cat_x)
+            mark()
+            alt_logp = forward(k)
+            mark()
+            _encode_allele_into(genome, ref_pos[:k], row_strand[:k], none[:k], alleles, R, indel, r, local_order, symbols, cat_x)
+            mark()
+            ref_logp = forward(k)
+            mark()
+            dead = (ref_pos[:k] < 0) | (ref_pos[:k] >= genome.length) | (row_allele[:k] < 0)
+            delta[c0:c0 + k] = torch.where(dead[:, None], nan, alt_logp - ref_logp)
+            # (the reference windows were encoded last; the INDEL window holds the site in column R - 1 on '+', R on '-')
+            if indel:
+                focal[c0:c0 + k] = symbols[:k].gather(1, (R - 1 + row_strand[:k].to(torch.int64))[:, None])[:, 0]
+            else:
+                focal[c0:c0 + k] = symbols[:k, R]
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            for c in range(0, len(marks), 5):
+                t = [marks[c + i].elapsed_time(marks[c + i + 1]) for i in range(4)]
+                timings["rows_encode_ms"] = timings.get("rows_encode_ms", 0.0) + t[0] + t[2]
+                timings["forward_ms"] = timings.get("forward_ms", 0.0) + t[1] + t[3]
+    return delta.reshape(m, slots, n_class), focal.reshape(m, slots)
