@@ -136,6 +136,25 @@ int mural_mutagenesis_rows_window(const MuralGenome* g, const int64_t* pos, cons
 int mural_mutagenesis_reduce_window(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, int64_t n_sites, int32_t W,
                                     int32_t n_class, int64_t first, int64_t count, float* delta, float* logp_map, void* stream);
 int mural_scores_log_softmax(const float* scores, int64_t n, int32_t n_class, float* out, void* stream);
+/* Mutagenesis profiles: the map reduced over sites in flight instead of written.
+ * mural_mutagenesis_profile_window: takes the place of mural_mutagenesis_reduce_window in a chunk; same ids, v = (site*W + j)*3 + a.
+ *   ref_logp / var_logp / ref_symbols : as mural_mutagenesis_reduce_window ([n_sites][n_class], [count][n_class], [n_sites][W])
+ *   group                : dev int32 [n_sites], or NULL: every site in group 0
+ *   table                : dev uint64 [n_groups][W][4][3][n_class][5], cell [group][column j][reference symbol 0..3][a][class]; words
+ *                          n (terms added), sum (sum of q, two's complement), abs (sum of |q|), sq_lo (sum of q*q mod 2^40),
+ *                          sq_hi (sum of q*q >> 40).  ACCUMULATED into: the caller zeroes it once.
+ *   status               : dev uint64 [3], accumulated into likewise: [0] bits (1: a term was infinite or NaN; 2: a finite term had
+ *                          |delta| >= 256), [1] / [2] the number of terms of either kind
+ * A term is one (id, class): delta = var_logp - ref_logp (the single float32 subtraction of the reduce), q = rne(delta * 2^30), valid when
+ * delta is finite and |delta| < 256 (so |q| < 2^38).  An invalid term adds nothing to the table and is counted in status.  A column whose
+ * reference symbol is not A/C/G/T and a site whose group lies outside [0, n_groups) add nothing anywhere.  n_sites <= 2^24 (refused
+ * otherwise): with at most 2^24 terms per cell no word overflows; the caller who keeps adding to one table watches the n words.  Any
+ * [first, first+count) inside [0, n_sites*W*3) may be asked for.  The adds are 64-bit integer atomics (through a per-block LDS table
+ * where the groups' cells fit and the call is long enough to be contended): the table is the same integers whatever the chunking and
+ * the order of arrival.  One launch; count == 0 launches nothing. */
+int mural_mutagenesis_profile_window(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, const int32_t* group,
+                                     int64_t n_sites, int32_t W, int32_t n_class, int32_t n_groups, int64_t first, int64_t count,
+                                     uint64_t* table, uint64_t* status, void* stream);
 /* Alleles that change the sequence's length.  Allele v of the table replaces the '+'-strand bases
  * [a_pos[v], a_pos[v] + a_ref_len[v]) by a_alt_len[v] plain bases: base i (0..3 = A C G T) in bits 2i, 2i+1 of a_alt[v].  ref_len = 0 is
  * an insertion before a_pos (a_pos = g->length appends), alt_len = 0 a deletion.  An allele is LIVE iff 0 <= a_pos, 0 <= a_ref_len,

@@ -386,6 +386,7 @@ PROTOTYPES = {
     "mural_mutagenesis_rows_window": (C.c_int, [C.POINTER(MuralGenome), VP, VP, I64, I32, I32, I64, I64, VP, VP, VP, VP, VP]),
     "mural_mutagenesis_reduce_window": (C.c_int, [VP, VP, VP, I64, I32, I32, I64, I64, VP, VP, VP]),
     "mural_scores_log_softmax": (C.c_int, [VP, I64, I32, VP, VP]),
+    "mural_mutagenesis_profile_window": (C.c_int, [VP, VP, VP, VP, I64, I32, I32, I32, I64, I64, VP, VP, VP]),
     "mural_encode_allele_windows": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, I64, VP, VP, VP, VP, I64, I32, I32, I32, I32, VP, VP, VP]),
     "mural_allele_rows": (C.c_int, [C.POINTER(MuralGenome), VP, VP, VP, I64, VP, I32, I32, I64, I64, VP, VP, VP, VP, VP]),
     "mural_snv_kernel_name": (C.c_char_p, []),

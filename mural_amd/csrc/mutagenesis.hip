@@ -176,6 +176,80 @@ __global__ __launch_bounds__(256) void mutagenesis_reduce_kernel(const float* __
   }
 }
 
+// The map reduced over sites instead of written (section 3.30).  A term is one (variant id, class); its cell is [group][column][ref][a]
+// [class], five words each (PW_*).  Everything added is an integer, so the table does not depend on which adds went through LDS, on the
+// order they arrived in or on how the ids were chunked.
+enum : int { PW_N = 0, PW_SUM = 1, PW_ABS = 2, PW_SQ_LO = 3, PW_SQ_HI = 4, PW_WORDS = 5 };
+enum : int { PF_NONFINITE = 1, PF_RANGE = 2 };     // status[0] bits; status[1], status[2]: how many terms of each kind
+constexpr int PROFILE_IDS_GLOBAL = 256;            // ids per block where every add is a global atomic
+constexpr int PROFILE_IDS_LDS = 2048;              // ... and where the block sums in LDS first: one flush of the table per 2048 ids
+constexpr int PROFILE_LDS_BYTES = 64 * 1024;
+
+template <class Mem>
+__device__ __forceinline__ void profile_add(Mem* __restrict__ cell, int64_t q) {
+  const u64 mag = (u64)(q < 0 ? -q : q);                                           // < 2^38
+  const u64 lo = mag * mag, hi = __umul64hi(mag, mag);                             // q^2 < 2^76
+  atomicAdd(cell + PW_N, 1ull);
+  if (q == 0) return;
+  atomicAdd(cell + PW_SUM, (u64)q);
+  atomicAdd(cell + PW_ABS, mag);
+  if (lo & ((1ull << 40) - 1)) atomicAdd(cell + PW_SQ_LO, lo & ((1ull << 40) - 1));
+  if ((lo >> 40) | hi) atomicAdd(cell + PW_SQ_HI, (lo >> 40) | (hi << 24));
+}
+
+// Block b owns the ids [b * ids_per_block, (b + 1) * ids_per_block) of the call, one thread per term.  Groups below lds_groups are summed
+// in the block's LDS table (lds_groups * W * 12 * C * 5 words of dynamic shared memory) and flushed once, the others go to `table` directly.
+__global__ __launch_bounds__(256) void mutagenesis_profile_kernel(const float* __restrict__ ref_logp, const float* __restrict__ var_logp,
+                                                                  const uint8_t* __restrict__ ref_sym, const int32_t* __restrict__ group,
+                                                                  int W, int C, int n_groups, int64_t first, int64_t count,
+                                                                  int ids_per_block, int lds_groups, u64* __restrict__ table,
+                                                                  u64* __restrict__ status) {
+  extern __shared__ u64 lds_table[];
+  const int64_t group_words = (int64_t)W * 12 * C * PW_WORDS;
+  const int lds_words = (int)(lds_groups * group_words);
+  for (int i = threadIdx.x; i < lds_words; i += blockDim.x) lds_table[i] = 0;
+  if (lds_words) __syncthreads();
+  const int64_t k0 = (int64_t)blockIdx.x * ids_per_block;
+  const int64_t k1 = k0 + ids_per_block < count ? k0 + ids_per_block : count;
+  u64 nonfinite = 0, range = 0;
+  for (int64_t t = k0 * C + threadIdx.x; t < k1 * C; t += blockDim.x) {
+    const int64_t k = t / C;
+    const int c = (int)(t - k * C);
+    const int64_t v = first + k;
+    const int64_t cell = v / 3;                  // site * W + j
+    const int a = (int)(v - cell * 3);
+    const int64_t site = cell / W;
+    const int j = (int)(cell - site * W);
+    const uint32_t ref = ref_sym[cell];
+    const int64_t g = group ? (int64_t)group[site] : 0;
+    if (ref >= 4u || g < 0 || g >= n_groups) continue;
+    // (judged on the bit pattern: the library is built with -fno-honor-nans)
+    const float delta = var_logp[t] - ref_logp[site * C + c];
+    const uint32_t mag = __float_as_uint(delta) & 0x7fffffffu;
+    if (mag >= 0x43800000u) {                    // |delta| >= 256, infinite or NaN
+      if (mag >= 0x7f800000u) ++nonfinite; else ++range;
+      continue;
+    }
+    const int64_t q = (int64_t)rintf(delta * 1073741824.0f);                       // exact: a power of two, |q| < 2^38
+    const int64_t at = ((((g * W + j) * 4 + ref) * 3 + a) * C + c) * PW_WORDS;
+    if (g < lds_groups) profile_add(lds_table + at, q);
+    else profile_add(table + at, q);
+  }
+  if (lds_words) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < lds_words; i += blockDim.x) {
+      const u64 x = lds_table[i];
+      if (x) atomicAdd(table + i, x);
+    }
+  }
+  nonfinite = wave_sum(nonfinite), range = wave_sum(range);
+  if ((threadIdx.x & 63) == 0 && (nonfinite | range)) {
+    atomicOr(status, (u64)((nonfinite ? PF_NONFINITE : 0) | (range ? PF_RANGE : 0)));
+    if (nonfinite) atomicAdd(status + 1, nonfinite);
+    if (range) atomicAdd(status + 2, range);
+  }
+}
+
 // out[i][c] = s[c] - (max + log sum exp(s - max)): one thread per row, classes in ascending order, so a row's bits depend on nothing
 // but the row
 __global__ __launch_bounds__(256) void scores_log_softmax_kernel(const float* __restrict__ scores, int64_t n, int C, float* __restrict__ out) {
@@ -298,6 +372,36 @@ extern "C" int mural_mutagenesis_reduce(const float* ref_logp, const float* var_
   int off, W;
   if (int rc = window_geometry(radius, 0, &off, &W)) return rc;
   return mural_mutagenesis_reduce_window(ref_logp, var_logp, ref_symbols, n_sites, W, n_class, first, count, delta, logp_map, stream);
+}
+
+extern "C" int mural_mutagenesis_profile_window(const float* ref_logp, const float* var_logp, const uint8_t* ref_symbols, const int32_t* group,
+                                                int64_t n_sites, int32_t W, int32_t n_class, int32_t n_groups, int64_t first, int64_t count,
+                                                uint64_t* table, uint64_t* status, void* stream) {
+  MURAL_REQUIRE(W >= 1, "mutagenesis_profile: W must be >= 1, got %d", W);
+  MURAL_REQUIRE(n_class >= 1, "mutagenesis_profile: n_class must be >= 1, got %d", n_class);
+  MURAL_REQUIRE(n_groups >= 1, "mutagenesis_profile: n_groups must be >= 1, got %d", n_groups);
+  MURAL_REQUIRE(n_sites >= 0 && n_sites <= (int64_t)1 << 24,
+                "mutagenesis_profile: at most 2^24 sites per call (a cell's sums are sized for 2^24 terms of |q| < 2^38), got %lld",
+                (long long)n_sites);
+  const int64_t group_words = (int64_t)W * 12 * n_class * PW_WORDS;
+  MURAL_REQUIRE(group_words <= INT64_MAX / 8 / n_groups && n_sites <= INT64_MAX / (3 * (int64_t)W) / n_class,
+                "mutagenesis_profile: sizes out of range");
+  MURAL_REQUIRE(first >= 0 && count >= 0 && first <= n_sites * W * 3 - count,
+                "mutagenesis_profile: ids [first, first + count) must lie in [0, n_sites * W * 3)");
+  if (count == 0) return MURAL_OK;
+  MURAL_REQUIRE(ref_logp && var_logp && ref_symbols && table && status, "mutagenesis_profile: pointers must not be NULL");
+  // the groups that fit are summed per block in LDS; a call of few ids (no contention to speak of) adds to the table directly
+  int64_t lds_groups = PROFILE_LDS_BYTES / 8 / group_words;
+  if (lds_groups > n_groups) lds_groups = n_groups;
+  if (count < 4 * PROFILE_IDS_LDS) lds_groups = 0;
+  const int ids_per_block = lds_groups ? PROFILE_IDS_LDS : PROFILE_IDS_GLOBAL;
+  const int64_t blocks = (count + ids_per_block - 1) / ids_per_block;
+  MURAL_REQUIRE(blocks <= INT32_MAX, "mutagenesis_profile: count out of range");
+  hipLaunchKernelGGL(mutagenesis_profile_kernel, dim3((unsigned)blocks), dim3(256), (size_t)(lds_groups * group_words * 8), (hipStream_t)stream,
+                     ref_logp, var_logp, ref_symbols, group, (int)W, (int)n_class, (int)n_groups, first, count, ids_per_block, (int)lds_groups,
+                     reinterpret_cast<u64*>(table), reinterpret_cast<u64*>(status));
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
 }
 
 extern "C" int mural_scores_log_softmax(const float* scores, int64_t n, int32_t n_class, float* out, void* stream) {

@@ -1,5 +1,5 @@
 """In-silico saturation mutagenesis and variant footprints on top of the SNV and INDEL forwards (csrc/mutagenesis.hip; DESIGN.md
-sections 3.27, 3.28 and 3.29).
+sections 3.27 to 3.30).
 
 ``saturation_mutagenesis`` answers "which bases of the +-distal_radius window make this site's rate what it is": every column of the
 window is replaced by each of its three alternatives, the window re-predicted, and the change in log-probability reported as a map
@@ -17,6 +17,10 @@ log-softmax.
 replacement (``Alleles``) -- on the sites it can reach; its windows come from ``mural_encode_allele_windows``, which reads the
 alternate haplotype in its own coordinates.  Twins: ``encode_allele_windows_host``, ``allele_rows_host``; ``alternate_sequence`` is the
 string patch they are pinned against.
+
+``mutagenesis_profile`` is the map reduced over sites in flight (section 3.30): the same chunk loop with an accumulating kernel
+(``mural_mutagenesis_profile_window``) in the place of the reduce, exact integer sums per [group, column, reference base, alternative,
+class] in a ``MutagenesisProfile`` whose tables add across chunks, calls and ranks.  Twin: ``mutagenesis_profile_host``.
 """
 import ctypes as C
 
@@ -147,6 +151,57 @@ def mutagenesis_reduce_host(ref_logp, var_logp, ref_symbols, first, delta, logp_
         last = ~plain & (a == 2)
         maps[site[last], j[last], 3] = nan
     return delta
+
+
+PROFILE_WORDS = 5                   # n, sum, abs, sq_lo, sq_hi of a cell (csrc/mutagenesis.hip: PW_*)
+PROFILE_SCALE = 30                  # q = rne(delta * 2^30)
+PROFILE_LIMIT = 256.0               # a term is valid when delta is finite and |delta| < 256
+PROFILE_MAX_SITES = 1 << 24         # per call: |q| < 2^38 and at most 2^24 terms per cell keep every word below 2^63
+PROFILE_NONFINITE, PROFILE_RANGE = 1, 2     # bits of status[0]; status[1] / status[2] count the terms of either kind
+
+
+def mutagenesis_profile_host(ref_logp, var_logp, ref_symbols, group, first, table, status=None):
+    """The numpy twin of ``mural_mutagenesis_profile_window``: adds the terms of the ids [first, first + count) into `table`, uint64
+    (n_groups, W, 4, 3, n_class, 5) indexed [group, column, reference symbol, a, class, word] in place (and the invalid terms into
+    `status`, uint64 (3,)).  `group`: int32 (n_sites,) or None for group 0 everywhere."""
+    ref_logp, var_logp = np.asarray(ref_logp, np.float32), np.asarray(var_logp, np.float32)
+    ref_symbols = np.asarray(ref_symbols, np.uint8)
+    n, W = ref_symbols.shape
+    n_groups, n_class = table.shape[0], ref_logp.shape[1]
+    if table.dtype != np.uint64 or table.shape != (n_groups, W, 4, 3, n_class, PROFILE_WORDS) or not table.flags.c_contiguous:
+        raise ValueError(f"mutagenesis_profile: table must be uint64 (n_groups, {W}, 4, 3, {n_class}, {PROFILE_WORDS})")
+    if n > PROFILE_MAX_SITES:
+        raise ValueError("mutagenesis_profile: at most 2^24 sites per call")
+    if first < 0 or first + len(var_logp) > n * W * 3:
+        raise ValueError("mutagenesis_profile: ids [first, first + count) must lie in [0, n_sites * W * 3)")
+    site, j, a = _ids(first, len(var_logp), W)
+    ref = ref_symbols[site, j].astype(np.int64)
+    grp = np.zeros(n, np.int64) if group is None else np.asarray(group, np.int32).astype(np.int64)
+    g = grp[site]
+    row = (ref < 4) & (g >= 0) & (g < n_groups)
+    with np.errstate(invalid="ignore", over="ignore"):
+        delta = var_logp - ref_logp[site]                                 # (count, n_class): the reduce's float32 subtraction
+        finite = np.isfinite(delta)
+        small = finite & (np.abs(delta) < np.float32(PROFILE_LIMIT))
+    term = row[:, None] & small
+    if status is not None:
+        nonfinite, out_of_range = int((row[:, None] & ~finite).sum()), int((row[:, None] & finite & ~small).sum())
+        status[0] |= np.uint64((PROFILE_NONFINITE if nonfinite else 0) | (PROFILE_RANGE if out_of_range else 0))
+        status[1] += np.uint64(nonfinite)
+        status[2] += np.uint64(out_of_range)
+    k, c = np.nonzero(term)
+    # float32 -> float64 is exact; times 2^30 only moves the exponent (|delta| < 2^8 and the smallest float32 is 2^-149: no overflow, no
+    # underflow in float64), so the product is delta * 2^30 itself and rint (to nearest, ties to even) is the one rounding of q
+    q = np.rint(delta[k, c].astype(np.float64) * float(1 << PROFILE_SCALE)).astype(np.int64)
+    mag = np.abs(q).astype(np.uint64)                                     # < 2^38: mag = hi * 2^20 + lo, mag^2 = hi^2 2^40 + (2 hi lo 2^20 + lo^2)
+    hi, lo = mag >> np.uint64(20), mag & np.uint64((1 << 20) - 1)
+    low = ((hi * lo) << np.uint64(21)) + lo * lo                          # < 2^60
+    cell = ((((g[k] * W + j[k]) * 4 + ref[k]) * 3 + a[k]) * n_class + c) * PROFILE_WORDS
+    flat = table.reshape(-1)
+    words = (np.ones(len(q), np.uint64), q.view(np.uint64), mag, low & np.uint64((1 << 40) - 1), hi * hi + (low >> np.uint64(40)))
+    for w, x in enumerate(words):
+        np.add.at(flat, cell + w, x)
+    return table
 
 
 def log_softmax_host(scores):
@@ -356,6 +411,30 @@ def saturation_mutagenesis(model, genome, pos, strand, local_radius=None, local_
     `local_radius` / `local_order` are ignored, and the log-probabilities are the log-softmax of ``forward_symbols``' scores (counted in
     ``forward_ms``).  The INDEL forward picks kernels by the size of a call, so its map is reproducible for one `chunk_windows` and
     agrees across values of it within the forward's own accuracy, not bit for bit."""
+    out = {}
+
+    def begin(ref_logp, ref_symbols, pos, strand, R, model_type):
+        n, W = ref_symbols.shape
+        # every element is written by the reduce (one writer each): no fill
+        delta = torch.empty((n, W, 4, ref_logp.shape[1]), dtype=torch.float32, device=pos.device)
+        logp_map = torch.empty_like(delta) if return_logp else None
+        out["map"] = MutagenesisMap(delta, ref_logp, ref_symbols, logp_map, pos, strand, R, model_type)
+        lib, n_class = _lib.lib(), ref_logp.shape[1]
+
+        def reduce(var, first, m, stream):
+            _lib.check(lib.mural_mutagenesis_reduce_window(ref_logp.data_ptr(), var.data_ptr(), ref_symbols.data_ptr(), n, W, n_class, first,
+                                                           m, delta.data_ptr(), logp_map.data_ptr() if return_logp else None, stream))
+        return reduce
+
+    _mutagenesis_chunks(model, genome, pos, strand, local_radius, local_order, chunk_windows, distal_radius, timings, begin)
+    return out["map"]
+
+
+def _mutagenesis_chunks(model, genome, pos, strand, local_radius, local_order, chunk_windows, distal_radius, timings, begin):
+    """The chunk loop ``saturation_mutagenesis`` and ``mutagenesis_profile`` share: checks the model and the sites, predicts the
+    unchanged windows, then runs enumerate -> encode -> ``forward_symbols`` -> reduce per chunk of `chunk_windows` variant ids with row
+    buffers allocated once.  ``begin(ref_logp, ref_symbols, pos, strand, R, model_type)`` is called once, before the first chunk, and
+    returns ``reduce(var_logp, first, m, stream)``, which consumes a chunk's log-probabilities (the third phase of `timings`)."""
     indel = _is_indel(model)
     if indel:
         R, r = _require_indel(model, distal_radius), 0
@@ -375,9 +454,7 @@ def saturation_mutagenesis(model, genome, pos, strand, local_radius=None, local_
         ref_symbols = genome.encode_symbols(pos, strand, R, model_type).sym
         ref_cat = genome.encode_kmer(pos, strand, r, local_order) if with_cat else None
         ref_logp = forward(ref_cat, ref_symbols) if n else torch.empty((0, n_class), dtype=torch.float32, device=dev)
-        # every element is written by the reduce (one writer each): no fill
-        delta = torch.empty((n, W, 4, n_class), dtype=torch.float32, device=dev)
-        logp_map = torch.empty_like(delta) if return_logp else None
+        reduce = begin(ref_logp, ref_symbols, pos, strand, R, model_type)
         total = n * W * 3
         cap = min(int(chunk_windows), max(total, 1))
         row_pos = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -410,14 +487,227 @@ def saturation_mutagenesis(model, genome, pos, strand, local_radius=None, local_
             mark()
             var = forward(cat_x[:m] if with_cat else None, symbols[:m])
             mark()
-            _lib.check(lib.mural_mutagenesis_reduce_window(ref_logp.data_ptr(), var.data_ptr(), ref_symbols.data_ptr(), n, W, n_class, first,
-                                                           m, delta.data_ptr(), logp_map.data_ptr() if return_logp else None, stream))
+            reduce(var, first, m, stream)
             mark()
         if timings is not None:
             torch.cuda.synchronize(dev)
             for k, name in enumerate(("rows_encode_ms", "forward_ms", "reduce_ms")):
                 timings[name] = timings.get(name, 0.0) + sum(marks[c + k].elapsed_time(marks[c + k + 1]) for c in range(0, len(marks), 4))
-    return MutagenesisMap(delta, ref_logp, ref_symbols, logp_map, pos, strand, R, model_type)
+
+
+def mutagenesis_profile_window(ref_logp, var_logp, ref_symbols, group, first, table, status):
+    """``mural_mutagenesis_profile_window`` on the device: the terms of the ids [first, first + count) added into `table` (int64 bit
+    patterns of the uint64 words, (n_groups, W, 4, 3, n_class, 5)) and `status` (int64 (3,)) in place.  Contiguous device tensors; `group`
+    int32 (n_sites,) or None."""
+    n, W = ref_symbols.shape
+    n_class, n_groups = ref_logp.shape[1], table.shape[0]
+    tensors = [(ref_logp, torch.float32, (n, n_class)), (var_logp, torch.float32, (var_logp.shape[0], n_class)),
+               (ref_symbols, torch.uint8, (n, W)), (table, torch.int64, (n_groups, W, 4, 3, n_class, PROFILE_WORDS)),
+               (status, torch.int64, (3,))]
+    if group is not None:
+        tensors.append((group, torch.int32, (n,)))
+    for t, dt, shape in tensors:
+        _lib.require_cuda(t, "mutagenesis_profile input")
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"mutagenesis_profile: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    dev = table.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mural_mutagenesis_profile_window(ref_logp.data_ptr(), var_logp.data_ptr(), ref_symbols.data_ptr(),
+                                                              None if group is None else group.data_ptr(), n, W, n_class, n_groups,
+                                                              int(first), var_logp.shape[0], table.data_ptr(), status.data_ptr(),
+                                                              _lib.current_stream_ptr(dev)))
+    return table
+
+
+class MutagenesisProfile:
+    """Saturation-mutagenesis maps reduced over sites: exact integer sums of q = rne(delta * 2^30) per [group,
+    window column, reference base, alternative, class].  ``words`` is one int64 tensor (the bit patterns of the uint64 words) that holds
+    the table and, in its last three entries, the status counters; ``table`` (n_groups, W, 4, 3, n_class, 5) and ``status`` (3,) are views
+    of it.  Tables add: across chunks, calls (``into=``), profiles (``merge``) and ranks (``all_reduce_``), to the same integers in any
+    order.  The float64 statistics are computed on the host from the integers.  A cell's words are sized for 2^24 terms; whoever adds
+    more than that many sites into one profile watches ``counts()``."""
+
+    __slots__ = ("words", "radius", "model_type", "n_class", "n_groups")
+
+    def __init__(self, words, radius, model_type, n_class, n_groups):
+        self.words, self.radius, self.model_type, self.n_class, self.n_groups = words, int(radius), model_type, int(n_class), int(n_groups)
+        if words.dtype != torch.int64 or words.dim() != 1 or words.shape[0] != self._cells() * PROFILE_WORDS + 3 or not words.is_contiguous():
+            raise ValueError(f"MutagenesisProfile: words must be a contiguous int64 tensor of {self._cells() * PROFILE_WORDS + 3} entries")
+
+    def _cells(self):
+        return self.n_groups * self.width * 12 * self.n_class
+
+    @classmethod
+    def zeros(cls, radius, model_type, n_class, n_groups=1, device="cpu"):
+        W = _window(radius, model_type)[1]
+        if n_class < 1 or n_groups < 1:
+            raise ValueError("MutagenesisProfile: n_class and n_groups must be >= 1")
+        return cls(torch.zeros(n_groups * W * 12 * n_class * PROFILE_WORDS + 3, dtype=torch.int64, device=device), radius, model_type,
+                   n_class, n_groups)
+
+    @property
+    def width(self):
+        return _window(self.radius, self.model_type)[1]
+
+    @property
+    def table(self):
+        return self.words[:-3].view(self.n_groups, self.width, 4, 3, self.n_class, PROFILE_WORDS)
+
+    @property
+    def status(self):
+        return self.words[-3:]
+
+    def table_host(self):
+        """The table as a uint64 numpy array (a copy unless the profile lives on the host, where it shares memory: the twin adds in place)."""
+        return self.table.cpu().numpy().view(np.uint64)
+
+    def status_host(self):
+        """(bits, non-finite terms, finite terms of |delta| >= 256) as Python ints."""
+        return tuple(int(x) for x in self.status.cpu().numpy().view(np.uint64))
+
+    def offsets(self):
+        """int64 (W,): the columns' distance from the site in window orientation.  SNV: -R .. R.  INDEL (W = 2 R): -R + 1 .. R, the
+        distances on '+'; a '-' site sits one column further right, its distances are these minus one."""
+        return np.arange(self.width, dtype=np.int64) + _window(self.radius, self.model_type)[0]
+
+    # -- statistics: float64 (n_groups, W, 4, 4, n_class) indexed [group, column, ref, alt base in window orientation, class] ---------
+    def _folded(self):
+        """(n, sum, abs, sq) as float64 in the (G, W, 4, 4, C) layout, zero where nothing was added, and the mask of empty entries."""
+        t = self.table_host()
+        G, W, C = self.n_groups, self.width, self.n_class
+        words = (t[..., 0].astype(np.float64), t[..., 1].view(np.int64).astype(np.float64), t[..., 2].astype(np.float64),
+                 t[..., 4].astype(np.float64) * float(1 << 40) + t[..., 3].astype(np.float64))
+        out = [np.zeros((G, W, 4, 4, C), np.float64) for _ in words]
+        for ref in range(4):
+            for a in range(3):
+                for o, w in zip(out, words):
+                    o[:, :, ref, a + (a >= ref)] = w[:, :, ref, a]
+        return out, out[0] == 0
+
+    def _stat(self, value):
+        (n, s, ab, sq), empty = self._folded()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(empty, np.nan, value(n, s, ab, sq))
+
+    def counts(self):
+        return self._stat(lambda n, s, ab, sq: n)
+
+    def mean(self):
+        return self._stat(lambda n, s, ab, sq: s / n / float(1 << PROFILE_SCALE))
+
+    def mean_abs(self):
+        return self._stat(lambda n, s, ab, sq: ab / n / float(1 << PROFILE_SCALE))
+
+    def rms(self):
+        return self._stat(lambda n, s, ab, sq: np.sqrt(sq / n) / float(1 << PROFILE_SCALE))
+
+    def by_distance(self):
+        """float64 (n_groups, W, n_class): mean |delta| over reference bases and alternatives, weighted by their counts, per window column
+        (``offsets()`` gives the columns' signed distance from the focal base); NaN where a column received nothing."""
+        (n, _, ab, _), _ = self._folded()
+        n, ab = n.sum(axis=(2, 3)), ab.sum(axis=(2, 3))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n == 0, np.nan, ab / n / float(1 << PROFILE_SCALE))
+
+    # -- adding tables ------------------------------------------------------------------------------------------------------------------
+    def _require_same(self, other, what):
+        mine = (self.radius, self.model_type, self.n_class, self.n_groups)
+        theirs = (other.radius, other.model_type, other.n_class, other.n_groups)
+        if mine != theirs:
+            raise ValueError(f"{what}: profiles of (radius, model_type, n_class, n_groups) = {mine} and {theirs} do not add")
+
+    def require_continues(self, radius, model_type, n_class, n_groups, device):
+        """ValueError unless a run of this window, class count and device can add into this profile (``mutagenesis_profile(.., into=)``;
+        n_groups = 1, the default, stands for the profile's own)."""
+        if (self.radius, self.model_type, self.n_class) != (radius, model_type, n_class) or self.words.device != torch.device(device):
+            raise ValueError(f"into: a profile of (radius, model_type, n_class) = {(self.radius, self.model_type, self.n_class)} on "
+                             f"{self.words.device} cannot continue with {(radius, model_type, n_class)} on {device}")
+        if n_groups not in (1, self.n_groups):
+            raise ValueError(f"into: the profile has {self.n_groups} groups, n_groups = {n_groups} was asked for")
+
+    def merge(self, other):
+        """Adds `other`'s integers and status counters to this profile in place; returns self."""
+        if not isinstance(other, MutagenesisProfile):
+            raise TypeError("merge: a MutagenesisProfile is needed")
+        self._require_same(other, "merge")
+        theirs = other.words.to(self.words.device)
+        self.words[:-3] += theirs[:-3]                       # int64 adds wrap as the uint64 adds do
+        self.words[-3] |= theirs[-3]
+        self.words[-2:] += theirs[-2:]
+        return self
+
+    __iadd__ = merge
+
+    def all_reduce_(self, process_group=None):
+        """One SUM all-reduce of ``words`` (table and counters) viewed as int64 -- wraparound is the two's-complement sum, so the result is
+        the uint64 sum -- after which the status bits are those of the summed counters.  Returns self."""
+        import torch.distributed as dist
+        dist.all_reduce(self.words, op=dist.ReduceOp.SUM, group=process_group)
+        self.words[-3] = (self.words[-2] != 0).to(torch.int64) * PROFILE_NONFINITE + (self.words[-1] != 0).to(torch.int64) * PROFILE_RANGE
+        return self
+
+    def save(self, path):
+        """The integers and the metadata as one .npz (``load`` reads it back)."""
+        with open(path, "wb") as fh:
+            np.savez(fh, table=self.table_host(), status=self.status.cpu().numpy().view(np.uint64), radius=np.int64(self.radius),
+                     model_type=np.array(self.model_type), n_class=np.int64(self.n_class), n_groups=np.int64(self.n_groups))
+
+    @classmethod
+    def load(cls, path, device="cpu"):
+        with np.load(path, allow_pickle=False) as z:
+            prof = cls.zeros(int(z["radius"]), str(z["model_type"]), int(z["n_class"]), int(z["n_groups"]))
+            table, status = z["table"], z["status"]
+        if table.dtype != np.uint64 or table.shape != tuple(prof.table.shape) or status.dtype != np.uint64 or status.shape != (3,):
+            raise ValueError(f"{path}: not a mutagenesis profile (table {table.dtype} {table.shape}, status {status.dtype} {status.shape})")
+        prof.words[:-3] = torch.from_numpy(table.view(np.int64).reshape(-1))
+        prof.words[-3:] = torch.from_numpy(status.view(np.int64))
+        prof.words = prof.words.to(device)
+        return prof
+
+
+def mutagenesis_profile(model, genome, pos, strand, groups=None, n_groups=1, local_radius=None, local_order=3, chunk_windows=1 << 17,
+                        distal_radius=None, into=None, timings=None):
+    """The saturation-mutagenesis maps of the sites reduced in flight into a ``MutagenesisProfile``: the chunk loop of
+    ``saturation_mutagenesis`` (same models, same refusals, same `timings`) with ``mural_mutagenesis_profile_window`` in the place of the
+    reduce, so no map is written.  `groups`: int32 group id per site (device tensor, or anything ``torch.as_tensor`` takes), None for one
+    group; a site whose id lies outside [0, n_groups) adds nothing.  `into` continues an existing profile (its n_groups holds; shapes and
+    model type must match, ValueError otherwise) and is returned.  For the SNV models the table equals, bit for bit, the twin applied to
+    the map's ``delta``, and does not depend on `chunk_windows`, on the order of the sites or on how they are split over calls; a
+    ``UNet_Small``'s is reproducible per `chunk_windows` only, as its map is."""
+    out = {}
+
+    def begin(ref_logp, ref_symbols, pos, strand, R, model_type):
+        n, n_class, dev = pos.shape[0], ref_logp.shape[1], pos.device
+        if n > PROFILE_MAX_SITES:
+            raise ValueError(f"mutagenesis_profile: {n} sites in one call; at most 2^24 are taken, because a cell's integer sums are sized "
+                             "for 2^24 terms (|q| < 2^38 each): split the sites over calls joined by into=")
+        if into is not None:
+            if not isinstance(into, MutagenesisProfile):
+                raise TypeError("into must be a MutagenesisProfile")
+            into.require_continues(R, model_type, n_class, n_groups, dev)
+            prof = into
+        else:
+            prof = MutagenesisProfile.zeros(R, model_type, n_class, n_groups, dev)
+        group = None
+        if groups is not None:
+            group = torch.as_tensor(groups).to(dev)
+            if group.shape != pos.shape or group.dtype.is_floating_point:
+                raise ValueError("groups must hold one integer id per site")
+            if group.dtype != torch.int32:             # ids that int32 cannot hold are outside every [0, n_groups)
+                group = torch.where((group < 0) | (group >= prof.n_groups), torch.full_like(group, -1), group).to(torch.int32)
+            group = group.contiguous()
+        out["profile"] = prof
+        table, status = prof.table, prof.status
+        lib, W = _lib.lib(), prof.width
+
+        def reduce(var, first, m, stream):
+            _lib.check(lib.mural_mutagenesis_profile_window(ref_logp.data_ptr(), var.data_ptr(), ref_symbols.data_ptr(),
+                                                            None if group is None else group.data_ptr(), n, W, n_class, prof.n_groups,
+                                                            first, m, table.data_ptr(), status.data_ptr(), stream))
+        return reduce
+
+    _mutagenesis_chunks(model, genome, pos, strand, local_radius, local_order, chunk_windows, distal_radius, timings, begin)
+    return out["profile"]
 
 
 def footprint_offsets(radius, model_type="snv", device=None):
