@@ -12,15 +12,15 @@
 //
 // mural_simulate_annot_rows, per call:
 //   * check kernel, a thread per row: the status bits (a bad probability, a negative start, a start below the row before it);
-//   * range and scan kernels: the pieces' rows cut into chunks of at most SIM_CHUNK_ROWS rows (row_chunks.h);
+//   * the plan (row_chunks.h: plan_row_chunks): the pieces' rows cut into chunks of at most SIM_CHUNK_ROWS rows;
 //   * draw kernel, a fixed grid of SIM_GRID_WAVES waves striding over the units (chunk, block of 64 replicates): the wave finds the
 //     chunk's piece, walks the chunk 64 rows at a time (a row per lane, four replicates per Philox call), counts the hits of a (class,
 //     replicate) over the 64 rows by ballot + popcount and keeps the count of replicate r0 + l in lane l; after the chunk ONE
 //     wave-instruction per class adds the 64 counts -- 256 contiguous bytes -- with 32-bit INTEGER atomics.
 // mural_simulate_rows: tile counts of the non-zero labels of one replicate (a wave per 64 rows), their exclusive scan, and a second pass
 // that recomputes the labels and writes each hit at prefix + its rank among the tile's hits: stable in row order.
-// No floating-point atomics, no synchronisation, no read-back.  The Philox round, a row's cum and the last counter word live in
-// simulate_draw.h, with the loop bounds; csrc/simulate_conseq.hip includes it as well.
+// No floating-point atomics, no synchronisation, no read-back.  The check kernel, the Philox round, a row's cum and the last counter
+// word live in simulate_draw.h, with the loop bounds; the per-transcript simulations include it as well.
 #include "common.h"
 #include "kmer_key.h"
 #include "row_chunks.h"
@@ -28,27 +28,6 @@
 
 namespace mural {
 namespace {
-
-template <typename T>
-__global__ __launch_bounds__(SIM_THREADS) void simulate_check_kernel(SimRows A, int64_t n, int check_order) {
-  const int64_t i = (int64_t)blockIdx.x * SIM_THREADS + threadIdx.x;
-  int32_t bad = 0;
-  if (i < n) {
-    u64 cum[SIM_MAX_CLASS - 1];
-    bad = row_cum<T>(A, i, cum);
-    if (check_order && i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
-  }
-  if (bad) atomicOr(A.status, bad);
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total (also to *total_out where given): one workgroup
-__global__ __launch_bounds__(SIM_SCAN_THREADS) void simulate_scan_kernel(int64_t* __restrict__ v, int64_t m, int64_t* __restrict__ total_out) {
-  const int64_t total = run_excl_scan<SIM_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
-  if (threadIdx.x == 0) {
-    v[m] = total;
-    if (total_out) *total_out = total;
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(SIM_THREADS) void simulate_draw_kernel(SimRows A, const int32_t* __restrict__ group, int64_t n_pieces,
@@ -154,13 +133,6 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_write_kernel(SimRows A, 
   }
 }
 
-int fill_rows(SimRows& A, const void* prob, int64_t prob_stride, const int64_t* start, const uint8_t* strand, int32_t n_class,
-              uint32_t chrom_key, uint64_t seed, int32_t* status) {
-  A.prob = prob, A.start = start, A.strand = strand, A.prob_stride = prob_stride, A.n_class = n_class;
-  A.chrom_key = chrom_key, A.seed_lo = (uint32_t)seed, A.seed_hi = (uint32_t)(seed >> 32), A.status = status;
-  return MURAL_OK;
-}
-
 int64_t tiles_of(int64_t n) { return (n + 63) / 64; }
 
 }  // namespace
@@ -186,11 +158,9 @@ extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* 
   if (s->n == 0) return MURAL_OK;
   MURAL_REQUIRE(s->prob && s->start && s->status, "simulate_annot_rows: NULL argument");
   MURAL_REQUIRE(s->prob_stride >= s->n_class, "simulate_annot_rows: prob_stride < n_class");
-  SimRows A{};
-  fill_rows(A, s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
+  const SimRows A = sim_rows(s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(SIM_THREADS);
-  const dim3 row_grid((unsigned)((s->n + SIM_THREADS - 1) / SIM_THREADS));
   if (s->n_pieces > 0) {      // (everything is checked before the first launch)
     MURAL_REQUIRE(s->piece_b0 && s->piece_b1 && s->piece_group && s->n_groups >= 1 && s->table,
                   "simulate_annot_rows: pieces without groups or table");
@@ -198,20 +168,13 @@ extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* 
                                        mural_simulate_annot_workspace_bytes(s->n_pieces)))
       return rc;
   }
-  if (s->prob_f64)
-    hipLaunchKernelGGL(simulate_check_kernel<double>, row_grid, block, 0, st, A, s->n, 1);
-  else
-    hipLaunchKernelGGL(simulate_check_kernel<float>, row_grid, block, 0, st, A, s->n, 1);
-  MURAL_HIP_CHECK(hipGetLastError());
+  if (const int rc = launch_simulate_check(st, A, s->n, s->prob_f64, 1)) return rc;
   if (s->n_pieces == 0) return MURAL_OK;
   WsArena ws(ws_ptr);
-  const RowChunks w = carve_row_chunks(ws, s->n_pieces);
-  const dim3 piece_grid((unsigned)((s->n_pieces + SIM_WAVES - 1) / SIM_WAVES));
-  hipLaunchKernelGGL(row_chunk_range_kernel<SIM_THREADS>, piece_grid, block, 0, st, s->start, s->n, s->piece_b0, s->piece_b1, s->piece_group,
-                     s->n_groups, s->n_pieces, SIM_CHUNK_ROWS, w);
-  MURAL_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(simulate_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, w.pre, s->n_pieces, (int64_t*)nullptr);
-  MURAL_HIP_CHECK(hipGetLastError());
+  RowChunks w;
+  if (const int rc = plan_row_chunks<SIM_THREADS, SIM_SCAN_THREADS>(st, s->start, s->n, s->piece_b0, s->piece_b1, s->piece_group, s->n_groups,
+                                                                    s->n_pieces, 0, SIM_CHUNK_ROWS, ws, w))
+    return rc;
   const int64_t n_waves = row_chunk_grid_waves(s->n, SIM_CHUNK_ROWS, (s->n_rep + 63) / 64, s->n_pieces, SIM_GRID_WAVES, SIM_WAVES);
   const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES));
   if (s->prob_f64)
@@ -242,24 +205,20 @@ extern "C" int mural_simulate_rows(const MuralSimulateRows* s, void* ws_ptr, siz
   if (const int rc = check_workspace("simulate_rows", "mural_simulate_rows_workspace_bytes", ws_ptr, ws_bytes,
                                      mural_simulate_rows_workspace_bytes(s->n)))
     return rc;
-  SimRows A{};
-  fill_rows(A, s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
+  const SimRows A = sim_rows(s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
   const int64_t n_tiles = tiles_of(s->n);
   WsArena ws(ws_ptr);
   int64_t* pre = ws.as<int64_t>((size_t)n_tiles + 1);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(SIM_THREADS);
-  const dim3 row_grid((unsigned)((s->n + SIM_THREADS - 1) / SIM_THREADS));
   const dim3 tile_grid((unsigned)((n_tiles + SIM_WAVES - 1) / SIM_WAVES));
-  if (s->prob_f64) {
-    hipLaunchKernelGGL(simulate_check_kernel<double>, row_grid, block, 0, st, A, s->n, 0);
+  if (const int rc = launch_simulate_check(st, A, s->n, s->prob_f64, 0)) return rc;      // (a list's rows need not ascend)
+  if (s->prob_f64)
     hipLaunchKernelGGL(simulate_count_kernel<double>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre);
-  } else {
-    hipLaunchKernelGGL(simulate_check_kernel<float>, row_grid, block, 0, st, A, s->n, 0);
+  else
     hipLaunchKernelGGL(simulate_count_kernel<float>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre);
-  }
   MURAL_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(simulate_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, pre, n_tiles, s->count);
+  hipLaunchKernelGGL(excl_scan_kernel<SIM_SCAN_THREADS>, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, pre, n_tiles, s->count);
   MURAL_HIP_CHECK(hipGetLastError());
   if (s->prob_f64)
     hipLaunchKernelGGL(simulate_write_kernel<double>, tile_grid, block, 0, st, A, s->n, s->replicate, n_tiles, pre, s->out_start, s->out_strand,

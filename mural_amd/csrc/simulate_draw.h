@@ -1,6 +1,7 @@
-// The stateless draw of the simulation kernels, shared by csrc/simulate.hip (counts per named interval set, mutation lists) and
-// csrc/simulate_conseq.hip (counts per transcript and consequence) so that their draws cannot drift: the Philox4x32-10 round, a row's
-// cumulative class bounds and the last counter word, with the loop bounds both files plan their launches on.
+// The stateless draw of the simulation kernels, shared by csrc/simulate.hip (counts per named interval set, mutation lists),
+// csrc/simulate_conseq.hip, csrc/simulate_txstruct.hip and csrc/simulate_txindel.hip (counts per transcript and bin) so that their draws
+// cannot drift: the rows' argument block, the check kernel (the status bits of every row), the Philox4x32-10 round, a row's cumulative
+// class bounds and the last counter word, with the loop bounds all four files plan their launches on.
 // summaries.simulate_rows_host is the specification; DESIGN.md section 3.20.
 #pragma once
 #include "common.h"
@@ -26,6 +27,14 @@ struct SimRows {
   uint32_t chrom_key, seed_lo, seed_hi;
   int32_t* status;
 };
+
+inline SimRows sim_rows(const void* prob, int64_t prob_stride, const int64_t* start, const uint8_t* strand, int32_t n_class,
+                        uint32_t chrom_key, uint64_t seed, int32_t* status) {
+  SimRows A{};
+  A.prob = prob, A.start = start, A.strand = strand, A.prob_stride = prob_stride, A.n_class = n_class;
+  A.chrom_key = chrom_key, A.seed_lo = (uint32_t)seed, A.seed_hi = (uint32_t)(seed >> 32), A.status = status;
+  return A;
+}
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t (&out)[4]) {
@@ -68,6 +77,30 @@ __device__ __forceinline__ int32_t row_cum(const SimRows& A, int64_t i, u64 (&cu
     for (int c = 0; c < SIM_MAX_CLASS - 1; ++c) cum[c] = 0;
   }
   return bad;
+}
+
+// a thread per row: the status bits (a bad probability, a negative start and, with check_order, a start below the row before it)
+template <typename T>
+__global__ __launch_bounds__(SIM_THREADS) void simulate_check_kernel(SimRows A, int64_t n, int check_order) {
+  const int64_t i = (int64_t)blockIdx.x * SIM_THREADS + threadIdx.x;
+  int32_t bad = 0;
+  if (i < n) {
+    u64 cum[SIM_MAX_CLASS - 1];
+    bad = row_cum<T>(A, i, cum);
+    if (check_order && i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
+  }
+  if (bad) atomicOr(A.status, bad);
+}
+
+// the check kernel on `st`; MURAL_OK or the error code of the launch
+inline int launch_simulate_check(hipStream_t st, const SimRows& A, int64_t n, bool prob_f64, int check_order) {
+  const dim3 grid((unsigned)((n + SIM_THREADS - 1) / SIM_THREADS)), block(SIM_THREADS);
+  if (prob_f64)
+    hipLaunchKernelGGL(simulate_check_kernel<double>, grid, block, 0, st, A, n, check_order);
+  else
+    hipLaunchKernelGGL(simulate_check_kernel<float>, grid, block, 0, st, A, n, check_order);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
 }
 
 __device__ __forceinline__ uint32_t last_counter_word(const SimRows& A, int64_t i, uint32_t block) {

@@ -7,9 +7,9 @@
 //
 // The loop bounds are csrc/simulate.hip's: SIM_CHUNK_ROWS rows a chunk, SIM_GRID_WAVES waves a grid, SIM_SCAN_THREADS threads in the
 // scan (mural_simulate_chunk_rows(), mural_simulate_grid_waves(), mural_simulate_scan_threads()).  Per call:
-//   * check kernel, a thread per row: the simulation's status bits (a bad probability, a negative start, a start below the row before);
-//   * range and scan kernels: the rows of an item are those whose HOME BASE lies in it (row_chunk_range_shift_kernel), cut into chunks
-//     of at most SIM_CHUNK_ROWS rows (row_chunks.h);
+//   * check kernel (simulate_draw.h), a thread per row: the simulation's status bits;
+//   * the plan (row_chunks.h: plan_row_chunks with a shift): the rows of an item are those whose HOME BASE lies in it, cut into chunks
+//     of at most SIM_CHUNK_ROWS rows;
 //   * draw kernel, a grid of at most SIM_GRID_WAVES waves striding over the units (chunk of a home item, group of up to STI_UNIT_BLOCKS
 //     blocks of 64 replicates).  The home item and an insertion's second item are wave-uniform and loaded once per unit.  A wave first
 //     walks its chunk 64 rows at a time, a row per lane, and forms the bin of every class of the row ONCE through txindel_bins.h -- a
@@ -63,24 +63,6 @@ struct SimTxindelArgs {      // (the fields txindel_bins.h reads, under its name
   uint32_t cls[SIM_MAX_CLASS];      // class c: lo | frame mode << 8 (txindel_class_word)
   uint32_t* table;
 };
-
-template <typename T>
-__global__ __launch_bounds__(SIM_THREADS) void simulate_txindel_check_kernel(SimRows A, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * SIM_THREADS + threadIdx.x;
-  int32_t bad = 0;
-  if (i < n) {
-    u64 cum[SIM_MAX_CLASS - 1];
-    bad = row_cum<T>(A, i, cum);
-    if (i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
-  }
-  if (bad) atomicOr(A.status, bad);
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup
-__global__ __launch_bounds__(SIM_SCAN_THREADS) void simulate_txindel_scan_kernel(int64_t* __restrict__ v, int64_t m) {
-  const int64_t total = run_excl_scan<SIM_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
-  if (threadIdx.x == 0) v[m] = total;
-}
 
 template <typename T>
 __global__ __launch_bounds__(SIM_THREADS) void simulate_txindel_draw_kernel(SimTxindelArgs A, const int64_t* __restrict__ row0,
@@ -227,8 +209,7 @@ extern "C" int mural_simulate_txindel_rows(const MuralSimulateTxindelRows* s, vo
   MURAL_REQUIRE(s->prob && s->start && s->status, "simulate_txindel_rows: NULL argument");
   MURAL_REQUIRE(s->prob_stride >= s->n_class, "simulate_txindel_rows: prob_stride < n_class");
   SimTxindelArgs A{};
-  A.rows.prob = s->prob, A.rows.start = s->start, A.rows.strand = s->strand, A.rows.prob_stride = s->prob_stride, A.rows.n_class = s->n_class;
-  A.rows.chrom_key = s->chrom_key, A.rows.seed_lo = (uint32_t)s->seed, A.rows.seed_hi = (uint32_t)(s->seed >> 32), A.rows.status = s->status;
+  A.rows = sim_rows(s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
   if (s->n_features > 0) {      // (everything is checked before the first launch)
     MURAL_REQUIRE(s->feat_b0 && s->feat_b1 && s->feat_tx && s->feat_kind && s->feat_seg && s->feat_prev && s->feat_next && s->tx_strand &&
                       s->tx_cds_len && s->n_transcripts >= 1 && s->table,
@@ -240,13 +221,7 @@ extern "C" int mural_simulate_txindel_rows(const MuralSimulateTxindelRows* s, vo
       return rc;
   }
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 block(SIM_THREADS);
-  const dim3 row_grid((unsigned)((s->n + SIM_THREADS - 1) / SIM_THREADS));
-  if (s->prob_f64)
-    hipLaunchKernelGGL(simulate_txindel_check_kernel<double>, row_grid, block, 0, st, A.rows, s->n);
-  else
-    hipLaunchKernelGGL(simulate_txindel_check_kernel<float>, row_grid, block, 0, st, A.rows, s->n);
-  MURAL_HIP_CHECK(hipGetLastError());
+  if (const int rc = launch_simulate_check(st, A.rows, s->n, s->prob_f64, 1)) return rc;
   if (s->n_features == 0) return MURAL_OK;
   A.n = s->n, A.chrom_len = s->chrom_length, A.n_tx = s->n_transcripts, A.n_rep = s->n_rep, A.kind = s->kind, A.off = s->breakpoint_offset;
   A.seg_b0 = s->seg_b0, A.seg_b1 = s->seg_b1, A.seg_cds0 = s->seg_cds0, A.seg_tx = s->seg_tx, A.n_seg = s->n_segments;
@@ -256,17 +231,14 @@ extern "C" int mural_simulate_txindel_rows(const MuralSimulateTxindelRows* s, vo
   for (int c = 1; c < s->n_class; ++c) A.cls[c] = txindel_class_word(s->class_len[c][0], s->class_len[c][1]);
   A.table = s->table;
   WsArena ws(ws_ptr);
-  const RowChunks w = carve_row_chunks(ws, s->n_features);
-  const dim3 feat_grid((unsigned)((s->n_features + SIM_WAVES - 1) / SIM_WAVES));
+  RowChunks w;
   const int64_t home_shift = A.off - (A.kind == TI_DELETION_START ? 0 : 1);
-  hipLaunchKernelGGL(row_chunk_range_shift_kernel<SIM_THREADS>, feat_grid, block, 0, st, s->start, s->n, A.feat_b0, A.feat_b1, A.feat_tx,
-                     A.n_tx, A.n_feat, home_shift, SIM_CHUNK_ROWS, w);
-  MURAL_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(simulate_txindel_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, w.pre, s->n_features);
-  MURAL_HIP_CHECK(hipGetLastError());
+  if (const int rc = plan_row_chunks<SIM_THREADS, SIM_SCAN_THREADS>(st, s->start, s->n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx, A.n_feat,
+                                                                    home_shift, SIM_CHUNK_ROWS, ws, w))
+    return rc;
   const int64_t n_rg = ((s->n_rep + 63) / 64 + STI_UNIT_BLOCKS - 1) / STI_UNIT_BLOCKS;
   const int64_t n_waves = row_chunk_grid_waves(s->n, SIM_CHUNK_ROWS, n_rg, s->n_features, SIM_GRID_WAVES, SIM_WAVES);
-  const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES));
+  const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES)), block(SIM_THREADS);
   if (s->prob_f64)
     hipLaunchKernelGGL(simulate_txindel_draw_kernel<double>, draw_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
   else

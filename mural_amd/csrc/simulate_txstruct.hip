@@ -7,8 +7,8 @@
 //
 // The loop bounds are csrc/simulate.hip's: SIM_CHUNK_ROWS rows a chunk, SIM_GRID_WAVES waves a grid, SIM_SCAN_THREADS threads in the
 // scan (mural_simulate_chunk_rows(), mural_simulate_grid_waves(), mural_simulate_scan_threads()).  Per call:
-//   * check kernel, a thread per row: the simulation's status bits (a bad probability, a negative start, a start below the row before);
-//   * range and scan kernels: the items' rows cut into chunks of at most SIM_CHUNK_ROWS rows (row_chunks.h);
+//   * check kernel (simulate_draw.h), a thread per row: the simulation's status bits;
+//   * the plan (row_chunks.h: plan_row_chunks): the items' rows cut into chunks of at most SIM_CHUNK_ROWS rows;
 //   * draw kernel, a grid of at most SIM_GRID_WAVES waves striding over the units (chunk of an item, group of up to STX_UNIT_BLOCKS
 //     blocks of 64 replicates).  The rows of one item fall in at most three bins (an intron: donor, acceptor, rest; a CDS part: start
 //     lost, cds; every other kind: one), so a wave first walks its chunk 64 rows at a time, a row per lane, and forms each row's three
@@ -41,49 +41,18 @@ constexpr int STX_SLOTS = 3;                               // the bins one item'
 constexpr int STX_KIND_CODING_INTRON = 3, STX_KIND_INTRON = 4, STX_KIND_CDS = 5;
 constexpr uint32_t STX_DEAD = STX_SLOTS | STX_SLOTS << 2 | STX_SLOTS << 4;      // the packed slots of a lane without a row
 
-struct SimTxstructArgs {      // (the fields conseq_bins.h reads, under its names)
+struct SimTxstructArgs {
   SimRows rows;
-  MuralGenome g;
-  const uint8_t* strand;      // (= rows.strand)
-  int64_t n;
-  int32_t n_tx, n_rep;
-  const int64_t* seg_b0;
-  const int64_t* seg_b1;
-  const int64_t* seg_cds0;
-  const int32_t* seg_tx;
-  const int32_t* seg_prev;
-  const int32_t* seg_next;
-  int64_t n_seg;
+  TxSegments tx;
+  int32_t n_rep;
   const int64_t* feat_b0;
   const int64_t* feat_b1;
   const int32_t* feat_tx;
   const uint8_t* feat_kind;
   const int32_t* feat_seg;
   int64_t n_feat;
-  const uint8_t* tx_strand;
-  const int64_t* tx_cds_len;
-  uint32_t aa_w[16];          // the 64 amino-acid bytes, four to a word
-  uint32_t alt_packed;        // alt_order[r][j] in bits [2 (3 r + j), +2)
   uint32_t* table;
 };
-
-template <typename T>
-__global__ __launch_bounds__(SIM_THREADS) void simulate_txstruct_check_kernel(SimRows A, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * SIM_THREADS + threadIdx.x;
-  int32_t bad = 0;
-  if (i < n) {
-    u64 cum[SIM_MAX_CLASS - 1];
-    bad = row_cum<T>(A, i, cum);
-    if (i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
-  }
-  if (bad) atomicOr(A.status, bad);
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup
-__global__ __launch_bounds__(SIM_SCAN_THREADS) void simulate_txstruct_scan_kernel(int64_t* __restrict__ v, int64_t m) {
-  const int64_t total = run_excl_scan<SIM_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
-  if (threadIdx.x == 0) v[m] = total;
-}
 
 template <typename T>
 __global__ __launch_bounds__(SIM_THREADS) void simulate_txstruct_draw_kernel(SimTxstructArgs A, const int64_t* __restrict__ row0,
@@ -91,11 +60,7 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txstruct_draw_kernel(Sim
                                                                              const int64_t* __restrict__ pre, int64_t n_waves) {
   __shared__ uint32_t aa_words[16];
   __shared__ uint16_t packed_slots[SIM_WAVES][STX_TILES][64];
-#pragma unroll
-  for (int j = 0; j < 16; ++j)      // (constant indices: the words stay scalar arguments)
-    if (threadIdx.x == j) aa_words[j] = A.aa_w[j];
-  __syncthreads();
-  const uint8_t* aa = reinterpret_cast<const uint8_t*>(aa_words);
+  const uint8_t* aa = stage_aa(A.tx, aa_words);
   const int lane = threadIdx.x & 63;
   uint16_t (&mine)[STX_TILES][64] = packed_slots[threadIdx.x >> 6];      // (a lane reads only what it wrote itself: no barrier)
   const int64_t wave = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
@@ -112,7 +77,7 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txstruct_draw_kernel(Sim
     const int64_t b0 = A.feat_b0[f], b1 = A.feat_b1[f];
     const int32_t tx = A.feat_tx[f];      // (0 <= tx < n_tx: the range kernel gave other items no chunk)
     const int kind = A.feat_kind[f];
-    const bool minus = A.tx_strand[tx] != 0;
+    const bool minus = A.tx.tx_strand[tx] != 0;
     // the bins of the item's slots; -1: the slot is not used
     int slot_bin[STX_SLOTS] = {-1, -1, -1};
     int64_t seg = 0, cds0 = 0, cds_len = 0;
@@ -124,9 +89,9 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txstruct_draw_kernel(Sim
       slot_bin[0] = 5, slot_bin[2] = 6;
     } else if (kind == STX_KIND_CDS) {
       seg = A.feat_seg[f];
-      if (seg < 0 || seg >= A.n_seg) continue;      // (a CDS item without its segment: skipped, as an item without its transcript)
-      if (A.seg_b0[seg] != b0 || A.seg_b1[seg] != b1 || A.seg_tx[seg] != tx) continue;
-      cds0 = A.seg_cds0[seg], cds_len = A.tx_cds_len[tx];
+      if (seg < 0 || seg >= A.tx.n_seg) continue;      // (a CDS item without its segment: skipped, as an item without its transcript)
+      if (A.tx.seg_b0[seg] != b0 || A.tx.seg_b1[seg] != b1 || A.tx.seg_tx[seg] != tx) continue;
+      cds0 = A.tx.seg_cds0[seg], cds_len = A.tx.tx_cds_len[tx];
       slot_bin[0] = 7, slot_bin[1] = 8;
     } else {
       continue;      // (an unknown kind)
@@ -159,7 +124,7 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txstruct_draw_kernel(Sim
         const int64_t x = cds0 + (minus ? b1 - 1 - q : q - b0);
         if (live && x < 3) {
           int bins[3];
-          conseq_row_bins(A, aa, seg, tx, minus, cds_len, b0, b1, cds0, i, q, bins);
+          conseq_row_bins(A.tx, A.rows.strand, aa, seg, tx, minus, cds_len, b0, b1, cds0, i, q, bins);
           word = 0;
 #pragma unroll
           for (int c = 0; c < 3; ++c) word |= ((bins[c] >= 1 && bins[c] <= 3) ? 0u : 1u) << (2 * c);      // aa_alt != aa_ref on a resolved codon
@@ -232,18 +197,14 @@ extern "C" int mural_simulate_txstruct_rows(const MuralSimulateTxstructRows* s, 
   MURAL_REQUIRE(s->n_features >= 0 && s->n_features <= STX_MAX_FEATURES, "simulate_txstruct_rows: 0 <= n_features <= 2^22 required");
   MURAL_REQUIRE(s->n_segments >= 0 && s->n_segments <= STX_MAX_SEGMENTS, "simulate_txstruct_rows: 0 <= n_segments <= 2^22 required");
   MURAL_REQUIRE(s->n_transcripts >= 0, "simulate_txstruct_rows: n_transcripts < 0");
-  uint32_t alt_packed = 0;
-  int bad_alt = 0;
-  MURAL_REQUIRE(conseq_pack_alt_order(s->alt_order, alt_packed, bad_alt),
-                "simulate_txstruct_rows: alt_order[%d] must name the three other bases once each", bad_alt);
+  SimTxstructArgs A{};
+  if (const int rc = fill_tx_segments("simulate_txstruct_rows", s, false, A.tx)) return rc;      // (alt_order alone)
   if (s->n == 0) return MURAL_OK;
   MURAL_REQUIRE(s->prob && s->start && s->status, "simulate_txstruct_rows: NULL argument");
   MURAL_REQUIRE(s->prob_stride >= 4, "simulate_txstruct_rows: prob_stride < n_class");
-  SimTxstructArgs A{};
-  A.rows.prob = s->prob, A.rows.start = s->start, A.rows.strand = s->strand, A.rows.prob_stride = s->prob_stride, A.rows.n_class = 4;
-  A.rows.chrom_key = s->chrom_key, A.rows.seed_lo = (uint32_t)s->seed, A.rows.seed_hi = (uint32_t)(s->seed >> 32), A.rows.status = s->status;
+  A.rows = sim_rows(s->prob, s->prob_stride, s->start, s->strand, 4, s->chrom_key, s->seed, s->status);
   if (s->n_features > 0) {      // (everything is checked before the first launch)
-    MURAL_REQUIRE(s->genome && s->genome->packed2 && s->genome->nmask && s->genome->length >= 0, "simulate_txstruct_rows: empty genome");
+    if (const int rc = fill_tx_segments("simulate_txstruct_rows", s, true, A.tx)) return rc;      // (the genome, and the fill)
     MURAL_REQUIRE(s->feat_b0 && s->feat_b1 && s->feat_tx && s->feat_kind && s->feat_seg && s->tx_strand && s->tx_cds_len &&
                       s->n_transcripts >= 1 && s->table,
                   "simulate_txstruct_rows: items without transcripts or table");
@@ -254,34 +215,19 @@ extern "C" int mural_simulate_txstruct_rows(const MuralSimulateTxstructRows* s, 
       return rc;
   }
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 block(SIM_THREADS);
-  const dim3 row_grid((unsigned)((s->n + SIM_THREADS - 1) / SIM_THREADS));
-  if (s->prob_f64)
-    hipLaunchKernelGGL(simulate_txstruct_check_kernel<double>, row_grid, block, 0, st, A.rows, s->n);
-  else
-    hipLaunchKernelGGL(simulate_txstruct_check_kernel<float>, row_grid, block, 0, st, A.rows, s->n);
-  MURAL_HIP_CHECK(hipGetLastError());
+  if (const int rc = launch_simulate_check(st, A.rows, s->n, s->prob_f64, 1)) return rc;
   if (s->n_features == 0) return MURAL_OK;
-  A.g = *s->genome;
-  A.strand = s->strand, A.n = s->n, A.n_tx = s->n_transcripts, A.n_rep = s->n_rep;
-  A.seg_b0 = s->seg_b0, A.seg_b1 = s->seg_b1, A.seg_cds0 = s->seg_cds0, A.seg_tx = s->seg_tx, A.seg_prev = s->seg_prev, A.seg_next = s->seg_next;
-  A.n_seg = s->n_segments;
+  A.n_rep = s->n_rep, A.table = s->table;
   A.feat_b0 = s->feat_b0, A.feat_b1 = s->feat_b1, A.feat_tx = s->feat_tx, A.feat_kind = s->feat_kind, A.feat_seg = s->feat_seg;
-  A.n_feat = s->n_features, A.tx_strand = s->tx_strand, A.tx_cds_len = s->tx_cds_len;
-  for (int j = 0; j < 64; ++j) A.aa_w[j >> 2] |= (uint32_t)s->aa[j] << (8 * (j & 3));
-  A.alt_packed = alt_packed;
-  A.table = s->table;
+  A.n_feat = s->n_features;
   WsArena ws(ws_ptr);
-  const RowChunks w = carve_row_chunks(ws, s->n_features);
-  const dim3 feat_grid((unsigned)((s->n_features + SIM_WAVES - 1) / SIM_WAVES));
-  hipLaunchKernelGGL(row_chunk_range_kernel<SIM_THREADS>, feat_grid, block, 0, st, s->start, s->n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx,
-                     A.n_feat, SIM_CHUNK_ROWS, w);
-  MURAL_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(simulate_txstruct_scan_kernel, dim3(1), dim3(SIM_SCAN_THREADS), 0, st, w.pre, s->n_features);
-  MURAL_HIP_CHECK(hipGetLastError());
+  RowChunks w;
+  if (const int rc = plan_row_chunks<SIM_THREADS, SIM_SCAN_THREADS>(st, s->start, s->n, s->feat_b0, s->feat_b1, s->feat_tx, s->n_transcripts,
+                                                                    s->n_features, 0, SIM_CHUNK_ROWS, ws, w))
+    return rc;
   const int64_t n_rg = ((s->n_rep + 63) / 64 + STX_UNIT_BLOCKS - 1) / STX_UNIT_BLOCKS;
   const int64_t n_waves = row_chunk_grid_waves(s->n, SIM_CHUNK_ROWS, n_rg, s->n_features, SIM_GRID_WAVES, SIM_WAVES);
-  const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES));
+  const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES)), block(SIM_THREADS);
   if (s->prob_f64)
     hipLaunchKernelGGL(simulate_txstruct_draw_kernel<double>, draw_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
   else

@@ -1,6 +1,8 @@
 // The row checks, the two-limb quantisation and the limb fold of the integer-sum summaries, shared by csrc/summary_kmer.hip (k-mer and
-// motif tables), csrc/summary_annot.hip (annotation tables) and csrc/summary_conseq.hip (consequence tables) so that their cells cannot
-// drift: q = rne(p * 2^71) carried as hi = floor(p * 2^31) and lo = rint((p * 2^31 - hi) * 2^40), each step exact in float64.
+// motif tables), csrc/summary_annot.hip (annotation tables) and the per-transcript tables (csrc/summary_conseq.hip,
+// csrc/summary_txstruct.hip, csrc/summary_txindel.hip) so that their cells cannot drift: q = rne(p * 2^71) carried as hi = floor(p * 2^31)
+// and lo = rint((p * 2^31 - hi) * 2^40), each step exact in float64.  The SNV rows of the consequence and structure tables (SnvRows),
+// their row function and their check kernel are here as well.
 // (csrc/summary_calib.hip carries 46-bit limbs at irregular cell positions: it has a quantisation, a fold and bounds of its own.)
 #pragma once
 #include "common.h"
@@ -41,6 +43,66 @@ __device__ __forceinline__ int32_t quantise_row(const T* __restrict__ prob, int 
   return bad_row;
 }
 
+// The SNV rows (4 classes) of a per-transcript table, as its kernels read them.
+struct SnvRows {
+  const void* prob;
+  const int64_t* start;
+  const uint8_t* strand;      // or nullptr: all '+'
+  const void* label;
+  int64_t prob_stride, n;
+  int32_t label_kind;
+  int32_t* status;
+};
+
+// X from the row fields of a public argument struct
+template <typename Pub>
+inline SnvRows snv_rows(const Pub* s) {
+  SnvRows X{};
+  X.prob = s->prob, X.start = s->start, X.strand = s->strand, X.label = s->label, X.prob_stride = s->prob_stride, X.n = s->n;
+  X.label_kind = s->label_kind, X.status = s->status;
+  return X;
+}
+
+// The checks of SNV row i (status bits, 0 if it counts) and the limbs of its classes 1 .. 3; class 0's probability is not read.
+template <typename T>
+__device__ __forceinline__ int32_t snv_row(const SnvRows& A, int64_t i, int& lab, u64 (&hi)[3], u64 (&lo)[3]) {
+  const T* __restrict__ p_row = static_cast<const T*>(A.prob) + i * A.prob_stride;
+  lab = load_label(A.label, A.label_kind, i);
+  int32_t bad = 0;
+  if (A.start[i] < 0) bad |= SM_BAD_START;
+  if (lab < 0 || lab >= 4) bad |= SM_BAD_LABEL;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    if (!quantise_prob((double)p_row[c + 1], hi[c], lo[c])) bad |= SM_BAD_PROB;      // (float -> double is exact)
+  return bad;
+}
+
+// a thread per SNV row: the status bits, a start below the row before it among them
+template <typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void snv_check_kernel(SnvRows A) {
+  const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  int32_t bad = 0;
+  if (i < A.n) {
+    int lab;
+    u64 hi[3], lo[3];
+    bad = snv_row<T>(A, i, lab, hi, lo);
+    if (i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
+  }
+  if (bad) atomicOr(A.status, bad);
+}
+
+// the check kernel on `st`; MURAL_OK or the error code of the launch
+template <int THREADS>
+inline int launch_snv_check(hipStream_t st, const SnvRows& A, bool prob_f64) {
+  const dim3 grid((unsigned)((A.n + THREADS - 1) / THREADS)), block(THREADS);
+  if (prob_f64)
+    hipLaunchKernelGGL((snv_check_kernel<double, THREADS>), grid, block, 0, st, A);
+  else
+    hipLaunchKernelGGL((snv_check_kernel<float, THREADS>), grid, block, 0, st, A);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
+}
+
 // The fold: the overflow of a sum of lo limbs goes into the sum of hi limbs; the pair's value hi * 2^40 + lo does not change.
 // THE LIMB BOUND.  A lo limb is at most 2^40 (2^40 itself where the fraction rounds up: the pair's value stays right), and a folded
 // lo is below 2^40.  A TERM is a lo limb or a folded sum of lo limbs; unfolded sums count as the terms they hold.  A cell that takes at
@@ -72,6 +134,16 @@ __global__ __launch_bounds__(THREADS) void summary_fold_kernel(FoldTables F) {
     fold_limbs(hi, lo);
     cell[nc] = hi, cell[2 * nc] = lo;
   }
+}
+
+// the fold of a per-transcript table [n_cells][3][1] at the end of a call, on `st`; MURAL_OK or the error code of the launch
+template <int THREADS>
+inline int launch_cell_fold(hipStream_t st, u64* table, int64_t n_cells) {
+  FoldTables F{};
+  F.table[0] = table, F.n_groups[0] = n_cells, F.nc = 1;      // [transcript][bin][3] = [cell][3][1]
+  hipLaunchKernelGGL(summary_fold_kernel<THREADS>, dim3((unsigned)((n_cells + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, F);
+  MURAL_HIP_CHECK(hipGetLastError());
+  return MURAL_OK;
 }
 
 }  // namespace mural

@@ -9,8 +9,9 @@
 // The items are those of csrc/summary_txstruct.hip (tables.read_transcript_structure) with two link arrays, feat_prev / feat_next, the
 // same transcript's neighbouring items in genomic order (tables.structure_links).  The stages are those of csrc/summary_txstruct.hip:
 //   * check kernel, a thread per row: the status bits;
-//   * range and scan kernels (row_chunks.h): an item's rows are those whose HOME BASE -- start + breakpoint_offset - 1 for an insertion
-//     and a deletion end, start + breakpoint_offset for a deletion start -- lies in it, cut into chunks of at most TI_CHUNK_ROWS rows;
+//   * the plan (row_chunks.h: plan_row_chunks with a shift): an item's rows are those whose HOME BASE -- start + breakpoint_offset - 1
+//     for an insertion and a deletion end, start + breakpoint_offset for a deletion start -- lies in it, cut into chunks of at most
+//     TI_CHUNK_ROWS rows;
 //   * reduce kernel, a grid of at most TI_GRID_WAVES waves striding over the chunks, a row per lane.  An insertion looks at the home
 //     item and, on its last boundary, at the item behind it (wave-uniform: loaded once per chunk).  A deletion of class c removes L =
 //     lo(c) <= 64 bases: the lane walks from the home item over feat_next (deletion start) or feat_prev (deletion end) while the items
@@ -101,12 +102,6 @@ __global__ __launch_bounds__(TI_THREADS) void summary_txindel_check_kernel(Txind
     if (i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
   }
   if (bad) atomicOr(A.status, bad);
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup
-__global__ __launch_bounds__(TI_SCAN_THREADS) void summary_txindel_scan_kernel(int64_t* __restrict__ v, int64_t m) {
-  const int64_t total = run_excl_scan<TI_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
-  if (threadIdx.x == 0) v[m] = total;
 }
 
 template <typename T>
@@ -239,8 +234,6 @@ extern "C" int mural_summary_txindel_rows(const MuralSummaryTxindelRows* s, void
     A.cls[c] = txindel_class_word(s->class_len[c][0], s->class_len[c][1]);
   }
   A.table = reinterpret_cast<u64*>(s->table), A.rows = reinterpret_cast<u64*>(s->rows), A.status = s->status;
-  WsArena ws(ws_ptr);
-  const RowChunks w = carve_row_chunks(ws, s->n_features);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(TI_THREADS);
   const dim3 row_grid((unsigned)((s->n + TI_THREADS - 1) / TI_THREADS));
@@ -249,13 +242,12 @@ extern "C" int mural_summary_txindel_rows(const MuralSummaryTxindelRows* s, void
   else
     hipLaunchKernelGGL(summary_txindel_check_kernel<float>, row_grid, block, 0, st, A);
   MURAL_HIP_CHECK(hipGetLastError());
-  const dim3 feat_grid((unsigned)((s->n_features + TI_WAVES - 1) / TI_WAVES));
+  WsArena ws(ws_ptr);
+  RowChunks w;
   const int64_t home_shift = A.off - (A.kind == TI_DELETION_START ? 0 : 1);
-  hipLaunchKernelGGL(row_chunk_range_shift_kernel<TI_THREADS>, feat_grid, block, 0, st, A.start, A.n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx,
-                     A.n_feat, home_shift, TI_CHUNK_ROWS, w);
-  MURAL_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(summary_txindel_scan_kernel, dim3(1), dim3(TI_SCAN_THREADS), 0, st, w.pre, s->n_features);
-  MURAL_HIP_CHECK(hipGetLastError());
+  if (const int rc = plan_row_chunks<TI_THREADS, TI_SCAN_THREADS>(st, A.start, A.n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx, A.n_feat,
+                                                                  home_shift, TI_CHUNK_ROWS, ws, w))
+    return rc;
   const int64_t n_waves = row_chunk_grid_waves(s->n, TI_CHUNK_ROWS, 1, s->n_features, TI_GRID_WAVES, TI_WAVES);
   const dim3 reduce_grid((unsigned)(n_waves / TI_WAVES));
   if (s->prob_f64)
@@ -263,10 +255,5 @@ extern "C" int mural_summary_txindel_rows(const MuralSummaryTxindelRows* s, void
   else
     hipLaunchKernelGGL(summary_txindel_reduce_kernel<float>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
   MURAL_HIP_CHECK(hipGetLastError());
-  const int64_t n_cells = (int64_t)s->n_transcripts * TI_BINS;
-  FoldTables F{};
-  F.table[0] = A.table, F.n_groups[0] = n_cells, F.nc = 1;      // [transcript][bin][3] = [cell][3][1]
-  hipLaunchKernelGGL(summary_fold_kernel<TI_THREADS>, dim3((unsigned)((n_cells + TI_THREADS - 1) / TI_THREADS)), block, 0, st, F);
-  MURAL_HIP_CHECK(hipGetLastError());
-  return MURAL_OK;
+  return launch_cell_fold<TI_THREADS>(st, A.table, (int64_t)s->n_transcripts * TI_BINS);
 }

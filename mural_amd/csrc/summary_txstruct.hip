@@ -9,8 +9,8 @@
 // The host (tables.read_transcript_structure) turns every transcript into ITEMS that tile its span: its blocks cut at thickStart /
 // thickEnd and the gaps between them, each with a kind; a CDS item names its CDS segment of tables.read_transcripts.  The stages are
 // those of csrc/summary_conseq.hip with the items in the place of the segments:
-//   * check kernel, a thread per row: the status bits;
-//   * range and scan kernels: the items' rows cut into chunks of at most TS_CHUNK_ROWS rows (row_chunks.h);
+//   * check kernel (summary_quant.h: snv_check_kernel), a thread per row: the status bits;
+//   * the plan (row_chunks.h: plan_row_chunks): the items' rows cut into chunks of at most TS_CHUNK_ROWS rows;
 //   * reduce kernel, a grid of at most TS_GRID_WAVES waves striding over the chunks: the wave finds the chunk's item and walks the chunk
 //     64 rows at a time, a row per lane.  The rows of one item fall in at most three bins (an intron: donor, acceptor, rest; a CDS part:
 //     start lost, cds; every other kind: one), so a lane carries three (hi, lo) SLOTS, mapped to bins by the item's kind at the atomics.
@@ -45,79 +45,25 @@ constexpr int TS_CELL_WORDS = 3 * TS_BINS;        // per transcript: [bin][label
 constexpr int TS_SLOTS = 3;                       // the bins one item's rows can fall in
 constexpr int TS_KIND_CODING_INTRON = 3, TS_KIND_INTRON = 4, TS_KIND_CDS = 5;
 
-struct TxstructArgs {      // (the fields conseq_bins.h reads, under its names)
-  MuralGenome g;
-  const void* prob;
-  const int64_t* start;
-  const uint8_t* strand;      // or nullptr: all '+'
-  const void* label;
-  int64_t prob_stride, n;
-  int32_t label_kind, n_tx;
-  const int64_t* seg_b0;
-  const int64_t* seg_b1;
-  const int64_t* seg_cds0;
-  const int32_t* seg_tx;
-  const int32_t* seg_prev;
-  const int32_t* seg_next;
-  int64_t n_seg;
+struct TxstructArgs {
+  SnvRows snv;
+  TxSegments tx;
   const int64_t* feat_b0;
   const int64_t* feat_b1;
   const int32_t* feat_tx;
   const uint8_t* feat_kind;
   const int32_t* feat_seg;
   int64_t n_feat;
-  const uint8_t* tx_strand;
-  const int64_t* tx_cds_len;
-  uint32_t aa_w[16];          // the 64 amino-acid bytes, four to a word
-  uint32_t alt_packed;        // alt_order[r][j] in bits [2 (3 r + j), +2)
   u64* table;
   u64* rows;
-  int32_t* status;
 };
-
-// The checks of row i (status bits, 0 if it counts) and the limbs of its classes 1 .. 3; class 0's probability is not read.
-template <typename T>
-__device__ __forceinline__ int32_t txstruct_row(const TxstructArgs& A, int64_t i, int& lab, u64 (&hi)[3], u64 (&lo)[3]) {
-  const T* __restrict__ p_row = static_cast<const T*>(A.prob) + i * A.prob_stride;
-  lab = load_label(A.label, A.label_kind, i);
-  int32_t bad = 0;
-  if (A.start[i] < 0) bad |= SM_BAD_START;
-  if (lab < 0 || lab >= 4) bad |= SM_BAD_LABEL;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    if (!quantise_prob((double)p_row[c + 1], hi[c], lo[c])) bad |= SM_BAD_PROB;      // (float -> double is exact)
-  return bad;
-}
-
-template <typename T>
-__global__ __launch_bounds__(TS_THREADS) void summary_txstruct_check_kernel(TxstructArgs A) {
-  const int64_t i = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
-  int32_t bad = 0;
-  if (i < A.n) {
-    int lab;
-    u64 hi[3], lo[3];
-    bad = txstruct_row<T>(A, i, lab, hi, lo);
-    if (i > 0 && A.start[i] < A.start[i - 1]) bad |= SM_BAD_ORDER;
-  }
-  if (bad) atomicOr(A.status, bad);
-}
-
-// exclusive prefix of v[0 .. m - 1] in place, v[m] = the total: one workgroup
-__global__ __launch_bounds__(TS_SCAN_THREADS) void summary_txstruct_scan_kernel(int64_t* __restrict__ v, int64_t m) {
-  const int64_t total = run_excl_scan<TS_SCAN_THREADS, int64_t>(m, [&](int64_t t) { return v[t]; }, [&](int64_t t, int64_t x) { v[t] = x; });
-  if (threadIdx.x == 0) v[m] = total;
-}
 
 template <typename T>
 __global__ __launch_bounds__(TS_THREADS) void summary_txstruct_reduce_kernel(TxstructArgs A, const int64_t* __restrict__ row0,
                                                                              const int64_t* __restrict__ row1,
                                                                              const int64_t* __restrict__ pre, int64_t n_waves) {
   __shared__ uint32_t aa_words[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j)      // (constant indices: the words stay scalar arguments)
-    if (threadIdx.x == j) aa_words[j] = A.aa_w[j];
-  __syncthreads();
-  const uint8_t* aa = reinterpret_cast<const uint8_t*>(aa_words);
+  const uint8_t* aa = stage_aa(A.tx, aa_words);
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * TS_WAVES + (threadIdx.x >> 6);
   const int64_t units = pre[A.n_feat];
@@ -128,7 +74,7 @@ __global__ __launch_bounds__(TS_THREADS) void summary_txstruct_reduce_kernel(Txs
     const int64_t b0 = A.feat_b0[f], b1 = A.feat_b1[f];
     const int32_t tx = A.feat_tx[f];      // (0 <= tx < n_tx: the range kernel gave other items no chunk)
     const int kind = A.feat_kind[f];
-    const bool minus = A.tx_strand[tx] != 0;
+    const bool minus = A.tx.tx_strand[tx] != 0;
     // the bins of the item's slots; -1: the slot is not used
     int slot_bin[TS_SLOTS] = {-1, -1, -1};
     int64_t seg = 0, cds0 = 0, cds_len = 0;
@@ -140,9 +86,9 @@ __global__ __launch_bounds__(TS_THREADS) void summary_txstruct_reduce_kernel(Txs
       slot_bin[0] = 5, slot_bin[2] = 6;
     } else if (kind == TS_KIND_CDS) {
       seg = A.feat_seg[f];
-      if (seg < 0 || seg >= A.n_seg) continue;      // (a CDS item without its segment: skipped, as an item without its transcript)
-      if (A.seg_b0[seg] != b0 || A.seg_b1[seg] != b1 || A.seg_tx[seg] != tx) continue;
-      cds0 = A.seg_cds0[seg], cds_len = A.tx_cds_len[tx];
+      if (seg < 0 || seg >= A.tx.n_seg) continue;      // (a CDS item without its segment: skipped, as an item without its transcript)
+      if (A.tx.seg_b0[seg] != b0 || A.tx.seg_b1[seg] != b1 || A.tx.seg_tx[seg] != tx) continue;
+      cds0 = A.tx.seg_cds0[seg], cds_len = A.tx.tx_cds_len[tx];
       slot_bin[0] = 7, slot_bin[1] = 8;
     } else {
       continue;      // (an unknown kind)
@@ -162,9 +108,9 @@ __global__ __launch_bounds__(TS_THREADS) void summary_txstruct_reduce_kernel(Txs
       bool live = false;
       int64_t q = b0;
       if (i < r1) {
-        q = A.start[i];
+        q = A.snv.start[i];
         // (the status is the check kernel's; q lies in [b0, b1) unless the rows do not ascend: then the row is skipped here)
-        live = txstruct_row<T>(A, i, lab, hi, lo) == 0 && q >= b0 && q < b1;
+        live = snv_row<T>(A.snv, i, lab, hi, lo) == 0 && q >= b0 && q < b1;
         if (live) {
           int slot = 0;
           if (kind == TS_KIND_CDS) {
@@ -184,7 +130,7 @@ __global__ __launch_bounds__(TS_THREADS) void summary_txstruct_reduce_kernel(Txs
         const int64_t x = cds0 + (minus ? b1 - 1 - q : q - b0);
         if (live && x < 3) {
           int bins[3];
-          conseq_row_bins(A, aa, seg, tx, minus, cds_len, b0, b1, cds0, i, q, bins);
+          conseq_row_bins(A.tx, A.snv.strand, aa, seg, tx, minus, cds_len, b0, b1, cds0, i, q, bins);
 #pragma unroll
           for (int c = 0; c < 3; ++c) slots[c] = (bins[c] >= 1 && bins[c] <= 3) ? 0 : 1;      // aa_alt != aa_ref on a resolved codon
         }
@@ -240,12 +186,10 @@ extern "C" int mural_summary_txstruct_rows(const MuralSummaryTxstructRows* s, vo
   MURAL_REQUIRE(s->n_segments >= 0, "summary_txstruct_rows: n_segments < 0");
   MURAL_REQUIRE(s->n_transcripts >= 0, "summary_txstruct_rows: n_transcripts < 0");
   MURAL_REQUIRE(s->label_kind >= 0 && s->label_kind <= 2, "summary_txstruct_rows: label_kind is 0 (float32), 1 (int32) or 2 (int64)");
-  uint32_t alt_packed = 0;
-  int bad_alt = 0;
-  MURAL_REQUIRE(conseq_pack_alt_order(s->alt_order, alt_packed, bad_alt),
-                "summary_txstruct_rows: alt_order[%d] must name the three other bases once each", bad_alt);
-  if (s->n == 0 || s->n_features == 0) return MURAL_OK;
-  MURAL_REQUIRE(s->genome && s->genome->packed2 && s->genome->nmask && s->genome->length >= 0, "summary_txstruct_rows: empty genome");
+  TxstructArgs A{};
+  const bool live = s->n > 0 && s->n_features > 0;
+  if (const int rc = fill_tx_segments("summary_txstruct_rows", s, live, A.tx)) return rc;
+  if (!live) return MURAL_OK;
   MURAL_REQUIRE(s->prob && s->start && s->label && s->status && s->table && s->rows, "summary_txstruct_rows: NULL argument");
   MURAL_REQUIRE(s->feat_b0 && s->feat_b1 && s->feat_tx && s->feat_kind && s->feat_seg && s->tx_strand && s->tx_cds_len &&
                     s->n_transcripts >= 1,
@@ -256,44 +200,23 @@ extern "C" int mural_summary_txstruct_rows(const MuralSummaryTxstructRows* s, vo
   if (const int rc = check_workspace("summary_txstruct_rows", "mural_summary_txstruct_workspace_bytes", ws_ptr, ws_bytes,
                                      mural_summary_txstruct_workspace_bytes(s->n_features)))
     return rc;
-  TxstructArgs A{};
-  A.g = *s->genome;
-  A.prob = s->prob, A.start = s->start, A.strand = s->strand, A.label = s->label, A.prob_stride = s->prob_stride, A.n = s->n;
-  A.label_kind = s->label_kind, A.n_tx = s->n_transcripts;
-  A.seg_b0 = s->seg_b0, A.seg_b1 = s->seg_b1, A.seg_cds0 = s->seg_cds0, A.seg_tx = s->seg_tx, A.seg_prev = s->seg_prev, A.seg_next = s->seg_next;
-  A.n_seg = s->n_segments;
+  A.snv = snv_rows(s);
   A.feat_b0 = s->feat_b0, A.feat_b1 = s->feat_b1, A.feat_tx = s->feat_tx, A.feat_kind = s->feat_kind, A.feat_seg = s->feat_seg;
-  A.n_feat = s->n_features, A.tx_strand = s->tx_strand, A.tx_cds_len = s->tx_cds_len;
-  for (int j = 0; j < 64; ++j) A.aa_w[j >> 2] |= (uint32_t)s->aa[j] << (8 * (j & 3));
-  A.alt_packed = alt_packed;
-  A.table = reinterpret_cast<u64*>(s->table), A.rows = reinterpret_cast<u64*>(s->rows), A.status = s->status;
-  WsArena ws(ws_ptr);
-  const RowChunks w = carve_row_chunks(ws, s->n_features);
+  A.n_feat = s->n_features;
+  A.table = reinterpret_cast<u64*>(s->table), A.rows = reinterpret_cast<u64*>(s->rows);
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 block(TS_THREADS);
-  const dim3 row_grid((unsigned)((s->n + TS_THREADS - 1) / TS_THREADS));
-  if (s->prob_f64)
-    hipLaunchKernelGGL(summary_txstruct_check_kernel<double>, row_grid, block, 0, st, A);
-  else
-    hipLaunchKernelGGL(summary_txstruct_check_kernel<float>, row_grid, block, 0, st, A);
-  MURAL_HIP_CHECK(hipGetLastError());
-  const dim3 feat_grid((unsigned)((s->n_features + TS_WAVES - 1) / TS_WAVES));
-  hipLaunchKernelGGL(row_chunk_range_kernel<TS_THREADS>, feat_grid, block, 0, st, A.start, A.n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx,
-                     A.n_feat, TS_CHUNK_ROWS, w);
-  MURAL_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(summary_txstruct_scan_kernel, dim3(1), dim3(TS_SCAN_THREADS), 0, st, w.pre, s->n_features);
-  MURAL_HIP_CHECK(hipGetLastError());
+  if (const int rc = launch_snv_check<TS_THREADS>(st, A.snv, s->prob_f64)) return rc;
+  WsArena ws(ws_ptr);
+  RowChunks w;
+  if (const int rc = plan_row_chunks<TS_THREADS, TS_SCAN_THREADS>(st, s->start, s->n, s->feat_b0, s->feat_b1, s->feat_tx, s->n_transcripts,
+                                                                  s->n_features, 0, TS_CHUNK_ROWS, ws, w))
+    return rc;
   const int64_t n_waves = row_chunk_grid_waves(s->n, TS_CHUNK_ROWS, 1, s->n_features, TS_GRID_WAVES, TS_WAVES);
-  const dim3 reduce_grid((unsigned)(n_waves / TS_WAVES));
+  const dim3 reduce_grid((unsigned)(n_waves / TS_WAVES)), block(TS_THREADS);
   if (s->prob_f64)
     hipLaunchKernelGGL(summary_txstruct_reduce_kernel<double>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
   else
     hipLaunchKernelGGL(summary_txstruct_reduce_kernel<float>, reduce_grid, block, 0, st, A, w.row0, w.row1, w.pre, n_waves);
   MURAL_HIP_CHECK(hipGetLastError());
-  const int64_t n_cells = (int64_t)s->n_transcripts * TS_BINS;
-  FoldTables F{};
-  F.table[0] = A.table, F.n_groups[0] = n_cells, F.nc = 1;      // [transcript][bin][3] = [cell][3][1]
-  hipLaunchKernelGGL(summary_fold_kernel<TS_THREADS>, dim3((unsigned)((n_cells + TS_THREADS - 1) / TS_THREADS)), block, 0, st, F);
-  MURAL_HIP_CHECK(hipGetLastError());
-  return MURAL_OK;
+  return launch_cell_fold<TS_THREADS>(st, A.table, (int64_t)s->n_transcripts * TS_BINS);
 }

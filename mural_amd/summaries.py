@@ -1,7 +1,8 @@
 """Genome summaries reduced in flight from the shards of a file-level prediction: the numpy "host twins" that specify the device
-reductions (csrc/summary.hip, csrc/summary_kmer.hip, csrc/summary_calib.hip, csrc/summary_annot.hip, csrc/summary_conseq.hip) and ``SummarySink``, the shard
-consumer that runs one reducer per summary kind -- window tables and totals, k-mer tables, motif tables, calibration metrics with the
-calibrator fit, annotation tables, consequence tables."""
+reductions (csrc/summary*.hip, csrc/simulate*.hip) and ``SummarySink``, the shard consumer that runs one reducer per summary kind --
+window tables and totals, k-mer tables, motif tables, calibration metrics with the calibrator fit, and the integer tables per name or
+transcript (annotations, consequences, transcript structure, INDEL structure and their simulated nulls), whose reducers share one
+lifecycle, ``_TableReducer``."""
 import ctypes as C
 import os
 import zlib
@@ -498,45 +499,89 @@ def _conseq_fold(table):
     return table
 
 
+def _upload_once(cache, name, arrays, dev):
+    """The device copies of `arrays` (an iterable, read only the first time) in cache[name]: uploaded once, from pinned memory and
+    non-blocking -- behind the work already enqueued; a pageable copy would wait for the forward --, the pinned tuple kept alive as the
+    last element."""
+    on_dev = cache.get(name)
+    if on_dev is None:
+        pinned = tuple(torch.from_numpy(np.ascontiguousarray(x)).pin_memory() for x in arrays)
+        on_dev = cache[name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    return on_dev
+
+
+def _grow_ws(acc, need, dev):
+    """(pointer, bytes) of acc["ws"], grown to `need` bytes or more (the launches of one stream run in order: one workspace serves
+    every entry that uses `acc`)."""
+    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
+        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    return acc["ws"].data_ptr(), acc["ws"].numel() * 8
+
+
+def _fill_rows(s, n_class, prob, prob_f64, prob_stride, start, n, strand=None, label=None, label_kind=None):
+    """The row fields every ``*_rows`` argument struct has, from device pointers; `strand` and `label` where the entry reads them."""
+    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
+    s.start, s.n, s.n_class = start, int(n), int(n_class)
+    if strand is not None:
+        s.strand = strand
+    if label is not None:
+        s.label, s.label_kind = label, int(label_kind)
+
+
+_SEG_KEYS = ("seg_b0", "seg_b1", "seg_cds0", "seg_tx", "seg_prev", "seg_next")
+_FEAT_KEYS = ("feat_b0", "feat_b1", "feat_tx", "feat_kind", "feat_seg", "feat_prev", "feat_next")
+
+
+def _fill_transcripts(s, n_transcripts, tx, seg_dev, n_seg_keys, feat_dev=None, codons=None):
+    """The transcript fields of a per-transcript argument struct: the strands and CDS lengths `tx`, the first `n_seg_keys` segment
+    arrays of `seg_dev` (None or empty: the chromosome has no CDS; 6 for the SNV structs, 4 for the INDEL structs, which have no
+    seg_prev / seg_next), the item arrays `feat_dev` (with their links where uploaded) and `codons` = (aa, alt_order, genome_struct)
+    for the entries that read codons."""
+    s.n_transcripts = int(n_transcripts)
+    s.tx_strand, s.tx_cds_len = tx[0].data_ptr(), tx[1].data_ptr()
+    if seg_dev is not None and seg_dev[0].shape[0]:
+        for key, x in zip(_SEG_KEYS[:n_seg_keys], seg_dev):
+            setattr(s, key, x.data_ptr())
+        s.n_segments = int(seg_dev[0].shape[0])
+    if feat_dev is not None:
+        for key, x in zip(_FEAT_KEYS, feat_dev[:-1]):
+            setattr(s, key, x.data_ptr())
+        s.n_features = int(feat_dev[0].shape[0])
+    if codons is not None:
+        aa, alt_order, genome_struct = codons
+        s.genome = C.pointer(genome_struct)
+        C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
+        C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+
+
+def _fill_indel(s, kind, breakpoint_offset, class_len, chrom_length):
+    s.kind, s.breakpoint_offset, s.chrom_length = int(kind), int(breakpoint_offset), -1 if chrom_length is None else int(chrom_length)
+    for c, (lo, hi) in enumerate(np.asarray(class_len).tolist()[:16]):
+        s.class_len[c][0], s.class_len[c][1] = lo, hi
+
+
 def _conseq_segments_device(acc, name, segments, dev):
     """The device arrays of chromosome `name`'s segments in acc["segments"], and the transcripts' strands and CDS lengths in acc["tx"]
     (`segments` may be a chromosome's dict of features: it has the same two): uploaded the first time, from pinned memory."""
-    if "tx" not in acc:
-        pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in ("tx_strand", "tx_cds_len"))
-        acc["tx"] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    _upload_once(acc, "tx", (segments[key] for key in ("tx_strand", "tx_cds_len")), dev)
     if "seg_b0" not in segments:
         return None
-    on_dev = acc["segments"].get(name)
-    if on_dev is None:
-        keys = ("seg_b0", "seg_b1", "seg_cds0", "seg_tx", "seg_prev", "seg_next")
-        pinned = tuple(torch.from_numpy(np.ascontiguousarray(segments[key])).pin_memory() for key in keys)
-        on_dev = acc["segments"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
-    return on_dev
+    return _upload_once(acc["segments"], name, (segments[key] for key in _SEG_KEYS), dev)
 
 
 def conseq_rows_device(acc, name, segments, n_transcripts, aa, alt_order, genome_struct, dev, *, prob, prob_f64, prob_stride, start,
                        strand, label, label_kind, n):
-    """One ``mural_summary_conseq_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 15],
-    rows int64 [n_transcripts * 2], status int32 [1], segments {chromosome: device arrays}, ws): the chromosome's segment arrays are
-    uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --, the workspace grows as needed."""
+    """One ``mural_summary_conseq_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 15], rows int64 [n_transcripts * 2], status int32 [1],
+    segments {chromosome: device arrays}, ws): the chromosome's segment arrays are uploaded the first time it arrives, the workspace
+    grows as needed."""
     lib = _lib.lib()
     on_dev = _conseq_segments_device(acc, name, segments, dev)
-    n_seg = int(on_dev[0].shape[0])
-    need = int(lib.mural_summary_conseq_workspace_bytes(n_seg))
-    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
     s = _lib.MuralSummaryConseqRows()
-    s.genome = C.pointer(genome_struct)
-    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
-    s.start, s.strand, s.label, s.label_kind = start, strand, label, int(label_kind)
-    s.n, s.n_class, s.n_transcripts = int(n), 4, int(n_transcripts)
-    s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in on_dev[:6])
-    s.n_segments = n_seg
-    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
-    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
-    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+    _fill_rows(s, 4, prob, prob_f64, prob_stride, start, n, strand, label, label_kind)
+    _fill_transcripts(s, n_transcripts, acc["tx"], on_dev, 6, codons=(aa, alt_order, genome_struct))
     s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
-    _lib.check(lib.mural_summary_conseq_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+    ws = _grow_ws(acc, int(lib.mural_summary_conseq_workspace_bytes(int(on_dev[0].shape[0]))), dev)
+    _lib.check(lib.mural_summary_conseq_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
 
 
 # ---- structure tables (csrc/summary_txstruct.hip: mural_summary_txstruct_rows): the same cells per transcript and place in its structure ---
@@ -622,37 +667,20 @@ def summary_txstruct_host(genome, prob, start, strand, label, segments, features
 
 def txstruct_rows_device(acc, conseq_acc, name, segments, features, n_transcripts, aa, alt_order, genome_struct, dev, *, prob, prob_f64,
                          prob_stride, start, strand, label, label_kind, n):
-    """One ``mural_summary_txstruct_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts *
-    27], rows int64 [n_transcripts * 2], status int32 [1], features {chromosome: device arrays}, ws): the chromosome's item arrays are
-    uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --, the workspace grows as needed.  The
-    segment arrays are those of `conseq_acc` (dict with "segments": {}), ``conseq_rows_device``'s accumulators, which uploaded them for
-    chromosome `name` just before -- or they are uploaded into it now; `segments` None: the chromosome has no CDS."""
+    """One ``mural_summary_txstruct_rows`` call on device pointers into the accumulators of `acc`
+    (dict: table int64 [n_transcripts * 27], rows int64 [n_transcripts * 2], status int32 [1], features {chromosome: device arrays},
+    ws): the chromosome's item arrays are uploaded the first time it arrives, the workspace grows as needed.  The segment arrays are
+    those of `conseq_acc` (dict with "segments": {}), ``conseq_rows_device``'s accumulators, which uploaded them for chromosome `name`
+    just before -- or they are uploaded into it now; `segments` None: the chromosome has no CDS."""
     lib = _lib.lib()
-    on_dev = acc["features"].get(name)
-    if on_dev is None:
-        keys = ("feat_b0", "feat_b1", "feat_tx", "feat_kind", "feat_seg")
-        pinned = tuple(torch.from_numpy(np.ascontiguousarray(features[key])).pin_memory() for key in keys)
-        on_dev = acc["features"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    on_dev = _upload_once(acc["features"], name, (features[key] for key in _FEAT_KEYS[:5]), dev)
     seg_dev = _conseq_segments_device(conseq_acc, name, features if segments is None else segments, dev)
-    n_feat = int(on_dev[0].shape[0])
-    need = int(lib.mural_summary_txstruct_workspace_bytes(n_feat))
-    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
     s = _lib.MuralSummaryTxstructRows()
-    s.genome = C.pointer(genome_struct)
-    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
-    s.start, s.strand, s.label, s.label_kind = start, strand, label, int(label_kind)
-    s.n, s.n_class, s.n_transcripts = int(n), 4, int(n_transcripts)
-    if seg_dev is not None and seg_dev[0].shape[0]:
-        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in seg_dev[:6])
-        s.n_segments = int(seg_dev[0].shape[0])
-    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg = (x.data_ptr() for x in on_dev[:5])
-    s.n_features = n_feat
-    s.tx_strand, s.tx_cds_len = conseq_acc["tx"][0].data_ptr(), conseq_acc["tx"][1].data_ptr()
-    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
-    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
+    _fill_rows(s, 4, prob, prob_f64, prob_stride, start, n, strand, label, label_kind)
+    _fill_transcripts(s, n_transcripts, conseq_acc["tx"], seg_dev, 6, on_dev, codons=(aa, alt_order, genome_struct))
     s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
-    _lib.check(lib.mural_summary_txstruct_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+    ws = _grow_ws(acc, int(lib.mural_summary_txstruct_workspace_bytes(int(on_dev[0].shape[0]))), dev)
+    _lib.check(lib.mural_summary_txstruct_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
 
 
 # ---- INDEL structure tables (csrc/summary_txindel.hip: mural_summary_txindel_rows): what an INDEL event does to the transcript -----------
@@ -822,37 +850,21 @@ def summary_txindel_host(prob, start, label, n_class, segments, features, n_tran
 
 def txindel_rows_device(acc, name, segments, features, links, n_transcripts, kind, breakpoint_offset, class_len, chrom_length, dev, *,
                         prob, prob_f64, prob_stride, start, label, label_kind, n, n_class):
-    """One ``mural_summary_txindel_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 30],
-    rows int64 [n_transcripts * 2], status int32 [1], features {chromosome: device arrays}, segments {the same}, ws): the chromosome's
-    item, link and segment arrays are uploaded the first time it arrives -- from pinned memory, behind the work already enqueued --,
-    the workspace grows as needed.  `segments` None: the chromosome has no CDS.  `class_len`: int32 [n_class][2]
+    """One ``mural_summary_txindel_rows`` call on device pointers into the accumulators of `acc` (dict: table int64 [n_transcripts * 30], rows int64 [n_transcripts * 2], status int32 [1], features
+    {chromosome: device arrays}, segments {the same}, ws): the chromosome's item, link and segment arrays are uploaded the first time
+    it arrives, the workspace grows as needed.  `segments` None: the chromosome has no CDS.  `class_len`: int32 [n_class][2]
     (``tables.check_indel_lengths``); `chrom_length` None: not known."""
     lib = _lib.lib()
-    on_dev = acc["features"].get(name)
-    if on_dev is None:
-        arrays = [features[key] for key in ("feat_b0", "feat_b1", "feat_tx", "feat_kind", "feat_seg")] + [np.asarray(x, np.int32) for x in links]
-        pinned = tuple(torch.from_numpy(np.ascontiguousarray(x)).pin_memory() for x in arrays)
-        on_dev = acc["features"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
+    arrays = [features[key] for key in _FEAT_KEYS[:5]] + [np.asarray(x, np.int32) for x in links]
+    on_dev = _upload_once(acc["features"], name, arrays, dev)
     seg_dev = _conseq_segments_device(acc, name, features if segments is None else segments, dev)
-    n_feat = int(on_dev[0].shape[0])
-    need = int(lib.mural_summary_txindel_workspace_bytes(n_feat))
-    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
     s = _lib.MuralSummaryTxindelRows()
-    s.prob, s.prob_f64, s.prob_stride = prob, int(prob_f64), int(prob_stride)
-    s.start, s.label, s.label_kind = start, label, int(label_kind)
-    s.n, s.n_class, s.n_transcripts = int(n), int(n_class), int(n_transcripts)
-    s.kind, s.breakpoint_offset, s.chrom_length = int(kind), int(breakpoint_offset), -1 if chrom_length is None else int(chrom_length)
-    for c, (lo, hi) in enumerate(np.asarray(class_len).tolist()[:16]):
-        s.class_len[c][0], s.class_len[c][1] = lo, hi
-    if seg_dev is not None and seg_dev[0].shape[0]:
-        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx = (x.data_ptr() for x in seg_dev[:4])
-        s.n_segments = int(seg_dev[0].shape[0])
-    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg, s.feat_prev, s.feat_next = (x.data_ptr() for x in on_dev[:7])
-    s.n_features = n_feat
-    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
+    _fill_rows(s, n_class, prob, prob_f64, prob_stride, start, n, label=label, label_kind=label_kind)
+    _fill_indel(s, kind, breakpoint_offset, class_len, chrom_length)
+    _fill_transcripts(s, n_transcripts, acc["tx"], seg_dev, 4, on_dev)
     s.table, s.rows, s.status = acc["table"].data_ptr(), acc["rows"].data_ptr(), acc["status"].data_ptr()
-    _lib.check(lib.mural_summary_txindel_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+    ws = _grow_ws(acc, int(lib.mural_summary_txindel_workspace_bytes(int(on_dev[0].shape[0]))), dev)
+    _lib.check(lib.mural_summary_txindel_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
 
 
 # ---- mutation sets drawn from the rates (csrc/simulate.hip: mural_simulate_annot_rows, mural_simulate_rows) -----------------------------
@@ -992,29 +1004,24 @@ def simulate_conseq_host(genome, prob, start, strand, segments, n_transcripts, c
     return table, status
 
 
+def _fill_draw(s, name, n_rep, seed, table, status):
+    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
+    s.table, s.status = table.data_ptr(), status.data_ptr()
+
+
 def simulate_conseq_rows_device(table, status, acc, name, n_transcripts, aa, alt_order, genome_struct, dev, n_rep, seed, *, prob, prob_f64,
                                 prob_stride, start, strand, n):
-    """One ``mural_simulate_conseq_rows`` call on device pointers into `table` (int32 [n_transcripts * 5 * n_rep]) and `status`, on the
-    segment arrays ``conseq_rows_device`` uploaded into `acc` for chromosome `name` just before; the workspace is `acc`'s (24 bytes a
-    segment in both entries, and the launches of one stream run in order)."""
+    """One ``mural_simulate_conseq_rows`` call on device pointers into `table`
+    (int32 [n_transcripts * 5 * n_rep]) and `status`, on the segment arrays ``conseq_rows_device`` uploaded into `acc` for chromosome
+    `name` just before; the workspace is `acc`'s (24 bytes a segment in both entries)."""
     lib = _lib.lib()
     on_dev = acc["segments"][name]
-    n_seg = int(on_dev[0].shape[0])
-    need = int(lib.mural_simulate_conseq_workspace_bytes(n_seg))
-    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
     s = _lib.MuralSimulateConseqRows()
-    s.genome = C.pointer(genome_struct)
-    s.prob, s.prob_f64, s.prob_stride, s.n_class = prob, int(prob_f64), int(prob_stride), 4
-    s.start, s.strand, s.n = start, strand, int(n)
-    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
-    s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in on_dev[:6])
-    s.n_segments, s.n_transcripts = n_seg, int(n_transcripts)
-    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
-    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
-    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
-    s.table, s.status = table.data_ptr(), status.data_ptr()
-    _lib.check(lib.mural_simulate_conseq_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+    _fill_rows(s, 4, prob, prob_f64, prob_stride, start, n, strand)
+    _fill_draw(s, name, n_rep, seed, table, status)
+    _fill_transcripts(s, n_transcripts, acc["tx"], on_dev, 6, codons=(aa, alt_order, genome_struct))
+    ws = _grow_ws(acc, int(lib.mural_simulate_conseq_workspace_bytes(int(on_dev[0].shape[0]))), dev)
+    _lib.check(lib.mural_simulate_conseq_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
 
 
 def simulate_txstruct_host(genome, prob, start, strand, segments, features, n_transcripts, chrom_key, seed, n_rep, aa=None, alt_order=None,
@@ -1075,31 +1082,17 @@ def simulate_lof_counts(conseq_counts, struct_counts):
 
 def simulate_txstruct_rows_device(table, status, acc, conseq_acc, name, n_transcripts, aa, alt_order, genome_struct, dev, n_rep, seed, *,
                                   prob, prob_f64, prob_stride, start, strand, n):
-    """One ``mural_simulate_txstruct_rows`` call on device pointers into `table` (int32 [n_transcripts * 9 * n_rep]) and `status`, on
-    the item arrays ``txstruct_rows_device`` uploaded into `acc` for chromosome `name` just before and the segment arrays of
-    `conseq_acc`; the workspace is `acc`'s (24 bytes an item in both entries, and the launches of one stream run in order)."""
+    """One ``mural_simulate_txstruct_rows`` call on device pointers into `table` (int32
+    [n_transcripts * 9 * n_rep]) and `status`, on the item arrays ``txstruct_rows_device`` uploaded into `acc` for chromosome `name`
+    just before and the segment arrays of `conseq_acc`; the workspace is `acc`'s (24 bytes an item in both entries)."""
     lib = _lib.lib()
     on_dev = acc["features"][name]
-    seg_dev = conseq_acc["segments"].get(name)
-    n_feat = int(on_dev[0].shape[0])
-    need = int(lib.mural_simulate_txstruct_workspace_bytes(n_feat))
-    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
     s = _lib.MuralSimulateTxstructRows()
-    s.genome = C.pointer(genome_struct)
-    s.prob, s.prob_f64, s.prob_stride, s.n_class = prob, int(prob_f64), int(prob_stride), 4
-    s.start, s.strand, s.n = start, strand, int(n)
-    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
-    if seg_dev is not None and seg_dev[0].shape[0]:
-        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx, s.seg_prev, s.seg_next = (x.data_ptr() for x in seg_dev[:6])
-        s.n_segments = int(seg_dev[0].shape[0])
-    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg = (x.data_ptr() for x in on_dev[:5])
-    s.n_features, s.n_transcripts = n_feat, int(n_transcripts)
-    s.tx_strand, s.tx_cds_len = conseq_acc["tx"][0].data_ptr(), conseq_acc["tx"][1].data_ptr()
-    C.memmove(s.aa, np.ascontiguousarray(aa, np.uint8).ctypes.data, 64)
-    C.memmove(s.alt_order, np.ascontiguousarray(alt_order, np.uint8).ctypes.data, 12)
-    s.table, s.status = table.data_ptr(), status.data_ptr()
-    _lib.check(lib.mural_simulate_txstruct_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+    _fill_rows(s, 4, prob, prob_f64, prob_stride, start, n, strand)
+    _fill_draw(s, name, n_rep, seed, table, status)
+    _fill_transcripts(s, n_transcripts, conseq_acc["tx"], conseq_acc["segments"].get(name), 6, on_dev, codons=(aa, alt_order, genome_struct))
+    ws = _grow_ws(acc, int(lib.mural_simulate_txstruct_workspace_bytes(int(on_dev[0].shape[0]))), dev)
+    _lib.check(lib.mural_simulate_txstruct_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
 
 
 def simulate_txindel_host(prob, start, strand, n_class, segments, features, n_transcripts, kind, chrom_key, seed, n_rep,
@@ -1167,31 +1160,18 @@ def simulate_indel_lof_counts(counts):
 
 def simulate_txindel_rows_device(table, status, acc, name, n_transcripts, kind, breakpoint_offset, class_len, chrom_length, dev, n_rep,
                                  seed, *, prob, prob_f64, prob_stride, start, strand, n, n_class):
-    """One ``mural_simulate_txindel_rows`` call on device pointers into `table` (int32 [n_transcripts * 10 * n_rep]) and `status`, on
-    the item, link and segment arrays ``txindel_rows_device`` uploaded into `acc` for chromosome `name` just before; the workspace is
-    `acc`'s (24 bytes an item in both entries, and the launches of one stream run in order)."""
+    """One ``mural_simulate_txindel_rows`` call on device pointers into `table` (int32
+    [n_transcripts * 10 * n_rep]) and `status`, on the item, link and segment arrays ``txindel_rows_device`` uploaded into `acc` for
+    chromosome `name` just before; the workspace is `acc`'s (24 bytes an item in both entries)."""
     lib = _lib.lib()
     on_dev = acc["features"][name]
-    seg_dev = acc["segments"].get(name)
-    n_feat = int(on_dev[0].shape[0])
-    need = int(lib.mural_simulate_txindel_workspace_bytes(n_feat))
-    if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-        acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
     s = _lib.MuralSimulateTxindelRows()
-    s.prob, s.prob_f64, s.prob_stride, s.n_class = prob, int(prob_f64), int(prob_stride), int(n_class)
-    s.start, s.strand, s.n = start, strand, int(n)
-    s.chrom_key, s.n_rep, s.seed = simulate_chrom_key(name), int(n_rep), int(seed)
-    s.kind, s.breakpoint_offset, s.chrom_length = int(kind), int(breakpoint_offset), -1 if chrom_length is None else int(chrom_length)
-    for c, (lo, hi) in enumerate(np.asarray(class_len).tolist()[:16]):
-        s.class_len[c][0], s.class_len[c][1] = lo, hi
-    if seg_dev is not None and seg_dev[0].shape[0]:
-        s.seg_b0, s.seg_b1, s.seg_cds0, s.seg_tx = (x.data_ptr() for x in seg_dev[:4])
-        s.n_segments = int(seg_dev[0].shape[0])
-    s.feat_b0, s.feat_b1, s.feat_tx, s.feat_kind, s.feat_seg, s.feat_prev, s.feat_next = (x.data_ptr() for x in on_dev[:7])
-    s.n_features, s.n_transcripts = n_feat, int(n_transcripts)
-    s.tx_strand, s.tx_cds_len = acc["tx"][0].data_ptr(), acc["tx"][1].data_ptr()
-    s.table, s.status = table.data_ptr(), status.data_ptr()
-    _lib.check(lib.mural_simulate_txindel_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+    _fill_rows(s, n_class, prob, prob_f64, prob_stride, start, n, strand)
+    _fill_draw(s, name, n_rep, seed, table, status)
+    _fill_indel(s, kind, breakpoint_offset, class_len, chrom_length)
+    _fill_transcripts(s, n_transcripts, acc["tx"], acc["segments"].get(name), 4, on_dev)
+    ws = _grow_ws(acc, int(lib.mural_simulate_txindel_workspace_bytes(int(on_dev[0].shape[0]))), dev)
+    _lib.check(lib.mural_simulate_txindel_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
 
 
 def simulate_pvalues(counts, observed=None):
@@ -1668,7 +1648,106 @@ class _KeyedReducer:
             self.kind["write"](*result[self.name][n], k, n, out_prefix)
 
 
-class _AnnotationReducer:
+_DEVICE_DTYPE = {np.uint64: torch.int64, np.uint32: torch.int32}
+
+
+class _TableReducer:
+    """The lifecycle of a reducer whose state is one or more integer tables that are plain sums over the rows: ONE set of tables for
+    the whole run on the host (created by the first host part) and one per device (created by the first device part, with a status
+    word), read back once and added.  ``_tables(k)`` describes them: (key of the device dict, shape, dtype, fold or None) each, the
+    fold being the carry of the lo limbs that follows every addition of two such tables (``_kmer_fold``, ``_conseq_fold``).  The state
+    -- ``host``, what ``read_back`` and ``merge`` return, what ``finish`` keeps under the attribute named by `kept` -- is the table
+    itself where there is one and the tuple of them otherwise.  A subclass keeps what is its own: the chromosomes it skips, its class
+    check, its host and device calls, ``finish`` and ``write``."""
+    kept = "sums"
+
+    def _tables(self, k):
+        raise NotImplementedError
+
+    def reset(self):
+        self.host = None               # the tables of the host shards
+        self.dev = {}                  # device -> dict(<key>: flat table ..., status, and what the subclass uploads)
+        setattr(self, self.kept, None)
+
+    def _state(self, tables, k):
+        return tables[0] if len(self._tables(k)) == 1 else tuple(tables)
+
+    def _zeros(self, k):
+        return self._state([np.zeros(shape, dtype) for _, shape, dtype, _ in self._tables(k)], k)
+
+    def _host(self, k):
+        if self.host is None:
+            self.host = self._zeros(k)
+        return self.host
+
+    def _acc(self, dev, k, **own):
+        """The device's accumulators, zeros the first time, with the subclass's `own` entries (caches, workspace)."""
+        acc = self.dev.get(dev)
+        if acc is None:
+            acc = self.dev[dev] = {key: torch.zeros(max(int(np.prod(shape)), 1), dtype=_DEVICE_DTYPE[dtype], device=dev)
+                                   for key, shape, dtype, _ in self._tables(k)}
+            acc.update(own, status=torch.zeros(1, dtype=torch.int32, device=dev))
+        return acc
+
+    def _added(self, states, k):
+        """The states added table by table, carries folded; None where there is none; never one of `states` itself."""
+        spec, out = self._tables(k), None
+        for st in states:
+            if st is None:
+                continue
+            st = (st,) if len(spec) == 1 else st
+            if out is None:
+                out = [t.copy() for t in st]
+                continue
+            for have, t, (_, _, _, fold) in zip(out, st, spec):
+                np.add(have, t, out=have)
+                if fold is not None:
+                    fold(have)
+        return None if out is None else self._state(out, k)
+
+    def read_back(self, k):
+        """The one read-back of the device tables, added to the host rows'."""
+        status, mine = 0, [self.host]
+        for acc in self.dev.values():
+            status |= int(acc["status"].item())
+            mine.append(self._state([acc[key].cpu().numpy().view(dtype)[:int(np.prod(shape))].reshape(shape)
+                                     for key, shape, dtype, _ in self._tables(k)], k))
+        return self._added(mine, k), status
+
+    def merge(self, states, k):
+        return self._added(states, k)
+
+    def finish(self, state, k, result):
+        setattr(self, self.kept, self._zeros(k) if state is None else state)
+
+
+def _check_simulation(n_rep, seed, table_bytes_max=None, cells=0, what="", seed_text="simulate_seed is an unsigned 64-bit integer"):
+    """The checks every simulation reducer makes: the replicates, the seed and -- given `table_bytes_max` -- the bytes of its uint32
+    table of `cells` cells (`what`: their description) per replicate.  `seed_text` is there for the INDEL structure simulation alone,
+    whose seed message has always been worded differently: callers match on these texts, so it stays."""
+    if not 1 <= n_rep <= SIMULATE_MAX_REPLICATES:
+        raise ValueError("simulate: 1 .. 2^20 replicates")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(seed_text)
+    need = cells * n_rep * 4
+    if table_bytes_max is not None and need > table_bytes_max:
+        raise ValueError(f"simulate: the table of {what} x {n_rep} replicates takes {need} bytes, above simulate_table_bytes_max = "
+                         f"{table_bytes_max}")
+
+
+def _device_rows(prob, start, **cols):
+    """The row keywords of the ``*_rows_device`` functions from a device part's tensors; `cols`: strand= (a tensor or None) and label=
+    where the function takes them."""
+    rows = dict(prob=prob.data_ptr(), prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
+                n=start.shape[0])
+    if "strand" in cols:
+        rows["strand"] = None if cols["strand"] is None else cols["strand"].data_ptr()
+    if "label" in cols:
+        rows.update(label=cols["label"].data_ptr(), label_kind=_LABEL_KIND[cols["label"].dtype])
+    return rows
+
+
+class _AnnotationReducer(_TableReducer):
     """Expected and observed mutations per name of an annotation BED (``tables.read_annotations``): ONE integer table [names][3][n_class]
     for the whole run on the host and one per device -- the group ids are global --, a chromosome's pieces uploaded the first time the
     chromosome arrives on a device, read back once.  A chromosome without pieces reduces nothing."""
@@ -1680,18 +1759,14 @@ class _AnnotationReducer:
             raise ValueError("annotations: 2^31 names or more")
         self.reset()
 
-    def reset(self):
-        self.host = None               # table uint64 [names][3][n_class] of the host shards
-        self.dev = {}                  # device -> dict(table, status, pieces {chromosome: (b0, b1, group)}, ws)
-        self.sums = None
+    def _tables(self, k):
+        return (("table", (len(self.names), 3, k or 0), np.uint64, _kmer_fold),)
 
     def host_part(self, name, prob, start, end, strand, label, k):
         pieces = self.pieces.get(name)
         if pieces is None:
             return 0
-        if self.host is None:
-            self.host = np.zeros((len(self.names), 3, k), np.uint64)
-        return summary_annot_host(prob, start, label, k, pieces, len(self.names), into=self.host)[1]
+        return summary_annot_host(prob, start, label, k, pieces, len(self.names), into=self._host(k))[1]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the reduction of a part behind its forward, into the device's one table."""
@@ -1699,48 +1774,20 @@ class _AnnotationReducer:
         if pieces is None or start.shape[0] == 0:
             return None
         dev, lib = prob.device, _lib.lib()
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(len(self.names) * 3 * k, dtype=torch.int64, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev), pieces={}, ws=None)
-        on_dev = acc["pieces"].get(name)
-        if on_dev is None:             # from pinned memory, behind the work already enqueued: a pageable copy would wait for the forward
-            pinned = tuple(torch.from_numpy(np.ascontiguousarray(x)).pin_memory() for x in pieces)
-            on_dev = acc["pieces"][name] = tuple(x.to(dev, non_blocking=True) for x in pinned) + (pinned,)
-        need = int(lib.mural_summary_annot_workspace_bytes(start.shape[0], k))
-        if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-            acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+        acc = self._acc(dev, k, pieces={}, ws=None)
+        on_dev = _upload_once(acc["pieces"], name, pieces, dev)
         s = _lib.MuralSummaryAnnotRows()
-        s.prob, s.prob_f64, s.prob_stride = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0)
-        s.start, s.label, s.label_kind = start.data_ptr(), label.data_ptr(), _LABEL_KIND[label.dtype]
-        s.n, s.n_class, s.n_groups = start.shape[0], k, len(self.names)
+        _fill_rows(s, k, **_device_rows(prob, start, label=label))
+        s.n_groups = len(self.names)
         s.piece_b0, s.piece_b1, s.piece_group, s.n_pieces = (on_dev[0].data_ptr(), on_dev[1].data_ptr(), on_dev[2].data_ptr(),
                                                              on_dev[0].shape[0])
         s.table, s.status = acc["table"].data_ptr(), acc["status"].data_ptr()
-        _lib.check(lib.mural_summary_annot_rows(C.byref(s), acc["ws"].data_ptr(), acc["ws"].numel() * 8, _lib.current_stream_ptr(dev)))
+        ws = _grow_ws(acc, int(lib.mural_summary_annot_workspace_bytes(start.shape[0], k)), dev)
+        _lib.check(lib.mural_summary_annot_rows(C.byref(s), *ws, _lib.current_stream_ptr(dev)))
         return None
 
-    def _added(self, tables):
-        """Integer tables added, carries folded; None where there is none."""
-        out = None
-        for t in tables:
-            if t is not None:
-                out = t.copy() if out is None else _kmer_fold(np.add(out, t, out=out))
-        return out
-
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, mine = 0, [self.host]
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine.append(acc["table"].cpu().numpy().view(np.uint64).reshape(len(self.names), 3, k))
-        return self._added(mine), status
-
-    def merge(self, states, k):
-        return self._added(states)
-
     def finish(self, state, k, result):
-        self.sums = np.zeros((len(self.names), 3, k or 0), np.uint64) if state is None else state
+        super().finish(state, k, result)
         result[self.name] = (list(self.names), annotation_meta(self.names, self.meta), annot_table_from_sums(self.sums, k or 0))
 
     def write(self, out_prefix, result, k, written):
@@ -1748,7 +1795,7 @@ class _AnnotationReducer:
         write_annotation_outputs(*result[self.name], k, out_prefix)
 
 
-class _ConsequenceReducer:
+class _ConsequenceReducer(_TableReducer):
     """Expected and observed mutations per transcript of a BED12 file by consequence (``summary_conseq_host`` is the rule): ONE integer
     table [transcripts][5][3] + row counters [transcripts][2] for the whole run on the host and one pair per device -- the transcript
     ids are global --, a chromosome's segment arrays uploaded the first time the chromosome arrives on a device, read back once.  A
@@ -1763,10 +1810,8 @@ class _ConsequenceReducer:
         self.genome = genome
         self.reset()
 
-    def reset(self):
-        self.host = None               # (table, rows) of the host shards
-        self.dev = {}                  # device -> dict(table, rows, status, segments {chromosome: device arrays}, tx, ws)
-        self.sums = None
+    def _tables(self, k):
+        return (("table", (len(self.names), 5, 3), np.uint64, _conseq_fold), ("rows", (len(self.names), 2), np.uint64, None))
 
     def _check(self, k):
         if k != 4:
@@ -1777,10 +1822,8 @@ class _ConsequenceReducer:
         segments = self.segments.get(name)
         if segments is None:
             return 0
-        if self.host is None:
-            self.host = (np.zeros((len(self.names), 5, 3), np.uint64), np.zeros((len(self.names), 2), np.uint64))
         return summary_conseq_host(self.genome(name), prob, start, strand, label, segments, len(self.names), self.meta["aa"],
-                                   self.alt_order, into=self.host)[2]
+                                   self.alt_order, into=self._host(k))[2]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the reduction of a part behind its forward, into the device's one pair of tables."""
@@ -1788,41 +1831,13 @@ class _ConsequenceReducer:
         segments = self.segments.get(name)
         if segments is None or start.shape[0] == 0:
             return None
-        dev, n_tx = prob.device, len(self.names)
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(n_tx * 15, dtype=torch.int64, device=dev),
-                                       rows=torch.zeros(n_tx * 2, dtype=torch.int64, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev), segments={}, ws=None)
-        genome = self.genome(name)
-        conseq_rows_device(acc, name, segments, n_tx, self.meta["aa"], self.alt_order, genome.as_struct(dev), dev, prob=prob.data_ptr(),
-                           prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
-                           strand=strand.data_ptr(), label=label.data_ptr(), label_kind=_LABEL_KIND[label.dtype], n=start.shape[0])
+        dev, genome = prob.device, self.genome(name)
+        conseq_rows_device(self._acc(dev, k, segments={}, ws=None), name, segments, len(self.names), self.meta["aa"], self.alt_order,
+                           genome.as_struct(dev), dev, **_device_rows(prob, start, strand=strand, label=label))
         return genome
 
-    def _added(self, states):
-        out = None
-        for st in states:
-            if st is not None:
-                out = (st[0].copy(), st[1].copy()) if out is None else (_conseq_fold(np.add(out[0], st[0], out=out[0])),
-                                                                        np.add(out[1], st[1], out=out[1]))
-        return out
-
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, mine, n_tx = 0, [self.host], len(self.names)
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine.append((acc["table"].cpu().numpy().view(np.uint64).reshape(n_tx, 5, 3),
-                         acc["rows"].cpu().numpy().view(np.uint64).reshape(n_tx, 2)))
-        return self._added(mine), status
-
-    def merge(self, states, k):
-        return self._added(states)
-
     def finish(self, state, k, result):
-        n_tx = len(self.names)
-        self.sums = (np.zeros((n_tx, 5, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if state is None else state
+        super().finish(state, k, result)
         result[self.name] = (list(self.names), self.meta, consequence_table_from_sums(*self.sums))
 
     def write(self, out_prefix, result, k, written):
@@ -1830,7 +1845,7 @@ class _ConsequenceReducer:
         write_consequence_outputs(*result[self.name], out_prefix, labels=self.labels)
 
 
-class _StructureReducer:
+class _StructureReducer(_TableReducer):
     """Expected and observed mutations per transcript by where a row lies in the transcript's structure (``summary_txstruct_host`` is
     the rule), behind the consequence reducer `conseq`, whose names, genome, codon table and device segment arrays it uses: ONE integer
     table [transcripts][9][3] + row counters [transcripts][2] for the whole run on the host and one pair per device, a chromosome's item
@@ -1841,21 +1856,17 @@ class _StructureReducer:
         self.features, self.conseq = features, conseq
         self.reset()
 
-    def reset(self):
-        self.host = None               # (table, rows) of the host shards
-        self.dev = {}                  # device -> dict(table, rows, status, features {chromosome: device arrays}, ws)
-        self.sums = None
+    def _tables(self, k):
+        n_tx = len(self.conseq.names)
+        return (("table", (n_tx, TX_BINS, 3), np.uint64, _conseq_fold), ("rows", (n_tx, 2), np.uint64, None))
 
     def host_part(self, name, prob, start, end, strand, label, k):
         self.conseq._check(k)
         features = self.features.get(name)
         if features is None:
             return 0
-        n_tx = len(self.conseq.names)
-        if self.host is None:
-            self.host = (np.zeros((n_tx, TX_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64))
-        return summary_txstruct_host(self.conseq.genome(name), prob, start, strand, label, self.conseq.segments.get(name), features, n_tx,
-                                     self.conseq.meta["aa"], self.conseq.alt_order, into=self.host)[2]
+        return summary_txstruct_host(self.conseq.genome(name), prob, start, strand, label, self.conseq.segments.get(name), features,
+                                     len(self.conseq.names), self.conseq.meta["aa"], self.conseq.alt_order, into=self._host(k))[2]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the reduction of a part behind its consequence reduction, into the device's one pair of tables."""
@@ -1863,35 +1874,16 @@ class _StructureReducer:
         features = self.features.get(name)
         if features is None or start.shape[0] == 0:
             return None
-        dev, n_tx = prob.device, len(self.conseq.names)
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(n_tx * 3 * TX_BINS, dtype=torch.int64, device=dev),
-                                       rows=torch.zeros(n_tx * 2, dtype=torch.int64, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev), features={}, ws=None, no_cds=dict(segments={}))
-        genome = self.conseq.genome(name)
+        dev, genome = prob.device, self.conseq.genome(name)
+        acc = self._acc(dev, k, features={}, ws=None, no_cds=dict(segments={}))
         # (the consequence reducer has no accumulators on a device that saw only chromosomes without CDS: the strands go to `no_cds`)
-        txstruct_rows_device(acc, self.conseq.dev.get(dev, acc["no_cds"]), name, self.conseq.segments.get(name), features, n_tx,
-                             self.conseq.meta["aa"], self.conseq.alt_order, genome.as_struct(dev), dev, prob=prob.data_ptr(),
-                             prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
-                             strand=strand.data_ptr(), label=label.data_ptr(), label_kind=_LABEL_KIND[label.dtype], n=start.shape[0])
+        txstruct_rows_device(acc, self.conseq.dev.get(dev, acc["no_cds"]), name, self.conseq.segments.get(name), features,
+                             len(self.conseq.names), self.conseq.meta["aa"], self.conseq.alt_order, genome.as_struct(dev), dev,
+                             **_device_rows(prob, start, strand=strand, label=label))
         return genome
 
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, mine, n_tx = 0, [self.host], len(self.conseq.names)
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine.append((acc["table"].cpu().numpy().view(np.uint64).reshape(n_tx, TX_BINS, 3),
-                         acc["rows"].cpu().numpy().view(np.uint64).reshape(n_tx, 2)))
-        return self.conseq._added(mine), status
-
-    def merge(self, states, k):
-        return self.conseq._added(states)
-
     def finish(self, state, k, result):
-        n_tx = len(self.conseq.names)
-        self.sums = (np.zeros((n_tx, TX_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if state is None else state
+        super().finish(state, k, result)
         result[self.name] = (list(self.conseq.names), *self.sums)
 
     def write(self, out_prefix, result, k, written):
@@ -1900,7 +1892,7 @@ class _StructureReducer:
         write_structure_outputs(names, self.conseq.meta, table, rows, self.conseq.sums[0][:, 2], out_prefix, labels=self.conseq.labels)
 
 
-class _IndelStructureReducer:
+class _IndelStructureReducer(_TableReducer):
     """Expected and observed INDEL events per transcript of a BED12 file by what they do to the transcript's structure
     (``summary_txindel_host`` is the rule): ONE integer table [transcripts][10][3] + row counters [transcripts][2] for the whole run on
     the host and one pair per device -- the transcript ids are global --, a chromosome's item, link and segment arrays uploaded the
@@ -1918,10 +1910,8 @@ class _IndelStructureReducer:
         self.links, self.class_len = {}, None
         self.reset()
 
-    def reset(self):
-        self.host = None               # (table, rows) of the host shards
-        self.dev = {}                  # device -> dict(table, rows, status, features, segments {chromosome: device arrays}, tx, ws)
-        self.sums = None
+    def _tables(self, k):
+        return (("table", (len(self.names), TXINDEL_BINS, 3), np.uint64, _conseq_fold), ("rows", (len(self.names), 2), np.uint64, None))
 
     def _part(self, name, k):
         """(features, links, chromosome length or None) of chromosome `name`, None where it has no items; the classes' lengths checked."""
@@ -1944,51 +1934,22 @@ class _IndelStructureReducer:
         part = self._part(name, k)
         if part is None:
             return 0
-        n_tx = len(self.names)
-        if self.host is None:
-            self.host = (np.zeros((n_tx, TXINDEL_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64))
-        return summary_txindel_host(prob, start, label, k, self.segments.get(name), part[0], n_tx, self.kind, self.offset, self.class_len,
-                                    part[2], links=part[1], into=self.host)[2]
+        return summary_txindel_host(prob, start, label, k, self.segments.get(name), part[0], len(self.names), self.kind, self.offset,
+                                    self.class_len, part[2], links=part[1], into=self._host(k))[2]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the reduction of a part behind its forward, into the device's one pair of tables."""
         part = self._part(name, k)
         if part is None or start.shape[0] == 0:
             return None
-        dev, n_tx = prob.device, len(self.names)
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(n_tx * 3 * TXINDEL_BINS, dtype=torch.int64, device=dev),
-                                       rows=torch.zeros(n_tx * 2, dtype=torch.int64, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev), features={}, segments={}, ws=None)
-        txindel_rows_device(acc, name, self.segments.get(name), part[0], part[1], n_tx, self.kind, self.offset, self.class_len, part[2], dev,
-                            prob=prob.data_ptr(), prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
-                            label=label.data_ptr(), label_kind=_LABEL_KIND[label.dtype], n=start.shape[0], n_class=k)
+        dev = prob.device
+        txindel_rows_device(self._acc(dev, k, features={}, segments={}, ws=None), name, self.segments.get(name), part[0], part[1],
+                            len(self.names), self.kind, self.offset, self.class_len, part[2], dev, n_class=k,
+                            **_device_rows(prob, start, label=label))
         return None
 
-    def _added(self, states):
-        out = None
-        for st in states:
-            if st is not None:
-                out = (st[0].copy(), st[1].copy()) if out is None else (_conseq_fold(np.add(out[0], st[0], out=out[0])),
-                                                                        np.add(out[1], st[1], out=out[1]))
-        return out
-
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, mine, n_tx = 0, [self.host], len(self.names)
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine.append((acc["table"].cpu().numpy().view(np.uint64).reshape(n_tx, TXINDEL_BINS, 3),
-                         acc["rows"].cpu().numpy().view(np.uint64).reshape(n_tx, 2)))
-        return self._added(mine), status
-
-    def merge(self, states, k):
-        return self._added(states)
-
     def finish(self, state, k, result):
-        n_tx = len(self.names)
-        self.sums = (np.zeros((n_tx, TXINDEL_BINS, 3), np.uint64), np.zeros((n_tx, 2), np.uint64)) if state is None else state
+        super().finish(state, k, result)
         result[self.name] = (list(self.names), *self.sums)
 
     def write(self, out_prefix, result, k, written):
@@ -1997,19 +1958,16 @@ class _IndelStructureReducer:
         write_indel_structure_outputs(names, self.meta, table, rows, self.kind, out_prefix, labels=self.labels)
 
 
-class _SimulationReducer:
+class _SimulationReducer(_TableReducer):
     """Mutation sets drawn from the rates (``simulate_rows_host`` is the rule): per name of the annotation reducer beside it the counts
     of every class in each of `n_rep` replicates -- ONE uint32 table [names][n_class - 1][n_rep] on the host and one per device, the
     pieces the annotation reducer uploaded, read back once --, and the replicates of `write` as mutation lists, a file per replicate
     written part by part (a rank's parts into its own part file; rank 0 strings them together in (shard, rank) order at close)."""
-    name = "simulation"
+    name, kept = "simulation", "counts"
 
     def __init__(self, n_rep, seed, write, annot, table_bytes_max, out_prefix, labels, rank, world):
         self.n_rep, self.seed, self.write_reps = int(n_rep), int(seed), tuple(int(r) for r in write)
-        if not 1 <= self.n_rep <= SIMULATE_MAX_REPLICATES:
-            raise ValueError("simulate: 1 .. 2^20 replicates")
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError("simulate_seed is an unsigned 64-bit integer")
+        _check_simulation(self.n_rep, self.seed)
         if any(not 0 <= r < self.n_rep for r in self.write_reps) or len(set(self.write_reps)) != len(self.write_reps):
             raise ValueError(f"simulate_write: distinct replicates in 0 .. {self.n_rep - 1}")
         if self.write_reps and out_prefix is None:
@@ -2018,10 +1976,11 @@ class _SimulationReducer:
         self.rank, self.world = rank, world
         self.reset()
 
+    def _tables(self, k):
+        return (("table", (self._groups(), max((k or 1) - 1, 0), self.n_rep), np.uint32, None),)
+
     def reset(self):
-        self.host = None               # table uint32 [names][n_class - 1][n_rep] of the host shards
-        self.dev = {}                  # device -> dict(table, status, ws, out)
-        self.counts = None
+        super().reset()
         self.pending = []              # device mutation lists not yet on the host: (event, chrom, shard number, {replicate: buffers})
         self.shard, self.last = -1, None
         self.index = {r: [] for r in self.write_reps}      # replicate -> [chromosome, bytes] per run of parts of one chromosome, in file order
@@ -2033,10 +1992,7 @@ class _SimulationReducer:
         return 0 if self.annot is None else len(self.annot.names)
 
     def _check_table(self, k):
-        need = self._groups() * (k - 1) * self.n_rep * 4
-        if need > self.table_bytes_max:
-            raise ValueError(f"simulate: the table of {self._groups()} names x {k - 1} classes x {self.n_rep} replicates takes {need} "
-                             f"bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        _check_simulation(self.n_rep, self.seed, self.table_bytes_max, self._groups() * (k - 1), f"{self._groups()} names x {k - 1} classes")
         if k < 2:
             raise ValueError("simulate needs at least 2 classes")
 
@@ -2065,9 +2021,7 @@ class _SimulationReducer:
         status = 0
         pieces = None if self.annot is None else self.annot.pieces.get(name)
         if pieces is not None:
-            if self.host is None:
-                self.host = np.zeros((self._groups(), k - 1, self.n_rep), np.uint32)
-            status |= simulate_annot_host(prob, start, strand, k, key, self.seed, pieces, self._groups(), self.n_rep, into=self.host)[1]
+            status |= simulate_annot_host(prob, start, strand, k, key, self.seed, pieces, self._groups(), self.n_rep, into=self._host(k))[1]
         if self.write_reps:
             self._drain()
             labels, st = simulate_rows_host(prob, start, strand, k, key, self.seed, self.write_reps, with_status=True)
@@ -2084,29 +2038,20 @@ class _SimulationReducer:
         if n == 0:
             return None
         dev, lib = prob.device, _lib.lib()
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(max(self._groups() * (k - 1) * self.n_rep, 1), dtype=torch.int32, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev), ws=None, copy=torch.cuda.Stream(dev))
-        key = simulate_chrom_key(name)
-        stream = _lib.current_stream_ptr(dev)
-
-        def workspace(need):
-            if acc["ws"] is None or acc["ws"].numel() * 8 < need:
-                acc["ws"] = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
-            return acc["ws"]
-
+        acc = self._acc(dev, k, ws=None)
+        if "copy" not in acc:
+            acc["copy"] = torch.cuda.Stream(dev)
+        key, stream, rows = simulate_chrom_key(name), _lib.current_stream_ptr(dev), _device_rows(prob, start, strand=strand)
         on_dev = None if self.annot is None else self.annot.dev.get(dev, {}).get("pieces", {}).get(name)      # uploaded just before
         if on_dev is not None:
             s = _lib.MuralSimulateAnnotRows()
-            s.prob, s.prob_f64, s.prob_stride, s.n_class = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0), k
-            s.start, s.strand, s.n = start.data_ptr(), strand.data_ptr(), n
+            _fill_rows(s, k, **rows)
             s.chrom_key, s.n_rep, s.seed = key, self.n_rep, self.seed
             s.piece_b0, s.piece_b1, s.piece_group, s.n_pieces = (on_dev[0].data_ptr(), on_dev[1].data_ptr(), on_dev[2].data_ptr(),
                                                                  on_dev[0].shape[0])
             s.n_groups, s.table, s.status = self._groups(), acc["table"].data_ptr(), acc["status"].data_ptr()
-            ws = workspace(int(lib.mural_simulate_annot_workspace_bytes(on_dev[0].shape[0])))
-            _lib.check(lib.mural_simulate_annot_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, stream))
+            ws = _grow_ws(acc, int(lib.mural_simulate_annot_workspace_bytes(on_dev[0].shape[0])), dev)
+            _lib.check(lib.mural_simulate_annot_rows(C.byref(s), *ws, stream))
         if self.write_reps:
             self._drain()
             lists = {}
@@ -2114,13 +2059,12 @@ class _SimulationReducer:
                 out = dict(start=torch.empty(n, dtype=torch.int64, device=dev), strand=torch.empty(n, dtype=torch.uint8, device=dev),
                            label=torch.empty(n, dtype=torch.uint8, device=dev), count=torch.zeros(1, dtype=torch.int64, device=dev))
                 s = _lib.MuralSimulateRows()
-                s.prob, s.prob_f64, s.prob_stride, s.n_class = prob.data_ptr(), int(prob.dtype == torch.float64), prob.stride(0), k
-                s.start, s.strand, s.n = start.data_ptr(), strand.data_ptr(), n
+                _fill_rows(s, k, **rows)
                 s.chrom_key, s.replicate, s.seed = key, r, self.seed
                 s.out_start, s.out_strand, s.out_label = out["start"].data_ptr(), out["strand"].data_ptr(), out["label"].data_ptr()
                 s.count, s.status = out["count"].data_ptr(), acc["status"].data_ptr()
-                ws = workspace(int(lib.mural_simulate_rows_workspace_bytes(n)))      # (the launches of one stream run in order)
-                _lib.check(lib.mural_simulate_rows(C.byref(s), ws.data_ptr(), ws.numel() * 8, stream))
+                ws = _grow_ws(acc, int(lib.mural_simulate_rows_workspace_bytes(n)), dev)
+                _lib.check(lib.mural_simulate_rows(C.byref(s), *ws, stream))
                 lists[r] = out
             event = torch.cuda.Event()
             event.record(torch.cuda.current_stream(dev))
@@ -2149,13 +2093,7 @@ class _SimulationReducer:
 
     def read_back(self, k):
         """The one read-back of the device tables, added to the host rows'; the mutation lists are flushed."""
-        status, table = 0, self.host
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            if self._groups() and k is not None:
-                mine = acc["table"].cpu().numpy().view(np.uint32)[:self._groups() * (k - 1) * self.n_rep]
-                mine = mine.reshape(self._groups(), k - 1, self.n_rep)
-                table = mine.copy() if table is None else table + mine
+        table, status = super().read_back(k)
         self._drain(wait=True)
         for r in self.write_reps:      # a rank without rows still has its (empty) file
             if r not in self.files:
@@ -2165,15 +2103,10 @@ class _SimulationReducer:
         return dict(table=table, index={r: [tuple(v) for v in segs] for r, segs in self.index.items()}), status
 
     def merge(self, states, k):
-        table = None
-        for st in states:
-            if st["table"] is not None:
-                table = st["table"].copy() if table is None else table + st["table"]
-        return dict(table=table, index=[st["index"] for st in states])
+        return dict(table=self._added([st["table"] for st in states], k), index=[st["index"] for st in states])
 
     def finish(self, state, k, result):
-        table = state["table"]
-        self.counts = np.zeros((self._groups(), max((k or 1) - 1, 0), self.n_rep), np.uint32) if table is None else table
+        super().finish(state["table"], k, result)
         self._index = state["index"]
         if self.annot is not None:
             names, _, annot = result["annotations"]
@@ -2209,74 +2142,42 @@ class _SimulationReducer:
                     os.unlink(path + ".part%04d" % rank)
 
 
-class _ConsequenceSimulationReducer:
+class _ConsequenceSimulationReducer(_TableReducer):
     """The simulated null of the consequence table (``simulate_conseq_host`` is the rule): per transcript of the consequence reducer
     before it, consequence bin and replicate the simulated count -- ONE uint32 table [transcripts][5][n_rep] on the host and one per
     device, on the segment arrays the consequence reducer uploaded just before, read back once."""
-    name = "consequence_simulation"
+    name, kept = "consequence_simulation", "counts"
 
     def __init__(self, n_rep, seed, conseq, table_bytes_max):
         self.n_rep, self.seed, self.conseq, self.table_bytes_max = int(n_rep), int(seed), conseq, int(table_bytes_max)
-        if not 1 <= self.n_rep <= SIMULATE_MAX_REPLICATES:
-            raise ValueError("simulate: 1 .. 2^20 replicates")
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError("simulate_seed is an unsigned 64-bit integer")
-        need = len(conseq.names) * 5 * self.n_rep * 4
-        if need > self.table_bytes_max:
-            raise ValueError(f"simulate: the table of {len(conseq.names)} transcripts x 5 consequences x {self.n_rep} replicates takes "
-                             f"{need} bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        _check_simulation(self.n_rep, self.seed, self.table_bytes_max, len(conseq.names) * 5, f"{len(conseq.names)} transcripts x 5 consequences")
         self.reset()
 
-    def reset(self):
-        self.host = None               # table uint32 [transcripts][5][n_rep] of the host shards
-        self.dev = {}                  # device -> dict(table, status)
-        self.counts = None
+    def _tables(self, k):
+        return (("table", (len(self.conseq.names), 5, self.n_rep), np.uint32, None),)
 
     def host_part(self, name, prob, start, end, strand, label, k):
         self.conseq._check(k)
         segments = self.conseq.segments.get(name)
         if segments is None:
             return 0
-        if self.host is None:
-            self.host = np.zeros((len(self.conseq.names), 5, self.n_rep), np.uint32)
         return simulate_conseq_host(self.conseq.genome(name), prob, start, strand, segments, len(self.conseq.names), simulate_chrom_key(name),
-                                    self.seed, self.n_rep, self.conseq.meta["aa"], self.conseq.alt_order, into=self.host)[1]
+                                    self.seed, self.n_rep, self.conseq.meta["aa"], self.conseq.alt_order, into=self._host(k))[1]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the draws of a part behind its consequence reduction, into the device's one table."""
         self.conseq._check(k)
         if self.conseq.segments.get(name) is None or start.shape[0] == 0:
             return None
-        dev, n_tx = prob.device, len(self.conseq.names)
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(max(n_tx * 5 * self.n_rep, 1), dtype=torch.int32, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev))
-        genome = self.conseq.genome(name)
-        simulate_conseq_rows_device(acc["table"], acc["status"], self.conseq.dev[dev], name, n_tx, self.conseq.meta["aa"],
-                                    self.conseq.alt_order, genome.as_struct(dev), dev, self.n_rep, self.seed, prob=prob.data_ptr(),
-                                    prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
-                                    strand=strand.data_ptr(), n=start.shape[0])
+        dev, genome = prob.device, self.conseq.genome(name)
+        acc = self._acc(dev, k)
+        simulate_conseq_rows_device(acc["table"], acc["status"], self.conseq.dev[dev], name, len(self.conseq.names), self.conseq.meta["aa"],
+                                    self.conseq.alt_order, genome.as_struct(dev), dev, self.n_rep, self.seed,
+                                    **_device_rows(prob, start, strand=strand))
         return genome
 
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, table, n_tx = 0, self.host, len(self.conseq.names)
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine = acc["table"].cpu().numpy().view(np.uint32)[:n_tx * 5 * self.n_rep].reshape(n_tx, 5, self.n_rep)
-            table = mine.copy() if table is None else table + mine
-        return table, status
-
-    def merge(self, states, k):
-        table = None
-        for st in states:
-            if st is not None:
-                table = st.copy() if table is None else table + st
-        return table
-
     def finish(self, state, k, result):
-        self.counts = np.zeros((len(self.conseq.names), 5, self.n_rep), np.uint32) if state is None else state
+        super().finish(state, k, result)
         names, _, table = result["consequences"]
         observed = table[:, 4:11:2] if self.conseq.labels else None
         result[self.name] = (names, self.counts, observed, table[:, 3:11:2])
@@ -2286,72 +2187,50 @@ class _ConsequenceSimulationReducer:
         write_consequence_simulation_outputs(*result[self.name], out_prefix)
 
 
-class _StructureSimulationReducer:
+class _StructureSimulationReducer(_TableReducer):
     """The simulated null of the structure table and of the loss-of-function count (``simulate_txstruct_host`` is the rule): per
     transcript, structure bin and replicate the simulated count -- ONE uint32 table [transcripts][9][n_rep] on the host and one per
     device, behind the structure reducer `struct` (whose item arrays and workspace it uses) and the consequence simulation `conseq_sim`
     (whose stop-gained counts of the same draws complete the LoF count), read back once."""
-    name = "structure_simulation"
+    name, kept = "structure_simulation", "counts"
 
     def __init__(self, n_rep, seed, struct, conseq_sim, table_bytes_max):
         self.n_rep, self.seed, self.struct, self.conseq_sim = int(n_rep), int(seed), struct, conseq_sim
         self.conseq, self.table_bytes_max = struct.conseq, int(table_bytes_max)
-        need = len(self.conseq.names) * TX_BINS * self.n_rep * 4
-        if need > self.table_bytes_max:
-            raise ValueError(f"simulate: the table of {len(self.conseq.names)} transcripts x {TX_BINS} structure bins x {self.n_rep} "
-                             f"replicates takes {need} bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        _check_simulation(self.n_rep, self.seed, self.table_bytes_max, len(self.conseq.names) * TX_BINS,
+                          f"{len(self.conseq.names)} transcripts x {TX_BINS} structure bins")
         self.reset()
 
+    def _tables(self, k):
+        return (("table", (len(self.conseq.names), TX_BINS, self.n_rep), np.uint32, None),)
+
     def reset(self):
-        self.host = None               # table uint32 [transcripts][9][n_rep] of the host shards
-        self.dev = {}                  # device -> dict(table, status)
-        self.counts = self.lof = None
+        super().reset()
+        self.lof = None
 
     def host_part(self, name, prob, start, end, strand, label, k):
         self.conseq._check(k)
         features = self.struct.features.get(name)
         if features is None:
             return 0
-        n_tx = len(self.conseq.names)
-        if self.host is None:
-            self.host = np.zeros((n_tx, TX_BINS, self.n_rep), np.uint32)
-        return simulate_txstruct_host(self.conseq.genome(name), prob, start, strand, self.conseq.segments.get(name), features, n_tx,
-                                      simulate_chrom_key(name), self.seed, self.n_rep, self.conseq.meta["aa"], self.conseq.alt_order,
-                                      into=self.host)[1]
+        return simulate_txstruct_host(self.conseq.genome(name), prob, start, strand, self.conseq.segments.get(name), features,
+                                      len(self.conseq.names), simulate_chrom_key(name), self.seed, self.n_rep, self.conseq.meta["aa"],
+                                      self.conseq.alt_order, into=self._host(k))[1]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the draws of a part behind its structure reduction, into the device's one table."""
         self.conseq._check(k)
         if self.struct.features.get(name) is None or start.shape[0] == 0:
             return None
-        dev, n_tx = prob.device, len(self.conseq.names)
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(max(n_tx * TX_BINS * self.n_rep, 1), dtype=torch.int32, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev))
-        genome = self.conseq.genome(name)
-        items = self.struct.dev[dev]
-        simulate_txstruct_rows_device(acc["table"], acc["status"], items, self.conseq.dev.get(dev, items["no_cds"]), name, n_tx,
-                                      self.conseq.meta["aa"], self.conseq.alt_order, genome.as_struct(dev), dev, self.n_rep, self.seed,
-                                      prob=prob.data_ptr(), prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0),
-                                      start=start.data_ptr(), strand=strand.data_ptr(), n=start.shape[0])
+        dev, genome = prob.device, self.conseq.genome(name)
+        acc, items = self._acc(dev, k), self.struct.dev[dev]
+        simulate_txstruct_rows_device(acc["table"], acc["status"], items, self.conseq.dev.get(dev, items["no_cds"]), name,
+                                      len(self.conseq.names), self.conseq.meta["aa"], self.conseq.alt_order, genome.as_struct(dev), dev,
+                                      self.n_rep, self.seed, **_device_rows(prob, start, strand=strand))
         return genome
 
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, table, n_tx = 0, self.host, len(self.conseq.names)
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine = acc["table"].cpu().numpy().view(np.uint32)[:n_tx * TX_BINS * self.n_rep].reshape(n_tx, TX_BINS, self.n_rep)
-            table = mine if table is None else table + mine      # (the copy the device gave is this call's own)
-        return table, status
-
-    def merge(self, states, k):
-        return self.conseq_sim.merge(states, k)
-
     def finish(self, state, k, result):
-        n_tx = len(self.conseq.names)
-        self.counts = np.zeros((n_tx, TX_BINS, self.n_rep), np.uint32) if state is None else state
+        super().finish(state, k, result)
         self.lof = simulate_lof_counts(self.conseq_sim.counts, self.counts)
         names, table, _ = result["transcript_structure"]
         expected, observed = structure_cells_from_sums(table, self.conseq.sums[0][:, 2])
@@ -2362,29 +2241,26 @@ class _StructureSimulationReducer:
         write_structure_simulation_outputs(*result[self.name], out_prefix)
 
 
-class _IndelStructureSimulationReducer:
+class _IndelStructureSimulationReducer(_TableReducer):
     """The simulated null of the INDEL structure table and of its loss-of-function counts (``simulate_txindel_host`` is the rule): per
     transcript, INDEL structure bin and replicate the simulated count -- ONE uint32 table [transcripts][10][n_rep] on the host and one
     per device, behind the INDEL structure reducer `struct`, whose item, link and segment arrays and workspace it uses, read back once.
     A cell takes one count per row that its transcript counts: the run keeps those below 2^32, as the structure simulation does."""
-    name = "indel_structure_simulation"
+    name, kept = "indel_structure_simulation", "counts"
 
     def __init__(self, n_rep, seed, struct, table_bytes_max):
         self.n_rep, self.seed, self.struct, self.table_bytes_max = int(n_rep), int(seed), struct, int(table_bytes_max)
-        if not 1 <= self.n_rep <= SIMULATE_MAX_REPLICATES:
-            raise ValueError("simulate: 1 .. 2^20 replicates")
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError("simulate: the seed is an unsigned 64-bit integer")
-        need = len(struct.names) * TXINDEL_BINS * self.n_rep * 4
-        if need > self.table_bytes_max:
-            raise ValueError(f"simulate: the table of {len(struct.names)} transcripts x {TXINDEL_BINS} INDEL structure bins x {self.n_rep} "
-                             f"replicates takes {need} bytes, above simulate_table_bytes_max = {self.table_bytes_max}")
+        _check_simulation(self.n_rep, self.seed, self.table_bytes_max, len(struct.names) * TXINDEL_BINS,
+                          f"{len(struct.names)} transcripts x {TXINDEL_BINS} INDEL structure bins",
+                          seed_text="simulate: the seed is an unsigned 64-bit integer")
         self.reset()
 
+    def _tables(self, k):
+        return (("table", (len(self.struct.names), TXINDEL_BINS, self.n_rep), np.uint32, None),)
+
     def reset(self):
-        self.host = None               # table uint32 [transcripts][10][n_rep] of the host shards
-        self.dev = {}                  # device -> dict(table, status)
-        self.counts = self.lof = self.lof_upper = None
+        super().reset()
+        self.lof = self.lof_upper = None
 
     def _part(self, name, k):
         if not 2 <= k <= 8:
@@ -2396,48 +2272,23 @@ class _IndelStructureSimulationReducer:
         part = self._part(name, k)
         if part is None:
             return 0
-        n_tx = len(self.struct.names)
-        if self.host is None:
-            self.host = np.zeros((n_tx, TXINDEL_BINS, self.n_rep), np.uint32)
-        return simulate_txindel_host(prob, start, strand, k, self.struct.segments.get(name), part[0], n_tx, self.struct.kind,
+        return simulate_txindel_host(prob, start, strand, k, self.struct.segments.get(name), part[0], len(self.struct.names), self.struct.kind,
                                      simulate_chrom_key(name), self.seed, self.n_rep, self.struct.offset, self.struct.class_len, part[2],
-                                     links=part[1], into=self.host)[1]
+                                     links=part[1], into=self._host(k))[1]
 
     def device_part(self, name, prob, start, end, strand, label, k):
         """Enqueue the draws of a part behind its INDEL structure reduction, into the device's one table."""
         part = self._part(name, k)
         if part is None or start.shape[0] == 0:
             return None
-        dev, n_tx = prob.device, len(self.struct.names)
-        acc = self.dev.get(dev)
-        if acc is None:
-            acc = self.dev[dev] = dict(table=torch.zeros(max(n_tx * TXINDEL_BINS * self.n_rep, 1), dtype=torch.int32, device=dev),
-                                       status=torch.zeros(1, dtype=torch.int32, device=dev))
-        simulate_txindel_rows_device(acc["table"], acc["status"], self.struct.dev[dev], name, n_tx, self.struct.kind, self.struct.offset,
-                                     self.struct.class_len, part[2], dev, self.n_rep, self.seed, prob=prob.data_ptr(),
-                                     prob_f64=prob.dtype == torch.float64, prob_stride=prob.stride(0), start=start.data_ptr(),
-                                     strand=None if strand is None else strand.data_ptr(), n=start.shape[0], n_class=k)
+        dev, acc = prob.device, self._acc(prob.device, k)
+        simulate_txindel_rows_device(acc["table"], acc["status"], self.struct.dev[dev], name, len(self.struct.names), self.struct.kind,
+                                     self.struct.offset, self.struct.class_len, part[2], dev, self.n_rep, self.seed, n_class=k,
+                                     **_device_rows(prob, start, strand=strand))
         return None
 
-    def read_back(self, k):
-        """The one read-back of the device tables, added to the host rows'."""
-        status, table, n_tx = 0, self.host, len(self.struct.names)
-        for acc in self.dev.values():
-            status |= int(acc["status"].item())
-            mine = acc["table"].cpu().numpy().view(np.uint32)[:n_tx * TXINDEL_BINS * self.n_rep].reshape(n_tx, TXINDEL_BINS, self.n_rep)
-            table = mine if table is None else table + mine      # (the copy the device gave is this call's own)
-        return table, status
-
-    def merge(self, states, k):
-        table = None
-        for st in states:
-            if st is not None:
-                table = st.copy() if table is None else table + st
-        return table
-
     def finish(self, state, k, result):
-        n_tx = len(self.struct.names)
-        self.counts = np.zeros((n_tx, TXINDEL_BINS, self.n_rep), np.uint32) if state is None else state
+        super().finish(state, k, result)
         self.lof, self.lof_upper = simulate_indel_lof_counts(self.counts)
         names, table, _ = result["indel_structure"]
         expected, observed = indel_structure_cells_from_sums(table)

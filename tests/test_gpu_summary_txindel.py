@@ -138,6 +138,31 @@ def test_past_the_chunk_length_the_grid_and_the_scan_threads(kind):
     assert int(want[1][-1, 0]) > 2 * chunk and int(want[1][:-1, 0].sum()) > (5 * per_tx - 4) * (len(names) - 2)
 
 
+@pytest.mark.parametrize("off", [0, 1])
+@pytest.mark.parametrize("kind", [0, 1, 2])
+def test_a_row_on_the_boundary_of_two_adjacent_items_goes_to_the_second(kind, off):
+    """The plan's ranges under the home-base shift (row_chunks.h): two transcripts whose items abut, a row at every start and equal
+    starts on the boundaries, so that for every pair of adjacent items [.., B) and [B, ..) there are rows with start + shift == B -- b1
+    of the first, b0 of the second -- whatever the shift of (kind, offset)."""
+    from mural_amd import tables
+    lines = [D.bed12("chr1", "coding", "+", [(20, 60), (80, 130), (150, 170)], (30, 160)), D.bed12("chr1", "plain", "-", [(40, 90), (110, 180)])]
+    names, meta, segments, features = tables.read_transcript_structure(io.StringIO("\n".join(lines) + "\n"))
+    segments, features = segments["chr1"], features["chr1"]
+    shift = off - (0 if kind == 1 else 1)
+    b0, b1, tx = (np.asarray(features[key]) for key in ("feat_b0", "feat_b1", "feat_tx"))
+    shared = sorted({int(b) for b, t in zip(b1, tx) if ((b0 == b) & (tx == t)).any()})      # b1 of an item = b0 of the same transcript's next
+    assert len(shared) >= 6 and 30 in shared and 60 in shared and 90 in shared
+    start = np.sort(np.concatenate([np.arange(5, 195), np.repeat(np.asarray(shared) - shift, 2)])).astype(np.int64)
+    assert len(start) <= 220 and all((start + shift == b).sum() == 3 for b in shared)
+    rng = np.random.default_rng(10 * kind + off)
+    prob = rng.dirichlet(np.ones(8), size=len(start)).astype(np.float32)
+    label = rng.integers(0, 8, size=len(start)).astype(np.int32)
+    acc, status = _kernel(prob, start, label, 8, segments, features, len(names), kind, off)
+    want = _twin(prob, start, label, 8, segments, features, len(names), kind, off)
+    assert status == 0 == want[2] and _same(acc, want, len(names))
+    assert int(want[1][0, 0]) > 150 and int(want[1][1, 0]) > 120      # both transcripts count the rows of their spans
+
+
 # ---- 3. status, and calls that launch nothing -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("what,bit", [("start", 1), ("label", 2), ("nan", 8), ("above", 8)])
 def test_bad_rows_are_skipped_and_set_status(record, what, bit):
