@@ -13,14 +13,14 @@
 // mural_simulate_annot_rows, per call:
 //   * check kernel, a thread per row: the status bits (a bad probability, a negative start, a start below the row before it);
 //   * the plan (row_chunks.h: plan_row_chunks): the pieces' rows cut into chunks of at most SIM_CHUNK_ROWS rows;
-//   * draw kernel, a fixed grid of SIM_GRID_WAVES waves striding over the units (chunk, block of 64 replicates): the wave finds the
-//     chunk's piece, walks the chunk 64 rows at a time (a row per lane, four replicates per Philox call), counts the hits of a (class,
-//     replicate) over the 64 rows by ballot + popcount and keeps the count of replicate r0 + l in lane l; after the chunk ONE
-//     wave-instruction per class adds the 64 counts -- 256 contiguous bytes -- with 32-bit INTEGER atomics.
+//   * draw kernel: simulate_draw.h's draw_count_units() (the units, the walk of a chunk, the counts and their atomics) around this
+//     file's policy: items = the pieces, owners = their groups, a unit = a chunk and ONE block of 64 replicates; every row has the same
+//     word, whose field c holds c, so that the bin is the drawn class minus one; an accumulator per class,
+//     table[(g * (n_class - 1) + c - 1) * n_rep + r].
 // mural_simulate_rows: tile counts of the non-zero labels of one replicate (a wave per 64 rows), their exclusive scan, and a second pass
 // that recomputes the labels and writes each hit at prefix + its rank among the tile's hits: stable in row order.
-// No floating-point atomics, no synchronisation, no read-back.  The check kernel, the Philox round, a row's cum and the last counter
-// word live in simulate_draw.h, with the loop bounds; the per-transcript simulations include it as well.
+// No floating-point atomics, no synchronisation, no read-back.  The check kernel, the Philox round, a row's cum, the last counter word
+// and the draw-and-count loop live in simulate_draw.h, with the loop bounds; the per-transcript simulations include it as well.
 #include "common.h"
 #include "kmer_key.h"
 #include "row_chunks.h"
@@ -29,62 +29,29 @@
 namespace mural {
 namespace {
 
-template <typename T>
-__global__ __launch_bounds__(SIM_THREADS) void simulate_draw_kernel(SimRows A, const int32_t* __restrict__ group, int64_t n_pieces,
-                                                                    const int64_t* __restrict__ row0, const int64_t* __restrict__ row1,
-                                                                    const int64_t* __restrict__ pre, int32_t n_rep, int64_t n_waves,
-                                                                    uint32_t* __restrict__ table) {
-  const int lane = threadIdx.x & 63, nc = A.n_class;
-  const int64_t wave = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
-  const int64_t n_rb = (n_rep + 63) / 64;
-  const int64_t units = pre[n_pieces] * n_rb;
-  for (int64_t unit = wave; unit < units; unit += n_waves) {
-    const int64_t t = unit / n_rb;
-    const int rb = (int)(unit % n_rb);
-    const int64_t p = row_chunk_item(pre, n_pieces, t);
-    const int64_t r0 = row0[p] + (t - pre[p]) * SIM_CHUNK_ROWS;
-    const int64_t r1 = min(r0 + SIM_CHUNK_ROWS, row1[p]);
-    const int reps_here = min(64, n_rep - rb * 64);
-    const int n_blocks = (reps_here + 3) / 4;
-    uint32_t acc[SIM_MAX_CLASS - 1];
-#pragma unroll
-    for (int c = 0; c < SIM_MAX_CLASS - 1; ++c) acc[c] = 0;
-    for (int64_t row = r0; row < r1; row += 64) {
-      const int64_t i = row + lane;
-      u64 cum[SIM_MAX_CLASS - 1];
-#pragma unroll
-      for (int c = 0; c < SIM_MAX_CLASS - 1; ++c) cum[c] = 0;
-      uint32_t s_lo = 0, s_hi = 0, last = 0;
-      if (i < r1) {
-        row_cum<T>(A, i, cum);      // (the status is the check kernel's)
-        const u64 s = (u64)A.start[i];
-        s_lo = (uint32_t)s, s_hi = (uint32_t)(s >> 32);
-        last = last_counter_word(A, i, 0);
-      }
-      for (int j = 0; j < n_blocks; ++j) {
-        uint32_t u[4];
-        philox4x32_10(s_lo, s_hi, A.chrom_key, last | (uint32_t)(rb * 16 + j), A.seed_lo, A.seed_hi, u);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          uint32_t below = 0;      // rows of the tile whose label is in 1 .. c - 1
-#pragma unroll
-          for (int c = 1; c < SIM_MAX_CLASS; ++c) {
-            if (c < nc) {      // (wave-uniform)
-              const uint32_t upto = (uint32_t)__popcll(__ballot((u64)u[k] < cum[c - 1]));      // cum ascends: labels 1 .. c
-              if (lane == j * 4 + k) acc[c - 1] += upto - below;
-              below = upto;
-            }
-          }
-        }
-      }
-    }
-    const int32_t g = group[p];
-    if (lane < reps_here) {
-#pragma unroll
-      for (int c = 1; c < SIM_MAX_CLASS; ++c)
-        if (c < nc && acc[c - 1]) atomicAdd(&table[((int64_t)g * (nc - 1) + (c - 1)) * n_rep + rb * 64 + lane], acc[c - 1]);
-    }
+struct AnnotDraw {
+  using Word = uint32_t;
+  static constexpr int BITS = 4, BOUNDS = SIM_MAX_CLASS - 1, ACCS = SIM_MAX_CLASS - 1, UNIT_BLOCKS = 1;      // (no row words to amortise)
+  static constexpr bool ROW_WORDS = false;
+  static constexpr Word WORD = 0x76543210u;      // field c: c -- the field beside the last class is a bin that is not present
+  const int32_t* group;
+  int n_class;
+  int32_t g;
+
+  __device__ __forceinline__ bool begin_unit(int64_t p) {
+    g = group[p];
+    return true;
   }
+  __device__ __forceinline__ uint32_t present() const { return (1u << (n_class - 1)) - 1; }
+  __device__ __forceinline__ int cell(int b) const { return b; }
+  __device__ __forceinline__ int32_t owner() const { return g; }
+  __device__ __forceinline__ int bins() const { return n_class - 1; }
+};
+
+template <typename T>
+__global__ __launch_bounds__(SIM_THREADS) void simulate_draw_kernel(SimDraw D, const int32_t* group) {
+  AnnotDraw pol{group, D.rows.n_class};
+  draw_count_units<T>(D, pol, nullptr);
 }
 
 // the label of row i in replicate `rep`
@@ -160,7 +127,6 @@ extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* 
   MURAL_REQUIRE(s->prob_stride >= s->n_class, "simulate_annot_rows: prob_stride < n_class");
   const SimRows A = sim_rows(s->prob, s->prob_stride, s->start, s->strand, s->n_class, s->chrom_key, s->seed, s->status);
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 block(SIM_THREADS);
   if (s->n_pieces > 0) {      // (everything is checked before the first launch)
     MURAL_REQUIRE(s->piece_b0 && s->piece_b1 && s->piece_group && s->n_groups >= 1 && s->table,
                   "simulate_annot_rows: pieces without groups or table");
@@ -170,21 +136,10 @@ extern "C" int mural_simulate_annot_rows(const MuralSimulateAnnotRows* s, void* 
   }
   if (const int rc = launch_simulate_check(st, A, s->n, s->prob_f64, 1)) return rc;
   if (s->n_pieces == 0) return MURAL_OK;
-  WsArena ws(ws_ptr);
-  RowChunks w;
-  if (const int rc = plan_row_chunks<SIM_THREADS, SIM_SCAN_THREADS>(st, s->start, s->n, s->piece_b0, s->piece_b1, s->piece_group, s->n_groups,
-                                                                    s->n_pieces, 0, SIM_CHUNK_ROWS, ws, w))
-    return rc;
-  const int64_t n_waves = row_chunk_grid_waves(s->n, SIM_CHUNK_ROWS, (s->n_rep + 63) / 64, s->n_pieces, SIM_GRID_WAVES, SIM_WAVES);
-  const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES));
-  if (s->prob_f64)
-    hipLaunchKernelGGL(simulate_draw_kernel<double>, draw_grid, block, 0, st, A, s->piece_group, s->n_pieces, w.row0, w.row1, w.pre, s->n_rep,
-                       n_waves, s->table);
-  else
-    hipLaunchKernelGGL(simulate_draw_kernel<float>, draw_grid, block, 0, st, A, s->piece_group, s->n_pieces, w.row0, w.row1, w.pre, s->n_rep,
-                       n_waves, s->table);
-  MURAL_HIP_CHECK(hipGetLastError());
-  return MURAL_OK;
+  SimDraw D{};
+  D.rows = A, D.n_items = s->n_pieces, D.n_rep = s->n_rep, D.table = s->table;
+  return launch_draw_count(st, D, s->prob_f64, s->n, s->piece_b0, s->piece_b1, s->piece_group, s->n_groups, 0, AnnotDraw::UNIT_BLOCKS, ws_ptr,
+                           simulate_draw_kernel<float>, simulate_draw_kernel<double>, s->piece_group);
 }
 
 extern "C" size_t mural_simulate_rows_workspace_bytes(int64_t n) {

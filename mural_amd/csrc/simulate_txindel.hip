@@ -10,7 +10,7 @@
 //   * check kernel (simulate_draw.h), a thread per row: the simulation's status bits;
 //   * the plan (row_chunks.h: plan_row_chunks with a shift): the rows of an item are those whose HOME BASE lies in it, cut into chunks
 //     of at most SIM_CHUNK_ROWS rows;
-//   * draw kernel, a grid of at most SIM_GRID_WAVES waves striding over the units (chunk of a home item, group of up to STI_UNIT_BLOCKS
+//   * draw kernel, a grid of at most SIM_GRID_WAVES waves striding over the units (chunk of a home item, group of up to SIM_UNIT_BLOCKS
 //     blocks of 64 replicates).  The home item and an insertion's second item are wave-uniform and loaded once per unit.  A wave first
 //     walks its chunk 64 rows at a time, a row per lane, and forms the bin of every class of the row ONCE through txindel_bins.h -- a
 //     deletion's walk is paid here, not per replicate --: 4 bits a class in one 32-bit word, 15 for "not counted", the word kept in LDS
@@ -31,13 +31,6 @@
 namespace mural {
 namespace {
 
-#ifndef STI_UNIT_BLOCKS
-#define STI_UNIT_BLOCKS 16
-#endif
-constexpr int STI_TILES = (int)(SIM_CHUNK_ROWS / 64);      // tiles of a chunk
-constexpr int64_t STI_MAX_ROWS = 1ll << 31;                // per call, as mural_summary_txindel_rows
-constexpr int64_t STI_MAX_FEATURES = 1ll << 22;
-constexpr int64_t STI_MAX_SEGMENTS = 1ll << 22;
 constexpr uint32_t STI_NOWHERE = 15;                       // the 4 bits of a class that is not counted
 constexpr uint32_t STI_DEAD = 0xFFFFFFFFu;                 // the word of a lane without a counted row
 
@@ -69,17 +62,17 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txindel_draw_kernel(SimT
                                                                             const int64_t* __restrict__ row1,
                                                                             const int64_t* __restrict__ pre, int64_t n_waves) {
   __shared__ uint32_t cls_words[SIM_MAX_CLASS];
-  __shared__ uint32_t bin_words[SIM_WAVES][STI_TILES][64];
+  __shared__ uint32_t bin_words[SIM_WAVES][SIM_TILES][64];
 #pragma unroll
   for (int j = 0; j < SIM_MAX_CLASS; ++j)      // (constant indices: the words stay scalar arguments)
     if (threadIdx.x == j) cls_words[j] = A.cls[j];
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  uint32_t (&mine)[STI_TILES][64] = bin_words[threadIdx.x >> 6];      // (a lane reads only what it wrote itself: no barrier)
+  uint32_t (&mine)[SIM_TILES][64] = bin_words[threadIdx.x >> 6];      // (a lane reads only what it wrote itself: no barrier)
   const int64_t wave = (int64_t)blockIdx.x * SIM_WAVES + (threadIdx.x >> 6);
   const int n_rep = A.n_rep, nc = A.rows.n_class;
   const int n_rb = (n_rep + 63) / 64;
-  const int64_t n_rg = (n_rb + STI_UNIT_BLOCKS - 1) / STI_UNIT_BLOCKS;
+  const int64_t n_rg = (n_rb + SIM_UNIT_BLOCKS - 1) / SIM_UNIT_BLOCKS;
   const int64_t units = pre[A.n_feat] * n_rg;
   const int64_t home_shift = A.off - (A.kind == TI_DELETION_START ? 0 : 1);
   for (int64_t unit = wave; unit < units; unit += n_waves) {
@@ -101,7 +94,7 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txindel_draw_kernel(SimT
     // the bins of the rows' classes, once per unit
     uint32_t seen = 0;      // bit b: a class of one of this lane's rows falls in bin b
     int tile = 0;
-    for (int64_t row = r0; row < r1; row += 64, ++tile) {      // (at most STI_TILES tiles: r1 - r0 <= SIM_CHUNK_ROWS)
+    for (int64_t row = r0; row < r1; row += 64, ++tile) {      // (at most SIM_TILES tiles: r1 - r0 <= SIM_CHUNK_ROWS)
       const int64_t i = row + lane;
       uint32_t word = STI_DEAD;
       if (i < r1) {
@@ -126,8 +119,8 @@ __global__ __launch_bounds__(SIM_THREADS) void simulate_txindel_draw_kernel(SimT
     for (int b = 0; b < TI_BINS; ++b)
       if (__ballot((seen >> b) & 1u)) present |= 1u << b;
     if (!present) continue;
-    const int rb_end = min(n_rb, (rg + 1) * STI_UNIT_BLOCKS);
-    for (int rb = rg * STI_UNIT_BLOCKS; rb < rb_end; ++rb) {
+    const int rb_end = min(n_rb, (rg + 1) * SIM_UNIT_BLOCKS);
+    for (int rb = rg * SIM_UNIT_BLOCKS; rb < rb_end; ++rb) {
       const int reps_here = min(64, n_rep - rb * 64);
       const int n_blocks = (reps_here + 3) / 4;
       uint32_t acc[TI_BINS];
@@ -195,11 +188,7 @@ extern "C" int mural_simulate_txindel_rows(const MuralSimulateTxindelRows* s, vo
   MURAL_REQUIRE(s, "simulate_txindel_rows: NULL argument");
   MURAL_REQUIRE(s->n_class >= 2 && s->n_class <= SIM_MAX_CLASS,
                 "simulate_txindel_rows: 2 <= n_class <= 8 required, the bound of the simulation's draw (n_class = %d)", s->n_class);
-  MURAL_REQUIRE(s->n_rep >= 1 && s->n_rep <= SIM_MAX_REP, "simulate_txindel_rows: 1 <= n_rep <= 2^20 required");
-  MURAL_REQUIRE(s->n >= 0 && s->n <= STI_MAX_ROWS, "simulate_txindel_rows: 0 <= n <= 2^31 required");
-  MURAL_REQUIRE(s->n_features >= 0 && s->n_features <= STI_MAX_FEATURES, "simulate_txindel_rows: 0 <= n_features <= 2^22 required");
-  MURAL_REQUIRE(s->n_segments >= 0 && s->n_segments <= STI_MAX_SEGMENTS, "simulate_txindel_rows: 0 <= n_segments <= 2^22 required");
-  MURAL_REQUIRE(s->n_transcripts >= 0, "simulate_txindel_rows: n_transcripts < 0");
+  if (const int rc = check_sim_tx_bounds("simulate_txindel_rows", s->n_rep, s->n, s->n_features, s->n_segments, s->n_transcripts)) return rc;
   MURAL_REQUIRE(s->kind >= 0 && s->kind <= 2, "simulate_txindel_rows: kind is 0 (insertion), 1 (deletion start) or 2 (deletion end)");
   MURAL_REQUIRE(s->breakpoint_offset == 0 || s->breakpoint_offset == 1, "simulate_txindel_rows: breakpoint_offset is 0 or 1");
   for (int c = 1; c < s->n_class; ++c)
@@ -236,7 +225,7 @@ extern "C" int mural_simulate_txindel_rows(const MuralSimulateTxindelRows* s, vo
   if (const int rc = plan_row_chunks<SIM_THREADS, SIM_SCAN_THREADS>(st, s->start, s->n, A.feat_b0, A.feat_b1, A.feat_tx, A.n_tx, A.n_feat,
                                                                     home_shift, SIM_CHUNK_ROWS, ws, w))
     return rc;
-  const int64_t n_rg = ((s->n_rep + 63) / 64 + STI_UNIT_BLOCKS - 1) / STI_UNIT_BLOCKS;
+  const int64_t n_rg = ((s->n_rep + 63) / 64 + SIM_UNIT_BLOCKS - 1) / SIM_UNIT_BLOCKS;
   const int64_t n_waves = row_chunk_grid_waves(s->n, SIM_CHUNK_ROWS, n_rg, s->n_features, SIM_GRID_WAVES, SIM_WAVES);
   const dim3 draw_grid((unsigned)(n_waves / SIM_WAVES)), block(SIM_THREADS);
   if (s->prob_f64)

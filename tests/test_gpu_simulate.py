@@ -157,6 +157,20 @@ def test_table_equals_the_twin(which, n_class, dtype, pad, strand_kind, n_rep):
     assert empty and not want[empty].any()
 
 
+@pytest.mark.parametrize("n_class", [2, 8])
+def test_table_equals_the_twin_with_the_fewest_and_the_most_classes_over_two_replicate_blocks(n_class):
+    """The field beside the last class's is no bin: a draw of class 0 and a lane without a row count nowhere, at 2 classes (one bound, six
+    that do not exist) and at 8 (seven bounds, the last field of the word), in a full block of replicates and a block of one."""
+    n, n_rep = 300, 65
+    prob, start, strand = _rows(n, n_class, np.float32, seed=40 + n_class)
+    ends = [0, int(start[0]), int(start[70]), int(start[200]) + 1, int(start[-1]) + 9]
+    pieces, n_groups = _all_pairs(ends)
+    got, status = _annot(prob, start, strand, n_class, pieces, n_groups, n_rep)
+    want, want_status = _twin(prob, start, strand, n_class, pieces, n_groups, n_rep)
+    assert status == 0 == want_status and want[..., 64].sum() > 0 and want.sum() < n * n_rep * n_groups      # (class 0 is drawn as well)
+    assert got.cpu().numpy().tobytes() == want.astype(np.uint32).tobytes()
+
+
 def test_300_nested_pieces_on_500_rows():
     prob, start, strand = _rows(500, 4, np.float32, seed=30)
     lo, hi = int(start[0]), int(start[-1]) + 1
